@@ -159,8 +159,9 @@ def preheat(step, dev, cap_s=2.0, tol=0.02):
 
 
 def timed_steps(step, steps, sync_all, dev):
-    """EXACTLY `steps` calls between two (barrier + synchronize) brackets -> wall seconds; one event per step boundary on
-    the launch stream gives the per-step distribution without serialising anything."""
+    """EXACTLY `steps` calls between two (barrier + synchronize) brackets -> (wall seconds, per-step distribution, what the
+    last timed call returned); one event per step boundary on the launch stream gives the distribution without serialising
+    anything."""
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     # untimed steps bracketed by events first: on a cold box the first event-recorded step of a process sometimes takes
     # ~50 ms of host time (seen as `slowest_step: 0` before this line existed) — first-use costs belong to the warm-up
@@ -173,7 +174,7 @@ def timed_steps(step, steps, sync_all, dev):
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(steps):
-        step()
+        last = step()
         ev[i + 1].record()
     sync_all()
     dt = time.perf_counter() - t0
@@ -182,7 +183,25 @@ def timed_steps(step, steps, sync_all, dev):
     out = {"p50": per[len(per) // 2], "min": per[0], "max": per[-1]}
     if per[-1] > 1.5 * per[len(per) // 2]:                 # an outlier step: say which one (a one-off stall shows, it is not hidden)
         out["slowest_step"] = raw.index(per[-1])
-    return dt, out
+    return dt, out, last
+
+
+def dump_outputs(path, arrays, rank, world, dist, dev, backend):
+    """--dump-outputs: the [pairs, 3] float32 results of the last timed step as `path`/<name>.npy (12 bytes per pair), every
+    rank's pairs in rank order.  Inputs and weights depend only on the seeds, so two builds can be compared file for file."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().to(torch.float32).contiguous()
+        if world > 1:
+            cdev = dev if backend == "nccl" else torch.device("cpu")
+            parts = [torch.empty_like(t, device=cdev) for _ in range(world)]
+            dist.all_gather(parts, t.to(cdev))
+            t = torch.cat(parts)
+        host[name] = t.cpu().numpy()
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for name, a in host.items():
+            np.save(os.path.join(path, name + ".npy"), a)
 
 
 def multi_gpu_report(model, out_local, dt_local, steps, B, rank, world, dist, dev, backend):
@@ -396,7 +415,13 @@ def main():
                     help="N > 1: seconds the side measurements (dual_bf16, train with its all-reduce, ...) may take before every rank gives up "
                          "on them and rank 0 prints the headline-only line")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (fwd_fp32: pose_delta; "
+                         "dual_bf16: pose_delta_a, pose_delta_b)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == "train":
+        # a training step's outputs depend on the weights, which every earlier step (the pre-heat's varying count included) updated
+        ap.error("--dump-outputs: --config train has no run-independent outputs (each step updates the weights)")
 
     if args.gpus > 1 and not args.dry_run and not args.shared_gpu and args.backend == "nccl":
         have = torch.cuda.device_count()
@@ -460,7 +485,9 @@ def main():
         pre = (0.0, 0, None) if args.no_preheat else preheat(step, dev)
         for _ in range(args.warmup):
             step()
-        dt, per_step = timed_steps(step, args.steps, sync_all, dev)      # ---- the timed region
+        dt, per_step, last = timed_steps(step, args.steps, sync_all, dev)      # ---- the timed region
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"pose_delta": last}, rank, world, dist, dev, args.backend)
         # ---- the same K steps once more with a HIP-event pair around every launch (on the launch stream): per-kernel
         #      durations for `roofline` / `kernels`.  Not part of `value`: event pairs serialise the launches.
         model.timing(True)
@@ -595,7 +622,7 @@ def main():
         import copy
         from tools import bench_configs
         sa = copy.copy(args)
-        sa.steps, sa.warmup, sa.batch = 10, 2, None
+        sa.steps, sa.warmup, sa.batch, sa.dump_outputs = 10, 2, None, None
         secondary = {}
         for name, fn in (("dual_bf16", bench_configs.run_dual_bf16), ("train", bench_configs.run_train)):
             try:

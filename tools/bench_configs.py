@@ -88,7 +88,10 @@ def run_dual_bf16(args, rank, world, dist, dev, sync_all, obs=None, emit=True):
         pre = (0.0, 0, None) if args.no_preheat else bench.preheat(step, dev)
         for _ in range(args.warmup):
             step()
-        dt, per_step = bench.timed_steps(step, args.steps, sync_all, dev)
+        dt, per_step, (last_a, last_b) = bench.timed_steps(step, args.steps, sync_all, dev)
+        if args.dump_outputs:
+            bench.dump_outputs(args.dump_outputs, {"pose_delta_a": last_a, "pose_delta_b": last_b}, rank, world, dist, dev,
+                               args.backend)
         ma.timing(True)
         for _ in range(args.steps):
             step()
@@ -193,7 +196,7 @@ def run_train(args, rank, world, dist, dev, sync_all, obs=None, emit=True):
     pre = (0.0, 0, None) if args.no_preheat else bench.preheat(step, dev)
     for _ in range(args.warmup):
         step()
-    dt, per_step = bench.timed_steps(step, args.steps, sync_all, dev)
+    dt, per_step, _ = bench.timed_steps(step, args.steps, sync_all, dev)
     model.timing(True)
     for _ in range(args.steps):
         step()
@@ -214,7 +217,7 @@ def run_train(args, rank, world, dist, dev, sync_all, obs=None, emit=True):
         ts.bucketed = not ts.bucketed
         for _ in range(2):
             step()
-        dt_other, _ = bench.timed_steps(step, args.steps, sync_all, dev)
+        dt_other, _, _ = bench.timed_steps(step, args.steps, sync_all, dev)
         dt_other = parallel.max_over_ranks(dt_other, dev)
         ts.bucketed = not ts.bucketed
         flat = ts.grad.clone() if backend_is_nccl(args) else ts.grad.detach().cpu()
