@@ -455,6 +455,25 @@ int pnvo_timing_read(pnvo_handle h, pnvo_kernel_time *entries, int cap, int *n_o
 size_t pnvo_packed_conv_floats(int cout, int cin, int kh, int kw);
 int pnvo_pack_conv_weight(const float *oihw, int cout, int cin, int kh, int kw, float *out);
 
+/* ---- Observation transform (VO.OBS_TRANSFORM / RL.OBS_TRANSFORM): resize the shortest edge with area interpolation and center
+ * crop, on the device.  Replaces image_resize_shortest_edge + center_crop (pointnav_vo/utils/misc_utils.py:241-288, :291-318) as
+ * ResizeCenterCropper (:81-121) and Resizer (:330-366) call them.  The caller computes the sizes on the host as the reference
+ * does (pointnav-vo_amd/obs_transforms.py): the resized grid rs_h x rs_w and the crop window out_h x out_w at (crop_y, crop_x)
+ * inside it (crop_y = crop_x = 0 and out = rs for a plain resize).  Only the crop window is computed.
+ *   src: n NHWC frames of `channels` (1..4) channels, src_dtype 0 = uint8 (converted to float exactly), 1 = float32; element
+ *        strides between frames / rows / pixels (channels are adjacent).
+ *   dst: float32; frame f goes to dst + (f / dst_group) * dst_group_stride + (f % dst_group) * dst_member_stride, rows and pixels
+ *        at the given element strides — dst_group = 2 with member stride 3 (rgb) or 1 (depth) writes (prev, cur) frame pairs
+ *        straight into the channel halves of [n/2,H,W,6] / [n/2,H,W,2] observation pairs.
+ *   div_rule: torch's CPU adaptive_avg_pool2d divides by the window in two ways, by the memory format it receives:
+ *        0 = contiguous NCHW input, (sum / kh) / kw;  1 = channels-last input, sum / (kh * kw).  Sums run in float32 in torch's
+ *        order (input row outer, column inner); results are bit-exact to F.interpolate(mode="area") in that format.
+ * No host synchronisation.  Bad sizes, strides or a crop window outside the resized grid return PNVO_ERR_ARG. */
+int pnvo_resize_area(const void *src, int src_dtype, int n, int in_h, int in_w, int channels, int64_t src_frame_stride,
+                     int64_t src_row_stride, int64_t src_pix_stride, int rs_h, int rs_w, int crop_y, int crop_x, int out_h, int out_w,
+                     float *dst, int dst_group, int64_t dst_group_stride, int64_t dst_member_stride, int64_t dst_row_stride,
+                     int64_t dst_pix_stride, int div_rule, void *stream);
+
 const char *pnvo_version(void);
 
 #ifdef __cplusplus

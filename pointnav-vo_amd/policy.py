@@ -1,8 +1,8 @@
 """HIP-backed navigation policy registered under the reference's name ``resnet_rnn_policy``.
 
 Drop-in for PointNavResNetPolicy (/root/reference/pointnav_vo/rl/policies/resnet_policy.py:25-58) in the configuration
-the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only resnet18 encoder, 2-layer LSTM, no
-observation transform, normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-133), same
+the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only resnet18 encoder, 2-layer LSTM, RL.OBS_TRANSFORM
+'none', 'resize' or 'resize_crop', normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-133), same
 ``state_dict`` keys/shapes, same ``act`` / ``get_value`` signatures and return values (policy.py:29-50).  The module tree
 only HOLDS parameters; ``act`` is one call into libpnvo.so (pnvo_policy_act) on the caller's current HIP stream plus the
 categorical sampling / arg-max over the 4 logits, which stays in torch as in the reference (policy.py:38-43).
@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .obs_transforms import DIV_CONTIGUOUS, as_transform, launch_resize, transformed_size
 from .registry import baseline_registry
 
 GOAL_SENSOR = "pointgoal_with_gps_compass"
@@ -116,14 +117,25 @@ class PointNavResNetPolicy(nn.Module):
         super().__init__()
         if rnn_type != "LSTM" or backbone != "resnet18":
             raise NotImplementedError("the HIP policy implements the resnet18 + LSTM configuration of ddppo_pointnav.yaml")
-        if obs_transform is not None or normalize_visual_inputs or list(vis_types) != ["depth"]:
-            raise NotImplementedError("the HIP policy implements the depth-only, untransformed, un-normalised encoder "
-                                      "(RL.Policy.visual_types = ['depth'], RL.OBS_TRANSFORM = 'none')")
+        if normalize_visual_inputs or list(vis_types) != ["depth"]:
+            raise NotImplementedError("the HIP policy implements the depth-only, un-normalised encoder "
+                                      "(RL.Policy.visual_types = ['depth'])")
         if goal_sensor_uuid != GOAL_SENSOR:
             raise NotImplementedError(goal_sensor_uuid)
-        shp = observation_space.spaces["depth"].shape     # (H, W, 1)
-        self._H, self._W = int(shp[0]), int(shp[1])
-        assert int(shp[2]) == 1
+        # RL.OBS_TRANSFORM (ddppo_trainer.py:92-103,131): this package's ResizeCenterCropper / Resizer or the reference's own instances
+        self._obs_transform = as_transform(obs_transform)
+        if self._obs_transform is not None:
+            if self._obs_transform.channels_last:
+                raise NotImplementedError("the policy hands the transform NCHW depth (resnet_policy.py:157-168): channels_last=False")
+            # the encoder runs on the transformed [VIS_H, VIS_W] frame; transform_observation_space writes (W, H, 1) into the depth
+            # space (resnet_policy.py:75-80), which the reference's sizes only use through the product W * H
+            self._obs_transform.transform_observation_space(observation_space)
+            self._W, self._H = (int(v) for v in self._obs_transform._size)
+        else:
+            shp = observation_space.spaces["depth"].shape     # (H, W, 1)
+            self._H, self._W = int(shp[0]), int(shp[1])
+            assert int(shp[2]) == 1
+        self._tgeom = {}
         self.dim_actions = int(action_space.n)
         self._hidden, self._layers, self._baseplanes = int(hidden_size), int(num_recurrent_layers), int(resnet_baseplanes)
         self._spec = policy_state_dict_spec(width=self._W, height=self._H, baseplanes=self._baseplanes,
@@ -207,6 +219,8 @@ class PointNavResNetPolicy(nn.Module):
         self._ensure(dev)
         depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
         B = depth.shape[0]
+        if self._obs_transform is not None:
+            depth = self._transform_depth(depth, dev)
         if tuple(depth.shape[1:]) != (self._H, self._W, 1):
             raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
         goal = observations[GOAL_SENSOR].to(device=dev, dtype=torch.float32).contiguous().reshape(B, 2)
@@ -224,6 +238,23 @@ class PointNavResNetPolicy(nn.Module):
             _lib.check(_lib.lib.pnvo_policy_act(self._handle, p(depth), p(goal), p(pa), p(mk), p(hin), int(B), p(hout),
                                                 p(feats), p(logits), p(value), stream))
         return feats, hout, logits, value
+
+    def _transform_depth(self, depth, dev):
+        """[B,Hs,Ws,1] sensor depth -> [B,VIS_H,VIS_W,1] by the observation transform, before avg_pool2d(2) (resnet_policy.py:157-168).
+        The reference permutes the depth to [B,1,H,W] and calls .contiguous(): torch's contiguous area kernel, (sum / kh) / kw."""
+        B, Hs, Ws = depth.shape[0], depth.shape[1], depth.shape[2]
+        geom = self._tgeom.get((Hs, Ws))
+        if geom is None:
+            geom = transformed_size(Hs, Ws, self._obs_transform.mode, self._obs_transform._size)
+            if tuple(geom[4:]) != (self._H, self._W):
+                raise ValueError(f"RL.OBS_TRANSFORM {self._obs_transform.mode!r} maps the {Hs}x{Ws} depth to {geom[4]}x{geom[5]}, but the "
+                                 f"policy's encoder takes {self._H}x{self._W}")
+            self._tgeom[(Hs, Ws)] = geom
+        out = torch.empty((B, self._H, self._W, 1), device=dev, dtype=torch.float32)
+        if B:
+            launch_resize(depth.data_ptr(), torch.float32, B, Hs, Ws, 1, (Hs * Ws, Ws, 1), geom, out.data_ptr(), 1,
+                          (self._H * self._W, 0, self._W, 1), DIV_CONTIGUOUS, dev)
+        return out
 
     def forward(self, *x):
         raise NotImplementedError                          # as the reference (policy.py:26-27)

@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from .checkpoint import load_vo_checkpoint
 from .common_vars import ACT_IDX2NAME, ACT_NAME2IDX
+from .obs_transforms import DIV_CHANNELS_LAST, DIV_CONTIGUOUS, ResizeCenterCropper, Resizer, launch_resize, transformed_size
 from .registry import baseline_registry
 from . import vo_cnn  # noqa: F401  (registers the models)
 
@@ -131,10 +132,14 @@ class BaseRLTrainerWithVO:
         self.device = device
 
     def _set_up_vo_obs_transformer(self) -> None:
-        if self.config.VO.OBS_TRANSFORM in ("resize_crop", "resize"):
-            raise NotImplementedError("VO.OBS_TRANSFORM other than 'none' is nav-loop plumbing outside the hot path "
-                                      "(default is 'none', configs/rl/ddppo_pointnav.yaml:99)")
-        self._vo_obs_transformer = None
+        # base_trainer_with_vo.py:24-35: the device mirrors of ResizeCenterCropper / Resizer (obs_transforms.py)
+        size = (self.config.VO.VIS_SIZE_W, self.config.VO.VIS_SIZE_H)
+        if self.config.VO.OBS_TRANSFORM == "resize_crop":
+            self._vo_obs_transformer = ResizeCenterCropper(size=size)
+        elif self.config.VO.OBS_TRANSFORM == "resize":
+            self._vo_obs_transformer = Resizer(size=size)
+        else:
+            self._vo_obs_transformer = None
 
     def _setup_vo_model(self, all_cfg) -> None:
         # base_trainer_with_vo.py:37-133
@@ -458,6 +463,8 @@ class BaseRLTrainerWithVO:
         tensors are built), one forward per action model (sep_act) over all of its pairs.  Mode 'rnd' (train-mode forwards with
         dropout, :295-308) builds the observation pairs (pnvo_build_obs_pairs).  One host synchronisation at the end."""
         assert len(prev_obs_list) == len(cur_obs_list) == len(acts)
+        if getattr(self, "_vo_obs_transformer", None) is not None:
+            return self._compute_transformed_batch(prev_obs_list, cur_obs_list, acts)
         n = len(acts)
         H, W = prev_obs_list[0]["depth"].shape[:2]
         rm = self.config.VO.REGRESS_MODEL
@@ -596,12 +603,109 @@ class BaseRLTrainerWithVO:
     def _compute_local_delta_states_from_vo(self, prev_obs, cur_obs, act, vis_video=False):
         """(prev_obs, cur_obs, act) -> (list of 3 np.float32, std list, extra_infos)  (:169-314; std is [0,0,0] in mode
         'det' and the per-component standard deviation of the rnd_mode_n dropout samples in mode 'rnd')."""
-        if getattr(self, "_vo_obs_transformer", None) is not None:
-            raise NotImplementedError
         deltas = self.compute_local_delta_states_batch([prev_obs], [cur_obs], [act])
         extra_infos = {}
-        if vis_video and "top_down" in self.config.VO.REGRESS_MODEL.name:
+        if vis_video and "top_down" in self.config.VO.REGRESS_MODEL.name and getattr(self, "_vo_obs_transformer", None) is not None:
+            # :270-275: the view of the TRANSFORMED cur frame, [H, W, 1] at the VIS size
+            extra_infos["ego_top_down_map"] = self._last_obs_pairs["top_down_view"][0, :, :, 1:2].clone()
+        elif vis_video and "top_down" in self.config.VO.REGRESS_MODEL.name:
             d = torch.from_numpy(np.ascontiguousarray(cur_obs["depth"], dtype=np.float32)).to(self.device)
             extra_infos["ego_top_down_map"] = self._top_down_view_generator.gen_top_down_view(d)
         stds = [0, 0, 0] if self.config.VO.REGRESS_MODEL.mode == "det" else list(self._last_std[0])
         return list(deltas[0]), stds, extra_infos
+
+    # ------------------------------------------------------------------------------------------------ VO.OBS_TRANSFORM
+    def _compute_transformed_batch(self, prev_obs_list, cur_obs_list, acts):
+        """compute_local_delta_states_batch with VO.OBS_TRANSFORM 'resize' / 'resize_crop' (base_trainer_with_vo.py:195-207): the 2N
+        frames are staged at the SENSOR size, one pnvo_resize_area launch per modality resamples them (crop fused) straight into the
+        float32 observation pairs at the VIS size, the one-hot depth and the top-down views are built from the transformed depth,
+        and the model runs its float-pair forward (model(obs_pairs)).  The transformed RGB keeps its fractions (the reference
+        interpolates the float RGB).  env_ids is accepted by the caller but the frame ring is not used here: both frames of every
+        pair are uploaded, and the results equal env_ids=None.  One host synchronisation at the end."""
+        tr = self._vo_obs_transformer
+        rm = self.config.VO.REGRESS_MODEL
+        if rm.mode not in ("det", "rnd"):
+            raise NotImplementedError(f"VO.REGRESS_MODEL.mode == {rm.mode!r}")
+        n = len(acts)
+        Hs, Ws = prev_obs_list[0]["depth"].shape[:2]
+        H, W = int(self.config.VO.VIS_SIZE_H), int(self.config.VO.VIS_SIZE_W)
+        geom = transformed_size(Hs, Ws, tr.mode, tr._size)
+        if tuple(geom[4:]) != (H, W):
+            raise ValueError(f"VO.OBS_TRANSFORM {tr.mode!r} maps the {Hs}x{Ws} sensor frames to {geom[4]}x{geom[5]}, but the VO model "
+                             f"takes VIS_SIZE_H x VIS_SIZE_W = {H}x{W}")
+        # the reference resamples an 8-channel NHWC tensor: permuted without .contiguous() torch's channels-last kernel divides every
+        # channel by kh * kw; a channels_last transformer makes it contiguous first ((sum / kh) / kw)
+        rule = DIV_CONTIGUOUS if tr.channels_last else DIV_CHANNELS_LAST
+        name = rm.name
+        vis = list(rm.visual_type)
+        want_rgb = "rgb" in vis
+        dev = self.device
+        keys = ["all"] * n if rm.regress_type == "unified_act" else [ACT_IDX2NAME[a] for a in acts]
+        order = sorted(range(n), key=lambda i: keys[i])    # one contiguous slice per action model, as the untransformed path
+        prev_obs_list = [prev_obs_list[i] for i in order]
+        cur_obs_list = [cur_obs_list[i] for i in order]
+        acts = [acts[i] for i in order]
+        keys = [keys[i] for i in order]
+        st = getattr(self, "_tstage", None)
+        shape = (Hs, Ws, H, W, want_rgb)
+        if st is None or st["cap"] < n or st["shape"] != shape:
+            cap = max(n, 2 * st["cap"]) if (st is not None and st["shape"] == shape) else n
+            st = dict(cap=cap, shape=shape,
+                      h_rgb=torch.empty((cap, 2, Hs, Ws, 3), dtype=torch.uint8).pin_memory() if want_rgb else None,
+                      h_dep=torch.empty((cap, 2, Hs, Ws), dtype=torch.float32).pin_memory(),
+                      d_rgb=torch.empty((cap, 2, Hs, Ws, 3), dtype=torch.uint8, device=dev) if want_rgb else None,
+                      d_dep=torch.empty((cap, 2, Hs, Ws), dtype=torch.float32, device=dev),
+                      rgb=torch.empty((cap, H, W, 6), dtype=torch.float32, device=dev) if want_rgb else None,
+                      depth=torch.empty((cap, H, W, 2), dtype=torch.float32, device=dev))
+            self._tstage = st
+        frames = [o for pc in zip(prev_obs_list, cur_obs_list) for o in pc]
+        pd_all, keep_d = self._frame_ptrs([f["depth"] for f in frames], np.float32, (Hs, Ws))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        threads = min(self.stage_threads, 2 * n)
+        out = np.zeros((n, 3), dtype=np.float32)
+        std = np.zeros((n, 3), dtype=np.float32)
+        pending = []
+        with torch.cuda.device(dev), torch.no_grad():
+            if want_rgb:
+                pr_all, keep_r = self._frame_ptrs([f["rgb"] for f in frames], np.uint8, (Hs, Ws, 3))
+                _lib.check(_lib.lib.pnvo_stage_frames2(C.c_void_p(C.addressof(pr_all)), Hs * Ws * 3, p(st["h_rgb"]),
+                                                       C.c_void_p(C.addressof(pd_all)), Hs * Ws * 4, p(st["h_dep"]), 2 * n, threads))
+                st["d_rgb"][:n].copy_(st["h_rgb"][:n], non_blocking=True)
+                # frames 2i / 2i+1 -> channels 0-2 / 3-5 of rgb pair i
+                launch_resize(st["d_rgb"].data_ptr(), torch.uint8, 2 * n, Hs, Ws, 3, (Hs * Ws * 3, Ws * 3, 3), geom,
+                              st["rgb"].data_ptr(), 2, (H * W * 6, 3, W * 6, 6), rule, dev)
+            else:
+                _lib.check(_lib.lib.pnvo_stage_frames(C.c_void_p(C.addressof(pd_all)), 2 * n, Hs * Ws * 4, p(st["h_dep"]), threads))
+            st["d_dep"][:n].copy_(st["h_dep"][:n], non_blocking=True)
+            launch_resize(st["d_dep"].data_ptr(), torch.float32, 2 * n, Hs, Ws, 1, (Hs * Ws, Ws, 1), geom,
+                          st["depth"].data_ptr(), 2, (H * W * 2, 1, W * 2, 2), rule, dev)
+            self._dd_flag = None
+            obs_pairs = self._build_obs_pairs(st["rgb"][:n] if want_rgb else None, st["depth"][:n])
+            self._last_obs_pairs = obs_pairs
+            for key in sorted(set(keys)):
+                idx = [i for i, k in enumerate(keys) if k == key]            # contiguous: the pairs are sorted by key
+                lo_k, hi_k = idx[0], idx[-1] + 1
+                sub = {k: v[lo_k:hi_k] for k, v in obs_pairs.items() if k in vis}
+                model = self.vo_model[key]
+                a = torch.as_tensor([acts[i] for i in idx], dtype=torch.long, device=dev) if "act_embed" in name else None
+                if rm.mode == "det":                      # :285-294
+                    if model.training:
+                        model.eval()
+                    pending.append((idx, model(sub, a) if a is not None else model(sub)))
+                else:                                     # 'rnd', :295-308
+                    model.train()
+                    samples = np.stack([(model(sub, a) if a is not None else model(sub)).cpu().numpy()
+                                        for _ in range(int(rm.rnd_mode_n))])
+                    out[idx] = samples.mean(axis=0)
+                    std[idx] = samples.std(axis=0)
+            for idx, res in pending:                      # the first .cpu() is the one synchronisation of the call
+                out[idx] = res.cpu().numpy()
+            torch.cuda.current_stream(dev).synchronize()
+        del keep_d
+        if self._dd_flag is not None:
+            assert int(self._dd_flag.item()) == 0, "depth must lie in [0, 1]"      # the reference's asserts (:136-137)
+        inv = np.empty(n, dtype=np.int64)
+        inv[np.asarray(order)] = np.arange(n)
+        out, std = out[inv], std[inv]
+        self._last_std = std
+        return out
