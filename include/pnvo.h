@@ -382,7 +382,9 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
  *   depth [B,H,W,1] in 0..1 (observations["depth"]);  goal [B,2] = pointgoal_with_gps_compass (rho, phi);
  *   prev_actions [B] int64;  masks [B] (0 at an episode start);  hidden_in / hidden_out [2*rnn_layers, B, hidden]
  *   (h of every layer, then c of every layer: rnn_state_encoder.py:47-61);  features [B,hidden], logits [B,n_actions],
- *   value [B] may each be NULL.  Sampling / argmax over the logits stays with the caller (policy.py:38-43). */
+ *   value [B] may each be NULL.  Sampling / argmax over the logits stays with the caller (policy.py:38-43).
+ *   hidden_in and hidden_out must not overlap (the LSTM writes a layer's state while other workgroups still read it):
+ *   overlapping ranges are refused with PNVO_ERR_ARG before anything is launched. */
 int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions,
                     const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                     float *value, void *stream);

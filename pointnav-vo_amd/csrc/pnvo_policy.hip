@@ -11,6 +11,7 @@
 // ddppo_trainer.py:118-121).  The recurrent part is tiny and weight-bandwidth-bound at B = number of environments
 // (9.4 MB of LSTM weights per step), so its Linears are wave-per-output-row dot products on the vector ALU, not MFMA.
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -230,9 +231,16 @@ int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *str
 
 int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_handle *out) {
   if (!cfg || !out) return pfail(PNVO_ERR_ARG, "null argument");
-  if (cfg->width < 64 || cfg->height < 64 || cfg->hidden % 4 != 0 || cfg->rnn_layers < 1 || cfg->rnn_layers > 4 ||
-      cfg->n_actions < 1 || cfg->n_actions > 32)
-    return pfail(PNVO_ERR_ARG, "unsupported policy configuration");
+  if (cfg->width < 64 || cfg->height < 64)
+    return pfail(PNVO_ERR_ARG, "unsupported policy observation size " + std::to_string(cfg->width) + "x" + std::to_string(cfg->height) +
+                                   " (width and height must be >= 64)");
+  // the visual encoder's visual_fc takes hidden sizes in multiples of 8 (pnvo_create); the LSTM's rows are read as float4
+  if (cfg->hidden <= 0 || cfg->hidden % 8 != 0)
+    return pfail(PNVO_ERR_ARG, "unsupported policy hidden_size " + std::to_string(cfg->hidden) + " (must be a positive multiple of 8)");
+  if (cfg->rnn_layers < 1 || cfg->rnn_layers > 4)
+    return pfail(PNVO_ERR_ARG, "unsupported policy num_recurrent_layers " + std::to_string(cfg->rnn_layers) + " (1 to 4)");
+  if (cfg->n_actions < 1 || cfg->n_actions > 32)
+    return pfail(PNVO_ERR_ARG, "unsupported policy action_space.n " + std::to_string(cfg->n_actions) + " (1 to 32)");
   pnvo_policy_s *h = new pnvo_policy_s();
   h->p.cfg = *cfg;
   h->p.device = device;
@@ -360,10 +368,17 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
   if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_act before pnvo_policy_load_weights");
   if (B <= 0 || !depth || !goal || !prev_actions || !masks || !hidden_in || !hidden_out)
     return pfail(PNVO_ERR_ARG, "null argument / bad batch");
-  PCHK(hipSetDevice(p.device));
-  hipStream_t s = (hipStream_t)stream;
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
+  {
+    // lstm_layer_kernel writes h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory
+    const uintptr_t bytes = (uintptr_t)2 * L * B * Hd * sizeof(float);
+    const uintptr_t in0 = (uintptr_t)hidden_in, out0 = (uintptr_t)hidden_out;
+    if (in0 < out0 + bytes && out0 < in0 + bytes)
+      return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * B * hidden floats): pass separate buffers");
+  }
+  PCHK(hipSetDevice(p.device));
+  hipStream_t s = (hipStream_t)stream;
   if (B > p.cap) {
     dfree(p.pooled);
     dfree(p.visual);

@@ -57,28 +57,37 @@ class Space:
 
 
 class Act:
-    n = 4
+    def __init__(self, n):
+        self.n = n
+
+
+# tag -> (H, W, B, steps, hidden_size, num_recurrent_layers, action_space.n); the last case is the non-default configuration
+# (its fixture records the three sizes; the others are the default 512 / 2 / 4)
+CASES = {"341x192_b3": (192, 341, 3, 4, 512, 2, 4), "128x96_b2": (96, 128, 2, 3, 512, 2, 4),
+         "128x96_h256_l3_a3_b3": (96, 128, 3, 3, 256, 3, 3)}
 
 
 def main():
     rp = import_policy()
-    for tag, (H, W, B, steps) in {"341x192_b3": (192, 341, 3, 4), "128x96_b2": (96, 128, 2, 3)}.items():
+    for tag, (H, W, B, steps, Hd, L, n_act) in CASES.items():
         space = Space({"depth": Box((H, W, 1)), "rgb": Box((H, W, 3)), "pointgoal_with_gps_compass": Box((2,))})
-        pol = rp.PointNavResNetPolicy(observation_space=space, action_space=Act(), hidden_size=512, rnn_type="LSTM",
-                                      num_recurrent_layers=2, backbone="resnet18",
+        pol = rp.PointNavResNetPolicy(observation_space=space, action_space=Act(n_act), hidden_size=Hd, rnn_type="LSTM",
+                                      num_recurrent_layers=L, backbone="resnet18",
                                       goal_sensor_uuid="pointgoal_with_gps_compass", normalize_visual_inputs=False,
                                       obs_transform=None, vis_types=["depth"])
-        spec = policy_state_dict_spec(width=W, height=H)
+        spec = policy_state_dict_spec(width=W, height=H, hidden=Hd, n_actions=n_act, rnn_layers=L)
         ref_sd = pol.state_dict()
         assert [(k, tuple(v.shape)) for k, v in ref_sd.items()] == [(n, tuple(s)) for n, s in spec], "state_dict spec drift"
         seed = 11
         sd = synth.make_state_dict(spec, seed=seed)
         rec = {"H": H, "W": W, "B": B, "steps": steps, "weight_seed": seed, "input_seed": 5}
+        if (Hd, L, n_act) != (512, 2, 4):
+            rec.update(hidden=Hd, layers=L, n_actions=n_act)
         for dtype, sfx in ((torch.float64, "64"), (torch.float32, "32")):
             pol.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
             pol = pol.to(dtype).eval()
-            hidden = torch.zeros(4, B, 512, dtype=dtype)
-            for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, rec["input_seed"])):
+            hidden = torch.zeros(2 * L, B, Hd, dtype=dtype)
+            for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, rec["input_seed"], n_act)):
                 obs = {"depth": torch.from_numpy(depth).to(dtype), "pointgoal_with_gps_compass": torch.from_numpy(goal).to(dtype)}
                 pa, mk = torch.from_numpy(prev).view(B, 1), torch.from_numpy(mask).view(B, 1).to(dtype)
                 with torch.no_grad():

@@ -25,17 +25,19 @@ class Space:
 
 
 class Act:
-    n = 4
+    def __init__(self, n=4):
+        self.n = n
 
 
-def build(H, W, seed):
+def build(H, W, seed, hidden=512, layers=2, n_actions=4):
     cls = baseline_registry.get_policy("resnet_rnn_policy")
     assert cls is PointNavResNetPolicy
     space = Space({"depth": Box((H, W, 1)), "rgb": Box((H, W, 3)), "pointgoal_with_gps_compass": Box((2,))})
-    pol = cls(observation_space=space, action_space=Act(), hidden_size=512, rnn_type="LSTM", num_recurrent_layers=2,
-              backbone="resnet18", goal_sensor_uuid="pointgoal_with_gps_compass", normalize_visual_inputs=False,
-              obs_transform=None, vis_types=["depth"])
-    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H), seed=seed)
+    pol = cls(observation_space=space, action_space=Act(n_actions), hidden_size=hidden, rnn_type="LSTM",
+              num_recurrent_layers=layers, backbone="resnet18", goal_sensor_uuid="pointgoal_with_gps_compass",
+              normalize_visual_inputs=False, obs_transform=None, vis_types=["depth"])
+    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H, hidden=hidden, n_actions=n_actions, rnn_layers=layers),
+                               seed=seed)
     assert list(pol.state_dict().keys()) == list(sd.keys())
     pol.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
     return pol.to("cuda:0").eval(), sd
@@ -46,15 +48,16 @@ def close(got, want, tol=2e-4):
     return np.abs(got - want).max() / scale < tol
 
 
-@pytest.mark.parametrize("fname", ["policy_128x96_b2.npz", "policy_341x192_b3.npz"])
+@pytest.mark.parametrize("fname", ["policy_128x96_b2.npz", "policy_341x192_b3.npz", "policy_128x96_h256_l3_a3_b3.npz"])
 def test_policy_steps_match_reference(fname):
     rec = load_golden(fname)
     H, W, B, steps = (int(rec[k]) for k in ("H", "W", "B", "steps"))
-    pol, sd = build(H, W, int(rec["weight_seed"]))
+    Hd, L, n_act = (int(rec.get(k, d)) for k, d in (("hidden", 512), ("layers", 2), ("n_actions", 4)))
+    pol, sd = build(H, W, int(rec["weight_seed"]), hidden=Hd, layers=L, n_actions=n_act)
     dev = torch.device("cuda", 0)
-    hidden = torch.zeros(pol.num_recurrent_layers, B, 512, device=dev)
-    hid_o = np.zeros((4, B, 512))
-    for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, int(rec["input_seed"]))):
+    hidden = torch.zeros(pol.num_recurrent_layers, B, Hd, device=dev)
+    hid_o = np.zeros((2 * L, B, Hd))
+    for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, int(rec["input_seed"]), n_act)):
         obs = {"depth": torch.from_numpy(depth).to(dev), "pointgoal_with_gps_compass": torch.from_numpy(goal).to(dev)}
         pa, mk = torch.from_numpy(prev).view(B, 1).to(dev), torch.from_numpy(mask).view(B, 1).to(dev)
         feats, hnew, logits, value = pol.features_and_logits(obs, hidden, pa, mk)

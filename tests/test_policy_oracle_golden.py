@@ -9,13 +9,15 @@ from pointnav_vo_amd import synth
 from pointnav_vo_amd.policy import policy_state_dict_spec
 
 
-@pytest.mark.parametrize("fname", ["policy_128x96_b2.npz", "policy_341x192_b3.npz"])
+@pytest.mark.parametrize("fname", ["policy_128x96_b2.npz", "policy_341x192_b3.npz", "policy_128x96_h256_l3_a3_b3.npz"])
 def test_policy_oracle_matches_reference(fname):
     rec = load_golden(fname)
     H, W, B, steps = (int(rec[k]) for k in ("H", "W", "B", "steps"))
-    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H), seed=int(rec["weight_seed"]))
-    hidden = np.zeros((4, B, 512))
-    for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, int(rec["input_seed"]))):
+    Hd, L, n_act = (int(rec.get(k, d)) for k, d in (("hidden", 512), ("layers", 2), ("n_actions", 4)))
+    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H, hidden=Hd, n_actions=n_act, rnn_layers=L),
+                               seed=int(rec["weight_seed"]))
+    hidden = np.zeros((2 * L, B, Hd))
+    for t, (depth, goal, prev, mask) in enumerate(synth.make_policy_inputs(H, W, B, steps, int(rec["input_seed"]), n_act)):
         out = policy_oracle.policy_step(sd, depth, goal, prev, mask, hidden, dtype=np.float64)
         for key, ref in (("features", "features64"), ("hidden", "hidden64"), ("logits", "logits_raw64"),
                          ("value", "value64")):
