@@ -110,7 +110,7 @@ int pnvo_forward(pnvo_handle h, const float *rgb, const float *depth, const floa
  *                                                            then leaves NaN poses and fails the handle's next call)
  *   "graph"           0 | 1                                  replay the forward from a captured hipGraph
  *   "wgrad_stem"      mx | fp32        "pool_bwd" fused | separate        "dgrad" phase | masked        (training step)
- *   "bf16_fuse"       on | off         "bf16_stem3" 0 | 1    "conv3_nt" 0 | 1   "stem_dbg" <int>            (experiments)
+ *   "bf16_fuse"       on | off         "stem_dbg" <int>                                           (experiments)
  * Unknown keys / values return PNVO_ERR_ARG with the accepted spellings in pnvo_last_error.
  */
 int pnvo_set_option(pnvo_handle h, const char *key, const char *value);

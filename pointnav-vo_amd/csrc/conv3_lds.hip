@@ -496,13 +496,7 @@ hipError_t launch_cfg(const ConvArgs &a, int tiles_x, int tiles_y, hipStream_t s
   const int ngroups = a.COUTP / 32 / NT;
   const long nwork = (long)a.B * tiles_x * tiles_y * ngroups;
   // persistent grid: as many workgroups as fit (LDS-limited), rounded so that every workgroup gets the same item count
-  long resident = 256L * (long)((160 * 1024) / lds);
-  static int cap = -1;
-  if (cap < 0) {
-    const char *e = std::getenv("PNVO_CONV3_WGS");     // experiment knob: workgroups per CU
-    cap = e ? std::atoi(e) : 0;
-  }
-  if (cap > 0) resident = 256L * cap;
+  const long resident = 256L * (long)((160 * 1024) / lds);
   const long rounds = (nwork + resident - 1) / resident;
   const long grid_x = (nwork + rounds - 1) / rounds;
   dim3 grid((unsigned)grid_x);

@@ -467,7 +467,7 @@ bool conv_bf16_plan(ConvBArgs &a, int ks, int stride, int *mw, int *nw, size_t *
     // the layer is narrow enough for the accumulators and the patch still fits; measured on layer 1: 0.155 -> 0.116 ms
     TR = 8;
     TC = 16;
-    if (ntt == 1 && a.Ho % 16 == 0 && !std::getenv("PNVO_BF16_T8")) {   // (layer 2 at 24 x 43 wastes a third of 16-row tiles: slower)
+    if (ntt == 1 && a.Ho % 16 == 0) {   // (layer 2 at 24 x 43 wastes a third of 16-row tiles: slower)
       const int cs_ = ks == 1 ? 1 : stride;
       const size_t patch = (size_t)(15 * cs_ + ks) * (15 * cs_ + ks) * (a.CIN * 2 + 16);
       if (patch <= (size_t)56 * 1024) TR = 16;

@@ -112,30 +112,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   const float g_oscale = mdl == 0 ? p.oscale : p.oscale_g[mdl - 1], g_ds_oscale = mdl == 0 ? p.ds_oscale : p.ds_oscale_g[mdl - 1];
   const float *g_gamma = mdl == 0 ? p.gn_gamma : p.gn_gamma_g[mdl - 1], *g_beta = mdl == 0 ? p.gn_beta : p.gn_beta_g[mdl - 1];
   const float *g_ds_gamma = mdl == 0 ? p.ds_gamma : p.ds_gamma_g[mdl - 1], *g_ds_beta = mdl == 0 ? p.ds_beta : p.ds_beta_g[mdl - 1];
-  // Deferred GroupNorm finalisation (round 6, small launches): the producer of this conv's input (fin_in) / of the skip branch (fin_res)
-  // left its partial sums un-finalised; waves 0 and 1 turn them into this sample's scale / shift tables before anything else holds
-  // registers (gn_finalize_wave16: gn_finalize_kernel's arithmetic, bit for bit).  One memory round trip + ~0.5 us of fp64 per
-  // workgroup: cheaper than a launch while launches are the bound (8-48 pairs), dearer at 256 pairs — the host defers accordingly.
-  if ((MODE == 1 || MODE == 2) && (p.fin_in.stats != nullptr || p.fin_res.stats != nullptr)) {
-    const int planes0 = NP * ((p.PR * p.PC) * (p.CK * 2 + 16));
-    float *ftab0 = reinterpret_cast<float *>(lds + (KSW ? max(planes0, 4 * MW * 4096) : planes0) + (size_t)p.MT * 32 * 8);
-    const long P_in = (long)p.H * p.W;
-    if (p.fin_in.stats != nullptr && wave == 0) {
-      const int Gn = p.CIN / p.fin_in.cpg;
-      const float *ga = mdl == 0 ? p.fin_in.gamma : p.fin_in.gamma_g[mdl - 1], *be = mdl == 0 ? p.fin_in.beta : p.fin_in.beta_g[mdl - 1];
-      for (int g0 = 0; g0 < Gn; g0 += 16)
-        gn_finalize_wave16(p.fin_in.stats + (long)n * p.fin_in.slots * p.CIN * 2, p.fin_in.slots, p.CIN, g0, Gn, p.fin_in.cpg, P_in, 1e-5f, ga, be,
-                           ftab0, ftab0 + p.CIN);
-    }
-    if (MODE == 2 && p.fin_res.stats != nullptr && wave == 1) {
-      const int Gn = p.CIN / p.fin_res.cpg;
-      const float *ga = mdl == 0 ? p.fin_res.gamma : p.fin_res.gamma_g[mdl - 1], *be = mdl == 0 ? p.fin_res.beta : p.fin_res.beta_g[mdl - 1];
-      for (int g0 = 0; g0 < Gn; g0 += 16)
-        gn_finalize_wave16(p.fin_res.stats + (long)n * p.fin_res.slots * p.CIN * 2, p.fin_res.slots, p.CIN, g0, Gn, p.fin_res.cpg, P_in, 1e-5f, ga, be,
-                           ftab0 + 2 * p.CIN, ftab0 + 3 * p.CIN);
-    }
-    __syncthreads();
-  }
   const int PR = p.PR, PC = p.PC, CK = p.CK;
   const int pitch = CK * 2 + 16;                   // bytes per patch pixel in one piece plane (odd number of 16-byte units)
   const int plane = PR * PC * pitch;               // bytes of one piece plane
@@ -199,24 +175,19 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     if (ck0 > 0) __syncthreads();                                        // the previous chunk's patch is no longer read
     {
       f32x4 sc0, sc1, sh0, sh1, rs0, rs1, rt0, rt1;
-      const bool fin_i = (MODE == 1 || MODE == 2) && p.fin_in.stats != nullptr;
-      const bool fin_r = MODE == 2 && p.fin_res.stats != nullptr;
-      const bool res_ss = MODE == 2 && (p.res_scale != nullptr || fin_r);
-      // Deferred GroupNorm finalisation (p.fin_in / p.fin_res): the sample's scale / shift tables were built at the top of the kernel,
-      // in LDS behind the pixel tables
-      float *ftab = reinterpret_cast<float *>(lds + tab_off + (size_t)p.MT * 32 * 8);   // [in scale | in shift | res scale | res shift][CIN]
+      const bool res_ss = MODE == 2 && p.res_scale != nullptr;
       auto load_ss = [&]() {
         if (MODE >= 1) {
-          const float *ps = fin_i ? ftab + ck0 + 8 * cg : p.in_scale + (long)n * p.CIN + ck0 + 8 * cg;
-          const float *pt = fin_i ? ftab + p.CIN + ck0 + 8 * cg : p.in_shift + (long)n * p.CIN + ck0 + 8 * cg;
+          const float *ps = p.in_scale + (long)n * p.CIN + ck0 + 8 * cg;
+          const float *pt = p.in_shift + (long)n * p.CIN + ck0 + 8 * cg;
           sc0 = *reinterpret_cast<const f32x4 *>(ps);
           sc1 = *reinterpret_cast<const f32x4 *>(ps + 4);
           sh0 = *reinterpret_cast<const f32x4 *>(pt);
           sh1 = *reinterpret_cast<const f32x4 *>(pt + 4);
         }
         if (res_ss) {
-          const float *ps = fin_r ? ftab + 2 * p.CIN + ck0 + 8 * cg : p.res_scale + (long)n * p.CIN + ck0 + 8 * cg;
-          const float *pt = fin_r ? ftab + 3 * p.CIN + ck0 + 8 * cg : p.res_shift + (long)n * p.CIN + ck0 + 8 * cg;
+          const float *ps = p.res_scale + (long)n * p.CIN + ck0 + 8 * cg;
+          const float *pt = p.res_shift + (long)n * p.CIN + ck0 + 8 * cg;
           rs0 = *reinterpret_cast<const f32x4 *>(ps);
           rs1 = *reinterpret_cast<const f32x4 *>(ps + 4);
           rt0 = *reinterpret_cast<const f32x4 *>(pt);
@@ -711,10 +682,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             s2 += o[1];
           }
           float *dst = stats + (((long)n * p.slots + tri * p.tiles_c + tci) * p.COUTP + nt * 32 + lane) * 2;
-          if (p.gn_ctr != nullptr) {                                       // read by the sample's last workgroup inside this launch
-            gn_stats_store(dst, s1, s2);
-            continue;
-          }
           dst[0] = s1;
           dst[1] = s2;
           if (gscale != nullptr) {                                         // the sample's only slot: finalise here (no launch)
@@ -731,21 +698,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   };
   emit(acc, p.y, p.stats, p.oscale_ptr, g_oscale, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd, false);
   if constexpr (DSF) emit(accd, p.ds_y, p.ds_stats, p.ds_oscale_ptr, g_ds_oscale, g_ds_gamma, g_ds_beta, p.ds_scale, p.ds_shift, p.ds_mu, p.ds_rstd, true);
-  if (p.stats != nullptr && p.gn_ctr != nullptr) {                        // several tiles per sample: the last one to arrive finalises
-    if (gn_last_arrival(p.gn_ctr + (long)n * gridDim.y + blockIdx.y, (unsigned)p.slots, reinterpret_cast<int *>(lds + 4096))) {
-      const int nt0 = (int)blockIdx.y * wn * NW, nt1 = min(nt0 + wn * NW, ntt);
-      const int NG = p.COUTP / p.gn_cpg;
-      for (int g = (nt0 * 32) / p.gn_cpg + wave; g < (nt1 * 32) / p.gn_cpg; g += NWV) {
-        gn_finalize_group_wave(p.stats + (long)n * p.slots * p.COUTP * 2, p.slots, p.COUTP, g, p.gn_cpg, p.gn_P, p.gn_eps, g_gamma, g_beta,
-                               p.gn_scale + (long)n * p.COUTP, p.gn_shift + (long)n * p.COUTP, p.gn_mu ? p.gn_mu + (long)n * NG + g : nullptr,
-                               p.gn_mu ? p.gn_rstd + (long)n * NG + g : nullptr);
-        if (DSF)
-          gn_finalize_group_wave(p.ds_stats + (long)n * p.slots * p.COUTP * 2, p.slots, p.COUTP, g, p.gn_cpg, p.gn_P, p.gn_eps, g_ds_gamma,
-                                 g_ds_beta, p.ds_scale + (long)n * p.COUTP, p.ds_shift + (long)n * p.COUTP, p.ds_mu ? p.ds_mu + (long)n * NG + g : nullptr,
-                                 p.ds_mu ? p.ds_rstd + (long)n * NG + g : nullptr);
-      }
-    }
-  }
   if (p.prof && lane == 0 && blockIdx.x == 13 && blockIdx.y == 0) {
     const unsigned long long t_f = __builtin_readcyclecounter();
     unsigned long long *d = p.prof + wave * 8;
@@ -1216,8 +1168,7 @@ bool conv_x3_plan(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *l
   const bool reg_ok = conv_x3_plan_impl(reg, ks, stride, &rmw, &rnw, &rlds, false);
   const long reg_wgs = reg_ok ? plan_wgs(reg, rnw) : 0;
   const int ntt = a.COUTP / 32;
-  static const long fine_below = std::getenv("PNVO_FINE_BELOW") ? std::atol(std::getenv("PNVO_FINE_BELOW")) : 224;   // (developer sweep; 224 measured best)
-  if (a.fine && a.np == 2 && ntt >= 2 && (!reg_ok || reg_wgs < fine_below)) {
+  if (a.fine && a.np == 2 && ntt >= 2 && (!reg_ok || reg_wgs < 224)) {   // (224 measured best)
     ConvX3Args f = a;
     int fmw = 0, fnw = 0;
     size_t flds = 0;
@@ -1368,8 +1319,7 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
   while (ck < 256 && a.CIN % (2 * ck) == 0) ck *= 2;
   // (W8 with the whole K = 256 in one 110 KB chunk — its launches are one workgroup per CU anyway: staging 14.5 k -> 7.8 k cycles per
   //  workgroup, the conv's time unchanged, 77-82 us on either form: not kept)
-  static const long w8_s2_lds = std::getenv("PNVO_X3_W8_LDS") ? std::atol(std::getenv("PNVO_X3_W8_LDS")) : 72;   // (developer sweep)
-  const size_t cap = (size_t)(a.w8 && stride == 2 ? w8_s2_lds : 72) * 1024;
+  const size_t cap = (size_t)72 * 1024;
   while (ck > 32 && np * a.PR * a.PC * (ck * 2 + 16) > cap) ck /= 2;
   if (np * a.PR * a.PC * (ck * 2 + 16) > cap + 4096) return false;
   if (a.CIN % ck) return false;
@@ -1385,9 +1335,9 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
     if (wgs < (a.np == 2 ? 112 : 192) && !force) return false;
   }
   a.slots = a.tiles_r * a.tiles_c;                               // one GroupNorm partial per tile
+  // planes, pixel tables (1 KB more would cost the 64-channel convs their third workgroup per CU)
   *lds_bytes = np * a.PR * a.PC * (ck * 2 + 16) + (size_t)a.MT * 32 * 4 * 2;
-  if (a.ksw) *lds_bytes = std::max(np * a.PR * a.PC * (ck * 2 + 16), (size_t)4 * a.MT * 4096) + (size_t)a.MT * 32 * 4 * 2;   // planes / the four waves' partial accumulator tiles, then the tables   // planes, pixel tables (a launch with a deferred GroupNorm adds 16 B per input
-                                                                                // channel behind them: pnvo_run_conv — 1 KB more would cost the 64-channel convs their third workgroup per CU)
+  if (a.ksw) *lds_bytes = std::max(np * a.PR * a.PC * (ck * 2 + 16), (size_t)4 * a.MT * 4096) + (size_t)a.MT * 32 * 4 * 2;   // planes / the four waves' partial accumulator tiles, then the tables
   return true;
 }
 }  // namespace

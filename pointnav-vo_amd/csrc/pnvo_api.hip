@@ -267,12 +267,7 @@ void free_workspace(pnvo_model_s *m) {
   free_dev(m->comp_raw);
   free_dev(m->hid);
   free_dev(m->stats);
-  free_dev(m->gn_ctr);
   free_dev(m->stats_ds);
-  free_dev(m->statsB);
-  if (m->keys_stream) (void)hipStreamSynchronize(m->keys_stream);     // a fill of the key buffer may still be in flight
-  free_dev(m->pool_keys);
-  m->keys_primed = false;
   for (int k = 0; k < 2; ++k) {
     free_dev(m->ssA[k]);
     free_dev(m->ssB[k]);
@@ -362,12 +357,7 @@ int ensure_workspace(pnvo_handle m, int B) {   // (also exported as pnvo_ensure_
   HIPCHK(m, alloc(m->hid, (size_t)B * c.hidden));
   HIPCHK(m, alloc(m->out_ws, (size_t)B * c.out_dim));
   HIPCHK(m, alloc(m->stats, st));
-  m->stats_floats = st;
   HIPCHK(m, alloc(m->stats_ds, st));
-  HIPCHK(m, alloc(m->statsB, st));
-  HIPCHK(m, alloc(m->pool_keys, (size_t)B * m->Hp * m->Wp * m->convs[0].coutp));
-  HIPCHK(m, alloc(m->gn_ctr, (size_t)B * 16));
-  HIPCHK(m, hipMemset(m->gn_ctr, 0, (size_t)B * 16 * sizeof(float)));
   for (int k = 0; k < 2; ++k) {
     HIPCHK(m, alloc(m->ssA[k], (size_t)B * maxc));
     HIPCHK(m, alloc(m->ssB[k], (size_t)B * maxc));
@@ -712,37 +702,10 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
         const float *sp = pnvo_train_x2_scale(m, l.name + ".weight");
         xa.oscale_ptr = sp ? sp + 1 : nullptr;
       }
-      // partial sums: the convs that write ssB keep a buffer of their own (a deferred finalisation reads the producer's sums while
-      // the consumer writes its own)
-      float *stats_buf = (ss[0] == m->ssB[0] && m->statsB != nullptr) ? m->statsB : m->stats;
-      auto pend_key = [&](const float *sc) { return sc == nullptr ? -1 : sc == m->ssA[0] ? 0 : sc == m->ssB[0] ? 1 : sc == m->ssD[0] ? 2 : -1; };
-      auto take_pend = [&](const float *sc, ConvX3Args::Fin &f) -> int {      // a pending finalisation behind `sc`: this launch does it
-        const int k = pend_key(sc);
-        if (k < 0 || !m->gn_pend[k].valid) return PNVO_OK;
-        if (rows || !(x3_mode == 1 || x3_mode == 2))
-          return fail(m, PNVO_ERR_STATE, "a deferred GroupNorm finalisation reached a launch that cannot do it (" + l.name + ")");
-        const auto &pd = m->gn_pend[k];
-        const Layer &pl = m->convs[pd.layer];
-        f.stats = pd.stats;
-        f.slots = pd.slots;
-        f.cpg = pd.cpg;
-        f.gamma = pl.gamma;
-        f.beta = pl.beta;
-        for (int g = 1; g < m->grp_n; ++g) {
-          f.gamma_g[g - 1] = m->grp[g]->convs[pd.layer].gamma;
-          f.beta_g[g - 1] = m->grp[g]->convs[pd.layer].beta;
-        }
-        m->gn_pend[k].valid = false;
-        return PNVO_OK;
-      };
-      if (int rcp = take_pend(in_scale, xa.fin_in)) return rcp;
-      if (tail != nullptr)
-        if (int rcp = take_pend(tail->res_scale, xa.fin_res)) return rcp;
-      if (xa.fin_in.stats != nullptr || xa.fin_res.stats != nullptr) ldsb += (size_t)xa.CIN * 16;   // the scale / shift tables built in the prologue
       xa.y = y;
       xa.in_scale = in_scale;
       xa.in_shift = in_shift;
-      xa.stats = stats_buf;
+      xa.stats = m->stats;
       if (tail != nullptr) {
         if (in_scale == nullptr) return fail(m, PNVO_ERR_STATE, "block tail without the conv's GroupNorm scale/shift");
         xa.res = tail->res;
@@ -755,14 +718,7 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
       const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
       const bool fuse = m->opt.gn_fuse && xa.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 &&
                         32 % cpg == 0 && l.cout % cpg == 0 && (rows || !(xa.persist_wgs > 0 && l.cin == 32 && l.coutp == 32));
-      // several tiles per sample: the sample's LAST workgroup to arrive finalises (gn_last_arrival; conv_x3_kernel only — the rows
-      // kernel with several bands and the persistent form keep the launch).  Not next to a side stream (one counter array).
-      const long x3_gy = rows ? 1 : ((l.coutp / 32) + xa.wn * nw - 1) / (xa.wn * nw);
-      const bool x3p = !rows && conv_x3_persistent(xa, l.k, l.stride, x3_mode, mw, nw);
-      const bool fuse_last = m->opt.gn_fuse == 1 && !rows && !x3p && xa.slots > 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 && 32 % cpg == 0 &&
-                             l.cout % cpg == 0 && x3_gy <= 16 && (m->side_stream == nullptr || s != m->side_stream) && m->gn_ctr != nullptr;
-      if (fuse_last) xa.gn_ctr = reinterpret_cast<unsigned *>(m->gn_ctr);
-      if ((fuse || fuse_last) && ride != nullptr) {
+      if (fuse && ride != nullptr) {
         xa.ds_gamma = ride->cd->gamma;
         xa.ds_beta = ride->cd->beta;
         xa.ds_scale = ride->ss[0];
@@ -770,7 +726,7 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
         xa.ds_mu = ride->mu;
         xa.ds_rstd = ride->rstd;
       }
-      if (fuse || fuse_last) {
+      if (fuse) {
         xa.gn_gamma = l.gamma;
         xa.gn_beta = l.beta;
         xa.gn_scale = ss[0];
@@ -788,46 +744,17 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
         else
           HIPCHK(m, launch_conv_x3(xa, l.k, l.stride, x3_mode, mw, nw, ldsb, s));
       }
-      if (fuse || fuse_last) return PNVO_OK;
-      // deferred: the consumer launch finalises (the forward set defer_main / defer_ride for this call: it knows the consumer)
-      const bool can_defer = l.cout == l.coutp && cpg >= 1 && l.cout % cpg == 0 && mu_out == nullptr;
-      const bool dm = can_defer && m->defer_main && pend_key(ss[0]) >= 0, dr = can_defer && ride != nullptr && m->defer_ride && ride->mu == nullptr && pend_key(ride->ss[0]) >= 0;
-      if (dm) {
-        auto &pd = m->gn_pend[pend_key(ss[0])];
-        pd.stats = stats_buf;
-        pd.slots = xa.slots;
-        pd.cpg = cpg;
-        pd.layer = (size_t)(&l - m->convs.data());
-        pd.valid = true;
-      }
-      if (dr) {
-        auto &pd = m->gn_pend[pend_key(ride->ss[0])];
-        pd.stats = m->stats_ds;
-        pd.slots = xa.slots;
-        pd.cpg = cpg;
-        pd.layer = (size_t)(ride->cd - m->convs.data());
-        pd.valid = true;
-      }
-      if (dm && (ride == nullptr || dr)) return PNVO_OK;
+      if (fuse) return PNVO_OK;
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      if (ride != nullptr && (dm || dr)) {      // one of the two stays a launch
-        if (!dm)
-          HIPCHK(m, launch_gn_finalize(stats_buf, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, ss[0], ss[1], s, xa.slots,
-                                       mu_out, rstd_out, m->grp_n > 1 ? &gg : nullptr));
-        if (!dr)
-          HIPCHK(m, launch_gn_finalize(m->stats_ds, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, ride->cd->gamma, ride->cd->beta, 1e-5f,
-                                       ride->ss[0], ride->ss[1], s, xa.slots, ride->mu, ride->rstd, m->grp_n > 1 ? &ggd : nullptr));
-        return PNVO_OK;
-      }
       if (ride != nullptr) {             // the conv's GroupNorm and the riding downsample conv's in one launch
-        const float *st2[2] = {stats_buf, m->stats_ds}, *ga2[2] = {l.gamma, ride->cd->gamma}, *be2[2] = {l.beta, ride->cd->beta};
+        const float *st2[2] = {m->stats, m->stats_ds}, *ga2[2] = {l.gamma, ride->cd->gamma}, *be2[2] = {l.beta, ride->cd->beta};
         float *sc2[2] = {ss[0], ride->ss[0]}, *sh2[2] = {ss[1], ride->ss[1]};
         float *mu2[2] = {mu_out, ride->mu}, *rs2[2] = {rstd_out, ride->rstd};
         HIPCHK(m, launch_gn_finalize_pair(st2, B, xa.slots, l.coutp, l.cout, l.groups, P, ga2, be2, 1e-5f, sc2, sh2, mu2, rs2, s,
                                           m->grp_n > 1 ? &gg : nullptr, m->grp_n > 1 ? &ggd : nullptr));
         return PNVO_OK;
       }
-      HIPCHK(m, launch_gn_finalize(stats_buf, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, ss[0], ss[1], s,
+      HIPCHK(m, launch_gn_finalize(m->stats, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, ss[0], ss[1], s,
                                    xa.slots, mu_out, rstd_out, m->grp_n > 1 ? &gg : nullptr));
       return PNVO_OK;
     }
@@ -836,8 +763,7 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
   if (m->grp_n > 1 && ss != nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " fell off the float16-piece tile kernel");
   const bool lds3 = conv3_lds_supported(a) && m->opt.conv != 3;
   if (lds3) {                    // 3x3 stride-1 residual-stage conv: input patch staged in LDS
-    int nt = (l.coutp / 32) % 2 == 0 ? 2 : 1;
-    if (m->opt.conv3_nt == 1) nt = 1;
+    const int nt = (l.coutp / 32) % 2 == 0 ? 2 : 1;
     a.slots = conv3_lds_slots(a);
     {
       Timed t(m, s, "conv:" + l.name, 2.0 * macs, bytes);
@@ -1233,21 +1159,17 @@ const OptDef kOptions[] = {
     {"train_pieces", "PNVO_TRAIN_PIECES", &PnvoOptions::train_pieces, false, {{"2", 2}, {"3", 3}, {nullptr, 0}}},
     {"x3_persist", "PNVO_X3_PERSIST", &PnvoOptions::x3_persist, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_rows", "PNVO_X3_ROWS", &PnvoOptions::x3_rows, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
-    {"ds_side", "PNVO_DS_SIDE", &PnvoOptions::ds_side, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_strip", "PNVO_X3_STRIP", &PnvoOptions::x3_strip, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
-    {"pool_async", "PNVO_POOL_ASYNC", &PnvoOptions::pool_async, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
-    {"gn_defer", "PNVO_GN_DEFER", &PnvoOptions::gn_defer, true, {{nullptr, 0}}},
     {"x3_fine", "PNVO_X3_FINE", &PnvoOptions::x3_fine, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_w8", "PNVO_X3_W8", &PnvoOptions::x3_w8, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_ksplit", "PNVO_X3_KSPLIT", &PnvoOptions::x3_ksplit, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"fc_rows", "PNVO_FC_ROWS", &PnvoOptions::fc_rows, true, {{nullptr, 0}}},
     {"head_fuse", "PNVO_HEAD_FUSE", &PnvoOptions::head_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"ds_fuse", "PNVO_DS_FUSE", &PnvoOptions::ds_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
-    {"gn_fuse", "PNVO_GN_FUSE", &PnvoOptions::gn_fuse, false, {{"on", 2}, {"single", 2}, {"last", 1}, {"off", 0}, {nullptr, 0}}},
+    {"gn_fuse", "PNVO_GN_FUSE", &PnvoOptions::gn_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_s2", nullptr, &PnvoOptions::x3_s2, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"tail", "PNVO_TAIL", &PnvoOptions::tail, false, {{"fused", 1}, {"separate", 0}, {nullptr, 0}}},
     {"pool", "PNVO_POOL", &PnvoOptions::pool, false, {{"fused", 1}, {"separate", 0}, {nullptr, 0}}},
-    {"conv3_nt", "PNVO_CONV3_NT", &PnvoOptions::conv3_nt, true, {{nullptr, 0}}},
     {"graph", "PNVO_GRAPH", &PnvoOptions::graph, true, {{nullptr, 0}}},
     {"stem_dbg", nullptr, &PnvoOptions::stem_dbg, true, {{nullptr, 0}}},
     {"stem_dbg_pad", nullptr, &PnvoOptions::stem_dbg_pad, true, {{nullptr, 0}}},
@@ -1256,7 +1178,6 @@ const OptDef kOptions[] = {
     {"pool_bwd", "PNVO_POOL_BWD", &PnvoOptions::pool_bwd, false, {{"fused", 1}, {"separate", 0}, {nullptr, 0}}},
     {"dgrad", "PNVO_DGRAD", &PnvoOptions::dgrad, false, {{"phase", 1}, {"masked", 0}, {nullptr, 0}}},
     {"bf16_fuse", nullptr, &PnvoOptions::bf16_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
-    {"bf16_stem3", "PNVO_BF16_STEM3", &PnvoOptions::bf16_stem3, true, {{nullptr, 0}}},
     {"input_fallback", "PNVO_INPUT_FALLBACK", &PnvoOptions::input_fallback, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"small_net", "PNVO_SMALL_NET", &PnvoOptions::small_net, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"small_max", "PNVO_SMALL_MAX", &PnvoOptions::small_max, true, {{nullptr, 0}}},
@@ -1842,38 +1763,10 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
 }  // namespace
 
 namespace {
-// Side stream, its two events and a statistics buffer of the main one's size (lazily; nothing while `s` is being captured: a graph
-// keeps the in-stream order).
-bool side_stream_ready(pnvo_handle m, hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return false;
-  if (!m->side_stream && hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking) != hipSuccess) return false;
-  if (!m->side_fork && hipEventCreateWithFlags(&m->side_fork, hipEventDisableTiming) != hipSuccess) return false;
-  if (!m->side_join && hipEventCreateWithFlags(&m->side_join, hipEventDisableTiming) != hipSuccess) return false;
-  if (m->stats_side_floats < m->stats_floats) {
-    if (m->stats_side) (void)hipFree(m->stats_side);
-    m->stats_side = nullptr;
-    m->stats_side_floats = 0;
-    if (hipMalloc((void **)&m->stats_side, m->stats_floats * sizeof(float)) != hipSuccess) return false;
-    m->stats_side_floats = m->stats_floats;
-  }
-  return true;
-}
-
 int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, const float *sh, const int64_t *actions, float *out, hipStream_t s);
 bool fc_rows_usable(pnvo_handle m, int B);
 int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, int B, const float *comp_raw, const float *sc, const float *sh,
                 const int64_t *actions, float *out, hipStream_t s);
-
-// Stream + events of option pool_async (lazily; not while `s` is being captured: a graph keeps the fill in-stream).
-bool keys_stream_ready(pnvo_handle m, hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return false;
-  if (!m->keys_stream && hipStreamCreateWithFlags(&m->keys_stream, hipStreamNonBlocking) != hipSuccess) return false;
-  if (!m->keys_free_ev && hipEventCreateWithFlags(&m->keys_free_ev, hipEventDisableTiming) != hipSuccess) return false;
-  if (!m->keys_ready_ev && hipEventCreateWithFlags(&m->keys_ready_ev, hipEventDisableTiming) != hipSuccess) return false;
-  return true;
-}
 
 int forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
                  const int64_t *actions, int B, float *out, hipStream_t s) {
@@ -1903,8 +1796,6 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
     if ((rc = maybe_tap(m, "input", m->xin, (size_t)B * c.height * c.width * m->CP, s)) != PNVO_OK) return rc;
   }
   size_t li = 0;
-  for (auto &pd : m->gn_pend) pd.valid = false;
-  m->defer_main = m->defer_ride = false;
   const Layer &stem = m->convs[li++];
   // (a7) GN + ReLU + maxpool.  Default: no pass at all — the stem writes pooled order-preserving keys (stem_mx.hip POOL), the
   // first block's first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs
@@ -1914,8 +1805,6 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
                           stem.coutp == stem.cout && pnvo_conv_takes_tail(m, m->convs[1], B);
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
-  float *keys = nxt;             // where the pooled keys live: the ping-pong buffer, or (pool_async) a buffer of their own
-  bool keys_async = false;
   const bool small = !pool_fused && stem_writes_slots(m) && pnvo_small_usable(m, B);
   if (small) {
     const float *src[4] = {rgb, depth, dd, tdv};
@@ -1928,17 +1817,10 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   {
     const float *src[4] = {rgb, depth, dd, tdv};
     if (pool_fused) {
-      const size_t nkeys = (size_t)B * m->Hp * m->Wp * stem.coutp;
-      keys_async = m->opt.pool_async && !m->timing && m->pool_keys != nullptr && keys_stream_ready(m, s);
-      keys = keys_async ? m->pool_keys : nxt;
-      if (keys_async && m->keys_primed) HIPCHK(m, hipStreamWaitEvent(s, m->keys_ready_ev, 0));   // the fill enqueued behind the last forward
-      if (!(keys_async && m->keys_primed && m->keys_primed_B >= B)) {
-        Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
-        HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(keys), STEM_POOL_INIT, nkeys, s));
-      }
-      if (keys_async) m->keys_primed = false;
+      Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
+      HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
     }
-    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, pool_fused ? reinterpret_cast<int *>(keys) : nullptr)) !=
+    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, pool_fused ? reinterpret_cast<int *>(nxt) : nullptr)) !=
         PNVO_OK)
       return rc;
   }
@@ -1983,36 +1865,16 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
         if ((rc = maybe_tap(m, tnb.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
         continue;
       }
-      if (keys_async && !m->keys_primed && (stage >= 3 || (stage == 2 && m->nblocks[2] + m->nblocks[3] == 0))) {
-        // the keys were consumed two stages ago: their fill for the NEXT forward goes to the key stream now, next to the MFMA-bound
-        // deep stages of this one (the first stage's convs are HBM-bound themselves)
-        HIPCHK(m, hipEventRecord(m->keys_free_ev, s));
-        HIPCHK(m, hipStreamWaitEvent(m->keys_stream, m->keys_free_ev, 0));
-        HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->pool_keys), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp,
-                                    m->keys_stream));
-        HIPCHK(m, hipEventRecord(m->keys_ready_ev, m->keys_stream));
-        m->keys_primed = true;
-        m->keys_primed_B = B;
-      }
       const Layer &c1 = m->convs[li++];
       const Layer &c2 = m->convs[li++];
       const bool ds = (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos);
-      // Deferred GroupNorm finalisation (option gn_defer, launches of up to that many pairs): c1's GroupNorm is finalised by c2's
-      // launch when that is a conv_x3_kernel launch; c2's and the downsample conv's by the launch that takes this block's tail
-      const bool defer_on = m->opt.gn_defer > 0 && B <= m->opt.gn_defer && m->tap_dst == nullptr && m->train == nullptr;
-      const size_t li_next = li + (ds ? 1 : 0);
-      const bool next_takes = li_next < m->convs.size() && pnvo_conv_takes_tail(m, m->convs[li_next], B);
-      const bool c2_x3 = pnvo_conv_on_x3(m, c2, B);
-      const bool defer_c1 = defer_on && c2_x3, defer_tail = defer_on && next_takes;
       // the block's downsample conv rides on c1's launch (conv_x3_kernel DSF): no launch, no finalisation of its own, and in the
       // block-tail mode the block input is not written to HBM at all — c1 and the downsample conv are its only readers
       const bool ds_ride = ds && !have_keys && pnvo_conv_takes_ds(m, c1, m->convs[li], B);
       const DsRide ride{ds_ride ? &m->convs[li] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
-      m->defer_main = defer_c1;
-      m->defer_ride = defer_tail;
       if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
         BlockTail ktail{nullptr, nullptr, nullptr, cur};
-        if ((rc = pnvo_run_conv(m, c1, B, keys, m->ssA[0], m->ssA[1], m->rawA, c1.coutp, m->ssA, nullptr, nullptr, 0, s, nullptr, nullptr,
+        if ((rc = pnvo_run_conv(m, c1, B, nxt, m->ssA[0], m->ssA[1], m->rawA, c1.coutp, m->ssA, nullptr, nullptr, 0, s, nullptr, nullptr,
                                 nullptr, &ktail)) != PNVO_OK)
           return rc;
         have_keys = false;
@@ -2027,26 +1889,8 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
                                      nullptr, nullptr, ds_ride ? &ride : nullptr)) != PNVO_OK) {
         return rc;
       }
-      m->defer_main = m->defer_ride = false;
       const long P = (long)c2.hout * c2.wout;
       const bool c2_small_generic = !layer_on_lds(m, c2, nullptr) && !pnvo_conv_on_x3(m, c2, B) && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
-      // The block's 1x1 stride-2 downsample conv reads only the block input (written by the first conv's stager) and owns rawD / ssD:
-      // it and its GroupNorm finalisation run on a side stream NEXT TO the second 3x3 conv instead of behind it (option ds_side) —
-      // forked here, joined where the downsample used to be launched.  Its GroupNorm partials go to a buffer of their own.
-      bool ds_forked = false;
-      // (measured: 256 pairs 2.331 -> 2.305 ms; 64 pairs no change; 16 pairs +0.05 ms — the fork / join events cost what the small
-      //  launches save, so only from 128 pairs on)
-      if (ds && !ds_ride && m->opt.ds_side && B >= 128 && !c2_small_generic && !m->timing && m->tap_dst == nullptr && m->train == nullptr && side_stream_ready(m, s)) {
-        const Layer &cd = m->convs[li + 0];
-        HIPCHK(m, hipEventRecord(m->side_fork, s));
-        HIPCHK(m, hipStreamWaitEvent(m->side_stream, m->side_fork, 0));
-        std::swap(m->stats, m->stats_side);
-        rc = run_conv(m, cd, B, cur, nullptr, nullptr, m->rawD, cd.coutp, m->ssD, nullptr, nullptr, 0, m->side_stream);
-        std::swap(m->stats, m->stats_side);
-        if (rc != PNVO_OK) return rc;
-        HIPCHK(m, hipEventRecord(m->side_join, m->side_stream));
-        ds_forked = true;
-      }
       if (c2_small_generic) {
         // small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one streaming
         // pass over the (L2-sized) tensor, so normalise once and run the conv on final activations
@@ -2058,23 +1902,14 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
         }
         if ((rc = run_conv(m, c2, B, napp, nullptr, nullptr, m->rawB, c2.coutp, m->ssB, nullptr, nullptr, 0, s)) != PNVO_OK)
           return rc;
-      } else {
-        m->defer_main = defer_tail;
-        rc = run_conv(m, c2, B, m->rawA, m->ssA[0], m->ssA[1], m->rawB, c2.coutp, m->ssB, nullptr, nullptr, 0, s);
-        m->defer_main = false;
-        if (rc != PNVO_OK) return rc;
+      } else if ((rc = run_conv(m, c2, B, m->rawA, m->ssA[0], m->ssA[1], m->rawB, c2.coutp, m->ssB, nullptr, nullptr, 0, s)) != PNVO_OK) {
+        return rc;
       }
       if (ds) {
         const Layer &cd = m->convs[li++];
-        m->defer_main = defer_tail && !ds_ride && !ds_forked;          // (a downsample conv launched on its own: the same consumer)
-        if (ds_ride) {                                                 // rawD / ssD came out of c1's launch
-        } else if (ds_forked) {
-          HIPCHK(m, hipStreamWaitEvent(s, m->side_join, 0));           // rawD / ssD are complete before the block tail's consumer
-        } else if ((rc = run_conv(m, cd, B, cur, nullptr, nullptr, m->rawD, cd.coutp, m->ssD, nullptr, nullptr, 0, s)) != PNVO_OK) {
-          m->defer_main = false;
+        if (!ds_ride &&                                                // (riding: rawD / ssD came out of c1's launch)
+            (rc = run_conv(m, cd, B, cur, nullptr, nullptr, m->rawD, cd.coutp, m->ssD, nullptr, nullptr, 0, s)) != PNVO_OK)
           return rc;
-        }
-        m->defer_main = false;
       }
       // (the last block's tail rides on the compression conv when that runs on conv_x3_kernel: nobody else reads that block output)
       if (li < m->convs.size() && pnvo_conv_takes_tail(m, m->convs[li], B)) {   // relu(GN2(conv2) + skip): computed by the next conv's stager
@@ -2329,7 +2164,6 @@ int pnvo_forward_grouped_raw(const pnvo_handle *handles, const int32_t *counts, 
   m->opt.conv = 1;                 // every GroupNorm-ed conv on conv_x3_kernel (its fine plan for small launches)
   m->opt.x3_rows = 0;              // (the row-streaming and resident-weight kernels hold ONE model's weights per workgroup)
   m->opt.x3_persist = 0;
-  if (m->opt.gn_fuse == 1) m->opt.gn_fuse = 2;
   m->grp_n = ng;
   int acc = 0;
   for (int k = 0; k < ng; ++k) {
@@ -2613,16 +2447,6 @@ int pnvo_destroy(pnvo_handle m) {
   free_workspace(m);
   if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
   if (m->stem_ev) (void)hipEventDestroy(m->stem_ev);
-  if (m->keys_stream) {
-    (void)hipStreamSynchronize(m->keys_stream);
-    (void)hipStreamDestroy(m->keys_stream);
-  }
-  if (m->keys_free_ev) (void)hipEventDestroy(m->keys_free_ev);
-  if (m->keys_ready_ev) (void)hipEventDestroy(m->keys_ready_ev);
-  if (m->side_fork) (void)hipEventDestroy(m->side_fork);
-  if (m->side_join) (void)hipEventDestroy(m->side_join);
-  if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
-  if (m->stats_side) (void)hipFree(m->stats_side);
   for (Layer &l : m->convs) {
     free_dev(l.wpk);
     free_dev(reinterpret_cast<float *&>(l.wpk_x3));

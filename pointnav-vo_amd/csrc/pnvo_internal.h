@@ -170,9 +170,6 @@ struct ConvX3Args {
   int gn_cpg;                        // channels per group (divides 32)
   float gn_eps;
   long gn_P;                         // pixels per sample
-  // slots > 1 with gn_scale set: [B][gridDim.y] arrival counters (zero between launches) — the LAST tile of a sample (and N-tile
-  // group) finalises (gn_finalize_group_wave: gn_finalize_kernel's arithmetic bit for bit); nullptr with slots > 1: the launch
-  unsigned *gn_ctr;
   // The block's 1x1 stride-2 downsample conv riding on a 3x3 stride-2 launch (conv_x3_kernel<.., DSF = true>; ds_wpk == nullptr: none):
   // its float16-piece operand (pack_conv_x2_weight of the 1x1 weight), raw output [B,Ho,Wo,COUTP], partial sums (the layout of `stats`,
   // a buffer of its own), weight scale, and its GroupNorm (same groups as the conv's; scale / shift written when the conv's are)
@@ -186,22 +183,12 @@ struct ConvX3Args {
   // GROUPED forward (pnvo_forward_grouped_raw: pairs of up to three action models in one launch chain, sorted by model): sample n
   // belongs to model (n >= grp_end0) + (n >= grp_end1), an end of 0 meaning "no such model" (the structs are zero-filled); models 1 / 2
   // take their operands from [0] / [1]
-  // DEFERRED GroupNorm finalisation (round 6, option gn_defer): the producer of this conv's input skipped its gn_finalize launch; this
-  // kernel turns the producer's partial sums into the scale / shift table of ITS sample in its prologue (fin_in: the input's GroupNorm,
-  // replaces in_scale / in_shift; fin_res: the skip branch's, replaces res_scale / res_shift) — gn_finalize_kernel's arithmetic bit for
-  // bit (gn_finalize_wave16), overlapped with the first patch loads.  stats == nullptr: the tables come from memory as before.
-  struct Fin {
-    const float *stats;              // [B][slots][CIN][2] partial sums of the producer
-    int slots, cpg;
-    const float *gamma, *beta, *gamma_g[2], *beta_g[2];   // affine parameters (and those of models 1 / 2 of a grouped forward)
-  } fin_in, fin_res;
   int grp_end0, grp_end1;
   const unsigned short *wpk_g[2], *ds_wpk_g[2];
   float oscale_g[2], ds_oscale_g[2];
   const float *gn_gamma_g[2], *gn_beta_g[2], *ds_gamma_g[2], *ds_beta_g[2];
 };
 #if defined(__HIPCC__)
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // One lane = one channel of a sample, lanes of a group adjacent and aligned: GroupNorm scale / shift from the channel's complete
 // sums (s1, s2), in gn_finalize_kernel's arithmetic — fp64, the butterfly over the group's lanes in its order (the wider offsets
 // of that kernel's 64-lane butterfly add exact zeros), no a*b+c contraction (elementwise.hip is compiled without it).
@@ -226,132 +213,11 @@ __device__ __forceinline__ void gn_finalize_lane(float s1, float s2, int cpg, lo
   *scale = (float)sc;
   *shift = (float)((double)beta - mu * sc);
 }
-// ---- GroupNorm finalisation by the LAST workgroup of a sample (multi-slot layers: no finalisation launch) ------------------------
-// Every workgroup that wrote GroupNorm partial sums of sample n bumps a device-scope counter; the one that brings it to `expect`
-// knows that all partials of the sample are in memory and turns them into scale / shift — gn_finalize_kernel's arithmetic, bit for
-// bit (one wave per group: the same lane -> (slot, channel) walk, fp64, the same 64-lane butterfly), so which workgroup arrives
-// last changes nothing.  The partials cross workgroups INSIDE a launch: they are written and read with agent-scope accesses (sc1:
-// coherent across the per-XCD L2s, smallnet.hip's protocol), the counter is bumped after the writer's stores are acknowledged
-// (s_waitcnt vmcnt(0) + workgroup barrier) — no L2 write-back or invalidate.  The last arriver also clears the counter for the next launch.
-__device__ __forceinline__ void gn_stats_store(float *dst, float s1, float s2) {
-  __hip_atomic_store(reinterpret_cast<unsigned *>(dst), __builtin_bit_cast(unsigned, s1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(reinterpret_cast<unsigned *>(dst) + 1, __builtin_bit_cast(unsigned, s2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// One full wave = one (sample, group): `stats` points at the sample's [slots][CP][2] partials, ns slots are summed.
-__device__ __forceinline__ void gn_finalize_group_wave(const float *stats, int ns, int CP, int g, int cpg, long P, float eps, const float *gamma,
-                                                       const float *beta, float *scale_n, float *shift_n, float *mu_out, float *rstd_out) {
-#pragma clang fp contract(off)
-  const int lane = (int)(threadIdx.x & 63);
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = lane; k < ns * cpg; k += 64) {
-    const int slot = k / cpg, c = g * cpg + k % cpg;
-    const unsigned *src = reinterpret_cast<const unsigned *>(stats + ((long)slot * CP + c) * 2);
-    s1 += (double)__builtin_bit_cast(float, __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    s2 += (double)__builtin_bit_cast(float, __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    s1 += __shfl_xor(s1, o);
-    s2 += __shfl_xor(s2, o);
-  }
-  const double cnt = (double)P * cpg;
-  const double mu = s1 / cnt;
-  double var = s2 / cnt - mu * mu;
-  if (var < 0.0) var = 0.0;
-  const double rstd = 1.0 / sqrt(var + (double)eps);
-  if (lane == 0 && mu_out != nullptr) {
-    *mu_out = (float)mu;
-    *rstd_out = (float)rstd;
-  }
-  for (int k = lane; k < cpg; k += 64) {
-    const int c = g * cpg + k;
-    const double sc = rstd * (double)gamma[c];
-    scale_n[c] = (float)sc;
-    shift_n[c] = (float)((double)beta[c] - mu * sc);
-  }
-}
-// Arrive (whole workgroup, behind its partial-sum stores); true for every thread of the workgroup that arrived last.
-// `flag` = one int of LDS scratch the caller no longer reads.
-__device__ __forceinline__ bool gn_last_arrival(unsigned *ctr, unsigned expect, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old + 1u == expect;
-    if (last) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = last;
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-// One WAVE finalises SIXTEEN groups at once — gn_finalize_kernel's result bit for bit with four lanes per group instead of a block
-// of 64.  That kernel: lane k of 64 adds elements k, k + 64, ... (element e = (slot e / cpg, channel g cpg + e % cpg)) in fp64, then a
-// xor-butterfly over 32, 16, ..., 1 — after every step the partner lanes hold the same value, so the result is the fixed tree
-// ((x[v] + x[v ^ 32]) + ...) whatever lane reads it.  Here lane 4 g' + q holds the sixteen "virtual lanes" v = 16 q + i of group g0 + g':
-// steps 32 and 16 are xor-shuffles across the four lanes (q ^ 2, q ^ 1), steps 8 ... 1 run inside the lane.  Same operands, same
-// order (a + b == b + a), no a*b+c contraction.  Groups >= G are skipped.  scale_tab / shift_tab: the sample's tables (LDS).
-__device__ __forceinline__ void gn_finalize_wave16(const float *stats_n, int ns, int CP, int g0, int G, int cpg, long P, float eps,
-                                                   const float *gamma, const float *beta, float *scale_tab, float *shift_tab) {
-#pragma clang fp contract(off)
-  const int lane = (int)(threadIdx.x & 63), q = lane & 3, g = g0 + (lane >> 2);
-  const bool live = g < G;
-  const int ne = ns * cpg;
-  double x1[16], x2[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    x1[i] = 0.0;
-    x2[i] = 0.0;
-  }
-  if (live) {
-    for (int e0 = 0; e0 < ne; e0 += 64) {                       // (one pass whenever slots * cpg <= 64)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int e = e0 + 16 * q + i;
-        if (e < ne) {
-          const int slot = e / cpg, c = g * cpg + e % cpg;
-          const f32x2_t v = *reinterpret_cast<const f32x2_t *>(stats_n + ((long)slot * CP + c) * 2);
-          x1[i] += (double)v[0];
-          x2[i] += (double)v[1];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {                                 // butterfly steps 32 and 16: across the group's four lanes
-    x1[i] += __shfl_xor(x1[i], 2);
-    x2[i] += __shfl_xor(x2[i], 2);
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    x1[i] += __shfl_xor(x1[i], 1);
-    x2[i] += __shfl_xor(x2[i], 1);
-  }
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1)                               // steps 8, 4, 2, 1: inside the lane
-#pragma unroll
-    for (int i = 0; i < o; ++i) {
-      x1[i] += x1[i + o];
-      x2[i] += x2[i + o];
-    }
-  if (!live) return;
-  const double cnt = (double)P * cpg;
-  const double mu = x1[0] / cnt;
-  double var = x2[0] / cnt - mu * mu;
-  if (var < 0.0) var = 0.0;
-  const double rstd = 1.0 / sqrt(var + (double)eps);
-  for (int t = q; t < cpg; t += 4) {
-    const int c = g * cpg + t;
-    const double sc = rstd * (double)gamma[c];
-    scale_tab[c] = (float)sc;
-    shift_tab[c] = (float)((double)beta[c] - mu * sc);
-  }
-}
 #endif
 bool conv_x3_plan(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *lds_bytes);
 // Row-streaming form of the 32 -> 32 channel 3x3 stride-1 convs (conv_rows.hip): plan fills rs_bands / rs_rows / slots.
 bool conv_rows32_plan(ConvX3Args &a, int ks, int stride, int mode, int num_cus);
 hipError_t launch_conv_rows32(const ConvX3Args &a, int mode, int num_cus, hipStream_t s);
-bool conv_x3_persistent(const ConvX3Args &a, int ks, int stride, int mode, int mw, int nw);   // would launch_conv_x3 take conv_x3p_kernel?
 hipError_t launch_conv_x3(const ConvX3Args &a, int ks, int stride, int mode, int mw, int nw, size_t lds_bytes, hipStream_t s);
 hipError_t launch_conv_x3_repack(const float *w_oihw, int cout, int cin, int cinp, int coutp, int kh, int kw, int transposed,
                                  unsigned short *out, hipStream_t s);

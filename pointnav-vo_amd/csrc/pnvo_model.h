@@ -38,31 +38,19 @@ struct PnvoOptions {
   int pieces = 2;      // operand pieces of conv_x3 at inference: 2 float16 (three product terms) or 3 bf16 (six exact terms)
   int train_pieces = 2;  // the same choice for the TRAINING forward's convs (their backward-data convs keep three bf16 pieces:
                          //   gradients do not fit float16's range)
-  int ds_side = 0;     // (opt-in) the 1x1 stride-2 downsample conv of a block (+ its GroupNorm finalisation) on a side stream next to the block's
-                       // second 3x3 conv: -1 % at 256 pairs on a GPU of its own, but 10x slower when two processes share a GPU (the fork / join
-                       // events across time-sliced queues) — off by default
   int x3_rows = 1;     // 32 -> 32 channel 3x3 stride-1 convs on the row-streaming kernel (conv_rows.hip) where it takes the launch
   int x3_persist = 1;  // shallow-stage 3x3 convs on the persistent form of conv_x3 (next tile's patch fetched during the K loop)
   int x3_strip = 1;    // 64- / 128-channel stride-1 convs on wide strip tiles with the N-tiles split over blockIdx.y (half the weight bytes per pixel)
-  int pool_async = 0;  // pooled-key buffer of its own, re-initialised for the next forward on a side stream (see pool_keys).  OFF: measured
-                       // slower at every batch (8 pairs 0.44 -> 0.50 ms, 256 pairs 2.37 -> 2.41): the two event hand-overs cost more than the 23 us fill
-  int gn_defer = 0;    // pairs up to which multi-tile GroupNorm finalisations move into the consumer conv's prologue (0: never = default).
-                       // Round 6: bit-identical, 4-10 launches fewer per forward — and slower (8 pairs 0.427 -> 0.448 ms, 32: 0.630 -> 0.663):
-                       // a memory round trip + ~0.5 us of fp64 in EVERY consumer workgroup costs more than a 4 us launch
   int x3_fine = 1;     // small launches of the float16-piece convs take one N-tile per workgroup instead of falling back to the fp32-pipe kernels
   int x3_w8 = 1;       // 256-channel convs on 6 x 11 maps with a tile per CU or more: eight waves of (3,1) tiles per workgroup (two per SIMD) instead of four of (3,2)
   int x3_ksplit = 1;   // fine-plan conv tiles of three / four M-tiles behind >= 128 input channels: the four waves split the K walk, partial sums meet in LDS
   int fc_rows = 48;    // up to this many samples the hidden layer and the head run as fc_rows.hip's two launches (every model of a grouped forward in one)
   int head_fuse = 1;   // the output head (Linear hidden -> out_dim) is computed by the hidden layer's split-K reduction launch (one launch less)
   int ds_fuse = 1;     // the 1x1 stride-2 downsample conv rides on its block's first 3x3 conv (bit-identical raw output, one launch less, block input read once)
-  int gn_fuse = 2;     // conv_x3 launches finalise their GroupNorm themselves (bit-identical, one launch less): 2 = launches with one tile per
-                       // sample (the default, `on`); 1 = `last`: also launches with several tiles per sample, by the sample's last workgroup to
-                       // arrive (round 6: measured SLOWER at every batch — every workgroup waits for its stores and an atomic round trip
-                       // before it leaves — kept as an option and a test of the protocol); 0 = never
+  int gn_fuse = 1;     // conv_x3 launches with one tile per sample finalise their GroupNorm themselves (bit-identical, one launch less)
   int x3_s2 = 1;       // stride-2 convs on conv_x3
   int tail = 1;        // BasicBlock tails fused into the next conv's stager (0: residual_kernel)
   int pool = 1;        // max-pool fused into the stem's epilogue (0: gn_relu_maxpool_kernel)
-  int conv3_nt = 0;    // 1: one N-tile per item in conv3_lds
   int graph = 0;       // forward replayed from a captured hipGraph
   int stem_dbg = 0, stem_dbg_pad = 0;   // developer instrumentation of the stem kernels
   int wgrad_stem = 0;  // 0 bf16 matrix cores, 1 fp32
@@ -70,7 +58,6 @@ struct PnvoOptions {
   int pool_bwd = 1;    // max-pool backward fused into the stem's GroupNorm backward
   int dgrad = 1;       // stride-2 backward-data as four parity-phase convs (0: masked taps)
   int bf16_fuse = 1;   // bf16 path: block tails fused
-  int bf16_stem3 = 0;  // bf16 path: exact three-piece stem (experiment)
   int input_fallback = 1;   // contract-breaking input (fractional rgb, soft depth codes): re-run on the dense stem and stay on it
   int small_net = 1;   // batches of <= small_max pairs: everything behind the stem conv in ONE persistent launch (smallnet.hip)
   int small_max = 3;   // largest batch the persistent kernel takes (1..4; round 6: the per-layer launches with their fine plans win from 4 pairs on — 0.370 against 0.400 ms)
@@ -145,33 +132,7 @@ struct pnvo_model_s {
   PnvoOptions opt;
   bool dense_sticky = false;                 // an input outside the mx/dd stems' contract was met: this handle stays on the dense stem
   int fallback_count = 0;                    // forwards re-run on the dense stem
-  hipStream_t side_stream = nullptr;         // option ds_side: forked behind a block's first conv, joined before the block tail's consumer
-  hipEvent_t side_fork = nullptr, side_join = nullptr;
-  float *stats_side = nullptr;               // the side stream's GroupNorm partials (the main stream's conv writes m->stats meanwhile)
-  size_t stats_side_floats = 0, stats_floats = 0;
-  // option pool_async: the pooled stem keys live in a buffer of their own, and their re-initialisation for the NEXT forward (a 135 MB
-  // fill at 256 pairs, 23 us on the critical path before the stem) runs on a stream of its own behind this forward's consumer of the
-  // keys, next to the MFMA-bound deep stages; the next forward's stem waits for it through an event (no host wait)
-  float *pool_keys = nullptr;                // [cap][Hp][Wp][baseplanes] int32 keys
-  hipStream_t keys_stream = nullptr;
-  hipEvent_t keys_free_ev = nullptr, keys_ready_ev = nullptr;
-  bool keys_primed = false;                  // the fill for the next forward is enqueued (keys_ready_ev recorded behind it)
-  int keys_primed_B = 0;                     //   ... for this many pairs
-  // Deferred GroupNorm finalisation (option gn_defer, small launches): a conv_x3 producer whose consumer is a conv_x3_kernel launch
-  // leaves its partial sums un-finalised; the consumer builds its sample's scale / shift table in its prologue (ConvX3Args::fin_in /
-  // fin_res).  gn_pend[k]: what is pending behind the scale / shift pair ssA (0), ssB (1), ssD (2); defer_main / defer_ride: set by the
-  // forward around a producer's pnvo_run_conv call.
-  struct GnPend {
-    const float *stats = nullptr;
-    int slots = 0, cpg = 0;
-    size_t layer = 0;                         // index into convs (gamma / beta; the same layer of the other models of a grouped forward)
-    bool valid = false;
-  } gn_pend[3];
-  bool defer_main = false, defer_ride = false;
-  float *statsB = nullptr;                   // partial sums of the convs that write ssB (the second conv of a block): a producer's sums
-                                             // must outlive the next launch, which writes its own
   float *stats_ds = nullptr;                 // GroupNorm partials of a downsample conv riding on its block's first conv (stats_floats)
-  float *gn_ctr = nullptr;                   // [cap][16] unsigned arrival counters of the in-kernel GroupNorm finalisation (zero between launches)
   hipEvent_t stem_ev = nullptr;              // recorded behind a contract-checking stem launch (pnvo_mark_stem)
   bool stem_ev_pending = false;
   // pnvo_forward_raw / pnvo_forward_dual_raw: sensor frames of the call in flight (the stem's RAW stager reads them)

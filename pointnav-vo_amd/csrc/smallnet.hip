@@ -887,7 +887,7 @@ bool pnvo_small_usable(pnvo_handle m, int B) {
   if (!m->opt.small_net || B < 1 || B > bmax) return false;
   if (m->bottleneck || m->tap_dst != nullptr || m->train != nullptr || m->graph_mode > 0) return false;
   if (m->precision != 0) return false;
-  if (m->opt.conv != 0 || !m->opt.tail || !m->opt.pool || m->opt.conv3_nt) return false;   // an explicit kernel selection is honoured
+  if (m->opt.conv != 0 || !m->opt.tail || !m->opt.pool) return false;   // an explicit kernel selection is honoured
   SmallNet *sn = static_cast<SmallNet *>(m->small);
   if (sn && (sn->unsupported || sn->failed)) return false;
   const pnvo_config &c = m->cfg;

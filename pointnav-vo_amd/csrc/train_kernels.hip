@@ -712,12 +712,10 @@ void wgrad_plan(WgradArgs &a) {
     a.pairs = a.ci_tiles * (a.COUT / 32);
     a.tiles_x = (a.W + 23) / 24;
     a.TW = ((a.W + a.tiles_x - 1) / a.tiles_x + 1) / 2 * 2;
-    static const int th_max = std::getenv("PNVO_WGRAD_TH") ? std::atoi(std::getenv("PNVO_WGRAD_TH")) : 8;
-    static const int wg_cu = std::getenv("PNVO_WGRAD_WGS") ? std::atoi(std::getenv("PNVO_WGRAD_WGS")) : 2;
-    a.tiles_y = (a.H + th_max - 1) / th_max;
+    a.tiles_y = (a.H + 7) / 8;                        // rows of at most 8
     a.TH = (a.H + a.tiles_y - 1) / a.tiles_y;
     const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-    long chunks = 256L * wg_cu / a.pairs;             // persistent workgroups per CU
+    long chunks = 256L * 2 / a.pairs;                 // two persistent workgroups per CU
     if (chunks < 1) chunks = 1;
     if (chunks > ntiles) chunks = ntiles;
     a.tiles_per_chunk = (int)((ntiles + chunks - 1) / chunks);

@@ -3,7 +3,6 @@
 #   e.g. bash tools/knob_sweep.sh PNVO_CONV_TILE "0 11 12 21 22 14" layer4      (generic conv wave tile: 10*MT+NT)
 #        bash tools/knob_sweep.sh PNVO_WAVE_WGS "2 3 4" layer2                   (wave-private conv: workgroups per CU)
 #        bash tools/knob_sweep.sh PNVO_WAVE_NT "1 2" layer3                      (wave-private conv: n-tiles per item)
-#        bash tools/knob_sweep.sh PNVO_CONV3_WGS "1 2 3" layer1                  (workgroup-tile conv: workgroups per CU)
 var=$1; vals=$2; filt=${3:-conv}
 for v in $vals; do
   echo "$var=$v"
