@@ -278,22 +278,68 @@ void free_workspace(pnvo_model_s *m) {
   m->cap = 0;
 }
 
-// Would this (GroupNorm-ed, bias-free) conv layer run on the LDS-staged 3x3 kernel?  *slots: its statistics slots.
-bool layer_on_lds(pnvo_handle m, const Layer &l, int *slots) {
-  ConvArgs a;
+// 3x3 (stride 1 or 2, pad 1) GroupNorm-ed convs run on conv_x3.hip unless option `conv` selects another kernel family
+bool x3_layer(pnvo_handle m, const Layer &l) {
+  const bool s2 = l.stride == 2 && m->opt.x3_s2;
+  const bool k3 = l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || s2);
+  const bool k1 = l.k == 1 && l.kw == 1 && l.pad == 0 && s2;      // the 1x1 stride-2 downsample convs (resnet.py:192-195)
+  return (k3 || k1) && !l.host_w.empty() && m->opt.conv <= 1;
+}
+// operand pieces of conv_x3: two float16 pieces (three product terms) when the layer's input is provably inside float16's range and
+// option pieces (train_pieces with a training step attached, whose device-side re-pack needs the weight's scale) asks for them;
+// three bf16 pieces (six exact terms) otherwise
+bool x3_two_pieces(pnvo_handle m, const Layer &l) {
+  if (m->bottleneck || !(l.in_bound < 6.0e4f)) return false;
+  if (m->train != nullptr)             // a training step is attached: operands are rebuilt on the device from the flat parameters
+    return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l.name + ".weight") != nullptr;
+  return m->opt.pieces == 2;
+}
+// The conv_x3 arguments of layer l at B samples before their plan: shape, operand pieces and handle m's plan options.
+void x3_fill(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa) {
+  std::memset(&xa, 0, sizeof(xa));
+  xa.force = m->opt.conv == 1;
+  xa.strip = m->opt.x3_strip;
+  xa.fine = m->opt.x3_fine;
+  xa.w8_ok = m->opt.x3_w8;
+  xa.ksw_ok = m->opt.x3_ksplit;
+  xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
+  xa.np = x3_two_pieces(m, l) ? 2 : 3;
+  xa.B = B;
+  xa.H = l.hin;
+  xa.W = l.win;
+  xa.CIN = l.cinp;
+  xa.Ho = l.hout;
+  xa.Wo = l.wout;
+  xa.COUTP = l.coutp;
+}
+bool x3_args(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa, int *mw, int *nw, size_t *ldsb) {
+  x3_fill(m, l, B, xa);
+  return conv_x3_plan(xa, l.k, l.stride, mw, nw, ldsb);
+}
+
+// The implicit-GEMM geometry of layer l at B samples, the rest of the launch zero.
+void conv_geometry(const Layer &l, int B, int y_cstride, ConvArgs &a) {
   std::memset(&a, 0, sizeof(a));
+  a.B = B;
+  a.H = l.hin;
+  a.W = l.win;
+  a.CIN = l.cinp;
+  a.Ho = l.hout;
+  a.Wo = l.wout;
+  a.COUT = l.cout;
+  a.COUTP = l.coutp;
   a.KH = l.k;
   a.KW = l.kw;
   a.stride = l.stride;
   a.pad = l.pad;
+  a.y_cstride = y_cstride;
   a.up = 1;
-  a.CIN = l.cinp;
-  a.COUTP = l.coutp;
-  a.H = l.hin;
-  a.W = l.win;
-  a.Ho = l.hout;
-  a.Wo = l.wout;
-  a.y_cstride = l.coutp;
+}
+
+// Would this (GroupNorm-ed, bias-free) conv layer run on the LDS-staged 3x3 kernel?  *slots: its statistics slots.
+bool layer_on_lds(pnvo_handle m, const Layer &l, int *slots) {
+  ConvArgs a;
+  conv_geometry(l, 0, l.coutp, a);
   if (!conv3_lds_supported(a) || m->opt.conv == 3) return false;
   if (slots) *slots = conv3_lds_slots(a);
   return true;
@@ -307,15 +353,8 @@ size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
   if (layer_on_lds(m, l, &s2) && s2 > slots) slots = s2;            // conv3_lds: slots = tiles x waves
   if ((l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || l.stride == 2)) || (l.k == 1 && l.stride == 2)) {   // conv_x3: slots = tiles
     ConvX3Args xa;
-    std::memset(&xa, 0, sizeof(xa));
-    xa.B = B;
-    xa.H = l.hin;
-    xa.W = l.win;
-    xa.CIN = l.cinp;
-    xa.Ho = l.hout;
-    xa.Wo = l.wout;
-    xa.COUTP = l.coutp;
-    xa.force = 1;                       // (sized for the forced plan: options may change between forwards)
+    x3_fill(m, l, B, xa);
+    xa.force = 1;                       // (sized for the forced plan: option conv may change between forwards)
     int mw, nw;
     size_t ldsb;
     if (conv_x3_plan(xa, l.k, l.stride, &mw, &nw, &ldsb) && xa.slots > slots) slots = xa.slots;
@@ -469,40 +508,6 @@ void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &
   if (li < h->convs.size()) h->convs[li].in_bound = bin;      // the compression conv reads the last block's output
 }
 
-namespace {
-// 3x3 (stride 1 or 2, pad 1) GroupNorm-ed convs run on conv_x3.hip unless option `conv` selects another kernel family
-bool x3_layer(pnvo_handle m, const Layer &l) {
-  const bool s2 = l.stride == 2 && m->opt.x3_s2;
-  const bool k3 = l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || s2);
-  const bool k1 = l.k == 1 && l.kw == 1 && l.pad == 0 && s2;      // the 1x1 stride-2 downsample convs (resnet.py:192-195)
-  return (k3 || k1) && !l.host_w.empty() && m->opt.conv <= 1;
-}
-bool x3_two_pieces(pnvo_handle m, const Layer &l) {
-  if (m->bottleneck || !(l.in_bound < 6.0e4f)) return false;
-  if (m->train != nullptr)             // a training step is attached: operands are rebuilt on the device from the flat parameters
-    return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l.name + ".weight") != nullptr;
-  return m->opt.pieces == 2;
-}
-bool x3_args(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa, int *mw, int *nw, size_t *ldsb) {
-  std::memset(&xa, 0, sizeof(xa));
-  xa.force = m->opt.conv == 1;
-    xa.strip = m->opt.x3_strip;
-    xa.fine = m->opt.x3_fine;
-    xa.w8_ok = m->opt.x3_w8;
-    xa.ksw_ok = m->opt.x3_ksplit;
-  xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
-  xa.np = x3_two_pieces(m, l) ? 2 : 3;
-  xa.B = B;
-  xa.H = l.hin;
-  xa.W = l.win;
-  xa.CIN = l.cinp;
-  xa.Ho = l.hout;
-  xa.Wo = l.wout;
-  xa.COUTP = l.coutp;
-  return conv_x3_plan(xa, l.k, l.stride, mw, nw, ldsb);
-}
-}  // namespace
-
 bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B) {
   if (!x3_layer(m, l) || l.groups <= 0) return false;
   ConvX3Args xa;
@@ -512,10 +517,10 @@ bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B) {
 }
 
 // The block's downsample conv rides on its first 3x3 conv when both run on the float16-piece form of conv_x3_kernel and share the
-// output geometry (they always do: resnet.py:189-212), at inference (a training forward keeps the block input for its backward pass
-// and its own launch schedule), and not while a tap wants the plain schedule.
+// output geometry (they always do: resnet.py:189-212), in the inference and the training forward alike (the training forward still
+// writes the block input: its backward pass reads it), and not while a tap wants the plain schedule.
 bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B) {
-  if (!m->opt.ds_fuse || m->tap_dst != nullptr || m->in_train_forward || m->bottleneck) return false;
+  if (!m->opt.ds_fuse || m->tap_dst != nullptr || m->bottleneck) return false;
   if (c1.k != 3 || c1.kw != 3 || c1.stride != 2 || c1.pad != 1 || cd.k != 1 || cd.kw != 1 || cd.stride != 2 || cd.pad != 0) return false;
   if (c1.cinp != cd.cinp || c1.coutp != cd.coutp || c1.cout != cd.cout || c1.hout != cd.hout || c1.wout != cd.wout || c1.hin != cd.hin ||
       c1.win != cd.win || c1.cout != c1.coutp || c1.groups != cd.groups || c1.groups <= 0 || cd.host_w.empty())
@@ -529,13 +534,161 @@ bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
   return pnvo_conv_on_x3(m, l, B);
 }
 
-// One conv + (optionally) the GroupNorm statistics finalisation that follows it.
-int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const float *in_scale, const float *in_shift,
-                  float *y, int y_cstride, float *ss[2], const float *bias, const int64_t *bias_row, int relu_out,
-                  hipStream_t s, const float *const *src, float *mu_out, float *rstd_out, const BlockTail *tail, const DsRide *ride) {
+namespace {
+// launch timing of a conv of l at B samples: algorithmic flops and bytes
+double conv_flops(const Layer &l, int B) { return 2.0 * ((double)((long)B * l.hout * l.wout) * l.cout * l.cin * l.k * l.kw); }
+double conv_bytes(const Layer &l, int B) {
+  return 4.0 * ((double)B * l.hin * l.win * l.cin + (double)((long)B * l.hout * l.wout) * l.cout + (double)l.cout * l.cin * l.k * l.kw);
+}
+
+// The conv_x3 weight operand of layer q of handle h in `pieces` pieces (2: float16 and the inverse of their scale, 3: bf16), rebuilt
+// when h's weights moved since it was made: re-packed on the device from the flat parameters of an attached training step (weight
+// and float16 scale live there: pnvo_train_refresh), else packed on the host and uploaded.
+int x3_operand(pnvo_handle h, Layer &q, int pieces, hipStream_t s) {
+  unsigned short *&wpk = pieces == 2 ? q.wpk_x2 : q.wpk_x3;
+  unsigned long long &gen = pieces == 2 ? q.x2_gen : q.x3_gen;
+  if (wpk && gen == h->weights_gen) return PNVO_OK;
+  const size_t nel = (size_t)q.k * q.kw * q.cinp * q.coutp * pieces;
+  if (!wpk) HIPCHK(h, hipMalloc((void **)&wpk, nel * 2));
+  const float *dev_w = h->train ? pnvo_train_weight_ptr(h, q.name + ".weight") : nullptr;
+  if (dev_w != nullptr && pieces == 2) {
+    HIPCHK(h, launch_conv_x2_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pnvo_train_x2_scale(h, q.name + ".weight"), wpk, s));
+  } else if (dev_w != nullptr) {
+    HIPCHK(h, launch_conv_x3_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, 0, wpk, s));
+  } else {
+    std::vector<unsigned short> pk(nel);
+    if (pieces == 2)
+      q.x2_oscale = pack_conv_x2_weight(q.host_w.data(), q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pk.data());
+    else
+      pack_conv_x3_weight(q.host_w.data(), q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pk.data());
+    HIPCHK(h, hipMemcpyAsync(wpk, pk.data(), nel * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  gen = h->weights_gen;
+  return PNVO_OK;
+}
+
+// conv_x3_kernel, or conv_rows32_kernel (rows), on the plan pnvo_run_conv made in xa, + the GroupNorm finalisation unless the conv does it.
+int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, ConvX3Args &xa, bool rows, int x3_mode, int mw, int nw,
+                size_t ldsb) {
+  hipStream_t s = r.s;
+  const DsRide *ride = r.ride;
+  const bool two = xa.np == 2;
+  Layer &lm = const_cast<Layer &>(l);
+  if (int rc = x3_operand(m, lm, xa.np, s)) return rc;
+  if (ride != nullptr) {             // the block's downsample conv on this launch (pnvo_conv_takes_ds said yes)
+    if (rows || !two || l.stride != 2 || l.k != 3) return fail(m, PNVO_ERR_STATE, "downsample ride on a conv that cannot carry it (" + l.name + ")");
+    Layer &dm = const_cast<Layer &>(*ride->cd);
+    if (int rc = x3_operand(m, dm, 2, s)) return rc;
+    xa.ds_wpk = dm.wpk_x2;
+    xa.ds_oscale = dm.x2_oscale;
+    if (m->train != nullptr) {
+      const float *sp = pnvo_train_x2_scale(m, dm.name + ".weight");
+      xa.ds_oscale_ptr = sp ? sp + 1 : nullptr;
+    }
+    xa.ds_y = ride->y;
+    xa.ds_stats = m->stats_ds;
+  }
+  GnGroup gg{0x7fffffff, 0x7fffffff, {nullptr, nullptr}, {nullptr, nullptr}}, ggd = gg;   // grouped forward: models 1 / 2 of this layer
+  if (r.grp != nullptr) {
+    const GroupedFwd &g = *r.grp;
+    if (!two || rows) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " is not on the float16-piece tile kernel");
+    const size_t idx = (size_t)(&l - m->convs.data());
+    if (idx >= m->convs.size()) return fail(m, PNVO_ERR_STATE, "grouped forward: layer outside the conv list");
+    xa.grp_end0 = g.end[0];
+    xa.grp_end1 = g.n > 2 ? g.end[1] : 0;
+    gg.end0 = ggd.end0 = g.end[0];
+    if (g.n > 2) gg.end1 = ggd.end1 = g.end[1];
+    for (int k = 1; k < g.n; ++k) {
+      pnvo_handle hk = g.h[k];
+      Layer &lk = hk->convs[idx];
+      if (!x3_two_pieces(hk, lk)) return fail(m, PNVO_ERR_STATE, "grouped forward: a model's " + l.name + " left the float16-piece form");
+      if (int rc = x3_operand(hk, lk, 2, s)) return fail(m, rc, hk->err);
+      xa.wpk_g[k - 1] = lk.wpk_x2;
+      xa.oscale_g[k - 1] = lk.x2_oscale;
+      xa.gn_gamma_g[k - 1] = gg.gamma[k - 1] = lk.gamma;
+      xa.gn_beta_g[k - 1] = gg.beta[k - 1] = lk.beta;
+      if (ride != nullptr) {
+        const size_t idd = (size_t)(ride->cd - m->convs.data());
+        Layer &dk = hk->convs[idd];
+        if (!x3_two_pieces(hk, dk)) return fail(m, PNVO_ERR_STATE, "grouped forward: a model's downsample conv left the float16-piece form");
+        if (int rc = x3_operand(hk, dk, 2, s)) return fail(m, rc, hk->err);
+        xa.ds_wpk_g[k - 1] = dk.wpk_x2;
+        xa.ds_oscale_g[k - 1] = dk.x2_oscale;
+        xa.ds_gamma_g[k - 1] = ggd.gamma[k - 1] = dk.gamma;
+        xa.ds_beta_g[k - 1] = ggd.beta[k - 1] = dk.beta;
+      }
+    }
+  }
+  xa.x = r.x;
+  xa.wpk = two ? lm.wpk_x2 : lm.wpk_x3;
+  xa.oscale = lm.x2_oscale;
+  if (two && m->train != nullptr) {
+    const float *sp = pnvo_train_x2_scale(m, l.name + ".weight");
+    xa.oscale_ptr = sp ? sp + 1 : nullptr;
+  }
+  xa.y = r.y;
+  xa.in_scale = r.in_scale;
+  xa.in_shift = r.in_shift;
+  xa.stats = m->stats;
+  if (r.tail != nullptr) {           // (its skip branch is in xa already: pnvo_run_conv)
+    if (r.in_scale == nullptr) return fail(m, PNVO_ERR_STATE, "block tail without the conv's GroupNorm scale/shift");
+    xa.xout = r.tail->out;
+  }
+  // one tile per sample (the 12 x 22 and 6 x 11 maps): the workgroup that sums a sample's channels also turns the sums into the
+  // GroupNorm scale / shift — the same fp64 arithmetic as gn_finalize_kernel, bit for bit, one launch less (option gn_fuse)
+  const long P = (long)l.hout * l.wout;
+  const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
+  const bool fuse = m->opt.gn_fuse && xa.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 &&
+                    32 % cpg == 0 && l.cout % cpg == 0 && (rows || !(xa.persist_wgs > 0 && l.cin == 32 && l.coutp == 32));
+  if (fuse && ride != nullptr) {
+    xa.ds_gamma = ride->cd->gamma;
+    xa.ds_beta = ride->cd->beta;
+    xa.ds_scale = ride->ss[0];
+    xa.ds_shift = ride->ss[1];
+    xa.ds_mu = ride->mu;
+    xa.ds_rstd = ride->rstd;
+  }
+  if (fuse) {
+    xa.gn_gamma = l.gamma;
+    xa.gn_beta = l.beta;
+    xa.gn_scale = r.ss[0];
+    xa.gn_shift = r.ss[1];
+    xa.gn_mu = r.mu;
+    xa.gn_rstd = r.rstd;
+    xa.gn_cpg = cpg;
+    xa.gn_eps = 1e-5f;
+    xa.gn_P = P;
+  }
+  {
+    Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B) + (r.tail ? 8.0 * B * l.hin * l.win * l.cin : 0.0));
+    if (rows)
+      HIPCHK(m, launch_conv_rows32(xa, x3_mode, m->num_cus, s));
+    else
+      HIPCHK(m, launch_conv_x3(xa, l.k, l.stride, x3_mode, mw, nw, ldsb, s));
+  }
+  if (fuse) return PNVO_OK;
+  Timed t(m, s, "gn_finalize", 0.0, 0.0);
+  if (ride != nullptr) {             // the conv's GroupNorm and the riding downsample conv's in one launch
+    const float *st2[2] = {m->stats, m->stats_ds}, *ga2[2] = {l.gamma, ride->cd->gamma}, *be2[2] = {l.beta, ride->cd->beta};
+    float *sc2[2] = {r.ss[0], ride->ss[0]}, *sh2[2] = {r.ss[1], ride->ss[1]};
+    float *mu2[2] = {r.mu, ride->mu}, *rs2[2] = {r.rstd, ride->rstd};
+    HIPCHK(m, launch_gn_finalize_pair(st2, B, xa.slots, l.coutp, l.cout, l.groups, P, ga2, be2, 1e-5f, sc2, sh2, mu2, rs2, s,
+                                      r.grp ? &gg : nullptr, r.grp ? &ggd : nullptr));
+    return PNVO_OK;
+  }
+  HIPCHK(m, launch_gn_finalize(m->stats, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0], r.ss[1], s,
+                               xa.slots, r.mu, r.rstd, r.grp ? &gg : nullptr));
+  return PNVO_OK;
+}
+
+// The float32-MFMA kernels: the LDS-staged 3x3 conv, else the generic implicit GEMM — linear layers split the reduction when the
+// output tiles alone cannot fill the chip, and the output head may ride on that reduction.
+int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+  hipStream_t s = r.s;
   ConvArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (src != nullptr) {          // fused stem: gather A from the observation tensors
+  conv_geometry(l, B, r.y_cstride, a);
+  if (r.src != nullptr) {        // fused stem: gather A from the observation tensors
     const int nsrc[4] = {m->cfg.n_rgb, m->cfg.n_depth, m->cfg.n_dd, m->cfg.n_tdv};
     a.src_mode = 1;
     a.zero_page = m->zero_page;
@@ -545,243 +698,43 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
           const int nc = 8 * j + 4 * hh + 2 * q;
           const int tn = m->stem_tensor_of_new[nc];
           SrcPiece &pc = a.pieces[j][hh][q];
-          pc.base = tn >= 0 ? src[tn] : nullptr;
+          pc.base = tn >= 0 ? r.src[tn] : nullptr;
           pc.nch = tn >= 0 ? nsrc[tn] : 0;
           pc.choff = m->stem_ch_of_new[nc];
         }
   }
-  a.x = x;
+  a.x = r.x;
   a.wpk = l.wpk;
-  a.y = y;
-  a.in_scale = in_scale;
-  a.in_shift = in_shift;
-  a.stats = ss ? m->stats : nullptr;
-  a.bias = bias;
-  a.bias_row = bias_row;
-  a.B = B;
-  a.H = l.hin;
-  a.W = l.win;
-  a.CIN = l.cinp;
-  a.Ho = l.hout;
-  a.Wo = l.wout;
-  a.COUT = l.cout;
-  a.COUTP = l.coutp;
-  a.KH = l.k;
-  a.KW = l.kw;
-  a.stride = l.stride;
-  a.pad = l.pad;
-  a.y_cstride = y_cstride;
-  a.relu_out = relu_out;
-  a.up = 1;
+  a.y = r.y;
+  a.in_scale = r.in_scale;
+  a.in_shift = r.in_shift;
+  a.stats = r.ss ? m->stats : nullptr;
+  a.bias = r.bias;
+  a.bias_row = r.bias_row;
+  a.relu_out = r.relu_out;
   const long P = (long)l.hout * l.wout, M = (long)B * P;
   choose_tile(M, l.coutp, &a.MT, &a.NT);
   a.slots = conv_slots((int)P, a.MT);
-  const double macs = (double)M * l.cout * l.cin * l.k * l.kw;
-  const double bytes = 4.0 * ((double)B * l.hin * l.win * l.cin + (double)M * l.cout + (double)l.cout * l.cin * l.k * l.kw);
-  // 3x3 stride-1 convs with GroupNorm: float32 results from the bf16 matrix cores (three-piece operands, conv_x3.hip);
-  // option conv=fp32 keeps the fp32-MFMA kernels.  Also in the training forward (the three-piece operand is rebuilt on the
-  // device after every optimiser step); not with a fused stem source, bias or output ReLU.
-  if (ss && src == nullptr && bias == nullptr && !relu_out && y_cstride == l.coutp && x3_layer(m, l)) {
-    ConvX3Args xa;
-    std::memset(&xa, 0, sizeof(xa));
-    xa.force = m->opt.conv == 1;
-    xa.strip = m->opt.x3_strip;
-    xa.fine = m->opt.x3_fine;
-    xa.w8_ok = m->opt.x3_w8;
-    xa.ksw_ok = m->opt.x3_ksplit;
-    xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
-    xa.B = B;
-    xa.H = l.hin;
-    xa.W = l.win;
-    xa.CIN = l.cinp;
-    xa.Ho = l.hout;
-    xa.Wo = l.wout;
-    xa.COUTP = l.coutp;
-    int mw = 0, nw = 0;
-    size_t ldsb = 0;
-    // operand pieces: two float16 pieces (three product terms) at inference when the layer's input is provably inside float16's
-    // range; three bf16 pieces (six exact terms) otherwise, on request (option pieces=3) and whenever a training step is attached
-    // (its device-side re-pack builds the three-piece operand from the flat parameters)
-    const bool two = x3_two_pieces(m, l);
-    xa.np = two ? 2 : 3;
-    const int x3_mode = tail ? (tail->res ? 2 : 3) : (in_scale ? 1 : 0);
-    // 32 -> 32 channels (layer1): the row-streaming kernel (conv_rows.hip) where it takes the launch — fewer statistics slots than
-    // the tile plan the buffer is sized for (stats_floats)
-    // (the plan refuses a block tail whose skip branch carries its own GroupNorm — a downsample skip, reachable with baseplanes 16:
-    //  the rows kernel adds the raw skip tensor — so the tail's fields are in place BEFORE the plan looks at them)
-    if (tail != nullptr) {
-      xa.res = tail->res;
-      xa.res_scale = tail->res_scale;
-      xa.res_shift = tail->res_shift;
-    }
-    const bool rows = two && m->opt.x3_rows && conv_rows32_plan(xa, l.k, l.stride, x3_mode, m->num_cus);
-    if (rows || conv_x3_plan(xa, l.k, l.stride, &mw, &nw, &ldsb)) {     // (the statistics buffer is sized for it: stats_floats)
-      Layer &lm = const_cast<Layer &>(l);
-      auto ensure_x2 = [&](Layer &q, pnvo_handle hq = nullptr) -> int {   // (re)build the two-piece float16 operand of a layer (of handle hq)
-        if (hq == nullptr) hq = m;
-        if (q.wpk_x2 && q.x2_gen == hq->weights_gen) return PNVO_OK;
-        const size_t nel = (size_t)q.k * q.kw * q.cinp * q.coutp * 2;
-        if (!q.wpk_x2) HIPCHK(m, hipMalloc((void **)&q.wpk_x2, nel * 2));
-        const float *dev_w = hq->train ? pnvo_train_weight_ptr(hq, q.name + ".weight") : nullptr;
-        if (dev_w != nullptr) {          // training attached: weight and scale live on the device (pnvo_train_refresh)
-          HIPCHK(m, launch_conv_x2_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pnvo_train_x2_scale(hq, q.name + ".weight"),
-                                          q.wpk_x2, s));
-        } else {
-          std::vector<unsigned short> pk(nel);
-          q.x2_oscale = pack_conv_x2_weight(q.host_w.data(), q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pk.data());
-          HIPCHK(m, hipMemcpyAsync(q.wpk_x2, pk.data(), nel * 2, hipMemcpyHostToDevice, s));
-          HIPCHK(m, hipStreamSynchronize(s));
-        }
-        q.x2_gen = hq->weights_gen;
-        return PNVO_OK;
-      };
-      if (two) {
-        if (int rc2 = ensure_x2(lm)) return rc2;
-      }
-      if (ride != nullptr) {             // the block's downsample conv on this launch (pnvo_conv_takes_ds said yes)
-        if (rows || !two || l.stride != 2 || l.k != 3) return fail(m, PNVO_ERR_STATE, "downsample ride on a conv that cannot carry it (" + l.name + ")");
-        Layer &dm = const_cast<Layer &>(*ride->cd);
-        if (int rc2 = ensure_x2(dm)) return rc2;
-        xa.ds_wpk = dm.wpk_x2;
-        xa.ds_oscale = dm.x2_oscale;
-        if (m->train != nullptr) {
-          const float *sp = pnvo_train_x2_scale(m, dm.name + ".weight");
-          xa.ds_oscale_ptr = sp ? sp + 1 : nullptr;
-        }
-        xa.ds_y = ride->y;
-        xa.ds_stats = m->stats_ds;
-      }
-      if (!two && (!lm.wpk_x3 || lm.x3_gen != m->weights_gen)) {   // (re)build the three-piece operand of this layer
-        const size_t nel = (size_t)l.k * l.kw * l.cinp * l.coutp * 3;
-        if (!lm.wpk_x3) HIPCHK(m, hipMalloc((void **)&lm.wpk_x3, nel * 2));
-        const float *dev_w = m->train ? pnvo_train_weight_ptr(m, l.name + ".weight") : nullptr;
-        if (dev_w != nullptr) {          // training attached: the current weight lives in the flat parameter buffer
-          HIPCHK(m, launch_conv_x3_repack(dev_w, l.cout, l.cin, l.cinp, l.coutp, l.k, l.kw, 0, lm.wpk_x3, s));
-        } else {
-          std::vector<unsigned short> pk(nel);
-          pack_conv_x3_weight(l.host_w.data(), l.cout, l.cin, l.cinp, l.coutp, l.k, l.kw, pk.data());
-          HIPCHK(m, hipMemcpyAsync(lm.wpk_x3, pk.data(), nel * 2, hipMemcpyHostToDevice, s));
-          HIPCHK(m, hipStreamSynchronize(s));
-        }
-        lm.x3_gen = m->weights_gen;
-      }
-      GnGroup gg{0x7fffffff, 0x7fffffff, {nullptr, nullptr}, {nullptr, nullptr}}, ggd = gg;   // grouped forward: models 1 / 2 of this layer
-      if (m->grp_n > 1) {
-        if (!two || rows) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " is not on the float16-piece tile kernel");
-        const size_t idx = (size_t)(&l - m->convs.data());
-        if (idx >= m->convs.size()) return fail(m, PNVO_ERR_STATE, "grouped forward: layer outside the conv list");
-        xa.grp_end0 = m->grp_end[0];
-        xa.grp_end1 = m->grp_n > 2 ? m->grp_end[1] : 0;
-        gg.end0 = ggd.end0 = m->grp_end[0];
-        if (m->grp_n > 2) gg.end1 = ggd.end1 = m->grp_end[1];
-        for (int k = 1; k < m->grp_n; ++k) {
-          pnvo_handle hk = m->grp[k];
-          Layer &lk = hk->convs[idx];
-          if (!x3_two_pieces(hk, lk)) return fail(m, PNVO_ERR_STATE, "grouped forward: a model's " + l.name + " left the float16-piece form");
-          if (int rc2 = ensure_x2(lk, hk)) return rc2;
-          xa.wpk_g[k - 1] = lk.wpk_x2;
-          xa.oscale_g[k - 1] = lk.x2_oscale;
-          xa.gn_gamma_g[k - 1] = gg.gamma[k - 1] = lk.gamma;
-          xa.gn_beta_g[k - 1] = gg.beta[k - 1] = lk.beta;
-          if (ride != nullptr) {
-            const size_t idd = (size_t)(ride->cd - m->convs.data());
-            Layer &dk = hk->convs[idd];
-            if (!x3_two_pieces(hk, dk)) return fail(m, PNVO_ERR_STATE, "grouped forward: a model's downsample conv left the float16-piece form");
-            if (int rc2 = ensure_x2(dk, hk)) return rc2;
-            xa.ds_wpk_g[k - 1] = dk.wpk_x2;
-            xa.ds_oscale_g[k - 1] = dk.x2_oscale;
-            xa.ds_gamma_g[k - 1] = ggd.gamma[k - 1] = dk.gamma;
-            xa.ds_beta_g[k - 1] = ggd.beta[k - 1] = dk.beta;
-          }
-        }
-      }
-      xa.x = x;
-      xa.wpk = two ? lm.wpk_x2 : lm.wpk_x3;
-      xa.oscale = lm.x2_oscale;
-      if (two && m->train != nullptr) {
-        const float *sp = pnvo_train_x2_scale(m, l.name + ".weight");
-        xa.oscale_ptr = sp ? sp + 1 : nullptr;
-      }
-      xa.y = y;
-      xa.in_scale = in_scale;
-      xa.in_shift = in_shift;
-      xa.stats = m->stats;
-      if (tail != nullptr) {
-        if (in_scale == nullptr) return fail(m, PNVO_ERR_STATE, "block tail without the conv's GroupNorm scale/shift");
-        xa.res = tail->res;
-        xa.res_scale = tail->res_scale;
-        xa.res_shift = tail->res_shift;
-        xa.xout = tail->out;
-      }
-      // one tile per sample (the 12 x 22 and 6 x 11 maps): the workgroup that sums a sample's channels also turns the sums into the
-      // GroupNorm scale / shift — the same fp64 arithmetic as gn_finalize_kernel, bit for bit, one launch less (option gn_fuse)
-      const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
-      const bool fuse = m->opt.gn_fuse && xa.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 &&
-                        32 % cpg == 0 && l.cout % cpg == 0 && (rows || !(xa.persist_wgs > 0 && l.cin == 32 && l.coutp == 32));
-      if (fuse && ride != nullptr) {
-        xa.ds_gamma = ride->cd->gamma;
-        xa.ds_beta = ride->cd->beta;
-        xa.ds_scale = ride->ss[0];
-        xa.ds_shift = ride->ss[1];
-        xa.ds_mu = ride->mu;
-        xa.ds_rstd = ride->rstd;
-      }
-      if (fuse) {
-        xa.gn_gamma = l.gamma;
-        xa.gn_beta = l.beta;
-        xa.gn_scale = ss[0];
-        xa.gn_shift = ss[1];
-        xa.gn_mu = mu_out;
-        xa.gn_rstd = rstd_out;
-        xa.gn_cpg = cpg;
-        xa.gn_eps = 1e-5f;
-        xa.gn_P = P;
-      }
-      {
-        Timed t(m, s, "conv:" + l.name, 2.0 * macs, bytes + (tail ? 8.0 * B * l.hin * l.win * l.cin : 0.0));
-        if (rows)
-          HIPCHK(m, launch_conv_rows32(xa, x3_mode, m->num_cus, s));
-        else
-          HIPCHK(m, launch_conv_x3(xa, l.k, l.stride, x3_mode, mw, nw, ldsb, s));
-      }
-      if (fuse) return PNVO_OK;
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      if (ride != nullptr) {             // the conv's GroupNorm and the riding downsample conv's in one launch
-        const float *st2[2] = {m->stats, m->stats_ds}, *ga2[2] = {l.gamma, ride->cd->gamma}, *be2[2] = {l.beta, ride->cd->beta};
-        float *sc2[2] = {ss[0], ride->ss[0]}, *sh2[2] = {ss[1], ride->ss[1]};
-        float *mu2[2] = {mu_out, ride->mu}, *rs2[2] = {rstd_out, ride->rstd};
-        HIPCHK(m, launch_gn_finalize_pair(st2, B, xa.slots, l.coutp, l.cout, l.groups, P, ga2, be2, 1e-5f, sc2, sh2, mu2, rs2, s,
-                                          m->grp_n > 1 ? &gg : nullptr, m->grp_n > 1 ? &ggd : nullptr));
-        return PNVO_OK;
-      }
-      HIPCHK(m, launch_gn_finalize(m->stats, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, ss[0], ss[1], s,
-                                   xa.slots, mu_out, rstd_out, m->grp_n > 1 ? &gg : nullptr));
-      return PNVO_OK;
-    }
-  }
-  if (tail != nullptr) return fail(m, PNVO_ERR_STATE, "block tail handed to a conv that cannot take it (" + l.name + ")");
-  if (m->grp_n > 1 && ss != nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " fell off the float16-piece tile kernel");
-  const bool lds3 = conv3_lds_supported(a) && m->opt.conv != 3;
-  if (lds3) {                    // 3x3 stride-1 residual-stage conv: input patch staged in LDS
+  if (conv3_lds_supported(a) && m->opt.conv != 3) {   // 3x3 stride-1 residual-stage conv: input patch staged in LDS
     const int nt = (l.coutp / 32) % 2 == 0 ? 2 : 1;
     a.slots = conv3_lds_slots(a);
     {
-      Timed t(m, s, "conv:" + l.name, 2.0 * macs, bytes);
+      Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
       HIPCHK(m, launch_conv3_lds(a, nt, s));
     }
-    if (ss) {
+    if (r.ss) {
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, ss[0],
-                                   ss[1], s, a.slots, mu_out, rstd_out));
+      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0],
+                                   r.ss[1], s, a.slots, r.mu, r.rstd));
     }
     return PNVO_OK;
   }
-  if (bias != nullptr && !ss) {  // linear layer: split the reduction when the output tiles alone cannot fill the chip
+  if (r.bias != nullptr && !r.ss) {  // linear layer: split the reduction when the output tiles alone cannot fill the chip
     a.kpart = reinterpret_cast<float *>(8);          // non-null: "scratch available" for the query
     const int ks = conv_ksplit(a);
     a.kpart = nullptr;
     if (ks > 1) {
-      const size_t need = (size_t)ks * M * y_cstride;
+      const size_t need = (size_t)ks * M * r.y_cstride;
       if (need > m->kpart_floats) {
         pnvo_drop_graphs(m);                         // captured launches point into the old scratch
         if (m->kpart) (void)hipFree(m->kpart);
@@ -795,30 +748,48 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const fl
     }
   }
   {
-    Timed t(m, s, "conv:" + l.name, 2.0 * macs, bytes);
+    Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
     HIPCHK(m, launch_conv(a, s));
-    if (a.ksplit > 1 && m->head_ride_out != nullptr && P == 1 && y_cstride == l.cout) {   // the output head on the reduction launch
-      HIPCHK(m, launch_ksplit_reduce_head(a, m->head_ride_w, m->head_bias, m->cfg.out_dim, m->head_ride_out, s));
-      m->head_rode = true;
+    if (a.ksplit > 1 && r.head_out != nullptr && P == 1 && r.y_cstride == l.cout) {   // the output head on the reduction launch
+      HIPCHK(m, launch_ksplit_reduce_head(a, r.head_w, m->head_bias, m->cfg.out_dim, r.head_out, s));
+      if (r.head_rode != nullptr) *r.head_rode = true;
     } else if (a.ksplit > 1) {
       HIPCHK(m, launch_ksplit_reduce(a, s));
     }
   }
-  if (ss) {
+  if (r.ss) {
     Timed t(m, s, "gn_finalize", 0.0, 0.0);
     HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, a.MT * 32, l.gamma, l.beta, 1e-5f,
-                                 ss[0], ss[1], s, 0, mu_out, rstd_out));
+                                 r.ss[0], r.ss[1], s, 0, r.mu, r.rstd));
   }
   return PNVO_OK;
 }
-
-namespace {
-inline int run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const float *in_scale, const float *in_shift,
-                    float *y, int y_cstride, float *ss[2], const float *bias, const int64_t *bias_row, int relu_out,
-                    hipStream_t s, const float *const *src = nullptr) {
-  return pnvo_run_conv(m, l, B, x, in_scale, in_shift, y, y_cstride, ss, bias, bias_row, relu_out, s, src, nullptr, nullptr);
-}
 }  // namespace
+
+int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+  // GroupNorm-ed 3x3 and 1x1 stride-2 convs: float32 results from the 16-bit matrix cores (conv_x3.hip; 32 -> 32 channels on the
+  // row-streaming conv_rows.hip where it takes the launch, with fewer statistics slots than the tile plan the buffer is sized for:
+  // stats_floats); option conv=fp32 keeps the fp32-MFMA kernels.  Not with a fused stem source, bias or output ReLU.
+  if (r.ss && r.src == nullptr && r.bias == nullptr && !r.relu_out && r.y_cstride == l.coutp && x3_layer(m, l)) {
+    ConvX3Args xa;
+    x3_fill(m, l, B, xa);
+    // (the rows plan refuses a block tail whose skip branch carries its own GroupNorm — a downsample skip, reachable with
+    //  baseplanes 16: the rows kernel adds the raw skip tensor — so the tail's fields are in place BEFORE the plan looks at them)
+    if (r.tail != nullptr) {
+      xa.res = r.tail->res;
+      xa.res_scale = r.tail->res_scale;
+      xa.res_shift = r.tail->res_shift;
+    }
+    const int x3_mode = r.tail ? (r.tail->res ? 2 : 3) : (r.in_scale ? 1 : 0);
+    const bool rows = xa.np == 2 && m->opt.x3_rows && conv_rows32_plan(xa, l.k, l.stride, x3_mode, m->num_cus);
+    int mw = 0, nw = 0;
+    size_t ldsb = 0;
+    if (rows || conv_x3_plan(xa, l.k, l.stride, &mw, &nw, &ldsb)) return run_conv_x3(m, l, B, r, xa, rows, x3_mode, mw, nw, ldsb);
+  }
+  if (r.tail != nullptr) return fail(m, PNVO_ERR_STATE, "block tail handed to a conv that cannot take it (" + l.name + ")");
+  if (r.grp != nullptr && r.ss != nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " fell off the float16-piece tile kernel");
+  return run_conv_fp32(m, l, B, r);
+}
 
 // The fused stem: input assembly + /255 + whitening gathered in the operand fetch (LDS-staged kernel when the channel
 // count allows, else MODE 2 of the generic kernel), raw output + GroupNorm scale/shift (+ optional mean/rstd).
@@ -843,16 +814,16 @@ static bool stem_lds_serves(pnvo_handle m) {
 
 // Inference forwards decide on the DEVICE whether the stem is redone on float32 operands (pnvo_stem_repair); the training forward
 // keeps the host-side event (its backward has to know, too).
-static bool stem_repairs_on_device(pnvo_handle m) {
-  return m->opt.input_fallback && m->dd_flag != nullptr && !m->in_train_forward && stem_lds_serves(m);
+static bool stem_repairs_on_device(pnvo_handle m, bool train_fwd) {
+  return m->opt.input_fallback && m->dd_flag != nullptr && !train_fwd && stem_lds_serves(m);
 }
 
 // The stem's place in the forward is the 16-bit-matrix-core stems' (8 x 16-tile slots, pooled keys, raw entry).  Once the input
 // fallback engaged (dense_sticky) that place is kept and the float32 stem stands in (stem_lds_kernel<.., PAIRED>) wherever it
 // serves the model; elsewhere, and in the training forward, the handle leaves the mx path as before.
-bool pnvo_stem_on_mx(pnvo_handle m) {
-  if (m->dense_sticky && (m->in_train_forward || !stem_lds_serves(m))) return false;
-  return m->mx_ok && (!m->in_train_forward || m->train_mx) && m->opt.stem <= 1;
+bool pnvo_stem_on_mx(pnvo_handle m, bool train_fwd) {
+  if (m->dense_sticky && (train_fwd || !stem_lds_serves(m))) return false;
+  return m->mx_ok && (!train_fwd || m->train_mx) && m->opt.stem <= 1;
 }
 
 // The float32 stem in the place of an 8 x 16-tile stem: raw output + that stem's GroupNorm slot layout (+ pooled keys).  `only_if`
@@ -904,14 +875,14 @@ static int pnvo_stem_standin(pnvo_handle m, int B, const float *const *src, floa
 
 // An event behind a contract-checking stem launch (see pnvo_input_fallback); nothing while a stream capture is under way
 // (an event recorded into a graph cannot be waited for: such forwards keep the deferred check of pnvo_check_inputs).
-// Does the stem kernel pnvo_run_stem would launch leave per-tile statistics ([B][slots][CP][2]) in m->stats?
+// Does the stem kernel an inference pnvo_run_stem would launch leave per-tile statistics ([B][slots][CP][2]) in m->stats?
 bool stem_writes_slots(pnvo_handle m) {
-  return pnvo_stem_on_mx(m) || (m->dd_ok && m->opt.stem != 3 && !m->dense_sticky) || stem_lds_serves(m);
+  return pnvo_stem_on_mx(m, false) || (m->dd_ok && m->opt.stem != 3 && !m->dense_sticky) || stem_lds_serves(m);
 }
 
-int pnvo_mark_stem(pnvo_handle m, hipStream_t s) {
+int pnvo_mark_stem(pnvo_handle m, hipStream_t s, bool train_fwd) {
   if (!m->dd_flag || m->dense_sticky || m->raw_depth != nullptr) return PNVO_OK;   // sensor frames: inside the contract by construction
-  if (stem_repairs_on_device(m)) return PNVO_OK;    // decided on the device: pnvo_stem_standin(.., only_if = the flag) follows the stem
+  if (stem_repairs_on_device(m, train_fwd)) return PNVO_OK;    // decided on the device: pnvo_stem_standin(.., only_if = the flag) follows the stem
   HIPCHK(m, launch_flag_publish(m->dd_flag_dev, m->dd_flag, s));   // the host-side decisions below / pnvo_check_inputs read the host copy
   if (!m->opt.input_fallback) return PNVO_OK;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -922,14 +893,14 @@ int pnvo_mark_stem(pnvo_handle m, hipStream_t s) {
   return PNVO_OK;
 }
 
-int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *ss[2], float *mu_out, float *rstd_out,
-                  hipStream_t s, int *pool_keys) {
+int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *const *ss, float *mu_out, float *rstd_out,
+                  hipStream_t s, int *pool_keys, bool train_fwd, bool skip_finalize, const GroupedFwd *grp) {
   const pnvo_config &c = m->cfg;
   const Layer &stem = m->convs[0];
   int rc = PNVO_OK;
   const bool lds_stem = (m->CPL <= 32) && (stem.coutp == 32 || stem.coutp == 64) && stem.cout == stem.coutp;
-  if (pool_keys != nullptr && !pnvo_stem_on_mx(m)) return fail(m, PNVO_ERR_STATE, "pooled stem output asked of a stem kernel without it");
-  if (pnvo_stem_on_mx(m)) {
+  if (pool_keys != nullptr && !pnvo_stem_on_mx(m, train_fwd)) return fail(m, PNVO_ERR_STATE, "pooled stem output asked of a stem kernel without it");
+  if (pnvo_stem_on_mx(m, train_fwd)) {
     // bf16 matrix cores, three exact weight pieces: float32 results (stem_mx.hip).  The training step keeps the kernels
     // below, whose operands it rebuilds on the device after every Adam step.
     StemMXArgs a;
@@ -941,8 +912,8 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
     // (an eval forward of a handle with a training step attached takes the float16 operand too when it is current: packed by the
     //  pnvo_load_weights that followed the last optimiser step)
     //  pnvo_load_weights that followed the last optimiser step — or kept current by the training step's device-side re-pack)
-    const bool h2_current = m->train == nullptr || m->mx_wpk2_dev || (!m->in_train_forward && m->weights_gen == m->weights_gen_at_load);
-    const bool want2 = m->in_train_forward ? m->opt.train_pieces == 2 : m->opt.pieces == 2;
+    const bool h2_current = m->train == nullptr || m->mx_wpk2_dev || (!train_fwd && m->weights_gen == m->weights_gen_at_load);
+    const bool want2 = train_fwd ? m->opt.train_pieces == 2 : m->opt.pieces == 2;
     const int pieces = (want2 && h2_current && m->mx_wpk2 != nullptr) ? 2 : 3;
     a.zero_page = m->mx_pages;
     a.wpk = pieces == 2 ? m->mx_wpk2 : m->mx_wpk3;
@@ -969,12 +940,12 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
     a.Hp = m->Hp;
     a.Wp = m->Wp;
     GnGroup sgg{0x7fffffff, 0x7fffffff, {nullptr, nullptr}, {nullptr, nullptr}};
-    if (m->grp_n > 1) {                 // grouped forward: the other models' stem operands (tile kernel only)
+    if (grp != nullptr) {               // grouped forward: the other models' stem operands (tile kernel only)
       if (pieces != 2 || pool_keys == nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward needs the float16-piece stem with pooled keys");
-      a.grp_end0 = sgg.end0 = m->grp_end[0];
-      if (m->grp_n > 2) a.grp_end1 = sgg.end1 = m->grp_end[1];
-      for (int k = 1; k < m->grp_n; ++k) {
-        pnvo_handle hk = m->grp[k];
+      a.grp_end0 = sgg.end0 = grp->end[0];
+      if (grp->n > 2) a.grp_end1 = sgg.end1 = grp->end[1];
+      for (int k = 1; k < grp->n; ++k) {
+        pnvo_handle hk = grp->h[k];
         if (hk->mx_wpk2 == nullptr || hk->mx_wpk2_dev) return fail(m, PNVO_ERR_STATE, "grouped forward: a model has no host-packed float16 stem operand");
         a.wpk_g[k - 1] = hk->mx_wpk2;
         a.oscale_g[k - 1] = hk->mx_oscale;
@@ -1007,7 +978,7 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
       //   tiles (auto otherwise): one tile per workgroup, two workgroups per CU — 0.99 ms, bound by the CU's vector-memory pipe
       //     (245 KB of weight fragments + 93 KB of patch per 128-pixel tile);
       //   (round 4's role-specialised persistent form — stem_ps_kernel, as fast as tiles — was retired in round 5: HISTORY.md.)
-      const bool rs = m->grp_n <= 1 && (m->opt.stem_form == 3 || m->opt.stem_form == 4 || m->opt.stem_form == 0) && stem_rs_takes(a, pieces, ntn, false, m->num_cus);
+      const bool rs = grp == nullptr && (m->opt.stem_form == 3 || m->opt.stem_form == 4 || m->opt.stem_form == 0) && stem_rs_takes(a, pieces, ntn, false, m->num_cus);
       m->mx_prof_rs = rs;
       if (rs)
         HIPCHK(m, launch_stem_rs(a, pieces, m->opt.stem_form == 4 || m->opt.stem_form == 0, m->num_cus, s));
@@ -1017,22 +988,22 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
     // a value outside the observation contract (the flag the stager raised): redone on float32 operands, decided on the DEVICE —
     // two launches that return at once while the flag is down; the host never waits (it reads the flag at its next entry and
     // moves the handle to the stand-in for good: pnvo_check_inputs)
-    if (!m->dense_sticky && m->raw_depth == nullptr && stem_repairs_on_device(m) &&
+    if (!m->dense_sticky && m->raw_depth == nullptr && stem_repairs_on_device(m, train_fwd) &&
         (rc = pnvo_stem_standin(m, B, src, y, a.slots, pool_keys, m->dd_flag_dev, s)) != PNVO_OK)
       return rc;
-    if ((rc = pnvo_mark_stem(m, s)) != PNVO_OK) return rc;
+    if ((rc = pnvo_mark_stem(m, s, train_fwd)) != PNVO_OK) return rc;
     m->stem_slots_out = a.slots;
-    if (!m->stem_skip_finalize) {
+    if (!skip_finalize) {
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
       HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
-                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out, m->grp_n > 1 ? &sgg : nullptr));
+                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out, grp ? &sgg : nullptr));
     }
-  } else if (m->dd_ok && m->opt.stem != 3 && m->dense_sticky && !m->in_train_forward && stem_lds_serves(m)) {
+  } else if (m->dd_ok && m->opt.stem != 3 && m->dense_sticky && !train_fwd && stem_lds_serves(m)) {
     // the input fallback engaged on the one-hot-aware stem: the float32 stem stands in, in that stem's slot layout
     const int slots = stem_dd_slots(m->Hs, m->Ws);
     if ((rc = pnvo_stem_standin(m, B, src, y, slots, nullptr, nullptr, s)) != PNVO_OK) return rc;
     m->stem_slots_out = slots;
-    if (!m->stem_skip_finalize) {
+    if (!skip_finalize) {
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
       HIPCHK(m, launch_gn_finalize(m->stats, B, slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
                                    stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, slots, mu_out, rstd_out));
@@ -1080,10 +1051,10 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
               4.0 * ((double)B * c.height * c.width * stem.cin + M * stem.cout + (double)stem.cout * stem.cin * 49));
       HIPCHK(m, launch_stem_dd(a, s));
     }
-    if (stem_repairs_on_device(m) && (rc = pnvo_stem_standin(m, B, src, y, a.slots, nullptr, m->dd_flag_dev, s)) != PNVO_OK) return rc;
-    if ((rc = pnvo_mark_stem(m, s)) != PNVO_OK) return rc;
+    if (stem_repairs_on_device(m, train_fwd) && (rc = pnvo_stem_standin(m, B, src, y, a.slots, nullptr, m->dd_flag_dev, s)) != PNVO_OK) return rc;
+    if ((rc = pnvo_mark_stem(m, s, train_fwd)) != PNVO_OK) return rc;
     m->stem_slots_out = a.slots;
-    if (!m->stem_skip_finalize) {
+    if (!skip_finalize) {
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
       HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
                                    stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out));
@@ -1123,14 +1094,14 @@ int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float
       HIPCHK(m, launch_stem_lds(a, stem.coutp, s));
     }
     m->stem_slots_out = a.slots;
-    if (!m->stem_skip_finalize) {
+    if (!skip_finalize) {
       Timed t(m, s, "gn_finalize", 0.0, 0.0);
       HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
                                    stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out));
     }
   } else {
-    if ((rc = pnvo_run_conv(m, stem, B, nullptr, m->stem_sc, m->stem_sh, y, stem.coutp, ss, nullptr, nullptr, 0, s, src,
-                            mu_out, rstd_out)) != PNVO_OK)
+    if ((rc = pnvo_run_conv(m, stem, B, {.in_scale = m->stem_sc, .in_shift = m->stem_sh, .y = y, .y_cstride = stem.coutp, .ss = ss,
+                                         .mu = mu_out, .rstd = rstd_out, .src = src, .grp = grp, .s = s})) != PNVO_OK)
       return rc;
   }
   return rc;
@@ -1643,7 +1614,7 @@ int pnvo_check_inputs(pnvo_handle m) {
     // already repaired: the handle runs the float32 stand-in since an earlier check; the flag only stays up for forwards still in
     // flight (turning input_fallback off afterwards must not turn every later forward into an error)
     if (m->dense_sticky) return PNVO_OK;
-    if (m->opt.input_fallback && !m->in_train_forward && stem_lds_serves(m)) {
+    if (m->opt.input_fallback && stem_lds_serves(m)) {
       // The flag is host-mapped: read without waiting for anything.  The forward that raised it repaired itself on the device
       // (pnvo_stem_standin behind its stem); from here on this handle launches the float32 stand-in directly.  The flag stays up
       // — repairs of forwards still in flight read it — until pnvo_set_option(h, "stem", ..) lifts the fallback.
@@ -1668,7 +1639,7 @@ int pnvo_check_inputs(pnvo_handle m) {
 
 namespace {
 int forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                 const int64_t *actions, int B, float *out, hipStream_t s);
+                 const int64_t *actions, int B, float *out, hipStream_t s, const GroupedFwd *grp);
 
 }  // namespace
 
@@ -1710,7 +1681,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
     m->graph_mode = m->opt.graph;
   }
   const bool plain = !m->graph_mode || m->timing || m->tap_dst != nullptr || m->train != nullptr || m->opt.stem_dbg != 0;
-  if (plain) return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s);
+  if (plain) return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s, nullptr);
 
   // ---- graph replay: key = everything the captured kernel arguments depend on
   const void *key[8] = {rgb, depth, dd, tdv, actions, m->raw_rgb, m->raw_depth, m->raw_err};   // (pnvo_set_option drops the captured graphs)
@@ -1720,7 +1691,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
       g.stamp = ++m->graph_clock;
       HIPCHK(m, hipGraphLaunch(g.exec, s));
       HIPCHK(m, hipMemcpyAsync(out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
-      return pnvo_mark_stem(m, s);
+      return pnvo_mark_stem(m, s, false);
     }
   bool again = false;                              // capture only call shapes that come back
   for (auto &g : m->seen) again = again || (g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0);
@@ -1731,7 +1702,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
     sn.B = B;
     if (m->seen.size() >= 16) m->seen.erase(m->seen.begin());
     m->seen.push_back(sn);
-    return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s);
+    return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s, nullptr);
   }
   if (!m->cap_stream) HIPCHK(m, hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
   pnvo_model_s::GraphEntry g;
@@ -1739,7 +1710,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
   g.B = B;
   g.stamp = ++m->graph_clock;
   HIPCHK(m, hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
-  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, m->out_ws, m->cap_stream);
+  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, m->out_ws, m->cap_stream, nullptr);
   const hipError_t ce = hipStreamEndCapture(m->cap_stream, &g.graph);
   if (rc != PNVO_OK) {
     if (ce == hipSuccess && g.graph) (void)hipGraphDestroy(g.graph);
@@ -1758,7 +1729,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
   m->graphs.push_back(g);
   HIPCHK(m, hipGraphLaunch(g.exec, s));
   HIPCHK(m, hipMemcpyAsync(out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
-  return pnvo_mark_stem(m, s);
+  return pnvo_mark_stem(m, s, false);
 }
 }  // namespace
 
@@ -1768,8 +1739,9 @@ bool fc_rows_usable(pnvo_handle m, int B);
 int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, int B, const float *comp_raw, const float *sc, const float *sh,
                 const int64_t *actions, float *out, hipStream_t s);
 
+// grp: a grouped forward's models (pnvo_forward_grouped_raw), or nullptr
 int forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                 const int64_t *actions, int B, float *out, hipStream_t s) {
+                 const int64_t *actions, int B, float *out, hipStream_t s, const GroupedFwd *grp) {
   const pnvo_config &c = m->cfg;
   int rc = PNVO_OK;
   // (a4+a5+a6) input assembly + /255 + whitening are fused into the stem kernel's operand fetch (pnvo_run_stem): the
@@ -1801,17 +1773,14 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   // first block's first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs
   // (conv_x3 MODE 3).  PNVO_POOL=separate, taps, Bottleneck models and the other stem kernels keep the pass.
   float *cur = m->bufY[0], *nxt = m->bufY[1];
-  const bool pool_fused = !m->bottleneck && pnvo_stem_on_mx(m) && m->opt.pool && m->convs.size() > 1 &&
+  const bool pool_fused = !m->bottleneck && pnvo_stem_on_mx(m, false) && m->opt.pool && m->convs.size() > 1 &&
                           stem.coutp == stem.cout && pnvo_conv_takes_tail(m, m->convs[1], B);
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
   const bool small = !pool_fused && stem_writes_slots(m) && pnvo_small_usable(m, B);
   if (small) {
     const float *src[4] = {rgb, depth, dd, tdv};
-    m->stem_skip_finalize = true;
-    rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, nullptr);
-    m->stem_skip_finalize = false;
-    if (rc != PNVO_OK) return rc;
+    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, nullptr, false, true, grp)) != PNVO_OK) return rc;
     return pnvo_small_forward(m, B, c.act_embed ? actions : nullptr, out, s);
   }
   {
@@ -1820,8 +1789,8 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
       Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
       HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
     }
-    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, pool_fused ? reinterpret_cast<int *>(nxt) : nullptr)) !=
-        PNVO_OK)
+    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, pool_fused ? reinterpret_cast<int *>(nxt) : nullptr, false,
+                            false, grp)) != PNVO_OK)
       return rc;
   }
   if ((rc = maybe_tap(m, "stem_conv", m->stem_raw, (size_t)B * m->Hs * m->Ws * stem.coutp, s)) != PNVO_OK) return rc;
@@ -1841,18 +1810,16 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
         const Layer &b2 = m->convs[li++];
         const Layer &b3 = m->convs[li++];
         const bool dsb = (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos);
-        if ((rc = run_conv(m, b1, B, cur, nullptr, nullptr, m->rawA, b1.coutp, m->ssA, nullptr, nullptr, 0, s)) != PNVO_OK)
-          return rc;
-        if ((rc = run_conv(m, b2, B, m->rawA, m->ssA[0], m->ssA[1], m->rawC, b2.coutp, m->ssB, nullptr, nullptr, 0, s)) !=
-            PNVO_OK)
-          return rc;
-        if ((rc = run_conv(m, b3, B, m->rawC, m->ssB[0], m->ssB[1], m->rawB, b3.coutp, m->ssA, nullptr, nullptr, 0, s)) !=
-            PNVO_OK)
+        if ((rc = pnvo_run_conv(m, b1, B, {.x = cur, .y = m->rawA, .y_cstride = b1.coutp, .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK ||
+            (rc = pnvo_run_conv(m, b2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawC, .y_cstride = b2.coutp,
+                                           .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK ||
+            (rc = pnvo_run_conv(m, b3, B, {.x = m->rawC, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawB, .y_cstride = b3.coutp,
+                                           .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
         const long Pb = (long)b3.hout * b3.wout;
         if (dsb) {
           const Layer &cd = m->convs[li++];
-          if ((rc = run_conv(m, cd, B, cur, nullptr, nullptr, m->rawD, cd.coutp, m->ssD, nullptr, nullptr, 0, s)) != PNVO_OK)
+          if ((rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
             return rc;
           Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
           HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
@@ -1874,19 +1841,19 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
       const DsRide ride{ds_ride ? &m->convs[li] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
       if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
         BlockTail ktail{nullptr, nullptr, nullptr, cur};
-        if ((rc = pnvo_run_conv(m, c1, B, nxt, m->ssA[0], m->ssA[1], m->rawA, c1.coutp, m->ssA, nullptr, nullptr, 0, s, nullptr, nullptr,
-                                nullptr, &ktail)) != PNVO_OK)
+        if ((rc = pnvo_run_conv(m, c1, B, {.x = nxt, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawA, .y_cstride = c1.coutp,
+                                           .ss = m->ssA, .tail = &ktail, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
         have_keys = false;
       } else if (have_tail) {    // the previous block's tail rides on this conv's stager, which also writes the block output
         if (ds_ride) tail.out = nullptr;                       // (nobody else reads this block's input)
-        if ((rc = pnvo_run_conv(m, c1, B, m->rawB, m->ssB[0], m->ssB[1], m->rawA, c1.coutp, m->ssA, nullptr, nullptr, 0, s, nullptr,
-                                nullptr, nullptr, &tail, ds_ride ? &ride : nullptr)) != PNVO_OK)
+        if ((rc = pnvo_run_conv(m, c1, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawA, .y_cstride = c1.coutp,
+                                           .ss = m->ssA, .tail = &tail, .ride = ds_ride ? &ride : nullptr, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
         std::swap(cur, nxt);
         have_tail = false;
-      } else if ((rc = pnvo_run_conv(m, c1, B, cur, nullptr, nullptr, m->rawA, c1.coutp, m->ssA, nullptr, nullptr, 0, s, nullptr, nullptr,
-                                     nullptr, nullptr, ds_ride ? &ride : nullptr)) != PNVO_OK) {
+      } else if ((rc = pnvo_run_conv(m, c1, B, {.x = cur, .y = m->rawA, .y_cstride = c1.coutp, .ss = m->ssA, .ride = ds_ride ? &ride : nullptr,
+                                                .grp = grp, .s = s})) != PNVO_OK) {
         return rc;
       }
       const long P = (long)c2.hout * c2.wout;
@@ -1900,15 +1867,16 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
           Timed t(m, s, "gn_relu_apply", 0.0, 8.0 * B * P * c2.cinp);
           HIPCHK(m, launch_apply_ss_relu(m->rawA, m->ssA[0], m->ssA[1], B, P, c2.cinp, napp, s));
         }
-        if ((rc = run_conv(m, c2, B, napp, nullptr, nullptr, m->rawB, c2.coutp, m->ssB, nullptr, nullptr, 0, s)) != PNVO_OK)
+        if ((rc = pnvo_run_conv(m, c2, B, {.x = napp, .y = m->rawB, .y_cstride = c2.coutp, .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
-      } else if ((rc = run_conv(m, c2, B, m->rawA, m->ssA[0], m->ssA[1], m->rawB, c2.coutp, m->ssB, nullptr, nullptr, 0, s)) != PNVO_OK) {
+      } else if ((rc = pnvo_run_conv(m, c2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawB, .y_cstride = c2.coutp,
+                                                .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK) {
         return rc;
       }
       if (ds) {
         const Layer &cd = m->convs[li++];
         if (!ds_ride &&                                                // (riding: rawD / ssD came out of c1's launch)
-            (rc = run_conv(m, cd, B, cur, nullptr, nullptr, m->rawD, cd.coutp, m->ssD, nullptr, nullptr, 0, s)) != PNVO_OK)
+            (rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
       }
       // (the last block's tail rides on the compression conv when that runs on conv_x3_kernel: nobody else reads that block output)
@@ -1935,11 +1903,11 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   const Layer &comp = m->convs[li++];
   if (have_tail) {               // the last block's tail in the compression conv's stager; its output is not materialised
     tail.out = nullptr;
-    if ((rc = pnvo_run_conv(m, comp, B, m->rawB, m->ssB[0], m->ssB[1], m->comp_raw, comp.coutp, m->ssC, nullptr, nullptr, 0, s, nullptr, nullptr,
-                            nullptr, &tail)) != PNVO_OK)
+    if ((rc = pnvo_run_conv(m, comp, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->comp_raw, .y_cstride = comp.coutp,
+                                         .ss = m->ssC, .tail = &tail, .grp = grp, .s = s})) != PNVO_OK)
       return rc;
     have_tail = false;
-  } else if ((rc = run_conv(m, comp, B, cur, nullptr, nullptr, m->comp_raw, comp.coutp, m->ssC, nullptr, nullptr, 0, s)) != PNVO_OK) {
+  } else if ((rc = pnvo_run_conv(m, comp, B, {.x = cur, .y = m->comp_raw, .y_cstride = comp.coutp, .ss = m->ssC, .grp = grp, .s = s})) != PNVO_OK) {
     return rc;
   }
   if (m->tap_dst != nullptr && m->tap_name == "compression") {
@@ -1948,20 +1916,20 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   }
   // (a11) Flatten + Linear + ReLU, then the output head — per action model in a grouped forward (each on its own handle: its
   // weights, bias rows and split-K scratch; the sample ranges are contiguous)
-  if (m->grp_n > 1) {
+  if (grp != nullptr) {
     bool rows_ok = !c.act_embed;
-    for (int k = 0; k < m->grp_n; ++k) rows_ok = rows_ok && fc_rows_usable(m->grp[k], B);
-    if (rows_ok) return run_fc_rows(m, m->grp, m->grp_end, m->grp_n, B, m->comp_raw, m->ssC[0], m->ssC[1], nullptr, out, s);
+    for (int k = 0; k < grp->n; ++k) rows_ok = rows_ok && fc_rows_usable(grp->h[k], B);
+    if (rows_ok) return run_fc_rows(m, grp->h, grp->end, grp->n, B, m->comp_raw, m->ssC[0], m->ssC[1], nullptr, out, s);
     int start = 0;
-    for (int k = 0; k < m->grp_n; ++k) {
-      const int Bk = m->grp_end[k] - start;
-      pnvo_handle hk = m->grp[k];
+    for (int k = 0; k < grp->n; ++k) {
+      const int Bk = grp->end[k] - start;
+      pnvo_handle hk = grp->h[k];
       if (k > 0 && (rc = ensure_workspace(hk, Bk)) != PNVO_OK) return fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk));
       const size_t crow = (size_t)m->fh * m->fw * m->comp_cp;
       rc = run_fc_head(hk, Bk, m->comp_raw + start * crow, m->ssC[0] + (size_t)start * m->comp_cp, m->ssC[1] + (size_t)start * m->comp_cp,
                        nullptr, out + (size_t)start * c.out_dim, s);
       if (rc != PNVO_OK) return k > 0 ? fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk)) : rc;
-      start = m->grp_end[k];
+      start = grp->end[k];
     }
     return PNVO_OK;
   }
@@ -2018,22 +1986,20 @@ int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, co
   }
   // the output head rides on the hidden layer's split-K reduction when there is one (option head_fuse); with a training step attached
   // the head's weight is read where the optimiser keeps it (the flat parameter buffer), the bias from its re-packed copy
-  m->head_rode = false;
-  m->head_ride_w = m->train != nullptr ? pnvo_train_weight_ptr(m, "output_head.1.weight") : m->head_w_plain;   // (OIHW of a 1x1 conv = [out_dim][hidden])
-  m->head_ride_out = (m->opt.head_fuse && !m->features_only && c.out_dim <= 4 && m->head_ride_w != nullptr) ? out : nullptr;
-  rc = run_conv(m, m->fc, B, comp_raw, sc, sh, m->hid, c.hidden, nullptr, m->fc_bias, c.act_embed ? actions : nullptr, 1, s);
-  m->head_ride_out = nullptr;
-  if (rc != PNVO_OK) return rc;
+  bool head_rode = false;
+  const float *head_w = m->train != nullptr ? pnvo_train_weight_ptr(m, "output_head.1.weight") : m->head_w_plain;   // (OIHW of a 1x1 conv = [out_dim][hidden])
+  float *head_out = (m->opt.head_fuse && !m->features_only && c.out_dim <= 4 && head_w != nullptr) ? out : nullptr;
+  if ((rc = pnvo_run_conv(m, m->fc, B, {.x = comp_raw, .in_scale = sc, .in_shift = sh, .y = m->hid, .y_cstride = c.hidden, .bias = m->fc_bias,
+                                        .bias_row = c.act_embed ? actions : nullptr, .relu_out = 1, .head_w = head_w, .head_out = head_out,
+                                        .head_rode = &head_rode, .s = s})) != PNVO_OK)
+    return rc;
   if ((rc = maybe_tap(m, "hidden", m->hid, (size_t)B * c.hidden, s)) != PNVO_OK) return rc;
-  if (m->head_rode) return PNVO_OK;
+  if (head_rode) return PNVO_OK;
   if (m->features_only) {                          // pnvo_forward_features: `out` receives the hidden vector
     HIPCHK(m, hipMemcpyAsync(out, m->hid, (size_t)B * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
     return PNVO_OK;
   }
-  if ((rc = run_conv(m, m->head, B, m->hid, nullptr, nullptr, out, c.out_dim, nullptr, m->head_bias, nullptr, 0, s)) !=
-      PNVO_OK)
-    return rc;
-  return PNVO_OK;
+  return pnvo_run_conv(m, m->head, B, {.x = m->hid, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
 }
 }  // namespace
 
@@ -2164,23 +2130,16 @@ int pnvo_forward_grouped_raw(const pnvo_handle *handles, const int32_t *counts, 
   m->opt.conv = 1;                 // every GroupNorm-ed conv on conv_x3_kernel (its fine plan for small launches)
   m->opt.x3_rows = 0;              // (the row-streaming and resident-weight kernels hold ONE model's weights per workgroup)
   m->opt.x3_persist = 0;
-  m->grp_n = ng;
-  int acc = 0;
-  for (int k = 0; k < ng; ++k) {
-    m->grp[k] = hs[k];
-    acc += cnt[k];
-    m->grp_end[k] = acc;
-  }
+  GroupedFwd grp{ng, {hs[0], hs[1], hs[2]}, {0, 0, 0}};
+  for (int k = 0, acc = 0; k < ng; ++k) grp.end[k] = acc += cnt[k];
   m->raw_rgb = rgb_frames;
   m->raw_depth = depth_frames;
   m->raw_err = err_flag;
-  rc = forward_body(m, nullptr, nullptr, nullptr, tdv, nullptr, B, out, s);
+  rc = forward_body(m, nullptr, nullptr, nullptr, tdv, nullptr, B, out, s, &grp);
   m->stem_ev_pending = false;
   m->raw_rgb = nullptr;
   m->raw_depth = nullptr;
   m->raw_err = nullptr;
-  m->grp_n = 0;
-  for (int k = 0; k < 3; ++k) m->grp[k] = nullptr;
   m->opt = saved;
   return rc;
 }
@@ -2233,10 +2192,10 @@ int pnvo_forward_features(pnvo_handle m, const float *rgb, const float *depth, c
   int rc = ensure_workspace(m, B);
   if (rc != PNVO_OK) return rc;
   m->features_only = true;
-  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream);
+  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream, nullptr);
   bool rerun = false;
   if (rc == PNVO_OK) rc = pnvo_input_fallback(m, (hipStream_t)stream, &rerun);
-  if (rc == PNVO_OK && rerun) rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream);
+  if (rc == PNVO_OK && rerun) rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream, nullptr);
   m->features_only = false;
   return rc;
 }

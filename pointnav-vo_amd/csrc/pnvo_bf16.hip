@@ -415,15 +415,14 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *de
     const int tm = h->timing;
     h->timing = 0;                                  // (their event records belong to the fp32 path's table)
     // (the output head rides on the hidden layer's split-K reduction when there is one: option head_fuse, as in the float32 forward)
-    h->head_rode = false;
-    h->head_ride_w = h->train != nullptr ? nullptr : h->head_w_plain;
-    h->head_ride_out = (h->opt.head_fuse && c.out_dim <= 4 && h->head_ride_w != nullptr) ? outs[z] : nullptr;
-    rc = pnvo_run_conv(h, h->fc, B, bs[z]->comp_raw, bs[z]->ssC[0], bs[z]->ssC[1], bs[z]->hid, c.hidden, nullptr, h->fc_bias,
-                       c.act_embed ? actions : nullptr, 1, s, nullptr, nullptr, nullptr);
-    h->head_ride_out = nullptr;
-    if (rc == PNVO_OK && !h->head_rode)
-      rc = pnvo_run_conv(h, h->head, B, bs[z]->hid, nullptr, nullptr, outs[z], c.out_dim, nullptr, h->head_bias, nullptr, 0, s,
-                         nullptr, nullptr, nullptr);
+    bool head_rode = false;
+    const float *head_w = h->train != nullptr ? nullptr : h->head_w_plain;
+    rc = pnvo_run_conv(h, h->fc, B, {.x = bs[z]->comp_raw, .in_scale = bs[z]->ssC[0], .in_shift = bs[z]->ssC[1], .y = bs[z]->hid,
+                                     .y_cstride = c.hidden, .bias = h->fc_bias, .bias_row = c.act_embed ? actions : nullptr, .relu_out = 1,
+                                     .head_w = head_w, .head_out = (h->opt.head_fuse && c.out_dim <= 4 && head_w != nullptr) ? outs[z] : nullptr,
+                                     .head_rode = &head_rode, .s = s});
+    if (rc == PNVO_OK && !head_rode)
+      rc = pnvo_run_conv(h, h->head, B, {.x = bs[z]->hid, .y = outs[z], .y_cstride = c.out_dim, .bias = h->head_bias, .s = s});
     h->timing = tm;
     if (rc != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, h->err);
   }

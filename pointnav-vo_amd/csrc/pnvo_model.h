@@ -83,16 +83,8 @@ struct pnvo_model_s {
   std::vector<Layer> convs;          // stem, residual stages in execution order, compression
   Layer fc, head;
   float *fc_bias = nullptr, *head_bias = nullptr;   // device; fc_bias has 1 or n_acts+1 rows
-  // grouped forward (pnvo_forward_grouped_raw), set on the LEADER handle for the duration of the call: handles of the action models
-  // in sample order (grp[0] = this handle), cumulative sample ends; kernels pick a sample's operands by its model
-  int grp_n = 0;
-  struct pnvo_model_s *grp[3] = {nullptr, nullptr, nullptr};
-  int grp_end[3] = {0, 0, 0};
   float *fc_rows_w = nullptr;                // device [hidden][fh * fw * comp_cp]: the hidden layer's weight rows in the activation's order (fc_rows.hip)
   float *head_w_plain = nullptr;             // device [out_dim][hidden]: the head's weight as loaded (the head riding on the hidden layer's split-K reduction)
-  const float *head_ride_w = nullptr;        // ... the weight it reads: head_w_plain, or the flat parameter buffer of an attached training step
-  float *head_ride_out = nullptr;            // set around the hidden layer's launch by the forward: where the riding head writes [B][out_dim]
-  bool head_rode = false;                    //   ... and whether it did (else the forward launches the head)
   std::vector<float> mean, stdev;    // host copies for the assemble kernel arguments (reference channel order)
   // fused stem: K-order of the stem = observation tensors concatenated (rgb | depth | dd | tdv), 2-channel pieces
   std::vector<int> stem_ref_of_new;  // new channel -> reference channel (vo_cnn.py:169-174 order), -1 = pad
@@ -127,7 +119,6 @@ struct pnvo_model_s {
   unsigned long long *mx_prof = nullptr;     // PNVO_STEM_DBG=9: per-wave phase cycle sums of stem_mx / stem_ps
   bool mx_prof_rs = false;                   //   ... the last stem launch was the resident-weight form
   int num_cus = 256;                         // compute units of the device (grid of the persistent kernels)
-  bool in_train_forward = false;
   bool train_mx = false;                     // the attached training step rebuilds the mx stem operands every step
   PnvoOptions opt;
   bool dense_sticky = false;                 // an input outside the mx/dd stems' contract was met: this handle stays on the dense stem
@@ -167,7 +158,6 @@ struct pnvo_model_s {
   void *train = nullptr;             // TrainState (pnvo_train_api.hip), present after pnvo_train_attach
   void *small = nullptr;             // SmallNet (smallnet.hip): the persistent small-batch kernel's operands, built on first use
   int stem_slots_out = 0;            // statistics slots per sample the last stem launch wrote into `stats` ([B][slots][CP][2])
-  bool stem_skip_finalize = false;   // the consumer of this forward's stem reduces those slots itself (smallnet.hip)
 
   // Opt-in (PNVO_GRAPH=1): the whole forward (~60 launches) captured once per (batch, tensor addresses, kernel
   // selection) into a hipGraph and replayed (see pnvo_forward for the measurement that keeps it off by default).
@@ -212,20 +202,49 @@ struct DsRide {
   float *mu, *rstd;      // [B,groups] statistics of the downsample GroupNorm for a backward pass, or nullptr
 };
 
+// A grouped forward (pnvo_forward_grouped_raw): pairs of n = 2 or 3 action models in one launch chain, sorted by model.  h[k] serves
+// the samples up to end[k] (h[0] = the handle that runs the chain); kernels pick a sample's operands by its model.
+struct GroupedFwd {
+  int n;
+  pnvo_model_s *h[3];
+  int end[3];
+};
+
+// One conv launch of pnvo_run_conv: a call site sets the members it uses (designated initializers, in this order).
+struct ConvRequest {
+  const float *x = nullptr;
+  const float *in_scale = nullptr, *in_shift = nullptr;   // [B,CIN] GroupNorm of the producer: relu(x*scale+shift) while staging
+  float *y = nullptr;
+  int y_cstride = 0;                         // channel stride of y
+  float *const *ss = nullptr;                // [2]: GroupNorm scale / shift of this conv's output; nullptr: no GroupNorm (linear layers)
+  float *mu = nullptr, *rstd = nullptr;      // [B,groups] statistics of that GroupNorm for a backward pass, or nullptr
+  const float *bias = nullptr;
+  const int64_t *bias_row = nullptr;         // [B] row of `bias` per sample, or nullptr (row 0)
+  int relu_out = 0;
+  const float *const *src = nullptr;         // fused stem: the observation tensors A is gathered from (x unused)
+  const BlockTail *tail = nullptr;
+  const DsRide *ride = nullptr;
+  const GroupedFwd *grp = nullptr;
+  // the output head on the hidden layer's split-K reduction launch (when there is one): its weight [out_dim][hidden], where it writes
+  // [B][out_dim], and whether it did (else the caller launches the head)
+  const float *head_w = nullptr;
+  float *head_out = nullptr;
+  bool *head_rode = nullptr;
+  hipStream_t s = nullptr;
+};
+
 // helpers implemented in pnvo_api.hip
-int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const float *x, const float *in_scale, const float *in_shift,
-                  float *y, int y_cstride, float *ss[2], const float *bias, const int64_t *bias_row, int relu_out,
-                  hipStream_t s, const float *const *src, float *mu_out, float *rstd_out, const BlockTail *tail = nullptr,
-                  const DsRide *ride = nullptr);
+int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r);   // one conv + the GroupNorm finalisation that follows it
 bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B);   // would pnvo_run_conv(c1) carry cd as a DsRide?
 bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B);                        // would pnvo_run_conv(l) use conv_x3.hip?
 bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B);   // would pnvo_run_conv(l) accept a BlockTail (conv_x3 path)?
 void pnvo_pack_conv_weight_cinp(const float *oihw, int cout, int cin, int cinp, int kh, int kw, std::vector<float> &out);
-int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *ss[2], float *mu_out, float *rstd_out,
-                  hipStream_t s, int *pool_keys = nullptr);
-bool pnvo_stem_on_mx(pnvo_handle m);
+// train_fwd: the training forward's stem; skip_finalize: the consumer of the stem's statistics slots reduces them itself (smallnet.hip)
+int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *const *ss, float *mu_out, float *rstd_out,
+                  hipStream_t s, int *pool_keys, bool train_fwd, bool skip_finalize, const GroupedFwd *grp);
+bool pnvo_stem_on_mx(pnvo_handle m, bool train_fwd);
 void pnvo_stem_raw_args(pnvo_handle m, pnvo::StemMXArgs &a);   // fills the RAW-stager fields of a stem launch when m->raw_depth is set
-int pnvo_mark_stem(pnvo_handle m, hipStream_t s);
+int pnvo_mark_stem(pnvo_handle m, hipStream_t s, bool train_fwd);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
 const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name);   // pnvo_train_api.hip: device pointer or nullptr

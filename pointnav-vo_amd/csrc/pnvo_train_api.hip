@@ -965,10 +965,7 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
   size_t li = 0;
   {
     ConvSave &cs = t->cs[li];
-    m->in_train_forward = true;
-    rc = pnvo_run_stem(m, B, t->src, cs.raw, cs.ss, cs.mu, cs.rstd, s);
-    m->in_train_forward = false;
-    if (rc != PNVO_OK) return rc;
+    if ((rc = pnvo_run_stem(m, B, t->src, cs.raw, cs.ss, cs.mu, cs.rstd, s, nullptr, true, false, nullptr)) != PNVO_OK) return rc;
     const Layer &stem = m->convs[li++];
     HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, stem.coutp, t->y[0], t->pool_idx, s));
   }
@@ -999,12 +996,12 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
         const ConvSave *sp = k ? &t->cs[ik[k - 1]] : nullptr;
         const DsRide *rd = (k == 0 && ds_ride) ? &ride : nullptr;
         if (k == 0 && have_tail) {       // the previous block's tail rides on this conv's stager, which writes xin (= tail.out)
-          rc = pnvo_run_conv(m, ck, B, tail_x->raw, tail_x->ss[0], tail_x->ss[1], sk.raw, ck.coutp, sk.ss, nullptr, nullptr, 0, s, nullptr,
-                             sk.mu, sk.rstd, &tail, rd);
+          rc = pnvo_run_conv(m, ck, B, {.x = tail_x->raw, .in_scale = tail_x->ss[0], .in_shift = tail_x->ss[1], .y = sk.raw, .y_cstride = ck.coutp,
+                                        .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .tail = &tail, .ride = rd, .s = s});
           have_tail = false;
         } else {
-          rc = pnvo_run_conv(m, ck, B, k ? sp->raw : xin, k ? sp->ss[0] : nullptr, k ? sp->ss[1] : nullptr, sk.raw, ck.coutp, sk.ss, nullptr,
-                             nullptr, 0, s, nullptr, sk.mu, sk.rstd, nullptr, rd);
+          rc = pnvo_run_conv(m, ck, B, {.x = k ? sp->raw : xin, .in_scale = k ? sp->ss[0] : nullptr, .in_shift = k ? sp->ss[1] : nullptr,
+                                        .y = sk.raw, .y_cstride = ck.coutp, .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .ride = rd, .s = s});
         }
         if (rc != PNVO_OK) return rc;
       }
@@ -1015,8 +1012,8 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
         const size_t id = li++;
         const Layer &cd = m->convs[id];
         ConvSave &sd = t->cs[id];
-        if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, xin, nullptr, nullptr, sd.raw, cd.coutp, sd.ss, nullptr, nullptr, 0, s, nullptr,
-                                            sd.mu, sd.rstd)) != PNVO_OK)
+        if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, {.x = xin, .y = sd.raw, .y_cstride = cd.coutp, .ss = sd.ss, .mu = sd.mu, .rstd = sd.rstd,
+                                                       .s = s})) != PNVO_OK)
           return rc;
         tail = BlockTail{sd.raw, sd.ss[0], sd.ss[1], yout};
       } else {
@@ -1036,8 +1033,8 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
     const size_t ic = li++;
     const Layer &comp = m->convs[ic];
     ConvSave &sc = t->cs[ic];
-    if ((rc = pnvo_run_conv(m, comp, B, t->y[nblk_total], nullptr, nullptr, sc.raw, comp.coutp, sc.ss, nullptr, nullptr, 0, s, nullptr,
-                            sc.mu, sc.rstd)) != PNVO_OK)
+    if ((rc = pnvo_run_conv(m, comp, B, {.x = t->y[nblk_total], .y = sc.raw, .y_cstride = comp.coutp, .ss = sc.ss, .mu = sc.mu, .rstd = sc.rstd,
+                                         .s = s})) != PNVO_OK)
       return rc;
     ++t->drop_step;
     const float *fcb = m->fc_bias;
@@ -1057,21 +1054,16 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
     if (t->drop_p > 0.f) {            // Dropout -> Linear -> ReLU -> Dropout -> Linear (vo_cnn.py:216-227), masks by hash
       HIPCHK(m, launch_dropout(sc.raw, sc.ss[0], sc.ss[1], B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed,
                                t->drop_step, 0, t->zdrop, s));
-      if ((rc = pnvo_run_conv(m, m->fc, B, t->zdrop, nullptr, nullptr, t->hid, c.hidden, nullptr, fcb, fcrow, 1, s,
-                              nullptr, nullptr, nullptr)) != PNVO_OK)
+      if ((rc = pnvo_run_conv(m, m->fc, B, {.x = t->zdrop, .y = t->hid, .y_cstride = c.hidden, .bias = fcb, .bias_row = fcrow, .relu_out = 1,
+                                            .s = s})) != PNVO_OK)
         return rc;
       HIPCHK(m, launch_dropout(t->hid, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, t->hdrop,
                                s));
-      if ((rc = pnvo_run_conv(m, m->head, B, t->hdrop, nullptr, nullptr, out, c.out_dim, nullptr, m->head_bias, nullptr, 0,
-                              s, nullptr, nullptr, nullptr)) != PNVO_OK)
-        return rc;
-      return PNVO_OK;
+      return pnvo_run_conv(m, m->head, B, {.x = t->hdrop, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
     }
-    if ((rc = pnvo_run_conv(m, m->fc, B, sc.raw, sc.ss[0], sc.ss[1], t->hid, c.hidden, nullptr, fcb, fcrow, 1, s,
-                            nullptr, nullptr, nullptr)) != PNVO_OK)
-      return rc;
-    if ((rc = pnvo_run_conv(m, m->head, B, t->hid, nullptr, nullptr, out, c.out_dim, nullptr, m->head_bias, nullptr, 0, s,
-                            nullptr, nullptr, nullptr)) != PNVO_OK)
+    if ((rc = pnvo_run_conv(m, m->fc, B, {.x = sc.raw, .in_scale = sc.ss[0], .in_shift = sc.ss[1], .y = t->hid, .y_cstride = c.hidden,
+                                          .bias = fcb, .bias_row = fcrow, .relu_out = 1, .s = s})) != PNVO_OK ||
+        (rc = pnvo_run_conv(m, m->head, B, {.x = t->hid, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s})) != PNVO_OK)
       return rc;
   }
   return PNVO_OK;
