@@ -288,12 +288,13 @@ def topdown_view(depth, consts, rows_around_center=50, blur_in=None, return_aux=
 
 
 # ----------------------------------------------------------------------------- baseline form: one pair per host thread
-def forward_pairs_parallel(sd, obs, *, ngroups, threads=None, dtype=np.float32, indices=None):
+def forward_pairs_parallel(sd, obs, *, ngroups, threads=None, dtype=np.float32, indices=None, taps=None):
     """The same forward, parallelised over PAIRS instead of inside each layer (frame pairs are independent; per-sample
     GroupNorm): `threads` host threads, each running whole single-pair forwards with an OpenMP team of one, so a pair's
     working set (7.9 MB of input, 2.1 MB of stem output, ...) stays in that core's caches.  ctypes releases the GIL inside
     the C calls.  Results equal `forward` (same per-element summation order).  bench.py's cpu_baseline leg.
-    `indices`: the pairs of `obs` to run, repeats allowed (a long timed sample over a small set of distinct pairs)."""
+    `indices`: the pairs of `obs` to run, repeats allowed (a long timed sample over a small set of distinct pairs).
+    `taps`: optional names of `forward`'s taps (e.g. ("hidden",)); then returns (out, {name: taps stacked over the pairs})."""
     from concurrent.futures import ThreadPoolExecutor
     threads = int(threads or usable_cores())
     idx = list(range(next(iter(obs.values())).shape[0])) if indices is None else [int(i) for i in indices]
@@ -304,8 +305,13 @@ def forward_pairs_parallel(sd, obs, *, ngroups, threads=None, dtype=np.float32, 
         set_threads(1)                                   # omp nthreads-var is per host thread: a team of one in THIS thread
 
     def one(i):
-        return forward(sdc, {k: v[i:i + 1] for k, v in obs.items()}, ngroups=ngroups, dtype=dtype)
+        t = {} if taps is not None else None
+        out = forward(sdc, {k: v[i:i + 1] for k, v in obs.items()}, ngroups=ngroups, dtype=dtype, taps=t)
+        return out, (None if taps is None else {name: t[name] for name in taps})
 
     with ThreadPoolExecutor(max_workers=min(threads, n), initializer=init) as ex:
-        outs = list(ex.map(one, idx))
-    return np.concatenate(outs, axis=0)
+        res = list(ex.map(one, idx))
+    out = np.concatenate([r[0] for r in res], axis=0)
+    if taps is None:
+        return out
+    return out, {name: np.concatenate([r[1][name] for r in res], axis=0) for name in taps}

@@ -337,6 +337,7 @@ class VisualOdometryCNNBase(nn.Module):
         """(kernel family, matrix-core FLOPs one launch executes) of a residual-stage conv at this batch size."""
         dev = next(self.parameters()).device
         self._ensure_handle(dev)
+        self._sync_weights()              # the selection depends on the loaded weights (a handle without them reports fp32 kernels)
         buf, fl = C.create_string_buffer(32), C.c_double(0.0)
         _lib.check(_lib.lib.pnvo_layer_kernel(self._handle, name.encode(), int(batch), buf, 32, C.byref(fl)), self._handle)
         return buf.value.decode(), float(fl.value)
