@@ -362,6 +362,13 @@ size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
   return (size_t)B * (size_t)slots * l.coutp * 2;
 }
 
+// Statistics slots per sample a stem kernel leaves in m->stats: 8 x 16 tiles (MX, DD), 4 x 16 tiles (LDS).
+int stem_slots(pnvo_handle m, StemPlan::Kernel k) {
+  if (k == StemPlan::GENERIC) return 0;
+  if (k == StemPlan::LDS) return stem_tiles_x(m->Ws) * stem_tiles_y(m->Hs);
+  return k == StemPlan::MX ? stem_mx_slots(m->Hs, m->Ws) : stem_dd_slots(m->Hs, m->Ws);
+}
+
 int ensure_workspace(pnvo_handle m, int B) {   // (also exported as pnvo_ensure_workspace)
   if (B <= m->cap) return PNVO_OK;
   free_workspace(m);
@@ -373,11 +380,8 @@ int ensure_workspace(pnvo_handle m, int B) {   // (also exported as pnvo_ensure_
     if (need > act) act = need;
   }
   int maxc = m->comp_cp;
-  size_t st = (size_t)B * stem_tiles_x(m->Ws) * stem_tiles_y(m->Hs) * m->convs[0].coutp * 2;   // LDS-staged stem
-  {
-    const size_t st_mx = (size_t)B * stem_mx_slots(m->Hs, m->Ws) * m->convs[0].coutp * 2;
-    if (st_mx > st) st = st_mx;
-  }
+  size_t st = 0;                        // GroupNorm partials: whichever stem or conv leaves the most slots (option stem may change)
+  for (StemPlan::Kernel k : {StemPlan::MX, StemPlan::DD, StemPlan::LDS}) st = std::max(st, (size_t)B * stem_slots(m, k) * m->convs[0].coutp * 2);
   for (const Layer &l : m->convs) {
     if (l.coutp > maxc) maxc = l.coutp;
     const size_t s = stats_floats(m, l, B);
@@ -791,14 +795,61 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
   return run_conv_fp32(m, l, B, r);
 }
 
-// The fused stem: input assembly + /255 + whitening gathered in the operand fetch (LDS-staged kernel when the channel
-// count allows, else MODE 2 of the generic kernel), raw output + GroupNorm scale/shift (+ optional mean/rstd).
-void pnvo_stem_raw_args(pnvo_handle m, StemMXArgs &a) {
-  if (m->raw_depth == nullptr) return;
-  a.raw_rgb = m->raw_rgb;
-  a.raw_depth = m->raw_depth;
+// The stem's place in the forward is the 16-bit-matrix-core stems' (8 x 16-tile slots, pooled keys, raw entry) or the one-hot-aware
+// stem's.  Once the input fallback engaged (dense_sticky) that place is kept and the float32 stem stands in (stem_lds_kernel<.., PAIRED>)
+// wherever it serves the model; elsewhere, and in the training forward, the handle leaves the fused stems for stem_lds.hip / the
+// generic kernel.
+StemPlan pnvo_stem_plan(pnvo_handle m, bool train_fwd, const RawFrames &raw) {
+  const Layer &stem = m->convs[0];
+  StemPlan p;
+  p.lds_serves = (m->CPL <= 32) && (stem.coutp == 32 || stem.coutp == 64) && stem.cout == stem.coutp;
+  const bool keeps_place = !m->dense_sticky || (!train_fwd && p.lds_serves);
+  if (keeps_place && m->mx_ok && (!train_fwd || m->train_mx) && m->opt.stem <= 1)
+    p.kernel = StemPlan::MX;
+  else if (keeps_place && m->dd_ok && m->opt.stem != 3)
+    p.kernel = StemPlan::DD;       // (in training its operands are rebuilt on the device every step: refresh_stem_dd)
+  else
+    p.kernel = p.lds_serves ? StemPlan::LDS : StemPlan::GENERIC;
+  const bool fused = p.kernel == StemPlan::MX || p.kernel == StemPlan::DD;
+  p.standin = fused && m->dense_sticky;
+  p.slots = stem_slots(m, p.kernel);
+  // Inference forwards decide on the DEVICE whether the stem is redone on float32 operands (a stand-in predicated on the contract
+  // flag); the training forward keeps the host-side event (its backward has to know, too).  Sensor frames are inside the contract
+  // by construction: nothing to repair, nothing to mark.
+  const bool on_device = m->opt.input_fallback && m->dd_flag != nullptr && !train_fwd && p.lds_serves;
+  p.repairs = fused && !p.standin && raw.depth == nullptr && on_device;
+  p.marks = m->dd_flag != nullptr && !m->dense_sticky && raw.depth == nullptr && !on_device;
+  // two float16 weight pieces at inference (5 MFMAs per tap); three bf16 pieces (7, every product exact) on request and while the
+  // float16 operand is stale: with a training step attached it is current when the step's device-side re-pack wrote it, or — eval
+  // forwards only — when a pnvo_load_weights followed the last optimiser step
+  const bool loaded_current = m->train == nullptr || m->weights_gen == m->weights_gen_at_load;
+  const bool h2_current = m->mx_wpk2_dev || (train_fwd ? m->train == nullptr : loaded_current);
+  const bool want2 = train_fwd ? m->opt.train_pieces == 2 : m->opt.pieces == 2;
+  p.pieces = (want2 && h2_current && m->mx_wpk2 != nullptr) ? 2 : 3;
+  p.h2_from_host = m->opt.pieces == 2 && m->mx_wpk2 != nullptr && loaded_current;
+  return p;
+}
+
+double pnvo_stem_in_bytes(pnvo_handle m, int B, const RawFrames &raw) {
+  const pnvo_config &c = m->cfg;
+  // the observation tensors (or, RAW: 6 B of rgb + 8 B of depth + 8 B of top-down view per pixel) once
+  return (double)B * c.height * c.width * (raw.depth ? (c.n_rgb ? 6.0 : 0.0) + 8.0 + (c.n_tdv ? 8.0 : 0.0) : 4.0 * m->convs[0].cin);
+}
+
+void pnvo_stem_mx_input(pnvo_handle m, int B, const float *const *src, const RawFrames &raw, StemMXArgs &a) {
+  for (int k = 0; k < 4; ++k) a.src[k] = src[k];
+  a.zero_page = m->mx_pages;
+  a.B = B;
+  a.H = m->cfg.height;
+  a.W = m->cfg.width;
+  a.Ho = m->Hs;
+  a.Wo = m->Ws;
+  a.slots = stem_slots(m, StemPlan::MX);
+  if (raw.depth == nullptr) return;
+  a.raw_rgb = raw.rgb;
+  a.raw_depth = raw.depth;
   a.raw_flags = (m->cfg.n_depth > 0 ? 1 : 0) | (m->cfg.n_dd > 0 ? 2 : 0);
-  a.raw_err = m->raw_err;
+  a.raw_err = raw.err;
   const int bins = 10;                                             // the mx stem's K-slot layout (n_dd == 20)
   for (int i = 0; i < bins; ++i) a.edges[i] = (float)((double)i * 1.0 / (double)bins);   // base_trainer_with_vo.py:105-115
   a.edges[bins] = 1.0f;
@@ -806,41 +857,37 @@ void pnvo_stem_raw_args(pnvo_handle m, StemMXArgs &a) {
   a.src[0] = a.src[1] = a.src[2] = nullptr;
 }
 
-// The float32-MFMA stem (stem_lds.hip) serves this model: the kernel the input-contract repair runs.
-static bool stem_lds_serves(pnvo_handle m) {
-  const Layer &stem = m->convs[0];
-  return (m->CPL <= 32) && (stem.coutp == 32 || stem.coutp == 64) && stem.cout == stem.coutp;
+// Forms of the 16-bit-matrix-core stem (option stem_form: auto | fast | resident | tiles):
+//   fast (auto when every workgroup gets >= 4 tiles): one 4-wave workgroup per CU for the whole launch, the weights in its
+//     registers, staging of the next tile and epilogue of the previous one between the MFMAs (stem_rs.hip), the remainder MFMAs
+//     of four taps in one K chunk and tap 48 split over the waves — 0.78 ms at 256 pairs, float32-grade equal to the others;
+//   resident: the same kernel in the tile kernel's summation order — 0.81 ms, bit-identical to tiles (the bf16 path's dual stem
+//     with its 196 KB of weight fragments takes this one);
+//   tiles (auto otherwise, and every grouped forward): one tile per workgroup, two workgroups per CU — 0.99 ms, bound by the CU's
+//     vector-memory pipe (245 KB of weight fragments + 93 KB of patch per 128-pixel tile);
+//   (round 4's role-specialised persistent form — stem_ps_kernel, as fast as tiles — was retired in round 5: HISTORY.md.)
+int pnvo_launch_stem_mx(pnvo_handle m, const StemMXArgs &a, int pieces, int ntiles, bool bf16_out, const GroupedFwd *grp, hipStream_t s) {
+  const int form = m->opt.stem_form;
+  const bool resident = grp == nullptr && (form == 3 || form == 4 || form == 0) && stem_rs_takes(a, pieces, ntiles, bf16_out, m->num_cus);
+  if (!bf16_out) m->mx_prof_rs = resident;         // (the bf16 path's launches carry no profile buffer)
+  if (resident)
+    HIPCHK(m, launch_stem_rs(a, pieces, !bf16_out && (form == 4 || form == 0), m->num_cus, s));
+  else
+    HIPCHK(m, launch_stem_mx(a, pieces, ntiles, bf16_out, s));
+  return PNVO_OK;
 }
 
-// Inference forwards decide on the DEVICE whether the stem is redone on float32 operands (pnvo_stem_repair); the training forward
-// keeps the host-side event (its backward has to know, too).
-static bool stem_repairs_on_device(pnvo_handle m, bool train_fwd) {
-  return m->opt.input_fallback && m->dd_flag != nullptr && !train_fwd && stem_lds_serves(m);
-}
-
-// The stem's place in the forward is the 16-bit-matrix-core stems' (8 x 16-tile slots, pooled keys, raw entry).  Once the input
-// fallback engaged (dense_sticky) that place is kept and the float32 stem stands in (stem_lds_kernel<.., PAIRED>) wherever it
-// serves the model; elsewhere, and in the training forward, the handle leaves the mx path as before.
-bool pnvo_stem_on_mx(pnvo_handle m, bool train_fwd) {
-  if (m->dense_sticky && (train_fwd || !stem_lds_serves(m))) return false;
-  return m->mx_ok && (!train_fwd || m->train_mx) && m->opt.stem <= 1;
-}
-
-// The float32 stem in the place of an 8 x 16-tile stem: raw output + that stem's GroupNorm slot layout (+ pooled keys).  `only_if`
-// (device-readable flag) makes both launches no-ops while it is zero.
-static int pnvo_stem_standin(pnvo_handle m, int B, const float *const *src, float *y, int slots, int *pool_keys, const int *only_if,
-                             hipStream_t s) {
+// The operands of stem_lds.hip: the dense stem, or (`slots` of an 8 x 16-tile stem, paired) the stand-in for one.
+static void stem_lds_args(pnvo_handle m, int B, const StemRequest &r, int slots, StemArgs &a) {
   const pnvo_config &c = m->cfg;
-  const Layer &stem = m->convs[0];
   const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
-  StemArgs a;
   std::memset(&a, 0, sizeof(a));
   for (int j = 0; j < m->CPL / 8; ++j)
     for (int hh = 0; hh < 2; ++hh)
       for (int q = 0; q < 2; ++q) {
         const int nc = 8 * j + 4 * hh + 2 * q;
         const int tn = nc < m->CP ? m->stem_tensor_of_new[nc] : -1;
-        a.pieces[j][hh][q].base = tn >= 0 ? src[tn] : nullptr;
+        a.pieces[j][hh][q].base = tn >= 0 ? r.src[tn] : nullptr;
         a.pieces[j][hh][q].nch = tn >= 0 ? nsrc[tn] : 0;
         a.pieces[j][hh][q].choff = tn >= 0 ? m->stem_ch_of_new[nc] : 0;
       }
@@ -848,7 +895,7 @@ static int pnvo_stem_standin(pnvo_handle m, int B, const float *const *src, floa
   a.sh = m->stem_sh;
   a.wpk = m->stem_wpk16;
   a.zero_page = m->zero_page;
-  a.y = y;
+  a.y = r.y;
   a.stats = m->stats;
   a.B = B;
   a.H = c.height;
@@ -857,32 +904,41 @@ static int pnvo_stem_standin(pnvo_handle m, int B, const float *const *src, floa
   a.Wo = m->Ws;
   a.CPL = m->CPL;
   a.slots = slots;
+}
+
+// The stem's entry of the timing table; the stand-in predicated on the contract flag is a "stem_repair" without figures.
+static Timed stem_timed(pnvo_handle m, int B, const StemRequest &r, bool repair) {
+  const Layer &stem = m->convs[0];
+  if (repair) return Timed(m, r.s, "stem_repair", 0.0, 0.0);
+  const double M = (double)B * m->Hs * m->Ws, wts = (double)stem.cout * stem.cin * 49;
+  return Timed(m, r.s, "conv:" + stem.name, 2.0 * M * wts, pnvo_stem_in_bytes(m, B, r.raw) + 4.0 * (M * stem.cout + wts));
+}
+
+// The float32 stem in the place of an 8 x 16-tile stem: raw output + that stem's GroupNorm slot layout (+ pooled keys).  `only_if`
+// (device-readable flag) makes both launches no-ops while it is zero.
+static int pnvo_stem_standin(pnvo_handle m, int B, const StemRequest &r, int slots, const int *only_if) {
+  const Layer &stem = m->convs[0];
+  StemArgs a;
+  stem_lds_args(m, B, r, slots, a);
   a.paired = 1;
   a.only_if = only_if;
   a.publish = only_if ? m->dd_flag : nullptr;     // a raised flag reaches the host-mapped copy from this launch
   {
-    const double M = (double)B * m->Hs * m->Ws;
-    Timed t(m, s, only_if ? "stem_repair" : "conv:" + stem.name, only_if ? 0.0 : 2.0 * M * stem.cout * stem.cin * 49,
-            only_if ? 0.0 : 4.0 * ((double)B * c.height * c.width * stem.cin + M * stem.cout + (double)stem.cout * stem.cin * 49));
-    HIPCHK(m, launch_stem_lds(a, stem.coutp, s));
+    Timed t = stem_timed(m, B, r, only_if != nullptr);
+    HIPCHK(m, launch_stem_lds(a, stem.coutp, r.s));
   }
-  if (pool_keys != nullptr) {
-    Timed t(m, s, only_if ? "stem_repair" : "pool_keys", 0.0, only_if ? 0.0 : 4.0 * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * stem.coutp);
-    HIPCHK(m, launch_pool_keys_from_raw(y, stem.gamma, B, m->Hs, m->Ws, stem.coutp, pool_keys, only_if, s));
+  if (r.pool_keys != nullptr) {
+    Timed t(m, r.s, only_if ? "stem_repair" : "pool_keys", 0.0, only_if ? 0.0 : 4.0 * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * stem.coutp);
+    HIPCHK(m, launch_pool_keys_from_raw(r.y, stem.gamma, B, m->Hs, m->Ws, stem.coutp, r.pool_keys, only_if, r.s));
   }
   return PNVO_OK;
 }
 
-// An event behind a contract-checking stem launch (see pnvo_input_fallback); nothing while a stream capture is under way
-// (an event recorded into a graph cannot be waited for: such forwards keep the deferred check of pnvo_check_inputs).
-// Does the stem kernel an inference pnvo_run_stem would launch leave per-tile statistics ([B][slots][CP][2]) in m->stats?
-bool stem_writes_slots(pnvo_handle m) {
-  return pnvo_stem_on_mx(m, false) || (m->dd_ok && m->opt.stem != 3 && !m->dense_sticky) || stem_lds_serves(m);
-}
-
-int pnvo_mark_stem(pnvo_handle m, hipStream_t s, bool train_fwd) {
-  if (!m->dd_flag || m->dense_sticky || m->raw_depth != nullptr) return PNVO_OK;   // sensor frames: inside the contract by construction
-  if (stem_repairs_on_device(m, train_fwd)) return PNVO_OK;    // decided on the device: pnvo_stem_standin(.., only_if = the flag) follows the stem
+// Behind a contract-checking stem launch whose repair is NOT decided on the device: the flag's host copy, and an event the caller
+// waits for (pnvo_input_fallback); no event while a stream capture is under way (an event recorded into a graph cannot be waited
+// for: such forwards keep the deferred check of pnvo_check_inputs).
+int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p) {
+  if (!p.marks) return PNVO_OK;
   HIPCHK(m, launch_flag_publish(m->dd_flag_dev, m->dd_flag, s));   // the host-side decisions below / pnvo_check_inputs read the host copy
   if (!m->opt.input_fallback) return PNVO_OK;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -893,218 +949,139 @@ int pnvo_mark_stem(pnvo_handle m, hipStream_t s, bool train_fwd) {
   return PNVO_OK;
 }
 
-int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *const *ss, float *mu_out, float *rstd_out,
-                  hipStream_t s, int *pool_keys, bool train_fwd, bool skip_finalize, const GroupedFwd *grp) {
-  const pnvo_config &c = m->cfg;
+// bf16 / float16 matrix cores, exact weight pieces: float32 results (stem_mx.hip, stem_rs.hip)
+static int stem_launch_mx(pnvo_handle m, int B, const StemRequest &r, const StemPlan &p, GnGroup &sgg) {
   const Layer &stem = m->convs[0];
+  StemMXArgs a;
+  std::memset(&a, 0, sizeof(a));
+  pnvo_stem_mx_input(m, B, r.src, r.raw, a);
+  a.wpk = p.pieces == 2 ? m->mx_wpk2 : m->mx_wpk3;
+  a.oscale = m->mx_oscale;
+  // (after a device-side re-pack the scale lives on the device; a later pnvo_load_weights re-packs on the host with its own)
+  a.oscale_ptr = m->mx_wpk2_dev ? m->mx_scale2_dev + 1 : nullptr;
+  a.bad_input = m->dd_flag_dev;
+  const int ntn = stem.cout / 32;
+  for (int g = 0; g < ntn; ++g) {
+    a.y[g] = r.y;
+    a.stats[g] = m->stats;
+    a.y_coff[g] = 32 * g;
+  }
+  a.y_cstride = stem.coutp;
+  a.stats_cstride = stem.coutp;
+  a.pool = r.pool_keys;
+  a.pool_gamma = stem.gamma;
+  a.Hp = m->Hp;
+  a.Wp = m->Wp;
+  if (r.grp != nullptr) {               // grouped forward: the other models' stem operands (tile kernel only)
+    if (p.pieces != 2 || r.pool_keys == nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward needs the float16-piece stem with pooled keys");
+    a.grp_end0 = sgg.end0 = r.grp->end[0];
+    if (r.grp->n > 2) a.grp_end1 = sgg.end1 = r.grp->end[1];
+    for (int k = 1; k < r.grp->n; ++k) {
+      pnvo_handle hk = r.grp->h[k];
+      if (hk->mx_wpk2 == nullptr || hk->mx_wpk2_dev) return fail(m, PNVO_ERR_STATE, "grouped forward: a model has no host-packed float16 stem operand");
+      a.wpk_g[k - 1] = hk->mx_wpk2;
+      a.oscale_g[k - 1] = hk->mx_oscale;
+      a.pool_gamma_g[k - 1] = sgg.gamma[k - 1] = hk->convs[0].gamma;
+      sgg.beta[k - 1] = hk->convs[0].beta;
+    }
+  }
+  a.dbg = m->opt.stem_dbg >= 16 ? m->opt.stem_dbg - 16 : 0;
+  if (m->opt.stem_dbg == 9 || m->opt.stem_dbg >= 16) {
+    if (!m->mx_prof) {
+      HIPCHK(m, hipMalloc((void **)&m->mx_prof, 2048));
+      HIPCHK(m, hipMemset(m->mx_prof, 0, 2048));
+    }
+    a.prof = m->mx_prof;
+  }
+  // the input fallback engaged: the float32 stem stands in (same place in the forward, same slot layout, pooled keys)
+  if (p.standin) return pnvo_stem_standin(m, B, r, p.slots, nullptr);
+  Timed t = stem_timed(m, B, r, false);
+  return pnvo_launch_stem_mx(m, a, p.pieces, ntn, false, r.grp, r.s);
+}
+
+// one-hot-aware stem (stem_dd.hip)
+static int stem_launch_dd(pnvo_handle m, int B, const StemRequest &r, const StemPlan &p) {
+  const pnvo_config &c = m->cfg;
+  if (p.standin) return pnvo_stem_standin(m, B, r, p.slots, nullptr);   // the input fallback engaged: in this stem's slot layout
+  const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
+  StemDDArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (int j = 0; j < 3; ++j)
+    for (int q = 0; q < 2; ++q) {
+      const int d = 4 * j + 2 * q;
+      const int tn = m->dd_dense_tensor[d];
+      a.pieces[j][0][q].base = tn >= 0 ? r.src[tn] : nullptr;
+      a.pieces[j][0][q].nch = tn >= 0 ? nsrc[tn] : 0;
+      a.pieces[j][0][q].choff = tn >= 0 ? m->dd_dense_ch[d] : 0;
+    }
+  a.sc = m->dd_sc;
+  a.sh = m->dd_sh;
+  a.wpk = m->dd_wpk;
+  a.table = m->dd_table;
+  a.dd = r.src[2];
+  a.zero_page = m->zero_page;
+  a.bad_onehot = m->dd_flag_dev;
+  a.y = r.y;
+  a.stats = m->stats;
+  a.B = B;
+  a.H = c.height;
+  a.W = c.width;
+  a.Ho = m->Hs;
+  a.Wo = m->Ws;
+  a.bins = m->dd_bins;
+  a.slots = p.slots;
+  a.dbg = m->opt.stem_dbg;
+  if (a.dbg == 9) {
+    if (!m->dd_prof) {
+      HIPCHK(m, hipMalloc((void **)&m->dd_prof, 64));
+      HIPCHK(m, hipMemset(m->dd_prof, 0, 64));
+    }
+    a.prof = m->dd_prof;
+  }
+  Timed t = stem_timed(m, B, r, false);
+  HIPCHK(m, launch_stem_dd(a, r.s));
+  return PNVO_OK;
+}
+
+// The fused stem: input assembly + /255 + whitening gathered in the operand fetch, raw output + GroupNorm scale / shift (+ optional
+// mean / rstd).
+int pnvo_run_stem(pnvo_handle m, int B, const StemRequest &r) {
+  const Layer &stem = m->convs[0];
+  const StemPlan p = pnvo_stem_plan(m, r.train_fwd, r.raw);
   int rc = PNVO_OK;
-  const bool lds_stem = (m->CPL <= 32) && (stem.coutp == 32 || stem.coutp == 64) && stem.cout == stem.coutp;
-  if (pool_keys != nullptr && !pnvo_stem_on_mx(m, train_fwd)) return fail(m, PNVO_ERR_STATE, "pooled stem output asked of a stem kernel without it");
-  if (pnvo_stem_on_mx(m, train_fwd)) {
-    // bf16 matrix cores, three exact weight pieces: float32 results (stem_mx.hip).  The training step keeps the kernels
-    // below, whose operands it rebuilds on the device after every Adam step.
-    StemMXArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int k = 0; k < 4; ++k) a.src[k] = src[k];
-    pnvo_stem_raw_args(m, a);
-    // two float16 weight pieces at inference (5 MFMAs per tap); three bf16 pieces (7, every product exact) on request and
-    // whenever a training step is attached (its device-side re-pack builds the three-piece operand)
-    // (an eval forward of a handle with a training step attached takes the float16 operand too when it is current: packed by the
-    //  pnvo_load_weights that followed the last optimiser step)
-    //  pnvo_load_weights that followed the last optimiser step — or kept current by the training step's device-side re-pack)
-    const bool h2_current = m->train == nullptr || m->mx_wpk2_dev || (!train_fwd && m->weights_gen == m->weights_gen_at_load);
-    const bool want2 = train_fwd ? m->opt.train_pieces == 2 : m->opt.pieces == 2;
-    const int pieces = (want2 && h2_current && m->mx_wpk2 != nullptr) ? 2 : 3;
-    a.zero_page = m->mx_pages;
-    a.wpk = pieces == 2 ? m->mx_wpk2 : m->mx_wpk3;
-    a.oscale = m->mx_oscale;
-    // (after a device-side re-pack the scale lives on the device; a later pnvo_load_weights re-packs on the host with its own)
-    a.oscale_ptr = m->mx_wpk2_dev ? m->mx_scale2_dev + 1 : nullptr;
-    a.bad_input = m->dd_flag_dev;
-    const int ntn = stem.cout / 32;
-    for (int g = 0; g < ntn; ++g) {
-      a.y[g] = y;
-      a.stats[g] = m->stats;
-      a.y_coff[g] = 32 * g;
+  if (r.pool_keys != nullptr && !p.pools()) return fail(m, PNVO_ERR_STATE, "pooled stem output asked of a stem kernel without it");
+  GnGroup sgg{0x7fffffff, 0x7fffffff, {nullptr, nullptr}, {nullptr, nullptr}};
+  switch (p.kernel) {
+    case StemPlan::MX: rc = stem_launch_mx(m, B, r, p, sgg); break;
+    case StemPlan::DD: rc = stem_launch_dd(m, B, r, p); break;
+    case StemPlan::LDS: {
+      StemArgs a;
+      stem_lds_args(m, B, r, p.slots, a);
+      a.dbg = m->opt.stem_dbg;
+      a.lds_pad = m->opt.stem_dbg_pad;
+      Timed t = stem_timed(m, B, r, false);
+      HIPCHK(m, launch_stem_lds(a, stem.coutp, r.s));
+      break;
     }
-    a.y_cstride = stem.coutp;
-    a.stats_cstride = stem.coutp;
-    a.B = B;
-    a.H = c.height;
-    a.W = c.width;
-    a.Ho = m->Hs;
-    a.Wo = m->Ws;
-    a.slots = stem_mx_slots(m->Hs, m->Ws);
-    a.pool = pool_keys;
-    a.pool_gamma = stem.gamma;
-    a.Hp = m->Hp;
-    a.Wp = m->Wp;
-    GnGroup sgg{0x7fffffff, 0x7fffffff, {nullptr, nullptr}, {nullptr, nullptr}};
-    if (grp != nullptr) {               // grouped forward: the other models' stem operands (tile kernel only)
-      if (pieces != 2 || pool_keys == nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward needs the float16-piece stem with pooled keys");
-      a.grp_end0 = sgg.end0 = grp->end[0];
-      if (grp->n > 2) a.grp_end1 = sgg.end1 = grp->end[1];
-      for (int k = 1; k < grp->n; ++k) {
-        pnvo_handle hk = grp->h[k];
-        if (hk->mx_wpk2 == nullptr || hk->mx_wpk2_dev) return fail(m, PNVO_ERR_STATE, "grouped forward: a model has no host-packed float16 stem operand");
-        a.wpk_g[k - 1] = hk->mx_wpk2;
-        a.oscale_g[k - 1] = hk->mx_oscale;
-        a.pool_gamma_g[k - 1] = sgg.gamma[k - 1] = hk->convs[0].gamma;
-        sgg.beta[k - 1] = hk->convs[0].beta;
-      }
-    }
-    a.dbg = m->opt.stem_dbg >= 16 ? m->opt.stem_dbg - 16 : 0;
-    if (m->opt.stem_dbg == 9 || m->opt.stem_dbg >= 16) {
-      if (!m->mx_prof) {
-        HIPCHK(m, hipMalloc((void **)&m->mx_prof, 2048));
-        HIPCHK(m, hipMemset(m->mx_prof, 0, 2048));
-      }
-      a.prof = m->mx_prof;
-    }
-    const double M = (double)B * m->Hs * m->Ws;
-    if (m->dense_sticky) {
-      // the input fallback engaged: the float32 stem stands in (same place in the forward, same slot layout, pooled keys)
-      if ((rc = pnvo_stem_standin(m, B, src, y, a.slots, pool_keys, nullptr, s)) != PNVO_OK) return rc;
-    } else {
-      // algorithmic bytes: the observation tensors (or, RAW: 6 B of rgb + 8 B of depth + 8 B of top-down view per pixel) once
-      const double in_bytes = (double)B * c.height * c.width * (m->raw_depth ? (c.n_rgb ? 6.0 : 0.0) + 8.0 + (c.n_tdv ? 8.0 : 0.0) : 4.0 * stem.cin);
-      Timed t(m, s, "conv:" + stem.name, 2.0 * M * stem.cout * stem.cin * 49,
-              in_bytes + 4.0 * (M * stem.cout + (double)stem.cout * stem.cin * 49));
-      // Forms of the float16-piece stem (option stem_form: auto | fast | resident | tiles):
-      //   fast (auto when every workgroup gets >= 4 tiles): one 4-wave workgroup per CU for the whole launch, the weights in its
-      //     registers, staging of the next tile and epilogue of the previous one between the MFMAs (stem_rs.hip), the remainder MFMAs
-      //     of four taps in one K chunk and tap 48 split over the waves — 0.78 ms at 256 pairs, float32-grade equal to the others;
-      //   resident: the same kernel in the tile kernel's summation order — 0.81 ms, bit-identical to tiles;
-      //   tiles (auto otherwise): one tile per workgroup, two workgroups per CU — 0.99 ms, bound by the CU's vector-memory pipe
-      //     (245 KB of weight fragments + 93 KB of patch per 128-pixel tile);
-      //   (round 4's role-specialised persistent form — stem_ps_kernel, as fast as tiles — was retired in round 5: HISTORY.md.)
-      const bool rs = grp == nullptr && (m->opt.stem_form == 3 || m->opt.stem_form == 4 || m->opt.stem_form == 0) && stem_rs_takes(a, pieces, ntn, false, m->num_cus);
-      m->mx_prof_rs = rs;
-      if (rs)
-        HIPCHK(m, launch_stem_rs(a, pieces, m->opt.stem_form == 4 || m->opt.stem_form == 0, m->num_cus, s));
-      else
-        HIPCHK(m, launch_stem_mx(a, pieces, ntn, false, s));
-    }
+    case StemPlan::GENERIC:             // MODE 2 of the generic kernel; pnvo_run_conv finalises the GroupNorm itself
+      return pnvo_run_conv(m, stem, B, {.in_scale = m->stem_sc, .in_shift = m->stem_sh, .y = r.y, .y_cstride = stem.coutp, .ss = r.ss,
+                                        .mu = r.mu, .rstd = r.rstd, .src = r.src, .grp = r.grp, .s = r.s});
+  }
+  if (rc != PNVO_OK) return rc;
+  if (p.kernel != StemPlan::LDS) {
     // a value outside the observation contract (the flag the stager raised): redone on float32 operands, decided on the DEVICE —
     // two launches that return at once while the flag is down; the host never waits (it reads the flag at its next entry and
     // moves the handle to the stand-in for good: pnvo_check_inputs)
-    if (!m->dense_sticky && m->raw_depth == nullptr && stem_repairs_on_device(m, train_fwd) &&
-        (rc = pnvo_stem_standin(m, B, src, y, a.slots, pool_keys, m->dd_flag_dev, s)) != PNVO_OK)
-      return rc;
-    if ((rc = pnvo_mark_stem(m, s, train_fwd)) != PNVO_OK) return rc;
-    m->stem_slots_out = a.slots;
-    if (!skip_finalize) {
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
-                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out, grp ? &sgg : nullptr));
-    }
-  } else if (m->dd_ok && m->opt.stem != 3 && m->dense_sticky && !train_fwd && stem_lds_serves(m)) {
-    // the input fallback engaged on the one-hot-aware stem: the float32 stem stands in, in that stem's slot layout
-    const int slots = stem_dd_slots(m->Hs, m->Ws);
-    if ((rc = pnvo_stem_standin(m, B, src, y, slots, nullptr, nullptr, s)) != PNVO_OK) return rc;
-    m->stem_slots_out = slots;
-    if (!skip_finalize) {
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
-                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, slots, mu_out, rstd_out));
-    }
-  } else if (m->dd_ok && m->opt.stem != 3 && !m->dense_sticky) {
-    // one-hot-aware stem (in training its operands are rebuilt on the device every step: refresh_stem_dd)
-    const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
-    StemDDArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int j = 0; j < 3; ++j)
-      for (int q = 0; q < 2; ++q) {
-        const int d = 4 * j + 2 * q;
-        const int tn = m->dd_dense_tensor[d];
-        a.pieces[j][0][q].base = tn >= 0 ? src[tn] : nullptr;
-        a.pieces[j][0][q].nch = tn >= 0 ? nsrc[tn] : 0;
-        a.pieces[j][0][q].choff = tn >= 0 ? m->dd_dense_ch[d] : 0;
-      }
-    a.sc = m->dd_sc;
-    a.sh = m->dd_sh;
-    a.wpk = m->dd_wpk;
-    a.table = m->dd_table;
-    a.dd = src[2];
-    a.zero_page = m->zero_page;
-    a.bad_onehot = m->dd_flag_dev;
-    a.y = y;
-    a.stats = m->stats;
-    a.B = B;
-    a.H = c.height;
-    a.W = c.width;
-    a.Ho = m->Hs;
-    a.Wo = m->Ws;
-    a.bins = m->dd_bins;
-    a.slots = stem_dd_slots(m->Hs, m->Ws);
-    a.dbg = m->opt.stem_dbg;
-    if (a.dbg == 9) {
-      if (!m->dd_prof) {
-        HIPCHK(m, hipMalloc((void **)&m->dd_prof, 64));
-        HIPCHK(m, hipMemset(m->dd_prof, 0, 64));
-      }
-      a.prof = m->dd_prof;
-    }
-    const double M = (double)B * m->Hs * m->Ws;
-    {
-      Timed t(m, s, "conv:" + stem.name, 2.0 * M * stem.cout * stem.cin * 49,
-              4.0 * ((double)B * c.height * c.width * stem.cin + M * stem.cout + (double)stem.cout * stem.cin * 49));
-      HIPCHK(m, launch_stem_dd(a, s));
-    }
-    if (stem_repairs_on_device(m, train_fwd) && (rc = pnvo_stem_standin(m, B, src, y, a.slots, nullptr, m->dd_flag_dev, s)) != PNVO_OK) return rc;
-    if ((rc = pnvo_mark_stem(m, s, train_fwd)) != PNVO_OK) return rc;
-    m->stem_slots_out = a.slots;
-    if (!skip_finalize) {
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
-                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out));
-    }
-  } else if (lds_stem) {
-    const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
-    StemArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int j = 0; j < m->CPL / 8; ++j)
-      for (int hh = 0; hh < 2; ++hh)
-        for (int q = 0; q < 2; ++q) {
-          const int nc = 8 * j + 4 * hh + 2 * q;
-          const int tn = nc < m->CP ? m->stem_tensor_of_new[nc] : -1;
-          a.pieces[j][hh][q].base = tn >= 0 ? src[tn] : nullptr;
-          a.pieces[j][hh][q].nch = tn >= 0 ? nsrc[tn] : 0;
-          a.pieces[j][hh][q].choff = tn >= 0 ? m->stem_ch_of_new[nc] : 0;
-        }
-    a.sc = m->stem_sc;
-    a.sh = m->stem_sh;
-    a.wpk = m->stem_wpk16;
-    a.zero_page = m->zero_page;
-    a.y = y;
-    a.stats = m->stats;
-    a.B = B;
-    a.H = c.height;
-    a.W = c.width;
-    a.Ho = m->Hs;
-    a.Wo = m->Ws;
-    a.CPL = m->CPL;
-    a.slots = stem_tiles_x(m->Ws) * stem_tiles_y(m->Hs);
-    a.dbg = m->opt.stem_dbg;
-    a.lds_pad = m->opt.stem_dbg_pad;
-    const double M = (double)B * m->Hs * m->Ws;
-    {
-      Timed t(m, s, "conv:" + stem.name, 2.0 * M * stem.cout * stem.cin * 49,
-              4.0 * ((double)B * c.height * c.width * stem.cin + M * stem.cout + (double)stem.cout * stem.cin * 49));
-      HIPCHK(m, launch_stem_lds(a, stem.coutp, s));
-    }
-    m->stem_slots_out = a.slots;
-    if (!skip_finalize) {
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1,
-                                   stem.gamma, stem.beta, 1e-5f, ss[0], ss[1], s, a.slots, mu_out, rstd_out));
-    }
-  } else {
-    if ((rc = pnvo_run_conv(m, stem, B, {.in_scale = m->stem_sc, .in_shift = m->stem_sh, .y = y, .y_cstride = stem.coutp, .ss = ss,
-                                         .mu = mu_out, .rstd = rstd_out, .src = src, .grp = grp, .s = s})) != PNVO_OK)
-      return rc;
+    if (p.repairs && (rc = pnvo_stem_standin(m, B, r, p.slots, m->dd_flag_dev)) != PNVO_OK) return rc;
+    if ((rc = pnvo_mark_stem(m, r.s, p)) != PNVO_OK) return rc;
   }
-  return rc;
+  if (r.slots_out != nullptr) *r.slots_out = p.slots;
+  if (!r.skip_finalize) {
+    Timed t(m, r.s, "gn_finalize", 0.0, 0.0);
+    HIPCHK(m, launch_gn_finalize(m->stats, B, p.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1, stem.gamma, stem.beta,
+                                 1e-5f, r.ss[0], r.ss[1], r.s, p.slots, r.mu, r.rstd, r.grp ? &sgg : nullptr));
+  }
+  return PNVO_OK;
 }
 
 int pnvo_ensure_workspace(pnvo_handle m, int B) { return ensure_workspace(m, B); }
@@ -1215,8 +1192,8 @@ int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun) {
 }
 
 namespace {
-int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                     const int64_t *actions, int B, float *out, hipStream_t s);
+int forward_dispatch(pnvo_handle m, int B, const FwdRequest &r);
+int forward_body(pnvo_handle m, int B, const FwdRequest &r);
 }
 
 
@@ -1232,7 +1209,7 @@ const char *pnvo_version(void) { return "pnvo 0.3 (gfx950: fp32 + f16/bf16 MFMA)
 const char *pnvo_last_error(pnvo_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 const char *pnvo_last_note(pnvo_handle h) {
-  if (h && h->loaded && h->opt.input_fallback && stem_lds_serves(h)) (void)pnvo_check_inputs(h);     // a raised input-contract flag (host-mapped, no wait) is noted here at the latest
+  if (h && h->loaded && h->opt.input_fallback && pnvo_stem_plan(h, false, {}).lds_serves) (void)pnvo_check_inputs(h);     // a raised input-contract flag (host-mapped, no wait) is noted here at the latest
   return h ? h->note.c_str() : "";
 }
 
@@ -1572,7 +1549,7 @@ int pnvo_get_option(pnvo_handle h, const char *key, char *buf, size_t cap) {
       word = c->word;
       break;
     }
-  if (d->field == &PnvoOptions::stem && h->loaded && h->opt.input_fallback && stem_lds_serves(h)) (void)pnvo_check_inputs(h);   // see pnvo_last_note
+  if (d->field == &PnvoOptions::stem && h->loaded && h->opt.input_fallback && pnvo_stem_plan(h, false, {}).lds_serves) (void)pnvo_check_inputs(h);   // see pnvo_last_note
   if (d->field == &PnvoOptions::stem && h->dense_sticky) word = "dense (fallback)";
   std::snprintf(buf, cap, "%s", word.c_str());
   return PNVO_OK;
@@ -1605,7 +1582,7 @@ int pnvo_forward_dual(pnvo_handle ha, pnvo_handle hb, const float *rgb, const fl
   HIPCHK(ha, hipSetDevice(ha->device));
   pnvo_handle hs[2] = {ha, hb};
   float *outs[2] = {out_a, out_b};
-  return pnvo_forward_bf16(hs, 2, rgb, depth, dd, tdv, nullptr, B, outs, (hipStream_t)stream);
+  return pnvo_forward_bf16(hs, 2, B, {.src = {rgb, depth, dd, tdv}, .s = (hipStream_t)stream}, outs);
 }
 
 int pnvo_check_inputs(pnvo_handle m) {
@@ -1614,7 +1591,7 @@ int pnvo_check_inputs(pnvo_handle m) {
     // already repaired: the handle runs the float32 stand-in since an earlier check; the flag only stays up for forwards still in
     // flight (turning input_fallback off afterwards must not turn every later forward into an error)
     if (m->dense_sticky) return PNVO_OK;
-    if (m->opt.input_fallback && stem_lds_serves(m)) {
+    if (m->opt.input_fallback && pnvo_stem_plan(m, false, {}).lds_serves) {
       // The flag is host-mapped: read without waiting for anything.  The forward that raised it repaired itself on the device
       // (pnvo_stem_standin behind its stem); from here on this handle launches the float32 stand-in directly.  The flag stays up
       // — repairs of forwards still in flight read it — until pnvo_set_option(h, "stem", ..) lifts the fallback.
@@ -1637,12 +1614,6 @@ int pnvo_check_inputs(pnvo_handle m) {
   return PNVO_OK;
 }
 
-namespace {
-int forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                 const int64_t *actions, int B, float *out, hipStream_t s, const GroupedFwd *grp);
-
-}  // namespace
-
 int pnvo_forward(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
                  const int64_t *actions, int B, float *out, void *stream) {
   if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
@@ -1655,24 +1626,24 @@ int pnvo_forward(pnvo_handle m, const float *rgb, const float *depth, const floa
   if (c.act_embed && !actions) return fail(m, PNVO_ERR_ARG, "act_embed model needs actions");
   if (int rc0 = pnvo_check_inputs(m)) return rc0;
   HIPCHK(m, hipSetDevice(m->device));
+  const FwdRequest r{.src = {rgb, depth, dd, tdv}, .actions = actions, .out = out, .s = (hipStream_t)stream};
   if (m->precision == 1) {
     pnvo_handle hs[1] = {m};
     float *outs[1] = {out};
-    return pnvo_forward_bf16(hs, 1, rgb, depth, dd, tdv, actions, B, outs, (hipStream_t)stream);
+    return pnvo_forward_bf16(hs, 1, B, r, outs);
   }
   int rc = ensure_workspace(m, B);
   if (rc != PNVO_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = forward_dispatch(m, rgb, depth, dd, tdv, actions, B, out, s)) != PNVO_OK) return rc;
+  if ((rc = forward_dispatch(m, B, r)) != PNVO_OK) return rc;
   bool rerun = false;
-  if ((rc = pnvo_input_fallback(m, s, &rerun)) != PNVO_OK) return rc;
-  return rerun ? forward_dispatch(m, rgb, depth, dd, tdv, actions, B, out, s) : PNVO_OK;
+  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
+  return rerun ? forward_dispatch(m, B, r) : PNVO_OK;
 }
 
 namespace {
-int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                     const int64_t *actions, int B, float *out, hipStream_t s) {
+int forward_dispatch(pnvo_handle m, int B, const FwdRequest &r) {
   const pnvo_config &c = m->cfg;
+  hipStream_t s = r.s;
   int rc = PNVO_OK;
   {
     // Opt-in (option graph=1).  Measured on ROCm 7.2 / MI355X: replaying the ~60-node graph is no faster than the plain
@@ -1681,17 +1652,18 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
     m->graph_mode = m->opt.graph;
   }
   const bool plain = !m->graph_mode || m->timing || m->tap_dst != nullptr || m->train != nullptr || m->opt.stem_dbg != 0;
-  if (plain) return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s, nullptr);
+  if (plain) return forward_body(m, B, r);
 
   // ---- graph replay: key = everything the captured kernel arguments depend on
-  const void *key[8] = {rgb, depth, dd, tdv, actions, m->raw_rgb, m->raw_depth, m->raw_err};   // (pnvo_set_option drops the captured graphs)
+  const void *key[8] = {r.src[0], r.src[1], r.src[2], r.src[3], r.actions, r.raw.rgb, r.raw.depth, r.raw.err};   // (pnvo_set_option drops the captured graphs)
+  const StemPlan sp = pnvo_stem_plan(m, false, r.raw);
   const size_t out_bytes = (size_t)B * c.out_dim * sizeof(float);
   for (auto &g : m->graphs)
     if (g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0) {
       g.stamp = ++m->graph_clock;
       HIPCHK(m, hipGraphLaunch(g.exec, s));
-      HIPCHK(m, hipMemcpyAsync(out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
-      return pnvo_mark_stem(m, s, false);
+      HIPCHK(m, hipMemcpyAsync(r.out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
+      return pnvo_mark_stem(m, s, sp);
     }
   bool again = false;                              // capture only call shapes that come back
   for (auto &g : m->seen) again = again || (g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0);
@@ -1702,7 +1674,7 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
     sn.B = B;
     if (m->seen.size() >= 16) m->seen.erase(m->seen.begin());
     m->seen.push_back(sn);
-    return forward_body(m, rgb, depth, dd, tdv, actions, B, out, s, nullptr);
+    return forward_body(m, B, r);
   }
   if (!m->cap_stream) HIPCHK(m, hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
   pnvo_model_s::GraphEntry g;
@@ -1710,7 +1682,10 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
   g.B = B;
   g.stamp = ++m->graph_clock;
   HIPCHK(m, hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
-  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, m->out_ws, m->cap_stream, nullptr);
+  FwdRequest rcap = r;                              // the captured forward writes the handle's own output buffer
+  rcap.out = m->out_ws;
+  rcap.s = m->cap_stream;
+  rc = forward_body(m, B, rcap);
   const hipError_t ce = hipStreamEndCapture(m->cap_stream, &g.graph);
   if (rc != PNVO_OK) {
     if (ce == hipSuccess && g.graph) (void)hipGraphDestroy(g.graph);
@@ -1728,30 +1703,28 @@ int forward_dispatch(pnvo_handle m, const float *rgb, const float *depth, const 
   }
   m->graphs.push_back(g);
   HIPCHK(m, hipGraphLaunch(g.exec, s));
-  HIPCHK(m, hipMemcpyAsync(out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
-  return pnvo_mark_stem(m, s, false);
+  HIPCHK(m, hipMemcpyAsync(r.out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
+  return pnvo_mark_stem(m, s, sp);
 }
 }  // namespace
 
 namespace {
-int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, const float *sh, const int64_t *actions, float *out, hipStream_t s);
-bool fc_rows_usable(pnvo_handle m, int B);
+// (r.actions, r.out, r.features_only, r.s of the request; the rows of `comp_raw` are the caller's to say)
+int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, const float *sh, const FwdRequest &r);
+bool fc_rows_usable(pnvo_handle m, int B, const FwdRequest &r);
 int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, int B, const float *comp_raw, const float *sc, const float *sh,
-                const int64_t *actions, float *out, hipStream_t s);
+                const FwdRequest &r);
 
-// grp: a grouped forward's models (pnvo_forward_grouped_raw), or nullptr
-int forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                 const int64_t *actions, int B, float *out, hipStream_t s, const GroupedFwd *grp) {
+int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
   const pnvo_config &c = m->cfg;
+  const GroupedFwd *grp = r.grp;
+  hipStream_t s = r.s;
   int rc = PNVO_OK;
   // (a4+a5+a6) input assembly + /255 + whitening are fused into the stem kernel's operand fetch (pnvo_run_stem): the
   // [B,H,W,30] tensor of the reference (vo_cnn.py:174-176) is never materialised.
   if (m->tap_dst != nullptr && m->tap_name == "input") {   // introspection only: materialise it for the tap
     AssembleArgs a;
-    a.src[0] = rgb;
-    a.src[1] = depth;
-    a.src[2] = dd;
-    a.src[3] = tdv;
+    for (int k = 0; k < 4; ++k) a.src[k] = r.src[k];
     a.nsrc[0] = c.n_rgb;
     a.nsrc[1] = c.n_depth;
     a.nsrc[2] = c.n_dd;
@@ -1773,26 +1746,26 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   // first block's first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs
   // (conv_x3 MODE 3).  PNVO_POOL=separate, taps, Bottleneck models and the other stem kernels keep the pass.
   float *cur = m->bufY[0], *nxt = m->bufY[1];
-  const bool pool_fused = !m->bottleneck && pnvo_stem_on_mx(m, false) && m->opt.pool && m->convs.size() > 1 &&
+  const StemPlan sp = pnvo_stem_plan(m, false, r.raw);
+  const bool pool_fused = !m->bottleneck && sp.pools() && m->opt.pool && m->convs.size() > 1 &&
                           stem.coutp == stem.cout && pnvo_conv_takes_tail(m, m->convs[1], B);
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
-  const bool small = !pool_fused && stem_writes_slots(m) && pnvo_small_usable(m, B);
+  const bool small = !pool_fused && sp.writes_slots() && pnvo_small_usable(m, B);
+  StemRequest sr{.src = {r.src[0], r.src[1], r.src[2], r.src[3]}, .raw = r.raw, .y = m->stem_raw, .ss = m->ssA, .grp = grp, .s = s};
   if (small) {
-    const float *src[4] = {rgb, depth, dd, tdv};
-    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, nullptr, false, true, grp)) != PNVO_OK) return rc;
-    return pnvo_small_forward(m, B, c.act_embed ? actions : nullptr, out, s);
+    int stem_slots = 0;
+    sr.slots_out = &stem_slots;
+    sr.skip_finalize = true;
+    if ((rc = pnvo_run_stem(m, B, sr)) != PNVO_OK) return rc;
+    return pnvo_small_forward(m, B, r, stem_slots);
   }
-  {
-    const float *src[4] = {rgb, depth, dd, tdv};
-    if (pool_fused) {
-      Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
-      HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
-    }
-    if ((rc = pnvo_run_stem(m, B, src, m->stem_raw, m->ssA, nullptr, nullptr, s, pool_fused ? reinterpret_cast<int *>(nxt) : nullptr, false,
-                            false, grp)) != PNVO_OK)
-      return rc;
+  if (pool_fused) {
+    Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
+    HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
+    sr.pool_keys = reinterpret_cast<int *>(nxt);
   }
+  if ((rc = pnvo_run_stem(m, B, sr)) != PNVO_OK) return rc;
   if ((rc = maybe_tap(m, "stem_conv", m->stem_raw, (size_t)B * m->Hs * m->Ws * stem.coutp, s)) != PNVO_OK) return rc;
   if (!pool_fused) {
     Timed t(m, s, "gn_relu_maxpool", 0.0, 4.0 * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * stem.coutp);
@@ -1918,44 +1891,46 @@ int forward_body(pnvo_handle m, const float *rgb, const float *depth, const floa
   // weights, bias rows and split-K scratch; the sample ranges are contiguous)
   if (grp != nullptr) {
     bool rows_ok = !c.act_embed;
-    for (int k = 0; k < grp->n; ++k) rows_ok = rows_ok && fc_rows_usable(grp->h[k], B);
-    if (rows_ok) return run_fc_rows(m, grp->h, grp->end, grp->n, B, m->comp_raw, m->ssC[0], m->ssC[1], nullptr, out, s);
+    FwdRequest rk = r;                   // model k's rows of the output; no act-embed models in a grouped forward
+    rk.actions = nullptr;
+    for (int k = 0; k < grp->n; ++k) rows_ok = rows_ok && fc_rows_usable(grp->h[k], B, rk);
+    if (rows_ok) return run_fc_rows(m, grp->h, grp->end, grp->n, B, m->comp_raw, m->ssC[0], m->ssC[1], rk);
     int start = 0;
     for (int k = 0; k < grp->n; ++k) {
       const int Bk = grp->end[k] - start;
       pnvo_handle hk = grp->h[k];
       if (k > 0 && (rc = ensure_workspace(hk, Bk)) != PNVO_OK) return fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk));
       const size_t crow = (size_t)m->fh * m->fw * m->comp_cp;
-      rc = run_fc_head(hk, Bk, m->comp_raw + start * crow, m->ssC[0] + (size_t)start * m->comp_cp, m->ssC[1] + (size_t)start * m->comp_cp,
-                       nullptr, out + (size_t)start * c.out_dim, s);
+      rk.out = r.out + (size_t)start * c.out_dim;
+      rc = run_fc_head(hk, Bk, m->comp_raw + start * crow, m->ssC[0] + (size_t)start * m->comp_cp, m->ssC[1] + (size_t)start * m->comp_cp, rk);
       if (rc != PNVO_OK) return k > 0 ? fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk)) : rc;
       start = grp->end[k];
     }
     return PNVO_OK;
   }
-  return run_fc_head(m, B, m->comp_raw, m->ssC[0], m->ssC[1], actions, out, s);
+  return run_fc_head(m, B, m->comp_raw, m->ssC[0], m->ssC[1], r);
 }
 
 // fc_rows.hip takes the two Linear layers of this handle at B samples (inference handles on float32, default kernels)
-bool fc_rows_usable(pnvo_handle m, int B) {
+bool fc_rows_usable(pnvo_handle m, int B, const FwdRequest &r) {
   const long kp = (long)m->fh * m->fw * m->comp_cp;
   return m->opt.fc_rows >= B && B >= 1 && m->fc_rows_w != nullptr && m->train == nullptr && m->precision == 0 && m->opt.conv == 0 &&
          m->comp_cp > 0 && 256 % m->comp_cp == 0 && kp % 4 == 0 && kp / 4 <= 64L * FC_ROWS_MAXV && m->cfg.hidden % 4 == 0 &&
-         (m->features_only || m->head_w_plain != nullptr);
+         (r.features_only || m->head_w_plain != nullptr);
 }
 
 // ... of up to three handles (a grouped forward: grp[k] serves the samples up to end[k]) in one launch each
 int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, int B, const float *comp_raw, const float *sc, const float *sh,
-                const int64_t *actions, float *out, hipStream_t s) {
+                const FwdRequest &r) {
   const pnvo_config &c = m->cfg;
   FcRowsArgs a;
   std::memset(&a, 0, sizeof(a));
   a.x = comp_raw;
   a.sc = sc;
   a.sh = sh;
-  a.hid = m->features_only ? out : m->hid;
-  a.out = out;
-  a.actions = c.act_embed ? actions : nullptr;
+  a.hid = r.features_only ? r.out : m->hid;
+  a.out = r.out;
+  a.actions = c.act_embed ? r.actions : nullptr;
   a.B = B;
   a.Kp = m->fh * m->fw * m->comp_cp;
   a.cp = m->comp_cp;
@@ -1969,33 +1944,35 @@ int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, i
     a.head_w[k] = grp[k]->head_w_plain;
     a.head_b[k] = grp[k]->head_bias;
   }
-  Timed t(m, s, "conv:" + m->fc.name, 2.0 * B * (double)a.Kp * c.hidden, 4.0 * ng * (double)a.Kp * c.hidden);
-  HIPCHK(m, launch_fc_rows(a, !m->features_only, s));
+  Timed t(m, r.s, "conv:" + m->fc.name, 2.0 * B * (double)a.Kp * c.hidden, 4.0 * ng * (double)a.Kp * c.hidden);
+  HIPCHK(m, launch_fc_rows(a, !r.features_only, r.s));
   return PNVO_OK;
 }
 
 // The hidden layer and the output head of handle m on B rows of the compression output.
-int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, const float *sh, const int64_t *actions, float *out, hipStream_t s) {
+int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, const float *sh, const FwdRequest &r) {
   const pnvo_config &c = m->cfg;
+  float *out = r.out;
+  hipStream_t s = r.s;
   int rc = PNVO_OK;
-  if (fc_rows_usable(m, B)) {
+  if (fc_rows_usable(m, B, r)) {
     pnvo_handle one[1] = {m};
     const int end[1] = {B};
-    if ((rc = run_fc_rows(m, one, end, 1, B, comp_raw, sc, sh, actions, out, s)) != PNVO_OK) return rc;
-    return m->features_only ? PNVO_OK : maybe_tap(m, "hidden", m->hid, (size_t)B * c.hidden, s);
+    if ((rc = run_fc_rows(m, one, end, 1, B, comp_raw, sc, sh, r)) != PNVO_OK) return rc;
+    return r.features_only ? PNVO_OK : maybe_tap(m, "hidden", m->hid, (size_t)B * c.hidden, s);
   }
   // the output head rides on the hidden layer's split-K reduction when there is one (option head_fuse); with a training step attached
   // the head's weight is read where the optimiser keeps it (the flat parameter buffer), the bias from its re-packed copy
   bool head_rode = false;
   const float *head_w = m->train != nullptr ? pnvo_train_weight_ptr(m, "output_head.1.weight") : m->head_w_plain;   // (OIHW of a 1x1 conv = [out_dim][hidden])
-  float *head_out = (m->opt.head_fuse && !m->features_only && c.out_dim <= 4 && head_w != nullptr) ? out : nullptr;
+  float *head_out = (m->opt.head_fuse && !r.features_only && c.out_dim <= 4 && head_w != nullptr) ? out : nullptr;
   if ((rc = pnvo_run_conv(m, m->fc, B, {.x = comp_raw, .in_scale = sc, .in_shift = sh, .y = m->hid, .y_cstride = c.hidden, .bias = m->fc_bias,
-                                        .bias_row = c.act_embed ? actions : nullptr, .relu_out = 1, .head_w = head_w, .head_out = head_out,
+                                        .bias_row = c.act_embed ? r.actions : nullptr, .relu_out = 1, .head_w = head_w, .head_out = head_out,
                                         .head_rode = &head_rode, .s = s})) != PNVO_OK)
     return rc;
   if ((rc = maybe_tap(m, "hidden", m->hid, (size_t)B * c.hidden, s)) != PNVO_OK) return rc;
   if (head_rode) return PNVO_OK;
-  if (m->features_only) {                          // pnvo_forward_features: `out` receives the hidden vector
+  if (r.features_only) {                           // pnvo_forward_features: `out` receives the hidden vector
     HIPCHK(m, hipMemcpyAsync(out, m->hid, (size_t)B * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
     return PNVO_OK;
   }
@@ -2007,9 +1984,10 @@ namespace {
 // Can this call run on the RAW stager (frames straight into the stem)?  Else the raw entry materialises the observation pairs
 // (pnvo_build_obs_pairs into a workspace of the handle) and takes the ordinary path: same results, the old cost.
 bool raw_direct(pnvo_handle m, const float *depth_frames) {
-  if (depth_frames == nullptr || !m->mx_ok || m->dense_sticky || m->opt.stem > 1 || m->tap_dst != nullptr) return false;
+  const StemPlan sp = pnvo_stem_plan(m, false, {});
+  if (depth_frames == nullptr || !sp.raw_stager() || m->tap_dst != nullptr) return false;
   if (m->precision == 1) return true;                                // bf16 path: its stem is the mx kernel (PIECES = 1)
-  return m->opt.pieces == 2 && m->mx_wpk2 != nullptr && (m->train == nullptr || m->weights_gen == m->weights_gen_at_load);
+  return sp.h2_from_host;     // (not sp.pieces == 2: the RAW stager is not built for the training step's device-side re-pack)
 }
 
 int raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, int B, int32_t *err_flag, hipStream_t s) {
@@ -2047,23 +2025,17 @@ int pnvo_forward_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *dept
     return pnvo_forward(m, c.n_rgb ? m->rawws[0] : nullptr, c.n_depth ? m->rawws[1] : nullptr, c.n_dd ? m->rawws[2] : nullptr, tdv,
                         actions, B, out, stream);
   }
-  m->raw_rgb = rgb_frames;
-  m->raw_depth = depth_frames;
-  m->raw_err = err_flag;
-  int rc;
+  const FwdRequest r{.src = {nullptr, nullptr, nullptr, tdv}, .raw = {rgb_frames, depth_frames, err_flag}, .actions = actions, .out = out, .s = s};
   if (m->precision == 1) {
     pnvo_handle hs[1] = {m};
     float *outs[1] = {out};
-    rc = pnvo_forward_bf16(hs, 1, nullptr, nullptr, nullptr, tdv, actions, B, outs, s);
-  } else {
-    rc = ensure_workspace(m, B);
-    // (frames are uint8 / the one-hot is derived in the stager: nothing for the input-contract check to find — no stem event)
-    if (rc == PNVO_OK) rc = forward_dispatch(m, nullptr, nullptr, nullptr, tdv, actions, B, out, s);
-    m->stem_ev_pending = false;
+    return pnvo_forward_bf16(hs, 1, B, r, outs);
   }
-  m->raw_rgb = nullptr;
-  m->raw_depth = nullptr;
-  m->raw_err = nullptr;
+  int rc = ensure_workspace(m, B);
+  // (frames are uint8 / the one-hot is derived in the stager: nothing for the input-contract check to find — no stem event; one
+  //  left pending by an earlier forward that failed between its stem and its wait is dropped here)
+  if (rc == PNVO_OK) rc = forward_dispatch(m, B, r);
+  m->stem_ev_pending = false;
   return rc;
 }
 
@@ -2081,8 +2053,9 @@ int pnvo_grouped_supported(const pnvo_handle *hs, int n) {
     if (!h->loaded) return fail(m, PNVO_ERR_STATE, "grouped forward before pnvo_load_weights");
     if (std::memcmp(&h->cfg, &c, sizeof(pnvo_config)) != 0 || h->device != m->device)
       return fail(m, PNVO_ERR_ARG, "the models of a grouped forward must share architecture and device");
-    if (h->precision != 0 || h->train != nullptr || h->bottleneck || c.act_embed || h->dense_sticky || h->opt.pieces != 2 || !h->mx_ok ||
-        h->mx_wpk2 == nullptr || h->tap_dst != nullptr || h->opt.stem > 1 || !h->opt.pool || !h->opt.tail || h->opt.conv > 1)
+    const StemPlan sp = pnvo_stem_plan(h, false, {});
+    if (h->precision != 0 || h->train != nullptr || h->bottleneck || c.act_embed || !sp.raw_stager() || !sp.h2_from_host ||
+        h->tap_dst != nullptr || !h->opt.pool || !h->opt.tail || h->opt.conv > 1)
       return fail(m, PNVO_ERR_STATE, "grouped forward needs float32 inference handles on the default float16-piece kernels (no training step, "
                                      "no tap, no act-embed, options pieces=2 / stem=auto / conv=auto / pool / tail at their defaults)");
     for (size_t li = 1; li < h->convs.size(); ++li)
@@ -2132,14 +2105,8 @@ int pnvo_forward_grouped_raw(const pnvo_handle *handles, const int32_t *counts, 
   m->opt.x3_persist = 0;
   GroupedFwd grp{ng, {hs[0], hs[1], hs[2]}, {0, 0, 0}};
   for (int k = 0, acc = 0; k < ng; ++k) grp.end[k] = acc += cnt[k];
-  m->raw_rgb = rgb_frames;
-  m->raw_depth = depth_frames;
-  m->raw_err = err_flag;
-  rc = forward_body(m, nullptr, nullptr, nullptr, tdv, nullptr, B, out, s, &grp);
-  m->stem_ev_pending = false;
-  m->raw_rgb = nullptr;
-  m->raw_depth = nullptr;
-  m->raw_err = nullptr;
+  rc = forward_body(m, B, {.src = {nullptr, nullptr, nullptr, tdv}, .raw = {rgb_frames, depth_frames, err_flag}, .out = out, .grp = &grp, .s = s});
+  m->stem_ev_pending = false;            // (as in pnvo_forward_raw)
   m->opt = saved;
   return rc;
 }
@@ -2166,16 +2133,9 @@ int pnvo_forward_dual_raw(pnvo_handle ha, pnvo_handle hb, const uint8_t *rgb_fra
     return pnvo_forward_dual(ha, hb, c.n_rgb ? ha->rawws[0] : nullptr, c.n_depth ? ha->rawws[1] : nullptr,
                              c.n_dd ? ha->rawws[2] : nullptr, tdv, B, out_a, out_b, stream);
   }
-  ha->raw_rgb = rgb_frames;
-  ha->raw_depth = depth_frames;
-  ha->raw_err = err_flag;
   pnvo_handle hs[2] = {ha, hb};
   float *outs[2] = {out_a, out_b};
-  const int rc = pnvo_forward_bf16(hs, 2, nullptr, nullptr, nullptr, tdv, nullptr, B, outs, s);
-  ha->raw_rgb = nullptr;
-  ha->raw_depth = nullptr;
-  ha->raw_err = nullptr;
-  return rc;
+  return pnvo_forward_bf16(hs, 2, B, {.src = {nullptr, nullptr, nullptr, tdv}, .raw = {rgb_frames, depth_frames, err_flag}, .s = s}, outs);
 }
 
 int pnvo_forward_features(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
@@ -2191,13 +2151,11 @@ int pnvo_forward_features(pnvo_handle m, const float *rgb, const float *depth, c
   HIPCHK(m, hipSetDevice(m->device));
   int rc = ensure_workspace(m, B);
   if (rc != PNVO_OK) return rc;
-  m->features_only = true;
-  rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream, nullptr);
+  const FwdRequest r{.src = {rgb, depth, dd, tdv}, .actions = actions, .out = hidden_out, .features_only = true, .s = (hipStream_t)stream};
+  if ((rc = forward_body(m, B, r)) != PNVO_OK) return rc;
   bool rerun = false;
-  if (rc == PNVO_OK) rc = pnvo_input_fallback(m, (hipStream_t)stream, &rerun);
-  if (rc == PNVO_OK && rerun) rc = forward_body(m, rgb, depth, dd, tdv, actions, B, hidden_out, (hipStream_t)stream, nullptr);
-  m->features_only = false;
-  return rc;
+  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
+  return rerun ? forward_body(m, B, r) : PNVO_OK;
 }
 
 int pnvo_discretize_depth(const float *depth, int64_t n, int64_t in_stride, int bins, float *onehot,
@@ -2516,7 +2474,7 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
     const Layer &l = h->convs[li];
     if (l.name != name) continue;
     const double alg = 2.0 * B * l.hout * l.wout * (double)l.cout * l.cin * l.k * l.kw;
-    if (stem_writes_slots(h) && pnvo_small_usable(h, B)) {      // a phase of the persistent small-batch kernel (fp32 MFMA)
+    if (pnvo_stem_plan(h, false, {}).writes_slots() && pnvo_small_usable(h, B)) {      // a phase of the persistent small-batch kernel (fp32 MFMA)
       std::snprintf(family, cap, "smallnet");
       if (executed_flops) {
         const int mb = l.cinp >= 128 ? 1 : l.cinp >= 64 ? 2 : 4, th = mb == 4 ? 8 : 4, tw = mb == 1 ? 4 : 8;

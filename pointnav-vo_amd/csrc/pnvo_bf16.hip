@@ -179,9 +179,9 @@ void pnvo_bf16_free(pnvo_handle m) {
   m->bf = nullptr;
 }
 
-int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                      const int64_t *actions, int B, float *const *outs, hipStream_t s) {
+int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float *const *outs) {
   pnvo_handle m = hs[0];
+  hipStream_t s = r.s;
   Bf16State *bs[2] = {nullptr, nullptr};
   int rc;
   for (int z = 0; z < nm; ++z) {
@@ -203,12 +203,7 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *de
   {
     StemMXArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.src[0] = rgb;
-    a.src[1] = depth;
-    a.src[2] = dd;
-    a.src[3] = tdv;
-    pnvo_stem_raw_args(m, a);                                    // (pnvo_forward_raw: sensor frames instead of src[0..2])
-    a.zero_page = m->mx_pages;
+    pnvo_stem_mx_input(m, B, r.src, r.raw, a);                   // (pnvo_forward_raw: sensor frames instead of src[0..2])
     a.wpk = nm == 2 ? bs[0]->dual_stem : bs[0]->stem_wpk;
     for (int z = 0; z < nm; ++z) {
       a.y[z] = bs[z]->stem_raw;
@@ -217,22 +212,10 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *de
     }
     a.y_cstride = 32;
     a.stats_cstride = 32;
-    a.B = B;
-    a.H = c.height;
-    a.W = c.width;
-    a.Ho = m->Hs;
-    a.Wo = m->Ws;
-    a.slots = stem_mx_slots(m->Hs, m->Ws);
     const double M = (double)B * m->Hs * m->Ws;
     {
-      const double in_bytes = (double)B * c.height * c.width * (m->raw_depth ? (c.n_rgb ? 6.0 : 0.0) + 8.0 + (c.n_tdv ? 8.0 : 0.0) : 4.0 * stem.cin);
-      PnvoTimed t(m, s, "bf16:stem", 2.0 * nm * M * stem.cout * stem.cin * 49, in_bytes + 2.0 * nm * M * stem.cout);
-      if ((m->opt.stem_form == 0 || m->opt.stem_form == 3 || m->opt.stem_form == 4) && stem_rs_takes(a, 1, nm, true, m->num_cus)) {
-        // two models: the dual stem with its 196 KB of weight fragments resident in registers (stem_rs.hip), bit-identical
-        HIPCHK(m, launch_stem_rs(a, 1, false, m->num_cus, s));
-      } else {
-        HIPCHK(m, launch_stem_mx(a, 1, nm, true, s));
-      }
+      PnvoTimed t(m, s, "bf16:stem", 2.0 * nm * M * stem.cout * stem.cin * 49, pnvo_stem_in_bytes(m, B, r.raw) + 2.0 * nm * M * stem.cout);
+      if ((rc = pnvo_launch_stem_mx(m, a, 1, nm, true, nullptr, s)) != PNVO_OK) return rc;
     }
     PnvoTimed t(m, s, "bf16:gn_finalize", 0.0, 0.0);
     auto st = each([&](int z) { return (const float *)bs[z]->stats; });
@@ -418,7 +401,7 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *de
     bool head_rode = false;
     const float *head_w = h->train != nullptr ? nullptr : h->head_w_plain;
     rc = pnvo_run_conv(h, h->fc, B, {.x = bs[z]->comp_raw, .in_scale = bs[z]->ssC[0], .in_shift = bs[z]->ssC[1], .y = bs[z]->hid,
-                                     .y_cstride = c.hidden, .bias = h->fc_bias, .bias_row = c.act_embed ? actions : nullptr, .relu_out = 1,
+                                     .y_cstride = c.hidden, .bias = h->fc_bias, .bias_row = c.act_embed ? r.actions : nullptr, .relu_out = 1,
                                      .head_w = head_w, .head_out = (h->opt.head_fuse && c.out_dim <= 4 && head_w != nullptr) ? outs[z] : nullptr,
                                      .head_rode = &head_rode, .s = s});
     if (rc == PNVO_OK && !head_rode)

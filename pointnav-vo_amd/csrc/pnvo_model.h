@@ -126,10 +126,6 @@ struct pnvo_model_s {
   float *stats_ds = nullptr;                 // GroupNorm partials of a downsample conv riding on its block's first conv (stats_floats)
   hipEvent_t stem_ev = nullptr;              // recorded behind a contract-checking stem launch (pnvo_mark_stem)
   bool stem_ev_pending = false;
-  // pnvo_forward_raw / pnvo_forward_dual_raw: sensor frames of the call in flight (the stem's RAW stager reads them)
-  const unsigned char *raw_rgb = nullptr;
-  const float *raw_depth = nullptr;
-  int *raw_err = nullptr;
   float *rawws[3] = {nullptr, nullptr, nullptr};   // rgb / depth / dd pair tensors of the materialising fallback of the raw entry
   int rawws_cap = 0;
   int precision = 0;                         // pnvo_set_precision: 0 float32 (default), 1 bfloat16 (BASELINE config 3)
@@ -137,7 +133,7 @@ struct pnvo_model_s {
   unsigned long long weights_gen_at_load = 0;  // weights_gen as pnvo_load_weights left it
   unsigned long long uid = 0;                // process-unique handle id (cache keys that must not alias a re-used address)
   unsigned long long weights_gen = 0;        // bumped by pnvo_load_weights AND by every pnvo_train_refresh (conv_x3 operands)
-  void *bf = nullptr;                        // Bf16State (pnvo_bf16.hip)             // set by pnvo_train_forward: its stem operands are rebuilt on the device
+  void *bf = nullptr;                        // Bf16State (pnvo_bf16.hip)
 
   int cap = 0;                       // batch the workspace is sized for
   float *xin = nullptr, *stem_raw = nullptr, *bufY[2] = {nullptr, nullptr};
@@ -154,10 +150,8 @@ struct pnvo_model_s {
   float *tap_dst = nullptr;
   size_t tap_cap = 0;
 
-  bool features_only = false;        // pnvo_forward_features: stop after the hidden layer
   void *train = nullptr;             // TrainState (pnvo_train_api.hip), present after pnvo_train_attach
   void *small = nullptr;             // SmallNet (smallnet.hip): the persistent small-batch kernel's operands, built on first use
-  int stem_slots_out = 0;            // statistics slots per sample the last stem launch wrote into `stats` ([B][slots][CP][2])
 
   // Opt-in (PNVO_GRAPH=1): the whole forward (~60 launches) captured once per (batch, tensor addresses, kernel
   // selection) into a hipGraph and replayed (see pnvo_forward for the measurement that keeps it off by default).
@@ -233,18 +227,72 @@ struct ConvRequest {
   hipStream_t s = nullptr;
 };
 
+// Sensor frames of a raw entry (pnvo_forward_raw, pnvo_forward_grouped_raw, pnvo_forward_dual_raw): the stem's RAW stager reads them
+// instead of the rgb / depth / discretised-depth pair tensors.
+struct RawFrames {
+  const unsigned char *rgb = nullptr;        // [B][2][H][W][3] uint8, or nullptr (model without rgb)
+  const float *depth = nullptr;              // [B][2][H][W]; non-null: the call runs on sensor frames
+  int *err = nullptr;                        // device flag: a depth outside [0, 1]
+};
+
+// Which stem a forward of this handle launches and what follows from that.  The rule is written once, in pnvo_stem_plan; the stem
+// launch, the workspace, the pooled-key and small-batch paths, the raw and grouped entries and pnvo_layer_kernel read this value.
+struct StemPlan {
+  // whose place in the forward and whose statistics-slot layout: stem_mx.hip / stem_rs.hip, stem_dd.hip, stem_lds.hip, pnvo_run_conv
+  enum Kernel { MX, DD, LDS, GENERIC } kernel = GENERIC;
+  bool lds_serves = false;   // stem_lds.hip serves this model: the kernel the input-contract repair and the stand-in run
+  bool standin = false;      // dense_sticky: stem_lds_kernel<.., PAIRED> launches in the MX / DD stem's place
+  bool repairs = false;      // a stand-in predicated on the contract flag follows the launch (decided on the device)
+  bool marks = false;        // pnvo_mark_stem has something to publish / record
+  int pieces = 3;            // MX: operand pieces, 2 float16 or 3 bf16
+  bool h2_from_host = false; // MX: option pieces=2 and the float16 operand as pnvo_load_weights packed it is current.  The raw and the
+                             //   grouped entries ask for this; `pieces` also takes the training step's device-side re-pack (mx_wpk2_dev)
+  int slots = 0;             // statistics slots per sample the launch leaves in m->stats ([B][slots][CP][2]); 0: GENERIC (no slots handed on)
+  bool writes_slots() const { return kernel != GENERIC; }   // per-tile statistics land in m->stats (smallnet.hip can take over)
+  bool pools() const { return kernel == MX; }               // can emit pooled keys
+  bool raw_stager() const { return kernel == MX && !standin; }   // sensor frames can go straight into the stem
+};
+
+// One stem launch of pnvo_run_stem (designated initializers, in this order).
+struct StemRequest {
+  const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // rgb | depth | dd | tdv pair tensors
+  RawFrames raw;
+  float *y = nullptr;                        // raw stem output
+  float *const *ss = nullptr;                // [2]: GroupNorm scale / shift
+  float *mu = nullptr, *rstd = nullptr;      // [B,groups] statistics for a backward pass, or nullptr
+  int *pool_keys = nullptr;                  // pooled order-preserving keys (MX only), or nullptr
+  bool train_fwd = false;                    // the training forward's stem
+  int *slots_out = nullptr;                  // receives the statistics slots per sample the launch wrote
+  bool skip_finalize = false;                // the consumer of those slots reduces them itself (smallnet.hip)
+  const GroupedFwd *grp = nullptr;
+  hipStream_t s = nullptr;
+};
+
+// One inference forward (forward_dispatch / forward_body, pnvo_forward_bf16, pnvo_small_forward, the Linear layers).
+struct FwdRequest {
+  const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // rgb | depth | dd | tdv pair tensors
+  RawFrames raw;
+  const int64_t *actions = nullptr;
+  float *out = nullptr;
+  bool features_only = false;                // pnvo_forward_features: stop after the hidden layer, `out` receives it
+  const GroupedFwd *grp = nullptr;           // a grouped forward's models (pnvo_forward_grouped_raw), or nullptr
+  hipStream_t s = nullptr;
+};
+
 // helpers implemented in pnvo_api.hip
 int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r);   // one conv + the GroupNorm finalisation that follows it
 bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B);   // would pnvo_run_conv(c1) carry cd as a DsRide?
 bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B);                        // would pnvo_run_conv(l) use conv_x3.hip?
 bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B);   // would pnvo_run_conv(l) accept a BlockTail (conv_x3 path)?
 void pnvo_pack_conv_weight_cinp(const float *oihw, int cout, int cin, int cinp, int kh, int kw, std::vector<float> &out);
-// train_fwd: the training forward's stem; skip_finalize: the consumer of the stem's statistics slots reduces them itself (smallnet.hip)
-int pnvo_run_stem(pnvo_handle m, int B, const float *const *src, float *y, float *const *ss, float *mu_out, float *rstd_out,
-                  hipStream_t s, int *pool_keys, bool train_fwd, bool skip_finalize, const GroupedFwd *grp);
-bool pnvo_stem_on_mx(pnvo_handle m, bool train_fwd);
-void pnvo_stem_raw_args(pnvo_handle m, pnvo::StemMXArgs &a);   // fills the RAW-stager fields of a stem launch when m->raw_depth is set
-int pnvo_mark_stem(pnvo_handle m, hipStream_t s, bool train_fwd);
+StemPlan pnvo_stem_plan(pnvo_handle m, bool train_fwd, const RawFrames &raw);
+int pnvo_run_stem(pnvo_handle m, int B, const StemRequest &r);   // the fused stem + the GroupNorm finalisation that follows it
+// the geometry and input side of a 16-bit-matrix-core stem launch (pair tensors or sensor frames), and the launch in the form option
+// stem_form selects — shared by the float32 forward and pnvo_bf16.hip
+void pnvo_stem_mx_input(pnvo_handle m, int B, const float *const *src, const RawFrames &raw, pnvo::StemMXArgs &a);
+double pnvo_stem_in_bytes(pnvo_handle m, int B, const RawFrames &raw);   // algorithmic bytes of the stem's input (timing table)
+int pnvo_launch_stem_mx(pnvo_handle m, const pnvo::StemMXArgs &a, int pieces, int ntiles, bool bf16_out, const GroupedFwd *grp, hipStream_t s);
+int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
 const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name);   // pnvo_train_api.hip: device pointer or nullptr
@@ -252,10 +300,9 @@ void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &
 const float *pnvo_train_x2_scale(pnvo_handle m, const std::string &name);     // device {scale, 1/scale} of that conv weight's float16 pieces, or nullptr
 void pnvo_bf16_free(pnvo_handle m);    // pnvo_bf16.hip
 bool pnvo_small_usable(pnvo_handle m, int B);   // smallnet.hip: does this call shape take the persistent kernel?
-int pnvo_small_forward(pnvo_handle m, int B, const int64_t *actions, float *out, hipStream_t s);
+int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots);   // stem_slots: as pnvo_run_stem left them in m->stats
 void pnvo_small_free(pnvo_handle m);
-int pnvo_forward_bf16(pnvo_handle *hs, int nm, const float *rgb, const float *depth, const float *dd, const float *tdv,
-                      const int64_t *actions, int B, float *const *outs, hipStream_t s);
+int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float *const *outs);   // outs[z]: model z's output (r.out unused)
 int pnvo_fail(pnvo_handle h, int code, const std::string &msg);
 void pnvo_free_dev(float *&p);
 int pnvo_ensure_workspace(pnvo_handle m, int B);

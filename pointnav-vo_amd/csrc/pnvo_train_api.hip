@@ -965,7 +965,9 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
   size_t li = 0;
   {
     ConvSave &cs = t->cs[li];
-    if ((rc = pnvo_run_stem(m, B, t->src, cs.raw, cs.ss, cs.mu, cs.rstd, s, nullptr, true, false, nullptr)) != PNVO_OK) return rc;
+    if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
+                                   .train_fwd = true, .s = s})) != PNVO_OK)
+      return rc;
     const Layer &stem = m->convs[li++];
     HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, stem.coutp, t->y[0], t->pool_idx, s));
   }

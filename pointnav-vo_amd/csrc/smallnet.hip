@@ -975,7 +975,7 @@ SnGN sn_gn(const Layer &l, const float *part, int slots) {
   return g;
 }
 
-int sn_build(pnvo_handle m, SmallNet *sn, int B) {
+int sn_build(pnvo_handle m, SmallNet *sn, int B, int stem_slots, bool features) {
   const pnvo_config &c = m->cfg;
   std::vector<SnPhase> ph;
   size_t need[4] = {0, 0, 0, 0};
@@ -1023,7 +1023,7 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
     p.Wo = m->Wp;
     p.in = m->stem_raw;
     p.out = m->bufY[0];
-    p.gin = sn_gn(stem, m->stats, m->stem_slots_out);
+    p.gin = sn_gn(stem, m->stats, stem_slots);
     p.gin.layout = 1;
     p.ntiles = sn->cus;
     ph.push_back(p);
@@ -1123,7 +1123,7 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
     p.bias = m->fc_bias;
     p.relu_out = 1;
     p.use_row = 1;
-    p.out = m->features_only ? nullptr : m->hid;   // pnvo_forward_features: the hidden vector IS the result (caller's tensor)
+    p.out = features ? nullptr : m->hid;   // pnvo_forward_features: the hidden vector IS the result (caller's tensor)
     ph.push_back(p);
     patch_floats = std::max(patch_floats, (size_t)B * p.K);
     SnPhase h;
@@ -1140,7 +1140,7 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
     h.bias = m->head_bias;
     h.relu_out = 0;
     h.out = nullptr;                               // the caller's tensor (SnArgs::final_out)
-    if (!m->features_only) {
+    if (!features) {
       ph.push_back(h);
       patch_floats = std::max(patch_floats, (size_t)B * h.K);
     }
@@ -1152,7 +1152,7 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
       sn->part_floats[k] = 0;
       HIPCHK(m, hipMalloc((void **)&sn->part[k], need[k] * sizeof(float)));
       sn->part_floats[k] = need[k];
-      return sn_build(m, sn, B);                   // pointers changed: lay the phases out again
+      return sn_build(m, sn, B, stem_slots, features);   // pointers changed: lay the phases out again
     }
   sn->lds_bytes = ((size_t)SN_FIXED_FLOATS + patch_floats) * sizeof(float);
   if (sn->lds_bytes > (size_t)156 * 1024) return -1;
@@ -1177,8 +1177,8 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
   HIPCHK(m, hipMemcpy(sn->ph_dev, ph.data(), ph.size() * sizeof(SnPhase), hipMemcpyHostToDevice));
   sn->ph = ph;
   sn->B = B;
-  sn->features = m->features_only;
-  sn->stem_slots = m->stem_slots_out;
+  sn->features = features;
+  sn->stem_slots = stem_slots;
   sn->ws_key[0] = m->stem_raw;
   sn->ws_key[1] = m->stats;
   sn->ws_key[2] = m->rawA;
@@ -1189,7 +1189,8 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B) {
 }  // namespace
 
 // Everything behind the stem conv (whose raw output is in m->stem_raw, its per-tile statistics in m->stats) for B pairs.
-int pnvo_small_forward(pnvo_handle m, int B, const int64_t *actions, float *out, hipStream_t s) {
+int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots) {
+  hipStream_t s = r.s;
   SmallNet *sn = static_cast<SmallNet *>(m->small);
   if (!sn) {
     sn = new SmallNet();
@@ -1212,10 +1213,10 @@ int pnvo_small_forward(pnvo_handle m, int B, const int64_t *actions, float *out,
     if ((rc = sn_pack_weights(m, sn)) != PNVO_OK) return rc;
     sn->B = -1;
   }
-  if (sn->B != B || sn->features != m->features_only || sn->stem_slots != m->stem_slots_out || sn->ws_key[0] != m->stem_raw || sn->ws_key[1] != m->stats ||
+  if (sn->B != B || sn->features != r.features_only || sn->stem_slots != stem_slots || sn->ws_key[0] != m->stem_raw || sn->ws_key[1] != m->stats ||
       sn->ws_key[2] != m->rawA || sn->ws_key[3] != m->fc_bias) {
     HIPCHK(m, hipStreamSynchronize(s));            // the table of an in-flight launch is about to be rewritten
-    rc = sn_build(m, sn, B);
+    rc = sn_build(m, sn, B, stem_slots, r.features_only);
     if (rc == -1) {
       sn->unsupported = true;
       return pnvo_fail(m, PNVO_ERR_STATE, "this model does not fit the small-batch kernel");
@@ -1233,9 +1234,9 @@ int pnvo_small_forward(pnvo_handle m, int B, const int64_t *actions, float *out,
   a.bar = sn->bar;
   a.bar_base = sn->bar_base;
   a.err = sn->err;
-  a.bias_row = actions;
-  a.final_out = out;
-  a.final_n = B * (m->features_only ? m->cfg.hidden : m->cfg.out_dim);
+  a.bias_row = m->cfg.act_embed ? r.actions : nullptr;
+  a.final_out = r.out;
+  a.final_n = B * (r.features_only ? m->cfg.hidden : m->cfg.out_dim);
   a.prof = nullptr;
   a.dbg = m->opt.small_prof;
   if (m->opt.small_prof) {
