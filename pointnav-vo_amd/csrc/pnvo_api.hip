@@ -113,34 +113,38 @@ void build_plan(pnvo_model_s *m) {
   const bool bott = c.backbone_depth == 50 || c.backbone_depth == 101;
   const int nblk[4] = {bott ? 3 : 2, bott ? 4 : 2, bott ? (c.backbone_depth == 101 ? 23 : 6) : 2, bott ? 3 : 2};
   m->bottleneck = bott;
-  m->nblocks.assign(nblk, nblk + 4);
-  for (int li = 1; li <= 4; ++li) {
-    const int planes = c.baseplanes << (li - 1);
-    for (int bi = 0; bi < nblk[li - 1]; ++bi) {
-      const std::string p = bb + "layer" + std::to_string(li) + "." + std::to_string(bi) + ".";
-      const int stride = (li > 1 && bi == 0) ? 2 : 1;
+  m->blocks.clear();
+  auto push = [&](Layer l) {                         // a conv of the block under construction
+    l.block = (int)m->blocks.size();
+    m->convs.push_back(l);
+    return (int)m->convs.size() - 1;
+  };
+  for (int st = 1; st <= 4; ++st) {
+    const int planes = c.baseplanes << (st - 1), cout = bott ? planes * 4 : planes;
+    for (int bi = 0; bi < nblk[st - 1]; ++bi) {
+      Block b;
+      b.stage = st;
+      b.index = bi;
+      b.tap = "layer" + std::to_string(st) + "." + std::to_string(bi);
+      const std::string p = bb + b.tap + ".";
+      const int stride = (st > 1 && bi == 0) ? 2 : 1;
       if (bott) {                                    // Bottleneck: 1x1 -> 3x3 (stride) -> 1x1 (x4), resnet.py:58-69
-        Layer b1 = make_layer(p + "convs.0", p + "convs.1", cin, planes, 1, 1, 0, h, w, g);
         Layer b2 = make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, stride, 1, h, w, g);
-        Layer b3 = make_layer(p + "convs.6", p + "convs.7", planes, planes * 4, 1, 1, 0, b2.hout, b2.wout, g);
-        m->convs.push_back(b1);
-        m->convs.push_back(b2);
-        m->convs.push_back(b3);
-        if (stride != 1 || cin != planes * 4)
-          m->convs.push_back(make_layer(p + "downsample.0", p + "downsample.1", cin, planes * 4, 1, stride, 0, h, w, g));
-        h = b2.hout;
-        w = b2.wout;
-        cin = planes * 4;
-        continue;
+        b.nconv = 3;
+        b.conv[0] = push(make_layer(p + "convs.0", p + "convs.1", cin, planes, 1, 1, 0, h, w, g));
+        b.conv[1] = push(b2);
+        b.conv[2] = push(make_layer(p + "convs.6", p + "convs.7", planes, cout, 1, 1, 0, b2.hout, b2.wout, g));
+      } else {
+        Layer c1 = make_layer(p + "convs.0", p + "convs.1", cin, planes, 3, stride, 1, h, w, g);
+        b.nconv = 2;
+        b.conv[0] = push(c1);
+        b.conv[1] = push(make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, 1, 1, c1.hout, c1.wout, g));
       }
-      Layer c1 = make_layer(p + "convs.0", p + "convs.1", cin, planes, 3, stride, 1, h, w, g);
-      m->convs.push_back(c1);
-      m->convs.push_back(make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, 1, 1, c1.hout, c1.wout, g));
-      if (stride != 1 || cin != planes)
-        m->convs.push_back(make_layer(p + "downsample.0", p + "downsample.1", cin, planes, 1, stride, 0, h, w, g));
-      h = c1.hout;
-      w = c1.wout;
-      cin = planes;
+      if (stride != 1 || cin != cout) b.ds = push(make_layer(p + "downsample.0", p + "downsample.1", cin, cout, 1, stride, 0, h, w, g));
+      m->blocks.push_back(b);
+      h = m->last(b).hout;
+      w = m->last(b).wout;
+      cin = cout;
     }
   }
   m->fh = h;
@@ -153,6 +157,7 @@ void build_plan(pnvo_model_s *m) {
     if (q - fl == 0.5) m->comp_c = ((long)fl % 2 == 0) ? (int)fl : (int)fl + 1;
   }
   m->comp_cp = rup(m->comp_c, 32);
+  m->comp = (int)m->convs.size();
   m->convs.push_back(make_layer("visual_encoder.compression.0", "visual_encoder.compression.1", cin, m->comp_c, 3, 1, 1,
                                 h, w, 1));
   // Linear(flat -> hidden) as a valid (pad 0) fh x fw "conv" over the channel-padded compression map
@@ -492,24 +497,18 @@ void pnvo_drop_graphs(pnvo_handle m) {
 void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &)> &gn_bound) {
   if (h->bottleneck || h->convs.empty()) return;
   float bin = gn_bound(h->convs[0]);                         // pooled stem output
-  size_t li = 1;
-  for (int stage = 1; stage <= 4; ++stage)
-    for (int bi = 0; bi < h->nblocks[stage - 1]; ++bi) {
-      if (li + 1 >= h->convs.size()) return;
-      Layer &c1 = h->convs[li++];
-      Layer &c2 = h->convs[li++];
-      const bool ds = li < h->convs.size() && h->convs[li].name.find("downsample") != std::string::npos;
-      c1.in_bound = bin;
-      c2.in_bound = gn_bound(c1);
-      float skip = bin;
-      if (ds) {
-        Layer &cd = h->convs[li++];
-        cd.in_bound = bin;
-        skip = gn_bound(cd);
-      }
-      bin = gn_bound(c2) + skip;
+  for (const Block &b : h->blocks) {
+    Layer &c1 = h->convs[b.conv[0]], &c2 = h->convs[b.conv[1]];
+    c1.in_bound = bin;
+    c2.in_bound = gn_bound(c1);
+    float skip = bin;
+    if (b.ds >= 0) {
+      h->convs[b.ds].in_bound = bin;
+      skip = gn_bound(h->convs[b.ds]);
     }
-  if (li < h->convs.size()) h->convs[li].in_bound = bin;      // the compression conv reads the last block's output
+    bin = gn_bound(c2) + skip;
+  }
+  h->convs[h->comp].in_bound = bin;                          // the compression conv reads the last block's output
 }
 
 bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B) {
@@ -1740,15 +1739,14 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
     HIPCHK(m, launch_assemble(a, s));
     if ((rc = maybe_tap(m, "input", m->xin, (size_t)B * c.height * c.width * m->CP, s)) != PNVO_OK) return rc;
   }
-  size_t li = 0;
-  const Layer &stem = m->convs[li++];
+  const Layer &stem = m->convs[0];
   // (a7) GN + ReLU + maxpool.  Default: no pass at all — the stem writes pooled order-preserving keys (stem_mx.hip POOL), the
   // first block's first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs
   // (conv_x3 MODE 3).  PNVO_POOL=separate, taps, Bottleneck models and the other stem kernels keep the pass.
   float *cur = m->bufY[0], *nxt = m->bufY[1];
   const StemPlan sp = pnvo_stem_plan(m, false, r.raw);
-  const bool pool_fused = !m->bottleneck && sp.pools() && m->opt.pool && m->convs.size() > 1 &&
-                          stem.coutp == stem.cout && pnvo_conv_takes_tail(m, m->convs[1], B);
+  const bool pool_fused = !m->bottleneck && sp.pools() && m->opt.pool && stem.coutp == stem.cout &&
+                          pnvo_conv_takes_tail(m, m->convs[m->blocks[0].conv[0]], B);
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
   const bool small = !pool_fused && sp.writes_slots() && pnvo_small_usable(m, B);
@@ -1776,104 +1774,100 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
   // (a8) residual stages
   BlockTail tail{};
   bool have_tail = false, have_keys = pool_fused;
-  for (int stage = 1; stage <= 4; ++stage) {
-    for (int bi = 0; bi < m->nblocks[stage - 1]; ++bi) {
-      if (m->bottleneck) {                           // conv1x1 -> GN -> ReLU -> conv3x3(s) -> GN -> ReLU -> conv1x1 -> GN
-        const Layer &b1 = m->convs[li++];
-        const Layer &b2 = m->convs[li++];
-        const Layer &b3 = m->convs[li++];
-        const bool dsb = (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos);
-        if ((rc = pnvo_run_conv(m, b1, B, {.x = cur, .y = m->rawA, .y_cstride = b1.coutp, .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK ||
-            (rc = pnvo_run_conv(m, b2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawC, .y_cstride = b2.coutp,
-                                           .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK ||
-            (rc = pnvo_run_conv(m, b3, B, {.x = m->rawC, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawB, .y_cstride = b3.coutp,
-                                           .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK)
-          return rc;
-        const long Pb = (long)b3.hout * b3.wout;
-        if (dsb) {
-          const Layer &cd = m->convs[li++];
-          if ((rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
-            return rc;
-          Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-          HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
-        } else {
-          Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-          HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], cur, nullptr, nullptr, B, Pb, b3.coutp, nxt, s));
-        }
-        std::swap(cur, nxt);
-        const std::string tnb = "layer" + std::to_string(stage) + "." + std::to_string(bi);
-        if ((rc = maybe_tap(m, tnb.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
-        continue;
-      }
-      const Layer &c1 = m->convs[li++];
-      const Layer &c2 = m->convs[li++];
-      const bool ds = (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos);
-      // the block's downsample conv rides on c1's launch (conv_x3_kernel DSF): no launch, no finalisation of its own, and in the
-      // block-tail mode the block input is not written to HBM at all — c1 and the downsample conv are its only readers
-      const bool ds_ride = ds && !have_keys && pnvo_conv_takes_ds(m, c1, m->convs[li], B);
-      const DsRide ride{ds_ride ? &m->convs[li] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
-      if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
-        BlockTail ktail{nullptr, nullptr, nullptr, cur};
-        if ((rc = pnvo_run_conv(m, c1, B, {.x = nxt, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawA, .y_cstride = c1.coutp,
-                                           .ss = m->ssA, .tail = &ktail, .grp = grp, .s = s})) != PNVO_OK)
-          return rc;
-        have_keys = false;
-      } else if (have_tail) {    // the previous block's tail rides on this conv's stager, which also writes the block output
-        if (ds_ride) tail.out = nullptr;                       // (nobody else reads this block's input)
-        if ((rc = pnvo_run_conv(m, c1, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawA, .y_cstride = c1.coutp,
-                                           .ss = m->ssA, .tail = &tail, .ride = ds_ride ? &ride : nullptr, .grp = grp, .s = s})) != PNVO_OK)
-          return rc;
-        std::swap(cur, nxt);
-        have_tail = false;
-      } else if ((rc = pnvo_run_conv(m, c1, B, {.x = cur, .y = m->rawA, .y_cstride = c1.coutp, .ss = m->ssA, .ride = ds_ride ? &ride : nullptr,
-                                                .grp = grp, .s = s})) != PNVO_OK) {
+  for (size_t bk = 0; bk < m->blocks.size(); ++bk) {
+    const Block &b = m->blocks[bk];
+    const bool ds = b.ds >= 0;
+    if (m->bottleneck) {                           // conv1x1 -> GN -> ReLU -> conv3x3(s) -> GN -> ReLU -> conv1x1 -> GN
+      const Layer &b1 = m->convs[b.conv[0]];
+      const Layer &b2 = m->convs[b.conv[1]];
+      const Layer &b3 = m->convs[b.conv[2]];
+      if ((rc = pnvo_run_conv(m, b1, B, {.x = cur, .y = m->rawA, .y_cstride = b1.coutp, .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK ||
+          (rc = pnvo_run_conv(m, b2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawC, .y_cstride = b2.coutp,
+                                         .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK ||
+          (rc = pnvo_run_conv(m, b3, B, {.x = m->rawC, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawB, .y_cstride = b3.coutp,
+                                         .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK)
         return rc;
-      }
-      const long P = (long)c2.hout * c2.wout;
-      const bool c2_small_generic = !layer_on_lds(m, c2, nullptr) && !pnvo_conv_on_x3(m, c2, B) && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
-      if (c2_small_generic) {
-        // small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one streaming
-        // pass over the (L2-sized) tensor, so normalise once and run the conv on final activations
-        // (scratch: rawD — unless the downsample conv rode on c1 and its output already sits there; `nxt` is free until the block tail)
-        float *napp = ds_ride ? nxt : m->rawD;
-        {
-          Timed t(m, s, "gn_relu_apply", 0.0, 8.0 * B * P * c2.cinp);
-          HIPCHK(m, launch_apply_ss_relu(m->rawA, m->ssA[0], m->ssA[1], B, P, c2.cinp, napp, s));
-        }
-        if ((rc = pnvo_run_conv(m, c2, B, {.x = napp, .y = m->rawB, .y_cstride = c2.coutp, .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK)
-          return rc;
-      } else if ((rc = pnvo_run_conv(m, c2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawB, .y_cstride = c2.coutp,
-                                                .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK) {
-        return rc;
-      }
+      const long Pb = (long)b3.hout * b3.wout;
       if (ds) {
-        const Layer &cd = m->convs[li++];
-        if (!ds_ride &&                                                // (riding: rawD / ssD came out of c1's launch)
-            (rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
+        const Layer &cd = m->convs[b.ds];
+        if ((rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
-      }
-      // (the last block's tail rides on the compression conv when that runs on conv_x3_kernel: nobody else reads that block output)
-      if (li < m->convs.size() && pnvo_conv_takes_tail(m, m->convs[li], B)) {   // relu(GN2(conv2) + skip): computed by the next conv's stager
-        tail.res = ds ? m->rawD : cur;
-        tail.res_scale = ds ? m->ssD[0] : nullptr;
-        tail.res_shift = ds ? m->ssD[1] : nullptr;
-        tail.out = nxt;
-        have_tail = true;
-        continue;
-      }
-      {
-        Timed t(m, s, "residual", 0.0, 12.0 * B * P * c2.coutp);
-        HIPCHK(m, launch_residual(m->rawB, m->ssB[0], m->ssB[1], ds ? m->rawD : cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, B,
-                                  P, c2.coutp, nxt, s));
+        Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
+        HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
+      } else {
+        Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
+        HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], cur, nullptr, nullptr, B, Pb, b3.coutp, nxt, s));
       }
       std::swap(cur, nxt);
-      const std::string tn = "layer" + std::to_string(stage) + "." + std::to_string(bi);
-      if ((rc = maybe_tap(m, tn.c_str(), cur, (size_t)B * P * c2.coutp, s)) != PNVO_OK) return rc;
+      if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
+      continue;
     }
+    const Layer &c1 = m->convs[b.conv[0]];
+    const Layer &c2 = m->convs[b.conv[1]];
+    // the block's downsample conv rides on c1's launch (conv_x3_kernel DSF): no launch, no finalisation of its own, and in the
+    // block-tail mode the block input is not written to HBM at all — c1 and the downsample conv are its only readers
+    const bool ds_ride = ds && !have_keys && pnvo_conv_takes_ds(m, c1, m->convs[b.ds], B);
+    const DsRide ride{ds_ride ? &m->convs[b.ds] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
+    if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
+      BlockTail ktail{nullptr, nullptr, nullptr, cur};
+      if ((rc = pnvo_run_conv(m, c1, B, {.x = nxt, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawA, .y_cstride = c1.coutp,
+                                         .ss = m->ssA, .tail = &ktail, .grp = grp, .s = s})) != PNVO_OK)
+        return rc;
+      have_keys = false;
+    } else if (have_tail) {    // the previous block's tail rides on this conv's stager, which also writes the block output
+      if (ds_ride) tail.out = nullptr;                       // (nobody else reads this block's input)
+      if ((rc = pnvo_run_conv(m, c1, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawA, .y_cstride = c1.coutp,
+                                         .ss = m->ssA, .tail = &tail, .ride = ds_ride ? &ride : nullptr, .grp = grp, .s = s})) != PNVO_OK)
+        return rc;
+      std::swap(cur, nxt);
+      have_tail = false;
+    } else if ((rc = pnvo_run_conv(m, c1, B, {.x = cur, .y = m->rawA, .y_cstride = c1.coutp, .ss = m->ssA, .ride = ds_ride ? &ride : nullptr,
+                                              .grp = grp, .s = s})) != PNVO_OK) {
+      return rc;
+    }
+    const long P = (long)c2.hout * c2.wout;
+    const bool c2_small_generic = !layer_on_lds(m, c2, nullptr) && !pnvo_conv_on_x3(m, c2, B) && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
+    if (c2_small_generic) {
+      // small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one streaming
+      // pass over the (L2-sized) tensor, so normalise once and run the conv on final activations
+      // (scratch: rawD — unless the downsample conv rode on c1 and its output already sits there; `nxt` is free until the block tail)
+      float *napp = ds_ride ? nxt : m->rawD;
+      {
+        Timed t(m, s, "gn_relu_apply", 0.0, 8.0 * B * P * c2.cinp);
+        HIPCHK(m, launch_apply_ss_relu(m->rawA, m->ssA[0], m->ssA[1], B, P, c2.cinp, napp, s));
+      }
+      if ((rc = pnvo_run_conv(m, c2, B, {.x = napp, .y = m->rawB, .y_cstride = c2.coutp, .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK)
+        return rc;
+    } else if ((rc = pnvo_run_conv(m, c2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawB, .y_cstride = c2.coutp,
+                                              .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK) {
+      return rc;
+    }
+    if (ds) {
+      const Layer &cd = m->convs[b.ds];
+      if (!ds_ride &&                                                // (riding: rawD / ssD came out of c1's launch)
+          (rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
+        return rc;
+    }
+    // (the last block's tail rides on the compression conv when that runs on conv_x3_kernel: nobody else reads that block output)
+    if (pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B)) {   // relu(GN2(conv2) + skip): computed by the next conv's stager
+      tail.res = ds ? m->rawD : cur;
+      tail.res_scale = ds ? m->ssD[0] : nullptr;
+      tail.res_shift = ds ? m->ssD[1] : nullptr;
+      tail.out = nxt;
+      have_tail = true;
+      continue;
+    }
+    {
+      Timed t(m, s, "residual", 0.0, 12.0 * B * P * c2.coutp);
+      HIPCHK(m, launch_residual(m->rawB, m->ssB[0], m->ssB[1], ds ? m->rawD : cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, B,
+                                P, c2.coutp, nxt, s));
+    }
+    std::swap(cur, nxt);
+    if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * P * c2.coutp, s)) != PNVO_OK) return rc;
   }
 
   // (a10) compression conv + GroupNorm(1, C)
-  const Layer &comp = m->convs[li++];
+  const Layer &comp = m->convs[m->comp];
   if (have_tail) {               // the last block's tail in the compression conv's stager; its output is not materialised
     tail.out = nullptr;
     if ((rc = pnvo_run_conv(m, comp, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->comp_raw, .y_cstride = comp.coutp,
@@ -2456,15 +2450,8 @@ int pnvo_tap_shape(pnvo_handle h, const char *name, int B, int64_t shape[4]) {
   if (n == "maxpool") return set(B, h->Hp, h->Wp, c.baseplanes);
   if (n == "compression") return set(B, h->fh, h->fw, h->comp_cp);
   if (n == "hidden") return set(B, 1, 1, c.hidden);
-  if (n.rfind("layer", 0) == 0 && n.size() == 8) {
-    const int li = n[5] - '0';
-    int hh = h->Hp, ww = h->Wp;
-    for (int k = 1; k < li; ++k) {
-      hh = halve(hh);
-      ww = halve(ww);
-    }
-    return set(B, hh, ww, c.baseplanes << (li - 1));
-  }
+  for (const Block &b : h->blocks)
+    if (n == b.tap) return set(B, h->last(b).hout, h->last(b).wout, h->last(b).coutp);
   return fail(h, PNVO_ERR_ARG, "unknown tap '" + n + "'");
 }
 
@@ -2485,8 +2472,8 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
     ConvX3Args xa;
     int mw, nw;
     size_t ldsb;
-    if (l.k == 1 && l.stride == 2 && li >= 3 && h->convs[li - 2].stride == 2 && pnvo_conv_takes_ds(h, h->convs[li - 2], l, B) &&
-        x3_args(h, h->convs[li - 2], B, xa, &mw, &nw, &ldsb)) {           // a downsample conv riding on its block's first conv
+    const Layer *c1 = l.block >= 0 && h->blocks[l.block].ds == (int)li ? &h->convs[h->blocks[l.block].conv[0]] : nullptr;
+    if (c1 && pnvo_conv_takes_ds(h, *c1, l, B) && x3_args(h, *c1, B, xa, &mw, &nw, &ldsb)) {   // a downsample conv riding on its block's first conv
       std::snprintf(family, cap, "x2-rides");
       if (executed_flops) *executed_flops = 3.0 * 2.0 * (double)B * xa.tiles_r * xa.tiles_c * xa.MT * 32.0 * l.coutp * (double)l.cinp;
       return PNVO_OK;

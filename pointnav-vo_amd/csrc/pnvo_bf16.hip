@@ -322,73 +322,68 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float
   // The tail of block k (GN2 + skip + ReLU) is not a pass of its own: conv1 of block k+1 (and the compression conv after
   // the last block) computes it while staging its input patch and writes the block output for the later readers (the
   // next skip branch / downsample conv).  PNVO_BF16_NOFUSE=1 keeps the separate residual kernel (A/B measurements).
-  size_t li = 1;
   Skip pend;                                       // tail of the previous block, still to be applied
   const Skip none;
-  for (int stage = 1; stage <= 4; ++stage)
-    for (int bi = 0; bi < m->nblocks[stage - 1]; ++bi) {
-      const size_t l1 = li++, l2 = li++;
-      const bool ds = li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos;
-      const Layer &c2 = m->convs[l2];
-      // the block's downsample conv rides on its first conv's launch (option ds_fuse); in the block-tail mode the block input is then
-      // not written at all: both of its readers are that launch
-      const Layer &c1 = m->convs[l1];
-      const bool ride_ok = ds && m->opt.ds_fuse && !(pend.on && pend.affine) /* the stager would read rawD while the ride writes it */ &&
-                           bs[0]->layers[l1].nw == 1 /* two N-tiles per wave: the second accumulator set does not fit (measured 56 -> 103 us) */ &&
-                           c1.cinp != 32 /* 32 input channels: the resident-weight persistent form takes the head (140 + 39 us with the separate
-                                            downsample conv against 235 us with the ride on the streaming form) */ &&
-                           c1.k == 3 && c1.stride == 2 && m->convs[li].k == 1 && m->convs[li].stride == 2 &&
-                           c1.cinp == m->convs[li].cinp && c1.coutp == m->convs[li].coutp && c1.hout == m->convs[li].hout &&
-                           c1.wout == m->convs[li].wout && c1.groups == m->convs[li].groups;
-      const long ride = ride_ok ? (long)li : -1;
-      if (pend.on) {                               // input = relu(GN2(rawB) + skip) of the previous block -> bufY[cur ^ 1]
-        if ((rc = conv(l1, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->rawA; }, 0,
-                       false, pend, ride_ok ? -1 : (cur ^ 1), ride)) != PNVO_OK)
-          return rc;
-        cur ^= 1;
-      } else if ((rc = conv(l1, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
-                            [&](int z) { return (void *)bs[z]->rawA; }, 0, false, none, -1, ride)) != PNVO_OK) {
+  for (const Block &blk : m->blocks) {
+    const size_t l1 = blk.conv[0], l2 = blk.conv[1];
+    const bool ds = blk.ds >= 0;
+    const Layer &c2 = m->convs[l2];
+    // the block's downsample conv rides on its first conv's launch (option ds_fuse); in the block-tail mode the block input is then
+    // not written at all: both of its readers are that launch
+    const Layer &c1 = m->convs[l1];
+    const bool ride_ok = ds && m->opt.ds_fuse && !(pend.on && pend.affine) /* the stager would read rawD while the ride writes it */ &&
+                         bs[0]->layers[l1].nw == 1 /* two N-tiles per wave: the second accumulator set does not fit (measured 56 -> 103 us) */ &&
+                         c1.cinp != 32 /* 32 input channels: the resident-weight persistent form takes the head (140 + 39 us with the separate
+                                          downsample conv against 235 us with the ride on the streaming form) */ &&
+                         c1.k == 3 && c1.stride == 2 && m->convs[blk.ds].k == 1 && m->convs[blk.ds].stride == 2 &&
+                         c1.cinp == m->convs[blk.ds].cinp && c1.coutp == m->convs[blk.ds].coutp && c1.hout == m->convs[blk.ds].hout &&
+                         c1.wout == m->convs[blk.ds].wout && c1.groups == m->convs[blk.ds].groups;
+    const long ride = ride_ok ? blk.ds : -1;
+    if (pend.on) {                               // input = relu(GN2(rawB) + skip) of the previous block -> bufY[cur ^ 1]
+      if ((rc = conv(l1, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->rawA; }, 0,
+                     false, pend, ride_ok ? -1 : (cur ^ 1), ride)) != PNVO_OK)
         return rc;
-      }
-      if ((rc = conv(l2, 1, [&](int z) { return (const unsigned short *)bs[z]->rawA; }, [&](int z) { return (void *)bs[z]->rawB; }, 1,
-                     false, none, -1)) != PNVO_OK)
-        return rc;
-      const long P = (long)c2.hout * c2.wout;
-      if (ds) {
-        const size_t ld = li++;
-        if (!ride_ok && (rc = conv(ld, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
-                                   [&](int z) { return (void *)bs[z]->rawD; }, 2, false, none, -1)) != PNVO_OK)
-          return rc;
-      }
-      if (fuse) {
-        pend.on = true;
-        pend.affine = ds;
-        pend.buf = cur;
-        continue;
-      }
-      auto a_ = each([&](int z) { return (const unsigned short *)bs[z]->rawB; });
-      auto sa = each([&](int z) { return (const float *)bs[z]->ssB[0]; });
-      auto ta = each([&](int z) { return (const float *)bs[z]->ssB[1]; });
-      auto y_ = each([&](int z) { return bs[z]->bufY[cur ^ 1]; });
-      if (ds) {
-        auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->rawD; });
-        auto sb = each([&](int z) { return (const float *)bs[z]->ssD[0]; });
-        auto tb = each([&](int z) { return (const float *)bs[z]->ssD[1]; });
-        PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
-        HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, sb.v, tb.v, B, P, c2.coutp, y_.v, nm, s));
-      } else {
-        auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; });
-        PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
-        HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, nullptr, nullptr, B, P, c2.coutp, y_.v, nm, s));
-      }
       cur ^= 1;
+    } else if ((rc = conv(l1, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
+                          [&](int z) { return (void *)bs[z]->rawA; }, 0, false, none, -1, ride)) != PNVO_OK) {
+      return rc;
     }
+    if ((rc = conv(l2, 1, [&](int z) { return (const unsigned short *)bs[z]->rawA; }, [&](int z) { return (void *)bs[z]->rawB; }, 1,
+                   false, none, -1)) != PNVO_OK)
+      return rc;
+    const long P = (long)c2.hout * c2.wout;
+    if (ds && !ride_ok && (rc = conv(blk.ds, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
+                                     [&](int z) { return (void *)bs[z]->rawD; }, 2, false, none, -1)) != PNVO_OK)
+      return rc;
+    if (fuse) {
+      pend.on = true;
+      pend.affine = ds;
+      pend.buf = cur;
+      continue;
+    }
+    auto a_ = each([&](int z) { return (const unsigned short *)bs[z]->rawB; });
+    auto sa = each([&](int z) { return (const float *)bs[z]->ssB[0]; });
+    auto ta = each([&](int z) { return (const float *)bs[z]->ssB[1]; });
+    auto y_ = each([&](int z) { return bs[z]->bufY[cur ^ 1]; });
+    if (ds) {
+      auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->rawD; });
+      auto sb = each([&](int z) { return (const float *)bs[z]->ssD[0]; });
+      auto tb = each([&](int z) { return (const float *)bs[z]->ssD[1]; });
+      PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
+      HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, sb.v, tb.v, B, P, c2.coutp, y_.v, nm, s));
+    } else {
+      auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; });
+      PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
+      HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, nullptr, nullptr, B, P, c2.coutp, y_.v, nm, s));
+    }
+    cur ^= 1;
+  }
   // (a10) compression conv + GroupNorm(1, C): fp32 output for the Linear layers
   if (pend.on) {
-    if ((rc = conv(li, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->comp_raw; }, 3,
+    if ((rc = conv(m->comp, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->comp_raw; }, 3,
                    true, pend, -1)) != PNVO_OK)
       return rc;
-  } else if ((rc = conv(li, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
+  } else if ((rc = conv(m->comp, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
                         [&](int z) { return (void *)bs[z]->comp_raw; }, 3, true, none, -1)) != PNVO_OK) {
     return rc;
   }

@@ -28,6 +28,18 @@ struct Layer {
   unsigned long long x2_gen = 0;
   float x2_oscale = 1.f;
   float in_bound = 3.0e38f;
+  int block = -1;           // index into pnvo_model_s::blocks of the residual block this conv belongs to (-1: stem, compression)
+};
+
+// One residual block of the plan: where its convs sit in pnvo_model_s::convs.  build_plan fills the table; every walk over the
+// residual stages (forwards, backward, workspaces, range guard, taps) iterates it.  The block output has the geometry of its last
+// conv: hout x wout x coutp.
+struct Block {
+  int stage = 0, index = 0;       // layer<stage>.<index>, stage 1..4
+  int nconv = 0;                  // 2 (BasicBlock) or 3 (Bottleneck)
+  int conv[3] = {-1, -1, -1};     // chain order
+  int ds = -1;                    // the downsample conv of the skip branch, or -1 (identity)
+  std::string tap;                // "layer<stage>.<index>"
 };
 
 // Per-handle options (pnvo_set_option; defaults from the PNVO_* environment, read ONCE in pnvo_create).
@@ -81,6 +93,11 @@ struct pnvo_model_s {
   int C = 0, CP = 0;                 // input channels, padded to 8
   int Hs = 0, Ws = 0, Hp = 0, Wp = 0, fh = 0, fw = 0, comp_c = 0, comp_cp = 0;
   std::vector<Layer> convs;          // stem, residual stages in execution order, compression
+  std::vector<Block> blocks;         // the residual blocks in forward order
+  int comp = -1;                     // index of the compression conv in convs
+  const Layer &last(const Block &b) const { return convs[b.conv[b.nconv - 1]]; }   // its geometry is the block output's
+  // the conv that reads block k's output: the next block's first conv, or the compression conv
+  int next_conv_after(size_t k) const { return k + 1 < blocks.size() ? blocks[k + 1].conv[0] : comp; }
   Layer fc, head;
   float *fc_bias = nullptr, *head_bias = nullptr;   // device; fc_bias has 1 or n_acts+1 rows
   float *fc_rows_w = nullptr;                // device [hidden][fh * fw * comp_cp]: the hidden layer's weight rows in the activation's order (fc_rows.hip)
@@ -140,7 +157,6 @@ struct pnvo_model_s {
   float *rawA = nullptr, *rawB = nullptr, *rawD = nullptr, *rawC = nullptr, *comp_raw = nullptr, *hid = nullptr,
         *stats = nullptr;
   bool bottleneck = false;           // resnet50 / resnet101 backbone
-  std::vector<int> nblocks;          // residual blocks per stage
   float *ssA[2] = {nullptr, nullptr}, *ssB[2] = {nullptr, nullptr}, *ssD[2] = {nullptr, nullptr},
         *ssC[2] = {nullptr, nullptr};
   float *tapbuf = nullptr;

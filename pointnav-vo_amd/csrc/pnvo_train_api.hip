@@ -461,21 +461,16 @@ int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
   }
   t->wg_partial_floats = wgmax;
   if ((rc = dmalloc(m, (void **)&t->wg_partial, wgmax * 4)) != PNVO_OK) return rc;
-  // block outputs: y[0] = pooled stem output, y[k] = output of residual block k (plan order)
+  // block outputs: y[0] = pooled stem output, y[k] = output of m->blocks[k - 1]
   size_t act = (size_t)B * m->Hp * m->Wp * c.baseplanes;
   const size_t stem = (size_t)B * m->Hs * m->Ws * c.baseplanes;
   {
-    const int K = m->bottleneck ? 3 : 2;
-    const int nb = m->nblocks[0] + m->nblocks[1] + m->nblocks[2] + m->nblocks[3];
-    t->y.assign((size_t)nb + 1, nullptr);
+    t->y.assign(m->blocks.size() + 1, nullptr);
     if ((rc = dmalloc(m, (void **)&t->y[0], act * 4)) != PNVO_OK) return rc;
-    size_t li = 1;
-    for (int k = 1; k <= nb; ++k) {
-      const Layer &last = m->convs[li + K - 1];
+    for (size_t k = 1; k <= m->blocks.size(); ++k) {
+      const Layer &last = m->last(m->blocks[k - 1]);
       const size_t n = (size_t)B * last.hout * last.wout * last.coutp;
       if ((rc = dmalloc(m, (void **)&t->y[k], n * 4)) != PNVO_OK) return rc;
-      li += K;
-      if (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos) ++li;
     }
     for (size_t k = 1; k < m->convs.size(); ++k) {      // scratch gradients are as large as the largest activation
       const Layer &l = m->convs[k];
@@ -962,80 +957,72 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
     HIPCHK(m, launch_whiten_table(run_mean, run_var, t->d_ref_of_new, t->d_tensor_of_new, m->CPL, m->stem_sc, m->stem_sh, s));
   if ((rc = refresh_stem_dd(m, t, s)) != PNVO_OK) return rc;   // W/std table, indicator weights: both move every step
 
-  size_t li = 0;
   {
-    ConvSave &cs = t->cs[li];
+    ConvSave &cs = t->cs[0];
     if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
                                    .train_fwd = true, .s = s})) != PNVO_OK)
       return rc;
-    const Layer &stem = m->convs[li++];
+    const Layer &stem = m->convs[0];
     HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, stem.coutp, t->y[0], t->pool_idx, s));
   }
   // residual blocks: a chain of K convs (BasicBlock K = 2, resnet.py:29-55; Bottleneck K = 3, :58-117) + the skip branch
-  const int K = m->bottleneck ? 3 : 2;
-  int yk = 0;
   BlockTail tail{};
   const ConvSave *tail_x = nullptr;
   bool have_tail = false;
-  for (int stage = 1; stage <= 4; ++stage)
-    for (int bi = 0; bi < m->nblocks[stage - 1]; ++bi) {
-      const float *xin = t->y[yk];
-      float *yout = t->y[yk + 1];
-      size_t ik[3];
-      for (int k = 0; k < K; ++k) ik[k] = li++;
-      const bool ds = (li < m->convs.size() && m->convs[li].name.find("downsample") != std::string::npos);
-      // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
-      // the backward pass reads it
-      const bool ds_ride = ds && K == 2 && pnvo_conv_takes_ds(m, m->convs[ik[0]], m->convs[li], B);
-      DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
-      if (ds_ride) {
-        ConvSave &sd = t->cs[li];
-        ride = DsRide{&m->convs[li], sd.raw, sd.ss, sd.mu, sd.rstd};
-      }
-      for (int k = 0; k < K; ++k) {
-        const Layer &ck = m->convs[ik[k]];
-        ConvSave &sk = t->cs[ik[k]];
-        const ConvSave *sp = k ? &t->cs[ik[k - 1]] : nullptr;
-        const DsRide *rd = (k == 0 && ds_ride) ? &ride : nullptr;
-        if (k == 0 && have_tail) {       // the previous block's tail rides on this conv's stager, which writes xin (= tail.out)
-          rc = pnvo_run_conv(m, ck, B, {.x = tail_x->raw, .in_scale = tail_x->ss[0], .in_shift = tail_x->ss[1], .y = sk.raw, .y_cstride = ck.coutp,
-                                        .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .tail = &tail, .ride = rd, .s = s});
-          have_tail = false;
-        } else {
-          rc = pnvo_run_conv(m, ck, B, {.x = k ? sp->raw : xin, .in_scale = k ? sp->ss[0] : nullptr, .in_shift = k ? sp->ss[1] : nullptr,
-                                        .y = sk.raw, .y_cstride = ck.coutp, .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .ride = rd, .s = s});
-        }
-        if (rc != PNVO_OK) return rc;
-      }
-      const Layer &cl = m->convs[ik[K - 1]];
-      ConvSave &sl = t->cs[ik[K - 1]];
-      const long P = (long)cl.hout * cl.wout;
-      if (ds) {
-        const size_t id = li++;
-        const Layer &cd = m->convs[id];
-        ConvSave &sd = t->cs[id];
-        if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, {.x = xin, .y = sd.raw, .y_cstride = cd.coutp, .ss = sd.ss, .mu = sd.mu, .rstd = sd.rstd,
-                                                       .s = s})) != PNVO_OK)
-          return rc;
-        tail = BlockTail{sd.raw, sd.ss[0], sd.ss[1], yout};
-      } else {
-        tail = BlockTail{xin, nullptr, nullptr, yout};
-      }
-      const bool last = stage == 4 && bi + 1 == m->nblocks[3];
-      if (!last && pnvo_conv_takes_tail(m, m->convs[li], B)) {   // the next block's first conv computes and writes yout
-        tail_x = &sl;
-        have_tail = true;
-      } else {
-        HIPCHK(m, launch_residual(sl.raw, sl.ss[0], sl.ss[1], tail.res, tail.res_scale, tail.res_shift, B, P, cl.coutp, yout, s));
-      }
-      ++yk;
+  for (size_t bk = 0; bk < m->blocks.size(); ++bk) {
+    const Block &b = m->blocks[bk];
+    const int K = b.nconv, *ik = b.conv;
+    const float *xin = t->y[bk];
+    float *yout = t->y[bk + 1];
+    const bool ds = b.ds >= 0;
+    // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
+    // the backward pass reads it
+    const bool ds_ride = ds && K == 2 && pnvo_conv_takes_ds(m, m->convs[ik[0]], m->convs[b.ds], B);
+    DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (ds_ride) {
+      ConvSave &sd = t->cs[b.ds];
+      ride = DsRide{&m->convs[b.ds], sd.raw, sd.ss, sd.mu, sd.rstd};
     }
-  const int nblk_total = yk;
+    for (int k = 0; k < K; ++k) {
+      const Layer &ck = m->convs[ik[k]];
+      ConvSave &sk = t->cs[ik[k]];
+      const ConvSave *sp = k ? &t->cs[ik[k - 1]] : nullptr;
+      const DsRide *rd = (k == 0 && ds_ride) ? &ride : nullptr;
+      if (k == 0 && have_tail) {       // the previous block's tail rides on this conv's stager, which writes xin (= tail.out)
+        rc = pnvo_run_conv(m, ck, B, {.x = tail_x->raw, .in_scale = tail_x->ss[0], .in_shift = tail_x->ss[1], .y = sk.raw, .y_cstride = ck.coutp,
+                                      .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .tail = &tail, .ride = rd, .s = s});
+        have_tail = false;
+      } else {
+        rc = pnvo_run_conv(m, ck, B, {.x = k ? sp->raw : xin, .in_scale = k ? sp->ss[0] : nullptr, .in_shift = k ? sp->ss[1] : nullptr,
+                                      .y = sk.raw, .y_cstride = ck.coutp, .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .ride = rd, .s = s});
+      }
+      if (rc != PNVO_OK) return rc;
+    }
+    const Layer &cl = m->convs[ik[K - 1]];
+    ConvSave &sl = t->cs[ik[K - 1]];
+    const long P = (long)cl.hout * cl.wout;
+    if (ds) {
+      const Layer &cd = m->convs[b.ds];
+      ConvSave &sd = t->cs[b.ds];
+      if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, {.x = xin, .y = sd.raw, .y_cstride = cd.coutp, .ss = sd.ss, .mu = sd.mu, .rstd = sd.rstd,
+                                                     .s = s})) != PNVO_OK)
+        return rc;
+      tail = BlockTail{sd.raw, sd.ss[0], sd.ss[1], yout};
+    } else {
+      tail = BlockTail{xin, nullptr, nullptr, yout};
+    }
+    const bool last = bk + 1 == m->blocks.size();
+    if (!last && pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B)) {   // the next block's first conv computes and writes yout
+      tail_x = &sl;
+      have_tail = true;
+    } else {
+      HIPCHK(m, launch_residual(sl.raw, sl.ss[0], sl.ss[1], tail.res, tail.res_scale, tail.res_shift, B, P, cl.coutp, yout, s));
+    }
+  }
   {
-    const size_t ic = li++;
-    const Layer &comp = m->convs[ic];
-    ConvSave &sc = t->cs[ic];
-    if ((rc = pnvo_run_conv(m, comp, B, {.x = t->y[nblk_total], .y = sc.raw, .y_cstride = comp.coutp, .ss = sc.ss, .mu = sc.mu, .rstd = sc.rstd,
+    const Layer &comp = m->convs[m->comp];
+    ConvSave &sc = t->cs[m->comp];
+    if ((rc = pnvo_run_conv(m, comp, B, {.x = t->y[m->blocks.size()], .y = sc.raw, .y_cstride = comp.coutp, .ss = sc.ss, .mu = sc.mu, .rstd = sc.rstd,
                                          .s = s})) != PNVO_OK)
       return rc;
     ++t->drop_step;
@@ -1105,7 +1092,6 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
   hipStream_t s = (hipStream_t)stream;
   int rc = PNVO_OK;
 
-  const int nblk_total = m->nblocks[0] + m->nblocks[1] + m->nblocks[2] + m->nblocks[3];
   if (!t->dmax && !m->bottleneck) {
     if ((rc = dmalloc(m, (void **)&t->dmax, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned))) != PNVO_OK) return rc;
   }
@@ -1140,7 +1126,7 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
     HIPCHK(m, launch_conv(d, s));
   }
   // ---- hidden layer: hid = relu(z . W1^T + b1)
-  const size_t icomp = m->convs.size() - 1;
+  const size_t icomp = m->comp;
   {
     if (t->drop_p > 0.f) {            // dropout backward: the same mask, then the ReLU mask of the un-dropped activation
       HIPCHK(m, launch_dropout(t->dh, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, t->dh, s));
@@ -1202,24 +1188,17 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
     const Layer &l = m->convs[icomp];
     if ((rc = run_gn_bwd(m, t, icomp, B, t->dz, 1, t->dz, s)) != PNVO_OK) return rc;   // in place: dz -> dCompRaw
     WgradArgs a = wgrad_args(l, B, l.cin, l.coutp);
-    a.x = t->y[nblk_total];
+    a.x = t->y[m->blocks.size()];
     a.dy = t->dz;
     a.mode = 0;
     if ((rc = run_wgrad(m, t, a, l.name + ".weight", nullptr, l.cin, s)) != PNVO_OK) return rc;
     if ((rc = run_dgrad(m, t, icomp, B, t->dz, dY, false, s)) != PNVO_OK) return rc;
   }
-  // ---- residual blocks, last to first.  Conv indices: walk m->convs backwards from the compression layer.
-  size_t li = icomp;
-  const int K = m->bottleneck ? 3 : 2;
-  for (int blk = nblk_total; blk >= 1; --blk) {
-    const bool ds = m->convs[li - 1].name.find("downsample") != std::string::npos;
-    const size_t id = ds ? li - 1 : 0;
-    size_t ik[3];
-    {
-      size_t last = ds ? li - 2 : li - 1;
-      for (int k = K - 1; k >= 0; --k) ik[k] = last - (size_t)(K - 1 - k);
-    }
-    li = ik[0];
+  // ---- residual blocks, last to first: m->blocks in reverse (t->y[blk] is the output of m->blocks[blk - 1])
+  for (size_t blk = m->blocks.size(); blk >= 1; --blk) {
+    const Block &b = m->blocks[blk - 1];
+    const int K = b.nconv, *ik = b.conv, id = b.ds;
+    const bool ds = id >= 0;
     const Layer &c1 = m->convs[ik[0]], &cl = m->convs[ik[K - 1]];
     const float *xin = t->y[blk - 1];
     const long nout = (long)B * cl.hout * cl.wout * cl.coutp;
@@ -1267,8 +1246,8 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
     std::swap(dY, dX);
     // leaving residual stage 4 / stage 2: every parameter from that stage's first offset upwards has its final gradient
     if (t->bucket_first.size() == 3) {
-      if (blk - 1 == m->nblocks[0] + m->nblocks[1] + m->nblocks[2]) report_bucket(t, 0, s);
-      if (blk - 1 == m->nblocks[0]) report_bucket(t, 1, s);
+      if (b.stage == 4 && b.index == 0) report_bucket(t, 0, s);
+      if (b.stage == 2 && b.index == 0) report_bucket(t, 1, s);
     }
   }
   // ---- stem: maxpool <- dY, GroupNorm + ReLU, weight gradient (no input gradient)

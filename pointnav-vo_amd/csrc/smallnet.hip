@@ -893,9 +893,10 @@ bool pnvo_small_usable(pnvo_handle m, int B) {
   const pnvo_config &c = m->cfg;
   if (c.baseplanes % 32 != 0 || c.hidden % 4 != 0) return false;
   for (size_t k = 1; k < m->convs.size(); ++k)
-    if (m->convs[k].cinp > 256 || (m->convs[k].cout != m->convs[k].coutp && k + 1 != m->convs.size())) return false;
-  for (int st = 0; st < 4; ++st)
-    if (m->nblocks[st] < 2) return false;
+    if (m->convs[k].cinp > 256 || (m->convs[k].cout != m->convs[k].coutp && (int)k != m->comp)) return false;
+  int per_stage[4] = {0, 0, 0, 0};
+  for (const Block &b : m->blocks) ++per_stage[b.stage - 1];
+  if (*std::min_element(per_stage, per_stage + 4) < 2) return false;
   if (B * std::max(m->convs[0].coutp, m->comp_cp) > SN_TAB) return false;
   if (m->comp_cp != 32 && m->comp_cp != 64 && m->comp_cp != 128) return false;
   // LDS: the largest patch of a conv phase, or the activation vectors of the Linear layers for the whole batch (large frames)
@@ -907,7 +908,7 @@ bool pnvo_small_usable(pnvo_handle m, int B) {
     floats = std::max(floats, (size_t)((th - 1) * l.stride + 3) * ((tw - 1) * l.stride + 3) * (l.cinp + 4));
   }
   if (((size_t)SN_FIXED_FLOATS + floats) * sizeof(float) > (size_t)156 * 1024) return false;
-  if (1 + (int)m->convs.size() - 1 + 2 > SN_MAXPH) return false;
+  if ((int)m->convs.size() + 2 > SN_MAXPH) return false;
   return true;
 }
 
@@ -1029,7 +1030,6 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B, int stem_slots, bool features) 
     ph.push_back(p);
   }
   // ---- residual stages
-  size_t li = 1;
   float *X = m->bufY[0], *Xn = m->bufY[1];
   bool have_tail = false;
   SnGN tail_gin, tail_gres;
@@ -1049,58 +1049,56 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B, int stem_slots, bool features) 
       p.in = X;
     }
   };
-  for (int stage = 1; stage <= 4; ++stage)
-    for (int bi = 0; bi < m->nblocks[stage - 1]; ++bi) {
-      const Layer &c1 = m->convs[li];
-      const Layer &c2 = m->convs[li + 1];
-      const bool ds = li + 2 < m->convs.size() && m->convs[li + 2].name.find("downsample") != std::string::npos;
-      SnPhase p1 = conv_phase(c1, 0);
-      apply_input(p1);
-      if (have_tail) {
-        if (ds && tail_gres.G > 0) return -1;      // would read and write the downsample buffers in one phase
-        std::swap(X, Xn);                          // X now names the buffer this phase's owners write
-        have_tail = false;
-      }
-      p1.w = sn->w[li];
-      p1.out = m->rawA;
-      p1.part = sn->part[0];
-      if (ds) {
-        const Layer &cd = m->convs[li + 2];
-        if (cd.k != 1 || cd.stride != c1.stride || cd.cinp != c1.cinp || cd.coutp != c1.coutp || c1.stride != 2) return -1;
-        p1.w_ds = sn->w[li + 2];
-        p1.out_ds = m->rawD;
-        p1.part_ds = sn->part[2];
-        need[2] = std::max(need[2], (size_t)B * p1.out_G * p1.out_slots * 2);
-      }
-      ph.push_back(p1);
-      SnPhase p2 = conv_phase(c2, 1);
-      p2.in_mode = 1;
-      p2.in = m->rawA;
-      p2.gin = sn_gn(c1, sn->part[0], p1.out_slots);
-      p2.w = sn->w[li + 1];
-      p2.out = m->rawB;
-      p2.part = sn->part[1];
-      ph.push_back(p2);
-      // the block's tail rides on the next phase
-      have_tail = true;
-      tail_in = m->rawB;
-      tail_gin = sn_gn(c2, sn->part[1], p2.out_slots);
-      if (ds) {
-        tail_res = m->rawD;
-        tail_gres = sn_gn(m->convs[li + 2], sn->part[2], p1.out_slots);
-      } else {
-        tail_res = X;
-        std::memset(&tail_gres, 0, sizeof(tail_gres));
-      }
-      li += ds ? 3 : 2;
+  for (const Block &b : m->blocks) {
+    const Layer &c1 = m->convs[b.conv[0]];
+    const Layer &c2 = m->convs[b.conv[1]];
+    const bool ds = b.ds >= 0;
+    SnPhase p1 = conv_phase(c1, 0);
+    apply_input(p1);
+    if (have_tail) {
+      if (ds && tail_gres.G > 0) return -1;      // would read and write the downsample buffers in one phase
+      std::swap(X, Xn);                          // X now names the buffer this phase's owners write
+      have_tail = false;
     }
+    p1.w = sn->w[b.conv[0]];
+    p1.out = m->rawA;
+    p1.part = sn->part[0];
+    if (ds) {
+      const Layer &cd = m->convs[b.ds];
+      if (cd.k != 1 || cd.stride != c1.stride || cd.cinp != c1.cinp || cd.coutp != c1.coutp || c1.stride != 2) return -1;
+      p1.w_ds = sn->w[b.ds];
+      p1.out_ds = m->rawD;
+      p1.part_ds = sn->part[2];
+      need[2] = std::max(need[2], (size_t)B * p1.out_G * p1.out_slots * 2);
+    }
+    ph.push_back(p1);
+    SnPhase p2 = conv_phase(c2, 1);
+    p2.in_mode = 1;
+    p2.in = m->rawA;
+    p2.gin = sn_gn(c1, sn->part[0], p1.out_slots);
+    p2.w = sn->w[b.conv[1]];
+    p2.out = m->rawB;
+    p2.part = sn->part[1];
+    ph.push_back(p2);
+    // the block's tail rides on the next phase
+    have_tail = true;
+    tail_in = m->rawB;
+    tail_gin = sn_gn(c2, sn->part[1], p2.out_slots);
+    if (ds) {
+      tail_res = m->rawD;
+      tail_gres = sn_gn(m->convs[b.ds], sn->part[2], p1.out_slots);
+    } else {
+      tail_res = X;
+      std::memset(&tail_gres, 0, sizeof(tail_gres));
+    }
+  }
   // ---- compression conv (GroupNorm(1, C) follows)
-  const Layer &comp = m->convs[li];
+  const Layer &comp = m->convs[m->comp];
   {
     SnPhase p = conv_phase(comp, 3);
     apply_input(p);
     p.blk_out = nullptr;
-    p.w = sn->w[li];
+    p.w = sn->w[m->comp];
     p.out = m->comp_raw;
     p.part = sn->part[3];
     ph.push_back(p);
