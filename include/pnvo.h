@@ -391,6 +391,59 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
 
 int pnvo_policy_destroy(pnvo_policy_handle h);
 
+/* ---- one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions, policy.py:52-63):
+ * rollout forward with saved activations, the PPO loss, back-propagation through time into ONE flat gradient buffer.  float32; no
+ * torch autograd anywhere on the path.  Rows of every [M, ...] tensor are T-major, row t*N + n (the order
+ * RolloutStorage.recurrent_generator yields), M = T*N. ----
+ *
+ * pnvo_policy_train_attach: params / grads are DEVICE buffers of n_floats floats holding every tensor of
+ * PointNavResNetPolicy.named_parameters() in that order at the offsets of `toc` (offsets multiples of 4 floats, the buffer 16-byte
+ * aligned), followed by at least pnvo_policy_train_tail_floats(h) further floats that belong to the library (the stem weight
+ * zero-padded to the encoder handle's two input channels, and that handle's unused output head).  After the call the recurrent part
+ * and the heads read their weights from `params` — pnvo_policy_act included, so an optimiser step on `params` followed by
+ * pnvo_policy_train_refresh is all it takes for the next act to use the new weights — and the visual encoder is attached with
+ * pnvo_train_attach.  pnvo_policy_load_weights is refused from then on.  Requires pnvo_policy_load_weights before it. */
+size_t pnvo_policy_train_tail_floats(pnvo_policy_handle h);
+int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc,
+                             int ntoc);
+
+/* Re-pack the encoder's kernel operands from `params` (after an optimiser step or any other write to it). */
+int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream);
+
+/* value, action_log_probs, entropy, rnn_hidden_states = evaluate_actions(...) with everything the backward needs kept in the
+ * handle.  depth [M,H,W,1], goal [M,2], prev_actions [M] int64, masks [M], actions [M] int64; hidden_in / hidden_out
+ * [2*rnn_layers, N, hidden] (must not overlap); value [M], logp [M] = log pi(action), entropy [1] = mean row entropy may each be NULL.
+ * The hidden state is masked at every step (equal to the reference's segment-wise masking).  M = N (T = 1) is the reference's
+ * single_forward case.  Workspaces grow on demand: a call with a larger M than any before allocates, later ones do not.
+ * train_encoder is accepted for symmetry with pnvo_policy_backward; the forward keeps the same activations either way. */
+int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions,
+                         const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder,
+                         float *hidden_out, float *value, float *logp, float *entropy, void *stream);
+
+/* The minibatch loss of rl/ppo/ppo.py:101-126 for the last pnvo_policy_evaluate: out3 (device) = {value_loss, action_loss,
+ * dist_entropy}; the gradient of total = value_loss * value_coef + action_loss - dist_entropy * entropy_coef with respect to the
+ * logits and the value stays in the handle for pnvo_policy_backward.  All inputs [M], device.  value_preds may be NULL when
+ * use_clipped_value_loss is 0. */
+int pnvo_policy_ppo_loss(pnvo_policy_handle h, const float *actions_logp_old, const float *adv, const float *value_preds,
+                         const float *returns, float clip, float value_coef, float entropy_coef, int use_clipped_value_loss,
+                         float *out3, void *stream);
+
+/* total.backward(): fills the whole gradient buffer (overwrites; no accumulation).  No gradient is taken with respect to the
+ * rollout's initial hidden state.  train_encoder = 0 (the reference's _static_encoder: net.visual_encoder frozen) stops after
+ * visual_fc — its weight and bias gradients are filled, the encoder's range is left zero. */
+int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream);
+
+/* nn.utils.clip_grad_norm_(parameters, max_norm) on the gradient buffer, on the device: the global 2-norm (written to norm_out
+ * [1], device, may be NULL) and the scaling by max_norm / (norm + 1e-6) when that is below 1.  No host synchronisation. */
+int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm_out, void *stream);
+
+/* Phase timing of the update step with HIP events recorded on the launch stream (tools/bench_ppo_update.py; not part of the drop-in
+ * surface).  mode 0 = off, 1 = on.  pnvo_policy_train_timing_read waits for the last pnvo_policy_backward and returns the
+ * milliseconds of the last evaluate / ppo_loss / backward: {encoder forward, LSTM forward + heads, loss, heads + BPTT + embedding
+ * backward, encoder backward}. */
+int pnvo_policy_train_timing(pnvo_policy_handle h, int mode);
+int pnvo_policy_train_timing_read(pnvo_policy_handle h, double ms[5]);
+
 /* F.avg_pool2d(x, 2) of 1-channel NHWC frames [N,H,W,1] -> [N,H/2,W/2,2] with channel 1 = 0 (resnet_policy.py:168). */
 int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *stream);
 

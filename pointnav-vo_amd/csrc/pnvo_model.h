@@ -312,6 +312,8 @@ int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
 const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name);   // pnvo_train_api.hip: device pointer or nullptr
+const float *pnvo_train_hidden(pnvo_handle m);   // pnvo_train_api.hip: [B, hidden] output of visual_fc of the last train-mode forward, or nullptr
+int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream);   // the backward entered below the output head
 void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &)> &gn_bound);   // pnvo_api.hip
 const float *pnvo_train_x2_scale(pnvo_handle m, const std::string &name);     // device {scale, 1/scale} of that conv weight's float16 pieces, or nullptr
 void pnvo_bf16_free(pnvo_handle m);    // pnvo_bf16.hip

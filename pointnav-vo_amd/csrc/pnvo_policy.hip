@@ -21,6 +21,7 @@
 #include "../../include/pnvo.h"
 #include "pnvo_internal.h"
 #include "pnvo_model.h"
+#include "pnvo_policy_state.h"
 
 namespace pnvo {
 namespace {
@@ -153,20 +154,6 @@ __global__ __launch_bounds__(256) void policy_heads_kernel(const float *x, const
   }
 }
 
-struct Policy {
-  pnvo_policy_config cfg;
-  int device = 0;
-  pnvo_handle enc = nullptr;
-  bool loaded = false;
-  // device weights (torch layouts)
-  float *emb = nullptr, *tgt_w = nullptr, *tgt_b = nullptr;
-  std::vector<float *> w_ih, w_hh, b_ih, b_hh;
-  float *act_w = nullptr, *act_b = nullptr, *cr_w = nullptr, *cr_b = nullptr;
-  // workspace
-  int cap = 0;
-  float *pooled = nullptr, *visual = nullptr, *x = nullptr;
-};
-
 int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
 
 #define PCHK(expr)                                                                              \
@@ -213,11 +200,26 @@ int upload(float *&dst, const float *src, size_t n) {
 
 using namespace pnvo;
 
-extern "C" {
+void pnvo::pnvo_policy_free_weights(Policy &p) {
+  if (!p.attached) {
+    dfree(p.emb);
+    dfree(p.tgt_w);
+    dfree(p.tgt_b);
+    for (auto &v : p.w_ih) dfree(v);
+    for (auto &v : p.w_hh) dfree(v);
+    for (auto &v : p.b_ih) dfree(v);
+    for (auto &v : p.b_hh) dfree(v);
+    dfree(p.act_w);
+    dfree(p.act_b);
+    dfree(p.cr_w);
+    dfree(p.cr_b);
+  }
+  p.emb = p.tgt_w = p.tgt_b = p.act_w = p.act_b = p.cr_w = p.cr_b = nullptr;
+  for (auto *v : {&p.w_ih, &p.w_hh, &p.b_ih, &p.b_hh})
+    for (auto &q : *v) q = nullptr;
+}
 
-struct pnvo_policy_s {
-  Policy p;
-};
+extern "C" {
 
 int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *stream) {
   if (!depth || !out || N < 0 || H < 2 || W < 2) return pfail(PNVO_ERR_ARG, "bad argument");
@@ -273,6 +275,9 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
                              int ntoc) {
   if (!h || !blob || !toc) return pfail(PNVO_ERR_ARG, "null argument");
   Policy &p = h->p;
+  if (p.attached)
+    return pfail(PNVO_ERR_STATE, "pnvo_policy_load_weights after pnvo_policy_train_attach: the parameters live in the caller's flat buffer "
+                                 "(write them there and call pnvo_policy_train_refresh)");
   PCHK(hipSetDevice(p.device));
   std::map<std::string, const pnvo_tensor_desc *> by;
   for (int k = 0; k < ntoc; ++k) by[toc[k].name] = &toc[k];
@@ -418,18 +423,9 @@ int pnvo_policy_destroy(pnvo_policy_handle h) {
   if (!h) return PNVO_OK;
   Policy &p = h->p;
   (void)hipSetDevice(p.device);
+  pnvo_policy_train_free(p);
   if (p.enc) pnvo_destroy(p.enc);
-  dfree(p.emb);
-  dfree(p.tgt_w);
-  dfree(p.tgt_b);
-  for (auto &v : p.w_ih) dfree(v);
-  for (auto &v : p.w_hh) dfree(v);
-  for (auto &v : p.b_ih) dfree(v);
-  for (auto &v : p.b_hh) dfree(v);
-  dfree(p.act_w);
-  dfree(p.act_b);
-  dfree(p.cr_w);
-  dfree(p.cr_b);
+  pnvo_policy_free_weights(p);
   dfree(p.pooled);
   dfree(p.visual);
   dfree(p.x);

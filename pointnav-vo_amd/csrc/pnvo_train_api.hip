@@ -1058,7 +1058,7 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
   return PNVO_OK;
 }
 
-static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream);
+static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream, const float *dh_in = nullptr, bool stop_after_fc = false);
 
 // bucket k of the gradient-ready hook is final: report it (host callback; the launches that produce it are enqueued on `s`)
 static void report_bucket(TrainState *t, size_t k, hipStream_t s) {
@@ -1081,11 +1081,28 @@ int pnvo_train_backward(pnvo_handle m, const float *grad_out, void *stream) {
   return rc;
 }
 
-static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream) {
+// The hidden vector of the last pnvo_train_forward (visual_fc's output after its ReLU), [B, hidden] on the device; nullptr before one.
+extern "C++" const float *pnvo_train_hidden(pnvo_handle m) {
+  return m && m->train && TS(m)->lastB > 0 ? TS(m)->hid : nullptr;
+}
+
+// The backward entered BELOW the output head: dh [B, hidden] = dLoss / d(hidden vector) comes from the caller (the navigation policy's
+// recurrent part, policy_train.hip), the head's own gradients are left alone.  stop_after_fc: only visual_fc's weight and bias
+// gradients are written (a frozen visual encoder).
+extern "C++" int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream) {
+  if (!dh) return pnvo_fail(m, PNVO_ERR_ARG, "null hidden gradient");
+  if (m && m->train) TS(m)->bucket_done.assign(TS(m)->bucket_first.size(), 0);
+  const int rc = train_backward_body(m, nullptr, stream, dh, stop_after_fc);
+  if (rc == PNVO_OK && m->train)
+    for (size_t k = 0; k < TS(m)->bucket_first.size(); ++k) report_bucket(TS(m), k, (hipStream_t)stream);
+  return rc;
+}
+
+static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream, const float *dh_in, bool stop_after_fc) {
   if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
   TrainState *t = TS(m);
   g_wgrad_x3 = m->opt.wgrad3;
-  if (t->lastB <= 0 || !grad_out) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_forward first");
+  if (t->lastB <= 0 || (!grad_out && !dh_in)) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_forward first");
   HIPCHK(m, hipSetDevice(m->device));
   const pnvo_config &c = m->cfg;
   const int B = t->lastB;
@@ -1096,9 +1113,11 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
     if ((rc = dmalloc(m, (void **)&t->dmax, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned))) != PNVO_OK) return rc;
   }
   if (t->dmax) HIPCHK(m, hipMemsetAsync(t->dmax, 0, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned), s));   // maxima of this backward's gradients
-  // ---- output head: out = hid . W2^T + b2
-  HIPCHK(m, launch_padcopy(grad_out, B, c.out_dim, 8, t->dout8, s));
-  {
+  // ---- output head: out = hid . W2^T + b2  (skipped when the caller supplies dLoss / dhid itself)
+  if (dh_in != nullptr) {
+    HIPCHK(m, hipMemcpyAsync(t->dh, dh_in, (size_t)B * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {
+    HIPCHK(m, launch_padcopy(grad_out, B, c.out_dim, 8, t->dout8, s));
     float *gb = gradp(m, t, "output_head.1.bias", &rc);
     if (!gb) return rc;
     HIPCHK(m, launch_colsum(grad_out, B, c.out_dim, c.out_dim, gb, s));
@@ -1161,6 +1180,7 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
       HIPCHK(m, launch_embed_scatter(t->dfeat, t->actions, B, c.n_acts + 1, t->grads + t->emb_off, s));
     }
     if ((rc = run_wgrad(m, t, a, m->fc.name + ".weight", nullptr, m->comp_c, s)) != PNVO_OK) return rc;
+    if (stop_after_fc) return PNVO_OK;
     ConvArgs d;
     std::memset(&d, 0, sizeof(d));
     d.x = t->gh;

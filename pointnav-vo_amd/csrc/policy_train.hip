@@ -1,0 +1,951 @@
+// policy_train.hip — one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions,
+// rl/policies/policy.py:52-63), gfx950 only, float32.
+//
+//   evaluate : depth [T*N] -> avg_pool2d(2) -> the visual encoder's TRAIN-mode forward (pnvo_train_forward: activations kept)
+//              -> x = [visual | tgt_embeding | prev_action_embedding]                       rollout_inputs_kernel, M = T*N rows
+//              -> per LSTM layer: G_x = X . W_ih^T + b_ih + b_hh over all M rows            gemm_f32_kernel (v_mfma_f32_32x32x2_f32)
+//                                 T launches of lstm_step_kernel (the only sequential part)  gates, c, h, masked h_prev kept
+//              -> logits / value / log pi(a) / entropy per row                               heads_eval_kernel
+//   ppo_loss : clipped surrogate, clipped or plain value loss, entropy mean; d total / d logits, d total / d value   ppo_loss_kernel
+//   backward : heads -> per layer (top first) T launches of bptt_step_kernel, then dW_ih / dW_hh / dX as GEMMs over all rows and the
+//              bias gradients as column sums -> embeddings -> d visual into the encoder's backward below its output head.
+// Rows are T-major (row t*N + n: the order RolloutStorage.recurrent_generator yields), weights in torch's [4H][K] layouts read straight
+// from the caller's flat parameter buffer, gate order i, f, g, o.  Every reduction runs in a fixed order (no float atomics): the same
+// call gives the same bits twice.  Masking h and c at EVERY step equals the reference's segment-wise masking
+// (model_utils/rnns/rnn_state_encoder.py:81-134): inside a segment all masks are 1.
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/pnvo.h"
+#include "pnvo_internal.h"
+#include "pnvo_model.h"
+#include "pnvo_policy_state.h"
+
+namespace pnvo {
+
+struct PolicyTrain {
+  float *params = nullptr, *grads = nullptr;
+  size_t n = 0, n_named = 0;          // floats handed over / floats covered by the parameter table (the rest is the tail below)
+  size_t o_emb = 0, o_tgt_w = 0, o_tgt_b = 0, o_stem = 0, o_act_w = 0, o_act_b = 0, o_cr_w = 0, o_cr_b = 0;
+  std::vector<size_t> o_wih, o_whh, o_bih, o_bhh;
+  size_t o_stem2 = 0;                 // tail: the stem weight zero-padded to the encoder handle's 2 input channels [C0,2,7,7],
+  int c0 = 0;                         //       then the handle's unused output head (hidden weights + 1 bias, zeros)
+  // the last evaluate
+  int T = 0, N = 0, M = 0;
+  bool have_loss = false;
+  // workspace, sized for capM rows
+  int capM = 0;
+  float *pooled = nullptr, *enc_out = nullptr, *x0 = nullptr, *g3 = nullptr, *masks = nullptr, *hid0 = nullptr;
+  int *rows = nullptr;
+  int64_t *actions = nullptr;
+  std::vector<float *> gates, c, y, hm;
+  float *logits = nullptr, *value = nullptr, *logp = nullptr, *ent = nullptr, *dlogits = nullptr, *dvalue = nullptr;
+  float *dY = nullptr, *dX0 = nullptr, *dG = nullptr, *dC = nullptr, *whhT = nullptr;
+  double *sq_part = nullptr;          // clip_grad_norm partial sums
+  // pnvo_policy_train_timing: events at the phase boundaries of evaluate / ppo_loss / backward (tools/bench_ppo_update.py)
+  bool timing = false;
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int SQ_BLOCKS = 1024;
+
+int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
+
+#define PCHK(expr)                                                                              \
+  do {                                                                                          \
+    hipError_t e__ = (expr);                                                                    \
+    if (e__ != hipSuccess) return pfail(PNVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+  } while (0)
+
+template <class T>
+void dfree(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------------------ rollout inputs
+// x [M, hidden + 64]: visual | Linear(3 -> 32)(rho, cos(-phi), sin(-phi)) | Embedding((a + 1) * mask)  — policy_inputs_kernel over the
+// M = T*N rows of a rollout; the gathered embedding row and (rho, cos(-phi), sin(-phi)) are kept per row for the backward
+__global__ __launch_bounds__(256) void rollout_inputs_kernel(const float *visual, const float *goal, const int64_t *prev, const float *masks,
+                                                           const float *tgt_w, const float *tgt_b, const float *emb, int n_emb, int M,
+                                                           int hidden, float *x, int *rows, float *g3) {
+  const int K = hidden + 64;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)M * K) return;
+  const int b = (int)(e / K), k = (int)(e % K);
+  float v;
+  if (k < hidden) {
+    v = visual[(long)b * hidden + k];
+  } else if (k < hidden + 32) {
+    const int j = k - hidden;
+    const float rho = goal[2 * b], phi = goal[2 * b + 1];
+    const float g0 = rho, g1 = cosf(-phi), g2 = sinf(-phi);
+    v = __builtin_fmaf(tgt_w[3 * j + 2], g2, __builtin_fmaf(tgt_w[3 * j + 1], g1, tgt_w[3 * j] * g0)) + tgt_b[j];
+    if (j == 0) {
+      g3[3 * b] = g0;
+      g3[3 * b + 1] = g1;
+      g3[3 * b + 2] = g2;
+    }
+  } else {
+    const int j = k - hidden - 32;
+    long row = (long)(((float)prev[b] + 1.0f) * masks[b]);     // ((prev_actions.float() + 1) * masks).long()
+    if (row < 0) row = 0;
+    if (row >= n_emb) row = n_emb - 1;
+    v = emb[row * 32 + j];
+    if (j == 0) rows[b] = (int)row;
+  }
+  x[e] = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------ float32 GEMM
+// C[m][n] = sum_k A(m,k) B(k,n) (+ bias0[n] + bias1[n]) on the exact-float32 matrix instruction (one k-ordered fmaf chain per output,
+// as conv_mfma.hip): workgroup = 64 x 64 outputs, wave = 32 x 32, K in steps of 32 staged through LDS as [k][m] / [k][n].  Both
+// operands are addressed by two strides, so the four products of the LSTM (X . W^T, dG^T . X, dG . W) are one kernel; AKC / BKC say
+// which index is contiguous in memory (k, else m / n) and pick the staging order that reads whole lines.
+struct GemmArgs {
+  const float *A, *B, *bias0, *bias1;
+  float *C;
+  int M, N, K;
+  long a_sm, a_sk, b_sk, b_sn, ldc;
+};
+
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
+  __shared__ float As[32][65], Bs[32][65];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int k0 = 0; k0 < g.K; k0 += 32) {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      const int kk = AKC ? (tid & 31) : p * 4 + (tid >> 6);
+      const int mm = AKC ? p * 8 + (tid >> 5) : (tid & 63);
+      const int m = m0 + mm, k = k0 + kk;
+      As[kk][mm] = (m < g.M && k < g.K) ? g.A[(long)m * g.a_sm + (long)k * g.a_sk] : 0.f;
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      const int kk = BKC ? (tid & 31) : p * 4 + (tid >> 6);
+      const int nn = BKC ? p * 8 + (tid >> 5) : (tid & 63);
+      const int n = n0 + nn, k = k0 + kk;
+      Bs[kk][nn] = (n < g.N && k < g.K) ? g.B[(long)k * g.b_sk + (long)n * g.b_sn] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      const float a = As[2 * kk + (lane >> 5)][wm + (lane & 31)];
+      const float b = Bs[2 * kk + (lane >> 5)][wn + (lane & 31)];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const int col = n0 + wn + (lane & 31);
+  if (col >= g.N) return;
+  float bias = 0.f;
+  if (g.bias0) bias = g.bias0[col];
+  if (g.bias1) bias += g.bias1[col];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (row < g.M) g.C[(long)row * g.ldc + col] = acc[r] + bias;
+  }
+}
+
+template <bool AKC, bool BKC>
+hipError_t launch_gemm(const GemmArgs &g, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_f32_kernel<AKC, BKC>), dim3((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64)), dim3(256), 0, s, g);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------ recurrent step
+// One (t, layer): workgroup = hidden unit j, wave = gate (lstm_layer_kernel's shape).  g holds this step's N rows of G_x on entry and
+// the ACTIVATED gates (i, f, g, o) on exit; y (= h[t], the layer's output rows), c[t] and hm = h[t-1] * mask[t] (dW_hh's operand)
+// are written beside them.  h_fin / c_fin: the rollout's final state (last step only, else nullptr).
+__global__ __launch_bounds__(256) void lstm_step_kernel(float *g, const float *h_prev, const float *c_prev, const float *w_hh,
+                                                      const float *masks, int N, int Hd, float *y, float *c_out, float *hm, float *h_fin,
+                                                      float *c_fin) {
+  __shared__ float sg[4][64];
+  const int lane = threadIdx.x & 63, gate = (int)(threadIdx.x >> 6), j = blockIdx.x;
+  const int n = gate * Hd + j, H4 = Hd >> 2;
+  const long G = 4L * Hd;
+  const f32x4 *wh = reinterpret_cast<const f32x4 *>(w_hh + (long)n * Hd);
+  for (int b0 = 0; b0 < N; b0 += 64) {
+    const int nb = min(64, N - b0);
+    for (int bb = 0; bb < nb; ++bb) {
+      const int b = b0 + bb;
+      const f32x4 *hr = reinterpret_cast<const f32x4 *>(h_prev + (long)b * Hd);
+      float u = 0.f;
+      for (int k = lane; k < H4; k += 64) {
+        const f32x4 w = wh[k], v = hr[k];
+        u = __builtin_fmaf(w[0], v[0], u);
+        u = __builtin_fmaf(w[1], v[1], u);
+        u = __builtin_fmaf(w[2], v[2], u);
+        u = __builtin_fmaf(w[3], v[3], u);
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) u += __shfl_xor(u, o);
+      if (lane == 0) sg[gate][bb] = g[b * G + n] + u * masks[b];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+      const int b = b0 + (int)threadIdx.x;
+      const long e = (long)b * Hd + j;
+      const float mk = masks[b];
+      const float i_ = 1.f / (1.f + expf(-sg[0][threadIdx.x]));
+      const float f_ = 1.f / (1.f + expf(-sg[1][threadIdx.x]));
+      const float g_ = tanhf(sg[2][threadIdx.x]);
+      const float o_ = 1.f / (1.f + expf(-sg[3][threadIdx.x]));
+      const float c = f_ * (c_prev[e] * mk) + i_ * g_;
+      const float h = o_ * tanhf(c);
+      c_out[e] = c;
+      y[e] = h;
+      hm[e] = h_prev[e] * mk;
+      g[b * G + j] = i_;
+      g[b * G + Hd + j] = f_;
+      g[b * G + 2 * Hd + j] = g_;
+      g[b * G + 3 * Hd + j] = o_;
+      if (h_fin != nullptr) {
+        h_fin[e] = h;
+        c_fin[e] = c;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ heads
+// One wave per row: logits (lane o < A keeps logit o), value (lane A), then log-softmax, log pi(a) and the row entropy across the lanes
+// (CategoricalNet / CustomFixedCategorical, utils/misc_utils.py:50-78; CriticHead, policy.py:66-74).  A <= 32.
+__global__ __launch_bounds__(256) void heads_eval_kernel(const float *feat, const float *act_w, const float *act_b, const float *cr_w,
+                                                       const float *cr_b, const int64_t *actions, int M, int Hd, int A, float *logits,
+                                                       float *value, float *logp, float *ent) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (m >= M) return;
+  const f32x4 *xr = reinterpret_cast<const f32x4 *>(feat + (long)m * Hd);
+  const int H4 = Hd >> 2;
+  float mine = 0.f;
+  for (int o = 0; o <= A; ++o) {
+    const f32x4 *wr = reinterpret_cast<const f32x4 *>(o < A ? act_w + (long)o * Hd : cr_w);
+    float s = 0.f;
+    for (int k = lane; k < H4; k += 64) {
+      const f32x4 w = wr[k], v = xr[k];
+      s = __builtin_fmaf(w[0], v[0], s);
+      s = __builtin_fmaf(w[1], v[1], s);
+      s = __builtin_fmaf(w[2], v[2], s);
+      s = __builtin_fmaf(w[3], v[3], s);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    if (lane == o) mine = s + (o < A ? act_b[o] : cr_b[0]);
+  }
+  const bool is_logit = lane < A;
+  float mx = is_logit ? mine : -INFINITY;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+  float se = is_logit ? expf(mine - mx) : 0.f;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) se += __shfl_xor(se, d);
+  const float lp = mine - (mx + logf(se));
+  float pe = is_logit ? expf(lp) * lp : 0.f;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) pe += __shfl_xor(pe, d);
+  long a = actions[m];
+  a = a < 0 ? 0 : (a >= A ? A - 1 : a);
+  const float lpa = __shfl(lp, (int)a);
+  if (is_logit) logits[(long)m * A + lane] = mine;
+  if (lane == A) value[m] = mine;
+  if (lane == 0) {
+    logp[m] = lpa;
+    ent[m] = -pe;
+  }
+}
+
+// out[0] = mean of x[0 .. n) — one workgroup, a fixed summation order
+__global__ __launch_bounds__(256) void mean_kernel(const float *x, int n, float *out) {
+  __shared__ double sd[256];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += (double)x[i];
+  sd[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(sd[0] / n);
+}
+
+// The minibatch loss of rl/ppo/ppo.py:101-126 and its gradient with respect to the logits and the value, one workgroup:
+//   ratio = exp(logp - logp_old); action_loss = -mean(min(ratio * adv, clamp(ratio, 1 - clip, 1 + clip) * adv))
+//   value_loss = 0.5 * mean(max((v - R)^2, (vp + clamp(v - vp, -clip, clip) - R)^2))   or   0.5 * mean((R - v)^2)
+//   total = value_loss * vc + action_loss - mean(entropy) * ec;      out3 = {value_loss, action_loss, mean(entropy)}
+// torch's gradient rules: min / max pass the gradient to the smaller / larger argument and half to each when they are equal, clamp
+// passes it where lo <= x <= hi — inside the clip range both branches are equal and the full gradient passes.
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const float *logits, const float *value, const float *logp, const float *ent,
+                                                     const int64_t *actions, const float *old_logp, const float *adv, const float *vpred,
+                                                     const float *ret, int M, int A, float clip, float vc, float ec, int use_clipped,
+                                                     float *out3, float *dlogits, float *dvalue) {
+  __shared__ double sd[3][256];
+  double sv = 0.0, sa = 0.0, se = 0.0;
+  const float inv_m = 1.f / (float)M;
+  for (int m = threadIdx.x; m < M; m += 256) {
+    const float ratio = expf(logp[m] - old_logp[m]), ad = adv[m];
+    const float lo = 1.f - clip, hi = 1.f + clip;
+    const float s1 = ratio * ad, s2 = fminf(fmaxf(ratio, lo), hi) * ad;
+    const bool inr = ratio >= lo && ratio <= hi;
+    const float g2 = inr ? ad : 0.f;
+    const float gr = s1 < s2 ? ad : (s1 > s2 ? g2 : 0.5f * ad + 0.5f * g2);
+    sa += (double)fminf(s1, s2);
+    const float g_lp = -(gr * ratio) * inv_m;                 // d total / d log pi(a)
+    const float v = value[m], R = ret[m];
+    if (use_clipped) {
+      const float vp = vpred[m], d = v - vp;
+      const float e1 = v - R, e2 = (vp + fminf(fmaxf(d, -clip), clip)) - R;
+      const float l1 = e1 * e1, l2 = e2 * e2;
+      const float ge2 = (d >= -clip && d <= clip) ? e2 : 0.f;
+      sv += (double)fmaxf(l1, l2);
+      const float gv = l1 > l2 ? 2.f * e1 : (l2 > l1 ? 2.f * ge2 : e1 + ge2);
+      dvalue[m] = vc * 0.5f * gv * inv_m;
+    } else {
+      const float e = R - v;
+      sv += (double)(e * e);
+      dvalue[m] = vc * (v - R) * inv_m;
+    }
+    const float H = ent[m];
+    se += (double)H;
+    const float *l = logits + (long)m * A;
+    float mx = l[0];
+    for (int k = 1; k < A; ++k) mx = fmaxf(mx, l[k]);
+    float sum = 0.f;
+    for (int k = 0; k < A; ++k) sum += expf(l[k] - mx);
+    const float lse = mx + logf(sum);
+    long a = actions[m];
+    a = a < 0 ? 0 : (a >= A ? A - 1 : a);
+    for (int k = 0; k < A; ++k) {
+      const float lpk = l[k] - lse, pk = expf(lpk);
+      // d log pi(a) / d logit_k = [k == a] - p_k;   d entropy / d logit_k = -p_k (log p_k + entropy)
+      dlogits[(long)m * A + k] = g_lp * ((k == a ? 1.f : 0.f) - pk) + ec * inv_m * pk * (lpk + H);
+    }
+  }
+  sd[0][threadIdx.x] = sv;
+  sd[1][threadIdx.x] = sa;
+  sd[2][threadIdx.x] = se;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sd[0][threadIdx.x] += sd[0][threadIdx.x + o];
+      sd[1][threadIdx.x] += sd[1][threadIdx.x + o];
+      sd[2][threadIdx.x] += sd[2][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out3[0] = (float)(0.5 * sd[0][0] / M);
+    out3[1] = (float)(-sd[1][0] / M);
+    out3[2] = (float)(sd[2][0] / M);
+  }
+}
+
+// head weight / bias gradients: one thread per (output o <= A, column k), rows summed in order
+__global__ __launch_bounds__(256) void heads_bwd_w_kernel(const float *feat, const float *dlogits, const float *dvalue, int M, int Hd, int A,
+                                                        float *g_act_w, float *g_act_b, float *g_cr_w, float *g_cr_b) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)(A + 1) * Hd) return;
+  const int o = (int)(e / Hd), k = (int)(e % Hd);
+  float s = 0.f, sb = 0.f;
+  for (int m = 0; m < M; ++m) {
+    const float d = o < A ? dlogits[(long)m * A + o] : dvalue[m];
+    s = __builtin_fmaf(d, feat[(long)m * Hd + k], s);
+    sb += d;
+  }
+  if (o < A) g_act_w[(long)o * Hd + k] = s; else g_cr_w[k] = s;
+  if (k == 0) {
+    if (o < A) g_act_b[o] = sb; else g_cr_b[0] = sb;
+  }
+}
+
+// d features = dlogits . W_act + dvalue . W_cr
+__global__ __launch_bounds__(256) void heads_bwd_x_kernel(const float *dlogits, const float *dvalue, const float *act_w, const float *cr_w,
+                                                        int M, int Hd, int A, float *dfeat) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)M * Hd) return;
+  const int m = (int)(e / Hd), k = (int)(e % Hd);
+  float s = dvalue[m] * cr_w[k];
+  for (int a = 0; a < A; ++a) s = __builtin_fmaf(dlogits[(long)m * A + a], act_w[(long)a * Hd + k], s);
+  dfeat[e] = s;
+}
+
+// dst [C][R] = src [R][C]^T
+__global__ __launch_bounds__(256) void transpose_kernel(const float *src, int R, int C, float *dst) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x & 31, ty = (int)(threadIdx.x >> 5);
+  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+  for (int i = ty; i < 32; i += 8)
+    if (r0 + i < R && c0 + tx < C) tile[i][tx] = src[(long)(r0 + i) * C + c0 + tx];
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8)
+    if (c0 + i < C && r0 + tx < R) dst[(long)(c0 + i) * R + r0 + tx] = tile[tx][i];
+}
+
+// ------------------------------------------------------------------------------------------------------------ BPTT step
+// One (t, layer), run for t = T-1 .. 0: workgroup = hidden unit j.  With the finished dgates[t+1] of the previous launch (dg_n; nullptr
+// at t = T-1) the four waves form dh_rec[b] = mask[t+1][b] * (dgates[t+1][b] . W_hh[:, j]) — each wave one gate block of the
+// transposed weight row whhT[j][0 .. 4H), summed in gate order — then the first lanes run the cell backward for (b, j):
+//   dh = dY[t] + dh_rec;  dc = dh * o * (1 - tanh(c)^2) + mask[t+1] * f[t+1] * dc[t+1]
+//   dgates[t] = (dc g i(1-i), dc c_prev f(1-f), dc i (1-g^2), dh tanh(c) o(1-o)),  c_prev = c[t-1] * mask[t]
+__global__ __launch_bounds__(256) void bptt_step_kernel(const float *gates_t, const float *gates_n, const float *dg_n, const float *dc_n,
+                                                      const float *mask_n, const float *c_t, const float *c_prev, const float *mask_t,
+                                                      const float *whhT, const float *dY_t, int N, int Hd, float *dg_t, float *dc_t) {
+  __shared__ float sg[4][64];
+  const int lane = threadIdx.x & 63, gate = (int)(threadIdx.x >> 6), j = blockIdx.x;
+  const int H4 = Hd >> 2;
+  const long G = 4L * Hd;
+  const f32x4 *wt = reinterpret_cast<const f32x4 *>(whhT + (long)j * G + (long)gate * Hd);
+  for (int b0 = 0; b0 < N; b0 += 64) {
+    const int nb = min(64, N - b0);
+    if (dg_n != nullptr) {
+      for (int bb = 0; bb < nb; ++bb) {
+        const f32x4 *dr = reinterpret_cast<const f32x4 *>(dg_n + (long)(b0 + bb) * G + (long)gate * Hd);
+        float u = 0.f;
+        for (int k = lane; k < H4; k += 64) {
+          const f32x4 w = wt[k], v = dr[k];
+          u = __builtin_fmaf(w[0], v[0], u);
+          u = __builtin_fmaf(w[1], v[1], u);
+          u = __builtin_fmaf(w[2], v[2], u);
+          u = __builtin_fmaf(w[3], v[3], u);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) u += __shfl_xor(u, o);
+        if (lane == 0) sg[gate][bb] = u;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+      const int b = b0 + (int)threadIdx.x;
+      const long e = (long)b * Hd + j;
+      float dh = dY_t[e], dc_rec = 0.f;
+      if (dg_n != nullptr) {
+        const float mn = mask_n[b];
+        dh += mn * (((sg[0][threadIdx.x] + sg[1][threadIdx.x]) + sg[2][threadIdx.x]) + sg[3][threadIdx.x]);
+        dc_rec = mn * gates_n[b * G + Hd + j] * dc_n[e];
+      }
+      const float i_ = gates_t[b * G + j], f_ = gates_t[b * G + Hd + j], g_ = gates_t[b * G + 2 * Hd + j], o_ = gates_t[b * G + 3 * Hd + j];
+      const float tc = tanhf(c_t[e]);
+      const float dc = dh * o_ * (1.f - tc * tc) + dc_rec;
+      const float cp = c_prev[e] * mask_t[b];
+      dc_t[e] = dc;
+      dg_t[b * G + j] = dc * g_ * i_ * (1.f - i_);
+      dg_t[b * G + Hd + j] = dc * cp * f_ * (1.f - f_);
+      dg_t[b * G + 2 * Hd + j] = dc * i_ * (1.f - g_ * g_);
+      dg_t[b * G + 3 * Hd + j] = dh * tc * o_ * (1.f - o_);
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ input gradients
+// From layer 0's dX [M, hidden + 64]: d visual (the first `hidden` columns, copied out contiguous), tgt_embeding's weight [32,3] and
+// bias [32], and prev_action_embedding [n_emb, 32] as an ordered sum over the rows that gathered each entry (no atomics; an entry no
+// row gathered gets exactly 0).
+__global__ __launch_bounds__(256) void inputs_bwd_kernel(const float *dX0, const int *rows, const float *g3, int M, int Hd, int n_emb,
+                                                       float *g_tgt_w, float *g_tgt_b, float *g_emb, float *dvis) {
+  const int K = Hd + 64;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long ncopy = (long)M * Hd;
+  if (e < ncopy) {
+    dvis[e] = dX0[(e / Hd) * K + (e % Hd)];
+    return;
+  }
+  const long q = e - ncopy;
+  if (q < 96) {
+    const int j = (int)(q / 3), c = (int)(q % 3);
+    float s = 0.f;
+    for (int m = 0; m < M; ++m) s = __builtin_fmaf(dX0[(long)m * K + Hd + j], g3[3 * m + c], s);
+    g_tgt_w[q] = s;
+  } else if (q < 128) {
+    const int j = (int)(q - 96);
+    float s = 0.f;
+    for (int m = 0; m < M; ++m) s += dX0[(long)m * K + Hd + j];
+    g_tgt_b[j] = s;
+  } else if (q < 128 + (long)n_emb * 32) {
+    const int r = (int)((q - 128) / 32), j = (int)((q - 128) % 32);
+    float s = 0.f;
+    for (int m = 0; m < M; ++m)
+      if (rows[m] == r) s += dX0[(long)m * K + Hd + 32 + j];
+    g_emb[(long)r * 32 + j] = s;
+  }
+}
+
+// the policy's stem weight [C0,1,7,7] <-> channel 0 of the encoder handle's [C0,2,7,7] (channel 1 stays 0)
+__global__ __launch_bounds__(256) void stem_pad_kernel(const float *w1, int c0, float *w2) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= c0 * 98) return;
+  const int o = e / 98, r = e % 98;
+  w2[e] = r < 49 ? w1[o * 49 + r] : 0.f;
+}
+__global__ __launch_bounds__(256) void stem_unpad_kernel(const float *w2, int c0, float *w1) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= c0 * 49) return;
+  w1[e] = w2[(e / 49) * 98 + (e % 49)];
+}
+
+// clip_grad_norm_: partial sums of squares over fixed slices, then every workgroup folds the partials in the same order and scales
+__global__ __launch_bounds__(256) void sumsq_kernel(const float *g, long n, double *part) {
+  __shared__ double sd[256];
+  double a = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)SQ_BLOCKS * 256) {
+    const double v = (double)g[i];
+    a += v * v;
+  }
+  sd[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = sd[0];
+}
+__global__ __launch_bounds__(256) void clip_scale_kernel(float *g, long n, const double *part, float max_norm, float *norm_out) {
+  __shared__ double sd[256];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < SQ_BLOCKS; i += 256) a += part[i];
+  sd[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+    __syncthreads();
+  }
+  const float norm = (float)sqrt(sd[0]);
+  if (norm_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  const float coef = max_norm / (norm + 1e-6f);              // nn.utils.clip_grad_norm_: clamp(max_norm / (total + 1e-6), max = 1)
+  if (!(coef < 1.f)) return;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) g[i] *= coef;
+}
+
+// phase boundary k of the update step (only while timing is on)
+hipError_t mark(PolicyTrain *t, int k, hipStream_t s) { return t->timing ? hipEventRecord(t->ev[k], s) : hipSuccess; }
+
+void free_ws(PolicyTrain *t) {
+  dfree(t->pooled);
+  dfree(t->enc_out);
+  dfree(t->x0);
+  dfree(t->g3);
+  dfree(t->masks);
+  dfree(t->hid0);
+  dfree(t->rows);
+  dfree(t->actions);
+  for (auto *v : {&t->gates, &t->c, &t->y, &t->hm})
+    for (auto &q : *v) dfree(q);
+  dfree(t->logits);
+  dfree(t->value);
+  dfree(t->logp);
+  dfree(t->ent);
+  dfree(t->dlogits);
+  dfree(t->dvalue);
+  dfree(t->dY);
+  dfree(t->dX0);
+  dfree(t->dG);
+  dfree(t->dC);
+  t->capM = 0;
+}
+
+int ensure_ws(Policy &p, PolicyTrain *t, int M) {
+  if (M <= t->capM) return PNVO_OK;
+  free_ws(t);
+  const pnvo_policy_config &c = p.cfg;
+  const size_t Hd = (size_t)c.hidden, K0 = Hd + 64, L = (size_t)c.rnn_layers, m = (size_t)M, A = (size_t)c.n_actions;
+  auto fl = [&](float *&q, size_t n) { return hipMalloc((void **)&q, (n ? n : 4) * sizeof(float)); };
+  PCHK(fl(t->pooled, m * (c.height / 2) * (c.width / 2) * 2));
+  PCHK(fl(t->enc_out, m));
+  PCHK(fl(t->x0, m * K0));
+  PCHK(fl(t->g3, m * 3));
+  PCHK(fl(t->masks, m));
+  PCHK(fl(t->hid0, 2 * L * m * Hd));
+  PCHK(hipMalloc((void **)&t->rows, m * sizeof(int)));
+  PCHK(hipMalloc((void **)&t->actions, m * sizeof(int64_t)));
+  t->gates.assign(L, nullptr);
+  t->c.assign(L, nullptr);
+  t->y.assign(L, nullptr);
+  t->hm.assign(L, nullptr);
+  for (size_t l = 0; l < L; ++l) {
+    PCHK(fl(t->gates[l], m * 4 * Hd));
+    PCHK(fl(t->c[l], m * Hd));
+    PCHK(fl(t->y[l], m * Hd));
+    PCHK(fl(t->hm[l], m * Hd));
+  }
+  PCHK(fl(t->logits, m * A));
+  PCHK(fl(t->value, m));
+  PCHK(fl(t->logp, m));
+  PCHK(fl(t->ent, m));
+  PCHK(fl(t->dlogits, m * A));
+  PCHK(fl(t->dvalue, m));
+  PCHK(fl(t->dY, m * Hd));
+  PCHK(fl(t->dX0, m * K0));
+  PCHK(fl(t->dG, m * 4 * Hd));
+  PCHK(fl(t->dC, m * Hd));
+  t->capM = M;
+  return PNVO_OK;
+}
+
+// the encoder handle's own parameter table inside the policy's flat buffer: the VO model's names, the padded stem and the unused head
+// in the tail
+int attach_encoder(Policy &p, PolicyTrain *t, const pnvo_tensor_desc *toc, int ntoc) {
+  const std::string pre = "net.visual_encoder.";
+  std::vector<std::string> names;
+  std::vector<pnvo_tensor_desc> etoc;
+  auto push = [&](const std::string &name, size_t off, std::vector<int64_t> shape) {
+    pnvo_tensor_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.offset = off;
+    d.ndim = (int)shape.size();
+    for (size_t k = 0; k < shape.size(); ++k) d.shape[k] = shape[k];
+    names.push_back(name);
+    etoc.push_back(d);
+  };
+  for (int k = 0; k < ntoc; ++k) {
+    const std::string nm = toc[k].name;
+    std::vector<int64_t> shape(toc[k].shape, toc[k].shape + toc[k].ndim);
+    if (nm == pre + "backbone.conv1.0.weight")
+      push("visual_encoder.backbone.conv1.0.weight", t->o_stem2, {shape[0], 2, shape[2], shape[3]});
+    else if (nm.compare(0, pre.size(), pre) == 0)
+      push("visual_encoder." + nm.substr(pre.size()), toc[k].offset, shape);
+    else if (nm == "net.visual_fc.1.weight")
+      push("visual_fc.2.weight", toc[k].offset, shape);
+    else if (nm == "net.visual_fc.1.bias")
+      push("visual_fc.2.bias", toc[k].offset, shape);
+  }
+  const size_t o_head = t->o_stem2 + (size_t)t->c0 * 98;
+  push("output_head.1.weight", o_head, {1, p.cfg.hidden});
+  push("output_head.1.bias", o_head + (size_t)p.cfg.hidden, {1});
+  for (size_t k = 0; k < etoc.size(); ++k) etoc[k].name = names[k].c_str();
+  const int rc = pnvo_train_attach(p.enc, t->params, t->grads, t->n, etoc.data(), (int)etoc.size());
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  return PNVO_OK;
+}
+
+size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 98 + (size_t)c.hidden + 1; }
+
+}  // namespace
+
+void pnvo_policy_train_free(Policy &p) {
+  PolicyTrain *t = p.train;
+  if (!t) return;
+  free_ws(t);
+  dfree(t->whhT);
+  dfree(t->sq_part);
+  for (hipEvent_t &e : t->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete t;
+  p.train = nullptr;
+}
+
+}  // namespace pnvo
+
+using namespace pnvo;
+
+extern "C" {
+
+size_t pnvo_policy_train_tail_floats(pnvo_policy_handle h) { return h ? tail_floats(h->p.cfg) : 0; }
+
+int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc, int ntoc) {
+  if (!h || !params || !grads || !toc) return pfail(PNVO_ERR_ARG, "null argument");
+  Policy &p = h->p;
+  if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach before pnvo_policy_load_weights");
+  PCHK(hipSetDevice(p.device));
+  const pnvo_policy_config &c = p.cfg;
+  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
+  std::map<std::string, const pnvo_tensor_desc *> by;
+  size_t n_named = 0;
+  for (int k = 0; k < ntoc; ++k) {
+    size_t cnt = 1;
+    for (int d = 0; d < toc[k].ndim; ++d) cnt *= (size_t)toc[k].shape[d];
+    if (toc[k].offset + cnt > n_floats) return pfail(PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range");
+    n_named = std::max(n_named, (size_t)toc[k].offset + cnt);
+    by[toc[k].name] = &toc[k];
+  }
+  if (n_floats < n_named + tail_floats(c))
+    return pfail(PNVO_ERR_ARG, "flat buffers hold " + std::to_string(n_floats) + " floats; the " + std::to_string(n_named) +
+                                   " of the parameter table need " + std::to_string(tail_floats(c)) +
+                                   " more behind them (pnvo_policy_train_tail_floats)");
+  int rc = PNVO_OK;
+  auto off = [&](const std::string &name, size_t numel, size_t *out) {
+    auto it = by.find(name);
+    if (it == by.end()) return pfail(PNVO_ERR_WEIGHTS, "parameter table is missing '" + name + "'");
+    size_t cnt = 1;
+    for (int d = 0; d < it->second->ndim; ++d) cnt *= (size_t)it->second->shape[d];
+    if (cnt != numel)
+      return pfail(PNVO_ERR_WEIGHTS, "parameter '" + name + "' has " + std::to_string(cnt) + " elements, expected " + std::to_string(numel));
+    *out = (size_t)it->second->offset;
+    return PNVO_OK;
+  };
+  pnvo_policy_train_free(p);
+  PolicyTrain *t = new PolicyTrain();
+  p.train = t;
+  t->params = params;
+  t->grads = grads;
+  t->n = n_floats;
+  t->n_named = n_named;
+  t->c0 = c.baseplanes;
+  t->o_stem2 = n_named;
+  t->o_wih.assign(L, 0);
+  t->o_whh.assign(L, 0);
+  t->o_bih.assign(L, 0);
+  t->o_bhh.assign(L, 0);
+  if ((rc = off("net.prev_action_embedding.weight", (size_t)(c.n_actions + 1) * 32, &t->o_emb)) != PNVO_OK) return rc;
+  if ((rc = off("net.tgt_embeding.weight", 96, &t->o_tgt_w)) != PNVO_OK) return rc;
+  if ((rc = off("net.tgt_embeding.bias", 32, &t->o_tgt_b)) != PNVO_OK) return rc;
+  if ((rc = off("net.visual_encoder.backbone.conv1.0.weight", (size_t)c.baseplanes * 49, &t->o_stem)) != PNVO_OK) return rc;
+  for (int l = 0; l < L; ++l) {
+    const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
+    const size_t K = l == 0 ? K0 : Hd;
+    if ((rc = off(r + "weight_ih" + sl, (size_t)4 * Hd * K, &t->o_wih[l])) != PNVO_OK) return rc;
+    if ((rc = off(r + "weight_hh" + sl, (size_t)4 * Hd * Hd, &t->o_whh[l])) != PNVO_OK) return rc;
+    if ((rc = off(r + "bias_ih" + sl, (size_t)4 * Hd, &t->o_bih[l])) != PNVO_OK) return rc;
+    if ((rc = off(r + "bias_hh" + sl, (size_t)4 * Hd, &t->o_bhh[l])) != PNVO_OK) return rc;
+  }
+  if ((rc = off("action_distribution.linear.weight", (size_t)c.n_actions * Hd, &t->o_act_w)) != PNVO_OK) return rc;
+  if ((rc = off("action_distribution.linear.bias", (size_t)c.n_actions, &t->o_act_b)) != PNVO_OK) return rc;
+  if ((rc = off("critic.fc.weight", (size_t)Hd, &t->o_cr_w)) != PNVO_OK) return rc;
+  if ((rc = off("critic.fc.bias", 1, &t->o_cr_b)) != PNVO_OK) return rc;
+  for (size_t o : {t->o_emb, t->o_tgt_w, t->o_stem, t->o_act_w, t->o_cr_w})
+    if (o % 4 != 0) return pfail(PNVO_ERR_ARG, "parameter offset " + std::to_string(o) + " is not a multiple of 4 floats (rows are read as float4)");
+  for (int l = 0; l < L; ++l)
+    if (t->o_wih[l] % 4 != 0 || t->o_whh[l] % 4 != 0)
+      return pfail(PNVO_ERR_ARG, "LSTM weight offset of layer " + std::to_string(l) + " is not a multiple of 4 floats (rows are read as float4)");
+  if (((uintptr_t)params & 15) != 0) return pfail(PNVO_ERR_ARG, "flat parameter buffer is not 16-byte aligned");
+  // tail: zero-padded stem + zero output head, gradients zero
+  PCHK(hipMemset(params + n_named, 0, tail_floats(c) * sizeof(float)));
+  PCHK(hipMemset(grads + n_named, 0, tail_floats(c) * sizeof(float)));
+  hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem, t->c0,
+                     params + t->o_stem2);
+  PCHK(hipGetLastError());
+  if ((rc = attach_encoder(p, t, toc, ntoc)) != PNVO_OK) return rc;
+  // the recurrent part and the heads read the flat buffer from now on (pnvo_policy_act included): no second copy
+  pnvo_policy_free_weights(p);
+  p.attached = true;
+  p.emb = params + t->o_emb;
+  p.tgt_w = params + t->o_tgt_w;
+  p.tgt_b = params + t->o_tgt_b;
+  for (int l = 0; l < L; ++l) {
+    p.w_ih[l] = params + t->o_wih[l];
+    p.w_hh[l] = params + t->o_whh[l];
+    p.b_ih[l] = params + t->o_bih[l];
+    p.b_hh[l] = params + t->o_bhh[l];
+  }
+  p.act_w = params + t->o_act_w;
+  p.act_b = params + t->o_act_b;
+  p.cr_w = params + t->o_cr_w;
+  p.cr_b = params + t->o_cr_b;
+  PCHK(hipMalloc((void **)&t->whhT, (size_t)4 * Hd * Hd * sizeof(float)));
+  PCHK(hipMalloc((void **)&t->sq_part, SQ_BLOCKS * sizeof(double)));
+  PCHK(hipDeviceSynchronize());
+  return PNVO_OK;
+}
+
+int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  PCHK(hipSetDevice(p.device));
+  hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->params + t->o_stem,
+                     t->c0, t->params + t->o_stem2);
+  PCHK(hipGetLastError());
+  const int rc = pnvo_train_refresh(p.enc, stream);
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  return PNVO_OK;
+}
+
+int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions, const float *masks,
+                         const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder, float *hidden_out,
+                         float *value, float *logp, float *entropy, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  if (T <= 0 || N <= 0 || (long)T * N > (1L << 20))
+    return pfail(PNVO_ERR_ARG, "bad rollout shape T = " + std::to_string(T) + ", N = " + std::to_string(N));
+  if (!depth || !goal || !prev_actions || !masks || !hidden_in || !actions || !hidden_out)
+    return pfail(PNVO_ERR_ARG, "null argument");
+  (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
+  const pnvo_policy_config &c = p.cfg;
+  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = T * N;
+  {
+    const uintptr_t bytes = (uintptr_t)2 * L * N * Hd * sizeof(float);
+    const uintptr_t in0 = (uintptr_t)hidden_in, out0 = (uintptr_t)hidden_out;
+    if (in0 < out0 + bytes && out0 < in0 + bytes)
+      return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * N * hidden floats): pass separate buffers");
+  }
+  PCHK(hipSetDevice(p.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = ensure_ws(p, t, M);
+  if (rc != PNVO_OK) return rc;
+  t->T = T;
+  t->N = N;
+  t->M = M;
+  t->have_loss = false;
+  // what the backward reads later is kept here: the caller's tensors may be gone by then
+  PCHK(hipMemcpyAsync(t->masks, masks, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
+  PCHK(hipMemcpyAsync(t->actions, actions, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  PCHK(hipMemcpyAsync(t->hid0, hidden_in, (size_t)2 * L * N * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+  PCHK(mark(t, 0, s));
+  if ((rc = pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK) return rc;
+  rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, nullptr, nullptr, t->enc_out, stream);
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  PCHK(mark(t, 1, s));
+  const float *visual = pnvo_train_hidden(p.enc);
+  if (!visual) return pfail(PNVO_ERR_STATE, "policy visual encoder kept no hidden vector");
+  hipLaunchKernelGGL(rollout_inputs_kernel, dim3((unsigned)(((long)M * K0 + 255) / 256)), dim3(256), 0, s, visual, goal, prev_actions,
+                     t->masks, p.tgt_w, p.tgt_b, p.emb, A + 1, M, Hd, t->x0, t->rows, t->g3);
+  const float *xin = t->x0;
+  int K = K0;
+  for (int l = 0; l < L; ++l) {
+    GemmArgs g{xin, p.w_ih[l], p.b_ih[l], p.b_hh[l], t->gates[l], M, 4 * Hd, K, (long)K, 1, 1, (long)K, 4L * Hd};
+    PCHK((launch_gemm<true, true>(g, s)));
+    for (int ts = 0; ts < T; ++ts) {
+      const size_t r = (size_t)ts * N;
+      const float *h_prev = ts ? t->y[l] + (r - N) * Hd : t->hid0 + (size_t)l * N * Hd;
+      const float *c_prev = ts ? t->c[l] + (r - N) * Hd : t->hid0 + (size_t)(L + l) * N * Hd;
+      const bool last = ts == T - 1;
+      hipLaunchKernelGGL(lstm_step_kernel, dim3((unsigned)Hd), dim3(256), 0, s, t->gates[l] + r * 4 * Hd, h_prev, c_prev, p.w_hh[l],
+                         t->masks + r, N, Hd, t->y[l] + r * Hd, t->c[l] + r * Hd, t->hm[l] + r * Hd,
+                         last ? hidden_out + (size_t)l * N * Hd : nullptr, last ? hidden_out + (size_t)(L + l) * N * Hd : nullptr);
+    }
+    xin = t->y[l];
+    K = Hd;
+  }
+  hipLaunchKernelGGL(heads_eval_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, t->y[L - 1], p.act_w, p.act_b, p.cr_w, p.cr_b,
+                     t->actions, M, Hd, A, t->logits, t->value, t->logp, t->ent);
+  if (value) PCHK(hipMemcpyAsync(value, t->value, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (logp) PCHK(hipMemcpyAsync(logp, t->logp, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (entropy) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, t->ent, M, entropy);
+  PCHK(hipGetLastError());
+  PCHK(mark(t, 2, s));
+  return PNVO_OK;
+}
+
+int pnvo_policy_ppo_loss(pnvo_policy_handle h, const float *actions_logp_old, const float *adv, const float *value_preds,
+                         const float *returns, float clip, float value_coef, float entropy_coef, int use_clipped_value_loss, float *out3,
+                         void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  if (t->M <= 0) return pfail(PNVO_ERR_STATE, "pnvo_policy_ppo_loss before pnvo_policy_evaluate");
+  if (!actions_logp_old || !adv || !returns || !out3 || (use_clipped_value_loss && !value_preds)) return pfail(PNVO_ERR_ARG, "null argument");
+  if (!(clip >= 0.f)) return pfail(PNVO_ERR_ARG, "clip_param " + std::to_string(clip) + " must be >= 0");
+  PCHK(hipSetDevice(p.device));
+  PCHK(mark(t, 3, (hipStream_t)stream));
+  hipLaunchKernelGGL(ppo_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, t->logits, t->value, t->logp, t->ent, t->actions,
+                     actions_logp_old, adv, value_preds, returns, t->M, p.cfg.n_actions, clip, value_coef, entropy_coef,
+                     use_clipped_value_loss ? 1 : 0, out3, t->dlogits, t->dvalue);
+  PCHK(hipGetLastError());
+  PCHK(mark(t, 4, (hipStream_t)stream));
+  t->have_loss = true;
+  return PNVO_OK;
+}
+
+int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  if (t->M <= 0 || !t->have_loss) return pfail(PNVO_ERR_STATE, "pnvo_policy_backward before pnvo_policy_evaluate + pnvo_policy_ppo_loss");
+  PCHK(hipSetDevice(p.device));
+  hipStream_t s = (hipStream_t)stream;
+  const pnvo_policy_config &c = p.cfg;
+  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = t->M, T = t->T, N = t->N;
+  float *G = t->grads;
+  PCHK(mark(t, 5, s));
+  PCHK(hipMemsetAsync(G, 0, t->n * sizeof(float), s));                 // overwrite semantics; a frozen encoder's range stays zero
+  const float *feat = t->y[L - 1];
+  hipLaunchKernelGGL(heads_bwd_w_kernel, dim3((unsigned)(((long)(A + 1) * Hd + 255) / 256)), dim3(256), 0, s, feat, t->dlogits, t->dvalue, M,
+                     Hd, A, G + t->o_act_w, G + t->o_act_b, G + t->o_cr_w, G + t->o_cr_b);
+  hipLaunchKernelGGL(heads_bwd_x_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, t->dlogits, t->dvalue, p.act_w,
+                     p.cr_w, M, Hd, A, t->dY);
+  for (int l = L - 1; l >= 0; --l) {
+    const int K = l == 0 ? K0 : Hd;
+    const float *X = l == 0 ? t->x0 : t->y[l - 1];
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((Hd + 31) / 32), (unsigned)((4 * Hd + 31) / 32)), dim3(256), 0, s, p.w_hh[l], 4 * Hd,
+                       Hd, t->whhT);
+    for (int ts = T - 1; ts >= 0; --ts) {
+      const size_t r = (size_t)ts * N, rn = r + N;
+      const bool last = ts == T - 1;
+      const float *c_prev = ts ? t->c[l] + (r - N) * Hd : t->hid0 + (size_t)(L + l) * N * Hd;
+      hipLaunchKernelGGL(bptt_step_kernel, dim3((unsigned)Hd), dim3(256), 0, s, t->gates[l] + r * 4 * Hd,
+                         last ? nullptr : t->gates[l] + rn * 4 * Hd, last ? nullptr : t->dG + rn * 4 * Hd, last ? nullptr : t->dC + rn * Hd,
+                         last ? nullptr : t->masks + rn, t->c[l] + r * Hd, c_prev, t->masks + r, t->whhT, t->dY + r * Hd, N, Hd,
+                         t->dG + r * 4 * Hd, t->dC + r * Hd);
+    }
+    // dW_ih = dG^T . X,  dW_hh = dG^T . (h_prev * mask),  db_ih = db_hh = colsum(dG),  dX = dG . W_ih
+    GemmArgs wi{t->dG, X, nullptr, nullptr, G + t->o_wih[l], 4 * Hd, K, M, 1, 4L * Hd, (long)K, 1, (long)K};
+    PCHK((launch_gemm<false, false>(wi, s)));
+    GemmArgs wh{t->dG, t->hm[l], nullptr, nullptr, G + t->o_whh[l], 4 * Hd, Hd, M, 1, 4L * Hd, (long)Hd, 1, (long)Hd};
+    PCHK((launch_gemm<false, false>(wh, s)));
+    PCHK(launch_colsum(t->dG, M, 4 * Hd, 4 * Hd, G + t->o_bih[l], s));
+    PCHK(hipMemcpyAsync(G + t->o_bhh[l], G + t->o_bih[l], (size_t)4 * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+    GemmArgs dx{t->dG, p.w_ih[l], nullptr, nullptr, l == 0 ? t->dX0 : t->dY, M, K, 4 * Hd, 4L * Hd, 1, (long)K, 1, (long)K};
+    PCHK((launch_gemm<true, false>(dx, s)));
+  }
+  // embeddings; d visual -> dY (contiguous [M, hidden]) -> the encoder's backward below its output head
+  hipLaunchKernelGGL(inputs_bwd_kernel, dim3((unsigned)(((long)M * Hd + 128 + (long)(A + 1) * 32 + 255) / 256)), dim3(256), 0, s, t->dX0,
+                     t->rows, t->g3, M, Hd, A + 1, G + t->o_tgt_w, G + t->o_tgt_b, G + t->o_emb, t->dY);
+  PCHK(hipGetLastError());
+  PCHK(mark(t, 6, s));
+  const int rc = pnvo_train_backward_from_hidden(p.enc, t->dY, train_encoder == 0, stream);
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  if (train_encoder) {
+    hipLaunchKernelGGL(stem_unpad_kernel, dim3((unsigned)((t->c0 * 49 + 255) / 256)), dim3(256), 0, s, G + t->o_stem2, t->c0, G + t->o_stem);
+    PCHK(hipGetLastError());
+  }
+  PCHK(mark(t, 7, s));
+  return PNVO_OK;
+}
+
+int pnvo_policy_train_timing(pnvo_policy_handle h, int mode) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  PolicyTrain *t = h->p.train;
+  PCHK(hipSetDevice(h->p.device));
+  if (mode)
+    for (hipEvent_t &e : t->ev)
+      if (!e) PCHK(hipEventCreate(&e));
+  t->timing = mode != 0;
+  return PNVO_OK;
+}
+
+int pnvo_policy_train_timing_read(pnvo_policy_handle h, double ms[5]) {
+  if (!h || !h->p.train || !ms) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  PolicyTrain *t = h->p.train;
+  if (!t->timing) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_timing(h, 1) first");
+  PCHK(hipEventSynchronize(t->ev[7]));
+  const int pairs[5][2] = {{0, 1}, {1, 2}, {3, 4}, {5, 6}, {6, 7}};
+  for (int k = 0; k < 5; ++k) {
+    float f = 0.f;
+    PCHK(hipEventElapsedTime(&f, t->ev[pairs[k][0]], t->ev[pairs[k][1]]));
+    ms[k] = (double)f;
+  }
+  return PNVO_OK;
+}
+
+int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm_out, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  if (!(max_norm > 0.f)) return pfail(PNVO_ERR_ARG, "max_grad_norm " + std::to_string(max_norm) + " must be > 0");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  PCHK(hipSetDevice(p.device));
+  const long n = (long)t->n_named;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, t->sq_part);
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, t->sq_part, max_norm, norm_out);
+  PCHK(hipGetLastError());
+  return PNVO_OK;
+}
+
+}  // extern "C"

@@ -6,7 +6,8 @@ the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only 
 ``state_dict`` keys/shapes, same ``act`` / ``get_value`` signatures and return values (policy.py:29-50).  The module tree
 only HOLDS parameters; ``act`` is one call into libpnvo.so (pnvo_policy_act) on the caller's current HIP stream plus the
 categorical sampling / arg-max over the 4 logits, which stays in torch as in the reference (policy.py:38-43).
-``evaluate_actions`` (PPO training of the policy) is not built.  No CPU fallback.
+``evaluate_actions`` (PPO training of the policy) exists once a ``ppo.PolicyTrainStep`` has been attached to the policy (ppo.py: the
+rollout forward, back-propagation through time and Adam on one flat buffer); a plain policy raises NotImplementedError.  No CPU fallback.
 """
 import ctypes as C
 import math
@@ -155,6 +156,7 @@ class PointNavResNetPolicy(nn.Module):
         self._handle = None
         self._handle_dev = None
         self._loaded_sig = None
+        self._train_step = None                            # ppo.PolicyTrainStep once attached: the weights then live in its flat buffer
 
     @property
     def num_recurrent_layers(self):
@@ -166,6 +168,11 @@ class PointNavResNetPolicy(nn.Module):
 
     # ------------------------------------------------------------------ libpnvo plumbing
     def _ensure(self, device):
+        if self._train_step is not None:                    # the library reads the train step's flat buffer: nothing to upload
+            if self._handle_dev != device.index:
+                raise RuntimeError("the policy moved to another device after a PolicyTrainStep was attached")
+            self._train_step._sync_params()
+            return
         if self._handle is None or self._handle_dev != device.index:
             self._release()
             cc = pnvo_policy_config(width=self._W, height=self._H, baseplanes=self._baseplanes, hidden=self._hidden,
@@ -281,5 +288,10 @@ class PointNavResNetPolicy(nn.Module):
         with torch.no_grad():
             return self._net(observations, rnn_hidden_states, prev_actions, masks)
 
-    def evaluate_actions(self, *a, **k):
-        raise NotImplementedError("PPO training of the policy (policy.py:52-63) is outside the built path")
+    def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
+        """-> (value [M,1], action_log_probs [M,1], distribution_entropy, rnn_hidden_states)  (policy.py:52-63), for a policy with a
+        ppo.PolicyTrainStep attached; gradients come from that step's backward(), not from autograd."""
+        if self._train_step is None:
+            raise NotImplementedError("PPO training of the policy (policy.py:52-63) is outside the built path "
+                                      "(attach a train step first: pointnav_vo_amd.ppo.PolicyTrainStep(policy) or ppo.PPO(policy, ...))")
+        return self._train_step.evaluate_actions(observations, rnn_hidden_states, prev_actions, masks, action)

@@ -1,0 +1,330 @@
+"""PPO update of the HIP navigation policy: the reference's `PPO` agent (pointnav_vo/rl/ppo/ppo.py) on libpnvo.so.
+
+The reference tunes the policy against the VO estimates with this update (configs/rl/ddppo_pointnav.yaml: TUNE_WITH_VO, train_encoder,
+num_steps 128, num_mini_batch 2, 2-layer LSTM).  `PolicyTrainStep` is to the policy what `VOTrainStep` (train.py) is to a VO model:
+it owns ONE flat parameter buffer and ONE flat gradient buffer on the device, makes the module's parameters views of them, and
+drives the C ABI —
+
+    pnvo_policy_evaluate     rollout forward (encoder in train mode, LSTM over T x N with mask resets), activations kept
+    pnvo_policy_ppo_loss     clipped surrogate / value loss / entropy and their gradient at the heads, from a kernel
+    pnvo_policy_backward     heads, back-propagation through time, embeddings, the encoder's backward
+    pnvo_policy_clip_grad_norm, pnvo_adam_step, pnvo_policy_train_refresh
+
+— with no torch autograd anywhere.  `PPO` keeps the reference agent's constructor and `update(rollouts)` contract, so a trainer's
+`self.agent.update(rollouts)` works; the loop over `rollouts.recurrent_generator` stays in Python and the loss sums stay on the device
+until the end (one synchronisation per update).  The gradient is one flat buffer: a data-parallel all-reduce is one call
+(parallel.allreduce_mean_(step.grad)) between `backward()` and `optimizer_step()`.
+
+Not here: the DD-PPO reducer and pre-emption logic, RolloutStorage, an autograd bridge for the reference's own PPO.update, GRU and
+non-resnet18 backbones.  No CPU fallback.
+"""
+import ctypes as C
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .policy import GOAL_SENSOR
+
+EPS_PPO = 1e-5
+ENCODER_PREFIX = "net.visual_encoder."
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def flat_offsets(spec):
+    """Layout of the flat buffers: (name, shape) in named_parameters() order -> ({name: (offset, numel)}, floats used).  Every tensor
+    starts at a multiple of 4 floats (the kernels read weight rows as 16-byte vectors); the gaps hold zeros."""
+    offsets, off = {}, 0
+    for name, shape in spec:
+        n = 1
+        for s in shape:
+            n *= int(s)
+        offsets[name] = (off, n)
+        off = (off + n + 3) // 4 * 4
+    return offsets, off
+
+
+class _AdamView:
+    """What a trainer reads of `agent.optimizer`: param_groups[0]['lr'] (read at every step), state_dict / load_state_dict."""
+
+    def __init__(self, step):
+        self._step = step
+        self.param_groups = [{"lr": step.lr, "eps": step.eps, "betas": tuple(step.betas), "weight_decay": 0, "amsgrad": False}]
+
+    def state_dict(self):
+        return self._step.state_dict()
+
+    def load_state_dict(self, sd):
+        self._step.load_state_dict(sd)
+        self.param_groups[0].update(lr=self._step.lr, eps=self._step.eps, betas=tuple(self._step.betas))
+
+    def zero_grad(self, set_to_none=False):
+        pass                                               # pnvo_policy_backward overwrites the gradient buffer
+
+
+class PolicyTrainStep:
+    def __init__(self, policy, lr=2.5e-4, eps=1e-5, max_grad_norm=0.5, train_encoder=True, betas=(0.9, 0.999)):
+        self.policy = policy
+        self.lr, self.eps, self.betas = float(lr), float(eps), tuple(betas)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.train_encoder = bool(train_encoder)
+        ref = next(policy.parameters())
+        if ref.device.type != "cuda":
+            raise RuntimeError("PolicyTrainStep runs on an MI355X only: move the policy with .to('cuda') first "
+                               "(there is no CPU fallback)")
+        self.dev = ref.device
+        policy._ensure(self.dev)                                # handle + kernel operand buffers
+        h = policy._handle
+        named = [(n, p) for n, p in policy.named_parameters()]
+        self.offsets, used = flat_offsets([(n, tuple(p.shape)) for n, p in named])
+        tail = int(_lib.lib.pnvo_policy_train_tail_floats(h))
+        self.n_params = used
+        self.flat = torch.zeros(used + tail, device=self.dev, dtype=torch.float32)
+        self.grad = torch.zeros(used + tail, device=self.dev, dtype=torch.float32)
+        self.exp_avg = torch.zeros(used, device=self.dev, dtype=torch.float32)
+        self.exp_avg_sq = torch.zeros(used, device=self.dev, dtype=torch.float32)
+        toc = (_lib.pnvo_tensor_desc * len(named))()
+        with torch.no_grad():
+            for i, (n, p) in enumerate(named):
+                off, k = self.offsets[n]
+                self.flat[off:off + k].copy_(p.detach().reshape(-1))
+                p.data = self.flat[off:off + k].view(p.shape)    # the module's parameters alias the flat buffer
+                p.grad = self.grad[off:off + k].view(p.shape)
+                toc[i].name = n.encode()
+                toc[i].offset = off
+                toc[i].ndim = p.dim()
+                for d, sz in enumerate(p.shape):
+                    toc[i].shape[d] = int(sz)
+        self._toc, self._named = toc, named
+        enc = [self.offsets[n] for n, _ in named if n.startswith(ENCODER_PREFIX)]
+        self.encoder_range = (min(o for o, _ in enc), max(o + k for o, k in enc))
+        torch.cuda.synchronize(self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_policy_train_attach(h, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), toc, len(named)))
+        self.step_count = 0
+        self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
+        self._norm = torch.zeros(1, device=self.dev, dtype=torch.float32)
+        self._psig = self._param_sig()
+        policy._train_step = self                               # evaluate_actions delegates here; act reads the flat buffer
+
+    # ------------------------------------------------------------------ parameter / optimizer state
+    def _trainable(self):
+        return [(n, p) for n, p in self._named if self.train_encoder or not n.startswith(ENCODER_PREFIX)]
+
+    def _ranges(self):
+        """Flat ranges the optimiser steps over: everything, or everything but net.visual_encoder (the reference's _static_encoder)."""
+        if self.train_encoder:
+            return [(0, self.n_params)]
+        lo, hi = self.encoder_range
+        return [(a, b) for a, b in ((0, lo), (hi, self.n_params)) if b > a]
+
+    def _param_sig(self):
+        return tuple((p.data_ptr(), p._version) for _, p in self._named)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _sync_params(self):
+        """Parameters edited outside the HIP Adam step (load_state_dict on resume, an in-place torch edit) land in the flat buffer but
+        not in the encoder's packed operands: re-alias what was re-pointed and re-pack (as VOTrainStep._sync_params)."""
+        sig = self._param_sig()
+        if sig == self._psig:
+            return
+        with torch.no_grad():
+            for n, p in self._named:
+                off, k = self.offsets[n]
+                view = self.flat[off:off + k].view(p.shape)
+                if p.data_ptr() != view.data_ptr():
+                    view.copy_(p.detach())
+                    p.data = view
+                    p.grad = self.grad[off:off + k].view(p.shape)
+        with torch.cuda.device(self.dev):
+            for _ in range(3):          # the encoder's GroupNorm range guard reads the bounds two refreshes back (train.py)
+                _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, self._stream()))
+        torch.cuda.current_stream(self.dev).synchronize()
+        self._psig = self._param_sig()
+
+    def state_dict(self):
+        """Optimizer state in torch.optim.Adam's layout over the trainable parameters, in order (what the reference's
+        optim.Adam(filter(requires_grad, actor_critic.parameters())) checkpoints)."""
+        state = {}
+        for i, (n, p) in enumerate(self._trainable()):
+            off, k = self.offsets[n]
+            state[i] = {"step": torch.tensor(float(self.step_count)),
+                        "exp_avg": self.exp_avg[off:off + k].view(p.shape).clone(),
+                        "exp_avg_sq": self.exp_avg_sq[off:off + k].view(p.shape).clone()}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
+                 "params": list(range(len(state)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        group = sd["param_groups"][0]
+        self.lr, self.eps, self.betas = float(group["lr"]), float(group["eps"]), tuple(group["betas"])
+        steps = set()
+        with torch.no_grad():
+            for i, (n, p) in enumerate(self._trainable()):
+                off, k = self.offsets[n]
+                st = sd["state"].get(i)
+                if st is None:
+                    self.exp_avg[off:off + k].zero_()
+                    self.exp_avg_sq[off:off + k].zero_()
+                else:
+                    self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
+                    self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+                    steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise ValueError("per-parameter Adam step counts differ; the HIP Adam keeps one step count for the policy")
+        self.step_count = steps.pop() if steps else 0
+
+    # ------------------------------------------------------------------ the update, piece by piece
+    def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
+        """-> (value [M,1], action_log_probs [M,1], distribution_entropy (scalar), rnn_hidden_states) as Policy.evaluate_actions
+        (policy.py:52-63).  Rows are T-major (row t*N + n); N = rnn_hidden_states.shape[1], T = M / N (T = 1: single_forward)."""
+        pol, dev = self.policy, self.dev
+        self._sync_params()
+        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
+        if pol._obs_transform is not None:
+            depth = pol._transform_depth(depth, dev)
+        M = depth.shape[0]
+        if tuple(depth.shape[1:]) != (pol._H, pol._W, 1):
+            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [M,{pol._H},{pol._W},1]")
+        hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
+        N = hin.shape[1]
+        if tuple(hin.shape) != (2 * pol._layers, N, pol._hidden) or N <= 0 or M % N != 0:
+            raise ValueError(f"rnn_hidden_states {tuple(hin.shape)} does not fit {M} rows: expected [{2 * pol._layers}, N, {pol._hidden}] "
+                             "with N dividing the number of rows")
+        T = M // N
+        goal = observations[GOAL_SENSOR].to(device=dev, dtype=torch.float32).contiguous().reshape(M, 2)
+        pa = prev_actions.to(device=dev, dtype=torch.int64).contiguous().reshape(M)
+        mk = masks.to(device=dev, dtype=torch.float32).contiguous().reshape(M)
+        act = action.to(device=dev, dtype=torch.int64).contiguous().reshape(M)
+        hout = torch.empty_like(hin)
+        value = torch.empty((M, 1), device=dev, dtype=torch.float32)
+        logp = torch.empty((M, 1), device=dev, dtype=torch.float32)
+        entropy = torch.empty((), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.pnvo_policy_evaluate(pol._handle, _ptr(depth), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T), int(N),
+                                                     _ptr(act), int(self.train_encoder), _ptr(hout), _ptr(value), _ptr(logp),
+                                                     _ptr(entropy), self._stream()))
+        return value, logp, entropy, hout
+
+    def ppo_loss(self, old_action_log_probs, adv_targ, value_preds, returns, clip_param, value_loss_coef, entropy_coef,
+                 use_clipped_value_loss=True):
+        """The minibatch loss of rl/ppo/ppo.py:101-126 for the last evaluate_actions -> device tensor [3] = (value_loss, action_loss,
+        dist_entropy); its gradient at the heads stays in the handle for backward().  The tensor is reused by the next call."""
+        f = lambda t: None if t is None else t.to(device=self.dev, dtype=torch.float32).contiguous().reshape(-1)
+        old, adv, vp, ret = f(old_action_log_probs), f(adv_targ), f(value_preds), f(returns)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_policy_ppo_loss(self.policy._handle, _ptr(old), _ptr(adv), _ptr(vp), _ptr(ret), float(clip_param),
+                                                     float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
+                                                     _ptr(self._out3), self._stream()))
+        return self._out3
+
+    def backward(self):
+        """total_loss.backward(): fills self.grad (overwrites)."""
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_policy_backward(self.policy._handle, int(self.train_encoder), self._stream()))
+
+    def clip_grad_norm(self):
+        """nn.utils.clip_grad_norm_(parameters, max_grad_norm) on the device -> the norm as a device tensor [1] (no host sync)."""
+        if self.max_grad_norm is None:
+            return None
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_policy_clip_grad_norm(self.policy._handle, float(self.max_grad_norm), _ptr(self._norm),
+                                                           self._stream()))
+        return self._norm
+
+    def timing(self, on=True):
+        """Record HIP events at the phase boundaries of the update (tools/bench_ppo_update.py)."""
+        _lib.check(_lib.lib.pnvo_policy_train_timing(self.policy._handle, int(bool(on))))
+
+    def phase_ms(self):
+        """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, LSTM forward +
+        heads, loss, heads + BPTT + embedding backward, encoder backward."""
+        ms = (C.c_double * 5)()
+        _lib.check(_lib.lib.pnvo_policy_train_timing_read(self.policy._handle, ms))
+        return dict(zip(("encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward"), (float(v) for v in ms)))
+
+    def optimizer_step(self):
+        """Adam over the trainable ranges, then the encoder's operands are re-packed from the flat buffer."""
+        self.step_count += 1
+        with torch.cuda.device(self.dev):
+            stream = self._stream()
+            for a, b in self._ranges():
+                _lib.check(_lib.lib.pnvo_adam_step(C.c_void_p(self.flat.data_ptr() + 4 * a), C.c_void_p(self.grad.data_ptr() + 4 * a),
+                                                   C.c_void_p(self.exp_avg.data_ptr() + 4 * a),
+                                                   C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * a), b - a, self.lr, self.betas[0],
+                                                   self.betas[1], self.eps, self.step_count, stream))
+            _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, stream))
+
+
+class PPO(nn.Module):
+    """The reference agent's contract (rl/ppo/ppo.py): same constructor keywords, get_advantages, update -> three floats."""
+
+    def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
+                 max_grad_norm=None, use_clipped_value_loss=True, use_normalized_advantage=True):
+        super().__init__()
+        self.actor_critic = actor_critic
+        self.clip_param = clip_param
+        self.ppo_epoch = ppo_epoch
+        self.num_mini_batch = num_mini_batch
+        self.value_loss_coef = value_loss_coef
+        self.entropy_coef = entropy_coef
+        self.max_grad_norm = max_grad_norm
+        self.use_clipped_value_loss = use_clipped_value_loss
+        self.use_normalized_advantage = use_normalized_advantage
+        # the reference's optimiser takes the parameters with requires_grad: a trainer freezes net.visual_encoder before it builds the agent
+        train_encoder = any(p.requires_grad for n, p in actor_critic.named_parameters() if n.startswith(ENCODER_PREFIX))
+        kw = {}
+        if lr is not None:
+            kw["lr"] = lr
+        if eps is not None:
+            kw["eps"] = eps
+        self.train_step = PolicyTrainStep(actor_critic, max_grad_norm=max_grad_norm, train_encoder=train_encoder, **kw)
+        self.optimizer = _AdamView(self.train_step)
+        self.device = next(actor_critic.parameters()).device
+
+    def forward(self, *x):
+        raise NotImplementedError
+
+    def get_advantages(self, rollouts):
+        advantages = rollouts.returns[:-1] - rollouts.value_preds[:-1]
+        if not self.use_normalized_advantage:
+            return advantages
+        return (advantages - advantages.mean()) / (advantages.std() + EPS_PPO)
+
+    def update(self, rollouts):
+        advantages = self.get_advantages(rollouts)
+        step = self.train_step
+        sums = torch.zeros(3, device=self.device, dtype=torch.float32)
+        for _ in range(self.ppo_epoch):
+            for sample in rollouts.recurrent_generator(advantages, self.num_mini_batch):
+                (obs_batch, recurrent_hidden_states_batch, actions_batch, prev_actions_batch, value_preds_batch, return_batch,
+                 masks_batch, old_action_log_probs_batch, adv_targ) = sample
+                step.evaluate_actions(obs_batch, recurrent_hidden_states_batch, prev_actions_batch, masks_batch, actions_batch)
+                sums += step.ppo_loss(old_action_log_probs_batch, adv_targ, value_preds_batch, return_batch, self.clip_param,
+                                      self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
+                self.before_backward(None)
+                step.backward()
+                self.after_backward(None)
+                self.before_step()
+                step.lr = float(self.optimizer.param_groups[0]["lr"])
+                step.optimizer_step()
+                self.after_step()
+        value_loss, action_loss, dist_entropy = (sums / (self.ppo_epoch * self.num_mini_batch)).tolist()   # the one synchronisation
+        return value_loss, action_loss, dist_entropy
+
+    def before_backward(self, loss):
+        pass
+
+    def after_backward(self, loss):
+        pass
+
+    def before_step(self):
+        self.train_step.clip_grad_norm()
+
+    def after_step(self):
+        pass

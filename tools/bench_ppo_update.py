@@ -1,0 +1,261 @@
+#!/usr/bin/env python3
+"""One PPO minibatch update of the navigation policy at the reference's shape, per phase, on the MI355X.
+
+    python tools/bench_ppo_update.py [--n 2 4] [--steps 128] [--iters 12] [--warmup 3] [--out profiles/ppo_update.md] [--no-eager]
+
+Shape: configs/rl/ddppo_pointnav.yaml — num_steps T = 128, N environments per minibatch, 341 x 192 depth, hidden 512, 2-layer LSTM,
+train_encoder.  The HIP path (pointnav_vo_amd.ppo.PolicyTrainStep) is timed per phase with HIP events recorded inside the library
+(pnvo_policy_train_timing: encoder forward, LSTM forward + heads, loss, heads + BPTT + embeddings backward, encoder backward) and
+with torch events around clip + Adam + refresh and around the whole update; medians over --iters after --warmup.
+
+Beside it, in the same run on the same GPU: the same update in plain torch eager ops with autograd (an nn.Module restatement of the
+policy with random weights: GroupNorm-ResNet18 encoder, nn.LSTM run over the segments between episode starts as the reference's
+RNNStateEncoder does, Categorical heads, the PPO loss, clip_grad_norm_, torch.optim.Adam).  It is the only comparison there is: the
+project could not do this update at all before.  No threshold: the record says which side wins, phase by phase.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, HIDDEN, LAYERS, ACTIONS = 192, 341, 512, 2, 4
+CLIP, VALUE_COEF, ENTROPY_COEF, LR, EPS, MAX_GRAD_NORM = 0.2, 0.5, 0.01, 2.5e-4, 1e-5, 0.2
+GOAL = "pointgoal_with_gps_compass"
+
+
+def make_batch(T, N, dev, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    M = T * N
+    masks = torch.ones(T, N)
+    masks[0] = 0                                            # every rollout starts an episode ...
+    for n in range(N):                                      # ... and each environment resets once more somewhere inside
+        masks[int(torch.randint(8, T - 8, (1,), generator=g)), n] = 0
+    b = dict(depth=torch.rand(M, H, W, 1, generator=g), goal=torch.rand(M, 2, generator=g) * 3,
+             prev=torch.randint(0, ACTIONS, (M, 1), generator=g), masks=masks.reshape(M, 1),
+             actions=torch.randint(0, ACTIONS, (M, 1), generator=g), hidden=torch.rand(2 * LAYERS, N, HIDDEN, generator=g) - 0.5,
+             old=-1.386 + 0.2 * torch.randn(M, 1, generator=g), adv=torch.randn(M, 1, generator=g),
+             vp=torch.randn(M, 1, generator=g) * 0.3)
+    b["ret"] = b["vp"] + b["adv"]
+    return {k: v.to(dev) for k, v in b.items()}
+
+
+class Timer:
+    def __init__(self):
+        self.t = {}
+
+    def span(self, name):
+        timer = self
+
+        class _S:
+            def __enter__(s):
+                s.a, s.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.a.record()
+
+            def __exit__(s, *exc):
+                s.b.record()
+                timer.t.setdefault(name, []).append((s.a, s.b))
+        return _S()
+
+    def medians(self, skip):
+        torch.cuda.synchronize()
+        return {k: statistics.median([a.elapsed_time(b) for a, b in v][skip:]) for k, v in self.t.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------- HIP path
+def bench_hip(T, N, iters, warmup, dev):
+    from pointnav_vo_amd.policy import PointNavResNetPolicy
+    from pointnav_vo_amd.ppo import PolicyTrainStep
+
+    class Box:
+        def __init__(self, shape):
+            self.shape = shape
+
+    class Space:
+        def __init__(self, d):
+            self.spaces = d
+
+    class Act:
+        n = ACTIONS
+
+    torch.manual_seed(0)
+    pol = PointNavResNetPolicy(observation_space=Space({"depth": Box((H, W, 1)), GOAL: Box((2,))}), action_space=Act(),
+                               hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type="LSTM", backbone="resnet18",
+                               normalize_visual_inputs=False, obs_transform=None, vis_types=["depth"]).to(dev)
+    step = PolicyTrainStep(pol, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM)
+    step.timing(True)
+    b = make_batch(T, N, dev)
+    obs = {"depth": b["depth"], GOAL: b["goal"]}
+    tm, phases = Timer(), []
+    for _ in range(warmup + iters):
+        with tm.span("whole update"):
+            step.evaluate_actions(obs, b["hidden"], b["prev"], b["masks"], b["actions"])
+            step.ppo_loss(b["old"], b["adv"], b["vp"], b["ret"], CLIP, VALUE_COEF, ENTROPY_COEF, True)
+            step.backward()
+            with tm.span("clip + Adam + refresh"):
+                step.clip_grad_norm()
+                step.optimizer_step()
+        phases.append(step.phase_ms())
+    out = {k: statistics.median([p[k] for p in phases[warmup:]]) for k in phases[0]}
+    out.update(tm.medians(warmup))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- eager torch
+def gn_conv(cin, cout, k, stride, groups):
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, k // 2, bias=False), nn.GroupNorm(groups, cout))
+
+
+class Block(nn.Module):
+    def __init__(self, cin, cout, stride, groups):
+        super().__init__()
+        self.a, self.b = gn_conv(cin, cout, 3, stride, groups), gn_conv(cout, cout, 3, 1, groups)
+        self.ds = gn_conv(cin, cout, 1, stride, groups) if (stride != 1 or cin != cout) else None
+
+    def forward(self, x):
+        r = x if self.ds is None else self.ds(x)
+        return F.relu(self.b(F.relu(self.a(x))) + r)
+
+
+class EagerPolicy(nn.Module):
+    """The depth-only resnet18 + LSTM policy (baseplanes 32, GroupNorm of baseplanes / 2 groups, 2048-float compression)."""
+
+    def __init__(self):
+        super().__init__()
+        bp, g = 32, 16
+        self.stem = gn_conv(1, bp, 7, 2, g)
+        blocks, cin = [], bp
+        for li in range(4):
+            for bi in range(2):
+                cout = bp << li
+                blocks.append(Block(cin, cout, 2 if (li > 0 and bi == 0) else 1, g))
+                cin = cout
+        self.blocks = nn.Sequential(*blocks)
+        h, w = H // 2, W // 2
+        for _ in range(5):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        comp = int(round(2048 / (h * w)))
+        self.comp = nn.Sequential(nn.Conv2d(cin, comp, 3, 1, 1, bias=False), nn.GroupNorm(1, comp))
+        self.fc = nn.Linear(comp * h * w, HIDDEN)
+        self.tgt = nn.Linear(3, 32)
+        self.emb = nn.Embedding(ACTIONS + 1, 32)
+        self.rnn = nn.LSTM(HIDDEN + 64, HIDDEN, LAYERS)
+        self.actor, self.critic = nn.Linear(HIDDEN, ACTIONS), nn.Linear(HIDDEN, 1)
+
+    def encode(self, depth):
+        x = F.avg_pool2d(depth.permute(0, 3, 1, 2), 2)
+        x = F.max_pool2d(F.relu(self.stem(x)), 3, 2, 1)
+        x = F.relu(self.comp(self.blocks(x)))
+        return F.relu(self.fc(x.flatten(1)))
+
+    def recur(self, visual, b, T, N):
+        goal, masks = b["goal"], b["masks"].view(T, N)
+        g3 = torch.stack([goal[:, 0], torch.cos(-goal[:, 1]), torch.sin(-goal[:, 1])], -1)
+        idx = ((b["prev"].float() + 1) * b["masks"]).long().squeeze(-1)
+        x = torch.cat([visual, self.tgt(g3), self.emb(idx)], 1).view(T, N, -1)
+        h, c = b["hidden"][:LAYERS], b["hidden"][LAYERS:]
+        starts = sorted(set([0] + (masks == 0).any(1).nonzero().flatten().tolist() + [T]))   # segments between episode starts
+        outs = []
+        for s, e in zip(starts[:-1], starts[1:]):
+            m = masks[s].view(1, N, 1)
+            o, (h, c) = self.rnn(x[s:e], (h * m, c * m))
+            outs.append(o)
+        feat = torch.cat(outs).view(T * N, -1)
+        dist = torch.distributions.Categorical(logits=self.actor(feat))
+        return self.critic(feat), dist.log_prob(b["actions"].squeeze(-1)).unsqueeze(-1), dist.entropy().mean()
+
+
+def bench_eager(T, N, iters, warmup, dev):
+    torch.manual_seed(0)
+    pol = EagerPolicy().to(dev)
+    opt = torch.optim.Adam(pol.parameters(), lr=LR, eps=EPS)
+    b = make_batch(T, N, dev)
+    tm = Timer()
+    for _ in range(warmup + iters):
+        with tm.span("whole update"):
+            with tm.span("encoder_forward"):
+                visual = pol.encode(b["depth"])
+            vis = visual.detach().requires_grad_(True)
+            with tm.span("lstm_forward"):
+                value, logp, entropy = pol.recur(vis, b, T, N)
+            with tm.span("loss"):
+                ratio = torch.exp(logp - b["old"])
+                action_loss = -torch.min(ratio * b["adv"], torch.clamp(ratio, 1 - CLIP, 1 + CLIP) * b["adv"]).mean()
+                vclip = b["vp"] + (value - b["vp"]).clamp(-CLIP, CLIP)
+                value_loss = 0.5 * torch.max((value - b["ret"]).pow(2), (vclip - b["ret"]).pow(2)).mean()
+                total = value_loss * VALUE_COEF + action_loss - entropy * ENTROPY_COEF
+            opt.zero_grad()
+            with tm.span("bptt"):
+                total.backward()
+            with tm.span("encoder_backward"):
+                visual.backward(vis.grad)
+            with tm.span("clip + Adam + refresh"):
+                nn.utils.clip_grad_norm_(pol.parameters(), MAX_GRAD_NORM)
+                opt.step()
+    return tm.medians(warmup)
+
+
+ORDER = ["encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward", "clip + Adam + refresh", "whole update"]
+LABEL = {"encoder_forward": "encoder forward", "lstm_forward": "LSTM forward + heads", "loss": "loss",
+         "bptt": "heads + BPTT + embeddings backward", "encoder_backward": "encoder backward",
+         "clip + Adam + refresh": "clip + Adam (+ operand refresh)", "whole update": "whole update (host-timed, events)"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[2, 4])
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-eager", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_ppo_update.py measures on an MI355X: no GPU here, nothing measured")
+    if a.iters < 10:
+        raise SystemExit("--iters must be at least 10 (median of >= 10 timed iterations)")
+    dev = torch.device("cuda", 0)
+    lines = ["# PPO minibatch update of the navigation policy: HIP path vs torch eager", "",
+             f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer LSTM, 4 actions, train_encoder; "
+             f"median of {a.iters} iterations after {a.warmup} warm-up, HIP events, one process, {torch.cuda.get_device_name(0)}.",
+             "The eager column is the same update in torch-ROCm eager ops with autograd (nn.LSTM over the segments between episode "
+             "starts, as the reference's RNNStateEncoder), random weights.  Milliseconds.", ""]
+    record = {}
+    for N in a.n:
+        hip = bench_hip(a.steps, N, a.iters, a.warmup, dev)
+        torch.cuda.empty_cache()
+        eager = None
+        if not a.no_eager:
+            try:
+                eager = bench_eager(a.steps, N, a.iters, a.warmup, dev)
+            except Exception as e:                                    # the record then says so instead of a number
+                eager = {"error": f"{type(e).__name__}: {e}"}
+            torch.cuda.empty_cache()
+        record[f"N={N}"] = {"hip": hip, "eager": eager}
+        lines += [f"## N = {N}  (M = {a.steps * N} frames)", "", "| phase | HIP path | torch eager | eager / HIP |", "|---|---:|---:|---:|"]
+        for k in ORDER:
+            e = eager.get(k) if eager and "error" not in eager else None
+            lines.append(f"| {LABEL[k]} | {hip[k]:.3f} | {'%.3f' % e if e is not None else 'not measured'} | "
+                         f"{'%.2f' % (e / hip[k]) if e is not None else '-'} |")
+        if eager and "error" in eager:
+            lines += ["", f"torch eager failed: `{eager['error']}`"]
+        lines.append("")
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(record))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
