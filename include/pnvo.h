@@ -444,6 +444,53 @@ int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm
 int pnvo_policy_train_timing(pnvo_policy_handle h, int mode);
 int pnvo_policy_train_timing_read(pnvo_policy_handle h, double ms[5]);
 
+/* ---- RolloutStorage on the device (pointnav_vo/rl/common/rollout_storage.py; pointnav-vo_amd/rollout_storage.py owns the
+ * tensors).  Stateless: DEVICE pointers to the storage's contiguous tensors, their sizes and a stream.  T = num_steps, N = num_envs;
+ * float32 fields are [T, N] (rewards, action_log_probs) or [T+1, N] (value_preds, returns, masks), actions [T, N] and prev_actions
+ * [T+1, N] are int64, recurrent_hidden_states is [T+1, L, N, H] with hidden_row = L*N*H floats per step.  Each call is ONE launch
+ * and never waits for the device.  Null pointers, non-positive sizes and a step outside the storage return PNVO_ERR_ARG. ---- */
+
+/* Replaces the seven small copy_ calls of insert() (rollout_storage.py:83-89): the *_in rows ([L,N,H] / [N]) go to row step + 1 of
+ * recurrent_hidden_states, prev_actions and masks and to row step of actions, action_log_probs, value_preds and rewards.
+ * 0 <= step < T.  The caller advances its step. */
+int pnvo_rollout_insert(float *recurrent_hidden_states, int64_t *actions, int64_t *prev_actions, float *action_log_probs,
+                        float *value_preds, float *rewards, float *masks, int T, int N, int64_t hidden_row, int step,
+                        const float *hidden_in, const int64_t *actions_in, const float *action_log_probs_in,
+                        const float *value_preds_in, const float *rewards_in, const float *masks_in, void *stream);
+
+/* Replaces after_update()'s copies of the small fields (rollout_storage.py:97-99): row `step` of recurrent_hidden_states, masks and
+ * prev_actions moves to row 0.  0 <= step <= T (0: nothing to do). */
+int pnvo_rollout_after_update(float *recurrent_hidden_states, int64_t *prev_actions, float *masks, int T, int N, int64_t hidden_row,
+                              int step, void *stream);
+
+/* Replaces compute_returns() (rollout_storage.py:102-120) over the first `step` rows (0 <= step <= T; DD-PPO ends rollouts early):
+ *   use_gae != 0: value_preds[step] = next_value; gae = 0; for t = step-1 .. 0:
+ *                   delta = (rewards[t] + (gamma * value_preds[t+1]) * masks[t+1]) - value_preds[t]
+ *                   gae = delta + (gamma_tau * masks[t+1]) * gae;   returns[t] = gae + value_preds[t]
+ *   use_gae == 0: returns[step] = next_value; for t = step-1 .. 0: returns[t] = ((returns[t+1] * gamma) * masks[t+1]) + rewards[t]
+ * in float32 with one rounding per operation, the reference's order: bit-equal to its torch result when gamma and gamma_tau are
+ * float32(gamma) and float32 of the double product gamma * tau.  next_value [N].  Rows the reference leaves alone are not written.
+ * A lane per environment; the [step(+1), N] slabs are staged in LDS with coalesced row loads, and read straight from global memory
+ * when a rollout is too long for the LDS budget. */
+int pnvo_rollout_compute_returns(const float *rewards, float *value_preds, const float *masks, float *returns, const float *next_value,
+                                 int T, int N, int step, int use_gae, float gamma, float gamma_tau, void *stream);
+
+/* Replaces the per-environment slicing, stacking and flattening of recurrent_generator() for ONE minibatch (rollout_storage.py:
+ * 143-199): the environments perm[start .. start + n_mb) (perm: int64 [N], every entry in [0, N) — validated by the caller, and an
+ * entry outside is skipped, never dereferenced) of the first `steps` rows of the seven [.., N] fields — advantages is [>= steps, N] —
+ * are written T-major, row t * n_mb + j, and recurrent_hidden_states[0, :, perm[start + j]] to hidden_out [L, n_mb, H]. */
+int pnvo_rollout_gather(const float *recurrent_hidden_states, const int64_t *actions, const int64_t *prev_actions,
+                        const float *value_preds, const float *returns, const float *masks, const float *action_log_probs,
+                        const float *advantages, const int64_t *perm, int N, int L, int H, int steps, int start, int n_mb,
+                        float *hidden_out, int64_t *actions_out, int64_t *prev_actions_out, float *value_preds_out, float *returns_out,
+                        float *masks_out, float *action_log_probs_out, float *advantages_out, void *stream);
+
+/* The same gather for one sensor (rollout_storage.py:146-149, 169-171, 186-189): frames [>= steps, N, F] -> out [steps * n_mb, F],
+ * frame t * n_mb + j = frames[t, perm[start + j]].  16-byte loads and stores when F % 4 == 0 and both bases are 16-byte aligned,
+ * a scalar form otherwise; the grid strides over the work and is bounded by the compute-unit count. */
+int pnvo_rollout_gather_frames(const float *frames, const int64_t *perm, int N, int64_t F, int steps, int start, int n_mb, float *out,
+                               void *stream);
+
 /* F.avg_pool2d(x, 2) of 1-channel NHWC frames [N,H,W,1] -> [N,H/2,W/2,2] with channel 1 = 0 (resnet_policy.py:168). */
 int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *stream);
 

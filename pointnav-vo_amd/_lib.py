@@ -118,6 +118,11 @@ _SIGNATURES = {
     "pnvo_policy_clip_grad_norm": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "pnvo_policy_train_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "pnvo_policy_train_timing_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "pnvo_rollout_insert": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 7),
+    "pnvo_rollout_after_update": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "pnvo_rollout_compute_returns": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p]),
+    "pnvo_rollout_gather": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p] * 9),
+    "pnvo_rollout_gather_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     "pnvo_avgpool2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pnvo_layer_kernel": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]),
     "pnvo_timing_mode": (C.c_int, [C.c_void_p, C.c_int]),

@@ -15,8 +15,11 @@ drives the C ABI —
 until the end (one synchronisation per update).  The gradient is one flat buffer: a data-parallel all-reduce is one call
 (parallel.allreduce_mean_(step.grad)) between `backward()` and `optimizer_step()`.
 
-Not here: the DD-PPO reducer and pre-emption logic, RolloutStorage, an autograd bridge for the reference's own PPO.update, GRU and
-non-resnet18 backbones.  No CPU fallback.
+`rollouts` is rollout_storage.RolloutStorage (the reference's class on the device: insert, compute_returns and the minibatch gather
+are one launch each); the agent reads only `returns`, `value_preds` and `recurrent_generator`.
+
+Not here: the DD-PPO reducer and pre-emption logic, an autograd bridge for the reference's own PPO.update, GRU and non-resnet18
+backbones.  No CPU fallback.
 """
 import ctypes as C
 
