@@ -6,6 +6,8 @@ path never routes through oracle/ or any CPU implementation.
 import ctypes as C
 import os
 
+import numpy as np
+
 # torch bundles its own ROCm runtime (torch/lib/libamdhip64.so, same SONAME as /opt/rocm's).  It must be the FIRST HIP
 # runtime mapped into the process, so that libpnvo.so's NEEDED libamdhip64.so.7 resolves to the copy torch uses:
 # two HIP/HSA runtimes in one process do not both get the GPU ("no ROCm-capable device is detected").
@@ -157,6 +159,29 @@ def check(rc, handle=None):
     if rc != PNVO_OK:
         msg = lib.pnvo_last_error(handle)
         raise PnvoError(f"libpnvo error {rc}: {msg.decode() if msg else '?'}")
+
+
+def make_toc(entries):
+    """[(name, offset in floats, shape)] -> the pnvo_tensor_desc array the load / attach calls take."""
+    toc = (pnvo_tensor_desc * len(entries))()
+    for i, (name, offset, shape) in enumerate(entries):
+        toc[i].name = name.encode()
+        toc[i].offset = int(offset)
+        toc[i].ndim = len(shape)
+        for k, s in enumerate(shape):
+            toc[i].shape[k] = int(s)
+    return toc
+
+
+def pack_tensors(named_tensors):
+    """[(name, tensor)] -> (host float32 blob of the tensors back to back, its toc)."""
+    blob = np.ascontiguousarray(np.concatenate(
+        [t.detach().to("cpu", torch.float32).reshape(-1).numpy() for _, t in named_tensors]), dtype=np.float32)
+    entries, off = [], 0
+    for name, t in named_tensors:
+        entries.append((name, off, tuple(t.shape)))
+        off += t.numel()
+    return blob, make_toc(entries)
 
 
 def version():

@@ -14,7 +14,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -44,10 +43,13 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float *d, int N, in
   out[2 * e + 1] = 0.f;
 }
 
-// LSTM input x [B, hidden + 64]: visual | Linear(3 -> 32)(rho, cos(-phi), sin(-phi)) | Embedding((a + 1) * mask)
+// LSTM input x [B, hidden + 64]: visual | Linear(3 -> 32)(rho, cos(-phi), sin(-phi)) | Embedding((a + 1) * mask).  The update step
+// (B = the T*N rows of a rollout) keeps the gathered embedding row (rows) and (rho, cos(-phi), sin(-phi)) (g3) per row for its backward;
+// both are nullptr on the act path.
 __global__ __launch_bounds__(256) void policy_inputs_kernel(const float *visual, const float *goal, const int64_t *prev,
                                                           const float *masks, const float *tgt_w, const float *tgt_b,
-                                                          const float *emb, int n_emb, int B, int hidden, float *x) {
+                                                          const float *emb, int n_emb, int B, int hidden, float *x, int *rows,
+                                                          float *g3) {
   const int K = hidden + 64;
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= (long)B * K) return;
@@ -60,12 +62,18 @@ __global__ __launch_bounds__(256) void policy_inputs_kernel(const float *visual,
     const float rho = goal[2 * b], phi = goal[2 * b + 1];
     const float g0 = rho, g1 = cosf(-phi), g2 = sinf(-phi);
     v = __builtin_fmaf(tgt_w[3 * j + 2], g2, __builtin_fmaf(tgt_w[3 * j + 1], g1, tgt_w[3 * j] * g0)) + tgt_b[j];
+    if (j == 0 && g3 != nullptr) {
+      g3[3 * b] = g0;
+      g3[3 * b + 1] = g1;
+      g3[3 * b + 2] = g2;
+    }
   } else {
     const int j = k - hidden - 32;
     long row = (long)(((float)prev[b] + 1.0f) * masks[b]);     // ((prev_actions.float() + 1) * masks).long()
     if (row < 0) row = 0;
     if (row >= n_emb) row = n_emb - 1;
     v = emb[row * 32 + j];
+    if (j == 0 && rows != nullptr) rows[b] = (int)row;
   }
   x[e] = v;
 }
@@ -154,40 +162,6 @@ __global__ __launch_bounds__(256) void policy_heads_kernel(const float *x, const
   }
 }
 
-int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
-
-#define PCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e__ = (expr);                                                                    \
-    if (e__ != hipSuccess) return pfail(PNVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
-void dfree(float *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-const float *find(const std::map<std::string, const pnvo_tensor_desc *> &by, const float *blob, size_t n,
-                  const std::string &name, std::vector<int64_t> shape, int *rc) {
-  auto it = by.find(name);
-  if (it == by.end()) {
-    *rc = pfail(PNVO_ERR_WEIGHTS, "policy state_dict is missing tensor '" + name + "'");
-    return nullptr;
-  }
-  const pnvo_tensor_desc *d = it->second;
-  size_t cnt = 1;
-  bool ok = d->ndim == (int)shape.size();
-  for (int k = 0; ok && k < d->ndim; ++k) {
-    ok = d->shape[k] == shape[k];
-    cnt *= (size_t)d->shape[k];
-  }
-  if (!ok || d->offset + cnt > n) {
-    *rc = pfail(PNVO_ERR_WEIGHTS, "policy tensor '" + name + "' has the wrong shape");
-    return nullptr;
-  }
-  return blob + d->offset;
-}
-
 int upload(float *&dst, const float *src, size_t n) {
   dfree(dst);
   PCHK(hipMalloc((void **)&dst, n * sizeof(float)));
@@ -201,22 +175,68 @@ int upload(float *&dst, const float *src, size_t n) {
 using namespace pnvo;
 
 void pnvo::pnvo_policy_free_weights(Policy &p) {
-  if (!p.attached) {
-    dfree(p.emb);
-    dfree(p.tgt_w);
-    dfree(p.tgt_b);
-    for (auto &v : p.w_ih) dfree(v);
-    for (auto &v : p.w_hh) dfree(v);
-    for (auto &v : p.b_ih) dfree(v);
-    for (auto &v : p.b_hh) dfree(v);
-    dfree(p.act_w);
-    dfree(p.act_b);
-    dfree(p.cr_w);
-    dfree(p.cr_b);
+  for (const PolicyParam &e : policy_params(p)) {
+    if (!p.attached) dfree(*e.slot);
+    *e.slot = nullptr;
   }
-  p.emb = p.tgt_w = p.tgt_b = p.act_w = p.act_b = p.cr_w = p.cr_b = nullptr;
-  for (auto *v : {&p.w_ih, &p.w_hh, &p.b_ih, &p.b_hh})
-    for (auto &q : *v) q = nullptr;
+}
+
+hipError_t pnvo::launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks,
+                                      int rows, float *x, int *rows_out, float *g3, hipStream_t s) {
+  const int Hd = p.cfg.hidden;
+  hipLaunchKernelGGL(policy_inputs_kernel, dim3((unsigned)(((long)rows * (Hd + 64) + 255) / 256)), dim3(256), 0, s, visual, goal, prev,
+                     masks, p.tgt_w, p.tgt_b, p.emb, p.cfg.n_actions + 1, rows, Hd, x, rows_out, g3);
+  return hipGetLastError();
+}
+
+const pnvo_tensor_desc *pnvo::policy_find(const pnvo_tensor_desc *toc, int ntoc, const PolicyParam &e, size_t n_floats, int *rc) {
+  for (int k = 0; k < ntoc; ++k) {
+    if (e.name != toc[k].name) continue;
+    const pnvo_tensor_desc &d = toc[k];
+    bool ok = d.ndim == (int)e.shape.size();
+    for (int i = 0; ok && i < d.ndim; ++i) ok = d.shape[i] == e.shape[i];
+    if (!ok || d.offset + numel(e.shape) > n_floats) {
+      *rc = pfail(PNVO_ERR_WEIGHTS, "policy tensor '" + e.name + "' has the wrong shape");
+      return nullptr;
+    }
+    return &d;
+  }
+  *rc = pfail(PNVO_ERR_WEIGHTS, "policy state_dict is missing tensor '" + e.name + "'");
+  return nullptr;
+}
+
+int pnvo::policy_encoder_table(const Policy &p, const pnvo_tensor_desc *toc, int ntoc, size_t n_floats, std::vector<EncoderEntry> *out) {
+  const std::string pre = "net.visual_encoder.";
+  out->clear();
+  for (int k = 0; k < ntoc; ++k) {
+    const std::string nm = toc[k].name;
+    if (toc[k].ndim < 0 || toc[k].ndim > 4) return pfail(PNVO_ERR_WEIGHTS, "tensor '" + nm + "' has a bad rank");
+    const std::vector<int64_t> shape(toc[k].shape, toc[k].shape + toc[k].ndim);
+    if (toc[k].offset + numel(shape) > n_floats) return pfail(PNVO_ERR_WEIGHTS, "tensor '" + nm + "' exceeds the buffer");
+    if (nm == pre + "backbone.conv1.0.weight") {          // [C0,1,7,7] -> [C0,2,7,7], second input channel = 0
+      if (shape != std::vector<int64_t>{p.cfg.baseplanes, 1, 7, 7}) return pfail(PNVO_ERR_WEIGHTS, "policy stem must take 1 depth channel");
+      out->push_back({"visual_encoder.backbone.conv1.0.weight", {shape[0], 2, 7, 7}, EncoderEntry::STEM, k});
+    } else if (nm.compare(0, pre.size(), pre) == 0) {
+      out->push_back({"visual_encoder." + nm.substr(pre.size()), shape, EncoderEntry::VIEW, k});
+    } else if (nm == "net.visual_fc.1.weight" || nm == "net.visual_fc.1.bias") {
+      out->push_back({"visual_fc.2." + nm.substr(nm.rfind('.') + 1), shape, EncoderEntry::VIEW, k});
+    }
+  }
+  out->push_back({"output_head.1.weight", {1, p.cfg.hidden}, EncoderEntry::ZEROS, -1});
+  out->push_back({"output_head.1.bias", {1}, EncoderEntry::ZEROS, -1});
+  return PNVO_OK;
+}
+
+std::vector<pnvo_tensor_desc> pnvo::encoder_toc(const std::vector<EncoderEntry> &entries, const std::vector<size_t> &offsets) {
+  std::vector<pnvo_tensor_desc> toc(entries.size());
+  for (size_t i = 0; i < entries.size(); ++i) {
+    std::memset(&toc[i], 0, sizeof(toc[i]));
+    toc[i].name = entries[i].name.c_str();
+    toc[i].offset = offsets[i];
+    toc[i].ndim = (int)entries[i].shape.size();
+    for (size_t d = 0; d < entries[i].shape.size(); ++d) toc[i].shape[d] = entries[i].shape[d];
+  }
+  return toc;
 }
 
 extern "C" {
@@ -263,10 +283,7 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
     delete h;
     return rc;
   }
-  h->p.w_ih.assign(cfg->rnn_layers, nullptr);
-  h->p.w_hh.assign(cfg->rnn_layers, nullptr);
-  h->p.b_ih.assign(cfg->rnn_layers, nullptr);
-  h->p.b_hh.assign(cfg->rnn_layers, nullptr);
+  for (auto *v : {&h->p.w_ih, &h->p.w_hh, &h->p.b_ih, &h->p.b_hh}) v->assign(cfg->rnn_layers, nullptr);   // policy_params()'s slots
   *out = h;
   return PNVO_OK;
 }
@@ -279,88 +296,35 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
     return pfail(PNVO_ERR_STATE, "pnvo_policy_load_weights after pnvo_policy_train_attach: the parameters live in the caller's flat buffer "
                                  "(write them there and call pnvo_policy_train_refresh)");
   PCHK(hipSetDevice(p.device));
-  std::map<std::string, const pnvo_tensor_desc *> by;
-  for (int k = 0; k < ntoc; ++k) by[toc[k].name] = &toc[k];
-  const pnvo_policy_config &c = p.cfg;
-  const int Hd = c.hidden, K0 = Hd + 64;
   int rc = PNVO_OK;
-  // ---- visual encoder + visual_fc: re-key into the VO model's naming, pad the stem to 2 input channels
+  // ---- visual encoder + visual_fc: the encoder handle's table, materialised into a blob of its own
   {
-    const std::string pre = "net.visual_encoder.";
+    std::vector<EncoderEntry> ent;
+    if ((rc = policy_encoder_table(p, toc, ntoc, n_floats, &ent)) != PNVO_OK) return rc;
     std::vector<float> eblob;
-    std::vector<std::string> names;
-    std::vector<pnvo_tensor_desc> etoc;
-    auto push = [&](const std::string &name, const float *src, std::vector<int64_t> shape, size_t cnt) {
-      pnvo_tensor_desc d;
-      std::memset(&d, 0, sizeof(d));
-      d.offset = eblob.size();
-      d.ndim = (int)shape.size();
-      for (size_t k = 0; k < shape.size(); ++k) d.shape[k] = shape[k];
-      names.push_back(name);
-      etoc.push_back(d);
-      if (src)
-        eblob.insert(eblob.end(), src, src + cnt);
-      else
+    std::vector<size_t> offs;
+    for (const EncoderEntry &e : ent) {
+      offs.push_back(eblob.size());
+      const size_t cnt = numel(e.shape);
+      if (e.src == EncoderEntry::VIEW) {
+        eblob.insert(eblob.end(), blob + toc[e.k].offset, blob + toc[e.k].offset + cnt);
+      } else {
         eblob.insert(eblob.end(), cnt, 0.f);
-    };
-    for (int k = 0; k < ntoc; ++k) {
-      const std::string nm = toc[k].name;
-      size_t cnt = 1;
-      std::vector<int64_t> shape;
-      for (int d = 0; d < toc[k].ndim; ++d) {
-        shape.push_back(toc[k].shape[d]);
-        cnt *= (size_t)toc[k].shape[d];
-      }
-      if (toc[k].offset + cnt > n_floats) return pfail(PNVO_ERR_WEIGHTS, "tensor '" + nm + "' exceeds the blob");
-      const float *src = blob + toc[k].offset;
-      if (nm == pre + "backbone.conv1.0.weight") {          // [C0,1,7,7] -> [C0,2,7,7], second input channel = 0
-        if (shape.size() != 4 || shape[1] != 1) return pfail(PNVO_ERR_WEIGHTS, "policy stem must take 1 depth channel");
-        const int64_t co = shape[0], kk = shape[2] * shape[3];
-        std::vector<float> w((size_t)co * 2 * kk, 0.f);
-        for (int64_t o = 0; o < co; ++o) std::memcpy(&w[(size_t)o * 2 * kk], src + o * kk, sizeof(float) * kk);
-        push("visual_encoder.backbone.conv1.0.weight", w.data(), {co, 2, shape[2], shape[3]}, w.size());
-      } else if (nm.compare(0, pre.size(), pre) == 0) {
-        push("visual_encoder." + nm.substr(pre.size()), src, shape, cnt);
-      } else if (nm == "net.visual_fc.1.weight") {
-        push("visual_fc.2.weight", src, shape, cnt);
-      } else if (nm == "net.visual_fc.1.bias") {
-        push("visual_fc.2.bias", src, shape, cnt);
+        if (e.src == EncoderEntry::STEM)                 // [C0,1,7,7] -> channel 0 of [C0,2,7,7]
+          for (int64_t o = 0; o < e.shape[0]; ++o)
+            std::memcpy(&eblob[offs.back() + (size_t)o * 98], blob + toc[e.k].offset + o * 49, sizeof(float) * 49);
       }
     }
-    push("output_head.1.weight", nullptr, {1, Hd}, (size_t)Hd);
-    push("output_head.1.bias", nullptr, {1}, 1);
-    for (size_t k = 0; k < etoc.size(); ++k) etoc[k].name = names[k].c_str();
+    const std::vector<pnvo_tensor_desc> etoc = encoder_toc(ent, offs);
     rc = pnvo_load_weights(p.enc, eblob.data(), eblob.size(), etoc.data(), (int)etoc.size());
     if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   }
   // ---- recurrent part and heads (kept in torch's layouts)
-  const float *s;
-  if (!(s = find(by, blob, n_floats, "net.prev_action_embedding.weight", {c.n_actions + 1, 32}, &rc))) return rc;
-  if ((rc = upload(p.emb, s, (size_t)(c.n_actions + 1) * 32)) != PNVO_OK) return rc;
-  if (!(s = find(by, blob, n_floats, "net.tgt_embeding.weight", {32, 3}, &rc))) return rc;
-  if ((rc = upload(p.tgt_w, s, 96)) != PNVO_OK) return rc;
-  if (!(s = find(by, blob, n_floats, "net.tgt_embeding.bias", {32}, &rc))) return rc;
-  if ((rc = upload(p.tgt_b, s, 32)) != PNVO_OK) return rc;
-  for (int l = 0; l < c.rnn_layers; ++l) {
-    const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
-    const int K = l == 0 ? K0 : Hd;
-    if (!(s = find(by, blob, n_floats, r + "weight_ih" + sl, {4 * Hd, K}, &rc))) return rc;
-    if ((rc = upload(p.w_ih[l], s, (size_t)4 * Hd * K)) != PNVO_OK) return rc;
-    if (!(s = find(by, blob, n_floats, r + "weight_hh" + sl, {4 * Hd, Hd}, &rc))) return rc;
-    if ((rc = upload(p.w_hh[l], s, (size_t)4 * Hd * Hd)) != PNVO_OK) return rc;
-    if (!(s = find(by, blob, n_floats, r + "bias_ih" + sl, {4 * Hd}, &rc))) return rc;
-    if ((rc = upload(p.b_ih[l], s, (size_t)4 * Hd)) != PNVO_OK) return rc;
-    if (!(s = find(by, blob, n_floats, r + "bias_hh" + sl, {4 * Hd}, &rc))) return rc;
-    if ((rc = upload(p.b_hh[l], s, (size_t)4 * Hd)) != PNVO_OK) return rc;
+  for (const PolicyParam &e : policy_params(p)) {
+    const pnvo_tensor_desc *d = policy_find(toc, ntoc, e, n_floats, &rc);
+    if (!d) return rc;
+    if ((rc = upload(*e.slot, blob + d->offset, numel(e.shape))) != PNVO_OK) return rc;
   }
-  if (!(s = find(by, blob, n_floats, "action_distribution.linear.weight", {c.n_actions, Hd}, &rc))) return rc;
-  if ((rc = upload(p.act_w, s, (size_t)c.n_actions * Hd)) != PNVO_OK) return rc;
-  if (!(s = find(by, blob, n_floats, "action_distribution.linear.bias", {c.n_actions}, &rc))) return rc;
-  if ((rc = upload(p.act_b, s, (size_t)c.n_actions)) != PNVO_OK) return rc;
-  if (!(s = find(by, blob, n_floats, "critic.fc.weight", {1, Hd}, &rc))) return rc;
-  if ((rc = upload(p.cr_w, s, (size_t)Hd)) != PNVO_OK) return rc;
-  if (!(s = find(by, blob, n_floats, "critic.fc.bias", {1}, &rc))) return rc;
-  if ((rc = upload(p.cr_b, s, 1)) != PNVO_OK) return rc;
   p.loaded = true;
   return PNVO_OK;
 }
@@ -375,13 +339,8 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
     return pfail(PNVO_ERR_ARG, "null argument / bad batch");
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
-  {
-    // lstm_layer_kernel writes h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory
-    const uintptr_t bytes = (uintptr_t)2 * L * B * Hd * sizeof(float);
-    const uintptr_t in0 = (uintptr_t)hidden_in, out0 = (uintptr_t)hidden_out;
-    if (in0 < out0 + bytes && out0 < in0 + bytes)
-      return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * B * hidden floats): pass separate buffers");
-  }
+  if (hidden_states_overlap(hidden_in, hidden_out, (size_t)2 * L * B * Hd))
+    return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * B * hidden floats): pass separate buffers");
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   if (B > p.cap) {
@@ -397,8 +356,7 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
   if (rc != PNVO_OK) return rc;
   rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
-  hipLaunchKernelGGL(policy_inputs_kernel, dim3((unsigned)(((long)B * K0 + 255) / 256)), dim3(256), 0, s, p.visual, goal,
-                     prev_actions, masks, p.tgt_w, p.tgt_b, p.emb, c.n_actions + 1, B, Hd, p.x);
+  PCHK(launch_policy_inputs(p, p.visual, goal, prev_actions, masks, B, p.x, nullptr, nullptr, s));
   // hidden_in / hidden_out: [2L, B, Hd] = (h_0 .. h_{L-1}, c_0 .. c_{L-1})  (rnn_state_encoder.py:47-61)
   const float *xin = p.x;
   int K = K0;

@@ -1,22 +1,26 @@
-// pnvo_policy_state.h — the navigation policy's handle, shared by its per-step forward (pnvo_policy.hip) and its PPO update step
-// (policy_train.hip).
+// pnvo_policy_state.h — the navigation policy's handle, its parameter table and the small host helpers shared by its per-step forward
+// (pnvo_policy.hip) and its PPO update step (policy_train.hip).
 #pragma once
+#include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/pnvo.h"
+#include "pnvo_model.h"
 
 namespace pnvo {
 
-struct PolicyTrain;                  // policy_train.hip: flat-buffer offsets, saved activations and scratch of the update step
+struct PolicyTrain;                  // policy_train.hip: the flat buffers, saved activations and scratch of the update step
 
 struct Policy {
   pnvo_policy_config cfg;
   int device = 0;
   pnvo_handle enc = nullptr;
   bool loaded = false;
-  // device weights (torch layouts): owned copies, or — once a train step is attached — pointers into the caller's flat buffer
+  // device weights (torch layouts), listed once in policy_params(): owned copies, or — once a train step is attached — pointers into
+  // the caller's flat buffer
   float *emb = nullptr, *tgt_w = nullptr, *tgt_b = nullptr;
-  std::vector<float *> w_ih, w_hh, b_ih, b_hh;
+  std::vector<float *> w_ih, w_hh, b_ih, b_hh;       // one per LSTM layer
   float *act_w = nullptr, *act_b = nullptr, *cr_w = nullptr, *cr_b = nullptr;
   bool attached = false;             // pnvo_policy_train_attach: the weight pointers above are not owned
   PolicyTrain *train = nullptr;
@@ -25,8 +29,82 @@ struct Policy {
   float *pooled = nullptr, *visual = nullptr, *x = nullptr;
 };
 
+// ---- the policy-owned tensors (everything but the visual encoder and visual_fc, which live in the encoder handle), in state_dict order
+struct PolicyParam {
+  std::string name;
+  std::vector<int64_t> shape;
+  float **slot;                      // where Policy keeps the device pointer
+  bool rows_as_float4;               // kernels read its rows as 16-byte vectors: the tensor must start at a multiple of 4 floats
+};
+
+inline std::vector<PolicyParam> policy_params(Policy &p) {
+  const int64_t Hd = p.cfg.hidden, A = p.cfg.n_actions;
+  std::vector<PolicyParam> t = {{"net.prev_action_embedding.weight", {A + 1, 32}, &p.emb, false},
+                                {"net.tgt_embeding.weight", {32, 3}, &p.tgt_w, false},
+                                {"net.tgt_embeding.bias", {32}, &p.tgt_b, false}};
+  for (int l = 0; l < p.cfg.rnn_layers; ++l) {
+    const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
+    t.push_back({r + "weight_ih" + sl, {4 * Hd, l == 0 ? Hd + 64 : Hd}, &p.w_ih[l], true});
+    t.push_back({r + "weight_hh" + sl, {4 * Hd, Hd}, &p.w_hh[l], true});
+    t.push_back({r + "bias_ih" + sl, {4 * Hd}, &p.b_ih[l], false});
+    t.push_back({r + "bias_hh" + sl, {4 * Hd}, &p.b_hh[l], false});
+  }
+  t.push_back({"action_distribution.linear.weight", {A, Hd}, &p.act_w, true});
+  t.push_back({"action_distribution.linear.bias", {A}, &p.act_b, false});
+  t.push_back({"critic.fc.weight", {1, Hd}, &p.cr_w, true});
+  t.push_back({"critic.fc.bias", {1}, &p.cr_b, false});
+  return t;
+}
+
+inline size_t numel(const std::vector<int64_t> &shape) {
+  size_t n = 1;
+  for (int64_t s : shape) n *= (size_t)s;
+  return n;
+}
+
+// ---- the encoder handle's table, from the caller's: the VO model's names (net.visual_encoder.* -> visual_encoder.*, net.visual_fc.1.*
+// -> visual_fc.2.*), the stem widened to the handle's two input channels [C0,2,7,7], and the handle's unused output head
+struct EncoderEntry {
+  enum Source { VIEW, STEM, ZEROS };  // entry k of the caller's table as it is / that entry zero-padded to 2 input channels / all zeros
+  std::string name;
+  std::vector<int64_t> shape;
+  Source src;
+  int k;
+};
+// pnvo_policy.hip; also checks the rank and the range (offset + numel <= n_floats) of EVERY entry of the caller's table
+int policy_encoder_table(const Policy &p, const pnvo_tensor_desc *toc, int ntoc, size_t n_floats, std::vector<EncoderEntry> *out);
+// the descriptors pnvo_load_weights / pnvo_train_attach take, with entry i at offsets[i] (the names point into `entries`)
+std::vector<pnvo_tensor_desc> encoder_toc(const std::vector<EncoderEntry> &entries, const std::vector<size_t> &offsets);
+// entry `e` of the parameter table in the caller's toc, with its full shape and range checked; nullptr with *rc set otherwise
+const pnvo_tensor_desc *policy_find(const pnvo_tensor_desc *toc, int ntoc, const PolicyParam &e, size_t n_floats, int *rc);
+
 void pnvo_policy_free_weights(Policy &p);     // pnvo_policy.hip: frees the owned copies (no-op on borrowed pointers) and nulls them
 void pnvo_policy_train_free(Policy &p);       // policy_train.hip
+// pnvo_policy.hip: x [rows, hidden + 64] = visual | tgt_embeding(goal) | prev_action_embedding; rows_out / g3 (optional, the update step's)
+// keep the gathered embedding row and (rho, cos(-phi), sin(-phi)) per row
+hipError_t launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks, int rows,
+                                float *x, int *rows_out, float *g3, hipStream_t s);
+
+// ---- host helpers of both files
+inline int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
+
+#define PCHK(expr)                                                                              \
+  do {                                                                                          \
+    hipError_t e__ = (expr);                                                                    \
+    if (e__ != hipSuccess) return pfail(PNVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+  } while (0)
+
+template <class T>
+void dfree(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+// The LSTM kernels write h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory.
+inline bool hidden_states_overlap(const float *in, const float *out, size_t floats) {
+  const uintptr_t bytes = (uintptr_t)floats * sizeof(float), a = (uintptr_t)in, b = (uintptr_t)out;
+  return a < b + bytes && b < a + bytes;
+}
 
 }  // namespace pnvo
 

@@ -2,7 +2,7 @@
 // rl/policies/policy.py:52-63), gfx950 only, float32.
 //
 //   evaluate : depth [T*N] -> avg_pool2d(2) -> the visual encoder's TRAIN-mode forward (pnvo_train_forward: activations kept)
-//              -> x = [visual | tgt_embeding | prev_action_embedding]                       rollout_inputs_kernel, M = T*N rows
+//              -> x = [visual | tgt_embeding | prev_action_embedding]                       policy_inputs_kernel, M = T*N rows
 //              -> per LSTM layer: G_x = X . W_ih^T + b_ih + b_hh over all M rows            gemm_f32_kernel (v_mfma_f32_32x32x2_f32)
 //                                 T launches of lstm_step_kernel (the only sequential part)  gates, c, h, masked h_prev kept
 //              -> logits / value / log pi(a) / entropy per row                               heads_eval_kernel
@@ -16,7 +16,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -30,8 +29,7 @@ namespace pnvo {
 struct PolicyTrain {
   float *params = nullptr, *grads = nullptr;
   size_t n = 0, n_named = 0;          // floats handed over / floats covered by the parameter table (the rest is the tail below)
-  size_t o_emb = 0, o_tgt_w = 0, o_tgt_b = 0, o_stem = 0, o_act_w = 0, o_act_b = 0, o_cr_w = 0, o_cr_b = 0;
-  std::vector<size_t> o_wih, o_whh, o_bih, o_bhh;
+  size_t o_stem = 0;                  // the policy's stem weight [C0,1,7,7] (the one tensor read here that is not a Policy slot)
   size_t o_stem2 = 0;                 // tail: the stem weight zero-padded to the encoder handle's 2 input channels [C0,2,7,7],
   int c0 = 0;                         //       then the handle's unused output head (hidden weights + 1 bias, zeros)
   // the last evaluate
@@ -58,53 +56,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SQ_BLOCKS = 1024;
 
-int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
-
-#define PCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e__ = (expr);                                                                    \
-    if (e__ != hipSuccess) return pfail(PNVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// ------------------------------------------------------------------------------------------------------------ rollout inputs
-// x [M, hidden + 64]: visual | Linear(3 -> 32)(rho, cos(-phi), sin(-phi)) | Embedding((a + 1) * mask)  — policy_inputs_kernel over the
-// M = T*N rows of a rollout; the gathered embedding row and (rho, cos(-phi), sin(-phi)) are kept per row for the backward
-__global__ __launch_bounds__(256) void rollout_inputs_kernel(const float *visual, const float *goal, const int64_t *prev, const float *masks,
-                                                           const float *tgt_w, const float *tgt_b, const float *emb, int n_emb, int M,
-                                                           int hidden, float *x, int *rows, float *g3) {
-  const int K = hidden + 64;
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long)M * K) return;
-  const int b = (int)(e / K), k = (int)(e % K);
-  float v;
-  if (k < hidden) {
-    v = visual[(long)b * hidden + k];
-  } else if (k < hidden + 32) {
-    const int j = k - hidden;
-    const float rho = goal[2 * b], phi = goal[2 * b + 1];
-    const float g0 = rho, g1 = cosf(-phi), g2 = sinf(-phi);
-    v = __builtin_fmaf(tgt_w[3 * j + 2], g2, __builtin_fmaf(tgt_w[3 * j + 1], g1, tgt_w[3 * j] * g0)) + tgt_b[j];
-    if (j == 0) {
-      g3[3 * b] = g0;
-      g3[3 * b + 1] = g1;
-      g3[3 * b + 2] = g2;
-    }
-  } else {
-    const int j = k - hidden - 32;
-    long row = (long)(((float)prev[b] + 1.0f) * masks[b]);     // ((prev_actions.float() + 1) * masks).long()
-    if (row < 0) row = 0;
-    if (row >= n_emb) row = n_emb - 1;
-    v = emb[row * 32 + j];
-    if (j == 0) rows[b] = (int)row;
-  }
-  x[e] = v;
-}
+// once attached every Policy slot points into the caller's flat parameter buffer: its gradient sits at the same offset of the other one
+float *grad_of(const PolicyTrain *t, const float *slot) { return t->grads + (slot - t->params); }
 
 // ------------------------------------------------------------------------------------------------------------ float32 GEMM
 // C[m][n] = sum_k A(m,k) B(k,n) (+ bias0[n] + bias1[n]) on the exact-float32 matrix instruction (one k-ordered fmaf chain per output,
@@ -599,37 +552,16 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   return PNVO_OK;
 }
 
-// the encoder handle's own parameter table inside the policy's flat buffer: the VO model's names, the padded stem and the unused head
-// in the tail
-int attach_encoder(Policy &p, PolicyTrain *t, const pnvo_tensor_desc *toc, int ntoc) {
-  const std::string pre = "net.visual_encoder.";
-  std::vector<std::string> names;
-  std::vector<pnvo_tensor_desc> etoc;
-  auto push = [&](const std::string &name, size_t off, std::vector<int64_t> shape) {
-    pnvo_tensor_desc d;
-    std::memset(&d, 0, sizeof(d));
-    d.offset = off;
-    d.ndim = (int)shape.size();
-    for (size_t k = 0; k < shape.size(); ++k) d.shape[k] = shape[k];
-    names.push_back(name);
-    etoc.push_back(d);
-  };
-  for (int k = 0; k < ntoc; ++k) {
-    const std::string nm = toc[k].name;
-    std::vector<int64_t> shape(toc[k].shape, toc[k].shape + toc[k].ndim);
-    if (nm == pre + "backbone.conv1.0.weight")
-      push("visual_encoder.backbone.conv1.0.weight", t->o_stem2, {shape[0], 2, shape[2], shape[3]});
-    else if (nm.compare(0, pre.size(), pre) == 0)
-      push("visual_encoder." + nm.substr(pre.size()), toc[k].offset, shape);
-    else if (nm == "net.visual_fc.1.weight")
-      push("visual_fc.2.weight", toc[k].offset, shape);
-    else if (nm == "net.visual_fc.1.bias")
-      push("visual_fc.2.bias", toc[k].offset, shape);
+// the encoder handle's own parameter table inside the policy's flat buffer: the caller's entries where they are, the padded stem and
+// the unused head in the tail
+int attach_encoder(Policy &p, PolicyTrain *t, const std::vector<EncoderEntry> &ent, const pnvo_tensor_desc *toc) {
+  std::vector<size_t> offs;
+  size_t o_head = t->o_stem2 + (size_t)t->c0 * 98;
+  for (const EncoderEntry &e : ent) {
+    offs.push_back(e.src == EncoderEntry::VIEW ? (size_t)toc[e.k].offset : e.src == EncoderEntry::STEM ? t->o_stem2 : o_head);
+    if (e.src == EncoderEntry::ZEROS) o_head += numel(e.shape);
   }
-  const size_t o_head = t->o_stem2 + (size_t)t->c0 * 98;
-  push("output_head.1.weight", o_head, {1, p.cfg.hidden});
-  push("output_head.1.bias", o_head + (size_t)p.cfg.hidden, {1});
-  for (size_t k = 0; k < etoc.size(); ++k) etoc[k].name = names[k].c_str();
+  const std::vector<pnvo_tensor_desc> etoc = encoder_toc(ent, offs);
   const int rc = pnvo_train_attach(p.enc, t->params, t->grads, t->n, etoc.data(), (int)etoc.size());
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   return PNVO_OK;
@@ -665,31 +597,31 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
   if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach before pnvo_policy_load_weights");
   PCHK(hipSetDevice(p.device));
   const pnvo_policy_config &c = p.cfg;
-  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
-  std::map<std::string, const pnvo_tensor_desc *> by;
-  size_t n_named = 0;
-  for (int k = 0; k < ntoc; ++k) {
-    size_t cnt = 1;
-    for (int d = 0; d < toc[k].ndim; ++d) cnt *= (size_t)toc[k].shape[d];
-    if (toc[k].offset + cnt > n_floats) return pfail(PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range");
-    n_named = std::max(n_named, (size_t)toc[k].offset + cnt);
-    by[toc[k].name] = &toc[k];
-  }
+  const int Hd = c.hidden;
+  int rc = PNVO_OK;
+  std::vector<EncoderEntry> ent;
+  if ((rc = policy_encoder_table(p, toc, ntoc, n_floats, &ent)) != PNVO_OK) return rc;     // (checks every entry's range)
+  size_t n_named = 0, o_stem = n_floats;
+  for (int k = 0; k < ntoc; ++k)
+    n_named = std::max(n_named, (size_t)toc[k].offset + numel(std::vector<int64_t>(toc[k].shape, toc[k].shape + toc[k].ndim)));
+  for (const EncoderEntry &e : ent)
+    if (e.src == EncoderEntry::STEM) o_stem = (size_t)toc[e.k].offset;
+  if (o_stem == n_floats) return pfail(PNVO_ERR_WEIGHTS, "parameter table is missing the visual encoder's stem weight");
   if (n_floats < n_named + tail_floats(c))
     return pfail(PNVO_ERR_ARG, "flat buffers hold " + std::to_string(n_floats) + " floats; the " + std::to_string(n_named) +
                                    " of the parameter table need " + std::to_string(tail_floats(c)) +
                                    " more behind them (pnvo_policy_train_tail_floats)");
-  int rc = PNVO_OK;
-  auto off = [&](const std::string &name, size_t numel, size_t *out) {
-    auto it = by.find(name);
-    if (it == by.end()) return pfail(PNVO_ERR_WEIGHTS, "parameter table is missing '" + name + "'");
-    size_t cnt = 1;
-    for (int d = 0; d < it->second->ndim; ++d) cnt *= (size_t)it->second->shape[d];
-    if (cnt != numel)
-      return pfail(PNVO_ERR_WEIGHTS, "parameter '" + name + "' has " + std::to_string(cnt) + " elements, expected " + std::to_string(numel));
-    *out = (size_t)it->second->offset;
-    return PNVO_OK;
-  };
+  if (((uintptr_t)params & 15) != 0) return pfail(PNVO_ERR_ARG, "flat parameter buffer is not 16-byte aligned");
+  const std::vector<PolicyParam> tab = policy_params(p);
+  std::vector<size_t> offs;
+  for (const PolicyParam &e : tab) {
+    const pnvo_tensor_desc *d = policy_find(toc, ntoc, e, n_floats, &rc);
+    if (!d) return rc;
+    if (e.rows_as_float4 && d->offset % 4 != 0)
+      return pfail(PNVO_ERR_ARG, "parameter '" + e.name + "' starts at float " + std::to_string(d->offset) +
+                                     ", not a multiple of 4 (its rows are read as float4)");
+    offs.push_back((size_t)d->offset);
+  }
   pnvo_policy_train_free(p);
   PolicyTrain *t = new PolicyTrain();
   p.train = t;
@@ -698,58 +630,27 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
   t->n = n_floats;
   t->n_named = n_named;
   t->c0 = c.baseplanes;
+  t->o_stem = o_stem;
   t->o_stem2 = n_named;
-  t->o_wih.assign(L, 0);
-  t->o_whh.assign(L, 0);
-  t->o_bih.assign(L, 0);
-  t->o_bhh.assign(L, 0);
-  if ((rc = off("net.prev_action_embedding.weight", (size_t)(c.n_actions + 1) * 32, &t->o_emb)) != PNVO_OK) return rc;
-  if ((rc = off("net.tgt_embeding.weight", 96, &t->o_tgt_w)) != PNVO_OK) return rc;
-  if ((rc = off("net.tgt_embeding.bias", 32, &t->o_tgt_b)) != PNVO_OK) return rc;
-  if ((rc = off("net.visual_encoder.backbone.conv1.0.weight", (size_t)c.baseplanes * 49, &t->o_stem)) != PNVO_OK) return rc;
-  for (int l = 0; l < L; ++l) {
-    const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
-    const size_t K = l == 0 ? K0 : Hd;
-    if ((rc = off(r + "weight_ih" + sl, (size_t)4 * Hd * K, &t->o_wih[l])) != PNVO_OK) return rc;
-    if ((rc = off(r + "weight_hh" + sl, (size_t)4 * Hd * Hd, &t->o_whh[l])) != PNVO_OK) return rc;
-    if ((rc = off(r + "bias_ih" + sl, (size_t)4 * Hd, &t->o_bih[l])) != PNVO_OK) return rc;
-    if ((rc = off(r + "bias_hh" + sl, (size_t)4 * Hd, &t->o_bhh[l])) != PNVO_OK) return rc;
+  rc = [&]() -> int {
+    // tail: zero-padded stem + zero output head, gradients zero
+    PCHK(hipMemset(params + n_named, 0, tail_floats(c) * sizeof(float)));
+    PCHK(hipMemset(grads + n_named, 0, tail_floats(c) * sizeof(float)));
+    hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem, t->c0,
+                       params + t->o_stem2);
+    PCHK(hipGetLastError());
+    PCHK(hipMalloc((void **)&t->whhT, (size_t)4 * Hd * Hd * sizeof(float)));
+    PCHK(hipMalloc((void **)&t->sq_part, SQ_BLOCKS * sizeof(double)));
+    return attach_encoder(p, t, ent, toc);
+  }();
+  if (rc != PNVO_OK) {                  // no half-built train step is left behind
+    pnvo_policy_train_free(p);
+    return rc;
   }
-  if ((rc = off("action_distribution.linear.weight", (size_t)c.n_actions * Hd, &t->o_act_w)) != PNVO_OK) return rc;
-  if ((rc = off("action_distribution.linear.bias", (size_t)c.n_actions, &t->o_act_b)) != PNVO_OK) return rc;
-  if ((rc = off("critic.fc.weight", (size_t)Hd, &t->o_cr_w)) != PNVO_OK) return rc;
-  if ((rc = off("critic.fc.bias", 1, &t->o_cr_b)) != PNVO_OK) return rc;
-  for (size_t o : {t->o_emb, t->o_tgt_w, t->o_stem, t->o_act_w, t->o_cr_w})
-    if (o % 4 != 0) return pfail(PNVO_ERR_ARG, "parameter offset " + std::to_string(o) + " is not a multiple of 4 floats (rows are read as float4)");
-  for (int l = 0; l < L; ++l)
-    if (t->o_wih[l] % 4 != 0 || t->o_whh[l] % 4 != 0)
-      return pfail(PNVO_ERR_ARG, "LSTM weight offset of layer " + std::to_string(l) + " is not a multiple of 4 floats (rows are read as float4)");
-  if (((uintptr_t)params & 15) != 0) return pfail(PNVO_ERR_ARG, "flat parameter buffer is not 16-byte aligned");
-  // tail: zero-padded stem + zero output head, gradients zero
-  PCHK(hipMemset(params + n_named, 0, tail_floats(c) * sizeof(float)));
-  PCHK(hipMemset(grads + n_named, 0, tail_floats(c) * sizeof(float)));
-  hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem, t->c0,
-                     params + t->o_stem2);
-  PCHK(hipGetLastError());
-  if ((rc = attach_encoder(p, t, toc, ntoc)) != PNVO_OK) return rc;
   // the recurrent part and the heads read the flat buffer from now on (pnvo_policy_act included): no second copy
   pnvo_policy_free_weights(p);
   p.attached = true;
-  p.emb = params + t->o_emb;
-  p.tgt_w = params + t->o_tgt_w;
-  p.tgt_b = params + t->o_tgt_b;
-  for (int l = 0; l < L; ++l) {
-    p.w_ih[l] = params + t->o_wih[l];
-    p.w_hh[l] = params + t->o_whh[l];
-    p.b_ih[l] = params + t->o_bih[l];
-    p.b_hh[l] = params + t->o_bhh[l];
-  }
-  p.act_w = params + t->o_act_w;
-  p.act_b = params + t->o_act_b;
-  p.cr_w = params + t->o_cr_w;
-  p.cr_b = params + t->o_cr_b;
-  PCHK(hipMalloc((void **)&t->whhT, (size_t)4 * Hd * Hd * sizeof(float)));
-  PCHK(hipMalloc((void **)&t->sq_part, SQ_BLOCKS * sizeof(double)));
+  for (size_t i = 0; i < tab.size(); ++i) *tab[i].slot = params + offs[i];
   PCHK(hipDeviceSynchronize());
   return PNVO_OK;
 }
@@ -780,12 +681,8 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = T * N;
-  {
-    const uintptr_t bytes = (uintptr_t)2 * L * N * Hd * sizeof(float);
-    const uintptr_t in0 = (uintptr_t)hidden_in, out0 = (uintptr_t)hidden_out;
-    if (in0 < out0 + bytes && out0 < in0 + bytes)
-      return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * N * hidden floats): pass separate buffers");
-  }
+  if (hidden_states_overlap(hidden_in, hidden_out, (size_t)2 * L * N * Hd))
+    return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * N * hidden floats): pass separate buffers");
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   int rc = ensure_ws(p, t, M);
@@ -805,8 +702,7 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   PCHK(mark(t, 1, s));
   const float *visual = pnvo_train_hidden(p.enc);
   if (!visual) return pfail(PNVO_ERR_STATE, "policy visual encoder kept no hidden vector");
-  hipLaunchKernelGGL(rollout_inputs_kernel, dim3((unsigned)(((long)M * K0 + 255) / 256)), dim3(256), 0, s, visual, goal, prev_actions,
-                     t->masks, p.tgt_w, p.tgt_b, p.emb, A + 1, M, Hd, t->x0, t->rows, t->g3);
+  PCHK(launch_policy_inputs(p, visual, goal, prev_actions, t->masks, M, t->x0, t->rows, t->g3, s));
   const float *xin = t->x0;
   int K = K0;
   for (int l = 0; l < L; ++l) {
@@ -868,7 +764,7 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
   PCHK(hipMemsetAsync(G, 0, t->n * sizeof(float), s));                 // overwrite semantics; a frozen encoder's range stays zero
   const float *feat = t->y[L - 1];
   hipLaunchKernelGGL(heads_bwd_w_kernel, dim3((unsigned)(((long)(A + 1) * Hd + 255) / 256)), dim3(256), 0, s, feat, t->dlogits, t->dvalue, M,
-                     Hd, A, G + t->o_act_w, G + t->o_act_b, G + t->o_cr_w, G + t->o_cr_b);
+                     Hd, A, grad_of(t, p.act_w), grad_of(t, p.act_b), grad_of(t, p.cr_w), grad_of(t, p.cr_b));
   hipLaunchKernelGGL(heads_bwd_x_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, t->dlogits, t->dvalue, p.act_w,
                      p.cr_w, M, Hd, A, t->dY);
   for (int l = L - 1; l >= 0; --l) {
@@ -886,18 +782,18 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
                          t->dG + r * 4 * Hd, t->dC + r * Hd);
     }
     // dW_ih = dG^T . X,  dW_hh = dG^T . (h_prev * mask),  db_ih = db_hh = colsum(dG),  dX = dG . W_ih
-    GemmArgs wi{t->dG, X, nullptr, nullptr, G + t->o_wih[l], 4 * Hd, K, M, 1, 4L * Hd, (long)K, 1, (long)K};
+    GemmArgs wi{t->dG, X, nullptr, nullptr, grad_of(t, p.w_ih[l]), 4 * Hd, K, M, 1, 4L * Hd, (long)K, 1, (long)K};
     PCHK((launch_gemm<false, false>(wi, s)));
-    GemmArgs wh{t->dG, t->hm[l], nullptr, nullptr, G + t->o_whh[l], 4 * Hd, Hd, M, 1, 4L * Hd, (long)Hd, 1, (long)Hd};
+    GemmArgs wh{t->dG, t->hm[l], nullptr, nullptr, grad_of(t, p.w_hh[l]), 4 * Hd, Hd, M, 1, 4L * Hd, (long)Hd, 1, (long)Hd};
     PCHK((launch_gemm<false, false>(wh, s)));
-    PCHK(launch_colsum(t->dG, M, 4 * Hd, 4 * Hd, G + t->o_bih[l], s));
-    PCHK(hipMemcpyAsync(G + t->o_bhh[l], G + t->o_bih[l], (size_t)4 * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PCHK(launch_colsum(t->dG, M, 4 * Hd, 4 * Hd, grad_of(t, p.b_ih[l]), s));
+    PCHK(hipMemcpyAsync(grad_of(t, p.b_hh[l]), grad_of(t, p.b_ih[l]), (size_t)4 * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
     GemmArgs dx{t->dG, p.w_ih[l], nullptr, nullptr, l == 0 ? t->dX0 : t->dY, M, K, 4 * Hd, 4L * Hd, 1, (long)K, 1, (long)K};
     PCHK((launch_gemm<true, false>(dx, s)));
   }
   // embeddings; d visual -> dY (contiguous [M, hidden]) -> the encoder's backward below its output head
   hipLaunchKernelGGL(inputs_bwd_kernel, dim3((unsigned)(((long)M * Hd + 128 + (long)(A + 1) * 32 + 255) / 256)), dim3(256), 0, s, t->dX0,
-                     t->rows, t->g3, M, Hd, A + 1, G + t->o_tgt_w, G + t->o_tgt_b, G + t->o_emb, t->dY);
+                     t->rows, t->g3, M, Hd, A + 1, grad_of(t, p.tgt_w), grad_of(t, p.tgt_b), grad_of(t, p.emb), t->dY);
   PCHK(hipGetLastError());
   PCHK(mark(t, 6, s));
   const int rc = pnvo_train_backward_from_hidden(p.enc, t->dY, train_encoder == 0, stream);

@@ -12,7 +12,6 @@ rollout forward, back-propagation through time and Adam on one flat buffer); a p
 import ctypes as C
 import math
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -186,17 +185,7 @@ class PointNavResNetPolicy(nn.Module):
             tensors = self._spec_tensors = [(n, sd[n]) for n, _ in self._spec]
         sig = tuple([(t.data_ptr(), t._version) for _, t in tensors])
         if sig != self._loaded_sig:
-            blob = np.ascontiguousarray(np.concatenate(
-                [t.detach().to("cpu", torch.float32).reshape(-1).numpy() for _, t in tensors]), dtype=np.float32)
-            toc = (_lib.pnvo_tensor_desc * len(tensors))()
-            off = 0
-            for i, (name, t) in enumerate(tensors):
-                toc[i].name = name.encode()
-                toc[i].offset = off
-                toc[i].ndim = t.dim()
-                for k, s in enumerate(t.shape):
-                    toc[i].shape[k] = int(s)
-                off += t.numel()
+            blob, toc = _lib.pack_tensors(tensors)
             _lib.check(_lib.lib.pnvo_policy_load_weights(self._handle, blob.ctypes.data_as(C.c_void_p), blob.size, toc,
                                                          len(tensors)))
             self._loaded_sig = sig

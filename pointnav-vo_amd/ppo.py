@@ -2,8 +2,9 @@
 
 The reference tunes the policy against the VO estimates with this update (configs/rl/ddppo_pointnav.yaml: TUNE_WITH_VO, train_encoder,
 num_steps 128, num_mini_batch 2, 2-layer LSTM).  `PolicyTrainStep` is to the policy what `VOTrainStep` (train.py) is to a VO model:
-it owns ONE flat parameter buffer and ONE flat gradient buffer on the device, makes the module's parameters views of them, and
-drives the C ABI —
+it holds one flat_params.FlatParams (`store`: ONE flat parameter buffer and ONE flat gradient buffer on the device, the module's
+parameters as views of them, Adam's moments and state dict; `flat`, `grad`, `exp_avg`, `exp_avg_sq`, `offsets` are the store's own
+objects) and drives the C ABI —
 
     pnvo_policy_evaluate     rollout forward (encoder in train mode, LSTM over T x N with mask resets), activations kept
     pnvo_policy_ppo_loss     clipped surrogate / value loss / entropy and their gradient at the heads, from a kernel
@@ -27,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat_params import FlatParams, flat_offsets  # noqa: F401  (flat_offsets: the layout rule, public here too)
 from .policy import GOAL_SENSOR
 
 EPS_PPO = 1e-5
@@ -35,19 +37,6 @@ ENCODER_PREFIX = "net.visual_encoder."
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def flat_offsets(spec):
-    """Layout of the flat buffers: (name, shape) in named_parameters() order -> ({name: (offset, numel)}, floats used).  Every tensor
-    starts at a multiple of 4 floats (the kernels read weight rows as 16-byte vectors); the gaps hold zeros."""
-    offsets, off = {}, 0
-    for name, shape in spec:
-        n = 1
-        for s in shape:
-            n *= int(s)
-        offsets[name] = (off, n)
-        off = (off + n + 3) // 4 * 4
-    return offsets, off
 
 
 class _AdamView:
@@ -81,106 +70,60 @@ class PolicyTrainStep:
         self.dev = ref.device
         policy._ensure(self.dev)                                # handle + kernel operand buffers
         h = policy._handle
-        named = [(n, p) for n, p in policy.named_parameters()]
-        self.offsets, used = flat_offsets([(n, tuple(p.shape)) for n, p in named])
-        tail = int(_lib.lib.pnvo_policy_train_tail_floats(h))
-        self.n_params = used
-        self.flat = torch.zeros(used + tail, device=self.dev, dtype=torch.float32)
-        self.grad = torch.zeros(used + tail, device=self.dev, dtype=torch.float32)
-        self.exp_avg = torch.zeros(used, device=self.dev, dtype=torch.float32)
-        self.exp_avg_sq = torch.zeros(used, device=self.dev, dtype=torch.float32)
-        toc = (_lib.pnvo_tensor_desc * len(named))()
-        with torch.no_grad():
-            for i, (n, p) in enumerate(named):
-                off, k = self.offsets[n]
-                self.flat[off:off + k].copy_(p.detach().reshape(-1))
-                p.data = self.flat[off:off + k].view(p.shape)    # the module's parameters alias the flat buffer
-                p.grad = self.grad[off:off + k].view(p.shape)
-                toc[i].name = n.encode()
-                toc[i].offset = off
-                toc[i].ndim = p.dim()
-                for d, sz in enumerate(p.shape):
-                    toc[i].shape[d] = int(sz)
-        self._toc, self._named = toc, named
-        enc = [self.offsets[n] for n, _ in named if n.startswith(ENCODER_PREFIX)]
+        # every tensor at a multiple of 4 floats (flat_offsets); the tail holds the encoder handle's padded stem and unused head
+        self.store = FlatParams(list(policy.named_parameters()), self.dev, align=4,
+                                tail=int(_lib.lib.pnvo_policy_train_tail_floats(h)))
+        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (self.store.flat, self.store.grad, self.store.exp_avg,
+                                                               self.store.exp_avg_sq)
+        self.offsets, self.n_params = self.store.offsets, self.store.n_params
+        enc = [self.offsets[n] for n, _ in self.store.named if n.startswith(ENCODER_PREFIX)]
         self.encoder_range = (min(o for o, _ in enc), max(o + k for o, k in enc))
         torch.cuda.synchronize(self.dev)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_policy_train_attach(h, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), toc, len(named)))
+            _lib.check(_lib.lib.pnvo_policy_train_attach(h, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), self.store.toc,
+                                                         len(self.store.named)))
         self.step_count = 0
         self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
         self._norm = torch.zeros(1, device=self.dev, dtype=torch.float32)
-        self._psig = self._param_sig()
         policy._train_step = self                               # evaluate_actions delegates here; act reads the flat buffer
 
     # ------------------------------------------------------------------ parameter / optimizer state
     def _trainable(self):
-        return [(n, p) for n, p in self._named if self.train_encoder or not n.startswith(ENCODER_PREFIX)]
+        return [n for n, _ in self.store.named if self.train_encoder or not n.startswith(ENCODER_PREFIX)]
 
     def _ranges(self):
-        """Flat ranges the optimiser steps over: everything, or everything but net.visual_encoder (the reference's _static_encoder)."""
+        """Flat ranges the optimiser steps over: everything, or everything but net.visual_encoder (the reference's _static_encoder).
+        They end with the last parameter, not at n_params: the library's tail starts right behind the last parameter, inside the final
+        alignment gap, and a copy the refresh rewrites must not collect Adam moments that no checkpoint carries."""
+        end = max(o + k for o, k in self.offsets.values())
         if self.train_encoder:
-            return [(0, self.n_params)]
+            return [(0, end)]
         lo, hi = self.encoder_range
-        return [(a, b) for a, b in ((0, lo), (hi, self.n_params)) if b > a]
-
-    def _param_sig(self):
-        return tuple((p.data_ptr(), p._version) for _, p in self._named)
+        return [(a, b) for a, b in ((0, lo), (hi, end)) if b > a]
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _sync_params(self):
         """Parameters edited outside the HIP Adam step (load_state_dict on resume, an in-place torch edit) land in the flat buffer but
-        not in the encoder's packed operands: re-alias what was re-pointed and re-pack (as VOTrainStep._sync_params)."""
-        sig = self._param_sig()
-        if sig == self._psig:
+        not in the encoder's packed operands: re-alias what was re-pointed and re-pack."""
+        if not self.store.changed():
             return
-        with torch.no_grad():
-            for n, p in self._named:
-                off, k = self.offsets[n]
-                view = self.flat[off:off + k].view(p.shape)
-                if p.data_ptr() != view.data_ptr():
-                    view.copy_(p.detach())
-                    p.data = view
-                    p.grad = self.grad[off:off + k].view(p.shape)
+        self.store.realias()
         with torch.cuda.device(self.dev):
-            for _ in range(3):          # the encoder's GroupNorm range guard reads the bounds two refreshes back (train.py)
+            for _ in range(3):                                 # three: flat_params.py, "The owner's part"
                 _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, self._stream()))
         torch.cuda.current_stream(self.dev).synchronize()
-        self._psig = self._param_sig()
+        self.store.mark()
 
     def state_dict(self):
         """Optimizer state in torch.optim.Adam's layout over the trainable parameters, in order (what the reference's
         optim.Adam(filter(requires_grad, actor_critic.parameters())) checkpoints)."""
-        state = {}
-        for i, (n, p) in enumerate(self._trainable()):
-            off, k = self.offsets[n]
-            state[i] = {"step": torch.tensor(float(self.step_count)),
-                        "exp_avg": self.exp_avg[off:off + k].view(p.shape).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[off:off + k].view(p.shape).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "params": list(range(len(state)))}
-        return {"state": state, "param_groups": [group]}
+        return self.store.adam_state_dict(self._trainable(), self.step_count, self.lr, self.betas, self.eps)
 
     def load_state_dict(self, sd):
-        group = sd["param_groups"][0]
+        self.step_count, group = self.store.load_adam_state_dict(sd, self._trainable())
         self.lr, self.eps, self.betas = float(group["lr"]), float(group["eps"]), tuple(group["betas"])
-        steps = set()
-        with torch.no_grad():
-            for i, (n, p) in enumerate(self._trainable()):
-                off, k = self.offsets[n]
-                st = sd["state"].get(i)
-                if st is None:
-                    self.exp_avg[off:off + k].zero_()
-                    self.exp_avg_sq[off:off + k].zero_()
-                else:
-                    self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                    self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-                    steps.add(int(st["step"]))
-        if len(steps) > 1:
-            raise ValueError("per-parameter Adam step counts differ; the HIP Adam keeps one step count for the policy")
-        self.step_count = steps.pop() if steps else 0
 
     # ------------------------------------------------------------------ the update, piece by piece
     def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
@@ -256,11 +199,7 @@ class PolicyTrainStep:
         self.step_count += 1
         with torch.cuda.device(self.dev):
             stream = self._stream()
-            for a, b in self._ranges():
-                _lib.check(_lib.lib.pnvo_adam_step(C.c_void_p(self.flat.data_ptr() + 4 * a), C.c_void_p(self.grad.data_ptr() + 4 * a),
-                                                   C.c_void_p(self.exp_avg.data_ptr() + 4 * a),
-                                                   C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * a), b - a, self.lr, self.betas[0],
-                                                   self.betas[1], self.eps, self.step_count, stream))
+            self.store.adam_step(self._ranges(), self.lr, self.betas, self.eps, self.step_count, stream)
             _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, stream))
 
 

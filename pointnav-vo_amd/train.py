@@ -7,8 +7,9 @@ Mirrors, for one action model, the body of the reference's training iteration
     loss = sum_d mean((gt_d - pred_d)^2)                     (vo_cnn_engine.py:135-198, loss_weight_fixed)
     loss.backward(); optimizer.step()                        (Adam lr 2.5e-4, eps 1e-8, wd 0: :122-133)
 
-Forward, backward, loss and Adam are HIP kernels behind the C ABI (pnvo_train_*); this class only owns the flat
-device buffers and performs the collectives the reference semantics call for when torch.distributed is initialised:
+Forward, backward, loss and Adam are HIP kernels behind the C ABI (pnvo_train_*); this class only holds the flat
+device buffers (one flat_params.FlatParams, `store`, in the tight layout; `flat`, `grad`, `exp_avg`, `exp_avg_sq`, `offsets` are the
+store's own objects) and performs the collectives the reference semantics call for when torch.distributed is initialised:
 RunningMeanAndVar's all-reduces (running_mean_and_var.py:27-38; batch sum and count travel as one buffer, the variance
 needs the global mean and is the second round) and the all-reduce of the flat gradient buffer (RCCL over xGMI on the GPU box;
 15.85 MB for the default model, in three buckets that start while the backward is still running: pnvo_train_set_grad_hook).  Dropout (the reference trains with p = 0.2 before both
@@ -22,6 +23,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, parallel
+from .flat_params import FlatParams
 
 
 def ms_feature_hw(cfg):
@@ -46,33 +48,13 @@ class VOTrainStep:
         self.dev = ref.device
         model._ensure_handle(self.dev)
         model._sync_weights()                                   # allocates the kernel operand buffers
-        named = [(n, p) for n, p in model.named_parameters()]
-        total = sum(p.numel() for _, p in named)
-        self.flat = torch.empty(total, device=self.dev, dtype=torch.float32)
-        self.grad = torch.zeros(total, device=self.dev, dtype=torch.float32)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
-        toc = (_lib.pnvo_tensor_desc * len(named))()
-        off = 0
-        self.offsets = {}
-        with torch.no_grad():
-            for i, (n, p) in enumerate(named):
-                k = p.numel()
-                self.flat[off:off + k].copy_(p.detach().reshape(-1))
-                p.data = self.flat[off:off + k].view(p.shape)    # the module's parameters alias the flat buffer
-                p.grad = self.grad[off:off + k].view(p.shape)
-                toc[i].name = n.encode()
-                toc[i].offset = off
-                toc[i].ndim = p.dim()
-                for d, sz in enumerate(p.shape):
-                    toc[i].shape[d] = int(sz)
-                self.offsets[n] = (off, k)
-                off += k
-        self._toc = toc
-        self._named = named
+        self.store = FlatParams(list(model.named_parameters()), self.dev)       # tight layout: the gradient buckets count on it
+        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (self.store.flat, self.store.grad, self.store.exp_avg,
+                                                               self.store.exp_avg_sq)
+        self.offsets, self.n_params = self.store.offsets, self.store.n_params
         model._loaded_sig = None          # p.data now aliases the flat buffer: the eval path re-reads it on its next call
-        _lib.check(_lib.lib.pnvo_train_attach(model._handle, _ptr(self.flat), _ptr(self.grad), total, toc, len(named)),
-                   model._handle)
+        _lib.check(_lib.lib.pnvo_train_attach(model._handle, _ptr(self.flat), _ptr(self.grad), self.n_params, self.store.toc,
+                                              len(self.store.named)), model._handle)
         self.dropout_p = float(getattr(model, "dropout_p", 0.0) or 0.0)
         _lib.check(_lib.lib.pnvo_train_set_dropout(model._handle, C.c_float(self.dropout_p), C.c_uint64(int(dropout_seed))),
                    model._handle)
@@ -82,7 +64,6 @@ class VOTrainStep:
         Cc = model.cfg.in_channels
         self._m12 = torch.empty(2 * Cc, device=self.dev)
         self._loss = torch.zeros(1, device=self.dev)
-        self._psig = self._param_sig()
         # data parallel: the gradient all-reduce travels in buckets that start while the backward is still running
         # (pnvo_train_set_grad_hook; layer4..head first — 80 % of the bytes — then layer2-3, then stem + layer1);
         # bucketed = False: ONE flat all-reduce after the backward (bench.py --no-overlap, the A/B of the two schedules)
@@ -93,67 +74,29 @@ class VOTrainStep:
         _lib.check(_lib.lib.pnvo_train_set_grad_hook(model._handle, C.cast(self._hook, C.c_void_p), None), model._handle)
 
     # ------------------------------------------------------------------ parameter / optimizer state
-    def _param_sig(self):
-        return tuple((p.data_ptr(), p._version) for _, p in self._named)
-
     def _sync_params(self, stream):
         """Parameters edited outside the HIP Adam step (model.load_state_dict on resume, an in-place torch edit) land in
         the flat buffer but not in the packed kernel operands: re-pack before the next train-mode forward."""
-        sig = self._param_sig()
-        if sig == self._psig:
+        if not self.store.changed():
             return
-        off = 0
-        with torch.no_grad():
-            for _, p in self._named:                      # a tensor re-pointed by the caller: alias it again
-                k = p.numel()
-                view = self.flat[off:off + k].view(p.shape)
-                if p.data_ptr() != view.data_ptr():
-                    view.copy_(p.detach())
-                    p.data = view
-                    p.grad = self.grad[off:off + k].view(p.shape)
-                off += k
-        # an outside edit can move a GroupNorm weight by any amount: the float16-piece range guard must be current NOW.  The forward
-        # reads the bounds of the parameters TWO refreshes back (a fixed lag — fine for Adam's lr-sized steps, and the same on every
-        # run and rank): three refreshes fill that ring with the edited parameters' bounds
-        for _ in range(3):
+        self.store.realias()
+        for _ in range(3):                                     # three: flat_params.py, "The owner's part"
             _lib.check(_lib.lib.pnvo_train_refresh(self.model._handle, stream), self.model._handle)
         torch.cuda.current_stream(self.dev).synchronize()
         self.model._loaded_sig = None
-        self._psig = self._param_sig()
+        self.store.mark()
+
+    def _names(self):
+        return [n for n, _ in self.store.named]
 
     def state_dict(self):
         """Optimizer state in torch.optim.Adam's layout (the reference checkpoints `optim_states`,
         vo_cnn_regression_geo_invariance_engine.py:1425-1433): per-parameter step / exp_avg / exp_avg_sq."""
-        state, off = {}, 0
-        for i, (_, p) in enumerate(self._named):
-            k = p.numel()
-            state[i] = {"step": torch.tensor(float(self.step_count)),
-                        "exp_avg": self.exp_avg[off:off + k].view(p.shape).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[off:off + k].view(p.shape).clone()}
-            off += k
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "params": list(range(len(self._named)))}
-        return {"state": state, "param_groups": [group]}
+        return self.store.adam_state_dict(self._names(), self.step_count, self.lr, self.betas, self.eps)
 
     def load_state_dict(self, sd):
-        group = sd["param_groups"][0]
+        self.step_count, group = self.store.load_adam_state_dict(sd, self._names())
         self.lr, self.eps, self.betas = float(group["lr"]), float(group["eps"]), tuple(group["betas"])
-        off, steps = 0, set()
-        with torch.no_grad():
-            for i, (_, p) in enumerate(self._named):
-                k = p.numel()
-                st = sd["state"].get(i)
-                if st is None:
-                    self.exp_avg[off:off + k].zero_()
-                    self.exp_avg_sq[off:off + k].zero_()
-                else:
-                    self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                    self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-                    steps.add(int(st["step"]))
-                off += k
-        if len(steps) > 1:
-            raise ValueError("per-parameter Adam step counts differ; the HIP Adam keeps one step count for the model")
-        self.step_count = steps.pop() if steps else 0
 
     def dropout_masks(self, batch):
         """Scaled masks (0 or 1/(1-p)) of the last forward: (m0 [B, fh*fw, Cpad] in the kernel's NHWC order with the
@@ -386,9 +329,7 @@ class VOTrainStep:
         self.step_count += 1
         with torch.cuda.device(self.dev):
             stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            _lib.check(_lib.lib.pnvo_adam_step(_ptr(self.flat), _ptr(self.grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
-                                               self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                               self.step_count, stream))
+            self.store.adam_step([(0, self.n_params)], self.lr, self.betas, self.eps, self.step_count, stream)
             _lib.check(_lib.lib.pnvo_train_refresh(h, stream), h)
         self.model._loaded_sig = None     # operands only the eval path owns are rebuilt from the flat buffer on its next call
 

@@ -12,7 +12,6 @@ a CUDA(ROCm) device, or whose HIP extension is missing, raises.
 import ctypes as C
 import math
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -194,17 +193,7 @@ class VisualOdometryCNNBase(nn.Module):
         sig = tuple([(t.data_ptr(), t._version) for _, t in tensors])
         if sig == self._loaded_sig:
             return
-        blob = np.concatenate([t.detach().to("cpu", torch.float32).reshape(-1).numpy() for _, t in tensors])
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        toc = (_lib.pnvo_tensor_desc * len(tensors))()
-        off = 0
-        for i, (name, t) in enumerate(tensors):
-            toc[i].name = name.encode()
-            toc[i].offset = off
-            toc[i].ndim = t.dim()
-            for k, s in enumerate(t.shape):
-                toc[i].shape[k] = int(s)
-            off += t.numel()
+        blob, toc = _lib.pack_tensors(tensors)
         _lib.check(_lib.lib.pnvo_load_weights(self._handle, blob.ctypes.data_as(C.c_void_p), blob.size, toc,
                                               len(tensors)), self._handle)
         self._loaded_sig = sig

@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import ppo_reference as R
+from pointnav_vo_amd import synth
 from pointnav_vo_amd.policy import PointNavResNetPolicy
 from pointnav_vo_amd.ppo import PPO, PolicyTrainStep
 
@@ -321,7 +322,59 @@ def test_ppo_update_matches_fp64_and_reduces_the_loss():
     assert agent.train_step.step_count == 4
 
 
-# ------------------------------------------------------------------------------------------------------------------ 6. unattached
+# ------------------------------------------------------------------------------------------------------------------ 6. resume
+def small_minibatch(iseed):
+    """T = 3, N = 2 on case A's policy: the first three steps of the first two environments of its rollout (resets at t = 0 and t = 2,
+    a non-zero initial state), with loss inputs of both signs."""
+    inp = R.rollout("A", iseed)
+    T, N, M = 3, 2, 6
+    rows = np.array([t * inp["N"] + n for t in range(T) for n in range(N)])
+    mb = dict({k: np.ascontiguousarray(inp[k][rows]) for k in ("depth", "goal", "prev", "masks", "actions")},
+              hidden=np.ascontiguousarray(inp["hidden"][:, :N]), T=T, N=N)
+    seed = 1000 * (iseed or 0) + 7
+    u = lambda tag, lo, hi: synth.uniform(seed, tag, (M,), lo, hi).astype(np.float32)
+    vp, adv = u("vp", -0.5, 0.5), u("adv", -1.0, 1.0)
+    return mb, dict(old=u("old", -1.8, -1.0), vp=vp, adv=adv, ret=vp + adv)
+
+
+def test_policy_and_optimizer_loaded_after_attach_resume_bit_equal():
+    """What test_parameters_loaded_after_attach_are_used_by_the_next_training_forward (test_gpu_fullsize.py) checks for VOTrainStep, for
+    the policy: policy.load_state_dict() and train_step.load_state_dict() AFTER a fresh PolicyTrainStep was attached must reach the
+    kernels (flat buffer, the encoder's packed operands, Adam's moments and step count).  Every reduction of the update has a fixed
+    order, so the resumed run is bit-equal to the one that never stopped."""
+    def update(step, mb):
+        run_update(step, *mb)
+        step.clip_grad_norm()
+        step.optimizer_step()
+
+    first, second = small_minibatch(None), small_minibatch(41)
+    pol_a = make_policy("A")
+    step_a = PolicyTrainStep(pol_a, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM)
+    update(step_a, first)
+    ckpt_policy = {k: v.detach().cpu().clone() for k, v in pol_a.state_dict().items()}
+    ckpt_optim = step_a.state_dict()
+    pol_b = make_policy("A")                                      # the initial weights again
+    step_b = PolicyTrainStep(pol_b, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM)
+    assert not torch.equal(step_b.flat, step_a.flat)
+    pol_b.load_state_dict(ckpt_policy)                            # lands in the flat buffer, AFTER the attach
+    step_b.load_state_dict(ckpt_optim)
+    update(step_a, second)
+    update(step_b, second)
+    torch.cuda.synchronize()
+    assert step_a.step_count == step_b.step_count == 2
+    n = step_a.n_params
+    assert torch.equal(step_b.flat[:n], step_a.flat[:n])
+    assert torch.equal(step_b.exp_avg, step_a.exp_avg) and torch.equal(step_b.exp_avg_sq, step_a.exp_avg_sq)
+    assert step_a.exp_avg.any() and step_a.exp_avg_sq.any()
+    one = dict(second[0], **{k: second[0][k][:2] for k in ("depth", "goal", "prev", "masks", "actions")}, T=1)
+    obs, hidden, prev, masks, _ = to_gpu(one)
+    la = pol_a.features_and_logits(obs, hidden, prev, masks)[2]
+    lb = pol_b.features_and_logits(obs, hidden, prev, masks)[2]
+    torch.cuda.synchronize()
+    assert torch.isfinite(la).all() and torch.equal(la, lb)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. unattached
 def test_unattached_policy_still_refuses_evaluate_actions():
     pol = make_policy("A")
     obs, hidden, prev, masks, actions = to_gpu(R.rollout("A"))
