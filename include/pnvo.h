@@ -356,14 +356,18 @@ int pnvo_destroy(pnvo_handle h);
 
 /* ---- the navigation policy's per-step forward: PointNavResNetPolicy.act
  * (pointnav_vo/rl/policies/policy.py:29-46, resnet_policy.py:26-58 and 177-282) for the depth-only configuration of
- * configs/rl/ddppo_pointnav.yaml (resnet18 backbone, 2-layer LSTM, normalize_visual_inputs False, no obs transform). ---- */
+ * configs/rl/ddppo_pointnav.yaml (resnet18 backbone, 2-layer LSTM, normalize_visual_inputs False, no obs transform); the recurrent
+ * core is torch.nn.LSTM or torch.nn.GRU (RL.Policy.rnn_backbone, model_utils/rnns/rnn_state_encoder.py:28). ---- */
+#define PNVO_RNN_LSTM 0
+#define PNVO_RNN_GRU 1
 typedef struct {
   int32_t width, height;      /* depth frame W, H (341, 192); the encoder sees (W/2, H/2) after avg_pool2d(2) */
   int32_t baseplanes;         /* resnet_baseplanes (32) */
   int32_t hidden;             /* hidden_size (512) */
   int32_t n_actions;          /* action_space.n (4) */
-  int32_t rnn_layers;         /* num_recurrent_layers (2, LSTM) */
+  int32_t rnn_layers;         /* num_recurrent_layers (2) */
   int32_t flat_size;          /* after_compression_flat_size (2048) */
+  int32_t rnn_type;           /* PNVO_RNN_LSTM (0: a zeroed field keeps the LSTM) or PNVO_RNN_GRU (1); anything else is refused */
 } pnvo_policy_config;
 
 typedef struct pnvo_policy_s *pnvo_policy_handle;
@@ -380,10 +384,11 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
 /* features, rnn_hidden_states = net(observations, rnn_hidden_states, prev_actions, masks); logits / value of the two
  * heads (policy.py:32-36).  All pointers are DEVICE memory:
  *   depth [B,H,W,1] in 0..1 (observations["depth"]);  goal [B,2] = pointgoal_with_gps_compass (rho, phi);
- *   prev_actions [B] int64;  masks [B] (0 at an episode start);  hidden_in / hidden_out [2*rnn_layers, B, hidden]
- *   (h of every layer, then c of every layer: rnn_state_encoder.py:47-61);  features [B,hidden], logits [B,n_actions],
- *   value [B] may each be NULL.  Sampling / argmax over the logits stays with the caller (policy.py:38-43).
- *   hidden_in and hidden_out must not overlap (the LSTM writes a layer's state while other workgroups still read it):
+ *   prev_actions [B] int64;  masks [B] (0 at an episode start);  hidden_in / hidden_out [S, B, hidden] with S = 2*rnn_layers for
+ *   the LSTM (h of every layer, then c of every layer: rnn_state_encoder.py:47-61) and S = rnn_layers for the GRU (h only);
+ *   features [B,hidden], logits [B,n_actions], value [B] may each be NULL.  Sampling / argmax over the logits stays with the
+ *   caller (policy.py:38-43).
+ *   hidden_in and hidden_out must not overlap (a layer's kernel writes its state while other workgroups still read it):
  *   overlapping ranges are refused with PNVO_ERR_ARG before anything is launched. */
 int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions,
                     const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
@@ -412,7 +417,8 @@ int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream);
 
 /* value, action_log_probs, entropy, rnn_hidden_states = evaluate_actions(...) with everything the backward needs kept in the
  * handle.  depth [M,H,W,1], goal [M,2], prev_actions [M] int64, masks [M], actions [M] int64; hidden_in / hidden_out
- * [2*rnn_layers, N, hidden] (must not overlap); value [M], logp [M] = log pi(action), entropy [1] = mean row entropy may each be NULL.
+ * [S, N, hidden], S = 2*rnn_layers (LSTM) or rnn_layers (GRU), as pnvo_policy_act (must not overlap); value [M], logp [M] =
+ * log pi(action), entropy [1] = mean row entropy may each be NULL.
  * The hidden state is masked at every step (equal to the reference's segment-wise masking).  M = N (T = 1) is the reference's
  * single_forward case.  Workspaces grow on demand: a call with a larger M than any before allocates, later ones do not.
  * train_encoder is accepted for symmetry with pnvo_policy_backward; the forward keeps the same activations either way. */
@@ -439,8 +445,8 @@ int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm
 
 /* Phase timing of the update step with HIP events recorded on the launch stream (tools/bench_ppo_update.py; not part of the drop-in
  * surface).  mode 0 = off, 1 = on.  pnvo_policy_train_timing_read waits for the last pnvo_policy_backward and returns the
- * milliseconds of the last evaluate / ppo_loss / backward: {encoder forward, LSTM forward + heads, loss, heads + BPTT + embedding
- * backward, encoder backward}. */
+ * milliseconds of the last evaluate / ppo_loss / backward: {encoder forward, LSTM or GRU forward + heads, loss, heads + BPTT +
+ * embedding backward, encoder backward}. */
 int pnvo_policy_train_timing(pnvo_policy_handle h, int mode);
 int pnvo_policy_train_timing_read(pnvo_policy_handle h, double ms[5]);
 

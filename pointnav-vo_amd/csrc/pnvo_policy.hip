@@ -4,7 +4,7 @@
 //   depth [B,H,W,1] -> avg_pool2d(2) -> GroupNorm-ResNet18 (baseplanes 32) -> compression conv + GN(1) + ReLU
 //   -> Flatten + Linear + ReLU (visual_fc)                              | the VO path's kernels, via a pnvo handle
 //   x = [visual (hidden) | tgt_embeding([rho, cos(-phi), sin(-phi)]) (32) | prev_action_embedding (32)]
-//   -> 2-layer LSTM with the hidden state masked at episode starts (model_utils/rnns/rnn_state_encoder.py:63-79)
+//   -> 2-layer LSTM, or GRU (cfg.rnn_type), with the hidden state masked at episode starts (model_utils/rnns/rnn_state_encoder.py:63-79)
 //   -> action logits (CategoricalNet, utils/misc_utils.py:67-78) and value (CriticHead, policy.py:66-74).
 // The visual encoder is the SAME kernel set as the VO model: a pnvo handle configured with (W/2, H/2), one depth
 // modality of 2 channels [pooled depth | 0] and no whitening (normalize_visual_inputs is False for the depth-only policy,
@@ -127,6 +127,67 @@ __global__ __launch_bounds__(256) void lstm_layer_kernel(const float *x, int K, 
       const float c = f_ * (c_prev[e] * masks[b]) + i_ * g_;
       c_out[e] = c;
       h_out[e] = o_ * tanhf(c);
+    }
+    __syncthreads();
+  }
+}
+
+// One GRU layer in one launch, in lstm_layer_kernel's shape: workgroup = hidden unit j, wave = gate (r, z, n; torch.nn.GRU's order),
+// W in torch's [3H][K] layout.  With hm = h_prev * mask:
+//   r = sigmoid((hm . W_hr + b_hr) + (x . W_ir + b_ir)),  z likewise,  q = hm . W_hn + b_hn,  n = tanh((x . W_in + b_in) + r * q),
+//   h' = (1 - z) * n + z * hm.
+// b_hn sits inside the product with r, so the n-wave keeps its input sum and its recurrent sum apart (sg[2] / sq) until r is known.
+__global__ __launch_bounds__(192) void gru_layer_kernel(const float *x, int K, const float *w_ih, const float *b_ih, const float *h_prev,
+                                                      const float *w_hh, const float *b_hh, const float *masks, int B, int Hd,
+                                                      float *h_out) {
+  __shared__ float sg[3][64], sq[64];
+  const int lane = threadIdx.x & 63, gate = (int)(threadIdx.x >> 6), j = blockIdx.x;
+  const int n = gate * Hd + j;
+  const f32x4 *wi = reinterpret_cast<const f32x4 *>(w_ih + (long)n * K), *wh = reinterpret_cast<const f32x4 *>(w_hh + (long)n * Hd);
+  const int K4 = K >> 2, H4 = Hd >> 2;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int nb = min(64, B - b0);
+    for (int bb = 0; bb < nb; ++bb) {
+      const int b = b0 + bb;
+      const f32x4 *xr = reinterpret_cast<const f32x4 *>(x + (long)b * K), *hr = reinterpret_cast<const f32x4 *>(h_prev + (long)b * Hd);
+      float s = 0.f, u = 0.f;
+      for (int k = lane; k < K4; k += 64) {
+        const f32x4 w = wi[k], v = xr[k];
+        s = __builtin_fmaf(w[0], v[0], s);
+        s = __builtin_fmaf(w[1], v[1], s);
+        s = __builtin_fmaf(w[2], v[2], s);
+        s = __builtin_fmaf(w[3], v[3], s);
+      }
+      for (int k = lane; k < H4; k += 64) {
+        const f32x4 w = wh[k], v = hr[k];
+        u = __builtin_fmaf(w[0], v[0], u);
+        u = __builtin_fmaf(w[1], v[1], u);
+        u = __builtin_fmaf(w[2], v[2], u);
+        u = __builtin_fmaf(w[3], v[3], u);
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        s += __shfl_xor(s, o);
+        u += __shfl_xor(u, o);
+      }
+      if (lane == 0) {
+        const float rec = u * masks[b] + b_hh[n], in = s + b_ih[n];
+        if (gate == 2) {
+          sg[2][bb] = in;
+          sq[bb] = rec;
+        } else {
+          sg[gate][bb] = rec + in;
+        }
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+      const int b = b0 + (int)threadIdx.x;
+      const long e = (long)b * Hd + j;
+      const float r_ = 1.f / (1.f + expf(-sg[0][threadIdx.x]));
+      const float z_ = 1.f / (1.f + expf(-sg[1][threadIdx.x]));
+      const float n_ = tanhf(sg[2][threadIdx.x] + r_ * sq[threadIdx.x]);
+      h_out[e] = (1.f - z_) * n_ + z_ * (h_prev[e] * masks[b]);
     }
     __syncthreads();
   }
@@ -256,13 +317,15 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
   if (cfg->width < 64 || cfg->height < 64)
     return pfail(PNVO_ERR_ARG, "unsupported policy observation size " + std::to_string(cfg->width) + "x" + std::to_string(cfg->height) +
                                    " (width and height must be >= 64)");
-  // the visual encoder's visual_fc takes hidden sizes in multiples of 8 (pnvo_create); the LSTM's rows are read as float4
+  // the visual encoder's visual_fc takes hidden sizes in multiples of 8 (pnvo_create); the recurrent weights' rows are read as float4
   if (cfg->hidden <= 0 || cfg->hidden % 8 != 0)
     return pfail(PNVO_ERR_ARG, "unsupported policy hidden_size " + std::to_string(cfg->hidden) + " (must be a positive multiple of 8)");
   if (cfg->rnn_layers < 1 || cfg->rnn_layers > 4)
     return pfail(PNVO_ERR_ARG, "unsupported policy num_recurrent_layers " + std::to_string(cfg->rnn_layers) + " (1 to 4)");
   if (cfg->n_actions < 1 || cfg->n_actions > 32)
     return pfail(PNVO_ERR_ARG, "unsupported policy action_space.n " + std::to_string(cfg->n_actions) + " (1 to 32)");
+  if (cfg->rnn_type != PNVO_RNN_LSTM && cfg->rnn_type != PNVO_RNN_GRU)
+    return pfail(PNVO_ERR_ARG, "unsupported policy rnn_type " + std::to_string(cfg->rnn_type) + " (0 = LSTM, 1 = GRU)");
   pnvo_policy_s *h = new pnvo_policy_s();
   h->p.cfg = *cfg;
   h->p.device = device;
@@ -339,8 +402,10 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
     return pfail(PNVO_ERR_ARG, "null argument / bad batch");
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
-  if (hidden_states_overlap(hidden_in, hidden_out, (size_t)2 * L * B * Hd))
-    return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * B * hidden floats): pass separate buffers");
+  const bool gru = is_gru(c);
+  if (hidden_states_overlap(hidden_in, hidden_out, rnn_state_floats(c, B)))
+    return pfail(PNVO_ERR_ARG, std::string("hidden_out overlaps hidden_in (each holds ") + (gru ? "" : "2 * ") +
+                                   "rnn_layers * B * hidden floats): pass separate buffers");
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   if (B > p.cap) {
@@ -357,16 +422,26 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
   rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   PCHK(launch_policy_inputs(p, p.visual, goal, prev_actions, masks, B, p.x, nullptr, nullptr, s));
-  // hidden_in / hidden_out: [2L, B, Hd] = (h_0 .. h_{L-1}, c_0 .. c_{L-1})  (rnn_state_encoder.py:47-61)
+  // hidden_in / hidden_out: LSTM [2L, B, Hd] = (h_0 .. h_{L-1}, c_0 .. c_{L-1}), GRU [L, B, Hd] = (h_0 .. h_{L-1})  (rnn_state_encoder.py:43-61)
   const float *xin = p.x;
   int K = K0;
-  for (int l = 0; l < L; ++l) {
-    const float *h_prev = hidden_in + (size_t)l * B * Hd, *c_prev = hidden_in + (size_t)(L + l) * B * Hd;
-    float *h_new = hidden_out + (size_t)l * B * Hd, *c_new = hidden_out + (size_t)(L + l) * B * Hd;
-    hipLaunchKernelGGL(lstm_layer_kernel, dim3((unsigned)Hd), dim3(256), 0, s, xin, K, p.w_ih[l], p.b_ih[l], h_prev, p.w_hh[l], p.b_hh[l],
-                       c_prev, masks, B, Hd, h_new, c_new);
-    xin = h_new;
-    K = Hd;
+  if (gru) {
+    for (int l = 0; l < L; ++l) {
+      float *h_new = hidden_out + (size_t)l * B * Hd;
+      hipLaunchKernelGGL(gru_layer_kernel, dim3((unsigned)Hd), dim3(192), 0, s, xin, K, p.w_ih[l], p.b_ih[l], hidden_in + (size_t)l * B * Hd,
+                         p.w_hh[l], p.b_hh[l], masks, B, Hd, h_new);
+      xin = h_new;
+      K = Hd;
+    }
+  } else {
+    for (int l = 0; l < L; ++l) {
+      const float *h_prev = hidden_in + (size_t)l * B * Hd, *c_prev = hidden_in + (size_t)(L + l) * B * Hd;
+      float *h_new = hidden_out + (size_t)l * B * Hd, *c_new = hidden_out + (size_t)(L + l) * B * Hd;
+      hipLaunchKernelGGL(lstm_layer_kernel, dim3((unsigned)Hd), dim3(256), 0, s, xin, K, p.w_ih[l], p.b_ih[l], h_prev, p.w_hh[l], p.b_hh[l],
+                         c_prev, masks, B, Hd, h_new, c_new);
+      xin = h_new;
+      K = Hd;
+    }
   }
   const float *feat = hidden_out + (size_t)(L - 1) * B * Hd;
   if (features) PCHK(hipMemcpyAsync(features, feat, (size_t)B * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));

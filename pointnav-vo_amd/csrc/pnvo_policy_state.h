@@ -20,7 +20,7 @@ struct Policy {
   // device weights (torch layouts), listed once in policy_params(): owned copies, or — once a train step is attached — pointers into
   // the caller's flat buffer
   float *emb = nullptr, *tgt_w = nullptr, *tgt_b = nullptr;
-  std::vector<float *> w_ih, w_hh, b_ih, b_hh;       // one per LSTM layer
+  std::vector<float *> w_ih, w_hh, b_ih, b_hh;       // one per recurrent layer
   float *act_w = nullptr, *act_b = nullptr, *cr_w = nullptr, *cr_b = nullptr;
   bool attached = false;             // pnvo_policy_train_attach: the weight pointers above are not owned
   PolicyTrain *train = nullptr;
@@ -37,17 +37,25 @@ struct PolicyParam {
   bool rows_as_float4;               // kernels read its rows as 16-byte vectors: the tensor must start at a multiple of 4 floats
 };
 
+// torch.nn.GRU keeps three gate blocks (r, z, n) per layer and one state tensor, torch.nn.LSTM four (i, f, g, o) and two (h, c)
+inline bool is_gru(const pnvo_policy_config &c) { return c.rnn_type == PNVO_RNN_GRU; }
+inline int rnn_gates(const pnvo_policy_config &c) { return is_gru(c) ? 3 : 4; }
+// floats of hidden_in / hidden_out for `rows` environments
+inline size_t rnn_state_floats(const pnvo_policy_config &c, int rows) {
+  return (size_t)(is_gru(c) ? 1 : 2) * c.rnn_layers * rows * c.hidden;
+}
+
 inline std::vector<PolicyParam> policy_params(Policy &p) {
-  const int64_t Hd = p.cfg.hidden, A = p.cfg.n_actions;
+  const int64_t Hd = p.cfg.hidden, A = p.cfg.n_actions, G = rnn_gates(p.cfg);
   std::vector<PolicyParam> t = {{"net.prev_action_embedding.weight", {A + 1, 32}, &p.emb, false},
                                 {"net.tgt_embeding.weight", {32, 3}, &p.tgt_w, false},
                                 {"net.tgt_embeding.bias", {32}, &p.tgt_b, false}};
   for (int l = 0; l < p.cfg.rnn_layers; ++l) {
     const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
-    t.push_back({r + "weight_ih" + sl, {4 * Hd, l == 0 ? Hd + 64 : Hd}, &p.w_ih[l], true});
-    t.push_back({r + "weight_hh" + sl, {4 * Hd, Hd}, &p.w_hh[l], true});
-    t.push_back({r + "bias_ih" + sl, {4 * Hd}, &p.b_ih[l], false});
-    t.push_back({r + "bias_hh" + sl, {4 * Hd}, &p.b_hh[l], false});
+    t.push_back({r + "weight_ih" + sl, {G * Hd, l == 0 ? Hd + 64 : Hd}, &p.w_ih[l], true});
+    t.push_back({r + "weight_hh" + sl, {G * Hd, Hd}, &p.w_hh[l], true});
+    t.push_back({r + "bias_ih" + sl, {G * Hd}, &p.b_ih[l], false});
+    t.push_back({r + "bias_hh" + sl, {G * Hd}, &p.b_hh[l], false});
   }
   t.push_back({"action_distribution.linear.weight", {A, Hd}, &p.act_w, true});
   t.push_back({"action_distribution.linear.bias", {A}, &p.act_b, false});
@@ -100,7 +108,7 @@ void dfree(T *&p) {
   p = nullptr;
 }
 
-// The LSTM kernels write h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory.
+// The recurrent kernels write h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory.
 inline bool hidden_states_overlap(const float *in, const float *out, size_t floats) {
   const uintptr_t bytes = (uintptr_t)floats * sizeof(float), a = (uintptr_t)in, b = (uintptr_t)out;
   return a < b + bytes && b < a + bytes;

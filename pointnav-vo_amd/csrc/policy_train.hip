@@ -13,6 +13,13 @@
 // from the caller's flat parameter buffer, gate order i, f, g, o.  Every reduction runs in a fixed order (no float atomics): the same
 // call gives the same bits twice.  Masking h and c at EVERY step equals the reference's segment-wise masking
 // (model_utils/rnns/rnn_state_encoder.py:81-134): inside a segment all masks are 1.
+//
+// With cfg.rnn_type = GRU the recurrent core is torch.nn.GRU (gate order r, z, n; weights [3H][K]; state [L, N, H], h only):
+//   evaluate : G_x = X . W_ih^T + b_ih ONLY (b_hn sits inside the product with r, so b_hh cannot ride on the input GEMM), then T launches
+//              of gru_step_kernel, which add the recurrent products and b_hh and keep (r, z, n, q = W_hn hm + b_hn), y and hm per row
+//   backward : T launches of gru_bptt_step_kernel filling dGx = (dr, dz, dn) and dGh = (dr, dz, dn * r); dW_ih = dGx^T . X,
+//              dW_hh = dGh^T . hm, db_ih = colsum(dGx), db_hh = colsum(dGh), dX = dGx . W_ih
+// Everything else (encoder, inputs, heads, loss, clipping) is shared; the type is branched on once per call, on the host.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -43,6 +50,7 @@ struct PolicyTrain {
   std::vector<float *> gates, c, y, hm;
   float *logits = nullptr, *value = nullptr, *logp = nullptr, *ent = nullptr, *dlogits = nullptr, *dvalue = nullptr;
   float *dY = nullptr, *dX0 = nullptr, *dG = nullptr, *dC = nullptr, *whhT = nullptr;
+  float *dGh = nullptr;               // GRU only: the recurrent side's gate gradients [M, 3H] (dG holds the input side's; dC holds dh)
   double *sq_part = nullptr;          // clip_grad_norm partial sums
   // pnvo_policy_train_timing: events at the phase boundaries of evaluate / ppo_loss / backward (tools/bench_ppo_update.py)
   bool timing = false;
@@ -173,6 +181,58 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(float *g, const float *h
         h_fin[e] = h;
         c_fin[e] = c;
       }
+    }
+    __syncthreads();
+  }
+}
+
+// One (t, layer) of a GRU, in lstm_step_kernel's shape with three waves (r, z, n).  g: this step's N rows of the [M, 4H] gate workspace,
+// holding G_x = X . W_ih^T + b_ih in blocks 0 .. 2 on entry and the ACTIVATED r, z, n and q = W_hn hm + b_hn (blocks 0 .. 3) on exit;
+// y (= h[t]) and hm = h[t-1] * mask[t] are written beside them.  h_fin: the rollout's final state (last step only, else nullptr).
+__global__ __launch_bounds__(192) void gru_step_kernel(float *g, const float *h_prev, const float *w_hh, const float *b_hh,
+                                                     const float *masks, int N, int Hd, float *y, float *hm, float *h_fin) {
+  __shared__ float sg[3][64];
+  const int lane = threadIdx.x & 63, gate = (int)(threadIdx.x >> 6), j = blockIdx.x;
+  const int n = gate * Hd + j, H4 = Hd >> 2;
+  const long G = 4L * Hd;
+  const f32x4 *wh = reinterpret_cast<const f32x4 *>(w_hh + (long)n * Hd);
+  for (int b0 = 0; b0 < N; b0 += 64) {
+    const int nb = min(64, N - b0);
+    for (int bb = 0; bb < nb; ++bb) {
+      const int b = b0 + bb;
+      const f32x4 *hr = reinterpret_cast<const f32x4 *>(h_prev + (long)b * Hd);
+      float u = 0.f;
+      for (int k = lane; k < H4; k += 64) {
+        const f32x4 w = wh[k], v = hr[k];
+        u = __builtin_fmaf(w[0], v[0], u);
+        u = __builtin_fmaf(w[1], v[1], u);
+        u = __builtin_fmaf(w[2], v[2], u);
+        u = __builtin_fmaf(w[3], v[3], u);
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) u += __shfl_xor(u, o);
+      if (lane == 0) {
+        const float rec = u * masks[b] + b_hh[n];
+        sg[gate][bb] = gate == 2 ? rec : rec + g[b * G + n];     // the n gate's two sums stay apart until r is known
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+      const int b = b0 + (int)threadIdx.x;
+      const long e = (long)b * Hd + j;
+      const float r_ = 1.f / (1.f + expf(-sg[0][threadIdx.x]));
+      const float z_ = 1.f / (1.f + expf(-sg[1][threadIdx.x]));
+      const float q_ = sg[2][threadIdx.x];
+      const float n_ = tanhf(g[b * G + 2 * Hd + j] + r_ * q_);
+      const float hmv = h_prev[e] * masks[b];
+      const float h = (1.f - z_) * n_ + z_ * hmv;
+      y[e] = h;
+      hm[e] = hmv;
+      g[b * G + j] = r_;
+      g[b * G + Hd + j] = z_;
+      g[b * G + 2 * Hd + j] = n_;
+      g[b * G + 3 * Hd + j] = q_;
+      if (h_fin != nullptr) h_fin[e] = h;
     }
     __syncthreads();
   }
@@ -408,6 +468,61 @@ __global__ __launch_bounds__(256) void bptt_step_kernel(const float *gates_t, co
   }
 }
 
+// One (t, layer) of a GRU, run for t = T-1 .. 0: workgroup = hidden unit j, three waves.  With the finished dGh[t+1] of the previous
+// launch (dgh_n; nullptr at t = T-1) the waves form dGh[t+1][b] . W_hh[:, j] — each wave one gate block of the transposed weight row
+// whhT[j][0 .. 3H), summed in gate order — then the first lanes run the cell backward for (b, j):
+//   dh = dY[t] + mask[t+1] * (z[t+1] * dh[t+1] + dGh[t+1] . W_hh[:, j])      (hm enters h' directly through z and through W_hh)
+//   dn_pre = dh (1 - z)(1 - n^2),  dz_pre = dh (hm - n) z (1 - z),  dr_pre = dn_pre q r (1 - r)
+//   dGx[t] = (dr_pre, dz_pre, dn_pre),  dGh[t] = (dr_pre, dz_pre, dn_pre * r)
+__global__ __launch_bounds__(192) void gru_bptt_step_kernel(const float *gates_t, const float *gates_n, const float *dgh_n,
+                                                          const float *dh_n, const float *mask_n, const float *hm_t, const float *whhT,
+                                                          const float *dY_t, int N, int Hd, float *dgx_t, float *dgh_t, float *dh_t) {
+  __shared__ float sg[3][64];
+  const int lane = threadIdx.x & 63, gate = (int)(threadIdx.x >> 6), j = blockIdx.x;
+  const int H4 = Hd >> 2;
+  const long G = 4L * Hd, G3 = 3L * Hd;
+  const f32x4 *wt = reinterpret_cast<const f32x4 *>(whhT + (long)j * G3 + (long)gate * Hd);
+  for (int b0 = 0; b0 < N; b0 += 64) {
+    const int nb = min(64, N - b0);
+    if (dgh_n != nullptr) {
+      for (int bb = 0; bb < nb; ++bb) {
+        const f32x4 *dr = reinterpret_cast<const f32x4 *>(dgh_n + (long)(b0 + bb) * G3 + (long)gate * Hd);
+        float u = 0.f;
+        for (int k = lane; k < H4; k += 64) {
+          const f32x4 w = wt[k], v = dr[k];
+          u = __builtin_fmaf(w[0], v[0], u);
+          u = __builtin_fmaf(w[1], v[1], u);
+          u = __builtin_fmaf(w[2], v[2], u);
+          u = __builtin_fmaf(w[3], v[3], u);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) u += __shfl_xor(u, o);
+        if (lane == 0) sg[gate][bb] = u;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+      const int b = b0 + (int)threadIdx.x;
+      const long e = (long)b * Hd + j;
+      float dh = dY_t[e];
+      if (dgh_n != nullptr)
+        dh += mask_n[b] * (gates_n[b * G + Hd + j] * dh_n[e] + ((sg[0][threadIdx.x] + sg[1][threadIdx.x]) + sg[2][threadIdx.x]));
+      const float r_ = gates_t[b * G + j], z_ = gates_t[b * G + Hd + j], n_ = gates_t[b * G + 2 * Hd + j], q_ = gates_t[b * G + 3 * Hd + j];
+      const float dn = dh * (1.f - z_) * (1.f - n_ * n_);
+      const float dz = dh * (hm_t[e] - n_) * z_ * (1.f - z_);
+      const float dr = dn * q_ * r_ * (1.f - r_);
+      dh_t[e] = dh;
+      dgx_t[b * G3 + j] = dr;
+      dgx_t[b * G3 + Hd + j] = dz;
+      dgx_t[b * G3 + 2 * Hd + j] = dn;
+      dgh_t[b * G3 + j] = dr;
+      dgh_t[b * G3 + Hd + j] = dz;
+      dgh_t[b * G3 + 2 * Hd + j] = dn * r_;
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------ input gradients
 // From layer 0's dX [M, hidden + 64]: d visual (the first `hidden` columns, copied out contiguous), tgt_embeding's weight [32,3] and
 // bias [32], and prev_action_embedding [n_emb, 32] as an ordered sum over the rows that gathered each entry (no atomics; an entry no
@@ -510,6 +625,7 @@ void free_ws(PolicyTrain *t) {
   dfree(t->dY);
   dfree(t->dX0);
   dfree(t->dG);
+  dfree(t->dGh);
   dfree(t->dC);
   t->capM = 0;
 }
@@ -525,7 +641,7 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   PCHK(fl(t->x0, m * K0));
   PCHK(fl(t->g3, m * 3));
   PCHK(fl(t->masks, m));
-  PCHK(fl(t->hid0, 2 * L * m * Hd));
+  PCHK(fl(t->hid0, rnn_state_floats(c, M)));
   PCHK(hipMalloc((void **)&t->rows, m * sizeof(int)));
   PCHK(hipMalloc((void **)&t->actions, m * sizeof(int64_t)));
   t->gates.assign(L, nullptr);
@@ -547,6 +663,7 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   PCHK(fl(t->dY, m * Hd));
   PCHK(fl(t->dX0, m * K0));
   PCHK(fl(t->dG, m * 4 * Hd));
+  if (is_gru(c)) PCHK(fl(t->dGh, m * 3 * Hd));
   PCHK(fl(t->dC, m * Hd));
   t->capM = M;
   return PNVO_OK;
@@ -681,8 +798,10 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = T * N;
-  if (hidden_states_overlap(hidden_in, hidden_out, (size_t)2 * L * N * Hd))
-    return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds 2 * rnn_layers * N * hidden floats): pass separate buffers");
+  const bool gru = is_gru(c);
+  if (hidden_states_overlap(hidden_in, hidden_out, rnn_state_floats(c, N)))
+    return pfail(PNVO_ERR_ARG, std::string("hidden_out overlaps hidden_in (each holds ") + (gru ? "" : "2 * ") +
+                                   "rnn_layers * N * hidden floats): pass separate buffers");
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   int rc = ensure_ws(p, t, M);
@@ -694,7 +813,7 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   // what the backward reads later is kept here: the caller's tensors may be gone by then
   PCHK(hipMemcpyAsync(t->masks, masks, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
   PCHK(hipMemcpyAsync(t->actions, actions, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-  PCHK(hipMemcpyAsync(t->hid0, hidden_in, (size_t)2 * L * N * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+  PCHK(hipMemcpyAsync(t->hid0, hidden_in, rnn_state_floats(c, N) * sizeof(float), hipMemcpyDeviceToDevice, s));
   PCHK(mark(t, 0, s));
   if ((rc = pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK) return rc;
   rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, nullptr, nullptr, t->enc_out, stream);
@@ -705,7 +824,20 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   PCHK(launch_policy_inputs(p, visual, goal, prev_actions, t->masks, M, t->x0, t->rows, t->g3, s));
   const float *xin = t->x0;
   int K = K0;
-  for (int l = 0; l < L; ++l) {
+  for (int l = 0; gru && l < L; ++l) {
+    // G_x into blocks 0 .. 2 of the [M, 4H] gate rows; b_hh is added by the step (b_hn belongs inside r * (...))
+    GemmArgs g{xin, p.w_ih[l], p.b_ih[l], nullptr, t->gates[l], M, 3 * Hd, K, (long)K, 1, 1, (long)K, 4L * Hd};
+    PCHK((launch_gemm<true, true>(g, s)));
+    for (int ts = 0; ts < T; ++ts) {
+      const size_t r = (size_t)ts * N;
+      const float *h_prev = ts ? t->y[l] + (r - N) * Hd : t->hid0 + (size_t)l * N * Hd;
+      hipLaunchKernelGGL(gru_step_kernel, dim3((unsigned)Hd), dim3(192), 0, s, t->gates[l] + r * 4 * Hd, h_prev, p.w_hh[l], p.b_hh[l],
+                         t->masks + r, N, Hd, t->y[l] + r * Hd, t->hm[l] + r * Hd, ts == T - 1 ? hidden_out + (size_t)l * N * Hd : nullptr);
+    }
+    xin = t->y[l];
+    K = Hd;
+  }
+  for (int l = 0; !gru && l < L; ++l) {
     GemmArgs g{xin, p.w_ih[l], p.b_ih[l], p.b_hh[l], t->gates[l], M, 4 * Hd, K, (long)K, 1, 1, (long)K, 4L * Hd};
     PCHK((launch_gemm<true, true>(g, s)));
     for (int ts = 0; ts < T; ++ts) {
@@ -767,7 +899,31 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
                      Hd, A, grad_of(t, p.act_w), grad_of(t, p.act_b), grad_of(t, p.cr_w), grad_of(t, p.cr_b));
   hipLaunchKernelGGL(heads_bwd_x_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, t->dlogits, t->dvalue, p.act_w,
                      p.cr_w, M, Hd, A, t->dY);
-  for (int l = L - 1; l >= 0; --l) {
+  const bool gru = is_gru(c);
+  for (int l = L - 1; gru && l >= 0; --l) {
+    const int K = l == 0 ? K0 : Hd, G3 = 3 * Hd;
+    const float *X = l == 0 ? t->x0 : t->y[l - 1];
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((Hd + 31) / 32), (unsigned)((G3 + 31) / 32)), dim3(256), 0, s, p.w_hh[l], G3, Hd,
+                       t->whhT);
+    for (int ts = T - 1; ts >= 0; --ts) {
+      const size_t r = (size_t)ts * N, rn = r + N;
+      const bool last = ts == T - 1;
+      hipLaunchKernelGGL(gru_bptt_step_kernel, dim3((unsigned)Hd), dim3(192), 0, s, t->gates[l] + r * 4 * Hd,
+                         last ? nullptr : t->gates[l] + rn * 4 * Hd, last ? nullptr : t->dGh + rn * G3, last ? nullptr : t->dC + rn * Hd,
+                         last ? nullptr : t->masks + rn, t->hm[l] + r * Hd, t->whhT, t->dY + r * Hd, N, Hd, t->dG + r * G3, t->dGh + r * G3,
+                         t->dC + r * Hd);
+    }
+    // dW_ih = dGx^T . X,  dW_hh = dGh^T . (h_prev * mask),  db_ih = colsum(dGx),  db_hh = colsum(dGh),  dX = dGx . W_ih
+    GemmArgs wi{t->dG, X, nullptr, nullptr, grad_of(t, p.w_ih[l]), G3, K, M, 1, (long)G3, (long)K, 1, (long)K};
+    PCHK((launch_gemm<false, false>(wi, s)));
+    GemmArgs wh{t->dGh, t->hm[l], nullptr, nullptr, grad_of(t, p.w_hh[l]), G3, Hd, M, 1, (long)G3, (long)Hd, 1, (long)Hd};
+    PCHK((launch_gemm<false, false>(wh, s)));
+    PCHK(launch_colsum(t->dG, M, G3, G3, grad_of(t, p.b_ih[l]), s));
+    PCHK(launch_colsum(t->dGh, M, G3, G3, grad_of(t, p.b_hh[l]), s));
+    GemmArgs dx{t->dG, p.w_ih[l], nullptr, nullptr, l == 0 ? t->dX0 : t->dY, M, K, G3, (long)G3, 1, (long)K, 1, (long)K};
+    PCHK((launch_gemm<true, false>(dx, s)));
+  }
+  for (int l = L - 1; !gru && l >= 0; --l) {
     const int K = l == 0 ? K0 : Hd;
     const float *X = l == 0 ? t->x0 : t->y[l - 1];
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((Hd + 31) / 32), (unsigned)((4 * Hd + 31) / 32)), dim3(256), 0, s, p.w_hh[l], 4 * Hd,

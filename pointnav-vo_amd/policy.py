@@ -1,8 +1,9 @@
 """HIP-backed navigation policy registered under the reference's name ``resnet_rnn_policy``.
 
 Drop-in for PointNavResNetPolicy (/root/reference/pointnav_vo/rl/policies/resnet_policy.py:25-58) in the configuration
-the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only resnet18 encoder, 2-layer LSTM, RL.OBS_TRANSFORM
-'none', 'resize' or 'resize_crop', normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-133), same
+the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only resnet18 encoder, 2-layer LSTM — or GRU, the other
+value RL.Policy.rnn_backbone takes (rnn_state_encoder.py:28) — RL.OBS_TRANSFORM 'none', 'resize' or 'resize_crop',
+normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-133), same
 ``state_dict`` keys/shapes, same ``act`` / ``get_value`` signatures and return values (policy.py:29-50).  The module tree
 only HOLDS parameters; ``act`` is one call into libpnvo.so (pnvo_policy_act) on the caller's current HIP stream plus the
 categorical sampling / arg-max over the 4 logits, which stays in torch as in the reference (policy.py:38-43).
@@ -27,11 +28,23 @@ class _Holder(nn.Module):
 
 
 class pnvo_policy_config(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("width", "height", "baseplanes", "hidden", "n_actions", "rnn_layers", "flat_size")]
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "baseplanes", "hidden", "n_actions", "rnn_layers", "flat_size", "rnn_type")]
 
 
-def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048):
+# rnn_type -> (pnvo_policy_config.rnn_type, gate blocks per weight, state tensors per layer): torch.nn.LSTM (i, f, g, o; h and c),
+# torch.nn.GRU (r, z, n; h only)
+RNN_TYPES = {"LSTM": (0, 4, 2), "GRU": (1, 3, 1)}
+
+
+def _rnn(rnn_type):
+    if rnn_type not in RNN_TYPES:
+        raise NotImplementedError(f"rnn_type {rnn_type!r}: the HIP policy implements 'LSTM' and 'GRU'")
+    return RNN_TYPES[rnn_type]
+
+
+def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048, rnn_type="LSTM"):
     """(name, shape) of every tensor of PointNavResNetPolicy.state_dict() for the depth-only resnet18 configuration."""
+    gates = _rnn(rnn_type)[1]
     def half(v):
         return (v + 1) // 2
     h, w = height // 2, width // 2                       # F.avg_pool2d(x, 2)
@@ -65,8 +78,8 @@ def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_action
     for layer in range(rnn_layers):
         k = hidden + 64 if layer == 0 else hidden
         r = "net.state_encoder.rnn."
-        spec += [(f"{r}weight_ih_l{layer}", (4 * hidden, k)), (f"{r}weight_hh_l{layer}", (4 * hidden, hidden)),
-                 (f"{r}bias_ih_l{layer}", (4 * hidden,)), (f"{r}bias_hh_l{layer}", (4 * hidden,))]
+        spec += [(f"{r}weight_ih_l{layer}", (gates * hidden, k)), (f"{r}weight_hh_l{layer}", (gates * hidden, hidden)),
+                 (f"{r}bias_ih_l{layer}", (gates * hidden,)), (f"{r}bias_hh_l{layer}", (gates * hidden,))]
     spec += [("action_distribution.linear.weight", (n_actions, hidden)), ("action_distribution.linear.bias", (n_actions,)),
              ("critic.fc.weight", (1, hidden)), ("critic.fc.bias", (1,))]
     return spec
@@ -98,7 +111,7 @@ class _NetHolder(_Holder):
 
     @property
     def num_recurrent_layers(self):
-        return self._layers * 2                            # LSTM: h and c (rnn_state_encoder.py:44-45)
+        return self._layers * self._states                 # LSTM: h and c, GRU: h (rnn_state_encoder.py:41-43)
 
     @property
     def output_size(self):
@@ -115,8 +128,10 @@ class PointNavResNetPolicy(nn.Module):
                  num_recurrent_layers=2, rnn_type="LSTM", resnet_baseplanes=32, backbone="resnet18",
                  normalize_visual_inputs=False, obs_transform=None, vis_types=("depth",), **kwargs):
         super().__init__()
-        if rnn_type != "LSTM" or backbone != "resnet18":
-            raise NotImplementedError("the HIP policy implements the resnet18 + LSTM configuration of ddppo_pointnav.yaml")
+        if backbone != "resnet18":
+            raise NotImplementedError(f"backbone {backbone!r}: the HIP policy implements the resnet18 encoder of ddppo_pointnav.yaml")
+        self._rnn_type = rnn_type
+        self._rnn_code, _, self._states = _rnn(rnn_type)
         if normalize_visual_inputs or list(vis_types) != ["depth"]:
             raise NotImplementedError("the HIP policy implements the depth-only, un-normalised encoder "
                                       "(RL.Policy.visual_types = ['depth'])")
@@ -139,7 +154,8 @@ class PointNavResNetPolicy(nn.Module):
         self.dim_actions = int(action_space.n)
         self._hidden, self._layers, self._baseplanes = int(hidden_size), int(num_recurrent_layers), int(resnet_baseplanes)
         self._spec = policy_state_dict_spec(width=self._W, height=self._H, baseplanes=self._baseplanes,
-                                            hidden=self._hidden, n_actions=self.dim_actions, rnn_layers=self._layers)
+                                            hidden=self._hidden, n_actions=self.dim_actions, rnn_layers=self._layers,
+                                            rnn_type=rnn_type)
         for name, shape in self._spec:
             parts = name.split(".")
             mod = self
@@ -151,7 +167,7 @@ class PointNavResNetPolicy(nn.Module):
         # the reference trainers read these through policy.net (ppo_trainer.py:618, ddppo_trainer.py:279)
         net = self.net
         net.__class__ = _NetHolder
-        net._layers, net._hidden = self._layers, self._hidden
+        net._layers, net._hidden, net._states = self._layers, self._hidden, self._states
         self._handle = None
         self._handle_dev = None
         self._loaded_sig = None
@@ -159,7 +175,7 @@ class PointNavResNetPolicy(nn.Module):
 
     @property
     def num_recurrent_layers(self):
-        return self._layers * 2                            # LSTM: h and c (rnn_state_encoder.py:44-45)
+        return self._layers * self._states                 # LSTM: h and c, GRU: h (rnn_state_encoder.py:41-43)
 
     @property
     def output_size(self):
@@ -175,7 +191,8 @@ class PointNavResNetPolicy(nn.Module):
         if self._handle is None or self._handle_dev != device.index:
             self._release()
             cc = pnvo_policy_config(width=self._W, height=self._H, baseplanes=self._baseplanes, hidden=self._hidden,
-                                    n_actions=self.dim_actions, rnn_layers=self._layers, flat_size=2048)
+                                    n_actions=self.dim_actions, rnn_layers=self._layers, flat_size=2048,
+                                    rnn_type=self._rnn_code)
             h = C.c_void_p()
             _lib.check(_lib.lib.pnvo_policy_create(C.byref(cc), int(device.index or 0), C.byref(h)))
             self._handle, self._handle_dev, self._loaded_sig = h, device.index, None
@@ -223,7 +240,7 @@ class PointNavResNetPolicy(nn.Module):
         pa = prev_actions.to(device=dev, dtype=torch.int64).contiguous().reshape(B)
         mk = masks.to(device=dev, dtype=torch.float32).contiguous().reshape(B)
         hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
-        assert tuple(hin.shape) == (2 * self._layers, B, self._hidden), tuple(hin.shape)
+        assert tuple(hin.shape) == (self.num_recurrent_layers, B, self._hidden), tuple(hin.shape)
         hout = torch.empty_like(hin)
         feats = torch.empty((B, self._hidden), device=dev, dtype=torch.float32) if want_features else None
         logits = torch.empty((B, self.dim_actions), device=dev, dtype=torch.float32)

@@ -1,12 +1,12 @@
 """PPO update of the HIP navigation policy: the reference's `PPO` agent (pointnav_vo/rl/ppo/ppo.py) on libpnvo.so.
 
 The reference tunes the policy against the VO estimates with this update (configs/rl/ddppo_pointnav.yaml: TUNE_WITH_VO, train_encoder,
-num_steps 128, num_mini_batch 2, 2-layer LSTM).  `PolicyTrainStep` is to the policy what `VOTrainStep` (train.py) is to a VO model:
+num_steps 128, num_mini_batch 2, 2-layer LSTM; a policy built with rnn_type="GRU" runs the same calls on the GRU kernels).  `PolicyTrainStep` is to the policy what `VOTrainStep` (train.py) is to a VO model:
 it holds one flat_params.FlatParams (`store`: ONE flat parameter buffer and ONE flat gradient buffer on the device, the module's
 parameters as views of them, Adam's moments and state dict; `flat`, `grad`, `exp_avg`, `exp_avg_sq`, `offsets` are the store's own
 objects) and drives the C ABI —
 
-    pnvo_policy_evaluate     rollout forward (encoder in train mode, LSTM over T x N with mask resets), activations kept
+    pnvo_policy_evaluate     rollout forward (encoder in train mode, LSTM or GRU over T x N with mask resets), activations kept
     pnvo_policy_ppo_loss     clipped surrogate / value loss / entropy and their gradient at the heads, from a kernel
     pnvo_policy_backward     heads, back-propagation through time, embeddings, the encoder's backward
     pnvo_policy_clip_grad_norm, pnvo_adam_step, pnvo_policy_train_refresh
@@ -19,7 +19,7 @@ until the end (one synchronisation per update).  The gradient is one flat buffer
 `rollouts` is rollout_storage.RolloutStorage (the reference's class on the device: insert, compute_returns and the minibatch gather
 are one launch each); the agent reads only `returns`, `value_preds` and `recurrent_generator`.
 
-Not here: the DD-PPO reducer and pre-emption logic, an autograd bridge for the reference's own PPO.update, GRU and non-resnet18
+Not here: the DD-PPO reducer and pre-emption logic, an autograd bridge for the reference's own PPO.update, non-resnet18
 backbones.  No CPU fallback.
 """
 import ctypes as C
@@ -139,8 +139,9 @@ class PolicyTrainStep:
             raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [M,{pol._H},{pol._W},1]")
         hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
         N = hin.shape[1]
-        if tuple(hin.shape) != (2 * pol._layers, N, pol._hidden) or N <= 0 or M % N != 0:
-            raise ValueError(f"rnn_hidden_states {tuple(hin.shape)} does not fit {M} rows: expected [{2 * pol._layers}, N, {pol._hidden}] "
+        S = pol.num_recurrent_layers
+        if tuple(hin.shape) != (S, N, pol._hidden) or N <= 0 or M % N != 0:
+            raise ValueError(f"rnn_hidden_states {tuple(hin.shape)} does not fit {M} rows: expected [{S}, N, {pol._hidden}] "
                              "with N dividing the number of rows")
         T = M // N
         goal = observations[GOAL_SENSOR].to(device=dev, dtype=torch.float32).contiguous().reshape(M, 2)
@@ -188,7 +189,7 @@ class PolicyTrainStep:
         _lib.check(_lib.lib.pnvo_policy_train_timing(self.policy._handle, int(bool(on))))
 
     def phase_ms(self):
-        """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, LSTM forward +
+        """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, LSTM (or GRU) forward +
         heads, loss, heads + BPTT + embedding backward, encoder backward."""
         ms = (C.c_double * 5)()
         _lib.check(_lib.lib.pnvo_policy_train_timing_read(self.policy._handle, ms))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-step latency / throughput of the HIP navigation policy (PointNavResNetPolicy.act)
 at the batch sizes a nav loop uses (B = environments per process), with the oracle port timed beside it.
-    python tools/bench_policy.py [--envs 1 4 16 64]"""
+    python tools/bench_policy.py [--envs 1 4 16 64] [--rnn {LSTM,GRU}]
+--rnn GRU times the GRU state encoder instead (no oracle port of it: the CPU baseline is skipped)."""
 import argparse
 import json
 import os
@@ -37,15 +38,18 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[1, 4, 16, 64])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--rnn", choices=["LSTM", "GRU"], default="LSTM")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     space = Space({"depth": Box((H, W, 1)), "pointgoal_with_gps_compass": Box((2,))})
-    pol = PointNavResNetPolicy(observation_space=space, action_space=Act(), hidden_size=512, rnn_type="LSTM",
+    pol = PointNavResNetPolicy(observation_space=space, action_space=Act(), hidden_size=512, rnn_type=a.rnn,
                                num_recurrent_layers=2, backbone="resnet18", vis_types=["depth"])
-    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H), seed=0)
+    sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H, rnn_type=a.rnn), seed=0)
     pol.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
     pol = pol.to(dev).eval()
     res = {"metric": "navigation-policy act() steps", "frame": f"{W}x{H} depth", "dtype": "f32", "results": []}
+    if a.rnn != "LSTM":
+        res["rnn"] = a.rnn
     for B in a.envs:
         depth, goal, prev, mask = synth.make_policy_inputs(H, W, B, 1, 1)[0]
         obs = {"depth": torch.from_numpy(depth).to(dev), "pointgoal_with_gps_compass": torch.from_numpy(goal).to(dev)}
@@ -60,7 +64,7 @@ def main():
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
         res["results"].append({"envs": B, "ms_per_step": dt * 1e3, "frames_per_s": B / dt})
-    if not a.no_cpu_baseline:
+    if not a.no_cpu_baseline and a.rnn == "LSTM":
         from oracle import oracle, policy_oracle
         B = 4
         depth, goal, prev, mask = synth.make_policy_inputs(H, W, B, 1, 1)[0]

@@ -2,6 +2,7 @@
 """One PPO minibatch update of the navigation policy at the reference's shape, per phase, on the MI355X.
 
     python tools/bench_ppo_update.py [--n 2 4] [--steps 128] [--iters 12] [--warmup 3] [--out profiles/ppo_update.md] [--no-eager]
+                                      [--rnn {LSTM,GRU}]
 
 Shape: configs/rl/ddppo_pointnav.yaml — num_steps T = 128, N environments per minibatch, 341 x 192 depth, hidden 512, 2-layer LSTM,
 train_encoder.  The HIP path (pointnav_vo_amd.ppo.PolicyTrainStep) is timed per phase with HIP events recorded inside the library
@@ -12,6 +13,7 @@ Beside it, in the same run on the same GPU: the same update in plain torch eager
 policy with random weights: GroupNorm-ResNet18 encoder, nn.LSTM run over the segments between episode starts as the reference's
 RNNStateEncoder does, Categorical heads, the PPO loss, clip_grad_norm_, torch.optim.Adam).  It is the only comparison there is: the
 project could not do this update at all before.  No threshold: the record says which side wins, phase by phase.
+--rnn GRU runs both sides with the GRU state encoder (state [LAYERS, N, HIDDEN]); the phase keys keep their names.
 """
 import argparse
 import json
@@ -32,7 +34,7 @@ CLIP, VALUE_COEF, ENTROPY_COEF, LR, EPS, MAX_GRAD_NORM = 0.2, 0.5, 0.01, 2.5e-4,
 GOAL = "pointgoal_with_gps_compass"
 
 
-def make_batch(T, N, dev, seed=0):
+def make_batch(T, N, dev, seed=0, rnn="LSTM"):
     g = torch.Generator().manual_seed(seed)
     M = T * N
     masks = torch.ones(T, N)
@@ -41,10 +43,12 @@ def make_batch(T, N, dev, seed=0):
         masks[int(torch.randint(8, T - 8, (1,), generator=g)), n] = 0
     b = dict(depth=torch.rand(M, H, W, 1, generator=g), goal=torch.rand(M, 2, generator=g) * 3,
              prev=torch.randint(0, ACTIONS, (M, 1), generator=g), masks=masks.reshape(M, 1),
-             actions=torch.randint(0, ACTIONS, (M, 1), generator=g), hidden=torch.rand(2 * LAYERS, N, HIDDEN, generator=g) - 0.5,
+             actions=torch.randint(0, ACTIONS, (M, 1), generator=g), hidden=torch.rand(2 * LAYERS, N, HIDDEN, generator=g) - 0.5,       # a GRU keeps the h blocks
              old=-1.386 + 0.2 * torch.randn(M, 1, generator=g), adv=torch.randn(M, 1, generator=g),
              vp=torch.randn(M, 1, generator=g) * 0.3)
     b["ret"] = b["vp"] + b["adv"]
+    if rnn == "GRU":
+        b["hidden"] = b["hidden"][:LAYERS].contiguous()
     return {k: v.to(dev) for k, v in b.items()}
 
 
@@ -71,7 +75,7 @@ class Timer:
 
 
 # ---------------------------------------------------------------------------------------------------------------- HIP path
-def bench_hip(T, N, iters, warmup, dev):
+def bench_hip(T, N, iters, warmup, dev, rnn="LSTM"):
     from pointnav_vo_amd.policy import PointNavResNetPolicy
     from pointnav_vo_amd.ppo import PolicyTrainStep
 
@@ -88,11 +92,11 @@ def bench_hip(T, N, iters, warmup, dev):
 
     torch.manual_seed(0)
     pol = PointNavResNetPolicy(observation_space=Space({"depth": Box((H, W, 1)), GOAL: Box((2,))}), action_space=Act(),
-                               hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type="LSTM", backbone="resnet18",
+                               hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type=rnn, backbone="resnet18",
                                normalize_visual_inputs=False, obs_transform=None, vis_types=["depth"]).to(dev)
     step = PolicyTrainStep(pol, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM)
     step.timing(True)
-    b = make_batch(T, N, dev)
+    b = make_batch(T, N, dev, rnn=rnn)
     obs = {"depth": b["depth"], GOAL: b["goal"]}
     tm, phases = Timer(), []
     for _ in range(warmup + iters):
@@ -126,10 +130,11 @@ class Block(nn.Module):
 
 
 class EagerPolicy(nn.Module):
-    """The depth-only resnet18 + LSTM policy (baseplanes 32, GroupNorm of baseplanes / 2 groups, 2048-float compression)."""
+    """The depth-only resnet18 + LSTM (or GRU) policy (baseplanes 32, GroupNorm of baseplanes / 2 groups, 2048-float compression)."""
 
-    def __init__(self):
+    def __init__(self, rnn="LSTM"):
         super().__init__()
+        self.gru = rnn == "GRU"
         bp, g = 32, 16
         self.stem = gn_conv(1, bp, 7, 2, g)
         blocks, cin = [], bp
@@ -147,7 +152,7 @@ class EagerPolicy(nn.Module):
         self.fc = nn.Linear(comp * h * w, HIDDEN)
         self.tgt = nn.Linear(3, 32)
         self.emb = nn.Embedding(ACTIONS + 1, 32)
-        self.rnn = nn.LSTM(HIDDEN + 64, HIDDEN, LAYERS)
+        self.rnn = getattr(nn, rnn)(HIDDEN + 64, HIDDEN, LAYERS)
         self.actor, self.critic = nn.Linear(HIDDEN, ACTIONS), nn.Linear(HIDDEN, 1)
 
     def encode(self, depth):
@@ -162,22 +167,23 @@ class EagerPolicy(nn.Module):
         idx = ((b["prev"].float() + 1) * b["masks"]).long().squeeze(-1)
         x = torch.cat([visual, self.tgt(g3), self.emb(idx)], 1).view(T, N, -1)
         h, c = b["hidden"][:LAYERS], b["hidden"][LAYERS:]
+        state = h if self.gru else (h, c)
         starts = sorted(set([0] + (masks == 0).any(1).nonzero().flatten().tolist() + [T]))   # segments between episode starts
         outs = []
         for s, e in zip(starts[:-1], starts[1:]):
             m = masks[s].view(1, N, 1)
-            o, (h, c) = self.rnn(x[s:e], (h * m, c * m))
+            o, state = self.rnn(x[s:e], state * m if self.gru else (state[0] * m, state[1] * m))
             outs.append(o)
         feat = torch.cat(outs).view(T * N, -1)
         dist = torch.distributions.Categorical(logits=self.actor(feat))
         return self.critic(feat), dist.log_prob(b["actions"].squeeze(-1)).unsqueeze(-1), dist.entropy().mean()
 
 
-def bench_eager(T, N, iters, warmup, dev):
+def bench_eager(T, N, iters, warmup, dev, rnn="LSTM"):
     torch.manual_seed(0)
-    pol = EagerPolicy().to(dev)
+    pol = EagerPolicy(rnn).to(dev)
     opt = torch.optim.Adam(pol.parameters(), lr=LR, eps=EPS)
-    b = make_batch(T, N, dev)
+    b = make_batch(T, N, dev, rnn=rnn)
     tm = Timer()
     for _ in range(warmup + iters):
         with tm.span("whole update"):
@@ -217,6 +223,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-eager", action="store_true")
+    ap.add_argument("--rnn", choices=["LSTM", "GRU"], default="LSTM")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ppo_update.py measures on an MI355X: no GPU here, nothing measured")
@@ -224,18 +231,18 @@ def main():
         raise SystemExit("--iters must be at least 10 (median of >= 10 timed iterations)")
     dev = torch.device("cuda", 0)
     lines = ["# PPO minibatch update of the navigation policy: HIP path vs torch eager", "",
-             f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer LSTM, 4 actions, train_encoder; "
+             f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer {a.rnn}, 4 actions, train_encoder; "
              f"median of {a.iters} iterations after {a.warmup} warm-up, HIP events, one process, {torch.cuda.get_device_name(0)}.",
-             "The eager column is the same update in torch-ROCm eager ops with autograd (nn.LSTM over the segments between episode "
+             f"The eager column is the same update in torch-ROCm eager ops with autograd (nn.{a.rnn} over the segments between episode "
              "starts, as the reference's RNNStateEncoder), random weights.  Milliseconds.", ""]
     record = {}
     for N in a.n:
-        hip = bench_hip(a.steps, N, a.iters, a.warmup, dev)
+        hip = bench_hip(a.steps, N, a.iters, a.warmup, dev, a.rnn)
         torch.cuda.empty_cache()
         eager = None
         if not a.no_eager:
             try:
-                eager = bench_eager(a.steps, N, a.iters, a.warmup, dev)
+                eager = bench_eager(a.steps, N, a.iters, a.warmup, dev, a.rnn)
             except Exception as e:                                    # the record then says so instead of a number
                 eager = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
@@ -243,7 +250,7 @@ def main():
         lines += [f"## N = {N}  (M = {a.steps * N} frames)", "", "| phase | HIP path | torch eager | eager / HIP |", "|---|---:|---:|---:|"]
         for k in ORDER:
             e = eager.get(k) if eager and "error" not in eager else None
-            lines.append(f"| {LABEL[k]} | {hip[k]:.3f} | {'%.3f' % e if e is not None else 'not measured'} | "
+            lines.append(f"| {LABEL[k].replace('LSTM', a.rnn)} | {hip[k]:.3f} | {'%.3f' % e if e is not None else 'not measured'} | "
                          f"{'%.2f' % (e / hip[k]) if e is not None else '-'} |")
         if eager and "error" in eager:
             lines += ["", f"torch eager failed: `{eager['error']}`"]
