@@ -584,6 +584,10 @@ int pnvo_resize_area(const void *src, int src_dtype, int n, int in_h, int in_w, 
 
 const char *pnvo_version(void);
 
+/* Bytes this library currently holds in device and host-mapped memory, over all handles of the process (0 before the first
+ * pnvo_create and again after the last destroy).  Memory the caller owns (tensors, flat parameter buffers) is not counted. */
+long long pnvo_device_bytes_live(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,7 @@ _SIGNATURES = {
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
                                    C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "pnvo_version": (C.c_char_p, []),
+    "pnvo_device_bytes_live": (C.c_longlong, []),
 }
 
 

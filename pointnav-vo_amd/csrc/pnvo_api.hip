@@ -27,27 +27,11 @@ int pnvo_fail(pnvo_handle h, int code, const std::string &msg) {
   return code;
 }
 
-// Sizes of the operand buffers upload() owns: a reload of same-sized data (every pnvo_load_weights after the first)
-// rewrites them in place, so device addresses cached elsewhere (the training step's re-pack maps, captured graphs)
-// stay valid across train -> eval -> train switches.
-static std::map<const void *, size_t> g_upload_floats;
-static std::mutex g_upload_mutex;      // handles of different host threads (one per device) load and destroy concurrently
-
-void pnvo_free_dev(float *&p) {
-  if (p) {
-    {
-      std::lock_guard<std::mutex> lk(g_upload_mutex);
-      g_upload_floats.erase(p);
-    }
-    (void)hipFree(p);
-  }
-  p = nullptr;
-}
+long long pnvo_device_bytes_live(void) { return g_device_bytes_live.load(); }
 
 namespace {
 
 inline int fail(pnvo_handle h, int code, const std::string &msg) { return pnvo_fail(h, code, msg); }
-inline void free_dev(float *&p) { pnvo_free_dev(p); }
 
 
 Layer make_layer(const std::string &name, const std::string &gn, int cin, int cout, int k, int stride, int pad,
@@ -116,7 +100,7 @@ void build_plan(pnvo_model_s *m) {
   m->blocks.clear();
   auto push = [&](Layer l) {                         // a conv of the block under construction
     l.block = (int)m->blocks.size();
-    m->convs.push_back(l);
+    m->convs.push_back(std::move(l));
     return (int)m->convs.size() - 1;
   };
   for (int st = 1; st <= 4; ++st) {
@@ -132,13 +116,15 @@ void build_plan(pnvo_model_s *m) {
         Layer b2 = make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, stride, 1, h, w, g);
         b.nconv = 3;
         b.conv[0] = push(make_layer(p + "convs.0", p + "convs.1", cin, planes, 1, 1, 0, h, w, g));
-        b.conv[1] = push(b2);
-        b.conv[2] = push(make_layer(p + "convs.6", p + "convs.7", planes, cout, 1, 1, 0, b2.hout, b2.wout, g));
+        const int h2 = b2.hout, w2 = b2.wout;
+        b.conv[1] = push(std::move(b2));
+        b.conv[2] = push(make_layer(p + "convs.6", p + "convs.7", planes, cout, 1, 1, 0, h2, w2, g));
       } else {
         Layer c1 = make_layer(p + "convs.0", p + "convs.1", cin, planes, 3, stride, 1, h, w, g);
         b.nconv = 2;
-        b.conv[0] = push(c1);
-        b.conv[1] = push(make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, 1, 1, c1.hout, c1.wout, g));
+        const int h1 = c1.hout, w1 = c1.wout;
+        b.conv[0] = push(std::move(c1));
+        b.conv[1] = push(make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, 1, 1, h1, w1, g));
       }
       if (stride != 1 || cin != cout) b.ds = push(make_layer(p + "downsample.0", p + "downsample.1", cin, cout, 1, stride, 0, h, w, g));
       m->blocks.push_back(b);
@@ -198,23 +184,6 @@ const float *find_tensor(pnvo_handle h, const Toc &t, const std::string &name, s
   return t.blob + d->offset;
 }
 
-int upload(pnvo_handle h, float *&dst, const float *src, size_t n) {
-  bool same = false;
-  if (dst) {
-    std::lock_guard<std::mutex> lk(g_upload_mutex);
-    auto it = g_upload_floats.find(dst);
-    same = it != g_upload_floats.end() && it->second == n;
-  }
-  if (!same) {
-    free_dev(dst);
-    HIPCHK(h, hipMalloc((void **)&dst, n * sizeof(float)));
-    std::lock_guard<std::mutex> lk(g_upload_mutex);
-    g_upload_floats[dst] = n;
-  }
-  HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-  return PNVO_OK;
-}
-
 }  // namespace
 
 // pack with an explicit padded input-channel count (the FC reads a channel-padded activation)
@@ -245,41 +214,35 @@ int load_conv(pnvo_handle h, const Toc &t, Layer &l, bool has_gn) {
   if (!w) return rc;
   std::vector<float> pk;
   pack_conv_weight_cinp(w, l.cout, l.cin, l.cinp, l.k, l.kw, pk);
-  if ((rc = upload(h, l.wpk, pk.data(), pk.size())) != PNVO_OK) return rc;
+  HIPCHK(h, l.wpk.upload(pk.data(), pk.size()));
   l.host_w.assign(w, w + (size_t)l.cout * l.cin * l.k * l.kw);
   if (has_gn) {
     const float *g = find_tensor(h, t, l.gn + ".weight", {l.cout}, &rc);
     if (!g) return rc;
     const float *b = find_tensor(h, t, l.gn + ".bias", {l.cout}, &rc);
     if (!b) return rc;
-    if ((rc = upload(h, l.gamma, g, l.cout)) != PNVO_OK) return rc;
-    if ((rc = upload(h, l.beta, b, l.cout)) != PNVO_OK) return rc;
+    HIPCHK(h, l.gamma.upload(g, l.cout));
+    HIPCHK(h, l.beta.upload(b, l.cout));
   }
   return PNVO_OK;
 }
 
+// The input-contract flag of the fused stems and its host-mapped copy, lowered (pnvo_load_weights).
+int reset_contract_flag(pnvo_handle h) {
+  if (!h->dd_flag) HIPCHK(h, h->dd_flag.alloc_host(1, hipHostMallocMapped | hipHostMallocCoherent));
+  if (!h->dd_flag_dev) HIPCHK(h, h->dd_flag_dev.alloc(1));
+  *(volatile int *)h->dd_flag = 0;
+  HIPCHK(h, hipMemset(h->dd_flag_dev, 0, sizeof(int)));
+  return PNVO_OK;
+}
+
+// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves cap = 0.
 void free_workspace(pnvo_model_s *m) {
   pnvo_drop_graphs(m);            // captured kernel arguments point into the workspace
-  free_dev(m->xin);
-  free_dev(m->stem_raw);
-  free_dev(m->out_ws);
-  free_dev(m->bufY[0]);
-  free_dev(m->bufY[1]);
-  free_dev(m->rawA);
-  free_dev(m->rawB);
-  free_dev(m->rawD);
-  free_dev(m->rawC);
-  free_dev(m->comp_raw);
-  free_dev(m->hid);
-  free_dev(m->stats);
-  free_dev(m->stats_ds);
-  for (int k = 0; k < 2; ++k) {
-    free_dev(m->ssA[k]);
-    free_dev(m->ssB[k]);
-    free_dev(m->ssD[k]);
-    free_dev(m->ssC[k]);
-  }
-  free_dev(m->tapbuf);
+  for (DevBuf<float> *b : {&m->xin, &m->stem_raw, &m->out_ws, &m->bufY[0], &m->bufY[1], &m->rawA, &m->rawB, &m->rawD, &m->rawC, &m->comp_raw,
+                           &m->hid, &m->stats, &m->stats_ds, &m->tapbuf})
+    b->reset();
+  for (DevPair<float> *q : {&m->ssA, &m->ssB, &m->ssD, &m->ssC}) q->reset();
   m->cap = 0;
 }
 
@@ -392,38 +355,28 @@ int ensure_workspace(pnvo_handle m, int B) {   // (also exported as pnvo_ensure_
     const size_t s = stats_floats(m, l, B);
     if (s > st) st = s;
   }
-  auto alloc = [&](float *&p, size_t n) -> hipError_t { return hipMalloc((void **)&p, n * sizeof(float)); };
   (void)npix;   // the assembled [B,H,W,CP] input is only materialised for the "input" tap (allocated lazily)
-  HIPCHK(m, alloc(m->stem_raw, (size_t)B * m->Hs * m->Ws * c.baseplanes));
-  HIPCHK(m, alloc(m->bufY[0], act));
-  HIPCHK(m, alloc(m->bufY[1], act));
-  HIPCHK(m, alloc(m->rawA, act));
-  HIPCHK(m, alloc(m->rawB, act));
-  HIPCHK(m, alloc(m->rawD, act));
-  if (m->bottleneck) HIPCHK(m, alloc(m->rawC, act));
-  HIPCHK(m, alloc(m->comp_raw, (size_t)B * m->fh * m->fw * m->comp_cp));
-  HIPCHK(m, alloc(m->hid, (size_t)B * c.hidden));
-  HIPCHK(m, alloc(m->out_ws, (size_t)B * c.out_dim));
-  HIPCHK(m, alloc(m->stats, st));
-  HIPCHK(m, alloc(m->stats_ds, st));
+  HIPCHK(m, m->stem_raw.alloc((size_t)B * m->Hs * m->Ws * c.baseplanes));
+  HIPCHK(m, m->bufY[0].alloc(act));
+  HIPCHK(m, m->bufY[1].alloc(act));
+  HIPCHK(m, m->rawA.alloc(act));
+  HIPCHK(m, m->rawB.alloc(act));
+  HIPCHK(m, m->rawD.alloc(act));
+  if (m->bottleneck) HIPCHK(m, m->rawC.alloc(act));
+  HIPCHK(m, m->comp_raw.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
+  HIPCHK(m, m->hid.alloc((size_t)B * c.hidden));
+  HIPCHK(m, m->out_ws.alloc((size_t)B * c.out_dim));
+  HIPCHK(m, m->stats.alloc(st));
+  HIPCHK(m, m->stats_ds.alloc(st));
   for (int k = 0; k < 2; ++k) {
-    HIPCHK(m, alloc(m->ssA[k], (size_t)B * maxc));
-    HIPCHK(m, alloc(m->ssB[k], (size_t)B * maxc));
-    HIPCHK(m, alloc(m->ssD[k], (size_t)B * maxc));
-    HIPCHK(m, alloc(m->ssC[k], (size_t)B * m->comp_cp));
+    HIPCHK(m, m->ssA.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, m->ssB.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, m->ssD.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, m->ssC.alloc(k, (size_t)B * m->comp_cp));
     HIPCHK(m, hipMemset(m->ssC[k], 0, (size_t)B * m->comp_cp * sizeof(float)));   // pad channels stay (0, 0)
   }
-  m->tapbuf_floats = (size_t)B * m->fh * m->fw * m->comp_cp;
-  HIPCHK(m, alloc(m->tapbuf, m->tapbuf_floats));
-  {                                     // split-K partials of the linear layers: <= 32 slices of [B, hidden]
-    const size_t need = (size_t)32 * B * (size_t)std::max(c.hidden, 32);
-    if (need > m->kpart_floats) {
-      free_dev(m->kpart);
-      m->kpart_floats = 0;
-      HIPCHK(m, alloc(m->kpart, need));
-      m->kpart_floats = need;
-    }
-  }
+  HIPCHK(m, m->tapbuf.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
+  HIPCHK(m, m->kpart.reserve((size_t)32 * B * (size_t)std::max(c.hidden, 32)));   // split-K partials of the linear layers: <= 32 slices of [B, hidden]
   m->cap = B;
   return PNVO_OK;
 }
@@ -548,11 +501,11 @@ double conv_bytes(const Layer &l, int B) {
 // when h's weights moved since it was made: re-packed on the device from the flat parameters of an attached training step (weight
 // and float16 scale live there: pnvo_train_refresh), else packed on the host and uploaded.
 int x3_operand(pnvo_handle h, Layer &q, int pieces, hipStream_t s) {
-  unsigned short *&wpk = pieces == 2 ? q.wpk_x2 : q.wpk_x3;
+  DevBuf<unsigned short> &wpk = pieces == 2 ? q.wpk_x2 : q.wpk_x3;
   unsigned long long &gen = pieces == 2 ? q.x2_gen : q.x3_gen;
   if (wpk && gen == h->weights_gen) return PNVO_OK;
   const size_t nel = (size_t)q.k * q.kw * q.cinp * q.coutp * pieces;
-  if (!wpk) HIPCHK(h, hipMalloc((void **)&wpk, nel * 2));
+  if (!wpk) HIPCHK(h, wpk.alloc(nel));
   const float *dev_w = h->train ? pnvo_train_weight_ptr(h, q.name + ".weight") : nullptr;
   if (dev_w != nullptr && pieces == 2) {
     HIPCHK(h, launch_conv_x2_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pnvo_train_x2_scale(h, q.name + ".weight"), wpk, s));
@@ -738,13 +691,9 @@ int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
     a.kpart = nullptr;
     if (ks > 1) {
       const size_t need = (size_t)ks * M * r.y_cstride;
-      if (need > m->kpart_floats) {
+      if (need > m->kpart.size()) {
         pnvo_drop_graphs(m);                         // captured launches point into the old scratch
-        if (m->kpart) (void)hipFree(m->kpart);
-        m->kpart = nullptr;
-        m->kpart_floats = 0;
-        HIPCHK(m, hipMalloc((void **)&m->kpart, need * sizeof(float)));
-        m->kpart_floats = need;
+        HIPCHK(m, m->kpart.alloc(need));
       }
       a.kpart = m->kpart;
       a.ksplit = ks;
@@ -987,7 +936,7 @@ static int stem_launch_mx(pnvo_handle m, int B, const StemRequest &r, const Stem
   a.dbg = m->opt.stem_dbg >= 16 ? m->opt.stem_dbg - 16 : 0;
   if (m->opt.stem_dbg == 9 || m->opt.stem_dbg >= 16) {
     if (!m->mx_prof) {
-      HIPCHK(m, hipMalloc((void **)&m->mx_prof, 2048));
+      HIPCHK(m, m->mx_prof.alloc(256));
       HIPCHK(m, hipMemset(m->mx_prof, 0, 2048));
     }
     a.prof = m->mx_prof;
@@ -1032,7 +981,7 @@ static int stem_launch_dd(pnvo_handle m, int B, const StemRequest &r, const Stem
   a.dbg = m->opt.stem_dbg;
   if (a.dbg == 9) {
     if (!m->dd_prof) {
-      HIPCHK(m, hipMalloc((void **)&m->dd_prof, 64));
+      HIPCHK(m, m->dd_prof.alloc(8));
       HIPCHK(m, hipMemset(m->dd_prof, 0, 64));
     }
     a.prof = m->dd_prof;
@@ -1301,14 +1250,14 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
     }
     std::vector<float> pk;
     pack_conv_weight_cinp(wp.data(), st.cout, h->CP, h->CP, st.k, st.kw, pk);
-    if ((rc = upload(h, st.wpk, pk.data(), pk.size())) != PNVO_OK) return rc;
-    if ((rc = upload(h, h->stem_sc, sc.data(), sc.size())) != PNVO_OK) return rc;
-    if ((rc = upload(h, h->stem_sh, sh.data(), sh.size())) != PNVO_OK) return rc;
+    HIPCHK(h, st.wpk.upload(pk.data(), pk.size()));
+    HIPCHK(h, h->stem_sc.upload(sc.data(), sc.size()));
+    HIPCHK(h, h->stem_sh.upload(sh.data(), sh.size()));
     std::vector<float> z(64, 0.f);
-    if ((rc = upload(h, h->zero_page, z.data(), z.size())) != PNVO_OK) return rc;
+    HIPCHK(h, h->zero_page.upload(z.data(), z.size()));
     std::vector<float> pk16((size_t)49 * h->CPL * st.cout);
     pack_stem_weight(wp.data(), st.cout, h->CP, h->CPL, pk16.data());
-    if ((rc = upload(h, h->stem_wpk16, pk16.data(), pk16.size())) != PNVO_OK) return rc;
+    HIPCHK(h, h->stem_wpk16.upload(pk16.data(), pk16.size()));
     // ---- one-hot-aware stem: split the input channels into dense (matrix cores) and one-hot depth bins (table gather)
     h->dd_ok = false;
     const int bins = c.n_dd / 2;
@@ -1363,14 +1312,11 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
           }
         std::vector<float> pkd((size_t)49 * 12 * st.cout);
         pack_stem_dd_weight(wd.data(), st.cout, pkd.data());
-        if ((rc = upload(h, h->dd_wpk, pkd.data(), pkd.size())) != PNVO_OK) return rc;
-        if ((rc = upload(h, h->dd_table, tab.data(), tab.size())) != PNVO_OK) return rc;
-        if ((rc = upload(h, h->dd_sc, sc16.data(), 12)) != PNVO_OK) return rc;
-        if ((rc = upload(h, h->dd_sh, sh16.data(), 12)) != PNVO_OK) return rc;
-        if (!h->dd_flag) HIPCHK(h, hipHostMalloc((void **)&h->dd_flag, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-        if (!h->dd_flag_dev) HIPCHK(h, hipMalloc((void **)&h->dd_flag_dev, sizeof(int)));
-        *(volatile int *)h->dd_flag = 0;
-        HIPCHK(h, hipMemset(h->dd_flag_dev, 0, sizeof(int)));
+        HIPCHK(h, h->dd_wpk.upload(pkd.data(), pkd.size()));
+        HIPCHK(h, h->dd_table.upload(tab.data(), tab.size()));
+        HIPCHK(h, h->dd_sc.upload(sc16.data(), 12));
+        HIPCHK(h, h->dd_sh.upload(sh16.data(), 12));
+        if ((rc = reset_contract_flag(h)) != PNVO_OK) return rc;
         h->dd_bins = bins;
         h->dd_ok = true;
       }
@@ -1429,25 +1375,18 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
       h->mx_slot_new = slot_new;
       std::vector<unsigned short> pk(stem_mx_packed_u16(3, st.cout / 32));
       pack_stem_mx_weight(h->mx_wk.data(), st.cout, 3, h->mx_xslot, pk.data());
-      if ((rc = upload(h, reinterpret_cast<float *&>(h->mx_wpk3), reinterpret_cast<const float *>(pk.data()), pk.size() / 2)) !=
-          PNVO_OK)
-        return rc;
+      HIPCHK(h, h->mx_wpk3.upload(pk.data(), pk.size()));
       {
         std::vector<unsigned short> pk2(stem_mx_packed_u16(2, st.cout / 32));
         h->mx_oscale = pack_stem_mx_weight_h(h->mx_wk.data(), st.cout, h->mx_xslot, pk2.data());
         h->mx_wpk2_dev = false;
-        if ((rc = upload(h, reinterpret_cast<float *&>(h->mx_wpk2), reinterpret_cast<const float *>(pk2.data()), pk2.size() / 2)) !=
-            PNVO_OK)
-          return rc;
+        HIPCHK(h, h->mx_wpk2.upload(pk2.data(), pk2.size()));
       }
       {
         std::vector<float> pages(64, 0.f);
-        if ((rc = upload(h, h->mx_pages, pages.data(), pages.size())) != PNVO_OK) return rc;
+        HIPCHK(h, h->mx_pages.upload(pages.data(), pages.size()));
       }
-      if (!h->dd_flag) HIPCHK(h, hipHostMalloc((void **)&h->dd_flag, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-      if (!h->dd_flag_dev) HIPCHK(h, hipMalloc((void **)&h->dd_flag_dev, sizeof(int)));
-      *(volatile int *)h->dd_flag = 0;
-      HIPCHK(h, hipMemset(h->dd_flag_dev, 0, sizeof(int)));
+      if ((rc = reset_contract_flag(h)) != PNVO_OK) return rc;
       h->mx_ok = true;
     }
   }
@@ -1470,10 +1409,10 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
       for (int o = 0; o < c.hidden; ++o)
         for (int ch = 0; ch < h->comp_c; ++ch)
           for (int q = 0; q < hw; ++q) rows[(size_t)o * kp + (size_t)q * h->comp_cp + ch] = vis[(size_t)o * flat + (size_t)ch * hw + q];
-      if ((rc = upload(h, h->fc_rows_w, rows.data(), rows.size())) != PNVO_OK) return rc;
+      HIPCHK(h, h->fc_rows_w.upload(rows.data(), rows.size()));
     }
     pack_conv_weight_cinp(vis.data(), c.hidden, h->comp_c, h->comp_cp, h->fh, h->fw, pk);
-    if ((rc = upload(h, h->fc.wpk, pk.data(), pk.size())) != PNVO_OK) return rc;
+    HIPCHK(h, h->fc.wpk.upload(pk.data(), pk.size()));
     const int rows = c.act_embed ? c.n_acts + 1 : 1;
     std::vector<float> bias((size_t)rows * c.hidden);
     const float *emb = nullptr;
@@ -1488,7 +1427,7 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
           for (int e = 0; e < 32; ++e) acc += (double)w1[(size_t)o * fc_in + flat + e] * (double)emb[a * 32 + e];
         bias[(size_t)a * c.hidden + o] = (float)(acc + (double)b1[o]);
       }
-    if ((rc = upload(h, h->fc_bias, bias.data(), bias.size())) != PNVO_OK) return rc;
+    HIPCHK(h, h->fc_bias.upload(bias.data(), bias.size()));
   }
   const float *w2 = find_tensor(h, t, "output_head.1.weight", {c.out_dim, c.hidden}, &rc);
   if (!w2) return rc;
@@ -1498,9 +1437,9 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
     std::vector<float> pk;
     h->head.host_w.assign(w2, w2 + (size_t)c.out_dim * c.hidden);
     pack_conv_weight_cinp(w2, c.out_dim, c.hidden, c.hidden, 1, 1, pk);
-    if ((rc = upload(h, h->head.wpk, pk.data(), pk.size())) != PNVO_OK) return rc;
-    if ((rc = upload(h, h->head_bias, b2, c.out_dim)) != PNVO_OK) return rc;
-    if ((rc = upload(h, h->head_w_plain, w2, (size_t)c.out_dim * c.hidden)) != PNVO_OK) return rc;
+    HIPCHK(h, h->head.wpk.upload(pk.data(), pk.size()));
+    HIPCHK(h, h->head_bias.upload(b2, c.out_dim));
+    HIPCHK(h, h->head_w_plain.upload(w2, (size_t)c.out_dim * c.hidden));
   }
   h->loaded = true;
   h->load_gen += 1;
@@ -1733,8 +1672,7 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
     a.C = m->C;
     a.CP = m->CP;
     a.npix = (long)B * c.height * c.width;
-    free_dev(m->xin);
-    HIPCHK(m, hipMalloc((void **)&m->xin, (size_t)a.npix * m->CP * sizeof(float)));
+    HIPCHK(m, m->xin.alloc((size_t)a.npix * m->CP));
     a.out = m->xin;
     HIPCHK(m, launch_assemble(a, s));
     if ((rc = maybe_tap(m, "input", m->xin, (size_t)B * c.height * c.width * m->CP, s)) != PNVO_OK) return rc;
@@ -1987,11 +1925,11 @@ bool raw_direct(pnvo_handle m, const float *depth_frames) {
 int raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, int B, int32_t *err_flag, hipStream_t s) {
   const pnvo_config &c = m->cfg;
   if (B > m->rawws_cap) {
-    for (float *&q : m->rawws) pnvo_free_dev(q);
+    for (DevBuf<float> &q : m->rawws) q.reset();
     const size_t px = (size_t)B * c.height * c.width;
-    if (c.n_rgb) HIPCHK(m, hipMalloc((void **)&m->rawws[0], px * 6 * sizeof(float)));
-    HIPCHK(m, hipMalloc((void **)&m->rawws[1], px * 2 * sizeof(float)));
-    if (c.n_dd) HIPCHK(m, hipMalloc((void **)&m->rawws[2], px * (size_t)c.n_dd * sizeof(float)));
+    if (c.n_rgb) HIPCHK(m, m->rawws[0].alloc(px * 6));
+    HIPCHK(m, m->rawws[1].alloc(px * 2));
+    if (c.n_dd) HIPCHK(m, m->rawws[2].alloc(px * (size_t)c.n_dd));
     m->rawws_cap = B;
   }
   HIPCHK(m, launch_frame_pairs(c.n_rgb ? rgb_frames : nullptr, depth_frames, B, c.height, c.width, c.n_dd / 2, m->rawws[0], m->rawws[1],
@@ -2355,35 +2293,9 @@ int pnvo_destroy(pnvo_handle m) {
   pnvo_train_free(m);
   pnvo_bf16_free(m);
   pnvo_small_free(m);
-  free_workspace(m);
+  pnvo_drop_graphs(m);
   if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
   if (m->stem_ev) (void)hipEventDestroy(m->stem_ev);
-  for (Layer &l : m->convs) {
-    free_dev(l.wpk);
-    free_dev(reinterpret_cast<float *&>(l.wpk_x3));
-    free_dev(reinterpret_cast<float *&>(l.wpk_x2));
-    free_dev(l.gamma);
-    free_dev(l.beta);
-  }
-  free_dev(m->fc.wpk);
-  free_dev(m->head.wpk);
-  free_dev(m->fc_bias);
-  free_dev(m->fc_rows_w);
-  free_dev(m->head_bias);
-  free_dev(m->head_w_plain);
-  free_dev(m->stem_sc);
-  free_dev(m->stem_sh);
-  free_dev(m->stem_wpk16);
-  free_dev(reinterpret_cast<float *&>(m->mx_wpk3));
-  free_dev(reinterpret_cast<float *&>(m->mx_wpk2));
-  if (m->mx_scale2_dev) (void)hipFree(m->mx_scale2_dev);
-  free_dev(m->mx_pages);
-  free_dev(m->dd_wpk);
-  free_dev(m->dd_table);
-  free_dev(m->dd_sc);
-  free_dev(m->dd_sh);
-  if (m->dd_flag) (void)hipHostFree(m->dd_flag);
-  if (m->dd_flag_dev) (void)hipFree(m->dd_flag_dev);
   if (m->mx_prof && m->mx_prof_rs) {
     unsigned long long pr[256];
     (void)hipMemcpy(pr, m->mx_prof, 2048, hipMemcpyDeviceToHost);
@@ -2394,7 +2306,6 @@ int pnvo_destroy(pnvo_handle m) {
       std::fprintf(stderr, "[pnvo] stem_rs wave %d (cycles per tile): k-loop with the next patch's staging %.0f  wait others %.0f  "
                    "exchange + epilogue %.0f  (%llu tiles)\n", w, q[0] / nt_, q[1] / nt_, q[2] / nt_, q[5]);
     }
-    (void)hipFree(m->mx_prof);
   } else if (m->mx_prof) {
     unsigned long long pr[32];
     (void)hipMemcpy(pr, m->mx_prof, 256, hipMemcpyDeviceToHost);
@@ -2403,7 +2314,6 @@ int pnvo_destroy(pnvo_handle m) {
       std::fprintf(stderr, "[pnvo] stem_mx wave %d (cycles per tile): staging %.0f  barrier %.0f  k-loop %.0f  reduce+epilogue %.0f  "
                    "(%llu tiles)\n", w, pr[8 * w] / nt_, pr[8 * w + 1] / nt_, pr[8 * w + 2] / nt_, pr[8 * w + 3] / nt_, pr[8 * w + 4]);
     }
-    (void)hipFree(m->mx_prof);
   }
   if (m->dd_prof) {
     unsigned long long pr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2412,11 +2322,7 @@ int pnvo_destroy(pnvo_handle m) {
     std::fprintf(stderr, "[pnvo] stem_dd phases (cycles per tile, workgroup thread 0): staging %.0f  k-loop %.0f (of which "
                  "row barriers %.0f)  epilogue %.0f  (%llu tiles)\n", (double)pr[0] / nt_, (double)pr[1] / nt_,
                  (double)pr[4] / nt_, (double)pr[2] / nt_, pr[3]);
-    (void)hipFree(m->dd_prof);
   }
-  free_dev(m->zero_page);
-  free_dev(m->kpart);
-  for (float *&q : m->rawws) free_dev(q);
   for (auto &r : m->trecs) {
     (void)hipEventDestroy(r.a);
     (void)hipEventDestroy(r.b);

@@ -23,46 +23,28 @@ struct BLayer {
   ConvBArgs plan;               // shape + tile plan (pointers filled per launch)
   int mw = 1, nw = 1;
   size_t lds = 0;
-  unsigned short *wpk = nullptr;
+  DevBuf<unsigned short> wpk;
 };
 
 struct Bf16State {
   unsigned long long gen = 0;
   std::vector<BLayer> layers;   // parallel to m->convs (index 0 unused: the stem)
-  unsigned short *stem_wpk = nullptr;        // PIECES = 1 packing, one N-tile group (this model on (prev, cur))
+  DevBuf<unsigned short> stem_wpk;           // PIECES = 1 packing, one N-tile group (this model on (prev, cur))
   std::vector<unsigned short> stem_host, stem_host_sw;   // host copies: as is / for the swapped pair
-  unsigned short *dual_stem = nullptr;       // [tap][fragment][2 models][lane]: this model + a partner's swapped packing
+  DevBuf<unsigned short> dual_stem;          // [tap][fragment][2 models][lane]: this model + a partner's swapped packing
   unsigned long long dual_partner = 0;       // process-unique id of the partner handle (an address can be re-used)
   unsigned long long dual_partner_gen = 0, dual_self_gen = 0;
   int cap = 0;
-  unsigned short *stem_raw = nullptr, *bufY[2] = {nullptr, nullptr}, *rawA = nullptr, *rawB = nullptr, *rawD = nullptr;
-  float *comp_raw = nullptr, *hid = nullptr, *stats = nullptr, *stats_ds = nullptr;   // stats_ds: partial sums of a riding downsample conv
-  float *ssA[2] = {nullptr, nullptr}, *ssB[2] = {nullptr, nullptr}, *ssD[2] = {nullptr, nullptr}, *ssC[2] = {nullptr, nullptr};
+  DevBuf<unsigned short> stem_raw, bufY[2], rawA, rawB, rawD;
+  DevBuf<float> comp_raw, hid, stats, stats_ds;   // stats_ds: partial sums of a riding downsample conv
+  DevPair<float> ssA, ssB, ssD, ssC;
 };
 
-template <typename T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
+// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves cap = 0.
 void free_ws(Bf16State *b) {
-  dfree(b->stem_raw);
-  dfree(b->bufY[0]);
-  dfree(b->bufY[1]);
-  dfree(b->rawA);
-  dfree(b->rawB);
-  dfree(b->rawD);
-  dfree(b->comp_raw);
-  dfree(b->hid);
-  dfree(b->stats);
-  dfree(b->stats_ds);
-  for (int k = 0; k < 2; ++k) {
-    dfree(b->ssA[k]);
-    dfree(b->ssB[k]);
-    dfree(b->ssD[k]);
-    dfree(b->ssC[k]);
-  }
+  for (DevBuf<unsigned short> *q : {&b->stem_raw, &b->bufY[0], &b->bufY[1], &b->rawA, &b->rawB, &b->rawD}) q->reset();
+  for (DevBuf<float> *q : {&b->comp_raw, &b->hid, &b->stats, &b->stats_ds}) q->reset();
+  for (DevPair<float> *q : {&b->ssA, &b->ssB, &b->ssD, &b->ssC}) q->reset();
   b->cap = 0;
 }
 
@@ -82,10 +64,7 @@ int prepare(pnvo_handle m) {
     b = new Bf16State();
     m->bf = b;
   }
-  if (b->layers.size() != m->convs.size()) {
-    for (BLayer &l : b->layers) dfree(l.wpk);
-    b->layers.assign(m->convs.size(), BLayer());
-  }
+  if (b->layers.size() != m->convs.size()) b->layers = std::vector<BLayer>(m->convs.size());
   for (size_t li = 1; li < m->convs.size(); ++li) {
     const Layer &l = m->convs[li];
     BLayer &bl = b->layers[li];
@@ -101,7 +80,7 @@ int prepare(pnvo_handle m) {
     if (l.host_w.empty()) return pnvo_fail(m, PNVO_ERR_STATE, "weights of '" + l.name + "' were not loaded");
     std::vector<unsigned short> pk((size_t)l.k * l.kw * bl.plan.CIN * l.coutp);
     pack_conv_bf16_weight(l.host_w.data(), l.cout, l.cin, bl.plan.CIN, l.coutp, l.k, l.kw, pk.data());
-    if (!bl.wpk) HIPCHK(m, hipMalloc((void **)&bl.wpk, pk.size() * 2));
+    if (!bl.wpk) HIPCHK(m, bl.wpk.alloc(pk.size()));
     HIPCHK(m, hipMemcpy(bl.wpk, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
   }
   {
@@ -110,7 +89,7 @@ int prepare(pnvo_handle m) {
     b->stem_host_sw.resize(n);
     pack_stem_mx_weight(m->mx_wk.data(), 32, 1, m->mx_xslot, b->stem_host.data());
     pack_stem_mx_weight(m->mx_wk_swapped.data(), 32, 1, m->mx_xslot, b->stem_host_sw.data());
-    if (!b->stem_wpk) HIPCHK(m, hipMalloc((void **)&b->stem_wpk, n * 2));
+    if (!b->stem_wpk) HIPCHK(m, b->stem_wpk.alloc(n));
     HIPCHK(m, hipMemcpy(b->stem_wpk, b->stem_host.data(), n * 2, hipMemcpyHostToDevice));
   }
   b->gen = m->load_gen;
@@ -130,17 +109,17 @@ int ensure_ws(pnvo_handle m, int B) {
     st = std::max(st, (size_t)B * b->layers[li].plan.slots * l.coutp * 2);
     maxc = std::max(maxc, l.coutp);
   }
-  HIPCHK(m, hipMalloc((void **)&b->stem_raw, (size_t)B * m->Hs * m->Ws * 32 * 2));
-  for (unsigned short **pp : {&b->bufY[0], &b->bufY[1], &b->rawA, &b->rawB, &b->rawD}) HIPCHK(m, hipMalloc((void **)pp, act * 2));
-  HIPCHK(m, hipMalloc((void **)&b->comp_raw, (size_t)B * m->fh * m->fw * m->comp_cp * 4));
-  HIPCHK(m, hipMalloc((void **)&b->hid, (size_t)B * c.hidden * 4));
-  HIPCHK(m, hipMalloc((void **)&b->stats, st * 4));
-  HIPCHK(m, hipMalloc((void **)&b->stats_ds, st * 4));
+  HIPCHK(m, b->stem_raw.alloc((size_t)B * m->Hs * m->Ws * 32));
+  for (DevBuf<unsigned short> *q : {&b->bufY[0], &b->bufY[1], &b->rawA, &b->rawB, &b->rawD}) HIPCHK(m, q->alloc(act));
+  HIPCHK(m, b->comp_raw.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
+  HIPCHK(m, b->hid.alloc((size_t)B * c.hidden));
+  HIPCHK(m, b->stats.alloc(st));
+  HIPCHK(m, b->stats_ds.alloc(st));
   for (int k = 0; k < 2; ++k) {
-    HIPCHK(m, hipMalloc((void **)&b->ssA[k], (size_t)B * maxc * 4));
-    HIPCHK(m, hipMalloc((void **)&b->ssB[k], (size_t)B * maxc * 4));
-    HIPCHK(m, hipMalloc((void **)&b->ssD[k], (size_t)B * maxc * 4));
-    HIPCHK(m, hipMalloc((void **)&b->ssC[k], (size_t)B * m->comp_cp * 4));
+    HIPCHK(m, b->ssA.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, b->ssB.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, b->ssD.alloc(k, (size_t)B * maxc));
+    HIPCHK(m, b->ssC.alloc(k, (size_t)B * m->comp_cp));
     HIPCHK(m, hipMemset(b->ssC[k], 0, (size_t)B * m->comp_cp * 4));      // pad channels stay (0, 0)
   }
   b->cap = B;
@@ -158,7 +137,7 @@ int dual_stem(pnvo_handle m0, pnvo_handle m1) {
     std::memcpy(&pk[(2 * tf) * 512], &b0->stem_host[tf * 512], 1024);
     std::memcpy(&pk[(2 * tf + 1) * 512], &b1->stem_host_sw[tf * 512], 1024);
   }
-  if (!b0->dual_stem) HIPCHK(m0, hipMalloc((void **)&b0->dual_stem, pk.size() * 2));
+  if (!b0->dual_stem) HIPCHK(m0, b0->dual_stem.alloc(pk.size()));
   HIPCHK(m0, hipMemcpy(b0->dual_stem, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
   b0->dual_partner = m1->uid;
   b0->dual_partner_gen = m1->load_gen;
@@ -169,13 +148,7 @@ int dual_stem(pnvo_handle m0, pnvo_handle m1) {
 }  // namespace
 
 void pnvo_bf16_free(pnvo_handle m) {
-  Bf16State *b = static_cast<Bf16State *>(m->bf);
-  if (!b) return;
-  free_ws(b);
-  for (BLayer &l : b->layers) dfree(l.wpk);
-  dfree(b->stem_wpk);
-  dfree(b->dual_stem);
-  delete b;
+  delete static_cast<Bf16State *>(m->bf);
   m->bf = nullptr;
 }
 
@@ -231,7 +204,7 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float
     auto x = each([&](int z) { return (const unsigned short *)bs[z]->stem_raw; });
     auto sc = each([&](int z) { return (const float *)bs[z]->ssA[0]; });
     auto sh = each([&](int z) { return (const float *)bs[z]->ssA[1]; });
-    auto o = each([&](int z) { return bs[z]->bufY[0]; });
+    auto o = each([&](int z) -> unsigned short * { return bs[z]->bufY[0]; });
     PnvoTimed t(m, s, "bf16:gn_relu_maxpool", 0.0, 2.0 * nm * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * 32);
     HIPCHK(m, launch_gn_relu_maxpool_bf16(x.v, sc.v, sh.v, B, m->Hs, m->Ws, 32, o.v, nm, s));
   }
@@ -273,7 +246,7 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float
     // (gn_finalize_lane: fp64, the butterfly order of the float32 path's fused finalisation) — one launch less per layer
     const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
     const bool gfuse = m->opt.gn_fuse && a.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 && 32 % cpg == 0 && l.cout % cpg == 0;
-    auto ssof = [&](int z) { return ss_sel == 0 ? bs[z]->ssA : ss_sel == 1 ? bs[z]->ssB : ss_sel == 2 ? bs[z]->ssD : bs[z]->ssC; };
+    auto ssof = [&](int z) -> float *const * { return ss_sel == 0 ? bs[z]->ssA : ss_sel == 1 ? bs[z]->ssB : ss_sel == 2 ? bs[z]->ssD : bs[z]->ssC; };
     for (int z = 0; z < 2; ++z) {
       const int k = z < nm ? z : 0;
       a.gn_gamma[z] = gfuse ? hs[k]->convs[li].gamma : nullptr;
@@ -364,7 +337,7 @@ int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float
     auto a_ = each([&](int z) { return (const unsigned short *)bs[z]->rawB; });
     auto sa = each([&](int z) { return (const float *)bs[z]->ssB[0]; });
     auto ta = each([&](int z) { return (const float *)bs[z]->ssB[1]; });
-    auto y_ = each([&](int z) { return bs[z]->bufY[cur ^ 1]; });
+    auto y_ = each([&](int z) -> unsigned short * { return bs[z]->bufY[cur ^ 1]; });
     if (ds) {
       auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->rawD; });
       auto sb = each([&](int z) { return (const float *)bs[z]->ssD[0]; });

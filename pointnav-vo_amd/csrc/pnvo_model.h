@@ -9,6 +9,10 @@
 
 #include "../../include/pnvo.h"
 #include "pnvo_internal.h"
+#include "dev_buf.h"
+
+using pnvo::DevBuf;
+using pnvo::DevPair;
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 static inline int halve(int x) { return (x - 1) / 2 + 1; }
@@ -17,14 +21,14 @@ struct Layer {
   std::string name, gn;     // state_dict prefixes (conv weight, following GroupNorm)
   int cin = 0, cinp = 0, cout = 0, coutp = 0, k = 1, kw = 1, stride = 1, pad = 0;
   int hin = 0, win = 0, hout = 0, wout = 0, groups = 1;
-  float *wpk = nullptr, *gamma = nullptr, *beta = nullptr;   // device
+  DevBuf<float> wpk, gamma, beta;
   std::vector<float> host_w;  // OIHW copy of the loaded weight (source of the bf16 packing, pnvo_bf16.hip)
   // float32-on-bf16-pipe path (conv_x3.hip): three-piece packed weights, built on first use after a (re)load
-  unsigned short *wpk_x3 = nullptr;
+  DevBuf<unsigned short> wpk_x3;
   unsigned long long x3_gen = 0;
   // two-piece float16 form of the same kernel (inference): packed weights, the inverse of their power-of-two scale, and an
   // upper bound of |input activation| from the producers' GroupNorm parameters (float16 pieces need it below 65504)
-  unsigned short *wpk_x2 = nullptr;
+  DevBuf<unsigned short> wpk_x2;
   unsigned long long x2_gen = 0;
   float x2_oscale = 1.f;
   float in_bound = 3.0e38f;
@@ -99,52 +103,51 @@ struct pnvo_model_s {
   // the conv that reads block k's output: the next block's first conv, or the compression conv
   int next_conv_after(size_t k) const { return k + 1 < blocks.size() ? blocks[k + 1].conv[0] : comp; }
   Layer fc, head;
-  float *fc_bias = nullptr, *head_bias = nullptr;   // device; fc_bias has 1 or n_acts+1 rows
-  float *fc_rows_w = nullptr;                // device [hidden][fh * fw * comp_cp]: the hidden layer's weight rows in the activation's order (fc_rows.hip)
-  float *head_w_plain = nullptr;             // device [out_dim][hidden]: the head's weight as loaded (the head riding on the hidden layer's split-K reduction)
+  DevBuf<float> fc_bias, head_bias;   // fc_bias has 1 or n_acts+1 rows
+  DevBuf<float> fc_rows_w;                   // [hidden][fh * fw * comp_cp]: the hidden layer's weight rows in the activation's order (fc_rows.hip)
+  DevBuf<float> head_w_plain;                // [out_dim][hidden]: the head's weight as loaded (the head riding on the hidden layer's split-K reduction)
   std::vector<float> mean, stdev;    // host copies for the assemble kernel arguments (reference channel order)
   // fused stem: K-order of the stem = observation tensors concatenated (rgb | depth | dd | tdv), 2-channel pieces
   std::vector<int> stem_ref_of_new;  // new channel -> reference channel (vo_cnn.py:169-174 order), -1 = pad
   std::vector<int> stem_tensor_of_new, stem_ch_of_new;
-  float *stem_sc = nullptr, *stem_sh = nullptr, *zero_page = nullptr;   // device: whitening table in the new order
-  float *kpart = nullptr;             // split-K partials of the linear layers (conv_mfma.hip conv_ksplit)
-  size_t kpart_floats = 0;
-  float *stem_wpk16 = nullptr;       // stem weights packed for the LDS-staged 16x16x4 kernel
+  DevBuf<float> stem_sc, stem_sh, zero_page; // whitening table in the new order
+  DevBuf<float> kpart;               // split-K partials of the linear layers (conv_mfma.hip conv_ksplit); only grows
+  DevBuf<float> stem_wpk16;          // stem weights packed for the LDS-staged 16x16x4 kernel
   int CPL = 0;                       // stem channels per pixel in LDS (C rounded up to 16)
   // one-hot-aware stem (stem_dd.hip): dense channels + indicator on the matrix cores, depth bins as a table gather
   bool dd_ok = false;
   int dd_bins = 0;
   std::vector<int> dd_dense_tensor, dd_dense_ch;   // dense channel d -> (observation tensor, channel), -1 = indicator/pad
-  float *dd_wpk = nullptr, *dd_table = nullptr, *dd_sc = nullptr, *dd_sh = nullptr;
-  int *dd_flag = nullptr;            // host-mapped copy of dd_flag_dev (published by the kernel behind the stem): what the HOST reads
-  int *dd_flag_dev = nullptr;        // device memory: raised by a fused stem whose stager met a value outside the observation contract;
+  DevBuf<float> dd_wpk, dd_table, dd_sc, dd_sh;
+  DevBuf<int> dd_flag;               // host-mapped copy of dd_flag_dev (published by the kernel behind the stem): what the HOST reads
+  DevBuf<int> dd_flag_dev;           // device memory: raised by a fused stem whose stager met a value outside the observation contract;
                                      // read by the predicated repair launches (a host-mapped flag costs every wave a PCIe round trip)
-  unsigned long long *dd_prof = nullptr;   // PNVO_STEM_DBG=9: {staging, K loop, epilogue} cycles, tiles
+  DevBuf<unsigned long long> dd_prof;      // PNVO_STEM_DBG=9: {staging, K loop, epilogue} cycles, tiles
 
   // stem on the bf16 matrix cores (stem_mx.hip): exact three-piece bf16 weights -> float32 results (inference default)
   bool mx_ok = false;
-  unsigned short *mx_wpk3 = nullptr;         // device: three-piece packing (float32 results)
-  unsigned short *mx_wpk2 = nullptr;         // device: two float16 pieces (inference default) and the inverse of their scale
+  DevBuf<unsigned short> mx_wpk3;            // three-piece packing (float32 results)
+  DevBuf<unsigned short> mx_wpk2;            // two float16 pieces (inference default) and the inverse of their scale
   float mx_oscale = 1.f;
-  float *mx_scale2_dev = nullptr;            // training: {scale, 1/scale} of mx_wpk2 as the device-side re-pack chose it
+  DevBuf<float> mx_scale2_dev;               // training: {scale, 1/scale} of mx_wpk2 as the device-side re-pack chose it
   bool mx_wpk2_dev = false;                  // mx_wpk2 currently holds the device-side re-pack (scale in mx_scale2_dev), not the host's
   std::vector<float> mx_wk, mx_wk_swapped;   // host [cout][32 slots][49]: whitening-folded weights, as is / for the
                                              //   (cur, prev) channel-swapped pair (geometric-invariance dual forward)
   int mx_xslot[4] = {-1, -1, -1, -1};        // K-slots of the float-modality channels
   std::vector<int> mx_slot_ref, mx_slot_new; // K-slot -> reference channel / position in the stem's tensor-major order (-1: none)
-  float *mx_pages = nullptr;                 // device: 64 zeros (out-of-image reads)
-  unsigned long long *mx_prof = nullptr;     // PNVO_STEM_DBG=9: per-wave phase cycle sums of stem_mx / stem_ps
+  DevBuf<float> mx_pages;                    // 64 zeros (out-of-image reads)
+  DevBuf<unsigned long long> mx_prof;        // PNVO_STEM_DBG=9: per-wave phase cycle sums of stem_mx / stem_ps
   bool mx_prof_rs = false;                   //   ... the last stem launch was the resident-weight form
   int num_cus = 256;                         // compute units of the device (grid of the persistent kernels)
   bool train_mx = false;                     // the attached training step rebuilds the mx stem operands every step
   PnvoOptions opt;
   bool dense_sticky = false;                 // an input outside the mx/dd stems' contract was met: this handle stays on the dense stem
   int fallback_count = 0;                    // forwards re-run on the dense stem
-  float *stats_ds = nullptr;                 // GroupNorm partials of a downsample conv riding on its block's first conv (stats_floats)
+  DevBuf<float> stats_ds;                    // GroupNorm partials of a downsample conv riding on its block's first conv (stats_floats)
   hipEvent_t stem_ev = nullptr;              // recorded behind a contract-checking stem launch (pnvo_mark_stem)
   bool stem_ev_pending = false;
-  float *rawws[3] = {nullptr, nullptr, nullptr};   // rgb / depth / dd pair tensors of the materialising fallback of the raw entry
-  int rawws_cap = 0;
+  DevBuf<float> rawws[3];                    // rgb / depth / dd pair tensors of the materialising fallback of the raw entry
+  int rawws_cap = 0;                         // batch they are sized for
   int precision = 0;                         // pnvo_set_precision: 0 float32 (default), 1 bfloat16 (BASELINE config 3)
   unsigned long long load_gen = 0;           // bumped by pnvo_load_weights (operands derived lazily are rebuilt)
   unsigned long long weights_gen_at_load = 0;  // weights_gen as pnvo_load_weights left it
@@ -153,14 +156,11 @@ struct pnvo_model_s {
   void *bf = nullptr;                        // Bf16State (pnvo_bf16.hip)
 
   int cap = 0;                       // batch the workspace is sized for
-  float *xin = nullptr, *stem_raw = nullptr, *bufY[2] = {nullptr, nullptr};
-  float *rawA = nullptr, *rawB = nullptr, *rawD = nullptr, *rawC = nullptr, *comp_raw = nullptr, *hid = nullptr,
-        *stats = nullptr;
+  DevBuf<float> xin, stem_raw, bufY[2];
+  DevBuf<float> rawA, rawB, rawD, rawC, comp_raw, hid, stats;
   bool bottleneck = false;           // resnet50 / resnet101 backbone
-  float *ssA[2] = {nullptr, nullptr}, *ssB[2] = {nullptr, nullptr}, *ssD[2] = {nullptr, nullptr},
-        *ssC[2] = {nullptr, nullptr};
-  float *tapbuf = nullptr;
-  size_t tapbuf_floats = 0;
+  DevPair<float> ssA, ssB, ssD, ssC;
+  DevBuf<float> tapbuf;
 
   std::string tap_name;
   float *tap_dst = nullptr;
@@ -180,7 +180,7 @@ struct pnvo_model_s {
   };
   std::vector<GraphEntry> graphs;
   std::vector<GraphEntry> seen;      // call shapes met once (captured when they come back: no capture for one-off calls)
-  float *out_ws = nullptr;           // [cap, out_dim]: the graph's output (copied to the caller's tensor after replay)
+  DevBuf<float> out_ws;              // [cap, out_dim]: the graph's output (copied to the caller's tensor after replay)
   hipStream_t cap_stream = nullptr;
   int graph_mode = -1;               // -1: read PNVO_GRAPH on first use; 0 off; 1 on
   unsigned long long graph_clock = 0;
@@ -322,7 +322,6 @@ int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots
 void pnvo_small_free(pnvo_handle m);
 int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float *const *outs);   // outs[z]: model z's output (r.out unused)
 int pnvo_fail(pnvo_handle h, int code, const std::string &msg);
-void pnvo_free_dev(float *&p);
 int pnvo_ensure_workspace(pnvo_handle m, int B);
 void pnvo_drop_graphs(pnvo_handle m);   // forget the captured forward graphs (their kernel arguments went stale)
 

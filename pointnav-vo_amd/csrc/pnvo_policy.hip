@@ -223,24 +223,10 @@ __global__ __launch_bounds__(256) void policy_heads_kernel(const float *x, const
   }
 }
 
-int upload(float *&dst, const float *src, size_t n) {
-  dfree(dst);
-  PCHK(hipMalloc((void **)&dst, n * sizeof(float)));
-  PCHK(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-  return PNVO_OK;
-}
-
 }  // namespace
 }  // namespace pnvo
 
 using namespace pnvo;
-
-void pnvo::pnvo_policy_free_weights(Policy &p) {
-  for (const PolicyParam &e : policy_params(p)) {
-    if (!p.attached) dfree(*e.slot);
-    *e.slot = nullptr;
-  }
-}
 
 hipError_t pnvo::launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks,
                                       int rows, float *x, int *rows_out, float *g3, hipStream_t s) {
@@ -383,10 +369,14 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
     if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   }
   // ---- recurrent part and heads (kept in torch's layouts)
-  for (const PolicyParam &e : policy_params(p)) {
-    const pnvo_tensor_desc *d = policy_find(toc, ntoc, e, n_floats, &rc);
+  const std::vector<PolicyParam> tab = policy_params(p);
+  p.owned.resize(tab.size());
+  for (size_t i = 0; i < tab.size(); ++i) {
+    const pnvo_tensor_desc *d = policy_find(toc, ntoc, tab[i], n_floats, &rc);
     if (!d) return rc;
-    if ((rc = upload(*e.slot, blob + d->offset, numel(e.shape))) != PNVO_OK) return rc;
+    PCHK(p.owned[i].alloc(numel(tab[i].shape)));
+    PCHK(hipMemcpy(p.owned[i], blob + d->offset, numel(tab[i].shape) * sizeof(float), hipMemcpyHostToDevice));
+    *tab[i].slot = p.owned[i];
   }
   p.loaded = true;
   return PNVO_OK;
@@ -409,12 +399,10 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   if (B > p.cap) {
-    dfree(p.pooled);
-    dfree(p.visual);
-    dfree(p.x);
-    PCHK(hipMalloc((void **)&p.pooled, (size_t)B * (c.height / 2) * (c.width / 2) * 2 * sizeof(float)));
-    PCHK(hipMalloc((void **)&p.visual, (size_t)B * Hd * sizeof(float)));
-    PCHK(hipMalloc((void **)&p.x, (size_t)B * K0 * sizeof(float)));
+    for (DevBuf<float> *b : {&p.pooled, &p.visual, &p.x}) b->reset();   // the old workspace goes first
+    PCHK(p.pooled.alloc((size_t)B * (c.height / 2) * (c.width / 2) * 2));
+    PCHK(p.visual.alloc((size_t)B * Hd));
+    PCHK(p.x.alloc((size_t)B * K0));
     p.cap = B;
   }
   int rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream);
@@ -458,10 +446,6 @@ int pnvo_policy_destroy(pnvo_policy_handle h) {
   (void)hipSetDevice(p.device);
   pnvo_policy_train_free(p);
   if (p.enc) pnvo_destroy(p.enc);
-  pnvo_policy_free_weights(p);
-  dfree(p.pooled);
-  dfree(p.visual);
-  dfree(p.x);
   delete h;
   return PNVO_OK;
 }

@@ -17,16 +17,17 @@ struct Policy {
   int device = 0;
   pnvo_handle enc = nullptr;
   bool loaded = false;
-  // device weights (torch layouts), listed once in policy_params(): owned copies, or — once a train step is attached — pointers into
-  // the caller's flat buffer
+  // device weights (torch layouts), listed once in policy_params(): views of the copies in `owned`, or — once a train step is
+  // attached — of the caller's flat buffer
   float *emb = nullptr, *tgt_w = nullptr, *tgt_b = nullptr;
   std::vector<float *> w_ih, w_hh, b_ih, b_hh;       // one per recurrent layer
   float *act_w = nullptr, *act_b = nullptr, *cr_w = nullptr, *cr_b = nullptr;
-  bool attached = false;             // pnvo_policy_train_attach: the weight pointers above are not owned
+  std::vector<DevBuf<float>> owned;  // pnvo_policy_load_weights' copies, in policy_params() order; empty once a train step is attached
+  bool attached = false;             // pnvo_policy_train_attach: the parameters live in the caller's flat buffer
   PolicyTrain *train = nullptr;
   // workspace
   int cap = 0;
-  float *pooled = nullptr, *visual = nullptr, *x = nullptr;
+  DevBuf<float> pooled, visual, x;
 };
 
 // ---- the policy-owned tensors (everything but the visual encoder and visual_fc, which live in the encoder handle), in state_dict order
@@ -86,7 +87,6 @@ std::vector<pnvo_tensor_desc> encoder_toc(const std::vector<EncoderEntry> &entri
 // entry `e` of the parameter table in the caller's toc, with its full shape and range checked; nullptr with *rc set otherwise
 const pnvo_tensor_desc *policy_find(const pnvo_tensor_desc *toc, int ntoc, const PolicyParam &e, size_t n_floats, int *rc);
 
-void pnvo_policy_free_weights(Policy &p);     // pnvo_policy.hip: frees the owned copies (no-op on borrowed pointers) and nulls them
 void pnvo_policy_train_free(Policy &p);       // policy_train.hip
 // pnvo_policy.hip: x [rows, hidden + 64] = visual | tgt_embeding(goal) | prev_action_embedding; rows_out / g3 (optional, the update step's)
 // keep the gathered embedding row and (rho, cos(-phi), sin(-phi)) per row
@@ -101,12 +101,6 @@ inline int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, c
     hipError_t e__ = (expr);                                                                    \
     if (e__ != hipSuccess) return pfail(PNVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
   } while (0)
-
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 
 // The recurrent kernels write h_out / c_out rows while other workgroups still read h_prev / c_prev: the two states must not share memory.
 inline bool hidden_states_overlap(const float *in, const float *out, size_t floats) {

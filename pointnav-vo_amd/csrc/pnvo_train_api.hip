@@ -17,13 +17,14 @@ using namespace pnvo;
 namespace {
 
 struct PackMap {
-  float *dst;
-  int *map;
-  long n;
+  float *dst;             // an operand buffer of the handle (not owned)
+  DevBuf<int> map;
 };
 
 struct ConvSave {
-  float *raw = nullptr, *ss[2] = {nullptr, nullptr}, *mu = nullptr, *rstd = nullptr;
+  DevBuf<float> raw;
+  DevPair<float> ss;
+  DevBuf<float> mu, rstd;
 };
 
 struct TocEnt {
@@ -33,49 +34,48 @@ struct TocEnt {
 };
 
 struct TrainState {
-  float *params = nullptr, *grads = nullptr;
+  float *params = nullptr, *grads = nullptr;   // the caller's flat buffers (not owned)
   size_t n = 0;
   std::map<std::string, TocEnt> toc;
   std::vector<PackMap> maps;
-  std::vector<float *> dgrad_w;     // per conv of m->convs (nullptr for the stem: no input gradient)
-  std::vector<std::array<float *, 4>> dgrad_wph;   // stride-2 3x3 convs: one sub-kernel per output parity phase (ph*2 + pw)
-  std::vector<unsigned short *> dgrad_x3;          // 3x3 stride-1 convs: three-piece operand of the backward-data conv (conv_x3.hip)
+  std::vector<DevBuf<float>> dgrad_w;     // per conv of m->convs (nullptr for the stem: no input gradient)
+  std::vector<std::array<DevBuf<float>, 4>> dgrad_wph;   // stride-2 3x3 convs: one sub-kernel per output parity phase (ph*2 + pw)
+  std::vector<DevBuf<unsigned short>> dgrad_x3;          // 3x3 stride-1 convs: three-piece operand of the backward-data conv (conv_x3.hip)
   std::vector<unsigned long long> dgrad_x3_gen;    //   ... built from the flat parameters when m->weights_gen moved
-  std::vector<unsigned short *> dgrad_x2;          //   ... and its two-piece float16 form (option train_pieces = 2)
+  std::vector<DevBuf<unsigned short>> dgrad_x2;          //   ... and its two-piece float16 form (option train_pieces = 2)
   std::vector<unsigned long long> dgrad_x2_gen;
-  unsigned *dmax = nullptr;                        // per conv: float bits of max |dRaw| of the backward in flight (gn_bwd_apply)
-  float *fc_t = nullptr, *head_t = nullptr;
-  int *d_ref_of_new = nullptr, *d_tensor_of_new = nullptr, *d_ciperm = nullptr;
-  GatherSeg *d_segs = nullptr;      // all re-pack maps as one segment table (pnvo_train_refresh)
+  DevBuf<unsigned> dmax;                           // per conv: float bits of max |dRaw| of the backward in flight (gn_bwd_apply)
+  DevBuf<float> fc_t, head_t;
+  DevBuf<int> d_ref_of_new, d_tensor_of_new, d_ciperm;
+  DevBuf<GatherSeg> d_segs;         // all re-pack maps as one segment table (pnvo_train_refresh)
   long seg_total = 0;
   int nseg = 0;
-  int *d_mxmaps = nullptr;          // mx stem: [slot_ref 32 | slot_new 32 | xslot 4]
-  int *d_ddmaps = nullptr;          // one-hot stem: [dense_ref 12 | dense_new 12 | dd_ref 2*bins | dd_new 2*bins]
+  DevBuf<int> d_mxmaps;             // mx stem: [slot_ref 32 | slot_new 32 | xslot 4]
+  DevBuf<int> d_ddmaps;             // one-hot stem: [dense_ref 12 | dense_new 12 | dd_ref 2*bins | dd_new 2*bins]
   int dd_nd = 0;
   size_t stem_w_off = 0;            // offset of the OIHW stem weight in the flat parameter buffer
   // saved activations (sized for capB)
   int capB = 0;
   int lastB = 0;
   std::vector<ConvSave> cs;
-  std::vector<float *> y;           // y[0] = pooled stem output, y[k] = output of residual block k
-  unsigned char *pool_idx = nullptr;
-  float *hid = nullptr;
+  std::vector<DevBuf<float>> y;     // y[0] = pooled stem output, y[k] = output of residual block k
+  DevBuf<unsigned char> pool_idx;
+  DevBuf<float> hid;
   const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // observation tensors of the last forward
   // scratch
-  float *dYa = nullptr, *dYb = nullptr, *G = nullptr, *dRaw = nullptr, *dA = nullptr, *dStem = nullptr;
-  float *dout8 = nullptr, *dh = nullptr, *gh = nullptr, *dz = nullptr;
-  float *gn_part = nullptr, *gn_coef = nullptr, *wg_partial = nullptr;
-  size_t wg_partial_floats = 0;
-  double *mom_part = nullptr;
+  DevBuf<float> dYa, dYb, G, dRaw, dA, dStem;
+  DevBuf<float> dout8, dh, gh, dz;
+  DevBuf<float> gn_part, gn_coef, wg_partial;
+  DevBuf<double> mom_part;
   // dropout (pnvo_train_set_dropout): p, seed, forward counter; dropped activations of the last forward
   float drop_p = 0.f;
   uint64_t drop_seed = 0, drop_step = 0;
-  float *zdrop = nullptr, *hdrop = nullptr, *dmask = nullptr;
+  DevBuf<float> zdrop, hdrop, dmask;
   // action-embedding variants: the Linear's 32 embedding columns as per-sample bias rows (train_kernels.hip embed_*)
   const long long *actions = nullptr;   // device [B], set by pnvo_train_set_actions for the next forward/backward
-  float *egath = nullptr, *efeat = nullptr, *biasB = nullptr, *dfeat = nullptr;
-  int64_t *iota = nullptr;
-  int *embed_err = nullptr;             // host-mapped flag: action outside the embedding table
+  DevBuf<float> egath, efeat, biasB, dfeat;
+  DevBuf<int64_t> iota;
+  DevBuf<int> embed_err;                // host-mapped flag: action outside the embedding table
   size_t w1_off = 0, b1_off = 0, emb_off = 0;
   long w1_pitch = 0;
   // gradient-ready hook (pnvo_train_set_grad_hook): the backward reports flat ranges [first, first + count) whose gradients
@@ -87,30 +87,20 @@ struct TrainState {
   // two-piece float16 operands of the training forward's convs: per conv weight {scale, 1/scale}, recomputed from the flat
   // parameters by ONE launch per pnvo_train_refresh (conv_x3.hip conv_x2_scale_kernel)
   std::map<std::string, int> x2_index;  // conv weight name -> row of x2_scale
-  long *x2_seg = nullptr;               // device [rows][2]: flat offset, element count
-  float *x2_scale = nullptr;            // device [rows][2]
+  DevBuf<long> x2_seg;                  // [rows][2]: flat offset, element count
+  DevBuf<float> x2_scale;               // [rows][2]
   // GroupNorm bounds behind Layer::in_bound (the range guard of the float16 pieces), tracked while gamma / beta move: one small
   // launch per pnvo_train_refresh writes max_c (|gamma_c| sqrt(N) + |beta_c|) per conv into host-mapped memory; the next training
   // forward chains them into in_bound without a synchronisation (a value may lag one optimiser step: a step moves gamma by <= lr)
   struct GnbSeg { long goff, boff; int c; float rootn; };
-  GnbSeg *gnb_seg = nullptr;            // device [convs]
-  float *gnb_host = nullptr;            // host-mapped [3][convs]: the bounds of the last three refreshes (ring); < 0: not computed yet
+  DevBuf<GnbSeg> gnb_seg;               // [convs]
+  DevBuf<float> gnb_host;               // host-mapped [3][convs]: the bounds of the last three refreshes (ring); < 0: not computed yet
   hipEvent_t gnb_ev[3] = {nullptr, nullptr, nullptr};   // behind the gn_bound_kernel of each ring entry
   long gnb_refreshes = 0;               // refreshes issued so far: entry (r % 3) holds refresh r
   int gnb_n = 0;
 };
 
 TrainState *TS(pnvo_handle m) { return reinterpret_cast<TrainState *>(m->train); }
-
-int dmalloc(pnvo_handle m, void **p, size_t bytes) {
-  HIPCHK(m, hipMalloc(p, bytes ? bytes : 16));
-  return PNVO_OK;
-}
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 
 // float "index tensor" of a parameter: value = flat offset + 1 (exact in fp32 below 2^24 elements)
 std::vector<float> index_tensor(const TocEnt &e) {
@@ -124,12 +114,8 @@ int add_map(pnvo_handle m, TrainState *t, float *dst, const std::vector<float> &
   for (size_t i = 0; i < mp.size(); ++i) mp[i] = (int)packed_idx[i];
   PackMap pm;
   pm.dst = dst;
-  pm.n = (long)mp.size();
-  pm.map = nullptr;
-  int rc = dmalloc(m, (void **)&pm.map, mp.size() * sizeof(int));
-  if (rc != PNVO_OK) return rc;
-  HIPCHK(m, hipMemcpy(pm.map, mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
-  t->maps.push_back(pm);
+  HIPCHK(m, pm.map.upload(mp.data(), mp.size()));
+  t->maps.push_back(std::move(pm));
   return PNVO_OK;
 }
 
@@ -156,11 +142,11 @@ std::vector<float> transpose_flip(const std::vector<float> &w, int cout, int cin
 int build_maps(pnvo_handle m, TrainState *t) {
   int rc = PNVO_OK;
   const pnvo_config &c = m->cfg;
-  t->dgrad_w.assign(m->convs.size(), nullptr);
-  t->dgrad_wph.assign(m->convs.size(), std::array<float *, 4>{nullptr, nullptr, nullptr, nullptr});
-  t->dgrad_x3.assign(m->convs.size(), nullptr);
+  t->dgrad_w.resize(m->convs.size());
+  t->dgrad_wph.resize(m->convs.size());
+  t->dgrad_x3.resize(m->convs.size());
   t->dgrad_x3_gen.assign(m->convs.size(), 0);
-  t->dgrad_x2.assign(m->convs.size(), nullptr);
+  t->dgrad_x2.resize(m->convs.size());
   t->dgrad_x2_gen.assign(m->convs.size(), 0);
   for (size_t li = 0; li < m->convs.size(); ++li) {
     Layer &l = m->convs[li];
@@ -189,7 +175,7 @@ int build_maps(pnvo_handle m, TrainState *t) {
       const std::vector<float> wt = transpose_flip(idx, l.cout, l.cin, l.k, l.kw);
       std::vector<float> pkt;
       pnvo_pack_conv_weight_cinp(wt.data(), l.cin, l.cout, l.coutp, l.k, l.kw, pkt);
-      if ((rc = dmalloc(m, (void **)&t->dgrad_w[li], pkt.size() * sizeof(float))) != PNVO_OK) return rc;
+      HIPCHK(m, t->dgrad_w[li].alloc(pkt.size()));
       if ((rc = add_map(m, t, t->dgrad_w[li], pkt)) != PNVO_OK) return rc;
       if (l.stride == 2 && l.k == 3 && l.kw == 3 && l.pad == 1) {
         // dX[2i+ph] = sum over the taps whose source row (2i+ph-1+kh)/2 is an integer: kh = 1 (ph = 0) or kh = 0, 2
@@ -206,8 +192,8 @@ int build_maps(pnvo_handle m, TrainState *t) {
                     sub[(((size_t)ci * l.cout + co) * nh + a) * nw + b] = wt[(((size_t)ci * l.cout + co) * 3 + th[a]) * 3 + tw[b]];
             std::vector<float> pks;
             pnvo_pack_conv_weight_cinp(sub.data(), l.cin, l.cout, l.coutp, nh, nw, pks);
-            float *&dst = t->dgrad_wph[li][ph * 2 + pw];
-            if ((rc = dmalloc(m, (void **)&dst, pks.size() * sizeof(float))) != PNVO_OK) return rc;
+            DevBuf<float> &dst = t->dgrad_wph[li][ph * 2 + pw];
+            HIPCHK(m, dst.alloc(pks.size()));
             if ((rc = add_map(m, t, dst, pks)) != PNVO_OK) return rc;
           }
       }
@@ -240,7 +226,7 @@ int build_maps(pnvo_handle m, TrainState *t) {
     if (emb->shape.size() != 2 || emb->shape[0] != c.n_acts + 1 || emb->shape[1] != 32)
       return pnvo_fail(m, PNVO_ERR_ARG, "action_embedding.weight must be [n_acts + 1, 32]");
     t->emb_off = emb->off;
-    if (!t->embed_err) HIPCHK(m, hipHostMalloc((void **)&t->embed_err, sizeof(int), hipHostMallocMapped));
+    if (!t->embed_err) HIPCHK(m, t->embed_err.alloc_host(1, hipHostMallocMapped));
     *t->embed_err = 0;
   }
   {
@@ -263,14 +249,14 @@ int build_maps(pnvo_handle m, TrainState *t) {
         for (int tap = 0; tap < T; ++tap)
           wt[((size_t)tap * m->comp_cp + ch) * c.hidden + o] = i1[(size_t)o * flat + (size_t)ch * T + tap];
     pnvo_pack_conv_weight_cinp(wt.data(), T * m->comp_cp, c.hidden, c.hidden, 1, 1, pk);
-    if ((rc = dmalloc(m, (void **)&t->fc_t, pk.size() * sizeof(float))) != PNVO_OK) return rc;
+    HIPCHK(m, t->fc_t.alloc(pk.size()));
     if ((rc = add_map(m, t, t->fc_t, pk)) != PNVO_OK) return rc;
     // dh = dOut . W2: CIN' = 8 (out_dim padded), COUT' = hidden, W'[o][d] = W2[d][o]
     std::vector<float> ht((size_t)c.hidden * c.out_dim);
     for (int o = 0; o < c.hidden; ++o)
       for (int d = 0; d < c.out_dim; ++d) ht[(size_t)o * c.out_dim + d] = i2[(size_t)d * c.hidden + o];
     pnvo_pack_conv_weight_cinp(ht.data(), c.hidden, c.out_dim, rup(c.out_dim, 8), 1, 1, pk);
-    if ((rc = dmalloc(m, (void **)&t->head_t, pk.size() * sizeof(float))) != PNVO_OK) return rc;
+    HIPCHK(m, t->head_t.alloc(pk.size()));
     if ((rc = add_map(m, t, t->head_t, pk)) != PNVO_OK) return rc;
   }
   // stem channel tables on device
@@ -279,9 +265,9 @@ int build_maps(pnvo_handle m, TrainState *t) {
     ron[k] = m->stem_ref_of_new[k];
     ton[k] = m->stem_tensor_of_new[k];
   }
-  if ((rc = dmalloc(m, (void **)&t->d_ref_of_new, m->CPL * sizeof(int))) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->d_tensor_of_new, m->CPL * sizeof(int))) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->d_ciperm, 32 * sizeof(int))) != PNVO_OK) return rc;
+  HIPCHK(m, t->d_ref_of_new.alloc(m->CPL));
+  HIPCHK(m, t->d_tensor_of_new.alloc(m->CPL));
+  HIPCHK(m, t->d_ciperm.alloc(32));
   std::vector<int> perm(32, -1);
   for (int k = 0; k < m->CP && k < 32; ++k) perm[k] = m->stem_ref_of_new[k];
   HIPCHK(m, hipMemcpy(t->d_ref_of_new, ron.data(), m->CPL * sizeof(int), hipMemcpyHostToDevice));
@@ -295,7 +281,7 @@ int build_maps(pnvo_handle m, TrainState *t) {
       mp[32 + k] = m->mx_slot_new[k];
     }
     for (int x = 0; x < 4; ++x) mp[64 + x] = m->mx_xslot[x];
-    if ((rc = dmalloc(m, (void **)&t->d_mxmaps, mp.size() * sizeof(int))) != PNVO_OK) return rc;
+    HIPCHK(m, t->d_mxmaps.alloc(mp.size()));
     HIPCHK(m, hipMemcpy(t->d_mxmaps, mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
     auto it = t->toc.find(m->convs[0].name + ".weight");
     if (it == t->toc.end()) return pnvo_fail(m, PNVO_ERR_WEIGHTS, "stem weight missing from the parameter table");
@@ -324,7 +310,7 @@ int build_maps(pnvo_handle m, TrainState *t) {
       mp[24 + 2 * bins + k] = nc;
     }
     t->dd_nd = nd;
-    if ((rc = dmalloc(m, (void **)&t->d_ddmaps, mp.size() * sizeof(int))) != PNVO_OK) return rc;
+    HIPCHK(m, t->d_ddmaps.alloc(mp.size()));
     HIPCHK(m, hipMemcpy(t->d_ddmaps, mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
     auto it = t->toc.find(m->convs[0].name + ".weight");
     if (it == t->toc.end()) return pnvo_fail(m, PNVO_ERR_WEIGHTS, "stem weight missing from the parameter table");
@@ -341,7 +327,7 @@ int refresh_stem_dd(pnvo_handle m, TrainState *t, hipStream_t s) {
                                     t->d_mxmaps + 64, m->mx_wpk3, s));
     if (m->opt.train_pieces == 2 && m->mx_wpk2 != nullptr) {      // the float16 operand of the training forward, with its own scale
       if (!m->mx_scale2_dev) {                    // {scale, 1/scale, integer maximum of the folded weights (zero between calls)}
-        HIPCHK(m, hipMalloc((void **)&m->mx_scale2_dev, 4 * sizeof(float)));
+        HIPCHK(m, m->mx_scale2_dev.alloc(4));
         HIPCHK(m, hipMemset(m->mx_scale2_dev, 0, 4 * sizeof(float)));
       }
       HIPCHK(m, launch_stem_mx_repack_h(t->params + t->stem_w_off, m->convs[0].cin, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32,
@@ -358,41 +344,16 @@ int refresh_stem_dd(pnvo_handle m, TrainState *t, hipStream_t s) {
   return PNVO_OK;
 }
 
+// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves capB = 0.
 void free_train_ws(TrainState *t) {
-  for (auto &c : t->cs) {
-    dfree(c.raw);
-    dfree(c.ss[0]);
-    dfree(c.ss[1]);
-    dfree(c.mu);
-    dfree(c.rstd);
-  }
   t->cs.clear();
-  for (auto &p : t->y) dfree(p);
   t->y.clear();
-  dfree(t->pool_idx);
-  dfree(t->hid);
-  dfree(t->dYa);
-  dfree(t->dYb);
-  dfree(t->G);
-  dfree(t->dRaw);
-  dfree(t->dA);
-  dfree(t->dStem);
-  dfree(t->dout8);
-  dfree(t->dh);
-  dfree(t->gh);
-  dfree(t->dz);
-  dfree(t->gn_part);
-  dfree(t->gn_coef);
-  dfree(t->wg_partial);
-  dfree(t->mom_part);
-  dfree(t->zdrop);
-  dfree(t->hdrop);
-  dfree(t->dmask);
-  dfree(t->egath);
-  dfree(t->efeat);
-  dfree(t->biasB);
-  dfree(t->dfeat);
-  dfree(t->iota);
+  for (DevBuf<float> *b : {&t->hid, &t->dYa, &t->dYb, &t->G, &t->dRaw, &t->dA, &t->dStem, &t->dout8, &t->dh, &t->gh, &t->dz, &t->gn_part,
+                           &t->gn_coef, &t->wg_partial, &t->zdrop, &t->hdrop, &t->dmask, &t->egath, &t->efeat, &t->biasB, &t->dfeat})
+    b->reset();
+  t->pool_idx.reset();
+  t->mom_part.reset();
+  t->iota.reset();
   t->capB = 0;
 }
 
@@ -433,13 +394,13 @@ int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
     const Layer &l = m->convs[li];
     ConvSave &s = t->cs[li];
     const size_t n = (size_t)B * l.hout * l.wout * l.coutp;
-    if ((rc = dmalloc(m, (void **)&s.raw, n * 4)) != PNVO_OK) return rc;
+    HIPCHK(m, s.raw.alloc(n));
     for (int k = 0; k < 2; ++k) {
-      if ((rc = dmalloc(m, (void **)&s.ss[k], (size_t)B * l.coutp * 4)) != PNVO_OK) return rc;
+      HIPCHK(m, s.ss.alloc(k, (size_t)B * l.coutp));
       HIPCHK(m, hipMemset(s.ss[k], 0, (size_t)B * l.coutp * 4));
     }
-    if ((rc = dmalloc(m, (void **)&s.mu, (size_t)B * l.groups * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&s.rstd, (size_t)B * l.groups * 4)) != PNVO_OK) return rc;
+    HIPCHK(m, s.mu.alloc((size_t)B * l.groups));
+    HIPCHK(m, s.rstd.alloc((size_t)B * l.groups));
     WgradArgs a = wgrad_args(l, B, li == 0 ? 32 : l.cin, l.coutp, li == 0 ? 2 : 0);
     wgmax = std::max(wgmax, wgrad_partial_floats(a));
   }
@@ -459,18 +420,17 @@ int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
     wgrad_stem_mx_plan(a);
     wgmax = std::max(wgmax, wgrad_stem_mx_scratch_floats(a));
   }
-  t->wg_partial_floats = wgmax;
-  if ((rc = dmalloc(m, (void **)&t->wg_partial, wgmax * 4)) != PNVO_OK) return rc;
+  HIPCHK(m, t->wg_partial.alloc(wgmax));
   // block outputs: y[0] = pooled stem output, y[k] = output of m->blocks[k - 1]
   size_t act = (size_t)B * m->Hp * m->Wp * c.baseplanes;
   const size_t stem = (size_t)B * m->Hs * m->Ws * c.baseplanes;
   {
-    t->y.assign(m->blocks.size() + 1, nullptr);
-    if ((rc = dmalloc(m, (void **)&t->y[0], act * 4)) != PNVO_OK) return rc;
+    t->y.resize(m->blocks.size() + 1);
+    HIPCHK(m, t->y[0].alloc(act));
     for (size_t k = 1; k <= m->blocks.size(); ++k) {
       const Layer &last = m->last(m->blocks[k - 1]);
       const size_t n = (size_t)B * last.hout * last.wout * last.coutp;
-      if ((rc = dmalloc(m, (void **)&t->y[k], n * 4)) != PNVO_OK) return rc;
+      HIPCHK(m, t->y[k].alloc(n));
     }
     for (size_t k = 1; k < m->convs.size(); ++k) {      // scratch gradients are as large as the largest activation
       const Layer &l = m->convs[k];
@@ -478,39 +438,39 @@ int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
       act = std::max(act, (size_t)B * l.hin * l.win * l.cinp);
     }
   }
-  if ((rc = dmalloc(m, (void **)&t->pool_idx, act)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->hid, (size_t)B * c.hidden * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dYa, act * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dYb, act * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->G, act * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dRaw, act * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dA, act * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dStem, stem * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dout8, (size_t)B * 8 * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dh, (size_t)B * c.hidden * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->gh, (size_t)B * c.hidden * 4)) != PNVO_OK) return rc;
-  if ((rc = dmalloc(m, (void **)&t->dz, (size_t)B * m->fh * m->fw * m->comp_cp * 4)) != PNVO_OK) return rc;
+  HIPCHK(m, t->pool_idx.alloc(act));
+  HIPCHK(m, t->hid.alloc((size_t)B * c.hidden));
+  HIPCHK(m, t->dYa.alloc(act));
+  HIPCHK(m, t->dYb.alloc(act));
+  HIPCHK(m, t->G.alloc(act));
+  HIPCHK(m, t->dRaw.alloc(act));
+  HIPCHK(m, t->dA.alloc(act));
+  HIPCHK(m, t->dStem.alloc(stem));
+  HIPCHK(m, t->dout8.alloc((size_t)B * 8));
+  HIPCHK(m, t->dh.alloc((size_t)B * c.hidden));
+  HIPCHK(m, t->gh.alloc((size_t)B * c.hidden));
+  HIPCHK(m, t->dz.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
   int maxc = m->comp_cp, maxg = 1;
   for (const Layer &l : m->convs) {
     maxc = std::max(maxc, l.coutp);
     maxg = std::max(maxg, l.groups);
   }
-  if ((rc = dmalloc(m, (void **)&t->gn_part, (size_t)B * 65 * maxc * 2 * 4)) != PNVO_OK) return rc;   // 64 chunks + [B][C][2]
-  if ((rc = dmalloc(m, (void **)&t->gn_coef, (size_t)B * maxg * 2 * 4)) != PNVO_OK) return rc;
+  HIPCHK(m, t->gn_part.alloc((size_t)B * 65 * maxc * 2));   // 64 chunks + [B][C][2]
+  HIPCHK(m, t->gn_coef.alloc((size_t)B * maxg * 2));
   {
     const size_t zf = (size_t)B * m->fh * m->fw * m->comp_cp, hf = (size_t)B * c.hidden;
-    if ((rc = dmalloc(m, (void **)&t->zdrop, zf * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->hdrop, hf * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->dmask, (zf > hf ? zf : hf) * 4)) != PNVO_OK) return rc;
+    HIPCHK(m, t->zdrop.alloc(zf));
+    HIPCHK(m, t->hdrop.alloc(hf));
+    HIPCHK(m, t->dmask.alloc(zf > hf ? zf : hf));
   }
-  if ((rc = dmalloc(m, (void **)&t->mom_part, (size_t)128 * MOMENTS_BLOCKS * 8)) != PNVO_OK) return rc;
+  HIPCHK(m, t->mom_part.alloc((size_t)128 * MOMENTS_BLOCKS));
   if (c.act_embed) {
     const int rows = std::max(B, c.n_acts + 1);
-    if ((rc = dmalloc(m, (void **)&t->egath, (size_t)rows * 32 * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->efeat, (size_t)rows * 32 * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->dfeat, (size_t)rows * 32 * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->biasB, (size_t)rows * c.hidden * 4)) != PNVO_OK) return rc;
-    if ((rc = dmalloc(m, (void **)&t->iota, (size_t)rows * 8)) != PNVO_OK) return rc;
+    HIPCHK(m, t->egath.alloc((size_t)rows * 32));
+    HIPCHK(m, t->efeat.alloc((size_t)rows * 32));
+    HIPCHK(m, t->dfeat.alloc((size_t)rows * 32));
+    HIPCHK(m, t->biasB.alloc((size_t)rows * c.hidden));
+    HIPCHK(m, t->iota.alloc((size_t)rows));
     std::vector<int64_t> io(rows);
     for (int k = 0; k < rows; ++k) io[k] = k;
     HIPCHK(m, hipMemcpy(t->iota, io.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
@@ -590,8 +550,7 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
         if (!t->dgrad_x2[li] || t->dgrad_x2_gen[li] != m->weights_gen) {
           const size_t nel = (size_t)9 * l.coutp * l.cin * 2;
           if (!t->dgrad_x2[li]) {
-            int rc = dmalloc(m, (void **)&t->dgrad_x2[li], nel * 2);
-            if (rc != PNVO_OK) return rc;
+            HIPCHK(m, t->dgrad_x2[li].alloc(nel));
           }
           HIPCHK(m, launch_conv_x2_repack(t->params + it->second.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, wsc, t->dgrad_x2[li], s, 1));
           t->dgrad_x2_gen[li] = m->weights_gen;
@@ -608,8 +567,7 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
       if (!t->dgrad_x3[li] || t->dgrad_x3_gen[li] != m->weights_gen) {
         const size_t nel = (size_t)9 * l.coutp * l.cin * 3;
         if (!t->dgrad_x3[li]) {
-          int rc = dmalloc(m, (void **)&t->dgrad_x3[li], nel * 2);
-          if (rc != PNVO_OK) return rc;
+          HIPCHK(m, t->dgrad_x3[li].alloc(nel));
         }
         HIPCHK(m, launch_conv_x3_repack(t->params + it->second.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, 1, t->dgrad_x3[li], s));
         t->dgrad_x3_gen[li] = m->weights_gen;
@@ -658,7 +616,7 @@ int run_wgrad(pnvo_handle m, TrainState *t, WgradArgs &a, const std::string &pna
   int rc = PNVO_OK;
   float *g = gradp(m, t, pname, &rc);
   if (!g) return rc;
-  if (wgrad_partial_floats(a) > t->wg_partial_floats) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+  if (wgrad_partial_floats(a) > t->wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
   a.partial = t->wg_partial;
   a.zero_page = m->zero_page;
   PnvoTimed tm(m, s, "wgrad:" + pname, 2.0 * (double)a.B * a.Ho * a.Wo * a.COUT * a.CIN * a.KH * a.KW, 0.0);
@@ -685,27 +643,6 @@ int run_gn_bwd(pnvo_handle m, TrainState *t, size_t li, int B, const float *dout
 void pnvo_train_free(pnvo_handle m) {
   if (!m || !m->train) return;
   TrainState *t = TS(m);
-  free_train_ws(t);
-  for (auto &pm : t->maps) dfree(pm.map);
-  for (auto &p : t->dgrad_w) dfree(p);
-  for (auto &p : t->dgrad_x2) dfree(p);
-  dfree(t->dmax);
-  for (auto &q : t->dgrad_wph)
-    for (auto &p : q) dfree(p);
-  dfree(t->fc_t);
-  dfree(t->head_t);
-  dfree(t->d_ref_of_new);
-  dfree(t->d_ddmaps);
-  dfree(t->d_mxmaps);
-  for (unsigned short *&q : t->dgrad_x3) dfree(q);
-  dfree(t->d_segs);
-  dfree(t->x2_seg);
-  dfree(t->x2_scale);
-  dfree(t->d_tensor_of_new);
-  dfree(t->d_ciperm);
-  if (t->embed_err) (void)hipHostFree(t->embed_err);
-  dfree(t->gnb_seg);
-  if (t->gnb_host) (void)hipHostFree(t->gnb_host);
   for (hipEvent_t &e : t->gnb_ev)
     if (e) (void)hipEventDestroy(e);
   m->train_mx = false;
@@ -723,6 +660,10 @@ int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_float
   pnvo_train_free(m);
   TrainState *t = new TrainState();
   m->train = t;
+  auto failed = [&](int rc) {          // a failed attach leaves no training state behind
+    pnvo_train_free(m);
+    return rc;
+  };
   t->params = params;
   t->grads = grads;
   t->n = n_floats;
@@ -734,14 +675,11 @@ int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_float
       e.shape.push_back(toc[k].shape[d]);
       e.numel *= (size_t)toc[k].shape[d];
     }
-    if (e.off + e.numel > n_floats) return pnvo_fail(m, PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range");
+    if (e.off + e.numel > n_floats) return failed(pnvo_fail(m, PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range"));
     t->toc[toc[k].name] = e;
   }
   int rc = build_maps(m, t);
-  if (rc != PNVO_OK) {
-    pnvo_train_free(m);
-    return rc;
-  }
+  if (rc != PNVO_OK) return failed(rc);
   {
     // Buckets of the gradient-ready hook.  The backward finishes the parameters in the order head, hidden layer, compression,
     // layer4 ... layer1, stem; a range can be reported early when everything at or above its first offset belongs to layers
@@ -765,7 +703,8 @@ int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_float
     }
     t->bucket_first.push_back(0);
   }
-  return pnvo_train_refresh(m, nullptr);
+  rc = pnvo_train_refresh(m, nullptr);
+  return rc == PNVO_OK ? rc : failed(rc);
 }
 
 int pnvo_train_set_grad_hook(pnvo_handle m, pnvo_grad_ready_fn fn, void *user) {
@@ -843,12 +782,11 @@ int pnvo_train_refresh(pnvo_handle m, void *stream) {
     long start = 0;
     for (const PackMap &pm : t->maps) {
       segs.push_back(GatherSeg{pm.map, pm.dst, start});
-      start += pm.n;
+      start += (long)pm.map.size();
     }
     t->seg_total = start;
     t->nseg = (int)segs.size();
-    int rc0 = dmalloc(m, (void **)&t->d_segs, segs.size() * sizeof(GatherSeg));
-    if (rc0 != PNVO_OK) return rc0;
+    HIPCHK(m, t->d_segs.alloc(segs.size()));
     HIPCHK(m, hipMemcpy(t->d_segs, segs.data(), segs.size() * sizeof(GatherSeg), hipMemcpyHostToDevice));
   }
   HIPCHK(m, launch_gather_all(t->params, t->d_segs, t->nseg, t->seg_total, (hipStream_t)stream));
@@ -863,10 +801,9 @@ int pnvo_train_refresh(pnvo_handle m, void *stream) {
       seg.push_back((long)it->second.numel);
     }
     if (!seg.empty()) {
-      int rc0 = dmalloc(m, (void **)&t->x2_seg, seg.size() * sizeof(long));
-      if (rc0 != PNVO_OK) return rc0;
+      HIPCHK(m, t->x2_seg.alloc(seg.size()));
       // {scale, 1/scale} per conv + the integer maxima launch_conv_x2_scales reduces into (zero between calls)
-      if ((rc0 = dmalloc(m, (void **)&t->x2_scale, (seg.size() + seg.size() / 2) * sizeof(float))) != PNVO_OK) return rc0;
+      HIPCHK(m, t->x2_scale.alloc(seg.size() + seg.size() / 2));
       HIPCHK(m, hipMemset(t->x2_scale, 0, (seg.size() + seg.size() / 2) * sizeof(float)));
       HIPCHK(m, hipMemcpy(t->x2_seg, seg.data(), seg.size() * sizeof(long), hipMemcpyHostToDevice));
     }
@@ -883,10 +820,9 @@ int pnvo_train_refresh(pnvo_handle m, void *stream) {
                                      (float)std::sqrt((double)(l.cout / l.groups) * l.hout * l.wout)};
       }
       t->gnb_n = (int)seg.size();
-      int rc0 = dmalloc(m, (void **)&t->gnb_seg, seg.size() * sizeof(TrainState::GnbSeg));
-      if (rc0 != PNVO_OK) return rc0;
+      HIPCHK(m, t->gnb_seg.alloc(seg.size()));
       HIPCHK(m, hipMemcpy(t->gnb_seg, seg.data(), seg.size() * sizeof(TrainState::GnbSeg), hipMemcpyHostToDevice));
-      HIPCHK(m, hipHostMalloc((void **)&t->gnb_host, 3 * seg.size() * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+      HIPCHK(m, t->gnb_host.alloc_host(3 * seg.size(), hipHostMallocMapped | hipHostMallocCoherent));
       for (int i = 0; i < 3 * t->gnb_n; ++i) t->gnb_host[i] = -1.f;
       for (hipEvent_t &e : t->gnb_ev) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
@@ -1110,7 +1046,7 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
   int rc = PNVO_OK;
 
   if (!t->dmax && !m->bottleneck) {
-    if ((rc = dmalloc(m, (void **)&t->dmax, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned))) != PNVO_OK) return rc;
+    HIPCHK(m, t->dmax.alloc(m->convs.size() * PNVO_ABSMAX_UINTS));
   }
   if (t->dmax) HIPCHK(m, hipMemsetAsync(t->dmax, 0, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned), s));   // maxima of this backward's gradients
   // ---- output head: out = hid . W2^T + b2  (skipped when the caller supplies dLoss / dhid itself)
@@ -1301,7 +1237,7 @@ static int train_backward_body(pnvo_handle m, const float *grad_out, void *strea
       a.Ho = m->Hs;
       a.Wo = m->Ws;
       wgrad_stem_mx_plan(a);
-      if (wgrad_stem_mx_scratch_floats(a) > t->wg_partial_floats) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+      if (wgrad_stem_mx_scratch_floats(a) > t->wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
       int rc2 = PNVO_OK;
       float *g = gradp(m, t, l.name + ".weight", &rc2);
       if (!g) return rc2;

@@ -34,7 +34,7 @@
 namespace pnvo {
 
 struct PolicyTrain {
-  float *params = nullptr, *grads = nullptr;
+  float *params = nullptr, *grads = nullptr;   // the caller's flat buffers (not owned)
   size_t n = 0, n_named = 0;          // floats handed over / floats covered by the parameter table (the rest is the tail below)
   size_t o_stem = 0;                  // the policy's stem weight [C0,1,7,7] (the one tensor read here that is not a Policy slot)
   size_t o_stem2 = 0;                 // tail: the stem weight zero-padded to the encoder handle's 2 input channels [C0,2,7,7],
@@ -44,14 +44,14 @@ struct PolicyTrain {
   bool have_loss = false;
   // workspace, sized for capM rows
   int capM = 0;
-  float *pooled = nullptr, *enc_out = nullptr, *x0 = nullptr, *g3 = nullptr, *masks = nullptr, *hid0 = nullptr;
-  int *rows = nullptr;
-  int64_t *actions = nullptr;
-  std::vector<float *> gates, c, y, hm;
-  float *logits = nullptr, *value = nullptr, *logp = nullptr, *ent = nullptr, *dlogits = nullptr, *dvalue = nullptr;
-  float *dY = nullptr, *dX0 = nullptr, *dG = nullptr, *dC = nullptr, *whhT = nullptr;
-  float *dGh = nullptr;               // GRU only: the recurrent side's gate gradients [M, 3H] (dG holds the input side's; dC holds dh)
-  double *sq_part = nullptr;          // clip_grad_norm partial sums
+  DevBuf<float> pooled, enc_out, x0, g3, masks, hid0;
+  DevBuf<int> rows;
+  DevBuf<int64_t> actions;
+  std::vector<DevBuf<float>> gates, c, y, hm;
+  DevBuf<float> logits, value, logp, ent, dlogits, dvalue;
+  DevBuf<float> dY, dX0, dG, dC, whhT;
+  DevBuf<float> dGh;                  // GRU only: the recurrent side's gate gradients [M, 3H] (dG holds the input side's; dC holds dh)
+  DevBuf<double> sq_part;             // clip_grad_norm partial sums
   // pnvo_policy_train_timing: events at the phase boundaries of evaluate / ppo_loss / backward (tools/bench_ppo_update.py)
   bool timing = false;
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -605,28 +605,14 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float *g, long n, const
 // phase boundary k of the update step (only while timing is on)
 hipError_t mark(PolicyTrain *t, int k, hipStream_t s) { return t->timing ? hipEventRecord(t->ev[k], s) : hipSuccess; }
 
+// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves capM = 0.
 void free_ws(PolicyTrain *t) {
-  dfree(t->pooled);
-  dfree(t->enc_out);
-  dfree(t->x0);
-  dfree(t->g3);
-  dfree(t->masks);
-  dfree(t->hid0);
-  dfree(t->rows);
-  dfree(t->actions);
-  for (auto *v : {&t->gates, &t->c, &t->y, &t->hm})
-    for (auto &q : *v) dfree(q);
-  dfree(t->logits);
-  dfree(t->value);
-  dfree(t->logp);
-  dfree(t->ent);
-  dfree(t->dlogits);
-  dfree(t->dvalue);
-  dfree(t->dY);
-  dfree(t->dX0);
-  dfree(t->dG);
-  dfree(t->dGh);
-  dfree(t->dC);
+  for (DevBuf<float> *b : {&t->pooled, &t->enc_out, &t->x0, &t->g3, &t->masks, &t->hid0, &t->logits, &t->value, &t->logp, &t->ent, &t->dlogits,
+                           &t->dvalue, &t->dY, &t->dX0, &t->dG, &t->dGh, &t->dC})
+    b->reset();
+  t->rows.reset();
+  t->actions.reset();
+  for (auto *v : {&t->gates, &t->c, &t->y, &t->hm}) v->clear();
   t->capM = 0;
 }
 
@@ -635,36 +621,32 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   free_ws(t);
   const pnvo_policy_config &c = p.cfg;
   const size_t Hd = (size_t)c.hidden, K0 = Hd + 64, L = (size_t)c.rnn_layers, m = (size_t)M, A = (size_t)c.n_actions;
-  auto fl = [&](float *&q, size_t n) { return hipMalloc((void **)&q, (n ? n : 4) * sizeof(float)); };
-  PCHK(fl(t->pooled, m * (c.height / 2) * (c.width / 2) * 2));
-  PCHK(fl(t->enc_out, m));
-  PCHK(fl(t->x0, m * K0));
-  PCHK(fl(t->g3, m * 3));
-  PCHK(fl(t->masks, m));
-  PCHK(fl(t->hid0, rnn_state_floats(c, M)));
-  PCHK(hipMalloc((void **)&t->rows, m * sizeof(int)));
-  PCHK(hipMalloc((void **)&t->actions, m * sizeof(int64_t)));
-  t->gates.assign(L, nullptr);
-  t->c.assign(L, nullptr);
-  t->y.assign(L, nullptr);
-  t->hm.assign(L, nullptr);
+  PCHK(t->pooled.alloc(m * (c.height / 2) * (c.width / 2) * 2));
+  PCHK(t->enc_out.alloc(m));
+  PCHK(t->x0.alloc(m * K0));
+  PCHK(t->g3.alloc(m * 3));
+  PCHK(t->masks.alloc(m));
+  PCHK(t->hid0.alloc(rnn_state_floats(c, M)));
+  PCHK(t->rows.alloc(m));
+  PCHK(t->actions.alloc(m));
+  for (auto *v : {&t->gates, &t->c, &t->y, &t->hm}) v->resize(L);
   for (size_t l = 0; l < L; ++l) {
-    PCHK(fl(t->gates[l], m * 4 * Hd));
-    PCHK(fl(t->c[l], m * Hd));
-    PCHK(fl(t->y[l], m * Hd));
-    PCHK(fl(t->hm[l], m * Hd));
+    PCHK(t->gates[l].alloc(m * 4 * Hd));
+    PCHK(t->c[l].alloc(m * Hd));
+    PCHK(t->y[l].alloc(m * Hd));
+    PCHK(t->hm[l].alloc(m * Hd));
   }
-  PCHK(fl(t->logits, m * A));
-  PCHK(fl(t->value, m));
-  PCHK(fl(t->logp, m));
-  PCHK(fl(t->ent, m));
-  PCHK(fl(t->dlogits, m * A));
-  PCHK(fl(t->dvalue, m));
-  PCHK(fl(t->dY, m * Hd));
-  PCHK(fl(t->dX0, m * K0));
-  PCHK(fl(t->dG, m * 4 * Hd));
-  if (is_gru(c)) PCHK(fl(t->dGh, m * 3 * Hd));
-  PCHK(fl(t->dC, m * Hd));
+  PCHK(t->logits.alloc(m * A));
+  PCHK(t->value.alloc(m));
+  PCHK(t->logp.alloc(m));
+  PCHK(t->ent.alloc(m));
+  PCHK(t->dlogits.alloc(m * A));
+  PCHK(t->dvalue.alloc(m));
+  PCHK(t->dY.alloc(m * Hd));
+  PCHK(t->dX0.alloc(m * K0));
+  PCHK(t->dG.alloc(m * 4 * Hd));
+  if (is_gru(c)) PCHK(t->dGh.alloc(m * 3 * Hd));
+  PCHK(t->dC.alloc(m * Hd));
   t->capM = M;
   return PNVO_OK;
 }
@@ -691,9 +673,6 @@ size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 
 void pnvo_policy_train_free(Policy &p) {
   PolicyTrain *t = p.train;
   if (!t) return;
-  free_ws(t);
-  dfree(t->whhT);
-  dfree(t->sq_part);
   for (hipEvent_t &e : t->ev)
     if (e) (void)hipEventDestroy(e);
   delete t;
@@ -756,8 +735,8 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
     hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem, t->c0,
                        params + t->o_stem2);
     PCHK(hipGetLastError());
-    PCHK(hipMalloc((void **)&t->whhT, (size_t)4 * Hd * Hd * sizeof(float)));
-    PCHK(hipMalloc((void **)&t->sq_part, SQ_BLOCKS * sizeof(double)));
+    PCHK(t->whhT.alloc((size_t)4 * Hd * Hd));
+    PCHK(t->sq_part.alloc(SQ_BLOCKS));
     return attach_encoder(p, t, ent, toc);
   }();
   if (rc != PNVO_OK) {                  // no half-built train step is left behind
@@ -765,7 +744,7 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
     return rc;
   }
   // the recurrent part and the heads read the flat buffer from now on (pnvo_policy_act included): no second copy
-  pnvo_policy_free_weights(p);
+  p.owned.clear();
   p.attached = true;
   for (size_t i = 0; i < tab.size(); ++i) *tab[i].slot = params + offs[i];
   PCHK(hipDeviceSynchronize());

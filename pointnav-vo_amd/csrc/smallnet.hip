@@ -835,25 +835,23 @@ int ilog2(int v) {
 // -------------------------------------------------------------------------------------------------------------------------
 struct SmallNet {
   unsigned long long load_gen = ~0ull;
-  std::vector<float *> w;            // per conv of m->convs (index 0 unused), fragment-packed
-  float *w_fc = nullptr, *w_head = nullptr;
-  float *part[4] = {nullptr, nullptr, nullptr, nullptr};   // conv1 / conv2 / downsample / compression partial statistics
-  size_t part_floats[4] = {0, 0, 0, 0};
-  SnPhase *ph_dev = nullptr;
-  int *tiles_dev = nullptr;
-  size_t tiles_cap = 0;
+  std::vector<DevBuf<float>> w;      // per conv of m->convs (index 0 unused), fragment-packed
+  DevBuf<float> w_fc, w_head;
+  DevBuf<float> part[4];             // conv1 / conv2 / downsample / compression partial statistics; only grow
+  DevBuf<SnPhase> ph_dev;
+  DevBuf<int> tiles_dev;             // only grows
   std::vector<SnPhase> ph;
   int B = -1, grid = 0, stem_slots = -1;
   bool features = false;             // built for pnvo_forward_features (no head phase)
   const void *ws_key[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t lds_bytes = 0;
-  unsigned *bar = nullptr;
+  DevBuf<unsigned> bar;
   unsigned bar_base = 0;
-  int *err = nullptr;                // host-mapped
+  DevBuf<int> err;                   // host-mapped
   bool unsupported = false, failed = false;
   int cus = 0;
   bool attr_set = false;
-  unsigned long long *prof = nullptr;   // device
+  DevBuf<unsigned long long> prof;
 };
 
 }  // namespace pnvo
@@ -861,18 +859,7 @@ struct SmallNet {
 using namespace pnvo;
 
 void pnvo_small_free(pnvo_handle m) {
-  SmallNet *sn = static_cast<SmallNet *>(m->small);
-  if (!sn) return;
-  for (float *&q : sn->w) pnvo_free_dev(q);
-  pnvo_free_dev(sn->w_fc);
-  pnvo_free_dev(sn->w_head);
-  for (float *&q : sn->part) pnvo_free_dev(q);
-  if (sn->ph_dev) (void)hipFree(sn->ph_dev);
-  if (sn->tiles_dev) (void)hipFree(sn->tiles_dev);
-  if (sn->bar) (void)hipFree(sn->bar);
-  if (sn->err) (void)hipHostFree(sn->err);
-  if (sn->prof) (void)hipFree(sn->prof);
-  delete sn;
+  delete static_cast<SmallNet *>(m->small);
   m->small = nullptr;
 }
 
@@ -914,16 +901,15 @@ bool pnvo_small_usable(pnvo_handle m, int B) {
 
 namespace {
 
-int sn_upload(pnvo_handle m, float *&dst, const std::vector<float> &v) {
-  pnvo_free_dev(dst);
-  HIPCHK(m, hipMalloc((void **)&dst, v.size() * sizeof(float)));
+int sn_upload(pnvo_handle m, DevBuf<float> &dst, const std::vector<float> &v) {
+  HIPCHK(m, dst.alloc(v.size()));
   HIPCHK(m, hipMemcpy(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
   return PNVO_OK;
 }
 
 int sn_pack_weights(pnvo_handle m, SmallNet *sn) {
   int rc;
-  sn->w.resize(m->convs.size(), nullptr);
+  sn->w.resize(m->convs.size());
   std::vector<float> pk;
   for (size_t k = 1; k < m->convs.size(); ++k) {
     const Layer &l = m->convs[k];
@@ -1145,11 +1131,8 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B, int stem_slots, bool features) 
   }
   // ---- buffers
   for (int k = 0; k < 4; ++k)
-    if (need[k] > sn->part_floats[k]) {
-      pnvo_free_dev(sn->part[k]);
-      sn->part_floats[k] = 0;
-      HIPCHK(m, hipMalloc((void **)&sn->part[k], need[k] * sizeof(float)));
-      sn->part_floats[k] = need[k];
+    if (need[k] > sn->part[k].size()) {
+      HIPCHK(m, sn->part[k].alloc(need[k]));
       return sn_build(m, sn, B, stem_slots, features);   // pointers changed: lay the phases out again
     }
   sn->lds_bytes = ((size_t)SN_FIXED_FLOATS + patch_floats) * sizeof(float);
@@ -1160,17 +1143,11 @@ int sn_build(pnvo_handle m, SmallNet *sn, int B, int stem_slots, bool features) 
   sn->grid = grid;
   for (SnPhase &p : ph)
     if (p.kind == 1) p.ntiles = grid;
-  if (tile_words.size() > sn->tiles_cap) {
-    if (sn->tiles_dev) (void)hipFree(sn->tiles_dev);
-    sn->tiles_dev = nullptr;
-    sn->tiles_cap = 0;
-    HIPCHK(m, hipMalloc((void **)&sn->tiles_dev, tile_words.size() * sizeof(int)));
-    sn->tiles_cap = tile_words.size();
-  }
+  HIPCHK(m, sn->tiles_dev.reserve(tile_words.size()));
   HIPCHK(m, hipMemcpy(sn->tiles_dev, tile_words.data(), tile_words.size() * sizeof(int), hipMemcpyHostToDevice));
   for (SnPhase &p : ph)
     if (p.kind == 0) p.tiles = sn->tiles_dev + (reinterpret_cast<size_t>(p.tiles) - 1);
-  if (!sn->ph_dev) HIPCHK(m, hipMalloc((void **)&sn->ph_dev, 64 * sizeof(SnPhase)));
+  if (!sn->ph_dev) HIPCHK(m, sn->ph_dev.alloc(64));
   if (ph.size() > (size_t)SN_MAXPH) return -1;
   HIPCHK(m, hipMemcpy(sn->ph_dev, ph.data(), ph.size() * sizeof(SnPhase), hipMemcpyHostToDevice));
   sn->ph = ph;
@@ -1196,9 +1173,9 @@ int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots
     hipDeviceProp_t prop;
     HIPCHK(m, hipGetDeviceProperties(&prop, m->device));
     sn->cus = prop.multiProcessorCount;
-    HIPCHK(m, hipMalloc((void **)&sn->bar, 256));
+    HIPCHK(m, sn->bar.alloc(64));
     HIPCHK(m, hipMemset(sn->bar, 0, 256));
-    HIPCHK(m, hipHostMalloc((void **)&sn->err, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(m, sn->err.alloc_host(1, hipHostMallocMapped | hipHostMallocCoherent));
     *(volatile int *)sn->err = 0;
   }
   if (*(volatile int *)sn->err != 0) {
@@ -1238,7 +1215,7 @@ int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots
   a.prof = nullptr;
   a.dbg = m->opt.small_prof;
   if (m->opt.small_prof) {
-    if (!sn->prof) HIPCHK(m, hipMalloc((void **)&sn->prof, 64 * 12 * sizeof(unsigned long long)));
+    if (!sn->prof) HIPCHK(m, sn->prof.alloc(64 * 12));
     HIPCHK(m, hipMemsetAsync(sn->prof, 0, 64 * 12 * sizeof(unsigned long long), s));
     a.prof = sn->prof;
   }

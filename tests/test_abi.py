@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 
@@ -48,6 +49,19 @@ def test_bad_arguments_return_error_codes():
     assert _lib.lib.pnvo_forward(None, None, None, None, None, None, 1, None, None) == -1
     assert _lib.lib.pnvo_destroy(None) == 0
     assert _lib.version().startswith("pnvo")
+
+
+def test_device_bytes_live_is_zero_in_a_fresh_process_and_after_a_failed_create():
+    """A process of its own: models of other tests alive in this one hold device memory on a GPU box."""
+    code = ("import ctypes as C\n"
+            "from pointnav_vo_amd import _lib\n"
+            "assert _lib.lib.pnvo_device_bytes_live() == 0\n"
+            "cfg = _lib.pnvo_config(width=341, height=192, n_rgb=0, n_depth=0, n_dd=0, n_tdv=0, baseplanes=32, hidden=512,\n"
+            "                       out_dim=3, normalize=1, act_embed=0, n_acts=4, flat_size=2048, max_batch=0)\n"
+            "h = C.c_void_p()\n"
+            "assert _lib.lib.pnvo_create(C.byref(cfg), 0, C.byref(h)) == -1\n"     # the blind model of the test above
+            "assert _lib.lib.pnvo_device_bytes_live() == 0\n")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 
 
 def test_loaded_library_was_built_from_this_tree():
