@@ -394,6 +394,24 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
                     const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                     float *value, void *stream);
 
+/* ---- the visual encoder on its own, and the policy fed with its output (the reference's frozen-encoder training,
+ * RL.DDPPO.train_encoder False: ddppo_trainer.py:158-161,257-271 stores net.visual_encoder(batch) in the rollout as
+ * observations["visual_features"], and PointNavResNetNet.forward takes that entry instead of running the encoder,
+ * resnet_policy.py:249-252). ----
+ *
+ * pnvo_policy_features_shape: shape = {C, fh, fw} of ResNetEncoder.output_shape for this handle's frame size; F = C * fh * fw.
+ * pnvo_policy_encode: depth [B,H,W,1] -> features_out [B,C,fh,fw] (NCHW, device) = relu(GroupNorm(compression conv(backbone(
+ *   avg_pool2d(depth, 2))))), on the per-layer kernels at every batch size.
+ * pnvo_policy_act_features: pnvo_policy_act with visual_features [B,C,fh,fw] in place of depth: the encoder does not run, visual_fc
+ *   reads net.visual_fc.1.weight in torch's [hidden, F] layout (rows in the NCHW flatten's order; F need not be a multiple of 4).  Same
+ *   outputs, same refusal of overlapping hidden_in / hidden_out.  The sums of visual_fc run in another order than on the depth path:
+ *   float32-grade equal, not bit-equal. */
+int pnvo_policy_features_shape(pnvo_policy_handle h, int64_t shape[3]);
+int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *features_out, void *stream);
+int pnvo_policy_act_features(pnvo_policy_handle h, const float *visual_features, const float *goal, const int64_t *prev_actions,
+                             const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
+                             float *value, void *stream);
+
 int pnvo_policy_destroy(pnvo_policy_handle h);
 
 /* ---- one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions, policy.py:52-63):
@@ -425,6 +443,15 @@ int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream);
 int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions,
                          const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder,
                          float *hidden_out, float *value, float *logp, float *entropy, void *stream);
+
+/* pnvo_policy_evaluate with visual_features [M,C,fh,fw] (pnvo_policy_features_shape) in place of depth: the encoder does not run.  The
+ * feature rows are copied into the handle (the caller's tensor may be gone by the backward).  pnvo_policy_ppo_loss and
+ * pnvo_policy_backward then work as after pnvo_policy_evaluate; the backward learns from the handle which kind of evaluate came last,
+ * fills net.visual_fc.1.{weight,bias}, the embeddings, the recurrent tensors and the heads, takes no gradient with respect to the
+ * features and leaves the encoder's range exactly zero, whatever train_encoder says. */
+int pnvo_policy_evaluate_features(pnvo_policy_handle h, const float *visual_features, const float *goal, const int64_t *prev_actions,
+                                  const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
+                                  float *value, float *logp, float *entropy, void *stream);
 
 /* The minibatch loss of rl/ppo/ppo.py:101-126 for the last pnvo_policy_evaluate: out3 (device) = {value_loss, action_loss,
  * dist_entropy}; the gradient of total = value_loss * value_coef + action_loss - dist_entropy * entropy_coef with respect to the

@@ -1687,7 +1687,7 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
                           pnvo_conv_takes_tail(m, m->convs[m->blocks[0].conv[0]], B);
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
-  const bool small = !pool_fused && sp.writes_slots() && pnvo_small_usable(m, B);
+  const bool small = !pool_fused && sp.writes_slots() && !r.stop_after_compression && pnvo_small_usable(m, B);
   StemRequest sr{.src = {r.src[0], r.src[1], r.src[2], r.src[3]}, .raw = r.raw, .y = m->stem_raw, .ss = m->ssA, .grp = grp, .s = s};
   if (small) {
     int stem_slots = 0;
@@ -1819,6 +1819,7 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
     HIPCHK(m, launch_apply_ss_relu(m->comp_raw, m->ssC[0], m->ssC[1], B, (long)m->fh * m->fw, m->comp_cp, m->tapbuf, s));
     if ((rc = maybe_tap(m, "compression", m->tapbuf, (size_t)B * m->fh * m->fw * m->comp_cp, s)) != PNVO_OK) return rc;
   }
+  if (r.stop_after_compression) return PNVO_OK;   // pnvo_forward_compression: the caller reads m->comp_raw and m->ssC
   // (a11) Flatten + Linear + ReLU, then the output head — per action model in a grouped forward (each on its own handle: its
   // weights, bias rows and split-K scratch; the sample ranges are contiguous)
   if (grp != nullptr) {
@@ -2084,6 +2085,24 @@ int pnvo_forward_features(pnvo_handle m, const float *rgb, const float *depth, c
   int rc = ensure_workspace(m, B);
   if (rc != PNVO_OK) return rc;
   const FwdRequest r{.src = {rgb, depth, dd, tdv}, .actions = actions, .out = hidden_out, .features_only = true, .s = (hipStream_t)stream};
+  if ((rc = forward_body(m, B, r)) != PNVO_OK) return rc;
+  bool rerun = false;
+  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
+  return rerun ? forward_body(m, B, r) : PNVO_OK;
+}
+
+extern "C++" int pnvo_forward_compression(pnvo_handle m, const float *depth, int B, void *stream) {
+  if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
+  if (!m->loaded) return fail(m, PNVO_ERR_STATE, "pnvo_forward_compression before pnvo_load_weights");
+  const pnvo_config &c = m->cfg;
+  if (B <= 0 || !depth || c.n_rgb > 0 || c.n_dd > 0 || c.n_tdv > 0 || c.n_depth <= 0)
+    return fail(m, PNVO_ERR_ARG, "pnvo_forward_compression takes a depth-only model and a positive batch");
+  if (m->precision != 0) return fail(m, PNVO_ERR_STATE, "pnvo_forward_compression runs on the float32 path");
+  if (int rc0 = pnvo_check_inputs(m)) return rc0;
+  HIPCHK(m, hipSetDevice(m->device));
+  int rc = ensure_workspace(m, B);
+  if (rc != PNVO_OK) return rc;
+  const FwdRequest r{.src = {nullptr, depth, nullptr, nullptr}, .stop_after_compression = true, .s = (hipStream_t)stream};
   if ((rc = forward_body(m, B, r)) != PNVO_OK) return rc;
   bool rerun = false;
   if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;

@@ -291,6 +291,7 @@ struct FwdRequest {
   const int64_t *actions = nullptr;
   float *out = nullptr;
   bool features_only = false;                // pnvo_forward_features: stop after the hidden layer, `out` receives it
+  bool stop_after_compression = false;       // pnvo_forward_compression: stop behind the compression conv and its finalisation
   const GroupedFwd *grp = nullptr;           // a grouped forward's models (pnvo_forward_grouped_raw), or nullptr
   hipStream_t s = nullptr;
 };
@@ -312,6 +313,9 @@ int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
 const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name);   // pnvo_train_api.hip: device pointer or nullptr
+// pnvo_api.hip: the forward up to the compression conv's raw NHWC output (m->comp_raw, channel-padded to m->comp_cp) and its per-sample
+// GroupNorm scale / shift (m->ssC), on the per-layer kernels at every batch size (the persistent small-batch kernel is not entered)
+int pnvo_forward_compression(pnvo_handle m, const float *depth, int B, void *stream);
 const float *pnvo_train_hidden(pnvo_handle m);   // pnvo_train_api.hip: [B, hidden] output of visual_fc of the last train-mode forward, or nullptr
 int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream);   // the backward entered below the output head
 void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &)> &gn_bound);   // pnvo_api.hip

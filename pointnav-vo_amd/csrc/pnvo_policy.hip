@@ -10,6 +10,9 @@
 // modality of 2 channels [pooled depth | 0] and no whitening (normalize_visual_inputs is False for the depth-only policy,
 // ddppo_trainer.py:118-121).  The recurrent part is tiny and weight-bandwidth-bound at B = number of environments
 // (9.4 MB of LSTM weights per step), so its Linears are wave-per-output-row dot products on the vector ALU, not MFMA.
+// pnvo_policy_encode is net.visual_encoder called on its own (the encoder handle stopped behind the compression conv, then
+// feature_pack_kernel -> [B, C, fh, fw]); pnvo_policy_act_features is the step fed with that tensor (vfc_rows_kernel / the GEMM of
+// policy_train.hip in place of the encoder).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -223,10 +226,106 @@ __global__ __launch_bounds__(256) void policy_heads_kernel(const float *x, const
   }
 }
 
+// The visual encoder's output as the reference hands it on (ResNetEncoder.forward, resnet_policy.py:157-175): the compression conv's raw
+// NHWC map [B, P = fh * fw, cp] (channels padded to cp, a multiple of 32) with its per-sample GroupNorm(1, C) scale / shift [B, cp]
+// -> relu(x * scale + shift) as [B, C, fh, fw], the padding channels dropped.  Thread = one element of the raw map.
+__global__ __launch_bounds__(256) void feature_pack_kernel(const float *raw, const float *sc, const float *sh, int B, int P, int C, int cp,
+                                                         float *out) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)B * P * cp) return;
+  const int c = (int)(e % cp);
+  if (c >= C) return;
+  const long bp = e / cp;
+  const int pix = (int)(bp % P);
+  const long b = bp / P;
+  out[(b * C + c) * P + pix] = fmaxf(__builtin_fmaf(raw[e], sc[b * cp + c], sh[b * cp + c]), 0.f);
+}
+
+// visual_fc from features for the batches of act (fc_rows.hip's shape): out[b][n] = relu(x[b] . W[n] + bias[n]), W in torch's [hidden][F]
+// layout.  Workgroup = four hidden units x one chunk of up to four samples (blockIdx.y), wave = hidden unit: the chunk's feature rows are
+// staged in LDS once, the wave streams its weight row once and keeps four sums.  F % 4 may be anything, so a row starts at any float:
+// the lanes below `head` take the elements in front of the row's first 16-byte boundary, the body runs on aligned float4 loads, the
+// lanes of the tail take what is left (< 4).  The features are read from LDS by index, whatever their alignment in memory.
+// float32 FMA chains and a fixed lane tree: the same bits every time.
+__global__ __launch_bounds__(256) void vfc_rows_kernel(const float *x, const float *w, const float *bias, int B, int F, int hidden, float *out) {
+  extern __shared__ float xs[];                            // [nb][F]
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  const int b0 = blockIdx.y * 4, nb = min(4, B - b0);
+  const float *xb = x + (long)b0 * F;
+  for (int i = threadIdx.x; i < nb * F; i += 256) xs[i] = xb[i];
+  __syncthreads();
+  if (n >= hidden) return;
+  const float *wp = w + (long)n * F;
+  const int head = min(F, (int)((4 - (((uintptr_t)wp >> 2) & 3)) & 3));
+  const int nv = (F - head) >> 2;
+  const float *xu[4];
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) xu[u] = xs + min(u, nb - 1) * F;   // (past the chunk's end: the last sample again, result unused)
+  if (lane < head) {
+    const float w0 = wp[lane];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = w0 * xu[u][lane];
+  }
+  const f32x4 *wv = reinterpret_cast<const f32x4 *>(wp + head);
+  for (int v = lane; v < nv; v += 64) {
+    const f32x4 w4 = wv[v];
+    const int k = head + 4 * v;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[u] = __builtin_fmaf(w4[e], xu[u][k + e], s[u]);
+  }
+  const int kt = head + 4 * nv + lane;
+  if (kt < F) {
+    const float w0 = wp[kt];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = __builtin_fmaf(w0, xu[u][kt], s[u]);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] += __shfl_xor(s[u], o);
+  if (lane < nb) {
+    const float sv = lane == 0 ? s[0] : (lane == 1 ? s[1] : (lane == 2 ? s[2] : s[3]));
+    out[(long)(b0 + lane) * hidden + n] = fmaxf(sv + bias[n], 0.f);
+  }
+}
+
+int ensure_pooled(Policy &p, int B) {
+  if (B <= p.cap_pooled) return PNVO_OK;
+  p.pooled.reset();                                        // the old workspace goes first
+  p.cap_pooled = 0;
+  PCHK(p.pooled.alloc((size_t)B * (p.cfg.height / 2) * (p.cfg.width / 2) * 2));
+  p.cap_pooled = B;
+  return PNVO_OK;
+}
+
 }  // namespace
 }  // namespace pnvo
 
 using namespace pnvo;
+
+void pnvo::policy_features_shape(const Policy &p, int64_t shape[3]) {
+  shape[0] = p.enc->comp_c;
+  shape[1] = p.enc->fh;
+  shape[2] = p.enc->fw;
+}
+
+int pnvo::launch_visual_fc(const Policy &p, const float *feat, int rows, float *out, hipStream_t s) {
+  const int F = (int)policy_feature_floats(p), Hd = p.cfg.hidden;
+  if (rows > VFC_ROWS_MAX) {
+    PCHK(launch_visual_fc_gemm(feat, p.vfc_w, p.vfc_b, rows, F, Hd, out, s));
+    return PNVO_OK;
+  }
+  const size_t lds = (size_t)4 * F * sizeof(float);
+  if (lds > 65536) return pfail(PNVO_ERR_ARG, "visual_fc row kernel: " + std::to_string(F) + " feature floats per sample do not fit its LDS stage");
+  hipLaunchKernelGGL(vfc_rows_kernel, dim3((unsigned)((Hd + 3) / 4), (unsigned)((rows + 3) / 4)), dim3(256), lds, s, feat, p.vfc_w, p.vfc_b, rows,
+                     F, Hd, out);
+  PCHK(hipGetLastError());
+  return PNVO_OK;
+}
 
 hipError_t pnvo::launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks,
                                       int rows, float *x, int *rows_out, float *g3, hipStream_t s) {
@@ -284,6 +383,78 @@ std::vector<pnvo_tensor_desc> pnvo::encoder_toc(const std::vector<EncoderEntry> 
     for (size_t d = 0; d < entries[i].shape.size(); ++d) toc[i].shape[d] = entries[i].shape[d];
   }
   return toc;
+}
+
+// the shared body of pnvo_policy_act (depth given) and pnvo_policy_act_features (vfeat given)
+static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *depth, const float *vfeat, const float *goal,
+                           const int64_t *prev_actions, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features,
+                           float *logits, float *value, void *stream) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  Policy &p = h->p;
+  if (!p.loaded) return pfail(PNVO_ERR_STATE, std::string(fn) + " before pnvo_policy_load_weights");
+  if (B <= 0 || (!depth && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !hidden_out)
+    return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  const pnvo_policy_config &c = p.cfg;
+  const int Hd = c.hidden, K0 = Hd + 64;
+  const bool gru = is_gru(c);
+  if (hidden_states_overlap(hidden_in, hidden_out, rnn_state_floats(c, B)))
+    return pfail(PNVO_ERR_ARG, std::string("hidden_out overlaps hidden_in (each holds ") + (gru ? "" : "2 * ") +
+                                   "rnn_layers * B * hidden floats): pass separate buffers");
+  PCHK(hipSetDevice(p.device));
+  hipStream_t s = (hipStream_t)stream;
+  if (B > p.cap) {
+    for (DevBuf<float> *b : {&p.visual, &p.x}) b->reset();   // the old workspace goes first
+    p.cap = 0;
+    PCHK(p.visual.alloc((size_t)B * Hd));
+    PCHK(p.x.alloc((size_t)B * K0));
+    p.cap = B;
+  }
+  int rc = PNVO_OK;
+  if (depth) {
+    if ((rc = ensure_pooled(p, B)) != PNVO_OK) return rc;
+    if ((rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK) return rc;
+    rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
+    if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  } else if ((rc = launch_visual_fc(p, vfeat, B, p.visual, s)) != PNVO_OK) {
+    return rc;
+  }
+  PCHK(launch_policy_inputs(p, p.visual, goal, prev_actions, masks, B, p.x, nullptr, nullptr, s));
+  return policy_act_tail(p, masks, hidden_in, B, hidden_out, features, logits, value, s);
+}
+
+int pnvo::policy_act_tail(Policy &p, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
+                          float *value, hipStream_t s) {
+  const pnvo_policy_config &c = p.cfg;
+  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
+  const bool gru = is_gru(c);
+  // hidden_in / hidden_out: LSTM [2L, B, Hd] = (h_0 .. h_{L-1}, c_0 .. c_{L-1}), GRU [L, B, Hd] = (h_0 .. h_{L-1})  (rnn_state_encoder.py:43-61)
+  const float *xin = p.x;
+  int K = K0;
+  if (gru) {
+    for (int l = 0; l < L; ++l) {
+      float *h_new = hidden_out + (size_t)l * B * Hd;
+      hipLaunchKernelGGL(gru_layer_kernel, dim3((unsigned)Hd), dim3(192), 0, s, xin, K, p.w_ih[l], p.b_ih[l], hidden_in + (size_t)l * B * Hd,
+                         p.w_hh[l], p.b_hh[l], masks, B, Hd, h_new);
+      xin = h_new;
+      K = Hd;
+    }
+  } else {
+    for (int l = 0; l < L; ++l) {
+      const float *h_prev = hidden_in + (size_t)l * B * Hd, *c_prev = hidden_in + (size_t)(L + l) * B * Hd;
+      float *h_new = hidden_out + (size_t)l * B * Hd, *c_new = hidden_out + (size_t)(L + l) * B * Hd;
+      hipLaunchKernelGGL(lstm_layer_kernel, dim3((unsigned)Hd), dim3(256), 0, s, xin, K, p.w_ih[l], p.b_ih[l], h_prev, p.w_hh[l], p.b_hh[l],
+                         c_prev, masks, B, Hd, h_new, c_new);
+      xin = h_new;
+      K = Hd;
+    }
+  }
+  const float *feat = hidden_out + (size_t)(L - 1) * B * Hd;
+  if (features) PCHK(hipMemcpyAsync(features, feat, (size_t)B * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (logits || value)
+    hipLaunchKernelGGL(policy_heads_kernel, dim3((unsigned)((c.n_actions + 1 + 3) / 4)), dim3(256), 0, s, feat, p.act_w, p.act_b, p.cr_w,
+                       p.cr_b, B, Hd, c.n_actions, logits, value);
+  PCHK(hipGetLastError());
+  return PNVO_OK;
 }
 
 extern "C" {
@@ -385,57 +556,42 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
 int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions,
                     const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                     float *value, void *stream) {
+  if (!depth) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  return policy_act_impl(h, "pnvo_policy_act", depth, nullptr, goal, prev_actions, masks, hidden_in, B, hidden_out, features, logits, value,
+                         stream);
+}
+
+int pnvo_policy_act_features(pnvo_policy_handle h, const float *visual_features, const float *goal, const int64_t *prev_actions,
+                             const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
+                             float *value, void *stream) {
+  if (!visual_features) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  return policy_act_impl(h, "pnvo_policy_act_features", nullptr, visual_features, goal, prev_actions, masks, hidden_in, B, hidden_out,
+                         features, logits, value, stream);
+}
+
+int pnvo_policy_features_shape(pnvo_policy_handle h, int64_t shape[3]) {
+  if (!h || !shape) return pfail(PNVO_ERR_ARG, "null argument");
+  policy_features_shape(h->p, shape);
+  return PNVO_OK;
+}
+
+int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *features_out, void *stream) {
   if (!h) return pfail(PNVO_ERR_ARG, "null handle");
   Policy &p = h->p;
-  if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_act before pnvo_policy_load_weights");
-  if (B <= 0 || !depth || !goal || !prev_actions || !masks || !hidden_in || !hidden_out)
-    return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_encode before pnvo_policy_load_weights");
+  if (B <= 0 || !depth || !features_out) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
   const pnvo_policy_config &c = p.cfg;
-  const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64;
-  const bool gru = is_gru(c);
-  if (hidden_states_overlap(hidden_in, hidden_out, rnn_state_floats(c, B)))
-    return pfail(PNVO_ERR_ARG, std::string("hidden_out overlaps hidden_in (each holds ") + (gru ? "" : "2 * ") +
-                                   "rnn_layers * B * hidden floats): pass separate buffers");
   PCHK(hipSetDevice(p.device));
-  hipStream_t s = (hipStream_t)stream;
-  if (B > p.cap) {
-    for (DevBuf<float> *b : {&p.pooled, &p.visual, &p.x}) b->reset();   // the old workspace goes first
-    PCHK(p.pooled.alloc((size_t)B * (c.height / 2) * (c.width / 2) * 2));
-    PCHK(p.visual.alloc((size_t)B * Hd));
-    PCHK(p.x.alloc((size_t)B * K0));
-    p.cap = B;
-  }
-  int rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream);
+  int rc = ensure_pooled(p, B);
   if (rc != PNVO_OK) return rc;
-  rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
+  if ((rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK) return rc;
+  rc = pnvo_forward_compression(p.enc, p.pooled, B, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
-  PCHK(launch_policy_inputs(p, p.visual, goal, prev_actions, masks, B, p.x, nullptr, nullptr, s));
-  // hidden_in / hidden_out: LSTM [2L, B, Hd] = (h_0 .. h_{L-1}, c_0 .. c_{L-1}), GRU [L, B, Hd] = (h_0 .. h_{L-1})  (rnn_state_encoder.py:43-61)
-  const float *xin = p.x;
-  int K = K0;
-  if (gru) {
-    for (int l = 0; l < L; ++l) {
-      float *h_new = hidden_out + (size_t)l * B * Hd;
-      hipLaunchKernelGGL(gru_layer_kernel, dim3((unsigned)Hd), dim3(192), 0, s, xin, K, p.w_ih[l], p.b_ih[l], hidden_in + (size_t)l * B * Hd,
-                         p.w_hh[l], p.b_hh[l], masks, B, Hd, h_new);
-      xin = h_new;
-      K = Hd;
-    }
-  } else {
-    for (int l = 0; l < L; ++l) {
-      const float *h_prev = hidden_in + (size_t)l * B * Hd, *c_prev = hidden_in + (size_t)(L + l) * B * Hd;
-      float *h_new = hidden_out + (size_t)l * B * Hd, *c_new = hidden_out + (size_t)(L + l) * B * Hd;
-      hipLaunchKernelGGL(lstm_layer_kernel, dim3((unsigned)Hd), dim3(256), 0, s, xin, K, p.w_ih[l], p.b_ih[l], h_prev, p.w_hh[l], p.b_hh[l],
-                         c_prev, masks, B, Hd, h_new, c_new);
-      xin = h_new;
-      K = Hd;
-    }
-  }
-  const float *feat = hidden_out + (size_t)(L - 1) * B * Hd;
-  if (features) PCHK(hipMemcpyAsync(features, feat, (size_t)B * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (logits || value)
-    hipLaunchKernelGGL(policy_heads_kernel, dim3((unsigned)((c.n_actions + 1 + 3) / 4)), dim3(256), 0, s, feat, p.act_w, p.act_b, p.cr_w,
-                       p.cr_b, B, Hd, c.n_actions, logits, value);
+  const pnvo_handle m = p.enc;
+  const int P = m->fh * m->fw;
+  const long total = (long)B * P * m->comp_cp;
+  hipLaunchKernelGGL(feature_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m->comp_raw, m->ssC[0],
+                     m->ssC[1], B, P, m->comp_c, m->comp_cp, features_out);
   PCHK(hipGetLastError());
   return PNVO_OK;
 }

@@ -22,15 +22,19 @@ struct Policy {
   float *emb = nullptr, *tgt_w = nullptr, *tgt_b = nullptr;
   std::vector<float *> w_ih, w_hh, b_ih, b_hh;       // one per recurrent layer
   float *act_w = nullptr, *act_b = nullptr, *cr_w = nullptr, *cr_b = nullptr;
+  // net.visual_fc.1 in torch's own [hidden, F] layout (rows in the NCHW flatten's order): what the visual_features entry points read.
+  // The depth path reads the encoder handle's channel-padded copy of the same two tensors.
+  float *vfc_w = nullptr, *vfc_b = nullptr;
   std::vector<DevBuf<float>> owned;  // pnvo_policy_load_weights' copies, in policy_params() order; empty once a train step is attached
   bool attached = false;             // pnvo_policy_train_attach: the parameters live in the caller's flat buffer
   PolicyTrain *train = nullptr;
   // workspace
-  int cap = 0;
+  int cap = 0, cap_pooled = 0;       // rows `visual` and `x` hold / frames `pooled` holds (only the entry points that take depth grow it)
   DevBuf<float> pooled, visual, x;
 };
 
-// ---- the policy-owned tensors (everything but the visual encoder and visual_fc, which live in the encoder handle), in state_dict order
+// ---- the policy-owned tensors (everything but the visual encoder, which lives in the encoder handle; visual_fc is held twice, here in
+// torch's layout for the visual_features path and there channel-padded for the depth path), in state_dict order
 struct PolicyParam {
   std::string name;
   std::vector<int64_t> shape;
@@ -46,11 +50,22 @@ inline size_t rnn_state_floats(const pnvo_policy_config &c, int rows) {
   return (size_t)(is_gru(c) ? 1 : 2) * c.rnn_layers * rows * c.hidden;
 }
 
+// the visual encoder's output [C, fh, fw] (ResNetEncoder.output_shape, resnet_policy.py:113-124) and its flattened size F
+void policy_features_shape(const Policy &p, int64_t shape[3]);       // pnvo_policy.hip
+inline int64_t policy_feature_floats(const Policy &p) {
+  int64_t s[3];
+  policy_features_shape(p, s);
+  return s[0] * s[1] * s[2];
+}
+
 inline std::vector<PolicyParam> policy_params(Policy &p) {
   const int64_t Hd = p.cfg.hidden, A = p.cfg.n_actions, G = rnn_gates(p.cfg);
   std::vector<PolicyParam> t = {{"net.prev_action_embedding.weight", {A + 1, 32}, &p.emb, false},
                                 {"net.tgt_embeding.weight", {32, 3}, &p.tgt_w, false},
                                 {"net.tgt_embeding.bias", {32}, &p.tgt_b, false}};
+  const int64_t F = policy_feature_floats(p);
+  t.push_back({"net.visual_fc.1.weight", {Hd, F}, &p.vfc_w, false});       // (F % 4 != 0 on some frame sizes: rows are not 16-byte aligned)
+  t.push_back({"net.visual_fc.1.bias", {Hd}, &p.vfc_b, false});
   for (int l = 0; l < p.cfg.rnn_layers; ++l) {
     const std::string r = "net.state_encoder.rnn.", sl = "_l" + std::to_string(l);
     t.push_back({r + "weight_ih" + sl, {G * Hd, l == 0 ? Hd + 64 : Hd}, &p.w_ih[l], true});
@@ -92,6 +107,14 @@ void pnvo_policy_train_free(Policy &p);       // policy_train.hip
 // keep the gathered embedding row and (rho, cos(-phi), sin(-phi)) per row
 hipError_t launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks, int rows,
                                 float *x, int *rows_out, float *g3, hipStream_t s);
+// out [rows, hidden] = relu(feat [rows, F] . vfc_w^T + vfc_b): the row kernel of pnvo_policy.hip up to VFC_ROWS_MAX rows, the float32
+// matrix-core GEMM of policy_train.hip above
+constexpr int VFC_ROWS_MAX = 48;
+int launch_visual_fc(const Policy &p, const float *feat, int rows, float *out, hipStream_t s);
+hipError_t launch_visual_fc_gemm(const float *feat, const float *w, const float *b, int rows, int F, int hidden, float *out, hipStream_t s);   // policy_train.hip
+// the recurrent layers and the heads of one act step on x [B, hidden + 64] (pnvo_policy.hip)
+int policy_act_tail(Policy &p, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
+                    float *value, hipStream_t s);
 
 // ---- host helpers of both files
 inline int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }

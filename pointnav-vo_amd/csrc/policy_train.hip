@@ -20,6 +20,11 @@
 //   backward : T launches of gru_bptt_step_kernel filling dGx = (dr, dz, dn) and dGh = (dr, dz, dn * r); dW_ih = dGx^T . X,
 //              dW_hh = dGh^T . hm, db_ih = colsum(dGx), db_hh = colsum(dGh), dX = dGx . W_ih
 // Everything else (encoder, inputs, heads, loss, clipping) is shared; the type is branched on once per call, on the host.
+//
+// pnvo_policy_evaluate_features takes the encoder's output [M, C, fh, fw] (observations["visual_features"], the reference's frozen-encoder
+// training) in place of depth: the encoder does not run, visual = relu(features . W_fc^T + b_fc) is launch_visual_fc (the row kernel of
+// pnvo_policy.hip for few rows, gemm_f32_kernel with a ReLU epilogue otherwise) on torch's [hidden, F] weight, and the backward ends with
+// the ReLU mask, dW_fc = d visual^T . features (the rows kept in the workspace) and db_fc = colsum: the encoder's range stays zero.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -45,6 +50,12 @@ struct PolicyTrain {
   // workspace, sized for capM rows
   int capM = 0;
   DevBuf<float> pooled, enc_out, x0, g3, masks, hid0;
+  int cap_pooled = 0;                 // frames `pooled` holds: grown by the evaluate that takes depth only
+  // the evaluate that takes visual_features: the feature rows [M, F] (kept: the caller's tensor may be gone by the backward) and
+  // visual = relu(visual_fc(features)) [M, hidden]; from_features says which kind of evaluate came last
+  DevBuf<float> feat, visual;
+  int cap_feat = 0;
+  bool from_features = false;
   DevBuf<int> rows;
   DevBuf<int64_t> actions;
   std::vector<DevBuf<float>> gates, c, y, hm;
@@ -77,6 +88,7 @@ struct GemmArgs {
   float *C;
   int M, N, K;
   long a_sm, a_sk, b_sk, b_sn, ldc;
+  int relu = 0;                       // epilogue: max(., 0) behind the bias
 };
 
 template <bool AKC, bool BKC>
@@ -120,7 +132,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (row < g.M) g.C[(long)row * g.ldc + col] = acc[r] + bias;
+    const float v = acc[r] + bias;
+    if (row < g.M) g.C[(long)row * g.ldc + col] = g.relu ? fmaxf(v, 0.f) : v;
   }
 }
 
@@ -556,6 +569,12 @@ __global__ __launch_bounds__(256) void inputs_bwd_kernel(const float *dX0, const
   }
 }
 
+// ReLU's backward in place: d[e] = 0 where the layer's output y[e] is not positive (torch: grad * (out > 0))
+__global__ __launch_bounds__(256) void relu_mask_kernel(const float *y, long n, float *d) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e < n && !(y[e] > 0.f)) d[e] = 0.f;
+}
+
 // the policy's stem weight [C0,1,7,7] <-> channel 0 of the encoder handle's [C0,2,7,7] (channel 1 stays 0)
 __global__ __launch_bounds__(256) void stem_pad_kernel(const float *w1, int c0, float *w2) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -607,13 +626,13 @@ hipError_t mark(PolicyTrain *t, int k, hipStream_t s) { return t->timing ? hipEv
 
 // Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves capM = 0.
 void free_ws(PolicyTrain *t) {
-  for (DevBuf<float> *b : {&t->pooled, &t->enc_out, &t->x0, &t->g3, &t->masks, &t->hid0, &t->logits, &t->value, &t->logp, &t->ent, &t->dlogits,
+  for (DevBuf<float> *b : {&t->pooled, &t->feat, &t->visual, &t->enc_out, &t->x0, &t->g3, &t->masks, &t->hid0, &t->logits, &t->value, &t->logp, &t->ent, &t->dlogits,
                            &t->dvalue, &t->dY, &t->dX0, &t->dG, &t->dGh, &t->dC})
     b->reset();
   t->rows.reset();
   t->actions.reset();
   for (auto *v : {&t->gates, &t->c, &t->y, &t->hm}) v->clear();
-  t->capM = 0;
+  t->capM = t->cap_pooled = t->cap_feat = 0;
 }
 
 int ensure_ws(Policy &p, PolicyTrain *t, int M) {
@@ -621,7 +640,6 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   free_ws(t);
   const pnvo_policy_config &c = p.cfg;
   const size_t Hd = (size_t)c.hidden, K0 = Hd + 64, L = (size_t)c.rnn_layers, m = (size_t)M, A = (size_t)c.n_actions;
-  PCHK(t->pooled.alloc(m * (c.height / 2) * (c.width / 2) * 2));
   PCHK(t->enc_out.alloc(m));
   PCHK(t->x0.alloc(m * K0));
   PCHK(t->g3.alloc(m * 3));
@@ -651,6 +669,26 @@ int ensure_ws(Policy &p, PolicyTrain *t, int M) {
   return PNVO_OK;
 }
 
+// the input side's workspace of the two kinds of evaluate: pooled frames, or feature rows and visual_fc's output
+int ensure_pooled(Policy &p, PolicyTrain *t, int M) {
+  if (M <= t->cap_pooled) return PNVO_OK;
+  t->pooled.reset();
+  t->cap_pooled = 0;
+  PCHK(t->pooled.alloc((size_t)M * (p.cfg.height / 2) * (p.cfg.width / 2) * 2));
+  t->cap_pooled = M;
+  return PNVO_OK;
+}
+int ensure_feat(Policy &p, PolicyTrain *t, int M) {
+  if (M <= t->cap_feat) return PNVO_OK;
+  t->feat.reset();
+  t->visual.reset();
+  t->cap_feat = 0;
+  PCHK(t->feat.alloc((size_t)M * policy_feature_floats(p)));
+  PCHK(t->visual.alloc((size_t)M * p.cfg.hidden));
+  t->cap_feat = M;
+  return PNVO_OK;
+}
+
 // the encoder handle's own parameter table inside the policy's flat buffer: the caller's entries where they are, the padded stem and
 // the unused head in the tail
 int attach_encoder(Policy &p, PolicyTrain *t, const std::vector<EncoderEntry> &ent, const pnvo_tensor_desc *toc) {
@@ -670,6 +708,11 @@ size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 
 
 }  // namespace
 
+hipError_t launch_visual_fc_gemm(const float *feat, const float *w, const float *b, int rows, int F, int hidden, float *out, hipStream_t s) {
+  GemmArgs g{feat, w, b, nullptr, out, rows, hidden, F, (long)F, 1, 1, (long)F, (long)hidden, 1};
+  return launch_gemm<true, true>(g, s);
+}
+
 void pnvo_policy_train_free(Policy &p) {
   PolicyTrain *t = p.train;
   if (!t) return;
@@ -682,6 +725,10 @@ void pnvo_policy_train_free(Policy &p) {
 }  // namespace pnvo
 
 using namespace pnvo;
+
+static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const float *vfeat, const float *goal, const int64_t *prev_actions,
+                                const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
+                                float *value, float *logp, float *entropy, void *stream);
 
 extern "C" {
 
@@ -767,14 +814,32 @@ int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream) {
 int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *goal, const int64_t *prev_actions, const float *masks,
                          const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder, float *hidden_out,
                          float *value, float *logp, float *entropy, void *stream) {
+  (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
+  if (!depth) return pfail(PNVO_ERR_ARG, "null argument");
+  return policy_evaluate_impl(h, depth, nullptr, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp, entropy, stream);
+}
+
+int pnvo_policy_evaluate_features(pnvo_policy_handle h, const float *visual_features, const float *goal, const int64_t *prev_actions,
+                                  const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
+                                  float *value, float *logp, float *entropy, void *stream) {
+  if (!visual_features) return pfail(PNVO_ERR_ARG, "null argument");
+  return policy_evaluate_impl(h, nullptr, visual_features, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp,
+                              entropy, stream);
+}
+
+}  // extern "C"
+
+// the shared body of pnvo_policy_evaluate (depth given) and pnvo_policy_evaluate_features (vfeat given)
+static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const float *vfeat, const float *goal, const int64_t *prev_actions,
+                                const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
+                                float *value, float *logp, float *entropy, void *stream) {
   if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
   Policy &p = h->p;
   PolicyTrain *t = p.train;
   if (T <= 0 || N <= 0 || (long)T * N > (1L << 20))
     return pfail(PNVO_ERR_ARG, "bad rollout shape T = " + std::to_string(T) + ", N = " + std::to_string(N));
-  if (!depth || !goal || !prev_actions || !masks || !hidden_in || !actions || !hidden_out)
+  if ((!depth && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !actions || !hidden_out)
     return pfail(PNVO_ERR_ARG, "null argument");
-  (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = T * N;
   const bool gru = is_gru(c);
@@ -785,6 +850,8 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   hipStream_t s = (hipStream_t)stream;
   int rc = ensure_ws(p, t, M);
   if (rc != PNVO_OK) return rc;
+  if ((rc = depth ? ensure_pooled(p, t, M) : ensure_feat(p, t, M)) != PNVO_OK) return rc;
+  t->from_features = depth == nullptr;
   t->T = T;
   t->N = N;
   t->M = M;
@@ -793,13 +860,22 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   PCHK(hipMemcpyAsync(t->masks, masks, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
   PCHK(hipMemcpyAsync(t->actions, actions, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   PCHK(hipMemcpyAsync(t->hid0, hidden_in, rnn_state_floats(c, N) * sizeof(float), hipMemcpyDeviceToDevice, s));
-  PCHK(mark(t, 0, s));
-  if ((rc = pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK) return rc;
-  rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, nullptr, nullptr, t->enc_out, stream);
-  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
-  PCHK(mark(t, 1, s));
-  const float *visual = pnvo_train_hidden(p.enc);
-  if (!visual) return pfail(PNVO_ERR_STATE, "policy visual encoder kept no hidden vector");
+  const float *visual = nullptr;
+  if (depth) {
+    PCHK(mark(t, 0, s));
+    if ((rc = pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK) return rc;
+    rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, nullptr, nullptr, t->enc_out, stream);
+    if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+    PCHK(mark(t, 1, s));
+    visual = pnvo_train_hidden(p.enc);
+    if (!visual) return pfail(PNVO_ERR_STATE, "policy visual encoder kept no hidden vector");
+  } else {                               // the encoder does not run: visual_fc on the caller's features, kept for dW = d visual^T . features
+    PCHK(hipMemcpyAsync(t->feat, vfeat, (size_t)M * policy_feature_floats(p) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PCHK(mark(t, 0, s));
+    if ((rc = launch_visual_fc(p, t->feat, M, t->visual, s)) != PNVO_OK) return rc;
+    PCHK(mark(t, 1, s));
+    visual = t->visual;
+  }
   PCHK(launch_policy_inputs(p, visual, goal, prev_actions, t->masks, M, t->x0, t->rows, t->g3, s));
   const float *xin = t->x0;
   int K = K0;
@@ -840,6 +916,8 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
   PCHK(mark(t, 2, s));
   return PNVO_OK;
 }
+
+extern "C" {
 
 int pnvo_policy_ppo_loss(pnvo_policy_handle h, const float *actions_logp_old, const float *adv, const float *value_preds,
                          const float *returns, float clip, float value_coef, float entropy_coef, int use_clipped_value_loss, float *out3,
@@ -931,6 +1009,18 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
                      t->rows, t->g3, M, Hd, A + 1, grad_of(t, p.tgt_w), grad_of(t, p.tgt_b), grad_of(t, p.emb), t->dY);
   PCHK(hipGetLastError());
   PCHK(mark(t, 6, s));
+  if (t->from_features) {
+    // visual_fc alone, whatever train_encoder says: nothing of the encoder ran, and no gradient is taken with respect to the features.
+    // d visual (t->dY) through the ReLU, dW = d visual^T . features, db = colsum(d visual); the encoder's range stays at the memset's zeros
+    const int F = (int)policy_feature_floats(p);
+    hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, t->visual, (long)M * Hd, t->dY);
+    PCHK(hipGetLastError());
+    GemmArgs dw{t->dY, t->feat, nullptr, nullptr, grad_of(t, p.vfc_w), Hd, F, M, 1, (long)Hd, (long)F, 1, (long)F};
+    PCHK((launch_gemm<false, false>(dw, s)));
+    PCHK(launch_colsum(t->dY, M, Hd, Hd, grad_of(t, p.vfc_b), s));
+    PCHK(mark(t, 7, s));
+    return PNVO_OK;
+  }
   const int rc = pnvo_train_backward_from_hidden(p.enc, t->dY, train_encoder == 0, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   if (train_encoder) {

@@ -8,10 +8,14 @@ normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-
 only HOLDS parameters; ``act`` is one call into libpnvo.so (pnvo_policy_act) on the caller's current HIP stream plus the
 categorical sampling / arg-max over the 4 logits, which stays in torch as in the reference (policy.py:38-43).
 ``evaluate_actions`` (PPO training of the policy) exists once a ``ppo.PolicyTrainStep`` has been attached to the policy (ppo.py: the
-rollout forward, back-propagation through time and Adam on one flat buffer); a plain policy raises NotImplementedError.  No CPU fallback.
+rollout forward, back-propagation through time and Adam on one flat buffer); a plain policy raises NotImplementedError.
+``policy.net.visual_encoder`` is callable (pnvo_policy_encode) and has ``output_shape``, and ``act`` / ``get_value`` / ``evaluate_actions``
+take ``observations["visual_features"]`` in place of ``depth`` (resnet_policy.py:249-252): the reference trainers' frozen-encoder
+branch (RL.DDPPO.train_encoder False, ddppo_trainer.py:158-161,257-271).  No CPU fallback.
 """
 import ctypes as C
 import math
+import weakref
 
 import torch
 import torch.nn as nn
@@ -21,6 +25,7 @@ from .obs_transforms import DIV_CONTIGUOUS, as_transform, launch_resize, transfo
 from .registry import baseline_registry
 
 GOAL_SENSOR = "pointgoal_with_gps_compass"
+FEATURES_KEY = "visual_features"                         # ddppo_trainer.py:257-271, resnet_policy.py:249-252
 
 
 class _Holder(nn.Module):
@@ -40,6 +45,14 @@ def _rnn(rnn_type):
     if rnn_type not in RNN_TYPES:
         raise NotImplementedError(f"rnn_type {rnn_type!r}: the HIP policy implements 'LSTM' and 'GRU'")
     return RNN_TYPES[rnn_type]
+
+
+def encoder_output_shape(*, width, height, flat_size=2048):
+    """ResNetEncoder.output_shape (resnet_policy.py:106-133) for a [height, width] depth frame: (C, fh, fw) with
+    fh, fw = ceil((H // 2) / 32), ceil((W // 2) / 32) — avg_pool2d(2), then the backbone's final_spatial_compress of 1 / 32 — and
+    C = round(flat_size / (fh * fw)): the shape of the tensor the encoder returns, rows before columns."""
+    fh, fw = int(math.ceil((height // 2) / 32)), int(math.ceil((width // 2) / 32))
+    return int(round(flat_size / (fh * fw))), fh, fw
 
 
 def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048, rnn_type="LSTM"):
@@ -74,6 +87,7 @@ def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_action
              (pre + "compression.1.bias", (comp,))]
     spec = [("net.prev_action_embedding.weight", (n_actions + 1, 32)), ("net.tgt_embeding.weight", (32, 3)),
             ("net.tgt_embeding.bias", (32,))] + spec
+    assert (comp, h, w) == encoder_output_shape(width=width, height=height, flat_size=flat_size)
     spec += [("net.visual_fc.1.weight", (hidden, comp * h * w)), ("net.visual_fc.1.bias", (hidden,))]
     for layer in range(rnn_layers):
         k = hidden + 64 if layer == 0 else hidden
@@ -122,6 +136,32 @@ class _NetHolder(_Holder):
         return False                                       # a depth encoder is always present here
 
 
+class _EncoderHolder(_Holder):
+    """`policy.net.visual_encoder` of the reference (ResNetEncoder, resnet_policy.py:61-175) as the trainers' frozen-encoder branch uses
+    it (ddppo_trainer.py:158-161,257-271; ppo_trainer.py:270-272): the holder of the encoder's parameters, callable on an observation
+    dict, with output_shape.  The policy it belongs to is reached through a weak reference: the policy is neither a submodule nor a
+    strong attribute of its own encoder."""
+
+    @property
+    def is_blind(self):
+        return False
+
+    @property
+    def output_shape(self):
+        return self._output_shape
+
+    def _policy(self):
+        pol = self._policy_ref()
+        if pol is None or pol.net.visual_encoder is not self:       # (a copied module tree keeps the original's reference)
+            raise RuntimeError("this visual encoder is not part of a live policy: call it through policy.net.visual_encoder")
+        return pol
+
+    def forward(self, observations):
+        """observations['depth'] [B,Hs,Ws,1] -> [B, C, fh, fw] float32 on the device: RL.OBS_TRANSFORM, avg_pool2d(2), the backbone,
+        compression conv + GroupNorm(1) + ReLU (one call into libpnvo.so: pnvo_policy_encode).  No gradient, no CPU fallback."""
+        return self._policy()._encode(observations)
+
+
 @baseline_registry.register_policy(name="resnet_rnn_policy")
 class PointNavResNetPolicy(nn.Module):
     def __init__(self, *, observation_space, action_space, goal_sensor_uuid=GOAL_SENSOR, hidden_size=512,
@@ -168,6 +208,12 @@ class PointNavResNetPolicy(nn.Module):
         net = self.net
         net.__class__ = _NetHolder
         net._layers, net._hidden, net._states = self._layers, self._hidden, self._states
+        # ... and call net.visual_encoder when RL.DDPPO.train_encoder is False (ddppo_trainer.py:257-271)
+        enc = net.visual_encoder
+        enc.__class__ = _EncoderHolder
+        enc._output_shape = encoder_output_shape(width=self._W, height=self._H)
+        enc._policy_ref = weakref.ref(self)
+        self._feat_shape = enc._output_shape
         self._handle = None
         self._handle_dev = None
         self._loaded_sig = None
@@ -229,13 +275,9 @@ class PointNavResNetPolicy(nn.Module):
             raise RuntimeError("pointnav_vo_amd policies run on an MI355X only: move the policy with .to('cuda') "
                                "(there is no CPU fallback)")
         dev = ref.device
+        vis, from_features = self._visual_input(observations, dev)
         self._ensure(dev)
-        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
-        B = depth.shape[0]
-        if self._obs_transform is not None:
-            depth = self._transform_depth(depth, dev)
-        if tuple(depth.shape[1:]) != (self._H, self._W, 1):
-            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
+        B = vis.shape[0]
         goal = observations[GOAL_SENSOR].to(device=dev, dtype=torch.float32).contiguous().reshape(B, 2)
         pa = prev_actions.to(device=dev, dtype=torch.int64).contiguous().reshape(B)
         mk = masks.to(device=dev, dtype=torch.float32).contiguous().reshape(B)
@@ -248,9 +290,52 @@ class PointNavResNetPolicy(nn.Module):
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(_lib.lib.pnvo_policy_act(self._handle, p(depth), p(goal), p(pa), p(mk), p(hin), int(B), p(hout),
-                                                p(feats), p(logits), p(value), stream))
+            fn = _lib.lib.pnvo_policy_act_features if from_features else _lib.lib.pnvo_policy_act
+            _lib.check(fn(self._handle, p(vis), p(goal), p(pa), p(mk), p(hin), int(B), p(hout), p(feats), p(logits), p(value), stream))
         return feats, hout, logits, value
+
+    def _visual_input(self, observations, dev):
+        """-> (tensor, from_features): observations['visual_features'] [B,C,fh,fw] when the key is present (resnet_policy.py:249-252: the
+        encoder does not run and 'depth' need not be there), else the transformed observations['depth'] [B,H,W,1].  Every check is made
+        here, before anything is launched."""
+        if FEATURES_KEY in observations:
+            feats = observations[FEATURES_KEY].to(device=dev, dtype=torch.float32).contiguous()
+            if feats.dim() < 1 or tuple(feats.shape[1:]) != tuple(self._feat_shape):
+                raise ValueError(f"observations['{FEATURES_KEY}'] has shape {tuple(feats.shape)}, expected "
+                                 f"{('B',) + tuple(self._feat_shape)} (net.visual_encoder.output_shape)")
+            return feats, True
+        if "depth" not in observations:
+            raise ValueError(f"observations hold neither '{FEATURES_KEY}' nor 'depth' (keys: {sorted(observations.keys())}): the policy "
+                             "needs one of them")
+        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
+        if self._obs_transform is not None:
+            depth = self._transform_depth(depth, dev)
+        if tuple(depth.shape[1:]) != (self._H, self._W, 1):
+            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
+        return depth, False
+
+    def _encode(self, observations):
+        ref = next(self.parameters())
+        if ref.device.type != "cuda":
+            raise RuntimeError("pointnav_vo_amd policies run on an MI355X only: move the policy with .to('cuda') "
+                               "(there is no CPU fallback)")
+        dev = ref.device
+        if "depth" not in observations:
+            raise ValueError(f"net.visual_encoder needs observations['depth'] (keys: {sorted(observations.keys())})")
+        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
+        if self._obs_transform is not None:
+            depth = self._transform_depth(depth, dev)
+        if tuple(depth.shape[1:]) != (self._H, self._W, 1):
+            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
+        self._ensure(dev)
+        B = depth.shape[0]
+        out = torch.empty((B,) + tuple(self._feat_shape), device=dev, dtype=torch.float32)
+        if B:
+            with torch.cuda.device(dev):
+                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                _lib.check(_lib.lib.pnvo_policy_encode(self._handle, C.c_void_p(depth.data_ptr()), int(B), C.c_void_p(out.data_ptr()),
+                                                       stream))
+        return out
 
     def _transform_depth(self, depth, dev):
         """[B,Hs,Ws,1] sensor depth -> [B,VIS_H,VIS_W,1] by the observation transform, before avg_pool2d(2) (resnet_policy.py:157-168).

@@ -83,6 +83,7 @@ class PolicyTrainStep:
             _lib.check(_lib.lib.pnvo_policy_train_attach(h, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), self.store.toc,
                                                          len(self.store.named)))
         self.step_count = 0
+        self._from_features = False                             # the last evaluate_actions took observations['visual_features']
         self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
         self._norm = torch.zeros(1, device=self.dev, dtype=torch.float32)
         policy._train_step = self                               # evaluate_actions delegates here; act reads the flat buffer
@@ -96,7 +97,9 @@ class PolicyTrainStep:
         They end with the last parameter, not at n_params: the library's tail starts right behind the last parameter, inside the final
         alignment gap, and a copy the refresh rewrites must not collect Adam moments that no checkpoint carries."""
         end = max(o + k for o, k in self.offsets.values())
-        if self.train_encoder:
+        # after an evaluate_actions from visual_features no encoder parameter has a gradient, whatever train_encoder says: the reference's
+        # have `grad is None` there and torch's Adam skips them (no step, no moment update)
+        if self.train_encoder and not self._from_features:
             return [(0, end)]
         lo, hi = self.encoder_range
         return [(a, b) for a, b in ((0, lo), (hi, end)) if b > a]
@@ -130,13 +133,9 @@ class PolicyTrainStep:
         """-> (value [M,1], action_log_probs [M,1], distribution_entropy (scalar), rnn_hidden_states) as Policy.evaluate_actions
         (policy.py:52-63).  Rows are T-major (row t*N + n); N = rnn_hidden_states.shape[1], T = M / N (T = 1: single_forward)."""
         pol, dev = self.policy, self.dev
+        vis, from_features = pol._visual_input(observations, dev)   # visual_features when present, else depth; checked before any launch
         self._sync_params()
-        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
-        if pol._obs_transform is not None:
-            depth = pol._transform_depth(depth, dev)
-        M = depth.shape[0]
-        if tuple(depth.shape[1:]) != (pol._H, pol._W, 1):
-            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [M,{pol._H},{pol._W},1]")
+        M = vis.shape[0]
         hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
         N = hin.shape[1]
         S = pol.num_recurrent_layers
@@ -153,9 +152,15 @@ class PolicyTrainStep:
         logp = torch.empty((M, 1), device=dev, dtype=torch.float32)
         entropy = torch.empty((), device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.pnvo_policy_evaluate(pol._handle, _ptr(depth), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T), int(N),
-                                                     _ptr(act), int(self.train_encoder), _ptr(hout), _ptr(value), _ptr(logp),
-                                                     _ptr(entropy), self._stream()))
+            if from_features:
+                _lib.check(_lib.lib.pnvo_policy_evaluate_features(pol._handle, _ptr(vis), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T),
+                                                                  int(N), _ptr(act), _ptr(hout), _ptr(value), _ptr(logp), _ptr(entropy),
+                                                                  self._stream()))
+            else:
+                _lib.check(_lib.lib.pnvo_policy_evaluate(pol._handle, _ptr(vis), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T), int(N),
+                                                         _ptr(act), int(self.train_encoder), _ptr(hout), _ptr(value), _ptr(logp),
+                                                         _ptr(entropy), self._stream()))
+        self._from_features = from_features
         return value, logp, entropy, hout
 
     def ppo_loss(self, old_action_log_probs, adv_targ, value_preds, returns, clip_param, value_loss_coef, entropy_coef,
@@ -171,7 +176,8 @@ class PolicyTrainStep:
         return self._out3
 
     def backward(self):
-        """total_loss.backward(): fills self.grad (overwrites)."""
+        """total_loss.backward(): fills self.grad (overwrites).  After an evaluate_actions from visual_features the encoder's range is
+        exactly zero, whatever train_encoder says (the library knows which kind of evaluate came last)."""
         with torch.cuda.device(self.dev):
             _lib.check(_lib.lib.pnvo_policy_backward(self.policy._handle, int(self.train_encoder), self._stream()))
 

@@ -14,6 +14,14 @@ policy with random weights: GroupNorm-ResNet18 encoder, nn.LSTM run over the seg
 RNNStateEncoder does, Categorical heads, the PPO loss, clip_grad_norm_, torch.optim.Adam).  It is the only comparison there is: the
 project could not do this update at all before.  No threshold: the record says which side wins, phase by phase.
 --rnn GRU runs both sides with the GRU state encoder (state [LAYERS, N, HIDDEN]); the phase keys keep their names.
+
+    python tools/bench_ppo_update.py --static-encoder [--n 2 8] [--out profiles/static_encoder.md]
+
+The frozen encoder (RL.DDPPO.train_encoder False) two ways, in one process on one GPU, on the same rollout and the same policy, the two
+updates alternating iteration by iteration: frames in (observations['depth'], train_encoder=False: the encoder's train-mode forward runs
+over all T * N frames and the backward stops behind visual_fc) against features in (observations['visual_features'], computed once by
+policy.net.visual_encoder: visual_fc's GEMM is all that is left of the encoder).  Then one full recurrent_generator pass (two minibatches
+of N environments each, every tensor gathered, waited for) of a RolloutStorage holding frames against one holding features only.
 """
 import argparse
 import json
@@ -111,6 +119,105 @@ def bench_hip(T, N, iters, warmup, dev, rnn="LSTM"):
     out = {k: statistics.median([p[k] for p in phases[warmup:]]) for k in phases[0]}
     out.update(tm.medians(warmup))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- frozen encoder
+def bench_static_encoder(T, N, iters, warmup, dev, rnn="LSTM"):
+    from pointnav_vo_amd.policy import FEATURES_KEY, PointNavResNetPolicy
+    from pointnav_vo_amd.ppo import PolicyTrainStep
+    from pointnav_vo_amd.rollout_storage import RolloutStorage
+
+    class Box:
+        def __init__(self, shape):
+            self.shape = shape
+
+    class Space:
+        def __init__(self, d):
+            self.spaces = d
+
+    class ActionSpace:
+        n = ACTIONS
+
+    torch.manual_seed(0)
+    pol = PointNavResNetPolicy(observation_space=Space({"depth": Box((H, W, 1)), GOAL: Box((2,))}), action_space=ActionSpace(),
+                               hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type=rnn, backbone="resnet18",
+                               normalize_visual_inputs=False, obs_transform=None, vis_types=["depth"]).to(dev)
+    enc = pol.net.visual_encoder
+    step = PolicyTrainStep(pol, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM, train_encoder=False)
+    step.timing(True)
+    b = make_batch(T, N, dev, rnn=rnn)
+    tm = Timer()
+    for _ in range(2):                                          # the first pass grows the workspaces; the second is the figure
+        with tm.span("encode"):
+            feats = torch.cat([enc({"depth": b["depth"][i:i + 64]}) for i in range(0, T * N, 64)])
+    inputs = {"frames": {"depth": b["depth"], GOAL: b["goal"]}, "features": {FEATURES_KEY: feats, GOAL: b["goal"]}}
+    phases = {"frames": [], "features": []}
+    for _ in range(warmup + iters):
+        for kind, obs in inputs.items():                        # alternating: both see the same machine state
+            with tm.span(kind + ": whole update"):
+                step.evaluate_actions(obs, b["hidden"], b["prev"], b["masks"], b["actions"])
+                step.ppo_loss(b["old"], b["adv"], b["vp"], b["ret"], CLIP, VALUE_COEF, ENTROPY_COEF, True)
+                step.backward()
+                with tm.span(kind + ": clip + Adam + refresh"):
+                    step.clip_grad_norm()
+                    step.optimizer_step()
+            phases[kind].append(step.phase_ms())
+    out = {kind: {k: statistics.median([p[k] for p in ph[warmup:]]) for k in ph[0]} for kind, ph in phases.items()}
+    # ---- the generator pass: 2 N environments, two minibatches
+    envs = 2 * N
+    S = (2 if rnn == "LSTM" else 1) * LAYERS
+    space = Space({"depth": Box((H, W, 1)), FEATURES_KEY: Box(tuple(enc.output_shape)), GOAL: Box((2,))})
+    adv = torch.zeros(T, envs, 1, device=dev)
+    stored = {}
+    for kind, sensor in (("frames", "depth"), ("features", FEATURES_KEY)):
+        st = RolloutStorage(T, envs, space, ActionSpace(), HIDDEN, S, sensors=[sensor, GOAL])
+        st.to(dev)
+        st.observations[sensor].uniform_()
+        st.step = T
+        stored[kind] = sum(v.numel() * 4 for v in st.observations.values())
+        for _ in range(warmup + iters):
+            with tm.span(kind + ": generator pass"):
+                for sample in st.recurrent_generator(adv, 2):
+                    pass
+        del st
+        torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    for kind in inputs:
+        for k in ("whole update", "clip + Adam + refresh", "generator pass"):
+            out[kind][k] = statistics.median([x.elapsed_time(y) for x, y in tm.t[f"{kind}: {k}"]][warmup:])
+        out[kind]["stored observation MB"] = stored[kind] / 1e6
+    out["encode_ms"] = tm.t["encode"][1][0].elapsed_time(tm.t["encode"][1][1])
+    return out
+
+
+STATIC_ORDER = ["encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward", "clip + Adam + refresh", "whole update",
+                               "generator pass", "stored observation MB"]
+
+
+def static_encoder_report(a, dev):
+    lines = ["# Frozen-encoder PPO update: frames in against features in", "",
+             f"`tools/bench_ppo_update.py --static-encoder`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer {a.rnn}, 4 actions, "
+             f"train_encoder False; median of {a.iters} iterations after {a.warmup} warm-up, HIP events, one process, one policy and one "
+             f"rollout for both columns, the two updates alternating, {torch.cuda.get_device_name(0)}.  Milliseconds unless named otherwise.",
+             "", "frames in: `observations['depth']` (the encoder's train-mode forward over all T * N frames, the backward stops behind "
+             "visual_fc).  features in: `observations['visual_features']` from `policy.net.visual_encoder` (visual_fc's GEMM is what "
+             "`encoder forward` holds, its backward what `encoder backward` holds).  generator pass: one `recurrent_generator` pass "
+             "over 2 N environments in two minibatches of a storage that holds the frames, or the features only.", ""]
+    record = {}
+    for N in a.n:
+        r = bench_static_encoder(a.steps, N, a.iters, a.warmup, dev, a.rnn)
+        torch.cuda.empty_cache()
+        record[f"N={N}"] = r
+        lines += [f"## N = {N}  (M = {a.steps * N} rows per minibatch)", "", "| phase | frames in | features in | frames / features |",
+                  "|---|---:|---:|---:|"]
+        for k in STATIC_ORDER:
+            f, g = r["frames"][k], r["features"][k]
+            lines.append(f"| {LABEL.get(k, k).replace('LSTM', a.rnn)} | {f:.3f} | {g:.3f} | {f / g if g > 0 else float('nan'):.2f} |")
+        ok = r["features"]["whole update"] <= r["frames"]["whole update"]
+        lines += ["", f"Encoding the {a.steps * N} frames (in batches of 64, once, not part of either update; a trainer encodes N frames per "
+                  f"rollout step instead): {r['encode_ms']:.3f} ms.",
+                  f"Whole update, features in at or below frames in: {'yes' if ok else 'NO - to be explained'}.", ""]
+    return lines, record
 
 
 # ---------------------------------------------------------------------------------------------------------------- eager torch
@@ -224,12 +331,17 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--rnn", choices=["LSTM", "GRU"], default="LSTM")
+    ap.add_argument("--static-encoder", action="store_true", help="frozen encoder: frames in against features in (see the docstring)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ppo_update.py measures on an MI355X: no GPU here, nothing measured")
     if a.iters < 10:
         raise SystemExit("--iters must be at least 10 (median of >= 10 timed iterations)")
     dev = torch.device("cuda", 0)
+    if a.static_encoder:
+        lines, record = static_encoder_report(a, dev)
+        finish(a, lines, record)
+        return
     lines = ["# PPO minibatch update of the navigation policy: HIP path vs torch eager", "",
              f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer {a.rnn}, 4 actions, train_encoder; "
              f"median of {a.iters} iterations after {a.warmup} warm-up, HIP events, one process, {torch.cuda.get_device_name(0)}.",
@@ -255,6 +367,10 @@ def main():
         if eager and "error" in eager:
             lines += ["", f"torch eager failed: `{eager['error']}`"]
         lines.append("")
+    finish(a, lines, record)
+
+
+def finish(a, lines, record):
     text = "\n".join(lines)
     print(text)
     print(json.dumps(record))
