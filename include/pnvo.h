@@ -361,13 +361,18 @@ int pnvo_destroy(pnvo_handle h);
 #define PNVO_RNN_LSTM 0
 #define PNVO_RNN_GRU 1
 typedef struct {
-  int32_t width, height;      /* depth frame W, H (341, 192); the encoder sees (W/2, H/2) after avg_pool2d(2) */
+  int32_t width, height;      /* frame W, H (341, 192) of every visual type; the encoder sees (W/2, H/2) after avg_pool2d(2) */
   int32_t baseplanes;         /* resnet_baseplanes (32) */
   int32_t hidden;             /* hidden_size (512) */
   int32_t n_actions;          /* action_space.n (4) */
   int32_t rnn_layers;         /* num_recurrent_layers (2) */
   int32_t flat_size;          /* after_compression_flat_size (2048) */
   int32_t rnn_type;           /* PNVO_RNN_LSTM (0: a zeroed field keeps the LSTM) or PNVO_RNN_GRU (1); anything else is refused */
+  /* RL.Policy.visual_types / normalize_visual_inputs (resnet_policy.py:82-101; ddppo_trainer.py:118-132).  All three zero: the
+   * depth-only, un-normalised policy of the entry points that take `depth` alone. */
+  int32_t rgb_channels;       /* 0: no "rgb" among the visual types; 3: observations["rgb"] feeds the encoder in front of the depth */
+  int32_t no_depth;           /* 1: "depth" is not among the visual types (needs rgb_channels = 3); 0: it is */
+  int32_t normalize;          /* normalize_visual_inputs -> net.visual_encoder.running_mean_and_var */
 } pnvo_policy_config;
 
 typedef struct pnvo_policy_s *pnvo_policy_handle;
@@ -412,6 +417,42 @@ int pnvo_policy_act_features(pnvo_policy_handle h, const float *visual_features,
                              const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                              float *value, void *stream);
 
+/* ---- RGB / RGB-D input and RunningMeanAndVar (ResNetEncoder.forward, resnet_policy.py:146-174: rgb / 255, torch.cat([rgb, depth]),
+ * F.avg_pool2d(x, 2), running_mean_and_var; model_utils/running_mean_and_var.py:22-63) for handles created with rgb_channels,
+ * no_depth or normalize set.  pnvo_policy_act_rgbd / _encode_rgbd / _evaluate_rgbd are pnvo_policy_act / _encode / _evaluate with
+ *   rgb         [B,H,W,3] values 0..255, uint8 (rgb_is_u8 = 1) or float32 (0): the same bits either way; NULL without rgb_channels
+ *   depth       [B,H,W,1] float32; NULL with no_depth
+ *   run_mean, run_var [C], run_count [1]   the module's own float32 buffers _mean, _var, _count (C = rgb_channels + depth): borrowed,
+ *               never owned; NULL without normalize
+ *   training    0: the buffers are read (module.eval()); 1: the batch — the B (or T * N) frames of this call — is merged into them first,
+ *               in place, on `stream`, with no host synchronisation, and the input is whitened with the UPDATED values
+ *               (running_mean_and_var.py:23-63, single process).  Ignored without normalize.
+ * One launch (policy_input_kernel) reads the frames once and writes the pooled NHWC tensor in the encoder handle's layout — one float
+ * modality of 2C channels [rgb / 255, depth | zeros] — and, when training, per-workgroup partial sums of the first and second moments
+ * about the current running mean; a second small launch adds the partials in a fixed order (the same bits on every run) and
+ * pnvo_rmv_merge's kernel folds them into the buffers (the moments stay float64 up to there: the first batches are centred on a
+ * running mean of zero).  The whitening rides on the encoder's float32 stem as its per-channel scale / shift pair,
+ * rewritten on the device from the buffers at every call; the encoder runs on the per-layer kernels at every batch size.
+ * On a handle with all three fields zero these calls are the depth-only ones (rgb, the statistics and `training` must be NULL / 0);
+ * the depth-only entry points refuse the other handles. */
+int pnvo_policy_act_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                         float *run_count, int training, const float *goal, const int64_t *prev_actions, const float *masks,
+                         const float *hidden_in, int B, float *hidden_out, float *features, float *logits, float *value, void *stream);
+int pnvo_policy_encode_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                            float *run_count, int training, int B, float *features_out, void *stream);
+/* (policy.py:52-63 around the same encoder: the update of rl/ppo/ppo.py:61-139 merges every minibatch it evaluates) */
+int pnvo_policy_evaluate_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                              float *run_count, int training, const float *goal, const int64_t *prev_actions, const float *masks,
+                              const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder, float *hidden_out,
+                              float *value, float *logp, float *entropy, void *stream);
+/* The input stage on its own (tools/bench_policy.py and tests; not part of the drop-in surface; replaces resnet_policy.py:150-168 and,
+ * with moments, running_mean_and_var.py:24-42): pooled_out [B,H/2,W/2,2C]; mode 0: pool only; 1: pool and moments in one pass; 2: pool,
+ * then the moments from a second pass over pooled_out (the two-launch form the fused one is measured against).  Modes 1 and 2 write
+ * m12_out [2C'] (float64) with C' = rgb_channels + depth: mean (x - center), then mean (x - center)^2, over the B * (H/2) * (W/2) pooled pixels;
+ * center [C'] may be NULL (0). */
+int pnvo_policy_input_stage(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, const float *center, int mode, int B,
+                            float *pooled_out, double *m12_out, void *stream);
+
 int pnvo_policy_destroy(pnvo_policy_handle h);
 
 /* ---- one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions, policy.py:52-63):
@@ -422,7 +463,7 @@ int pnvo_policy_destroy(pnvo_policy_handle h);
  * pnvo_policy_train_attach: params / grads are DEVICE buffers of n_floats floats holding every tensor of
  * PointNavResNetPolicy.named_parameters() in that order at the offsets of `toc` (offsets multiples of 4 floats, the buffer 16-byte
  * aligned), followed by at least pnvo_policy_train_tail_floats(h) further floats that belong to the library (the stem weight
- * zero-padded to the encoder handle's two input channels, and that handle's unused output head).  After the call the recurrent part
+ * [C0,C,7,7] zero-padded to the encoder handle's 2C input channels, and that handle's unused output head).  After the call the recurrent part
  * and the heads read their weights from `params` — pnvo_policy_act included, so an optimiser step on `params` followed by
  * pnvo_policy_train_refresh is all it takes for the next act to use the new weights — and the visual encoder is attached with
  * pnvo_train_attach.  pnvo_policy_load_weights is refused from then on.  Requires pnvo_policy_load_weights before it. */

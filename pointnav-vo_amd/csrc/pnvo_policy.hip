@@ -10,6 +10,10 @@
 // modality of 2 channels [pooled depth | 0] and no whitening (normalize_visual_inputs is False for the depth-only policy,
 // ddppo_trainer.py:118-121).  The recurrent part is tiny and weight-bandwidth-bound at B = number of environments
 // (9.4 MB of LSTM weights per step), so its Linears are wave-per-output-row dot products on the vector ALU, not MFMA.
+// Policies whose visual types name rgb, or that normalise their input (pnvo_policy_config.rgb_channels / no_depth / normalize), enter
+// through pnvo_policy_act_rgbd / pnvo_policy_encode_rgbd: policy_input_kernel (rgb / 255, torch.cat([rgb, depth]), the pool, the zero
+// channels and — in training mode — the batch moments of RunningMeanAndVar in ONE pass over the frames) in front of a handle configured
+// with one float modality of 2C channels on the float32 stem, whose whitening pair policy_whiten_kernel writes from the module's buffers.
 // pnvo_policy_encode is net.visual_encoder called on its own (the encoder handle stopped behind the compression conv, then
 // feature_pack_kernel -> [B, C, fh, fw]); pnvo_policy_act_features is the step fed with that tensor (vfc_rows_kernel / the GEMM of
 // policy_train.hip in place of the encoder).
@@ -29,6 +33,7 @@ namespace pnvo {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // F.avg_pool2d(x, 2) of a 1-channel NHWC frame (floor: odd trailing row / column dropped) -> [N,H/2,W/2,2] with
 // channel 1 = 0 (the encoder's stem consumes 2-channel pieces).
@@ -44,6 +49,218 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float *d, int N, in
   const float s = ((p[0] + p[1]) + p[W]) + p[W + 1];
   out[2 * e] = s * 0.25f;
   out[2 * e + 1] = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the input stage
+// ResNetEncoder.forward up to the backbone (resnet_policy.py:150-170) for the rgb / rgb-d / normalised handles, in one pass over the
+// frames: rgb / 255, torch.cat([rgb, depth]), F.avg_pool2d(x, 2) (floor: an odd trailing row / column is dropped) -> [N,H/2,W/2,2C],
+// channels [rgb, depth | C zeros]: ONE float modality of the encoder handle, whose reference order (first halves, then second halves)
+// is then the reference's channel order followed by zero-weight channels.  With `train` the launch also leaves, per workgroup, the
+// sums of (x - center) and (x - center)^2 per channel over its pooled pixels — the power-3 quantities of pnvo_input_moments that
+// pnvo_rmv_merge consumes — so RunningMeanAndVar's update (running_mean_and_var.py:24-42) costs no second pass over the frames.
+//
+// Bandwidth-bound: a thread owns FOUR consecutive pooled pixels of a row, i.e. two input rows of 8 pixels — 24 bytes of uint8 rgb per
+// row, fetched as the 6 or 7 aligned dwords that cover them and shifted into place (a row starts at any byte: W * 3 need not be a
+// multiple of 4), or 24 floats of float32 rgb / 8 floats of depth, fetched as the aligned 16-byte chunks that cover them and selected
+// by the start's offset.  An aligned chunk is only loaded when it holds at least one element the thread needs, so every load stays
+// inside the 16-byte block of a valid element.  uint8 converts to float exactly: both kinds of rgb give the same bits.
+// Sums: per thread in pixel order, a fixed xor tree over the wave, the four waves in order -> part[row][workgroup] (doubles); no atomics.
+template <int NF>
+__device__ __forceinline__ void load_row(const float *p, int nvalid, float (&out)[NF]) {
+  constexpr int NC = (NF + 3 + 3) / 4;
+  const uintptr_t a = (uintptr_t)p;
+  const unsigned m = (unsigned)(a >> 2) & 3u;
+  const f32x4 *q = reinterpret_cast<const f32x4 *>(a - 4 * m);
+  const float *end = p + nvalid;
+  float t[NC * 4];
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const f32x4 c = reinterpret_cast<const float *>(q + i) < end ? q[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[4 * i + e] = c[e];
+  }
+#pragma unroll
+  for (int j = 0; j < NF; ++j) out[j] = m == 0 ? t[j] : (m == 1 ? t[j + 1] : (m == 2 ? t[j + 2] : t[j + 3]));
+}
+template <int NF>
+__device__ __forceinline__ void load_row(const unsigned char *p, int nvalid, float (&out)[NF]) {
+  static_assert(NF % 4 == 0, "whole dwords");
+  constexpr int NW = NF / 4 + 1;
+  const uintptr_t a = (uintptr_t)p;
+  const unsigned m = (unsigned)a & 3u;
+  const unsigned *q = reinterpret_cast<const unsigned *>(a - m);
+  const unsigned char *end = p + nvalid;
+  unsigned w[NW];
+#pragma unroll
+  for (int i = 0; i < NW; ++i) w[i] = reinterpret_cast<const unsigned char *>(q + i) < end ? q[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < NF / 4; ++i) {
+    const unsigned v = (unsigned)(((((unsigned long long)w[i + 1]) << 32) | (unsigned long long)w[i]) >> (8 * m));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) out[4 * i + e] = (float)((v >> (8 * e)) & 0xffu);
+  }
+}
+
+constexpr int INPUT_MAX_BLOCKS = 2048;      // workgroups of a launch = rows of `part` per moment
+
+template <int CR, bool HAS_D, typename RGB_T>
+__global__ __launch_bounds__(256) void policy_input_kernel(const RGB_T *rgb, const float *depth, int N, int H, int W, const float *center,
+                                                         int train, float *out, double *part) {
+  constexpr int C = CR + (HAS_D ? 1 : 0), C2 = 2 * C;
+  const int Ho = H / 2, Wo = W / 2, Gw = (Wo + 3) / 4;
+  const long groups = (long)N * Ho * Gw;
+  float ctr[C];
+  double s1[C], s2[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    ctr[c] = (train && center != nullptr) ? center[c] : 0.f;
+    s1[c] = 0.0;
+    s2[c] = 0.0;
+  }
+  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+    const int xq = (int)(g % Gw);
+    const int y = (int)((g / Gw) % Ho);
+    const long n = g / ((long)Gw * Ho);
+    const int npx = min(4, Wo - 4 * xq);
+    float v[4][C];
+    if constexpr (CR > 0) {
+      float r0[8 * CR], r1[8 * CR];
+      const RGB_T *p0 = rgb + ((n * H + 2 * y) * W + 8 * xq) * CR;
+      load_row(p0, 2 * CR * npx, r0);
+      load_row(p0 + (long)W * CR, 2 * CR * npx, r1);
+#pragma unroll
+      for (int px = 0; px < 4; ++px)
+#pragma unroll
+        for (int c = 0; c < CR; ++c)
+          v[px][c] = (((r0[2 * CR * px + c] / 255.0f + r0[2 * CR * px + CR + c] / 255.0f) + r1[2 * CR * px + c] / 255.0f) +
+                      r1[2 * CR * px + CR + c] / 255.0f) * 0.25f;
+    }
+    if constexpr (HAS_D) {
+      float d0[8], d1[8];
+      const float *p0 = depth + (n * H + 2 * y) * W + 8 * xq;
+      load_row(p0, 2 * npx, d0);
+      load_row(p0 + W, 2 * npx, d1);
+#pragma unroll
+      for (int px = 0; px < 4; ++px) v[px][CR] = (((d0[2 * px] + d0[2 * px + 1]) + d1[2 * px]) + d1[2 * px + 1]) * 0.25f;
+    }
+    float *o = out + ((n * Ho + y) * Wo + 4 * xq) * C2;
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      if (px >= npx) break;
+      float e[C2];
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        e[c] = v[px][c];
+        e[C + c] = 0.f;
+      }
+      if constexpr (C2 % 4 == 0) {                         // a pixel is 32 bytes: 16-byte stores
+#pragma unroll
+        for (int k = 0; k < C2; k += 4) *reinterpret_cast<f32x4 *>(o + px * C2 + k) = f32x4{e[k], e[k + 1], e[k + 2], e[k + 3]};
+      } else {                                             // 8 or 24 bytes: 8-byte stores
+#pragma unroll
+        for (int k = 0; k < C2; k += 2) *reinterpret_cast<f32x2 *>(o + px * C2 + k) = f32x2{e[k], e[k + 1]};
+      }
+      if (train) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const double d = (double)(v[px][c] - ctr[c]);
+          s1[c] += d;
+          s2[c] += d * d;
+        }
+      }
+    }
+  }
+  if (!train) return;                                      // (uniform)
+  __shared__ double red[2 * C][4];
+  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int k = 0; k < 2 * C; ++k) {
+    double s = k < C ? s1[k % C] : s2[k % C];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) red[k][wave] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C)
+    part[(long)threadIdx.x * gridDim.x + blockIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+
+// The moments from the pooled tensor [npix, 2C] instead (the two-launch form pnvo_policy_input_stage mode 2 measures the fused one
+// against): thread = pixels npix-strided, the same partial layout.
+template <int C>
+__global__ __launch_bounds__(256) void pooled_moments_kernel(const float *pooled, long npix, const float *center, double *part) {
+  float ctr[C];
+  double s1[C], s2[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    ctr[c] = center != nullptr ? center[c] : 0.f;
+    s1[c] = 0.0;
+    s2[c] = 0.0;
+  }
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < npix; e += (long)gridDim.x * 256) {
+    float x[C];
+    if constexpr (C % 2 == 0) {
+#pragma unroll
+      for (int c = 0; c < C; c += 2) {
+        const f32x2 t = *reinterpret_cast<const f32x2 *>(pooled + e * 2 * C + c);
+        x[c] = t[0];
+        x[c + 1] = t[1];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) x[c] = pooled[e * 2 * C + c];
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const double d = (double)(x[c] - ctr[c]);
+      s1[c] += d;
+      s2[c] += d * d;
+    }
+  }
+  __shared__ double red[2 * C][4];
+  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int k = 0; k < 2 * C; ++k) {
+    double s = k < C ? s1[k % C] : s2[k % C];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) red[k][wave] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C)
+    part[(long)threadIdx.x * gridDim.x + blockIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+
+// one wave per row of `part` (channel c's first moment, then its second): the workgroups' sums in a fixed order -> m12[row] = sum / npix
+// (float64: the first batches are centred on a running mean of zero, and e2 - e1^2 of a narrow channel does not survive float32)
+__global__ __launch_bounds__(64) void input_moments_final_kernel(const double *part, int nb, double npix, double *m12) {
+  const int row = blockIdx.x;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nb; k += 64) s += part[(long)row * nb + k];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  if (threadIdx.x == 0) m12[row] = s / npix;
+}
+
+// RunningMeanAndVar's buffers [C] -> the encoder handle's 2C channels (mean 0 / variance 1 on the zero channels: what its train-mode
+// forward takes) and the float32 stem's whitening pair (x - mean) / sqrt(max(var, 1e-2)) = x * sc + sh over its CPL channel slots
+// (running_mean_and_var.py:62-63; the arithmetic of whiten_table_kernel).  The handle's one modality keeps its channels in place:
+// stem channel c is reference channel c.
+__global__ __launch_bounds__(64) void policy_whiten_kernel(const float *mean, const float *var, int C, int CPL, float *mean_pad, float *var_pad,
+                                                         float *sc, float *sh) {
+  const int c = threadIdx.x;
+  if (c >= CPL) return;
+  const float mu = c < C ? mean[c] : 0.f, vr = c < C ? var[c] : 1.f;
+  float a = 0.f, b = 0.f;
+  if (c < 2 * C) {
+    mean_pad[c] = mu;
+    var_pad[c] = vr;
+    const double sd = sqrt(fmax((double)vr, 1e-2));
+    a = (float)(1.0 / sd);
+    b = (float)(-(double)mu / sd);
+  }
+  sc[c] = a;
+  sh[c] = b;
 }
 
 // LSTM input x [B, hidden + 64]: visual | Linear(3 -> 32)(rho, cos(-phi), sin(-phi)) | Embedding((a + 1) * mask).  The update step
@@ -293,11 +510,50 @@ __global__ __launch_bounds__(256) void vfc_rows_kernel(const float *x, const flo
   }
 }
 
+template <int CR, bool HAS_D>
+hipError_t launch_policy_input_t(const void *rgb, int rgb_is_u8, const float *depth, int N, int H, int W, const float *center, int train,
+                                 float *out, double *part, int nb, hipStream_t s) {
+  if (rgb_is_u8)
+    hipLaunchKernelGGL((policy_input_kernel<CR, HAS_D, unsigned char>), dim3((unsigned)nb), dim3(256), 0, s, (const unsigned char *)rgb, depth, N,
+                       H, W, center, train, out, part);
+  else
+    hipLaunchKernelGGL((policy_input_kernel<CR, HAS_D, float>), dim3((unsigned)nb), dim3(256), 0, s, (const float *)rgb, depth, N, H, W, center,
+                       train, out, part);
+  return hipGetLastError();
+}
+
+// workgroups of the input stage for N frames: one thread per group of four pooled pixels, grid-strided above INPUT_MAX_BLOCKS
+int input_blocks(const pnvo_policy_config &c, int N) {
+  const long groups = (long)N * (c.height / 2) * ((c.width / 2 + 3) / 4);
+  return (int)std::min<long>((groups + 255) / 256, INPUT_MAX_BLOCKS);
+}
+
+hipError_t launch_policy_input(const pnvo_policy_config &c, const void *rgb, int rgb_is_u8, const float *depth, int N, const float *center,
+                               int train, float *out, double *part, hipStream_t s) {
+  const int nb = input_blocks(c, N);
+  if (c.rgb_channels == 3 && !c.no_depth) return launch_policy_input_t<3, true>(rgb, rgb_is_u8, depth, N, c.height, c.width, center, train, out, part, nb, s);
+  if (c.rgb_channels == 3) return launch_policy_input_t<3, false>(rgb, rgb_is_u8, nullptr, N, c.height, c.width, center, train, out, part, nb, s);
+  return launch_policy_input_t<0, true>(nullptr, 0, depth, N, c.height, c.width, center, train, out, part, nb, s);
+}
+
+hipError_t launch_pooled_moments(int C, const float *pooled, long npix, const float *center, double *part, int nb, hipStream_t s) {
+  if (C == 4) hipLaunchKernelGGL((pooled_moments_kernel<4>), dim3((unsigned)nb), dim3(256), 0, s, pooled, npix, center, part);
+  else if (C == 3) hipLaunchKernelGGL((pooled_moments_kernel<3>), dim3((unsigned)nb), dim3(256), 0, s, pooled, npix, center, part);
+  else hipLaunchKernelGGL((pooled_moments_kernel<1>), dim3((unsigned)nb), dim3(256), 0, s, pooled, npix, center, part);
+  return hipGetLastError();
+}
+
+int ensure_moments(Policy &p) {
+  if (!p.in_part) PCHK(p.in_part.alloc((size_t)8 * INPUT_MAX_BLOCKS));
+  if (!p.m12) PCHK(p.m12.alloc(8));
+  return PNVO_OK;
+}
+
 int ensure_pooled(Policy &p, int B) {
   if (B <= p.cap_pooled) return PNVO_OK;
   p.pooled.reset();                                        // the old workspace goes first
   p.cap_pooled = 0;
-  PCHK(p.pooled.alloc((size_t)B * (p.cfg.height / 2) * (p.cfg.width / 2) * 2));
+  PCHK(p.pooled.alloc(policy_pooled_floats(p.cfg, B)));
   p.cap_pooled = B;
   return PNVO_OK;
 }
@@ -335,6 +591,48 @@ hipError_t pnvo::launch_policy_inputs(const Policy &p, const float *visual, cons
   return hipGetLastError();
 }
 
+int pnvo::policy_obs_check(const Policy &p, const PolicyObs &o, const char *fn) {
+  const pnvo_policy_config &c = p.cfg;
+  const std::string f(fn);
+  if ((c.rgb_channels > 0) != (o.rgb != nullptr))
+    return pfail(PNVO_ERR_ARG, f + ": rgb " + (o.rgb ? "given to a policy without rgb among its visual types" : "missing"));
+  if ((c.no_depth == 0) != (o.depth != nullptr))
+    return pfail(PNVO_ERR_ARG, f + ": depth " + (o.depth ? "given to a policy without depth among its visual types" : "missing"));
+  if (c.normalize ? (!o.mean || !o.var || !o.count) : (o.mean || o.var || o.count || o.training))
+    return pfail(PNVO_ERR_ARG, f + (c.normalize ? ": the policy normalises its visual inputs: run_mean, run_var and run_count are required"
+                                                : ": the policy does not normalise its visual inputs: no statistics, training = 0"));
+  if ((o.rgb && !o.rgb_is_u8 && ((uintptr_t)o.rgb & 3)) || ((uintptr_t)o.depth & 3))
+    return pfail(PNVO_ERR_ARG, f + ": float32 frames must be 4-byte aligned");
+  return PNVO_OK;
+}
+
+int pnvo::policy_input_stage(Policy &p, const PolicyObs &o, int B, float *pooled, hipStream_t s) {
+  const pnvo_policy_config &c = p.cfg;
+  const int C = policy_channels(c);
+  const bool train = c.normalize && o.training;
+  int rc = PNVO_OK;
+  if (train && (rc = ensure_moments(p)) != PNVO_OK) return rc;
+  if (c.normalize && !p.mean_pad) {
+    PCHK(p.mean_pad.alloc(8));
+    PCHK(p.var_pad.alloc(8));
+  }
+  PCHK(launch_policy_input(c, o.rgb, o.rgb_is_u8, o.depth, B, o.mean, train ? 1 : 0, pooled, p.in_part, s));
+  if (train) {
+    const double npix = (double)B * (c.height / 2) * (c.width / 2);
+    hipLaunchKernelGGL(input_moments_final_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, s, p.in_part, input_blocks(c, B), npix, p.m12);
+    PCHK(hipGetLastError());
+    // RunningMeanAndVar.forward's training branch on the module's own buffers (running_mean_and_var.py:41-60): pnvo_rmv_merge's
+    // kernel, fed the float64 moments
+    PCHK(launch_rmv_merge(p.m12, C, B, o.mean, o.var, o.count, s));
+  }
+  if (c.normalize) {
+    hipLaunchKernelGGL(policy_whiten_kernel, dim3(1), dim3(64), 0, s, o.mean, o.var, C, p.enc->CPL, p.mean_pad, p.var_pad, p.enc->stem_sc,
+                       p.enc->stem_sh);
+    PCHK(hipGetLastError());
+  }
+  return PNVO_OK;
+}
+
 const pnvo_tensor_desc *pnvo::policy_find(const pnvo_tensor_desc *toc, int ntoc, const PolicyParam &e, size_t n_floats, int *rc) {
   for (int k = 0; k < ntoc; ++k) {
     if (e.name != toc[k].name) continue;
@@ -359,10 +657,14 @@ int pnvo::policy_encoder_table(const Policy &p, const pnvo_tensor_desc *toc, int
     if (toc[k].ndim < 0 || toc[k].ndim > 4) return pfail(PNVO_ERR_WEIGHTS, "tensor '" + nm + "' has a bad rank");
     const std::vector<int64_t> shape(toc[k].shape, toc[k].shape + toc[k].ndim);
     if (toc[k].offset + numel(shape) > n_floats) return pfail(PNVO_ERR_WEIGHTS, "tensor '" + nm + "' exceeds the buffer");
-    if (nm == pre + "backbone.conv1.0.weight") {          // [C0,1,7,7] -> [C0,2,7,7], second input channel = 0
-      if (shape != std::vector<int64_t>{p.cfg.baseplanes, 1, 7, 7}) return pfail(PNVO_ERR_WEIGHTS, "policy stem must take 1 depth channel");
-      out->push_back({"visual_encoder.backbone.conv1.0.weight", {shape[0], 2, 7, 7}, EncoderEntry::STEM, k});
+    if (nm == pre + "backbone.conv1.0.weight") {          // [C0,C,7,7] -> [C0,2C,7,7], the second half of the input channels = 0
+      const int64_t C = policy_channels(p.cfg);
+      if (shape != std::vector<int64_t>{p.cfg.baseplanes, C, 7, 7})
+        return pfail(PNVO_ERR_WEIGHTS, "policy stem must take " + std::to_string(C) + " input channel" + (C == 1 ? " (depth)" : "s"));
+      out->push_back({"visual_encoder.backbone.conv1.0.weight", {shape[0], 2 * C, 7, 7}, EncoderEntry::STEM, k});
     } else if (nm.compare(0, pre.size(), pre) == 0) {
+      // (RunningMeanAndVar's buffers are no parameters: the handle's whitening pair is written from them on the device at every call)
+      if (nm.compare(pre.size(), 21, "running_mean_and_var.") == 0) continue;
       out->push_back({"visual_encoder." + nm.substr(pre.size()), shape, EncoderEntry::VIEW, k});
     } else if (nm == "net.visual_fc.1.weight" || nm == "net.visual_fc.1.bias") {
       out->push_back({"visual_fc.2." + nm.substr(nm.rfind('.') + 1), shape, EncoderEntry::VIEW, k});
@@ -385,15 +687,24 @@ std::vector<pnvo_tensor_desc> pnvo::encoder_toc(const std::vector<EncoderEntry> 
   return toc;
 }
 
-// the shared body of pnvo_policy_act (depth given) and pnvo_policy_act_features (vfeat given)
-static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *depth, const float *vfeat, const float *goal,
+// a handle with rgb / normalisation reached through an entry point that takes depth alone
+static int refuse_plain_entry(const Policy &p, const char *fn) {
+  if (policy_is_plain(p.cfg)) return PNVO_OK;
+  return pfail(PNVO_ERR_STATE, std::string(fn) + ": this policy takes rgb and / or RunningMeanAndVar statistics (rgb_channels, no_depth, normalize): "
+                                   "call " + fn + "_rgbd");
+}
+
+// the shared body of pnvo_policy_act (depth given), pnvo_policy_act_rgbd (obs given) and pnvo_policy_act_features (vfeat given)
+static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *depth, const PolicyObs *obs, const float *vfeat, const float *goal,
                            const int64_t *prev_actions, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features,
                            float *logits, float *value, void *stream) {
   if (!h) return pfail(PNVO_ERR_ARG, "null handle");
   Policy &p = h->p;
   if (!p.loaded) return pfail(PNVO_ERR_STATE, std::string(fn) + " before pnvo_policy_load_weights");
-  if (B <= 0 || (!depth && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !hidden_out)
+  if (B <= 0 || (!depth && !obs && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !hidden_out)
     return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  int rc = PNVO_OK;
+  if (obs && (rc = policy_obs_check(p, *obs, fn)) != PNVO_OK) return rc;
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, K0 = Hd + 64;
   const bool gru = is_gru(c);
@@ -409,10 +720,10 @@ static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *de
     PCHK(p.x.alloc((size_t)B * K0));
     p.cap = B;
   }
-  int rc = PNVO_OK;
-  if (depth) {
+  if (depth || obs) {
     if ((rc = ensure_pooled(p, B)) != PNVO_OK) return rc;
-    if ((rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK) return rc;
+    if ((rc = obs ? policy_input_stage(p, *obs, B, p.pooled, s) : pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK)
+      return rc;
     rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
     if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   } else if ((rc = launch_visual_fc(p, vfeat, B, p.visual, s)) != PNVO_OK) {
@@ -483,6 +794,11 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
     return pfail(PNVO_ERR_ARG, "unsupported policy action_space.n " + std::to_string(cfg->n_actions) + " (1 to 32)");
   if (cfg->rnn_type != PNVO_RNN_LSTM && cfg->rnn_type != PNVO_RNN_GRU)
     return pfail(PNVO_ERR_ARG, "unsupported policy rnn_type " + std::to_string(cfg->rnn_type) + " (0 = LSTM, 1 = GRU)");
+  // (read behind rnn_type: callers built against the eight-field struct are served or refused by the checks above)
+  if ((cfg->rgb_channels != 0 && cfg->rgb_channels != 3) || (cfg->no_depth != 0 && cfg->no_depth != 1) ||
+      (cfg->normalize != 0 && cfg->normalize != 1) || (cfg->no_depth && cfg->rgb_channels == 0))
+    return pfail(PNVO_ERR_ARG, "unsupported policy visual input: rgb_channels " + std::to_string(cfg->rgb_channels) + " (0 or 3), no_depth " +
+                                   std::to_string(cfg->no_depth) + " (0, or 1 with rgb), normalize " + std::to_string(cfg->normalize) + " (0 or 1)");
   pnvo_policy_s *h = new pnvo_policy_s();
   h->p.cfg = *cfg;
   h->p.device = device;
@@ -490,18 +806,31 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
   std::memset(&ec, 0, sizeof(ec));
   ec.width = cfg->width / 2;             // after F.avg_pool2d(x, 2)  (resnet_policy.py:168)
   ec.height = cfg->height / 2;
-  ec.n_depth = 2;                        // [pooled depth | 0]
+  ec.n_depth = 2 * policy_channels(*cfg);   // [pooled depth | 0], or [rgb / 255, depth | zeros] / [rgb / 255 | zeros] (policy_input_kernel)
   ec.baseplanes = cfg->baseplanes;
   ec.hidden = cfg->hidden;
   ec.out_dim = 1;                        // unused head (the policy stops at the hidden vector)
-  ec.normalize = 0;
+  ec.normalize = cfg->normalize;         // the whitening rides on the stem's scale / shift pair (policy_whiten_kernel)
   ec.n_acts = 4;
   ec.flat_size = cfg->flat_size;
   ec.max_batch = 16;
-  const int rc = pnvo_create(&ec, device, &h->p.enc);
+  int rc = pnvo_create(&ec, device, &h->p.enc);
   if (rc != PNVO_OK) {
     delete h;
     return rc;
+  }
+  if (!policy_is_plain(*cfg)) {
+    // Pooled rgb is no integer 0..255 and the statistics move on the device: these handles run the float32 stem, which takes any
+    // float input and reads its whitening pair from a device table, at every batch size on the per-layer kernels; the stem's weight
+    // gradient stays on the float32 kernel that reads the same table.
+    const char *opts[3][2] = {{"stem", "dense"}, {"small_net", "off"}, {"wgrad_stem", "fp32"}};
+    for (auto &o : opts)
+      if ((rc = pnvo_set_option(h->p.enc, o[0], o[1])) != PNVO_OK) {
+        rc = pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(h->p.enc));
+        pnvo_destroy(h->p.enc);
+        delete h;
+        return rc;
+      }
   }
   for (auto *v : {&h->p.w_ih, &h->p.w_hh, &h->p.b_ih, &h->p.b_hh}) v->assign(cfg->rnn_layers, nullptr);   // policy_params()'s slots
   *out = h;
@@ -530,9 +859,21 @@ int pnvo_policy_load_weights(pnvo_policy_handle h, const float *blob, size_t n_f
         eblob.insert(eblob.end(), blob + toc[e.k].offset, blob + toc[e.k].offset + cnt);
       } else {
         eblob.insert(eblob.end(), cnt, 0.f);
-        if (e.src == EncoderEntry::STEM)                 // [C0,1,7,7] -> channel 0 of [C0,2,7,7]
+        if (e.src == EncoderEntry::STEM) {               // [C0,C,7,7] -> channels 0 .. C-1 of [C0,2C,7,7]
+          const size_t row = (size_t)policy_channels(p.cfg) * 49;
           for (int64_t o = 0; o < e.shape[0]; ++o)
-            std::memcpy(&eblob[offs.back() + (size_t)o * 98], blob + toc[e.k].offset + o * 49, sizeof(float) * 49);
+            std::memcpy(&eblob[offs.back() + (size_t)o * 2 * row], blob + toc[e.k].offset + o * row, sizeof(float) * row);
+        }
+      }
+    }
+    if (p.cfg.normalize) {
+      // the handle wants its statistics at load: mean 0 / variance 1 over its 2C channels, stand-ins until the first call's
+      // policy_whiten_kernel writes the whitening pair from the module's buffers
+      const int64_t C2 = 2 * policy_channels(p.cfg);
+      for (int k = 0; k < 2; ++k) {
+        ent.push_back({std::string("visual_encoder.running_mean_and_var.") + (k ? "_var" : "_mean"), {1, C2, 1, 1}, EncoderEntry::ZEROS, -1});
+        offs.push_back(eblob.size());
+        eblob.insert(eblob.end(), (size_t)C2, k ? 1.f : 0.f);
       }
     }
     const std::vector<pnvo_tensor_desc> etoc = encoder_toc(ent, offs);
@@ -557,7 +898,8 @@ int pnvo_policy_act(pnvo_policy_handle h, const float *depth, const float *goal,
                     const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                     float *value, void *stream) {
   if (!depth) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
-  return policy_act_impl(h, "pnvo_policy_act", depth, nullptr, goal, prev_actions, masks, hidden_in, B, hidden_out, features, logits, value,
+  if (h && refuse_plain_entry(h->p, "pnvo_policy_act") != PNVO_OK) return PNVO_ERR_STATE;
+  return policy_act_impl(h, "pnvo_policy_act", depth, nullptr, nullptr, goal, prev_actions, masks, hidden_in, B, hidden_out, features, logits, value,
                          stream);
 }
 
@@ -565,7 +907,7 @@ int pnvo_policy_act_features(pnvo_policy_handle h, const float *visual_features,
                              const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                              float *value, void *stream) {
   if (!visual_features) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
-  return policy_act_impl(h, "pnvo_policy_act_features", nullptr, visual_features, goal, prev_actions, masks, hidden_in, B, hidden_out,
+  return policy_act_impl(h, "pnvo_policy_act_features", nullptr, nullptr, visual_features, goal, prev_actions, masks, hidden_in, B, hidden_out,
                          features, logits, value, stream);
 }
 
@@ -575,16 +917,20 @@ int pnvo_policy_features_shape(pnvo_policy_handle h, int64_t shape[3]) {
   return PNVO_OK;
 }
 
-int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *features_out, void *stream) {
+static int policy_encode_impl(pnvo_policy_handle h, const char *fn, const float *depth, const PolicyObs *obs, int B, float *features_out,
+                              void *stream) {
   if (!h) return pfail(PNVO_ERR_ARG, "null handle");
   Policy &p = h->p;
-  if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_policy_encode before pnvo_policy_load_weights");
-  if (B <= 0 || !depth || !features_out) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  if (!p.loaded) return pfail(PNVO_ERR_STATE, std::string(fn) + " before pnvo_policy_load_weights");
+  if (B <= 0 || (!depth && !obs) || !features_out) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  int rc = PNVO_OK;
+  if (obs && (rc = policy_obs_check(p, *obs, fn)) != PNVO_OK) return rc;
   const pnvo_policy_config &c = p.cfg;
   PCHK(hipSetDevice(p.device));
-  int rc = ensure_pooled(p, B);
-  if (rc != PNVO_OK) return rc;
-  if ((rc = pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK) return rc;
+  if ((rc = ensure_pooled(p, B)) != PNVO_OK) return rc;
+  if ((rc = obs ? policy_input_stage(p, *obs, B, p.pooled, (hipStream_t)stream) : pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) !=
+      PNVO_OK)
+    return rc;
   rc = pnvo_forward_compression(p.enc, p.pooled, B, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   const pnvo_handle m = p.enc;
@@ -593,6 +939,67 @@ int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *f
   hipLaunchKernelGGL(feature_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m->comp_raw, m->ssC[0],
                      m->ssC[1], B, P, m->comp_c, m->comp_cp, features_out);
   PCHK(hipGetLastError());
+  return PNVO_OK;
+}
+
+int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *features_out, void *stream) {
+  if (h && refuse_plain_entry(h->p, "pnvo_policy_encode") != PNVO_OK) return PNVO_ERR_STATE;
+  if (!depth) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
+  return policy_encode_impl(h, "pnvo_policy_encode", depth, nullptr, B, features_out, stream);
+}
+
+// rgb, the statistics and `training` of a *_rgbd call on a depth-only, un-normalised handle: nothing to take
+static bool plain_rgbd_call(const void *rgb, const float *mean, const float *var, const float *count, int training) {
+  return rgb == nullptr && mean == nullptr && var == nullptr && count == nullptr && training == 0;
+}
+
+int pnvo_policy_act_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                         float *run_count, int training, const float *goal, const int64_t *prev_actions, const float *masks,
+                         const float *hidden_in, int B, float *hidden_out, float *features, float *logits, float *value, void *stream) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  if (policy_is_plain(h->p.cfg) && plain_rgbd_call(rgb, run_mean, run_var, run_count, training))
+    return pnvo_policy_act(h, depth, goal, prev_actions, masks, hidden_in, B, hidden_out, features, logits, value, stream);
+  PolicyObs o;
+  o.rgb = rgb, o.rgb_is_u8 = rgb_is_u8, o.depth = depth, o.mean = run_mean, o.var = run_var, o.count = run_count, o.training = training;
+  return policy_act_impl(h, "pnvo_policy_act_rgbd", nullptr, &o, nullptr, goal, prev_actions, masks, hidden_in, B, hidden_out, features, logits,
+                         value, stream);
+}
+
+int pnvo_policy_encode_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                            float *run_count, int training, int B, float *features_out, void *stream) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  if (policy_is_plain(h->p.cfg) && plain_rgbd_call(rgb, run_mean, run_var, run_count, training))
+    return pnvo_policy_encode(h, depth, B, features_out, stream);
+  PolicyObs o;
+  o.rgb = rgb, o.rgb_is_u8 = rgb_is_u8, o.depth = depth, o.mean = run_mean, o.var = run_var, o.count = run_count, o.training = training;
+  return policy_encode_impl(h, "pnvo_policy_encode_rgbd", nullptr, &o, B, features_out, stream);
+}
+
+int pnvo_policy_input_stage(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, const float *center, int mode, int B,
+                            float *pooled_out, double *m12_out, void *stream) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  Policy &p = h->p;
+  const pnvo_policy_config &c = p.cfg;
+  if (policy_is_plain(c)) return pfail(PNVO_ERR_STATE, "pnvo_policy_input_stage: the depth-only, un-normalised policy pools with pnvo_avgpool2");
+  if (B <= 0 || mode < 0 || mode > 2 || !pooled_out || (mode && !m12_out) || ((uintptr_t)pooled_out & 15) || ((uintptr_t)m12_out & 7))
+    return pfail(PNVO_ERR_ARG, "null argument / bad batch / bad mode / pooled_out not 16-byte aligned");
+  PolicyObs o;
+  o.rgb = rgb, o.rgb_is_u8 = rgb_is_u8, o.depth = depth;
+  if ((c.rgb_channels > 0) != (rgb != nullptr) || (c.no_depth == 0) != (depth != nullptr) || (rgb && !rgb_is_u8 && ((uintptr_t)rgb & 3)) ||
+      ((uintptr_t)depth & 3))
+    return pfail(PNVO_ERR_ARG, "pnvo_policy_input_stage: frames do not match the policy's visual types");
+  PCHK(hipSetDevice(p.device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = PNVO_OK;
+  if (mode && (rc = ensure_moments(p)) != PNVO_OK) return rc;
+  const int C = policy_channels(c), nb = input_blocks(c, B);
+  const long npix = (long)B * (c.height / 2) * (c.width / 2);
+  PCHK(launch_policy_input(c, rgb, rgb_is_u8, depth, B, center, mode == 1, pooled_out, p.in_part, s));
+  if (mode == 2) PCHK(launch_pooled_moments(C, pooled_out, npix, center, p.in_part, nb, s));
+  if (mode) {
+    hipLaunchKernelGGL(input_moments_final_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, s, p.in_part, nb, (double)npix, m12_out);
+    PCHK(hipGetLastError());
+  }
   return PNVO_OK;
 }
 

@@ -31,7 +31,34 @@ struct Policy {
   // workspace
   int cap = 0, cap_pooled = 0;       // rows `visual` and `x` hold / frames `pooled` holds (only the entry points that take depth grow it)
   DevBuf<float> pooled, visual, x;
+  // the input stage of the rgb / rgb-d / normalised handles (policy_input_stage): per-workgroup partial sums of the moments, the
+  // moments [2C] (float64), and the statistics padded to the encoder handle's 2C channels (mean 0, variance 1 on the zero channels)
+  DevBuf<double> in_part, m12;
+  DevBuf<float> mean_pad, var_pad;
 };
+
+// ---- the visual input (pnvo_policy_config.rgb_channels / no_depth / normalize).  C channels in the reference's torch.cat order (rgb,
+// then depth); the encoder handle takes ONE float modality of 2C channels: the C real ones, then C zero channels with zero weights.
+inline int policy_channels(const pnvo_policy_config &c) { return c.rgb_channels + (c.no_depth ? 0 : 1); }
+// today's depth-only, un-normalised policy: the 16-bit-matrix-core stem, the persistent small-batch encoder, the depth-only entry points
+inline bool policy_is_plain(const pnvo_policy_config &c) { return c.rgb_channels == 0 && c.no_depth == 0 && c.normalize == 0; }
+inline size_t policy_pooled_floats(const pnvo_policy_config &c, int frames) {
+  return (size_t)frames * (c.height / 2) * (c.width / 2) * 2 * policy_channels(c);
+}
+// One call's visual observations and the module's RunningMeanAndVar buffers (borrowed), as the *_rgbd entry points take them
+struct PolicyObs {
+  const void *rgb = nullptr;         // [B,H,W,3] uint8 or float32, values 0..255
+  int rgb_is_u8 = 0;
+  const float *depth = nullptr;      // [B,H,W,1]
+  float *mean = nullptr, *var = nullptr, *count = nullptr;
+  int training = 0;
+};
+// pnvo_policy.hip.  policy_obs_check: the pointers fit the handle's configuration (else PNVO_ERR_ARG, nothing launched).
+// policy_input_stage: frames -> pooled [B,H/2,W/2,2C] (rgb / 255, avg_pool2d(2), zero channels); with normalize and o.training the
+// batch is merged into the buffers; with normalize the padded statistics (Policy::mean_pad / var_pad) and the encoder stem's scale /
+// shift pair are rewritten from the buffers.  All on `s`, no host synchronisation.
+int policy_obs_check(const Policy &p, const PolicyObs &o, const char *fn);
+int policy_input_stage(Policy &p, const PolicyObs &o, int B, float *pooled, hipStream_t s);
 
 // ---- the policy-owned tensors (everything but the visual encoder, which lives in the encoder handle; visual_fc is held twice, here in
 // torch's layout for the visual_features path and there channel-padded for the depth path), in state_dict order
@@ -89,7 +116,7 @@ inline size_t numel(const std::vector<int64_t> &shape) {
 // ---- the encoder handle's table, from the caller's: the VO model's names (net.visual_encoder.* -> visual_encoder.*, net.visual_fc.1.*
 // -> visual_fc.2.*), the stem widened to the handle's two input channels [C0,2,7,7], and the handle's unused output head
 struct EncoderEntry {
-  enum Source { VIEW, STEM, ZEROS };  // entry k of the caller's table as it is / that entry zero-padded to 2 input channels / all zeros
+  enum Source { VIEW, STEM, ZEROS };  // entry k of the caller's table as it is / that entry [C0,C,7,7] zero-padded to 2C input channels / all zeros
   std::string name;
   std::vector<int64_t> shape;
   Source src;

@@ -1,7 +1,9 @@
 // policy_train.hip — one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions,
 // rl/policies/policy.py:52-63), gfx950 only, float32.
 //
-//   evaluate : depth [T*N] -> avg_pool2d(2) -> the visual encoder's TRAIN-mode forward (pnvo_train_forward: activations kept)
+//   evaluate : depth [T*N] -> avg_pool2d(2) (or, pnvo_policy_evaluate_rgbd: rgb / depth frames -> the input stage of pnvo_policy.hip, which
+//              in training mode merges the T*N rows into RunningMeanAndVar's buffers first) -> the visual encoder's TRAIN-mode forward
+//              (pnvo_train_forward: activations kept)
 //              -> x = [visual | tgt_embeding | prev_action_embedding]                       policy_inputs_kernel, M = T*N rows
 //              -> per LSTM layer: G_x = X . W_ih^T + b_ih + b_hh over all M rows            gemm_f32_kernel (v_mfma_f32_32x32x2_f32)
 //                                 T launches of lstm_step_kernel (the only sequential part)  gates, c, h, masked h_prev kept
@@ -41,9 +43,9 @@ namespace pnvo {
 struct PolicyTrain {
   float *params = nullptr, *grads = nullptr;   // the caller's flat buffers (not owned)
   size_t n = 0, n_named = 0;          // floats handed over / floats covered by the parameter table (the rest is the tail below)
-  size_t o_stem = 0;                  // the policy's stem weight [C0,1,7,7] (the one tensor read here that is not a Policy slot)
-  size_t o_stem2 = 0;                 // tail: the stem weight zero-padded to the encoder handle's 2 input channels [C0,2,7,7],
-  int c0 = 0;                         //       then the handle's unused output head (hidden weights + 1 bias, zeros)
+  size_t o_stem = 0;                  // the policy's stem weight [C0,C,7,7] (the one tensor read here that is not a Policy slot)
+  size_t o_stem2 = 0;                 // tail: the stem weight zero-padded to the encoder handle's 2C input channels [C0,2C,7,7],
+  int c0 = 0, stem_row = 49;          //       then the handle's unused output head (hidden weights + 1 bias, zeros); stem_row = C * 49
   // the last evaluate
   int T = 0, N = 0, M = 0;
   bool have_loss = false;
@@ -576,16 +578,17 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(const float *y, long n, 
 }
 
 // the policy's stem weight [C0,1,7,7] <-> channel 0 of the encoder handle's [C0,2,7,7] (channel 1 stays 0)
-__global__ __launch_bounds__(256) void stem_pad_kernel(const float *w1, int c0, float *w2) {
+// row = C * 49 floats of one output channel of the policy's stem weight [C0,C,7,7]; the handle's [C0,2C,7,7] has rows of 2 * row
+__global__ __launch_bounds__(256) void stem_pad_kernel(const float *w1, int c0, int row, float *w2) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= c0 * 98) return;
-  const int o = e / 98, r = e % 98;
-  w2[e] = r < 49 ? w1[o * 49 + r] : 0.f;
+  if (e >= c0 * 2 * row) return;
+  const int o = e / (2 * row), r = e % (2 * row);
+  w2[e] = r < row ? w1[o * row + r] : 0.f;
 }
-__global__ __launch_bounds__(256) void stem_unpad_kernel(const float *w2, int c0, float *w1) {
+__global__ __launch_bounds__(256) void stem_unpad_kernel(const float *w2, int c0, int row, float *w1) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= c0 * 49) return;
-  w1[e] = w2[(e / 49) * 98 + (e % 49)];
+  if (e >= c0 * row) return;
+  w1[e] = w2[(e / row) * 2 * row + (e % row)];
 }
 
 // clip_grad_norm_: partial sums of squares over fixed slices, then every workgroup folds the partials in the same order and scales
@@ -674,7 +677,7 @@ int ensure_pooled(Policy &p, PolicyTrain *t, int M) {
   if (M <= t->cap_pooled) return PNVO_OK;
   t->pooled.reset();
   t->cap_pooled = 0;
-  PCHK(t->pooled.alloc((size_t)M * (p.cfg.height / 2) * (p.cfg.width / 2) * 2));
+  PCHK(t->pooled.alloc(policy_pooled_floats(p.cfg, M)));
   t->cap_pooled = M;
   return PNVO_OK;
 }
@@ -693,7 +696,7 @@ int ensure_feat(Policy &p, PolicyTrain *t, int M) {
 // the unused head in the tail
 int attach_encoder(Policy &p, PolicyTrain *t, const std::vector<EncoderEntry> &ent, const pnvo_tensor_desc *toc) {
   std::vector<size_t> offs;
-  size_t o_head = t->o_stem2 + (size_t)t->c0 * 98;
+  size_t o_head = t->o_stem2 + (size_t)t->c0 * 2 * t->stem_row;
   for (const EncoderEntry &e : ent) {
     offs.push_back(e.src == EncoderEntry::VIEW ? (size_t)toc[e.k].offset : e.src == EncoderEntry::STEM ? t->o_stem2 : o_head);
     if (e.src == EncoderEntry::ZEROS) o_head += numel(e.shape);
@@ -704,7 +707,7 @@ int attach_encoder(Policy &p, PolicyTrain *t, const std::vector<EncoderEntry> &e
   return PNVO_OK;
 }
 
-size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 98 + (size_t)c.hidden + 1; }
+size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 98 * policy_channels(c) + (size_t)c.hidden + 1; }
 
 }  // namespace
 
@@ -726,9 +729,9 @@ void pnvo_policy_train_free(Policy &p) {
 
 using namespace pnvo;
 
-static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const float *vfeat, const float *goal, const int64_t *prev_actions,
-                                const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
-                                float *value, float *logp, float *entropy, void *stream);
+static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const PolicyObs *obs, const float *vfeat, const float *goal,
+                                const int64_t *prev_actions, const float *masks, const float *hidden_in, int T, int N, const int64_t *actions,
+                                float *hidden_out, float *value, float *logp, float *entropy, void *stream);
 
 extern "C" {
 
@@ -773,14 +776,15 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
   t->n = n_floats;
   t->n_named = n_named;
   t->c0 = c.baseplanes;
+  t->stem_row = 49 * policy_channels(c);
   t->o_stem = o_stem;
   t->o_stem2 = n_named;
   rc = [&]() -> int {
     // tail: zero-padded stem + zero output head, gradients zero
     PCHK(hipMemset(params + n_named, 0, tail_floats(c) * sizeof(float)));
     PCHK(hipMemset(grads + n_named, 0, tail_floats(c) * sizeof(float)));
-    hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem, t->c0,
-                       params + t->o_stem2);
+    hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 2 * t->stem_row + 255) / 256)), dim3(256), 0, nullptr, params + t->o_stem,
+                       t->c0, t->stem_row, params + t->o_stem2);
     PCHK(hipGetLastError());
     PCHK(t->whhT.alloc((size_t)4 * Hd * Hd));
     PCHK(t->sq_part.alloc(SQ_BLOCKS));
@@ -803,8 +807,8 @@ int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream) {
   Policy &p = h->p;
   PolicyTrain *t = p.train;
   PCHK(hipSetDevice(p.device));
-  hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 98 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t->params + t->o_stem,
-                     t->c0, t->params + t->o_stem2);
+  hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 2 * t->stem_row + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     t->params + t->o_stem, t->c0, t->stem_row, t->params + t->o_stem2);
   PCHK(hipGetLastError());
   const int rc = pnvo_train_refresh(p.enc, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
@@ -816,29 +820,47 @@ int pnvo_policy_evaluate(pnvo_policy_handle h, const float *depth, const float *
                          float *value, float *logp, float *entropy, void *stream) {
   (void)train_encoder;                   // the forward is the same either way: visual_fc's gradient needs the saved activations
   if (!depth) return pfail(PNVO_ERR_ARG, "null argument");
-  return policy_evaluate_impl(h, depth, nullptr, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp, entropy, stream);
+  if (h && !policy_is_plain(h->p.cfg))
+    return pfail(PNVO_ERR_STATE, "pnvo_policy_evaluate: this policy takes rgb and / or RunningMeanAndVar statistics: call pnvo_policy_evaluate_rgbd");
+  return policy_evaluate_impl(h, depth, nullptr, nullptr, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp, entropy, stream);
 }
 
 int pnvo_policy_evaluate_features(pnvo_policy_handle h, const float *visual_features, const float *goal, const int64_t *prev_actions,
                                   const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
                                   float *value, float *logp, float *entropy, void *stream) {
   if (!visual_features) return pfail(PNVO_ERR_ARG, "null argument");
-  return policy_evaluate_impl(h, nullptr, visual_features, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp,
+  return policy_evaluate_impl(h, nullptr, nullptr, visual_features, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp,
                               entropy, stream);
+}
+
+int pnvo_policy_evaluate_rgbd(pnvo_policy_handle h, const void *rgb, int rgb_is_u8, const float *depth, float *run_mean, float *run_var,
+                              float *run_count, int training, const float *goal, const int64_t *prev_actions, const float *masks,
+                              const float *hidden_in, int T, int N, const int64_t *actions, int train_encoder, float *hidden_out,
+                              float *value, float *logp, float *entropy, void *stream) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  if (policy_is_plain(h->p.cfg) && !rgb && !run_mean && !run_var && !run_count && !training)
+    return pnvo_policy_evaluate(h, depth, goal, prev_actions, masks, hidden_in, T, N, actions, train_encoder, hidden_out, value, logp, entropy,
+                                stream);
+  PolicyObs o;
+  o.rgb = rgb, o.rgb_is_u8 = rgb_is_u8, o.depth = depth, o.mean = run_mean, o.var = run_var, o.count = run_count, o.training = training;
+  return policy_evaluate_impl(h, nullptr, &o, nullptr, goal, prev_actions, masks, hidden_in, T, N, actions, hidden_out, value, logp, entropy,
+                              stream);
 }
 
 }  // extern "C"
 
-// the shared body of pnvo_policy_evaluate (depth given) and pnvo_policy_evaluate_features (vfeat given)
-static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const float *vfeat, const float *goal, const int64_t *prev_actions,
-                                const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
-                                float *value, float *logp, float *entropy, void *stream) {
+// the shared body of pnvo_policy_evaluate (depth given), pnvo_policy_evaluate_rgbd (obs given) and pnvo_policy_evaluate_features (vfeat given)
+static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const PolicyObs *obs, const float *vfeat, const float *goal,
+                                const int64_t *prev_actions, const float *masks, const float *hidden_in, int T, int N, const int64_t *actions,
+                                float *hidden_out, float *value, float *logp, float *entropy, void *stream) {
   if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
   Policy &p = h->p;
   PolicyTrain *t = p.train;
   if (T <= 0 || N <= 0 || (long)T * N > (1L << 20))
     return pfail(PNVO_ERR_ARG, "bad rollout shape T = " + std::to_string(T) + ", N = " + std::to_string(N));
-  if ((!depth && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !actions || !hidden_out)
+  if (obs)
+    if (int rc0 = policy_obs_check(p, *obs, "pnvo_policy_evaluate_rgbd")) return rc0;
+  if ((!depth && !obs && !vfeat) || !goal || !prev_actions || !masks || !hidden_in || !actions || !hidden_out)
     return pfail(PNVO_ERR_ARG, "null argument");
   const pnvo_policy_config &c = p.cfg;
   const int Hd = c.hidden, L = c.rnn_layers, K0 = Hd + 64, A = c.n_actions, M = T * N;
@@ -850,8 +872,8 @@ static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const 
   hipStream_t s = (hipStream_t)stream;
   int rc = ensure_ws(p, t, M);
   if (rc != PNVO_OK) return rc;
-  if ((rc = depth ? ensure_pooled(p, t, M) : ensure_feat(p, t, M)) != PNVO_OK) return rc;
-  t->from_features = depth == nullptr;
+  if ((rc = (depth || obs) ? ensure_pooled(p, t, M) : ensure_feat(p, t, M)) != PNVO_OK) return rc;
+  t->from_features = vfeat != nullptr;
   t->T = T;
   t->N = N;
   t->M = M;
@@ -861,10 +883,15 @@ static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const 
   PCHK(hipMemcpyAsync(t->actions, actions, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   PCHK(hipMemcpyAsync(t->hid0, hidden_in, rnn_state_floats(c, N) * sizeof(float), hipMemcpyDeviceToDevice, s));
   const float *visual = nullptr;
-  if (depth) {
+  if (depth || obs) {
     PCHK(mark(t, 0, s));
-    if ((rc = pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK) return rc;
-    rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, nullptr, nullptr, t->enc_out, stream);
+    // the M = T * N rows are ONE batch of RunningMeanAndVar (policy.py:52-63 runs the net once over the minibatch); the train-mode
+    // forward takes the statistics over the handle's 2C channels, as the input stage padded them
+    if ((rc = obs ? policy_input_stage(p, *obs, M, t->pooled, s) : pnvo_avgpool2(depth, M, c.height, c.width, t->pooled, stream)) != PNVO_OK)
+      return rc;
+    const bool norm = c.normalize != 0;
+    rc = pnvo_train_forward(p.enc, nullptr, t->pooled, nullptr, nullptr, M, norm ? (const float *)p.mean_pad : nullptr,
+                            norm ? (const float *)p.var_pad : nullptr, t->enc_out, stream);
     if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
     PCHK(mark(t, 1, s));
     visual = pnvo_train_hidden(p.enc);
@@ -1024,7 +1051,8 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
   const int rc = pnvo_train_backward_from_hidden(p.enc, t->dY, train_encoder == 0, stream);
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   if (train_encoder) {
-    hipLaunchKernelGGL(stem_unpad_kernel, dim3((unsigned)((t->c0 * 49 + 255) / 256)), dim3(256), 0, s, G + t->o_stem2, t->c0, G + t->o_stem);
+    hipLaunchKernelGGL(stem_unpad_kernel, dim3((unsigned)((t->c0 * t->stem_row + 255) / 256)), dim3(256), 0, s, G + t->o_stem2, t->c0, t->stem_row,
+                       G + t->o_stem);
     PCHK(hipGetLastError());
   }
   PCHK(mark(t, 7, s));

@@ -1838,7 +1838,10 @@ __global__ __launch_bounds__(64) void moments_final_kernel(const MomentsArgs a, 
 
 // RunningMeanAndVar's train-mode update in one launch (single process; running_mean_and_var.py:41-60): batch mean and the
 // variance about it from the one-pass moments e1 = E[x - c], e2 = E[(x - c)^2] about the old running mean c, then Chan's merge.
-__global__ void rmv_merge_kernel(const float *m12, int C, float nb, float *mean, float *var, float *count) {
+// The moments arrive as float32 (pnvo_input_moments' output) or as float64 (the navigation policy's input stage, whose first batches
+// are centred on a running mean of zero: e2 - e1^2 would lose the variance of a narrow channel to float32's rounding of e2).
+template <typename T>
+__global__ void rmv_merge_kernel(const T *m12, int C, float nb, float *mean, float *var, float *count) {
   const int c = threadIdx.x;
   const float cnt = *count;
   __syncthreads();                                        // (everybody has read the old count)
@@ -1857,7 +1860,11 @@ __global__ void rmv_merge_kernel(const float *m12, int C, float nb, float *mean,
 }
 
 hipError_t launch_rmv_merge(const float *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s) {
-  hipLaunchKernelGGL(rmv_merge_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, (float)B, mean, var, count);
+  hipLaunchKernelGGL(rmv_merge_kernel<float>, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, (float)B, mean, var, count);
+  return hipGetLastError();
+}
+hipError_t launch_rmv_merge(const double *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s) {
+  hipLaunchKernelGGL(rmv_merge_kernel<double>, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, (float)B, mean, var, count);
   return hipGetLastError();
 }
 

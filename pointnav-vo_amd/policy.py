@@ -1,9 +1,10 @@
 """HIP-backed navigation policy registered under the reference's name ``resnet_rnn_policy``.
 
-Drop-in for PointNavResNetPolicy (/root/reference/pointnav_vo/rl/policies/resnet_policy.py:25-58) in the configuration
-the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: depth-only resnet18 encoder, 2-layer LSTM — or GRU, the other
-value RL.Policy.rnn_backbone takes (rnn_state_encoder.py:28) — RL.OBS_TRANSFORM 'none', 'resize' or 'resize_crop',
-normalize_visual_inputs False): same constructor keywords (ddppo_trainer.py:122-133), same
+Drop-in for PointNavResNetPolicy (/root/reference/pointnav_vo/rl/policies/resnet_policy.py:25-58) in the configurations
+the reference's nav loop uses (configs/rl/ddppo_pointnav.yaml:48-54: resnet18 encoder, 2-layer LSTM — or GRU, the other
+value RL.Policy.rnn_backbone takes (rnn_state_encoder.py:28) — RL.OBS_TRANSFORM 'none', 'resize' or 'resize_crop';
+RL.Policy.visual_types 'depth', 'rgb' or both, normalize_visual_inputs False or True with RunningMeanAndVar's three buffers updated on
+the device whenever the policy runs in training mode, single process): same constructor keywords (ddppo_trainer.py:122-133), same
 ``state_dict`` keys/shapes, same ``act`` / ``get_value`` signatures and return values (policy.py:29-50).  The module tree
 only HOLDS parameters; ``act`` is one call into libpnvo.so (pnvo_policy_act) on the caller's current HIP stream plus the
 categorical sampling / arg-max over the 4 logits, which stays in torch as in the reference (policy.py:38-43).
@@ -33,7 +34,8 @@ class _Holder(nn.Module):
 
 
 class pnvo_policy_config(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("width", "height", "baseplanes", "hidden", "n_actions", "rnn_layers", "flat_size", "rnn_type")]
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "baseplanes", "hidden", "n_actions", "rnn_layers", "flat_size", "rnn_type",
+                                         "rgb_channels", "no_depth", "normalize")]
 
 
 # rnn_type -> (pnvo_policy_config.rnn_type, gate blocks per weight, state tensors per layer): torch.nn.LSTM (i, f, g, o; h and c),
@@ -55,16 +57,33 @@ def encoder_output_shape(*, width, height, flat_size=2048):
     return int(round(flat_size / (fh * fw))), fh, fw
 
 
-def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048, rnn_type="LSTM"):
-    """(name, shape) of every tensor of PointNavResNetPolicy.state_dict() for the depth-only resnet18 configuration."""
+RMV_PREFIX = "net.visual_encoder.running_mean_and_var."
+
+
+def visual_channels(vis_types):
+    """(rgb channels, depth channels) the encoder takes for RL.Policy.visual_types: membership, as the reference tests it
+    (resnet_policy.py:82-94); torch.cat order is rgb, then depth (:150-167)."""
+    n_rgb, n_depth = (3 if "rgb" in vis_types else 0), (1 if "depth" in vis_types else 0)
+    if n_rgb + n_depth == 0:
+        raise NotImplementedError(f"vis_types {list(vis_types)!r}: the HIP policy is not blind (it takes 'depth', 'rgb' or both)")
+    return n_rgb, n_depth
+
+
+def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048, rnn_type="LSTM",
+                           vis_types=("depth",), normalize_visual_inputs=False):
+    """(name, shape) of every tensor of PointNavResNetPolicy.state_dict() for the resnet18 configuration, in its order; with
+    normalize_visual_inputs the three RunningMeanAndVar buffers come first among the encoder's entries."""
     gates = _rnn(rnn_type)[1]
+    n_in = sum(visual_channels(vis_types))
     def half(v):
         return (v + 1) // 2
     h, w = height // 2, width // 2                       # F.avg_pool2d(x, 2)
     spec = []
     pre = "net.visual_encoder."
     bb = pre + "backbone."
-    spec += [(bb + "conv1.0.weight", (baseplanes, 1, 7, 7)), (bb + "conv1.1.weight", (baseplanes,)),
+    if normalize_visual_inputs:                          # running_mean_and_var.py:16-18
+        spec += [(RMV_PREFIX + "_mean", (1, n_in, 1, 1)), (RMV_PREFIX + "_var", (1, n_in, 1, 1)), (RMV_PREFIX + "_count", ())]
+    spec += [(bb + "conv1.0.weight", (baseplanes, n_in, 7, 7)), (bb + "conv1.1.weight", (baseplanes,)),
              (bb + "conv1.1.bias", (baseplanes,))]
     h, w = half(half(h)), half(half(w))                  # stem stride 2 + maxpool
     cin = baseplanes
@@ -120,6 +139,22 @@ def _init(name, shape):
     return t
 
 
+class _Frames:
+    """The visual input of one call of an rgb / rgb-d / normalised policy: the transformed frames on the device and the statistics
+    buffers, as the *_rgbd entry points take them.  `shape[0]` is the number of frames."""
+
+    def __init__(self, rgb, depth, stats):
+        self.rgb, self.depth, self.stats = rgb, depth, stats
+        self.shape = (rgb if rgb is not None else depth).shape[:1]
+
+    def args(self):
+        """(rgb, rgb_is_u8, depth, run_mean, run_var, run_count, training) of pnvo_policy_act_rgbd / _encode_rgbd / _evaluate_rgbd."""
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        mean, var, count, training = self.stats if self.stats is not None else (None, None, None, 0)
+        return (p(self.rgb), int(self.rgb is not None and self.rgb.dtype == torch.uint8), p(self.depth), p(mean), p(var), p(count),
+                int(training))
+
+
 class _NetHolder(_Holder):
     """`policy.net` of the reference (PointNavResNetNet, resnet_policy.py:177-282) as far as its callers read it."""
 
@@ -133,7 +168,7 @@ class _NetHolder(_Holder):
 
     @property
     def is_blind(self):
-        return False                                       # a depth encoder is always present here
+        return False                                       # a visual encoder is always present here
 
 
 class _EncoderHolder(_Holder):
@@ -157,8 +192,9 @@ class _EncoderHolder(_Holder):
         return pol
 
     def forward(self, observations):
-        """observations['depth'] [B,Hs,Ws,1] -> [B, C, fh, fw] float32 on the device: RL.OBS_TRANSFORM, avg_pool2d(2), the backbone,
-        compression conv + GroupNorm(1) + ReLU (one call into libpnvo.so: pnvo_policy_encode).  No gradient, no CPU fallback."""
+        """observations['depth'] [B,Hs,Ws,1] and / or ['rgb'] [B,Hs,Ws,3] -> [B, C, fh, fw] float32 on the device: RL.OBS_TRANSFORM,
+        avg_pool2d(2), RunningMeanAndVar (updated first when the policy is in training mode), the backbone, compression conv +
+        GroupNorm(1) + ReLU (one call into libpnvo.so: pnvo_policy_encode / pnvo_policy_encode_rgbd).  No gradient, no CPU fallback."""
         return self._policy()._encode(observations)
 
 
@@ -172,30 +208,40 @@ class PointNavResNetPolicy(nn.Module):
             raise NotImplementedError(f"backbone {backbone!r}: the HIP policy implements the resnet18 encoder of ddppo_pointnav.yaml")
         self._rnn_type = rnn_type
         self._rnn_code, _, self._states = _rnn(rnn_type)
-        if normalize_visual_inputs or list(vis_types) != ["depth"]:
-            raise NotImplementedError("the HIP policy implements the depth-only, un-normalised encoder "
-                                      "(RL.Policy.visual_types = ['depth'])")
+        self._n_rgb, self._n_depth = visual_channels(vis_types)
+        self._normalize = bool(normalize_visual_inputs)
+        # today's depth-only, un-normalised policy keeps its own path (pnvo_policy_act: the persistent small-batch encoder, the VO
+        # frame-ring hand-off); every other configuration runs the *_rgbd entry points on the per-layer kernels
+        self._plain = self._n_rgb == 0 and not self._normalize
+        self._vis_keys = [k for k, n in (("rgb", self._n_rgb), ("depth", self._n_depth)) if n]
+        for k in self._vis_keys:
+            if k not in observation_space.spaces:
+                raise ValueError(f"vis_types names {k!r}, which the observation space does not hold")
         if goal_sensor_uuid != GOAL_SENSOR:
             raise NotImplementedError(goal_sensor_uuid)
         # RL.OBS_TRANSFORM (ddppo_trainer.py:92-103,131): this package's ResizeCenterCropper / Resizer or the reference's own instances
         self._obs_transform = as_transform(obs_transform)
         if self._obs_transform is not None:
             if self._obs_transform.channels_last:
-                raise NotImplementedError("the policy hands the transform NCHW depth (resnet_policy.py:157-168): channels_last=False")
+                raise NotImplementedError("the policy hands the transform NCHW frames (resnet_policy.py:150-167): channels_last=False")
             # the encoder runs on the transformed [VIS_H, VIS_W] frame; transform_observation_space writes (W, H, 1) into the depth
             # space (resnet_policy.py:75-80), which the reference's sizes only use through the product W * H
             self._obs_transform.transform_observation_space(observation_space)
             self._W, self._H = (int(v) for v in self._obs_transform._size)
         else:
-            shp = observation_space.spaces["depth"].shape     # (H, W, 1)
-            self._H, self._W = int(shp[0]), int(shp[1])
-            assert int(shp[2]) == 1
+            shapes = {k: tuple(int(v) for v in observation_space.spaces[k].shape) for k in self._vis_keys}     # (H, W, 3) / (H, W, 1)
+            self._H, self._W = shapes[self._vis_keys[-1]][:2]
+            for k, n in (("rgb", self._n_rgb), ("depth", self._n_depth)):
+                if n and shapes[k] != (self._H, self._W, n):
+                    raise ValueError(f"observation space {k!r} has shape {shapes[k]}, expected {(self._H, self._W, n)}: the visual "
+                                     "types are concatenated on the channel axis (resnet_policy.py:167)")
         self._tgeom = {}
         self.dim_actions = int(action_space.n)
         self._hidden, self._layers, self._baseplanes = int(hidden_size), int(num_recurrent_layers), int(resnet_baseplanes)
         self._spec = policy_state_dict_spec(width=self._W, height=self._H, baseplanes=self._baseplanes,
                                             hidden=self._hidden, n_actions=self.dim_actions, rnn_layers=self._layers,
-                                            rnn_type=rnn_type)
+                                            rnn_type=rnn_type, vis_types=tuple(vis_types),
+                                            normalize_visual_inputs=self._normalize)
         for name, shape in self._spec:
             parts = name.split(".")
             mod = self
@@ -203,7 +249,11 @@ class PointNavResNetPolicy(nn.Module):
                 if not hasattr(mod, p):
                     mod.add_module(p, _Holder())
                 mod = getattr(mod, p)
-            mod.register_parameter(parts[-1], nn.Parameter(_init(name, tuple(shape))))
+            if name.startswith(RMV_PREFIX):                     # RunningMeanAndVar's statistics: buffers, zero (running_mean_and_var.py:16-18)
+                mod.register_buffer(parts[-1], torch.zeros(tuple(shape)))
+            else:
+                mod.register_parameter(parts[-1], nn.Parameter(_init(name, tuple(shape))))
+        self._param_spec = [(n, sh) for n, sh in self._spec if not n.startswith(RMV_PREFIX)]
         # the reference trainers read these through policy.net (ppo_trainer.py:618, ddppo_trainer.py:279)
         net = self.net
         net.__class__ = _NetHolder
@@ -238,14 +288,15 @@ class PointNavResNetPolicy(nn.Module):
             self._release()
             cc = pnvo_policy_config(width=self._W, height=self._H, baseplanes=self._baseplanes, hidden=self._hidden,
                                     n_actions=self.dim_actions, rnn_layers=self._layers, flat_size=2048,
-                                    rnn_type=self._rnn_code)
+                                    rnn_type=self._rnn_code, rgb_channels=self._n_rgb, no_depth=int(self._n_depth == 0),
+                                    normalize=int(self._normalize))
             h = C.c_void_p()
             _lib.check(_lib.lib.pnvo_policy_create(C.byref(cc), int(device.index or 0), C.byref(h)))
             self._handle, self._handle_dev, self._loaded_sig = h, device.index, None
         tensors = getattr(self, "_spec_tensors", None)      # (the walk over the module tree costs ~50 us per step: kept until _apply)
         if tensors is None:
             sd = dict(self.named_parameters())
-            tensors = self._spec_tensors = [(n, sd[n]) for n, _ in self._spec]
+            tensors = self._spec_tensors = [(n, sd[n]) for n, _ in self._param_spec]
         sig = tuple([(t.data_ptr(), t._version) for _, t in tensors])
         if sig != self._loaded_sig:
             blob, toc = _lib.pack_tensors(tensors)
@@ -290,29 +341,84 @@ class PointNavResNetPolicy(nn.Module):
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            fn = _lib.lib.pnvo_policy_act_features if from_features else _lib.lib.pnvo_policy_act
-            _lib.check(fn(self._handle, p(vis), p(goal), p(pa), p(mk), p(hin), int(B), p(hout), p(feats), p(logits), p(value), stream))
+            if isinstance(vis, _Frames):
+                _lib.check(_lib.lib.pnvo_policy_act_rgbd(self._handle, *vis.args(), p(goal), p(pa), p(mk), p(hin), int(B), p(hout), p(feats),
+                                                         p(logits), p(value), stream))
+            else:
+                fn = _lib.lib.pnvo_policy_act_features if from_features else _lib.lib.pnvo_policy_act
+                _lib.check(fn(self._handle, p(vis), p(goal), p(pa), p(mk), p(hin), int(B), p(hout), p(feats), p(logits), p(value), stream))
         return feats, hout, logits, value
 
     def _visual_input(self, observations, dev):
-        """-> (tensor, from_features): observations['visual_features'] [B,C,fh,fw] when the key is present (resnet_policy.py:249-252: the
-        encoder does not run and 'depth' need not be there), else the transformed observations['depth'] [B,H,W,1].  Every check is made
-        here, before anything is launched."""
+        """-> (input, from_features): observations['visual_features'] [B,C,fh,fw] when the key is present (resnet_policy.py:249-252: the
+        encoder does not run, the frames need not be there and the statistics are not touched), else the transformed
+        observations['depth'] [B,H,W,1] of the depth-only, un-normalised policy, else the _Frames of the other configurations.  Every
+        check is made here, before anything is launched."""
         if FEATURES_KEY in observations:
             feats = observations[FEATURES_KEY].to(device=dev, dtype=torch.float32).contiguous()
             if feats.dim() < 1 or tuple(feats.shape[1:]) != tuple(self._feat_shape):
                 raise ValueError(f"observations['{FEATURES_KEY}'] has shape {tuple(feats.shape)}, expected "
                                  f"{('B',) + tuple(self._feat_shape)} (net.visual_encoder.output_shape)")
             return feats, True
-        if "depth" not in observations:
-            raise ValueError(f"observations hold neither '{FEATURES_KEY}' nor 'depth' (keys: {sorted(observations.keys())}): the policy "
-                             "needs one of them")
-        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
-        if self._obs_transform is not None:
-            depth = self._transform_depth(depth, dev)
-        if tuple(depth.shape[1:]) != (self._H, self._W, 1):
-            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
-        return depth, False
+        return self._frames(observations, dev, f"observations hold neither '{FEATURES_KEY}' nor {{}} (keys: {{}}): the policy needs one "
+                                               "of them"), False
+
+    def _frames(self, observations, dev, missing):
+        """The encoder's input from the sensor entries, checked (keys, dtype, shape, the statistics' process model) and transformed."""
+        for k in self._vis_keys:
+            if k not in observations:
+                raise ValueError(missing.format(repr(k), sorted(observations.keys())))
+        rgb = depth = None
+        if self._n_rgb:
+            rgb = observations["rgb"]
+            # uint8 as the simulator hands it, float32 in 0..255 as batch_obs and RolloutStorage do: the same bits either way
+            if rgb.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"observations['rgb'] has dtype {rgb.dtype}, expected torch.uint8 or torch.float32 (values 0..255)")
+            if rgb.dim() != 4 or rgb.shape[3] != 3:
+                raise ValueError(f"observations['rgb'] has shape {tuple(rgb.shape)}, expected [B,H,W,3]")
+            if self._obs_transform is None and tuple(rgb.shape[1:]) != (self._H, self._W, 3):
+                raise ValueError(f"observations['rgb'] has shape {tuple(rgb.shape)}, expected [B,{self._H},{self._W},3]")
+        if self._n_depth:
+            depth = observations["depth"]
+            if depth.dim() != 4 or depth.shape[3] != 1:
+                raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,H,W,1]")
+            if self._obs_transform is None and tuple(depth.shape[1:]) != (self._H, self._W, 1):
+                raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
+            if rgb is not None and depth.shape[0] != rgb.shape[0]:
+                raise ValueError(f"observations['rgb'] holds {rgb.shape[0]} frames, observations['depth'] {depth.shape[0]}")
+        stats = self._statistics(dev) if not self._plain else None
+        if self._obs_transform is not None:                     # (the geometry is checked before the first launch)
+            for t in (rgb, depth):
+                if t is not None:
+                    self._transform_geometry(t.shape[1], t.shape[2])
+        if depth is not None:
+            depth = depth.to(device=dev, dtype=torch.float32).contiguous()
+            if self._obs_transform is not None:
+                depth = self._transform(depth, dev)
+        if self._plain:
+            return depth
+        if rgb is not None:
+            rgb = rgb.to(device=dev).contiguous()
+            if self._obs_transform is not None:
+                rgb = self._transform(rgb, dev)
+        return _Frames(rgb, depth, stats)
+
+    def _statistics(self, dev):
+        """(_mean, _var, _count, training) of net.visual_encoder.running_mean_and_var as the library borrows them, or None without
+        normalisation.  In training mode the reference all-reduces the batch moments over the processes (running_mean_and_var.py:
+        27-38); that reduction is not built, so a process group and training mode together are refused."""
+        if not self._normalize:
+            return None
+        if self.training and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("normalize_visual_inputs in training mode under torch.distributed: the cross-process reduction "
+                                      "(all_reduce) of RunningMeanAndVar's batch moments is not built; run one process, or call "
+                                      ".eval() on the policy")
+        rmv = self.net.visual_encoder.running_mean_and_var
+        bufs = (rmv._mean, rmv._var, rmv._count)
+        for name, b in zip(("_mean", "_var", "_count"), bufs):
+            if b.device != dev or b.dtype != torch.float32 or not b.is_contiguous():
+                raise RuntimeError(f"{RMV_PREFIX}{name} must be a contiguous float32 buffer on {dev} (it is {b.dtype} on {b.device})")
+        return bufs + (int(self.training),)
 
     def _encode(self, observations):
         ref = next(self.parameters())
@@ -320,38 +426,41 @@ class PointNavResNetPolicy(nn.Module):
             raise RuntimeError("pointnav_vo_amd policies run on an MI355X only: move the policy with .to('cuda') "
                                "(there is no CPU fallback)")
         dev = ref.device
-        if "depth" not in observations:
-            raise ValueError(f"net.visual_encoder needs observations['depth'] (keys: {sorted(observations.keys())})")
-        depth = observations["depth"].to(device=dev, dtype=torch.float32).contiguous()
-        if self._obs_transform is not None:
-            depth = self._transform_depth(depth, dev)
-        if tuple(depth.shape[1:]) != (self._H, self._W, 1):
-            raise ValueError(f"observations['depth'] has shape {tuple(depth.shape)}, expected [B,{self._H},{self._W},1]")
+        vis = self._frames(observations, dev, "net.visual_encoder needs observations[{}] (keys: {})")
         self._ensure(dev)
-        B = depth.shape[0]
+        B = vis.shape[0]
         out = torch.empty((B,) + tuple(self._feat_shape), device=dev, dtype=torch.float32)
         if B:
             with torch.cuda.device(dev):
                 stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                _lib.check(_lib.lib.pnvo_policy_encode(self._handle, C.c_void_p(depth.data_ptr()), int(B), C.c_void_p(out.data_ptr()),
-                                                       stream))
+                if isinstance(vis, _Frames):
+                    _lib.check(_lib.lib.pnvo_policy_encode_rgbd(self._handle, *vis.args(), int(B), C.c_void_p(out.data_ptr()), stream))
+                else:
+                    _lib.check(_lib.lib.pnvo_policy_encode(self._handle, C.c_void_p(vis.data_ptr()), int(B), C.c_void_p(out.data_ptr()),
+                                                           stream))
         return out
 
-    def _transform_depth(self, depth, dev):
-        """[B,Hs,Ws,1] sensor depth -> [B,VIS_H,VIS_W,1] by the observation transform, before avg_pool2d(2) (resnet_policy.py:157-168).
-        The reference permutes the depth to [B,1,H,W] and calls .contiguous(): torch's contiguous area kernel, (sum / kh) / kw."""
-        B, Hs, Ws = depth.shape[0], depth.shape[1], depth.shape[2]
+    def _transform_geometry(self, Hs, Ws):
         geom = self._tgeom.get((Hs, Ws))
         if geom is None:
             geom = transformed_size(Hs, Ws, self._obs_transform.mode, self._obs_transform._size)
             if tuple(geom[4:]) != (self._H, self._W):
-                raise ValueError(f"RL.OBS_TRANSFORM {self._obs_transform.mode!r} maps the {Hs}x{Ws} depth to {geom[4]}x{geom[5]}, but the "
+                raise ValueError(f"RL.OBS_TRANSFORM {self._obs_transform.mode!r} maps the {Hs}x{Ws} frame to {geom[4]}x{geom[5]}, but the "
                                  f"policy's encoder takes {self._H}x{self._W}")
             self._tgeom[(Hs, Ws)] = geom
-        out = torch.empty((B, self._H, self._W, 1), device=dev, dtype=torch.float32)
+        return geom
+
+    def _transform(self, frames, dev):
+        """[B,Hs,Ws,c] sensor frames (c = 1 depth, 3 rgb, uint8 or float32) -> [B,VIS_H,VIS_W,c] float32 by the observation transform,
+        before avg_pool2d(2) (resnet_policy.py:150-168).  The reference permutes each sensor to [B,c,H,W] and calls .contiguous():
+        torch's contiguous area kernel, (sum / kh) / kw per channel.  It divides rgb by 255 in front of the transform; here the raw
+        0..255 values are resized and the input stage divides behind it (both steps are linear)."""
+        B, Hs, Ws, c = (int(v) for v in frames.shape)
+        geom = self._transform_geometry(Hs, Ws)
+        out = torch.empty((B, self._H, self._W, c), device=dev, dtype=torch.float32)
         if B:
-            launch_resize(depth.data_ptr(), torch.float32, B, Hs, Ws, 1, (Hs * Ws, Ws, 1), geom, out.data_ptr(), 1,
-                          (self._H * self._W, 0, self._W, 1), DIV_CONTIGUOUS, dev)
+            launch_resize(frames.data_ptr(), frames.dtype, B, Hs, Ws, c, (Hs * Ws * c, Ws * c, c), geom, out.data_ptr(), 1,
+                          (self._H * self._W * c, 0, self._W * c, c), DIV_CONTIGUOUS, dev)
         return out
 
     def forward(self, *x):

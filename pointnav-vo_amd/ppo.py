@@ -7,6 +7,8 @@ parameters as views of them, Adam's moments and state dict; `flat`, `grad`, `exp
 objects) and drives the C ABI —
 
     pnvo_policy_evaluate     rollout forward (encoder in train mode, LSTM or GRU over T x N with mask resets), activations kept
+                             (pnvo_policy_evaluate_rgbd for rgb / rgb-d / normalised policies: in training mode the minibatch is
+                             merged into RunningMeanAndVar's buffers first; they are buffers — no gradient, no Adam moments)
     pnvo_policy_ppo_loss     clipped surrogate / value loss / entropy and their gradient at the heads, from a kernel
     pnvo_policy_backward     heads, back-propagation through time, embeddings, the encoder's backward
     pnvo_policy_clip_grad_norm, pnvo_adam_step, pnvo_policy_train_refresh
@@ -29,7 +31,7 @@ import torch.nn as nn
 
 from . import _lib
 from .flat_params import FlatParams, flat_offsets  # noqa: F401  (flat_offsets: the layout rule, public here too)
-from .policy import GOAL_SENSOR
+from .policy import GOAL_SENSOR, _Frames
 
 EPS_PPO = 1e-5
 ENCODER_PREFIX = "net.visual_encoder."
@@ -133,7 +135,9 @@ class PolicyTrainStep:
         """-> (value [M,1], action_log_probs [M,1], distribution_entropy (scalar), rnn_hidden_states) as Policy.evaluate_actions
         (policy.py:52-63).  Rows are T-major (row t*N + n); N = rnn_hidden_states.shape[1], T = M / N (T = 1: single_forward)."""
         pol, dev = self.policy, self.dev
-        vis, from_features = pol._visual_input(observations, dev)   # visual_features when present, else depth; checked before any launch
+        # visual_features when present, else the frames (and, in training mode, RunningMeanAndVar's buffers, which this call updates
+        # before it whitens: once per minibatch, as the reference's evaluate_actions does); checked before any launch
+        vis, from_features = pol._visual_input(observations, dev)
         self._sync_params()
         M = vis.shape[0]
         hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
@@ -156,6 +160,10 @@ class PolicyTrainStep:
                 _lib.check(_lib.lib.pnvo_policy_evaluate_features(pol._handle, _ptr(vis), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T),
                                                                   int(N), _ptr(act), _ptr(hout), _ptr(value), _ptr(logp), _ptr(entropy),
                                                                   self._stream()))
+            elif isinstance(vis, _Frames):
+                _lib.check(_lib.lib.pnvo_policy_evaluate_rgbd(pol._handle, *vis.args(), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T),
+                                                              int(N), _ptr(act), int(self.train_encoder), _ptr(hout), _ptr(value),
+                                                              _ptr(logp), _ptr(entropy), self._stream()))
             else:
                 _lib.check(_lib.lib.pnvo_policy_evaluate(pol._handle, _ptr(vis), _ptr(goal), _ptr(pa), _ptr(mk), _ptr(hin), int(T), int(N),
                                                          _ptr(act), int(self.train_encoder), _ptr(hout), _ptr(value), _ptr(logp),

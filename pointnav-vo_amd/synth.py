@@ -149,6 +149,25 @@ def make_policy_inputs(H, W, B, steps, seed, n_actions=4):
     return out
 
 
+def make_policy_rgbd_inputs(H, W, B, steps, seed, n_actions=4, depth_band=(0.4, 0.6)):
+    """make_policy_inputs with an rgb frame per environment: list of (rgb [B,H,W,3] uint8, depth [B,H,W,1] float32, goal, prev_actions,
+    masks).  The depth is make_policy_inputs' own, scaled into `depth_band` (a narrow band: its pooled variance lies far below
+    RunningMeanAndVar's 1e-2 clamp).  The rgb is three parts of a half-resolution make_raw_obs frame, repeated 2 x 2, to one part of a
+    full-resolution one: F.avg_pool2d(x, 2) keeps most of its variance (about 0.05 after / 255, far above the clamp), which the
+    pooling of independent pixels would quarter to the clamp's neighbourhood."""
+    out = []
+    lo, hi = depth_band
+    for t, (depth, goal, prev, mask) in enumerate(make_policy_inputs(H, W, B, steps, seed, n_actions)):
+        rgb = np.empty((B, H, W, 3), np.uint8)
+        for b in range(B):
+            fine = make_raw_obs(H, W, seed=seed, index=100 * t + b)["rgb"].astype(np.int64)
+            half = make_raw_obs((H + 1) // 2, (W + 1) // 2, seed=seed, index=100 * t + b + 50)["rgb"].astype(np.int64)
+            coarse = np.repeat(np.repeat(half, 2, axis=0), 2, axis=1)[:H, :W]
+            rgb[b] = ((3 * coarse + fine) // 4).astype(np.uint8)
+        out.append((rgb, (lo + (hi - lo) * depth).astype(np.float32), goal, prev, mask))
+    return out
+
+
 def make_joint_batch(P, H, W, observation_space, dd_bins=10, seed=0):
     """The batch layout "inverse_joint_train" produces (vo/dataset/regression_geo_invariance_iter_dataset.py:342-386): P turn
     samples, each followed by its channel-swapped (cur, prev) entry for the opposite action.  Returns (obs dict [2P,...],

@@ -2,7 +2,7 @@
 """One PPO minibatch update of the navigation policy at the reference's shape, per phase, on the MI355X.
 
     python tools/bench_ppo_update.py [--n 2 4] [--steps 128] [--iters 12] [--warmup 3] [--out profiles/ppo_update.md] [--no-eager]
-                                      [--rnn {LSTM,GRU}]
+                                      [--rnn {LSTM,GRU}] [--visual-types depth | rgb depth | rgb] [--rgb-dtype {uint8,float32}]
 
 Shape: configs/rl/ddppo_pointnav.yaml — num_steps T = 128, N environments per minibatch, 341 x 192 depth, hidden 512, 2-layer LSTM,
 train_encoder.  The HIP path (pointnav_vo_amd.ppo.PolicyTrainStep) is timed per phase with HIP events recorded inside the library
@@ -14,6 +14,9 @@ policy with random weights: GroupNorm-ResNet18 encoder, nn.LSTM run over the seg
 RNNStateEncoder does, Categorical heads, the PPO loss, clip_grad_norm_, torch.optim.Adam).  It is the only comparison there is: the
 project could not do this update at all before.  No threshold: the record says which side wins, phase by phase.
 --rnn GRU runs both sides with the GRU state encoder (state [LAYERS, N, HIDDEN]); the phase keys keep their names.
+--visual-types with rgb times the HIP path alone on an rgb / rgb-d policy built as the reference trainers build it
+(normalize_visual_inputs on) in training mode: the encoder-forward phase then holds the input stage (rgb / 255, pool, the batch
+moments) and RunningMeanAndVar's update; --rgb-dtype says how the minibatch holds rgb (float32 is what RolloutStorage hands out).
 
     python tools/bench_ppo_update.py --static-encoder [--n 2 8] [--out profiles/static_encoder.md]
 
@@ -83,7 +86,7 @@ class Timer:
 
 
 # ---------------------------------------------------------------------------------------------------------------- HIP path
-def bench_hip(T, N, iters, warmup, dev, rnn="LSTM"):
+def bench_hip(T, N, iters, warmup, dev, rnn="LSTM", visual_types=("depth",), rgb_dtype="uint8"):
     from pointnav_vo_amd.policy import PointNavResNetPolicy
     from pointnav_vo_amd.ppo import PolicyTrainStep
 
@@ -99,13 +102,21 @@ def bench_hip(T, N, iters, warmup, dev, rnn="LSTM"):
         n = ACTIONS
 
     torch.manual_seed(0)
-    pol = PointNavResNetPolicy(observation_space=Space({"depth": Box((H, W, 1)), GOAL: Box((2,))}), action_space=Act(),
-                               hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type=rnn, backbone="resnet18",
-                               normalize_visual_inputs=False, obs_transform=None, vis_types=["depth"]).to(dev)
+    vis = [k for k in ("rgb", "depth") if k in visual_types]
+    plain = vis == ["depth"]
+    pol = PointNavResNetPolicy(observation_space=Space({"depth": Box((H, W, 1)), "rgb": Box((H, W, 3)), GOAL: Box((2,))}),
+                               action_space=Act(), hidden_size=HIDDEN, num_recurrent_layers=LAYERS, rnn_type=rnn, backbone="resnet18",
+                               normalize_visual_inputs=not plain, obs_transform=None, vis_types=vis).to(dev)
+    pol.train(not plain)
     step = PolicyTrainStep(pol, lr=LR, eps=EPS, max_grad_norm=MAX_GRAD_NORM)
     step.timing(True)
     b = make_batch(T, N, dev, rnn=rnn)
-    obs = {"depth": b["depth"], GOAL: b["goal"]}
+    obs = {GOAL: b["goal"]}
+    if "depth" in vis:
+        obs["depth"] = b["depth"]
+    if "rgb" in vis:
+        rgb = torch.randint(0, 256, (T * N, H, W, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1))
+        obs["rgb"] = (rgb if rgb_dtype == "uint8" else rgb.float()).to(dev)
     tm, phases = Timer(), []
     for _ in range(warmup + iters):
         with tm.span("whole update"):
@@ -332,7 +343,12 @@ def main():
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--rnn", choices=["LSTM", "GRU"], default="LSTM")
     ap.add_argument("--static-encoder", action="store_true", help="frozen encoder: frames in against features in (see the docstring)")
+    ap.add_argument("--visual-types", nargs="+", choices=["rgb", "depth"], default=["depth"])
+    ap.add_argument("--rgb-dtype", choices=["uint8", "float32"], default="uint8")
     a = ap.parse_args()
+    with_rgb = "rgb" in a.visual_types
+    if with_rgb and a.static_encoder:
+        raise SystemExit("--static-encoder measures the depth-only policy")
     if not torch.cuda.is_available():
         raise SystemExit("bench_ppo_update.py measures on an MI355X: no GPU here, nothing measured")
     if a.iters < 10:
@@ -343,16 +359,18 @@ def main():
         finish(a, lines, record)
         return
     lines = ["# PPO minibatch update of the navigation policy: HIP path vs torch eager", "",
-             f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 depth, hidden 512, 2-layer {a.rnn}, 4 actions, train_encoder; "
+             f"`tools/bench_ppo_update.py`: T = {a.steps}, 341 x 192 {' + '.join(k for k in ('rgb', 'depth') if k in a.visual_types)}"
+             f"{' (rgb as ' + a.rgb_dtype + ', normalize_visual_inputs, training mode)' if with_rgb else ''}, hidden 512, 2-layer {a.rnn}, "
+             "4 actions, train_encoder; "
              f"median of {a.iters} iterations after {a.warmup} warm-up, HIP events, one process, {torch.cuda.get_device_name(0)}.",
              f"The eager column is the same update in torch-ROCm eager ops with autograd (nn.{a.rnn} over the segments between episode "
              "starts, as the reference's RNNStateEncoder), random weights.  Milliseconds.", ""]
     record = {}
     for N in a.n:
-        hip = bench_hip(a.steps, N, a.iters, a.warmup, dev, a.rnn)
+        hip = bench_hip(a.steps, N, a.iters, a.warmup, dev, a.rnn, a.visual_types, a.rgb_dtype)
         torch.cuda.empty_cache()
         eager = None
-        if not a.no_eager:
+        if not a.no_eager and not with_rgb:                            # (the eager restatement is the depth-only policy)
             try:
                 eager = bench_eager(a.steps, N, a.iters, a.warmup, dev, a.rnn)
             except Exception as e:                                    # the record then says so instead of a number
