@@ -511,6 +511,41 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream);
  * [1], device, may be NULL) and the scaling by max_norm / (norm + 1e-6) when that is below 1.  No host synchronisation. */
 int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm_out, void *stream);
 
+/* The same with the gradient scaled first, in the same two launches: the norm is that of scale * g (each product rounded to float32
+ * before it is squared, as a separate g *= scale pass would leave it), and g <- g * (scale * clip) is written once, clip = min(1,
+ * max_norm / (norm + 1e-6)).  max_norm <= 0: scale only (norm_out still receives the norm).  scale = 1 gives the bits of
+ * pnvo_policy_clip_grad_norm.  Data-parallel training passes scale = 1 / world_size behind the gradient's all-reduce (sum). */
+int pnvo_policy_clip_grad_norm_scaled(pnvo_policy_handle h, float scale, float max_norm, float *norm_out, void *stream);
+
+/*
+ * Gradient-ready hook of the policy's update step, the contract of pnvo_train_set_grad_hook: during pnvo_policy_backward the library
+ * calls fn(user, first, count, stream) on the host each time a range of the flat gradient is final (its producing launches are
+ * enqueued on `stream`).  Every float of every parameter that has a gradient in this backward is reported exactly once; a range may
+ * span the alignment gaps between neighbouring tensors (always zero) and never reaches the library's tail behind the last parameter.
+ * Order: the embeddings, the recurrent tensors and the heads before the encoder's backward is entered; then — through the encoder
+ * handle's own hook — the encoder and net.visual_fc without the stem weight; the stem weight last, once it has been un-padded from the
+ * tail.  With train_encoder = 0, and after pnvo_policy_evaluate_features, net.visual_fc follows the first group and the encoder's range
+ * (exactly zero on every rank) is not reported.  pnvo_policy_grad_buckets returns the ranges of such a backward, in its order, without
+ * running one: first / count hold up to cap entries, *n_out receives the number there are.  fn = NULL removes the hook.
+ */
+int pnvo_policy_set_grad_hook(pnvo_policy_handle h, pnvo_grad_ready_fn fn, void *user);
+int pnvo_policy_grad_buckets(pnvo_policy_handle h, int train_encoder, int from_features, uint64_t *first, uint64_t *count, int cap,
+                             int *n_out);
+
+/*
+ * Cross-process reduction of RunningMeanAndVar's batch statistics inside the input stage (running_mean_and_var.py:24-42 under
+ * torch.distributed).  With a hook set, every entry point that merges in training mode (pnvo_policy_act_rgbd, _encode_rgbd,
+ * _evaluate_rgbd) leaves in `sums` (a caller-owned device buffer of 2C + 1 doubles, C = the policy's input channels) the un-normalised
+ * sums about the current running mean c — sums[ch] = sum (x - c), sums[C + ch] = sum (x - c)^2 over the call's pooled pixels,
+ * sums[2C] = its number of frames — calls fn(user, sums, 2C + 1, stream) on the host, which must enqueue on `stream` an in-place
+ * sum of the buffer over the ranks, and then takes the batch moments and Chan's merge from the reduced sums and the reduced frame count,
+ * both read on the device: one round, no host synchronisation of the library's own.  The running mean is the same on all ranks (the
+ * caller broadcasts the buffers once), so the reduced second sums give the variance about the global batch mean.  One rank, or a hook
+ * that leaves the buffer alone: the bits of the path without a hook.  fn = NULL removes the hook.
+ */
+typedef void (*pnvo_stats_reduce_fn)(void *user, double *sums, int n, void *stream);
+int pnvo_policy_set_stats_hook(pnvo_policy_handle h, pnvo_stats_reduce_fn fn, void *user, double *sums);
+
 /* Phase timing of the update step with HIP events recorded on the launch stream (tools/bench_ppo_update.py; not part of the drop-in
  * surface).  mode 0 = off, 1 = on.  pnvo_policy_train_timing_read waits for the last pnvo_policy_backward and returns the
  * milliseconds of the last evaluate / ppo_loss / backward: {encoder forward, LSTM or GRU forward + heads, loss, heads + BPTT +

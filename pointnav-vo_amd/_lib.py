@@ -20,6 +20,7 @@ PNVO_OK = 0
 
 
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+STATS_REDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)        # pnvo_stats_reduce_fn
 
 
 class PnvoError(RuntimeError):
@@ -134,6 +135,11 @@ _SIGNATURES = {
                                        C.c_int, C.c_void_p, C.c_void_p]),
     "pnvo_policy_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pnvo_policy_clip_grad_norm": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pnvo_policy_clip_grad_norm_scaled": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "pnvo_policy_set_grad_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pnvo_policy_grad_buckets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
+                                           C.POINTER(C.c_int)]),
+    "pnvo_policy_set_stats_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_policy_train_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "pnvo_policy_train_timing_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "pnvo_rollout_insert": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 7),

@@ -442,6 +442,8 @@ hipError_t launch_maxpool_bwd(const float *dpool, const unsigned char *idx, int 
                               hipStream_t s);
 hipError_t launch_rmv_merge(const float *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s);
 hipError_t launch_rmv_merge(const double *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s);   // float64 moments
+// the same merge with the batch's frame count read from the device (a double: the all-reduced count of the data-parallel input stage)
+hipError_t launch_rmv_merge_dev(const double *m12, int C, const double *nb, float *mean, float *var, float *count, hipStream_t s);
 hipError_t launch_colsum(const float *x, int rows, int cols, int ld, float *out, hipStream_t s);
 hipError_t launch_padcopy(const float *src, int rows, int cols, int ldd, float *dst, hipStream_t s);
 // y = [relu(x*scale[n,c]+shift[n,c]) or x] * keep/(1-p); keep = hash(seed, step, layer, element) >= p.  x viewed as

@@ -242,6 +242,18 @@ __global__ __launch_bounds__(64) void input_moments_final_kernel(const double *p
   if (threadIdx.x == 0) m12[row] = s / npix;
 }
 
+// The data-parallel input stage (pnvo_policy_set_stats_hook).  input_moments_final_kernel with npix = 1 leaves the un-normalised sums
+// in sums[0 .. 2C); this launch adds the call's frame count behind them, so that ONE all-reduce carries both ...
+__global__ __launch_bounds__(64) void stats_count_kernel(double frames, double *count) {
+  if (threadIdx.x == 0) *count = frames;
+}
+// ... and this one turns the reduced sums into the batch moments m12[row] = sums[row] / (frames * pixels per frame), the division
+// input_moments_final_kernel makes on one rank (the product of two integers is exact in float64: one rank gives the same bits).
+__global__ __launch_bounds__(64) void stats_moments_kernel(const double *sums, int C, double frame_pix, double *m12) {
+  const int row = threadIdx.x;
+  if (row < 2 * C) m12[row] = sums[row] / (sums[2 * C] * frame_pix);
+}
+
 // RunningMeanAndVar's buffers [C] -> the encoder handle's 2C channels (mean 0 / variance 1 on the zero channels: what its train-mode
 // forward takes) and the float32 stem's whitening pair (x - mean) / sqrt(max(var, 1e-2)) = x * sc + sh over its CPL channel slots
 // (running_mean_and_var.py:62-63; the arithmetic of whiten_table_kernel).  The handle's one modality keeps its channels in place:
@@ -617,7 +629,18 @@ int pnvo::policy_input_stage(Policy &p, const PolicyObs &o, int B, float *pooled
     PCHK(p.var_pad.alloc(8));
   }
   PCHK(launch_policy_input(c, o.rgb, o.rgb_is_u8, o.depth, B, o.mean, train ? 1 : 0, pooled, p.in_part, s));
-  if (train) {
+  if (train && p.stats_hook) {
+    // one round over the ranks: sums about the (rank-identical) running mean and the frame count, reduced in place by the caller's
+    // hook on this stream; the moments and the merge then read the reduced values on the device
+    double *S = p.stats_sums;
+    hipLaunchKernelGGL(input_moments_final_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, s, p.in_part, input_blocks(c, B), 1.0, S);
+    hipLaunchKernelGGL(stats_count_kernel, dim3(1), dim3(64), 0, s, (double)B, S + 2 * C);
+    PCHK(hipGetLastError());
+    p.stats_hook(p.stats_user, S, 2 * C + 1, (void *)s);
+    hipLaunchKernelGGL(stats_moments_kernel, dim3(1), dim3(64), 0, s, S, C, (double)(c.height / 2) * (c.width / 2), p.m12);
+    PCHK(hipGetLastError());
+    PCHK(launch_rmv_merge_dev(p.m12, C, S + 2 * C, o.mean, o.var, o.count, s));
+  } else if (train) {
     const double npix = (double)B * (c.height / 2) * (c.width / 2);
     hipLaunchKernelGGL(input_moments_final_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, s, p.in_part, input_blocks(c, B), npix, p.m12);
     PCHK(hipGetLastError());
@@ -1000,6 +1023,17 @@ int pnvo_policy_input_stage(pnvo_policy_handle h, const void *rgb, int rgb_is_u8
     hipLaunchKernelGGL(input_moments_final_kernel, dim3((unsigned)(2 * C)), dim3(64), 0, s, p.in_part, nb, (double)npix, m12_out);
     PCHK(hipGetLastError());
   }
+  return PNVO_OK;
+}
+
+int pnvo_policy_set_stats_hook(pnvo_policy_handle h, pnvo_stats_reduce_fn fn, void *user, double *sums) {
+  if (!h) return pfail(PNVO_ERR_ARG, "null handle");
+  Policy &p = h->p;
+  if (fn && !p.cfg.normalize) return pfail(PNVO_ERR_STATE, "pnvo_policy_set_stats_hook: the policy does not normalise its visual inputs");
+  if (fn && (!sums || ((uintptr_t)sums & 7))) return pfail(PNVO_ERR_ARG, "pnvo_policy_set_stats_hook: sums must be an 8-byte aligned device buffer");
+  p.stats_hook = fn;
+  p.stats_user = fn ? user : nullptr;
+  p.stats_sums = fn ? sums : nullptr;
   return PNVO_OK;
 }
 

@@ -35,6 +35,10 @@ struct Policy {
   // moments [2C] (float64), and the statistics padded to the encoder handle's 2C channels (mean 0, variance 1 on the zero channels)
   DevBuf<double> in_part, m12;
   DevBuf<float> mean_pad, var_pad;
+  // pnvo_policy_set_stats_hook: the cross-process reduction of the batch sums (stats_sums: the caller's 2C + 1 doubles, borrowed)
+  pnvo_stats_reduce_fn stats_hook = nullptr;
+  void *stats_user = nullptr;
+  double *stats_sums = nullptr;
 };
 
 // ---- the visual input (pnvo_policy_config.rgb_channels / no_depth / normalize).  C channels in the reference's torch.cat order (rgb,

@@ -27,10 +27,12 @@
 // training) in place of depth: the encoder does not run, visual = relu(features . W_fc^T + b_fc) is launch_visual_fc (the row kernel of
 // pnvo_policy.hip for few rows, gemm_f32_kernel with a ReLU epilogue otherwise) on torch's [hidden, F] weight, and the backward ends with
 // the ReLU mask, dW_fc = d visual^T . features (the rows kept in the workspace) and db_fc = colsum: the encoder's range stays zero.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pnvo.h"
@@ -68,6 +70,16 @@ struct PolicyTrain {
   // pnvo_policy_train_timing: events at the phase boundaries of evaluate / ppo_loss / backward (tools/bench_ppo_update.py)
   bool timing = false;
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // pnvo_policy_set_grad_hook.  The flat ranges of the parameter table by the side that produces their gradient, each list ascending and
+  // disjoint (neighbouring tensors of one side are one range, alignment gaps included): `early` — embeddings, recurrent tensors, heads:
+  // final before the encoder's backward; `enc` — net.visual_encoder without the stem weight; `vfc` — net.visual_fc; the stem weight is
+  // [o_stem, o_stem + c0 * stem_row).  enc_pass: what the running backward lets through of the encoder handle's own reports
+  // (0: nothing, 1: vfc, 2: vfc and enc).
+  typedef std::vector<std::pair<size_t, size_t>> Ranges;    // (first, end)
+  Ranges r_early, r_enc, r_vfc;
+  pnvo_grad_ready_fn hook = nullptr;
+  void *hook_user = nullptr;
+  int enc_pass = 0;
 };
 
 namespace {
@@ -592,11 +604,13 @@ __global__ __launch_bounds__(256) void stem_unpad_kernel(const float *w2, int c0
 }
 
 // clip_grad_norm_: partial sums of squares over fixed slices, then every workgroup folds the partials in the same order and scales
-__global__ __launch_bounds__(256) void sumsq_kernel(const float *g, long n, double *part) {
+// (scale: pnvo_policy_clip_grad_norm_scaled — the norm of scale * g with each product rounded to float32, then ONE write of
+// g * (scale * clip); scale = 1 multiplies by one, exactly)
+__global__ __launch_bounds__(256) void sumsq_kernel(const float *g, long n, float scale, double *part) {
   __shared__ double sd[256];
   double a = 0.0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)SQ_BLOCKS * 256) {
-    const double v = (double)g[i];
+    const double v = (double)(g[i] * scale);
     a += v * v;
   }
   sd[threadIdx.x] = a;
@@ -607,7 +621,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float *g, long n, doub
   }
   if (threadIdx.x == 0) part[blockIdx.x] = sd[0];
 }
-__global__ __launch_bounds__(256) void clip_scale_kernel(float *g, long n, const double *part, float max_norm, float *norm_out) {
+__global__ __launch_bounds__(256) void clip_scale_kernel(float *g, long n, const double *part, float scale, float max_norm, float *norm_out) {
   __shared__ double sd[256];
   double a = 0.0;
   for (int i = threadIdx.x; i < SQ_BLOCKS; i += 256) a += part[i];
@@ -620,8 +634,77 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float *g, long n, const
   const float norm = (float)sqrt(sd[0]);
   if (norm_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
   const float coef = max_norm / (norm + 1e-6f);              // nn.utils.clip_grad_norm_: clamp(max_norm / (total + 1e-6), max = 1)
-  if (!(coef < 1.f)) return;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) g[i] *= coef;
+  const bool clip = max_norm > 0.f && coef < 1.f;            // (max_norm <= 0: scale only)
+  if (!clip && scale == 1.f) return;
+  const float f = clip ? scale * coef : scale;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) g[i] *= f;
+}
+
+// ---- gradient-ready ranges (pnvo_policy_set_grad_hook)
+void report(const PolicyTrain *t, const PolicyTrain::Ranges &r, hipStream_t s) {
+  if (!t->hook) return;
+  for (const auto &ab : r) t->hook(t->hook_user, (uint64_t)ab.first, (uint64_t)(ab.second - ab.first), (void *)s);
+}
+// the part of [first, end) inside the ranges of `r`, appended to `out`
+void clip_ranges(size_t first, size_t end, const PolicyTrain::Ranges &r, PolicyTrain::Ranges *out) {
+  for (const auto &ab : r) {
+    const size_t a = std::max(first, ab.first), b = std::min(end, ab.second);
+    if (b > a) out->push_back({a, b});
+  }
+}
+// what one report [first, end) of the encoder handle means here: that handle was attached to the whole flat buffer (tail and all), so
+// its ranges are cut down to the tensors its backward fills — net.visual_fc, and with a trained encoder net.visual_encoder without the
+// stem weight, whose gradient is still in the tail's padded copy at that point
+PolicyTrain::Ranges encoder_pieces(const PolicyTrain *t, int pass, size_t first, size_t end) {
+  PolicyTrain::Ranges enc_vfc, out;
+  if (pass >= 2) enc_vfc = t->r_enc;
+  if (pass >= 1) enc_vfc.insert(enc_vfc.end(), t->r_vfc.begin(), t->r_vfc.end());
+  std::sort(enc_vfc.begin(), enc_vfc.end());
+  clip_ranges(first, end, enc_vfc, &out);
+  return out;
+}
+void encoder_hook(void *user, uint64_t first, uint64_t count, void *stream) {
+  const PolicyTrain *t = static_cast<const PolicyTrain *>(user);
+  if (t->hook && t->enc_pass) report(t, encoder_pieces(t, t->enc_pass, (size_t)first, (size_t)(first + count)), (hipStream_t)stream);
+}
+// the table's entries sorted by offset -> the three lists; the stem weight splits the encoder's range where it lies
+void build_ranges(PolicyTrain *t, const pnvo_tensor_desc *toc, int ntoc) {
+  struct Ent { size_t a, b; int side; };
+  std::vector<Ent> es;
+  for (int k = 0; k < ntoc; ++k) {
+    const std::string nm = toc[k].name;
+    const size_t a = (size_t)toc[k].offset, b = a + numel(std::vector<int64_t>(toc[k].shape, toc[k].shape + toc[k].ndim));
+    const int side = a == t->o_stem ? 3 : nm.rfind("net.visual_encoder.", 0) == 0 ? 1 : nm.rfind("net.visual_fc.", 0) == 0 ? 2 : 0;
+    if (b > a) es.push_back({a, b, side});
+  }
+  std::sort(es.begin(), es.end(), [](const Ent &x, const Ent &y) { return x.a < y.a; });
+  PolicyTrain::Ranges *lists[3] = {&t->r_early, &t->r_enc, &t->r_vfc};
+  for (auto *l : lists) l->clear();
+  int prev = -1;
+  for (const Ent &e : es) {
+    if (e.side < 3) {
+      if (e.side == prev) lists[e.side]->back().second = e.b;
+      else lists[e.side]->push_back({e.a, e.b});
+    }
+    prev = e.side;
+  }
+}
+// every range one backward reports, in its order
+PolicyTrain::Ranges backward_ranges(Policy &p, const PolicyTrain *t, bool train_encoder, bool from_features) {
+  PolicyTrain::Ranges out = t->r_early;
+  if (from_features || !train_encoder) {
+    out.insert(out.end(), t->r_vfc.begin(), t->r_vfc.end());
+    return out;
+  }
+  uint64_t first[8], count[8];
+  int n = 0;
+  if (pnvo_train_grad_buckets(p.enc, first, count, 8, &n) == PNVO_OK)
+    for (int k = 0; k < n && k < 8; ++k) {
+      const PolicyTrain::Ranges pc = encoder_pieces(t, 2, (size_t)first[k], (size_t)(first[k] + count[k]));
+      out.insert(out.end(), pc.begin(), pc.end());
+    }
+  out.push_back({t->o_stem, t->o_stem + (size_t)t->c0 * t->stem_row});
+  return out;
 }
 
 // phase boundary k of the update step (only while timing is on)
@@ -788,7 +871,12 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
     PCHK(hipGetLastError());
     PCHK(t->whhT.alloc((size_t)4 * Hd * Hd));
     PCHK(t->sq_part.alloc(SQ_BLOCKS));
-    return attach_encoder(p, t, ent, toc);
+    build_ranges(t, toc, ntoc);
+    const int rc2 = attach_encoder(p, t, ent, toc);
+    if (rc2 != PNVO_OK) return rc2;
+    // the encoder handle's reports pass through encoder_hook (a no-op until pnvo_policy_set_grad_hook names a receiver)
+    if (pnvo_train_set_grad_hook(p.enc, encoder_hook, t) != PNVO_OK) return pfail(PNVO_ERR_STATE, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+    return PNVO_OK;
   }();
   if (rc != PNVO_OK) {                  // no half-built train step is left behind
     pnvo_policy_train_free(p);
@@ -1036,6 +1124,7 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
                      t->rows, t->g3, M, Hd, A + 1, grad_of(t, p.tgt_w), grad_of(t, p.tgt_b), grad_of(t, p.emb), t->dY);
   PCHK(hipGetLastError());
   PCHK(mark(t, 6, s));
+  report(t, t->r_early, s);             // embeddings, recurrent tensors, heads: final; they can travel while the encoder's backward runs
   if (t->from_features) {
     // visual_fc alone, whatever train_encoder says: nothing of the encoder ran, and no gradient is taken with respect to the features.
     // d visual (t->dY) through the ReLU, dW = d visual^T . features, db = colsum(d visual); the encoder's range stays at the memset's zeros
@@ -1045,15 +1134,19 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
     GemmArgs dw{t->dY, t->feat, nullptr, nullptr, grad_of(t, p.vfc_w), Hd, F, M, 1, (long)Hd, (long)F, 1, (long)F};
     PCHK((launch_gemm<false, false>(dw, s)));
     PCHK(launch_colsum(t->dY, M, Hd, Hd, grad_of(t, p.vfc_b), s));
+    report(t, t->r_vfc, s);
     PCHK(mark(t, 7, s));
     return PNVO_OK;
   }
+  t->enc_pass = train_encoder ? 2 : 1;
   const int rc = pnvo_train_backward_from_hidden(p.enc, t->dY, train_encoder == 0, stream);
+  t->enc_pass = 0;
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   if (train_encoder) {
     hipLaunchKernelGGL(stem_unpad_kernel, dim3((unsigned)((t->c0 * t->stem_row + 255) / 256)), dim3(256), 0, s, G + t->o_stem2, t->c0, t->stem_row,
                        G + t->o_stem);
     PCHK(hipGetLastError());
+    report(t, {{t->o_stem, t->o_stem + (size_t)t->c0 * t->stem_row}}, s);
   }
   PCHK(mark(t, 7, s));
   return PNVO_OK;
@@ -1084,16 +1177,46 @@ int pnvo_policy_train_timing_read(pnvo_policy_handle h, double ms[5]) {
   return PNVO_OK;
 }
 
-int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm_out, void *stream) {
-  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
-  if (!(max_norm > 0.f)) return pfail(PNVO_ERR_ARG, "max_grad_norm " + std::to_string(max_norm) + " must be > 0");
+static int clip_grad_norm_impl(pnvo_policy_handle h, float scale, float max_norm, float *norm_out, void *stream) {
   Policy &p = h->p;
   PolicyTrain *t = p.train;
   PCHK(hipSetDevice(p.device));
   const long n = (long)t->n_named;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, t->sq_part);
-  hipLaunchKernelGGL(clip_scale_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, t->sq_part, max_norm, norm_out);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, scale, t->sq_part);
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(SQ_BLOCKS), dim3(256), 0, (hipStream_t)stream, t->grads, n, t->sq_part, scale, max_norm, norm_out);
   PCHK(hipGetLastError());
+  return PNVO_OK;
+}
+
+int pnvo_policy_clip_grad_norm(pnvo_policy_handle h, float max_norm, float *norm_out, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  if (!(max_norm > 0.f)) return pfail(PNVO_ERR_ARG, "max_grad_norm " + std::to_string(max_norm) + " must be > 0");
+  return clip_grad_norm_impl(h, 1.f, max_norm, norm_out, stream);
+}
+
+int pnvo_policy_clip_grad_norm_scaled(pnvo_policy_handle h, float scale, float max_norm, float *norm_out, void *stream) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  if (!std::isfinite(scale) || !(scale > 0.f)) return pfail(PNVO_ERR_ARG, "gradient scale " + std::to_string(scale) + " must be finite and > 0");
+  if (std::isnan(max_norm)) return pfail(PNVO_ERR_ARG, "max_grad_norm is NaN");
+  return clip_grad_norm_impl(h, scale, max_norm > 0.f ? max_norm : 0.f, norm_out, stream);
+}
+
+int pnvo_policy_set_grad_hook(pnvo_policy_handle h, pnvo_grad_ready_fn fn, void *user) {
+  if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  h->p.train->hook = fn;
+  h->p.train->hook_user = fn ? user : nullptr;
+  return PNVO_OK;
+}
+
+int pnvo_policy_grad_buckets(pnvo_policy_handle h, int train_encoder, int from_features, uint64_t *first, uint64_t *count, int cap,
+                             int *n_out) {
+  if (!h || !h->p.train || !n_out) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  const PolicyTrain::Ranges r = backward_ranges(h->p, h->p.train, train_encoder != 0, from_features != 0);
+  *n_out = (int)r.size();
+  for (int k = 0; k < *n_out && k < cap && first && count; ++k) {
+    first[k] = (uint64_t)r[k].first;
+    count[k] = (uint64_t)(r[k].second - r[k].first);
+  }
   return PNVO_OK;
 }
 

@@ -1840,8 +1840,9 @@ __global__ __launch_bounds__(64) void moments_final_kernel(const MomentsArgs a, 
 // variance about it from the one-pass moments e1 = E[x - c], e2 = E[(x - c)^2] about the old running mean c, then Chan's merge.
 // The moments arrive as float32 (pnvo_input_moments' output) or as float64 (the navigation policy's input stage, whose first batches
 // are centred on a running mean of zero: e2 - e1^2 would lose the variance of a narrow channel to float32's rounding of e2).
+// (nb = the batch's frame count: a launch argument, or — the data-parallel input stage — the all-reduced count read from the device)
 template <typename T>
-__global__ void rmv_merge_kernel(const T *m12, int C, float nb, float *mean, float *var, float *count) {
+__device__ __forceinline__ void rmv_merge_body(const T *m12, int C, float nb, float *mean, float *var, float *count) {
   const int c = threadIdx.x;
   const float cnt = *count;
   __syncthreads();                                        // (everybody has read the old count)
@@ -1858,6 +1859,13 @@ __global__ void rmv_merge_kernel(const T *m12, int C, float nb, float *mean, flo
   }
   if (c == 0) *count = cnt + nb;
 }
+template <typename T>
+__global__ void rmv_merge_kernel(const T *m12, int C, float nb, float *mean, float *var, float *count) {
+  rmv_merge_body(m12, C, nb, mean, var, count);
+}
+__global__ void rmv_merge_dev_kernel(const double *m12, int C, const double *nb, float *mean, float *var, float *count) {
+  rmv_merge_body(m12, C, (float)*nb, mean, var, count);
+}
 
 hipError_t launch_rmv_merge(const float *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s) {
   hipLaunchKernelGGL(rmv_merge_kernel<float>, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, (float)B, mean, var, count);
@@ -1865,6 +1873,11 @@ hipError_t launch_rmv_merge(const float *m12, int C, int B, float *mean, float *
 }
 hipError_t launch_rmv_merge(const double *m12, int C, int B, float *mean, float *var, float *count, hipStream_t s) {
   hipLaunchKernelGGL(rmv_merge_kernel<double>, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, (float)B, mean, var, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_rmv_merge_dev(const double *m12, int C, const double *nb, float *mean, float *var, float *count, hipStream_t s) {
+  hipLaunchKernelGGL(rmv_merge_dev_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, m12, C, nb, mean, var, count);
   return hipGetLastError();
 }
 

@@ -46,3 +46,33 @@ def allreduce_mean_(flat: torch.Tensor) -> torch.Tensor:
         dist.all_reduce(flat)
         flat /= dist.get_world_size()
     return flat
+
+
+class BucketAllReduce:
+    """The gradient all-reduce of a training step in ranges that start while its backward is still running (VOTrainStep, DDPPO): each
+    range travels on ONE communication stream behind an event recorded on the launch stream; `wait` makes the launch stream wait for
+    all of them (no host block with RCCL).  The sum is left in place: the caller divides (or folds 1 / world into its clipping)."""
+
+    def __init__(self, device):
+        self.dev = device
+        self.pending = []                      # (work handle, first, count) of the all-reduces in flight
+        self._comm = None
+
+    def start(self, grad, first, count):
+        """All-reduce grad[first : first + count] behind everything enqueued on the current stream so far."""
+        main = torch.cuda.current_stream(self.dev)
+        if self._comm is None:
+            self._comm = torch.cuda.Stream(self.dev)
+        ev = torch.cuda.Event()
+        ev.record(main)
+        with torch.cuda.stream(self._comm):
+            self._comm.wait_event(ev)
+            work = dist.all_reduce(grad[first:first + count], async_op=True)
+        self.pending.append((work, first, count))
+
+    def wait(self):
+        for work, _, _ in self.pending:
+            work.wait()                        # the current stream waits for the collective
+        if self._comm is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(self._comm)
+        self.pending = []

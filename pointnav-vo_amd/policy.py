@@ -268,6 +268,8 @@ class PointNavResNetPolicy(nn.Module):
         self._handle_dev = None
         self._loaded_sig = None
         self._train_step = None                            # ppo.PolicyTrainStep once attached: the weights then live in its flat buffer
+        self._dist_stats = False                           # distributed_statistics(): RunningMeanAndVar's moments are all-reduced
+        self._stats_hook = self._stats_sums = None         # (the callback object and the device buffer the library borrows)
 
     @property
     def num_recurrent_layers(self):
@@ -278,10 +280,41 @@ class PointNavResNetPolicy(nn.Module):
         return self._hidden
 
     # ------------------------------------------------------------------ libpnvo plumbing
+    def distributed_statistics(self, on=True):
+        """Opt in to (or out of) the cross-process reduction of RunningMeanAndVar's batch moments (running_mean_and_var.py:24-42 under
+        torch.distributed): in training mode every act / get_value / net.visual_encoder / evaluate_actions call then all-reduces 2C + 1
+        float64 sums over the default process group inside the input stage (one round, on the launch stream), so EVERY rank must make
+        the same calls in the same order, and the three buffers must start out equal on all ranks (DDPPO.init_distributed broadcasts
+        them).  A policy without normalize_visual_inputs has nothing to reduce."""
+        self._dist_stats = bool(on) and self._normalize
+        if self._handle is not None:
+            self._install_stats_hook()
+        return self
+
+    def _on_stats(self, user, sums, n, stream):
+        """pnvo_stats_reduce_fn: called by the input stage on the host; the sums are final on the launch stream (the current one)."""
+        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.all_reduce(self._stats_sums)
+
+    def _install_stats_hook(self):
+        on = self._stats_hook is not None
+        if on == self._dist_stats:
+            return
+        if self._dist_stats:
+            dev = torch.device("cuda", self._handle_dev or 0)
+            self._stats_sums = torch.zeros(2 * (self._n_rgb + self._n_depth) + 1, device=dev, dtype=torch.float64)
+            self._stats_hook = _lib.STATS_REDUCE_FN(self._on_stats)
+            _lib.check(_lib.lib.pnvo_policy_set_stats_hook(self._handle, C.cast(self._stats_hook, C.c_void_p), None,
+                                                           C.c_void_p(self._stats_sums.data_ptr())))
+        else:
+            _lib.check(_lib.lib.pnvo_policy_set_stats_hook(self._handle, None, None, None))
+            self._stats_hook = self._stats_sums = None
+
     def _ensure(self, device):
         if self._train_step is not None:                    # the library reads the train step's flat buffer: nothing to upload
             if self._handle_dev != device.index:
                 raise RuntimeError("the policy moved to another device after a PolicyTrainStep was attached")
+            self._install_stats_hook()
             self._train_step._sync_params()
             return
         if self._handle is None or self._handle_dev != device.index:
@@ -293,6 +326,8 @@ class PointNavResNetPolicy(nn.Module):
             h = C.c_void_p()
             _lib.check(_lib.lib.pnvo_policy_create(C.byref(cc), int(device.index or 0), C.byref(h)))
             self._handle, self._handle_dev, self._loaded_sig = h, device.index, None
+            self._stats_hook = self._stats_sums = None          # (a new handle has no hook yet)
+        self._install_stats_hook()
         tensors = getattr(self, "_spec_tensors", None)      # (the walk over the module tree costs ~50 us per step: kept until _apply)
         if tensors is None:
             sd = dict(self.named_parameters())
@@ -406,12 +441,14 @@ class PointNavResNetPolicy(nn.Module):
     def _statistics(self, dev):
         """(_mean, _var, _count, training) of net.visual_encoder.running_mean_and_var as the library borrows them, or None without
         normalisation.  In training mode the reference all-reduces the batch moments over the processes (running_mean_and_var.py:
-        27-38); that reduction is not built, so a process group and training mode together are refused."""
+        27-38); here that reduction is an opt-in (distributed_statistics), because it makes every call a collective: without it a
+        process group and training mode together are refused."""
         if not self._normalize:
             return None
-        if self.training and torch.distributed.is_available() and torch.distributed.is_initialized():
+        if self.training and not self._dist_stats and torch.distributed.is_available() and torch.distributed.is_initialized():
             raise NotImplementedError("normalize_visual_inputs in training mode under torch.distributed: the cross-process reduction "
-                                      "(all_reduce) of RunningMeanAndVar's batch moments is not built; run one process, or call "
+                                      "(all_reduce) of RunningMeanAndVar's batch moments is off; call policy.distributed_statistics(True) "
+                                      "(DDPPO.init_distributed does) so that every rank's calls reduce them, run one process, or call "
                                       ".eval() on the policy")
         rmv = self.net.visual_encoder.running_mean_and_var
         bufs = (rmv._mean, rmv._var, rmv._count)

@@ -15,13 +15,14 @@ objects) and drives the C ABI —
 
 — with no torch autograd anywhere.  `PPO` keeps the reference agent's constructor and `update(rollouts)` contract, so a trainer's
 `self.agent.update(rollouts)` works; the loop over `rollouts.recurrent_generator` stays in Python and the loss sums stay on the device
-until the end (one synchronisation per update).  The gradient is one flat buffer: a data-parallel all-reduce is one call
-(parallel.allreduce_mean_(step.grad)) between `backward()` and `optimizer_step()`.
+until the end (one synchronisation per update).  The gradient is one flat buffer; the data-parallel agent is ddppo.DDPPO (the
+reference's DecentralizedDistributedMixin in front of this PPO: its all-reduce rides on the ranges pnvo_policy_backward reports through
+pnvo_policy_set_grad_hook, between `backward()` and `optimizer_step()`, and the division by the world size is folded into the clipping).
 
 `rollouts` is rollout_storage.RolloutStorage (the reference's class on the device: insert, compute_returns and the minibatch gather
 are one launch each); the agent reads only `returns`, `value_preds` and `recurrent_generator`.
 
-Not here: the DD-PPO reducer and pre-emption logic, an autograd bridge for the reference's own PPO.update, non-resnet18
+Not here: the DD-PPO trainer and its pre-emption logic, an autograd bridge for the reference's own PPO.update, non-resnet18
 backbones.  No CPU fallback.
 """
 import ctypes as C
@@ -115,6 +116,10 @@ class PolicyTrainStep:
         if not self.store.changed():
             return
         self.store.realias()
+        self._repack()
+
+    def _repack(self):
+        """The kernel operands (the padded stem, the encoder's packed weights) from the flat buffer as it is now."""
         with torch.cuda.device(self.dev):
             for _ in range(3):                                 # three: flat_params.py, "The owner's part"
                 _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, self._stream()))

@@ -68,8 +68,7 @@ class VOTrainStep:
         # (pnvo_train_set_grad_hook; layer4..head first — 80 % of the bytes — then layer2-3, then stem + layer1);
         # bucketed = False: ONE flat all-reduce after the backward (bench.py --no-overlap, the A/B of the two schedules)
         self.bucketed = True
-        self._pending = []                     # (work handle, first, count) of the all-reduces in flight
-        self._comm = None
+        self._buckets = parallel.BucketAllReduce(self.dev)     # the all-reduces in flight, on one communication stream
         self._hook = _lib.GRAD_READY_FN(self._on_grad_ready)
         _lib.check(_lib.lib.pnvo_train_set_grad_hook(model._handle, C.cast(self._hook, C.c_void_p), None), model._handle)
 
@@ -260,15 +259,7 @@ class VOTrainStep:
     def _allreduce_bucket(self, first, count):
         """Start the all-reduce of grad[first : first + count] behind everything enqueued on the current stream so far, on the
         communication stream (RCCL runs next to the rest of the backward); optimizer_step waits for it."""
-        main = torch.cuda.current_stream(self.dev)
-        if self._comm is None:
-            self._comm = torch.cuda.Stream(self.dev)
-        ev = torch.cuda.Event()
-        ev.record(main)
-        with torch.cuda.stream(self._comm):
-            self._comm.wait_event(ev)
-            work = dist.all_reduce(self.grad[first:first + count], async_op=True)
-        self._pending.append((work, first, count))
+        self._buckets.start(self.grad, first, count)
 
     def _on_grad_ready(self, user, first, count, stream):
         """pnvo_grad_ready_fn: called by pnvo_train_backward on the host when a flat gradient range is final."""
@@ -287,14 +278,10 @@ class VOTrainStep:
             return
         world = dist.get_world_size()
         if self.bucketed:
-            if not self._pending:
+            if not self._buckets.pending:
                 for first, count in self._bucket_ranges():
                     self._allreduce_bucket(first, count)
-            for work, _, _ in self._pending:
-                work.wait()                    # the current stream waits for the collective (no host block with RCCL)
-            if self._comm is not None:
-                torch.cuda.current_stream(self.dev).wait_stream(self._comm)
-            self._pending = []
+            self._buckets.wait()               # the current stream waits for the collectives (no host block with RCCL)
             self.grad /= world
         else:
             parallel.allreduce_mean_(self.grad)
@@ -311,7 +298,7 @@ class VOTrainStep:
                 self._update_running_stats(None, 0, stream)
                 self.model._loaded_sig = None
             self.grad.zero_()
-            self._pending = []                  # (no backward ran: optimizer_step issues the bucket sequence itself)
+            self._buckets.pending = []          # (no backward ran: optimizer_step issues the bucket sequence itself)
 
     def absent_backward(self):
         """The point of the collective sequence where this model's backward would start its bucket all-reduces, on a rank that
