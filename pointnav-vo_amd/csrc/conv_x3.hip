@@ -82,10 +82,20 @@ constexpr int x3_wpe(int mw, int nw, int np, bool dsf = false) {
 // staged chunk (B fragments fetched once per workgroup instead of once per wave, MW MFMA triples per fragment pair instead of one); the
 // four partial accumulator sets meet in LDS in wave order and wave w finishes M-tile w as before.  For the deep stages of small batches:
 // a (1,1) wave tile walks 432 dependent-latency-bound MFMAs alone, a quarter of the K walk with three or four tiles is half of that.
-template <int KS, int STRIDE, int MODE, int MW, int NW, int NP, bool DSF = false, bool W8 = false, bool KSW = false>
+// M16 (NP = 2, KS = 3, stride 1, no riding conv, no K split): the K loop multiplies on v_mfma_f32_16x16x32_f16.  MW and NW then count
+// 16-row M-sub-tiles and 16-column N-sub-tiles of the wave: M is padded to 16 rows instead of 32 — the 6 x 11 maps (66 positions) take
+// 5 x 16 = 80 rows instead of 96, the 12 x 22 strips 272 instead of 288.  A step covers TWO k-chunks (32 channels, 64 contiguous bytes of
+// a patch pixel): the A fragment of a sub-tile is one 16-byte read at qtab[row] + toff + 16 * (lane >> 4), row = lane & 15; the B fragment
+// of N-sub-tile js is the 16-byte granule pack_conv_x2_weight wrote for k-chunk 2 c + (kg >> 1), lane slot (kg & 1) * 32 + 16 * js + n
+// (n = lane & 15, kg = lane >> 4): no packing of its own.  Same terms (a1 w0, a0 w1, a0 w0), steps tap-major with the k-chunks inside.
+// Stager, tables and the statistics slots are the 32-row form's; conv_x3_plan picks the flavour from the launch geometry alone.
+template <int KS, int STRIDE, int MODE, int MW, int NW, int NP, bool DSF = false, bool W8 = false, bool KSW = false, bool M16 = false>
 __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(W8 ? 2 : x3_wpe(MW, NW, NP, DSF), W8 ? 2 : x3_wpe(MW, NW, NP, DSF)))) void conv_x3_kernel(const ConvX3Args p) {
   constexpr int NTH = W8 ? 512 : 256, NWV = NTH / 64;
   constexpr int EMW = KSW ? 1 : MW;                 // M-tiles a wave finishes in the epilogue
+  constexpr int NWT = M16 ? NW / 2 : NW;            // 32-column N-tiles of the wave
+  constexpr int TW = M16 ? (MW * NW + 3) / 4 : MW * NW;   // accumulator registers of the wave in units of 16 (what the stager may use beside them)
+  static_assert(!M16 || (NP == 2 && KS == 3 && STRIDE == 1 && !DSF && !KSW && NW % 2 == 0), "16x16x32 flavour: float16-piece 3x3 stride-1 convs, whole N-tiles");
   static_assert(!KSW || (NW == 1 && NP == 2 && KS == 3 && !DSF && !W8), "K split over the waves: float16-piece 3x3 convs, one N-tile");
   static_assert(!DSF || (KS == 3 && STRIDE == 2 && NP == 2 && (MODE == 0 || MODE == 2)), "the downsample rides on a float16-piece 3x3 stride-2 conv");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -132,7 +142,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 
   const int wn = p.wn;                                                   // wave grid: (NWV / wn) x wn
   const int wave_m = wave / wn;
-  const int wave_n = (wave & (wn - 1)) + (int)blockIdx.y * wn;            // blockIdx.y = group of wn * NW N-tiles
+  const int wave_n = (wave & (wn - 1)) + (int)blockIdx.y * wn;            // blockIdx.y = group of wn * NWT N-tiles
   const int ntt = p.COUTP >> 5, kct = p.CIN >> 4;                        // N-tiles, 16-channel k-chunks of the layer
 
   f32x16 acc[MW][NW];
@@ -142,6 +152,18 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     for (int j = 0; j < NW; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // M16: the wave rows share the tile's mt16 sub-tiles evenly, the first rows taking the larger share (strips: 9 + 8); a wave's last
+  // sub-tile may not exist (m16_last: wave-uniform), the others always do (conv_x3_plan)
+  f32x4 acc16[M16 ? MW : 1][M16 ? NW : 1];
+  const int mt16 = (npix + 15) >> 4;
+  const int m16_row = (mt16 + NWV / wn - 1) / (NWV / wn), m16_sub0 = wave_m * m16_row;
+  const bool m16_last = m16_sub0 + MW <= mt16 && MW <= m16_row;
+  if (M16) {
+#pragma unroll
+    for (int i = 0; i < MW; ++i)
+#pragma unroll
+      for (int j = 0; j < NW; ++j) acc16[M16 ? i : 0][M16 ? j : 0] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   f32x16 accd[DSF ? MW : 1][DSF ? NW : 1];                               // DSF: the downsample conv's accumulators
   if (DSF) {
 #pragma unroll
@@ -300,9 +322,9 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
           *reinterpret_cast<u32x4 *>(lds + 2 * plane + r.off[k]) = o2;
         }
       };
-      constexpr bool PIPE = !((MODE == 2 && (MW * NW >= 6 || x3_wpe(MW, NW, NP) == 3 || DSF)) || (DSF && MW * NW == 4));   // (the block-tail stager of the 96-accumulator tile /
+      constexpr bool PIPE = !((MODE == 2 && (TW >= 6 || (M16 && !W8) || x3_wpe(MW, NW, NP) == 3 || DSF)) || (DSF && MW * NW == 4));   // (the block-tail stager of the 96-accumulator tile /
                                                                                          //  of the 168-register small tiles would spill)
-      if (MW * NW <= 2 && !(MODE == 2 && (x3_wpe(MW, NW, NP) == 3 || DSF))) {
+      if (TW <= 2 && !(MODE == 2 && (x3_wpe(MW, NW, NP) == 3 || DSF))) {
         // few accumulators: registers for three rounds in flight — the whole patch of the 32- / 64-channel stages is ONE memory
         // latency instead of three (their staging phase is as long as their MFMA phase)
         for (int pix = pl; pix < nppix; pix += 6 * PS) {
@@ -337,6 +359,88 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 
     // ---- compute: steps s = (tap, 16-channel chunk).  B fragments (three weight pieces per N-tile) stream from L2 one
     // step ahead (two register sets); A fragments (three planes per M-tile) come from LDS at the start of the step.
+    if constexpr (M16) {
+      // ---- 16x16x32 flavour: steps s = (tap, PAIR of k-chunks); B two register sets, one step ahead; a sub-tile's A registers take the
+      // next step's fragments as soon as its MFMAs are issued.  9 * CK / 32 steps per staged chunk (odd for CK = 32: the tail below).
+      unsigned aoff[MW];
+#pragma unroll
+      for (int i = 0; i < MW; ++i) {
+        const int sub = min(m16_sub0 + i, mt16 - 1);
+        aoff[i] = qtab[sub * 16 + (lane & 15)] + (unsigned)((lane >> 4) * 16);
+      }
+      const int kcc = CK >> 4, kcp = CK >> 5;                            // k-chunks / k-chunk pairs per staged chunk
+      const int nsteps = KS * KS * kcp;
+      const unsigned kstep = (unsigned)ntt * (NP * 1024u);               // bytes of one k-chunk of B (all N-tiles, both pieces)
+      const char *wb_n = reinterpret_cast<const char *>(g_wpk) + (long)(ck0 >> 4) * kstep;
+      unsigned toff_n = 0;
+      int kc_n = 0, kw_n = 0;
+      auto advance = [&]() {                                             // the step being fetched, as running offsets
+        ++kc_n;
+        toff_n += 64;
+        wb_n += 2 * kstep;
+        if (kc_n == kcp) {
+          kc_n = 0;
+          toff_n += (unsigned)(pitch - kcp * 64);
+          wb_n += (long)(kct - kcc) * kstep;
+          if (++kw_n == KS) {
+            kw_n = 0;
+            toff_n += (unsigned)((PC - KS) * pitch);
+          }
+        }
+      };
+      const int kg = lane >> 4;
+      unsigned voff[NW];                                                 // lane's byte offset inside a k-chunk pair of B
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+        voff[j] = (unsigned)min(wave_n * NWT + (j >> 1), ntt - 1) * (NP * 1024u) + (unsigned)(kg >> 1) * kstep +
+                  (unsigned)((kg & 1) * 32 + 16 * (j & 1) + (lane & 15)) * 16u;
+      auto loadA = [&](int i, u32x4 (*a)[MW]) {
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) a[pc][i] = *reinterpret_cast<const u32x4 *>(lds + pc * plane + aoff[i] + toff_n);
+      };
+      auto loadB = [&](u32x4 (*b)[NW]) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j)
+#pragma unroll
+          for (int pc = 0; pc < NP; ++pc) b[pc][j] = *reinterpret_cast<const u32x4 *>(wb_n + (size_t)voff[j] + pc * 1024);
+      };
+      auto step = [&](u32x4 (*a)[MW], const u32x4 (*b)[NW]) {
+#pragma unroll
+        for (int i = 0; i < MW; ++i) {
+          if (i == MW - 1 && !m16_last) break;
+          constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};             // a1 w0, a0 w1, a0 w0 per accumulator; the two N-sub-tiles of an N-tile
+#pragma unroll                                                            // interleaved: the same instruction pattern per N-tile in every wave grid
+          for (int jt = 0; jt < NWT; ++jt)
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+              for (int j = 2 * jt; j < 2 * jt + 2; ++j)
+                acc16[M16 ? i : 0][M16 ? j : 0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[TA[t]][i]), __builtin_bit_cast(f16x8, b[TB[t]][M16 ? j : 0]),
+                                                                                         acc16[M16 ? i : 0][M16 ? j : 0], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          loadA(i, a);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      u32x4 a[NP][MW], b0[NP][NW], b1[NP][NW];
+      loadB(b0);
+#pragma unroll
+      for (int i = 0; i < MW; ++i) loadA(i, a);
+      advance();                                                         // -> step 1
+#pragma unroll 1
+      for (int s = 0; s < nsteps; s += 2) {                              // entering: the trackers stand at step min(s + 1, nsteps - 1)
+        loadB(b1);
+        __builtin_amdgcn_sched_barrier(0);
+        step(a, b0);                                                     // multiplies step s, fetches A of step s + 1
+        if (s + 2 < nsteps) advance();
+        if (s + 1 < nsteps) {
+          loadB(b0);
+          __builtin_amdgcn_sched_barrier(0);
+          step(a, b1);                                                   // multiplies step s + 1, fetches A of step s + 2
+          if (s + 3 < nsteps) advance();
+        }
+      }
+    } else {
     unsigned aoff[MW];
 #pragma unroll
     for (int i = 0; i < MW; ++i) {
@@ -578,6 +682,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         }
       }
     }
+    }
     c_mm += __builtin_readcyclecounter() - t_b;
   }
   if constexpr (KSW) {
@@ -606,6 +711,44 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   // (DSF) once more for the downsample conv that rode on it: accumulators, output tensor, statistics and GroupNorm outputs of each.
   const int rr16 = lane >> 5;
   const long ybase = (((long)n * p.Ho + r0) * p.Wo + c0) * p.COUTP;
+  // t1 / t2: the wave's sums of channel nt * 32 + lane of its N-tile j over its rows, in lanes 0-31
+  auto put_stats = [&](const float *t1, const float *t2, float *stats, const float *gamma, const float *beta, float *gscale, float *gshift, float *gmu,
+                       float *grstd) {
+    if (stats != nullptr) {                                                // one slot per tile: the waves along M meet in LDS
+      const int rows = NWV / wn;
+      float *red = reinterpret_cast<float *>(lds);                        // [wave][NWT][32 channels][2]
+      if (rows > 1) {
+        __syncthreads();                                                   // the patch (the first pass's scratch) is no longer read
+        if (lane < 32)
+#pragma unroll
+          for (int j = 0; j < NWT; ++j) *reinterpret_cast<f32x2 *>(red + ((wave * NWT + j) * 32 + lane) * 2) = f32x2{t1[j], t2[j]};
+        __syncthreads();
+      }
+      if (wave_m == 0 && lane < 32) {
+#pragma unroll
+        for (int j = 0; j < NWT; ++j) {
+          const int nt = wave_n * NWT + j;
+          if (nt >= ntt) continue;
+          float s1 = t1[j], s2 = t2[j];
+          for (int w = 1; w < rows; ++w) {                                 // fixed order: bit-reproducible
+            const f32x2 o = *reinterpret_cast<const f32x2 *>(red + (((w * wn + (wave & (wn - 1))) * NWT + j) * 32 + lane) * 2);
+            s1 += o[0];
+            s2 += o[1];
+          }
+          float *dst = stats + (((long)n * p.slots + tri * p.tiles_c + tci) * p.COUTP + nt * 32 + lane) * 2;
+          dst[0] = s1;
+          dst[1] = s2;
+          if (gscale != nullptr) {                                         // the sample's only slot: finalise here (no launch)
+            const int c = nt * 32 + lane;
+            const bool first = gmu != nullptr && c % p.gn_cpg == 0;
+            const long gi = (long)n * (p.COUTP / p.gn_cpg) + c / p.gn_cpg;
+            gn_finalize_lane(s1, s2, p.gn_cpg, p.gn_P, p.gn_eps, gamma[c], beta[c], gscale + (long)n * p.COUTP + c,
+                             gshift + (long)n * p.COUTP + c, first ? gmu + gi : nullptr, first ? grstd + gi : nullptr);
+          }
+        }
+      }
+    }
+  };
   auto emit = [&](f32x16 (*ac)[NW], float *yout, float *stats, const float *oscale_ptr, float oscale, const float *gamma, const float *beta,
                   float *gscale, float *gshift, float *gmu, float *grstd, bool again) {
     if (NP == 2) {                                                         // undo the weights' power-of-two scale (exact)
@@ -660,42 +803,55 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         t2[j] += s2 + __shfl_xor(s2, 32);
       }
     }
-    if (stats != nullptr) {                                                // one slot per tile: the waves along M meet in LDS
-      const int rows = NWV / wn;
-      float *red = reinterpret_cast<float *>(lds);                        // [wave][NW][32 channels][2]
-      if (rows > 1) {
-        __syncthreads();                                                   // the patch (the first pass's scratch) is no longer read
-        if (lane < 32)
-#pragma unroll
-          for (int j = 0; j < NW; ++j) *reinterpret_cast<f32x2 *>(red + ((wave * NW + j) * 32 + lane) * 2) = f32x2{t1[j], t2[j]};
-        __syncthreads();
-      }
-      if (wave_m == 0 && lane < 32) {
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-          const int nt = wave_n * NW + j;
-          if (nt >= ntt) continue;
-          float s1 = t1[j], s2 = t2[j];
-          for (int w = 1; w < rows; ++w) {                                 // fixed order: bit-reproducible
-            const f32x2 o = *reinterpret_cast<const f32x2 *>(red + (((w * wn + (wave & (wn - 1))) * NW + j) * 32 + lane) * 2);
-            s1 += o[0];
-            s2 += o[1];
-          }
-          float *dst = stats + (((long)n * p.slots + tri * p.tiles_c + tci) * p.COUTP + nt * 32 + lane) * 2;
-          dst[0] = s1;
-          dst[1] = s2;
-          if (gscale != nullptr) {                                         // the sample's only slot: finalise here (no launch)
-            const int c = nt * 32 + lane;
-            const bool first = gmu != nullptr && c % p.gn_cpg == 0;
-            const long gi = (long)n * (p.COUTP / p.gn_cpg) + c / p.gn_cpg;
-            gn_finalize_lane(s1, s2, p.gn_cpg, p.gn_P, p.gn_eps, gamma[c], beta[c], gscale + (long)n * p.COUTP + c,
-                             gshift + (long)n * p.COUTP + c, first ? gmu + gi : nullptr, first ? grstd + gi : nullptr);
-          }
-        }
-      }
-    }
+    put_stats(t1, t2, stats, gamma, beta, gscale, gshift, gmu, grstd);
     (void)again;
   };
+  if constexpr (M16) {
+    // 16 x 16 accumulators: column lane & 15, rows 4 * (lane >> 4) + r.  A channel's partial sums sit in the four lane groups: added in one
+    // fixed order (+16, then +32), sub-tiles in order; lanes 0-31 then hold the channels of each N-tile as the 32-row form's do.
+    const float os = (p.oscale_ptr != nullptr ? *p.oscale_ptr : g_oscale) * in_div;
+    float t1[NWT], t2[NWT];
+#pragma unroll
+    for (int j = 0; j < NWT; ++j) t1[j] = t2[j] = 0.f;
+    const bool upper = (lane & 16) != 0;                                   // lanes 16-31 keep the N-tile's upper 16 channels
+#pragma unroll
+    for (int i = 0; i < MW; ++i) {
+      const int sub = m16_sub0 + i;
+      if (sub >= mt16 || (i == MW - 1 && !m16_last)) continue;
+      const u32x4 ent = *reinterpret_cast<const u32x4 *>(otab + sub * 16 + 4 * (lane >> 4));
+      const bool whole = !__any((int)((ent[0] | ent[1] | ent[2] | ent[3]) >> 31));   // wave-uniform
+      // stores of N-sub-tile j; the channel's sums over the sub-tile's 16 rows, in every lane group
+      // (no a*b+c contraction of the scale into the sums: the wave grids must round alike, and the compiler decides per instantiation)
+      auto sub_tile = [&](int j, float &s1, float &s2) {
+#pragma clang fp contract(off)
+        const int co = (wave_n * NWT + (j >> 1)) * 32 + 16 * (j & 1) + (lane & 15);
+        s1 = s2 = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned e = ent[r];
+          const bool ok = whole || (int)e >= 0;
+          const float v = ok ? acc16[M16 ? i : 0][M16 ? j : 0][r] * os : 0.f;
+          if (ok) (p.y + ybase + co)[e] = v;
+          s1 += v;
+          s2 = __builtin_fmaf(v, v, s2);
+        }
+        s1 += __shfl_xor(s1, 16);
+        s2 += __shfl_xor(s2, 16);
+        s1 += __shfl_xor(s1, 32);
+        s2 += __shfl_xor(s2, 32);
+      };
+#pragma unroll
+      for (int j = 0; j < NWT; ++j) {
+        if (wave_n * NWT + j >= ntt) continue;
+        float a1, a2, b1, b2;
+        sub_tile(2 * j, a1, a2);
+        sub_tile(2 * j + 1, b1, b2);
+        t1[j] += upper ? b1 : a1;                                          // sub-tiles of this wave, in order
+        t2[j] += upper ? b2 : a2;
+      }
+    }
+    put_stats(t1, t2, p.stats, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd);
+  } else
   emit(acc, p.y, p.stats, p.oscale_ptr, g_oscale, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd, false);
   if constexpr (DSF) emit(accd, p.ds_y, p.ds_stats, p.ds_oscale_ptr, g_ds_oscale, g_ds_gamma, g_ds_beta, p.ds_scale, p.ds_shift, p.ds_mu, p.ds_rstd, true);
   if (p.prof && lane == 0 && blockIdx.x == 13 && blockIdx.y == 0) {
@@ -1113,6 +1269,24 @@ hipError_t launch_ks(const ConvX3Args &a, int mode, int mw, int nw, dim3 grid, s
       return hipErrorInvalidValue;
     }
   }
+  if constexpr (KS == 3 && STRIDE == 1 && NP == 2) if (a.m16) {          // 16x16x32 flavour: (mw, nw) are the plan's 32-row / 32-column counts
+#define PNVO_X3M(MODE_)                                                                                                                   \
+  if (mode == MODE_ && a.w8 && mw == 3 && nw == 1) {                                                                                     \
+    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 5, 2, NP, false, true, false, true>), grid, dim3(512), ldsb, s, a);             \
+    return hipGetLastError();                                                                                                            \
+  }                                                                                                                                      \
+  if (mode == MODE_ && !a.w8 && mw == 3 && nw == 2) {                                                                                    \
+    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 5, 4, NP, false, false, false, true>), grid, dim3(256), ldsb, s, a);            \
+    return hipGetLastError();                                                                                                            \
+  }                                                                                                                                      \
+  if (mode == MODE_ && !a.w8 && mw == 5 && nw == 1) {                                                                                    \
+    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 9, 2, NP, false, false, false, true>), grid, dim3(256), ldsb, s, a);            \
+    return hipGetLastError();                                                                                                            \
+  }
+    PNVO_X3M(0) PNVO_X3M(1) PNVO_X3M(2) PNVO_X3M(3)
+#undef PNVO_X3M
+    return hipErrorInvalidValue;
+  }
   PNVO_X3(0, 1, 1) PNVO_X3(1, 1, 1) PNVO_X3(0, 2, 1) PNVO_X3(1, 2, 1) PNVO_X3(0, 2, 2) PNVO_X3(1, 2, 2) PNVO_X3(0, 3, 2) PNVO_X3(1, 3, 2)      // what conv_x3_plan picks
   PNVO_X3(2, 1, 1) PNVO_X3(2, 2, 1) PNVO_X3(2, 2, 2) PNVO_X3(2, 3, 2) PNVO_X3(3, 1, 1) PNVO_X3(3, 2, 1) PNVO_X3(3, 2, 2) PNVO_X3(3, 3, 2)
 
@@ -1194,6 +1368,7 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
   if (!((ks == 3 && (stride == 1 || stride == 2)) || (ks == 1 && stride == 2))) return false;
   a.w8 = 0;
   a.ksw = 0;
+  a.m16 = 0;
   const int ntt = a.COUTP / 32;
   // Operand bandwidth decides the wave tile: per wave and cycle the MFMAs want 16/NW bytes of A (LDS, 128 B/clk per CU) and
   // 16/MW bytes of B (L1, 64 B/clk per CU) at full rate, eight waves per CU.  (MW, NW) = (3, 2) keeps both under their limits
@@ -1312,6 +1487,18 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
     }
   }
   if (!a.ksw && ((a.w8 ? 8 : 4) / a.wn) * *mw < a.MT) return false;
+  // 16x16x32 flavour (option x3_m16), from the launch geometry alone — not from the stager mode, the kind of forward or x3_w8 — on the
+  // launches whose K loop is bound by the MFMA count: M padded to 16 rows instead of 32.
+  //   one tile per sample, 256 -> 256 channels, from 200 tiles on (the 6 x 11 maps: 66 positions = 5 sub-tiles instead of 3 M-tiles):
+  //     eight waves of 5 x 2 sub-tiles, or (x3_w8=off) four waves of 5 x 4 — the same MFMA chain per output in both;
+  //   strips of 17 or 18 sub-tiles (the 12 x 22 map whole: 264 positions), 128 -> 128 channels: wave rows of 9 and 8 sub-tiles x 2.
+  {
+    const int mt16 = (TR * TC + 15) / 16;
+    const long ntiles = (long)a.B * a.tiles_r * a.tiles_c;
+    const bool one_tile = !fine && !strip && ntiles >= 200 && a.MT == 3 && mt16 == 5 && ntt == 8 && a.CIN == 256 && *mw == 3 && (a.w8 ? *nw == 1 : (*nw == 2 && a.wn == 4));
+    const bool strip16 = strip && *mw == 5 && a.CIN == 128 && (mt16 == 17 || mt16 == 18);
+    if (a.m16_ok && a.np == 2 && ks == 3 && stride == 1 && (one_tile || strip16)) a.m16 = 1;
+  }
   // channel chunk: the largest multiple-of-32 divisor of CIN (power-of-two steps) whose three planes fit 72 KB
   // (a power of two: the stager's thread -> (pixel, 8-channel group) split uses masks; 32 always divides CIN)
   const size_t np = a.np == 2 ? 2 : 3;                          // operand pieces = LDS planes (tiles are sized for three: same plan)

@@ -269,6 +269,7 @@ void x3_fill(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa) {
   xa.strip = m->opt.x3_strip;
   xa.fine = m->opt.x3_fine;
   xa.w8_ok = m->opt.x3_w8;
+  xa.m16_ok = m->opt.x3_m16;
   xa.ksw_ok = m->opt.x3_ksplit;
   xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
   xa.np = x3_two_pieces(m, l) ? 2 : 3;
@@ -1058,6 +1059,7 @@ const OptDef kOptions[] = {
     {"x3_strip", "PNVO_X3_STRIP", &PnvoOptions::x3_strip, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_fine", "PNVO_X3_FINE", &PnvoOptions::x3_fine, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_w8", "PNVO_X3_W8", &PnvoOptions::x3_w8, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
+    {"x3_m16", "PNVO_X3_M16", &PnvoOptions::x3_m16, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_ksplit", "PNVO_X3_KSPLIT", &PnvoOptions::x3_ksplit, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"fc_rows", "PNVO_FC_ROWS", &PnvoOptions::fc_rows, true, {{nullptr, 0}}},
     {"head_fuse", "PNVO_HEAD_FUSE", &PnvoOptions::head_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
@@ -2405,9 +2407,10 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
     }
     if (x3_layer(h, l) && l.groups > 0 && x3_args(h, l, B, xa, &mw, &nw, &ldsb)) {
       std::snprintf(family, cap, xa.np == 2 ? "x2" : "x3");
-      // tiles x M-tiles x 32 pixels x padded outputs x K, six bf16 (x3) or three float16 (x2) MFMA terms per float32 product
+      // tiles x M-tiles x 32 pixels (the 16x16x32 flavour of x2: 16-row sub-tiles x 16) x padded outputs x K, six bf16 (x3) or three float16 (x2) MFMA terms per float32 product
+      const double rows = xa.m16 ? ((xa.TR * xa.TC + 15) / 16) * 16.0 : xa.MT * 32.0;
       if (executed_flops)
-        *executed_flops = (xa.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * xa.tiles_r * xa.tiles_c * xa.MT * 32.0 * l.coutp * (double)l.cinp * l.k * l.kw;
+        *executed_flops = (xa.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * xa.tiles_r * xa.tiles_c * rows * l.coutp * (double)l.cinp * l.k * l.kw;
       return PNVO_OK;
     }
     std::snprintf(family, cap, "%s", layer_on_lds(h, l, nullptr) ? "fp32-lds" : "fp32-generic");
