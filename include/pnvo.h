@@ -658,6 +658,16 @@ int pnvo_check_inputs(pnvo_handle h);
  * channel padding and the six-term expansion included): what bench.py prices against the peak of that pipe. */
 int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size_t cap, double *executed_flops);
 
+/* Host only (no device, no handle): what the conv_x3 planner decides for one problem, as one line in buf —
+ *   "<family> <instance key> | grid <x>x<y> block <threads> lds <bytes> | <tile geometry> slots <n> mrows <n>"   tile, persistent
+ *   "rows mode<m> | grid <x> block <threads> lds <bytes> | bands <n> rows <n> slots <n>"                          the row-streaming form
+ *   "none"                                                                                                        conv_x3.hip leaves the launch
+ * problem: n = 23 ints — B, H, W, CIN, Ho, Wo, COUTP (padded channels), kernel size, stride, operand pieces (2 / 3), stager mode
+ * (0-3), tail skip with its own scale, gradient input with an absolute-maximum record, riding downsample conv (0 / 1 each), then the
+ * plan options force, strip, fine, w8, m16, ksplit, persistent workgroups, rows (options conv=x3, x3_strip ... x3_rows) and the CU count.
+ * problem == NULL: the instance key of row n of the table of instantiated kernels, PNVO_ERR_ARG past its last row. */
+int pnvo_conv_x3_describe(const int *problem, int n, char *buf, size_t cap);
+
 int pnvo_timing_mode(pnvo_handle h, int mode);
 int pnvo_timing_read(pnvo_handle h, pnvo_kernel_time *entries, int cap, int *n_out);
 

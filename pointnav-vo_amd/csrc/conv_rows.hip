@@ -417,23 +417,31 @@ __global__ __launch_bounds__(RS_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 
 // Does the row-streaming kernel take this launch?  32 -> 32 channels, two float16 pieces, rows short enough for the ring
 // (a tile's taps reach P + 1 positions back and ahead: P + 1 <= 128), and enough bands to occupy the chip.
-bool conv_rows32_plan(ConvX3Args &a, int ks, int stride, int mode, int num_cus) {
-  if (ks != 3 || stride != 1 || a.np != 2 || a.CIN != 32 || a.COUTP != 32 || a.in_absmax != nullptr) return false;
-  if (mode < 0 || mode > 3 || (mode == 2 && a.res_scale != nullptr)) return false;      // (a downsample skip branch: 32 -> 32 stride-1 blocks have none)
-  if (a.Ho != a.H || a.Wo != a.W || a.W + 3 > RS_HG || a.W < 8 || a.H < 8 || (long)a.B * a.H * a.W * 128 >= (1L << 31)) return false;
+bool conv_rows32_candidate(const ConvX3Problem &q, ConvX3Plan &p) {
+  const int num_cus = q.opt.num_cus;
+  if (!q.opt.rows || q.ks != 3 || q.stride != 1 || q.np != 2 || q.CIN != 32 || q.COUTP != 32 || q.absmax) return false;
+  if (q.mode < 0 || q.mode > 3 || (q.mode == 2 && q.tail_scaled)) return false;      // (a downsample skip branch: 32 -> 32 stride-1 blocks have none)
+  if (q.Ho != q.H || q.Wo != q.W || q.W + 3 > RS_HG || q.W < 8 || q.H < 8 || (long)q.B * q.H * q.W * 128 >= (1L << 31)) return false;
   // bands: whole samples from one per CU on (one wave of items); below that 2 or 4 bands of >= 12 rows (a band re-reads two halo rows:
   // narrower ones measured slower than the tile kernels); fewer items than CUs: the tile kernels spread better
   int bands = 1;
-  while ((long)a.B * bands < num_cus && bands < 4 && a.H / (bands * 2) >= 12) bands *= 2;
-  if ((long)a.B * bands < num_cus) return false;
-  if (const char *e = std::getenv("PNVO_ROWS_DBG")) a.rs_dbg = std::atoi(e);
-  a.rs_rows = (a.H + bands - 1) / bands;
-  a.rs_bands = (a.H + a.rs_rows - 1) / a.rs_rows;
-  a.slots = a.rs_bands;
+  while ((long)q.B * bands < num_cus && bands < 4 && q.H / (bands * 2) >= 12) bands *= 2;
+  if ((long)q.B * bands < num_cus) return false;
+  p = ConvX3Plan{};
+  p.family = ConvX3Plan::ROWS;
+  p.mode = q.mode;
+  p.np = 2;
+  p.rs_rows = (q.H + bands - 1) / bands;
+  p.rs_bands = (q.H + p.rs_rows - 1) / p.rs_rows;
+  p.slots = p.rs_bands;
+  const long items = (long)q.B * p.rs_bands;
+  p.grid_x = (unsigned)(items < num_cus ? items : num_cus);
+  p.block = RS_THREADS;
+  p.lds_bytes = RS_LDS;
   return true;
 }
 
-hipError_t launch_conv_rows32(const ConvX3Args &a, int mode, int num_cus, hipStream_t s) {
+hipError_t launch_conv_rows32(const ConvX3Args &a, const ConvX3Plan &p, hipStream_t s) {
   static std::mutex attr_mu;
   static unsigned long long attr_seen = 0;
   if (pnvo_first_launch_on_device(attr_mu, attr_seen)) {
@@ -446,10 +454,11 @@ hipError_t launch_conv_rows32(const ConvX3Args &a, int mode, int num_cus, hipStr
       e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_rows32_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
     if (e != hipSuccess) return e;
   }
-  const long items = (long)a.B * a.rs_bands;
-  const unsigned gx = (unsigned)(items < num_cus ? items : num_cus);
+  const unsigned gx = p.grid_x;
+  const int mode = p.mode;
   ConvX3Args q = a;
 #if PNVO_ROWS_ABL
+  if (const char *e = std::getenv("PNVO_ROWS_DBG")) q.rs_dbg = std::atoi(e);
   static unsigned long long *prof = nullptr;             // PNVO_ROWS_PROF=1: role cycles of the waves of item 7, printed per launch (syncs)
   if (std::getenv("PNVO_ROWS_PROF") != nullptr) {
     if (!prof && hipMalloc((void **)&prof, 8 * 8 * 8) != hipSuccess) return hipErrorOutOfMemory;

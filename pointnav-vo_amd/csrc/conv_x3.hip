@@ -1239,137 +1239,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BRES ? 2 : 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Every instantiated conv_x3_kernel / conv_x3p_kernel flavour, one row each: conv_x3_plan looks the instance of its plan up here (no
+// row: no plan), launch_conv_x3 launches the row the plan names.
 namespace {
-template <int KS, int STRIDE, int NP>
-hipError_t launch_ks(const ConvX3Args &a, int mode, int mw, int nw, dim3 grid, size_t ldsb, hipStream_t s) {
-#define PNVO_X3(MODE_, MW_, NW_)                                                                          \
-  if (mode == MODE_ && mw == MW_ && nw == NW_) {                                                          \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, MW_, NW_, NP>), grid, dim3(256), ldsb, s, a);   \
-    return hipGetLastError();                                                                             \
-  }
-  if constexpr (KS == 3 && STRIDE == 2 && NP == 2) {
-    if (a.ds_wpk != nullptr) {                                           // the block's downsample conv rides on this launch (DSF)
-#define PNVO_X3D(MODE_, MW_, NW_)                                                                               \
-  if (mode == MODE_ && mw == MW_ && nw == NW_) {                                                                \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, MW_, NW_, NP, true>), grid, dim3(256), ldsb, s, a);   \
-    return hipGetLastError();                                                                                   \
-  }
-      if (a.w8) {                                                         // eight waves: the 256-channel head on 6 x 11 maps
-#define PNVO_X3DW(MODE_)                                                                                                  \
-  if (mode == MODE_ && mw == 3 && nw == 1) {                                                                             \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 3, 1, NP, true, true>), grid, dim3(512), ldsb, s, a);          \
-    return hipGetLastError();                                                                                            \
-  }
-        PNVO_X3DW(0) PNVO_X3DW(2)
-#undef PNVO_X3DW
-        return hipErrorInvalidValue;
-      }
-      PNVO_X3D(0, 1, 1) PNVO_X3D(2, 1, 1) PNVO_X3D(0, 2, 1) PNVO_X3D(2, 2, 1) PNVO_X3D(0, 2, 2) PNVO_X3D(2, 2, 2) PNVO_X3D(0, 3, 2) PNVO_X3D(2, 3, 2)
-#undef PNVO_X3D
-      return hipErrorInvalidValue;
-    }
-  }
-  if constexpr (KS == 3 && STRIDE == 1 && NP == 2) if (a.m16) {          // 16x16x32 flavour: (mw, nw) are the plan's 32-row / 32-column counts
-#define PNVO_X3M(MODE_)                                                                                                                   \
-  if (mode == MODE_ && a.w8 && mw == 3 && nw == 1) {                                                                                     \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 5, 2, NP, false, true, false, true>), grid, dim3(512), ldsb, s, a);             \
-    return hipGetLastError();                                                                                                            \
-  }                                                                                                                                      \
-  if (mode == MODE_ && !a.w8 && mw == 3 && nw == 2) {                                                                                    \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 5, 4, NP, false, false, false, true>), grid, dim3(256), ldsb, s, a);            \
-    return hipGetLastError();                                                                                                            \
-  }                                                                                                                                      \
-  if (mode == MODE_ && !a.w8 && mw == 5 && nw == 1) {                                                                                    \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 9, 2, NP, false, false, false, true>), grid, dim3(256), ldsb, s, a);            \
-    return hipGetLastError();                                                                                                            \
-  }
-    PNVO_X3M(0) PNVO_X3M(1) PNVO_X3M(2) PNVO_X3M(3)
-#undef PNVO_X3M
-    return hipErrorInvalidValue;
-  }
-  PNVO_X3(0, 1, 1) PNVO_X3(1, 1, 1) PNVO_X3(0, 2, 1) PNVO_X3(1, 2, 1) PNVO_X3(0, 2, 2) PNVO_X3(1, 2, 2) PNVO_X3(0, 3, 2) PNVO_X3(1, 3, 2)      // what conv_x3_plan picks
-  PNVO_X3(2, 1, 1) PNVO_X3(2, 2, 1) PNVO_X3(2, 2, 2) PNVO_X3(2, 3, 2) PNVO_X3(3, 1, 1) PNVO_X3(3, 2, 1) PNVO_X3(3, 2, 2) PNVO_X3(3, 3, 2)
-
-  if (KS == 3 && STRIDE == 1 && NP == 2) {                                                      // wide strips (conv_x3_plan)
-    PNVO_X3(0, 5, 1) PNVO_X3(1, 5, 1) PNVO_X3(2, 5, 1) PNVO_X3(3, 5, 1)   // (mode 3 on a strip plan: a 128-channel first block)
-    if constexpr (KS == 3 && STRIDE == 1 && NP == 2) if (a.ksw) {          // fine plan, K split over the waves (three / four M-tiles)
-#define PNVO_X3K(MODE_, MW_)                                                                                             \
-  if (mode == MODE_ && mw == MW_ && nw == 1) {                                                                          \
-    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, MW_, 1, NP, false, false, true>), grid, dim3(256), ldsb, s, a); \
-    return hipGetLastError();                                                                                           \
-  }
-      PNVO_X3K(0, 3) PNVO_X3K(1, 3) PNVO_X3K(2, 3) PNVO_X3K(0, 4) PNVO_X3K(1, 4) PNVO_X3K(2, 4)
-#undef PNVO_X3K
-      return hipErrorInvalidValue;
-    }
-  }
-  if constexpr (KS == 3 && NP == 2) if (a.w8) {          // eight waves: the 256-channel 6 x 11 maps
-#define PNVO_X3W(MODE_)                                                                                                  \
-  if (mode == MODE_ && mw == 3 && nw == 1) {                                                                            \
-  hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE_, 3, 1, NP, false, true>), grid, dim3(512), ldsb, s, a);        \
-  return hipGetLastError();                                                                                           \
-  }
-    PNVO_X3W(0) PNVO_X3W(1) PNVO_X3W(2) PNVO_X3W(3)
-#undef PNVO_X3W
-    return hipErrorInvalidValue;
-  }
-#undef PNVO_X3
-  return hipErrorInvalidValue;
+struct X3Key {
+  int P, KS, STRIDE, NP, MODE, MW, NW, DSF, W8, KSW, M16;              // P: conv_x3p_kernel<MODE, MW, NW, true> (resident weights)
+  bool operator==(const X3Key &o) const { return std::memcmp(this, &o, sizeof(X3Key)) == 0; }
+};
+struct X3Instance {
+  X3Key key;
+  int threads;
+  hipError_t (*launch)(const ConvX3Args &a, dim3 grid, size_t lds_bytes, hipStream_t s);
+};
+template <int P, int KS, int STRIDE, int NP, int MODE, int MW, int NW, bool DSF, bool W8, bool KSW, bool M16>
+hipError_t x3_launch(const ConvX3Args &a, dim3 grid, size_t lds_bytes, hipStream_t s) {
+  if constexpr (P != 0)
+    hipLaunchKernelGGL((conv_x3p_kernel<MODE, MW, NW, true>), grid, dim3(256), lds_bytes, s, a);
+  else
+    hipLaunchKernelGGL((conv_x3_kernel<KS, STRIDE, MODE, MW, NW, NP, DSF, W8, KSW, M16>), grid, dim3(W8 ? 512 : 256), lds_bytes, s, a);
+  return hipGetLastError();
 }
-}  // namespace
-
-// Fills the plan fields of `a` from its shape fields; false: the layer is outside what the kernel covers.
-namespace {
-bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *lds_bytes, bool fine);
-long plan_wgs(const ConvX3Args &a, int nw) {
-  const int ntt = a.COUTP / 32;
-  return (long)a.B * a.tiles_r * a.tiles_c * ((ntt + a.wn * nw - 1) / (a.wn * nw));
-}
-}  // namespace
-
-// The plan of a launch.  Round 6: when the regular plan would give the launch fewer than 224 workgroups (small batches: the deep
-// stages have one or two tiles per sample) a FINE plan is tried — one N-tile per workgroup (blockIdx.y = N-tile), the four waves
-// along M, no strips — which multiplies the workgroups by the layer's N-tiles at the price of staging the patch once per N-tile
-// (L2 serves it).  It keeps the deep stages of 8-48-pair batches on the float16 matrix pipe, with block tails, riding
-// downsample convs and in-kernel GroupNorm finalisation, where they used to fall back to the fp32-pipe kernels plus separate
-// residual / normalisation passes (option x3_fine; same MFMA order per output: bit-identical raw outputs to the regular plan).
-bool conv_x3_plan(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *lds_bytes) {
-  ConvX3Args reg = a;
-  int rmw = 0, rnw = 0;
-  size_t rlds = 0;
-  const int force0 = a.force;
-  reg.force = 1;                                                       // (the regular plan's shape, whatever its size)
-  const bool reg_ok = conv_x3_plan_impl(reg, ks, stride, &rmw, &rnw, &rlds, false);
-  const long reg_wgs = reg_ok ? plan_wgs(reg, rnw) : 0;
-  const int ntt = a.COUTP / 32;
-  if (a.fine && a.np == 2 && ntt >= 2 && (!reg_ok || reg_wgs < 224)) {   // (224 measured best)
-    ConvX3Args f = a;
-    int fmw = 0, fnw = 0;
-    size_t flds = 0;
-    f.force = 1;
-    if (conv_x3_plan_impl(f, ks, stride, &fmw, &fnw, &flds, true)) {
-      const long fw = plan_wgs(f, fnw);
-      if (fw > reg_wgs && (fw >= 48 || force0)) {
-        f.force = force0;
-        a = f;
-        *mw = fmw;
-        *nw = fnw;
-        *lds_bytes = flds;
-        return true;
-      }
-    }
-  }
-  return conv_x3_plan_impl(a, ks, stride, mw, nw, lds_bytes, false);
+#define X3I(P, KS, ST, NP, MODE, MW, NW, DSF, W8, KSW, M16) \
+  {{P, KS, ST, NP, MODE, MW, NW, DSF, W8, KSW, M16}, (W8) ? 512 : 256, x3_launch<P, KS, ST, NP, MODE, MW, NW, DSF, W8, KSW, M16>},
+#define X3_MODES(KS, ST, NP, MW, NW, DSF, W8, KSW, M16)   /* stager modes 0-3 */ \
+  X3I(0, KS, ST, NP, 0, MW, NW, DSF, W8, KSW, M16) X3I(0, KS, ST, NP, 1, MW, NW, DSF, W8, KSW, M16) \
+  X3I(0, KS, ST, NP, 2, MW, NW, DSF, W8, KSW, M16) X3I(0, KS, ST, NP, 3, MW, NW, DSF, W8, KSW, M16)
+#define X3_TILES(KS, ST, NP, MODE, DSF)                   /* the four wave tiles of the regular and fine plans */ \
+  X3I(0, KS, ST, NP, MODE, 1, 1, DSF, 0, 0, 0) X3I(0, KS, ST, NP, MODE, 2, 1, DSF, 0, 0, 0) \
+  X3I(0, KS, ST, NP, MODE, 2, 2, DSF, 0, 0, 0) X3I(0, KS, ST, NP, MODE, 3, 2, DSF, 0, 0, 0)
+// (the (5, 1) strip tile is planned for 3x3 stride-1 two-piece launches only; it has always been instantiated for every (KS, STRIDE, NP))
+#define X3_GENERAL(KS, ST, NP) \
+  X3_TILES(KS, ST, NP, 0, 0) X3_TILES(KS, ST, NP, 1, 0) X3_TILES(KS, ST, NP, 2, 0) X3_TILES(KS, ST, NP, 3, 0) X3_MODES(KS, ST, NP, 5, 1, 0, 0, 0, 0)
+const X3Instance x3_table[] = {
+  X3_GENERAL(3, 1, 2) X3_GENERAL(3, 2, 2) X3_GENERAL(1, 2, 2) X3_GENERAL(3, 1, 3) X3_GENERAL(3, 2, 3) X3_GENERAL(1, 2, 3)
+  X3_TILES(3, 2, 2, 0, 1) X3_TILES(3, 2, 2, 2, 1)                              // the block's downsample conv rides on the launch (DSF)
+  X3I(0, 3, 2, 2, 0, 3, 1, 1, 1, 0, 0) X3I(0, 3, 2, 2, 2, 3, 1, 1, 1, 0, 0)      // ... on eight waves: the 256-channel head on 6 x 11 maps
+  X3_MODES(3, 1, 2, 3, 1, 0, 1, 0, 0) X3_MODES(3, 2, 2, 3, 1, 0, 1, 0, 0)         // eight waves: the 256-channel 6 x 11 maps
+  X3_MODES(3, 1, 2, 5, 2, 0, 1, 0, 1) X3_MODES(3, 1, 2, 5, 4, 0, 0, 0, 1) X3_MODES(3, 1, 2, 9, 2, 0, 0, 0, 1)   // 16x16x32 flavour: the 32-row plans (3,1) W8, (3,2), (5,1)
+  X3I(0, 3, 1, 2, 0, 3, 1, 0, 0, 1, 0) X3I(0, 3, 1, 2, 1, 3, 1, 0, 0, 1, 0) X3I(0, 3, 1, 2, 2, 3, 1, 0, 0, 1, 0)   // fine plan, K split over the waves (three / four M-tiles)
+  X3I(0, 3, 1, 2, 0, 4, 1, 0, 0, 1, 0) X3I(0, 3, 1, 2, 1, 4, 1, 0, 0, 1, 0) X3I(0, 3, 1, 2, 2, 4, 1, 0, 0, 1, 0)
+  X3I(1, 3, 1, 2, 0, 1, 1, 0, 0, 0, 0) X3I(1, 3, 1, 2, 1, 1, 1, 0, 0, 0, 0) X3I(1, 3, 1, 2, 0, 2, 1, 0, 0, 0, 0) X3I(1, 3, 1, 2, 1, 2, 1, 0, 0, 0, 0)   // (resident weights, plain / GN-input modes)
+};
+#undef X3_GENERAL
+#undef X3_TILES
+#undef X3_MODES
+#undef X3I
+constexpr int x3_table_rows = (int)(sizeof(x3_table) / sizeof(x3_table[0]));
+int x3_find(const X3Key &k) {
+  for (int i = 0; i < x3_table_rows; ++i)
+    if (x3_table[i].key == k) return i;
+  return -1;
 }
 
-namespace {
-bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *lds_bytes, bool fine) {
-  if (a.CIN % 32 || a.COUTP % 32 || a.COUTP > 1024 || a.CIN > 1024) return false;
-  if (!((ks == 3 && (stride == 1 || stride == 2)) || (ks == 1 && stride == 2))) return false;
-  a.w8 = 0;
-  a.ksw = 0;
-  a.m16 = 0;
-  const int ntt = a.COUTP / 32;
+// One candidate plan of q — the regular one, or the FINE one (one N-tile per workgroup) — whatever its launch size; NONE: the layer is
+// outside what the kernel covers.  mw / nw are the 32-row form's counts until the end.
+ConvX3Plan tile_candidate(const ConvX3Problem &q, bool fine) {
+  ConvX3Plan p;
+  const int ks = q.ks, stride = q.stride;
+  int mw = 0, nw = 0;
+  if (q.CIN % 32 || q.COUTP % 32 || q.COUTP > 1024 || q.CIN > 1024) return {};
+  if (!((ks == 3 && (stride == 1 || stride == 2)) || (ks == 1 && stride == 2))) return {};
+  const int ntt = q.COUTP / 32;
+  const bool strip_shape = q.opt.strip && !fine && q.np == 2 && stride == 1 && ks == 3 && ntt == 4 && q.Wo >= 16 && q.Ho >= 8;
   // Operand bandwidth decides the wave tile: per wave and cycle the MFMAs want 16/NW bytes of A (LDS, 128 B/clk per CU) and
   // 16/MW bytes of B (L1, 64 B/clk per CU) at full rate, eight waves per CU.  (MW, NW) = (3, 2) keeps both under their limits
   // (64 and 43 B/clk); (2, 2) sits on the L1 limit, (2, 1) on both.  A layer with one N-tile cannot reuse A at all (16 B per
@@ -1378,115 +1309,115 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
   if (stride == 2 && ks == 3) {
     // the patch of a stride-2 conv is four times its output tile: the tile is what 76 KB of three-piece patch allow at 32-channel
     // chunks (PR x PC <= 324 pixels of 240 B): 4 x 16 outputs on the wide maps, else whole rows
-    TC = a.Wo >= 32 ? 16 : a.Wo;
+    TC = q.Wo >= 32 ? 16 : q.Wo;
     const int pc = 2 * TC + 1;
     TR = (324 / pc - 1) / 2;                                     // (two-piece patches would allow 486 pixels: 12 x 22 outputs in three tiles of four rows
                                                                  //  instead of four of three — measured neutral, 93.2 vs 93.8 us: that head is not MFMA-bound)
-    if (TR < 1) return false;
-    if (TR > a.Ho) TR = a.Ho;
+    if (TR < 1) return {};
+    if (TR > q.Ho) TR = q.Ho;
     while (TR > 1 && TR * TC > (ntt == 2 ? 64 : (ntt == 4 ? 128 : 96))) --TR;    // M-tiles the wave grid below covers
-  } else if (ntt == 1 && stride == 1 && ks == 3 && a.CIN > 32 && a.np == 2 && a.Wo < 32 && a.Ho * a.Wo <= 128) {
+  } else if (ntt == 1 && stride == 1 && ks == 3 && q.CIN > 32 && q.np == 2 && q.Wo < 32 && q.Ho * q.Wo <= 128) {
     // one N-tile behind MANY input channels on a small map (the compression conv, vo_cnn.py:76-101: 256 -> 31 channels on 6 x 11):
     // the whole map is one tile, the four waves along M with one M-tile each (round 6; it ran on the fp32 pipe at 60 TFLOP/s —
     // no A reuse with a single N-tile, but three float16 MFMAs per K = 16 are still five times less pipe time than eight fp32 ones)
-    TC = a.Wo;
-    TR = a.Ho;
+    TC = q.Wo;
+    TR = q.Ho;
   } else if (ntt == 1) {
     // one N-tile (32 output channels): all four waves along M, two M-tiles each -> 16 x 16 outputs (18 x 18 patch = 76 KB)
-    if (stride != 1 || ks != 3 || a.CIN != 32) return false;
-    TC = a.Wo >= 16 ? 16 : a.Wo;
+    if (stride != 1 || ks != 3 || q.CIN != 32) return {};
+    TC = q.Wo >= 16 ? 16 : q.Wo;
     TR = 256 / TC;
     while (TR > 1 && (TR + 2) * (TC + 2) > 324) --TR;
-    if (TR > a.Ho) TR = a.Ho;
-    if (TR * TC <= 96) return false;                               // (small maps: not worth it)
-  } else if (a.strip && !fine && a.np == 2 && stride == 1 && ks == 3 && ntt == 4 && a.Wo >= 16 && a.Ho >= 8) {
+    if (TR > q.Ho) TR = q.Ho;
+    if (TR * TC <= 96) return {};                               // (small maps: not worth it)
+  } else if (strip_shape) {
     // Round 4: what bounds these layers is the CU's vector-memory pipe, and most of its traffic is weight fragments — every workgroup
     // streams the layer's whole B operand for ITS pixels.  Wide strips (up to 288 pixels = nine M-tiles: the 12 x 22 map whole, the
     // 24 x 43 map in four) with the N-tiles split over blockIdx.y (two per workgroup, one per wave column, five M-tiles per wave)
     // halve the weight bytes per pixel of the 8 x 22 tiles.  Measured at 256 pairs: the 128-channel stage 0.074 -> 0.067 ms per conv;
     // the 64-channel stage (24 x 43 in four strips) 3 % SLOWER than its 8 x 16 tiles and left alone.
-    const int ncol = (a.Wo + 21) / 22;
-    TC = (a.Wo + ncol - 1) / ncol;
+    const int ncol = (q.Wo + 21) / 22;
+    TC = (q.Wo + ncol - 1) / ncol;
     TR = 288 / TC;
-    if (TR > a.Ho) TR = a.Ho;
-    const int nrow = (a.Ho + TR - 1) / TR;
-    TR = (a.Ho + nrow - 1) / nrow;
-  } else if (a.Wo >= 32) {
+    if (TR > q.Ho) TR = q.Ho;
+    const int nrow = (q.Ho + TR - 1) / TR;
+    TR = (q.Ho + nrow - 1) / nrow;
+  } else if (q.Wo >= 32) {
     TR = 8;
     TC = 16;
   } else {
-    TC = a.Wo;
+    TC = q.Wo;
     int target = ntt == 4 ? 192 : (ntt >= 8 ? 96 : 128);           // pixels per tile: six / three / four M-tiles
     // fine plan with the K split over the waves: three M-tiles per tile (12 x 22 maps: three balanced tiles of four rows instead of 8 + 4)
-    if (fine && a.ksw_ok && ks == 3 && stride == 1 && a.np == 2 && a.CIN >= 128) target = 96;
+    if (fine && q.opt.ksw && ks == 3 && stride == 1 && q.np == 2 && q.CIN >= 128) target = 96;
     TR = target / TC;
     if (TR < 1) TR = 1;
-    if (TR > a.Ho) TR = a.Ho;
+    if (TR > q.Ho) TR = q.Ho;
   }
   // (fine plan with the 12 x 22 map whole — nine M-tiles on (3,1) wave tiles, GroupNorm finalised in the kernel — was measured: three
   //  launches fewer but 32 pairs 0.626 -> 0.640 ms, and below 12 pairs its 4 B workgroups miss the threshold: not kept)
-  a.TR = TR;
-  a.TC = TC;
-  a.tiles_r = (a.Ho + TR - 1) / TR;
-  a.tiles_c = (a.Wo + TC - 1) / TC;
-  a.MT = (TR * TC + 31) / 32;
+  p.TR = TR;
+  p.TC = TC;
+  p.tiles_r = (q.Ho + TR - 1) / TR;
+  p.tiles_c = (q.Wo + TC - 1) / TC;
+  p.MT = (TR * TC + 31) / 32;
   const int cs = ks == 1 ? 1 : stride;
-  a.PR = (TR - 1) * cs + ks;
-  a.PC = (TC - 1) * cs + ks;
+  p.PR = (TR - 1) * cs + ks;
+  p.PC = (TC - 1) * cs + ks;
   // wave grid (4 / wn) x wn and accumulators per wave (accumulators + one A set + two B sets within 256 registers)
-  const bool strip = a.strip && !fine && a.np == 2 && stride == 1 && ks == 3 && ntt == 4 && a.Wo >= 16 && a.Ho >= 8 && a.MT > 6;
+  const bool strip = strip_shape && p.MT > 6;
   if (fine) {                                                      // one N-tile per workgroup, the four waves along M
-    if (a.MT > 8) return false;
-    a.wn = 1;
-    *mw = (a.MT + 3) / 4;
-    *nw = 1;
+    if (p.MT > 8) return {};
+    p.wn = 1;
+    mw = (p.MT + 3) / 4;
+    nw = 1;
     // three / four M-tiles behind many input channels (the 128- / 256-channel stages): the waves split K instead of M (KSW)
-    if (a.ksw_ok && (a.MT == 3 || a.MT == 4) && ks == 3 && stride == 1 && a.np == 2 && a.CIN >= 128) {
-      a.ksw = 1;
-      *mw = a.MT;
+    if (q.opt.ksw && (p.MT == 3 || p.MT == 4) && ks == 3 && stride == 1 && q.np == 2 && q.CIN >= 128) {
+      p.ksw = true;
+      mw = p.MT;
     }
   } else if (strip) {
-    a.wn = 2;
-    *mw = (a.MT + 1) / 2;                                          // two wave rows
-    *nw = 1;
-    if (*mw > 5) return false;
-    if (*mw < 5) *mw = 5;                                          // (one instantiation)
+    p.wn = 2;
+    mw = (p.MT + 1) / 2;                                          // two wave rows
+    nw = 1;
+    if (mw > 5) return {};
+    if (mw < 5) mw = 5;                                          // (one instantiation)
   } else if (ntt == 1) {
-    a.wn = 1;
-    *mw = a.CIN > 32 ? 1 : 2;
-    *nw = 1;
-    if (a.ksw_ok && a.CIN >= 128 && (a.MT == 3 || a.MT == 4) && ks == 3 && stride == 1 && a.np == 2) {   // the compression conv: K over the waves
-      a.ksw = 1;
-      *mw = a.MT;
+    p.wn = 1;
+    mw = q.CIN > 32 ? 1 : 2;
+    nw = 1;
+    if (q.opt.ksw && q.CIN >= 128 && (p.MT == 3 || p.MT == 4) && ks == 3 && stride == 1 && q.np == 2) {   // the compression conv: K over the waves
+      p.ksw = true;
+      mw = p.MT;
     }
   } else if (ntt == 2) {
-    a.wn = 2;
-    *mw = a.MT > 2 ? 2 : 1;
-    *nw = 1;
+    p.wn = 2;
+    mw = p.MT > 2 ? 2 : 1;
+    nw = 1;
   } else if (ntt == 4) {
-    a.wn = 2;
-    *mw = a.MT > 4 ? 3 : 2;
-    *nw = 2;
+    p.wn = 2;
+    mw = p.MT > 4 ? 3 : 2;
+    nw = 2;
   } else {
-    a.wn = 4;
-    *mw = a.MT > 2 ? 3 : 2;
-    *nw = 2;
+    p.wn = 4;
+    mw = p.MT > 2 ? 3 : 2;
+    nw = 2;
     // fewer tiles than CUs (6 x 11 maps: one tile per image; 128 pairs): four N-tiles per workgroup instead of eight doubles
     // the workgroups (measured: 9.23 -> 9.03 ms per training step at 128 pairs; at 256 tiles it costs 0.127 -> 0.170 ms per conv)
-    const long ntiles = (long)a.B * a.tiles_r * a.tiles_c;
-    if (ntiles < 200 && a.MT <= 4) {
-      a.wn = 2;
-      *mw = 2;
+    const long ntiles = (long)q.B * p.tiles_r * p.tiles_c;
+    if (ntiles < 200 && p.MT <= 4) {
+      p.wn = 2;
+      mw = 2;
     }
     // one tile per sample and a tile per CU or more: eight waves of (3,1) tiles, all eight N-tiles in one workgroup (W8)
-    if (a.w8_ok && !fine && ntiles >= 200 && a.MT == 3 && ntt == 8 && a.np == 2 && ks == 3) {   // (stride 1 and the stride-2 block head)
-      a.w8 = 1;
-      a.wn = 8;
-      *mw = 3;
-      *nw = 1;
+    if (q.opt.w8 && !fine && ntiles >= 200 && p.MT == 3 && ntt == 8 && q.np == 2 && ks == 3) {   // (stride 1 and the stride-2 block head)
+      p.w8 = true;
+      p.wn = 8;
+      mw = 3;
+      nw = 1;
     }
   }
-  if (!a.ksw && ((a.w8 ? 8 : 4) / a.wn) * *mw < a.MT) return false;
+  if (!p.ksw && ((p.w8 ? 8 : 4) / p.wn) * mw < p.MT) return {};
   // 16x16x32 flavour (option x3_m16), from the launch geometry alone — not from the stager mode, the kind of forward or x3_w8 — on the
   // launches whose K loop is bound by the MFMA count: M padded to 16 rows instead of 32.
   //   one tile per sample, 256 -> 256 channels, from 200 tiles on (the 6 x 11 maps: 66 positions = 5 sub-tiles instead of 3 M-tiles):
@@ -1494,51 +1425,125 @@ bool conv_x3_plan_impl(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size
   //   strips of 17 or 18 sub-tiles (the 12 x 22 map whole: 264 positions), 128 -> 128 channels: wave rows of 9 and 8 sub-tiles x 2.
   {
     const int mt16 = (TR * TC + 15) / 16;
-    const long ntiles = (long)a.B * a.tiles_r * a.tiles_c;
-    const bool one_tile = !fine && !strip && ntiles >= 200 && a.MT == 3 && mt16 == 5 && ntt == 8 && a.CIN == 256 && *mw == 3 && (a.w8 ? *nw == 1 : (*nw == 2 && a.wn == 4));
-    const bool strip16 = strip && *mw == 5 && a.CIN == 128 && (mt16 == 17 || mt16 == 18);
-    if (a.m16_ok && a.np == 2 && ks == 3 && stride == 1 && (one_tile || strip16)) a.m16 = 1;
+    const long ntiles = (long)q.B * p.tiles_r * p.tiles_c;
+    const bool one_tile = !fine && !strip && ntiles >= 200 && p.MT == 3 && mt16 == 5 && ntt == 8 && q.CIN == 256 && mw == 3 && (p.w8 ? nw == 1 : (nw == 2 && p.wn == 4));
+    const bool strip16 = strip && mw == 5 && q.CIN == 128 && (mt16 == 17 || mt16 == 18);
+    if (q.opt.m16 && q.np == 2 && ks == 3 && stride == 1 && (one_tile || strip16)) p.m16 = true;
   }
   // channel chunk: the largest multiple-of-32 divisor of CIN (power-of-two steps) whose three planes fit 72 KB
   // (a power of two: the stager's thread -> (pixel, 8-channel group) split uses masks; 32 always divides CIN)
-  const size_t np = a.np == 2 ? 2 : 3;                          // operand pieces = LDS planes (tiles are sized for three: same plan)
+  const size_t np = q.np == 2 ? 2 : 3;                          // operand pieces = LDS planes (tiles are sized for three: same plan)
   int ck = 32;
-  while (ck < 256 && a.CIN % (2 * ck) == 0) ck *= 2;
+  while (ck < 256 && q.CIN % (2 * ck) == 0) ck *= 2;
   // (W8 with the whole K = 256 in one 110 KB chunk — its launches are one workgroup per CU anyway: staging 14.5 k -> 7.8 k cycles per
   //  workgroup, the conv's time unchanged, 77-82 us on either form: not kept)
   const size_t cap = (size_t)72 * 1024;
-  while (ck > 32 && np * a.PR * a.PC * (ck * 2 + 16) > cap) ck /= 2;
-  if (np * a.PR * a.PC * (ck * 2 + 16) > cap + 4096) return false;
-  if (a.CIN % ck) return false;
-  a.CK = ck;
-  // Few workgroups (small batches: the reference's navigation loop calls with ONE pair): a workgroup walks its whole K loop alone
-  // (≈ 60-110 us on the deep stages) while the fp32 kernels split small problems over the chip — they keep those launches
-  // (measured: batch 1 0.41 ms against 0.72 with conv_x3 everywhere; break-even per layer at ~200 workgroups).  Option conv=x3 (a.force) takes them anyway.
-  {
-    const bool force = a.force != 0;
-    const long wgs = (long)a.B * a.tiles_r * a.tiles_c * ((ntt + a.wn * *nw - 1) / (a.wn * *nw));
-    // (break-even measured at ~200 workgroups for the six-term form; the three-term float16 form halves the K loop: batch 64
-    //  — 128 workgroups on the deep stages — 1.09 ms with it against 1.18 without, batch 32 — 64 workgroups — 0.82 against 0.78)
-    if (wgs < (a.np == 2 ? 112 : 192) && !force) return false;
-  }
-  a.slots = a.tiles_r * a.tiles_c;                               // one GroupNorm partial per tile
+  while (ck > 32 && np * p.PR * p.PC * (ck * 2 + 16) > cap) ck /= 2;
+  if (np * p.PR * p.PC * (ck * 2 + 16) > cap + 4096) return {};
+  if (q.CIN % ck) return {};
+  p.CK = ck;
+  p.slots = p.tiles_r * p.tiles_c;                               // one GroupNorm partial per tile
   // planes, pixel tables (1 KB more would cost the 64-channel convs their third workgroup per CU)
-  *lds_bytes = np * a.PR * a.PC * (ck * 2 + 16) + (size_t)a.MT * 32 * 4 * 2;
-  if (a.ksw) *lds_bytes = std::max(np * a.PR * a.PC * (ck * 2 + 16), (size_t)4 * a.MT * 4096) + (size_t)a.MT * 32 * 4 * 2;   // planes / the four waves' partial accumulator tiles, then the tables
-  return true;
+  p.lds_bytes = np * p.PR * p.PC * (ck * 2 + 16) + (size_t)p.MT * 32 * 4 * 2;
+  if (p.ksw) p.lds_bytes = std::max(np * p.PR * p.PC * (ck * 2 + 16), (size_t)4 * p.MT * 4096) + (size_t)p.MT * 32 * 4 * 2;   // planes / the four waves' partial accumulator tiles, then the tables
+  // the instance's template arguments: 16-row / 16-column counts with M16 — (3,1) on eight waves -> (5,2), (3,2) -> (5,4), (5,1) -> (9,2)
+  p.mw = p.m16 ? 2 * mw - 1 : mw;
+  p.nw = p.m16 ? 2 * nw : nw;
+  p.m_rows = p.m16 ? ((TR * TC + 15) / 16) * 16 : p.MT * 32;
+  const long ntiles = (long)q.B * p.tiles_r * p.tiles_c;
+  p.grid_x = (unsigned)(((ntiles + 7) / 8) * 8);
+  p.grid_y = (unsigned)((ntt + p.wn * nw - 1) / (p.wn * nw));         // wn * nw N-tiles per workgroup
+  p.block = p.w8 ? 512 : 256;
+  p.family = ConvX3Plan::TILE;
+  return p;
 }
 }  // namespace
 
-// Does launch_conv_x3 take the persistent resident-weight form (conv_x3p_kernel) for this planned launch?
-bool conv_x3_persistent(const ConvX3Args &a, int ks, int stride, int mode, int mw, int nw) {
-  const long ntiles = (long)a.B * a.tiles_r * a.tiles_c;
-  const int ntt = a.COUTP / 32, pwgs = a.persist_wgs;
-  const bool bres = ntt == 1 && a.CIN == 32 && nw == 1 && (mode == 0 || mode == 1);   // the layer's weights stay in registers
-  return a.np == 2 && ks == 3 && stride == 1 && bres && mw * nw <= 2 && a.CK == a.CIN && pwgs >= 8 &&
-         (long)a.PR * a.PC * (a.CK / 8) <= 6 * 256 && ntiles >= 2L * pwgs;
+// The plan of a launch: the row-streaming form where it takes the launch, else a tile plan, on the persistent kernel where that serves.
+// Round 6: when the regular plan would give the launch fewer than 224 workgroups (small batches: the deep
+// stages have one or two tiles per sample) a FINE plan is tried — one N-tile per workgroup (blockIdx.y = N-tile), the four waves
+// along M, no strips — which multiplies the workgroups by the layer's N-tiles at the price of staging the patch once per N-tile
+// (L2 serves it).  It keeps the deep stages of 8-48-pair batches on the float16 matrix pipe, with block tails, riding
+// downsample convs and in-kernel GroupNorm finalisation, where they used to fall back to the fp32-pipe kernels plus separate
+// residual / normalisation passes (option x3_fine; same MFMA order per output: bit-identical raw outputs to the regular plan).
+ConvX3Plan conv_x3_plan(const ConvX3Problem &q) {
+  ConvX3Plan none, p;
+  if (q.mode < 0 || q.mode > 3) return none;
+  if (q.ds && !(q.ks == 3 && q.stride == 2 && q.np == 2)) return none;   // only the float16-piece 3x3 stride-2 kernels carry a downsample conv
+  if (conv_rows32_candidate(q, p)) return p;
+  const auto wgs = [&](const ConvX3Plan &c) { return c ? (long)q.B * c.tiles_r * c.tiles_c * c.grid_y : 0L; };   // (before grid.x is padded to 8)
+  const ConvX3Plan reg = tile_candidate(q, false);
+  const int ntt = q.COUTP / 32;
+  if (q.opt.fine && q.np == 2 && ntt >= 2 && wgs(reg) < 224) {   // (224 measured best)
+    const ConvX3Plan fine = tile_candidate(q, true);
+    if (wgs(fine) > wgs(reg) && (wgs(fine) >= 48 || q.opt.force)) p = fine;
+  }
+  // Few workgroups (small batches: the reference's navigation loop calls with ONE pair): a workgroup walks its whole K loop alone
+  // (≈ 60-110 us on the deep stages) while the fp32 kernels split small problems over the chip — they keep those launches
+  // (measured: batch 1 0.41 ms against 0.72 with conv_x3 everywhere; break-even per layer at ~200 workgroups).  Option conv=x3 (q.opt.force) takes them anyway.
+  // (break-even measured at ~200 workgroups for the six-term form; the three-term float16 form halves the K loop: batch 64
+  //  — 128 workgroups on the deep stages — 1.09 ms with it against 1.18 without, batch 32 — 64 workgroups — 0.82 against 0.78)
+  if (!p && reg && (wgs(reg) >= (q.np == 2 ? 112 : 192) || q.opt.force)) p = reg;
+  if (!p) return none;
+  // persistent form (conv_x3p_kernel): float16 pieces, 3x3 stride 1, the whole K in one staged chunk, small wave tiles, no block
+  // tail in the stager, six patch pixels per thread at most, and enough tiles to walk
+  // (measured at 256 pairs: with the weights resident the 32 -> 32 convs go 0.107 -> 0.085 ms; the prefetching form WITHOUT resident
+  //  weights — 64-channel stage — is 9 % slower than one tile per workgroup, and the pooled-key input mode, which also writes the
+  //  pooled activations, loses more from two workgroups per CU than it gains: both stay on conv_x3_kernel)
+  const long ntiles = (long)q.B * p.tiles_r * p.tiles_c;
+  const int pwgs = q.opt.persist_wgs;
+  const bool bres = ntt == 1 && q.CIN == 32 && p.nw == 1 && (q.mode == 0 || q.mode == 1);   // the layer's weights stay in registers
+  if (q.np == 2 && q.ks == 3 && q.stride == 1 && bres && p.mw * p.nw <= 2 && p.CK == q.CIN && pwgs >= 8 &&
+      (long)p.PR * p.PC * (p.CK / 8) <= 6 * 256 && ntiles >= 2L * pwgs) {
+    p.family = ConvX3Plan::PERSISTENT;
+    p.grid_x = (unsigned)(((pwgs / 3) * 2) & ~7);                       // two workgroups per CU (256 registers per lane)
+  }
+  p.mode = q.mode;
+  p.np = q.np == 2 ? 2 : 3;
+  p.dsf = q.ds;
+  p.inst = x3_find({p.family == ConvX3Plan::PERSISTENT, q.ks, q.stride, p.np, p.mode, p.mw, p.nw, p.dsf, p.w8, p.ksw, p.m16});
+  return p.inst >= 0 ? p : none;
 }
 
-hipError_t launch_conv_x3(const ConvX3Args &a0, int ks, int stride, int mode, int mw, int nw, size_t lds_bytes, hipStream_t s) {
+ConvX3Args conv_x3_args(const ConvX3Problem &q, const ConvX3Plan &p) {
+  ConvX3Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.B = q.B; a.H = q.H; a.W = q.W; a.CIN = q.CIN; a.Ho = q.Ho; a.Wo = q.Wo; a.COUTP = q.COUTP;
+  a.TR = p.TR; a.TC = p.TC; a.tiles_r = p.tiles_r; a.tiles_c = p.tiles_c; a.PR = p.PR; a.PC = p.PC; a.CK = p.CK; a.MT = p.MT; a.wn = p.wn;
+  a.slots = p.slots; a.rs_bands = p.rs_bands; a.rs_rows = p.rs_rows;
+  return a;
+}
+
+// "<family> <instance key> | grid, block, LDS bytes | geometry and slots" of q's plan, "none" without one; q == nullptr: the key of
+// table row `row`.  Touches no HIP runtime call.
+int conv_x3_describe(const ConvX3Problem *q, int row, char *buf, size_t cap) {
+  const auto key = [&](const X3Key &k, int at) {
+    return std::snprintf(buf + at, cap - at, "%s ks%d s%d np%d mode%d mw%d nw%d dsf%d w8%d ksw%d m16%d", k.P ? "persistent" : "tile", k.KS, k.STRIDE, k.NP,
+                         k.MODE, k.MW, k.NW, k.DSF, k.W8, k.KSW, k.M16);
+  };
+  if (q == nullptr) {
+    if (row < 0 || row >= x3_table_rows) return -1;
+    key(x3_table[row].key, 0);
+    return 0;
+  }
+  const ConvX3Plan p = conv_x3_plan(*q);
+  if (!p) {
+    std::snprintf(buf, cap, "none");
+  } else if (p.family == ConvX3Plan::ROWS) {
+    std::snprintf(buf, cap, "rows mode%d | grid %u block %d lds %zu | bands %d rows %d slots %d", p.mode, p.grid_x, p.block, p.lds_bytes, p.rs_bands,
+                  p.rs_rows, p.slots);
+  } else {
+    const int at = key(x3_table[p.inst].key, 0);
+    if (at > 0 && (size_t)at < cap)
+      std::snprintf(buf + at, cap - at, " | grid %ux%u block %d lds %zu | TR %d TC %d tiles %dx%d PR %d PC %d CK %d MT %d wn %d slots %d mrows %d", p.grid_x,
+                    p.grid_y, x3_table[p.inst].threads, p.lds_bytes, p.TR, p.TC, p.tiles_r, p.tiles_c, p.PR, p.PC, p.CK, p.MT, p.wn, p.slots, p.m_rows);
+  }
+  return 0;
+}
+
+hipError_t launch_conv_x3(const ConvX3Args &a0, const ConvX3Plan &p, hipStream_t s) {
+  if (p.inst < 0 || p.inst >= x3_table_rows) return hipErrorInvalidValue;
+  const int mw = p.mw, nw = p.nw;
   ConvX3Args a = a0;
   static unsigned long long *prof = nullptr;             // PNVO_X3_PROF=1: phase cycles of workgroup 13, printed per launch (syncs)
   static const bool want = std::getenv("PNVO_X3_PROF") != nullptr;
@@ -1560,37 +1565,7 @@ hipError_t launch_conv_x3(const ConvX3Args &a0, int ks, int stride, int mode, in
                    a.MT, a.CK, mw, nw, a.wn, h[0], h[1], h[2], h[3], h[4], h[24], h[25], h[26], h[27]);
     }
   } dump{a, mw, nw, s, prof};
-  const long ntiles = (long)a.B * a.tiles_r * a.tiles_c;
-  const int ntt = a.COUTP / 32, per_wg = a.wn * nw;   // N-tiles one workgroup covers
-  dim3 grid((unsigned)(((ntiles + 7) / 8) * 8), (unsigned)((ntt + per_wg - 1) / per_wg), 1u);
-  // persistent form (conv_x3p_kernel): float16 pieces, 3x3 stride 1, the whole K in one staged chunk, small wave tiles, no block
-  // tail in the stager, six patch pixels per thread at most, and enough tiles to walk
-  const int pwgs = a.persist_wgs;
-  // (measured at 256 pairs: with the weights resident the 32 -> 32 convs go 0.107 -> 0.085 ms; the prefetching form WITHOUT resident
-  //  weights — 64-channel stage — is 9 % slower than one tile per workgroup, and the pooled-key input mode, which also writes the
-  //  pooled activations, loses more from two workgroups per CU than it gains: both stay on conv_x3_kernel)
-  if (conv_x3_persistent(a, ks, stride, mode, mw, nw)) {
-    const bool bres = true;
-    dim3 pg((unsigned)(pwgs & ~7), grid.y, 1u);
-    if (bres) pg.x = (unsigned)(((pwgs / 3) * 2) & ~7);                 // two workgroups per CU (256 registers per lane)
-#define PNVO_X3P(MODE_, MW_, NW_)                                                                        \
-  if (mode == MODE_ && mw == MW_ && nw == NW_) {                                                         \
-    hipLaunchKernelGGL((conv_x3p_kernel<MODE_, MW_, NW_, true>), pg, dim3(256), lds_bytes, s, a);       \
-    return hipGetLastError();                                                                            \
-  }
-    PNVO_X3P(0, 1, 1) PNVO_X3P(1, 1, 1) PNVO_X3P(0, 2, 1) PNVO_X3P(1, 2, 1)     // (bres only: resident weights, plain / GN-input modes)
-#undef PNVO_X3P
-  }
-  if (a.np == 2) {
-    if (ks == 3 && stride == 1) return launch_ks<3, 1, 2>(a, mode, mw, nw, grid, lds_bytes, s);
-    if (ks == 3 && stride == 2) return launch_ks<3, 2, 2>(a, mode, mw, nw, grid, lds_bytes, s);
-    if (ks == 1 && stride == 2) return launch_ks<1, 2, 2>(a, mode, mw, nw, grid, lds_bytes, s);
-    return hipErrorInvalidValue;
-  }
-  if (ks == 3 && stride == 1) return launch_ks<3, 1, 3>(a, mode, mw, nw, grid, lds_bytes, s);
-  if (ks == 3 && stride == 2) return launch_ks<3, 2, 3>(a, mode, mw, nw, grid, lds_bytes, s);
-  if (ks == 1 && stride == 2) return launch_ks<1, 2, 3>(a, mode, mw, nw, grid, lds_bytes, s);
-  return hipErrorInvalidValue;
+  return x3_table[p.inst].launch(a, dim3(p.grid_x, p.grid_y, 1u), p.lds_bytes, s);
 }
 
 // B operand: out[tap][k-chunk (cin/16)][N-tile (coutp/32)][piece 3][lane = kh*32 + n][8 bf16]

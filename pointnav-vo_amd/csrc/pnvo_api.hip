@@ -262,28 +262,22 @@ bool x3_two_pieces(pnvo_handle m, const Layer &l) {
     return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l.name + ".weight") != nullptr;
   return m->opt.pieces == 2;
 }
-// The conv_x3 arguments of layer l at B samples before their plan: shape, operand pieces and handle m's plan options.
-void x3_fill(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa) {
-  std::memset(&xa, 0, sizeof(xa));
-  xa.force = m->opt.conv == 1;
-  xa.strip = m->opt.x3_strip;
-  xa.fine = m->opt.x3_fine;
-  xa.w8_ok = m->opt.x3_w8;
-  xa.m16_ok = m->opt.x3_m16;
-  xa.ksw_ok = m->opt.x3_ksplit;
-  xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
-  xa.np = x3_two_pieces(m, l) ? 2 : 3;
-  xa.B = B;
-  xa.H = l.hin;
-  xa.W = l.win;
-  xa.CIN = l.cinp;
-  xa.Ho = l.hout;
-  xa.Wo = l.wout;
-  xa.COUTP = l.coutp;
+// The conv_x3 problem of layer l at B samples: shape, operand pieces and handle m's plan options; stager mode 0, no tail, no ride.
+ConvX3Problem x3_problem(pnvo_handle m, const Layer &l, int B) {
+  ConvX3Problem q{.B = B, .H = l.hin, .W = l.win, .CIN = l.cinp, .Ho = l.hout, .Wo = l.wout, .COUTP = l.coutp, .ks = l.k, .stride = l.stride};
+  q.np = x3_two_pieces(m, l) ? 2 : 3;
+  q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = m->opt.x3_fine, .w8 = m->opt.x3_w8, .m16 = m->opt.x3_m16,
+           .ksw = m->opt.x3_ksplit, .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0, .rows = m->opt.x3_rows, .num_cus = m->num_cus};
+  return q;
 }
-bool x3_args(pnvo_handle m, const Layer &l, int B, ConvX3Args &xa, int *mw, int *nw, size_t *ldsb) {
-  x3_fill(m, l, B, xa);
-  return conv_x3_plan(xa, l.k, l.stride, mw, nw, ldsb);
+// The plan of l on the tile kernels (the rows form, which a launch may take in their place, aside): whether conv_x3.hip has the layer
+// at B samples, its statistics slots and executed FLOPs.  ds: with the block's downsample conv riding on it.
+ConvX3Plan x3_tile_plan(pnvo_handle m, const Layer &l, int B, bool ds = false, bool force = false) {
+  ConvX3Problem q = x3_problem(m, l, B);
+  q.ds = ds;
+  q.opt.rows = 0;
+  if (force) q.opt.force = 1;
+  return conv_x3_plan(q);
 }
 
 // The implicit-GEMM geometry of layer l at B samples, the rest of the launch zero.
@@ -321,12 +315,8 @@ size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
   int slots = conv_slots((int)P, MT), s2 = 0;
   if (layer_on_lds(m, l, &s2) && s2 > slots) slots = s2;            // conv3_lds: slots = tiles x waves
   if ((l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || l.stride == 2)) || (l.k == 1 && l.stride == 2)) {   // conv_x3: slots = tiles
-    ConvX3Args xa;
-    x3_fill(m, l, B, xa);
-    xa.force = 1;                       // (sized for the forced plan: option conv may change between forwards)
-    int mw, nw;
-    size_t ldsb;
-    if (conv_x3_plan(xa, l.k, l.stride, &mw, &nw, &ldsb) && xa.slots > slots) slots = xa.slots;
+    const ConvX3Plan p = x3_tile_plan(m, l, B, false, true);   // (sized for the forced plan: option conv may change between forwards)
+    if (p && p.slots > slots) slots = p.slots;
   }
   return (size_t)B * (size_t)slots * l.coutp * 2;
 }
@@ -466,11 +456,7 @@ void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &
 }
 
 bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B) {
-  if (!x3_layer(m, l) || l.groups <= 0) return false;
-  ConvX3Args xa;
-  int mw, nw;
-  size_t ldsb;
-  return x3_args(m, l, B, xa, &mw, &nw, &ldsb);
+  return x3_layer(m, l) && l.groups > 0 && x3_tile_plan(m, l, B);
 }
 
 // The block's downsample conv rides on its first 3x3 conv when both run on the float16-piece form of conv_x3_kernel and share the
@@ -483,7 +469,7 @@ bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B) 
       c1.win != cd.win || c1.cout != c1.coutp || c1.groups != cd.groups || c1.groups <= 0 || cd.host_w.empty())
     return false;
   if (!x3_layer(m, c1) || !x3_layer(m, cd) || !x3_two_pieces(m, c1) || !x3_two_pieces(m, cd)) return false;
-  return pnvo_conv_on_x3(m, c1, B);
+  return (bool)x3_tile_plan(m, c1, B, true);
 }
 
 bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
@@ -525,16 +511,15 @@ int x3_operand(pnvo_handle h, Layer &q, int pieces, hipStream_t s) {
   return PNVO_OK;
 }
 
-// conv_x3_kernel, or conv_rows32_kernel (rows), on the plan pnvo_run_conv made in xa, + the GroupNorm finalisation unless the conv does it.
-int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, ConvX3Args &xa, bool rows, int x3_mode, int mw, int nw,
-                size_t ldsb) {
+// conv_x3_kernel / conv_x3p_kernel, or conv_rows32_kernel (rows), on plan p of problem q, + the GroupNorm finalisation unless the conv does it.
+int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvX3Problem &q, const ConvX3Plan &p) {
   hipStream_t s = r.s;
   const DsRide *ride = r.ride;
-  const bool two = xa.np == 2;
+  const bool two = q.np == 2, rows = p.family == ConvX3Plan::ROWS;
+  ConvX3Args xa = conv_x3_args(q, p);
   Layer &lm = const_cast<Layer &>(l);
-  if (int rc = x3_operand(m, lm, xa.np, s)) return rc;
-  if (ride != nullptr) {             // the block's downsample conv on this launch (pnvo_conv_takes_ds said yes)
-    if (rows || !two || l.stride != 2 || l.k != 3) return fail(m, PNVO_ERR_STATE, "downsample ride on a conv that cannot carry it (" + l.name + ")");
+  if (int rc = x3_operand(m, lm, q.np, s)) return rc;
+  if (ride != nullptr) {             // the block's downsample conv on this launch (pnvo_conv_takes_ds said yes; the plan carries it: q.ds)
     Layer &dm = const_cast<Layer &>(*ride->cd);
     if (int rc = x3_operand(m, dm, 2, s)) return rc;
     xa.ds_wpk = dm.wpk_x2;
@@ -588,8 +573,11 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, Conv
   xa.in_scale = r.in_scale;
   xa.in_shift = r.in_shift;
   xa.stats = m->stats;
-  if (r.tail != nullptr) {           // (its skip branch is in xa already: pnvo_run_conv)
+  if (r.tail != nullptr) {
     if (r.in_scale == nullptr) return fail(m, PNVO_ERR_STATE, "block tail without the conv's GroupNorm scale/shift");
+    xa.res = r.tail->res;
+    xa.res_scale = r.tail->res_scale;
+    xa.res_shift = r.tail->res_shift;
     xa.xout = r.tail->out;
   }
   // one tile per sample (the 12 x 22 and 6 x 11 maps): the workgroup that sums a sample's channels also turns the sums into the
@@ -597,7 +585,7 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, Conv
   const long P = (long)l.hout * l.wout;
   const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
   const bool fuse = m->opt.gn_fuse && xa.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 &&
-                    32 % cpg == 0 && l.cout % cpg == 0 && (rows || !(xa.persist_wgs > 0 && l.cin == 32 && l.coutp == 32));
+                    32 % cpg == 0 && l.cout % cpg == 0 && (rows || !(q.opt.persist_wgs > 0 && l.cin == 32 && l.coutp == 32));
   if (fuse && ride != nullptr) {
     xa.ds_gamma = ride->cd->gamma;
     xa.ds_beta = ride->cd->beta;
@@ -620,9 +608,9 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, Conv
   {
     Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B) + (r.tail ? 8.0 * B * l.hin * l.win * l.cin : 0.0));
     if (rows)
-      HIPCHK(m, launch_conv_rows32(xa, x3_mode, m->num_cus, s));
+      HIPCHK(m, launch_conv_rows32(xa, p, s));
     else
-      HIPCHK(m, launch_conv_x3(xa, l.k, l.stride, x3_mode, mw, nw, ldsb, s));
+      HIPCHK(m, launch_conv_x3(xa, p, s));
   }
   if (fuse) return PNVO_OK;
   Timed t(m, s, "gn_finalize", 0.0, 0.0);
@@ -724,21 +712,15 @@ int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
   // row-streaming conv_rows.hip where it takes the launch, with fewer statistics slots than the tile plan the buffer is sized for:
   // stats_floats); option conv=fp32 keeps the fp32-MFMA kernels.  Not with a fused stem source, bias or output ReLU.
   if (r.ss && r.src == nullptr && r.bias == nullptr && !r.relu_out && r.y_cstride == l.coutp && x3_layer(m, l)) {
-    ConvX3Args xa;
-    x3_fill(m, l, B, xa);
+    ConvX3Problem q = x3_problem(m, l, B);
+    q.mode = r.tail ? (r.tail->res ? 2 : 3) : (r.in_scale ? 1 : 0);
     // (the rows plan refuses a block tail whose skip branch carries its own GroupNorm — a downsample skip, reachable with
-    //  baseplanes 16: the rows kernel adds the raw skip tensor — so the tail's fields are in place BEFORE the plan looks at them)
-    if (r.tail != nullptr) {
-      xa.res = r.tail->res;
-      xa.res_scale = r.tail->res_scale;
-      xa.res_shift = r.tail->res_shift;
-    }
-    const int x3_mode = r.tail ? (r.tail->res ? 2 : 3) : (r.in_scale ? 1 : 0);
-    const bool rows = xa.np == 2 && m->opt.x3_rows && conv_rows32_plan(xa, l.k, l.stride, x3_mode, m->num_cus);
-    int mw = 0, nw = 0;
-    size_t ldsb = 0;
-    if (rows || conv_x3_plan(xa, l.k, l.stride, &mw, &nw, &ldsb)) return run_conv_x3(m, l, B, r, xa, rows, x3_mode, mw, nw, ldsb);
+    //  baseplanes 16: the rows kernel adds the raw skip tensor)
+    q.tail_scaled = r.tail != nullptr && r.tail->res_scale != nullptr;
+    q.ds = r.ride != nullptr;
+    if (const ConvX3Plan p = conv_x3_plan(q)) return run_conv_x3(m, l, B, r, q, p);
   }
+  if (r.ride != nullptr) return fail(m, PNVO_ERR_STATE, "downsample ride on a conv that cannot carry it (" + l.name + ")");
   if (r.tail != nullptr) return fail(m, PNVO_ERR_STATE, "block tail handed to a conv that cannot take it (" + l.name + ")");
   if (r.grp != nullptr && r.ss != nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " fell off the float16-piece tile kernel");
   return run_conv_fp32(m, l, B, r);
@@ -2396,21 +2378,19 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
       }
       return PNVO_OK;
     }
-    ConvX3Args xa;
-    int mw, nw;
-    size_t ldsb;
     const Layer *c1 = l.block >= 0 && h->blocks[l.block].ds == (int)li ? &h->convs[h->blocks[l.block].conv[0]] : nullptr;
-    if (c1 && pnvo_conv_takes_ds(h, *c1, l, B) && x3_args(h, *c1, B, xa, &mw, &nw, &ldsb)) {   // a downsample conv riding on its block's first conv
+    if (c1 && pnvo_conv_takes_ds(h, *c1, l, B)) {   // a downsample conv riding on its block's first conv
+      const ConvX3Plan p = x3_tile_plan(h, *c1, B, true);
       std::snprintf(family, cap, "x2-rides");
-      if (executed_flops) *executed_flops = 3.0 * 2.0 * (double)B * xa.tiles_r * xa.tiles_c * xa.MT * 32.0 * l.coutp * (double)l.cinp;
+      if (executed_flops) *executed_flops = 3.0 * 2.0 * (double)B * p.tiles_r * p.tiles_c * p.MT * 32.0 * l.coutp * (double)l.cinp;
       return PNVO_OK;
     }
-    if (x3_layer(h, l) && l.groups > 0 && x3_args(h, l, B, xa, &mw, &nw, &ldsb)) {
-      std::snprintf(family, cap, xa.np == 2 ? "x2" : "x3");
+    if (pnvo_conv_on_x3(h, l, B)) {
+      const ConvX3Plan p = x3_tile_plan(h, l, B);
+      std::snprintf(family, cap, p.np == 2 ? "x2" : "x3");
       // tiles x M-tiles x 32 pixels (the 16x16x32 flavour of x2: 16-row sub-tiles x 16) x padded outputs x K, six bf16 (x3) or three float16 (x2) MFMA terms per float32 product
-      const double rows = xa.m16 ? ((xa.TR * xa.TC + 15) / 16) * 16.0 : xa.MT * 32.0;
       if (executed_flops)
-        *executed_flops = (xa.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * xa.tiles_r * xa.tiles_c * rows * l.coutp * (double)l.cinp * l.k * l.kw;
+        *executed_flops = (p.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * p.tiles_r * p.tiles_c * (double)p.m_rows * l.coutp * (double)l.cinp * l.k * l.kw;
       return PNVO_OK;
     }
     std::snprintf(family, cap, "%s", layer_on_lds(h, l, nullptr) ? "fp32-lds" : "fp32-generic");
@@ -2418,6 +2398,18 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
     return PNVO_OK;
   }
   return fail(h, PNVO_ERR_ARG, std::string("no residual-stage conv named '") + name + "'");
+}
+
+int pnvo_conv_x3_describe(const int *problem, int n, char *buf, size_t cap) {
+  if (!buf || cap == 0) return fail(nullptr, PNVO_ERR_ARG, "bad argument");
+  if (problem == nullptr) return conv_x3_describe(nullptr, n, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;   // (past the last row: no message)
+  if (n != 23) return fail(nullptr, PNVO_ERR_ARG, "a conv_x3 problem has 23 fields");
+  const int *v = problem;
+  ConvX3Problem q{.B = v[0], .H = v[1], .W = v[2], .CIN = v[3], .Ho = v[4], .Wo = v[5], .COUTP = v[6], .ks = v[7], .stride = v[8], .np = v[9],
+                  .mode = v[10], .tail_scaled = v[11] != 0, .absmax = v[12] != 0, .ds = v[13] != 0};
+  q.opt = {.force = v[14], .strip = v[15], .fine = v[16], .w8 = v[17], .m16 = v[18], .ksw = v[19], .persist_wgs = v[20], .rows = v[21], .num_cus = v[22]};
+  conv_x3_describe(&q, 0, buf, cap);
+  return PNVO_OK;
 }
 
 int pnvo_timing_mode(pnvo_handle h, int mode) {

@@ -146,23 +146,15 @@ struct ConvX3Args {
   float *xout;
   float *stats;                      // [B,slots,COUTP,2] GroupNorm partial sums or nullptr
   int B, H, W, CIN, Ho, Wo, COUTP;
-  int TR, TC, tiles_r, tiles_c, PR, PC, CK, MT, wn, slots;   // filled by conv_x3_plan
+  int TR, TC, tiles_r, tiles_c, PR, PC, CK, MT, wn, slots;   // the plan's tile geometry (conv_x3_args)
   unsigned long long *prof;          // PNVO_X3_PROF=1: phase cycles of one workgroup (nullptr otherwise)
-  int force;                         // conv_x3_plan: take the layer at any launch size (option conv=x3)
-  // np == 2 on a GRADIENT input (backward-data): float bits of max |x| over the input tensor (gn_bwd_apply's absmax); the stager
-  // multiplies by 2^(14 - e) before the float16 split, the epilogue divides again (both exact)
+  // two float16 pieces on a GRADIENT input (backward-data): float bits of max |x| over the input tensor (gn_bwd_apply's absmax); the
+  // stager multiplies by 2^(14 - e) before the float16 split, the epilogue divides again (both exact)
   const unsigned *in_absmax;         //   (64 slots of 16 uints: readers take the maximum, absmax_of())
-  int rs_bands, rs_rows;             // conv_rows32_plan (conv_rows.hip): bands per sample, rows per band
+  int rs_bands, rs_rows;             // the rows plan (conv_rows.hip): bands per sample, rows per band
   int rs_dbg;                        // developer ablations (env PNVO_ROWS_DBG; WRONG RESULTS, timing only): 1 no loads, 2 no stores, 4 no MFMAs, 8 no conversion
-  int np;                            // operand pieces: 3 = bf16 (six exact product terms; 0 means 3), 2 = float16 (three terms)
-  float oscale;                      // np == 2: inverse of the power-of-two scale folded into the packed weights
-  const float *oscale_ptr;           //   ... or where it lives on the device (training: the scale follows the weights)
-  int persist_wgs;                   // > 0: eligible launches take conv_x3p_kernel with this many workgroups (3 per CU); 0: never
-  int w8_ok, w8;                     // option x3_w8 / conv_x3_plan's decision: eight waves per workgroup (two per SIMD) — 256-channel 6 x 11 maps, one tile per sample
-  int m16_ok, m16;                   // option x3_m16 / conv_x3_plan's decision: the K loop on 16x16x32 MFMAs, M padded to 16 rows (mw / nw stay the 32-row form's counts)
-  int ksw_ok, ksw;                   // option x3_ksplit / conv_x3_plan's decision: fine-plan tiles of three / four M-tiles split K over the four waves
-  int fine;                          // conv_x3_plan: allow the fine plan (one N-tile per workgroup) for launches below 224 workgroups (option x3_fine)
-  int strip;                         // conv_x3_plan: wide strip tiles with the N-tiles split over blockIdx.y for 64 / 128 output channels
+  const float *oscale_ptr;           // two float16 pieces: where the inverse of the power-of-two scale folded into the packed weights lives on the
+  float oscale;                      //   device (training: the scale follows the weights), or (nullptr) the value itself
   // GroupNorm finalisation inside the conv (slots == 1: the workgroup that wrote a sample's only partial sums holds the complete sums
   // of its channels): scale / shift [B,COUTP] as gn_finalize_kernel would write them, bit for bit; nullptr: the separate launch
   const float *gn_gamma, *gn_beta;
@@ -215,11 +207,48 @@ __device__ __forceinline__ void gn_finalize_lane(float s1, float s2, int cpg, lo
   *shift = (float)((double)beta - mu * sc);
 }
 #endif
-bool conv_x3_plan(ConvX3Args &a, int ks, int stride, int *mw, int *nw, size_t *lds_bytes);
-// Row-streaming form of the 32 -> 32 channel 3x3 stride-1 convs (conv_rows.hip): plan fills rs_bands / rs_rows / slots.
-bool conv_rows32_plan(ConvX3Args &a, int ks, int stride, int mode, int num_cus);
-hipError_t launch_conv_rows32(const ConvX3Args &a, int mode, int num_cus, hipStream_t s);
-hipError_t launch_conv_x3(const ConvX3Args &a, int ks, int stride, int mode, int mw, int nw, size_t lds_bytes, hipStream_t s);
+// conv_x3 on the host: a PROBLEM (shape, operand pieces, stager mode, the handle's options) -> conv_x3_plan -> a PLAN (kernel family,
+// the instance's row in the table of instantiated kernels, launch size, tile geometry) -> conv_x3_args + launch_conv_x3.
+struct ConvX3Opts {
+  int force;                         // take the layer at any launch size (option conv=x3)
+  int strip;                         // wide strip tiles with the N-tiles split over blockIdx.y for 64 / 128 output channels (option x3_strip)
+  int fine;                          // allow the fine plan (one N-tile per workgroup) for launches below 224 workgroups (option x3_fine)
+  int w8;                            // option x3_w8: eight waves per workgroup (two per SIMD) — 256-channel 6 x 11 maps, one tile per sample
+  int m16;                           // option x3_m16: the K loop on 16x16x32 MFMAs, M padded to 16 rows
+  int ksw;                           // option x3_ksplit: fine-plan tiles of three / four M-tiles split K over the four waves
+  int persist_wgs;                   // > 0: eligible launches take conv_x3p_kernel with this many workgroups (3 per CU); 0: never
+  int rows;                          // option x3_rows: 32 -> 32 channel 3x3 stride-1 convs on conv_rows32_kernel where it takes the launch
+  int num_cus;
+};
+struct ConvX3Problem {
+  int B, H, W, CIN, Ho, Wo, COUTP, ks, stride;
+  int np;                            // operand pieces: 3 = bf16 (six exact product terms), 2 = float16 (three terms)
+  int mode;                          // stager: 0 plain, 1 relu(x*scale+shift), 2 block tail with the skip tensor `res`, 3 block tail on pooled keys
+  bool tail_scaled;                  // mode 2: the skip branch carries its own scale / shift (a downsample branch)
+  bool absmax;                       // a gradient input with its absolute-maximum record (ConvX3Args::in_absmax)
+  bool ds;                           // the block's 1x1 stride-2 downsample conv rides on the launch
+  ConvX3Opts opt;
+};
+struct ConvX3Plan {
+  enum Family { NONE, TILE, PERSISTENT, ROWS } family = NONE;   // conv_x3_kernel, conv_x3p_kernel, conv_rows32_kernel
+  int inst = -1;                     // TILE / PERSISTENT: row of the instance table
+  int mode = 0, np = 0;
+  int mw = 0, nw = 0;                // the instance's template arguments (16-row / 16-column counts with M16)
+  bool dsf = false, w8 = false, ksw = false, m16 = false;
+  unsigned grid_x = 0, grid_y = 1;
+  int block = 0;
+  size_t lds_bytes = 0;
+  int TR = 0, TC = 0, tiles_r = 0, tiles_c = 0, PR = 0, PC = 0, CK = 0, MT = 0, wn = 0, slots = 0;
+  int rs_bands = 0, rs_rows = 0;     // ROWS: bands per sample, rows per band
+  int m_rows = 0;                    // rows of M one tile's MFMAs cover (executed FLOPs): 32 MT, or 16-row sub-tiles x 16 with M16
+  explicit operator bool() const { return family != NONE; }
+};
+ConvX3Plan conv_x3_plan(const ConvX3Problem &q);                                  // pure host code; NONE: outside what the kernels cover
+bool conv_rows32_candidate(const ConvX3Problem &q, ConvX3Plan &p);                // the rows form of q, if it takes the launch (conv_rows.hip)
+ConvX3Args conv_x3_args(const ConvX3Problem &q, const ConvX3Plan &p);             // shape and the plan's geometry, every operand zero
+int conv_x3_describe(const ConvX3Problem *q, int row, char *buf, size_t cap);     // one line for q's plan, or (q == nullptr) for a table row
+hipError_t launch_conv_rows32(const ConvX3Args &a, const ConvX3Plan &p, hipStream_t s);
+hipError_t launch_conv_x3(const ConvX3Args &a, const ConvX3Plan &p, hipStream_t s);   // TILE / PERSISTENT
 hipError_t launch_conv_x3_repack(const float *w_oihw, int cout, int cin, int cinp, int coutp, int kh, int kw, int transposed,
                                  unsigned short *out, hipStream_t s);
 void pack_conv_x3_weight(const float *oihw, int cout, int cin, int cinp, int coutp, int kh, int kw, unsigned short *out);

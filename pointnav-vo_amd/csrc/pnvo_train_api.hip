@@ -526,26 +526,20 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
   }
   // 3x3 stride-1: float32 results from the bf16 matrix cores (three-piece operands), as in the forward (PNVO_CONV=fp32: off)
   if (l.k == 3 && l.kw == 3 && l.stride == 1 && l.pad == 1 && !accum && l.cin % 32 == 0 && m->opt.conv <= 1) {
-    ConvX3Args xa;
-    std::memset(&xa, 0, sizeof(xa));
-    xa.force = m->opt.conv == 1;
-    xa.strip = m->opt.x3_strip;
-    xa.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;   // (32 -> 32 backward-data convs: resident weights, conv_x3p_kernel)
-    xa.B = B;
-    xa.H = l.hout;
-    xa.W = l.wout;
-    xa.CIN = l.coutp;
-    xa.Ho = l.hin;
-    xa.Wo = l.win;
-    xa.COUTP = l.cin;
-    int mw = 0, nw = 0;
-    size_t ldsb = 0;
     auto it = t->toc.find(l.name + ".weight");
     // two float16 pieces (three terms) when the training forward uses them: the gradient is scaled by a power of two from its
     // absolute maximum (tracked by the GroupNorm backward that produced it), the weights carry the forward's per-tensor scale
     const float *wsc = m->opt.train_pieces == 2 && t->dmax != nullptr ? pnvo_train_x2_scale(m, l.name + ".weight") : nullptr;
-    xa.np = wsc != nullptr ? 2 : 3;
-    if (it != t->toc.end() && conv_x3_plan(xa, 3, 1, &mw, &nw, &ldsb)) {
+    // the transposed conv: input and output channels and sizes swapped, plain stager
+    ConvX3Problem q{.B = B, .H = l.hout, .W = l.wout, .CIN = l.coutp, .Ho = l.hin, .Wo = l.win, .COUTP = l.cin, .ks = 3, .stride = 1};
+    q.np = wsc != nullptr ? 2 : 3;
+    q.absmax = wsc != nullptr;
+    q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = 0, .w8 = 0, .m16 = 0, .ksw = 0,   // backward-data: the fine plan, W8, M16 and the K split stay off
+             .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0,   // (32 -> 32 backward-data convs: resident weights, conv_x3p_kernel)
+             .rows = 0, .num_cus = m->num_cus};                       // ... and the rows form, which has no gradient-input scaling
+    const ConvX3Plan p = it != t->toc.end() ? conv_x3_plan(q) : ConvX3Plan{};
+    if (p) {
+      ConvX3Args xa = conv_x3_args(q, p);
       if (wsc != nullptr) {
         if (!t->dgrad_x2[li] || t->dgrad_x2_gen[li] != m->weights_gen) {
           const size_t nel = (size_t)9 * l.coutp * l.cin * 2;
@@ -561,7 +555,7 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
         xa.oscale_ptr = wsc + 1;
         xa.in_absmax = t->dmax + li * PNVO_ABSMAX_UINTS;
         PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-        HIPCHK(m, launch_conv_x3(xa, 3, 1, 0, mw, nw, ldsb, s));
+        HIPCHK(m, launch_conv_x3(xa, p, s));
         return PNVO_OK;
       }
       if (!t->dgrad_x3[li] || t->dgrad_x3_gen[li] != m->weights_gen) {
@@ -576,7 +570,7 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
       xa.wpk = t->dgrad_x3[li];
       xa.y = dx;
       PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-      HIPCHK(m, launch_conv_x3(xa, 3, 1, 0, mw, nw, ldsb, s));
+      HIPCHK(m, launch_conv_x3(xa, p, s));
       return PNVO_OK;
     }
   }

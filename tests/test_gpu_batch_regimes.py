@@ -15,7 +15,7 @@ Batches (default options, num_cus = 256 on the MI355X; the predicates in pointna
     16 17 32 33      fine plans (conv_x3_plan: regular plan < 224 workgroups; fine plan >= 48 workgroups), K split behind
                      >= 128 input channels (x3_ksplit): the deep stages of 6-48 pairs
     48 | 49          fc_rows_usable: the hidden layer and the head on fc_rows.hip up to 48 samples
-    63 | 64 65       conv_rows32_plan: layer1's 32 -> 32 convs on the row-streaming kernel once B * bands >= 256 (48-row maps:
+    63 | 64 65       conv_rows32_candidate: layer1's 32 -> 32 convs on the row-streaming kernel once B * bands >= 256 (48-row maps:
                      up to 4 bands of 12 rows: 64 pairs on), 2 bands at 128, 1 band at 256
     100 128 129      conv_x3 on every 3x3 conv (>= 192 workgroups), fused pool and block tails, downsample rides
     199 | 200        the eight-wave (3,1) tiles of the 256-channel 6 x 11 convs (one tile per pair: ntiles >= 200)
@@ -172,6 +172,43 @@ def test_the_sweep_covers_every_conv_family():
     print("families:", {k: sorted(v) for k, v in seen.items()})
     assert "smallnet" in seen and "x2" in seen, seen.keys()
     assert any(k.startswith("fp32") for k in seen), seen.keys()
+
+
+ENGAGING = [7, 8, 16, 48, 64, 128, 200, 256]      # per-layer kernels, resident stem, fine plans, last fc_rows batch, rows form, conv_x3 everywhere, eight waves, configs[1]
+
+
+def test_layer_families_are_what_the_planner_describes(ctx):
+    """At each regime's engaging batch: the family pnvo_layer_kernel reports for every residual-stage conv is the one the conv_x3
+    planner takes for that layer's problem (pnvo_conv_x3_describe), and that line is the one recorded in
+    tests/golden/conv_x3_plans.txt from the planner before the problem -> plan -> table refactor.  No forward runs."""
+    import test_conv_x3_plan as plans
+    model = ctx["model"]
+    lines, index = plans.read_golden()
+    grid = plans.grid()
+    pieces = int(model.get_option("pieces"))
+    convs = ms.conv_plan(model.cfg)
+    for B in ENGAGING:
+        assert B in plans.BATCHES and B in BATCHES
+        for i, cd in enumerate(convs):
+            if i == 0:
+                continue
+            fam = model.layer_kernel(cd.name, B)[0]
+            np_ = 3 if fam == "x3" else pieces
+
+            def line_of(c, ds):
+                H, W, CIN, Ho, Wo, COUTP, ks, stride, _ = plans.fwd_shape(c)
+                q = plans.problem_of(B=B, H=H, W=W, CIN=CIN, Ho=Ho, Wo=Wo, COUTP=COUTP, ks=ks, stride=stride, np=np_, ds=ds)
+                line = plans.describe(q)
+                assert line == plans.golden_line(lines, index, grid, q), (cd.name, B, line)
+                return line
+
+            want = None
+            if cd.k == 1:                               # a downsample conv (plan order c1, c2, downsample): rides on c1 where c1 carries it
+                if line_of(convs[i - 2], 1) != "none" and np_ == 2:
+                    want = "x2-rides"
+            if want is None:
+                want = "fp32" if line_of(cd, 0) == "none" else ("x2" if np_ == 2 else "x3")
+            assert fam == want or (want == "fp32" and fam.startswith("fp32")), (cd.name, B, fam, want)
 
 
 def test_dual_bf16_forward_at_256_every_position(ctx):

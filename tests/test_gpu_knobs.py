@@ -356,7 +356,7 @@ def test_downsample_ride_on_an_odd_resolution_and_with_taps():
 
 def test_narrow_models_are_refused_not_mis_served():
     """ADVICE r5 asked for a resnet_baseplanes = 16 model: its layer2 would be a 32 -> 32 channel stage whose second block takes a block
-    tail with a DOWNSAMPLE skip (res * scale + shift), which conv_rows32_kernel's block-tail mode does not apply.  conv_rows32_plan now
+    tail with a DOWNSAMPLE skip (res * scale + shift), which conv_rows32_kernel's block-tail mode does not apply.  conv_rows32_candidate now
     sees the tail's fields before it decides (csrc/pnvo_api.hip) — and such a model cannot reach it in the first place: pnvo_create
     refuses base widths below 32 (every registered reference variant has 32 or 64, vo_cnn.py:236-561) with an error, never a fallback."""
     import numpy as np
