@@ -52,6 +52,11 @@ typedef struct {
   int32_t flat_size;          /* after_compression_flat_size (2048) */
   int32_t max_batch;          /* workspace sizing hint; the workspace grows on demand */
   int32_t backbone_depth;     /* 0 or 18: resnet18 (BasicBlock); 50 / 101: Bottleneck [3,4,6,3] / [3,4,23,3] (resnet.py:226-241) */
+  /* Appended; zero keeps the models above.  Both need backbone_depth 50 or 101 (resnet.py:244-286). */
+  int32_t resnext;            /* 1: ResNeXtBottleneck geometry — expansion 2, stage planes 2 * baseplanes * 2^(s-1), and the 3x3 conv of the
+                                 FIRST block of each stage grouped with cardinality baseplanes / 2 (resnet.py:198-210 hands the
+                                 cardinality to that block only) */
+  int32_t se;                 /* 1: every block carries the squeeze-and-excite branch (resnet.py:71-140): se.excite.{0,2}.{weight,bias} */
 } pnvo_config;
 
 /* One entry of the reference state_dict: name exactly as model.state_dict() spells it,
@@ -373,6 +378,12 @@ typedef struct {
   int32_t rgb_channels;       /* 0: no "rgb" among the visual types; 3: observations["rgb"] feeds the encoder in front of the depth */
   int32_t no_depth;           /* 1: "depth" is not among the visual types (needs rgb_channels = 3); 0: it is */
   int32_t normalize;          /* normalize_visual_inputs -> net.visual_encoder.running_mean_and_var */
+  /* RL.Policy.backbone (resnet_policy.py:96-101), appended; all three zero: resnet18.  The fields of pnvo_config with the same names:
+   * resnet50 / resnet101 = (50 / 101, 0, 0), se_resnet50 = (50, 0, 1), resneXt50 = (50, 1, 0), se_resneXt50 / 101 = (50 / 101, 1, 1).
+   * The act, encode and visual_features entry points serve every backbone; the encoder of a non-resnet18 policy has no backward:
+   * pnvo_policy_evaluate / _evaluate_rgbd refuse it (evaluate pnvo_policy_encode's output with pnvo_policy_evaluate_features), and
+   * pnvo_policy_backward with train_encoder = 1 does too. */
+  int32_t backbone_depth, resnext, se;
 } pnvo_policy_config;
 
 typedef struct pnvo_policy_s *pnvo_policy_handle;
@@ -473,6 +484,13 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
 
 /* Re-pack the encoder's kernel operands from `params` (after an optimiser step or any other write to it). */
 int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream);
+
+/* Non-resnet18 policies (backbone_depth / resnext / se): the encoder is NOT attached — it keeps the copy of its weights that
+ * pnvo_policy_load_weights made, pnvo_policy_train_refresh leaves it alone, and no optimiser step may move it (train_encoder False).
+ * After a write to the encoder's range of `params` from outside (a checkpoint loaded on resume) this call re-reads it: a device-to-
+ * host copy and pnvo_load_weights on the encoder handle, with the table pnvo_policy_train_attach took; it waits for `stream`.  On a
+ * resnet18 policy it is pnvo_policy_train_refresh. */
+int pnvo_policy_train_reload_encoder(pnvo_policy_handle h, const pnvo_tensor_desc *toc, int ntoc, void *stream);
 
 /* value, action_log_probs, entropy, rnn_hidden_states = evaluate_actions(...) with everything the backward needs kept in the
  * handle.  depth [M,H,W,1], goal [M,2], prev_actions [M] int64, masks [M], actions [M] int64; hidden_in / hidden_out

@@ -30,7 +30,7 @@ class PnvoError(RuntimeError):
 class pnvo_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "width", "height", "n_rgb", "n_depth", "n_dd", "n_tdv", "baseplanes", "hidden", "out_dim", "normalize",
-        "act_embed", "n_acts", "flat_size", "max_batch", "backbone_depth")]
+        "act_embed", "n_acts", "flat_size", "max_batch", "backbone_depth", "resnext", "se")]
 
 
 class pnvo_tensor_desc(C.Structure):
@@ -129,6 +129,7 @@ _SIGNATURES = {
     "pnvo_policy_train_tail_floats": (C.c_size_t, [C.c_void_p]),
     "pnvo_policy_train_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(pnvo_tensor_desc), C.c_int]),
     "pnvo_policy_train_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pnvo_policy_train_reload_encoder": (C.c_int, [C.c_void_p, C.POINTER(pnvo_tensor_desc), C.c_int, C.c_void_p]),
     "pnvo_policy_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_policy_ppo_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,

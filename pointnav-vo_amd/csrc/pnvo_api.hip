@@ -96,7 +96,11 @@ void build_plan(pnvo_model_s *m) {
   int h = m->Hp, w = m->Wp, cin = c.baseplanes;
   const bool bott = c.backbone_depth == 50 || c.backbone_depth == 101;
   const int nblk[4] = {bott ? 3 : 2, bott ? 4 : 2, bott ? (c.backbone_depth == 101 ? 23 : 6) : 2, bott ? 3 : 2};
+  // ResNeXtBottleneck / SEResNeXtBottleneck (resnet.py:143-150,172-173): expansion 2 on doubled stage planes, cardinality baseplanes / 2
+  const bool resnext = bott && c.resnext != 0, se = bott && c.se != 0;
+  const int expansion = resnext ? 2 : 4, cardinality = resnext ? c.baseplanes / 2 : 1;
   m->bottleneck = bott;
+  m->grouped_se = resnext || se;
   m->blocks.clear();
   auto push = [&](Layer l) {                         // a conv of the block under construction
     l.block = (int)m->blocks.size();
@@ -104,7 +108,7 @@ void build_plan(pnvo_model_s *m) {
     return (int)m->convs.size() - 1;
   };
   for (int st = 1; st <= 4; ++st) {
-    const int planes = c.baseplanes << (st - 1), cout = bott ? planes * 4 : planes;
+    const int planes = (resnext ? 2 * c.baseplanes : c.baseplanes) << (st - 1), cout = bott ? planes * expansion : planes;
     for (int bi = 0; bi < nblk[st - 1]; ++bi) {
       Block b;
       b.stage = st;
@@ -116,8 +120,10 @@ void build_plan(pnvo_model_s *m) {
         Layer b2 = make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, stride, 1, h, w, g);
         b.nconv = 3;
         b.conv[0] = push(make_layer(p + "convs.0", p + "convs.1", cin, planes, 1, 1, 0, h, w, g));
+        if (bi == 0) b2.cgroups = cardinality;       // _make_layer hands the cardinality to the first block of a stage only (resnet.py:198-210)
         const int h2 = b2.hout, w2 = b2.wout;
         b.conv[1] = push(std::move(b2));
+        if (se) b.se_r = cout / 16;                  // SE(planes * expansion, r = 16): int(planes / r), resnet.py:72-80
         b.conv[2] = push(make_layer(p + "convs.6", p + "convs.7", planes, cout, 1, 1, 0, h2, w2, g));
       } else {
         Layer c1 = make_layer(p + "convs.0", p + "convs.1", cin, planes, 3, stride, 1, h, w, g);
@@ -127,9 +133,9 @@ void build_plan(pnvo_model_s *m) {
         b.conv[1] = push(make_layer(p + "convs.3", p + "convs.4", planes, planes, 3, 1, 1, h1, w1, g));
       }
       if (stride != 1 || cin != cout) b.ds = push(make_layer(p + "downsample.0", p + "downsample.1", cin, cout, 1, stride, 0, h, w, g));
-      m->blocks.push_back(b);
-      h = m->last(b).hout;
-      w = m->last(b).wout;
+      m->blocks.push_back(std::move(b));
+      h = m->last(m->blocks.back()).hout;
+      w = m->last(m->blocks.back()).wout;
       cin = cout;
     }
   }
@@ -210,12 +216,22 @@ inline void pack_conv_weight_cinp(const float *oihw, int cout, int cin, int cinp
 
 int load_conv(pnvo_handle h, const Toc &t, Layer &l, bool has_gn) {
   int rc = PNVO_OK;
-  const float *w = find_tensor(h, t, l.name + ".weight", {l.cout, l.cin, l.k, l.kw}, &rc);
+  const float *w = find_tensor(h, t, l.name + ".weight", {l.cout, l.cin / l.cgroups, l.k, l.kw}, &rc);
   if (!w) return rc;
-  std::vector<float> pk;
-  pack_conv_weight_cinp(w, l.cout, l.cin, l.cinp, l.k, l.kw, pk);
-  HIPCHK(h, l.wpk.upload(pk.data(), pk.size()));
-  l.host_w.assign(w, w + (size_t)l.cout * l.cin * l.k * l.kw);
+  if (l.cgroups > 1) {                 // grouped conv [cout, cin / groups, 3, 3]: conv_group.hip's operand, and no other kernel's
+    const int cg = l.cin / l.cgroups;
+    if (l.cin != l.cout || !conv_group_supported(l.cout, cg, l.k, l.stride, l.pad))
+      return fail(h, PNVO_ERR_ARG, "grouped conv " + l.name + ": unsupported geometry (" + std::to_string(l.cout) + " channels in groups of " +
+                                       std::to_string(cg) + ")");
+    std::vector<float> pk(conv_group_packed_floats(l.cout, cg));
+    pack_conv_group_weight(w, l.cout, cg, pk.data());
+    HIPCHK(h, l.wpk_grp.upload(pk.data(), pk.size()));
+  } else {
+    std::vector<float> pk;
+    pack_conv_weight_cinp(w, l.cout, l.cin, l.cinp, l.k, l.kw, pk);
+    HIPCHK(h, l.wpk.upload(pk.data(), pk.size()));
+    l.host_w.assign(w, w + (size_t)l.cout * l.cin * l.k * l.kw);
+  }
   if (has_gn) {
     const float *g = find_tensor(h, t, l.gn + ".weight", {l.cout}, &rc);
     if (!g) return rc;
@@ -242,7 +258,7 @@ void free_workspace(pnvo_model_s *m) {
   for (DevBuf<float> *b : {&m->xin, &m->stem_raw, &m->out_ws, &m->bufY[0], &m->bufY[1], &m->rawA, &m->rawB, &m->rawD, &m->rawC, &m->comp_raw,
                            &m->hid, &m->stats, &m->stats_ds, &m->tapbuf})
     b->reset();
-  for (DevPair<float> *q : {&m->ssA, &m->ssB, &m->ssD, &m->ssC}) q->reset();
+  for (DevPair<float> *q : {&m->ssA, &m->ssB, &m->ssD, &m->ssC, &m->ssE}) q->reset();
   m->cap = 0;
 }
 
@@ -251,7 +267,7 @@ bool x3_layer(pnvo_handle m, const Layer &l) {
   const bool s2 = l.stride == 2 && m->opt.x3_s2;
   const bool k3 = l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || s2);
   const bool k1 = l.k == 1 && l.kw == 1 && l.pad == 0 && s2;      // the 1x1 stride-2 downsample convs (resnet.py:192-195)
-  return (k3 || k1) && !l.host_w.empty() && m->opt.conv <= 1;
+  return (k3 || k1) && l.cgroups == 1 && !l.host_w.empty() && m->opt.conv <= 1;
 }
 // operand pieces of conv_x3: two float16 pieces (three product terms) when the layer's input is provably inside float16's range and
 // option pieces (train_pieces with a training step attached, whose device-side re-pack needs the weight's scale) asks for them;
@@ -312,6 +328,7 @@ size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
   const long P = (long)l.hout * l.wout, M = (long)B * P;
   int MT, NT;
   choose_tile(M, l.coutp, &MT, &NT);
+  if (l.cgroups > 1) return (size_t)B * (size_t)conv_group_slots((int)P) * l.coutp * 2;   // conv_group.hip: one slot per 32 pixels
   int slots = conv_slots((int)P, MT), s2 = 0;
   if (layer_on_lds(m, l, &s2) && s2 > slots) slots = s2;            // conv3_lds: slots = tiles x waves
   if ((l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || l.stride == 2)) || (l.k == 1 && l.stride == 2)) {   // conv_x3: slots = tiles
@@ -363,6 +380,7 @@ int ensure_workspace(pnvo_handle m, int B) {   // (also exported as pnvo_ensure_
     HIPCHK(m, m->ssA.alloc(k, (size_t)B * maxc));
     HIPCHK(m, m->ssB.alloc(k, (size_t)B * maxc));
     HIPCHK(m, m->ssD.alloc(k, (size_t)B * maxc));
+    if (m->cfg.se) HIPCHK(m, m->ssE.alloc(k, (size_t)B * maxc));
     HIPCHK(m, m->ssC.alloc(k, (size_t)B * m->comp_cp));
     HIPCHK(m, hipMemset(m->ssC[k], 0, (size_t)B * m->comp_cp * sizeof(float)));   // pad channels stay (0, 0)
   }
@@ -479,7 +497,7 @@ bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
 
 namespace {
 // launch timing of a conv of l at B samples: algorithmic flops and bytes
-double conv_flops(const Layer &l, int B) { return 2.0 * ((double)((long)B * l.hout * l.wout) * l.cout * l.cin * l.k * l.kw); }
+double conv_flops(const Layer &l, int B) { return 2.0 * ((double)((long)B * l.hout * l.wout) * l.cout * (l.cin / l.cgroups) * l.k * l.kw); }
 double conv_bytes(const Layer &l, int B) {
   return 4.0 * ((double)B * l.hin * l.win * l.cin + (double)((long)B * l.hout * l.wout) * l.cout + (double)l.cout * l.cin * l.k * l.kw);
 }
@@ -707,7 +725,28 @@ int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
 }
 }  // namespace
 
+namespace {
+// The grouped 3x3 conv of a ResNeXt block (conv_group.hip) + the GroupNorm finalisation that follows it.
+int run_conv_group(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+  if (!r.ss || r.src != nullptr || r.bias != nullptr || r.relu_out || r.y_cstride != l.coutp || r.tail != nullptr || r.ride != nullptr ||
+      r.grp != nullptr || l.cout != l.coutp || l.cin != l.cinp || !l.wpk_grp)
+    return fail(m, PNVO_ERR_STATE, "grouped conv " + l.name + " asked for something only the dense kernels do");
+  const int P = l.hout * l.wout;
+  ConvGroupArgs a{.x = r.x, .wpk = l.wpk_grp, .in_scale = r.in_scale, .in_shift = r.in_shift, .y = r.y, .stats = m->stats, .B = B, .H = l.hin,
+                  .W = l.win, .Ho = l.hout, .Wo = l.wout, .C = l.cout, .cg = l.cin / l.cgroups, .stride = l.stride, .slots = conv_group_slots(P)};
+  {
+    Timed t(m, r.s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
+    HIPCHK(m, launch_conv_group(a, r.s));
+  }
+  Timed t(m, r.s, "gn_finalize", 0.0, 0.0);
+  HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0], r.ss[1], r.s, a.slots, r.mu,
+                               r.rstd));
+  return PNVO_OK;
+}
+}  // namespace
+
 int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+  if (l.cgroups > 1) return run_conv_group(m, l, B, r);
   // GroupNorm-ed 3x3 and 1x1 stride-2 convs: float32 results from the 16-bit matrix cores (conv_x3.hip; 32 -> 32 channels on the
   // row-streaming conv_rows.hip where it takes the launch, with fewer statistics slots than the tile plan the buffer is sized for:
   // stats_floats); option conv=fp32 keeps the fp32-MFMA kernels.  Not with a fused stem source, bias or output ReLU.
@@ -1154,6 +1193,9 @@ int pnvo_create(const pnvo_config *cfg, int device, pnvo_handle *out) {
   if (cfg->width < 32 || cfg->height < 32) return fail(nullptr, PNVO_ERR_ARG, "observation_size must be >= 32x32");
   if (cfg->baseplanes < 32 || cfg->baseplanes % 32 || cfg->hidden % 8 || cfg->hidden <= 0 || cfg->out_dim <= 0)
     return fail(nullptr, PNVO_ERR_ARG, "unsupported baseplanes / hidden_size / output_dim");
+  if ((cfg->resnext != 0 && cfg->resnext != 1) || (cfg->se != 0 && cfg->se != 1) ||
+      ((cfg->resnext || cfg->se) && cfg->backbone_depth != 50 && cfg->backbone_depth != 101))
+    return fail(nullptr, PNVO_ERR_ARG, "unsupported backbone: resnext / se are 0 or 1 and need backbone_depth 50 or 101");
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(nullptr, PNVO_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   hipDeviceProp_t prop;
@@ -1200,6 +1242,24 @@ int pnvo_load_weights(pnvo_handle h, const float *blob, size_t n_floats, const p
   }
   for (Layer &l : h->convs)
     if ((rc = load_conv(h, t, l, true)) != PNVO_OK) return rc;
+  for (Block &b : h->blocks) {         // SE(planes * expansion).excite: Linear(C, C / 16), ReLU, Linear(C / 16, C), Sigmoid (resnet.py:75-80)
+    if (b.se_r == 0) continue;
+    const std::string pre = "visual_encoder.backbone." + b.tap + ".se.excite.";
+    const int C = h->last(b).cout, R = b.se_r;
+    if (!se_gate_supported(C, R)) return fail(h, PNVO_ERR_ARG, "SE branch of " + b.tap + ": unsupported width " + std::to_string(C));
+    const float *w1 = find_tensor(h, t, pre + "0.weight", {R, C}, &rc);
+    if (!w1) return rc;
+    const float *b1 = find_tensor(h, t, pre + "0.bias", {R}, &rc);
+    if (!b1) return rc;
+    const float *w2 = find_tensor(h, t, pre + "2.weight", {C, R}, &rc);
+    if (!w2) return rc;
+    const float *b2 = find_tensor(h, t, pre + "2.bias", {C}, &rc);
+    if (!b2) return rc;
+    HIPCHK(h, b.se_w1.upload(w1, (size_t)R * C));
+    HIPCHK(h, b.se_b1.upload(b1, R));
+    HIPCHK(h, b.se_w2.upload(w2, (size_t)C * R));
+    HIPCHK(h, b.se_b2.upload(b2, C));
+  }
   if (!h->bottleneck) {
     // Upper bounds of |activation| entering each conv of the residual stages, from the GroupNorm parameters alone: a group of N
     // elements normalised to unit variance has |x^| <= sqrt(N), so |relu(GN(x))| <= max_c (|gamma_c| sqrt(N) + |beta_c|); a block
@@ -1480,6 +1540,8 @@ int pnvo_get_option(pnvo_handle h, const char *key, char *buf, size_t cap) {
 int pnvo_set_precision(pnvo_handle h, int precision) {
   if (!h) return fail(h, PNVO_ERR_ARG, "null handle");
   if (precision != 0 && precision != 1) return fail(h, PNVO_ERR_ARG, "precision must be 0 (float32) or 1 (bfloat16)");
+  if (precision == 1 && h->grouped_se)
+    return fail(h, PNVO_ERR_ARG, "bfloat16 precision: SE / ResNeXt backbones run in float32 only (their grouped conv and gate have no bf16 form)");
   h->precision = precision;
   return PNVO_OK;
 }
@@ -1710,15 +1772,25 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
                                          .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK)
         return rc;
       const long Pb = (long)b3.hout * b3.wout;
+      // SE block: out = se(out) * out (resnet.py:131-140) — the gate scales the last GroupNorm's scale / shift pair, the tail is unchanged
+      float *const *ss3 = m->ssA;
+      if (b.se_r > 0) {
+        if (b3.cout != b3.coutp) return fail(m, PNVO_ERR_STATE, "SE block " + b.tap + " on a channel-padded map");
+        Timed t(m, s, "se_gate:" + b.tap, 2.0 * B * (2.0 * b.se_r + (double)Pb) * b3.cout, 4.0 * B * Pb * b3.cout);
+        HIPCHK(m, launch_se_gate({.x = m->rawB, .scale = m->ssA[0], .shift = m->ssA[1], .w1 = b.se_w1, .b1 = b.se_b1, .w2 = b.se_w2,
+                                  .b2 = b.se_b2, .out_scale = m->ssE[0], .out_shift = m->ssE[1], .B = B, .P = (int)Pb, .C = b3.cout,
+                                  .R = b.se_r}, s));
+        ss3 = m->ssE;
+      }
       if (ds) {
         const Layer &cd = m->convs[b.ds];
         if ((rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
           return rc;
         Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-        HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
+        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
       } else {
         Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-        HIPCHK(m, launch_residual(m->rawB, m->ssA[0], m->ssA[1], cur, nullptr, nullptr, B, Pb, b3.coutp, nxt, s));
+        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], cur, nullptr, nullptr, B, Pb, b3.coutp, nxt, s));
       }
       std::swap(cur, nxt);
       if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
@@ -2369,7 +2441,13 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
   for (size_t li = 1; li < h->convs.size(); ++li) {
     const Layer &l = h->convs[li];
     if (l.name != name) continue;
-    const double alg = 2.0 * B * l.hout * l.wout * (double)l.cout * l.cin * l.k * l.kw;
+    const double alg = 2.0 * B * l.hout * l.wout * (double)l.cout * (l.cin / l.cgroups) * l.k * l.kw;
+    if (l.cgroups > 1) {                               // conv_group.hip: 32-pixel slots x slabs of max(cg, 16) channels, dense inside a slab
+      std::snprintf(family, cap, "group");
+      const int cg = l.cin / l.cgroups;
+      if (executed_flops) *executed_flops = 2.0 * B * conv_group_slots(l.hout * l.wout) * 32.0 * l.cout * (double)(cg > 16 ? cg : 16) * 9.0;
+      return PNVO_OK;
+    }
     if (pnvo_stem_plan(h, false, {}).writes_slots() && pnvo_small_usable(h, B)) {      // a phase of the persistent small-batch kernel (fp32 MFMA)
       std::snprintf(family, cap, "smallnet");
       if (executed_flops) {

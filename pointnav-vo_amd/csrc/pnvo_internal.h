@@ -379,6 +379,33 @@ inline bool pnvo_first_launch_on_device(std::mutex &mu, unsigned long long &seen
 hipError_t launch_pool_keys_from_raw(const float *x, const float *gamma, int B, int H, int W, int C, int *keys, const int *only_if,
                                      hipStream_t s);
 
+// The grouped 3x3 conv of the ResNeXt blocks (conv_group.hip): C -> C channels in groups of cg, stride 1 or 2, pad 1.
+struct ConvGroupArgs {
+  const float *x;                    // [B,H,W,C] NHWC
+  const float *wpk;                  // pack_conv_group_weight()
+  const float *in_scale, *in_shift;  // [B,C]: relu(x * scale + shift) while the operand is fetched; nullptr: x as it is
+  float *y;                          // [B,Ho,Wo,C] raw output
+  float *stats;                      // [B,slots,C,2] partial (sum, sumsq) per 32-pixel slot, or nullptr
+  int B, H, W, Ho, Wo, C, cg, stride, slots;
+};
+int conv_group_slots(int P);         // statistics slots per sample
+bool conv_group_supported(int C, int cg, int ks, int stride, int pad);
+size_t conv_group_packed_floats(int C, int cg);
+void pack_conv_group_weight(const float *w, int C, int cg, float *out);   // w: torch's [C][cg][3][3]
+hipError_t launch_conv_group(const ConvGroupArgs &a, hipStream_t s);
+
+// The squeeze-and-excite gate of an SE block (se_gate.hip): (scale, shift) [B,C] of the block's last GroupNorm -> (g * scale, g * shift),
+// g = sigmoid(W2 . relu(W1 . mean_p(GN(x)) + b1) + b2).
+struct SeGateArgs {
+  const float *x;                    // [B,P,C] raw output of the block's last conv
+  const float *scale, *shift;        // [B,C]
+  const float *w1, *b1, *w2, *b2;    // [R,C], [R], [C,R], [C]
+  float *out_scale, *out_shift;      // [B,C]
+  int B, P, C, R;
+};
+bool se_gate_supported(int C, int R);
+hipError_t launch_se_gate(const SeGateArgs &a, hipStream_t s);
+
 // y = relu(a*sa+ta + r)  with r = b (plain) or b*sb+tb.  a,b,y: [B,P,C].
 hipError_t launch_residual(const float *a, const float *sa, const float *ta, const float *b, const float *sb,
                            const float *tb, int B, long P, int C, float *y, hipStream_t s);

@@ -33,6 +33,9 @@ struct Layer {
   float x2_oscale = 1.f;
   float in_bound = 3.0e38f;
   int block = -1;           // index into pnvo_model_s::blocks of the residual block this conv belongs to (-1: stem, compression)
+  // grouped conv (ResNeXt, resnet.py:63): the CONV's group count (`groups` above is the GroupNorm's); the weight is [cout, cin / cgroups, k, k]
+  int cgroups = 1;
+  DevBuf<float> wpk_grp;    // conv_group.hip's packing of it
 };
 
 // One residual block of the plan: where its convs sit in pnvo_model_s::convs.  build_plan fills the table; every walk over the
@@ -44,6 +47,9 @@ struct Block {
   int conv[3] = {-1, -1, -1};     // chain order
   int ds = -1;                    // the downsample conv of the skip branch, or -1 (identity)
   std::string tap;                // "layer<stage>.<index>"
+  // squeeze-and-excite branch (resnet.py:71-93) on the block's last GroupNorm output: se.excite.0 [se_r, C], se.excite.2 [C, se_r]
+  int se_r = 0;                   // int(C / 16); 0: no SE branch
+  DevBuf<float> se_w1, se_b1, se_w2, se_b2;
 };
 
 // Per-handle options (pnvo_set_option; defaults from the PNVO_* environment, read ONCE in pnvo_create).
@@ -159,8 +165,10 @@ struct pnvo_model_s {
   int cap = 0;                       // batch the workspace is sized for
   DevBuf<float> xin, stem_raw, bufY[2];
   DevBuf<float> rawA, rawB, rawD, rawC, comp_raw, hid, stats;
-  bool bottleneck = false;           // resnet50 / resnet101 backbone
+  bool bottleneck = false;           // resnet50 / resnet101 backbone and their ResNeXt / SE forms
+  bool grouped_se = false;           // a block with a grouped conv or an SE branch: inference on float32 only, no backward
   DevPair<float> ssA, ssB, ssD, ssC;
+  DevPair<float> ssE;                // SE models: the gated scale / shift pair of a block's last GroupNorm (se_gate.hip)
   DevBuf<float> tapbuf;
 
   std::string tap_name;

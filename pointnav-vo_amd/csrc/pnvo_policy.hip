@@ -717,6 +717,19 @@ static int refuse_plain_entry(const Policy &p, const char *fn) {
                                    "call " + fn + "_rgbd");
 }
 
+// p.pooled [B, ...] -> features_out [B,C,fh,fw] (NCHW): the encoder up to the compression block, channel padding dropped
+static int policy_encode_pooled(Policy &p, int B, float *features_out, hipStream_t s) {
+  const int rc = pnvo_forward_compression(p.enc, p.pooled, B, s);
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  const pnvo_handle m = p.enc;
+  const int P = m->fh * m->fw;
+  const long total = (long)B * P * m->comp_cp;
+  hipLaunchKernelGGL(feature_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->comp_raw, m->ssC[0], m->ssC[1], B, P,
+                     m->comp_c, m->comp_cp, features_out);
+  PCHK(hipGetLastError());
+  return PNVO_OK;
+}
+
 // the shared body of pnvo_policy_act (depth given), pnvo_policy_act_rgbd (obs given) and pnvo_policy_act_features (vfeat given)
 static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *depth, const PolicyObs *obs, const float *vfeat, const float *goal,
                            const int64_t *prev_actions, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features,
@@ -747,8 +760,20 @@ static int policy_act_impl(pnvo_policy_handle h, const char *fn, const float *de
     if ((rc = ensure_pooled(p, B)) != PNVO_OK) return rc;
     if ((rc = obs ? policy_input_stage(p, *obs, B, p.pooled, s) : pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) != PNVO_OK)
       return rc;
-    rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
-    if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+    if (p.attached && !policy_resnet18(c)) {
+      // a frozen non-resnet18 encoder is not attached to the update step: its handle's copy of visual_fc went stale with the first
+      // optimiser step.  The encoder's output goes through the policy's own visual_fc (the flat buffer), as on the visual_features path.
+      if (B > p.cap_feat) {
+        p.feat.reset();
+        p.cap_feat = 0;
+        PCHK(p.feat.alloc((size_t)B * policy_feature_floats(p)));
+        p.cap_feat = B;
+      }
+      if ((rc = policy_encode_pooled(p, B, p.feat, s)) != PNVO_OK || (rc = launch_visual_fc(p, p.feat, B, p.visual, s)) != PNVO_OK) return rc;
+    } else {
+      rc = pnvo_forward_features(p.enc, nullptr, p.pooled, nullptr, nullptr, nullptr, B, p.visual, stream);
+      if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+    }
   } else if ((rc = launch_visual_fc(p, vfeat, B, p.visual, s)) != PNVO_OK) {
     return rc;
   }
@@ -822,6 +847,9 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
       (cfg->normalize != 0 && cfg->normalize != 1) || (cfg->no_depth && cfg->rgb_channels == 0))
     return pfail(PNVO_ERR_ARG, "unsupported policy visual input: rgb_channels " + std::to_string(cfg->rgb_channels) + " (0 or 3), no_depth " +
                                    std::to_string(cfg->no_depth) + " (0, or 1 with rgb), normalize " + std::to_string(cfg->normalize) + " (0 or 1)");
+  // (read behind normalize: zero keeps resnet18; pnvo_create checks the combination)
+  if (cfg->backbone_depth != 0 && cfg->backbone_depth != 18 && cfg->backbone_depth != 50 && cfg->backbone_depth != 101)
+    return pfail(PNVO_ERR_ARG, "unsupported policy backbone_depth " + std::to_string(cfg->backbone_depth) + " (0 / 18, 50 or 101)");
   pnvo_policy_s *h = new pnvo_policy_s();
   h->p.cfg = *cfg;
   h->p.device = device;
@@ -837,6 +865,9 @@ int pnvo_policy_create(const pnvo_policy_config *cfg, int device, pnvo_policy_ha
   ec.n_acts = 4;
   ec.flat_size = cfg->flat_size;
   ec.max_batch = 16;
+  ec.backbone_depth = cfg->backbone_depth;
+  ec.resnext = cfg->resnext;
+  ec.se = cfg->se;
   int rc = pnvo_create(&ec, device, &h->p.enc);
   if (rc != PNVO_OK) {
     delete h;
@@ -954,15 +985,7 @@ static int policy_encode_impl(pnvo_policy_handle h, const char *fn, const float 
   if ((rc = obs ? policy_input_stage(p, *obs, B, p.pooled, (hipStream_t)stream) : pnvo_avgpool2(depth, B, c.height, c.width, p.pooled, stream)) !=
       PNVO_OK)
     return rc;
-  rc = pnvo_forward_compression(p.enc, p.pooled, B, stream);
-  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
-  const pnvo_handle m = p.enc;
-  const int P = m->fh * m->fw;
-  const long total = (long)B * P * m->comp_cp;
-  hipLaunchKernelGGL(feature_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m->comp_raw, m->ssC[0],
-                     m->ssC[1], B, P, m->comp_c, m->comp_cp, features_out);
-  PCHK(hipGetLastError());
-  return PNVO_OK;
+  return policy_encode_pooled(p, B, features_out, (hipStream_t)stream);
 }
 
 int pnvo_policy_encode(pnvo_policy_handle h, const float *depth, int B, float *features_out, void *stream) {

@@ -31,6 +31,8 @@ struct Policy {
   // workspace
   int cap = 0, cap_pooled = 0;       // rows `visual` and `x` hold / frames `pooled` holds (only the entry points that take depth grow it)
   DevBuf<float> pooled, visual, x;
+  DevBuf<float> feat;                // [cap_feat, F]: the encoder's output on its way to visual_fc (policy_visual_from_frames)
+  int cap_feat = 0;
   // the input stage of the rgb / rgb-d / normalised handles (policy_input_stage): per-workgroup partial sums of the moments, the
   // moments [2C] (float64), and the statistics padded to the encoder handle's 2C channels (mean 0, variance 1 on the zero channels)
   DevBuf<double> in_part, m12;
@@ -46,6 +48,9 @@ struct Policy {
 inline int policy_channels(const pnvo_policy_config &c) { return c.rgb_channels + (c.no_depth ? 0 : 1); }
 // today's depth-only, un-normalised policy: the 16-bit-matrix-core stem, the persistent small-batch encoder, the depth-only entry points
 inline bool policy_is_plain(const pnvo_policy_config &c) { return c.rgb_channels == 0 && c.no_depth == 0 && c.normalize == 0; }
+// RL.Policy.backbone other than resnet18 (pnvo_policy_config.backbone_depth / resnext / se): the encoder runs its inference forward only —
+// frozen, never attached to the update step, evaluated from frames as encode + the visual_features path
+inline bool policy_resnet18(const pnvo_policy_config &c) { return (c.backbone_depth == 0 || c.backbone_depth == 18) && !c.resnext && !c.se; }
 inline size_t policy_pooled_floats(const pnvo_policy_config &c, int frames) {
   return (size_t)frames * (c.height / 2) * (c.width / 2) * 2 * policy_channels(c);
 }

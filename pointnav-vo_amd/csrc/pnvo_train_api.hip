@@ -649,6 +649,9 @@ extern "C" {
 int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc, int ntoc) {
   if (!m || !params || !grads || !toc) return pnvo_fail(m, PNVO_ERR_ARG, "null argument");
   if (!m->loaded) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach before pnvo_load_weights");
+  if (m->grouped_se)
+    return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach: SE / ResNeXt backbones have no backward (the grouped conv and the gate are "
+                                        "inference kernels): these encoders run frozen");
   if (n_floats >= (1u << 24)) return pnvo_fail(m, PNVO_ERR_ARG, "flat parameter buffer too large for the index maps");
   HIPCHK(m, hipSetDevice(m->device));
   pnvo_train_free(m);

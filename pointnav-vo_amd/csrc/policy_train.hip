@@ -872,6 +872,9 @@ int pnvo_policy_train_attach(pnvo_policy_handle h, float *params, float *grads, 
     PCHK(t->whhT.alloc((size_t)4 * Hd * Hd));
     PCHK(t->sq_part.alloc(SQ_BLOCKS));
     build_ranges(t, toc, ntoc);
+    // a non-resnet18 encoder stays what pnvo_policy_load_weights made it: frozen, on its own copy of the weights
+    // (pnvo_policy_train_reload_encoder re-reads them from the flat buffer)
+    if (!policy_resnet18(c)) return PNVO_OK;
     const int rc2 = attach_encoder(p, t, ent, toc);
     if (rc2 != PNVO_OK) return rc2;
     // the encoder handle's reports pass through encoder_hook (a no-op until pnvo_policy_set_grad_hook names a receiver)
@@ -898,7 +901,50 @@ int pnvo_policy_train_refresh(pnvo_policy_handle h, void *stream) {
   hipLaunchKernelGGL(stem_pad_kernel, dim3((unsigned)((t->c0 * 2 * t->stem_row + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      t->params + t->o_stem, t->c0, t->stem_row, t->params + t->o_stem2);
   PCHK(hipGetLastError());
+  if (!policy_resnet18(p.cfg)) return PNVO_OK;           // frozen encoder on its own copy of the weights: nothing moved
   const int rc = pnvo_train_refresh(p.enc, stream);
+  if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
+  return PNVO_OK;
+}
+
+int pnvo_policy_train_reload_encoder(pnvo_policy_handle h, const pnvo_tensor_desc *toc, int ntoc, void *stream) {
+  if (!h || !h->p.train || !toc) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
+  Policy &p = h->p;
+  PolicyTrain *t = p.train;
+  if (policy_resnet18(p.cfg)) return pnvo_policy_train_refresh(h, stream);   // attached encoders re-pack on the device
+  PCHK(hipSetDevice(p.device));
+  std::vector<EncoderEntry> ent;
+  int rc = policy_encoder_table(p, toc, ntoc, t->n, &ent);
+  if (rc != PNVO_OK) return rc;
+  PCHK(hipStreamSynchronize((hipStream_t)stream));
+  std::vector<float> host(t->n_named);
+  PCHK(hipMemcpy(host.data(), t->params, t->n_named * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<float> eblob;
+  std::vector<size_t> offs;
+  for (const EncoderEntry &e : ent) {
+    offs.push_back(eblob.size());
+    const size_t cnt = numel(e.shape);
+    if (e.src == EncoderEntry::VIEW) {
+      eblob.insert(eblob.end(), host.begin() + toc[e.k].offset, host.begin() + toc[e.k].offset + cnt);
+    } else {
+      eblob.insert(eblob.end(), cnt, 0.f);
+      if (e.src == EncoderEntry::STEM) {
+        const size_t row = (size_t)t->stem_row;
+        for (int64_t o = 0; o < e.shape[0]; ++o)
+          std::memcpy(&eblob[offs.back() + (size_t)o * 2 * row], host.data() + toc[e.k].offset + o * row, sizeof(float) * row);
+      }
+    }
+  }
+  if (p.cfg.normalize) {
+    const int64_t C2 = 2 * policy_channels(p.cfg);
+    for (int k = 0; k < 2; ++k) {
+      ent.push_back({std::string("visual_encoder.running_mean_and_var.") + (k ? "_var" : "_mean"), {1, C2, 1, 1}, EncoderEntry::ZEROS, -1});
+      offs.push_back(eblob.size());
+      eblob.insert(eblob.end(), (size_t)C2, k ? 1.f : 0.f);
+    }
+  }
+  const std::vector<pnvo_tensor_desc> etoc = encoder_toc(ent, offs);
+  rc = pnvo_load_weights(p.enc, eblob.data(), eblob.size(), etoc.data(), (int)etoc.size());
   if (rc != PNVO_OK) return pfail(rc, std::string("policy visual encoder: ") + pnvo_last_error(p.enc));
   return PNVO_OK;
 }
@@ -944,6 +990,9 @@ static int policy_evaluate_impl(pnvo_policy_handle h, const float *depth, const 
   if (!h || !h->p.train) return pfail(PNVO_ERR_STATE, "pnvo_policy_train_attach first");
   Policy &p = h->p;
   PolicyTrain *t = p.train;
+  if (!vfeat && !policy_resnet18(p.cfg))
+    return pfail(PNVO_ERR_STATE, "evaluate from frames runs the encoder's training forward, which a non-resnet18 backbone does not have: encode the "
+                                 "frames (pnvo_policy_encode / _encode_rgbd) and call pnvo_policy_evaluate_features (RL.DDPPO.train_encoder: False)");
   if (T <= 0 || N <= 0 || (long)T * N > (1L << 20))
     return pfail(PNVO_ERR_ARG, "bad rollout shape T = " + std::to_string(T) + ", N = " + std::to_string(N));
   if (obs)
@@ -1059,6 +1108,8 @@ int pnvo_policy_backward(pnvo_policy_handle h, int train_encoder, void *stream) 
   Policy &p = h->p;
   PolicyTrain *t = p.train;
   if (t->M <= 0 || !t->have_loss) return pfail(PNVO_ERR_STATE, "pnvo_policy_backward before pnvo_policy_evaluate + pnvo_policy_ppo_loss");
+  if (train_encoder && !policy_resnet18(p.cfg))
+    return pfail(PNVO_ERR_STATE, "pnvo_policy_backward: a non-resnet18 encoder has no backward (RL.DDPPO.train_encoder: False)");
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   const pnvo_policy_config &c = p.cfg;

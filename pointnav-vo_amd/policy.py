@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import model_spec as ms
 from .obs_transforms import DIV_CONTIGUOUS, as_transform, launch_resize, transformed_size
 from .registry import baseline_registry
 
@@ -35,7 +36,7 @@ class _Holder(nn.Module):
 
 class pnvo_policy_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "baseplanes", "hidden", "n_actions", "rnn_layers", "flat_size", "rnn_type",
-                                         "rgb_channels", "no_depth", "normalize")]
+                                         "rgb_channels", "no_depth", "normalize", "backbone_depth", "resnext", "se")]
 
 
 # rnn_type -> (pnvo_policy_config.rnn_type, gate blocks per weight, state tensors per layer): torch.nn.LSTM (i, f, g, o; h and c),
@@ -70,14 +71,12 @@ def visual_channels(vis_types):
 
 
 def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_actions=4, rnn_layers=2, flat_size=2048, rnn_type="LSTM",
-                           vis_types=("depth",), normalize_visual_inputs=False):
-    """(name, shape) of every tensor of PointNavResNetPolicy.state_dict() for the resnet18 configuration, in its order; with
-    normalize_visual_inputs the three RunningMeanAndVar buffers come first among the encoder's entries."""
+                           vis_types=("depth",), normalize_visual_inputs=False, backbone="resnet18"):
+    """(name, shape) of every tensor of PointNavResNetPolicy.state_dict(), in its order, for each of the seven backbones of
+    resnet.py:226-286 (model_spec.BACKBONES); with normalize_visual_inputs the three RunningMeanAndVar buffers come first among the
+    encoder's entries."""
     gates = _rnn(rnn_type)[1]
     n_in = sum(visual_channels(vis_types))
-    def half(v):
-        return (v + 1) // 2
-    h, w = height // 2, width // 2                       # F.avg_pool2d(x, 2)
     spec = []
     pre = "net.visual_encoder."
     bb = pre + "backbone."
@@ -85,22 +84,13 @@ def policy_state_dict_spec(*, width, height, baseplanes=32, hidden=512, n_action
         spec += [(RMV_PREFIX + "_mean", (1, n_in, 1, 1)), (RMV_PREFIX + "_var", (1, n_in, 1, 1)), (RMV_PREFIX + "_count", ())]
     spec += [(bb + "conv1.0.weight", (baseplanes, n_in, 7, 7)), (bb + "conv1.1.weight", (baseplanes,)),
              (bb + "conv1.1.bias", (baseplanes,))]
-    h, w = half(half(h)), half(half(w))                  # stem stride 2 + maxpool
-    cin = baseplanes
-    for li in range(1, 5):
-        planes = baseplanes << (li - 1)
-        for bi in range(2):
-            p = f"{bb}layer{li}.{bi}."
-            stride = 2 if (li > 1 and bi == 0) else 1
-            spec += [(p + "convs.0.weight", (planes, cin, 3, 3)), (p + "convs.1.weight", (planes,)),
-                     (p + "convs.1.bias", (planes,)), (p + "convs.3.weight", (planes, planes, 3, 3)),
-                     (p + "convs.4.weight", (planes,)), (p + "convs.4.bias", (planes,))]
-            if stride != 1 or cin != planes:
-                spec += [(p + "downsample.0.weight", (planes, cin, 1, 1)), (p + "downsample.1.weight", (planes,)),
-                         (p + "downsample.1.bias", (planes,))]
-            if stride == 2:
-                h, w = half(h), half(w)
-            cin = planes
+    # the residual stages on the pooled frame (F.avg_pool2d(x, 2), then stem stride 2 + maxpool): the VO models' block table
+    # (model_spec.block_plan: BasicBlock, Bottleneck, ResNeXt and SE blocks)
+    cfg = ms.config_from_kwargs(observation_space={"depth": None}, observation_size=(width // 2, height // 2),
+                                resnet_baseplanes=baseplanes, backbone=backbone)
+    blocks, (cin, h, w) = ms.block_plan(cfg, bb)
+    for prefix, convs, se in blocks:
+        spec += ms.block_spec(prefix, convs, se)
     comp = int(round(flat_size / (h * w)))               # resnet_policy.py:113-117 (python round)
     spec += [(pre + "compression.0.weight", (comp, cin, 3, 3)), (pre + "compression.1.weight", (comp,)),
              (pre + "compression.1.bias", (comp,))]
@@ -129,6 +119,8 @@ def _init(name, shape):
         nn.init.orthogonal_(t) if leaf == "weight" else t.zero_()
     elif name == "net.prev_action_embedding.weight":
         nn.init.normal_(t)
+    elif ".se.excite." in name:                          # ResNetEncoder.layer_init covers the SE branch's Linear layers too
+        nn.init.kaiming_normal_(t, nn.init.calculate_gain("relu")) if leaf == "weight" else t.zero_()
     elif len(shape) in (2, 4):                           # ResNetEncoder.layer_init / torch defaults
         nn.init.kaiming_normal_(t, nn.init.calculate_gain("relu")) if len(shape) == 4 else \
             nn.init.kaiming_uniform_(t, a=math.sqrt(5))
@@ -204,8 +196,10 @@ class PointNavResNetPolicy(nn.Module):
                  num_recurrent_layers=2, rnn_type="LSTM", resnet_baseplanes=32, backbone="resnet18",
                  normalize_visual_inputs=False, obs_transform=None, vis_types=("depth",), **kwargs):
         super().__init__()
-        if backbone != "resnet18":
-            raise NotImplementedError(f"backbone {backbone!r}: the HIP policy implements the resnet18 encoder of ddppo_pointnav.yaml")
+        # resnet.py:226-286: resnet18 | resnet50 | resnet101 | resneXt50 | se_resnet50 | se_resneXt50 | se_resneXt101 (the reference
+        # resolves the name with getattr(resnet, backbone)); every backbone but resnet18 runs frozen (ppo.PolicyTrainStep)
+        self._backbone = backbone
+        self._backbone_fields = ms.backbone_fields(backbone)
         self._rnn_type = rnn_type
         self._rnn_code, _, self._states = _rnn(rnn_type)
         self._n_rgb, self._n_depth = visual_channels(vis_types)
@@ -241,7 +235,7 @@ class PointNavResNetPolicy(nn.Module):
         self._spec = policy_state_dict_spec(width=self._W, height=self._H, baseplanes=self._baseplanes,
                                             hidden=self._hidden, n_actions=self.dim_actions, rnn_layers=self._layers,
                                             rnn_type=rnn_type, vis_types=tuple(vis_types),
-                                            normalize_visual_inputs=self._normalize)
+                                            normalize_visual_inputs=self._normalize, backbone=backbone)
         for name, shape in self._spec:
             parts = name.split(".")
             mod = self
@@ -322,7 +316,8 @@ class PointNavResNetPolicy(nn.Module):
             cc = pnvo_policy_config(width=self._W, height=self._H, baseplanes=self._baseplanes, hidden=self._hidden,
                                     n_actions=self.dim_actions, rnn_layers=self._layers, flat_size=2048,
                                     rnn_type=self._rnn_code, rgb_channels=self._n_rgb, no_depth=int(self._n_depth == 0),
-                                    normalize=int(self._normalize))
+                                    normalize=int(self._normalize), backbone_depth=self._backbone_fields[0],
+                                    resnext=self._backbone_fields[1], se=self._backbone_fields[2])
             h = C.c_void_p()
             _lib.check(_lib.lib.pnvo_policy_create(C.byref(cc), int(device.index or 0), C.byref(h)))
             self._handle, self._handle_dev, self._loaded_sig = h, device.index, None

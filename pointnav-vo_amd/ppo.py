@@ -22,8 +22,12 @@ pnvo_policy_set_grad_hook, between `backward()` and `optimizer_step()`, and the 
 `rollouts` is rollout_storage.RolloutStorage (the reference's class on the device: insert, compute_returns and the minibatch gather
 are one launch each); the agent reads only `returns`, `value_preds` and `recurrent_generator`.
 
-Not here: the DD-PPO trainer and its pre-emption logic, an autograd bridge for the reference's own PPO.update, non-resnet18
-backbones.  No CPU fallback.
+A policy on another backbone than resnet18 (resnet50 .. se_resneXt101) trains with a FROZEN encoder only (RL.DDPPO.train_encoder:
+False, the setting the distributed DD-PPO encoders come with): evaluate_actions on frames is net.visual_encoder's inference forward
+followed by the visual_features path, and train_encoder=True is refused before anything is launched.
+
+Not here: the DD-PPO trainer and its pre-emption logic, an autograd bridge for the reference's own PPO.update, the encoder's backward
+for Bottleneck / ResNeXt / SE policies.  No CPU fallback.
 """
 import ctypes as C
 
@@ -66,6 +70,11 @@ class PolicyTrainStep:
         self.lr, self.eps, self.betas = float(lr), float(eps), tuple(betas)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.train_encoder = bool(train_encoder)
+        self._frozen_backbone = getattr(policy, "_backbone", "resnet18") != "resnet18"
+        if self._frozen_backbone and self.train_encoder:
+            raise NotImplementedError(f"backbone {policy._backbone!r}: the encoder's backward exists for resnet18 only; train this policy "
+                                      "with a frozen encoder (RL.DDPPO.train_encoder: False — no parameter of net.visual_encoder with "
+                                      "requires_grad, or PolicyTrainStep(..., train_encoder=False))")
         ref = next(policy.parameters())
         if ref.device.type != "cuda":
             raise RuntimeError("PolicyTrainStep runs on an MI355X only: move the policy with .to('cuda') first "
@@ -121,6 +130,9 @@ class PolicyTrainStep:
     def _repack(self):
         """The kernel operands (the padded stem, the encoder's packed weights) from the flat buffer as it is now."""
         with torch.cuda.device(self.dev):
+            if self._frozen_backbone:                          # the encoder keeps its own copy of the weights: re-read it from the flat buffer
+                _lib.check(_lib.lib.pnvo_policy_train_reload_encoder(self.policy._handle, self.store.toc, len(self.store.named),
+                                                                     self._stream()))
             for _ in range(3):                                 # three: flat_params.py, "The owner's part"
                 _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, self._stream()))
         torch.cuda.current_stream(self.dev).synchronize()
@@ -144,6 +156,10 @@ class PolicyTrainStep:
         # before it whitens: once per minibatch, as the reference's evaluate_actions does); checked before any launch
         vis, from_features = pol._visual_input(observations, dev)
         self._sync_params()
+        if self._frozen_backbone and not from_features:
+            # no training forward for this encoder, and none needed: frozen, its output is what the inference forward gives (in training
+            # mode RunningMeanAndVar merges the minibatch first, once, as the reference's evaluate_actions does)
+            vis, from_features = pol._encode(observations), True
         M = vis.shape[0]
         hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
         N = hin.shape[1]

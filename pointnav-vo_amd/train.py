@@ -42,6 +42,9 @@ class VOTrainStep:
     def __init__(self, model, lr=2.5e-4, eps=1e-8, betas=(0.9, 0.999), dropout_seed=0):
         self.model = model
         self.lr, self.eps, self.betas = float(lr), float(eps), betas
+        if model.cfg.resnext or model.cfg.se:
+            raise NotImplementedError("VOTrainStep: SE / ResNeXt backbones have no backward (the grouped conv and the squeeze-and-excite "
+                                      "gate are inference kernels); resnet18 / resnet50 / resnet101 models train")
         ref = next(model.parameters())
         if ref.device.type != "cuda":
             raise RuntimeError("VOTrainStep runs on an MI355X only: move the model with .to('cuda') first")

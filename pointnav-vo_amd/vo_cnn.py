@@ -95,6 +95,8 @@ class VisualOdometryCNNBase(nn.Module):
         normalisation statistics; resnet18 models).  Applies to the eval-mode forward and to dual_forward()."""
         if precision not in ("float32", "bfloat16"):
             raise ValueError(precision)
+        if precision == "bfloat16" and (self.cfg.resnext or self.cfg.se):
+            raise NotImplementedError('precision="bfloat16": SE / ResNeXt backbones run in float32 only')
         self._precision = precision
         if self._handle is not None:
             _lib.check(_lib.lib.pnvo_set_precision(self._handle, int(precision == "bfloat16")), self._handle)
@@ -169,7 +171,7 @@ class VisualOdometryCNNBase(nn.Module):
                               n_tdv=c.n_tdv, baseplanes=c.baseplanes, hidden=c.hidden, out_dim=c.out_dim,
                               normalize=int(c.normalize), act_embed=int(c.act_embed), n_acts=c.n_acts,
                               flat_size=c.after_compression_flat_size, max_batch=0,
-                              backbone_depth=c.backbone_depth)
+                              backbone_depth=c.backbone_depth, resnext=int(c.resnext), se=int(c.se))
         h = C.c_void_p()
         _lib.check(_lib.lib.pnvo_create(C.byref(cc), int(device.index or 0), C.byref(h)))
         self._handle, self._handle_dev, self._loaded_sig = h, device.index, None

@@ -2,6 +2,9 @@
 """Per-step latency / throughput of the HIP navigation policy (PointNavResNetPolicy.act)
 at the batch sizes a nav loop uses (B = environments per process), with the oracle port timed beside it.
     python tools/bench_policy.py [--envs 1 4 16 64] [--rnn {LSTM,GRU}] [--visual-types depth | rgb depth | rgb] [--rgb-dtype {uint8,float32}]
+                                 [--backbone NAME] [--encode-frames N]
+--backbone: any of model_spec.BACKBONES (resnet50 .. se_resneXt101; no oracle port of them: the CPU baseline is skipped).
+--encode-frames N also times net.visual_encoder on N frames (the frozen-encoder collection's call shape).
 --rnn GRU times the GRU state encoder instead (no oracle port of it: the CPU baseline is skipped).
 --visual-types with rgb builds the policy as the reference trainers do (normalize_visual_inputs on, ddppo_trainer.py:118-132) and runs it
 in training mode, as PPOTrainer's collection does: every act merges its batch into RunningMeanAndVar's buffers.  The input stage is
@@ -74,20 +77,25 @@ def main():
     ap.add_argument("--rnn", choices=["LSTM", "GRU"], default="LSTM")
     ap.add_argument("--visual-types", nargs="+", choices=["rgb", "depth"], default=["depth"])
     ap.add_argument("--rgb-dtype", choices=["uint8", "float32"], default="uint8")
+    ap.add_argument("--backbone", default="resnet18")
+    ap.add_argument("--encode-frames", type=int, default=0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     vis = [k for k in ("rgb", "depth") if k in a.visual_types]
     plain = vis == ["depth"]
     space = Space({"depth": Box((H, W, 1)), "rgb": Box((H, W, 3)), "pointgoal_with_gps_compass": Box((2,))})
     pol = PointNavResNetPolicy(observation_space=space, action_space=Act(), hidden_size=512, rnn_type=a.rnn,
-                               num_recurrent_layers=2, backbone="resnet18", vis_types=vis, normalize_visual_inputs=not plain)
+                               num_recurrent_layers=2, backbone=a.backbone, vis_types=vis, normalize_visual_inputs=not plain)
     kw = {} if plain else dict(vis_types=tuple(vis), normalize_visual_inputs=True)
+    kw["backbone"] = a.backbone
     sd = synth.make_state_dict(policy_state_dict_spec(width=W, height=H, rnn_type=a.rnn, **kw), seed=0)
     pol.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
     pol = pol.to(dev).train(not plain)
     res = {"metric": "navigation-policy act() steps", "frame": f"{W}x{H} {'+'.join(vis)}", "dtype": "f32", "results": []}
     if a.rnn != "LSTM":
         res["rnn"] = a.rnn
+    if a.backbone != "resnet18":
+        res["backbone"] = a.backbone
     if not plain:
         res["rgb_dtype"], res["mode"] = a.rgb_dtype, "training (statistics updated at every act)"
     for B in a.envs:
@@ -114,7 +122,23 @@ def main():
         if not plain:
             row["input_stage"] = input_stage(pol, obs, vis, B, dev, dt * 1e3)
         res["results"].append(row)
-    if not a.no_cpu_baseline and a.rnn == "LSTM":
+    if a.encode_frames > 0:
+        n = a.encode_frames
+        frames = {k: (torch.from_numpy(synth.uniform(3, k, (n, H, W, 1), 0.0, 1.0).astype(np.float32)) if k == "depth" else
+                      torch.from_numpy((synth.bits(3, k, n * H * W * 3) % np.uint64(256)).astype(np.uint8).reshape(n, H, W, 3))).to(dev)
+                  for k in vis}
+        enc = pol.net.visual_encoder
+        for _ in range(3):
+            enc(frames)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reps = max(3, a.steps // 5)
+        for _ in range(reps):
+            enc(frames)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        res["visual_encoder"] = {"frames": n, "ms": dt * 1e3, "frames_per_s": n / dt}
+    if not a.no_cpu_baseline and a.rnn == "LSTM" and a.backbone == "resnet18":
         from oracle import oracle, policy_oracle
         B = 4
         depth, goal, prev, mask = synth.make_policy_inputs(H, W, B, 1, 1)[0]
