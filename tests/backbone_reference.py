@@ -1,5 +1,6 @@
 """CPU model of the Bottleneck / ResNeXt / SE-ResNeXt encoders (resnet.py:58-286) and of the navigation policy and VO model around
-them, for tests/test_policy_backbones_host.py and tests/test_gpu_policy_backbones.py (TEST INFRASTRUCTURE ONLY).
+them, for tests/test_policy_backbones_host.py, tests/test_gpu_policy_backbones.py and the batch-regime modules
+tests/test_gpu_backbone_regimes.py / tests/test_backbone_regimes_host.py (TEST INFRASTRUCTURE ONLY).
 
 oracle.torch_train_ref.forward knows BasicBlock and the plain Bottleneck; it has no grouped conv and no squeeze-and-excite branch.
 `encoder_forward` below restates the whole VO-model forward with both, from torch primitives alone (F.conv2d(groups=), F.group_norm,
@@ -231,9 +232,9 @@ def ppo_reference(dtype="float64"):
 
 
 # ---- the VO model
-def vo_spec():
-    cfg = ms.config_from_kwargs(observation_space=VO["space"], observation_size=(VO["W"], VO["H"]), hidden_size=VO["hidden"],
-                                backbone=VO["backbone"], normalize_visual_inputs=True, output_dim=3,
+def vo_spec(backbone=None, W=None, H=None):
+    cfg = ms.config_from_kwargs(observation_space=VO["space"], observation_size=(W or VO["W"], H or VO["H"]), hidden_size=VO["hidden"],
+                                backbone=backbone or VO["backbone"], normalize_visual_inputs=True, output_dim=3,
                                 discretized_depth_channels=VO["dd_bins"])
     return cfg, ms.state_dict_spec(cfg)
 
@@ -253,6 +254,141 @@ def vo_forward(sd, obs, dtype="float64"):
     with torch.no_grad():
         out, _ = encoder_forward(params, params, {k: torch.as_tensor(v) for k, v in obs.items()}, ngroups=cfg.ngroups, train=False, dtype=dt)
     return out.double().numpy()
+
+
+# ---- the batch-regime pool (tests/test_gpu_backbone_regimes.py and tests/test_backbone_regimes_host.py)
+POOL_P, POOL_A = 31, 12                                   # a prime pool and a stride coprime to it
+REGIME_TOL = 2e-4                                         # of each position's own scale (tests/test_gpu_policy.py's bound)
+REF32_TOL = REGIME_TOL / 4                                # what the float32 restatement itself has to stay under on the pool
+EVEN_H, EVEN_W = 128, 128                                 # policy frames with even maps all the way down: 16x16, 8x8, 4x4, 2x2
+ZERO_BORDER = (3, 14, 22, 29)                             # pool samples with a zero border of 2, 4, 6, 8 pixels
+FLAT = dict(constant=7, two_level=19, ripple=27)         # pool samples with (nearly) no variance: see _pool_edges
+ZERO_MASK = (0, 5, 17, 26)                                # pool samples whose episode starts (mask 0) in the policy pool
+VO_TAPS = ("layer1.0", "layer1.1", "layer2.0", "layer2.1", "layer3.0", "layer3.1", "layer4.0", "layer4.1")
+POLICY_KEYS = ("encoder", "features", "hidden", "logits", "value")
+POSITION_AXIS = {"hidden": 1}                             # the recurrent state is [states, B, hidden]; everything else [B, ...]
+
+
+def positions(B):
+    """Pool sample of every position of a batch of B: (A i + c_B) mod P.  Two positions closer than P hold different samples, and the
+    offset c_B differs between any two batches the regime modules use."""
+    return (POOL_A * np.arange(B) + 7 * B + 22 * (B // POOL_P)) % POOL_P
+
+
+def _pool_edges(frames):
+    """Zero borders and flat frames, in place, on {name: [P,H,W,C]} (depth in 0..1, rgb in 0..255).  Flat frames give tiny GroupNorm
+    variances: one constant frame (depth 0.25, rgb 64), one of two constant halves, one with a 1 - 2 % ripple around a constant.
+    (A constant frame is ill-conditioned at every level: the float32 restatement sits at 2e-5 .. 4e-4 of scale on it against 2 - 6e-6
+    on a textured frame, depending on the level and the model; (0.25, 64) is the level that stays below 3e-5 on every model of the
+    regime modules, the others were measured at 0, 0.1, 0.45, 0.6, 0.8 and 1.)"""
+    for n, i in enumerate(ZERO_BORDER):
+        z = 2 * (n + 1)
+        for v in frames.values():
+            v[i, :z] = 0
+            v[i, -z:] = 0
+            v[i, :, :z] = 0
+            v[i, :, -2 * z:] = 0
+    for k, v in frames.items():
+        rgb = k == "rgb"
+        half = v.shape[1] // 2
+        v[FLAT["constant"]] = 64 if rgb else 0.25
+        v[FLAT["two_level"], :half] = 60 if rgb else 0.3
+        v[FLAT["two_level"], half:] = 200 if rgb else 0.7
+        r = v[FLAT["ripple"]].astype(np.float64)
+        v[FLAT["ripple"]] = (128 + 0.02 * (r - 128)) if rgb else (0.45 + 0.01 * (r - 0.5))
+
+
+def policy_pool(H=H, W=W, seed=86):
+    """POOL_P distinct act-step samples: rgb uint8 [P,H,W,3], depth [P,H,W,1], goal, prev, mask (zero at ZERO_MASK) and a non-zero
+    incoming LSTM state [2 L, P, HIDDEN]; ZERO_BORDER frames with a zero border, FLAT frames flat.  The value is one number per
+    position, judged on its own scale: the seed is the first of 81, 84, 85, 86, 87 (float64 restatement, CPU) with no position's
+    |value| below 9e-3 on any model of the regime modules."""
+    rgb, depth, goal, prev, _ = synth.make_policy_rgbd_inputs(H, W, POOL_P, 1, seed, N_ACT)[0]
+    _pool_edges({"rgb": rgb, "depth": depth})
+    mask = np.ones(POOL_P, np.float32)
+    mask[list(ZERO_MASK)] = 0.0
+    h0 = synth.uniform(seed, "h0", (LAYERS, POOL_P, HIDDEN), -1.0, 1.0)
+    c0 = synth.uniform(seed, "c0", (LAYERS, POOL_P, HIDDEN), -3.0, 3.0)
+    return dict(rgb=rgb, depth=depth, goal=goal, prev=prev, mask=mask, hidden=np.concatenate([h0, c0]).astype(np.float32))
+
+
+def vo_pool(H, W, seed=82):
+    """POOL_P distinct observation pairs of the VO case's modalities: float16-rounded depth in the first half, dense float32 depth in the
+    second, the same edge frames as policy_pool."""
+    half = POOL_P // 2
+    a = synth.make_obs_pairs(half, H, W, observation_space=list(VO["space"]), dd_bins=1, seed=seed, depth_fp16=True)
+    b = synth.make_obs_pairs(POOL_P - half, H, W, observation_space=list(VO["space"]), dd_bins=1, seed=seed, depth_fp16=False, start=half)
+    pool = {k: np.concatenate([a[k], b[k]]) for k in a}
+    _pool_edges(pool)
+    return pool
+
+
+@functools.lru_cache(maxsize=None)
+def pool_state_dict(backbone, vis, normalize, H=H, W=W):
+    """Synthetic LSTM-policy weights at a frame size of the regime modules; shared, read-only."""
+    return synth.make_state_dict(spec(backbone=backbone, vis=tuple(vis), normalize=normalize, rnn="LSTM", H=H, W=W), seed=WEIGHT_SEED)
+
+
+def position_err(got, want, axis=0):
+    """max |got - want| / (max |want| + 1e-6) of every position along `axis`, each on its own scale -> float64 numpy [positions].
+    Takes numpy arrays or torch tensors (computed where `want` lives); a non-finite value gives a non-finite error."""
+    want = torch.as_tensor(want)
+    got = torch.as_tensor(got).to(device=want.device, dtype=torch.float64).reshape(want.shape)
+    want = want.to(torch.float64)
+    d = (got - want).abs().movedim(axis, 0).reshape(want.shape[axis], -1).amax(1)
+    s = want.abs().movedim(axis, 0).reshape(want.shape[axis], -1).amax(1)
+    return (d / (s + 1e-6)).cpu().numpy()
+
+
+def policy_pool_reference(sd, pool, vis, dtype="float64"):
+    """One restatement act step over the pool (every sample is independent of the others: GroupNorm, the SE squeeze and the recurrent
+    core work per sample) -> {POLICY_KEYS: float64 numpy}."""
+    r = policy_step(sd, {k: pool[k] for k in vis}, pool["goal"], pool["prev"], pool["mask"], pool["hidden"], "LSTM", dtype)
+    return {k: r[k] for k in POLICY_KEYS}
+
+
+def vo_pool_reference(sd, cfg, pool, taps, dtype="float64"):
+    """The VO restatement over the pool -> {'pose': [P,3], 'encoder' and each of `taps`: NHWC float64 numpy, as model.tap returns them}."""
+    dt = getattr(torch, dtype)
+    params = {k: torch.as_tensor(np.asarray(v)).to(dt) for k, v in sd.items()}
+    rec = {}
+    with torch.no_grad():
+        out, _ = encoder_forward(params, params, {k: torch.as_tensor(v) for k, v in pool.items()}, ngroups=cfg.ngroups, train=False,
+                                 dtype=dt, record=rec)
+    res = {"pose": out.double().numpy()}
+    for k in tuple(taps) + ("encoder",):
+        res[k] = rec[k].permute(0, 2, 3, 1).double().contiguous().numpy()
+    return res
+
+
+def pool_sequence(pool, T=4, N=32, seed=83):
+    """A T-major evaluate_actions input of T x N depth frames drawn from the pool by positions(T N): every episode starts at t = 0,
+    every fifth environment resets again at t = T / 2; a non-zero incoming state."""
+    M = T * N
+    idx = positions(M)
+    masks = np.ones((T, N), np.float32)
+    masks[0] = 0.0
+    masks[T // 2, 1::5] = 0.0
+    h0 = synth.uniform(seed, "h0", (LAYERS, N, HIDDEN), -1.0, 1.0)
+    c0 = synth.uniform(seed, "c0", (LAYERS, N, HIDDEN), -3.0, 3.0)
+    return dict(depth=pool["depth"][idx], goal=pool["goal"][idx], prev=pool["prev"][idx], masks=masks.reshape(-1),
+                actions=(synth.bits(seed, "taken", M) % np.uint64(N_ACT)).astype(np.int64),
+                hidden=np.concatenate([h0, c0]).astype(np.float32), T=T, N=N)
+
+
+def sequence_reference(sd, inp, dtype="float64"):
+    """The restatement's evaluate_actions forward -> value [M], logp [M], entropy [1], hidden [2 L, N, HIDDEN] (float64 numpy)."""
+    dt = getattr(torch, dtype)
+    params, bufs = G.split(sd)
+    with policy() as g, torch.no_grad():
+        value, logp, entropy, hidden = g.forward(G.R.leaves(params, dt), bufs, inp, dt, "LSTM", False)[:4]
+    f = lambda t: t.double().numpy()
+    return dict(value=f(value), logp=f(logp), entropy=f(entropy).reshape(1), hidden=f(hidden))
+
+
+def worst_ref32(ref64, ref32):
+    """Worst per-position error of the float32 restatement against the float64 one over a pool reference -> {key: error}."""
+    return {k: float(position_err(ref32[k], v, POSITION_AXIS.get(k, 0)).max()) for k, v in ref64.items()}
 
 
 if __name__ == "__main__":
