@@ -278,24 +278,6 @@ bool x3_two_pieces(pnvo_handle m, const Layer &l) {
     return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l.name + ".weight") != nullptr;
   return m->opt.pieces == 2;
 }
-// The conv_x3 problem of layer l at B samples: shape, operand pieces and handle m's plan options; stager mode 0, no tail, no ride.
-ConvX3Problem x3_problem(pnvo_handle m, const Layer &l, int B) {
-  ConvX3Problem q{.B = B, .H = l.hin, .W = l.win, .CIN = l.cinp, .Ho = l.hout, .Wo = l.wout, .COUTP = l.coutp, .ks = l.k, .stride = l.stride};
-  q.np = x3_two_pieces(m, l) ? 2 : 3;
-  q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = m->opt.x3_fine, .w8 = m->opt.x3_w8, .m16 = m->opt.x3_m16,
-           .ksw = m->opt.x3_ksplit, .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0, .rows = m->opt.x3_rows, .num_cus = m->num_cus};
-  return q;
-}
-// The plan of l on the tile kernels (the rows form, which a launch may take in their place, aside): whether conv_x3.hip has the layer
-// at B samples, its statistics slots and executed FLOPs.  ds: with the block's downsample conv riding on it.
-ConvX3Plan x3_tile_plan(pnvo_handle m, const Layer &l, int B, bool ds = false, bool force = false) {
-  ConvX3Problem q = x3_problem(m, l, B);
-  q.ds = ds;
-  q.opt.rows = 0;
-  if (force) q.opt.force = 1;
-  return conv_x3_plan(q);
-}
-
 // The implicit-GEMM geometry of layer l at B samples, the rest of the launch zero.
 void conv_geometry(const Layer &l, int B, int y_cstride, ConvArgs &a) {
   std::memset(&a, 0, sizeof(a));
@@ -315,26 +297,88 @@ void conv_geometry(const Layer &l, int B, int y_cstride, ConvArgs &a) {
   a.up = 1;
 }
 
-// Would this (GroupNorm-ed, bias-free) conv layer run on the LDS-staged 3x3 kernel?  *slots: its statistics slots.
-bool layer_on_lds(pnvo_handle m, const Layer &l, int *slots) {
-  ConvArgs a;
-  conv_geometry(l, 0, l.coutp, a);
-  if (!conv3_lds_supported(a) || m->opt.conv == 3) return false;
-  if (slots) *slots = conv3_lds_slots(a);
-  return true;
+// launch timing of a conv of l at B samples: algorithmic flops and bytes
+double conv_flops(const Layer &l, int B) { return 2.0 * ((double)((long)B * l.hout * l.wout) * l.cout * (l.cin / l.cgroups) * l.k * l.kw); }
+double conv_bytes(const Layer &l, int B) {
+  return 4.0 * ((double)B * l.hin * l.win * l.cin + (double)((long)B * l.hout * l.wout) * l.cout + (double)l.cout * l.cin * l.k * l.kw);
 }
 
-size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
-  const long P = (long)l.hout * l.wout, M = (long)B * P;
-  int MT, NT;
-  choose_tile(M, l.coutp, &MT, &NT);
-  if (l.cgroups > 1) return (size_t)B * (size_t)conv_group_slots((int)P) * l.coutp * 2;   // conv_group.hip: one slot per 32 pixels
-  int slots = conv_slots((int)P, MT), s2 = 0;
-  if (layer_on_lds(m, l, &s2) && s2 > slots) slots = s2;            // conv3_lds: slots = tiles x waves
-  if ((l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || l.stride == 2)) || (l.k == 1 && l.stride == 2)) {   // conv_x3: slots = tiles
-    const ConvX3Plan p = x3_tile_plan(m, l, B, false, true);   // (sized for the forced plan: option conv may change between forwards)
-    if (p && p.slots > slots) slots = p.slots;
+// The block's downsample conv cd rides on its first 3x3 conv c1 when both run on the float16-piece form of conv_x3_kernel and share the
+// output geometry (they always do: resnet.py:189-212), in the inference and the training forward alike (the training forward still
+// writes the block input: its backward pass reads it), and not while a tap wants the plain schedule.  (c1's side — 3x3, stride 2, two
+// float16 pieces — is the plan's to refuse: conv_x3_plan.)
+bool ride_fits(pnvo_handle m, const Layer &c1, const Layer &cd) {
+  if (!m->opt.ds_fuse || m->tap_dst != nullptr || m->bottleneck || cd.k != 1 || cd.kw != 1 || cd.stride != 2 || cd.pad != 0) return false;
+  if (c1.cinp != cd.cinp || c1.coutp != cd.coutp || c1.cout != cd.cout || c1.hout != cd.hout || c1.wout != cd.wout || c1.hin != cd.hin ||
+      c1.win != cd.win || c1.cout != c1.coutp || c1.groups != cd.groups || cd.host_w.empty())
+    return false;
+  return x3_layer(m, cd) && x3_two_pieces(m, cd);
+}
+}  // namespace
+
+// Which kernel family runs conv l at B samples for this ask, and what follows from that.  The one place that decides it.
+ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk &ask) {
+  ConvChoice c;
+  const int P = l.hout * l.wout;
+  c.flops = conv_flops(l, B);
+  if (l.cgroups > 1) {           // conv_group.hip: 32-pixel slots x slabs of max(cg, 16) channels, dense inside a slab
+    c.family = ConvChoice::GROUP;
+    c.slots = conv_group_slots(P);
+    c.flops = 2.0 * B * c.slots * 32.0 * l.cout * (double)std::max(l.cin / l.cgroups, 16) * 9.0;
+    return c;
   }
+  // GroupNorm-ed 3x3 and 1x1 stride-2 convs: float32 results from the 16-bit matrix cores (conv_x3.hip) where its planner takes the
+  // launch; option conv=fp32 keeps the fp32-MFMA kernels.
+  const bool dense_gn = ask.gn && !ask.plain;
+  if (dense_gn && l.groups > 0 && x3_layer(m, l) && (ask.ride == nullptr || ride_fits(m, l, *ask.ride))) {
+    // The schedule's rule, kept as it stood before this value existed: forward_body, the training forward and pnvo_layer_kernel decide
+    // tails, rides and the small-generic pre-pass per LAYER, before a stager mode is known, so they ask about the tile kernels on the
+    // plain stager (a default ask: mode 0) with the rows form off.  Only the launch's own ask (conv_ask: rows_form) lets
+    // conv_rows32_kernel take the tile plan's place — with fewer statistics slots than the tile plan the buffer is sized for.
+    const bool tile_kernels_only = !ask.rows_form;
+    // The conv_x3 problem: shape, operand pieces, stager mode and handle m's plan options.  (tail_scaled: the rows plan refuses a block
+    // tail whose skip branch carries its own GroupNorm — a downsample skip, reachable with baseplanes 16: the rows kernel adds the raw skip tensor)
+    ConvX3Problem q{.B = B, .H = l.hin, .W = l.win, .CIN = l.cinp, .Ho = l.hout, .Wo = l.wout, .COUTP = l.coutp, .ks = l.k, .stride = l.stride,
+                    .np = x3_two_pieces(m, l) ? 2 : 3, .mode = ask.tail == ConvAsk::KEYS ? 3 : ask.tail != ConvAsk::NONE ? 2 : ask.affine ? 1 : 0,
+                    .tail_scaled = ask.tail == ConvAsk::SKIP_SCALED, .ds = ask.ride != nullptr};
+    q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = m->opt.x3_fine, .w8 = m->opt.x3_w8, .m16 = m->opt.x3_m16,
+             .ksw = m->opt.x3_ksplit, .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0, .rows = tile_kernels_only ? 0 : m->opt.x3_rows,
+             .num_cus = m->num_cus};
+    if (const ConvX3Plan p = conv_x3_plan(q)) {
+      c.family = ConvChoice::X3;
+      c.x3q = q;
+      c.x3p = p;
+      c.slots = p.slots;
+      // tiles x M-tiles x 32 pixels (the 16x16x32 flavour of x2: 16-row sub-tiles x 16) x padded outputs x K, six bf16 (x3) or three float16 (x2) MFMA terms per float32 product
+      if (p.family != ConvX3Plan::ROWS)
+        c.flops = (p.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * p.tiles_r * p.tiles_c * (double)p.m_rows * l.coutp * (double)l.cinp * l.k * l.kw;
+      return c;
+    }
+  }
+  // The float32-MFMA kernels: the LDS-staged 3x3 conv (input patch staged in LDS; slots = tiles x waves), else the generic implicit GEMM
+  ConvArgs a;
+  conv_geometry(l, B, l.coutp, a);
+  choose_tile((long)B * P, l.coutp, &c.MT, &c.NT);
+  const bool lds = dense_gn && m->opt.conv != 3 && conv3_lds_supported(a);
+  c.family = lds ? ConvChoice::FP32_LDS : ConvChoice::FP32_GENERIC;
+  c.slots = lds ? conv3_lds_slots(a) : conv_slots(P, c.MT);
+  return c;
+}
+
+bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
+  // taps want the block outputs of the plain schedule; option tail=separate: the pass of its own
+  return m->tap_dst == nullptr && m->opt.tail && pnvo_conv_choice(m, l, B, {}).family == ConvChoice::X3;
+}
+
+namespace {
+// GroupNorm partials of l at B samples: the most slots of the families an option change can select without the workspace regrowing
+// (generic, LDS, the forced tile plan — stride 2 included —, group)
+size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
+  const PnvoOptions saved = m->opt;
+  int slots = 0;
+  m->opt.x3_s2 = 1;
+  for (m->opt.conv = 1; m->opt.conv <= 3; ++m->opt.conv) slots = std::max(slots, pnvo_conv_choice(m, l, B, {}).slots);   // x3 | fp32 | generic
+  m->opt = saved;
   return (size_t)B * (size_t)slots * l.coutp * 2;
 }
 
@@ -473,35 +517,7 @@ void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &
   h->convs[h->comp].in_bound = bin;                          // the compression conv reads the last block's output
 }
 
-bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B) {
-  return x3_layer(m, l) && l.groups > 0 && x3_tile_plan(m, l, B);
-}
-
-// The block's downsample conv rides on its first 3x3 conv when both run on the float16-piece form of conv_x3_kernel and share the
-// output geometry (they always do: resnet.py:189-212), in the inference and the training forward alike (the training forward still
-// writes the block input: its backward pass reads it), and not while a tap wants the plain schedule.
-bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B) {
-  if (!m->opt.ds_fuse || m->tap_dst != nullptr || m->bottleneck) return false;
-  if (c1.k != 3 || c1.kw != 3 || c1.stride != 2 || c1.pad != 1 || cd.k != 1 || cd.kw != 1 || cd.stride != 2 || cd.pad != 0) return false;
-  if (c1.cinp != cd.cinp || c1.coutp != cd.coutp || c1.cout != cd.cout || c1.hout != cd.hout || c1.wout != cd.wout || c1.hin != cd.hin ||
-      c1.win != cd.win || c1.cout != c1.coutp || c1.groups != cd.groups || c1.groups <= 0 || cd.host_w.empty())
-    return false;
-  if (!x3_layer(m, c1) || !x3_layer(m, cd) || !x3_two_pieces(m, c1) || !x3_two_pieces(m, cd)) return false;
-  return (bool)x3_tile_plan(m, c1, B, true);
-}
-
-bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
-  if (m->tap_dst != nullptr || !m->opt.tail) return false;   // taps want the block outputs of the plain schedule; option tail=separate: the pass of its own
-  return pnvo_conv_on_x3(m, l, B);
-}
-
 namespace {
-// launch timing of a conv of l at B samples: algorithmic flops and bytes
-double conv_flops(const Layer &l, int B) { return 2.0 * ((double)((long)B * l.hout * l.wout) * l.cout * (l.cin / l.cgroups) * l.k * l.kw); }
-double conv_bytes(const Layer &l, int B) {
-  return 4.0 * ((double)B * l.hin * l.win * l.cin + (double)((long)B * l.hout * l.wout) * l.cout + (double)l.cout * l.cin * l.k * l.kw);
-}
-
 // The conv_x3 weight operand of layer q of handle h in `pieces` pieces (2: float16 and the inverse of their scale, 3: bf16), rebuilt
 // when h's weights moved since it was made: re-packed on the device from the flat parameters of an attached training step (weight
 // and float16 scale live there: pnvo_train_refresh), else packed on the host and uploaded.
@@ -529,15 +545,27 @@ int x3_operand(pnvo_handle h, Layer &q, int pieces, hipStream_t s) {
   return PNVO_OK;
 }
 
-// conv_x3_kernel / conv_x3p_kernel, or conv_rows32_kernel (rows), on plan p of problem q, + the GroupNorm finalisation unless the conv does it.
-int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvX3Problem &q, const ConvX3Plan &p) {
+// The GroupNorm finalisation behind a conv (or stem) of l that left `slots` partials per sample in m->stats — wave_rows > 0: the generic
+// kernel's flattened wave tiles of that many pixels.
+int finalize_gn(pnvo_handle m, const Layer &l, int B, int slots, int wave_rows, float *const *ss, float *mu, float *rstd, hipStream_t s,
+                const GnGroup *gg = nullptr) {
+  Timed t(m, s, "gn_finalize", 0.0, 0.0);
+  HIPCHK(m, launch_gn_finalize(m->stats, B, slots, l.coutp, l.cout, l.groups, (long)l.hout * l.wout, wave_rows ? wave_rows : 1, l.gamma, l.beta, 1e-5f,
+                               ss[0], ss[1], s, wave_rows ? 0 : slots, mu, rstd, gg));
+  return PNVO_OK;
+}
+
+// conv_x3_kernel / conv_x3p_kernel, or conv_rows32_kernel (rows), on the choice's plan, + the GroupNorm finalisation unless the conv does it.
+int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvChoice &c) {
+  const ConvX3Problem &q = c.x3q;
+  const ConvX3Plan &p = c.x3p;
   hipStream_t s = r.s;
   const DsRide *ride = r.ride;
   const bool two = q.np == 2, rows = p.family == ConvX3Plan::ROWS;
   ConvX3Args xa = conv_x3_args(q, p);
   Layer &lm = const_cast<Layer &>(l);
   if (int rc = x3_operand(m, lm, q.np, s)) return rc;
-  if (ride != nullptr) {             // the block's downsample conv on this launch (pnvo_conv_takes_ds said yes; the plan carries it: q.ds)
+  if (ride != nullptr) {             // the block's downsample conv on this launch (the schedule's choice for this ride said X3; the plan carries it: q.ds)
     Layer &dm = const_cast<Layer &>(*ride->cd);
     if (int rc = x3_operand(m, dm, 2, s)) return rc;
     xa.ds_wpk = dm.wpk_x2;
@@ -631,8 +659,8 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, cons
       HIPCHK(m, launch_conv_x3(xa, p, s));
   }
   if (fuse) return PNVO_OK;
-  Timed t(m, s, "gn_finalize", 0.0, 0.0);
   if (ride != nullptr) {             // the conv's GroupNorm and the riding downsample conv's in one launch
+    Timed t(m, s, "gn_finalize", 0.0, 0.0);
     const float *st2[2] = {m->stats, m->stats_ds}, *ga2[2] = {l.gamma, ride->cd->gamma}, *be2[2] = {l.beta, ride->cd->beta};
     float *sc2[2] = {r.ss[0], ride->ss[0]}, *sh2[2] = {r.ss[1], ride->ss[1]};
     float *mu2[2] = {r.mu, ride->mu}, *rs2[2] = {r.rstd, ride->rstd};
@@ -640,14 +668,12 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, cons
                                       r.grp ? &gg : nullptr, r.grp ? &ggd : nullptr));
     return PNVO_OK;
   }
-  HIPCHK(m, launch_gn_finalize(m->stats, B, xa.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0], r.ss[1], s,
-                               xa.slots, r.mu, r.rstd, r.grp ? &gg : nullptr));
-  return PNVO_OK;
+  return finalize_gn(m, l, B, xa.slots, 0, r.ss, r.mu, r.rstd, s, r.grp ? &gg : nullptr);
 }
 
 // The float32-MFMA kernels: the LDS-staged 3x3 conv, else the generic implicit GEMM — linear layers split the reduction when the
 // output tiles alone cannot fill the chip, and the output head may ride on that reduction.
-int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvChoice &c) {
   hipStream_t s = r.s;
   ConvArgs a;
   conv_geometry(l, B, r.y_cstride, a);
@@ -676,21 +702,16 @@ int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
   a.bias_row = r.bias_row;
   a.relu_out = r.relu_out;
   const long P = (long)l.hout * l.wout, M = (long)B * P;
-  choose_tile(M, l.coutp, &a.MT, &a.NT);
-  a.slots = conv_slots((int)P, a.MT);
-  if (conv3_lds_supported(a) && m->opt.conv != 3) {   // 3x3 stride-1 residual-stage conv: input patch staged in LDS
+  a.MT = c.MT;
+  a.NT = c.NT;
+  a.slots = c.slots;
+  if (c.family == ConvChoice::FP32_LDS) {             // 3x3 stride-1 residual-stage conv: input patch staged in LDS
     const int nt = (l.coutp / 32) % 2 == 0 ? 2 : 1;
-    a.slots = conv3_lds_slots(a);
     {
       Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
       HIPCHK(m, launch_conv3_lds(a, nt, s));
     }
-    if (r.ss) {
-      Timed t(m, s, "gn_finalize", 0.0, 0.0);
-      HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0],
-                                   r.ss[1], s, a.slots, r.mu, r.rstd));
-    }
-    return PNVO_OK;
+    return finalize_gn(m, l, B, a.slots, 0, r.ss, r.mu, r.rstd, s);
   }
   if (r.bias != nullptr && !r.ss) {  // linear layer: split the reduction when the output tiles alone cannot fill the chip
     a.kpart = reinterpret_cast<float *>(8);          // non-null: "scratch available" for the query
@@ -716,53 +737,43 @@ int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
       HIPCHK(m, launch_ksplit_reduce(a, s));
     }
   }
-  if (r.ss) {
-    Timed t(m, s, "gn_finalize", 0.0, 0.0);
-    HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, a.MT * 32, l.gamma, l.beta, 1e-5f,
-                                 r.ss[0], r.ss[1], s, 0, r.mu, r.rstd));
-  }
-  return PNVO_OK;
+  return r.ss ? finalize_gn(m, l, B, a.slots, a.MT * 32, r.ss, r.mu, r.rstd, s) : PNVO_OK;
 }
-}  // namespace
 
-namespace {
 // The grouped 3x3 conv of a ResNeXt block (conv_group.hip) + the GroupNorm finalisation that follows it.
-int run_conv_group(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
+int run_conv_group(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvChoice &c) {
   if (!r.ss || r.src != nullptr || r.bias != nullptr || r.relu_out || r.y_cstride != l.coutp || r.tail != nullptr || r.ride != nullptr ||
       r.grp != nullptr || l.cout != l.coutp || l.cin != l.cinp || !l.wpk_grp)
     return fail(m, PNVO_ERR_STATE, "grouped conv " + l.name + " asked for something only the dense kernels do");
-  const int P = l.hout * l.wout;
   ConvGroupArgs a{.x = r.x, .wpk = l.wpk_grp, .in_scale = r.in_scale, .in_shift = r.in_shift, .y = r.y, .stats = m->stats, .B = B, .H = l.hin,
-                  .W = l.win, .Ho = l.hout, .Wo = l.wout, .C = l.cout, .cg = l.cin / l.cgroups, .stride = l.stride, .slots = conv_group_slots(P)};
+                  .W = l.win, .Ho = l.hout, .Wo = l.wout, .C = l.cout, .cg = l.cin / l.cgroups, .stride = l.stride, .slots = c.slots};
   {
     Timed t(m, r.s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
     HIPCHK(m, launch_conv_group(a, r.s));
   }
-  Timed t(m, r.s, "gn_finalize", 0.0, 0.0);
-  HIPCHK(m, launch_gn_finalize(m->stats, B, a.slots, l.coutp, l.cout, l.groups, P, 1, l.gamma, l.beta, 1e-5f, r.ss[0], r.ss[1], r.s, a.slots, r.mu,
-                               r.rstd));
-  return PNVO_OK;
+  return finalize_gn(m, l, B, a.slots, 0, r.ss, r.mu, r.rstd, r.s);
+}
+
+// What request r asks of its conv's kernel (the launch's own ask: the rows form may take it).
+ConvAsk conv_ask(const Layer &l, const ConvRequest &r) {
+  const ConvAsk::Tail tail = !r.tail ? ConvAsk::NONE : !r.tail->res ? ConvAsk::KEYS : r.tail->res_scale ? ConvAsk::SKIP_SCALED : ConvAsk::SKIP;
+  return {.gn = r.ss != nullptr, .plain = r.src != nullptr || r.bias != nullptr || r.relu_out != 0 || r.y_cstride != l.coutp,
+          .affine = r.in_scale != nullptr, .tail = tail, .ride = r.ride ? r.ride->cd : nullptr, .rows_form = true};
 }
 }  // namespace
 
 int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r) {
-  if (l.cgroups > 1) return run_conv_group(m, l, B, r);
-  // GroupNorm-ed 3x3 and 1x1 stride-2 convs: float32 results from the 16-bit matrix cores (conv_x3.hip; 32 -> 32 channels on the
-  // row-streaming conv_rows.hip where it takes the launch, with fewer statistics slots than the tile plan the buffer is sized for:
-  // stats_floats); option conv=fp32 keeps the fp32-MFMA kernels.  Not with a fused stem source, bias or output ReLU.
-  if (r.ss && r.src == nullptr && r.bias == nullptr && !r.relu_out && r.y_cstride == l.coutp && x3_layer(m, l)) {
-    ConvX3Problem q = x3_problem(m, l, B);
-    q.mode = r.tail ? (r.tail->res ? 2 : 3) : (r.in_scale ? 1 : 0);
-    // (the rows plan refuses a block tail whose skip branch carries its own GroupNorm — a downsample skip, reachable with
-    //  baseplanes 16: the rows kernel adds the raw skip tensor)
-    q.tail_scaled = r.tail != nullptr && r.tail->res_scale != nullptr;
-    q.ds = r.ride != nullptr;
-    if (const ConvX3Plan p = conv_x3_plan(q)) return run_conv_x3(m, l, B, r, q, p);
-  }
+  const ConvChoice c = pnvo_conv_choice(m, l, B, conv_ask(l, r));
+  // (a choice and the workspace's sizing that drifted apart would be an out-of-bounds device write)
+  if (r.ss != nullptr && ((size_t)B * c.slots * l.coutp * 2 > m->stats.size() ||
+                          (r.ride != nullptr && (size_t)B * c.slots * r.ride->cd->coutp * 2 > m->stats_ds.size())))
+    return fail(m, PNVO_ERR_STATE, "conv " + l.name + ": the launch's GroupNorm partials do not fit the workspace");
+  if (c.family == ConvChoice::GROUP) return run_conv_group(m, l, B, r, c);
+  if (c.family == ConvChoice::X3) return run_conv_x3(m, l, B, r, c);
   if (r.ride != nullptr) return fail(m, PNVO_ERR_STATE, "downsample ride on a conv that cannot carry it (" + l.name + ")");
   if (r.tail != nullptr) return fail(m, PNVO_ERR_STATE, "block tail handed to a conv that cannot take it (" + l.name + ")");
   if (r.grp != nullptr && r.ss != nullptr) return fail(m, PNVO_ERR_STATE, "grouped forward: layer " + l.name + " fell off the float16-piece tile kernel");
-  return run_conv_fp32(m, l, B, r);
+  return run_conv_fp32(m, l, B, r, c);
 }
 
 // The stem's place in the forward is the 16-bit-matrix-core stems' (8 x 16-tile slots, pooled keys, raw entry) or the one-hot-aware
@@ -1046,12 +1057,7 @@ int pnvo_run_stem(pnvo_handle m, int B, const StemRequest &r) {
     if ((rc = pnvo_mark_stem(m, r.s, p)) != PNVO_OK) return rc;
   }
   if (r.slots_out != nullptr) *r.slots_out = p.slots;
-  if (!r.skip_finalize) {
-    Timed t(m, r.s, "gn_finalize", 0.0, 0.0);
-    HIPCHK(m, launch_gn_finalize(m->stats, B, p.slots, stem.coutp, stem.cout, stem.groups, (long)m->Hs * m->Ws, 1, stem.gamma, stem.beta,
-                                 1e-5f, r.ss[0], r.ss[1], r.s, p.slots, r.mu, r.rstd, r.grp ? &sgg : nullptr));
-  }
-  return PNVO_OK;
+  return r.skip_finalize ? PNVO_OK : finalize_gn(m, stem, B, p.slots, 0, r.ss, r.mu, r.rstd, r.s, r.grp ? &sgg : nullptr);
 }
 
 int pnvo_ensure_workspace(pnvo_handle m, int B) { return ensure_workspace(m, B); }
@@ -1782,15 +1788,13 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
                                   .R = b.se_r}, s));
         ss3 = m->ssE;
       }
-      if (ds) {
-        const Layer &cd = m->convs[b.ds];
-        if ((rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
-          return rc;
+      if (ds && (rc = pnvo_run_conv(m, m->convs[b.ds], B, {.x = cur, .y = m->rawD, .y_cstride = m->convs[b.ds].coutp, .ss = m->ssD, .grp = grp,
+                                                           .s = s})) != PNVO_OK)
+        return rc;
+      {
         Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], m->rawD, m->ssD[0], m->ssD[1], B, Pb, b3.coutp, nxt, s));
-      } else {
-        Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], cur, nullptr, nullptr, B, Pb, b3.coutp, nxt, s));
+        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], ds ? m->rawD : cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, B, Pb, b3.coutp,
+                                  nxt, s));
       }
       std::swap(cur, nxt);
       if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
@@ -1800,7 +1804,7 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
     const Layer &c2 = m->convs[b.conv[1]];
     // the block's downsample conv rides on c1's launch (conv_x3_kernel DSF): no launch, no finalisation of its own, and in the
     // block-tail mode the block input is not written to HBM at all — c1 and the downsample conv are its only readers
-    const bool ds_ride = ds && !have_keys && pnvo_conv_takes_ds(m, c1, m->convs[b.ds], B);
+    const bool ds_ride = ds && !have_keys && pnvo_conv_choice(m, c1, B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
     const DsRide ride{ds_ride ? &m->convs[b.ds] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
     if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
       BlockTail ktail{nullptr, nullptr, nullptr, cur};
@@ -1820,7 +1824,7 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
       return rc;
     }
     const long P = (long)c2.hout * c2.wout;
-    const bool c2_small_generic = !layer_on_lds(m, c2, nullptr) && !pnvo_conv_on_x3(m, c2, B) && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
+    const bool c2_small_generic = pnvo_conv_choice(m, c2, B, {}).family == ConvChoice::FP32_GENERIC && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
     if (c2_small_generic) {
       // small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one streaming
       // pass over the (L2-sized) tensor, so normalise once and run the conv on final activations
@@ -2441,14 +2445,8 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
   for (size_t li = 1; li < h->convs.size(); ++li) {
     const Layer &l = h->convs[li];
     if (l.name != name) continue;
-    const double alg = 2.0 * B * l.hout * l.wout * (double)l.cout * (l.cin / l.cgroups) * l.k * l.kw;
-    if (l.cgroups > 1) {                               // conv_group.hip: 32-pixel slots x slabs of max(cg, 16) channels, dense inside a slab
-      std::snprintf(family, cap, "group");
-      const int cg = l.cin / l.cgroups;
-      if (executed_flops) *executed_flops = 2.0 * B * conv_group_slots(l.hout * l.wout) * 32.0 * l.cout * (double)(cg > 16 ? cg : 16) * 9.0;
-      return PNVO_OK;
-    }
-    if (pnvo_stem_plan(h, false, {}).writes_slots() && pnvo_small_usable(h, B)) {      // a phase of the persistent small-batch kernel (fp32 MFMA)
+    const ConvChoice c = pnvo_conv_choice(h, l, B, {});
+    if (c.family != ConvChoice::GROUP && pnvo_stem_plan(h, false, {}).writes_slots() && pnvo_small_usable(h, B)) {   // a phase of the persistent small-batch kernel (fp32 MFMA)
       std::snprintf(family, cap, "smallnet");
       if (executed_flops) {
         const int mb = l.cinp >= 128 ? 1 : l.cinp >= 64 ? 2 : 4, th = mb == 4 ? 8 : 4, tw = mb == 1 ? 4 : 8;
@@ -2457,22 +2455,15 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
       return PNVO_OK;
     }
     const Layer *c1 = l.block >= 0 && h->blocks[l.block].ds == (int)li ? &h->convs[h->blocks[l.block].conv[0]] : nullptr;
-    if (c1 && pnvo_conv_takes_ds(h, *c1, l, B)) {   // a downsample conv riding on its block's first conv
-      const ConvX3Plan p = x3_tile_plan(h, *c1, B, true);
+    const ConvChoice cr = c1 ? pnvo_conv_choice(h, *c1, B, {.ride = &l}) : ConvChoice{};
+    if (c1 && cr.family == ConvChoice::X3) {        // a downsample conv riding on its block's first conv
       std::snprintf(family, cap, "x2-rides");
-      if (executed_flops) *executed_flops = 3.0 * 2.0 * (double)B * p.tiles_r * p.tiles_c * p.MT * 32.0 * l.coutp * (double)l.cinp;
+      if (executed_flops) *executed_flops = 3.0 * 2.0 * (double)B * cr.x3p.tiles_r * cr.x3p.tiles_c * cr.x3p.MT * 32.0 * l.coutp * (double)l.cinp;
       return PNVO_OK;
     }
-    if (pnvo_conv_on_x3(h, l, B)) {
-      const ConvX3Plan p = x3_tile_plan(h, l, B);
-      std::snprintf(family, cap, p.np == 2 ? "x2" : "x3");
-      // tiles x M-tiles x 32 pixels (the 16x16x32 flavour of x2: 16-row sub-tiles x 16) x padded outputs x K, six bf16 (x3) or three float16 (x2) MFMA terms per float32 product
-      if (executed_flops)
-        *executed_flops = (p.np == 2 ? 3.0 : 6.0) * 2.0 * (double)B * p.tiles_r * p.tiles_c * (double)p.m_rows * l.coutp * (double)l.cinp * l.k * l.kw;
-      return PNVO_OK;
-    }
-    std::snprintf(family, cap, "%s", layer_on_lds(h, l, nullptr) ? "fp32-lds" : "fp32-generic");
-    if (executed_flops) *executed_flops = alg;
+    const char *const names[] = {"group", c.x3p.np == 2 ? "x2" : "x3", "fp32-lds", "fp32-generic"};   // ConvChoice::Family
+    std::snprintf(family, cap, "%s", names[c.family]);
+    if (executed_flops) *executed_flops = c.flops;
     return PNVO_OK;
   }
   return fail(h, PNVO_ERR_ARG, std::string("no residual-stage conv named '") + name + "'");

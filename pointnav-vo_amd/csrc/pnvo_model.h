@@ -278,6 +278,30 @@ struct StemPlan {
   bool raw_stager() const { return kernel == MX && !standin; }   // sensor frames can go straight into the stem
 };
 
+// What a conv launch wants of its kernel beyond layer and batch (designated initializers, in this order).  No buffer pointers: the
+// schedule asks before it builds a ConvRequest; pnvo_run_conv derives the launch's own ask from its request.
+struct ConvAsk {
+  bool gn = true;              // a GroupNorm follows: the launch leaves statistics slots
+  bool plain = false;          // fused stem source, bias, output ReLU or y_cstride != coutp (linear layers, generic stem): conv_mfma.hip only
+  bool affine = false;         // the producer's GroupNorm scale / shift (+ ReLU) applied while staging
+  enum Tail { NONE, SKIP, SKIP_SCALED, KEYS } tail = NONE;   // BlockTail: skip tensor, skip tensor with its own scale / shift, pooled stem keys
+  const Layer *ride = nullptr; // the block's downsample conv rides on the launch (DsRide::cd)
+  bool rows_form = false;      // the launch itself asks: conv_rows32_kernel may take the tile plan's place (see pnvo_conv_choice)
+};
+
+// Which kernel family runs a residual-stage conv at B samples for an ask, and what follows from that.  The rule is written once, in
+// pnvo_conv_choice; pnvo_run_conv executes the value, the workspace sizes the statistics buffers from it, the forward schedules
+// (tails, rides, the small-generic pre-pass) and pnvo_layer_kernel read it.
+struct ConvChoice {
+  // conv_group.hip, conv_x3.hip / conv_rows.hip, conv3_lds.hip, conv_mfma.hip
+  enum Family { GROUP, X3, FP32_LDS, FP32_GENERIC } family = FP32_GENERIC;
+  pnvo::ConvX3Problem x3q{};   // X3: the launch's problem and its plan
+  pnvo::ConvX3Plan x3p;
+  int slots = 0;               // statistics slots per sample the launch writes ([B][slots][coutp][2] in m->stats)
+  int MT = 0, NT = 0;          // FP32_*: choose_tile's wave tile
+  double flops = 0.0;          // executed matrix-core FLOPs (X3: of the tile plan)
+};
+
 // One stem launch of pnvo_run_stem (designated initializers, in this order).
 struct StemRequest {
   const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // rgb | depth | dd | tdv pair tensors
@@ -307,9 +331,8 @@ struct FwdRequest {
 
 // helpers implemented in pnvo_api.hip
 int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r);   // one conv + the GroupNorm finalisation that follows it
-bool pnvo_conv_takes_ds(pnvo_handle m, const Layer &c1, const Layer &cd, int B);   // would pnvo_run_conv(c1) carry cd as a DsRide?
-bool pnvo_conv_on_x3(pnvo_handle m, const Layer &l, int B);                        // would pnvo_run_conv(l) use conv_x3.hip?
-bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B);   // would pnvo_run_conv(l) accept a BlockTail (conv_x3 path)?
+ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk &ask);
+bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B);   // does the schedule hand l a BlockTail (l on conv_x3, no tap, option tail)?
 void pnvo_pack_conv_weight_cinp(const float *oihw, int cout, int cin, int cinp, int kh, int kw, std::vector<float> &out);
 StemPlan pnvo_stem_plan(pnvo_handle m, bool train_fwd, const RawFrames &raw);
 int pnvo_run_stem(pnvo_handle m, int B, const StemRequest &r);   // the fused stem + the GroupNorm finalisation that follows it

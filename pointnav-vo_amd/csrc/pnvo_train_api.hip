@@ -910,7 +910,7 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
     const bool ds = b.ds >= 0;
     // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
     // the backward pass reads it
-    const bool ds_ride = ds && K == 2 && pnvo_conv_takes_ds(m, m->convs[ik[0]], m->convs[b.ds], B);
+    const bool ds_ride = ds && K == 2 && pnvo_conv_choice(m, m->convs[ik[0]], B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
     DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (ds_ride) {
       ConvSave &sd = t->cs[b.ds];
