@@ -466,6 +466,46 @@ int pnvo_policy_input_stage(pnvo_policy_handle h, const void *rgb, int rgb_is_u8
 
 int pnvo_policy_destroy(pnvo_policy_handle h);
 
+/* ---- the baseline navigation policy: PointNavBaselinePolicy (pointnav_vo/rl/ppo/policy.py:82-163), the one the reference's plain
+ * PPOTrainer builds (rl/ppo/ppo_trainer.py:79-85).  SimpleCNN (model_utils/visual_encoders/simple_cnn.py: Conv 8x8 s4 + ReLU, Conv 4x4 s2
+ * + ReLU, Conv 3x3 s1, Flatten (NCHW), Linear + ReLU; bias, no normalisation, no padding) on cat([rgb / 255, depth]); the raw goal
+ * vector behind its embedding; one GRU layer (RNNStateEncoder's defaults); the two heads of the policy above.  A handle of its own: all
+ * float32 (FMA chains in the convs, fp32 matrix cores in the Linear), every sum in a fixed order, so a sample's bits depend neither on
+ * the batch size nor on its position.  A step is seven launches: conv1 (reads the sensor frames: / 255 and the channel concatenation
+ * happen in its loader), conv2, conv3, the split-K Linear, partial sums + GRU input row, the GRU layer, the heads.  Forward only. ---- */
+typedef struct {
+  int32_t width, height;      /* frame W, H of every visual type: both >= 36 (the smallest frame that leaves conv3 one output pixel) */
+  int32_t rgb_channels;       /* 0: no "rgb" in the observation space; 3: it is there */
+  int32_t depth_channels;     /* 0: no "depth"; 1: it is there.  Both zero: a blind policy, x = goal alone, no encoder */
+  int32_t hidden;             /* hidden_size (512): a positive multiple of 8 */
+  int32_t n_actions;          /* action_space.n: 1 to 32 */
+  int32_t goal_dim;           /* observation_space.spaces[goal_sensor_uuid].shape[0]: 1 to 8 (2) */
+} pnvo_baseline_config;
+
+typedef struct pnvo_baseline_s *pnvo_baseline_handle;
+
+int pnvo_baseline_create(const pnvo_baseline_config *cfg, int device, pnvo_baseline_handle *out);
+
+/* Tensor names as PointNavBaselinePolicy.state_dict() spells them: net.visual_encoder.cnn.{0,2,4,6}.{weight,bias} (absent when blind),
+ * net.state_encoder.rnn.{weight_ih_l0,weight_hh_l0,bias_ih_l0,bias_hh_l0}, action_distribution.linear.*, critic.fc.*.  blob is HOST
+ * memory; a missing or mis-shaped tensor gives PNVO_ERR_WEIGHTS.  The conv weights are re-laid [ky][kx][c][o], the Linear's columns are
+ * permuted from the NCHW flatten's order to the NHWC order conv3 writes, weight_ih_l0 is zero-padded to a row pitch that is a multiple
+ * of four floats. */
+int pnvo_baseline_load_weights(pnvo_baseline_handle h, const float *blob, size_t n_floats, const pnvo_tensor_desc *toc, int ntoc);
+
+/* net.visual_encoder(observations): rgb [B,H,W,3] values 0..255, uint8 (rgb_is_u8 = 1) or float32 (0), the same bits either way, NULL
+ * without rgb_channels; depth [B,H,W,1] float32, NULL without depth_channels -> embed [B,hidden].  Device pointers, asynchronous on
+ * `stream`.  A blind handle has no encoder: PNVO_ERR_STATE. */
+int pnvo_baseline_encode(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, const float *depth, int B, float *embed, void *stream);
+
+/* One step: x = cat([embed, goal]); x, h = GRU(x, h * mask); logits / value of the two heads.  goal [B,goal_dim] as the sensor gives
+ * it; masks [B]; hidden_in / hidden_out [1,B,hidden], which must not overlap (PNVO_ERR_ARG before anything is launched); features
+ * [B,hidden], logits [B,n_actions] and value [B] may each be NULL.  prev_actions is no input of this policy. */
+int pnvo_baseline_act(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, const float *depth, const float *goal, const float *masks,
+                      const float *hidden_in, int B, float *hidden_out, float *features, float *logits, float *value, void *stream);
+
+int pnvo_baseline_destroy(pnvo_baseline_handle h);
+
 /* ---- one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions, policy.py:52-63):
  * rollout forward with saved activations, the PPO loss, back-propagation through time into ONE flat gradient buffer.  float32; no
  * torch autograd anywhere on the path.  Rows of every [M, ...] tensor are T-major, row t*N + n (the order

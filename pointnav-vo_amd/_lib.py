@@ -126,6 +126,12 @@ _SIGNATURES = {
     "pnvo_policy_input_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "pnvo_policy_destroy": (C.c_int, [C.c_void_p]),
+    "pnvo_baseline_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "pnvo_baseline_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    "pnvo_baseline_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_destroy": (C.c_int, [C.c_void_p]),
     "pnvo_policy_train_tail_floats": (C.c_size_t, [C.c_void_p]),
     "pnvo_policy_train_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(pnvo_tensor_desc), C.c_int]),
     "pnvo_policy_train_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -571,6 +571,21 @@ int ensure_pooled(Policy &p, int B) {
 }
 
 }  // namespace
+
+// gru_layer_kernel / policy_heads_kernel for the baseline policy's handle (simple_cnn.hip): the same launches policy_act_tail makes
+hipError_t launch_gru_layer(const float *x, int K, const float *w_ih, const float *b_ih, const float *h_prev, const float *w_hh,
+                            const float *b_hh, const float *masks, int B, int Hd, float *h_out, hipStream_t s) {
+  hipLaunchKernelGGL(gru_layer_kernel, dim3((unsigned)Hd), dim3(192), 0, s, x, K, w_ih, b_ih, h_prev, w_hh, b_hh, masks, B, Hd, h_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_policy_heads(const float *feat, const float *act_w, const float *act_b, const float *cr_w, const float *cr_b, int B, int Hd,
+                               int n_actions, float *logits, float *value, hipStream_t s) {
+  hipLaunchKernelGGL(policy_heads_kernel, dim3((unsigned)((n_actions + 1 + 3) / 4)), dim3(256), 0, s, feat, act_w, act_b, cr_w, cr_b, B, Hd,
+                     n_actions, logits, value);
+  return hipGetLastError();
+}
+
 }  // namespace pnvo
 
 using namespace pnvo;

@@ -152,6 +152,13 @@ hipError_t launch_visual_fc_gemm(const float *feat, const float *w, const float 
 int policy_act_tail(Policy &p, const float *masks, const float *hidden_in, int B, float *hidden_out, float *features, float *logits,
                     float *value, hipStream_t s);
 
+// one GRU layer (x [B, K], K % 4 == 0, rows 16-byte aligned; w_ih [3 Hd, K]) and the two heads, as policy_act_tail launches them: the
+// baseline policy's handle (simple_cnn.hip) runs the same kernels (pnvo_policy.hip)
+hipError_t launch_gru_layer(const float *x, int K, const float *w_ih, const float *b_ih, const float *h_prev, const float *w_hh,
+                            const float *b_hh, const float *masks, int B, int Hd, float *h_out, hipStream_t s);
+hipError_t launch_policy_heads(const float *feat, const float *act_w, const float *act_b, const float *cr_w, const float *cr_b, int B, int Hd,
+                               int n_actions, float *logits, float *value, hipStream_t s);
+
 // ---- host helpers of both files
 inline int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }
 
