@@ -472,7 +472,8 @@ int pnvo_policy_destroy(pnvo_policy_handle h);
  * vector behind its embedding; one GRU layer (RNNStateEncoder's defaults); the two heads of the policy above.  A handle of its own: all
  * float32 (FMA chains in the convs, fp32 matrix cores in the Linear), every sum in a fixed order, so a sample's bits depend neither on
  * the batch size nor on its position.  A step is seven launches: conv1 (reads the sensor frames: / 255 and the channel concatenation
- * happen in its loader), conv2, conv3, the split-K Linear, partial sums + GRU input row, the GRU layer, the heads.  Forward only. ---- */
+ * happen in its loader), conv2, conv3, the split-K Linear, partial sums + GRU input row, the GRU layer, the heads.  Its PPO update is
+ * the pnvo_baseline_train_* group below. ---- */
 typedef struct {
   int32_t width, height;      /* frame W, H of every visual type: both >= 36 (the smallest frame that leaves conv3 one output pixel) */
   int32_t rgb_channels;       /* 0: no "rgb" in the observation space; 3: it is there */
@@ -505,6 +506,52 @@ int pnvo_baseline_act(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, co
                       const float *hidden_in, int B, float *hidden_out, float *features, float *logits, float *value, void *stream);
 
 int pnvo_baseline_destroy(pnvo_baseline_handle h);
+
+/* ---- one PPO minibatch update of the baseline policy (what the reference's PPOTrainer does with it: rl/ppo/ppo.py:61-139 around
+ * Policy.evaluate_actions), the pnvo_policy_* update step's contract on this handle: rollout forward with saved activations, the PPO
+ * loss, back-propagation through time and through SimpleCNN into ONE flat gradient buffer.  float32; no torch autograd, no atomics
+ * (two runs of the same update give the same bits).  Rows of every [M, ...] tensor are T-major, row t*N + n, M = T*N. ----
+ *
+ * pnvo_baseline_train_attach: params / grads are DEVICE buffers of n_floats floats (16-byte aligned) holding every tensor of
+ * PointNavBaselinePolicy.named_parameters() in torch's own layouts at the offsets of `toc` (multiples of 4 floats).  Requires
+ * pnvo_baseline_load_weights before it; that call is refused from then on.  After it the tensors whose layout already is torch's
+ * (weight_hh_l0, every bias, the heads) are read from `params` directly — pnvo_baseline_act / _encode included — and the handle's
+ * kernel-layout operands ([K][Cout] conv weights, the Linear's weight with its columns in NHWC order, weight_ih_l0 at the padded
+ * pitch) are rebuilt from `params` on the device, here and by every pnvo_baseline_train_refresh: an optimiser step on `params`
+ * followed by a refresh is all it takes for the next act to use the new weights.  Gradients land in `grads` in torch's layouts (OIHW
+ * convs, the Linear's columns in the NCHW flatten's order, weight_ih_l0 [3H, hidden + goal_dim] unpadded).  Every entry is checked
+ * before the handle changes. */
+int pnvo_baseline_train_attach(pnvo_baseline_handle h, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc,
+                               int ntoc);
+int pnvo_baseline_train_refresh(pnvo_baseline_handle h, void *stream);
+
+/* value, action_log_probs, entropy, rnn_hidden_states = evaluate_actions(...), everything the backward needs kept in the handle: the
+ * frames in the dtype given (rgb [M,H,W,3] uint8 or float32, depth [M,H,W,1]; NULL as the handle's visual types say), masks [M],
+ * actions [M] int64 and hidden_in [1,N,hidden] are copied, the caller's tensors may be gone by the backward.  goal [M,goal_dim];
+ * hidden_in / hidden_out must not overlap; value [M], logp [M], entropy [1] may each be NULL.  The state is masked at every step.  The
+ * embedding, the value and the final state have the bits T successive pnvo_baseline_act calls give.  prev_actions is no input of this
+ * policy.  Workspaces grow on demand. */
+int pnvo_baseline_evaluate(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, const float *depth, const float *goal,
+                           const float *masks, const float *hidden_in, int T, int N, const int64_t *actions, float *hidden_out,
+                           float *value, float *logp, float *entropy, void *stream);
+
+/* As pnvo_policy_ppo_loss, for the last pnvo_baseline_evaluate. */
+int pnvo_baseline_ppo_loss(pnvo_baseline_handle h, const float *actions_logp_old, const float *adv, const float *value_preds,
+                           const float *returns, float clip, float value_coef, float entropy_coef, int use_clipped_value_loss,
+                           float *out3, void *stream);
+
+/* total.backward(): fills the whole gradient buffer (overwrites).  train_encoder = 0 (no net.visual_encoder.* parameter with
+ * requires_grad) skips SimpleCNN's backward — the Linear cnn.6 included, it is part of net.visual_encoder — and leaves that range
+ * exactly zero; the other gradients have the bits of the full backward.  A blind handle has no encoder tensors at all. */
+int pnvo_baseline_backward(pnvo_baseline_handle h, int train_encoder, void *stream);
+
+/* As pnvo_policy_clip_grad_norm. */
+int pnvo_baseline_clip_grad_norm(pnvo_baseline_handle h, float max_norm, float *norm_out, void *stream);
+
+/* As pnvo_policy_train_timing / _timing_read: the same five phases (encoder forward, GRU forward + heads, loss, heads + BPTT + d embed,
+ * encoder backward). */
+int pnvo_baseline_train_timing(pnvo_baseline_handle h, int mode);
+int pnvo_baseline_train_timing_read(pnvo_baseline_handle h, double ms[5]);
 
 /* ---- one PPO minibatch update of the navigation policy (rl/ppo/ppo.py:61-139 around Policy.evaluate_actions, policy.py:52-63):
  * rollout forward with saved activations, the PPO loss, back-propagation through time into ONE flat gradient buffer.  float32; no

@@ -132,6 +132,16 @@ _SIGNATURES = {
     "pnvo_baseline_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_baseline_destroy": (C.c_int, [C.c_void_p]),
+    "pnvo_baseline_train_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(pnvo_tensor_desc), C.c_int]),
+    "pnvo_baseline_train_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_ppo_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                         C.c_int, C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pnvo_baseline_clip_grad_norm": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pnvo_baseline_train_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "pnvo_baseline_train_timing_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "pnvo_policy_train_tail_floats": (C.c_size_t, [C.c_void_p]),
     "pnvo_policy_train_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(pnvo_tensor_desc), C.c_int]),
     "pnvo_policy_train_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),

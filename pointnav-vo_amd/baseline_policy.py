@@ -6,8 +6,9 @@ cat([rgb / 255, depth]), the raw goal vector behind its embedding, a one-layer G
 PointNavResNetPolicy.  Same positional constructor, same ``state_dict`` names / shapes / order, same ``act`` / ``get_value`` signatures
 and return values.  The module tree only HOLDS parameters; a step is one call into libpnvo.so (pnvo_baseline_act: seven launches on the
 caller's current HIP stream) plus the categorical sampling / arg-max over the logits, which stays in torch as in policy.py of this
-package.  ``policy.net`` and ``policy.net.visual_encoder`` are callable as the reference's are.  Forward only: ``evaluate_actions`` (the
-PPO update of this policy) is not built.  No CPU fallback.
+package.  ``policy.net`` and ``policy.net.visual_encoder`` are callable as the reference's are.  ``evaluate_actions`` (the PPO update of
+this policy) delegates to an attached ``ppo.BaselineTrainStep`` (``ppo.PPO(policy, ...)`` attaches one); the weights then live in that
+step's flat buffer and the library reads them there.  No CPU fallback.
 """
 import ctypes as C
 import weakref
@@ -157,9 +158,15 @@ class PointNavBaselinePolicy(nn.Module):
         self._handle_dev = None
         self._loaded_sig = None
         self._spec_tensors = None
+        self._train_step = None                              # ppo.BaselineTrainStep once attached: the weights then live in its flat buffer
 
     # ------------------------------------------------------------------ libpnvo plumbing
     def _ensure(self, device):
+        if self._train_step is not None:                     # the library reads the train step's flat buffer: nothing to upload
+            if self._handle_dev != device.index:
+                raise RuntimeError("the policy moved to another device after a BaselineTrainStep was attached")
+            self._train_step._sync_params()
+            return
         if self._handle is None or self._handle_dev != device.index:
             self._release()
             cc = pnvo_baseline_config(width=self._W, height=self._H, rgb_channels=self._n_rgb, depth_channels=self._n_depth,
@@ -280,5 +287,9 @@ class PointNavBaselinePolicy(nn.Module):
             return self._net(observations, rnn_hidden_states, masks)
 
     def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
-        raise NotImplementedError("the PPO update of the baseline policy (policy.py:56-68) is not built: the HIP path runs its act / "
-                                  "get_value step only")
+        """-> (value [M,1], action_log_probs [M,1], distribution_entropy, rnn_hidden_states)  (policy.py:52-63), for a policy with a
+        ppo.BaselineTrainStep attached; gradients come from that step's backward(), not from autograd."""
+        if self._train_step is None:
+            raise NotImplementedError("the PPO update of the baseline policy (policy.py:56-68) needs a train step: attach one with "
+                                      "pointnav_vo_amd.ppo.BaselineTrainStep(policy) or ppo.PPO(policy, ...)")
+        return self._train_step.evaluate_actions(observations, rnn_hidden_states, prev_actions, masks, action)

@@ -419,7 +419,10 @@ __global__ __launch_bounds__(192) void gru_layer_kernel(const float *x, int K, c
       const float r_ = 1.f / (1.f + expf(-sg[0][threadIdx.x]));
       const float z_ = 1.f / (1.f + expf(-sg[1][threadIdx.x]));
       const float n_ = tanhf(sg[2][threadIdx.x] + r_ * sq[threadIdx.x]);
-      h_out[e] = (1.f - z_) * n_ + z_ * (h_prev[e] * masks[b]);
+      {                                                    // two rounded products and their sum, spelled out: gru_step_kernel of the
+#pragma clang fp contract(off)                             // update step (policy_train.hip) forms h the same way, bit for bit
+        h_out[e] = (1.f - z_) * n_ + z_ * (h_prev[e] * masks[b]);
+      }
     }
     __syncthreads();
   }

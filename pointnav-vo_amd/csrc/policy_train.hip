@@ -87,7 +87,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int SQ_BLOCKS = 1024;
+constexpr int SQ_BLOCKS = CLIP_PARTIALS;
 
 // once attached every Policy slot points into the caller's flat parameter buffer: its gradient sits at the same offset of the other one
 float *grad_of(const PolicyTrain *t, const float *slot) { return t->grads + (slot - t->params); }
@@ -96,15 +96,7 @@ float *grad_of(const PolicyTrain *t, const float *slot) { return t->grads + (slo
 // C[m][n] = sum_k A(m,k) B(k,n) (+ bias0[n] + bias1[n]) on the exact-float32 matrix instruction (one k-ordered fmaf chain per output,
 // as conv_mfma.hip): workgroup = 64 x 64 outputs, wave = 32 x 32, K in steps of 32 staged through LDS as [k][m] / [k][n].  Both
 // operands are addressed by two strides, so the four products of the LSTM (X . W^T, dG^T . X, dG . W) are one kernel; AKC / BKC say
-// which index is contiguous in memory (k, else m / n) and pick the staging order that reads whole lines.
-struct GemmArgs {
-  const float *A, *B, *bias0, *bias1;
-  float *C;
-  int M, N, K;
-  long a_sm, a_sk, b_sk, b_sn, ldc;
-  int relu = 0;                       // epilogue: max(., 0) behind the bias
-};
-
+// which index is contiguous in memory (k, else m / n) and pick the staging order that reads whole lines.  (GemmArgs: pnvo_policy_state.h)
 template <bool AKC, bool BKC>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   __shared__ float As[32][65], Bs[32][65];
@@ -252,7 +244,11 @@ __global__ __launch_bounds__(192) void gru_step_kernel(float *g, const float *h_
       const float q_ = sg[2][threadIdx.x];
       const float n_ = tanhf(g[b * G + 2 * Hd + j] + r_ * q_);
       const float hmv = h_prev[e] * masks[b];
-      const float h = (1.f - z_) * n_ + z_ * hmv;
+      float h;
+      {                                                    // two rounded products and their sum, as gru_layer_kernel of the act path
+#pragma clang fp contract(off)                             // (pnvo_policy.hip) forms them: the rollout has the bits of T act steps
+        h = (1.f - z_) * n_ + z_ * hmv;
+      }
       y[e] = h;
       hm[e] = hmv;
       g[b * G + j] = r_;
@@ -797,6 +793,59 @@ size_t tail_floats(const pnvo_policy_config &c) { return (size_t)c.baseplanes * 
 hipError_t launch_visual_fc_gemm(const float *feat, const float *w, const float *b, int rows, int F, int hidden, float *out, hipStream_t s) {
   GemmArgs g{feat, w, b, nullptr, out, rows, hidden, F, (long)F, 1, 1, (long)F, (long)hidden, 1};
   return launch_gemm<true, true>(g, s);
+}
+
+// ---- the kernels above as launches for simple_cnn_train.hip (pnvo_policy_state.h)
+hipError_t launch_gemm_f32(const GemmArgs &g, bool akc, bool bkc, hipStream_t s) {
+  if (akc) return bkc ? launch_gemm<true, true>(g, s) : launch_gemm<true, false>(g, s);
+  return bkc ? launch_gemm<false, true>(g, s) : launch_gemm<false, false>(g, s);
+}
+hipError_t launch_gru_step(float *g, const float *h_prev, const float *w_hh, const float *b_hh, const float *masks, int N, int Hd, float *y,
+                           float *hm, float *h_fin, hipStream_t s) {
+  hipLaunchKernelGGL(gru_step_kernel, dim3((unsigned)Hd), dim3(192), 0, s, g, h_prev, w_hh, b_hh, masks, N, Hd, y, hm, h_fin);
+  return hipGetLastError();
+}
+hipError_t launch_gru_bptt_step(const float *gates_t, const float *gates_n, const float *dgh_n, const float *dh_n, const float *mask_n,
+                                const float *hm_t, const float *whhT, const float *dY_t, int N, int Hd, float *dgx_t, float *dgh_t,
+                                float *dh_t, hipStream_t s) {
+  hipLaunchKernelGGL(gru_bptt_step_kernel, dim3((unsigned)Hd), dim3(192), 0, s, gates_t, gates_n, dgh_n, dh_n, mask_n, hm_t, whhT, dY_t, N, Hd,
+                     dgx_t, dgh_t, dh_t);
+  return hipGetLastError();
+}
+hipError_t launch_heads_eval(const float *feat, const float *act_w, const float *act_b, const float *cr_w, const float *cr_b,
+                             const int64_t *actions, int M, int Hd, int A, float *logits, float *value, float *logp, float *ent,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(heads_eval_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, feat, act_w, act_b, cr_w, cr_b, actions, M, Hd, A, logits,
+                     value, logp, ent);
+  return hipGetLastError();
+}
+hipError_t launch_mean(const float *x, int n, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, x, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_ppo_loss(const float *logits, const float *value, const float *logp, const float *ent, const int64_t *actions,
+                           const float *old_logp, const float *adv, const float *vpred, const float *ret, int M, int A, float clip, float vc,
+                           float ec, int use_clipped, float *out3, float *dlogits, float *dvalue, hipStream_t s) {
+  hipLaunchKernelGGL(ppo_loss_kernel, dim3(1), dim3(256), 0, s, logits, value, logp, ent, actions, old_logp, adv, vpred, ret, M, A, clip, vc, ec,
+                     use_clipped, out3, dlogits, dvalue);
+  return hipGetLastError();
+}
+hipError_t launch_heads_bwd(const float *feat, const float *dlogits, const float *dvalue, const float *act_w, const float *cr_w, int M, int Hd,
+                            int A, float *g_act_w, float *g_act_b, float *g_cr_w, float *g_cr_b, float *dfeat, hipStream_t s) {
+  hipLaunchKernelGGL(heads_bwd_w_kernel, dim3((unsigned)(((long)(A + 1) * Hd + 255) / 256)), dim3(256), 0, s, feat, dlogits, dvalue, M, Hd, A,
+                     g_act_w, g_act_b, g_cr_w, g_cr_b);
+  hipLaunchKernelGGL(heads_bwd_x_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, dlogits, dvalue, act_w, cr_w, M, Hd, A,
+                     dfeat);
+  return hipGetLastError();
+}
+hipError_t launch_transpose(const float *src, int R, int C, float *dst, hipStream_t s) {
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32)), dim3(256), 0, s, src, R, C, dst);
+  return hipGetLastError();
+}
+hipError_t launch_clip_grad_norm(float *g, long n, float scale, float max_norm, double *sq_part, float *norm_out, hipStream_t s) {
+  hipLaunchKernelGGL(sumsq_kernel, dim3(SQ_BLOCKS), dim3(256), 0, s, g, n, scale, sq_part);
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(SQ_BLOCKS), dim3(256), 0, s, g, n, sq_part, scale, max_norm, norm_out);
+  return hipGetLastError();
 }
 
 void pnvo_policy_train_free(Policy &p) {

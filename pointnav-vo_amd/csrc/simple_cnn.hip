@@ -29,29 +29,14 @@
 #include "../../include/pnvo.h"
 #include "pnvo_internal.h"
 #include "pnvo_model.h"
+#include "pnvo_baseline_state.h"
 #include "pnvo_policy_state.h"
 
 namespace pnvo {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KC = 64;         // k per LDS chunk
-constexpr int LDA = KC + 4;    // row pitch of the activation tile: consecutive pixel rows start four banks apart
-
-struct TileArgs {
-  const void *rgb;             // conv1: [B,H,W,3] uint8 or float32
-  const float *depth;          // conv1: [B,H,W,1]
-  const float *in;             // conv2 / conv3: [B,H,W,CIN]
-  const float *wt;             // [KH*KW*CIN][COUT]: k = (ky * KW + kx) * CIN + c
-  const float *bias;           // [COUT]
-  float *out;                  // [B,OH,OW,COUT]
-  int M, H, W, OH, OW;         // M = B * OH * OW output pixels
-};
-
-// SRC 0: NHWC float activations (CIN % 4 == 0: float4 loads of four channels of one tap); 1 / 2: the sensor frames with float32 /
-// uint8 rgb, CIN = NRGB + (depth ? 1 : 0) channels in the reference's torch.cat order, element loads (a pixel's taps of one kernel row
-// are contiguous in memory).  Threads = 16 pixel groups x COUT / 4 channel groups; a thread owns pixels tm + 16 i (i < TM) x 4 channels.
+// (TileArgs, KC, LDA and the loader of the activation tile: pnvo_baseline_state.h — the update step's weight gradient reads the same way)
+// Threads = 16 pixel groups x COUT / 4 channel groups; a thread owns pixels tm + 16 i (i < TM) x 4 channels.
 template <int SRC, int NRGB, int CIN, int KH, int KW, int S, int COUT, int TM, bool RELU>
 __global__ __launch_bounds__(4 * COUT) void conv_tile_kernel(TileArgs a) {
   constexpr int BM = 16 * TM, TNG = COUT / 4, NT = 16 * TNG, K = KH * KW * CIN;
@@ -61,11 +46,7 @@ __global__ __launch_bounds__(4 * COUT) void conv_tile_kernel(TileArgs a) {
   __shared__ unsigned pix[BM];                   // (b * H + oy * S) * W + ox * S of the tile's pixels (past the end: the last pixel again)
   const int tid = threadIdx.x, tn = tid % TNG, tm = tid / TNG;
   const int m0 = blockIdx.x * BM;
-  for (int i = tid; i < BM; i += NT) {
-    const int m = min(m0 + i, a.M - 1);
-    const int P = a.OH * a.OW, b = m / P, r = m - b * P, oy = r / a.OW, ox = r - oy * a.OW;
-    pix[i] = ((unsigned)b * a.H + oy * S) * a.W + ox * S;
-  }
+  tile_pixels<S>(a, m0, BM, tid, NT, pix);
   float acc[TM][4];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -73,35 +54,7 @@ __global__ __launch_bounds__(4 * COUT) void conv_tile_kernel(TileArgs a) {
     for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
   for (int k0 = 0; k0 < K; k0 += KC) {
     __syncthreads();                             // the previous chunk has been read (first pass: pix is written)
-    if constexpr (SRC == 0) {
-      for (int g = tid; g < BM * (KC / 4); g += NT) {
-        const int m = g / (KC / 4), q = g % (KC / 4), k = k0 + 4 * q, tap = k / CIN, c = k % CIN;
-        const unsigned toff = (unsigned)(tap / KW) * a.W + tap % KW;
-        *reinterpret_cast<f32x4 *>(&As[m * LDA + 4 * q]) = *reinterpret_cast<const f32x4 *>(a.in + (size_t)(pix[m] + toff) * CIN + c);
-      }
-    } else if constexpr (CIN == 4) {             // rgb-d: one tap of one pixel = (r, g, b) / 255 and the depth, stored as one float4
-      for (int g = tid; g < BM * (KC / 4); g += NT) {
-        const int m = g / (KC / 4), q = g % (KC / 4), tap = k0 / 4 + q;
-        const size_t p = (size_t)pix[m] + (unsigned)(tap / KW) * a.W + tap % KW;
-        f32x4 v;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          v[c] = (SRC == 2 ? (float)static_cast<const uint8_t *>(a.rgb)[p * 3 + c] : static_cast<const float *>(a.rgb)[p * 3 + c]) / 255.0f;
-        v[3] = a.depth[p];
-        *reinterpret_cast<f32x4 *>(&As[m * LDA + 4 * q]) = v;
-      }
-    } else {
-      for (int g = tid; g < BM * KC; g += NT) {
-        const int m = g / KC, kk = g % KC, k = k0 + kk, tap = k / CIN, c = k % CIN;
-        const size_t p = (size_t)pix[m] + (unsigned)(tap / KW) * a.W + tap % KW;
-        float v;
-        if (c < NRGB)
-          v = (SRC == 2 ? (float)static_cast<const uint8_t *>(a.rgb)[p * 3 + c] : static_cast<const float *>(a.rgb)[p * 3 + c]) / 255.0f;
-        else
-          v = a.depth[p];
-        As[m * LDA + kk] = v;
-      }
-    }
+    tile_load_a<SRC, NRGB, CIN, KW>(a, pix, k0, BM, tid, NT, As);
     for (int g = tid; g < KC * COUT / 4; g += NT)
       reinterpret_cast<f32x4 *>(Bs)[g] = reinterpret_cast<const f32x4 *>(a.wt + (size_t)k0 * COUT)[g];
     __syncthreads();
@@ -227,35 +180,9 @@ __global__ __launch_bounds__(256) void fc_sum_inputs_kernel(const float *part, i
 
 }  // namespace
 
-struct Baseline {
-  pnvo_baseline_config cfg;
-  int device = 0;
-  bool loaded = false;
-  int C = 0;                         // input channels: rgb, then depth
-  int oh[3] = {0, 0, 0}, ow[3] = {0, 0, 0};   // the three conv maps
-  int F = 0;                         // 32 * oh[2] * ow[2]
-  int E = 0;                         // embedding width in front of the goal: hidden, or 0 when blind
-  int Kp = 0;                        // the GRU input row's pitch: E + goal_dim rounded up to a multiple of 4
-  int nks = 0;                       // K slices of the Linear
-  DevBuf<float> cw[3], cb[3];        // conv weights [K][COUT] and biases
-  DevBuf<float> fcw, fcb;            // Linear [hidden][F], columns in NHWC order
-  DevBuf<float> w_ih, w_hh, b_ih, b_hh, act_w, act_b, cr_w, cr_b;
-  // workspace, grown on demand
-  int cap = 0;
-  DevBuf<float> a1, a2, a3, part, x;
-};
-
-static inline bool blind(const pnvo_baseline_config &c) { return c.rgb_channels + c.depth_channels == 0; }
-
 }  // namespace pnvo
 
 using namespace pnvo;
-
-extern "C" {
-struct pnvo_baseline_s {
-  pnvo::Baseline p;
-};
-}
 
 static int ensure_rows(Baseline &p, int B) {
   if (B <= p.cap) return PNVO_OK;
@@ -271,8 +198,9 @@ static int ensure_rows(Baseline &p, int B) {
   return PNVO_OK;
 }
 
-// the frames fit the handle (else PNVO_ERR_ARG, nothing launched)
-static int frames_check(const Baseline &p, const char *fn, const void *rgb, int rgb_is_u8, const float *depth, int B) {
+namespace pnvo {
+
+int baseline_frames_check(const Baseline &p, const char *fn, const void *rgb, int rgb_is_u8, const float *depth, int B) {
   const pnvo_baseline_config &c = p.cfg;
   if ((c.rgb_channels > 0) != (rgb != nullptr) || (c.depth_channels > 0) != (depth != nullptr))
     return pfail(PNVO_ERR_ARG, std::string(fn) + ": rgb / depth do not match the handle's visual types (rgb_channels " +
@@ -283,31 +211,34 @@ static int frames_check(const Baseline &p, const char *fn, const void *rgb, int 
 }
 
 // frames -> part (the Linear's partial tiles); the caller sums them (fc_sum_inputs_kernel)
-static int encoder_launches(Baseline &p, const void *rgb, int rgb_is_u8, const float *depth, int B, hipStream_t s) {
+int baseline_encoder_launches(const Baseline &p, const void *rgb, int rgb_is_u8, const float *depth, int B, float *o1, float *o2, float *o3,
+                              float *part, hipStream_t s) {
   const pnvo_baseline_config &c = p.cfg;
-  TileArgs a1{rgb, depth, nullptr, p.cw[0], p.cb[0], p.a1, B * p.oh[0] * p.ow[0], c.height, c.width, p.oh[0], p.ow[0]};
+  TileArgs a1{rgb, depth, nullptr, p.cw[0], p.cb[0], o1, B * p.oh[0] * p.ow[0], c.height, c.width, p.oh[0], p.ow[0]};
   if (c.rgb_channels && c.depth_channels)
     PCHK(rgb_is_u8 ? (launch_conv<2, 3, 4, 8, 8, 4, 32, true>(a1, s)) : (launch_conv<1, 3, 4, 8, 8, 4, 32, true>(a1, s)));
   else if (c.rgb_channels)
     PCHK(rgb_is_u8 ? (launch_conv<2, 3, 3, 8, 8, 4, 32, true>(a1, s)) : (launch_conv<1, 3, 3, 8, 8, 4, 32, true>(a1, s)));
   else
     PCHK((launch_conv<1, 0, 1, 8, 8, 4, 32, true>(a1, s)));
-  TileArgs a2{nullptr, nullptr, p.a1, p.cw[1], p.cb[1], p.a2, B * p.oh[1] * p.ow[1], p.oh[0], p.ow[0], p.oh[1], p.ow[1]};
+  TileArgs a2{nullptr, nullptr, o1, p.cw[1], p.cb[1], o2, B * p.oh[1] * p.ow[1], p.oh[0], p.ow[0], p.oh[1], p.ow[1]};
   PCHK((launch_conv<0, 0, 32, 4, 4, 2, 64, true>(a2, s)));
-  TileArgs a3{nullptr, nullptr, p.a2, p.cw[2], p.cb[2], p.a3, B * p.oh[2] * p.ow[2], p.oh[1], p.ow[1], p.oh[2], p.ow[2]};
+  TileArgs a3{nullptr, nullptr, o2, p.cw[2], p.cb[2], o3, B * p.oh[2] * p.ow[2], p.oh[1], p.ow[1], p.oh[2], p.ow[2]};
   PCHK((launch_conv<0, 0, 64, 3, 3, 1, 32, false>(a3, s)));
   hipLaunchKernelGGL(fc_splitk_kernel, dim3((unsigned)((c.hidden + 15) / 16), (unsigned)p.nks, (unsigned)((B + FC_ROWS - 1) / FC_ROWS)), dim3(256),
-                     0, s, p.a3, p.fcw, B, p.F, c.hidden, p.F / 16, p.part);
+                     0, s, o3, p.fcw, B, p.F, c.hidden, p.F / 16, part);
   PCHK(hipGetLastError());
   return PNVO_OK;
 }
 
-static hipError_t launch_sum_inputs(const Baseline &p, const float *goal, int B, float *x, float *embed, hipStream_t s) {
+hipError_t baseline_sum_inputs(const Baseline &p, const float *part, const float *goal, int B, float *x, float *embed, hipStream_t s) {
   const int Kp = x ? p.Kp : p.E;                 // (encode: one thread per element of the embedding)
-  hipLaunchKernelGGL(fc_sum_inputs_kernel, dim3((unsigned)(((long)B * Kp + 255) / 256)), dim3(256), 0, s, p.part, p.nks, p.fcb, goal, B, p.E,
+  hipLaunchKernelGGL(fc_sum_inputs_kernel, dim3((unsigned)(((long)B * Kp + 255) / 256)), dim3(256), 0, s, part, p.nks, p.fcb, goal, B, p.E,
                      p.cfg.goal_dim, Kp, x, embed);
   return hipGetLastError();
 }
+
+}  // namespace pnvo
 
 extern "C" {
 
@@ -351,6 +282,9 @@ int pnvo_baseline_load_weights(pnvo_baseline_handle h, const float *blob, size_t
   if (!h || !blob || !toc || ntoc < 0) return pfail(PNVO_ERR_ARG, "null argument");
   Baseline &p = h->p;
   const pnvo_baseline_config &c = p.cfg;
+  if (p.attached)
+    return pfail(PNVO_ERR_STATE, "pnvo_baseline_load_weights after pnvo_baseline_train_attach: the parameters live in the caller's flat buffer "
+                                 "(write them there and call pnvo_baseline_train_refresh)");
   PCHK(hipSetDevice(p.device));
   int rc = PNVO_OK;
   // every tensor is found and checked before the first upload
@@ -375,6 +309,15 @@ int pnvo_baseline_load_weights(pnvo_baseline_handle h, const float *blob, size_t
   const float *aw = find("action_distribution.linear.weight", {A, Hd}), *ab = find("action_distribution.linear.bias", {A});
   const float *vw = find("critic.fc.weight", {1, Hd}), *vb = find("critic.fc.bias", {1});
   if (!wih || !whh || !bih || !bhh || !aw || !ab || !vw || !vb) return rc;
+  // the tensors kept in torch's layout: one owned copy each, in a fixed order (a reload rewrites the same allocations in place)
+  size_t n_own = 0;
+  p.owned.resize(11);
+  auto own = [&](const float **slot, const float *src, size_t n) -> int {
+    DevBuf<float> &b = p.owned[n_own++];
+    PCHK(b.upload(src, n));
+    *slot = b;
+    return PNVO_OK;
+  };
   std::vector<float> t;
   if (!blind(c)) {
     for (int l = 0; l < 3; ++l) {                 // OIHW -> [ky][kx][c][o]
@@ -384,7 +327,7 @@ int pnvo_baseline_load_weights(pnvo_baseline_handle h, const float *blob, size_t
         for (int64_t ch = 0; ch < ci[l]; ++ch)
           for (int64_t tp = 0; tp < taps; ++tp) t[(size_t)((tp * ci[l] + ch) * co[l] + o)] = cw[l][(o * ci[l] + ch) * taps + tp];
       PCHK(p.cw[l].upload(t.data(), t.size()));
-      PCHK(p.cb[l].upload(cb[l], (size_t)co[l]));
+      if ((rc = own(&p.cb[l], cb[l], (size_t)co[l])) != PNVO_OK) return rc;
     }
     const int64_t P = p.oh[2] * p.ow[2];          // column c * P + pix (NCHW flatten) -> pix * 32 + c (the map conv3 writes)
     t.assign((size_t)(Hd * p.F), 0.f);
@@ -392,18 +335,15 @@ int pnvo_baseline_load_weights(pnvo_baseline_handle h, const float *blob, size_t
       for (int64_t ch = 0; ch < 32; ++ch)
         for (int64_t px = 0; px < P; ++px) t[(size_t)(n * p.F + px * 32 + ch)] = fw[n * p.F + ch * P + px];
     PCHK(p.fcw.upload(t.data(), t.size()));
-    PCHK(p.fcb.upload(fb, (size_t)Hd));
+    if ((rc = own(&p.fcb, fb, (size_t)Hd)) != PNVO_OK) return rc;
   }
   t.assign((size_t)(3 * Hd * p.Kp), 0.f);         // [3 Hd][K] -> pitch Kp, zero columns behind the goal
   for (int64_t n = 0; n < 3 * Hd; ++n) std::memcpy(&t[(size_t)(n * p.Kp)], wih + n * K, sizeof(float) * (size_t)K);
   PCHK(p.w_ih.upload(t.data(), t.size()));
-  PCHK(p.w_hh.upload(whh, (size_t)(3 * Hd * Hd)));
-  PCHK(p.b_ih.upload(bih, (size_t)(3 * Hd)));
-  PCHK(p.b_hh.upload(bhh, (size_t)(3 * Hd)));
-  PCHK(p.act_w.upload(aw, (size_t)(A * Hd)));
-  PCHK(p.act_b.upload(ab, (size_t)A));
-  PCHK(p.cr_w.upload(vw, (size_t)Hd));
-  PCHK(p.cr_b.upload(vb, 1));
+  if ((rc = own(&p.w_hh, whh, (size_t)(3 * Hd * Hd))) != PNVO_OK || (rc = own(&p.b_ih, bih, (size_t)(3 * Hd))) != PNVO_OK ||
+      (rc = own(&p.b_hh, bhh, (size_t)(3 * Hd))) != PNVO_OK || (rc = own(&p.act_w, aw, (size_t)(A * Hd))) != PNVO_OK ||
+      (rc = own(&p.act_b, ab, (size_t)A)) != PNVO_OK || (rc = own(&p.cr_w, vw, (size_t)Hd)) != PNVO_OK || (rc = own(&p.cr_b, vb, 1)) != PNVO_OK)
+    return rc;
   p.loaded = true;
   return PNVO_OK;
 }
@@ -414,13 +354,13 @@ int pnvo_baseline_encode(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8,
   if (blind(p.cfg)) return pfail(PNVO_ERR_STATE, "pnvo_baseline_encode: a blind policy has no visual encoder");
   if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_baseline_encode before pnvo_baseline_load_weights");
   if (B <= 0 || !embed) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
-  int rc = frames_check(p, "pnvo_baseline_encode", rgb, rgb_is_u8, depth, B);
+  int rc = baseline_frames_check(p, "pnvo_baseline_encode", rgb, rgb_is_u8, depth, B);
   if (rc != PNVO_OK) return rc;
   PCHK(hipSetDevice(p.device));
   if ((rc = ensure_rows(p, B)) != PNVO_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = encoder_launches(p, rgb, rgb_is_u8, depth, B, s)) != PNVO_OK) return rc;
-  PCHK(launch_sum_inputs(p, nullptr, B, nullptr, embed, s));
+  if ((rc = baseline_encoder_launches(p, rgb, rgb_is_u8, depth, B, p.a1, p.a2, p.a3, p.part, s)) != PNVO_OK) return rc;
+  PCHK(baseline_sum_inputs(p, p.part, nullptr, B, nullptr, embed, s));
   return PNVO_OK;
 }
 
@@ -431,7 +371,7 @@ int pnvo_baseline_act(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, co
   const pnvo_baseline_config &c = p.cfg;
   if (!p.loaded) return pfail(PNVO_ERR_STATE, "pnvo_baseline_act before pnvo_baseline_load_weights");
   if (B <= 0 || !goal || !masks || !hidden_in || !hidden_out) return pfail(PNVO_ERR_ARG, "null argument / bad batch");
-  int rc = frames_check(p, "pnvo_baseline_act", rgb, rgb_is_u8, depth, B);
+  int rc = baseline_frames_check(p, "pnvo_baseline_act", rgb, rgb_is_u8, depth, B);
   if (rc != PNVO_OK) return rc;
   if (((uintptr_t)hidden_in & 15) || ((uintptr_t)hidden_out & 15))
     return pfail(PNVO_ERR_ARG, "pnvo_baseline_act: hidden_in / hidden_out must be 16-byte aligned");
@@ -441,8 +381,8 @@ int pnvo_baseline_act(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, co
   PCHK(hipSetDevice(p.device));
   if ((rc = ensure_rows(p, B)) != PNVO_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (!blind(c) && (rc = encoder_launches(p, rgb, rgb_is_u8, depth, B, s)) != PNVO_OK) return rc;
-  PCHK(launch_sum_inputs(p, goal, B, p.x, nullptr, s));
+  if (!blind(c) && (rc = baseline_encoder_launches(p, rgb, rgb_is_u8, depth, B, p.a1, p.a2, p.a3, p.part, s)) != PNVO_OK) return rc;
+  PCHK(baseline_sum_inputs(p, p.part, goal, B, p.x, nullptr, s));
   PCHK(launch_gru_layer(p.x, p.Kp, p.w_ih, p.b_ih, hidden_in, p.w_hh, p.b_hh, masks, B, c.hidden, hidden_out, s));
   if (features) PCHK(hipMemcpyAsync(features, hidden_out, (size_t)B * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (logits || value) PCHK(launch_policy_heads(hidden_out, p.act_w, p.act_b, p.cr_w, p.cr_b, B, c.hidden, c.n_actions, logits, value, s));
@@ -452,6 +392,7 @@ int pnvo_baseline_act(pnvo_baseline_handle h, const void *rgb, int rgb_is_u8, co
 int pnvo_baseline_destroy(pnvo_baseline_handle h) {
   if (!h) return PNVO_OK;
   (void)hipSetDevice(h->p.device);
+  pnvo_baseline_train_free(h->p);
   delete h;
   return PNVO_OK;
 }

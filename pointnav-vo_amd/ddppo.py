@@ -127,4 +127,10 @@ class DecentralizedDistributedMixin:
 
 
 class DDPPO(DecentralizedDistributedMixin, PPO):
-    pass
+    def __init__(self, actor_critic, *args, **kwargs):
+        from .baseline_policy import PointNavBaselinePolicy
+        if isinstance(actor_critic, PointNavBaselinePolicy):   # before anything is attached or launched
+            raise NotImplementedError("DDPPO on a PointNavBaselinePolicy: the data-parallel update (gradient-ready ranges, the all-reduce "
+                                      "schedule) is built for PointNavResNetPolicy only, as the reference's DD-PPO trainer never builds "
+                                      "the baseline policy; use ppo.PPO")
+        super().__init__(actor_critic, *args, **kwargs)

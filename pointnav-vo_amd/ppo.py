@@ -26,6 +26,9 @@ A policy on another backbone than resnet18 (resnet50 .. se_resneXt101) trains wi
 False, the setting the distributed DD-PPO encoders come with): evaluate_actions on frames is net.visual_encoder's inference forward
 followed by the visual_features path, and train_encoder=True is refused before anything is launched.
 
+`BaselineTrainStep` is the same surface for baseline_policy.PointNavBaselinePolicy (the policy of the reference's plain PPOTrainer) on
+pnvo_baseline_evaluate / _ppo_loss / _backward; `PPO` picks it by the policy's class.
+
 Not here: the DD-PPO trainer and its pre-emption logic, an autograd bridge for the reference's own PPO.update, the encoder's backward
 for Bottleneck / ResNeXt / SE policies.  No CPU fallback.
 """
@@ -239,6 +242,125 @@ class PolicyTrainStep:
             _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, stream))
 
 
+class BaselineTrainStep(PolicyTrainStep):
+    """PolicyTrainStep's public surface for baseline_policy.PointNavBaselinePolicy (pnvo_baseline_train_* / _evaluate / _ppo_loss /
+    _backward / _clip_grad_norm): the same flat store, Adam and optimizer state dict; the parameters stay in torch's layouts in `flat`
+    and the gradients land in `grad` in torch's layouts, the handle re-lays its kernel operands from `flat` on the device after every
+    optimiser step (pnvo_baseline_train_refresh).  float32 frames-in only: no visual_features input, no bf16."""
+
+    def __init__(self, policy, lr=2.5e-4, eps=1e-5, max_grad_norm=0.5, train_encoder=True, betas=(0.9, 0.999)):
+        self.policy = policy
+        self.lr, self.eps, self.betas = float(lr), float(eps), tuple(betas)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.train_encoder = bool(train_encoder)
+        self._frozen_backbone = False
+        self._from_features = False
+        ref = next(policy.parameters())
+        if ref.device.type != "cuda":
+            raise RuntimeError("BaselineTrainStep runs on an MI355X only: move the policy with .to('cuda') first "
+                               "(there is no CPU fallback)")
+        self.dev = ref.device
+        policy._ensure(self.dev)                                # handle + kernel operand buffers
+        self.store = FlatParams(list(policy.named_parameters()), self.dev, align=4)
+        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (self.store.flat, self.store.grad, self.store.exp_avg,
+                                                               self.store.exp_avg_sq)
+        self.offsets, self.n_params = self.store.offsets, self.store.n_params
+        enc = [self.offsets[n] for n, _ in self.store.named if n.startswith(ENCODER_PREFIX)]
+        self.encoder_range = (min(o for o, _ in enc), max(o + k for o, k in enc)) if enc else None      # None: a blind policy
+        torch.cuda.synchronize(self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_baseline_train_attach(policy._handle, _ptr(self.flat), _ptr(self.grad), self.flat.numel(),
+                                                           self.store.toc, len(self.store.named)))
+        self.step_count = 0
+        self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
+        self._norm = torch.zeros(1, device=self.dev, dtype=torch.float32)
+        policy._train_step = self                               # evaluate_actions delegates here; act reads the flat buffer
+
+    def _ranges(self):
+        end = max(o + k for o, k in self.offsets.values())
+        if self.train_encoder or self.encoder_range is None:
+            return [(0, end)]
+        lo, hi = self.encoder_range
+        return [(a, b) for a, b in ((0, lo), (hi, end)) if b > a]
+
+    def _repack(self):
+        """The handle's kernel-layout operands from the flat buffer as it is now (one pass is all: nothing here lags a refresh)."""
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_baseline_train_refresh(self.policy._handle, self._stream()))
+        torch.cuda.current_stream(self.dev).synchronize()
+        self.store.mark()
+
+    def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
+        """-> (value [M,1], action_log_probs [M,1], distribution_entropy (scalar), rnn_hidden_states [1,N,hidden]) as
+        Policy.evaluate_actions (policy.py:52-63).  Rows are T-major (row t*N + n); N = rnn_hidden_states.shape[1], T = M / N.
+        prev_actions is accepted and ignored, as in the reference's net."""
+        pol, dev = self.policy, self.dev
+        rgb, u8, depth, M = pol._frames(observations, dev)      # checked before any launch
+        goal = observations[pol.goal_sensor_uuid].to(device=dev, dtype=torch.float32).contiguous()
+        if M is None:
+            M = int(goal.shape[0])
+        goal = goal.reshape(M, pol._goal_dim)
+        self._sync_params()
+        hin = rnn_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
+        N = hin.shape[1] if hin.dim() == 3 else 0
+        if tuple(hin.shape) != (1, N, pol._hidden) or N <= 0 or M % N != 0:
+            raise ValueError(f"rnn_hidden_states {tuple(hin.shape)} does not fit {M} rows: expected [1, N, {pol._hidden}] "
+                             "with N dividing the number of rows")
+        T = M // N
+        mk = masks.to(device=dev, dtype=torch.float32).contiguous().reshape(M)
+        act = action.to(device=dev, dtype=torch.int64).contiguous().reshape(M)
+        hout = torch.empty_like(hin)
+        value = torch.empty((M, 1), device=dev, dtype=torch.float32)
+        logp = torch.empty((M, 1), device=dev, dtype=torch.float32)
+        entropy = torch.empty((), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.pnvo_baseline_evaluate(pol._handle, _ptr(rgb), u8, _ptr(depth), _ptr(goal), _ptr(mk), _ptr(hin), int(T),
+                                                       int(N), _ptr(act), _ptr(hout), _ptr(value), _ptr(logp), _ptr(entropy),
+                                                       self._stream()))
+        return value, logp, entropy, hout
+
+    def ppo_loss(self, old_action_log_probs, adv_targ, value_preds, returns, clip_param, value_loss_coef, entropy_coef,
+                 use_clipped_value_loss=True):
+        f = lambda t: None if t is None else t.to(device=self.dev, dtype=torch.float32).contiguous().reshape(-1)
+        old, adv, vp, ret = f(old_action_log_probs), f(adv_targ), f(value_preds), f(returns)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_baseline_ppo_loss(self.policy._handle, _ptr(old), _ptr(adv), _ptr(vp), _ptr(ret), float(clip_param),
+                                                       float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
+                                                       _ptr(self._out3), self._stream()))
+        return self._out3
+
+    def backward(self):
+        """total_loss.backward(): fills self.grad (overwrites).  With train_encoder False the net.visual_encoder range stays exactly zero."""
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_baseline_backward(self.policy._handle, int(self.train_encoder), self._stream()))
+
+    def clip_grad_norm(self):
+        if self.max_grad_norm is None:
+            return None
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib.pnvo_baseline_clip_grad_norm(self.policy._handle, float(self.max_grad_norm), _ptr(self._norm),
+                                                             self._stream()))
+        return self._norm
+
+    def timing(self, on=True):
+        _lib.check(_lib.lib.pnvo_baseline_train_timing(self.policy._handle, int(bool(on))))
+
+    def phase_ms(self):
+        """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, GRU forward + heads,
+        loss, heads + BPTT + d embed, encoder backward (PolicyTrainStep's names)."""
+        ms = (C.c_double * 5)()
+        _lib.check(_lib.lib.pnvo_baseline_train_timing_read(self.policy._handle, ms))
+        return dict(zip(("encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward"), (float(v) for v in ms)))
+
+    def optimizer_step(self):
+        """Adam over the trainable ranges, then the handle's operands are re-laid from the flat buffer."""
+        self.step_count += 1
+        with torch.cuda.device(self.dev):
+            stream = self._stream()
+            self.store.adam_step(self._ranges(), self.lr, self.betas, self.eps, self.step_count, stream)
+            _lib.check(_lib.lib.pnvo_baseline_train_refresh(self.policy._handle, stream))
+
+
 class PPO(nn.Module):
     """The reference agent's contract (rl/ppo/ppo.py): same constructor keywords, get_advantages, update -> three floats."""
 
@@ -261,7 +383,9 @@ class PPO(nn.Module):
             kw["lr"] = lr
         if eps is not None:
             kw["eps"] = eps
-        self.train_step = PolicyTrainStep(actor_critic, max_grad_norm=max_grad_norm, train_encoder=train_encoder, **kw)
+        from .baseline_policy import PointNavBaselinePolicy
+        step_cls = BaselineTrainStep if isinstance(actor_critic, PointNavBaselinePolicy) else PolicyTrainStep
+        self.train_step = step_cls(actor_critic, max_grad_norm=max_grad_norm, train_encoder=train_encoder, **kw)
         self.optimizer = _AdamView(self.train_step)
         self.device = next(actor_critic.parameters()).device
 
