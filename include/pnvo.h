@@ -705,6 +705,29 @@ int pnvo_rollout_gather(const float *recurrent_hidden_states, const int64_t *act
 int pnvo_rollout_gather_frames(const float *frames, const int64_t *perm, int N, int64_t F, int steps, int start, int n_mb, float *out,
                                void *stream);
 
+/* ---- Goal and pose of the navigation loop on the device (pointnav_vo/utils/geometry_utils.py:69-99, 115-144; the loop of
+ * rl/ppo/ppo_trainer.py:724-891; pointnav-vo_amd/geometry.py's GoalTracker owns the tensors).  Stateless: DEVICE pointers to the
+ * caller's contiguous state tensors over E environments — goal float64 [E,3] (the goal in the agent frame), rot float64 [E,4]
+ * ([x,y,z,w]), pos float64 [E,3], polar float32 [E,2] ((rho, -phi): the policy's pointgoal_with_gps_compass) — and a stream.
+ * env: DEVICE int32 [n], the state row of each input row, distinct and inside [0, E) (validated by the caller: the calls do not
+ * know E); NULL means rows 0..n-1.  State rows that env does not name are not written.  rot and pos may be NULL together: only
+ * the goal is tracked.  One thread per row; float64 in the operation order of geometry.py's compute_goal_pos_batch /
+ * compute_global_state with one rounding per operation, so everything but sin, cos, hypot and atan2 is bit-equal to those host
+ * functions.  Each call is ONE launch (none for n == 0) and never waits for the device.  A null required pointer, n < 0 or
+ * exactly one of rot / pos being NULL return PNVO_ERR_ARG. ---- */
+
+/* Row i of deltas (DEVICE float32 (dx, dz, dyaw), rows delta_row_stride floats apart, widened to double first) advances state
+ * row env[i]: goal and polar as compute_goal_pos_batch, rot and pos as compute_global_state. */
+int pnvo_nav_update(const float *deltas, int64_t delta_row_stride, const int32_t *env, int n, double *goal, double *rot, double *pos,
+                    float *polar, void *stream);
+
+/* Episode start (ppo_trainer.py:727-740): goal[env[i]] and polar[env[i]] become compute_goal_pos(goal_world[i], start_delta[i])
+ * and rot / pos rows env[i] the start pose.  goal_world, start_delta ((sx, sz, 2 atan2(r_y, r_w)), computed by the caller),
+ * start_pos: DEVICE float64 [n,3]; start_rot [n,4]; start_rot / start_pos are read only when the pose is tracked.  The same
+ * device function as the update, with a double delta. */
+int pnvo_nav_reset(const double *goal_world, const double *start_delta, const double *start_rot, const double *start_pos,
+                   const int32_t *env, int n, double *goal, double *rot, double *pos, float *polar, void *stream);
+
 /* F.avg_pool2d(x, 2) of 1-channel NHWC frames [N,H,W,1] -> [N,H/2,W/2,2] with channel 1 = 0 (resnet_policy.py:168). */
 int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *stream);
 

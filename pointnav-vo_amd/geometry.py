@@ -7,7 +7,15 @@ Restates /root/reference/pointnav_vo/utils/geometry_utils.py:69-99 (`compute_glo
 definitions (q v q^-1 rotation; polar = (hypot(x, y), atan2(y, x))) in closed form for rotations about the y axis.
 PARITY UNPINNED (no golden vectors can be captured without those packages); covered by property tests.
 Quaternions are numpy arrays [x, y, z, w] (habitat's `quaternion_to_list` order).
+
+The functions below are the host form, and the definition of the arithmetic.  `GoalTracker` is the device form for the
+navigation loop: it keeps goal, pose and the policy's polar goal of E environments in device tensors and advances them
+straight from the VO output (csrc/nav_state.hip: pnvo_nav_update / pnvo_nav_reset, float64 in the operation order of
+`compute_goal_pos_batch` and `compute_global_state`, bit-equal to them except through sin, cos, hypot and atan2), so the deltas
+never travel to the host between the VO forward and the next `policy.act`.
 """
+import ctypes as C
+
 import numpy as np
 
 
@@ -71,3 +79,168 @@ def compute_goal_pos_batch(prev_goal_pos, local_delta_states):
     rho = np.hypot(-cur[:, 2], cur[:, 0])
     phi = np.arctan2(cur[:, 0], -cur[:, 2])
     return {"cartesian": cur, "polar": np.stack([rho, -phi], axis=1).astype(np.float32)}
+
+
+class GoalTracker:
+    """Goal, pose and polar goal of `num_envs` environments as device tensors, advanced by the VO deltas without a host round trip
+    (the device form of the bookkeeping of rl/ppo/ppo_trainer.py:727-740, 856-878):
+
+      goal   float64 [E,3]   goal position in the agent frame        (`compute_goal_pos(...)["cartesian"]`)
+      rot    float64 [E,4]   global rotation [x,y,z,w] from the VO   (`compute_global_state(...)[0]`; None without track_pose)
+      pos    float64 [E,3]   global position from the VO             (`compute_global_state(...)[1]`; None without track_pose)
+      polar  float32 [E,2]   (rho, -phi): what the policy reads as `pointgoal_with_gps_compass`
+
+    `polar` (like the other three) is ONE tensor for the tracker's lifetime, UPDATED IN PLACE by the next `update` / `reset`: feed it
+    to `policy.act` of this step, and clone it if its values must outlive the next update.  `update` and `reset` are one launch each
+    on the current stream and never wait for the device; `cartesian()` and `global_state()` copy to the host on demand (trajectory
+    logging).  The launches need an MI355X: a tracker on a CPU device can be built and validates its arguments, but there is no CPU
+    path behind it."""
+
+    _INDEX_CACHE_MAX = 64
+
+    def __init__(self, num_envs, device, track_pose=True):
+        import torch
+        if int(num_envs) != num_envs or int(num_envs) < 1:
+            raise ValueError(f"num_envs must be a positive integer, got {num_envs!r}")
+        self.num_envs = int(num_envs)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:      # ("cuda" -> the current device, as tensors report it)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.track_pose = bool(track_pose)
+        E, dev = self.num_envs, self.device
+        self.goal = torch.zeros((E, 3), dtype=torch.float64, device=dev)
+        self.polar = torch.zeros((E, 2), dtype=torch.float32, device=dev)
+        self.rot = self.pos = None
+        if self.track_pose:
+            self.rot = torch.zeros((E, 4), dtype=torch.float64, device=dev)
+            self.rot[:, 3] = 1.0
+            self.pos = torch.zeros((E, 3), dtype=torch.float64, device=dev)
+        self._index_cache = {}
+
+    # ------------------------------------------------------------------ argument checks (before anything is launched)
+    def _check_indices(self, env_indices, n=None):
+        try:
+            idx = tuple(env_indices)
+        except TypeError:
+            raise ValueError(f"env_indices must be a sequence of environment indices, got {env_indices!r}") from None
+        if n is not None and len(idx) != n:
+            raise ValueError(f"{len(idx)} environment indices for {n} rows")
+        for e in idx:
+            if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)):
+                raise ValueError(f"environment index {e!r} is not an integer")
+            if not 0 <= int(e) < self.num_envs:
+                raise ValueError(f"environment index {int(e)} outside [0, {self.num_envs})")
+        idx = tuple(int(e) for e in idx)
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"environment indices must be distinct within a call, got {list(idx)}")
+        return idx
+
+    def _need_gpu(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("GoalTracker runs its updates on an MI355X only (there is no CPU fallback); use compute_goal_pos_batch "
+                               "/ compute_global_state on the host")
+
+    def _device_indices(self, idx):
+        """int32 device tensor of an index tuple, cached per tuple (the loop repeats a handful of them)."""
+        import torch
+        t = self._index_cache.get(idx)
+        if t is None:
+            if len(self._index_cache) >= self._INDEX_CACHE_MAX:
+                self._index_cache.clear()
+            t = self._index_cache[idx] = torch.tensor(idx, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        return t
+
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    # ------------------------------------------------------------------ episode start and step
+    def reset(self, env_indices, goal_positions, start_positions, start_rotations):
+        """Episode start of the given environments (ppo_trainer.py:727-740), from host arrays: goal_positions [n,3] in the world
+        frame, start_positions [n,3], start_rotations [n,4] as [x,y,z,w].  goal / polar rows become
+        `compute_goal_pos(goal_position, (sx, sz, 2 atan2(r_y, r_w)))`, rot / pos rows the start pose.  The start delta is built
+        here in numpy as the reference does; one pinned non-blocking upload, one launch."""
+        import torch
+        idx = self._check_indices(env_indices)
+        n = len(idx)
+
+        def host(a, cols, what):
+            try:
+                a = np.asarray(a, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what} must be a numeric array of shape ({n}, {cols})") from None
+            if a.shape != (n, cols):
+                raise ValueError(f"{what} must have shape ({n}, {cols}), got {a.shape}")
+            return a
+
+        goals = host(goal_positions, 3, "goal_positions")
+        spos = host(start_positions, 3, "start_positions")
+        srot = host(start_rotations, 4, "start_rotations")
+        self._need_gpu()
+        if n == 0:
+            return
+        # one pinned block: float64 goal [n,3] | start delta [n,3] | start rotation [n,4] | start position [n,3], then the int32
+        # indices (torch's pinned allocator keeps the block alive until the copy below has run)
+        h = torch.empty(n * 13 * 8 + n * 4, dtype=torch.uint8, pin_memory=True)
+        hd = h[: n * 13 * 8].view(torch.float64).numpy()
+        hd[0:3 * n].reshape(n, 3)[:] = goals
+        delta = hd[3 * n:6 * n].reshape(n, 3)
+        delta[:, 0] = spos[:, 0]
+        delta[:, 1] = spos[:, 2]
+        delta[:, 2] = 2 * np.arctan2(srot[:, 1], srot[:, 3])
+        hd[6 * n:10 * n].reshape(n, 4)[:] = srot
+        hd[10 * n:13 * n].reshape(n, 3)[:] = spos
+        h[n * 13 * 8:].view(torch.int32).numpy()[:] = idx
+        dev = self.device
+        from . import _lib
+        with torch.cuda.device(dev):
+            d = h.to(dev, non_blocking=True)
+            at = lambda doubles: C.c_void_p(d.data_ptr() + 8 * doubles)
+            _lib.check(_lib.lib.pnvo_nav_reset(at(0), at(3 * n), at(6 * n), at(10 * n), at(13 * n), n, self._ptr(self.goal),
+                                               self._ptr(self.rot), self._ptr(self.pos), self._ptr(self.polar),
+                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def update(self, deltas, env_indices=None):
+        """One simulator step: row i of `deltas` — a CUDA float32 [n,3] tensor of (dx, dz, dyaw), any row stride, e.g. what
+        `compute_local_delta_states_batch(..., to_host=False)` returns — advances environment env_indices[i] (all `num_envs`
+        environments in order when env_indices is None).  Environments not named keep every byte of their state.  One launch on the
+        current stream, no host wait; the index tensor of a repeated env_indices tuple is cached."""
+        import torch
+        if not isinstance(deltas, torch.Tensor):
+            raise ValueError(f"deltas must be a CUDA float32 tensor [n,3], got {type(deltas).__name__}")
+        if deltas.dim() != 2 or deltas.shape[1] != 3 or deltas.dtype != torch.float32:
+            raise ValueError(f"deltas must be float32 [n,3], got {deltas.dtype} {tuple(deltas.shape)}")
+        n = int(deltas.shape[0])
+        if env_indices is None:
+            if n != self.num_envs:
+                raise ValueError(f"{n} delta rows for {self.num_envs} environments: pass env_indices to update a subset")
+            idx = None
+        else:
+            idx = self._check_indices(env_indices, n)
+        if not deltas.is_cuda:
+            raise ValueError("deltas must be a CUDA tensor (the host form of this update is compute_goal_pos_batch)")
+        self._need_gpu()
+        if deltas.device != self.device:
+            raise ValueError(f"deltas are on {deltas.device}, the tracker on {self.device}")
+        if n == 0:
+            return
+        if deltas.stride(1) != 1:
+            deltas = deltas.contiguous()
+        dev = self.device
+        from . import _lib
+        with torch.cuda.device(dev):
+            env = self._device_indices(idx) if idx is not None else None
+            _lib.check(_lib.lib.pnvo_nav_update(self._ptr(deltas), int(deltas.stride(0)) if n > 1 else 3, self._ptr(env), n,
+                                                self._ptr(self.goal), self._ptr(self.rot), self._ptr(self.pos), self._ptr(self.polar),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    # ------------------------------------------------------------------ host copies (trajectory logging)
+    def cartesian(self):
+        """Host copy of the goal positions in the agent frames, float64 [E,3] (waits for the device)."""
+        return self.goal.cpu().numpy()
+
+    def global_state(self):
+        """Host copies (rotations float64 [E,4] as [x,y,z,w], positions float64 [E,3]) of the pose from the VO (waits for the device)."""
+        if not self.track_pose:
+            raise RuntimeError("this GoalTracker was built with track_pose=False")
+        return self.rot.cpu().numpy(), self.pos.cpu().numpy()

@@ -452,7 +452,34 @@ class BaseRLTrainerWithVO:
             np.stack([np.asarray(obs_list[i]["depth"], dtype=np.float32).reshape(H, W, 1) for i in mi])).to(dev)
         return out
 
-    def compute_local_delta_states_batch(self, prev_obs_list, cur_obs_list, acts, env_ids=None):
+    def check_deferred(self):
+        """What a `compute_local_delta_states_batch(..., to_host=False)` call left for later, done now: wait (on the host) for the
+        event recorded behind that call's copies — its pinned staging may be refilled afterwards — and examine its depth-range flag,
+        which travelled to pinned host memory behind the forwards.  Raises the reference's assertion ("depth must lie in [0, 1]") for
+        the call that broke it, once.  Every boundary call on the trainer starts with this; the navigation loop may call it where a
+        late report suits it (after it fetched the actions the event has long completed).  A no-op without such a call pending."""
+        pend = getattr(self, "_deferred", None)
+        if pend is None:
+            return
+        self._deferred = None
+        event, h_flag = pend
+        event.synchronize()
+        assert int(h_flag[0]) == 0, "depth must lie in [0, 1]"      # the reference's asserts (:136-137)
+
+    def _unpermute_index(self, order):
+        """Device int64 index that puts rows in sorted-by-model order back into the caller's order, cached per permutation."""
+        cache = self.__dict__.setdefault("_unpermute_cache", {})
+        key = tuple(order)
+        idx = cache.get(key)
+        if idx is None:
+            if len(cache) > 64:
+                cache.clear()
+            inv = np.empty(len(order), dtype=np.int64)
+            inv[np.asarray(order)] = np.arange(len(order))
+            idx = cache[key] = torch.from_numpy(inv).pin_memory().to(self.device, non_blocking=True)
+        return idx
+
+    def compute_local_delta_states_batch(self, prev_obs_list, cur_obs_list, acts, env_ids=None, to_host=True):
         """Batched sibling of _compute_local_delta_states_from_vo: lists of observation dicts and actions ->
         float32 array [N,3].  env_ids (optional, one hashable id per pair, distinct within a call; mode 'det'): the call keeps each
         environment's cur frame and its top-down view on the device and, when the next call's prev frame IS that frame (the
@@ -461,8 +488,21 @@ class BaseRLTrainerWithVO:
         caller's stream.  Mode 'det': the frames then go STRAIGHT into the model (pnvo_forward_raw: pair concatenation, uint8 ->
         float and the one-hot depth of base_trainer_with_vo.py:172-269 happen in the stem's operand fetch; no observation-pair
         tensors are built), one forward per action model (sep_act) over all of its pairs.  Mode 'rnd' (train-mode forwards with
-        dropout, :295-308) builds the observation pairs (pnvo_build_obs_pairs).  One host synchronisation at the end."""
+        dropout, :295-308) builds the observation pairs (pnvo_build_obs_pairs).  One host synchronisation at the end.
+        to_host=False (mode 'det' without VO.OBS_TRANSFORM; a ValueError otherwise, before anything is launched): the deltas come
+        back as a CUDA float32 [N,3] tensor in the caller's order — put back into it on the device — and the call does NOT wait for
+        the GPU: feed them to geometry.GoalTracker.update.  What the final synchronisation guards is deferred instead: an event is
+        recorded behind the call's copies and the asynchronous copy of the depth-range flag, and the next boundary call on this
+        trainer (or check_deferred()) waits for it on the host before it refills the pinned staging, then raises the reference's
+        depth assertion if that call broke it."""
         assert len(prev_obs_list) == len(cur_obs_list) == len(acts)
+        if not to_host:
+            if self.config.VO.REGRESS_MODEL.mode != "det":
+                raise ValueError(f"to_host=False needs VO.REGRESS_MODEL.mode == 'det', not {self.config.VO.REGRESS_MODEL.mode!r}: the "
+                                 "dropout samples of the other modes are averaged on the host")
+            if getattr(self, "_vo_obs_transformer", None) is not None:
+                raise ValueError(f"to_host=False is not built for VO.OBS_TRANSFORM == {self.config.VO.OBS_TRANSFORM!r}")
+        self.check_deferred()                             # (only a to_host=False call leaves anything to wait for)
         if getattr(self, "_vo_obs_transformer", None) is not None:
             return self._compute_transformed_batch(prev_obs_list, cur_obs_list, acts)
         n = len(acts)
@@ -588,6 +628,17 @@ class BaseRLTrainerWithVO:
                     out[idx] = samples.mean(axis=0)
                     std[idx] = samples.std(axis=0)
             st["h_flag"].copy_(st["flag"], non_blocking=True)
+            if not to_host:
+                # the per-model results are contiguous slices of the sorted order, in that order
+                res = pending[0][1] if len(pending) == 1 else torch.cat([r for _, r in pending])
+                if order is not None:
+                    res = res.index_select(0, self._unpermute_index(order))
+                if getattr(self, "_stage_event", None) is None:
+                    self._stage_event = torch.cuda.Event()
+                self._stage_event.record(main)            # behind every H2D copy of the call and the flag's D2H copy
+                self._deferred = (self._stage_event, st["h_flag"])
+                self._last_std = std
+                return res
             for idx, res in pending:                      # the first .cpu() is the one synchronisation of the call
                 out[idx] = res.cpu().numpy()
         if not pending:

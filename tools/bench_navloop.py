@@ -10,7 +10,11 @@ simulator step and for E parallel environments of one process:
 Everything the reference does on the trainer process between two simulator steps, with host numpy observations as the
 simulator delivers them (uint8 rgb + float32 depth, PCIe copies included).  Reports env-steps/s and the eval wall-clock this
 implies for the GPU part of 994 episodes (the reference's full run took 4.5 h including simulation).
-    python tools/bench_navloop.py [--envs 8 32] [--steps 30]"""
+    python tools/bench_navloop.py [--envs 8 32] [--steps 30] [--device-goal]
+
+--device-goal keeps the goal on the device: the VO call returns its deltas as a device tensor (to_host=False), geometry.GoalTracker
+advances the goal from them in one launch, and the policy reads tracker.polar — the only device-to-host copy left in a loop step is
+the actions.  Without the flag the loop is the host form above."""
 import argparse
 import json
 import os
@@ -47,11 +51,12 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--episode-steps", type=float, default=150.0, help="mean steps per episode used for the extrapolation")
+    ap.add_argument("--device-goal", action="store_true", help="goal update on the device (GoalTracker), deltas never reach the host")
     a = ap.parse_args()
-    print(json.dumps(run(a.envs, a.steps, a.episode_steps, torch.device("cuda", 0))))
+    print(json.dumps(run(a.envs, a.steps, a.episode_steps, torch.device("cuda", 0), device_goal=a.device_goal)))
 
 
-def run(envs, steps, episode_steps=150.0, dev=None):
+def run(envs, steps, episode_steps=150.0, dev=None, device_goal=False):
     """-> the result record (also what bench.py reports under secondary["navloop_gpu_side"])."""
     import types
     a = types.SimpleNamespace(envs=envs, steps=steps, episode_steps=episode_steps)
@@ -78,8 +83,14 @@ def run(envs, steps, episode_steps=150.0, dev=None):
     frames = [synth.make_raw_obs(H, W, seed=5, index=i) for i in range(96)]
     res = {"metric": "nav-loop env-steps (policy act + VO + goal update; simulator excluded)", "unit": "env-steps/s",
            "frame": f"{W}x{H}", "dtype": "f32", "results": []}
+    if device_goal:
+        res["goal_update"] = "device (GoalTracker; deltas stay on the GPU)"
     for E in a.envs:
         goals = [np.array([0.0, 0.0, -5.0]) for _ in range(E)]           # goal in the agent frame (x, y, z)
+        tracker = None
+        if device_goal:                     # the same start: agents at the origin, looking down -z (the pose is not logged here)
+            tracker = geometry.GoalTracker(E, dev, track_pose=False)
+            tracker.reset(range(E), np.stack(goals), np.zeros((E, 3)), np.tile([0.0, 0.0, 0.0, 1.0], (E, 1)))
         hid = torch.zeros(pol.num_recurrent_layers, E, 512, device=dev)
         prev_a = torch.zeros(E, 1, dtype=torch.long, device=dev)
         masks = torch.ones(E, 1, device=dev)
@@ -105,17 +116,24 @@ def run(envs, steps, episode_steps=150.0, dev=None):
                 depth = t.ring_depth(prev_obs, env_ids)
             else:
                 depth = torch.from_numpy(np.stack([o["depth"] for o in prev_obs])).to(dev, non_blocking=True)
-            polar = geometry.compute_goal_pos_batch(np.stack(goals), np.zeros((E, 3)))["polar"]
-            obs = {"depth": depth, "pointgoal_with_gps_compass": torch.from_numpy(polar).to(dev)}
+            if tracker is not None:
+                obs = {"depth": depth, "pointgoal_with_gps_compass": tracker.polar}
+            else:
+                polar = geometry.compute_goal_pos_batch(np.stack(goals), np.zeros((E, 3)))["polar"]
+                obs = {"depth": depth, "pointgoal_with_gps_compass": torch.from_numpy(polar).to(dev)}
             tp = mark("policy input (stack + H2D)", tp)
             _, act, _, hid = pol.act(obs, hid, prev_a, masks, deterministic=False)
             tp = mark("policy.act", tp)
             acts = (act.view(-1).cpu().numpy() % 3 + 1).tolist()          # STOP never ends a synthetic episode here
             tp = mark("actions to host", tp)
             cur_obs = [frames[(e + s + 1) % 96] for e in range(E)]
-            deltas = t.compute_local_delta_states_batch(prev_obs, cur_obs, acts, env_ids=env_ids)   # prev_obs IS last step's cur_obs: frame ring
+            deltas = t.compute_local_delta_states_batch(prev_obs, cur_obs, acts, env_ids=env_ids,   # prev_obs IS last step's cur_obs: frame ring
+                                                        to_host=tracker is None)
             tp = mark("VO boundary call", tp)
-            goals[:] = list(geometry.compute_goal_pos_batch(np.stack(goals), deltas)["cartesian"])
+            if tracker is not None:
+                tracker.update(deltas)
+            else:
+                goals[:] = list(geometry.compute_goal_pos_batch(np.stack(goals), deltas)["cartesian"])
             prev_a = torch.as_tensor(acts, device=dev).view(E, 1)
             prev_obs = cur_obs
             mark("goal update", tp)
@@ -130,6 +148,7 @@ def run(envs, steps, episode_steps=150.0, dev=None):
             step(s)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
+        t.check_deferred()
         if phases:
             print(f"[navloop] {E} envs, ms per loop step by phase (host-synchronised):",
                   {k: round(1e3 * v / a.steps, 3) for k, v in ph.items()}, file=sys.stderr)
