@@ -341,6 +341,29 @@ int pnvo_mse_loss_coef(const float *pred, const float *target, const float *coef
 int pnvo_geo_inverse_loss(const float *deltas, const int32_t *actions, int n_entries, int move_forward, float weight,
                           float *out4, float *grad, void *stream);
 
+/* The regression metrics of an evaluation pass (VOCNNRegressionGeometricInvarianceEngine.eval, engine :1020-1257, through
+ * _process_one_batch(train_flag=False) :618-751 and _compute_and_update_info :1259-1311 around vo_cnn_engine.py:135-198): ONE
+ * launch turns a batch's predictions into the reference's table of per-subset metrics and adds it to running totals.  All
+ * pointers are DEVICE memory:
+ *   pred, target [M,3] float32, columns (dx, dz, dyaw);  slot [M] int32, the table row an entry belongs to — the caller numbers
+ *   the (action model, data type) subsets; -1 and every other value outside [0, n_slots) belong to no row and are never used as
+ *   an index;  weights [M,3] float32, _compute_loss_weights' per-entry values, NULL = ones;  dz_mask [M] float32, NULL = ones;
+ *   table [n_slots][3][4] FLOAT64 and count [n_slots] int64, both accumulated into.
+ * Per slot and d, over the slot's entries S:  loss = mean_S(diff^2 [* mask for dz] * w_d);  abs_diff = mean sqrt(diff^2 [* mask]),
+ * for dz over the entries of S with mask == 1 only;  target_magnitude = mean|target| + 1e-8 over those same entries;
+ * relative_diff = abs_diff / target_magnitude;  a dz subset without a mask == 1 entry gives abs_diff 0, target_magnitude 1e-8,
+ * relative_diff 0 and still the mean over S as its loss.  table[slot][d][0..3] += multiplier * {loss, abs_diff, target_magnitude,
+ * relative_diff}, count[slot] += |S|;  multiplier is cur_batch_size in evaluation (update="sum") and 1 for the training logs
+ * (update="append").
+ * Departure from the reference: a slot WITHOUT entries adds nothing and keeps its count, where the reference takes the mean of an
+ * empty tensor and carries NaN into its totals.
+ * Float64 arithmetic, no atomics, one fixed summation order (strided per-thread partials, then a fixed tree): the same inputs
+ * give the same bits.  One workgroup, any M >= 1.  Asynchronous on `stream`, never waits for the device.  A null required
+ * pointer, M <= 0, n_slots <= 0 or n_slots > PNVO_VO_METRICS_MAX_SLOTS return PNVO_ERR_ARG before any launch. */
+#define PNVO_VO_METRICS_MAX_SLOTS 16
+int pnvo_vo_metrics(const float *pred, const float *target, const int32_t *slot, const float *weights, const float *dz_mask, int M,
+                    int n_slots, float multiplier, double *table, int64_t *count, void *stream);
+
 /* nn.Dropout(p) of the two places the reference has one — before visual_fc's Linear and before output_head's Linear
  * (pointnav_vo/vo/models/vo_cnn.py:216-227) — for the train-mode forward/backward.  torch's RNG stream cannot be
  * reproduced; the mask is a counter-based hash of (seed, forward count, layer, element): keep with probability 1-p,

@@ -7,6 +7,8 @@ Sub-modules:
   registry     mirror of the reference's baseline_registry VO-model API
   vo_cnn       nn.Module mirrors registered under the reference's model names (HIP forward)
   trainer      mirror of BaseRLTrainerWithVO (_setup_vo_model / _compute_local_delta_states_from_vo)
+  train        VOTrainStep / GeoInvarianceTrainStep: the VO engine's training iteration
+  evaluate     GeoInvarianceEvalStep: the VO engine's evaluation pass, metrics accumulated on the device
   policy       PointNavResNetPolicy (resnet_rnn_policy) on the HIP path
   baseline_policy  PointNavBaselinePolicy (SimpleCNN + GRU, the plain PPOTrainer's policy) on the HIP path
 """

@@ -91,6 +91,7 @@ _SIGNATURES = {
     "pnvo_mse_loss_coef": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_geo_inverse_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "pnvo_vo_metrics": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_train_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64]),
     "pnvo_train_dropout_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pnvo_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float,

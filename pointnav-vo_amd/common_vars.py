@@ -12,6 +12,11 @@ TURN_RIGHT = 3
 ACT_IDX2NAME = {UNIFIED: "unified", MOVE_FORWARD: "forward", TURN_LEFT: "left", TURN_RIGHT: "right"}
 ACT_NAME2IDX = {"forward": MOVE_FORWARD, "left": TURN_LEFT, "right": TURN_RIGHT, "all": -1}
 
+EPSILON = 1e-8
+CUR_REL_TO_PREV = 0
+PREV_REL_TO_CUR = 1
+DATA_TYPE_ID2STR = {CUR_REL_TO_PREV: "cur_rel_to_prev", PREV_REL_TO_CUR: "prev_rel_to_cur"}
+
 # [x, z, w]
 NO_NOISE_DELTAS = {
     MOVE_FORWARD: [0.0, -0.25, 0.0],

@@ -376,6 +376,58 @@ def regression_coef(n, data_types=None, loss_weights=None, dz_regress_masks=None
     return coef.to(device) if device is not None else coef
 
 
+VO_METRICS_MAX_SLOTS = 16                          # include/pnvo.h PNVO_VO_METRICS_MAX_SLOTS
+
+
+def regressed_types(invariance_types):
+    """The data types the engine regresses (`tmp_data_types`, vo_cnn_regression_geo_invariance_engine.py:682-687), or None
+    without invariance types (:620-679: one subset per action model, whatever the entries' data types)."""
+    if len(invariance_types) == 0:
+        return None
+    both = "inverse_joint_train" in invariance_types or "inverse_data_augment_only" in invariance_types
+    return [CUR_REL_TO_PREV] + ([PREV_REL_TO_CUR] if both else [])
+
+
+def vo_metric_slots(actions, data_types, acts, types):
+    """Row of pnvo_vo_metrics' table for every entry (host int32 [M]): model index * n_types + type index over the action models
+    `acts` (-1: every action) and the regressed `types` (None: one row per model); -1 for an entry no row takes."""
+    actions = torch.as_tensor(actions).reshape(-1).to("cpu", torch.int64)
+    acts = list(acts)
+    if -1 in acts and len(acts) > 1:
+        raise ValueError("a unified model (act = -1) takes every entry: it cannot share a table with per-action models")
+    n_types = 1 if types is None else len(types)
+    if len(acts) * n_types > VO_METRICS_MAX_SLOTS:
+        raise ValueError(f"{len(acts)} models x {n_types} data types exceed the {VO_METRICS_MAX_SLOTS} rows of the metrics table")
+    row = torch.full((actions.numel(),), -1, dtype=torch.int32)
+    for mi, act in enumerate(acts):
+        row[actions == act if act != -1 else torch.ones_like(actions, dtype=torch.bool)] = mi * n_types
+    if types is not None:
+        dt = torch.as_tensor(data_types).reshape(-1).to("cpu", torch.int64)
+        tix = torch.full_like(row, -1)
+        for ti, t in enumerate(types):
+            tix[dt == t] = ti
+        row = torch.where((row >= 0) & (tix >= 0), row + tix, torch.full_like(row, -1))
+    return row
+
+
+def to_device_async(t, dev):
+    """A host tensor to the device through pinned memory, without a wait for the stream (a pageable copy may wait)."""
+    if t.device.type != "cpu":
+        return t.to(dev)
+    return t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def launch_vo_metrics(preds, targets, slot, weights, dz_mask, n_slots, multiplier, table, count, stream):
+    """pnvo_vo_metrics on device tensors: preds / targets [M,3] float32, slot [M] int32, weights [M,3] and dz_mask [M] float32
+    or None, table [n_slots,3,4] float64 and count [n_slots] int64 accumulated into."""
+    assert preds.dtype == targets.dtype == torch.float32 and slot.dtype == torch.int32
+    assert table.dtype == torch.float64 and count.dtype == torch.int64
+    assert preds.is_contiguous() and targets.is_contiguous() and table.is_contiguous()
+    assert tuple(table.shape) == (n_slots, 3, 4) and count.numel() == n_slots and slot.numel() == preds.shape[0]
+    _lib.check(_lib.lib.pnvo_vo_metrics(_ptr(preds), _ptr(targets), _ptr(slot), _ptr(weights), _ptr(dz_mask), int(preds.shape[0]),
+                                        int(n_slots), C.c_float(float(multiplier)), _ptr(table), _ptr(count), stream))
+
+
 class GeoInvarianceTrainStep:
     """One training iteration of VOCNNRegressionGeometricInvarianceEngine for a dict of action models
     (vo_cnn_regression_geo_invariance_engine.py:855-901 around _process_one_batch :451-807): every model sees the
@@ -387,12 +439,36 @@ class GeoInvarianceTrainStep:
 
     steps: {act: VOTrainStep} with act in {-1 (all actions), MOVE_FORWARD, TURN_LEFT, TURN_RIGHT}."""
 
-    def __init__(self, steps, invariance_types=("inverse_joint_train",), loss_inv_weight=1.0):
+    def __init__(self, steps, invariance_types=("inverse_joint_train",), loss_inv_weight=1.0, metrics=False):
         self.steps = dict(steps)
         self.invariance_types = tuple(invariance_types)
         self.loss_inv_weight = float(loss_inv_weight)
         self.dev = next(iter(self.steps.values())).dev
         self.last_logs = {}
+        # metrics = True: every step also leaves the reference's per-step regression logs (update="append", :604-616 and
+        # :1288-1296) in last_logs — "abs_diffs" / "target_magnitudes" / "relative_diffs", device float64 [n_slots,3] over
+        # (dx, dz, dyaw), rows named by last_logs["slots"] = [(act, data type or None)]; a row without entries in the batch is 0.
+        # One more launch (pnvo_vo_metrics on the predictions the step already has); off, nothing is launched or logged.
+        self.metrics = bool(metrics)
+
+    def _log_metrics(self, preds, targets, actions, data_types, loss_weights, dz_regress_masks, stream):
+        dev = self.dev
+        types = regressed_types(self.invariance_types)
+        acts = list(self.steps.keys())
+        n_slots = len(acts) * (1 if types is None else len(types))
+        slot = to_device_async(vo_metric_slots(actions, data_types, acts, types), dev)
+        w = None
+        if loss_weights is not None:
+            w = to_device_async(torch.stack([torch.as_tensor(loss_weights[k], dtype=torch.float32).reshape(-1).cpu()
+                                             for k in ("dx", "dz", "dyaw")], dim=1), dev)
+        m = None
+        if dz_regress_masks is not None:
+            m = to_device_async(torch.as_tensor(dz_regress_masks, dtype=torch.float32).reshape(-1), dev)
+        table = torch.zeros((n_slots, 3, 4), device=dev, dtype=torch.float64)
+        count = torch.zeros(n_slots, device=dev, dtype=torch.int64)
+        launch_vo_metrics(preds, targets.contiguous(), slot, w, m, n_slots, 1.0, table, count, stream)
+        self.last_logs = dict(self.last_logs, abs_diffs=table[:, :, 1], target_magnitudes=table[:, :, 2], relative_diffs=table[:, :, 3],
+                              slots=[(a, t) for a in acts for t in (types if types is not None else [None])])
 
     def step(self, batch, actions, data_types, targets, loss_weights=None, dz_regress_masks=None):
         """batch: dict of NHWC device tensors [M,...] (the model's observation_pairs); actions [M] int; data_types [M]
@@ -461,6 +537,8 @@ class GeoInvarianceTrainStep:
                     full.index_copy_(0, dv, ginv)
                     for act, di in idx_of.items():
                         grads[act] += full.index_select(0, di)
+            if self.metrics and M > 0:
+                self._log_metrics(preds, targets, actions, data_types, loss_weights, dz_regress_masks, stream)
             for act, st in self.steps.items():                   # one fixed order on every rank: the bucket all-reduces of a
                 if act in idx_of:                                #   model start inside its backward ...
                     st.backward(grads[act])
