@@ -375,7 +375,11 @@ int pnvo_train_set_dropout(pnvo_handle h, float p, uint64_t seed);
  * columns of act_embed variants).  For checkers. */
 int pnvo_train_dropout_mask(pnvo_handle h, int layer, float *out, void *stream);
 
-/* torch.optim.Adam(weight_decay=0, amsgrad=False) on flat device buffers; step counts from 1. */
+/* torch.optim.Adam(weight_decay=0, amsgrad=False) on flat device buffers; step counts from 1.  lr, beta1 and beta2 are taken as the
+ * decimals their caller wrote in double (the shortest decimal that rounds to the float given: 0.999f -> 0.999), and every constant
+ * of the step - the complements 1 - beta1 and 1 - beta2, lr / (1 - beta1^step), sqrt(1 - beta2^step) - is formed from them in double
+ * on the host and rounded to float once, as torch does; exp_avg is torch's lerp_.  The moments of a checkpoint are then those of
+ * torch's float32 Adam to float32 rounding, in both directions. */
 int pnvo_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
                    float beta2, float eps, int step, void *stream);
 

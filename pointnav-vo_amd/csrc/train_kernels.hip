@@ -5,6 +5,8 @@
 //   moments behind RunningMeanAndVar's train-mode update.
 // Backward-DATA of the convs reuses conv_mfma_kernel (flipped/transposed packed weights, `up` = forward stride).
 // Reductions have one writer per partial and a fixed summation order: gradients are bit-reproducible.
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -1673,25 +1675,45 @@ hipError_t launch_geo_inverse_loss(const float *deltas, const int *actions, int 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// torch.optim.Adam (weight_decay 0, amsgrad off) on flat buffers; step counts from 1
-__global__ __launch_bounds__(256) void adam_kernel(float *p, const float *g, float *m, float *v, long n, float lr, float b1,
-                                                 float b2, float eps, float bc1, float sqrt_bc2) {
+// torch.optim.Adam (weight_decay 0, amsgrad off) on flat buffers; step counts from 1.
+// Every constant of the step is formed in double on the host and rounded to float ONCE, as torch does with its Python doubles:
+// the complements omb1 = 1 - beta1 and omb2 = 1 - beta2 (the kernel does not subtract from the float betas: 1.f - 0.999f is
+// 0.99998713e-3, 1.29e-5 low — the subtraction is exact, the float 0.999f is 0.99900001 — and exp_avg_sq inherits that), the step
+// size lr / (1 - beta1^step) and sqrt(1 - beta2^step), from lr and the betas as their caller wrote them (as_written).  exp_avg is torch's
+// lerp_(grad, 1 - beta1) in its two forms, m + w (g - m) below w = 0.5 and g - (g - m)(1 - w) from there on: beta1 * m would carry
+// the rounding error of the float 0.9 (2.6e-8) into every step of a decay, w (g - m) a tenth of that of the float 0.1.
+__global__ __launch_bounds__(256) void adam_kernel(float *p, const float *g, float *m, float *v, long n, float omb1, float b2,
+                                                 float omb2, float eps, float step_size, float sqrt_bc2) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
-  const float gi = g[e];
-  const float mi = b1 * m[e] + (1.f - b1) * gi;
-  const float vi = b2 * v[e] + (1.f - b2) * gi * gi;
+  const float gi = g[e], mo = m[e];
+  const float mi = omb1 < 0.5f ? mo + omb1 * (gi - mo) : gi - (gi - mo) * (1.f - omb1);
+  const float vi = b2 * v[e] + omb2 * gi * gi;
   m[e] = mi;
   v[e] = vi;
-  p[e] -= (lr / bc1) * mi / (sqrtf(vi) / sqrt_bc2 + eps);
+  p[e] -= step_size * mi / (sqrtf(vi) / sqrt_bc2 + eps);
+}
+
+// A hyper-parameter crosses the C ABI as a float; its caller wrote it as a decimal in double (0.999, 2.5e-4) and torch computes
+// with that double.  The float still determines it: the shortest decimal that rounds to the float (what repr() of a float32 prints)
+// is what was written, for anything of up to seven significant digits; a value that is exact in float32 (0.5) comes back exactly.
+static double as_written(float x) {
+  char buf[40];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+    if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+  }
+  return (double)x;      // not finite
 }
 
 hipError_t launch_adam(float *p, const float *g, float *m, float *v, long n, float lr, float b1, float b2, float eps,
                        int step, hipStream_t s) {
-  const float bc1 = 1.f - (float)pow((double)b1, (double)step);
-  const float sq2 = (float)sqrt(1.0 - pow((double)b2, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, bc1,
-                     sq2);
+  const double lrd = as_written(lr), b1d = as_written(b1), b2d = as_written(b2);
+  const float omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
+  const float step_size = (float)(lrd / (1.0 - pow(b1d, (double)step)));
+  const float sq2 = (float)sqrt(1.0 - pow(b2d, (double)step));
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, omb1, b2, omb2, eps,
+                     step_size, sq2);
   return hipGetLastError();
 }
 
