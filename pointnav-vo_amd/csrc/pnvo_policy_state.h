@@ -144,7 +144,7 @@ void pnvo_policy_train_free(Policy &p);       // policy_train.hip
 hipError_t launch_policy_inputs(const Policy &p, const float *visual, const float *goal, const int64_t *prev, const float *masks, int rows,
                                 float *x, int *rows_out, float *g3, hipStream_t s);
 // out [rows, hidden] = relu(feat [rows, F] . vfc_w^T + vfc_b): the row kernel of pnvo_policy.hip up to VFC_ROWS_MAX rows, the float32
-// matrix-core GEMM of policy_train.hip above
+// matrix-core GEMM of ppo_core.hip above
 constexpr int VFC_ROWS_MAX = 48;
 int launch_visual_fc(const Policy &p, const float *feat, int rows, float *out, hipStream_t s);
 hipError_t launch_visual_fc_gemm(const float *feat, const float *w, const float *b, int rows, int F, int hidden, float *out, hipStream_t s);   // policy_train.hip
@@ -158,39 +158,6 @@ hipError_t launch_gru_layer(const float *x, int K, const float *w_ih, const floa
                             const float *b_hh, const float *masks, int B, int Hd, float *h_out, hipStream_t s);
 hipError_t launch_policy_heads(const float *feat, const float *act_w, const float *act_b, const float *cr_w, const float *cr_b, int B, int Hd,
                                int n_actions, float *logits, float *value, hipStream_t s);
-
-// ---- the update step's kernels of policy_train.hip as launches, for the baseline policy's update step (simple_cnn_train.hip): the
-// same kernels, not copies.
-// C[m][n] = sum_k A(m,k) B(k,n) (+ bias0[n] + bias1[n]) on the exact-float32 matrix instruction; both operands addressed by two strides
-struct GemmArgs {
-  const float *A, *B, *bias0, *bias1;
-  float *C;
-  int M, N, K;
-  long a_sm, a_sk, b_sk, b_sn, ldc;
-  int relu = 0;                       // epilogue: max(., 0) behind the bias
-};
-// akc / bkc: k is the contiguous index of A / B in memory (else m / n): picks the staging order that reads whole lines
-hipError_t launch_gemm_f32(const GemmArgs &g, bool akc, bool bkc, hipStream_t s);
-// one GRU step over N rows: g [N, 4 Hd] holds G_x = x . W_ih^T + b_ih in blocks 0 .. 2 on entry, (r, z, n, q) on exit
-hipError_t launch_gru_step(float *g, const float *h_prev, const float *w_hh, const float *b_hh, const float *masks, int N, int Hd, float *y,
-                           float *hm, float *h_fin, hipStream_t s);
-hipError_t launch_gru_bptt_step(const float *gates_t, const float *gates_n, const float *dgh_n, const float *dh_n, const float *mask_n,
-                                const float *hm_t, const float *whhT, const float *dY_t, int N, int Hd, float *dgx_t, float *dgh_t,
-                                float *dh_t, hipStream_t s);
-hipError_t launch_heads_eval(const float *feat, const float *act_w, const float *act_b, const float *cr_w, const float *cr_b,
-                             const int64_t *actions, int M, int Hd, int A, float *logits, float *value, float *logp, float *ent,
-                             hipStream_t s);
-hipError_t launch_mean(const float *x, int n, float *out, hipStream_t s);
-hipError_t launch_ppo_loss(const float *logits, const float *value, const float *logp, const float *ent, const int64_t *actions,
-                           const float *old_logp, const float *adv, const float *vpred, const float *ret, int M, int A, float clip, float vc,
-                           float ec, int use_clipped, float *out3, float *dlogits, float *dvalue, hipStream_t s);
-// head weight / bias gradients and d features = dlogits . W_act + dvalue . W_cr
-hipError_t launch_heads_bwd(const float *feat, const float *dlogits, const float *dvalue, const float *act_w, const float *cr_w, int M, int Hd,
-                            int A, float *g_act_w, float *g_act_b, float *g_cr_w, float *g_cr_b, float *dfeat, hipStream_t s);
-hipError_t launch_transpose(const float *src, int R, int C, float *dst, hipStream_t s);       // dst [C][R] = src [R][C]^T
-// clip_grad_norm_ on g[0 .. n): sq_part holds CLIP_PARTIALS doubles of scratch
-constexpr int CLIP_PARTIALS = 1024;
-hipError_t launch_clip_grad_norm(float *g, long n, float scale, float max_norm, double *sq_part, float *norm_out, hipStream_t s);
 
 // ---- host helpers of both files
 inline int pfail(int code, const std::string &msg) { return pnvo_fail(nullptr, code, msg); }

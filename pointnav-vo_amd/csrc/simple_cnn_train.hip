@@ -5,9 +5,10 @@
 //   evaluate : the retained frames [T*N] -> conv_tile_kernel x 3, fc_splitk_kernel, fc_sum_inputs_kernel of simple_cnn.hip on M = T*N rows
 //              (every chain there is independent of the batch size and the row's position: the embedding has the bits act gives)
 //              -> G_x = X . W_ih^T + b_ih                                gru_gx_kernel: the summation order of the act path's GRU kernel
-//              -> T launches of gru_step_kernel, heads_eval_kernel        policy_train.hip's kernels through pnvo_policy_state.h
-//   ppo_loss : ppo_loss_kernel (policy_train.hip)
-//   backward : heads, T launches of gru_bptt_step_kernel, dW_ih / dW_hh / dX on gemm_f32_kernel, the bias column sums  (policy_train.hip's)
+//              -> the GRU's T steps, the heads                            core_recurrent_forward (G_x given), core_heads
+//   ppo_loss, clip_grad_norm, timing : forwards to the core (ppo_core.hip's PpoCore, pnvo_ppo_core.h: the retained rollout, the recurrent
+//              and head kernels, the loss, the clipping — shared with the ResNet policy's update step; this file keeps the SimpleCNN side)
+//   backward : core_backward (heads, BPTT, dW_ih / dW_hh and the bias gradients, dX on torch's [3H][K] weight)
 //              -> d embed = the first `hidden` columns of dX under the ReLU mask                     relu_mask_cols_kernel
 //              -> Linear: db6 = colsum, dW6 = d^T . a3 and dA3 = d . W6 on gemm_f32_kernel.  conv3 writes NHWC, the flat gradient wants the
 //                 NCHW flatten's column order: the ACTIVATION is un-permuted (a3 -> [M][32][P], batched_transpose_kernel: 2 * M * F * 4 bytes)
@@ -33,32 +34,22 @@
 #include "pnvo_model.h"
 #include "pnvo_baseline_state.h"
 #include "pnvo_policy_state.h"
+#include "pnvo_ppo_core.h"
 
 namespace pnvo {
 
 struct BaselineTrain {
-  float *params = nullptr, *grads = nullptr;   // the caller's flat buffers (not owned)
-  size_t n = 0, n_named = 0;          // floats handed over / floats covered by the parameter table
+  PpoCore core;                       // flat buffers, retained rollout, the recurrent layer's and the heads' scratch
   // flat offsets: conv weights (OIHW) and biases, the Linear (columns in the NCHW flatten's order), the recurrent tensors, the heads
-  size_t o_cw[3] = {0, 0, 0}, o_cb[3] = {0, 0, 0}, o_fcw = 0, o_fcb = 0, o_wih = 0, o_whh = 0, o_bih = 0, o_bhh = 0;
-  size_t o_aw = 0, o_ab = 0, o_vw = 0, o_vb = 0;
-  // the last evaluate
-  int T = 0, N = 0, M = 0;
-  bool have_loss = false;
-  int rgb_is_u8 = 0;
-  // workspace, sized for capM rows: the frames in the dtype given, the forward's activations, the backward's gradients
-  int capM = 0;
+  struct Offsets {
+    size_t cw[3] = {0, 0, 0}, cb[3] = {0, 0, 0}, fcw = 0, fcb = 0, wih = 0, whh = 0, bih = 0, bhh = 0, aw = 0, ab = 0, vw = 0, vb = 0;
+  } o;
+  int rgb_is_u8 = 0;                  // of the last evaluate
+  // workspace, sized for core.capM rows: the frames in the dtype given, the forward's activations, the encoder's gradients
   DevBuf<uint8_t> rgb;
-  DevBuf<float> depth, a1, a2, a3, part, x, gates, y, hm, masks, hid0;
-  DevBuf<int64_t> actions;
-  DevBuf<float> logits, value, logp, ent, dlogits, dvalue;
-  DevBuf<float> dY, dX, dG, dGh, dH, whhT;
+  DevBuf<float> depth, a1, a2, a3, part, x, dX;
   DevBuf<float> a3t, d3, d2, d1;      // conv3's map in the NCHW flatten's order; dA3, dA2, dA1 (NHWC)
   DevBuf<float> wpart, bpart;         // weight / bias gradient partials of one conv [slices][K][COUT], [slices][COUT]
-  DevBuf<double> sq_part;             // clip_grad_norm partial sums
-  // pnvo_baseline_train_timing: events at the phase boundaries of evaluate / ppo_loss / backward
-  bool timing = false;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -358,8 +349,6 @@ hipError_t launch_batched_transpose(const float *src, int R, int C, long nb, flo
   return hipGetLastError();
 }
 
-// phase boundary k of the update step (only while timing is on)
-hipError_t mark(BaselineTrain *t, int k, hipStream_t s) { return t->timing ? hipEventRecord(t->ev[k], s) : hipSuccess; }
 
 // the handle's kernel-layout operands from the flat parameter buffer
 int relay_operands(Baseline &p, BaselineTrain *t, hipStream_t s) {
@@ -369,76 +358,58 @@ int relay_operands(Baseline &p, BaselineTrain *t, hipStream_t s) {
     const int kk[3] = {8, 4, 3}, ci[3] = {p.C, 32, 64}, co[3] = {32, 64, 32};
     for (int l = 0; l < 3; ++l) {
       const int taps = kk[l] * kk[l], nel = taps * ci[l] * co[l];
-      hipLaunchKernelGGL(relay_conv_w_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s, t->params + t->o_cw[l], ci[l], co[l], taps,
+      hipLaunchKernelGGL(relay_conv_w_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s, t->core.params + t->o.cw[l], ci[l], co[l], taps,
                          (float *)p.cw[l]);
     }
-    PCHK(launch_batched_transpose(t->params + t->o_fcw, 32, p.oh[2] * p.ow[2], Hd, p.fcw, s));
+    PCHK(launch_batched_transpose(t->core.params + t->o.fcw, 32, p.oh[2] * p.ow[2], Hd, p.fcw, s));
   }
-  hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((3 * Hd * p.Kp + 255) / 256)), dim3(256), 0, s, t->params + t->o_wih, 3 * Hd, K, p.Kp,
+  hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((3 * Hd * p.Kp + 255) / 256)), dim3(256), 0, s, t->core.params + t->o.wih, 3 * Hd, K, p.Kp,
                      (float *)p.w_ih);
   PCHK(hipGetLastError());
   return PNVO_OK;
 }
 
+// the GRU layer as the core reads it: torch's weight_ih_l0 [3H][K] in the flat buffer, the input rows x [M][K] at pitch Kp
+RnnLayer baseline_layer(const Baseline &p, const BaselineTrain *t) {
+  return {t->core.params + t->o.wih, p.w_hh, p.b_ih, p.b_hh, p.E + p.cfg.goal_dim, p.Kp};
+}
+Heads baseline_heads(const Baseline &p) { return {p.act_w, p.act_b, p.cr_w, p.cr_b}; }
+
 void free_ws(BaselineTrain *t) {
-  for (DevBuf<float> *b : {&t->depth, &t->a1, &t->a2, &t->a3, &t->part, &t->x, &t->gates, &t->y, &t->hm, &t->masks, &t->hid0, &t->logits, &t->value,
-                           &t->logp, &t->ent, &t->dlogits, &t->dvalue, &t->dY, &t->dX, &t->dG, &t->dGh, &t->dH, &t->a3t, &t->d3, &t->d2, &t->d1})
-    b->reset();
+  for (DevBuf<float> *b : {&t->depth, &t->a1, &t->a2, &t->a3, &t->part, &t->x, &t->dX, &t->a3t, &t->d3, &t->d2, &t->d1}) b->reset();
   t->rgb.reset();
-  t->actions.reset();
-  t->capM = 0;
+  core_release(&t->core);
 }
 
 int ensure_ws(Baseline &p, BaselineTrain *t, int M, int N) {
-  const pnvo_baseline_config &c = p.cfg;
-  const size_t Hd = (size_t)c.hidden, m = (size_t)M, A = (size_t)c.n_actions, K = (size_t)(p.E + c.goal_dim);
-  PCHK(t->hid0.reserve((size_t)N * Hd));
-  if (M <= t->capM) return PNVO_OK;
-  free_ws(t);                                      // the old workspace goes first; a failed regrow leaves capM = 0
-  PCHK(t->hid0.reserve((size_t)N * Hd));
-  if (!blind(c)) {
-    const size_t px = (size_t)c.height * c.width;
-    if (c.rgb_channels) PCHK(t->rgb.alloc(m * px * 3 * sizeof(float)));      // (either dtype fits)
-    if (c.depth_channels) PCHK(t->depth.alloc(m * px));
-    const size_t n1 = m * p.oh[0] * p.ow[0] * 32, n2 = m * p.oh[1] * p.ow[1] * 64, n3 = m * p.F;
-    PCHK(t->a1.alloc(n1));
-    PCHK(t->a2.alloc(n2));
-    PCHK(t->a3.alloc(n3));
-    PCHK(t->part.alloc((size_t)p.nks * m * Hd));
-    PCHK(t->d1.alloc(n1));
-    PCHK(t->d2.alloc(n2));
-    PCHK(t->d3.alloc(n3));
-    PCHK(t->a3t.alloc(n3));
+  if (M > t->core.capM) {
+    free_ws(t);                                    // the old workspace goes first; a failed regrow leaves core.capM = 0
+    const pnvo_baseline_config &c = p.cfg;
+    const size_t Hd = (size_t)c.hidden, m = (size_t)M, K = (size_t)(p.E + c.goal_dim);
+    if (!blind(c)) {
+      const size_t px = (size_t)c.height * c.width;
+      if (c.rgb_channels) PCHK(t->rgb.alloc(m * px * 3 * sizeof(float)));      // (either dtype fits)
+      if (c.depth_channels) PCHK(t->depth.alloc(m * px));
+      const size_t n1 = m * p.oh[0] * p.ow[0] * 32, n2 = m * p.oh[1] * p.ow[1] * 64, n3 = m * p.F;
+      PCHK(t->a1.alloc(n1));
+      PCHK(t->a2.alloc(n2));
+      PCHK(t->a3.alloc(n3));
+      PCHK(t->part.alloc((size_t)p.nks * m * Hd));
+      PCHK(t->d1.alloc(n1));
+      PCHK(t->d2.alloc(n2));
+      PCHK(t->d3.alloc(n3));
+      PCHK(t->a3t.alloc(n3));
+    }
+    PCHK(t->x.alloc(m * p.Kp));
+    PCHK(t->dX.alloc(m * K));
   }
-  PCHK(t->x.alloc(m * p.Kp));
-  PCHK(t->gates.alloc(m * 4 * Hd));
-  PCHK(t->y.alloc(m * Hd));
-  PCHK(t->hm.alloc(m * Hd));
-  PCHK(t->masks.alloc(m));
-  PCHK(t->actions.alloc(m));
-  PCHK(t->logits.alloc(m * A));
-  PCHK(t->value.alloc(m));
-  PCHK(t->logp.alloc(m));
-  PCHK(t->ent.alloc(m));
-  PCHK(t->dlogits.alloc(m * A));
-  PCHK(t->dvalue.alloc(m));
-  PCHK(t->dY.alloc(m * Hd));
-  PCHK(t->dX.alloc(m * K));
-  PCHK(t->dG.alloc(m * 3 * Hd));
-  PCHK(t->dGh.alloc(m * 3 * Hd));
-  PCHK(t->dH.alloc(m * Hd));
-  t->capM = M;
-  return PNVO_OK;
+  return core_reserve(&t->core, M, N);
 }
 
 }  // namespace
 
 void pnvo_baseline_train_free(Baseline &p) {
-  BaselineTrain *t = p.train;
-  if (!t) return;
-  for (hipEvent_t &e : t->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete t;
+  delete p.train;
   p.train = nullptr;
 }
 
@@ -460,7 +431,7 @@ int pnvo_baseline_train_attach(pnvo_baseline_handle h, float *params, float *gra
   const pnvo_baseline_config &c = p.cfg;
   const int64_t Hd = c.hidden, A = c.n_actions, K = p.E + c.goal_dim;
   int rc = PNVO_OK;
-  BaselineTrain nt;                    // offsets are collected here: nothing of the handle changes before every entry has been checked
+  BaselineTrain::Offsets o;            // collected here: nothing of the handle changes before every entry has been checked
   // rows the kernels read as 16-byte vectors must start at a multiple of 4 floats
   auto find = [&](const std::string &name, std::vector<int64_t> shape, bool f4, size_t *off) -> bool {
     PolicyParam e{name, std::move(shape), nullptr, f4};
@@ -478,14 +449,14 @@ int pnvo_baseline_train_attach(pnvo_baseline_handle h, float *params, float *gra
     const int64_t kk[3] = {8, 4, 3}, ci[3] = {p.C, 32, 64}, co[3] = {32, 64, 32};
     for (int l = 0; l < 3; ++l) {
       const std::string pre = cnn + std::to_string(2 * l);
-      if (!find(pre + ".weight", {co[l], ci[l], kk[l], kk[l]}, false, &nt.o_cw[l]) || !find(pre + ".bias", {co[l]}, true, &nt.o_cb[l])) return rc;
+      if (!find(pre + ".weight", {co[l], ci[l], kk[l], kk[l]}, false, &o.cw[l]) || !find(pre + ".bias", {co[l]}, true, &o.cb[l])) return rc;
     }
-    if (!find(cnn + "6.weight", {Hd, (int64_t)p.F}, true, &nt.o_fcw) || !find(cnn + "6.bias", {Hd}, false, &nt.o_fcb)) return rc;
+    if (!find(cnn + "6.weight", {Hd, (int64_t)p.F}, true, &o.fcw) || !find(cnn + "6.bias", {Hd}, false, &o.fcb)) return rc;
   }
-  if (!find(rnn + "weight_ih_l0", {3 * Hd, K}, false, &nt.o_wih) || !find(rnn + "weight_hh_l0", {3 * Hd, Hd}, true, &nt.o_whh) ||
-      !find(rnn + "bias_ih_l0", {3 * Hd}, false, &nt.o_bih) || !find(rnn + "bias_hh_l0", {3 * Hd}, false, &nt.o_bhh) ||
-      !find("action_distribution.linear.weight", {A, Hd}, true, &nt.o_aw) || !find("action_distribution.linear.bias", {A}, false, &nt.o_ab) ||
-      !find("critic.fc.weight", {1, Hd}, true, &nt.o_vw) || !find("critic.fc.bias", {1}, false, &nt.o_vb))
+  if (!find(rnn + "weight_ih_l0", {3 * Hd, K}, false, &o.wih) || !find(rnn + "weight_hh_l0", {3 * Hd, Hd}, true, &o.whh) ||
+      !find(rnn + "bias_ih_l0", {3 * Hd}, false, &o.bih) || !find(rnn + "bias_hh_l0", {3 * Hd}, false, &o.bhh) ||
+      !find("action_distribution.linear.weight", {A, Hd}, true, &o.aw) || !find("action_distribution.linear.bias", {A}, false, &o.ab) ||
+      !find("critic.fc.weight", {1, Hd}, true, &o.vw) || !find("critic.fc.bias", {1}, false, &o.vb))
     return rc;
   size_t n_named = 0;
   for (int k = 0; k < ntoc; ++k) {
@@ -497,13 +468,10 @@ int pnvo_baseline_train_attach(pnvo_baseline_handle h, float *params, float *gra
   pnvo_baseline_train_free(p);
   BaselineTrain *t = new BaselineTrain();
   p.train = t;
-  t->params = params, t->grads = grads, t->n = n_floats, t->n_named = n_named;
-  for (int l = 0; l < 3; ++l) t->o_cw[l] = nt.o_cw[l], t->o_cb[l] = nt.o_cb[l];
-  t->o_fcw = nt.o_fcw, t->o_fcb = nt.o_fcb, t->o_wih = nt.o_wih, t->o_whh = nt.o_whh, t->o_bih = nt.o_bih, t->o_bhh = nt.o_bhh;
-  t->o_aw = nt.o_aw, t->o_ab = nt.o_ab, t->o_vw = nt.o_vw, t->o_vb = nt.o_vb;
+  t->o = o;
   rc = [&]() -> int {
-    PCHK(t->whhT.alloc((size_t)3 * Hd * Hd));
-    PCHK(t->sq_part.alloc(CLIP_PARTIALS));
+    const int rc1 = core_init(&t->core, "pnvo_baseline", p.device, params, grads, n_floats, n_named, c.hidden, 1, c.n_actions, true);
+    if (rc1 != PNVO_OK) return rc1;
     const int rc2 = relay_operands(p, t, nullptr);
     if (rc2 != PNVO_OK) return rc2;
     PCHK(hipDeviceSynchronize());
@@ -517,11 +485,11 @@ int pnvo_baseline_train_attach(pnvo_baseline_handle h, float *params, float *gra
   p.owned.clear();
   p.attached = true;
   if (!blind(c)) {
-    for (int l = 0; l < 3; ++l) p.cb[l] = params + t->o_cb[l];
-    p.fcb = params + t->o_fcb;
+    for (int l = 0; l < 3; ++l) p.cb[l] = params + o.cb[l];
+    p.fcb = params + o.fcb;
   }
-  p.w_hh = params + t->o_whh, p.b_ih = params + t->o_bih, p.b_hh = params + t->o_bhh;
-  p.act_w = params + t->o_aw, p.act_b = params + t->o_ab, p.cr_w = params + t->o_vw, p.cr_b = params + t->o_vb;
+  p.w_hh = params + o.whh, p.b_ih = params + o.bih, p.b_hh = params + o.bhh;
+  p.act_w = params + o.aw, p.act_b = params + o.ab, p.cr_w = params + o.vw, p.cr_b = params + o.vb;
   return PNVO_OK;
 }
 
@@ -538,144 +506,99 @@ int pnvo_baseline_evaluate(pnvo_baseline_handle h, const void *rgb, int rgb_is_u
   Baseline &p = h->p;
   BaselineTrain *t = p.train;
   const pnvo_baseline_config &c = p.cfg;
-  if (T <= 0 || N <= 0 || (long)T * N > (1L << 20))
-    return pfail(PNVO_ERR_ARG, "bad rollout shape T = " + std::to_string(T) + ", N = " + std::to_string(N));
-  if (!goal || !masks || !hidden_in || !actions || !hidden_out) return pfail(PNVO_ERR_ARG, "null argument");
-  const int M = T * N, Hd = c.hidden, A = c.n_actions;
-  int rc = baseline_frames_check(p, "pnvo_baseline_evaluate", rgb, rgb_is_u8, depth, M);
+  const int Hd = c.hidden;
+  int rc = core_check_rollout("pnvo_baseline_evaluate", T, N, {goal, masks, actions}, hidden_in, hidden_out, (size_t)N * Hd, "N * hidden");
   if (rc != PNVO_OK) return rc;
-  if (((uintptr_t)hidden_in & 15) || ((uintptr_t)hidden_out & 15))
-    return pfail(PNVO_ERR_ARG, "pnvo_baseline_evaluate: hidden_in / hidden_out must be 16-byte aligned");
-  if (hidden_states_overlap(hidden_in, hidden_out, (size_t)N * Hd))
-    return pfail(PNVO_ERR_ARG, "hidden_out overlaps hidden_in (each holds N * hidden floats): pass separate buffers");
+  const int M = T * N;
+  if ((rc = baseline_frames_check(p, "pnvo_baseline_evaluate", rgb, rgb_is_u8, depth, M)) != PNVO_OK) return rc;
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   if ((rc = ensure_ws(p, t, M, N)) != PNVO_OK) return rc;
-  t->T = T, t->N = N, t->M = M;
-  t->have_loss = false;
   t->rgb_is_u8 = rgb_is_u8;
-  // what the backward reads later is kept here: the caller's tensors may be gone by then
-  PCHK(hipMemcpyAsync(t->masks, masks, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
-  PCHK(hipMemcpyAsync(t->actions, actions, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-  PCHK(hipMemcpyAsync(t->hid0, hidden_in, (size_t)N * Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if ((rc = core_keep(&t->core, T, N, masks, actions, hidden_in, s)) != PNVO_OK) return rc;
   const size_t px = (size_t)M * c.height * c.width;
   if (rgb) PCHK(hipMemcpyAsync(t->rgb, rgb, px * 3 * (rgb_is_u8 ? 1 : sizeof(float)), hipMemcpyDeviceToDevice, s));
   if (depth) PCHK(hipMemcpyAsync(t->depth, depth, px * sizeof(float), hipMemcpyDeviceToDevice, s));
-  PCHK(mark(t, 0, s));
+  PCHK(core_mark(&t->core, 0, s));
   if (!blind(c) && (rc = baseline_encoder_launches(p, rgb ? (const void *)t->rgb : nullptr, rgb_is_u8, depth ? (const float *)t->depth : nullptr, M,
                                                    t->a1, t->a2, t->a3, t->part, s)) != PNVO_OK)
     return rc;
   PCHK(baseline_sum_inputs(p, t->part, goal, M, t->x, nullptr, s));
-  PCHK(mark(t, 1, s));
-  hipLaunchKernelGGL(gru_gx_kernel, dim3((unsigned)(3 * Hd)), dim3(256), 0, s, t->x, p.Kp, p.w_ih, p.b_ih, M, Hd, t->gates);
+  PCHK(core_mark(&t->core, 1, s));
+  hipLaunchKernelGGL(gru_gx_kernel, dim3((unsigned)(3 * Hd)), dim3(256), 0, s, t->x, p.Kp, p.w_ih, p.b_ih, M, Hd, t->core.gates[0]);
   PCHK(hipGetLastError());
-  for (int ts = 0; ts < T; ++ts) {
-    const size_t r = (size_t)ts * N;
-    const float *h_prev = ts ? t->y + (r - N) * Hd : (const float *)t->hid0;
-    PCHK(launch_gru_step(t->gates + r * 4 * Hd, h_prev, p.w_hh, p.b_hh, t->masks + r, N, Hd, t->y + r * Hd, t->hm + r * Hd,
-                         ts == T - 1 ? hidden_out : nullptr, s));
-  }
-  PCHK(launch_heads_eval(t->y, p.act_w, p.act_b, p.cr_w, p.cr_b, t->actions, M, Hd, A, t->logits, t->value, t->logp, t->ent, s));
-  if (value) PCHK(hipMemcpyAsync(value, t->value, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (logp) PCHK(hipMemcpyAsync(logp, t->logp, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (entropy) PCHK(launch_mean(t->ent, M, entropy, s));
-  PCHK(mark(t, 2, s));
-  return PNVO_OK;
+  const RnnLayer layer = baseline_layer(p, t);
+  if ((rc = core_recurrent_forward(&t->core, &layer, t->x, true, hidden_out, s)) != PNVO_OK) return rc;
+  return core_heads(&t->core, baseline_heads(p), value, logp, entropy, s);
 }
 
 int pnvo_baseline_ppo_loss(pnvo_baseline_handle h, const float *actions_logp_old, const float *adv, const float *value_preds,
                            const float *returns, float clip, float value_coef, float entropy_coef, int use_clipped_value_loss, float *out3,
                            void *stream) {
   TRAIN_OR_FAIL(h);
-  Baseline &p = h->p;
-  BaselineTrain *t = p.train;
-  if (t->M <= 0) return pfail(PNVO_ERR_STATE, "pnvo_baseline_ppo_loss before pnvo_baseline_evaluate");
-  if (!actions_logp_old || !adv || !returns || !out3 || (use_clipped_value_loss && !value_preds)) return pfail(PNVO_ERR_ARG, "null argument");
-  if (!(clip >= 0.f)) return pfail(PNVO_ERR_ARG, "clip_param " + std::to_string(clip) + " must be >= 0");
-  PCHK(hipSetDevice(p.device));
-  hipStream_t s = (hipStream_t)stream;
-  PCHK(mark(t, 3, s));
-  PCHK(launch_ppo_loss(t->logits, t->value, t->logp, t->ent, t->actions, actions_logp_old, adv, value_preds, returns, t->M, p.cfg.n_actions, clip,
-                       value_coef, entropy_coef, use_clipped_value_loss ? 1 : 0, out3, t->dlogits, t->dvalue, s));
-  PCHK(mark(t, 4, s));
-  t->have_loss = true;
-  return PNVO_OK;
+  return core_ppo_loss(&h->p.train->core, actions_logp_old, adv, value_preds, returns, clip, value_coef, entropy_coef, use_clipped_value_loss,
+                       out3, (hipStream_t)stream);
 }
 
 int pnvo_baseline_backward(pnvo_baseline_handle h, int train_encoder, void *stream) {
   TRAIN_OR_FAIL(h);
   Baseline &p = h->p;
   BaselineTrain *t = p.train;
-  if (t->M <= 0 || !t->have_loss) return pfail(PNVO_ERR_STATE, "pnvo_baseline_backward before pnvo_baseline_evaluate + pnvo_baseline_ppo_loss");
+  int rc = core_backward_ready(&t->core);
+  if (rc != PNVO_OK) return rc;
   PCHK(hipSetDevice(p.device));
   hipStream_t s = (hipStream_t)stream;
   const pnvo_baseline_config &c = p.cfg;
-  const int Hd = c.hidden, A = c.n_actions, M = t->M, T = t->T, N = t->N, G3 = 3 * Hd, K = p.E + c.goal_dim, Kp = p.Kp;
+  const int Hd = c.hidden, M = t->core.M, K = p.E + c.goal_dim, Kp = p.Kp;
   const bool encoder = !blind(c) && train_encoder != 0;
-  float *G = t->grads;
+  float *G = t->core.grads;
   auto g = [&](size_t off) { return G + off; };
-  int rc = encoder ? reserve_wgrad(p, t, M) : PNVO_OK;
-  if (rc != PNVO_OK) return rc;
-  PCHK(mark(t, 5, s));
+  if (encoder && (rc = reserve_wgrad(p, t, M)) != PNVO_OK) return rc;
+  PCHK(core_mark(&t->core, 5, s));
   // overwrite semantics; a frozen encoder's range stays zero.  The Linear's weight gradient, 51 MB at the reference's frame, is written
   // in full by its GEMM: it is left out of the clear
   if (encoder) {
-    const size_t lo = t->o_fcw, hi = t->o_fcw + (size_t)Hd * p.F;
+    const size_t lo = t->o.fcw, hi = t->o.fcw + (size_t)Hd * p.F;
     if (lo > 0) PCHK(hipMemsetAsync(G, 0, lo * sizeof(float), s));
-    if (t->n > hi) PCHK(hipMemsetAsync(G + hi, 0, (t->n - hi) * sizeof(float), s));
+    if (t->core.n > hi) PCHK(hipMemsetAsync(G + hi, 0, (t->core.n - hi) * sizeof(float), s));
   } else {
-    PCHK(hipMemsetAsync(G, 0, t->n * sizeof(float), s));
+    PCHK(hipMemsetAsync(G, 0, t->core.n * sizeof(float), s));
   }
-  PCHK(launch_heads_bwd(t->y, t->dlogits, t->dvalue, p.act_w, p.cr_w, M, Hd, A, g(t->o_aw), g(t->o_ab), g(t->o_vw), g(t->o_vb), t->dY, s));
-  PCHK(launch_transpose(p.w_hh, G3, Hd, t->whhT, s));
-  for (int ts = T - 1; ts >= 0; --ts) {
-    const size_t r = (size_t)ts * N, rn = r + N;
-    const bool last = ts == T - 1;
-    PCHK(launch_gru_bptt_step(t->gates + r * 4 * Hd, last ? nullptr : t->gates + rn * 4 * Hd, last ? nullptr : t->dGh + rn * G3,
-                              last ? nullptr : t->dH + rn * Hd, last ? nullptr : t->masks + rn, t->hm + r * Hd, t->whhT, t->dY + r * Hd, N, Hd,
-                              t->dG + r * G3, t->dGh + r * G3, t->dH + r * Hd, s));
-  }
-  // dW_ih = dGx^T . X (the unpadded K columns of the rows at pitch Kp),  dW_hh = dGh^T . (h_prev * mask),  db = column sums
-  GemmArgs wi{t->dG, t->x, nullptr, nullptr, g(t->o_wih), G3, K, M, 1, (long)G3, (long)Kp, 1, (long)K};
-  PCHK(launch_gemm_f32(wi, false, false, s));
-  GemmArgs wh{t->dGh, t->hm, nullptr, nullptr, g(t->o_whh), G3, Hd, M, 1, (long)G3, (long)Hd, 1, (long)Hd};
-  PCHK(launch_gemm_f32(wh, false, false, s));
-  PCHK(launch_colsum(t->dG, M, G3, G3, g(t->o_bih), s));
-  PCHK(launch_colsum(t->dGh, M, G3, G3, g(t->o_bhh), s));
-  if (!encoder) {                        // blind, or net.visual_encoder frozen: its range stays at the clear's zeros
-    PCHK(mark(t, 6, s));
-    PCHK(mark(t, 7, s));
+  // blind, or net.visual_encoder frozen: no dX, and the encoder's range stays at the clear's zeros
+  const RnnLayer layer = baseline_layer(p, t);
+  if ((rc = core_backward(&t->core, &layer, baseline_heads(p), t->x, encoder ? (float *)t->dX : nullptr, s)) != PNVO_OK) return rc;
+  if (!encoder) {
+    PCHK(core_mark(&t->core, 6, s));
+    PCHK(core_mark(&t->core, 7, s));
     return PNVO_OK;
   }
-  // dX = dGx . W_ih on torch's [3H][K]; d embed = its first `hidden` columns under the Linear's ReLU
-  GemmArgs dx{t->dG, t->params + t->o_wih, nullptr, nullptr, t->dX, M, K, G3, (long)G3, 1, (long)K, 1, (long)K};
-  PCHK(launch_gemm_f32(dx, true, false, s));
+  // d embed = the first `hidden` columns of dX under the Linear's ReLU
   hipLaunchKernelGGL(relu_mask_cols_kernel, dim3((unsigned)(((long)M * Hd + 255) / 256)), dim3(256), 0, s, t->x, Kp, M, Hd, K, t->dX);
   PCHK(hipGetLastError());
-  PCHK(mark(t, 6, s));
+  PCHK(core_mark(&t->core, 6, s));
   // the Linear: db6, dW6 = d^T . a3 (a3 un-permuted to the NCHW flatten's order, the gradient written in torch's layout), dA3 = d . W6
   const int P3 = p.oh[2] * p.ow[2], F = p.F;
-  PCHK(launch_colsum(t->dX, M, Hd, K, g(t->o_fcb), s));
+  PCHK(launch_colsum(t->dX, M, Hd, K, g(t->o.fcb), s));
   PCHK(launch_batched_transpose(t->a3, P3, 32, M, t->a3t, s));
-  GemmArgs dw6{t->dX, t->a3t, nullptr, nullptr, g(t->o_fcw), Hd, F, M, 1, (long)K, (long)F, 1, (long)F};
+  GemmArgs dw6{t->dX, t->a3t, nullptr, nullptr, g(t->o.fcw), Hd, F, M, 1, (long)K, (long)F, 1, (long)F};
   PCHK(launch_gemm_f32(dw6, false, false, s));
   GemmArgs da3{t->dX, p.fcw, nullptr, nullptr, t->d3, M, F, Hd, (long)K, 1, (long)F, 1, (long)F};
   PCHK(launch_gemm_f32(da3, true, false, s));
   // conv3 (3x3, stride 1, 64 -> 32; no ReLU behind it)
   TileArgs t3{nullptr, nullptr, t->a2, nullptr, nullptr, nullptr, M * P3, p.oh[1], p.ow[1], p.oh[2], p.ow[2]};
-  if ((rc = launch_wgrad<0, 0, 64, 3, 3, 1, 32>(t, t3, t->d3, g(t->o_cw[2]), g(t->o_cb[2]), s)) != PNVO_OK) return rc;
+  if ((rc = launch_wgrad<0, 0, 64, 3, 3, 1, 32>(t, t3, t->d3, g(t->o.cw[2]), g(t->o.cb[2]), s)) != PNVO_OK) return rc;
   DgradArgs g3{t->d3, p.cw[2], t->a2, t->d2, M, p.oh[1], p.ow[1], p.oh[2], p.ow[2]};
   PCHK((launch_dgrad<64, 3, 3, 1, 32>(g3, s)));
   // conv2 (4x4, stride 2, 32 -> 64)
   TileArgs t2{nullptr, nullptr, t->a1, nullptr, nullptr, nullptr, M * p.oh[1] * p.ow[1], p.oh[0], p.ow[0], p.oh[1], p.ow[1]};
-  if ((rc = launch_wgrad<0, 0, 32, 4, 4, 2, 64>(t, t2, t->d2, g(t->o_cw[1]), g(t->o_cb[1]), s)) != PNVO_OK) return rc;
+  if ((rc = launch_wgrad<0, 0, 32, 4, 4, 2, 64>(t, t2, t->d2, g(t->o.cw[1]), g(t->o.cb[1]), s)) != PNVO_OK) return rc;
   DgradArgs g2{t->d2, p.cw[1], t->a1, t->d1, M, p.oh[0], p.ow[0], p.oh[1], p.ow[1]};
   PCHK((launch_dgrad<32, 4, 4, 2, 64>(g2, s)));
   // conv1 (8x8, stride 4, frames -> 32): the weight gradient alone, through the forward's frame loader
   const void *rgb = c.rgb_channels ? (const void *)t->rgb : nullptr;
   TileArgs t1{rgb, c.depth_channels ? (const float *)t->depth : nullptr, nullptr, nullptr, nullptr, nullptr, M * p.oh[0] * p.ow[0], c.height, c.width,
               p.oh[0], p.ow[0]};
-  float *gw1 = g(t->o_cw[0]), *gb1 = g(t->o_cb[0]);
+  float *gw1 = g(t->o.cw[0]), *gb1 = g(t->o.cb[0]);
   if (c.rgb_channels && c.depth_channels)
     rc = t->rgb_is_u8 ? launch_wgrad<2, 3, 4, 8, 8, 4, 32>(t, t1, t->d1, gw1, gb1, s) : launch_wgrad<1, 3, 4, 8, 8, 4, 32>(t, t1, t->d1, gw1, gb1, s);
   else if (c.rgb_channels)
@@ -683,42 +606,24 @@ int pnvo_baseline_backward(pnvo_baseline_handle h, int train_encoder, void *stre
   else
     rc = launch_wgrad<1, 0, 1, 8, 8, 4, 32>(t, t1, t->d1, gw1, gb1, s);
   if (rc != PNVO_OK) return rc;
-  PCHK(mark(t, 7, s));
+  PCHK(core_mark(&t->core, 7, s));
   return PNVO_OK;
 }
 
 int pnvo_baseline_clip_grad_norm(pnvo_baseline_handle h, float max_norm, float *norm_out, void *stream) {
   TRAIN_OR_FAIL(h);
   if (!(max_norm > 0.f)) return pfail(PNVO_ERR_ARG, "max_grad_norm " + std::to_string(max_norm) + " must be > 0");
-  BaselineTrain *t = h->p.train;
-  PCHK(hipSetDevice(h->p.device));
-  PCHK(launch_clip_grad_norm(t->grads, (long)t->n_named, 1.f, max_norm, t->sq_part, norm_out, (hipStream_t)stream));
-  return PNVO_OK;
+  return core_clip_grad_norm(&h->p.train->core, 1.f, max_norm, norm_out, (hipStream_t)stream);
 }
 
 int pnvo_baseline_train_timing(pnvo_baseline_handle h, int mode) {
   TRAIN_OR_FAIL(h);
-  BaselineTrain *t = h->p.train;
-  PCHK(hipSetDevice(h->p.device));
-  if (mode)
-    for (hipEvent_t &e : t->ev)
-      if (!e) PCHK(hipEventCreate(&e));
-  t->timing = mode != 0;
-  return PNVO_OK;
+  return core_timing(&h->p.train->core, mode);
 }
 
 int pnvo_baseline_train_timing_read(pnvo_baseline_handle h, double ms[5]) {
   if (!h || !h->p.train || !ms) return pfail(PNVO_ERR_STATE, "pnvo_baseline_train_attach first");
-  BaselineTrain *t = h->p.train;
-  if (!t->timing) return pfail(PNVO_ERR_STATE, "pnvo_baseline_train_timing(h, 1) first");
-  PCHK(hipEventSynchronize(t->ev[7]));
-  const int pairs[5][2] = {{0, 1}, {1, 2}, {3, 4}, {5, 6}, {6, 7}};
-  for (int k = 0; k < 5; ++k) {
-    float f = 0.f;
-    PCHK(hipEventElapsedTime(&f, t->ev[pairs[k][0]], t->ev[pairs[k][1]]));
-    ms[k] = (double)f;
-  }
-  return PNVO_OK;
+  return core_timing_read(&h->p.train->core, ms);
 }
 
 }  // extern "C"

@@ -68,6 +68,20 @@ class _AdamView:
 
 
 class PolicyTrainStep:
+    _abi = "pnvo_policy_"                                   # prefix of the library's update-step entry points for this kind of policy
+
+    def _fn(self, name):
+        return getattr(_lib.lib, self._abi + name)
+
+    def _attach(self):
+        """-> (the library's attach, floats it wants behind the parameters: the encoder handle's padded stem and unused head)"""
+        return _lib.lib.pnvo_policy_train_attach, int(_lib.lib.pnvo_policy_train_tail_floats(self.policy._handle))
+
+    def _encoder_range(self):
+        """Flat range [lo, hi) of net.visual_encoder's parameters; None when the policy has none (a blind baseline policy)."""
+        enc = [self.offsets[n] for n, _ in self.store.named if n.startswith(ENCODER_PREFIX)]
+        return (min(o for o, _ in enc), max(o + k for o, k in enc)) if enc else None
+
     def __init__(self, policy, lr=2.5e-4, eps=1e-5, max_grad_norm=0.5, train_encoder=True, betas=(0.9, 0.999)):
         self.policy = policy
         self.lr, self.eps, self.betas = float(lr), float(eps), tuple(betas)
@@ -80,23 +94,19 @@ class PolicyTrainStep:
                                       "requires_grad, or PolicyTrainStep(..., train_encoder=False))")
         ref = next(policy.parameters())
         if ref.device.type != "cuda":
-            raise RuntimeError("PolicyTrainStep runs on an MI355X only: move the policy with .to('cuda') first "
+            raise RuntimeError(f"{type(self).__name__} runs on an MI355X only: move the policy with .to('cuda') first "
                                "(there is no CPU fallback)")
         self.dev = ref.device
         policy._ensure(self.dev)                                # handle + kernel operand buffers
-        h = policy._handle
-        # every tensor at a multiple of 4 floats (flat_offsets); the tail holds the encoder handle's padded stem and unused head
-        self.store = FlatParams(list(policy.named_parameters()), self.dev, align=4,
-                                tail=int(_lib.lib.pnvo_policy_train_tail_floats(h)))
+        attach, tail = self._attach()
+        self.store = FlatParams(list(policy.named_parameters()), self.dev, align=4, tail=tail)     # every tensor at a multiple of 4 floats
         self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (self.store.flat, self.store.grad, self.store.exp_avg,
                                                                self.store.exp_avg_sq)
         self.offsets, self.n_params = self.store.offsets, self.store.n_params
-        enc = [self.offsets[n] for n, _ in self.store.named if n.startswith(ENCODER_PREFIX)]
-        self.encoder_range = (min(o for o, _ in enc), max(o + k for o, k in enc))
+        self.encoder_range = self._encoder_range()
         torch.cuda.synchronize(self.dev)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_policy_train_attach(h, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), self.store.toc,
-                                                         len(self.store.named)))
+            _lib.check(attach(policy._handle, _ptr(self.flat), _ptr(self.grad), self.flat.numel(), self.store.toc, len(self.store.named)))
         self.step_count = 0
         self._from_features = False                             # the last evaluate_actions took observations['visual_features']
         self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
@@ -114,7 +124,7 @@ class PolicyTrainStep:
         end = max(o + k for o, k in self.offsets.values())
         # after an evaluate_actions from visual_features no encoder parameter has a gradient, whatever train_encoder says: the reference's
         # have `grad is None` there and torch's Adam skips them (no step, no moment update)
-        if self.train_encoder and not self._from_features:
+        if (self.train_encoder and not self._from_features) or self.encoder_range is None:
             return [(0, end)]
         lo, hi = self.encoder_range
         return [(a, b) for a, b in ((0, lo), (hi, end)) if b > a]
@@ -137,7 +147,7 @@ class PolicyTrainStep:
                 _lib.check(_lib.lib.pnvo_policy_train_reload_encoder(self.policy._handle, self.store.toc, len(self.store.named),
                                                                      self._stream()))
             for _ in range(3):                                 # three: flat_params.py, "The owner's part"
-                _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, self._stream()))
+                _lib.check(self._fn("train_refresh")(self.policy._handle, self._stream()))
         torch.cuda.current_stream(self.dev).synchronize()
         self.store.mark()
 
@@ -202,35 +212,35 @@ class PolicyTrainStep:
         f = lambda t: None if t is None else t.to(device=self.dev, dtype=torch.float32).contiguous().reshape(-1)
         old, adv, vp, ret = f(old_action_log_probs), f(adv_targ), f(value_preds), f(returns)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_policy_ppo_loss(self.policy._handle, _ptr(old), _ptr(adv), _ptr(vp), _ptr(ret), float(clip_param),
-                                                     float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
-                                                     _ptr(self._out3), self._stream()))
+            _lib.check(self._fn("ppo_loss")(self.policy._handle, _ptr(old), _ptr(adv), _ptr(vp), _ptr(ret), float(clip_param),
+                                            float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
+                                            _ptr(self._out3), self._stream()))
         return self._out3
 
     def backward(self):
         """total_loss.backward(): fills self.grad (overwrites).  After an evaluate_actions from visual_features the encoder's range is
-        exactly zero, whatever train_encoder says (the library knows which kind of evaluate came last)."""
+        exactly zero, whatever train_encoder says (the library knows which kind of evaluate came last); with train_encoder False it
+        stays exactly zero too."""
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_policy_backward(self.policy._handle, int(self.train_encoder), self._stream()))
+            _lib.check(self._fn("backward")(self.policy._handle, int(self.train_encoder), self._stream()))
 
     def clip_grad_norm(self):
         """nn.utils.clip_grad_norm_(parameters, max_grad_norm) on the device -> the norm as a device tensor [1] (no host sync)."""
         if self.max_grad_norm is None:
             return None
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_policy_clip_grad_norm(self.policy._handle, float(self.max_grad_norm), _ptr(self._norm),
-                                                           self._stream()))
+            _lib.check(self._fn("clip_grad_norm")(self.policy._handle, float(self.max_grad_norm), _ptr(self._norm), self._stream()))
         return self._norm
 
     def timing(self, on=True):
         """Record HIP events at the phase boundaries of the update (tools/bench_ppo_update.py)."""
-        _lib.check(_lib.lib.pnvo_policy_train_timing(self.policy._handle, int(bool(on))))
+        _lib.check(self._fn("train_timing")(self.policy._handle, int(bool(on))))
 
     def phase_ms(self):
         """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, LSTM (or GRU) forward +
         heads, loss, heads + BPTT + embedding backward, encoder backward."""
         ms = (C.c_double * 5)()
-        _lib.check(_lib.lib.pnvo_policy_train_timing_read(self.policy._handle, ms))
+        _lib.check(self._fn("train_timing_read")(self.policy._handle, ms))
         return dict(zip(("encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward"), (float(v) for v in ms)))
 
     def optimizer_step(self):
@@ -239,7 +249,7 @@ class PolicyTrainStep:
         with torch.cuda.device(self.dev):
             stream = self._stream()
             self.store.adam_step(self._ranges(), self.lr, self.betas, self.eps, self.step_count, stream)
-            _lib.check(_lib.lib.pnvo_policy_train_refresh(self.policy._handle, stream))
+            _lib.check(self._fn("train_refresh")(self.policy._handle, stream))
 
 
 class BaselineTrainStep(PolicyTrainStep):
@@ -248,40 +258,10 @@ class BaselineTrainStep(PolicyTrainStep):
     and the gradients land in `grad` in torch's layouts, the handle re-lays its kernel operands from `flat` on the device after every
     optimiser step (pnvo_baseline_train_refresh).  float32 frames-in only: no visual_features input, no bf16."""
 
-    def __init__(self, policy, lr=2.5e-4, eps=1e-5, max_grad_norm=0.5, train_encoder=True, betas=(0.9, 0.999)):
-        self.policy = policy
-        self.lr, self.eps, self.betas = float(lr), float(eps), tuple(betas)
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.train_encoder = bool(train_encoder)
-        self._frozen_backbone = False
-        self._from_features = False
-        ref = next(policy.parameters())
-        if ref.device.type != "cuda":
-            raise RuntimeError("BaselineTrainStep runs on an MI355X only: move the policy with .to('cuda') first "
-                               "(there is no CPU fallback)")
-        self.dev = ref.device
-        policy._ensure(self.dev)                                # handle + kernel operand buffers
-        self.store = FlatParams(list(policy.named_parameters()), self.dev, align=4)
-        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (self.store.flat, self.store.grad, self.store.exp_avg,
-                                                               self.store.exp_avg_sq)
-        self.offsets, self.n_params = self.store.offsets, self.store.n_params
-        enc = [self.offsets[n] for n, _ in self.store.named if n.startswith(ENCODER_PREFIX)]
-        self.encoder_range = (min(o for o, _ in enc), max(o + k for o, k in enc)) if enc else None      # None: a blind policy
-        torch.cuda.synchronize(self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_baseline_train_attach(policy._handle, _ptr(self.flat), _ptr(self.grad), self.flat.numel(),
-                                                           self.store.toc, len(self.store.named)))
-        self.step_count = 0
-        self._out3 = torch.zeros(3, device=self.dev, dtype=torch.float32)
-        self._norm = torch.zeros(1, device=self.dev, dtype=torch.float32)
-        policy._train_step = self                               # evaluate_actions delegates here; act reads the flat buffer
+    _abi = "pnvo_baseline_"
 
-    def _ranges(self):
-        end = max(o + k for o, k in self.offsets.values())
-        if self.train_encoder or self.encoder_range is None:
-            return [(0, end)]
-        lo, hi = self.encoder_range
-        return [(a, b) for a, b in ((0, lo), (hi, end)) if b > a]
+    def _attach(self):
+        return _lib.lib.pnvo_baseline_train_attach, 0
 
     def _repack(self):
         """The handle's kernel-layout operands from the flat buffer as it is now (one pass is all: nothing here lags a refresh)."""
@@ -318,47 +298,6 @@ class BaselineTrainStep(PolicyTrainStep):
                                                        int(N), _ptr(act), _ptr(hout), _ptr(value), _ptr(logp), _ptr(entropy),
                                                        self._stream()))
         return value, logp, entropy, hout
-
-    def ppo_loss(self, old_action_log_probs, adv_targ, value_preds, returns, clip_param, value_loss_coef, entropy_coef,
-                 use_clipped_value_loss=True):
-        f = lambda t: None if t is None else t.to(device=self.dev, dtype=torch.float32).contiguous().reshape(-1)
-        old, adv, vp, ret = f(old_action_log_probs), f(adv_targ), f(value_preds), f(returns)
-        with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_baseline_ppo_loss(self.policy._handle, _ptr(old), _ptr(adv), _ptr(vp), _ptr(ret), float(clip_param),
-                                                       float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
-                                                       _ptr(self._out3), self._stream()))
-        return self._out3
-
-    def backward(self):
-        """total_loss.backward(): fills self.grad (overwrites).  With train_encoder False the net.visual_encoder range stays exactly zero."""
-        with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_baseline_backward(self.policy._handle, int(self.train_encoder), self._stream()))
-
-    def clip_grad_norm(self):
-        if self.max_grad_norm is None:
-            return None
-        with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib.pnvo_baseline_clip_grad_norm(self.policy._handle, float(self.max_grad_norm), _ptr(self._norm),
-                                                             self._stream()))
-        return self._norm
-
-    def timing(self, on=True):
-        _lib.check(_lib.lib.pnvo_baseline_train_timing(self.policy._handle, int(bool(on))))
-
-    def phase_ms(self):
-        """Milliseconds of the last evaluate_actions / ppo_loss / backward (waits for the backward): encoder forward, GRU forward + heads,
-        loss, heads + BPTT + d embed, encoder backward (PolicyTrainStep's names)."""
-        ms = (C.c_double * 5)()
-        _lib.check(_lib.lib.pnvo_baseline_train_timing_read(self.policy._handle, ms))
-        return dict(zip(("encoder_forward", "lstm_forward", "loss", "bptt", "encoder_backward"), (float(v) for v in ms)))
-
-    def optimizer_step(self):
-        """Adam over the trainable ranges, then the handle's operands are re-laid from the flat buffer."""
-        self.step_count += 1
-        with torch.cuda.device(self.dev):
-            stream = self._stream()
-            self.store.adam_step(self._ranges(), self.lr, self.betas, self.eps, self.step_count, stream)
-            _lib.check(_lib.lib.pnvo_baseline_train_refresh(self.policy._handle, stream))
 
 
 class PPO(nn.Module):
