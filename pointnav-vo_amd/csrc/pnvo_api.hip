@@ -275,7 +275,7 @@ bool x3_layer(pnvo_handle m, const Layer &l) {
 bool x3_two_pieces(pnvo_handle m, const Layer &l) {
   if (m->bottleneck || !(l.in_bound < 6.0e4f)) return false;
   if (m->train != nullptr)             // a training step is attached: operands are rebuilt on the device from the flat parameters
-    return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l.name + ".weight") != nullptr;
+    return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l) != nullptr;
   return m->opt.pieces == 2;
 }
 // The implicit-GEMM geometry of layer l at B samples, the rest of the launch zero.
@@ -527,9 +527,9 @@ int x3_operand(pnvo_handle h, Layer &q, int pieces, hipStream_t s) {
   if (wpk && gen == h->weights_gen) return PNVO_OK;
   const size_t nel = (size_t)q.k * q.kw * q.cinp * q.coutp * pieces;
   if (!wpk) HIPCHK(h, wpk.alloc(nel));
-  const float *dev_w = h->train ? pnvo_train_weight_ptr(h, q.name + ".weight") : nullptr;
+  const float *dev_w = h->train ? pnvo_train_weight_ptr(h, q) : nullptr;
   if (dev_w != nullptr && pieces == 2) {
-    HIPCHK(h, launch_conv_x2_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pnvo_train_x2_scale(h, q.name + ".weight"), wpk, s));
+    HIPCHK(h, launch_conv_x2_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, pnvo_train_x2_scale(h, q), wpk, s));
   } else if (dev_w != nullptr) {
     HIPCHK(h, launch_conv_x3_repack(dev_w, q.cout, q.cin, q.cinp, q.coutp, q.k, q.kw, 0, wpk, s));
   } else {
@@ -571,7 +571,7 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, cons
     xa.ds_wpk = dm.wpk_x2;
     xa.ds_oscale = dm.x2_oscale;
     if (m->train != nullptr) {
-      const float *sp = pnvo_train_x2_scale(m, dm.name + ".weight");
+      const float *sp = pnvo_train_x2_scale(m, dm);
       xa.ds_oscale_ptr = sp ? sp + 1 : nullptr;
     }
     xa.ds_y = ride->y;
@@ -612,7 +612,7 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, cons
   xa.wpk = two ? lm.wpk_x2 : lm.wpk_x3;
   xa.oscale = lm.x2_oscale;
   if (two && m->train != nullptr) {
-    const float *sp = pnvo_train_x2_scale(m, l.name + ".weight");
+    const float *sp = pnvo_train_x2_scale(m, l);
     xa.oscale_ptr = sp ? sp + 1 : nullptr;
   }
   xa.y = r.y;
@@ -1957,7 +1957,7 @@ int run_fc_head(pnvo_handle m, int B, const float *comp_raw, const float *sc, co
   // the output head rides on the hidden layer's split-K reduction when there is one (option head_fuse); with a training step attached
   // the head's weight is read where the optimiser keeps it (the flat parameter buffer), the bias from its re-packed copy
   bool head_rode = false;
-  const float *head_w = m->train != nullptr ? pnvo_train_weight_ptr(m, "output_head.1.weight") : m->head_w_plain;   // (OIHW of a 1x1 conv = [out_dim][hidden])
+  const float *head_w = m->train != nullptr ? pnvo_train_weight_ptr(m, m->head) : m->head_w_plain;   // (OIHW of a 1x1 conv = [out_dim][hidden])
   float *head_out = (m->opt.head_fuse && !r.features_only && c.out_dim <= 4 && head_w != nullptr) ? out : nullptr;
   if ((rc = pnvo_run_conv(m, m->fc, B, {.x = comp_raw, .in_scale = sc, .in_shift = sh, .y = m->hid, .y_cstride = c.hidden, .bias = m->fc_bias,
                                         .bias_row = c.act_embed ? r.actions : nullptr, .relu_out = 1, .head_w = head_w, .head_out = head_out,

@@ -344,14 +344,14 @@ int pnvo_launch_stem_mx(pnvo_handle m, const pnvo::StemMXArgs &a, int pieces, in
 int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
-const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name);   // pnvo_train_api.hip: device pointer or nullptr
+const float *pnvo_train_weight_ptr(pnvo_handle m, const Layer &l);   // pnvo_train_api.hip: l's weight in the flat parameter buffer (a conv of m, m->fc, m->head), or nullptr
 // pnvo_api.hip: the forward up to the compression conv's raw NHWC output (m->comp_raw, channel-padded to m->comp_cp) and its per-sample
 // GroupNorm scale / shift (m->ssC), on the per-layer kernels at every batch size (the persistent small-batch kernel is not entered)
 int pnvo_forward_compression(pnvo_handle m, const float *depth, int B, void *stream);
 const float *pnvo_train_hidden(pnvo_handle m);   // pnvo_train_api.hip: [B, hidden] output of visual_fc of the last train-mode forward, or nullptr
 int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream);   // the backward entered below the output head
 void pnvo_chain_in_bounds(pnvo_handle h, const std::function<float(const Layer &)> &gn_bound);   // pnvo_api.hip
-const float *pnvo_train_x2_scale(pnvo_handle m, const std::string &name);     // device {scale, 1/scale} of that conv weight's float16 pieces, or nullptr
+const float *pnvo_train_x2_scale(pnvo_handle m, const Layer &l);     // device {scale, 1/scale} of conv l's float16 pieces, or nullptr
 void pnvo_bf16_free(pnvo_handle m);    // pnvo_bf16.hip
 bool pnvo_small_usable(pnvo_handle m, int B);   // smallnet.hip: does this call shape take the persistent kernel?
 int pnvo_small_forward(pnvo_handle m, int B, const FwdRequest &r, int stem_slots);   // stem_slots: as pnvo_run_stem left them in m->stats

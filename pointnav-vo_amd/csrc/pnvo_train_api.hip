@@ -5,10 +5,14 @@
 // (/root/reference/pointnav_vo/vo/engine/vo_cnn_regression_geo_invariance_engine.py:855-901, :586; loss
 //  vo_cnn_engine.py:135-198; Adam :122-133).  The flat parameter / gradient buffers are caller-owned device memory in
 // the reference's state_dict parameter order, so the data-parallel all-reduce is ONE collective on one buffer.
+//
+// pnvo_train_attach resolves every parameter name to its flat offset ONCE (TrainLayer, TrainLinear) and builds every table that
+// never changes afterwards; the refresh, the forward and the backward only read those records and launch.
 #include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 
 #include "pnvo_model.h"
 
@@ -27,57 +31,81 @@ struct ConvSave {
   DevBuf<float> mu, rstd;
 };
 
+// the caller's parameter table by name: a local of pnvo_train_attach (run-time code reads the records below)
 struct TocEnt {
   size_t off;
   std::vector<int64_t> shape;
   size_t numel;
 };
+using Toc = std::map<std::string, TocEnt>;
+
+struct Param {                // a parameter inside the flat buffers
+  size_t off = 0, numel = 0;
+};
+struct Weight : Param {
+  std::string t_wgrad;        // its timing entry: "wgrad:<name>"
+};
+
+// What pnvo_train_attach bound for conv li of m->convs.
+struct TrainLayer {
+  Weight w;
+  Param gamma, beta;          // the GroupNorm behind it
+  int x2_row = -1;            // row of TrainState::x2_scale, or -1 (stem, Bottleneck models)
+  std::string t_dgrad;        // timing entry "dgrad:<name>"
+  // backward-data operands (none for the stem: no input gradient)
+  DevBuf<float> dgrad_w;                       // flipped / transposed weights, re-packed by the gather of every refresh
+  std::array<DevBuf<float>, 4> dgrad_wph;      // stride-2 3x3 convs: one sub-kernel per output parity phase (ph*2 + pw)
+  DevBuf<unsigned short> dgrad_x[2];           // 3x3 stride-1 convs on conv_x3.hip: [0] two float16 pieces (option train_pieces = 2),
+  unsigned long long dgrad_x_gen[2] = {0, 0};  //   [1] three bf16 pieces; built from the flat parameters when m->weights_gen moved
+};
+struct TrainLinear {
+  Weight w;
+  Param b;
+};
+
+// everything sized for TrainState::capB: saved activations of the last forward and the backward's scratch
+struct TrainWs {
+  std::vector<ConvSave> cs;
+  std::vector<DevBuf<float>> y;     // y[0] = pooled stem output, y[k] = output of residual block k
+  DevBuf<unsigned char> pool_idx;
+  DevBuf<float> hid;
+  DevBuf<float> dYa, dYb, G, dRaw, dA, dStem;
+  DevBuf<float> dout8, dh, gh, dz;
+  DevBuf<float> gn_part, gn_coef, wg_partial;
+  DevBuf<double> mom_part;
+  DevBuf<float> zdrop, hdrop, dmask;          // dropped activations of the last forward
+  DevBuf<float> egath, efeat, biasB, dfeat;   // action embedding: gathered rows, dropped rows, per-sample bias rows, gradient
+  DevBuf<int64_t> iota;
+};
 
 struct TrainState {
   float *params = nullptr, *grads = nullptr;   // the caller's flat buffers (not owned)
   size_t n = 0;
-  std::map<std::string, TocEnt> toc;
+  std::vector<TrainLayer> conv;     // index-aligned with m->convs
+  TrainLinear fc, head;
+  size_t emb_off = 0;               // action_embedding.weight (act_embed models)
+  long w1_pitch = 0;                // columns of the hidden layer's weight: flat (+ 32 embedding columns)
+  size_t stem_w_off = 0;            // offset of the OIHW stem weight in the flat parameter buffer
   std::vector<PackMap> maps;
-  std::vector<DevBuf<float>> dgrad_w;     // per conv of m->convs (nullptr for the stem: no input gradient)
-  std::vector<std::array<DevBuf<float>, 4>> dgrad_wph;   // stride-2 3x3 convs: one sub-kernel per output parity phase (ph*2 + pw)
-  std::vector<DevBuf<unsigned short>> dgrad_x3;          // 3x3 stride-1 convs: three-piece operand of the backward-data conv (conv_x3.hip)
-  std::vector<unsigned long long> dgrad_x3_gen;    //   ... built from the flat parameters when m->weights_gen moved
-  std::vector<DevBuf<unsigned short>> dgrad_x2;          //   ... and its two-piece float16 form (option train_pieces = 2)
-  std::vector<unsigned long long> dgrad_x2_gen;
-  DevBuf<unsigned> dmax;                           // per conv: float bits of max |dRaw| of the backward in flight (gn_bwd_apply)
+  DevBuf<unsigned> dmax;            // per conv: float bits of max |dRaw| of the backward in flight (gn_bwd_apply)
   DevBuf<float> fc_t, head_t;
   DevBuf<int> d_ref_of_new, d_tensor_of_new, d_ciperm;
-  DevBuf<GatherSeg> d_segs;         // all re-pack maps as one segment table (pnvo_train_refresh)
+  DevBuf<GatherSeg> d_segs;         // all re-pack maps as one segment table
   long seg_total = 0;
   int nseg = 0;
   DevBuf<int> d_mxmaps;             // mx stem: [slot_ref 32 | slot_new 32 | xslot 4]
   DevBuf<int> d_ddmaps;             // one-hot stem: [dense_ref 12 | dense_new 12 | dd_ref 2*bins | dd_new 2*bins]
   int dd_nd = 0;
-  size_t stem_w_off = 0;            // offset of the OIHW stem weight in the flat parameter buffer
-  // saved activations (sized for capB)
   int capB = 0;
   int lastB = 0;
-  std::vector<ConvSave> cs;
-  std::vector<DevBuf<float>> y;     // y[0] = pooled stem output, y[k] = output of residual block k
-  DevBuf<unsigned char> pool_idx;
-  DevBuf<float> hid;
+  TrainWs ws;
   const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // observation tensors of the last forward
-  // scratch
-  DevBuf<float> dYa, dYb, G, dRaw, dA, dStem;
-  DevBuf<float> dout8, dh, gh, dz;
-  DevBuf<float> gn_part, gn_coef, wg_partial;
-  DevBuf<double> mom_part;
-  // dropout (pnvo_train_set_dropout): p, seed, forward counter; dropped activations of the last forward
+  // dropout (pnvo_train_set_dropout): p, seed, forward counter
   float drop_p = 0.f;
   uint64_t drop_seed = 0, drop_step = 0;
-  DevBuf<float> zdrop, hdrop, dmask;
   // action-embedding variants: the Linear's 32 embedding columns as per-sample bias rows (train_kernels.hip embed_*)
   const long long *actions = nullptr;   // device [B], set by pnvo_train_set_actions for the next forward/backward
-  DevBuf<float> egath, efeat, biasB, dfeat;
-  DevBuf<int64_t> iota;
   DevBuf<int> embed_err;                // host-mapped flag: action outside the embedding table
-  size_t w1_off = 0, b1_off = 0, emb_off = 0;
-  long w1_pitch = 0;
   // gradient-ready hook (pnvo_train_set_grad_hook): the backward reports flat ranges [first, first + count) whose gradients
   // are final while the rest of it is still being enqueued; bucket_first = lower bounds of the ranges, latest layers first
   pnvo_grad_ready_fn hook = nullptr;
@@ -86,7 +114,7 @@ struct TrainState {
   std::vector<char> bucket_done;        // per backward: which ranges have been reported (the end of the backward reports the rest)
   // two-piece float16 operands of the training forward's convs: per conv weight {scale, 1/scale}, recomputed from the flat
   // parameters by ONE launch per pnvo_train_refresh (conv_x3.hip conv_x2_scale_kernel)
-  std::map<std::string, int> x2_index;  // conv weight name -> row of x2_scale
+  int x2_rows = 0;
   DevBuf<long> x2_seg;                  // [rows][2]: flat offset, element count
   DevBuf<float> x2_scale;               // [rows][2]
   // GroupNorm bounds behind Layer::in_bound (the range guard of the float16 pieces), tracked while gamma / beta move: one small
@@ -101,6 +129,16 @@ struct TrainState {
 };
 
 TrainState *TS(pnvo_handle m) { return reinterpret_cast<TrainState *>(m->train); }
+
+const std::string T_GN_BWD = "gn_bwd";
+
+// index of l in m->convs, or -1 (m->fc, m->head, a layer of another handle)
+long conv_index(pnvo_handle m, const Layer &l) {
+  const Layer *first = m->convs.data();
+  return std::less_equal<const Layer *>()(first, &l) && std::less<const Layer *>()(&l, first + m->convs.size()) ? &l - first : -1;
+}
+
+// ---- pnvo_train_attach: names -> records, re-pack maps, tables ------------------------------------------------------------
 
 // float "index tensor" of a parameter: value = flat offset + 1 (exact in fp32 below 2^24 elements)
 std::vector<float> index_tensor(const TocEnt &e) {
@@ -119,9 +157,9 @@ int add_map(pnvo_handle m, TrainState *t, float *dst, const std::vector<float> &
   return PNVO_OK;
 }
 
-const TocEnt *need(pnvo_handle m, TrainState *t, const std::string &name, int *rc) {
-  auto it = t->toc.find(name);
-  if (it == t->toc.end()) {
+const TocEnt *need(pnvo_handle m, const Toc &toc, const std::string &name, int *rc) {
+  auto it = toc.find(name);
+  if (it == toc.end()) {
     *rc = pnvo_fail(m, PNVO_ERR_WEIGHTS, "parameter table is missing '" + name + "'");
     return nullptr;
   }
@@ -139,140 +177,151 @@ std::vector<float> transpose_flip(const std::vector<float> &w, int cout, int cin
   return o;
 }
 
-int build_maps(pnvo_handle m, TrainState *t) {
+// the stem's forward operands: channel order of the fused gather (pnvo_load_weights does the same permutation)
+int map_stem_weight(pnvo_handle m, TrainState *t, const std::vector<float> &idx) {
+  const Layer &l = m->convs[0];
+  const int T = l.k * l.kw;
   int rc = PNVO_OK;
-  const pnvo_config &c = m->cfg;
-  t->dgrad_w.resize(m->convs.size());
-  t->dgrad_wph.resize(m->convs.size());
-  t->dgrad_x3.resize(m->convs.size());
-  t->dgrad_x3_gen.assign(m->convs.size(), 0);
-  t->dgrad_x2.resize(m->convs.size());
-  t->dgrad_x2_gen.assign(m->convs.size(), 0);
-  for (size_t li = 0; li < m->convs.size(); ++li) {
-    Layer &l = m->convs[li];
-    const TocEnt *w = need(m, t, l.name + ".weight", &rc);
-    if (!w) return rc;
-    const std::vector<float> idx = index_tensor(*w);
-    const int T = l.k * l.kw;
-    std::vector<float> pk;
-    if (li == 0) {   // stem: channel order of the fused gather (pnvo_load_weights does the same permutation)
-      std::vector<float> wp((size_t)l.cout * m->CP * T, 0.f);
-      for (int nc = 0; nc < m->CP; ++nc) {
-        const int r = m->stem_ref_of_new[nc];
-        if (r < 0) continue;
-        for (int o = 0; o < l.cout; ++o)
-          std::memcpy(&wp[((size_t)o * m->CP + nc) * T], &idx[((size_t)o * l.cin + r) * T], sizeof(float) * T);
-      }
-      pnvo_pack_conv_weight_cinp(wp.data(), l.cout, m->CP, m->CP, l.k, l.kw, pk);
-      if ((rc = add_map(m, t, l.wpk, pk)) != PNVO_OK) return rc;
-      std::vector<float> pk16((size_t)49 * m->CPL * l.cout);
-      pack_stem_weight(wp.data(), l.cout, m->CP, m->CPL, pk16.data());
-      if ((rc = add_map(m, t, m->stem_wpk16, pk16)) != PNVO_OK) return rc;
-    } else {
-      pnvo_pack_conv_weight_cinp(idx.data(), l.cout, l.cin, l.cinp, l.k, l.kw, pk);
-      if ((rc = add_map(m, t, l.wpk, pk)) != PNVO_OK) return rc;
-      // backward-data operand: "conv" with CIN' = coutp (gradient channels), COUT' = cin
-      const std::vector<float> wt = transpose_flip(idx, l.cout, l.cin, l.k, l.kw);
-      std::vector<float> pkt;
-      pnvo_pack_conv_weight_cinp(wt.data(), l.cin, l.cout, l.coutp, l.k, l.kw, pkt);
-      HIPCHK(m, t->dgrad_w[li].alloc(pkt.size()));
-      if ((rc = add_map(m, t, t->dgrad_w[li], pkt)) != PNVO_OK) return rc;
-      if (l.stride == 2 && l.k == 3 && l.kw == 3 && l.pad == 1) {
-        // dX[2i+ph] = sum over the taps whose source row (2i+ph-1+kh)/2 is an integer: kh = 1 (ph = 0) or kh = 0, 2
-        // (ph = 1), reading dY rows i, or i and i+1 — a 1- or 2-tap stride-1 conv per parity phase, no masked taps
-        for (int ph = 0; ph < 2; ++ph)
-          for (int pw = 0; pw < 2; ++pw) {
-            const int th[2] = {ph ? 0 : 1, 2}, tw[2] = {pw ? 0 : 1, 2};
-            const int nh = ph ? 2 : 1, nw = pw ? 2 : 1;
-            std::vector<float> sub((size_t)l.cin * l.cout * nh * nw);
-            for (int ci = 0; ci < l.cin; ++ci)
-              for (int co = 0; co < l.cout; ++co)
-                for (int a = 0; a < nh; ++a)
-                  for (int b = 0; b < nw; ++b)
-                    sub[(((size_t)ci * l.cout + co) * nh + a) * nw + b] = wt[(((size_t)ci * l.cout + co) * 3 + th[a]) * 3 + tw[b]];
-            std::vector<float> pks;
-            pnvo_pack_conv_weight_cinp(sub.data(), l.cin, l.cout, l.coutp, nh, nw, pks);
-            DevBuf<float> &dst = t->dgrad_wph[li][ph * 2 + pw];
-            HIPCHK(m, dst.alloc(pks.size()));
-            if ((rc = add_map(m, t, dst, pks)) != PNVO_OK) return rc;
-          }
-      }
+  std::vector<float> wp((size_t)l.cout * m->CP * T, 0.f), pk;
+  for (int nc = 0; nc < m->CP; ++nc) {
+    const int r = m->stem_ref_of_new[nc];
+    if (r < 0) continue;
+    for (int o = 0; o < l.cout; ++o)
+      std::memcpy(&wp[((size_t)o * m->CP + nc) * T], &idx[((size_t)o * l.cin + r) * T], sizeof(float) * T);
+  }
+  pnvo_pack_conv_weight_cinp(wp.data(), l.cout, m->CP, m->CP, l.k, l.kw, pk);
+  if ((rc = add_map(m, t, l.wpk, pk)) != PNVO_OK) return rc;
+  std::vector<float> pk16((size_t)49 * m->CPL * l.cout);
+  pack_stem_weight(wp.data(), l.cout, m->CP, m->CPL, pk16.data());
+  return add_map(m, t, m->stem_wpk16, pk16);
+}
+
+// conv li's forward operand and its backward-data operands: "conv" with CIN' = coutp (gradient channels), COUT' = cin
+int map_conv_weight(pnvo_handle m, TrainState *t, size_t li, const std::vector<float> &idx) {
+  const Layer &l = m->convs[li];
+  TrainLayer &tl = t->conv[li];
+  int rc = PNVO_OK;
+  std::vector<float> pk;
+  pnvo_pack_conv_weight_cinp(idx.data(), l.cout, l.cin, l.cinp, l.k, l.kw, pk);
+  if ((rc = add_map(m, t, l.wpk, pk)) != PNVO_OK) return rc;
+  const std::vector<float> wt = transpose_flip(idx, l.cout, l.cin, l.k, l.kw);
+  pnvo_pack_conv_weight_cinp(wt.data(), l.cin, l.cout, l.coutp, l.k, l.kw, pk);
+  HIPCHK(m, tl.dgrad_w.alloc(pk.size()));
+  if ((rc = add_map(m, t, tl.dgrad_w, pk)) != PNVO_OK) return rc;
+  if (!(l.stride == 2 && l.k == 3 && l.kw == 3 && l.pad == 1)) return PNVO_OK;
+  // dX[2i+ph] = sum over the taps whose source row (2i+ph-1+kh)/2 is an integer: kh = 1 (ph = 0) or kh = 0, 2
+  // (ph = 1), reading dY rows i, or i and i+1 — a 1- or 2-tap stride-1 conv per parity phase, no masked taps
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      const int th[2] = {ph ? 0 : 1, 2}, tw[2] = {pw ? 0 : 1, 2};
+      const int nh = ph ? 2 : 1, nw = pw ? 2 : 1;
+      std::vector<float> sub((size_t)l.cin * l.cout * nh * nw);
+      for (int ci = 0; ci < l.cin; ++ci)
+        for (int co = 0; co < l.cout; ++co)
+          for (int a = 0; a < nh; ++a)
+            for (int b = 0; b < nw; ++b)
+              sub[(((size_t)ci * l.cout + co) * nh + a) * nw + b] = wt[(((size_t)ci * l.cout + co) * 3 + th[a]) * 3 + tw[b]];
+      pnvo_pack_conv_weight_cinp(sub.data(), l.cin, l.cout, l.coutp, nh, nw, pk);
+      DevBuf<float> &dst = tl.dgrad_wph[ph * 2 + pw];
+      HIPCHK(m, dst.alloc(pk.size()));
+      if ((rc = add_map(m, t, dst, pk)) != PNVO_OK) return rc;
     }
-    const TocEnt *g = need(m, t, l.gn + ".weight", &rc);
+  return PNVO_OK;
+}
+
+int bind_convs(pnvo_handle m, TrainState *t, const Toc &toc) {
+  int rc = PNVO_OK;
+  t->conv.resize(m->convs.size());
+  for (size_t li = 0; li < m->convs.size(); ++li) {
+    const Layer &l = m->convs[li];
+    TrainLayer &tl = t->conv[li];
+    const TocEnt *w = need(m, toc, l.name + ".weight", &rc);
+    if (!w) return rc;
+    tl.w.off = w->off;
+    tl.w.numel = w->numel;
+    tl.w.t_wgrad = "wgrad:" + l.name + ".weight";
+    tl.t_dgrad = "dgrad:" + l.name;
+    if (li == 0) t->stem_w_off = w->off;
+    if ((rc = li == 0 ? map_stem_weight(m, t, index_tensor(*w)) : map_conv_weight(m, t, li, index_tensor(*w))) != PNVO_OK) return rc;
+    const TocEnt *g = need(m, toc, l.gn + ".weight", &rc);
     if (!g) return rc;
-    const TocEnt *b = need(m, t, l.gn + ".bias", &rc);
+    const TocEnt *b = need(m, toc, l.gn + ".bias", &rc);
     if (!b) return rc;
+    tl.gamma = Param{g->off, g->numel};
+    tl.beta = Param{b->off, b->numel};
     if ((rc = add_map(m, t, l.gamma, index_tensor(*g))) != PNVO_OK) return rc;
     if ((rc = add_map(m, t, l.beta, index_tensor(*b))) != PNVO_OK) return rc;
   }
-  // linear layers
+  return PNVO_OK;
+}
+
+int bind_linears(pnvo_handle m, TrainState *t, const Toc &toc) {
+  int rc = PNVO_OK;
+  const pnvo_config &c = m->cfg;
   const int T = m->fh * m->fw, flat = m->comp_c * T;
-  const TocEnt *w1 = need(m, t, m->fc.name + ".weight", &rc);
+  const TocEnt *w1 = need(m, toc, m->fc.name + ".weight", &rc);
   if (!w1) return rc;
-  const TocEnt *b1 = need(m, t, m->fc.name + ".bias", &rc);
+  const TocEnt *b1 = need(m, toc, m->fc.name + ".bias", &rc);
   if (!b1) return rc;
-  const TocEnt *w2 = need(m, t, "output_head.1.weight", &rc);
+  const TocEnt *w2 = need(m, toc, m->head.name + ".weight", &rc);
   if (!w2) return rc;
-  const TocEnt *b2 = need(m, t, "output_head.1.bias", &rc);
+  const TocEnt *b2 = need(m, toc, m->head.name + ".bias", &rc);
   if (!b2) return rc;
   const int fc_in = flat + (c.act_embed ? 32 : 0);
   if ((int)w1->shape[1] != fc_in) return pnvo_fail(m, PNVO_ERR_ARG, m->fc.name + ".weight has the wrong number of columns");
-  t->w1_off = w1->off;
+  t->fc = TrainLinear{{{w1->off, w1->numel}, "wgrad:" + m->fc.name + ".weight"}, {b1->off, b1->numel}};
+  t->head = TrainLinear{{{w2->off, w2->numel}, "wgrad:" + m->head.name + ".weight"}, {b2->off, b2->numel}};
   t->w1_pitch = fc_in;
-  t->b1_off = b1->off;
   if (c.act_embed) {
-    const TocEnt *emb = need(m, t, "action_embedding.weight", &rc);
+    const TocEnt *emb = need(m, toc, "action_embedding.weight", &rc);
     if (!emb) return rc;
     if (emb->shape.size() != 2 || emb->shape[0] != c.n_acts + 1 || emb->shape[1] != 32)
       return pnvo_fail(m, PNVO_ERR_ARG, "action_embedding.weight must be [n_acts + 1, 32]");
     t->emb_off = emb->off;
-    if (!t->embed_err) HIPCHK(m, t->embed_err.alloc_host(1, hipHostMallocMapped));
+    HIPCHK(m, t->embed_err.alloc_host(1, hipHostMallocMapped));
     *t->embed_err = 0;
   }
-  {
-    const std::vector<float> i1full = index_tensor(*w1), i2 = index_tensor(*w2);
-    std::vector<float> i1((size_t)c.hidden * flat);          // the visual columns
-    for (int o = 0; o < c.hidden; ++o)
-      std::memcpy(&i1[(size_t)o * flat], &i1full[(size_t)o * fc_in], sizeof(float) * (size_t)flat);
-    std::vector<float> pk;
-    pnvo_pack_conv_weight_cinp(i1.data(), c.hidden, m->comp_c, m->comp_cp, m->fh, m->fw, pk);
-    if ((rc = add_map(m, t, m->fc.wpk, pk)) != PNVO_OK) return rc;
-    if (!c.act_embed)        // act-embed: the per-action bias rows are rebuilt by refresh_embed_bias
-      if ((rc = add_map(m, t, m->fc_bias, index_tensor(*b1))) != PNVO_OK) return rc;
-    pnvo_pack_conv_weight_cinp(i2.data(), c.out_dim, c.hidden, c.hidden, 1, 1, pk);
-    if ((rc = add_map(m, t, m->head.wpk, pk)) != PNVO_OK) return rc;
-    if ((rc = add_map(m, t, m->head_bias, index_tensor(*b2))) != PNVO_OK) return rc;
-    // dz = g_h . W1 as a 1x1 conv: CIN' = hidden, COUT' = T*comp_cp, W'[tap*comp_cp + ch][o] = W1[o][ch*T + tap]
-    std::vector<float> wt((size_t)T * m->comp_cp * c.hidden, 0.f);
-    for (int o = 0; o < c.hidden; ++o)
-      for (int ch = 0; ch < m->comp_c; ++ch)
-        for (int tap = 0; tap < T; ++tap)
-          wt[((size_t)tap * m->comp_cp + ch) * c.hidden + o] = i1[(size_t)o * flat + (size_t)ch * T + tap];
-    pnvo_pack_conv_weight_cinp(wt.data(), T * m->comp_cp, c.hidden, c.hidden, 1, 1, pk);
-    HIPCHK(m, t->fc_t.alloc(pk.size()));
-    if ((rc = add_map(m, t, t->fc_t, pk)) != PNVO_OK) return rc;
-    // dh = dOut . W2: CIN' = 8 (out_dim padded), COUT' = hidden, W'[o][d] = W2[d][o]
-    std::vector<float> ht((size_t)c.hidden * c.out_dim);
-    for (int o = 0; o < c.hidden; ++o)
-      for (int d = 0; d < c.out_dim; ++d) ht[(size_t)o * c.out_dim + d] = i2[(size_t)d * c.hidden + o];
-    pnvo_pack_conv_weight_cinp(ht.data(), c.hidden, c.out_dim, rup(c.out_dim, 8), 1, 1, pk);
-    HIPCHK(m, t->head_t.alloc(pk.size()));
-    if ((rc = add_map(m, t, t->head_t, pk)) != PNVO_OK) return rc;
-  }
-  // stem channel tables on device
-  std::vector<int> ron(m->CPL, -1), ton(m->CPL, -1);
+  const std::vector<float> i1full = index_tensor(*w1), i2 = index_tensor(*w2);
+  std::vector<float> i1((size_t)c.hidden * flat);          // the visual columns
+  for (int o = 0; o < c.hidden; ++o)
+    std::memcpy(&i1[(size_t)o * flat], &i1full[(size_t)o * fc_in], sizeof(float) * (size_t)flat);
+  std::vector<float> pk;
+  pnvo_pack_conv_weight_cinp(i1.data(), c.hidden, m->comp_c, m->comp_cp, m->fh, m->fw, pk);
+  if ((rc = add_map(m, t, m->fc.wpk, pk)) != PNVO_OK) return rc;
+  if (!c.act_embed)        // act-embed: the per-action bias rows are rebuilt by pnvo_train_refresh
+    if ((rc = add_map(m, t, m->fc_bias, index_tensor(*b1))) != PNVO_OK) return rc;
+  pnvo_pack_conv_weight_cinp(i2.data(), c.out_dim, c.hidden, c.hidden, 1, 1, pk);
+  if ((rc = add_map(m, t, m->head.wpk, pk)) != PNVO_OK) return rc;
+  if ((rc = add_map(m, t, m->head_bias, index_tensor(*b2))) != PNVO_OK) return rc;
+  // dz = g_h . W1 as a 1x1 conv: CIN' = hidden, COUT' = T*comp_cp, W'[tap*comp_cp + ch][o] = W1[o][ch*T + tap]
+  std::vector<float> wt((size_t)T * m->comp_cp * c.hidden, 0.f);
+  for (int o = 0; o < c.hidden; ++o)
+    for (int ch = 0; ch < m->comp_c; ++ch)
+      for (int tap = 0; tap < T; ++tap)
+        wt[((size_t)tap * m->comp_cp + ch) * c.hidden + o] = i1[(size_t)o * flat + (size_t)ch * T + tap];
+  pnvo_pack_conv_weight_cinp(wt.data(), T * m->comp_cp, c.hidden, c.hidden, 1, 1, pk);
+  HIPCHK(m, t->fc_t.alloc(pk.size()));
+  if ((rc = add_map(m, t, t->fc_t, pk)) != PNVO_OK) return rc;
+  // dh = dOut . W2: CIN' = 8 (out_dim padded), COUT' = hidden, W'[o][d] = W2[d][o]
+  std::vector<float> ht((size_t)c.hidden * c.out_dim);
+  for (int o = 0; o < c.hidden; ++o)
+    for (int d = 0; d < c.out_dim; ++d) ht[(size_t)o * c.out_dim + d] = i2[(size_t)d * c.hidden + o];
+  pnvo_pack_conv_weight_cinp(ht.data(), c.hidden, c.out_dim, rup(c.out_dim, 8), 1, 1, pk);
+  HIPCHK(m, t->head_t.alloc(pk.size()));
+  return add_map(m, t, t->head_t, pk);
+}
+
+// stem channel tables on the device, and the maps of the device-side stem re-packs
+int build_stem_tables(pnvo_handle m, TrainState *t) {
+  std::vector<int> ron(m->CPL, -1), ton(m->CPL, -1), perm(32, -1);
   for (int k = 0; k < m->CP; ++k) {
     ron[k] = m->stem_ref_of_new[k];
     ton[k] = m->stem_tensor_of_new[k];
+    if (k < 32) perm[k] = m->stem_ref_of_new[k];
   }
-  HIPCHK(m, t->d_ref_of_new.alloc(m->CPL));
-  HIPCHK(m, t->d_tensor_of_new.alloc(m->CPL));
-  HIPCHK(m, t->d_ciperm.alloc(32));
-  std::vector<int> perm(32, -1);
-  for (int k = 0; k < m->CP && k < 32; ++k) perm[k] = m->stem_ref_of_new[k];
-  HIPCHK(m, hipMemcpy(t->d_ref_of_new, ron.data(), m->CPL * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(m, hipMemcpy(t->d_tensor_of_new, ton.data(), m->CPL * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(m, hipMemcpy(t->d_ciperm, perm.data(), 32 * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(m, t->d_ref_of_new.upload(ron.data(), ron.size()));
+  HIPCHK(m, t->d_tensor_of_new.upload(ton.data(), ton.size()));
+  HIPCHK(m, t->d_ciperm.upload(perm.data(), perm.size()));
   m->train_mx = false;
   if (m->mx_ok && m->convs[0].cout == 32 && m->mx_slot_ref.size() == 32) {   // stem on the bf16 matrix cores: device-side repack
     std::vector<int> mp(68, -1);
@@ -281,41 +330,379 @@ int build_maps(pnvo_handle m, TrainState *t) {
       mp[32 + k] = m->mx_slot_new[k];
     }
     for (int x = 0; x < 4; ++x) mp[64 + x] = m->mx_xslot[x];
-    HIPCHK(m, t->d_mxmaps.alloc(mp.size()));
-    HIPCHK(m, hipMemcpy(t->d_mxmaps, mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
-    auto it = t->toc.find(m->convs[0].name + ".weight");
-    if (it == t->toc.end()) return pnvo_fail(m, PNVO_ERR_WEIGHTS, "stem weight missing from the parameter table");
-    t->stem_w_off = it->second.off;
+    HIPCHK(m, t->d_mxmaps.upload(mp.data(), mp.size()));
     m->train_mx = true;
   }
-  if (m->dd_ok) {                  // the one-hot-aware stem's operands are rebuilt on the device after every step
-    const int bins = m->dd_bins;
-    std::vector<int> mp(24 + 4 * bins, -1);
-    auto find_new = [&](int tensor, int ch) {
-      for (int nc = 0; nc < m->CP; ++nc)
-        if (m->stem_tensor_of_new[nc] == tensor && m->stem_ch_of_new[nc] == ch && m->stem_ref_of_new[nc] >= 0) return nc;
-      return -1;
-    };
-    int nd = 0;
-    for (int d = 0; d < 12; ++d) {
-      if (m->dd_dense_tensor[d] < 0) continue;
-      const int nc = find_new(m->dd_dense_tensor[d], m->dd_dense_ch[d]);
-      mp[d] = m->stem_ref_of_new[nc];
-      mp[12 + d] = nc;
-      nd = d + 1;
-    }
-    for (int k = 0; k < 2 * bins; ++k) {
-      const int nc = find_new(2, k);
-      mp[24 + k] = m->stem_ref_of_new[nc];
-      mp[24 + 2 * bins + k] = nc;
-    }
-    t->dd_nd = nd;
-    HIPCHK(m, t->d_ddmaps.alloc(mp.size()));
-    HIPCHK(m, hipMemcpy(t->d_ddmaps, mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice));
-    auto it = t->toc.find(m->convs[0].name + ".weight");
-    if (it == t->toc.end()) return pnvo_fail(m, PNVO_ERR_WEIGHTS, "stem weight missing from the parameter table");
-    t->stem_w_off = it->second.off;
+  if (!m->dd_ok) return PNVO_OK;
+  // the one-hot-aware stem's operands are rebuilt on the device after every step
+  const int bins = m->dd_bins;
+  std::vector<int> mp(24 + 4 * bins, -1);
+  auto find_new = [&](int tensor, int ch) {
+    for (int nc = 0; nc < m->CP; ++nc)
+      if (m->stem_tensor_of_new[nc] == tensor && m->stem_ch_of_new[nc] == ch && m->stem_ref_of_new[nc] >= 0) return nc;
+    return -1;
+  };
+  for (int d = 0; d < 12; ++d) {
+    if (m->dd_dense_tensor[d] < 0) continue;
+    const int nc = find_new(m->dd_dense_tensor[d], m->dd_dense_ch[d]);
+    mp[d] = m->stem_ref_of_new[nc];
+    mp[12 + d] = nc;
+    t->dd_nd = d + 1;
   }
+  for (int k = 0; k < 2 * bins; ++k) {
+    const int nc = find_new(2, k);
+    mp[24 + k] = m->stem_ref_of_new[nc];
+    mp[24 + 2 * bins + k] = nc;
+  }
+  HIPCHK(m, t->d_ddmaps.upload(mp.data(), mp.size()));
+  return PNVO_OK;
+}
+
+// What pnvo_train_refresh launches over: the segment table of all re-pack maps, one float16 scale row per 3x3 / strided conv
+// conv_x3.hip may take, and the GroupNorm-bound segments with their host-mapped ring.  The maps never change after attach.
+int build_refresh_tables(pnvo_handle m, TrainState *t) {
+  std::vector<GatherSeg> segs;
+  for (const PackMap &pm : t->maps) {
+    segs.push_back(GatherSeg{pm.map, pm.dst, t->seg_total});
+    t->seg_total += (long)pm.map.size();
+  }
+  t->nseg = (int)segs.size();
+  HIPCHK(m, t->d_segs.upload(segs.data(), segs.size()));
+  if (m->bottleneck) return PNVO_OK;
+  std::vector<long> x2;
+  std::vector<TrainState::GnbSeg> gnb(m->convs.size(), TrainState::GnbSeg{0, 0, 0, 0.f});
+  for (size_t li = 0; li < m->convs.size(); ++li) {
+    const Layer &l = m->convs[li];
+    TrainLayer &tl = t->conv[li];
+    if (li >= 1) {
+      tl.x2_row = t->x2_rows++;
+      x2.push_back((long)tl.w.off);
+      x2.push_back((long)tl.w.numel);
+    }
+    if (l.groups > 0)
+      gnb[li] = TrainState::GnbSeg{(long)tl.gamma.off, (long)tl.beta.off, l.cout, (float)std::sqrt((double)(l.cout / l.groups) * l.hout * l.wout)};
+  }
+  if (!x2.empty()) {
+    HIPCHK(m, t->x2_seg.upload(x2.data(), x2.size()));
+    // {scale, 1/scale} per conv + the integer maxima launch_conv_x2_scales reduces into (zero between calls)
+    HIPCHK(m, t->x2_scale.alloc(x2.size() + x2.size() / 2));
+    HIPCHK(m, hipMemset(t->x2_scale, 0, t->x2_scale.size() * sizeof(float)));
+  }
+  t->gnb_n = (int)gnb.size();
+  HIPCHK(m, t->gnb_seg.upload(gnb.data(), gnb.size()));
+  HIPCHK(m, t->gnb_host.alloc_host(3 * gnb.size(), hipHostMallocMapped | hipHostMallocCoherent));
+  for (int i = 0; i < 3 * t->gnb_n; ++i) t->gnb_host[i] = -1.f;
+  for (hipEvent_t &e : t->gnb_ev) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return PNVO_OK;
+}
+
+// Buckets of the gradient-ready hook.  The backward finishes the parameters in the order head, hidden layer, compression,
+// layer4 ... layer1, stem; a range can be reported early when everything at or above its first offset belongs to layers
+// the backward has left (true for the reference's state_dict order; any other order falls back to one final range).
+void build_buckets(TrainState *t, const Toc &toc) {
+  auto stage_of = [](const std::string &nm) {          // 5: after the residual stages, 1..4: residual stage, 0: stem / other
+    const std::string bb = "visual_encoder.backbone.layer";
+    if (nm.rfind(bb, 0) == 0 && nm.size() > bb.size()) return nm[bb.size()] - '0';
+    if (nm.rfind("visual_encoder.backbone.", 0) == 0 || nm.rfind("action_embedding", 0) == 0) return 0;
+    return 5;
+  };
+  for (int lo_stage : {4, 2}) {
+    size_t first = t->n, below_end = 0;
+    for (auto &kv : toc) {
+      if (stage_of(kv.first) >= lo_stage) first = std::min(first, kv.second.off);
+      else below_end = std::max(below_end, kv.second.off + kv.second.numel);
+    }
+    if (first < t->n && below_end <= first && (t->bucket_first.empty() || first < t->bucket_first.back()) && first > 0)
+      t->bucket_first.push_back(first);
+  }
+  t->bucket_first.push_back(0);
+}
+
+// ---- workspace -----------------------------------------------------------------------------------------------------------
+
+// What the forward conv of a weight-gradient launch read.
+struct ConvInput {
+  const float *x = nullptr;        // a plain tensor (a block input, the dropped activations), or
+  const ConvSave *gn = nullptr;    // relu(GroupNorm(gn->raw)) of the producer, recomputed in the fetch, or
+  bool obs = false;                // the stem's gathered, whitened observation tensors
+};
+
+// The weight-gradient launch of layer l (a conv of m->convs, m->fc or m->head) at B samples, planned: input geometry = the forward
+// conv's.  ensure_train_ws sizes the scratch through it (null tensors), the backward launches through it.
+WgradArgs wgrad_request(pnvo_handle m, const TrainState *t, const Layer &l, int B, const ConvInput &in, const float *dy) {
+  const pnvo_config &c = m->cfg;
+  WgradArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.use_x3 = m->opt.wgrad3;
+  a.B = B;
+  a.H = l.hin;
+  a.W = l.win;
+  a.Ho = l.hout;
+  a.Wo = l.wout;
+  a.COUT = l.cout;
+  a.KH = l.k;
+  a.KW = l.kw;
+  a.stride = l.stride;
+  a.pad = l.pad;
+  a.dy = dy;
+  a.DYC = &l == &m->head ? 8 : &l == &m->fc ? c.hidden : l.coutp;       // dout8 / gh / a conv's raw-output gradient
+  // channels per pixel of what the kernel reads.  The hidden layer reads the channel-PADDED compression map (H/W/CIN = fh, fw,
+  // comp_cp tell the kernel the real row pitch); comp_cp is comp_c rounded up to whole 32-channel tiles, so the plan is the same.
+  a.CIN = in.obs ? 32 : &l == &m->fc ? m->comp_cp : l.cin;
+  if (in.obs) {                    // mode 2 reads its per-channel whitening from the device tables
+    const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
+    for (int k = 0; k < 32; ++k) {
+      const int tn = k < m->CP ? m->stem_tensor_of_new[k] : -1;
+      if (tn >= 0) a.src[k] = SrcLane{t->src[tn], nsrc[tn], m->stem_ch_of_new[k], 0.f, 0.f};
+    }
+    a.in_scale = m->stem_sc;
+    a.in_shift = m->stem_sh;
+    a.mode = 2;
+  } else if (in.gn != nullptr) {
+    a.x = in.gn->raw;
+    a.in_scale = in.gn->ss[0];
+    a.in_shift = in.gn->ss[1];
+    a.mode = 1;
+  } else {
+    a.x = in.x;
+  }
+  wgrad_plan(a);                   // picks the kernel by mode and geometry
+  return a;
+}
+
+// stem weight gradient on the bf16 matrix cores
+WgradStemMXArgs wgrad_stem_mx_request(pnvo_handle m, const TrainState *t, int B) {
+  WgradStemMXArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (int k = 0; k < 4; ++k) a.src[k] = t->src[k];
+  a.dy = t->ws.dStem;
+  a.zero_page = m->zero_page;
+  a.B = B;
+  a.H = m->cfg.height;
+  a.W = m->cfg.width;
+  a.Ho = m->Hs;
+  a.Wo = m->Ws;
+  wgrad_stem_mx_plan(a);
+  return a;
+}
+
+// floats of the largest weight-gradient scratch of a backward at B samples
+size_t wgrad_scratch_floats(pnvo_handle m, const TrainState *t, int B) {
+  size_t n = 0;
+  for (size_t li = 0; li < m->convs.size(); ++li)
+    n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->convs[li], B, ConvInput{.obs = li == 0}, nullptr)));
+  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->fc, B, {}, nullptr)));
+  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->head, B, {}, nullptr)));
+  if (m->train_mx) n = std::max(n, wgrad_stem_mx_scratch_floats(wgrad_stem_mx_request(m, t, B)));
+  return n;
+}
+
+// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves capB = 0.
+void free_train_ws(TrainState *t) {
+  t->ws = TrainWs{};
+  t->capB = 0;
+}
+
+int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
+  if (B <= t->capB) return PNVO_OK;
+  free_train_ws(t);
+  int rc = pnvo_ensure_workspace(m, B);    // stats buffer etc. of the inference path are reused
+  if (rc != PNVO_OK) return rc;
+  const pnvo_config &c = m->cfg;
+  TrainWs &w = t->ws;
+  w.cs.resize(m->convs.size());
+  // scratch gradients are as large as the largest activation
+  size_t act = (size_t)B * m->Hp * m->Wp * c.baseplanes;
+  int maxc = m->comp_cp, maxg = 1;
+  for (size_t li = 0; li < m->convs.size(); ++li) {
+    const Layer &l = m->convs[li];
+    ConvSave &s = w.cs[li];
+    HIPCHK(m, s.raw.alloc((size_t)B * l.hout * l.wout * l.coutp));
+    for (int k = 0; k < 2; ++k) {
+      HIPCHK(m, s.ss.alloc(k, (size_t)B * l.coutp));
+      HIPCHK(m, hipMemset(s.ss[k], 0, (size_t)B * l.coutp * 4));
+    }
+    HIPCHK(m, s.mu.alloc((size_t)B * l.groups));
+    HIPCHK(m, s.rstd.alloc((size_t)B * l.groups));
+    if (li >= 1) act = std::max({act, (size_t)B * l.hout * l.wout * l.coutp, (size_t)B * l.hin * l.win * l.cinp});
+    maxc = std::max(maxc, l.coutp);
+    maxg = std::max(maxg, l.groups);
+  }
+  HIPCHK(m, w.wg_partial.alloc(wgrad_scratch_floats(m, t, B)));
+  // block outputs: y[0] = pooled stem output, y[k] = output of m->blocks[k - 1]
+  w.y.resize(m->blocks.size() + 1);
+  HIPCHK(m, w.y[0].alloc((size_t)B * m->Hp * m->Wp * c.baseplanes));
+  for (size_t k = 1; k <= m->blocks.size(); ++k) {
+    const Layer &last = m->last(m->blocks[k - 1]);
+    HIPCHK(m, w.y[k].alloc((size_t)B * last.hout * last.wout * last.coutp));
+  }
+  HIPCHK(m, w.pool_idx.alloc(act));
+  const size_t nh = (size_t)B * c.hidden, nz = (size_t)B * m->fh * m->fw * m->comp_cp;
+  const std::pair<DevBuf<float> *, size_t> bufs[] = {
+      {&w.hid, nh},      {&w.dYa, act},     {&w.dYb, act}, {&w.G, act},   {&w.dRaw, act},
+      {&w.dA, act},      {&w.dStem, (size_t)B * m->Hs * m->Ws * c.baseplanes},
+      {&w.dout8, (size_t)B * 8},            {&w.dh, nh},   {&w.gh, nh},   {&w.dz, nz},
+      {&w.gn_part, (size_t)B * 65 * maxc * 2},   // 64 chunks + [B][C][2]
+      {&w.gn_coef, (size_t)B * maxg * 2},   {&w.zdrop, nz}, {&w.hdrop, nh}, {&w.dmask, std::max(nz, nh)}};
+  for (const auto &b : bufs) HIPCHK(m, b.first->alloc(b.second));
+  HIPCHK(m, w.mom_part.alloc((size_t)128 * MOMENTS_BLOCKS));
+  if (c.act_embed) {
+    const int rows = std::max(B, c.n_acts + 1);
+    for (DevBuf<float> *b : {&w.egath, &w.efeat, &w.dfeat}) HIPCHK(m, b->alloc((size_t)rows * 32));
+    HIPCHK(m, w.biasB.alloc((size_t)rows * c.hidden));
+    std::vector<int64_t> io(rows);
+    for (int k = 0; k < rows; ++k) io[k] = k;
+    HIPCHK(m, w.iota.upload(io.data(), io.size()));
+  }
+  t->capB = B;
+  return PNVO_OK;
+}
+
+// ---- backward launches -----------------------------------------------------------------------------------------------------
+
+// The backward-data conv of layer l: dX[B, hin, win, cin] (+)= conv(dRaw[B, hout, wout, coutp], wpk = flipped / transposed weights).
+// phase < 0: the full form (every tap, the forward's stride as upsampling).  phase = ph*2 + pw: the 1- or 2-tap dense stride-1 conv
+// that produces output parity (ph, pw) of a stride-2 3x3 conv (a.Ho or a.Wo may come out 0: nothing to launch).
+ConvArgs dgrad_conv_args(const Layer &l, int B, const float *draw, const float *wpk, float *dx, bool accum, int phase) {
+  const bool full = phase < 0;
+  const int ph = full ? 0 : phase >> 1, pw = full ? 0 : phase & 1;
+  ConvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.x = draw;
+  a.wpk = wpk;
+  a.y = dx;
+  a.B = B;
+  a.H = l.hout;
+  a.W = l.wout;
+  a.CIN = l.coutp;
+  a.Ho = full ? l.hin : (l.hin - ph + 1) / 2;
+  a.Wo = full ? l.win : (l.win - pw + 1) / 2;
+  a.COUT = l.cin;
+  a.COUTP = rup(l.cin, 32);
+  a.KH = full ? l.k : ph ? 2 : 1;
+  a.KW = full ? l.kw : pw ? 2 : 1;
+  a.stride = 1;
+  a.pad = full ? l.k - 1 - l.pad : 0;
+  a.up = full ? l.stride : 1;
+  a.accum = accum ? 1 : 0;
+  a.y_cstride = l.cin;
+  if (!full) {
+    a.y_sh = a.y_sw = 2;
+    a.y_oh = ph;
+    a.y_ow = pw;
+    a.y_H = l.hin;
+    a.y_W = l.win;
+  }
+  if (a.Ho > 0 && a.Wo > 0) {
+    choose_tile((long)B * a.Ho * a.Wo, a.COUTP, &a.MT, &a.NT);
+    a.slots = conv_slots(a.Ho * a.Wo, a.MT);
+  }
+  return a;
+}
+
+// A transposed Linear as a 1x1 conv over B one-pixel samples: y[B, cout] = x[B, cin] . wpk
+ConvArgs linear_t_args(const float *x, const float *wpk, float *y, int B, int cin, int cout) {
+  ConvArgs d;
+  std::memset(&d, 0, sizeof(d));
+  d.x = x;
+  d.wpk = wpk;
+  d.y = y;
+  d.B = B;
+  d.H = d.W = d.Ho = d.Wo = 1;
+  d.CIN = cin;
+  d.COUT = cout;
+  d.COUTP = rup(cout, 32);
+  d.KH = d.KW = 1;
+  d.stride = 1;
+  d.up = 1;
+  d.y_cstride = cout;
+  choose_tile(B, d.COUTP, &d.MT, &d.NT);
+  d.slots = conv_slots(1, d.MT);
+  return d;
+}
+
+// The conv_x3 operand of conv li's backward-data conv in np pieces (2: float16 on the forward's per-tensor scale wsc, 3: bf16),
+// rebuilt from the flat parameters when m's weights moved since it was made.
+int dgrad_x3_operand(pnvo_handle m, TrainState *t, size_t li, int np, const float *wsc, hipStream_t s) {
+  const Layer &l = m->convs[li];
+  TrainLayer &tl = t->conv[li];
+  DevBuf<unsigned short> &wpk = tl.dgrad_x[np - 2];
+  if (wpk && tl.dgrad_x_gen[np - 2] == m->weights_gen) return PNVO_OK;
+  if (!wpk) HIPCHK(m, wpk.alloc((size_t)9 * l.coutp * l.cin * np));
+  if (np == 2)
+    HIPCHK(m, launch_conv_x2_repack(t->params + tl.w.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, wsc, wpk, s, 1));
+  else
+    HIPCHK(m, launch_conv_x3_repack(t->params + tl.w.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, 1, wpk, s));
+  tl.dgrad_x_gen[np - 2] = m->weights_gen;
+  return PNVO_OK;
+}
+
+// backward-data of conv li: dX[B, hin, win, cin] (+)= conv(dRaw[B, hout, wout, coutp], flipped/transposed weights)
+int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw, float *dx, bool accum, hipStream_t s) {
+  const Layer &l = m->convs[li];
+  TrainLayer &tl = t->conv[li];
+  const double flops = 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw;
+  if (tl.dgrad_wph[0] != nullptr && m->opt.dgrad) {   // stride-2 3x3: four dense parity-phase convs instead of 9 taps, 3/4 masked
+    PnvoTimed tm(m, s, tl.t_dgrad, flops, 0.0);
+    for (int phase = 0; phase < 4; ++phase) {
+      const ConvArgs a = dgrad_conv_args(l, B, draw, tl.dgrad_wph[phase], dx, accum, phase);
+      if (a.Ho > 0 && a.Wo > 0) HIPCHK(m, launch_conv(a, s));
+    }
+    return PNVO_OK;
+  }
+  // 3x3 stride-1: float32 results from the bf16 matrix cores (three-piece operands), as in the forward (PNVO_CONV=fp32: off)
+  if (l.k == 3 && l.kw == 3 && l.stride == 1 && l.pad == 1 && !accum && l.cin % 32 == 0 && m->opt.conv <= 1) {
+    // two float16 pieces (three terms) when the training forward uses them: the gradient is scaled by a power of two from its
+    // absolute maximum (tracked by the GroupNorm backward that produced it), the weights carry the forward's per-tensor scale
+    const float *wsc = m->opt.train_pieces == 2 && t->dmax != nullptr ? pnvo_train_x2_scale(m, l) : nullptr;
+    // the transposed conv: input and output channels and sizes swapped, plain stager
+    ConvX3Problem q{.B = B, .H = l.hout, .W = l.wout, .CIN = l.coutp, .Ho = l.hin, .Wo = l.win, .COUTP = l.cin, .ks = 3, .stride = 1};
+    q.np = wsc != nullptr ? 2 : 3;
+    q.absmax = wsc != nullptr;
+    q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = 0, .w8 = 0, .m16 = 0, .ksw = 0,   // backward-data: the fine plan, W8, M16 and the K split stay off
+             .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0,   // (32 -> 32 backward-data convs: resident weights, conv_x3p_kernel)
+             .rows = 0, .num_cus = m->num_cus};                       // ... and the rows form, which has no gradient-input scaling
+    if (const ConvX3Plan p = conv_x3_plan(q)) {
+      if (int rc = dgrad_x3_operand(m, t, li, q.np, wsc, s)) return rc;
+      ConvX3Args xa = conv_x3_args(q, p);
+      xa.x = draw;
+      xa.wpk = tl.dgrad_x[q.np - 2];
+      xa.y = dx;
+      if (wsc != nullptr) {
+        xa.oscale_ptr = wsc + 1;
+        xa.in_absmax = t->dmax + li * PNVO_ABSMAX_UINTS;
+      }
+      PnvoTimed tm(m, s, tl.t_dgrad, flops, 0.0);
+      HIPCHK(m, launch_conv_x3(xa, p, s));
+      return PNVO_OK;
+    }
+  }
+  const ConvArgs a = dgrad_conv_args(l, B, draw, tl.dgrad_w, dx, accum, -1);
+  PnvoTimed tm(m, s, tl.t_dgrad, flops, 0.0);
+  if (conv3_lds_supported(a))         // backward-data of a 3x3 stride-1 conv is a 3x3 stride-1 conv: LDS-staged kernel
+    HIPCHK(m, launch_conv3_lds(a, (a.COUTP / 32) % 2 == 0 ? 2 : 1, s));
+  else
+    HIPCHK(m, launch_conv(a, s));
+  return PNVO_OK;
+}
+
+int run_wgrad(pnvo_handle m, TrainState *t, WgradArgs &a, const Weight &w, const int *perm, int cin_out, hipStream_t s) {
+  if (wgrad_partial_floats(a) > t->ws.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+  a.partial = t->ws.wg_partial;
+  a.zero_page = m->zero_page;
+  PnvoTimed tm(m, s, w.t_wgrad, 2.0 * (double)a.B * a.Ho * a.Wo * a.COUT * a.CIN * a.KH * a.KW, 0.0);
+  HIPCHK(m, launch_wgrad(a, t->grads + w.off, perm, cin_out, s));
+  return PNVO_OK;
+}
+
+int run_gn_bwd(pnvo_handle m, TrainState *t, size_t li, int B, const float *dout, int mask, float *dx, hipStream_t s) {
+  const Layer &l = m->convs[li];
+  const TrainLayer &tl = t->conv[li];
+  const ConvSave &c = t->ws.cs[li];
+  PnvoTimed tm(m, s, T_GN_BWD, 0.0, 0.0);
+  HIPCHK(m, launch_gn_bwd(c.raw, dout, c.ss[0], c.ss[1], c.mu, c.rstd, l.gamma, B, (long)l.hout * l.wout, l.coutp, l.cout, l.groups, mask,
+                          t->ws.gn_part, t->ws.gn_coef, t->grads + tl.gamma.off, t->grads + tl.beta.off, dx, s,
+                          t->dmax ? t->dmax + li * PNVO_ABSMAX_UINTS : nullptr));
   return PNVO_OK;
 }
 
@@ -344,294 +731,6 @@ int refresh_stem_dd(pnvo_handle m, TrainState *t, hipStream_t s) {
   return PNVO_OK;
 }
 
-// Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves capB = 0.
-void free_train_ws(TrainState *t) {
-  t->cs.clear();
-  t->y.clear();
-  for (DevBuf<float> *b : {&t->hid, &t->dYa, &t->dYb, &t->G, &t->dRaw, &t->dA, &t->dStem, &t->dout8, &t->dh, &t->gh, &t->dz, &t->gn_part,
-                           &t->gn_coef, &t->wg_partial, &t->zdrop, &t->hdrop, &t->dmask, &t->egath, &t->efeat, &t->biasB, &t->dfeat})
-    b->reset();
-  t->pool_idx.reset();
-  t->mom_part.reset();
-  t->iota.reset();
-  t->capB = 0;
-}
-
-// weight-gradient launch descriptor of conv `l` for batch B (input geometry = the forward conv's)
-thread_local int g_wgrad_x3 = 1;          // option wgrad3 of the handle whose call is in flight (set at the entry points)
-
-WgradArgs wgrad_args(const Layer &l, int B, int cin_kernel, int dyc, int mode = 0) {
-  WgradArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.use_x3 = g_wgrad_x3;
-  a.mode = mode;                 // wgrad_plan picks the kernel by mode
-  a.B = B;
-  a.H = l.hin;
-  a.W = l.win;
-  a.CIN = cin_kernel;
-  a.Ho = l.hout;
-  a.Wo = l.wout;
-  a.COUT = l.cout;
-  a.DYC = dyc;
-  a.KH = l.k;
-  a.KW = l.kw;
-  a.stride = l.stride;
-  a.pad = l.pad;
-  wgrad_plan(a);
-  return a;
-}
-
-int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
-  g_wgrad_x3 = m->opt.wgrad3;
-  if (B <= t->capB) return PNVO_OK;
-  free_train_ws(t);
-  int rc = pnvo_ensure_workspace(m, B);    // stats buffer etc. of the inference path are reused
-  if (rc != PNVO_OK) return rc;
-  const pnvo_config &c = m->cfg;
-  t->cs.resize(m->convs.size());
-  size_t wgmax = 0;
-  for (size_t li = 0; li < m->convs.size(); ++li) {
-    const Layer &l = m->convs[li];
-    ConvSave &s = t->cs[li];
-    const size_t n = (size_t)B * l.hout * l.wout * l.coutp;
-    HIPCHK(m, s.raw.alloc(n));
-    for (int k = 0; k < 2; ++k) {
-      HIPCHK(m, s.ss.alloc(k, (size_t)B * l.coutp));
-      HIPCHK(m, hipMemset(s.ss[k], 0, (size_t)B * l.coutp * 4));
-    }
-    HIPCHK(m, s.mu.alloc((size_t)B * l.groups));
-    HIPCHK(m, s.rstd.alloc((size_t)B * l.groups));
-    WgradArgs a = wgrad_args(l, B, li == 0 ? 32 : l.cin, l.coutp, li == 0 ? 2 : 0);
-    wgmax = std::max(wgmax, wgrad_partial_floats(a));
-  }
-  {
-    WgradArgs a = wgrad_args(m->fc, B, m->comp_c, c.hidden);
-    a.CIN = m->comp_c;
-    wgmax = std::max(wgmax, wgrad_partial_floats(a));
-    WgradArgs h = wgrad_args(m->head, B, c.hidden, 8);
-    wgmax = std::max(wgmax, wgrad_partial_floats(h));
-  }
-  if (m->train_mx) {                 // stem weight gradient on the bf16 matrix cores
-    WgradStemMXArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.Ho = m->Hs;
-    a.Wo = m->Ws;
-    wgrad_stem_mx_plan(a);
-    wgmax = std::max(wgmax, wgrad_stem_mx_scratch_floats(a));
-  }
-  HIPCHK(m, t->wg_partial.alloc(wgmax));
-  // block outputs: y[0] = pooled stem output, y[k] = output of m->blocks[k - 1]
-  size_t act = (size_t)B * m->Hp * m->Wp * c.baseplanes;
-  const size_t stem = (size_t)B * m->Hs * m->Ws * c.baseplanes;
-  {
-    t->y.resize(m->blocks.size() + 1);
-    HIPCHK(m, t->y[0].alloc(act));
-    for (size_t k = 1; k <= m->blocks.size(); ++k) {
-      const Layer &last = m->last(m->blocks[k - 1]);
-      const size_t n = (size_t)B * last.hout * last.wout * last.coutp;
-      HIPCHK(m, t->y[k].alloc(n));
-    }
-    for (size_t k = 1; k < m->convs.size(); ++k) {      // scratch gradients are as large as the largest activation
-      const Layer &l = m->convs[k];
-      act = std::max(act, (size_t)B * l.hout * l.wout * l.coutp);
-      act = std::max(act, (size_t)B * l.hin * l.win * l.cinp);
-    }
-  }
-  HIPCHK(m, t->pool_idx.alloc(act));
-  HIPCHK(m, t->hid.alloc((size_t)B * c.hidden));
-  HIPCHK(m, t->dYa.alloc(act));
-  HIPCHK(m, t->dYb.alloc(act));
-  HIPCHK(m, t->G.alloc(act));
-  HIPCHK(m, t->dRaw.alloc(act));
-  HIPCHK(m, t->dA.alloc(act));
-  HIPCHK(m, t->dStem.alloc(stem));
-  HIPCHK(m, t->dout8.alloc((size_t)B * 8));
-  HIPCHK(m, t->dh.alloc((size_t)B * c.hidden));
-  HIPCHK(m, t->gh.alloc((size_t)B * c.hidden));
-  HIPCHK(m, t->dz.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
-  int maxc = m->comp_cp, maxg = 1;
-  for (const Layer &l : m->convs) {
-    maxc = std::max(maxc, l.coutp);
-    maxg = std::max(maxg, l.groups);
-  }
-  HIPCHK(m, t->gn_part.alloc((size_t)B * 65 * maxc * 2));   // 64 chunks + [B][C][2]
-  HIPCHK(m, t->gn_coef.alloc((size_t)B * maxg * 2));
-  {
-    const size_t zf = (size_t)B * m->fh * m->fw * m->comp_cp, hf = (size_t)B * c.hidden;
-    HIPCHK(m, t->zdrop.alloc(zf));
-    HIPCHK(m, t->hdrop.alloc(hf));
-    HIPCHK(m, t->dmask.alloc(zf > hf ? zf : hf));
-  }
-  HIPCHK(m, t->mom_part.alloc((size_t)128 * MOMENTS_BLOCKS));
-  if (c.act_embed) {
-    const int rows = std::max(B, c.n_acts + 1);
-    HIPCHK(m, t->egath.alloc((size_t)rows * 32));
-    HIPCHK(m, t->efeat.alloc((size_t)rows * 32));
-    HIPCHK(m, t->dfeat.alloc((size_t)rows * 32));
-    HIPCHK(m, t->biasB.alloc((size_t)rows * c.hidden));
-    HIPCHK(m, t->iota.alloc((size_t)rows));
-    std::vector<int64_t> io(rows);
-    for (int k = 0; k < rows; ++k) io[k] = k;
-    HIPCHK(m, hipMemcpy(t->iota, io.data(), (size_t)rows * 8, hipMemcpyHostToDevice));
-  }
-  t->capB = B;
-  return PNVO_OK;
-}
-
-float *gradp(pnvo_handle m, TrainState *t, const std::string &name, int *rc) {
-  const TocEnt *e = need(m, t, name, rc);
-  return e ? t->grads + e->off : nullptr;
-}
-
-// backward-data of conv `l`: dX[B, hin, win, cin] (+)= conv(dRaw[B, hout, wout, coutp], flipped/transposed weights)
-int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw, float *dx, bool accum, hipStream_t s) {
-  const Layer &l = m->convs[li];
-  if (t->dgrad_wph[li][0] != nullptr && m->opt.dgrad) {   // stride-2 3x3: four dense parity-phase convs instead of 9 taps, 3/4 masked
-    PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw) {
-        ConvArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.x = draw;
-        a.wpk = t->dgrad_wph[li][ph * 2 + pw];
-        a.y = dx;
-        a.B = B;
-        a.H = l.hout;
-        a.W = l.wout;
-        a.CIN = l.coutp;
-        a.Ho = (l.hin - ph + 1) / 2;
-        a.Wo = (l.win - pw + 1) / 2;
-        if (a.Ho <= 0 || a.Wo <= 0) continue;
-        a.COUT = l.cin;
-        a.COUTP = rup(l.cin, 32);
-        a.KH = ph ? 2 : 1;
-        a.KW = pw ? 2 : 1;
-        a.stride = 1;
-        a.pad = 0;
-        a.up = 1;
-        a.accum = accum ? 1 : 0;
-        a.y_cstride = l.cin;
-        a.y_sh = a.y_sw = 2;
-        a.y_oh = ph;
-        a.y_ow = pw;
-        a.y_H = l.hin;
-        a.y_W = l.win;
-        const long M = (long)B * a.Ho * a.Wo;
-        choose_tile(M, a.COUTP, &a.MT, &a.NT);
-        a.slots = conv_slots(a.Ho * a.Wo, a.MT);
-        HIPCHK(m, launch_conv(a, s));
-      }
-    return PNVO_OK;
-  }
-  // 3x3 stride-1: float32 results from the bf16 matrix cores (three-piece operands), as in the forward (PNVO_CONV=fp32: off)
-  if (l.k == 3 && l.kw == 3 && l.stride == 1 && l.pad == 1 && !accum && l.cin % 32 == 0 && m->opt.conv <= 1) {
-    auto it = t->toc.find(l.name + ".weight");
-    // two float16 pieces (three terms) when the training forward uses them: the gradient is scaled by a power of two from its
-    // absolute maximum (tracked by the GroupNorm backward that produced it), the weights carry the forward's per-tensor scale
-    const float *wsc = m->opt.train_pieces == 2 && t->dmax != nullptr ? pnvo_train_x2_scale(m, l.name + ".weight") : nullptr;
-    // the transposed conv: input and output channels and sizes swapped, plain stager
-    ConvX3Problem q{.B = B, .H = l.hout, .W = l.wout, .CIN = l.coutp, .Ho = l.hin, .Wo = l.win, .COUTP = l.cin, .ks = 3, .stride = 1};
-    q.np = wsc != nullptr ? 2 : 3;
-    q.absmax = wsc != nullptr;
-    q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = 0, .w8 = 0, .m16 = 0, .ksw = 0,   // backward-data: the fine plan, W8, M16 and the K split stay off
-             .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0,   // (32 -> 32 backward-data convs: resident weights, conv_x3p_kernel)
-             .rows = 0, .num_cus = m->num_cus};                       // ... and the rows form, which has no gradient-input scaling
-    const ConvX3Plan p = it != t->toc.end() ? conv_x3_plan(q) : ConvX3Plan{};
-    if (p) {
-      ConvX3Args xa = conv_x3_args(q, p);
-      if (wsc != nullptr) {
-        if (!t->dgrad_x2[li] || t->dgrad_x2_gen[li] != m->weights_gen) {
-          const size_t nel = (size_t)9 * l.coutp * l.cin * 2;
-          if (!t->dgrad_x2[li]) {
-            HIPCHK(m, t->dgrad_x2[li].alloc(nel));
-          }
-          HIPCHK(m, launch_conv_x2_repack(t->params + it->second.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, wsc, t->dgrad_x2[li], s, 1));
-          t->dgrad_x2_gen[li] = m->weights_gen;
-        }
-        xa.x = draw;
-        xa.wpk = t->dgrad_x2[li];
-        xa.y = dx;
-        xa.oscale_ptr = wsc + 1;
-        xa.in_absmax = t->dmax + li * PNVO_ABSMAX_UINTS;
-        PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-        HIPCHK(m, launch_conv_x3(xa, p, s));
-        return PNVO_OK;
-      }
-      if (!t->dgrad_x3[li] || t->dgrad_x3_gen[li] != m->weights_gen) {
-        const size_t nel = (size_t)9 * l.coutp * l.cin * 3;
-        if (!t->dgrad_x3[li]) {
-          HIPCHK(m, t->dgrad_x3[li].alloc(nel));
-        }
-        HIPCHK(m, launch_conv_x3_repack(t->params + it->second.off, l.cin, l.cout, l.coutp, l.cin, 3, 3, 1, t->dgrad_x3[li], s));
-        t->dgrad_x3_gen[li] = m->weights_gen;
-      }
-      xa.x = draw;
-      xa.wpk = t->dgrad_x3[li];
-      xa.y = dx;
-      PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-      HIPCHK(m, launch_conv_x3(xa, p, s));
-      return PNVO_OK;
-    }
-  }
-  ConvArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = draw;
-  a.wpk = t->dgrad_w[li];
-  a.y = dx;
-  a.B = B;
-  a.H = l.hout;
-  a.W = l.wout;
-  a.CIN = l.coutp;
-  a.Ho = l.hin;
-  a.Wo = l.win;
-  a.COUT = l.cin;
-  a.COUTP = rup(l.cin, 32);
-  a.KH = l.k;
-  a.KW = l.kw;
-  a.stride = 1;
-  a.pad = l.k - 1 - l.pad;
-  a.up = l.stride;
-  a.accum = accum ? 1 : 0;
-  a.y_cstride = l.cin;
-  const long M = (long)B * l.hin * l.win;
-  choose_tile(M, a.COUTP, &a.MT, &a.NT);
-  a.slots = conv_slots(l.hin * l.win, a.MT);
-  PnvoTimed tm(m, s, "dgrad:" + l.name, 2.0 * (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw, 0.0);
-  if (conv3_lds_supported(a))         // backward-data of a 3x3 stride-1 conv is a 3x3 stride-1 conv: LDS-staged kernel
-    HIPCHK(m, launch_conv3_lds(a, (a.COUTP / 32) % 2 == 0 ? 2 : 1, s));
-  else
-    HIPCHK(m, launch_conv(a, s));
-  return PNVO_OK;
-}
-
-int run_wgrad(pnvo_handle m, TrainState *t, WgradArgs &a, const std::string &pname, const int *perm, int cin_out,
-              hipStream_t s) {
-  int rc = PNVO_OK;
-  float *g = gradp(m, t, pname, &rc);
-  if (!g) return rc;
-  if (wgrad_partial_floats(a) > t->wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
-  a.partial = t->wg_partial;
-  a.zero_page = m->zero_page;
-  PnvoTimed tm(m, s, "wgrad:" + pname, 2.0 * (double)a.B * a.Ho * a.Wo * a.COUT * a.CIN * a.KH * a.KW, 0.0);
-  HIPCHK(m, launch_wgrad(a, g, perm, cin_out, s));
-  return PNVO_OK;
-}
-
-int run_gn_bwd(pnvo_handle m, TrainState *t, size_t li, int B, const float *dout, int mask, float *dx, hipStream_t s) {
-  const Layer &l = m->convs[li];
-  const ConvSave &c = t->cs[li];
-  int rc = PNVO_OK;
-  float *dg = gradp(m, t, l.gn + ".weight", &rc);
-  if (!dg) return rc;
-  float *db = gradp(m, t, l.gn + ".bias", &rc);
-  if (!db) return rc;
-  PnvoTimed tm(m, s, "gn_bwd", 0.0, 0.0);
-  HIPCHK(m, launch_gn_bwd(c.raw, dout, c.ss[0], c.ss[1], c.mu, c.rstd, l.gamma, B, (long)l.hout * l.wout, l.coutp, l.cout,
-                          l.groups, mask, t->gn_part, t->gn_coef, dg, db, dx, s, t->dmax ? t->dmax + li * PNVO_ABSMAX_UINTS : nullptr));
-  return PNVO_OK;
-}
-
 }  // namespace
 
 void pnvo_train_free(pnvo_handle m) {
@@ -644,104 +743,26 @@ void pnvo_train_free(pnvo_handle m) {
   m->train = nullptr;
 }
 
-extern "C" {
-
-int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc, int ntoc) {
-  if (!m || !params || !grads || !toc) return pnvo_fail(m, PNVO_ERR_ARG, "null argument");
-  if (!m->loaded) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach before pnvo_load_weights");
-  if (m->grouped_se)
-    return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach: SE / ResNeXt backbones have no backward (the grouped conv and the gate are "
-                                        "inference kernels): these encoders run frozen");
-  if (n_floats >= (1u << 24)) return pnvo_fail(m, PNVO_ERR_ARG, "flat parameter buffer too large for the index maps");
-  HIPCHK(m, hipSetDevice(m->device));
-  pnvo_train_free(m);
-  TrainState *t = new TrainState();
-  m->train = t;
-  auto failed = [&](int rc) {          // a failed attach leaves no training state behind
-    pnvo_train_free(m);
-    return rc;
-  };
-  t->params = params;
-  t->grads = grads;
-  t->n = n_floats;
-  for (int k = 0; k < ntoc; ++k) {
-    TocEnt e;
-    e.off = toc[k].offset;
-    e.numel = 1;
-    for (int d = 0; d < toc[k].ndim; ++d) {
-      e.shape.push_back(toc[k].shape[d]);
-      e.numel *= (size_t)toc[k].shape[d];
-    }
-    if (e.off + e.numel > n_floats) return failed(pnvo_fail(m, PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range"));
-    t->toc[toc[k].name] = e;
-  }
-  int rc = build_maps(m, t);
-  if (rc != PNVO_OK) return failed(rc);
-  {
-    // Buckets of the gradient-ready hook.  The backward finishes the parameters in the order head, hidden layer, compression,
-    // layer4 ... layer1, stem; a range can be reported early when everything at or above its first offset belongs to layers
-    // the backward has left (true for the reference's state_dict order; any other order falls back to one final range).
-    auto stage_of = [](const std::string &nm) {          // 5: after the residual stages, 1..4: residual stage, 0: stem / other
-      const std::string bb = "visual_encoder.backbone.layer";
-      if (nm.rfind(bb, 0) == 0 && nm.size() > bb.size()) return nm[bb.size()] - '0';
-      if (nm.rfind("visual_encoder.backbone.", 0) == 0 || nm.rfind("action_embedding", 0) == 0) return 0;
-      return 5;
-    };
-    t->bucket_first.clear();
-    for (int lo_stage : {4, 2}) {
-      size_t first = n_floats, below_end = 0;
-      for (auto &kv : t->toc) {
-        const int st = stage_of(kv.first);
-        if (st >= lo_stage) first = std::min(first, kv.second.off);
-        else below_end = std::max(below_end, kv.second.off + kv.second.numel);
-      }
-      if (first < n_floats && below_end <= first && (t->bucket_first.empty() || first < t->bucket_first.back()) && first > 0)
-        t->bucket_first.push_back(first);
-    }
-    t->bucket_first.push_back(0);
-  }
-  rc = pnvo_train_refresh(m, nullptr);
-  return rc == PNVO_OK ? rc : failed(rc);
-}
-
-int pnvo_train_set_grad_hook(pnvo_handle m, pnvo_grad_ready_fn fn, void *user) {
-  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
-  TS(m)->hook = fn;
-  TS(m)->hook_user = user;
-  return PNVO_OK;
-}
-
-int pnvo_train_grad_buckets(pnvo_handle m, uint64_t *first, uint64_t *count, int cap, int *n_out) {
-  if (!m || !m->train || !n_out) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
-  TrainState *t = TS(m);
-  *n_out = (int)t->bucket_first.size();
-  size_t end = t->n;
-  for (int k = 0; k < *n_out && k < cap && first && count; ++k) {
-    first[k] = t->bucket_first[k];
-    count[k] = end - t->bucket_first[k];
-    end = t->bucket_first[k];
-  }
-  return PNVO_OK;
-}
-
-// device pointer of a parameter inside the caller's flat buffer (nullptr: not attached / unknown name)
-extern "C++" const float *pnvo_train_x2_scale(pnvo_handle m, const std::string &name) {
+// device {scale, 1/scale} of conv l's float16 pieces (nullptr: not attached, a Bottleneck model, not a conv that has a row)
+const float *pnvo_train_x2_scale(pnvo_handle m, const Layer &l) {
   if (!m || !m->train) return nullptr;
   TrainState *t = TS(m);
-  auto it = t->x2_index.find(name);
-  return it == t->x2_index.end() || !t->x2_scale ? nullptr : t->x2_scale + 2 * it->second;
+  const long li = conv_index(m, l);
+  return li < 0 || t->conv[li].x2_row < 0 || !t->x2_scale ? nullptr : t->x2_scale + 2 * t->conv[li].x2_row;
 }
 
-extern "C++" const float *pnvo_train_weight_ptr(pnvo_handle m, const std::string &name) {
+// device pointer of l's weight inside the caller's flat buffer (nullptr: not attached / not a layer of m)
+const float *pnvo_train_weight_ptr(pnvo_handle m, const Layer &l) {
   if (!m || !m->train) return nullptr;
   TrainState *t = TS(m);
-  auto it = t->toc.find(name);
-  return it == t->toc.end() ? nullptr : t->params + it->second.off;
+  if (&l == &m->fc || &l == &m->head) return t->params + (&l == &m->fc ? t->fc : t->head).w.off;
+  const long li = conv_index(m, l);
+  return li < 0 ? nullptr : t->params + t->conv[li].w.off;
 }
 
-__global__ __launch_bounds__(64) void gn_bound_kernel(const float *params, const TrainState::GnbSeg *seg, float *out) {
+extern "C" __global__ __launch_bounds__(64) void gn_bound_kernel(const float *params, const TrainState::GnbSeg *seg, float *out) {
   const TrainState::GnbSeg sg = seg[blockIdx.x];
-  if (sg.c <= 0) {                       // no GroupNorm (or parameters not found) behind this conv: "no bound", never "not computed yet"
+  if (sg.c <= 0) {                       // no GroupNorm behind this conv: "no bound", never "not computed yet"
     if (threadIdx.x == 0) __hip_atomic_store(out + blockIdx.x, 3.0e38f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     return;
   }
@@ -769,100 +790,98 @@ static void chain_tracked_bounds(pnvo_handle m, TrainState *t) {
   });
 }
 
-int pnvo_train_refresh(pnvo_handle m, void *stream) {
-  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
-  HIPCHK(m, hipSetDevice(m->device));
-  TrainState *t = TS(m);
-  m->weights_gen += 1;               // operands derived lazily from the weights (conv_x3) are rebuilt at their next use
-  if (!t->d_segs) {                 // segment table of all re-pack maps (built once; the maps never change after attach)
-    std::vector<GatherSeg> segs;
-    long start = 0;
-    for (const PackMap &pm : t->maps) {
-      segs.push_back(GatherSeg{pm.map, pm.dst, start});
-      start += (long)pm.map.size();
+// ---- training forward ------------------------------------------------------------------------------------------------------
+
+// residual blocks: a chain of K convs (BasicBlock K = 2, resnet.py:29-55; Bottleneck K = 3, :58-117) + the skip branch
+static int forward_blocks(pnvo_handle m, TrainState *t, int B, hipStream_t s) {
+  TrainWs &w = t->ws;
+  int rc = PNVO_OK;
+  BlockTail tail{};
+  const ConvSave *tail_x = nullptr;      // non-null: the previous block's tail rides on the next conv's stager
+  for (size_t bk = 0; bk < m->blocks.size(); ++bk) {
+    const Block &b = m->blocks[bk];
+    const int K = b.nconv, *ik = b.conv;
+    const float *xin = w.y[bk];
+    float *yout = w.y[bk + 1];
+    const bool ds = b.ds >= 0;
+    // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
+    // the backward pass reads it
+    const bool ds_ride = ds && K == 2 && pnvo_conv_choice(m, m->convs[ik[0]], B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
+    DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (ds_ride) {
+      ConvSave &sd = w.cs[b.ds];
+      ride = DsRide{&m->convs[b.ds], sd.raw, sd.ss, sd.mu, sd.rstd};
     }
-    t->seg_total = start;
-    t->nseg = (int)segs.size();
-    HIPCHK(m, t->d_segs.alloc(segs.size()));
-    HIPCHK(m, hipMemcpy(t->d_segs, segs.data(), segs.size() * sizeof(GatherSeg), hipMemcpyHostToDevice));
-  }
-  HIPCHK(m, launch_gather_all(t->params, t->d_segs, t->nseg, t->seg_total, (hipStream_t)stream));
-  if (!t->x2_seg && !m->bottleneck) {       // the 3x3 / strided convs conv_x3.hip may take: one scale row each
-    std::vector<long> seg;
-    for (size_t li = 1; li < m->convs.size(); ++li) {
-      const Layer &l = m->convs[li];
-      auto it = t->toc.find(l.name + ".weight");
-      if (it == t->toc.end()) continue;
-      t->x2_index[l.name + ".weight"] = (int)(seg.size() / 2);
-      seg.push_back((long)it->second.off);
-      seg.push_back((long)it->second.numel);
-    }
-    if (!seg.empty()) {
-      HIPCHK(m, t->x2_seg.alloc(seg.size()));
-      // {scale, 1/scale} per conv + the integer maxima launch_conv_x2_scales reduces into (zero between calls)
-      HIPCHK(m, t->x2_scale.alloc(seg.size() + seg.size() / 2));
-      HIPCHK(m, hipMemset(t->x2_scale, 0, (seg.size() + seg.size() / 2) * sizeof(float)));
-      HIPCHK(m, hipMemcpy(t->x2_seg, seg.data(), seg.size() * sizeof(long), hipMemcpyHostToDevice));
-    }
-  }
-  if (t->x2_seg) HIPCHK(m, launch_conv_x2_scales(t->params, t->x2_seg, (int)t->x2_index.size(), t->x2_scale, (hipStream_t)stream));
-  if (!m->bottleneck) {                // GroupNorm bounds of the CURRENT parameters -> host-mapped table (chain_tracked_bounds)
-    if (!t->gnb_seg) {
-      std::vector<TrainState::GnbSeg> seg(m->convs.size(), TrainState::GnbSeg{0, 0, 0, 0.f});
-      for (size_t li = 0; li < m->convs.size(); ++li) {
-        const Layer &l = m->convs[li];
-        auto g = t->toc.find(l.gn + ".weight"), b = t->toc.find(l.gn + ".bias");
-        if (l.gn.empty() || g == t->toc.end() || b == t->toc.end() || l.groups <= 0) continue;
-        seg[li] = TrainState::GnbSeg{(long)g->second.off, (long)b->second.off, l.cout,
-                                     (float)std::sqrt((double)(l.cout / l.groups) * l.hout * l.wout)};
+    for (int k = 0; k < K; ++k) {
+      const Layer &ck = m->convs[ik[k]];
+      ConvSave &sk = w.cs[ik[k]];
+      const ConvSave *sp = k ? &w.cs[ik[k - 1]] : nullptr;
+      const DsRide *rd = (k == 0 && ds_ride) ? &ride : nullptr;
+      if (k == 0 && tail_x != nullptr) {       // this conv's stager computes the previous block's tail and writes xin (= tail.out)
+        rc = pnvo_run_conv(m, ck, B, {.x = tail_x->raw, .in_scale = tail_x->ss[0], .in_shift = tail_x->ss[1], .y = sk.raw, .y_cstride = ck.coutp,
+                                      .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .tail = &tail, .ride = rd, .s = s});
+        tail_x = nullptr;
+      } else {
+        rc = pnvo_run_conv(m, ck, B, {.x = k ? sp->raw : xin, .in_scale = k ? sp->ss[0] : nullptr, .in_shift = k ? sp->ss[1] : nullptr,
+                                      .y = sk.raw, .y_cstride = ck.coutp, .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .ride = rd, .s = s});
       }
-      t->gnb_n = (int)seg.size();
-      HIPCHK(m, t->gnb_seg.alloc(seg.size()));
-      HIPCHK(m, hipMemcpy(t->gnb_seg, seg.data(), seg.size() * sizeof(TrainState::GnbSeg), hipMemcpyHostToDevice));
-      HIPCHK(m, t->gnb_host.alloc_host(3 * seg.size(), hipHostMallocMapped | hipHostMallocCoherent));
-      for (int i = 0; i < 3 * t->gnb_n; ++i) t->gnb_host[i] = -1.f;
-      for (hipEvent_t &e : t->gnb_ev) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      if (rc != PNVO_OK) return rc;
     }
-    // A refresh that is being CAPTURED would bake one ring entry into the graph: every replay rewrites that entry while the host reads
-    // another one behind an event that is never recorded.  So a captured refresh leaves the ring alone and marks every entry unknown
-    // (-1) and restarts the two-refresh lag: chain_tracked_bounds then leaves Layer::in_bound as last chained (the load-time bounds
-    // when nothing was chained yet) instead of reading an entry that no event orders.
-    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cst) != hipSuccess || cst != hipStreamCaptureStatusNone;
-    if (capturing) {
-      for (int i = 0; i < 3 * t->gnb_n; ++i) t->gnb_host[i] = -1.f;
-      t->gnb_refreshes = 0;
+    const Layer &cl = m->convs[ik[K - 1]];
+    ConvSave &sl = w.cs[ik[K - 1]];
+    if (ds) {
+      const Layer &cd = m->convs[b.ds];
+      ConvSave &sd = w.cs[b.ds];
+      if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, {.x = xin, .y = sd.raw, .y_cstride = cd.coutp, .ss = sd.ss, .mu = sd.mu, .rstd = sd.rstd,
+                                                     .s = s})) != PNVO_OK)
+        return rc;
+      tail = BlockTail{sd.raw, sd.ss[0], sd.ss[1], yout};
     } else {
-      const int e = (int)(t->gnb_refreshes % 3);
-      hipLaunchKernelGGL(gn_bound_kernel, dim3((unsigned)t->gnb_n), dim3(64), 0, (hipStream_t)stream, t->params, t->gnb_seg,
-                         t->gnb_host + (size_t)e * t->gnb_n);
-      HIPCHK(m, hipGetLastError());
-      HIPCHK(m, hipEventRecord(t->gnb_ev[e], (hipStream_t)stream));
-      t->gnb_refreshes += 1;
+      tail = BlockTail{xin, nullptr, nullptr, yout};
     }
+    const bool last = bk + 1 == m->blocks.size();
+    if (!last && pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B))   // the next block's first conv computes and writes yout
+      tail_x = &sl;
+    else
+      HIPCHK(m, launch_residual(sl.raw, sl.ss[0], sl.ss[1], tail.res, tail.res_scale, tail.res_shift, B, (long)cl.hout * cl.wout, cl.coutp,
+                                yout, s));
   }
-  if (m->cfg.act_embed) {      // eval-mode bias rows bias[a][o] = b1[o] + W1[o][flat:] . emb[a]  (pnvo_load_weights does this on the host)
-    const pnvo_config &c = m->cfg;
-    const int rows = c.n_acts + 1, flat = m->comp_c * m->fh * m->fw;
-    int rc = ensure_train_ws(m, t, t->capB > 0 ? t->capB : 1);
-    if (rc != PNVO_OK) return rc;
-    HIPCHK(m, launch_embed_gather(t->params + t->emb_off, nullptr, rows, rows, t->egath, nullptr, (hipStream_t)stream));
-    HIPCHK(m, launch_embed_bias(t->egath, t->params + t->w1_off, t->w1_pitch, flat, t->params + t->b1_off, rows, c.hidden,
-                                m->fc_bias, (hipStream_t)stream));
-  }
-  return refresh_stem_dd(m, t, (hipStream_t)stream);
+  return PNVO_OK;
 }
 
-static int train_forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
-                              const float *run_mean, const float *run_var, float *out, void *stream);
-
-int pnvo_train_forward(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
-                       const float *run_mean, const float *run_var, float *out, void *stream) {
-  int rc = train_forward_body(m, rgb, depth, dd, tdv, B, run_mean, run_var, out, stream);
-  if (rc != PNVO_OK) return rc;
-  bool rerun = false;                  // an input outside the fused stems' contract: once more on the dense stem (pnvo_api.hip)
-  if ((rc = pnvo_input_fallback(m, (hipStream_t)stream, &rerun)) != PNVO_OK) return rc;
-  return rerun ? train_forward_body(m, rgb, depth, dd, tdv, B, run_mean, run_var, out, stream) : PNVO_OK;
+// Dropout -> Linear -> ReLU -> Dropout -> Linear (vo_cnn.py:216-227) on the compression conv's output, masks by hash
+static int forward_linears(pnvo_handle m, TrainState *t, int B, float *out, hipStream_t s) {
+  const pnvo_config &c = m->cfg;
+  TrainWs &w = t->ws;
+  const ConvSave &sc = w.cs[m->comp];
+  int rc = PNVO_OK;
+  ++t->drop_step;
+  const float *fcb = m->fc_bias;
+  const int64_t *fcrow = nullptr;
+  if (c.act_embed) {                // the embedding columns of the Linear as per-sample bias rows (vo_cnn_act_embed.py:63-72)
+    const int flat = m->comp_c * m->fh * m->fw;
+    HIPCHK(m, launch_embed_gather(t->params + t->emb_off, t->actions, B, c.n_acts + 1, w.egath, t->embed_err, s));
+    if (t->drop_p > 0.f)            // nn.Dropout acts on the concatenated [visual | embedding] vector: mask "layer" 2
+      HIPCHK(m, launch_dropout(w.egath, nullptr, nullptr, B, 1, 32, t->drop_p, t->drop_seed, t->drop_step, 2, w.efeat, s));
+    else
+      HIPCHK(m, hipMemcpyAsync(w.efeat, w.egath, (size_t)B * 32 * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(m, launch_embed_bias(w.efeat, t->params + t->fc.w.off, t->w1_pitch, flat, t->params + t->fc.b.off, B, c.hidden, w.biasB, s));
+    fcb = w.biasB;
+    fcrow = w.iota;
+  }
+  if (t->drop_p > 0.f) {
+    HIPCHK(m, launch_dropout(sc.raw, sc.ss[0], sc.ss[1], B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed, t->drop_step, 0,
+                             w.zdrop, s));
+    if ((rc = pnvo_run_conv(m, m->fc, B, {.x = w.zdrop, .y = w.hid, .y_cstride = c.hidden, .bias = fcb, .bias_row = fcrow, .relu_out = 1,
+                                          .s = s})) != PNVO_OK)
+      return rc;
+    HIPCHK(m, launch_dropout(w.hid, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, w.hdrop, s));
+    return pnvo_run_conv(m, m->head, B, {.x = w.hdrop, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
+  }
+  if ((rc = pnvo_run_conv(m, m->fc, B, {.x = sc.raw, .in_scale = sc.ss[0], .in_shift = sc.ss[1], .y = w.hid, .y_cstride = c.hidden,
+                                        .bias = fcb, .bias_row = fcrow, .relu_out = 1, .s = s})) != PNVO_OK)
+    return rc;
+  return pnvo_run_conv(m, m->head, B, {.x = w.hid, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
 }
 
 static int train_forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
@@ -889,109 +908,22 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
   if (c.normalize)   // RunningMeanAndVar buffers live on the device and change every step (running_mean_and_var.py:54-60)
     HIPCHK(m, launch_whiten_table(run_mean, run_var, t->d_ref_of_new, t->d_tensor_of_new, m->CPL, m->stem_sc, m->stem_sh, s));
   if ((rc = refresh_stem_dd(m, t, s)) != PNVO_OK) return rc;   // W/std table, indicator weights: both move every step
-
-  {
-    ConvSave &cs = t->cs[0];
-    if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
-                                   .train_fwd = true, .s = s})) != PNVO_OK)
-      return rc;
-    const Layer &stem = m->convs[0];
-    HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, stem.coutp, t->y[0], t->pool_idx, s));
-  }
-  // residual blocks: a chain of K convs (BasicBlock K = 2, resnet.py:29-55; Bottleneck K = 3, :58-117) + the skip branch
-  BlockTail tail{};
-  const ConvSave *tail_x = nullptr;
-  bool have_tail = false;
-  for (size_t bk = 0; bk < m->blocks.size(); ++bk) {
-    const Block &b = m->blocks[bk];
-    const int K = b.nconv, *ik = b.conv;
-    const float *xin = t->y[bk];
-    float *yout = t->y[bk + 1];
-    const bool ds = b.ds >= 0;
-    // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
-    // the backward pass reads it
-    const bool ds_ride = ds && K == 2 && pnvo_conv_choice(m, m->convs[ik[0]], B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
-    DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (ds_ride) {
-      ConvSave &sd = t->cs[b.ds];
-      ride = DsRide{&m->convs[b.ds], sd.raw, sd.ss, sd.mu, sd.rstd};
-    }
-    for (int k = 0; k < K; ++k) {
-      const Layer &ck = m->convs[ik[k]];
-      ConvSave &sk = t->cs[ik[k]];
-      const ConvSave *sp = k ? &t->cs[ik[k - 1]] : nullptr;
-      const DsRide *rd = (k == 0 && ds_ride) ? &ride : nullptr;
-      if (k == 0 && have_tail) {       // the previous block's tail rides on this conv's stager, which writes xin (= tail.out)
-        rc = pnvo_run_conv(m, ck, B, {.x = tail_x->raw, .in_scale = tail_x->ss[0], .in_shift = tail_x->ss[1], .y = sk.raw, .y_cstride = ck.coutp,
-                                      .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .tail = &tail, .ride = rd, .s = s});
-        have_tail = false;
-      } else {
-        rc = pnvo_run_conv(m, ck, B, {.x = k ? sp->raw : xin, .in_scale = k ? sp->ss[0] : nullptr, .in_shift = k ? sp->ss[1] : nullptr,
-                                      .y = sk.raw, .y_cstride = ck.coutp, .ss = sk.ss, .mu = sk.mu, .rstd = sk.rstd, .ride = rd, .s = s});
-      }
-      if (rc != PNVO_OK) return rc;
-    }
-    const Layer &cl = m->convs[ik[K - 1]];
-    ConvSave &sl = t->cs[ik[K - 1]];
-    const long P = (long)cl.hout * cl.wout;
-    if (ds) {
-      const Layer &cd = m->convs[b.ds];
-      ConvSave &sd = t->cs[b.ds];
-      if (!ds_ride && (rc = pnvo_run_conv(m, cd, B, {.x = xin, .y = sd.raw, .y_cstride = cd.coutp, .ss = sd.ss, .mu = sd.mu, .rstd = sd.rstd,
-                                                     .s = s})) != PNVO_OK)
-        return rc;
-      tail = BlockTail{sd.raw, sd.ss[0], sd.ss[1], yout};
-    } else {
-      tail = BlockTail{xin, nullptr, nullptr, yout};
-    }
-    const bool last = bk + 1 == m->blocks.size();
-    if (!last && pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B)) {   // the next block's first conv computes and writes yout
-      tail_x = &sl;
-      have_tail = true;
-    } else {
-      HIPCHK(m, launch_residual(sl.raw, sl.ss[0], sl.ss[1], tail.res, tail.res_scale, tail.res_shift, B, P, cl.coutp, yout, s));
-    }
-  }
-  {
-    const Layer &comp = m->convs[m->comp];
-    ConvSave &sc = t->cs[m->comp];
-    if ((rc = pnvo_run_conv(m, comp, B, {.x = t->y[m->blocks.size()], .y = sc.raw, .y_cstride = comp.coutp, .ss = sc.ss, .mu = sc.mu, .rstd = sc.rstd,
-                                         .s = s})) != PNVO_OK)
-      return rc;
-    ++t->drop_step;
-    const float *fcb = m->fc_bias;
-    const int64_t *fcrow = nullptr;
-    if (c.act_embed) {                // the embedding columns of the Linear as per-sample bias rows (vo_cnn_act_embed.py:63-72)
-      const int flat = m->comp_c * m->fh * m->fw;
-      HIPCHK(m, launch_embed_gather(t->params + t->emb_off, t->actions, B, c.n_acts + 1, t->egath, t->embed_err, s));
-      if (t->drop_p > 0.f)            // nn.Dropout acts on the concatenated [visual | embedding] vector: mask "layer" 2
-        HIPCHK(m, launch_dropout(t->egath, nullptr, nullptr, B, 1, 32, t->drop_p, t->drop_seed, t->drop_step, 2, t->efeat, s));
-      else
-        HIPCHK(m, hipMemcpyAsync(t->efeat, t->egath, (size_t)B * 32 * 4, hipMemcpyDeviceToDevice, s));
-      HIPCHK(m, launch_embed_bias(t->efeat, t->params + t->w1_off, t->w1_pitch, flat, t->params + t->b1_off, B, c.hidden,
-                                  t->biasB, s));
-      fcb = t->biasB;
-      fcrow = t->iota;
-    }
-    if (t->drop_p > 0.f) {            // Dropout -> Linear -> ReLU -> Dropout -> Linear (vo_cnn.py:216-227), masks by hash
-      HIPCHK(m, launch_dropout(sc.raw, sc.ss[0], sc.ss[1], B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed,
-                               t->drop_step, 0, t->zdrop, s));
-      if ((rc = pnvo_run_conv(m, m->fc, B, {.x = t->zdrop, .y = t->hid, .y_cstride = c.hidden, .bias = fcb, .bias_row = fcrow, .relu_out = 1,
-                                            .s = s})) != PNVO_OK)
-        return rc;
-      HIPCHK(m, launch_dropout(t->hid, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, t->hdrop,
-                               s));
-      return pnvo_run_conv(m, m->head, B, {.x = t->hdrop, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
-    }
-    if ((rc = pnvo_run_conv(m, m->fc, B, {.x = sc.raw, .in_scale = sc.ss[0], .in_shift = sc.ss[1], .y = t->hid, .y_cstride = c.hidden,
-                                          .bias = fcb, .bias_row = fcrow, .relu_out = 1, .s = s})) != PNVO_OK ||
-        (rc = pnvo_run_conv(m, m->head, B, {.x = t->hid, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s})) != PNVO_OK)
-      return rc;
-  }
-  return PNVO_OK;
+  TrainWs &w = t->ws;
+  ConvSave &cs = w.cs[0];
+  if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
+                                 .train_fwd = true, .s = s})) != PNVO_OK)
+    return rc;
+  HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, m->convs[0].coutp, w.y[0], w.pool_idx, s));
+  if ((rc = forward_blocks(m, t, B, s)) != PNVO_OK) return rc;
+  const Layer &comp = m->convs[m->comp];
+  ConvSave &sc = w.cs[m->comp];
+  if ((rc = pnvo_run_conv(m, comp, B, {.x = w.y[m->blocks.size()], .y = sc.raw, .y_cstride = comp.coutp, .ss = sc.ss, .mu = sc.mu, .rstd = sc.rstd,
+                                       .s = s})) != PNVO_OK)
+    return rc;
+  return forward_linears(m, t, B, out, s);
 }
 
-static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream, const float *dh_in = nullptr, bool stop_after_fc = false);
+// ---- backward --------------------------------------------------------------------------------------------------------------
 
 // bucket k of the gradient-ready hook is final: report it (host callback; the launches that produce it are enqueued on `s`)
 static void report_bucket(TrainState *t, size_t k, hipStream_t s) {
@@ -1004,264 +936,279 @@ static void report_bucket(TrainState *t, size_t k, hipStream_t s) {
   t->hook(t->hook_user, (uint64_t)t->bucket_first[k], (uint64_t)(end - t->bucket_first[k]), (void *)s);
 }
 
-int pnvo_train_backward(pnvo_handle m, const float *grad_out, void *stream) {
-  if (m && m->train) TS(m)->bucket_done.assign(TS(m)->bucket_first.size(), 0);
-  const int rc = train_backward_body(m, grad_out, stream);
-  // the end of the backward: every range not reported on the way (whatever the number of split points a parameter order allowed —
-  // with exactly one of them the in-backward reports are skipped and BOTH ranges are due here), latest layers first
-  if (rc == PNVO_OK && m->train)
-    for (size_t k = 0; k < TS(m)->bucket_first.size(); ++k) report_bucket(TS(m), k, (hipStream_t)stream);
+// output head: out = hid . W2^T + b2
+static int backward_head(pnvo_handle m, TrainState *t, int B, const float *grad_out, hipStream_t s) {
+  const pnvo_config &c = m->cfg;
+  TrainWs &w = t->ws;
+  HIPCHK(m, launch_padcopy(grad_out, B, c.out_dim, 8, w.dout8, s));
+  HIPCHK(m, launch_colsum(grad_out, B, c.out_dim, c.out_dim, t->grads + t->head.b.off, s));
+  WgradArgs a = wgrad_request(m, t, m->head, B, {.x = t->drop_p > 0.f ? w.hdrop : w.hid}, w.dout8);
+  if (int rc = run_wgrad(m, t, a, t->head.w, nullptr, c.hidden, s)) return rc;
+  HIPCHK(m, launch_conv(linear_t_args(w.dout8, t->head_t, w.dh, B, 8, c.hidden), s));
+  return PNVO_OK;
+}
+
+// hidden layer: hid = relu(z . W1^T + b1); dh -> dz (stop_after_fc: only the layer's own gradients)
+static int backward_hidden(pnvo_handle m, TrainState *t, int B, bool stop_after_fc, hipStream_t s) {
+  const pnvo_config &c = m->cfg;
+  TrainWs &w = t->ws;
+  const bool drop = t->drop_p > 0.f;
+  if (drop)                         // dropout backward: the same mask, then the ReLU mask of the un-dropped activation
+    HIPCHK(m, launch_dropout(w.dh, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, w.dh, s));
+  HIPCHK(m, launch_relu_mask(w.dh, w.hid, nullptr, (long)B * c.hidden, w.gh, s));
+  HIPCHK(m, launch_colsum(w.gh, B, c.hidden, c.hidden, t->grads + t->fc.b.off, s));
+  // with dropout the Linear saw the dropped, already activated feature
+  WgradArgs a = wgrad_request(m, t, m->fc, B, drop ? ConvInput{.x = w.zdrop} : ConvInput{.gn = &w.cs[m->comp]}, w.gh);
+  if (c.act_embed) {                // gradient rows are [flat | 32] wide; the embedding columns and rows come from embed_*
+    const int flat = m->comp_c * m->fh * m->fw;
+    a.grad_pitch = t->w1_pitch;
+    HIPCHK(m, launch_embed_backward(w.gh, w.efeat, t->params + t->fc.w.off, t->w1_pitch, flat, B, c.hidden, t->grads + t->fc.w.off, w.dfeat,
+                                    s));
+    if (drop) HIPCHK(m, launch_dropout(w.dfeat, nullptr, nullptr, B, 1, 32, t->drop_p, t->drop_seed, t->drop_step, 2, w.dfeat, s));
+    HIPCHK(m, launch_embed_scatter(w.dfeat, t->actions, B, c.n_acts + 1, t->grads + t->emb_off, s));
+  }
+  if (int rc = run_wgrad(m, t, a, t->fc.w, nullptr, m->comp_c, s)) return rc;
+  if (stop_after_fc) return PNVO_OK;
+  HIPCHK(m, launch_conv(linear_t_args(w.gh, t->fc_t, w.dz, B, c.hidden, m->fh * m->fw * m->comp_cp), s));
+  if (drop)
+    HIPCHK(m, launch_dropout(w.dz, nullptr, nullptr, B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed, t->drop_step, 0, w.dz, s));
+  return PNVO_OK;
+}
+
+// compression conv + GroupNorm(1) + ReLU: dz -> dY
+static int backward_compression(pnvo_handle m, TrainState *t, int B, float *dY, hipStream_t s) {
+  TrainWs &w = t->ws;
+  const size_t li = m->comp;
+  const Layer &l = m->convs[li];
+  int rc = run_gn_bwd(m, t, li, B, w.dz, 1, w.dz, s);   // in place: dz -> dCompRaw
+  if (rc != PNVO_OK) return rc;
+  WgradArgs a = wgrad_request(m, t, l, B, {.x = w.y[m->blocks.size()]}, w.dz);
+  if ((rc = run_wgrad(m, t, a, t->conv[li].w, nullptr, l.cin, s)) != PNVO_OK) return rc;
+  return run_dgrad(m, t, li, B, w.dz, dY, false, s);
+}
+
+// residual block b, whose input is y[blk - 1] and output y[blk]: dY (gradient of the output) -> dX (of the input)
+static int backward_block(pnvo_handle m, TrainState *t, size_t blk, int B, const float *dY, float *dX, hipStream_t s) {
+  TrainWs &w = t->ws;
+  const Block &b = m->blocks[blk - 1];
+  const int K = b.nconv, *ik = b.conv;
+  const Layer &c1 = m->convs[ik[0]], &cl = m->convs[ik[K - 1]];
+  const float *xin = w.y[blk - 1];
+  int rc = PNVO_OK;
+  // G = dY * (y > 0)
+  HIPCHK(m, launch_relu_mask(dY, w.y[blk], nullptr, (long)B * cl.hout * cl.wout * cl.coutp, w.G, s));
+  // the chain, last conv first: GroupNorm (+ ReLU mask for every conv but the last) <- incoming gradient
+  const float *din = w.G;
+  for (int k = K - 1; k >= 0; --k) {
+    const Layer &ck = m->convs[ik[k]];
+    if ((rc = run_gn_bwd(m, t, ik[k], B, din, k == K - 1 ? 0 : 1, w.dRaw, s)) != PNVO_OK) return rc;
+    // conv k > 0 saw relu(GN(raw of the previous conv))
+    WgradArgs a = wgrad_request(m, t, ck, B, k ? ConvInput{.gn = &w.cs[ik[k - 1]]} : ConvInput{.x = xin}, w.dRaw);
+    if (a.lds3 == 6 && m->opt.train_pieces == 2 && t->dmax != nullptr && ck.in_bound < 6.0e4f) {
+      a.np = 2;                     // float16 pieces: X inside float16's range (the forward's bound), dY scaled from its maximum
+      a.dy_absmax = t->dmax + ik[k] * PNVO_ABSMAX_UINTS;
+    }
+    if ((rc = run_wgrad(m, t, a, t->conv[ik[k]].w, nullptr, ck.cin, s)) != PNVO_OK) return rc;
+    if ((rc = run_dgrad(m, t, ik[k], B, w.dRaw, k ? w.dA : dX, false, s)) != PNVO_OK) return rc;
+    din = w.dA;
+  }
+  if (b.ds < 0) {                   // identity skip
+    HIPCHK(m, launch_add(dX, w.G, (long)B * c1.hin * c1.win * c1.cin, dX, s));
+    return PNVO_OK;
+  }
+  const Layer &cd = m->convs[b.ds];
+  if ((rc = run_gn_bwd(m, t, b.ds, B, w.G, 0, w.dRaw, s)) != PNVO_OK) return rc;
+  WgradArgs a = wgrad_request(m, t, cd, B, {.x = xin}, w.dRaw);
+  if ((rc = run_wgrad(m, t, a, t->conv[b.ds].w, nullptr, cd.cin, s)) != PNVO_OK) return rc;
+  return run_dgrad(m, t, b.ds, B, w.dRaw, dX, true, s);
+}
+
+// stem: maxpool <- dY, GroupNorm + ReLU, weight gradient (no input gradient)
+static int backward_stem(pnvo_handle m, TrainState *t, int B, const float *dY, hipStream_t s) {
+  TrainWs &w = t->ws;
+  const Layer &l = m->convs[0];
+  const TrainLayer &tl = t->conv[0];
+  if (m->opt.pool_bwd && l.coutp == l.cout && l.cout % 4 == 0 && l.cout <= 256 && 256 % (l.cout / 4) == 0) {
+    // max-pool backward folded into the stem's GroupNorm backward: the un-pooled gradient is never materialised
+    const ConvSave &cs0 = w.cs[0];
+    PnvoTimed tm(m, s, T_GN_BWD, 0.0, 0.0);
+    HIPCHK(m, launch_gn_bwd_pool(cs0.raw, dY, w.pool_idx, m->Hs, m->Ws, m->Hp, m->Wp, cs0.ss[0], cs0.ss[1], cs0.mu, cs0.rstd, l.gamma, B, l.cout,
+                                 l.groups, w.gn_part, w.gn_coef, t->grads + tl.gamma.off, t->grads + tl.beta.off, w.dStem, s));
+  } else {
+    HIPCHK(m, launch_maxpool_bwd(dY, w.pool_idx, B, m->Hs, m->Ws, l.coutp, w.dStem, s));
+    if (int rc = run_gn_bwd(m, t, 0, B, w.dStem, 1, w.dStem, s)) return rc;
+  }
+  // option wgrad_stem=fp32: the float32-MFMA kernel; also once an input outside the exact-operand contract was met
+  const bool stem_fp32 = m->opt.wgrad_stem == 1 || m->dense_sticky;
+  if (m->train_mx && l.coutp == 32 && !stem_fp32) {
+    const WgradStemMXArgs a = wgrad_stem_mx_request(m, t, B);
+    if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+    PnvoTimed tm(m, s, tl.w.t_wgrad, 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
+    HIPCHK(m, launch_wgrad_stem_mx(a, w.wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, t->grads + tl.w.off, s));
+    return PNVO_OK;
+  }
+  WgradArgs a = wgrad_request(m, t, l, B, {.obs = true}, w.dStem);
+  return run_wgrad(m, t, a, tl.w, t->d_ciperm, l.cin, s);
+}
+
+// grad_out: dLoss / dOut, or nullptr with dh_in = dLoss / d(hidden vector) from the caller (the head's gradients are left alone)
+static int train_backward_body(pnvo_handle m, TrainState *t, const float *grad_out, const float *dh_in, bool stop_after_fc, hipStream_t s) {
+  if (t->lastB <= 0 || (!grad_out && !dh_in)) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_forward first");
+  HIPCHK(m, hipSetDevice(m->device));
+  const int B = t->lastB;
+  int rc = PNVO_OK;
+  if (!t->dmax && !m->bottleneck) HIPCHK(m, t->dmax.alloc(m->convs.size() * PNVO_ABSMAX_UINTS));
+  if (t->dmax) HIPCHK(m, hipMemsetAsync(t->dmax, 0, t->dmax.size() * sizeof(unsigned), s));   // maxima of this backward's gradients
+  if (dh_in != nullptr)
+    HIPCHK(m, hipMemcpyAsync(t->ws.dh, dh_in, (size_t)B * m->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
+  else if ((rc = backward_head(m, t, B, grad_out, s)) != PNVO_OK)
+    return rc;
+  if ((rc = backward_hidden(m, t, B, stop_after_fc, s)) != PNVO_OK || stop_after_fc) return rc;
+  float *dY = t->ws.dYa, *dX = t->ws.dYb;
+  if ((rc = backward_compression(m, t, B, dY, s)) != PNVO_OK) return rc;
+  // residual blocks, last to first: m->blocks in reverse (y[blk] is the output of m->blocks[blk - 1])
+  for (size_t blk = m->blocks.size(); blk >= 1; --blk) {
+    if ((rc = backward_block(m, t, blk, B, dY, dX, s)) != PNVO_OK) return rc;
+    std::swap(dY, dX);
+    // leaving residual stage 4 / stage 2: every parameter from that stage's first offset upwards has its final gradient
+    const Block &b = m->blocks[blk - 1];
+    if (t->bucket_first.size() == 3 && b.index == 0 && (b.stage == 4 || b.stage == 2)) report_bucket(t, b.stage == 4 ? 0 : 1, s);
+  }
+  return backward_stem(m, t, B, dY, s);
+}
+
+// One backward of the gradient-ready hook's contract: reset the buckets, run, report what is left.  The end of the backward
+// reports every range not reported on the way (whatever the number of split points a parameter order allowed — with exactly one of
+// them the in-backward reports are skipped and BOTH ranges are due here), latest layers first.
+static int run_backward(pnvo_handle m, const float *grad_out, const float *dh_in, bool stop_after_fc, void *stream) {
+  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  TrainState *t = TS(m);
+  t->bucket_done.assign(t->bucket_first.size(), 0);
+  const int rc = train_backward_body(m, t, grad_out, dh_in, stop_after_fc, (hipStream_t)stream);
+  for (size_t k = 0; rc == PNVO_OK && k < t->bucket_first.size(); ++k) report_bucket(t, k, (hipStream_t)stream);
   return rc;
 }
 
 // The hidden vector of the last pnvo_train_forward (visual_fc's output after its ReLU), [B, hidden] on the device; nullptr before one.
-extern "C++" const float *pnvo_train_hidden(pnvo_handle m) {
-  return m && m->train && TS(m)->lastB > 0 ? TS(m)->hid : nullptr;
-}
+const float *pnvo_train_hidden(pnvo_handle m) { return m && m->train && TS(m)->lastB > 0 ? TS(m)->ws.hid : nullptr; }
 
 // The backward entered BELOW the output head: dh [B, hidden] = dLoss / d(hidden vector) comes from the caller (the navigation policy's
 // recurrent part, policy_train.hip), the head's own gradients are left alone.  stop_after_fc: only visual_fc's weight and bias
 // gradients are written (a frozen visual encoder).
-extern "C++" int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream) {
+int pnvo_train_backward_from_hidden(pnvo_handle m, const float *dh, bool stop_after_fc, void *stream) {
   if (!dh) return pnvo_fail(m, PNVO_ERR_ARG, "null hidden gradient");
-  if (m && m->train) TS(m)->bucket_done.assign(TS(m)->bucket_first.size(), 0);
-  const int rc = train_backward_body(m, nullptr, stream, dh, stop_after_fc);
-  if (rc == PNVO_OK && m->train)
-    for (size_t k = 0; k < TS(m)->bucket_first.size(); ++k) report_bucket(TS(m), k, (hipStream_t)stream);
-  return rc;
+  return run_backward(m, nullptr, dh, stop_after_fc, stream);
 }
 
-static int train_backward_body(pnvo_handle m, const float *grad_out, void *stream, const float *dh_in, bool stop_after_fc) {
-  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
-  TrainState *t = TS(m);
-  g_wgrad_x3 = m->opt.wgrad3;
-  if (t->lastB <= 0 || (!grad_out && !dh_in)) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_forward first");
-  HIPCHK(m, hipSetDevice(m->device));
-  const pnvo_config &c = m->cfg;
-  const int B = t->lastB;
-  hipStream_t s = (hipStream_t)stream;
-  int rc = PNVO_OK;
+extern "C" {
 
-  if (!t->dmax && !m->bottleneck) {
-    HIPCHK(m, t->dmax.alloc(m->convs.size() * PNVO_ABSMAX_UINTS));
+int pnvo_train_attach(pnvo_handle m, float *params, float *grads, size_t n_floats, const pnvo_tensor_desc *toc, int ntoc) {
+  if (!m || !params || !grads || !toc) return pnvo_fail(m, PNVO_ERR_ARG, "null argument");
+  if (!m->loaded) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach before pnvo_load_weights");
+  if (m->grouped_se)
+    return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach: SE / ResNeXt backbones have no backward (the grouped conv and the gate are "
+                                        "inference kernels): these encoders run frozen");
+  if (n_floats >= (1u << 24)) return pnvo_fail(m, PNVO_ERR_ARG, "flat parameter buffer too large for the index maps");
+  HIPCHK(m, hipSetDevice(m->device));
+  pnvo_train_free(m);
+  TrainState *t = new TrainState();
+  m->train = t;
+  auto failed = [&](int rc) {          // a failed attach leaves no training state behind
+    pnvo_train_free(m);
+    return rc;
+  };
+  t->params = params;
+  t->grads = grads;
+  t->n = n_floats;
+  Toc names;
+  for (int k = 0; k < ntoc; ++k) {
+    TocEnt e;
+    e.off = toc[k].offset;
+    e.numel = 1;
+    for (int d = 0; d < toc[k].ndim; ++d) {
+      e.shape.push_back(toc[k].shape[d]);
+      e.numel *= (size_t)toc[k].shape[d];
+    }
+    if (e.off + e.numel > n_floats) return failed(pnvo_fail(m, PNVO_ERR_ARG, std::string("parameter '") + toc[k].name + "' out of range"));
+    names[toc[k].name] = e;
   }
-  if (t->dmax) HIPCHK(m, hipMemsetAsync(t->dmax, 0, m->convs.size() * PNVO_ABSMAX_UINTS * sizeof(unsigned), s));   // maxima of this backward's gradients
-  // ---- output head: out = hid . W2^T + b2  (skipped when the caller supplies dLoss / dhid itself)
-  if (dh_in != nullptr) {
-    HIPCHK(m, hipMemcpyAsync(t->dh, dh_in, (size_t)B * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else {
-    HIPCHK(m, launch_padcopy(grad_out, B, c.out_dim, 8, t->dout8, s));
-    float *gb = gradp(m, t, "output_head.1.bias", &rc);
-    if (!gb) return rc;
-    HIPCHK(m, launch_colsum(grad_out, B, c.out_dim, c.out_dim, gb, s));
-    WgradArgs a = wgrad_args(m->head, B, c.hidden, 8);
-    a.x = t->drop_p > 0.f ? t->hdrop : t->hid;
-    a.dy = t->dout8;
-    a.mode = 0;
-    if ((rc = run_wgrad(m, t, a, "output_head.1.weight", nullptr, c.hidden, s)) != PNVO_OK) return rc;
-    ConvArgs d;
-    std::memset(&d, 0, sizeof(d));
-    d.x = t->dout8;
-    d.wpk = t->head_t;
-    d.y = t->dh;
-    d.B = B;
-    d.H = d.W = d.Ho = d.Wo = 1;
-    d.CIN = 8;
-    d.COUT = c.hidden;
-    d.COUTP = rup(c.hidden, 32);
-    d.KH = d.KW = 1;
-    d.stride = 1;
-    d.up = 1;
-    d.y_cstride = c.hidden;
-    choose_tile(B, d.COUTP, &d.MT, &d.NT);
-    d.slots = conv_slots(1, d.MT);
-    HIPCHK(m, launch_conv(d, s));
-  }
-  // ---- hidden layer: hid = relu(z . W1^T + b1)
-  const size_t icomp = m->comp;
-  {
-    if (t->drop_p > 0.f) {            // dropout backward: the same mask, then the ReLU mask of the un-dropped activation
-      HIPCHK(m, launch_dropout(t->dh, nullptr, nullptr, B, 1, c.hidden, t->drop_p, t->drop_seed, t->drop_step, 1, t->dh, s));
-    }
-    HIPCHK(m, launch_relu_mask(t->dh, t->hid, nullptr, (long)B * c.hidden, t->gh, s));
-    float *gb = gradp(m, t, m->fc.name + ".bias", &rc);
-    if (!gb) return rc;
-    HIPCHK(m, launch_colsum(t->gh, B, c.hidden, c.hidden, gb, s));
-    const ConvSave &sc = t->cs[icomp];
-    WgradArgs a = wgrad_args(m->fc, B, m->comp_c, c.hidden);
-    a.CIN = m->comp_c;
-    a.x = sc.raw;
-    a.in_scale = sc.ss[0];
-    a.in_shift = sc.ss[1];
-    a.dy = t->gh;
-    a.mode = 1;
-    if (t->drop_p > 0.f) {            // the Linear saw the dropped, already activated feature
-      a.x = t->zdrop;
-      a.in_scale = a.in_shift = nullptr;
-      a.mode = 0;
-    }
-    // the activation tensor is channel-padded: tell the kernel the real row pitch through H/W/CIN = (fh, fw, comp_cp)
-    a.CIN = m->comp_cp;
-    wgrad_plan(a);
-    if (c.act_embed) {                // gradient rows are [flat | 32] wide; the embedding columns and rows come from embed_*
-      const int flat = m->comp_c * m->fh * m->fw;
-      a.grad_pitch = t->w1_pitch;
-      HIPCHK(m, launch_embed_backward(t->gh, t->efeat, t->params + t->w1_off, t->w1_pitch, flat, B, c.hidden,
-                                      t->grads + t->w1_off, t->dfeat, s));
-      if (t->drop_p > 0.f)
-        HIPCHK(m, launch_dropout(t->dfeat, nullptr, nullptr, B, 1, 32, t->drop_p, t->drop_seed, t->drop_step, 2, t->dfeat, s));
-      HIPCHK(m, launch_embed_scatter(t->dfeat, t->actions, B, c.n_acts + 1, t->grads + t->emb_off, s));
-    }
-    if ((rc = run_wgrad(m, t, a, m->fc.name + ".weight", nullptr, m->comp_c, s)) != PNVO_OK) return rc;
-    if (stop_after_fc) return PNVO_OK;
-    ConvArgs d;
-    std::memset(&d, 0, sizeof(d));
-    d.x = t->gh;
-    d.wpk = t->fc_t;
-    d.y = t->dz;
-    d.B = B;
-    d.H = d.W = d.Ho = d.Wo = 1;
-    d.CIN = c.hidden;
-    d.COUT = m->fh * m->fw * m->comp_cp;
-    d.COUTP = rup(d.COUT, 32);
-    d.KH = d.KW = 1;
-    d.stride = 1;
-    d.up = 1;
-    d.y_cstride = d.COUT;
-    choose_tile(B, d.COUTP, &d.MT, &d.NT);
-    d.slots = conv_slots(1, d.MT);
-    HIPCHK(m, launch_conv(d, s));
-  }
-  if (t->drop_p > 0.f)
-    HIPCHK(m, launch_dropout(t->dz, nullptr, nullptr, B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed,
-                             t->drop_step, 0, t->dz, s));
-  // ---- compression conv + GroupNorm(1) + ReLU
-  float *dY = t->dYa, *dX = t->dYb;
-  {
-    const Layer &l = m->convs[icomp];
-    if ((rc = run_gn_bwd(m, t, icomp, B, t->dz, 1, t->dz, s)) != PNVO_OK) return rc;   // in place: dz -> dCompRaw
-    WgradArgs a = wgrad_args(l, B, l.cin, l.coutp);
-    a.x = t->y[m->blocks.size()];
-    a.dy = t->dz;
-    a.mode = 0;
-    if ((rc = run_wgrad(m, t, a, l.name + ".weight", nullptr, l.cin, s)) != PNVO_OK) return rc;
-    if ((rc = run_dgrad(m, t, icomp, B, t->dz, dY, false, s)) != PNVO_OK) return rc;
-  }
-  // ---- residual blocks, last to first: m->blocks in reverse (t->y[blk] is the output of m->blocks[blk - 1])
-  for (size_t blk = m->blocks.size(); blk >= 1; --blk) {
-    const Block &b = m->blocks[blk - 1];
-    const int K = b.nconv, *ik = b.conv, id = b.ds;
-    const bool ds = id >= 0;
-    const Layer &c1 = m->convs[ik[0]], &cl = m->convs[ik[K - 1]];
-    const float *xin = t->y[blk - 1];
-    const long nout = (long)B * cl.hout * cl.wout * cl.coutp;
-    const long nin = (long)B * c1.hin * c1.win * c1.cin;
-    // G = dY * (y > 0)
-    HIPCHK(m, launch_relu_mask(dY, t->y[blk], nullptr, nout, t->G, s));
-    // the chain, last conv first: GroupNorm (+ ReLU mask for every conv but the last) <- incoming gradient
-    const float *din = t->G;
-    for (int k = K - 1; k >= 0; --k) {
-      const Layer &ck = m->convs[ik[k]];
-      if ((rc = run_gn_bwd(m, t, ik[k], B, din, k == K - 1 ? 0 : 1, t->dRaw, s)) != PNVO_OK) return rc;
-      WgradArgs a = wgrad_args(ck, B, ck.cin, ck.coutp, k ? 1 : 0);
-      if (k) {                        // the conv saw relu(GN(raw of the previous conv)): recomputed in the fetch
-        const ConvSave &sp = t->cs[ik[k - 1]];
-        a.x = sp.raw;
-        a.in_scale = sp.ss[0];
-        a.in_shift = sp.ss[1];
-        a.mode = 1;
-      } else {
-        a.x = xin;
-        a.mode = 0;
-      }
-      a.dy = t->dRaw;
-      if (a.lds3 == 6 && m->opt.train_pieces == 2 && t->dmax != nullptr && ck.in_bound < 6.0e4f) {
-        a.np = 2;                     // float16 pieces: X inside float16's range (the forward's bound), dY scaled from its maximum
-        a.dy_absmax = t->dmax + ik[k] * PNVO_ABSMAX_UINTS;
-      }
-      if ((rc = run_wgrad(m, t, a, ck.name + ".weight", nullptr, ck.cin, s)) != PNVO_OK) return rc;
-      if ((rc = run_dgrad(m, t, ik[k], B, t->dRaw, k ? t->dA : dX, false, s)) != PNVO_OK) return rc;
-      din = t->dA;
-    }
-    // skip connection
-    if (ds) {
-      const Layer &cd = m->convs[id];
-      if ((rc = run_gn_bwd(m, t, id, B, t->G, 0, t->dRaw, s)) != PNVO_OK) return rc;
-      WgradArgs a = wgrad_args(cd, B, cd.cin, cd.coutp);
-      a.x = xin;
-      a.dy = t->dRaw;
-      a.mode = 0;
-      if ((rc = run_wgrad(m, t, a, cd.name + ".weight", nullptr, cd.cin, s)) != PNVO_OK) return rc;
-      if ((rc = run_dgrad(m, t, id, B, t->dRaw, dX, true, s)) != PNVO_OK) return rc;
-    } else {
-      HIPCHK(m, launch_add(dX, t->G, nin, dX, s));
-    }
-    std::swap(dY, dX);
-    // leaving residual stage 4 / stage 2: every parameter from that stage's first offset upwards has its final gradient
-    if (t->bucket_first.size() == 3) {
-      if (b.stage == 4 && b.index == 0) report_bucket(t, 0, s);
-      if (b.stage == 2 && b.index == 0) report_bucket(t, 1, s);
-    }
-  }
-  // ---- stem: maxpool <- dY, GroupNorm + ReLU, weight gradient (no input gradient)
-  {
-    const Layer &l = m->convs[0];
-    if (m->opt.pool_bwd && l.coutp == l.cout && l.cout % 4 == 0 && l.cout <= 256 && 256 % (l.cout / 4) == 0) {
-      // max-pool backward folded into the stem's GroupNorm backward: the un-pooled gradient is never materialised
-      const ConvSave &cs0 = t->cs[0];
-      float *dg = gradp(m, t, l.gn + ".weight", &rc);
-      if (!dg) return rc;
-      float *db = gradp(m, t, l.gn + ".bias", &rc);
-      if (!db) return rc;
-      PnvoTimed tm(m, s, "gn_bwd", 0.0, 0.0);
-      HIPCHK(m, launch_gn_bwd_pool(cs0.raw, dY, t->pool_idx, m->Hs, m->Ws, m->Hp, m->Wp, cs0.ss[0], cs0.ss[1], cs0.mu, cs0.rstd, l.gamma,
-                                   B, l.cout, l.groups, t->gn_part, t->gn_coef, dg, db, t->dStem, s));
-    } else {
-      HIPCHK(m, launch_maxpool_bwd(dY, t->pool_idx, B, m->Hs, m->Ws, l.coutp, t->dStem, s));
-      if ((rc = run_gn_bwd(m, t, 0, B, t->dStem, 1, t->dStem, s)) != PNVO_OK) return rc;
-    }
-    // option wgrad_stem=fp32: the float32-MFMA kernel; also once an input outside the exact-operand contract was met
-    const bool stem_fp32 = m->opt.wgrad_stem == 1 || m->dense_sticky;
-    if (m->train_mx && l.coutp == 32 && !stem_fp32) {
-      WgradStemMXArgs a;
-      std::memset(&a, 0, sizeof(a));
-      for (int k = 0; k < 4; ++k) a.src[k] = t->src[k];
-      a.dy = t->dStem;
-      a.zero_page = m->zero_page;
-      a.B = B;
-      a.H = c.height;
-      a.W = c.width;
-      a.Ho = m->Hs;
-      a.Wo = m->Ws;
-      wgrad_stem_mx_plan(a);
-      if (wgrad_stem_mx_scratch_floats(a) > t->wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
-      int rc2 = PNVO_OK;
-      float *g = gradp(m, t, l.name + ".weight", &rc2);
-      if (!g) return rc2;
-      PnvoTimed tm(m, s, "wgrad:" + l.name + ".weight", 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
-      HIPCHK(m, launch_wgrad_stem_mx(a, t->wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, g, s));
-      return PNVO_OK;
-    }
-    WgradArgs a = wgrad_args(l, B, 32, l.coutp, 2);
-    a.dy = t->dStem;
-    const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
-    std::vector<float> sc(m->CPL), sh(m->CPL);
-    // the whitening constants are on the device (stem_sc/sh); the kernel wants them per lane: read them back once per
-    // call is a sync — instead pass pointers: lanes load sc/sh from the device table themselves
-    for (int k = 0; k < 32; ++k) {
-      const int tn = k < m->CP ? m->stem_tensor_of_new[k] : -1;
-      a.src[k].base = tn >= 0 ? t->src[tn] : nullptr;
-      a.src[k].nch = tn >= 0 ? nsrc[tn] : 0;
-      a.src[k].choff = tn >= 0 ? m->stem_ch_of_new[k] : 0;
-      a.src[k].sc = 0.f;
-      a.src[k].sh = 0.f;
-    }
-    a.in_scale = m->stem_sc;     // mode 2 reads its per-channel whitening from these device tables
-    a.in_shift = m->stem_sh;
-    if ((rc = run_wgrad(m, t, a, l.name + ".weight", t->d_ciperm, l.cin, s)) != PNVO_OK) return rc;
+  int rc = PNVO_OK;
+  if ((rc = bind_convs(m, t, names)) != PNVO_OK || (rc = bind_linears(m, t, names)) != PNVO_OK || (rc = build_stem_tables(m, t)) != PNVO_OK ||
+      (rc = build_refresh_tables(m, t)) != PNVO_OK)
+    return failed(rc);
+  build_buckets(t, names);
+  rc = pnvo_train_refresh(m, nullptr);
+  return rc == PNVO_OK ? rc : failed(rc);
+}
+
+int pnvo_train_set_grad_hook(pnvo_handle m, pnvo_grad_ready_fn fn, void *user) {
+  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  TS(m)->hook = fn;
+  TS(m)->hook_user = user;
+  return PNVO_OK;
+}
+
+int pnvo_train_grad_buckets(pnvo_handle m, uint64_t *first, uint64_t *count, int cap, int *n_out) {
+  if (!m || !m->train || !n_out) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  TrainState *t = TS(m);
+  *n_out = (int)t->bucket_first.size();
+  size_t end = t->n;
+  for (int k = 0; k < *n_out && k < cap && first && count; ++k) {
+    first[k] = t->bucket_first[k];
+    count[k] = end - t->bucket_first[k];
+    end = t->bucket_first[k];
   }
   return PNVO_OK;
 }
+
+// The operands that follow the flat parameters, rebuilt after every optimiser step.  Only launches: every table was built by attach.
+int pnvo_train_refresh(pnvo_handle m, void *stream) {
+  if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  HIPCHK(m, hipSetDevice(m->device));
+  TrainState *t = TS(m);
+  hipStream_t s = (hipStream_t)stream;
+  m->weights_gen += 1;               // operands derived lazily from the weights (conv_x3) are rebuilt at their next use
+  HIPCHK(m, launch_gather_all(t->params, t->d_segs, t->nseg, t->seg_total, s));
+  if (t->x2_seg) HIPCHK(m, launch_conv_x2_scales(t->params, t->x2_seg, t->x2_rows, t->x2_scale, s));
+  if (!m->bottleneck) {                // GroupNorm bounds of the CURRENT parameters -> host-mapped table (chain_tracked_bounds)
+    // A refresh that is being CAPTURED would bake one ring entry into the graph: every replay rewrites that entry while the host reads
+    // another one behind an event that is never recorded.  So a captured refresh leaves the ring alone and marks every entry unknown
+    // (-1) and restarts the two-refresh lag: chain_tracked_bounds then leaves Layer::in_bound as last chained (the load-time bounds
+    // when nothing was chained yet) instead of reading an entry that no event orders.
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cst) != hipSuccess || cst != hipStreamCaptureStatusNone;
+    if (capturing) {
+      for (int i = 0; i < 3 * t->gnb_n; ++i) t->gnb_host[i] = -1.f;
+      t->gnb_refreshes = 0;
+    } else {
+      const int e = (int)(t->gnb_refreshes % 3);
+      hipLaunchKernelGGL(gn_bound_kernel, dim3((unsigned)t->gnb_n), dim3(64), 0, s, t->params, t->gnb_seg, t->gnb_host + (size_t)e * t->gnb_n);
+      HIPCHK(m, hipGetLastError());
+      HIPCHK(m, hipEventRecord(t->gnb_ev[e], s));
+      t->gnb_refreshes += 1;
+    }
+  }
+  if (m->cfg.act_embed) {      // eval-mode bias rows bias[a][o] = b1[o] + W1[o][flat:] . emb[a]  (pnvo_load_weights does this on the host)
+    const pnvo_config &c = m->cfg;
+    const int rows = c.n_acts + 1, flat = m->comp_c * m->fh * m->fw;
+    int rc = ensure_train_ws(m, t, t->capB > 0 ? t->capB : 1);
+    if (rc != PNVO_OK) return rc;
+    HIPCHK(m, launch_embed_gather(t->params + t->emb_off, nullptr, rows, rows, t->ws.egath, nullptr, s));
+    HIPCHK(m, launch_embed_bias(t->ws.egath, t->params + t->fc.w.off, t->w1_pitch, flat, t->params + t->fc.b.off, rows, c.hidden, m->fc_bias, s));
+  }
+  return refresh_stem_dd(m, t, s);
+}
+
+int pnvo_train_forward(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
+                       const float *run_mean, const float *run_var, float *out, void *stream) {
+  int rc = train_forward_body(m, rgb, depth, dd, tdv, B, run_mean, run_var, out, stream);
+  if (rc != PNVO_OK) return rc;
+  bool rerun = false;                  // an input outside the fused stems' contract: once more on the dense stem (pnvo_api.hip)
+  if ((rc = pnvo_input_fallback(m, (hipStream_t)stream, &rerun)) != PNVO_OK) return rc;
+  return rerun ? train_forward_body(m, rgb, depth, dd, tdv, B, run_mean, run_var, out, stream) : PNVO_OK;
+}
+
+int pnvo_train_backward(pnvo_handle m, const float *grad_out, void *stream) { return run_backward(m, grad_out, nullptr, false, stream); }
 
 int pnvo_train_set_dropout(pnvo_handle m, float p, uint64_t seed) {
   if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
@@ -1329,7 +1276,7 @@ int pnvo_input_moments(pnvo_handle m, const float *rgb, const float *depth, cons
   a.center = center;
   a.npix = (long)B * c.height * c.width;
   a.pw = power;
-  HIPCHK(m, launch_moments(a, m->C, t->mom_part, out, (hipStream_t)stream));
+  HIPCHK(m, launch_moments(a, m->C, t->ws.mom_part, out, (hipStream_t)stream));
   return PNVO_OK;
 }
 

@@ -120,7 +120,9 @@ def test_conv_x3_agrees_with_the_fp32_kernels_at_odd_sizes():
 TRAIN_KNOBS = [{"PNVO_CONV": "x3"}, {"PNVO_WGRAD_STEM": "fp32"}, {"PNVO_WGRAD": "lds9"}, {"PNVO_WGRAD": "generic"},
                # the exact fallbacks of the training step: three bf16 pieces (forward + backward), 3x3 weight gradients on the fp32 pipe
                {"PNVO_CONV": "x3", "PNVO_TRAIN_PIECES": "3"}, {"PNVO_CONV": "x3", "PNVO_WGRAD3": "fp32"},
-               {"PNVO_CONV": "x3", "PNVO_TRAIN_PIECES": "3", "PNVO_WGRAD3": "fp32"}]
+               {"PNVO_CONV": "x3", "PNVO_TRAIN_PIECES": "3", "PNVO_WGRAD3": "fp32"},
+               # the other forms of the backward-data and pool-backward branches: masked-tap stride-2 convs, un-fused max-pool backward
+               {"PNVO_DGRAD": "masked"}, {"PNVO_POOL_BWD": "separate"}, {"PNVO_CONV": "x3", "PNVO_DGRAD": "masked"}]
 
 
 @pytest.mark.parametrize("env", TRAIN_KNOBS, ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
