@@ -2,6 +2,7 @@
 // Host-side only; every kernel lives in conv_mfma.hip / elementwise.hip.  gfx950 only, no fallbacks.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -263,11 +264,11 @@ void free_workspace(pnvo_model_s *m) {
 }
 
 // 3x3 (stride 1 or 2, pad 1) GroupNorm-ed convs run on conv_x3.hip unless option `conv` selects another kernel family
-bool x3_layer(pnvo_handle m, const Layer &l) {
-  const bool s2 = l.stride == 2 && m->opt.x3_s2;
+bool x3_layer(const PnvoOptions &o, const Layer &l) {
+  const bool s2 = l.stride == 2 && o.x3_s2;
   const bool k3 = l.k == 3 && l.kw == 3 && l.pad == 1 && (l.stride == 1 || s2);
   const bool k1 = l.k == 1 && l.kw == 1 && l.pad == 0 && s2;      // the 1x1 stride-2 downsample convs (resnet.py:192-195)
-  return (k3 || k1) && l.cgroups == 1 && !l.host_w.empty() && m->opt.conv <= 1;
+  return (k3 || k1) && l.cgroups == 1 && !l.host_w.empty() && o.conv <= 1;
 }
 // operand pieces of conv_x3: two float16 pieces (three product terms) when the layer's input is provably inside float16's range and
 // option pieces (train_pieces with a training step attached, whose device-side re-pack needs the weight's scale) asks for them;
@@ -307,17 +308,17 @@ double conv_bytes(const Layer &l, int B) {
 // output geometry (they always do: resnet.py:189-212), in the inference and the training forward alike (the training forward still
 // writes the block input: its backward pass reads it), and not while a tap wants the plain schedule.  (c1's side — 3x3, stride 2, two
 // float16 pieces — is the plan's to refuse: conv_x3_plan.)
-bool ride_fits(pnvo_handle m, const Layer &c1, const Layer &cd) {
-  if (!m->opt.ds_fuse || m->tap_dst != nullptr || m->bottleneck || cd.k != 1 || cd.kw != 1 || cd.stride != 2 || cd.pad != 0) return false;
+bool ride_fits(pnvo_handle m, const PnvoOptions &o, const Layer &c1, const Layer &cd) {
+  if (!o.ds_fuse || m->tap_dst != nullptr || m->bottleneck || cd.k != 1 || cd.kw != 1 || cd.stride != 2 || cd.pad != 0) return false;
   if (c1.cinp != cd.cinp || c1.coutp != cd.coutp || c1.cout != cd.cout || c1.hout != cd.hout || c1.wout != cd.wout || c1.hin != cd.hin ||
       c1.win != cd.win || c1.cout != c1.coutp || c1.groups != cd.groups || cd.host_w.empty())
     return false;
-  return x3_layer(m, cd) && x3_two_pieces(m, cd);
+  return x3_layer(o, cd) && x3_two_pieces(m, cd);
 }
-}  // namespace
 
-// Which kernel family runs conv l at B samples for this ask, and what follows from that.  The one place that decides it.
-ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk &ask) {
+// Which kernel family runs conv l at B samples for this ask under options o, and what follows from that.  The one place that decides
+// it: a forward asks with the handle's options (pnvo_conv_choice), the workspace with copies that select each family (stats_floats).
+ConvChoice conv_choice(pnvo_handle m, const PnvoOptions &o, const Layer &l, int B, const ConvAsk &ask) {
   ConvChoice c;
   const int P = l.hout * l.wout;
   c.flops = conv_flops(l, B);
@@ -330,7 +331,7 @@ ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk 
   // GroupNorm-ed 3x3 and 1x1 stride-2 convs: float32 results from the 16-bit matrix cores (conv_x3.hip) where its planner takes the
   // launch; option conv=fp32 keeps the fp32-MFMA kernels.
   const bool dense_gn = ask.gn && !ask.plain;
-  if (dense_gn && l.groups > 0 && x3_layer(m, l) && (ask.ride == nullptr || ride_fits(m, l, *ask.ride))) {
+  if (dense_gn && l.groups > 0 && x3_layer(o, l) && (ask.ride == nullptr || ride_fits(m, o, l, *ask.ride))) {
     // The schedule's rule, kept as it stood before this value existed: forward_body, the training forward and pnvo_layer_kernel decide
     // tails, rides and the small-generic pre-pass per LAYER, before a stager mode is known, so they ask about the tile kernels on the
     // plain stager (a default ask: mode 0) with the rows form off.  Only the launch's own ask (conv_ask: rows_form) lets
@@ -341,8 +342,8 @@ ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk 
     ConvX3Problem q{.B = B, .H = l.hin, .W = l.win, .CIN = l.cinp, .Ho = l.hout, .Wo = l.wout, .COUTP = l.coutp, .ks = l.k, .stride = l.stride,
                     .np = x3_two_pieces(m, l) ? 2 : 3, .mode = ask.tail == ConvAsk::KEYS ? 3 : ask.tail != ConvAsk::NONE ? 2 : ask.affine ? 1 : 0,
                     .tail_scaled = ask.tail == ConvAsk::SKIP_SCALED, .ds = ask.ride != nullptr};
-    q.opt = {.force = m->opt.conv == 1, .strip = m->opt.x3_strip, .fine = m->opt.x3_fine, .w8 = m->opt.x3_w8, .m16 = m->opt.x3_m16,
-             .ksw = m->opt.x3_ksplit, .persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0, .rows = tile_kernels_only ? 0 : m->opt.x3_rows,
+    q.opt = {.force = o.conv == 1, .strip = o.x3_strip, .fine = o.x3_fine, .w8 = o.x3_w8, .m16 = o.x3_m16,
+             .ksw = o.x3_ksplit, .persist_wgs = o.x3_persist ? 3 * m->num_cus : 0, .rows = tile_kernels_only ? 0 : o.x3_rows,
              .num_cus = m->num_cus};
     if (const ConvX3Plan p = conv_x3_plan(q)) {
       c.family = ConvChoice::X3;
@@ -359,10 +360,19 @@ ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk 
   ConvArgs a;
   conv_geometry(l, B, l.coutp, a);
   choose_tile((long)B * P, l.coutp, &c.MT, &c.NT);
-  const bool lds = dense_gn && m->opt.conv != 3 && conv3_lds_supported(a);
+  const bool lds = dense_gn && o.conv != 3 && conv3_lds_supported(a);
   c.family = lds ? ConvChoice::FP32_LDS : ConvChoice::FP32_GENERIC;
   c.slots = lds ? conv3_lds_slots(a) : conv_slots(P, c.MT);
   return c;
+}
+}  // namespace
+
+ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk &ask) { return conv_choice(m, m->opt, l, B, ask); }
+
+// Does block b's downsample conv ride on the launch of its first conv at B samples?  Only a two-conv block carries a ride (ride_fits
+// refuses Bottleneck models; said here for the walks that serve both block kinds); the rest is the conv choice's to say.
+bool pnvo_ds_rides(pnvo_handle m, const Block &b, int B) {
+  return b.ds >= 0 && b.nconv == 2 && pnvo_conv_choice(m, m->convs[b.conv[0]], B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
 }
 
 bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B) {
@@ -374,11 +384,10 @@ namespace {
 // GroupNorm partials of l at B samples: the most slots of the families an option change can select without the workspace regrowing
 // (generic, LDS, the forced tile plan — stride 2 included —, group)
 size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
-  const PnvoOptions saved = m->opt;
+  PnvoOptions o = m->opt;
   int slots = 0;
-  m->opt.x3_s2 = 1;
-  for (m->opt.conv = 1; m->opt.conv <= 3; ++m->opt.conv) slots = std::max(slots, pnvo_conv_choice(m, l, B, {}).slots);   // x3 | fp32 | generic
-  m->opt = saved;
+  o.x3_s2 = 1;
+  for (o.conv = 1; o.conv <= 3; ++o.conv) slots = std::max(slots, conv_choice(m, o, l, B, {}).slots);   // x3 | fp32 | generic
   return (size_t)B * (size_t)slots * l.coutp * 2;
 }
 
@@ -1171,6 +1180,59 @@ int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun) {
 namespace {
 int forward_dispatch(pnvo_handle m, int B, const FwdRequest &r);
 int forward_body(pnvo_handle m, int B, const FwdRequest &r);
+
+// Do the pair tensors / the sensor frames a caller handed over match the model's observation space?
+bool pairs_match(const pnvo_config &c, const float *rgb, const float *depth, const float *dd, const float *tdv) {
+  return (c.n_rgb > 0) == (rgb != nullptr) && (c.n_depth > 0) == (depth != nullptr) && (c.n_dd > 0) == (dd != nullptr) &&
+         (c.n_tdv > 0) == (tdv != nullptr);
+}
+bool frames_match(const pnvo_config &c, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv) {
+  return (c.n_rgb > 0) == (rgb_frames != nullptr) && !((c.n_depth > 0 || c.n_dd > 0) && depth_frames == nullptr) &&
+         (c.n_tdv > 0) == (tdv != nullptr);
+}
+// The entry checks of a single-handle forward in their order: handle, weights, batch / output, then what `inputs_match` says of the inputs
+int check_entry(pnvo_handle m, const char *entry, int B, const void *out, bool inputs_match, const char *inputs) {
+  if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
+  if (!m->loaded) return fail(m, PNVO_ERR_STATE, std::string(entry) + " before pnvo_load_weights");
+  if (B <= 0 || !out) return fail(m, PNVO_ERR_ARG, "bad batch / null output");
+  if (!inputs_match) return fail(m, PNVO_ERR_ARG, std::string(inputs) + " do not match the model's observation_space");
+  return PNVO_OK;
+}
+int check_pairs(pnvo_handle m, const char *entry, const float *rgb, const float *depth, const float *dd, const float *tdv, int B, const void *out) {
+  return check_entry(m, entry, B, out, !m || pairs_match(m->cfg, rgb, depth, dd, tdv), "observation tensors");
+}
+int check_frames(pnvo_handle m, const char *entry, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, int B, const void *out) {
+  return check_entry(m, entry, B, out, !m || frames_match(m->cfg, rgb_frames, depth_frames, tdv), "sensor frames");
+}
+
+// ... of the two handles of a dual forward, up to the inputs
+int check_dual(pnvo_handle ha, pnvo_handle hb, const char *entry, int B, const void *out_a, const void *out_b) {
+  if (!ha || !hb) return fail(ha, PNVO_ERR_ARG, "null handle");
+  if (!ha->loaded || !hb->loaded) return fail(ha, PNVO_ERR_STATE, std::string(entry) + " before pnvo_load_weights");
+  if (B <= 0 || !out_a || !out_b) return fail(ha, PNVO_ERR_ARG, "bad batch / null output");
+  if (ha->precision != 1 || hb->precision != 1)
+    return fail(ha, PNVO_ERR_STATE, std::string(entry) + " runs the bfloat16 path: call pnvo_set_precision(h, 1) on both models");
+  if (std::memcmp(&ha->cfg, &hb->cfg, sizeof(pnvo_config)) != 0 || ha->device != hb->device)
+    return fail(ha, PNVO_ERR_ARG, "the two models of a dual forward must share architecture and device");
+  return PNVO_OK;
+}
+
+// precision == 1: one model on the bfloat16 path
+int forward_bf16_one(pnvo_handle m, int B, const FwdRequest &r) {
+  float *outs[1] = {r.out};
+  return pnvo_forward_bf16(&m, 1, B, r, outs);
+}
+
+// Size the workspace, run the forward (through the graph cache where the entry allows it) and, where a stem left its contract event
+// pending, wait for it and run again on the dense stem when the input broke the contract.
+int run_forward(pnvo_handle m, int B, const FwdRequest &r, bool graphs_allowed) {
+  int (*const run)(pnvo_handle, int, const FwdRequest &) = graphs_allowed ? forward_dispatch : forward_body;
+  int rc = ensure_workspace(m, B);
+  if (rc != PNVO_OK || (rc = run(m, B, r)) != PNVO_OK) return rc;
+  bool rerun = false;
+  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
+  return rerun ? run(m, B, r) : PNVO_OK;
+}
 }
 
 
@@ -1554,20 +1616,11 @@ int pnvo_set_precision(pnvo_handle h, int precision) {
 
 int pnvo_forward_dual(pnvo_handle ha, pnvo_handle hb, const float *rgb, const float *depth, const float *dd, const float *tdv,
                       int B, float *out_a, float *out_b, void *stream) {
-  if (!ha || !hb) return fail(ha, PNVO_ERR_ARG, "null handle");
-  if (!ha->loaded || !hb->loaded) return fail(ha, PNVO_ERR_STATE, "pnvo_forward_dual before pnvo_load_weights");
-  if (B <= 0 || !out_a || !out_b) return fail(ha, PNVO_ERR_ARG, "bad batch / null output");
-  if (ha->precision != 1 || hb->precision != 1)
-    return fail(ha, PNVO_ERR_STATE, "pnvo_forward_dual runs the bfloat16 path: call pnvo_set_precision(h, 1) on both models");
-  if (std::memcmp(&ha->cfg, &hb->cfg, sizeof(pnvo_config)) != 0 || ha->device != hb->device)
-    return fail(ha, PNVO_ERR_ARG, "the two models of a dual forward must share architecture and device");
+  if (int rc0 = check_dual(ha, hb, "pnvo_forward_dual", B, out_a, out_b)) return rc0;
   if (ha->cfg.act_embed)
     return fail(ha, PNVO_ERR_ARG, "pnvo_forward_dual covers the separate-action models (act_left_right_inv_joint); act-embed "
                                   "models take their actions through pnvo_forward");
-  const pnvo_config &c = ha->cfg;
-  if ((c.n_rgb > 0) != (rgb != nullptr) || (c.n_depth > 0) != (depth != nullptr) || (c.n_dd > 0) != (dd != nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(ha, PNVO_ERR_ARG, "observation tensors do not match the model's observation_space");
+  if (!pairs_match(ha->cfg, rgb, depth, dd, tdv)) return fail(ha, PNVO_ERR_ARG, "observation tensors do not match the model's observation_space");
   if (int rc0 = pnvo_check_inputs(ha)) return rc0;
   HIPCHK(ha, hipSetDevice(ha->device));
   pnvo_handle hs[2] = {ha, hb};
@@ -1606,28 +1659,12 @@ int pnvo_check_inputs(pnvo_handle m) {
 
 int pnvo_forward(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
                  const int64_t *actions, int B, float *out, void *stream) {
-  if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
-  if (!m->loaded) return fail(m, PNVO_ERR_STATE, "pnvo_forward before pnvo_load_weights");
-  if (B <= 0 || !out) return fail(m, PNVO_ERR_ARG, "bad batch / null output");
-  const pnvo_config &c = m->cfg;
-  if ((c.n_rgb > 0) != (rgb != nullptr) || (c.n_depth > 0) != (depth != nullptr) || (c.n_dd > 0) != (dd != nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(m, PNVO_ERR_ARG, "observation tensors do not match the model's observation_space");
-  if (c.act_embed && !actions) return fail(m, PNVO_ERR_ARG, "act_embed model needs actions");
+  if (int rc0 = check_pairs(m, "pnvo_forward", rgb, depth, dd, tdv, B, out)) return rc0;
+  if (m->cfg.act_embed && !actions) return fail(m, PNVO_ERR_ARG, "act_embed model needs actions");
   if (int rc0 = pnvo_check_inputs(m)) return rc0;
   HIPCHK(m, hipSetDevice(m->device));
   const FwdRequest r{.src = {rgb, depth, dd, tdv}, .actions = actions, .out = out, .s = (hipStream_t)stream};
-  if (m->precision == 1) {
-    pnvo_handle hs[1] = {m};
-    float *outs[1] = {out};
-    return pnvo_forward_bf16(hs, 1, B, r, outs);
-  }
-  int rc = ensure_workspace(m, B);
-  if (rc != PNVO_OK) return rc;
-  if ((rc = forward_dispatch(m, B, r)) != PNVO_OK) return rc;
-  bool rerun = false;
-  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
-  return rerun ? forward_dispatch(m, B, r) : PNVO_OK;
+  return m->precision == 1 ? forward_bf16_one(m, B, r) /* before any float32 workspace is sized */ : run_forward(m, B, r, true);
 }
 
 namespace {
@@ -1648,16 +1685,16 @@ int forward_dispatch(pnvo_handle m, int B, const FwdRequest &r) {
   const void *key[8] = {r.src[0], r.src[1], r.src[2], r.src[3], r.actions, r.raw.rgb, r.raw.depth, r.raw.err};   // (pnvo_set_option drops the captured graphs)
   const StemPlan sp = pnvo_stem_plan(m, false, r.raw);
   const size_t out_bytes = (size_t)B * c.out_dim * sizeof(float);
-  for (auto &g : m->graphs)
-    if (g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0) {
-      g.stamp = ++m->graph_clock;
-      HIPCHK(m, hipGraphLaunch(g.exec, s));
-      HIPCHK(m, hipMemcpyAsync(r.out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
-      return pnvo_mark_stem(m, s, sp);
-    }
-  bool again = false;                              // capture only call shapes that come back
-  for (auto &g : m->seen) again = again || (g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0);
-  if (!again) {
+  auto find = [&](std::vector<pnvo_model_s::GraphEntry> &v) {
+    return std::find_if(v.begin(), v.end(), [&](const pnvo_model_s::GraphEntry &g) { return g.B == B && std::memcmp(g.key, key, sizeof(key)) == 0; });
+  };
+  if (auto g = find(m->graphs); g != m->graphs.end()) {
+    g->stamp = ++m->graph_clock;
+    HIPCHK(m, hipGraphLaunch(g->exec, s));
+    HIPCHK(m, hipMemcpyAsync(r.out, m->out_ws, out_bytes, hipMemcpyDeviceToDevice, s));
+    return pnvo_mark_stem(m, s, sp);
+  }
+  if (find(m->seen) == m->seen.end()) {            // capture only call shapes that come back
     pnvo_model_s::GraphEntry sn;
     std::memset(&sn, 0, sizeof(sn));
     std::memcpy(sn.key, key, sizeof(key));
@@ -1705,14 +1742,28 @@ bool fc_rows_usable(pnvo_handle m, int B, const FwdRequest &r);
 int run_fc_rows(pnvo_handle m, pnvo_handle const *grp, const int *end, int ng, int B, const float *comp_raw, const float *sc, const float *sh,
                 const FwdRequest &r);
 
-int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
+// A raw conv output and the scale / shift pair of the GroupNorm that follows it: what the next conv, the gate or the block tail reads.
+struct RawGn {
+  float *x;
+  float *const *ss;
+};
+
+// What the steps of a float32 forward hand on.
+struct FwdState {
+  float *cur, *nxt;          // the block input / where the next block output goes
+  bool have_keys = false;    // `nxt` holds pooled stem keys: the first conv of the first block decodes them and writes `cur`
+  bool have_tail = false;    // the last block's tail relu(GN(rawB) + skip) is still to be applied, by the stager of the next conv
+  BlockTail tail{};
+  bool done = false;         // the persistent small-batch launch ran everything behind the stem
+};
+
+// (a4-a7) stem + max-pool.  Input assembly, /255 and whitening are fused into the stem kernel's operand fetch (pnvo_run_stem): the
+// [B,H,W,30] tensor of the reference (vo_cnn.py:174-176) is only materialised for the "input" tap.
+int forward_stem(pnvo_handle m, int B, const FwdRequest &r, FwdState &st) {
   const pnvo_config &c = m->cfg;
-  const GroupedFwd *grp = r.grp;
   hipStream_t s = r.s;
   int rc = PNVO_OK;
-  // (a4+a5+a6) input assembly + /255 + whitening are fused into the stem kernel's operand fetch (pnvo_run_stem): the
-  // [B,H,W,30] tensor of the reference (vo_cnn.py:174-176) is never materialised.
-  if (m->tap_dst != nullptr && m->tap_name == "input") {   // introspection only: materialise it for the tap
+  if (m->tap_dst != nullptr && m->tap_name == "input") {
     AssembleArgs a;
     for (int k = 0; k < 4; ++k) a.src[k] = r.src[k];
     a.nsrc[0] = c.n_rgb;
@@ -1730,178 +1781,164 @@ int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
     if ((rc = maybe_tap(m, "input", m->xin, (size_t)B * c.height * c.width * m->CP, s)) != PNVO_OK) return rc;
   }
   const Layer &stem = m->convs[0];
-  // (a7) GN + ReLU + maxpool.  Default: no pass at all — the stem writes pooled order-preserving keys (stem_mx.hip POOL), the
-  // first block's first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs
-  // (conv_x3 MODE 3).  PNVO_POOL=separate, taps, Bottleneck models and the other stem kernels keep the pass.
-  float *cur = m->bufY[0], *nxt = m->bufY[1];
+  // GN + ReLU + maxpool.  Default: no pass at all — the stem writes pooled order-preserving keys (stem_mx.hip POOL), the first block's
+  // first conv decodes / normalises them while staging and writes the pooled activations the skip branch needs (conv_x3 MODE 3).
+  // PNVO_POOL=separate, taps, Bottleneck models and the other stem kernels keep the pass.
   const StemPlan sp = pnvo_stem_plan(m, false, r.raw);
-  const bool pool_fused = !m->bottleneck && sp.pools() && m->opt.pool && stem.coutp == stem.cout &&
-                          pnvo_conv_takes_tail(m, m->convs[m->blocks[0].conv[0]], B);
+  st.have_keys = !m->bottleneck && sp.pools() && m->opt.pool && stem.coutp == stem.cout &&
+                 pnvo_conv_takes_tail(m, m->convs[m->blocks[0].conv[0]], B);
+  StemRequest sr{.src = {r.src[0], r.src[1], r.src[2], r.src[3]}, .raw = r.raw, .y = m->stem_raw, .ss = m->ssA, .grp = r.grp, .s = s};
   // Batches of the navigation loop (one or two pairs): everything behind the stem conv is ONE persistent launch (smallnet.hip),
   // which also reduces the stem's GroupNorm statistics itself.
-  const bool small = !pool_fused && sp.writes_slots() && !r.stop_after_compression && pnvo_small_usable(m, B);
-  StemRequest sr{.src = {r.src[0], r.src[1], r.src[2], r.src[3]}, .raw = r.raw, .y = m->stem_raw, .ss = m->ssA, .grp = grp, .s = s};
-  if (small) {
+  if (!st.have_keys && sp.writes_slots() && !r.stop_after_compression && pnvo_small_usable(m, B)) {
     int stem_slots = 0;
     sr.slots_out = &stem_slots;
     sr.skip_finalize = true;
+    st.done = true;
     if ((rc = pnvo_run_stem(m, B, sr)) != PNVO_OK) return rc;
     return pnvo_small_forward(m, B, r, stem_slots);
   }
-  if (pool_fused) {
+  if (st.have_keys) {
     Timed t(m, s, "pool_init", 0.0, 4.0 * B * m->Hp * m->Wp * stem.coutp);
-    HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
-    sr.pool_keys = reinterpret_cast<int *>(nxt);
+    HIPCHK(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st.nxt), STEM_POOL_INIT, (size_t)B * m->Hp * m->Wp * stem.coutp, s));
+    sr.pool_keys = reinterpret_cast<int *>(st.nxt);
   }
   if ((rc = pnvo_run_stem(m, B, sr)) != PNVO_OK) return rc;
   if ((rc = maybe_tap(m, "stem_conv", m->stem_raw, (size_t)B * m->Hs * m->Ws * stem.coutp, s)) != PNVO_OK) return rc;
-  if (!pool_fused) {
+  if (!st.have_keys) {
     Timed t(m, s, "gn_relu_maxpool", 0.0, 4.0 * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * stem.coutp);
-    HIPCHK(m, launch_gn_relu_maxpool(m->stem_raw, m->ssA[0], m->ssA[1], B, m->Hs, m->Ws, stem.coutp, cur, s));
+    HIPCHK(m, launch_gn_relu_maxpool(m->stem_raw, m->ssA[0], m->ssA[1], B, m->Hs, m->Ws, stem.coutp, st.cur, s));
   }
-  if ((rc = maybe_tap(m, "maxpool", cur, (size_t)B * m->Hp * m->Wp * stem.coutp, s)) != PNVO_OK) return rc;
+  return maybe_tap(m, "maxpool", st.cur, (size_t)B * m->Hp * m->Wp * stem.coutp, s);
+}
 
-  // (a8) residual stages
-  BlockTail tail{};
-  bool have_tail = false, have_keys = pool_fused;
+// (a8) residual stages: per block a chain of nconv convs (BasicBlock 2, resnet.py:29-55; Bottleneck 3, :58-117), each reading the raw
+// output of the one before through its GroupNorm pair, then the SE gate, the skip branch and the tail.  Raw outputs: rawA, (rawC,) rawB
+// in chain order, pairs ssA / ssB in turn; the downsample conv's in rawD / ssD.
+int forward_blocks(pnvo_handle m, int B, const FwdRequest &r, FwdState &st) {
+  hipStream_t s = r.s;
+  int rc = PNVO_OK;
   for (size_t bk = 0; bk < m->blocks.size(); ++bk) {
     const Block &b = m->blocks[bk];
+    const int K = b.nconv;
     const bool ds = b.ds >= 0;
-    if (m->bottleneck) {                           // conv1x1 -> GN -> ReLU -> conv3x3(s) -> GN -> ReLU -> conv1x1 -> GN
-      const Layer &b1 = m->convs[b.conv[0]];
-      const Layer &b2 = m->convs[b.conv[1]];
-      const Layer &b3 = m->convs[b.conv[2]];
-      if ((rc = pnvo_run_conv(m, b1, B, {.x = cur, .y = m->rawA, .y_cstride = b1.coutp, .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK ||
-          (rc = pnvo_run_conv(m, b2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawC, .y_cstride = b2.coutp,
-                                         .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK ||
-          (rc = pnvo_run_conv(m, b3, B, {.x = m->rawC, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawB, .y_cstride = b3.coutp,
-                                         .ss = m->ssA, .grp = grp, .s = s})) != PNVO_OK)
-        return rc;
-      const long Pb = (long)b3.hout * b3.wout;
-      // SE block: out = se(out) * out (resnet.py:131-140) — the gate scales the last GroupNorm's scale / shift pair, the tail is unchanged
-      float *const *ss3 = m->ssA;
-      if (b.se_r > 0) {
-        if (b3.cout != b3.coutp) return fail(m, PNVO_ERR_STATE, "SE block " + b.tap + " on a channel-padded map");
-        Timed t(m, s, "se_gate:" + b.tap, 2.0 * B * (2.0 * b.se_r + (double)Pb) * b3.cout, 4.0 * B * Pb * b3.cout);
-        HIPCHK(m, launch_se_gate({.x = m->rawB, .scale = m->ssA[0], .shift = m->ssA[1], .w1 = b.se_w1, .b1 = b.se_b1, .w2 = b.se_w2,
-                                  .b2 = b.se_b2, .out_scale = m->ssE[0], .out_shift = m->ssE[1], .B = B, .P = (int)Pb, .C = b3.cout,
-                                  .R = b.se_r}, s));
-        ss3 = m->ssE;
-      }
-      if (ds && (rc = pnvo_run_conv(m, m->convs[b.ds], B, {.x = cur, .y = m->rawD, .y_cstride = m->convs[b.ds].coutp, .ss = m->ssD, .grp = grp,
-                                                           .s = s})) != PNVO_OK)
-        return rc;
-      {
-        Timed t(m, s, "residual", 0.0, 12.0 * B * Pb * b3.coutp);
-        HIPCHK(m, launch_residual(m->rawB, ss3[0], ss3[1], ds ? m->rawD : cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, B, Pb, b3.coutp,
-                                  nxt, s));
-      }
-      std::swap(cur, nxt);
-      if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * Pb * b3.coutp, s)) != PNVO_OK) return rc;
-      continue;
-    }
-    const Layer &c1 = m->convs[b.conv[0]];
-    const Layer &c2 = m->convs[b.conv[1]];
-    // the block's downsample conv rides on c1's launch (conv_x3_kernel DSF): no launch, no finalisation of its own, and in the
-    // block-tail mode the block input is not written to HBM at all — c1 and the downsample conv are its only readers
-    const bool ds_ride = ds && !have_keys && pnvo_conv_choice(m, c1, B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
+    // The block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF): no launch, no finalisation of its own.  Not
+    // while pooled keys are pending: the key-decoding stager has no riding form.
+    const bool ds_ride = !st.have_keys && pnvo_ds_rides(m, b, B);
     const DsRide ride{ds_ride ? &m->convs[b.ds] : nullptr, m->rawD, m->ssD, nullptr, nullptr};
-    if (have_keys) {           // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
-      BlockTail ktail{nullptr, nullptr, nullptr, cur};
-      if ((rc = pnvo_run_conv(m, c1, B, {.x = nxt, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawA, .y_cstride = c1.coutp,
-                                         .ss = m->ssA, .tail = &ktail, .grp = grp, .s = s})) != PNVO_OK)
-        return rc;
-      have_keys = false;
-    } else if (have_tail) {    // the previous block's tail rides on this conv's stager, which also writes the block output
-      if (ds_ride) tail.out = nullptr;                       // (nobody else reads this block's input)
-      if ((rc = pnvo_run_conv(m, c1, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->rawA, .y_cstride = c1.coutp,
-                                         .ss = m->ssA, .tail = &tail, .ride = ds_ride ? &ride : nullptr, .grp = grp, .s = s})) != PNVO_OK)
-        return rc;
-      std::swap(cur, nxt);
-      have_tail = false;
-    } else if ((rc = pnvo_run_conv(m, c1, B, {.x = cur, .y = m->rawA, .y_cstride = c1.coutp, .ss = m->ssA, .ride = ds_ride ? &ride : nullptr,
-                                              .grp = grp, .s = s})) != PNVO_OK) {
-      return rc;
-    }
-    const long P = (long)c2.hout * c2.wout;
-    const bool c2_small_generic = pnvo_conv_choice(m, c2, B, {}).family == ConvChoice::FP32_GENERIC && (size_t)B * P * c2.cinp * 4 <= ((size_t)48 << 20);
-    if (c2_small_generic) {
-      // small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one streaming
-      // pass over the (L2-sized) tensor, so normalise once and run the conv on final activations
-      // (scratch: rawD — unless the downsample conv rode on c1 and its output already sits there; `nxt` is free until the block tail)
-      float *napp = ds_ride ? nxt : m->rawD;
-      {
-        Timed t(m, s, "gn_relu_apply", 0.0, 8.0 * B * P * c2.cinp);
-        HIPCHK(m, launch_apply_ss_relu(m->rawA, m->ssA[0], m->ssA[1], B, P, c2.cinp, napp, s));
+    const BlockTail ktail{nullptr, nullptr, nullptr, st.cur};
+    RawGn last{nullptr, nullptr};
+    for (int k = 0; k < K; ++k) {
+      const Layer &ck = m->convs[b.conv[k]];
+      const RawGn out{k == K - 1 ? m->rawB : k == 0 ? m->rawA : m->rawC, k % 2 ? m->ssB : m->ssA};
+      ConvRequest q{.y = out.x, .y_cstride = ck.coutp, .ss = out.ss, .grp = r.grp, .s = s};
+      const long P = (long)ck.hout * ck.wout;
+      if (k == 0 && st.have_keys) {     // pooled stem keys in `nxt`: decoded + normalised by this conv's stager, activations -> `cur`
+        q.x = st.nxt, q.in_scale = m->ssA[0], q.in_shift = m->ssA[1], q.tail = &ktail;
+      } else if (k == 0 && st.have_tail) {   // the previous block's tail rides on this conv's stager, which also writes the block output
+        // with a ride in tail mode the block input is not written to HBM at all: this conv and the downsample conv are its only readers
+        if (ds_ride) st.tail.out = nullptr;
+        q.x = m->rawB, q.in_scale = m->ssB[0], q.in_shift = m->ssB[1], q.tail = &st.tail, q.ride = ds_ride ? &ride : nullptr;
+      } else if (k == 0) {
+        q.x = st.cur, q.ride = ds_ride ? &ride : nullptr;
+      } else if (K == 2 && pnvo_conv_choice(m, ck, B, {}).family == ConvChoice::FP32_GENERIC && (size_t)B * P * ck.cinp * 4 <= ((size_t)48 << 20)) {
+        // Second conv of a BasicBlock, small deep stage on the generic kernel: its per-tap GroupNorm+ReLU prologue costs more than one
+        // streaming pass over the (L2-sized) tensor, so normalise once and run the conv on final activations.  Scratch: rawD — unless
+        // the downsample conv rode and its output already sits there; `nxt` is free until the block tail.
+        float *napp = ds_ride ? st.nxt : m->rawD;
+        Timed t(m, s, "gn_relu_apply", 0.0, 8.0 * B * P * ck.cinp);
+        HIPCHK(m, launch_apply_ss_relu(last.x, last.ss[0], last.ss[1], B, P, ck.cinp, napp, s));
+        q.x = napp;
+      } else {
+        q.x = last.x, q.in_scale = last.ss[0], q.in_shift = last.ss[1];
       }
-      if ((rc = pnvo_run_conv(m, c2, B, {.x = napp, .y = m->rawB, .y_cstride = c2.coutp, .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK)
-        return rc;
-    } else if ((rc = pnvo_run_conv(m, c2, B, {.x = m->rawA, .in_scale = m->ssA[0], .in_shift = m->ssA[1], .y = m->rawB, .y_cstride = c2.coutp,
-                                              .ss = m->ssB, .grp = grp, .s = s})) != PNVO_OK) {
-      return rc;
+      if ((rc = pnvo_run_conv(m, ck, B, q)) != PNVO_OK) return rc;
+      if (k == 0 && st.have_tail) std::swap(st.cur, st.nxt);
+      if (k == 0) st.have_keys = st.have_tail = false;
+      last = out;
     }
-    if (ds) {
+    const Layer &cl = m->last(b);
+    const long P = (long)cl.hout * cl.wout;
+    // SE block: out = se(out) * out (resnet.py:131-140) — the gate scales the last GroupNorm's scale / shift pair, the tail is unchanged
+    if (b.se_r > 0) {
+      if (cl.cout != cl.coutp) return fail(m, PNVO_ERR_STATE, "SE block " + b.tap + " on a channel-padded map");
+      Timed t(m, s, "se_gate:" + b.tap, 2.0 * B * (2.0 * b.se_r + (double)P) * cl.cout, 4.0 * B * P * cl.cout);
+      HIPCHK(m, launch_se_gate({.x = last.x, .scale = last.ss[0], .shift = last.ss[1], .w1 = b.se_w1, .b1 = b.se_b1, .w2 = b.se_w2,
+                                .b2 = b.se_b2, .out_scale = m->ssE[0], .out_shift = m->ssE[1], .B = B, .P = (int)P, .C = cl.cout, .R = b.se_r}, s));
+      last.ss = m->ssE;
+    }
+    if (ds && !ds_ride) {                                            // (riding: rawD / ssD came out of the first conv's launch)
       const Layer &cd = m->convs[b.ds];
-      if (!ds_ride &&                                                // (riding: rawD / ssD came out of c1's launch)
-          (rc = pnvo_run_conv(m, cd, B, {.x = cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = grp, .s = s})) != PNVO_OK)
+      if ((rc = pnvo_run_conv(m, cd, B, {.x = st.cur, .y = m->rawD, .y_cstride = cd.coutp, .ss = m->ssD, .grp = r.grp, .s = s})) != PNVO_OK)
         return rc;
     }
-    // (the last block's tail rides on the compression conv when that runs on conv_x3_kernel: nobody else reads that block output)
-    if (pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B)) {   // relu(GN2(conv2) + skip): computed by the next conv's stager
-      tail.res = ds ? m->rawD : cur;
-      tail.res_scale = ds ? m->ssD[0] : nullptr;
-      tail.res_shift = ds ? m->ssD[1] : nullptr;
-      tail.out = nxt;
-      have_tail = true;
+    st.tail = BlockTail{ds ? m->rawD : st.cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, st.nxt};
+    // relu(GN(last) + skip) is computed by the next conv's stager where that conv takes a tail (the compression conv behind the last
+    // block: nobody else reads that block output) — of a two-conv block only: a Bottleneck block always runs its own pass and is tapped,
+    // whatever pnvo_conv_takes_tail says of the conv behind it.
+    if (K == 2 && pnvo_conv_takes_tail(m, m->convs[m->next_conv_after(bk)], B)) {
+      st.have_tail = true;
       continue;
     }
     {
-      Timed t(m, s, "residual", 0.0, 12.0 * B * P * c2.coutp);
-      HIPCHK(m, launch_residual(m->rawB, m->ssB[0], m->ssB[1], ds ? m->rawD : cur, ds ? m->ssD[0] : nullptr, ds ? m->ssD[1] : nullptr, B,
-                                P, c2.coutp, nxt, s));
+      Timed t(m, s, "residual", 0.0, 12.0 * B * P * cl.coutp);
+      HIPCHK(m, launch_residual(last.x, last.ss[0], last.ss[1], st.tail.res, st.tail.res_scale, st.tail.res_shift, B, P, cl.coutp, st.nxt, s));
     }
-    std::swap(cur, nxt);
-    if ((rc = maybe_tap(m, b.tap.c_str(), cur, (size_t)B * P * c2.coutp, s)) != PNVO_OK) return rc;
+    std::swap(st.cur, st.nxt);
+    if ((rc = maybe_tap(m, b.tap.c_str(), st.cur, (size_t)B * P * cl.coutp, s)) != PNVO_OK) return rc;
   }
+  return PNVO_OK;
+}
 
-  // (a10) compression conv + GroupNorm(1, C)
+// (a10) compression conv + GroupNorm(1, C); a pending tail of the last block in its stager, that block's output not materialised
+int forward_compression(pnvo_handle m, int B, const FwdRequest &r, FwdState &st) {
   const Layer &comp = m->convs[m->comp];
-  if (have_tail) {               // the last block's tail in the compression conv's stager; its output is not materialised
-    tail.out = nullptr;
-    if ((rc = pnvo_run_conv(m, comp, B, {.x = m->rawB, .in_scale = m->ssB[0], .in_shift = m->ssB[1], .y = m->comp_raw, .y_cstride = comp.coutp,
-                                         .ss = m->ssC, .tail = &tail, .grp = grp, .s = s})) != PNVO_OK)
-      return rc;
-    have_tail = false;
-  } else if ((rc = pnvo_run_conv(m, comp, B, {.x = cur, .y = m->comp_raw, .y_cstride = comp.coutp, .ss = m->ssC, .grp = grp, .s = s})) != PNVO_OK) {
-    return rc;
+  hipStream_t s = r.s;
+  int rc = PNVO_OK;
+  ConvRequest q{.x = st.cur, .y = m->comp_raw, .y_cstride = comp.coutp, .ss = m->ssC, .grp = r.grp, .s = s};
+  if (st.have_tail) {
+    st.tail.out = nullptr;
+    q.x = m->rawB, q.in_scale = m->ssB[0], q.in_shift = m->ssB[1], q.tail = &st.tail;
   }
+  if ((rc = pnvo_run_conv(m, comp, B, q)) != PNVO_OK) return rc;
+  st.have_tail = false;
   if (m->tap_dst != nullptr && m->tap_name == "compression") {
     HIPCHK(m, launch_apply_ss_relu(m->comp_raw, m->ssC[0], m->ssC[1], B, (long)m->fh * m->fw, m->comp_cp, m->tapbuf, s));
     if ((rc = maybe_tap(m, "compression", m->tapbuf, (size_t)B * m->fh * m->fw * m->comp_cp, s)) != PNVO_OK) return rc;
   }
-  if (r.stop_after_compression) return PNVO_OK;   // pnvo_forward_compression: the caller reads m->comp_raw and m->ssC
-  // (a11) Flatten + Linear + ReLU, then the output head — per action model in a grouped forward (each on its own handle: its
-  // weights, bias rows and split-K scratch; the sample ranges are contiguous)
-  if (grp != nullptr) {
-    bool rows_ok = !c.act_embed;
-    FwdRequest rk = r;                   // model k's rows of the output; no act-embed models in a grouped forward
-    rk.actions = nullptr;
-    for (int k = 0; k < grp->n; ++k) rows_ok = rows_ok && fc_rows_usable(grp->h[k], B, rk);
-    if (rows_ok) return run_fc_rows(m, grp->h, grp->end, grp->n, B, m->comp_raw, m->ssC[0], m->ssC[1], rk);
-    int start = 0;
-    for (int k = 0; k < grp->n; ++k) {
-      const int Bk = grp->end[k] - start;
-      pnvo_handle hk = grp->h[k];
-      if (k > 0 && (rc = ensure_workspace(hk, Bk)) != PNVO_OK) return fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk));
-      const size_t crow = (size_t)m->fh * m->fw * m->comp_cp;
-      rk.out = r.out + (size_t)start * c.out_dim;
-      rc = run_fc_head(hk, Bk, m->comp_raw + start * crow, m->ssC[0] + (size_t)start * m->comp_cp, m->ssC[1] + (size_t)start * m->comp_cp, rk);
-      if (rc != PNVO_OK) return k > 0 ? fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk)) : rc;
-      start = grp->end[k];
-    }
-    return PNVO_OK;
+  return PNVO_OK;
+}
+
+// (a11) Flatten + Linear + ReLU, then the output head — per action model in a grouped forward (each on its own handle: its weights, bias
+// rows and split-K scratch; the sample ranges are contiguous)
+int forward_linears(pnvo_handle m, int B, const FwdRequest &r) {
+  const pnvo_config &c = m->cfg;
+  const GroupedFwd *grp = r.grp;
+  if (grp == nullptr) return run_fc_head(m, B, m->comp_raw, m->ssC[0], m->ssC[1], r);
+  int rc = PNVO_OK;
+  bool rows_ok = !c.act_embed;
+  FwdRequest rk = r;                   // model k's rows of the output; no act-embed models in a grouped forward
+  rk.actions = nullptr;
+  for (int k = 0; k < grp->n; ++k) rows_ok = rows_ok && fc_rows_usable(grp->h[k], B, rk);
+  if (rows_ok) return run_fc_rows(m, grp->h, grp->end, grp->n, B, m->comp_raw, m->ssC[0], m->ssC[1], rk);
+  const size_t crow = (size_t)m->fh * m->fw * m->comp_cp;
+  for (int k = 0, start = 0; k < grp->n; start = grp->end[k++]) {
+    const int Bk = grp->end[k] - start;
+    pnvo_handle hk = grp->h[k];
+    if (k > 0 && (rc = ensure_workspace(hk, Bk)) != PNVO_OK) return fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk));
+    rk.out = r.out + (size_t)start * c.out_dim;
+    rc = run_fc_head(hk, Bk, m->comp_raw + start * crow, m->ssC[0] + (size_t)start * m->comp_cp, m->ssC[1] + (size_t)start * m->comp_cp, rk);
+    if (rc != PNVO_OK) return k > 0 ? fail(m, rc, std::string("grouped forward: ") + pnvo_last_error(hk)) : rc;
   }
-  return run_fc_head(m, B, m->comp_raw, m->ssC[0], m->ssC[1], r);
+  return PNVO_OK;
+}
+
+int forward_body(pnvo_handle m, int B, const FwdRequest &r) {
+  FwdState st{.cur = m->bufY[0], .nxt = m->bufY[1]};
+  int rc;
+  if ((rc = forward_stem(m, B, r, st)) != PNVO_OK || st.done) return rc;
+  if ((rc = forward_blocks(m, B, r, st)) != PNVO_OK || (rc = forward_compression(m, B, r, st)) != PNVO_OK) return rc;
+  return r.stop_after_compression ? PNVO_OK : forward_linears(m, B, r);   // (pnvo_forward_compression: the caller reads m->comp_raw and m->ssC)
 }
 
 // fc_rows.hip takes the two Linear layers of this handle at B samples (inference handles on float32, default kernels)
@@ -2001,13 +2038,8 @@ int raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth
 
 int pnvo_forward_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const int64_t *actions, int B,
                      float *out, int32_t *err_flag, void *stream) {
-  if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
-  if (!m->loaded) return fail(m, PNVO_ERR_STATE, "pnvo_forward_raw before pnvo_load_weights");
-  if (B <= 0 || !out) return fail(m, PNVO_ERR_ARG, "bad batch / null output");
+  if (int rc0 = check_frames(m, "pnvo_forward_raw", rgb_frames, depth_frames, tdv, B, out)) return rc0;
   const pnvo_config &c = m->cfg;
-  if ((c.n_rgb > 0) != (rgb_frames != nullptr) || ((c.n_depth > 0 || c.n_dd > 0) && depth_frames == nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(m, PNVO_ERR_ARG, "sensor frames do not match the model's observation_space");
   if (c.act_embed && !actions) return fail(m, PNVO_ERR_ARG, "act_embed model needs actions");
   if (int rc0 = pnvo_check_inputs(m)) return rc0;
   HIPCHK(m, hipSetDevice(m->device));
@@ -2019,11 +2051,7 @@ int pnvo_forward_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *dept
                         actions, B, out, stream);
   }
   const FwdRequest r{.src = {nullptr, nullptr, nullptr, tdv}, .raw = {rgb_frames, depth_frames, err_flag}, .actions = actions, .out = out, .s = s};
-  if (m->precision == 1) {
-    pnvo_handle hs[1] = {m};
-    float *outs[1] = {out};
-    return pnvo_forward_bf16(hs, 1, B, r, outs);
-  }
+  if (m->precision == 1) return forward_bf16_one(m, B, r);
   int rc = ensure_workspace(m, B);
   // (frames are uint8 / the one-hot is derived in the stager: nothing for the input-contract check to find — no stem event; one
   //  left pending by an earlier forward that failed between its stem and its wait is dropped here)
@@ -2085,8 +2113,7 @@ int pnvo_forward_grouped_raw(const pnvo_handle *handles, const int32_t *counts, 
   if (int rcs = pnvo_grouped_supported(hs, ng)) return rcs;
   for (int k = 0; k < ng; ++k)
     if (int rc0 = pnvo_check_inputs(hs[k])) return rc0;
-  if ((c.n_rgb > 0) != (rgb_frames != nullptr) || ((c.n_depth > 0 || c.n_dd > 0) && depth_frames == nullptr) || (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(m, PNVO_ERR_ARG, "sensor frames do not match the models' observation_space");
+  if (!frames_match(c, rgb_frames, depth_frames, tdv)) return fail(m, PNVO_ERR_ARG, "sensor frames do not match the models' observation_space");
   if (!raw_direct(m, depth_frames)) return fail(m, PNVO_ERR_STATE, "grouped forward needs the sensor-frame stager of the float16-piece stem");
   HIPCHK(m, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
@@ -2106,18 +2133,10 @@ int pnvo_forward_grouped_raw(const pnvo_handle *handles, const int32_t *counts, 
 
 int pnvo_forward_dual_raw(pnvo_handle ha, pnvo_handle hb, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, int B,
                           float *out_a, float *out_b, int32_t *err_flag, void *stream) {
-  if (!ha || !hb) return fail(ha, PNVO_ERR_ARG, "null handle");
-  if (!ha->loaded || !hb->loaded) return fail(ha, PNVO_ERR_STATE, "pnvo_forward_dual_raw before pnvo_load_weights");
-  if (B <= 0 || !out_a || !out_b) return fail(ha, PNVO_ERR_ARG, "bad batch / null output");
-  if (ha->precision != 1 || hb->precision != 1)
-    return fail(ha, PNVO_ERR_STATE, "pnvo_forward_dual_raw runs the bfloat16 path: call pnvo_set_precision(h, 1) on both models");
-  if (std::memcmp(&ha->cfg, &hb->cfg, sizeof(pnvo_config)) != 0 || ha->device != hb->device)
-    return fail(ha, PNVO_ERR_ARG, "the two models of a dual forward must share architecture and device");
+  if (int rc0 = check_dual(ha, hb, "pnvo_forward_dual_raw", B, out_a, out_b)) return rc0;
   const pnvo_config &c = ha->cfg;
   if (c.act_embed) return fail(ha, PNVO_ERR_ARG, "pnvo_forward_dual_raw covers the separate-action models");
-  if ((c.n_rgb > 0) != (rgb_frames != nullptr) || ((c.n_depth > 0 || c.n_dd > 0) && depth_frames == nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(ha, PNVO_ERR_ARG, "sensor frames do not match the model's observation_space");
+  if (!frames_match(c, rgb_frames, depth_frames, tdv)) return fail(ha, PNVO_ERR_ARG, "sensor frames do not match the model's observation_space");
   HIPCHK(ha, hipSetDevice(ha->device));
   hipStream_t s = (hipStream_t)stream;
   if (!raw_direct(ha, depth_frames)) {
@@ -2133,22 +2152,11 @@ int pnvo_forward_dual_raw(pnvo_handle ha, pnvo_handle hb, const uint8_t *rgb_fra
 
 int pnvo_forward_features(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv,
                           const int64_t *actions, int B, float *hidden_out, void *stream) {
-  if (!m) return fail(m, PNVO_ERR_ARG, "null handle");
-  if (!m->loaded) return fail(m, PNVO_ERR_STATE, "pnvo_forward_features before pnvo_load_weights");
-  if (B <= 0 || !hidden_out) return fail(m, PNVO_ERR_ARG, "bad batch / null output");
-  const pnvo_config &c = m->cfg;
-  if ((c.n_rgb > 0) != (rgb != nullptr) || (c.n_depth > 0) != (depth != nullptr) || (c.n_dd > 0) != (dd != nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
-    return fail(m, PNVO_ERR_ARG, "observation tensors do not match the model's observation_space");
+  if (int rc0 = check_pairs(m, "pnvo_forward_features", rgb, depth, dd, tdv, B, hidden_out)) return rc0;
   if (int rc0 = pnvo_check_inputs(m)) return rc0;
   HIPCHK(m, hipSetDevice(m->device));
-  int rc = ensure_workspace(m, B);
-  if (rc != PNVO_OK) return rc;
-  const FwdRequest r{.src = {rgb, depth, dd, tdv}, .actions = actions, .out = hidden_out, .features_only = true, .s = (hipStream_t)stream};
-  if ((rc = forward_body(m, B, r)) != PNVO_OK) return rc;
-  bool rerun = false;
-  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
-  return rerun ? forward_body(m, B, r) : PNVO_OK;
+  return run_forward(m, B, {.src = {rgb, depth, dd, tdv}, .actions = actions, .out = hidden_out, .features_only = true, .s = (hipStream_t)stream},
+                     false);
 }
 
 extern "C++" int pnvo_forward_compression(pnvo_handle m, const float *depth, int B, void *stream) {
@@ -2160,13 +2168,7 @@ extern "C++" int pnvo_forward_compression(pnvo_handle m, const float *depth, int
   if (m->precision != 0) return fail(m, PNVO_ERR_STATE, "pnvo_forward_compression runs on the float32 path");
   if (int rc0 = pnvo_check_inputs(m)) return rc0;
   HIPCHK(m, hipSetDevice(m->device));
-  int rc = ensure_workspace(m, B);
-  if (rc != PNVO_OK) return rc;
-  const FwdRequest r{.src = {nullptr, depth, nullptr, nullptr}, .stop_after_compression = true, .s = (hipStream_t)stream};
-  if ((rc = forward_body(m, B, r)) != PNVO_OK) return rc;
-  bool rerun = false;
-  if ((rc = pnvo_input_fallback(m, r.s, &rerun)) != PNVO_OK) return rc;
-  return rerun ? forward_body(m, B, r) : PNVO_OK;
+  return run_forward(m, B, {.src = {nullptr, depth, nullptr, nullptr}, .stop_after_compression = true, .s = (hipStream_t)stream}, false);
 }
 
 int pnvo_discretize_depth(const float *depth, int64_t n, int64_t in_stride, int bins, float *onehot,

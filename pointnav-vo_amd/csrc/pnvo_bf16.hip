@@ -35,14 +35,14 @@ struct Bf16State {
   unsigned long long dual_partner = 0;       // process-unique id of the partner handle (an address can be re-used)
   unsigned long long dual_partner_gen = 0, dual_self_gen = 0;
   int cap = 0;
-  DevBuf<unsigned short> stem_raw, bufY[2], rawA, rawB, rawD;
+  DevBuf<unsigned short> stem_raw, bufY0, bufY1, rawA, rawB, rawD;
   DevBuf<float> comp_raw, hid, stats, stats_ds;   // stats_ds: partial sums of a riding downsample conv
   DevPair<float> ssA, ssB, ssD, ssC;
 };
 
 // Before a regrow: the old workspace goes first (not old and new side by side), and a failed regrow leaves cap = 0.
 void free_ws(Bf16State *b) {
-  for (DevBuf<unsigned short> *q : {&b->stem_raw, &b->bufY[0], &b->bufY[1], &b->rawA, &b->rawB, &b->rawD}) q->reset();
+  for (DevBuf<unsigned short> *q : {&b->stem_raw, &b->bufY0, &b->bufY1, &b->rawA, &b->rawB, &b->rawD}) q->reset();
   for (DevBuf<float> *q : {&b->comp_raw, &b->hid, &b->stats, &b->stats_ds}) q->reset();
   for (DevPair<float> *q : {&b->ssA, &b->ssB, &b->ssD, &b->ssC}) q->reset();
   b->cap = 0;
@@ -110,7 +110,7 @@ int ensure_ws(pnvo_handle m, int B) {
     maxc = std::max(maxc, l.coutp);
   }
   HIPCHK(m, b->stem_raw.alloc((size_t)B * m->Hs * m->Ws * 32));
-  for (DevBuf<unsigned short> *q : {&b->bufY[0], &b->bufY[1], &b->rawA, &b->rawB, &b->rawD}) HIPCHK(m, q->alloc(act));
+  for (DevBuf<unsigned short> *q : {&b->bufY0, &b->bufY1, &b->rawA, &b->rawB, &b->rawD}) HIPCHK(m, q->alloc(act));
   HIPCHK(m, b->comp_raw.alloc((size_t)B * m->fh * m->fw * m->comp_cp));
   HIPCHK(m, b->hid.alloc((size_t)B * c.hidden));
   HIPCHK(m, b->stats.alloc(st));
@@ -152,230 +152,248 @@ void pnvo_bf16_free(pnvo_handle m) {
   m->bf = nullptr;
 }
 
-int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float *const *outs) {
-  pnvo_handle m = hs[0];
-  hipStream_t s = r.s;
-  Bf16State *bs[2] = {nullptr, nullptr};
-  int rc;
-  for (int z = 0; z < nm; ++z) {
-    if ((rc = prepare(hs[z])) != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, hs[z]->err);
-    bs[z] = static_cast<Bf16State *>(hs[z]->bf);
-    if ((rc = ensure_ws(hs[z], B)) != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, hs[z]->err);
-  }
-  if (nm == 2 && (rc = dual_stem(hs[0], hs[1])) != PNVO_OK) return rc;
-  const pnvo_config &c = m->cfg;
-  const Layer &stem = m->convs[0];
-  auto each = [&](auto f) {                       // per-model pointer arrays for the batched launches
-    using T = decltype(f(0));
-    struct R { T v[2]; } r;
-    for (int z = 0; z < 2; ++z) r.v[z] = f(z < nm ? z : 0);
-    return r;
-  };
+namespace {
 
-  // (a4-a6) fused stem, one N-tile per model
+typedef DevBuf<unsigned short> Bf16State::*Act;   // an activation buffer of the workspace, by name
+typedef DevPair<float> Bf16State::*Gn;            // a GroupNorm scale / shift pair of it
+
+// The one or two models of a forward.  The batched launches take per-model pointer arrays of two: with one model the second entry
+// repeats the first (k).
+struct Models {
+  pnvo_handle *hs;
+  Bf16State *bs[2];
+  int nm;
+  int k(int z) const { return z < nm ? z : 0; }
+};
+
+// One conv of the residual stages or the compression conv (a call site sets the members it uses, in this order).
+struct ConvBRequest {
+  Act x = nullptr;             // input
+  Gn x_gn = nullptr;           // the producer's pair: relu(GN(x)) while staging
+  Act skip = nullptr;          // with x_gn: the fused BasicBlock tail relu(GN2(x) + skip) computed while staging — skip is the block input
+  Gn skip_gn = nullptr;        //   buffer, or with skip_gn the raw downsample conv (its GroupNorm applied in the fetch)
+  Act xout = nullptr;          // where the stager writes that block output for the later readers, or none
+  Act y = nullptr;             // raw output; nullptr: the float32 compression output comp_raw
+  Gn y_gn = nullptr;           // pair of the GroupNorm that follows
+  long ride = -1;              // >= 0: the layer index of the block's 1x1 stride-2 downsample conv, computed by this launch
+                               //   (conv_bf16_kernel DSF): raw output -> rawD, GroupNorm -> ssD
+};
+
+// GroupNorm finalisation of layer li's partial sums in `stats` into `dst`, both models in one launch
+int gn_finalize(const Models &M, int B, size_t li, DevBuf<float> Bf16State::*stats, int slots, Gn dst, hipStream_t s) {
+  const Layer &l = M.hs[0]->convs[li];
+  const float *st[2], *ga[2], *be[2];
+  float *sc[2], *sh[2];
+  for (int z = 0; z < 2; ++z) {
+    const int k = M.k(z);
+    st[z] = M.bs[k]->*stats;
+    ga[z] = M.hs[k]->convs[li].gamma;
+    be[z] = M.hs[k]->convs[li].beta;
+    sc[z] = (M.bs[k]->*dst)[0];
+    sh[z] = (M.bs[k]->*dst)[1];
+  }
+  HIPCHK(M.hs[0], launch_gn_finalize2(st, B, slots, l.coutp, l.cout, l.groups, (long)l.hout * l.wout, ga, be, 1e-5f, sc, sh, M.nm, s));
+  return PNVO_OK;
+}
+
+// (a4-a7) fused stem, one N-tile per model, its GroupNorm, then GN + ReLU + maxpool -> bufY0
+int stem_bf16(const Models &M, int B, const FwdRequest &r) {
+  pnvo_handle m = M.hs[0];
+  hipStream_t s = r.s;
+  const Layer &stem = m->convs[0];
+  const int nm = M.nm;
+  int rc;
   {
     StemMXArgs a;
     std::memset(&a, 0, sizeof(a));
     pnvo_stem_mx_input(m, B, r.src, r.raw, a);                   // (pnvo_forward_raw: sensor frames instead of src[0..2])
-    a.wpk = nm == 2 ? bs[0]->dual_stem : bs[0]->stem_wpk;
+    a.wpk = nm == 2 ? M.bs[0]->dual_stem : M.bs[0]->stem_wpk;
     for (int z = 0; z < nm; ++z) {
-      a.y[z] = bs[z]->stem_raw;
-      a.stats[z] = bs[z]->stats;
+      a.y[z] = M.bs[z]->stem_raw;
+      a.stats[z] = M.bs[z]->stats;
       a.y_coff[z] = 0;
     }
     a.y_cstride = 32;
     a.stats_cstride = 32;
-    const double M = (double)B * m->Hs * m->Ws;
+    const double P = (double)B * m->Hs * m->Ws;
     {
-      PnvoTimed t(m, s, "bf16:stem", 2.0 * nm * M * stem.cout * stem.cin * 49, pnvo_stem_in_bytes(m, B, r.raw) + 2.0 * nm * M * stem.cout);
+      PnvoTimed t(m, s, "bf16:stem", 2.0 * nm * P * stem.cout * stem.cin * 49, pnvo_stem_in_bytes(m, B, r.raw) + 2.0 * nm * P * stem.cout);
       if ((rc = pnvo_launch_stem_mx(m, a, 1, nm, true, nullptr, s)) != PNVO_OK) return rc;
     }
     PnvoTimed t(m, s, "bf16:gn_finalize", 0.0, 0.0);
-    auto st = each([&](int z) { return (const float *)bs[z]->stats; });
-    auto ga = each([&](int z) { return (const float *)hs[z]->convs[0].gamma; });
-    auto be = each([&](int z) { return (const float *)hs[z]->convs[0].beta; });
-    auto sc = each([&](int z) { return bs[z]->ssA[0]; });
-    auto sh = each([&](int z) { return bs[z]->ssA[1]; });
-    HIPCHK(m, launch_gn_finalize2(st.v, B, a.slots, 32, 32, stem.groups, (long)m->Hs * m->Ws, ga.v, be.v, 1e-5f, sc.v, sh.v, nm, s));
+    if ((rc = gn_finalize(M, B, 0, &Bf16State::stats, a.slots, &Bf16State::ssA, s)) != PNVO_OK) return rc;
   }
-  // (a7) GN + ReLU + maxpool
-  int cur = 0;
+  const unsigned short *x[2];
+  const float *sc[2], *sh[2];
+  unsigned short *o[2];
+  for (int z = 0; z < 2; ++z) {
+    const Bf16State *b = M.bs[M.k(z)];
+    x[z] = b->stem_raw, sc[z] = b->ssA[0], sh[z] = b->ssA[1], o[z] = b->bufY0;
+  }
+  PnvoTimed t(m, s, "bf16:gn_relu_maxpool", 0.0, 2.0 * nm * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * 32);
+  HIPCHK(m, launch_gn_relu_maxpool_bf16(x, sc, sh, B, m->Hs, m->Ws, 32, o, nm, s));
+  return PNVO_OK;
+}
+
+// One conv + its GroupNorm finalisation (and its riding downsample conv's).  Stager mode 0: plain input; 1: relu(GN(x)) of the
+// producer; 2: the block tail.
+int run_conv_bf16(const Models &M, int B, size_t li, const ConvBRequest &q, hipStream_t s) {
+  pnvo_handle m = M.hs[0];
+  const Layer &l = m->convs[li];
+  const BLayer &bl = M.bs[0]->layers[li];
+  const int mode = q.skip ? 2 : q.x_gn ? 1 : 0, nm = M.nm;
+  ConvBArgs a = bl.plan;
+  a.B = B;
+  a.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
+  // one tile per sample (the 12 x 22 and 6 x 11 maps): the workgroup that sums a sample's channels finalises its GroupNorm too
+  // (gn_finalize_lane: fp64, the butterfly order of the float32 path's fused finalisation) — one launch less per layer
+  const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
+  const bool gfuse = m->opt.gn_fuse && a.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 && 32 % cpg == 0 && l.cout % cpg == 0;
+  for (int z = 0; z < 2; ++z) {
+    const int k = M.k(z);
+    const Bf16State *b = M.bs[k];
+    a.x[z] = b->*q.x;
+    a.wpk[z] = b->layers[li].wpk;
+    a.y[z] = q.y ? (void *)(b->*q.y) : (void *)b->comp_raw;
+    a.stats[z] = b->stats;
+    a.in_scale[z] = q.x_gn ? (b->*q.x_gn)[0] : nullptr;
+    a.in_shift[z] = q.x_gn ? (b->*q.x_gn)[1] : nullptr;
+    a.x2[z] = q.skip ? (const unsigned short *)(b->*q.skip) : nullptr;
+    a.in_scale2[z] = q.skip_gn ? (b->*q.skip_gn)[0] : nullptr;
+    a.in_shift2[z] = q.skip_gn ? (b->*q.skip_gn)[1] : nullptr;
+    a.xout[z] = q.xout ? (unsigned short *)(b->*q.xout) : nullptr;
+    a.gn_gamma[z] = gfuse ? M.hs[k]->convs[li].gamma : nullptr;
+    a.gn_beta[z] = gfuse ? M.hs[k]->convs[li].beta : nullptr;
+    a.gn_scale[z] = gfuse ? (b->*q.y_gn)[0] : nullptr;
+    a.gn_shift[z] = gfuse ? (b->*q.y_gn)[1] : nullptr;
+    if (q.ride >= 0) {
+      a.ds_wpk[z] = b->layers[q.ride].wpk;
+      a.ds_y[z] = b->rawD;
+      a.ds_stats[z] = b->stats_ds;
+      a.ds_gamma[z] = gfuse ? M.hs[k]->convs[q.ride].gamma : nullptr;
+      a.ds_beta[z] = gfuse ? M.hs[k]->convs[q.ride].beta : nullptr;
+      a.ds_scale[z] = gfuse ? b->ssD[0] : nullptr;
+      a.ds_shift[z] = gfuse ? b->ssD[1] : nullptr;
+    }
+  }
+  a.gn_cpg = cpg;
+  a.gn_eps = 1e-5f;
+  a.gn_P = (long)l.hout * l.wout;
+  const double macs = (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw;
   {
-    auto x = each([&](int z) { return (const unsigned short *)bs[z]->stem_raw; });
-    auto sc = each([&](int z) { return (const float *)bs[z]->ssA[0]; });
-    auto sh = each([&](int z) { return (const float *)bs[z]->ssA[1]; });
-    auto o = each([&](int z) -> unsigned short * { return bs[z]->bufY[0]; });
-    PnvoTimed t(m, s, "bf16:gn_relu_maxpool", 0.0, 2.0 * nm * B * ((double)m->Hs * m->Ws + (double)m->Hp * m->Wp) * 32);
-    HIPCHK(m, launch_gn_relu_maxpool_bf16(x.v, sc.v, sh.v, B, m->Hs, m->Ws, 32, o.v, nm, s));
+    PnvoTimed t(m, s, "bf16:conv:" + l.name, 2.0 * nm * macs,
+                2.0 * nm * ((double)B * l.hin * l.win * l.cin * (mode == 2 ? 3 : 1) + (double)B * l.hout * l.wout * l.cout));
+    HIPCHK(m, launch_conv_bf16(a, l.k, l.stride, mode, q.y == nullptr, bl.mw, bl.nw, bl.lds, nm, s));
   }
+  if (gfuse) return PNVO_OK;
+  PnvoTimed t(m, s, "bf16:gn_finalize", 0.0, 0.0);
+  int rc = gn_finalize(M, B, li, &Bf16State::stats, a.slots, q.y_gn, s);
+  // the riding downsample conv's GroupNorm (same geometry, its own sums and parameters)
+  if (rc == PNVO_OK && q.ride >= 0) rc = gn_finalize(M, B, (size_t)q.ride, &Bf16State::stats_ds, a.slots, &Bf16State::ssD, s);
+  return rc;
+}
 
-  // one conv of the residual stages + its GroupNorm finalisation.  mode 0: plain input; 1: relu(GN(x)) of the producer
-  // (ssA); 2: the fused BasicBlock tail relu(GN2(rawB) + skip) — computed while staging and written to `xout`
-  struct Skip {
-    bool on = false, affine = false;     // affine: the skip branch is the raw downsample conv (GN applied in the fetch)
-    int buf = 0;                         // else: the block input bufY[buf]
-  };
-  const bool fuse = m->opt.bf16_fuse != 0;
-  // ride (>= 0): the layer index of the block's 1x1 stride-2 downsample conv, computed by this launch (conv_bf16_kernel DSF): raw output ->
-  // rawD, GroupNorm -> ssD
-  auto conv = [&](size_t li, int mode, auto xin, auto yout, int ss_sel /*0 A, 1 B, 2 D, 3 C*/, bool f32out, const Skip &sk,
-                  int out_buf, long ride = -1) -> int {
-    const Layer &l = m->convs[li];
-    ConvBArgs a = bs[0]->layers[li].plan;
-    a.B = B;
-    a.persist_wgs = m->opt.x3_persist ? 3 * m->num_cus : 0;
-    for (int z = 0; z < 2; ++z) {
-      const int k = z < nm ? z : 0;
-      a.x[z] = xin(k);
-      a.wpk[z] = bs[k]->layers[li].wpk;
-      a.y[z] = yout(k);
-      a.stats[z] = bs[k]->stats;
-      a.in_scale[z] = mode == 1 ? bs[k]->ssA[0] : mode == 2 ? bs[k]->ssB[0] : nullptr;
-      a.in_shift[z] = mode == 1 ? bs[k]->ssA[1] : mode == 2 ? bs[k]->ssB[1] : nullptr;
-      a.x2[z] = mode == 2 ? (sk.affine ? bs[k]->rawD : bs[k]->bufY[sk.buf]) : nullptr;
-      a.in_scale2[z] = mode == 2 && sk.affine ? bs[k]->ssD[0] : nullptr;
-      a.in_shift2[z] = mode == 2 && sk.affine ? bs[k]->ssD[1] : nullptr;
-      a.xout[z] = mode == 2 && out_buf >= 0 ? bs[k]->bufY[out_buf] : nullptr;
-      if (ride >= 0) {
-        a.ds_wpk[z] = bs[k]->layers[ride].wpk;
-        a.ds_y[z] = bs[k]->rawD;
-        a.ds_stats[z] = bs[k]->stats_ds;
-      }
-    }
-    // one tile per sample (the 12 x 22 and 6 x 11 maps): the workgroup that sums a sample's channels finalises its GroupNorm too
-    // (gn_finalize_lane: fp64, the butterfly order of the float32 path's fused finalisation) — one launch less per layer
-    const int cpg = l.groups > 0 ? l.cout / l.groups : 0;
-    const bool gfuse = m->opt.gn_fuse && a.slots == 1 && l.cout == l.coutp && cpg >= 1 && cpg <= 32 && 32 % cpg == 0 && l.cout % cpg == 0;
-    auto ssof = [&](int z) -> float *const * { return ss_sel == 0 ? bs[z]->ssA : ss_sel == 1 ? bs[z]->ssB : ss_sel == 2 ? bs[z]->ssD : bs[z]->ssC; };
-    for (int z = 0; z < 2; ++z) {
-      const int k = z < nm ? z : 0;
-      a.gn_gamma[z] = gfuse ? hs[k]->convs[li].gamma : nullptr;
-      a.gn_beta[z] = gfuse ? hs[k]->convs[li].beta : nullptr;
-      a.gn_scale[z] = gfuse ? ssof(k)[0] : nullptr;
-      a.gn_shift[z] = gfuse ? ssof(k)[1] : nullptr;
-      if (ride >= 0) {
-        a.ds_gamma[z] = gfuse ? hs[k]->convs[ride].gamma : nullptr;
-        a.ds_beta[z] = gfuse ? hs[k]->convs[ride].beta : nullptr;
-        a.ds_scale[z] = gfuse ? bs[k]->ssD[0] : nullptr;
-        a.ds_shift[z] = gfuse ? bs[k]->ssD[1] : nullptr;
-      }
-    }
-    a.gn_cpg = cpg;
-    a.gn_eps = 1e-5f;
-    a.gn_P = (long)l.hout * l.wout;
-    const double macs = (double)B * l.hout * l.wout * l.cout * l.cin * l.k * l.kw;
-    {
-      PnvoTimed t(m, s, "bf16:conv:" + l.name, 2.0 * nm * macs,
-                  2.0 * nm * ((double)B * l.hin * l.win * l.cin * (mode == 2 ? 3 : 1) + (double)B * l.hout * l.wout * l.cout));
-      HIPCHK(m, launch_conv_bf16(a, l.k, l.stride, mode, f32out, bs[0]->layers[li].mw, bs[0]->layers[li].nw, bs[0]->layers[li].lds,
-                                 nm, s));
-    }
-    if (gfuse) return PNVO_OK;
-    PnvoTimed t(m, s, "bf16:gn_finalize", 0.0, 0.0);
-    auto st = each([&](int z) { return (const float *)bs[z]->stats; });
-    auto ga = each([&](int z) { return (const float *)hs[z]->convs[li].gamma; });
-    auto be = each([&](int z) { return (const float *)hs[z]->convs[li].beta; });
-    auto sc = each([&](int z) { return ssof(z)[0]; });
-    auto sh = each([&](int z) { return ssof(z)[1]; });
-    HIPCHK(m, launch_gn_finalize2(st.v, B, a.slots, l.coutp, l.cout, l.groups, (long)l.hout * l.wout, ga.v, be.v, 1e-5f, sc.v, sh.v,
-                                  nm, s));
-    if (ride >= 0) {                     // the riding downsample conv's GroupNorm (same geometry, its own sums and parameters)
-      auto std_ = each([&](int z) { return (const float *)bs[z]->stats_ds; });
-      auto gad = each([&](int z) { return (const float *)hs[z]->convs[ride].gamma; });
-      auto bed = each([&](int z) { return (const float *)hs[z]->convs[ride].beta; });
-      auto scd = each([&](int z) { return bs[z]->ssD[0]; });
-      auto shd = each([&](int z) { return bs[z]->ssD[1]; });
-      HIPCHK(m, launch_gn_finalize2(std_.v, B, a.slots, l.coutp, l.cout, l.groups, (long)l.hout * l.wout, gad.v, bed.v, 1e-5f, scd.v, shd.v,
-                                    nm, s));
-    }
-    return PNVO_OK;
-  };
+// What the block walk hands on: the buffer that holds (or, with a tail pending, will hold) the block output, and the tail of the last
+// block where it is still to be applied — relu(GN2(rawB) + skip), the skip its block input or (skip_gn) its raw downsample conv.
+struct WalkBf16 {
+  Act cur = &Bf16State::bufY0, nxt = &Bf16State::bufY1;
+  Act skip = nullptr;
+  Gn skip_gn = nullptr;
+};
 
-  // (a8) residual stages (BasicBlock: conv3x3(s) -> GN -> ReLU -> conv3x3 -> GN; + identity / conv1x1(s)+GN; ReLU).
-  // The tail of block k (GN2 + skip + ReLU) is not a pass of its own: conv1 of block k+1 (and the compression conv after
-  // the last block) computes it while staging its input patch and writes the block output for the later readers (the
-  // next skip branch / downsample conv).  PNVO_BF16_NOFUSE=1 keeps the separate residual kernel (A/B measurements).
-  Skip pend;                                       // tail of the previous block, still to be applied
-  const Skip none;
+// (a8) residual stages (BasicBlock: conv3x3(s) -> GN -> ReLU -> conv3x3 -> GN; + identity / conv1x1(s)+GN; ReLU).
+// The tail of block k (GN2 + skip + ReLU) is not a pass of its own: conv1 of block k+1 (and the compression conv after
+// the last block) computes it while staging its input patch and writes the block output for the later readers (the
+// next skip branch / downsample conv).  PNVO_BF16_NOFUSE=1 keeps the separate residual kernel (A/B measurements).
+int blocks_bf16(const Models &M, int B, WalkBf16 &w, hipStream_t s) {
+  pnvo_handle m = M.hs[0];
+  const int nm = M.nm;
+  int rc;
   for (const Block &blk : m->blocks) {
     const size_t l1 = blk.conv[0], l2 = blk.conv[1];
     const bool ds = blk.ds >= 0;
-    const Layer &c2 = m->convs[l2];
+    const Layer &c1 = m->convs[l1], &c2 = m->convs[l2];
     // the block's downsample conv rides on its first conv's launch (option ds_fuse); in the block-tail mode the block input is then
     // not written at all: both of its readers are that launch
-    const Layer &c1 = m->convs[l1];
-    const bool ride_ok = ds && m->opt.ds_fuse && !(pend.on && pend.affine) /* the stager would read rawD while the ride writes it */ &&
-                         bs[0]->layers[l1].nw == 1 /* two N-tiles per wave: the second accumulator set does not fit (measured 56 -> 103 us) */ &&
+    const bool ride_ok = ds && m->opt.ds_fuse && !w.skip_gn /* the stager would read rawD while the ride writes it */ &&
+                         M.bs[0]->layers[l1].nw == 1 /* two N-tiles per wave: the second accumulator set does not fit (measured 56 -> 103 us) */ &&
                          c1.cinp != 32 /* 32 input channels: the resident-weight persistent form takes the head (140 + 39 us with the separate
                                           downsample conv against 235 us with the ride on the streaming form) */ &&
                          c1.k == 3 && c1.stride == 2 && m->convs[blk.ds].k == 1 && m->convs[blk.ds].stride == 2 &&
                          c1.cinp == m->convs[blk.ds].cinp && c1.coutp == m->convs[blk.ds].coutp && c1.hout == m->convs[blk.ds].hout &&
                          c1.wout == m->convs[blk.ds].wout && c1.groups == m->convs[blk.ds].groups;
     const long ride = ride_ok ? blk.ds : -1;
-    if (pend.on) {                               // input = relu(GN2(rawB) + skip) of the previous block -> bufY[cur ^ 1]
-      if ((rc = conv(l1, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->rawA; }, 0,
-                     false, pend, ride_ok ? -1 : (cur ^ 1), ride)) != PNVO_OK)
-        return rc;
-      cur ^= 1;
-    } else if ((rc = conv(l1, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
-                          [&](int z) { return (void *)bs[z]->rawA; }, 0, false, none, -1, ride)) != PNVO_OK) {
-      return rc;
-    }
-    if ((rc = conv(l2, 1, [&](int z) { return (const unsigned short *)bs[z]->rawA; }, [&](int z) { return (void *)bs[z]->rawB; }, 1,
-                   false, none, -1)) != PNVO_OK)
-      return rc;
-    const long P = (long)c2.hout * c2.wout;
-    if (ds && !ride_ok && (rc = conv(blk.ds, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
-                                     [&](int z) { return (void *)bs[z]->rawD; }, 2, false, none, -1)) != PNVO_OK)
-      return rc;
-    if (fuse) {
-      pend.on = true;
-      pend.affine = ds;
-      pend.buf = cur;
-      continue;
-    }
-    auto a_ = each([&](int z) { return (const unsigned short *)bs[z]->rawB; });
-    auto sa = each([&](int z) { return (const float *)bs[z]->ssB[0]; });
-    auto ta = each([&](int z) { return (const float *)bs[z]->ssB[1]; });
-    auto y_ = each([&](int z) -> unsigned short * { return bs[z]->bufY[cur ^ 1]; });
-    if (ds) {
-      auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->rawD; });
-      auto sb = each([&](int z) { return (const float *)bs[z]->ssD[0]; });
-      auto tb = each([&](int z) { return (const float *)bs[z]->ssD[1]; });
-      PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
-      HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, sb.v, tb.v, B, P, c2.coutp, y_.v, nm, s));
+    if (w.skip) {                                // input = relu(GN2(rawB) + skip) of the previous block -> nxt
+      rc = run_conv_bf16(M, B, l1, {.x = &Bf16State::rawB, .x_gn = &Bf16State::ssB, .skip = w.skip, .skip_gn = w.skip_gn,
+                                    .xout = ride_ok ? nullptr : w.nxt, .y = &Bf16State::rawA, .y_gn = &Bf16State::ssA, .ride = ride}, s);
+      std::swap(w.cur, w.nxt);
     } else {
-      auto b_ = each([&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; });
-      PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
-      HIPCHK(m, launch_residual_bf16(a_.v, sa.v, ta.v, b_.v, nullptr, nullptr, B, P, c2.coutp, y_.v, nm, s));
+      rc = run_conv_bf16(M, B, l1, {.x = w.cur, .y = &Bf16State::rawA, .y_gn = &Bf16State::ssA, .ride = ride}, s);
     }
-    cur ^= 1;
-  }
-  // (a10) compression conv + GroupNorm(1, C): fp32 output for the Linear layers
-  if (pend.on) {
-    if ((rc = conv(m->comp, 2, [&](int z) { return (const unsigned short *)bs[z]->rawB; }, [&](int z) { return (void *)bs[z]->comp_raw; }, 3,
-                   true, pend, -1)) != PNVO_OK)
+    if (rc != PNVO_OK ||
+        (rc = run_conv_bf16(M, B, l2, {.x = &Bf16State::rawA, .x_gn = &Bf16State::ssA, .y = &Bf16State::rawB, .y_gn = &Bf16State::ssB}, s)) != PNVO_OK)
       return rc;
-  } else if ((rc = conv(m->comp, 0, [&](int z) { return (const unsigned short *)bs[z]->bufY[cur]; },
-                        [&](int z) { return (void *)bs[z]->comp_raw; }, 3, true, none, -1)) != PNVO_OK) {
-    return rc;
+    if (ds && !ride_ok && (rc = run_conv_bf16(M, B, blk.ds, {.x = w.cur, .y = &Bf16State::rawD, .y_gn = &Bf16State::ssD}, s)) != PNVO_OK) return rc;
+    w.skip = ds ? &Bf16State::rawD : w.cur;
+    w.skip_gn = ds ? &Bf16State::ssD : nullptr;
+    if (m->opt.bf16_fuse) continue;
+    const unsigned short *xa[2], *xb[2];
+    const float *sa[2], *ta[2], *sb[2], *tb[2];
+    unsigned short *y[2];
+    for (int z = 0; z < 2; ++z) {
+      const Bf16State *b = M.bs[M.k(z)];
+      xa[z] = b->rawB, sa[z] = b->ssB[0], ta[z] = b->ssB[1], xb[z] = b->*w.skip, y[z] = b->*w.nxt;
+      if (ds) sb[z] = b->ssD[0], tb[z] = b->ssD[1];
+    }
+    const long P = (long)c2.hout * c2.wout;
+    PnvoTimed t(m, s, "bf16:residual", 0.0, 6.0 * nm * B * P * c2.coutp);
+    HIPCHK(m, launch_residual_bf16(xa, sa, ta, xb, ds ? sb : nullptr, ds ? tb : nullptr, B, P, c2.coutp, y, nm, s));
+    std::swap(w.cur, w.nxt);
+    w.skip = nullptr, w.skip_gn = nullptr;
   }
-  // (a11) Flatten + Linear + ReLU + output head: the fp32 split-K linear kernels on each model
-  for (int z = 0; z < nm; ++z) {
-    pnvo_handle h = hs[z];
+  return PNVO_OK;
+}
+
+// (a11) Flatten + Linear + ReLU + output head: the fp32 split-K linear kernels on each model
+int linears_bf16(const Models &M, int B, const FwdRequest &r, float *const *outs) {
+  for (int z = 0; z < M.nm; ++z) {
+    pnvo_handle h = M.hs[z];
+    const pnvo_config &c = h->cfg;
+    const Bf16State *b = M.bs[z];
     const int tm = h->timing;
     h->timing = 0;                                  // (their event records belong to the fp32 path's table)
     // (the output head rides on the hidden layer's split-K reduction when there is one: option head_fuse, as in the float32 forward)
     bool head_rode = false;
     const float *head_w = h->train != nullptr ? nullptr : h->head_w_plain;
-    rc = pnvo_run_conv(h, h->fc, B, {.x = bs[z]->comp_raw, .in_scale = bs[z]->ssC[0], .in_shift = bs[z]->ssC[1], .y = bs[z]->hid,
-                                     .y_cstride = c.hidden, .bias = h->fc_bias, .bias_row = c.act_embed ? r.actions : nullptr, .relu_out = 1,
-                                     .head_w = head_w, .head_out = (h->opt.head_fuse && c.out_dim <= 4 && head_w != nullptr) ? outs[z] : nullptr,
-                                     .head_rode = &head_rode, .s = s});
+    int rc = pnvo_run_conv(h, h->fc, B, {.x = b->comp_raw, .in_scale = b->ssC[0], .in_shift = b->ssC[1], .y = b->hid,
+                                         .y_cstride = c.hidden, .bias = h->fc_bias, .bias_row = c.act_embed ? r.actions : nullptr, .relu_out = 1,
+                                         .head_w = head_w, .head_out = (h->opt.head_fuse && c.out_dim <= 4 && head_w != nullptr) ? outs[z] : nullptr,
+                                         .head_rode = &head_rode, .s = r.s});
     if (rc == PNVO_OK && !head_rode)
-      rc = pnvo_run_conv(h, h->head, B, {.x = bs[z]->hid, .y = outs[z], .y_cstride = c.out_dim, .bias = h->head_bias, .s = s});
+      rc = pnvo_run_conv(h, h->head, B, {.x = b->hid, .y = outs[z], .y_cstride = c.out_dim, .bias = h->head_bias, .s = r.s});
     h->timing = tm;
-    if (rc != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, h->err);
+    if (rc != PNVO_OK) return z == 0 ? rc : pnvo_fail(M.hs[0], rc, h->err);
   }
   return PNVO_OK;
+}
+
+}  // namespace
+
+int pnvo_forward_bf16(pnvo_handle *hs, int nm, int B, const FwdRequest &r, float *const *outs) {
+  pnvo_handle m = hs[0];
+  Models M{hs, {nullptr, nullptr}, nm};
+  int rc;
+  for (int z = 0; z < nm; ++z) {
+    if ((rc = prepare(hs[z])) != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, hs[z]->err);
+    M.bs[z] = static_cast<Bf16State *>(hs[z]->bf);
+    if ((rc = ensure_ws(hs[z], B)) != PNVO_OK) return z == 0 ? rc : pnvo_fail(m, rc, hs[z]->err);
+  }
+  if (nm == 2 && (rc = dual_stem(hs[0], hs[1])) != PNVO_OK) return rc;
+  WalkBf16 w;
+  if ((rc = stem_bf16(M, B, r)) != PNVO_OK || (rc = blocks_bf16(M, B, w, r.s)) != PNVO_OK) return rc;
+  // (a10) compression conv + GroupNorm(1, C): fp32 output for the Linear layers; a pending tail in its stager, the block output not written
+  const ConvBRequest comp = w.skip ? ConvBRequest{.x = &Bf16State::rawB, .x_gn = &Bf16State::ssB, .skip = w.skip, .skip_gn = w.skip_gn, .y_gn = &Bf16State::ssC}
+                                   : ConvBRequest{.x = w.cur, .y_gn = &Bf16State::ssC};
+  if ((rc = run_conv_bf16(M, B, m->comp, comp, r.s)) != PNVO_OK) return rc;
+  return linears_bf16(M, B, r, outs);
 }

@@ -332,6 +332,7 @@ struct FwdRequest {
 // helpers implemented in pnvo_api.hip
 int pnvo_run_conv(pnvo_handle m, const Layer &l, int B, const ConvRequest &r);   // one conv + the GroupNorm finalisation that follows it
 ConvChoice pnvo_conv_choice(pnvo_handle m, const Layer &l, int B, const ConvAsk &ask);
+bool pnvo_ds_rides(pnvo_handle m, const Block &b, int B);         // does b's downsample conv ride on its first conv's launch (float32 forwards)?
 bool pnvo_conv_takes_tail(pnvo_handle m, const Layer &l, int B);   // does the schedule hand l a BlockTail (l on conv_x3, no tap, option tail)?
 void pnvo_pack_conv_weight_cinp(const float *oihw, int cout, int cin, int cinp, int kh, int kw, std::vector<float> &out);
 StemPlan pnvo_stem_plan(pnvo_handle m, bool train_fwd, const RawFrames &raw);

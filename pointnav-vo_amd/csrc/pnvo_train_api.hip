@@ -806,7 +806,7 @@ static int forward_blocks(pnvo_handle m, TrainState *t, int B, hipStream_t s) {
     const bool ds = b.ds >= 0;
     // the block's downsample conv rides on its first conv's launch (conv_x3_kernel DSF); the block input stays in memory here —
     // the backward pass reads it
-    const bool ds_ride = ds && K == 2 && pnvo_conv_choice(m, m->convs[ik[0]], B, {.ride = &m->convs[b.ds]}).family == ConvChoice::X3;
+    const bool ds_ride = pnvo_ds_rides(m, b, B);
     DsRide ride{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (ds_ride) {
       ConvSave &sd = w.cs[b.ds];
