@@ -23,6 +23,23 @@
 //   3  pooled stem keys (stem_mx.hip POOL): decode, * |scale| + shift, ReLU; pooled activations written to xout.
 // Also covers the 1x1 stride-2 downsample convs (KS = 1: the stager reads only the pixels the conv uses).
 // conv_x3_plan() takes a layer only when its launch has >= 192 workgroups (PNVO_CONV=x3 forces it).
+//
+// Addressing (conv_x3_kernel): every global access is a buffer operation on a descriptor built once per workgroup from scalar values —
+// the sample's plane of x, res, xout, y and ds_y (base + n * plane bytes, range one plane) and the packed weights wpk / ds_wpk — at a
+// 32-bit byte offset.  An offset with bit 31 set (X3_OOB) is out of every range: the load returns zeros, the store is dropped.
+//   stager    a patch pixel outside the image, or past the patch in a thread's last round, loads at X3_OOB — the zeros ARE the padding
+//             of mode 0; modes 1-3 still select on `in` behind the input transform (a mask multiply would turn an infinity into a NaN).
+//             The xout store of modes 2 / 3 goes to X3_OOB unless the tile owns the pixel (and xout's range is empty where the schedule
+//             wants no block output, or in the workgroups of another N-tile group).  A pixel slot past the patch writes its LDS words
+//             into the 16 pad bytes of a patch pixel (pitch = 2 CK + 16: nothing reads them): no branch around the round.  The walk is
+//             (LDS offset, plane offset, xout offset, in) per pixel, from 24-bit multiplies; it is recomputed per channel chunk — a
+//             register table of it has a run-time length, and the 16-row strips have no registers to spare for a bounded one.
+//   K loop    B fragments: the lane's constant offset in the vector offset, the running (tap, k-chunk) offset in the scalar offset,
+//             the piece in the immediate: no 64-bit VALU add per fragment and step.
+//   epilogue  one store loop: otab holds byte offsets from the tile's first pixel with bit 31 for an absent one; + the lane's channel once
+//             per M-tile; tile origin and N-tile in the scalar offset.  The sums keep their select and their order.
+// conv_x3p_kernel keeps its flat addressing (it serves only launches the row-streaming kernel leaves, option x3_rows=off).
+// Float operations on every value and their order are those of the flat-addressed form: tests/test_gpu_conv_x3_bits.py.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +69,21 @@ __device__ __forceinline__ unsigned pack2h(float a, float b) {
 }
 __device__ __forceinline__ float lo_f(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float hi_f(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+// Buffer addressing (file header; conv_rows.hip's descriptor recipe).  A plane stays below 2^31 bytes (tile_candidate), so an offset with
+// bit 31 set is out of every range.
+constexpr unsigned X3_OOB = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_rsrc(const void *base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ u32x4 x3_ldu(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+}
+__device__ __forceinline__ f32x4 x3_ldf(__amdgpu_buffer_rsrc_t r, unsigned voff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
+}
+__device__ __forceinline__ void x3_stf(__amdgpu_buffer_rsrc_t r, unsigned voff, f32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
+}
 }  // namespace
 
 // NP = 3: three bf16 pieces per operand, six product terms (every kept product exact).  NP = 2: two float16 pieces per operand
@@ -126,8 +158,22 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   const int pitch = CK * 2 + 16;                   // bytes per patch pixel in one piece plane (odd number of 16-byte units)
   const int plane = PR * PC * pitch;               // bytes of one piece plane
   const int npix = p.TR * p.TC;
-  // pixel table behind the three planes: [0] patch byte offset of tile pixel q's top-left tap; [1] element offset of its output
-  // pixel inside the sample's output plane, bit 31 set when the pixel does not exist
+  // the sample's planes of the activation tensors and the packed weights, one descriptor each (scalar registers only)
+  const unsigned xplane = (unsigned)(p.H * p.W * p.CIN) * 4u, yplane = (unsigned)(p.Ho * p.Wo * p.COUTP) * 4u;
+  const __amdgpu_buffer_rsrc_t rx = x3_rsrc(reinterpret_cast<const char *>(p.x) + (size_t)n * xplane, xplane);
+  const __amdgpu_buffer_rsrc_t rres = x3_rsrc(MODE == 2 ? reinterpret_cast<const char *>(p.res) + (size_t)n * xplane : nullptr, MODE == 2 ? xplane : 0u);
+  // (block output / pooled activations: written by the workgroups of the first N-tile group, where the schedule wants them at all —
+  //  an empty range drops every store)
+  const bool xo = MODE >= 2 && p.xout != nullptr && blockIdx.y == 0;
+  const __amdgpu_buffer_rsrc_t rxo = x3_rsrc(xo ? reinterpret_cast<const char *>(p.xout) + (size_t)n * xplane : nullptr, xo ? xplane : 0u);
+  const __amdgpu_buffer_rsrc_t ry = x3_rsrc(reinterpret_cast<const char *>(p.y) + (size_t)n * yplane, yplane);
+  const __amdgpu_buffer_rsrc_t rdy = x3_rsrc(DSF ? reinterpret_cast<const char *>(p.ds_y) + (size_t)n * yplane : nullptr, DSF ? yplane : 0u);
+  const unsigned wbytes = (unsigned)(p.CIN >> 4) * (unsigned)(p.COUTP >> 5) * (NP * 1024u);   // one tap of the B operand
+  const __amdgpu_buffer_rsrc_t rw = x3_rsrc(g_wpk, (unsigned)(KS * KS) * wbytes);
+  const __amdgpu_buffer_rsrc_t rdw = x3_rsrc(DSF ? g_ds_wpk : nullptr, DSF ? wbytes : 0u);
+  const unsigned ytile = (unsigned)((r0 * p.Wo + c0) * p.COUTP) * 4u;   // the tile's first output pixel inside the sample's plane (bytes)
+  // pixel table behind the three planes: [0] patch byte offset of tile pixel q's top-left tap; [1] byte offset of its output
+  // pixel from the tile's first one, bit 31 set when the pixel does not exist (X3_OOB: the store is dropped)
   // (KSW: the tables sit behind the partial-sum area of the K-split reduction as well: the epilogue reads them after it)
   const int tab_off = KSW ? max(NP * plane, 4 * MW * 4096) : NP * plane;
   unsigned *qtab = reinterpret_cast<unsigned *>(lds + tab_off);
@@ -137,7 +183,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     const int tr = q / p.TC, tc = q - tr * p.TC;
     qtab[e] = (unsigned)(((tr * CS) * PC + tc * CS) * pitch);
     const bool ok = e < npix && r0 + tr < p.Ho && c0 + tc < p.Wo;
-    otab[e] = (unsigned)((tr * p.Wo + tc) * p.COUTP) | (ok ? 0u : 0x80000000u);
+    otab[e] = ((unsigned)((tr * p.Wo + tc) * p.COUTP) * 4u) | (ok ? 0u : X3_OOB);
   }
 
   const int wn = p.wn;                                                   // wave grid: (NWV / wn) x wn
@@ -190,6 +236,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   const int cg = threadIdx.x & (G - 1), pl = threadIdx.x / G, PS = NTH / G;
   const int dr = PS / PC, dc = PS - dr * PC;
   const int nppix = PR * PC;
+  // the thread's walk over the patch starts here for every channel chunk; a pixel slot past the patch (last round) converts zeros
+  // into the 16 pad bytes behind a pixel of the thread's own column of slots — nobody reads them — instead of branching around the round
+  const int pr_first = pl / PC, pc_first = pl - pr_first * PC;
+  const unsigned cin4 = (unsigned)p.CIN * 4u;
+  const unsigned trash = (unsigned)(min(pl, nppix - 1) * pitch + CK * 2);
 
   unsigned long long c_stage = 0, c_mm = 0, t_0 = __builtin_readcyclecounter(), r_0 = wall_clock64();
   for (int ck0 = 0; ck0 < p.CIN; ck0 += CK) {
@@ -217,38 +268,36 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         }
       };
       load_ss();
-      int pr = pl / PC, pc = pl - pr * PC;
-      const long img = ((long)n * p.H * p.W) * p.CIN + ck0 + 8 * cg;
-      const float *xb = p.x + img;
-      // two pixels per thread and round; the loads of the next round are in flight while this one is split and stored
+      int pr = pr_first, pc = pc_first;
+      const unsigned cb = (unsigned)(ck0 + 8 * cg) * 4u;               // the thread's channel group inside a pixel (bytes)
+      // two pixels per thread and round; the loads of the next round are in flight while this one is split and stored.
+      // A pixel is three words: its LDS byte offset (the trash granule for a pixel past the patch), its byte offset in the sample's
+      // plane (X3_OOB outside the image: the loads return the zeros of the padding) and, modes 2 / 3, the same offset for the xout
+      // store (X3_OOB unless this tile owns the pixel).
       struct Round {
         f32x4 v[2][2], w[2][2];
-        unsigned off[2];
-        int gofs[2];
-        bool ok[2], in[2], own[2];
+        unsigned off[2], xofs[2];
+        bool in[2];
       };
       auto fetch = [&](int pix, Round &r) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int hi = hi0 + pr * PSTEP, wi = wi0 + pc * PSTEP;
-          r.ok[k] = pix + k * PS < nppix;
-          r.in[k] = r.ok[k] && hi >= 0 && hi < p.H && wi >= 0 && wi < p.W;
-          r.off[k] = (unsigned)((pr * PC + pc) * pitch + 16 * cg);
-          r.v[k][0] = r.v[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+          const bool ok = pix + k * PS < nppix;
+          r.in[k] = ok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+          r.off[k] = ok ? (unsigned)__umul24((unsigned)(pix + k * PS), (unsigned)pitch) + 16u * (unsigned)cg : trash;
+          // (24-bit multiplies: a plane below 2^31 bytes of >= 32 channels has fewer than 2^24 pixels)
+          const unsigned g = r.in[k] ? (unsigned)__umul24((unsigned)(__mul24(hi, p.W) + wi), cin4) + cb : X3_OOB;
           if (MODE >= 2) {
             // the tile owns the input pixels under its own outputs (stride 2: the 2 x 2 block of each): every pixel once
-            r.own[k] = r.in[k] && p.xout != nullptr && blockIdx.y == 0 && pr >= PAD && pr < PAD + p.TR * CS && pc >= PAD && pc < PAD + p.TC * CS;
-            r.gofs[k] = (hi * p.W + wi) * p.CIN;
+            const bool own = (unsigned)(pr - PAD) < (unsigned)(p.TR * CS) && (unsigned)(pc - PAD) < (unsigned)(p.TC * CS);
+            r.xofs[k] = own ? g : X3_OOB;
           }
-          if (r.in[k]) {
-            const float *src = xb + ((long)hi * p.W + wi) * p.CIN;
-            r.v[k][0] = *reinterpret_cast<const f32x4 *>(src);
-            r.v[k][1] = *reinterpret_cast<const f32x4 *>(src + 4);
-            if (MODE == 2) {
-              const float *rsrc = p.res + img + ((long)hi * p.W + wi) * p.CIN;
-              r.w[k][0] = *reinterpret_cast<const f32x4 *>(rsrc);
-              r.w[k][1] = *reinterpret_cast<const f32x4 *>(rsrc + 4);
-            }
+          r.v[k][0] = x3_ldf(rx, g);
+          r.v[k][1] = x3_ldf(rx, g + 16u);
+          if (MODE == 2) {
+            r.w[k][0] = x3_ldf(rres, g);
+            r.w[k][1] = x3_ldf(rres, g + 16u);
           }
           pr += dr;
           pc += dc;
@@ -261,7 +310,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
       auto split_store = [&](const Round &r) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-          if (!r.ok[k]) continue;
           float f[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
@@ -284,12 +332,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             }
             f[e] = t;
           }
-          if (MODE >= 2 && r.own[k]) {
-            float *dst = p.xout + img + r.gofs[k];
-            *reinterpret_cast<f32x4 *>(dst) = f32x4{f[0], f[1], f[2], f[3]};
-            *reinterpret_cast<f32x4 *>(dst + 4) = f32x4{f[4], f[5], f[6], f[7]};
+          if (MODE >= 2) {
+            x3_stf(rxo, r.xofs[k], f32x4{f[0], f[1], f[2], f[3]});
+            x3_stf(rxo, r.xofs[k] + 16u, f32x4{f[4], f[5], f[6], f[7]});
           }
-          if (NP == 2) {                                                 // two float16 pieces of the eight channels
+          if constexpr (NP == 2) {                                       // two float16 pieces of the eight channels
             if (in_scaled) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) f[e] *= in_mul;
@@ -304,22 +351,22 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             }
             *reinterpret_cast<u32x4 *>(lds + r.off[k]) = o0;
             *reinterpret_cast<u32x4 *>(lds + plane + r.off[k]) = o1;
-            continue;
-          }
-          u32x4 o0, o1, o2;                                              // the three bf16 pieces of the eight channels
+          } else {
+            u32x4 o0, o1, o2;                                            // the three bf16 pieces of the eight channels
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float a = f[2 * e], b = f[2 * e + 1];
-            const unsigned h = pack2(a, b);
-            const float ra = a - lo_f(h), rb = b - hi_f(h);
-            const unsigned m = pack2(ra, rb);
-            o0[e] = h;
-            o1[e] = m;
-            o2[e] = pack2(ra - lo_f(m), rb - hi_f(m));
+            for (int e = 0; e < 4; ++e) {
+              const float a = f[2 * e], b = f[2 * e + 1];
+              const unsigned h = pack2(a, b);
+              const float ra = a - lo_f(h), rb = b - hi_f(h);
+              const unsigned m = pack2(ra, rb);
+              o0[e] = h;
+              o1[e] = m;
+              o2[e] = pack2(ra - lo_f(m), rb - hi_f(m));
+            }
+            *reinterpret_cast<u32x4 *>(lds + r.off[k]) = o0;
+            *reinterpret_cast<u32x4 *>(lds + plane + r.off[k]) = o1;
+            *reinterpret_cast<u32x4 *>(lds + 2 * plane + r.off[k]) = o2;
           }
-          *reinterpret_cast<u32x4 *>(lds + r.off[k]) = o0;
-          *reinterpret_cast<u32x4 *>(lds + plane + r.off[k]) = o1;
-          *reinterpret_cast<u32x4 *>(lds + 2 * plane + r.off[k]) = o2;
         }
       };
       constexpr bool PIPE = !((MODE == 2 && (TW >= 6 || (M16 && !W8) || x3_wpe(MW, NW, NP) == 3 || DSF)) || (DSF && MW * NW == 4));   // (the block-tail stager of the 96-accumulator tile /
@@ -371,7 +418,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
       const int kcc = CK >> 4, kcp = CK >> 5;                            // k-chunks / k-chunk pairs per staged chunk
       const int nsteps = KS * KS * kcp;
       const unsigned kstep = (unsigned)ntt * (NP * 1024u);               // bytes of one k-chunk of B (all N-tiles, both pieces)
-      const char *wb_n = reinterpret_cast<const char *>(g_wpk) + (long)(ck0 >> 4) * kstep;
+      unsigned wb_n = (unsigned)(ck0 >> 4) * kstep;                       // the step's byte offset in the B operand: the loads' scalar offset
       unsigned toff_n = 0;
       int kc_n = 0, kw_n = 0;
       auto advance = [&]() {                                             // the step being fetched, as running offsets
@@ -381,7 +428,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         if (kc_n == kcp) {
           kc_n = 0;
           toff_n += (unsigned)(pitch - kcp * 64);
-          wb_n += (long)(kct - kcc) * kstep;
+          wb_n += (unsigned)(kct - kcc) * kstep;
           if (++kw_n == KS) {
             kw_n = 0;
             toff_n += (unsigned)((PC - KS) * pitch);
@@ -402,7 +449,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
         for (int j = 0; j < NW; ++j)
 #pragma unroll
-          for (int pc = 0; pc < NP; ++pc) b[pc][j] = *reinterpret_cast<const u32x4 *>(wb_n + (size_t)voff[j] + pc * 1024);
+          for (int pc = 0; pc < NP; ++pc) b[pc][j] = x3_ldu(rw, voff[j] + pc * 1024u, wb_n);
       };
       auto step = [&](u32x4 (*a)[MW], const u32x4 (*b)[NW]) {
 #pragma unroll
@@ -452,7 +499,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     // The step being fetched (one ahead of the one being multiplied), kept as running offsets: a division per step costs the
     // wave ~50 scalar instructions between two MFMA groups, and with one wave per SIMD (6 x 11 maps) nobody fills that gap.
     const unsigned kstep = (unsigned)ntt * (NP * 1024u);                 // bytes of one k-chunk of B (all N-tiles, NP pieces)
-    const char *wb_n = reinterpret_cast<const char *>(g_wpk) + (long)(ck0 >> 4) * kstep;
+    unsigned wb_n = (unsigned)(ck0 >> 4) * kstep;                       // the step's byte offset in the B operand: the loads' scalar offset
     unsigned toff_n = 0;                                                 // patch byte offset of the step's (tap, k-chunk)
     int kc_n = 0, kw_n = 0;
     auto advance = [&]() {
@@ -462,7 +509,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
       if (kc_n == kcc) {
         kc_n = 0;
         toff_n += (unsigned)(pitch - kcc * 32);
-        wb_n += (long)(kct - kcc) * kstep;
+        wb_n += (unsigned)(kct - kcc) * kstep;
         if (++kw_n == KS) {
           kw_n = 0;
           toff_n += (unsigned)((PC - KS) * pitch);
@@ -475,13 +522,13 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     // Small wave tiles only (one or two accumulator tiles: the fine plan's launches, the 32- / 64-channel stages): on the larger tiles
     // the ring was neutral at 256 pairs (2.275 against 2.270 ms) and cost the 128-pair training step 0.4 % (15-28 registers per variant).
     constexpr bool RING = NP == 2 && KS == 3 && MW * NW <= 2;
-    const char *wb_b = wb_n;                                             // RING: the B step being fetched
+    unsigned wb_b = wb_n;                                                // RING: the B step being fetched
     int kc_b = 0;
     auto advanceB = [&]() {
       wb_b += kstep;
       if (++kc_b == kcc) {
         kc_b = 0;
-        wb_b += (long)(kct - kcc) * kstep;
+        wb_b += (unsigned)(kct - kcc) * kstep;
       }
     };
     unsigned voff[NW];                                                   // lane's byte offset inside a k-chunk of B
@@ -491,7 +538,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
       for (int j = 0; j < NW; ++j)
 #pragma unroll
-        for (int pc = 0; pc < NP; ++pc) b[pc][j] = *reinterpret_cast<const u32x4 *>(wb_b + (size_t)voff[j] + pc * 1024);
+        for (int pc = 0; pc < NP; ++pc) b[pc][j] = x3_ldu(rw, voff[j] + pc * 1024u, wb_b);
     };
     // A fragments of M-tile i (three planes) / B fragments (three weight pieces per N-tile) of the step being fetched
     auto loadA = [&](int i, u32x4 (*a)[MW]) {
@@ -502,7 +549,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
       for (int j = 0; j < NW; ++j)
 #pragma unroll
-        for (int pc = 0; pc < NP; ++pc) b[pc][j] = *reinterpret_cast<const u32x4 *>(wb_n + (size_t)voff[j] + pc * 1024);
+        for (int pc = 0; pc < NP; ++pc) b[pc][j] = x3_ldu(rw, voff[j] + pc * 1024u, wb_n);
     };
     // One step: M-tile by M-tile; as soon as an M-tile's MFMAs are issued its A registers take the NEXT step's fragments, so
     // the LDS latency hides behind the other M-tiles' MFMAs
@@ -537,11 +584,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     // operand, [k-chunk][N-tile][piece][lane][8]; those of the chunk's first k-chunk are fetched before the main loop.
     u32x4 bd0[DSF ? NP : 1][NW], bd1[DSF ? NP : 1][NW];
     auto loadBd = [&](u32x4 (*b)[NW], int kc) {
-      const char *wd = reinterpret_cast<const char *>(g_ds_wpk) + (long)((ck0 >> 4) + kc) * kstep;
+      const unsigned wd = (unsigned)((ck0 >> 4) + kc) * kstep;
 #pragma unroll
       for (int j = 0; j < NW; ++j)
 #pragma unroll
-        for (int pc = 0; pc < NP; ++pc) b[pc][j] = *reinterpret_cast<const u32x4 *>(wd + (size_t)voff[j] + pc * 1024);
+        for (int pc = 0; pc < NP; ++pc) b[pc][j] = x3_ldu(rdw, voff[j] + pc * 1024u, wd);
     };
     if constexpr (KSW) {
       // this wave's quarter of the chunk's steps, B through a ring of three register sets (two steps ahead), A one step ahead
@@ -551,7 +598,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         kc_n = kc;
         kw_n = kw;
         toff_n = (unsigned)((kh * PC + kw) * pitch + kc * 32);
-        wb_n += ((long)tap * kct + kc) * kstep;
+        wb_n += (unsigned)(tap * kct + kc) * kstep;
         kc_b = kc;
         wb_b = wb_n;
       }
@@ -710,7 +757,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
   // ---- epilogue: raw output + per-(sample, tile, channel) GroupNorm partial sums (one writer per slot).  Runs once for the conv and
   // (DSF) once more for the downsample conv that rode on it: accumulators, output tensor, statistics and GroupNorm outputs of each.
   const int rr16 = lane >> 5;
-  const long ybase = (((long)n * p.Ho + r0) * p.Wo + c0) * p.COUTP;
   // t1 / t2: the wave's sums of channel nt * 32 + lane of its N-tile j over its rows, in lanes 0-31
   auto put_stats = [&](const float *t1, const float *t2, float *stats, const float *gamma, const float *beta, float *gscale, float *gshift, float *gmu,
                        float *grstd) {
@@ -749,7 +795,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
       }
     }
   };
-  auto emit = [&](f32x16 (*ac)[NW], float *yout, float *stats, const float *oscale_ptr, float oscale, const float *gamma, const float *beta,
+  auto emit = [&](f32x16 (*ac)[NW], const __amdgpu_buffer_rsrc_t &ryo, float *stats, const float *oscale_ptr, float oscale, const float *gamma, const float *beta,
                   float *gscale, float *gshift, float *gmu, float *grstd, bool again) {
     if (NP == 2) {                                                         // undo the weights' power-of-two scale (exact)
       const float os = (oscale_ptr != nullptr ? *oscale_ptr : oscale) * in_div;
@@ -767,37 +813,24 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     for (int i = 0; i < EMW; ++i) {
       const int mt = KSW ? wave : wave_m * MW + i;
       if (mt >= p.MT) continue;
+      // the lane's sixteen rows: byte offset of the pixel from the tile's first + the lane's channel; bit 31 (an absent pixel) survives
+      // the addition and drops the store.  Tile origin and N-tile are the store's scalar offset.
       u32x4 ent[4];
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) ent[g4] = *reinterpret_cast<const u32x4 *>(otab + mt * 32 + 8 * g4 + 4 * rr16);
-      unsigned flags = 0;
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) flags |= ent[g4][0] | ent[g4][1] | ent[g4][2] | ent[g4][3];
-      const bool whole = !__any((int)(flags >> 31));                       // wave-uniform
+      for (int g4 = 0; g4 < 4; ++g4) ent[g4] = *reinterpret_cast<const u32x4 *>(otab + mt * 32 + 8 * g4 + 4 * rr16) + (unsigned)((lane & 31) * 4);
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
         const int nt = wave_n * NW + j;
         if (nt >= ntt) continue;
-        const int co = nt * 32 + (lane & 31);
+        const unsigned so = ytile + (unsigned)nt * 128u;
         float s1 = 0.f, s2 = 0.f;
-        if (whole) {                                                       // every pixel of the M-tile exists: plain stores
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float v = ac[i][j][r];
-            (yout + ybase + co)[ent[r >> 2][r & 3]] = v;
-            s1 += v;
-            s2 = __builtin_fmaf(v, v, s2);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const unsigned e = ent[r >> 2][r & 3];
-            const bool ok = (int)e >= 0;
-            const float v = ok ? ac[i][j][r] : 0.f;
-            if (ok) (yout + ybase + co)[e] = v;
-            s1 += v;
-            s2 = __builtin_fmaf(v, v, s2);
-          }
+        for (int r = 0; r < 16; ++r) {
+          const unsigned e = ent[r >> 2][r & 3];
+          const float v = (int)e >= 0 ? ac[i][j][r] : 0.f;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ryo, e, so, 0);
+          s1 += v;
+          s2 = __builtin_fmaf(v, v, s2);
         }
         t1[j] += s1 + __shfl_xor(s1, 32);                                  // M-tiles of this wave, in order
         t2[j] += s2 + __shfl_xor(s2, 32);
@@ -818,20 +851,18 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     for (int i = 0; i < MW; ++i) {
       const int sub = m16_sub0 + i;
       if (sub >= mt16 || (i == MW - 1 && !m16_last)) continue;
-      const u32x4 ent = *reinterpret_cast<const u32x4 *>(otab + sub * 16 + 4 * (lane >> 4));
-      const bool whole = !__any((int)((ent[0] | ent[1] | ent[2] | ent[3]) >> 31));   // wave-uniform
+      const u32x4 ent = *reinterpret_cast<const u32x4 *>(otab + sub * 16 + 4 * (lane >> 4)) + (unsigned)((lane & 15) * 4);   // (+ the lane's channel)
       // stores of N-sub-tile j; the channel's sums over the sub-tile's 16 rows, in every lane group
       // (no a*b+c contraction of the scale into the sums: the wave grids must round alike, and the compiler decides per instantiation)
       auto sub_tile = [&](int j, float &s1, float &s2) {
 #pragma clang fp contract(off)
-        const int co = (wave_n * NWT + (j >> 1)) * 32 + 16 * (j & 1) + (lane & 15);
+        const unsigned so = ytile + (unsigned)((wave_n * NWT + (j >> 1)) * 32 + 16 * (j & 1)) * 4u;
         s1 = s2 = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const unsigned e = ent[r];
-          const bool ok = whole || (int)e >= 0;
-          const float v = ok ? acc16[M16 ? i : 0][M16 ? j : 0][r] * os : 0.f;
-          if (ok) (p.y + ybase + co)[e] = v;
+          const float v = (int)e >= 0 ? acc16[M16 ? i : 0][M16 ? j : 0][r] * os : 0.f;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, e, so, 0);
           s1 += v;
           s2 = __builtin_fmaf(v, v, s2);
         }
@@ -852,8 +883,8 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     }
     put_stats(t1, t2, p.stats, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd);
   } else
-  emit(acc, p.y, p.stats, p.oscale_ptr, g_oscale, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd, false);
-  if constexpr (DSF) emit(accd, p.ds_y, p.ds_stats, p.ds_oscale_ptr, g_ds_oscale, g_ds_gamma, g_ds_beta, p.ds_scale, p.ds_shift, p.ds_mu, p.ds_rstd, true);
+  emit(acc, ry, p.stats, p.oscale_ptr, g_oscale, g_gamma, g_beta, p.gn_scale, p.gn_shift, p.gn_mu, p.gn_rstd, false);
+  if constexpr (DSF) emit(accd, rdy, p.ds_stats, p.ds_oscale_ptr, g_ds_oscale, g_ds_gamma, g_ds_beta, p.ds_scale, p.ds_shift, p.ds_mu, p.ds_rstd, true);
   if (p.prof && lane == 0 && blockIdx.x == 13 && blockIdx.y == 0) {
     const unsigned long long t_f = __builtin_readcyclecounter();
     unsigned long long *d = p.prof + wave * 8;
@@ -1299,6 +1330,8 @@ ConvX3Plan tile_candidate(const ConvX3Problem &q, bool fine) {
   int mw = 0, nw = 0;
   if (q.CIN % 32 || q.COUTP % 32 || q.COUTP > 1024 || q.CIN > 1024) return {};
   if (!((ks == 3 && (stride == 1 || stride == 2)) || (ks == 1 && stride == 2))) return {};
+  // the kernels address a sample's plane with 32-bit byte offsets whose bit 31 means "absent" (as conv_rows32_candidate bounds its tensor)
+  if ((long)q.H * q.W * q.CIN * 4 >= (1L << 31) || (long)q.Ho * q.Wo * q.COUTP * 4 >= (1L << 31)) return {};
   const int ntt = q.COUTP / 32;
   const bool strip_shape = q.opt.strip && !fine && q.np == 2 && stride == 1 && ks == 3 && ntt == 4 && q.Wo >= 16 && q.Ho >= 8;
   // Operand bandwidth decides the wave tile: per wave and cycle the MFMAs want 16/NW bytes of A (LDS, 128 B/clk per CU) and
