@@ -269,6 +269,16 @@ int pnvo_dataset_pairs(const uint8_t *prev_rgb, const uint8_t *cur_rgb, const ui
                        const float *edges, float *rgb_pairs, float *depth_pairs, float *dd_pairs, float *tdv_pairs,
                        int32_t *err_flag, void *stream);
 
+/* The frame form of pnvo_dataset_pairs: the same M entries as SENSOR frames, the inputs of pnvo_train_forward_raw /
+ * pnvo_input_moments_raw — rgb_frames uint8 [M][2][H][W][3] and depth_frames float32 [M][2][H][W] (the float16 depth widened), entry
+ * m from sample src[m], a swap[m] != 0 entry as (cur, prev).  1.44 MB per 341x192 pair with the top-down pair tensor against 7.86 MB
+ * of pair tensors; the one-hot depth is not stored (the training step derives it from depth_frames with the edges it is given: pass
+ * it the edges pnvo_dataset_pairs would have compared with).  Either output may be NULL.  The top-down pair tensor of the same
+ * entries comes from pnvo_dataset_pairs with only tdv_pairs non-null.  err_flag is set when a depth is outside [0,1]. */
+int pnvo_dataset_frames(const uint8_t *prev_rgb, const uint8_t *cur_rgb, const uint16_t *prev_depth, const uint16_t *cur_depth,
+                        const int32_t *src, const int32_t *swap, int N, int M, int H, int W, uint8_t *rgb_frames, float *depth_frames,
+                        int32_t *err_flag, void *stream);
+
 /* ---- training step (BASELINE config 4).  One optimisation step of one action model, replacing the body of the
  * reference's training iteration: zero_grad / forward in train mode / loss / backward / optimizer.step()
  * (pointnav_vo/vo/engine/vo_cnn_regression_geo_invariance_engine.py:855-901; loss vo_cnn_engine.py:135-198; Adam
@@ -288,6 +298,25 @@ int pnvo_train_refresh(pnvo_handle h, void *stream);
  * update — and its all-reduces — with pnvo_input_moments). */
 int pnvo_train_forward(pnvo_handle h, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
                        const float *run_mean, const float *run_var, float *out, void *stream);
+
+/*
+ * pnvo_train_forward from the SENSOR frames (tensor contract of pnvo_forward_raw): rgb_frames uint8 [B][2][H][W][3] (NULL for models
+ * without rgb), depth_frames float32 [B][2][H][W], tdv float32 [B][H][W][2] (NULL without it).  No observation-pair tensors are
+ * built: the stem reads the frames in its operand fetch, and the training state records that the last forward came from frames (the
+ * frame pointers and the edges are kept) — pnvo_train_backward / pnvo_train_backward_from_hidden then run the stem's weight gradient on
+ * the same frames, so the caller keeps them alive and unchanged until the backward has run.
+ *   edges    HOST float[bins + 1], the bin edges of the one-hot depth (e_i <= d < e_{i+1}, last bin closed); NULL: float32(i / bins),
+ *            the navigation boundary's.  A step fed by the dataset passes the float16-rounded edges the dataset compares with.
+ *   err_flag device int32, may be NULL: set to 1 when a depth lies outside [0, 1]; never read by the library.
+ * Results are bit-identical to pnvo_build_obs_pairs (with these edges) + pnvo_train_forward + pnvo_train_backward.  The call makes no
+ * host wait of any kind: sensor frames are inside the stems' input contract by construction, so unlike pnvo_train_forward there is
+ * no stem event to wait for.  That holds for handles whose training step runs the 16-bit-matrix-core stem (the default models at
+ * option stem auto / mx, wgrad_stem mx, no input fallback engaged).  Every other handle (vo_cnn_wider, options stem=dd / stem=dense,
+ * wgrad_stem=fp32) is served by materialising the pairs into a workspace of the training state with the existing kernels and taking
+ * the pair path: same results as that path, the cost of the separate path (its wait included).
+ */
+int pnvo_train_forward_raw(pnvo_handle h, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const float *edges,
+                           int B, const float *run_mean, const float *run_var, float *out, int32_t *err_flag, void *stream);
 
 /* act_embed variants (vo_cnn_act_embed.py:63-72): the actions [B] (DEVICE int64, values in [0, n_acts]) of the NEXT
  * pnvo_train_forward / pnvo_train_backward pair; the caller keeps the buffer alive until the backward has run. */
@@ -316,6 +345,12 @@ int pnvo_train_grad_buckets(pnvo_handle h, uint64_t *first, uint64_t *count, int
  * out[c] = mean (x_c - center_c), out[C + c] = mean (x_c - center_c)^2, out: device [2C]. */
 int pnvo_input_moments(pnvo_handle h, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
                        const float *center, int power, float *out, void *stream);
+/* The same moments from the sensor frames (tensors, edges and err_flag as pnvo_train_forward_raw; power 1, 2 or 3): one pass over the
+ * frames, fp64 partial sums in a fixed order, no atomics.  Every term is the float32 value pnvo_input_moments forms from the pair
+ * tensors, so the two agree to the last float32 ulp or two (the fp64 sums run in a different order); handles the frame-reading
+ * kernels do not serve (see pnvo_train_forward_raw) run pnvo_input_moments on the materialised pairs. */
+int pnvo_input_moments_raw(pnvo_handle h, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const float *edges,
+                           int B, const float *center, int power, float *out, int32_t *err_flag, void *stream);
 
 /* RunningMeanAndVar.forward, training branch, for ONE process (running_mean_and_var.py:41-60; the multi-process branch
  * :27-38 needs its all-reduces between the steps and stays on the host): m12 = pnvo_input_moments(power 3, center = the

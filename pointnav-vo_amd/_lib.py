@@ -71,6 +71,7 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "pnvo_half_to_float": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pnvo_dataset_pairs": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p] * 7),
+    "pnvo_dataset_frames": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p] * 4),
     "pnvo_topdown_view_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "pnvo_topdown_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
@@ -80,6 +81,10 @@ _SIGNATURES = {
     "pnvo_train_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pnvo_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pnvo_train_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pnvo_input_moments_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_train_set_grad_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pnvo_train_grad_buckets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),

@@ -736,6 +736,62 @@ hipError_t launch_dataset_pairs(const unsigned char *prev_rgb, const unsigned ch
   return hipGetLastError();
 }
 
+// The frame form of dataset_pairs_kernel: entry m of the batch as SENSOR frames — rgb uint8 [M][2][npix][3], depth float32
+// [M][2][npix] (the float16 widened) — the inputs of pnvo_train_forward_raw; a swapped entry is (cur, prev).  Thread = one pixel of
+// one frame; blockIdx.y = entry, blockIdx.z = slot in the pair.
+struct DatasetFramesArgs {
+  const unsigned char *rgb[2];     // prev, cur: [N][npix*3]
+  const unsigned short *depth[2];  // prev, cur: [N][npix] float16 bits
+  const int *src, *swap;           // [M]
+  long npix;
+  int nsamples;                    // N
+  unsigned char *o_rgb;            // may be nullptr
+  float *o_depth;                  // may be nullptr
+  int *err_flag;
+};
+
+__global__ __launch_bounds__(256) void dataset_frames_kernel(const DatasetFramesArgs a) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  const int m = blockIdx.y, f = blockIdx.z;
+  if (p >= a.npix) return;
+  const int i = a.src[m];
+  if (i < 0 || i >= a.nsamples) return;                                   // (an entry that names no sample of the chunk: nothing is read)
+  const int which = f ^ (a.swap[m] != 0);
+  const long fo = ((long)m * 2 + f) * a.npix;                             // first pixel of the output frame
+  if (a.o_depth != nullptr) {
+    const float d = half_bits_to_float(a.depth[which][(long)i * a.npix + p]);
+    if (!(d >= 0.f && d <= 1.f) && a.err_flag != nullptr) *a.err_flag = 1;
+    a.o_depth[fo + p] = d;
+  }
+  if (a.o_rgb != nullptr) {
+    // frames start at any byte (npix * 3 per frame): bytes, three per thread (consecutive threads write consecutive bytes)
+    const unsigned char *r = a.rgb[which] + ((long)i * a.npix + p) * 3;
+    unsigned char *o = a.o_rgb + (fo + p) * 3;
+    o[0] = r[0];
+    o[1] = r[1];
+    o[2] = r[2];
+  }
+}
+
+hipError_t launch_dataset_frames(const unsigned char *prev_rgb, const unsigned char *cur_rgb, const unsigned short *prev_depth,
+                                 const unsigned short *cur_depth, const int *src, const int *swap, int N, int M, int H, int W,
+                                 unsigned char *o_rgb, float *o_depth, int *err_flag, hipStream_t s) {
+  DatasetFramesArgs a;
+  a.nsamples = N;
+  a.rgb[0] = prev_rgb;
+  a.rgb[1] = cur_rgb;
+  a.depth[0] = prev_depth;
+  a.depth[1] = cur_depth;
+  a.src = src;
+  a.swap = swap;
+  a.npix = (long)H * W;
+  a.o_rgb = o_rgb;
+  a.o_depth = o_depth;
+  a.err_flag = err_flag;
+  hipLaunchKernelGGL(dataset_frames_kernel, dim3((unsigned)((a.npix + 255) / 256), (unsigned)M, 2), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 // Boundary: raw simulator frames -> the observation-pair tensors of _compute_local_delta_states_from_vo
 // (base_trainer_with_vo.py:172-229): rgb uint8 [n][2][H][W][3] and depth float32 [n][2][H][W] (prev, cur) ->
 // rgb_pairs [n,H,W,6] (0..255 as float), depth_pairs [n,H,W,2], dd_pairs [n,H,W,2*bins] one-hot (float32 edges i/bins,
@@ -790,7 +846,7 @@ __global__ __launch_bounds__(256) void frame_pairs_kernel(const FramePairsArgs a
 }
 
 hipError_t launch_frame_pairs(const unsigned char *rgb, const float *depth, int n, int H, int W, int bins, float *o_rgb,
-                              float *o_depth, float *o_dd, int *err_flag, hipStream_t s) {
+                              float *o_depth, float *o_dd, int *err_flag, hipStream_t s, const float *edges) {
   if (bins < 0 || bins > 64) return hipErrorInvalidValue;
   FramePairsArgs a;
   a.rgb = rgb;
@@ -802,6 +858,8 @@ hipError_t launch_frame_pairs(const unsigned char *rgb, const float *depth, int 
   a.npix = (long)H * W;
   a.bins = bins;
   for (int k = 0; k <= bins; ++k) a.ed.e[k] = (k == bins ? 1.0f : (float)((double)k / (double)(bins > 0 ? bins : 1)));
+  if (edges != nullptr)                                                   // caller-defined (HOST) edges
+    for (int k = 0; k <= bins; ++k) a.ed.e[k] = edges[k];
   hipLaunchKernelGGL(frame_pairs_kernel, dim3((unsigned)((a.npix + 255) / 256), (unsigned)n), dim3(256), 0, s, a);
   return hipGetLastError();
 }

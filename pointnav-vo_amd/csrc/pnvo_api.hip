@@ -843,6 +843,8 @@ void pnvo_stem_mx_input(pnvo_handle m, int B, const float *const *src, const Raw
   const int bins = 10;                                             // the mx stem's K-slot layout (n_dd == 20)
   for (int i = 0; i < bins; ++i) a.edges[i] = (float)((double)i * 1.0 / (double)bins);   // base_trainer_with_vo.py:105-115
   a.edges[bins] = 1.0f;
+  if (raw.edges != nullptr)                                        // the caller's (pnvo_train_forward_raw: the dataset's float16-rounded edges)
+    for (int i = 0; i <= bins; ++i) a.edges[i] = raw.edges[i];
   a.edges[bins + 1] = 1.0f;
   a.src[0] = a.src[1] = a.src[2] = nullptr;
 }
@@ -2021,20 +2023,37 @@ bool raw_direct(pnvo_handle m, const float *depth_frames) {
 }
 
 int raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, int B, int32_t *err_flag, hipStream_t s) {
-  const pnvo_config &c = m->cfg;
-  if (B > m->rawws_cap) {
-    for (DevBuf<float> &q : m->rawws) q.reset();
-    const size_t px = (size_t)B * c.height * c.width;
-    if (c.n_rgb) HIPCHK(m, m->rawws[0].alloc(px * 6));
-    HIPCHK(m, m->rawws[1].alloc(px * 2));
-    if (c.n_dd) HIPCHK(m, m->rawws[2].alloc(px * (size_t)c.n_dd));
-    m->rawws_cap = B;
-  }
-  HIPCHK(m, launch_frame_pairs(c.n_rgb ? rgb_frames : nullptr, depth_frames, B, c.height, c.width, c.n_dd / 2, m->rawws[0], m->rawws[1],
-                               m->rawws[2], err_flag, s));
-  return PNVO_OK;
+  return pnvo_raw_materialise(m, rgb_frames, depth_frames, B, nullptr, err_flag, s);
 }
 }  // namespace
+
+extern "C++" {
+int pnvo_check_frames(pnvo_handle m, const char *entry, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, int B,
+                      const void *out) {
+  return check_frames(m, entry, rgb_frames, depth_frames, tdv, B, out);
+}
+
+int pnvo_raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, int B, const float *edges, int32_t *err_flag,
+                         hipStream_t s, DevBuf<float> *ws, int *cap) {
+  const pnvo_config &c = m->cfg;
+  if (ws == nullptr) {
+    ws = m->rawws;
+    cap = &m->rawws_cap;
+  }
+  if (B > *cap) {
+    for (int k = 0; k < 3; ++k) ws[k].reset();
+    *cap = 0;
+    const size_t px = (size_t)B * c.height * c.width;
+    if (c.n_rgb) HIPCHK(m, ws[0].alloc(px * 6));
+    HIPCHK(m, ws[1].alloc(px * 2));
+    if (c.n_dd) HIPCHK(m, ws[2].alloc(px * (size_t)c.n_dd));
+    *cap = B;
+  }
+  HIPCHK(m, launch_frame_pairs(c.n_rgb ? rgb_frames : nullptr, depth_frames, B, c.height, c.width, c.n_dd / 2, ws[0], ws[1], ws[2], err_flag,
+                               s, edges));
+  return PNVO_OK;
+}
+}  // extern "C++"
 
 int pnvo_forward_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const int64_t *actions, int B,
                      float *out, int32_t *err_flag, void *stream) {
@@ -2231,6 +2250,18 @@ int pnvo_dataset_pairs(const uint8_t *prev_rgb, const uint8_t *cur_rgb, const ui
   if (M == 0) return PNVO_OK;
   HIPCHK(nullptr, launch_dataset_pairs(prev_rgb, cur_rgb, prev_depth, cur_depth, tdv_frames, src, swap, N, M, H, W, bins, edges,
                                        rgb_pairs, depth_pairs, dd_pairs, tdv_pairs, err_flag, (hipStream_t)stream));
+  return PNVO_OK;
+}
+
+int pnvo_dataset_frames(const uint8_t *prev_rgb, const uint8_t *cur_rgb, const uint16_t *prev_depth, const uint16_t *cur_depth,
+                        const int32_t *src, const int32_t *swap, int N, int M, int H, int W, uint8_t *rgb_frames, float *depth_frames,
+                        int32_t *err_flag, void *stream) {
+  if (!prev_depth || !cur_depth || !src || !swap || N <= 0 || M < 0 || H <= 0 || W <= 0) return fail(nullptr, PNVO_ERR_ARG, "bad argument");
+  if (rgb_frames && (!prev_rgb || !cur_rgb)) return fail(nullptr, PNVO_ERR_ARG, "rgb frames requested without rgb frames of the chunk");
+  if (!rgb_frames && !depth_frames) return fail(nullptr, PNVO_ERR_ARG, "no output requested");
+  if (M == 0) return PNVO_OK;
+  HIPCHK(nullptr, launch_dataset_frames(prev_rgb, cur_rgb, prev_depth, cur_depth, src, swap, N, M, H, W, rgb_frames, depth_frames, err_flag,
+                                        (hipStream_t)stream));
   return PNVO_OK;
 }
 

@@ -112,7 +112,7 @@ struct StemMXArgs {
   const float *raw_depth;         // [B][2][H][W] float32; non-null selects the RAW stager
   int raw_flags;                  // bit 0: the model has the depth modality, bit 1: discretised depth
   int *raw_err;                   // device flag: a depth outside [0, 1]
-  float edges[12];                // bin edges e_0 .. e_10 of the one-hot depth (float32(i / 10))
+  float edges[12];                // bin edges e_0 .. e_10 of the one-hot depth (float32(i / 10), or RawFrames::edges)
   // developer ablations of stem_rs_kernel (option stem_dbg = 16 + bits; WRONG RESULTS, timing only)
   int dbg;
   // grouped forward (see ConvX3Args): operands of models 1 / 2 (stem_mx_kernel only)
@@ -428,7 +428,10 @@ hipError_t launch_ring_assemble(const unsigned char *up_rgb, const float *up_dep
                                 float *ring_dep, float *ring_tdv, const int *idx, int n, int H, int W, unsigned char *pair_rgb,
                                 float *pair_dep, float *pair_tdv, hipStream_t s);
 hipError_t launch_frame_pairs(const unsigned char *rgb, const float *depth, int n, int H, int W, int bins, float *o_rgb,
-                              float *o_depth, float *o_dd, int *err_flag, hipStream_t s);
+                              float *o_depth, float *o_dd, int *err_flag, hipStream_t s, const float *edges = nullptr);
+hipError_t launch_dataset_frames(const unsigned char *prev_rgb, const unsigned char *cur_rgb, const unsigned short *prev_depth,
+                                 const unsigned short *cur_depth, const int *src, const int *swap, int N, int M, int H, int W,
+                                 unsigned char *o_rgb, float *o_depth, int *err_flag, hipStream_t s);
 size_t topdown_workspace_bytes(int N, int H, int W);
 hipError_t launch_topdown(const float *depth, int N, int H, int W, int64_t in_fstride, int64_t in_pstride,
                           const float *consts_host, int rows_around_center, float *out, int64_t out_fstride,
@@ -477,7 +480,16 @@ struct WgradStemMXArgs {
   int tiles_x, tiles_y, tiles_per_wg, nwg;   // filled by wgrad_stem_mx_plan
   unsigned long long *prof;   // PNVO_WSM_PROF: phase cycle counters of one workgroup, or nullptr
 };
+// The same kernel fed by the SENSOR frames (pnvo_train_forward_raw): src[0..2] stay null, src[3] is the top-down pair tensor.
+struct WgradStemMXFrameArgs : WgradStemMXArgs {
+  const unsigned char *rgb_frames;   // [B][2][H][W][3] uint8, or nullptr (model without rgb)
+  const float *depth_frames;         // [B][2][H][W] float32
+  float edges[12];                   // bin edges e_0 .. e_10 of the one-hot depth (+ 1 pad)
+  int flags;                         // bit 0: the model has the depth modality, bit 1: the one-hot depth
+};
 void wgrad_stem_mx_plan(WgradStemMXArgs &a);
+hipError_t launch_wgrad_stem_mx_frames(const WgradStemMXFrameArgs &a, float *scratch, const float *sc_new, const float *sh_new,
+                                       const int *slot_ref, const int *slot_new, int cin, float *grad, hipStream_t s);
 size_t wgrad_stem_mx_scratch_floats(const WgradStemMXArgs &a);
 hipError_t launch_wgrad_stem_mx(const WgradStemMXArgs &a, float *scratch, const float *sc_new, const float *sh_new, const int *slot_ref,
                                 const int *slot_new, int cin, float *grad, hipStream_t s);
@@ -538,6 +550,20 @@ struct MomentsArgs {
   int pw;                   // 1: mean of (x - center), 2: mean of (x - center)^2, 3: both (out[0..C), out[C..2C))
   int nblk[4];              // filled by launch_moments: blocks of each tensor (proportional to its channel count)
 };
+// The same moments from the sensor frames (pnvo_input_moments_raw).  Quantity q: 0-5 rgb pair channel | 6-7 depth | 8-27 one-hot | 28-29 tdv.
+struct MomentsRawArgs {
+  const unsigned char *rgb;  // [B][2][H][W][3] or nullptr
+  const float *depth;        // [B][2][H][W]
+  const float *tdv;          // [B][H][W][2] or nullptr
+  int cof[30];               // reference channel of quantity q, or -1 (the model lacks it)
+  const float *center;       // [C] or nullptr
+  long npix, fpix;           // B*H*W, H*W
+  int pw;
+  int *err_flag;             // set when a depth lies outside [0, 1]
+  float edges[12];
+};
+constexpr int MOMENTS_RAW_BLOCKS = 1024;
+hipError_t launch_moments_raw(const MomentsRawArgs &a, int C, double *part, float *out, hipStream_t s);
 constexpr int MOMENTS_BLOCKS = 2048;   // partial slots per row: `part` holds 2 * C * MOMENTS_BLOCKS doubles
 hipError_t launch_moments(const MomentsArgs &a, int C, double *part, float *out, hipStream_t s);
 

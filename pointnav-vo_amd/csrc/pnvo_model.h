@@ -258,6 +258,7 @@ struct RawFrames {
   const unsigned char *rgb = nullptr;        // [B][2][H][W][3] uint8, or nullptr (model without rgb)
   const float *depth = nullptr;              // [B][2][H][W]; non-null: the call runs on sensor frames
   int *err = nullptr;                        // device flag: a depth outside [0, 1]
+  const float *edges = nullptr;              // HOST float[bins + 1]: bin edges of the one-hot depth, or nullptr: float32(i / bins)
 };
 
 // Which stem a forward of this handle launches and what follows from that.  The rule is written once, in pnvo_stem_plan; the stem
@@ -344,6 +345,13 @@ double pnvo_stem_in_bytes(pnvo_handle m, int B, const RawFrames &raw);   // algo
 int pnvo_launch_stem_mx(pnvo_handle m, const pnvo::StemMXArgs &a, int pieces, int ntiles, bool bf16_out, const GroupedFwd *grp, hipStream_t s);
 int pnvo_mark_stem(pnvo_handle m, hipStream_t s, const StemPlan &p);
 int pnvo_input_fallback(pnvo_handle m, hipStream_t s, bool *rerun);   // after the forward is enqueued: wait for the stem, re-run on the dense stem?
+// pnvo_api.hip: the observation pairs of B frame pairs into ws[0..2] (rgb | depth | one-hot with the HOST `edges`, nullptr:
+// float32(i / bins)), grown to B pairs when *cap is smaller — what every frame entry falls back on when the frame-reading kernels do
+// not serve the handle.  ws = nullptr: the inference entries' workspace m->rawws.
+int pnvo_raw_materialise(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, int B, const float *edges, int32_t *err_flag,
+                         hipStream_t s, pnvo::DevBuf<float> *ws = nullptr, int *cap = nullptr);
+int pnvo_check_frames(pnvo_handle m, const char *entry, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, int B,
+                      const void *out);
 void pnvo_train_free(pnvo_handle m);   // pnvo_train_api.hip
 const float *pnvo_train_weight_ptr(pnvo_handle m, const Layer &l);   // pnvo_train_api.hip: l's weight in the flat parameter buffer (a conv of m, m->fc, m->head), or nullptr
 // pnvo_api.hip: the forward up to the compression conv's raw NHWC output (m->comp_raw, channel-padded to m->comp_cp) and its per-sample

@@ -100,6 +100,15 @@ struct TrainState {
   int lastB = 0;
   TrainWs ws;
   const float *src[4] = {nullptr, nullptr, nullptr, nullptr};   // observation tensors of the last forward
+  // ... or, from_frames (pnvo_train_forward_raw on the frame-reading kernels), its sensor frames: src[3] is the top-down pair tensor,
+  // src[0..2] are null and the stem's weight gradient reads the frames with the same bin edges
+  bool from_frames = false;
+  const unsigned char *f_rgb = nullptr;
+  const float *f_depth = nullptr;
+  float f_edges[12] = {0};
+  // ... or, where those kernels do not serve the handle, the pairs materialised from them (kept until the backward has read them)
+  DevBuf<float> fpairs[3];
+  int fpairs_cap = 0;
   // dropout (pnvo_train_set_dropout): p, seed, forward counter
   float drop_p = 0.f;
   uint64_t drop_seed = 0, drop_step = 0;
@@ -484,6 +493,27 @@ WgradStemMXArgs wgrad_stem_mx_request(pnvo_handle m, const TrainState *t, int B)
   a.Wo = m->Ws;
   wgrad_stem_mx_plan(a);
   return a;
+}
+
+// the same launch from the sensor frames of the last forward
+WgradStemMXFrameArgs wgrad_stem_mx_frames_request(pnvo_handle m, const TrainState *t, int B) {
+  WgradStemMXFrameArgs a;
+  std::memset(&a, 0, sizeof(a));
+  static_cast<WgradStemMXArgs &>(a) = wgrad_stem_mx_request(m, t, B);
+  a.rgb_frames = t->f_rgb;
+  a.depth_frames = t->f_depth;
+  std::memcpy(a.edges, t->f_edges, sizeof(a.edges));
+  a.flags = (m->cfg.n_depth > 0 ? 1 : 0) | (m->cfg.n_dd > 0 ? 2 : 0);
+  return a;
+}
+
+// Do the frame-reading kernels serve this handle's training step — the 16-bit-matrix-core stem in the forward (stem plan MX) and
+// wgrad_stem_mx_kernel<FRAMES> in the backward?  Else every frame entry materialises the pairs into the handle's workspace and takes
+// the pair path (the rule of pnvo_forward_raw): same results as the pair path, the cost of the separate path.
+bool train_frames_direct(pnvo_handle m) {
+  const StemPlan sp = pnvo_stem_plan(m, true, {});
+  return m->train_mx && sp.kernel == StemPlan::MX && !sp.standin && m->opt.wgrad_stem != 1 && !m->dense_sticky &&
+         m->convs[0].coutp == 32 && (m->cfg.n_dd == 0 || m->cfg.n_dd == 20);
 }
 
 // floats of the largest weight-gradient scratch of a backward at B samples
@@ -884,13 +914,14 @@ static int forward_linears(pnvo_handle m, TrainState *t, int B, float *out, hipS
   return pnvo_run_conv(m, m->head, B, {.x = w.hid, .y = out, .y_cstride = c.out_dim, .bias = m->head_bias, .s = s});
 }
 
+// raw != nullptr: the sensor frames feed the stem (rgb / depth / dd are null; the caller checked them against the model)
 static int train_forward_body(pnvo_handle m, const float *rgb, const float *depth, const float *dd, const float *tdv, int B,
-                              const float *run_mean, const float *run_var, float *out, void *stream) {
+                              const float *run_mean, const float *run_var, float *out, void *stream, const RawFrames *raw = nullptr) {
   if (!m || !m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
   if (B <= 0 || !out) return pnvo_fail(m, PNVO_ERR_ARG, "bad batch / null output");
   const pnvo_config &c = m->cfg;
-  if ((c.n_rgb > 0) != (rgb != nullptr) || (c.n_depth > 0) != (depth != nullptr) || (c.n_dd > 0) != (dd != nullptr) ||
-      (c.n_tdv > 0) != (tdv != nullptr))
+  if (raw == nullptr && ((c.n_rgb > 0) != (rgb != nullptr) || (c.n_depth > 0) != (depth != nullptr) || (c.n_dd > 0) != (dd != nullptr) ||
+      (c.n_tdv > 0) != (tdv != nullptr)))
     return pnvo_fail(m, PNVO_ERR_ARG, "observation tensors do not match the model's observation_space");
   if (c.normalize && (!run_mean || !run_var)) return pnvo_fail(m, PNVO_ERR_ARG, "running statistics required");
   HIPCHK(m, hipSetDevice(m->device));
@@ -905,12 +936,19 @@ static int train_forward_body(pnvo_handle m, const float *rgb, const float *dept
   t->src[1] = depth;
   t->src[2] = dd;
   t->src[3] = tdv;
+  t->from_frames = raw != nullptr;
+  if (raw != nullptr) {
+    t->f_rgb = raw->rgb;
+    t->f_depth = raw->depth;
+    for (int i = 0; i < 12; ++i) t->f_edges[i] = i >= 10 ? 1.0f : raw->edges != nullptr ? raw->edges[i] : (float)((double)i * 1.0 / 10.0);
+    if (raw->edges != nullptr) t->f_edges[10] = raw->edges[10];
+  }
   if (c.normalize)   // RunningMeanAndVar buffers live on the device and change every step (running_mean_and_var.py:54-60)
     HIPCHK(m, launch_whiten_table(run_mean, run_var, t->d_ref_of_new, t->d_tensor_of_new, m->CPL, m->stem_sc, m->stem_sh, s));
   if ((rc = refresh_stem_dd(m, t, s)) != PNVO_OK) return rc;   // W/std table, indicator weights: both move every step
   TrainWs &w = t->ws;
   ConvSave &cs = w.cs[0];
-  if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
+  if ((rc = pnvo_run_stem(m, B, {.src = {t->src[0], t->src[1], t->src[2], t->src[3]}, .raw = raw ? *raw : RawFrames{}, .y = cs.raw, .ss = cs.ss, .mu = cs.mu, .rstd = cs.rstd,
                                  .train_fwd = true, .s = s})) != PNVO_OK)
     return rc;
   HIPCHK(m, launch_maxpool_train(cs.raw, cs.ss[0], cs.ss[1], B, m->Hs, m->Ws, m->convs[0].coutp, w.y[0], w.pool_idx, s));
@@ -1040,6 +1078,16 @@ static int backward_stem(pnvo_handle m, TrainState *t, int B, const float *dY, h
   }
   // option wgrad_stem=fp32: the float32-MFMA kernel; also once an input outside the exact-operand contract was met
   const bool stem_fp32 = m->opt.wgrad_stem == 1 || m->dense_sticky;
+  if (t->from_frames) {              // the forward read sensor frames: wgrad_stem_mx_kernel<FRAMES> reads them again, nothing else can
+    if (!train_frames_direct(m))
+      return pnvo_fail(m, PNVO_ERR_STATE, "the last forward came from sensor frames and an option moved the handle off the frame-reading "
+                                          "kernels before its backward: run pnvo_train_forward_raw again");
+    const WgradStemMXFrameArgs a = wgrad_stem_mx_frames_request(m, t, B);
+    if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+    PnvoTimed tm(m, s, tl.w.t_wgrad, 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
+    HIPCHK(m, launch_wgrad_stem_mx_frames(a, w.wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, t->grads + tl.w.off, s));
+    return PNVO_OK;
+  }
   if (m->train_mx && l.coutp == 32 && !stem_fp32) {
     const WgradStemMXArgs a = wgrad_stem_mx_request(m, t, B);
     if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
@@ -1208,6 +1256,25 @@ int pnvo_train_forward(pnvo_handle m, const float *rgb, const float *depth, cons
   return rerun ? train_forward_body(m, rgb, depth, dd, tdv, B, run_mean, run_var, out, stream) : PNVO_OK;
 }
 
+// pnvo_train_forward from the sensor frames.  On the frame-reading kernels nothing is waited for: frames are inside the stems' input
+// contract by construction (no event, no re-run), and the record on the training state tells the backward which stem ran.
+int pnvo_train_forward_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const float *edges, int B,
+                           const float *run_mean, const float *run_var, float *out, int32_t *err_flag, void *stream) {
+  if (int rc0 = pnvo_check_frames(m, "pnvo_train_forward_raw", rgb_frames, depth_frames, tdv, B, out)) return rc0;
+  if (!m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  if (!depth_frames) return pnvo_fail(m, PNVO_ERR_ARG, "pnvo_train_forward_raw: depth_frames is required");
+  const pnvo_config &c = m->cfg;
+  if (!train_frames_direct(m)) {
+    HIPCHK(m, hipSetDevice(m->device));
+    TrainState *t = TS(m);
+    if (int rc = pnvo_raw_materialise(m, rgb_frames, depth_frames, B, edges, err_flag, (hipStream_t)stream, t->fpairs, &t->fpairs_cap)) return rc;
+    return pnvo_train_forward(m, c.n_rgb ? t->fpairs[0] : nullptr, c.n_depth ? t->fpairs[1] : nullptr, c.n_dd ? t->fpairs[2] : nullptr, tdv, B,
+                              run_mean, run_var, out, stream);
+  }
+  const RawFrames raw{rgb_frames, depth_frames, err_flag, edges};
+  return train_forward_body(m, nullptr, nullptr, nullptr, tdv, B, run_mean, run_var, out, stream, &raw);
+}
+
 int pnvo_train_backward(pnvo_handle m, const float *grad_out, void *stream) { return run_backward(m, grad_out, nullptr, false, stream); }
 
 int pnvo_train_set_dropout(pnvo_handle m, float p, uint64_t seed) {
@@ -1277,6 +1344,47 @@ int pnvo_input_moments(pnvo_handle m, const float *rgb, const float *depth, cons
   a.npix = (long)B * c.height * c.width;
   a.pw = power;
   HIPCHK(m, launch_moments(a, m->C, t->ws.mom_part, out, (hipStream_t)stream));
+  return PNVO_OK;
+}
+
+// pnvo_input_moments from the sensor frames: one pass over the frames (moments_raw_partial_kernel) where the frame-reading kernels
+// serve the handle, else the pair kernel on the materialised pairs (bit-equal to pnvo_input_moments on pnvo_build_obs_pairs' tensors).
+int pnvo_input_moments_raw(pnvo_handle m, const uint8_t *rgb_frames, const float *depth_frames, const float *tdv, const float *edges, int B,
+                           const float *center, int power, float *out, int32_t *err_flag, void *stream) {
+  if (int rc0 = pnvo_check_frames(m, "pnvo_input_moments_raw", rgb_frames, depth_frames, tdv, B, out)) return rc0;
+  if (!m->train) return pnvo_fail(m, PNVO_ERR_STATE, "pnvo_train_attach first");
+  if (!depth_frames || power < 1 || power > 3) return pnvo_fail(m, PNVO_ERR_ARG, "bad argument");
+  HIPCHK(m, hipSetDevice(m->device));
+  const pnvo_config &c = m->cfg;
+  if (!train_frames_direct(m)) {
+    TrainState *t = TS(m);
+    if (int rc = pnvo_raw_materialise(m, rgb_frames, depth_frames, B, edges, err_flag, (hipStream_t)stream, t->fpairs, &t->fpairs_cap)) return rc;
+    return pnvo_input_moments(m, c.n_rgb ? t->fpairs[0] : nullptr, c.n_depth ? t->fpairs[1] : nullptr, c.n_dd ? t->fpairs[2] : nullptr, tdv, B,
+                              center, power, out, stream);
+  }
+  TrainState *t = TS(m);
+  int rc = ensure_train_ws(m, t, B);
+  if (rc != PNVO_OK) return rc;
+  MomentsRawArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rgb = rgb_frames;
+  a.depth = depth_frames;
+  a.tdv = tdv;
+  for (int &q : a.cof) q = -1;
+  for (int k = 0; k < m->CP; ++k) {
+    const int r = m->stem_ref_of_new[k];
+    if (r < 0) continue;
+    const int tn = m->stem_tensor_of_new[k], ch = m->stem_ch_of_new[k];
+    a.cof[tn == 0 ? ch : tn == 1 ? 6 + ch : tn == 2 ? 8 + ch : 28 + ch] = r;
+  }
+  a.center = center;
+  a.fpix = (long)c.height * c.width;
+  a.npix = (long)B * a.fpix;
+  a.pw = power;
+  a.err_flag = err_flag;
+  for (int i = 0; i < 12; ++i) a.edges[i] = i >= 10 ? 1.0f : edges != nullptr ? edges[i] : (float)((double)i * 1.0 / 10.0);
+  if (edges != nullptr) a.edges[10] = edges[10];
+  HIPCHK(m, launch_moments_raw(a, m->C, t->ws.mom_part, out, (hipStream_t)stream));
   return PNVO_OK;
 }
 

@@ -66,7 +66,9 @@ inline float host_bf16_to_float(unsigned short h) {
 // cast and _discretize_depth_func (base_trainer_with_vo.py:135-167,196-229) happen while staging, the 7.86 MB per pair of
 // observation tensors are never written or read (0.92 MB of frames + 0.52 MB of top-down view instead).  The one-hot depth
 // becomes two 2-byte LDS writes into a zeroed row: bin = the reference's (e_i <= d < e_{i+1}, last bin closed) from an
-// 11-entry edge table in LDS, bit-identical to discretize_depth_kernel.
+// 11-entry edge table in LDS, bit-identical to discretize_depth_kernel.  The edges are the launch's (StemMXArgs::edges): float32(i / 10)
+// for the inference entries, the caller's for the training forward from frames (pnvo_train_forward_raw: <2, ..> and <3, 1, false,
+// false, true>, raw output, mu / rstd kept by the finalisation).
 template <int PIECES, int NT, bool BF16OUT, bool POOL = false, bool RAW = false>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_mx_kernel(const StemMXArgs p) {
   constexpr bool EXTRA = PIECES >= 2;                      // float32(-grade) results: float modalities split on the A side too
@@ -851,6 +853,9 @@ hipError_t launch_stem_mx(const StemMXArgs &a, int pieces, int ntiles_n, bool bf
         hipLaunchKernelGGL((stem_mx_kernel<2, 1, false, true, true>), dim3(gx, (unsigned)ntiles_n), dim3(NTHREADS), ldsb, s, p);
       else
         hipLaunchKernelGGL((stem_mx_kernel<2, 1, false, false, true>), dim3(gx, (unsigned)ntiles_n), dim3(NTHREADS), ldsb, s, p);
+    } else if (pieces == 3 && !bf16_out && a.pool == nullptr) {   // the training forward on three bf16 pieces (option train_pieces=3,
+      const size_t ldsb = RED_OFF + 4 * 1 * 32 * 2 * sizeof(float) + 64;   //  or while the float16 operand is stale): raw output
+      hipLaunchKernelGGL((stem_mx_kernel<3, 1, false, false, true>), dim3(gx, (unsigned)ntiles_n), dim3(NTHREADS), ldsb, s, p);
     } else if (pieces == 1 && bf16_out && ntiles_n % 2 == 0) {
       const size_t ldsb = RED_OFF + 4 * 2 * 32 * 2 * sizeof(float) + 64;
       hipLaunchKernelGGL((stem_mx_kernel<1, 2, true, false, true>), dim3(gx, (unsigned)(ntiles_n / 2)), dim3(NTHREADS), ldsb, s, p);

@@ -1918,4 +1918,134 @@ hipError_t launch_moments(const MomentsArgs &a0, int C, double *part, float *out
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The same moments from the SENSOR frames (pnvo_input_moments_raw): uint8 rgb [B][2][H][W][3], float32 depth [B][2][H][W] and the
+// top-down pair tensor [B][H][W][2], ONE pass, no observation-pair tensors.  Every term is the float32 value moments_partial_kernel
+// forms for that channel — (float)byte / 255.0f - c, d - c, t - c — summed in fp64.  The one-hot channels are not formed per pixel: a
+// thread counts the pixels of each bin (the comparisons of discretize_depth_kernel with the launch's edges) and the block adds
+// n1 * fl(1 - c) + n0 * fl(0 - c) (and the squares) in fp64: the same float32 terms, not the algebraic p - c.
+// Quantity q of a pair pixel: 0-5 rgb (prev r g b, cur r g b) | 6-7 depth | 8-27 one-hot (prev bins, cur bins) | 28-29 top-down view.
+// Stage 1: a thread walks pair pixels gid, gid + T, ...; the block's 2 x 30 sums are reduced in a fixed order (butterfly inside a
+// wave, the four waves in turn) into part[row][block].  Stage 2 is moments_final_kernel's sum over the blocks.
+__global__ __launch_bounds__(256) void moments_raw_partial_kernel(const MomentsRawArgs a, int C, double *part) {
+  __shared__ double red[4][60];
+  __shared__ int cnt[4][21];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long T = (long)gridDim.x * 256;
+  float ctr[10];                                           // rgb 0-5, depth 6-7, top-down view 8-9
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const int c = a.cof[k < 8 ? k : 20 + k];
+    ctr[k] = (a.center != nullptr && c >= 0) ? a.center[c] : 0.f;
+  }
+  double s[10], q[10];
+  int nb[20], npx = 0;
+#pragma unroll
+  for (int k = 0; k < 10; ++k) s[k] = q[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 20; ++k) nb[k] = 0;
+  bool bad = false;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < a.npix; e += T) {
+    const long n = e / a.fpix, px = e - n * a.fpix;
+    float v[10];
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const long fi = (n * 2 + f) * a.fpix + px;
+      if (a.rgb != nullptr) {
+        const unsigned char *r = a.rgb + fi * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[3 * f + k] = (float)r[k] / 255.0f - ctr[3 * f + k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[3 * f + k] = 0.f;
+      }
+      const float d = a.depth[fi];
+      v[6 + f] = d - ctr[6 + f];
+      bad = bad || !(d >= 0.f && d <= 1.f);
+#pragma unroll
+      for (int k = 0; k < 10; ++k) {
+        const float lo = a.edges[k], hi = a.edges[k + 1];
+        nb[10 * f + k] += ((k == 9) ? (d >= lo && d <= hi) : (d >= lo && d < hi)) ? 1 : 0;
+      }
+    }
+    const f32x2 t = a.tdv != nullptr ? *reinterpret_cast<const f32x2 *>(a.tdv + 2 * e) : f32x2{0.f, 0.f};
+    v[8] = t[0] - ctr[8];
+    v[9] = t[1] - ctr[9];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const double x = (double)v[k];
+      s[k] += x;
+      q[k] += x * x;
+    }
+    ++npx;
+  }
+  if (bad && a.err_flag != nullptr) *a.err_flag = 1;
+  // fixed-order reduction: butterfly inside the wave, then the four waves in turn
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      s[k] += __shfl_xor(s[k], o);
+      q[k] += __shfl_xor(q[k], o);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 20; ++k) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) nb[k] += __shfl_xor(nb[k], o);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) npx += __shfl_xor(npx, o);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const int qn = k < 8 ? k : 20 + k;
+      red[wave][qn] = s[k];
+      red[wave][30 + qn] = q[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 20; ++k) cnt[wave][k] = nb[k];
+    cnt[wave][20] = npx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 60) {
+    const int qn = threadIdx.x % 30, pass = threadIdx.x / 30;
+    const int c = a.cof[qn];
+    if (c < 0) return;
+    double r;
+    if (qn >= 8 && qn < 28) {
+      const int n1 = cnt[0][qn - 8] + cnt[1][qn - 8] + cnt[2][qn - 8] + cnt[3][qn - 8];
+      const int n0 = cnt[0][20] + cnt[1][20] + cnt[2][20] + cnt[3][20] - n1;
+      const float cc = a.center != nullptr ? a.center[c] : 0.f;
+      const double e1 = (double)(1.0f - cc), e0 = (double)(0.0f - cc);
+      r = pass ? (double)n1 * (e1 * e1) + (double)n0 * (e0 * e0) : (double)n1 * e1 + (double)n0 * e0;
+    } else {
+      r = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+    part[((long)pass * C + c) * gridDim.x + blockIdx.x] = r;
+  }
+}
+
+// one wave per output row: the fixed-order fp64 sum of moments_final_kernel over the blocks; pw 1 / 2 pick the first / second sums
+__global__ __launch_bounds__(64) void moments_raw_final_kernel(const double *part, int nb, int C, int pw, long npix, float *out) {
+  const int row = blockIdx.x;
+  const int prow = pw == 2 ? C + row : row;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nb; k += 64) s += part[(long)prow * nb + k];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  if (threadIdx.x == 0) out[row] = (float)(s / (double)npix);
+}
+
+// `part`: 2 * C * MOMENTS_RAW_BLOCKS doubles
+hipError_t launch_moments_raw(const MomentsRawArgs &a, int C, double *part, float *out, hipStream_t s) {
+  long nb = (a.npix + 255) / 256;
+  if (nb > MOMENTS_RAW_BLOCKS) nb = MOMENTS_RAW_BLOCKS;
+  if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(moments_raw_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, a, C, part);
+  const int rows = a.pw == 3 ? 2 * C : C;
+  hipLaunchKernelGGL(moments_raw_final_kernel, dim3(rows), dim3(64), 0, s, part, (int)nb, C, a.pw, a.npix, out);
+  return hipGetLastError();
+}
+
 }  // namespace pnvo

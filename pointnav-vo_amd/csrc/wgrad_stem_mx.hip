@@ -21,9 +21,28 @@
 // registers, many instructions in flight); after the barrier all eight waves convert / split / transpose it into the operand
 // buffer and the next multiply starts.  Measured per tile (PNVO_WSM_PROF=1): DMA 14.5 k cycles (one 1-KiB instruction per
 // ~165 cycles = 6 B/cycle/CU), multiply 9.5-11.5 k, convert 5 k: 1.12 ms for 128 pairs against 2.07 ms on the fp32 pipe.
+//
+// Two instantiations of one kernel.  wgrad_stem_mx_kernel<false> is the above.  wgrad_stem_mx_kernel<true> (FRAMES) is what the
+// backward of pnvo_train_forward_raw launches: the loader wave fetches the same 31-pixel row segments from the SENSOR frames — two
+// uint8 rgb rows (3 B per pixel), two float32 depth rows, the top-down pair row: 46 16-byte pieces = 0.7 KB per patch row instead
+// of 234 = 3.7 KB, one wave instruction per row and one M0 per four rows — and the converter fills the SAME 48 operand rows: rows
+// 0-19 from the depth values with the launch's bin edges (e_i <= d < e_{i+1}, last bin closed: the comparisons of the forward's
+// RAW stager and of discretize_depth_kernel), rows 20-25 as uint8 - 128, the float rows as the same three-piece split, row 30 as
+// before; rows of a modality the model lacks stay zero.  Everything behind the operand buffer — the multiply, the fp64
+// cross-workgroup sum, the sc / sh fold — is shared code: the same products are summed in the same order, the gradient is
+// bit-identical to the pair form's (tests/test_gpu_train_frames.py).  Frame rows start at any byte (W * 3 B per rgb row): a piece
+// address is the row's first byte rounded DOWN to 8 — the alignment the pair form's pieces have — and the converter adds the
+// residual (0-7) back; a piece that would cross either end of its tensor reads the zero page and the converter takes the pixels
+// of such a region (inside the image, so inside the tensor) from global memory.
+// Measured per tile at 128 pairs (PNVO_WSM_PROF=1, profiles/train_from_frames.md): the loader wave's issue + wait fall from 14.5 k
+// to 6.5 k cycles, but the tile does not get shorter: the slowest multiplier wave needs ~17 k either way (multiply + barrier:
+// 16.9 k pairs, 17.2 k frames — the DMA of the pair form was hidden behind it by a few hundred cycles only), and the converter,
+// which derives the one-hot rows with comparisons and reads rgb by bytes, takes 7.9 k against 5.3 k.  1.26 ms against 1.12 ms:
+// the frame form buys the 5.5x smaller batch and the training forward without a host wait, not a faster weight gradient.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "pnvo_internal.h"
 
@@ -63,6 +82,23 @@ constexpr int RAW_ROW = 4096 + 16;                 // (+16: the rows on differen
 constexpr int RAW_OFF = BUF_BYTES;                 // raw buffer behind the operands
 constexpr int DY_OFF = RAW_OFF + PR * RAW_ROW, DY_ROW = 2048;
 constexpr int LDS_BYTES = DY_OFF + TH * DY_ROW;    // 163 248
+// FRAMES (the instantiation pnvo_train_forward_raw's backward launches): the same 31-pixel row segments fetched from the SENSOR
+// frames — uint8 rgb [B][2][H][W][3] and float32 depth [B][2][H][W] (prev, cur) — and the top-down pair tensor; the one-hot rows are
+// derived from the depth by the converter.  Frame rows start at any byte, the DMA pieces keep the 8-byte address alignment of the
+// pieces above: a region's first piece starts at its first byte rounded DOWN to 8 and the converter adds the residual (0-7) back.
+// Per patch row [rgb prev 7 pieces | rgb cur 7 | depth prev 8 | depth cur 8 | tdv 16] = 46 pieces (736 B against 3744 B): ONE wave
+// instruction, so four patch rows share an M0; row i of such a group sits 4 i lanes into its instruction's 1 KiB (row stride
+// 1024 + 64 B: the converter's rows on different banks).  A piece that would cross either end of its tensor reads the zero page;
+// the converter reads the pixels of such a row from global memory (they are inside the image, so inside the tensor).
+constexpr int FP_RGB = 7, FP_DEP = 8, FP_TDV = 16, FPIECES = 2 * FP_RGB + 2 * FP_DEP + FP_TDV;   // 46
+constexpr int FO_RGB = 0, FO_DEP = 2 * FP_RGB * 16, FO_TDV = FO_DEP + 2 * FP_DEP * 16;           // byte offsets inside a row: 0, 224, 480
+constexpr int FR_ROW = 1024 + 64;                  // rows of one M0 group
+static_assert(PR % 4 == 1, "the last M0 group is one row");
+static_assert(FPIECES + 3 * 4 <= 64, "four rows of a group, each 4 lanes further into its instruction");
+static_assert(7 + 31 * 3 <= FP_RGB * 16 && 4 + 31 * 4 <= FP_DEP * 16 && 4 + 31 * 8 <= FP_TDV * 16, "residual + 31 pixels fit the pieces");
+static_assert(((PR + 3) / 4 - 1) * RAW_ROW + 3 * FR_ROW + 1024 <= PR * RAW_ROW, "the frame rows fit the raw buffer");
+constexpr int ETAB_OFF = LDS_BYTES;                // FRAMES: the bin edges e_0 .. e_10 (+ 1 pad) behind everything else
+constexpr int LDS_BYTES_FRAMES = LDS_BYTES + 48;
 constexpr int NPOS = PR * 4;                       // (patch row, parity, jj group of 8) positions of the patch
 constexpr int NTHREADS = 512;
 
@@ -73,7 +109,9 @@ __device__ __forceinline__ float lo16(unsigned u) { return __builtin_bit_cast(fl
 __device__ __forceinline__ float hi16(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 }  // namespace
 
-__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad_stem_mx_kernel(const WgradStemMXArgs p) {
+template <bool FRAMES>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad_stem_mx_kernel(
+    const std::conditional_t<FRAMES, WgradStemMXFrameArgs, WgradStemMXArgs> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -83,6 +121,8 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))
 
   // rows 31 and 40-47 and the dYt pads are never written by the converter: zero the operand buffer once
   for (int e = threadIdx.x; e < BUF_BYTES / 16; e += NTHREADS) reinterpret_cast<u32x4 *>(lds)[e] = u32x4{0u, 0u, 0u, 0u};
+  if constexpr (FRAMES)
+    if (threadIdx.x < 12) reinterpret_cast<float *>(lds + ETAB_OFF)[threadIdx.x] = p.edges[threadIdx.x];   // (first read after a barrier)
 
   struct Tile {
     int n, oy0, ox0, hi0, wi0;
@@ -117,9 +157,30 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))
   // lane constants of the four instructions of a patch row (piece r = 64 i + lane): byte offset from the row's first patch
   // pixel in its tensor | tensor << 16 | patch column << 20 (dd only) | valid << 28; and of the two of a dY row
   int fc[4], dc[2];
+  // FRAMES, row i of an M0 group (lane = 4 i + piece): the lane's piece address is LINEAR in (sample, first patch pixel of the row) —
+  // fb + n * fns + pixel * fstr, rounded down to 8, + foff — so a row costs each lane one multiply-add, the rounding and two
+  // bounds compares, with no selection between tensors in the loop: [flo, fend) is the lane's tensor (empty: no piece / no tensor)
+  long fb[FRAMES ? 4 : 1], fns[FRAMES ? 4 : 1], flo[FRAMES ? 4 : 1], fend[FRAMES ? 4 : 1];
+  int fstr[FRAMES ? 4 : 1], foff[FRAMES ? 4 : 1];
   auto lane_consts = [&]() {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      if constexpr (FRAMES) {
+        const int r = lane - 4 * i;
+        const int reg = r < FP_RGB ? 0 : r < 2 * FP_RGB ? 1 : r < 2 * FP_RGB + FP_DEP ? 2 : r < 2 * FP_RGB + 2 * FP_DEP ? 3 : 4;
+        const int first = reg == 0 ? 0 : reg == 1 ? FP_RGB : reg == 2 ? 2 * FP_RGB : reg == 3 ? 2 * FP_RGB + FP_DEP : 2 * FP_RGB + 2 * FP_DEP;
+        const long tensor = reg < 2 ? (long)p.rgb_frames : reg < 4 ? (long)p.depth_frames : (long)p.src[3];
+        const int stride = reg < 2 ? 3 : reg < 4 ? 4 : 8;                     // bytes per pixel
+        const long per_n = (reg < 4 ? 2 : 1) * npix * stride;                 // bytes per sample
+        const bool valid = r >= 0 && r < FPIECES && tensor != 0;
+        fstr[i] = stride;
+        foff[i] = 16 * (r - first);
+        fns[i] = per_n;
+        fb[i] = tensor + ((reg == 1 || reg == 3) ? npix * stride : 0);        // (the cur frame follows the prev frame)
+        flo[i] = valid ? tensor : 1;
+        fend[i] = valid ? tensor + (long)p.B * per_n : 0;
+        continue;
+      }
       const int r = 64 * i + lane;
       int c, ten, pc = 0;
       if (r < 155) {
@@ -148,8 +209,33 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))
     const Tile T = tile_of(t);
     const char *zp = reinterpret_cast<const char *>(p.zero_page);
     const long tot_rgb = (long)p.B * npix * 24, tot_f = (long)p.B * npix * 8;
+    if constexpr (FRAMES) {
+      long ft[4];                                                              // the lane's address for pixel 0 of the tile's sample
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ft[i] = fb[i] + (long)T.n * fns[i];
 #pragma unroll 1
-    for (int row = 0; row < PR; ++row) {
+      for (int row0 = 0; row0 < PR; row0 += 4) {
+        const char *g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int hi = T.hi0 + row0 + i;
+          const bool rowok = row0 + i < PR && hi >= 0 && hi < p.H;
+          const int pin = hi * p.W + T.wi0;                                    // first patch pixel inside its frame (may be outside)
+          const long pa = ((ft[i] + (long)pin * fstr[i]) & ~7L) + foff[i];
+          const bool ok = rowok && pa >= flo[i] && pa + 16 <= fend[i];
+          g[i] = ok ? reinterpret_cast<const char *>(pa) : zp;
+        }
+        set_m0((unsigned)(RAW_OFF + (row0 >> 2) * RAW_ROW));
+        dma16_0(g[0]);
+        if (row0 + 1 < PR) {                                                  // (the last group is one row)
+          dma16_1(g[1]);
+          dma16_2(g[2]);
+          dma16_3(g[3]);
+        }
+      }
+    }
+#pragma unroll 1
+    for (int row = 0; row < (FRAMES ? 0 : PR); ++row) {
       const int hi = T.hi0 + row;
       const bool rowok = hi >= 0 && hi < p.H;
       const long pix0 = (long)T.n * npix + (long)hi * p.W + T.wi0;          // first patch pixel of the row (may be outside)
@@ -206,7 +292,143 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))
         const int hi = T.hi0 + pr;
         const bool rowok = hi >= 0 && hi < p.H;
         unsigned char *dst = lds + pr * XS_ROW + par * XS_PAR;
-        if (kind < 10) {
+        if constexpr (FRAMES) {
+          if (kind < 15) {
+            // the same operand rows from the frame pieces.  A region's bytes start `res` into its pieces (the loader rounded the
+            // address down to 8); a region whose pieces were not all fetched (they would have crossed an end of the tensor: the first
+            // rows of the first frame, the last of the last) is read from global memory instead, in-image pixels only.
+            const unsigned char *frow = lds + RAW_OFF + (pr >> 2) * RAW_ROW + (pr & 3) * FR_ROW;
+            const long pin = (long)hi * p.W + T.wi0;
+            const long fp0 = ((long)T.n * 2) * npix + pin;                    // the row's first patch pixel in the prev frame
+            struct Region {
+              const unsigned char *l;   // the region's first byte in LDS
+              bool edge;                // not all of its pieces were fetched
+            };
+            auto region = [&](const void *tensor, long tensor_bytes, long byte_off, int lds_off, int npieces) {
+              const long lo = (long)tensor, a = lo + byte_off, a0 = a & ~7L;
+              return Region{frow + lds_off + (int)(a - a0), a0 < lo || a0 + npieces * 16 > lo + tensor_bytes};
+            };
+            auto gmem = [&](const void *tensor, long byte_off) { return reinterpret_cast<const char *>(tensor) + byte_off; };
+            const long rgb_bytes = (long)p.B * npix * 6, f_bytes = (long)p.B * npix * 8;
+            // pixel e of the unit: patch column, "inside the image" (a modality the model lacks counts as outside), byte of the
+            // pixel inside a region.  The values come from LDS; ONE branch per unit re-reads an edge region from memory.
+            auto column = [&](int e) { return 2 * (8 * g + e) + par; };
+            auto inside = [&](int e) { return rowok && column(e) < PCOLS && T.wi0 + column(e) >= 0 && T.wi0 + column(e) < p.W; };
+            auto pixel = [&](int e) { return min(column(e), PCOLS - 1); };
+            f32x2 v[8];
+            if (kind < 10) {
+              // one-hot depth, channels 2 kind, 2 kind + 1: bins b0, b0 + 1 of frame f (e_i <= d < e_{i+1}, last bin closed)
+              const int f = kind >= 5 ? 1 : 0, b0 = 2 * (kind - 5 * f);
+              const Region r = region(p.depth_frames, f_bytes, (fp0 + f * npix) * 4, FO_DEP + f * FP_DEP * 16, FP_DEP);
+              const float *et = reinterpret_cast<const float *>(lds + ETAB_OFF);
+              const float e0 = et[b0], e1 = et[b0 + 1], e2 = et[b0 + 2];
+              const bool closed = b0 + 1 == 9, present = (p.flags & 2) != 0;
+              float d[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) d[e] = *reinterpret_cast<const float *>(r.l + 4 * pixel(e));
+              if (r.edge && present) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  if (inside(e)) d[e] = *reinterpret_cast<const float *>(gmem(p.depth_frames, (fp0 + f * npix) * 4 + 4 * pixel(e)));
+              }
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                const bool in = present && inside(e);
+                const bool h0 = d[e] >= e0 && d[e] < e1, h1 = closed ? (d[e] >= e1 && d[e] <= e2) : (d[e] >= e1 && d[e] < e2);
+                v[e] = f32x2{(in && h0) ? 1.f : 0.f, (in && h1) ? 1.f : 0.f};
+              }
+#pragma unroll
+              for (int j = 0; j < 2; ++j) {
+                const int slot = 2 * kind + j;
+                const u32x4 w = {pk(v[0][j], v[1][j]), pk(v[2][j], v[3][j]), pk(v[4][j], v[5][j]), pk(v[6][j], v[7][j])};
+                *reinterpret_cast<u32x4 *>(dst + slot * XS_SLOT + ((g ^ ((slot >> 3) & 1)) << 4)) = w;
+              }
+              continue;
+            }
+            const int type = kind - 10;
+            if (type < 3) {
+              // rgb pair channels 2 type, 2 type + 1 (prev r g b | cur r g b), uint8 - 128
+              const Region r0 = region(p.rgb_frames, rgb_bytes, fp0 * 3, FO_RGB, FP_RGB);
+              const Region r1 = region(p.rgb_frames, rgb_bytes, (fp0 + npix) * 3, FO_RGB + FP_RGB * 16, FP_RGB);
+              const int ca = 2 * type, cb = ca + 1;
+              const bool fa = ca >= 3, fb = cb >= 3;
+              const int oa = ca - 3 * fa, ob = cb - 3 * fb;
+              const bool present = p.rgb_frames != nullptr;
+              const Region &ra = fa ? r1 : r0, &rb = fb ? r1 : r0;
+              unsigned xa[8], xb[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                xa[e] = ra.l[3 * pixel(e) + oa];
+                xb[e] = rb.l[3 * pixel(e) + ob];
+              }
+              if ((r0.edge || r1.edge) && present) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  if (inside(e)) {
+                    xa[e] = (unsigned char)*gmem(p.rgb_frames, (fp0 + (fa ? npix : 0)) * 3 + 3 * pixel(e) + oa);
+                    xb[e] = (unsigned char)*gmem(p.rgb_frames, (fp0 + (fb ? npix : 0)) * 3 + 3 * pixel(e) + ob);
+                  }
+              }
+#pragma unroll
+              for (int e = 0; e < 8; ++e)   // (rgb is centred: outside stays 0, not -128)
+                v[e] = (present && inside(e)) ? f32x2{(float)xa[e] - 128.f, (float)xb[e] - 128.f} : f32x2{0.f, 0.f};
+            } else if (type == 3) {
+              // depth (prev, cur)
+              const Region r0 = region(p.depth_frames, f_bytes, fp0 * 4, FO_DEP, FP_DEP);
+              const Region r1 = region(p.depth_frames, f_bytes, (fp0 + npix) * 4, FO_DEP + FP_DEP * 16, FP_DEP);
+              const bool present = (p.flags & 1) != 0;
+#pragma unroll
+              for (int e = 0; e < 8; ++e)
+                v[e] = f32x2{*reinterpret_cast<const float *>(r0.l + 4 * pixel(e)), *reinterpret_cast<const float *>(r1.l + 4 * pixel(e))};
+              if ((r0.edge || r1.edge) && present) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  if (inside(e))
+                    v[e] = f32x2{*reinterpret_cast<const float *>(gmem(p.depth_frames, fp0 * 4 + 4 * pixel(e))),
+                                 *reinterpret_cast<const float *>(gmem(p.depth_frames, (fp0 + npix) * 4 + 4 * pixel(e)))};
+              }
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = (present && inside(e)) ? v[e] : f32x2{0.f, 0.f};
+            } else {
+              // top-down view pair
+              const Region r = region(p.src[3], f_bytes, ((long)T.n * npix + pin) * 8, FO_TDV, FP_TDV);
+              const bool present = p.src[3] != nullptr;
+#pragma unroll
+              for (int e = 0; e < 8; ++e)
+                v[e] = f32x2{*reinterpret_cast<const float *>(r.l + 8 * pixel(e)), *reinterpret_cast<const float *>(r.l + 8 * pixel(e) + 4)};
+              if (r.edge && present) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  if (inside(e))
+                    v[e] = f32x2{*reinterpret_cast<const float *>(gmem(p.src[3], ((long)T.n * npix + pin) * 8 + 8 * pixel(e))),
+                                 *reinterpret_cast<const float *>(gmem(p.src[3], ((long)T.n * npix + pin) * 8 + 8 * pixel(e) + 4))};
+              }
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = (present && inside(e)) ? v[e] : f32x2{0.f, 0.f};
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              unsigned h[4], m[4], l[4];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const float a = v[2 * k][j], b = v[2 * k + 1][j];
+                h[k] = pk(a, b);
+                const float ra = a - lo16(h[k]), rb = b - hi16(h[k]);
+                m[k] = pk(ra, rb);
+                l[k] = pk(ra - lo16(m[k]), rb - hi16(m[k]));
+              }
+              const int slot = 20 + 2 * type + j;
+              *reinterpret_cast<u32x4 *>(dst + slot * XS_SLOT + ((g ^ ((slot >> 3) & 1)) << 4)) = u32x4{h[0], h[1], h[2], h[3]};
+              if (type >= 3) {
+                const int sm = 32 + 2 * (type - 3) + j, sl = 36 + 2 * (type - 3) + j;
+                *reinterpret_cast<u32x4 *>(dst + sm * XS_SLOT + ((g ^ ((sm >> 3) & 1)) << 4)) = u32x4{m[0], m[1], m[2], m[3]};
+                *reinterpret_cast<u32x4 *>(dst + sl * XS_SLOT + ((g ^ ((sl >> 3) & 1)) << 4)) = u32x4{l[0], l[1], l[2], l[3]};
+              }
+            }
+            continue;
+          }
+        }
+        if (!FRAMES && kind < 10) {
           // the one-hot depth: channels 2 kind, 2 kind + 1 (slots 0-19)
           f32x2 v[8];
 #pragma unroll
@@ -220,7 +442,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))
             const u32x4 w = {pk(v[0][j], v[1][j]), pk(v[2][j], v[3][j]), pk(v[4][j], v[5][j]), pk(v[6][j], v[7][j])};
             *reinterpret_cast<u32x4 *>(dst + slot * XS_SLOT + ((g ^ ((slot >> 3) & 1)) << 4)) = w;
           }
-        } else if (kind < 15) {
+        } else if (!FRAMES && kind < 15) {
           // rgb 0-1, 2-3, 4-5 (slots 20-25, minus 128), depth (26-27), top-down view (28-29); the float modalities also
           // write their second and third bf16 pieces (rows 32-35, 36-39)
           const int type = kind - 10;
@@ -471,19 +693,21 @@ void wgrad_stem_mx_plan(WgradStemMXArgs &a) {
 
 size_t wgrad_stem_mx_scratch_floats(const WgradStemMXArgs &a) { return (size_t)(a.nwg + 1) * 49 * NROW * 32; }
 
+namespace {
 // `scratch`: wgrad_stem_mx_scratch_floats(a) floats (partials of every workgroup + the summed G)
-hipError_t launch_wgrad_stem_mx(const WgradStemMXArgs &a0, float *scratch, const float *sc_new, const float *sh_new, const int *slot_ref,
-                                const int *slot_new, int cin, float *grad, hipStream_t s) {
-  WgradStemMXArgs a = a0;
+template <bool FRAMES, typename ARGS>
+hipError_t launch_wgrad_stem_mx_form(const ARGS &a0, float *scratch, const float *sc_new, const float *sh_new, const int *slot_ref,
+                                     const int *slot_new, int cin, float *grad, hipStream_t s) {
+  ARGS a = a0;
   a.partial = scratch;
-  static unsigned long long *prof = nullptr;             // PNVO_WSM_PROF=1: per-phase cycles of workgroup 5, printed once
+  static unsigned long long *prof = nullptr;             // PNVO_WSM_PROF=1: per-phase cycles of workgroup 5, printed once per form
   if (std::getenv("PNVO_WSM_PROF") && !prof) {
     (void)hipMalloc((void **)&prof, 512);
     (void)hipMemset(prof, 0, 512);
   }
   a.prof = prof;
   float *G = scratch + (size_t)a.nwg * 49 * NROW * 32;
-  hipLaunchKernelGGL(wgrad_stem_mx_kernel, dim3((unsigned)a.nwg), dim3(NTHREADS), (size_t)LDS_BYTES, s, a);
+  hipLaunchKernelGGL(wgrad_stem_mx_kernel<FRAMES>, dim3((unsigned)a.nwg), dim3(NTHREADS), (size_t)(FRAMES ? LDS_BYTES_FRAMES : LDS_BYTES), s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(wgrad_stem_mx_sum_kernel, dim3(49 * NROW), dim3(256), 0, s, a.partial, a.nwg, G);
@@ -496,12 +720,25 @@ hipError_t launch_wgrad_stem_mx(const WgradStemMXArgs &a0, float *scratch, const
       (void)hipStreamSynchronize(s);
       (void)hipMemcpy(h, prof, 512, hipMemcpyDeviceToHost);
       const unsigned long long n = h[4] ? h[4] : 1;
-      std::fprintf(stderr, "[pnvo] wgrad_stem_mx cycles per tile (%llu tiles): wave 7 issue %llu wait %llu barrier %llu convert %llu | wave 0 "
+      std::fprintf(stderr, "[pnvo] wgrad_stem_mx%s cycles per tile (%llu tiles): wave 7 issue %llu wait %llu barrier %llu convert %llu | wave 0 "
                            "mfma+dma %llu wait %llu barrier %llu convert %llu | wave 3 mfma+dma %llu wait %llu barrier %llu convert %llu\n",
-                   n, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[8] / n, h[16] / n, h[24] / n, h[32] / n, h[11] / n, h[19] / n, h[27] / n, h[35] / n);
+                   FRAMES ? " (frames)" : "", n, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[8] / n, h[16] / n, h[24] / n, h[32] / n, h[11] / n, h[19] / n, h[27] / n, h[35] / n);
     }
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_wgrad_stem_mx(const WgradStemMXArgs &a, float *scratch, const float *sc_new, const float *sh_new, const int *slot_ref,
+                                const int *slot_new, int cin, float *grad, hipStream_t s) {
+  return launch_wgrad_stem_mx_form<false>(a, scratch, sc_new, sh_new, slot_ref, slot_new, cin, grad, s);
+}
+
+// The frame-reading instantiation: a.rgb_frames / a.depth_frames / a.src[3] in the place of the four pair tensors.
+hipError_t launch_wgrad_stem_mx_frames(const WgradStemMXFrameArgs &a, float *scratch, const float *sc_new, const float *sh_new,
+                                       const int *slot_ref, const int *slot_new, int cin, float *grad, hipStream_t s) {
+  if (a.depth_frames == nullptr) return hipErrorInvalidValue;
+  return launch_wgrad_stem_mx_form<true>(a, scratch, sc_new, sh_new, slot_ref, slot_new, cin, grad, s);
 }
 
 }  // namespace pnvo

@@ -145,12 +145,20 @@ class StatePairBatcher:
         self.tdv = NormalizedDepth2TopDownViewHabitat(**top_down_view_infos) if gen_top_down_view else None
         self._flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
-    def process_chunk(self, chunk, idxs=None, chunk_i=0):
+    def process_chunk(self, chunk, idxs=None, chunk_i=0, frames=False):
         """chunk: dict with the HDF5 datasets of one chunk (numpy): actions [N], prev_rgbs / cur_rgbs [N, H*W*3] uint8,
         prev_depths / cur_depths [N, H*W] float16, delta_positions [N,3], delta_rotations [N,4], and for the inversion modes
         prev/cur_global_positions [N,3], prev/cur_global_rotations [N,4].  Returns the reference's batch tuple as a dict
-        of tensors (observations on the device, float32 NHWC; bookkeeping on the host)."""
+        of tensors (observations on the device, float32 NHWC; bookkeeping on the host).
+
+        frames=True: the observations as SENSOR frames instead of the four pair tensors — "rgb_frames" uint8 [M,2,H,W,3],
+        "depth_frames" float32 [M,2,H,W] (pnvo_dataset_frames), "top_down_view_pairs" as before and "edges", this batcher's
+        float16-rounded bin edges (None without the one-hot depth): what VOTrainStep.forward_train_raw / step_raw and a frame batch
+        of GeoInvarianceTrainStep take (1.44 MB per 341x192 entry against 7.86 MB; the training step derives the one-hot depth
+        from depth_frames with `edges`, bit-identical to "discretized_depth_pairs").  The bookkeeping keys are the same."""
         H, W, dev = self.H, self.W, self.dev
+        if dev.type != "cuda":                                         # (the constructor's refusal, for either form)
+            raise RuntimeError("StatePairBatcher runs on an MI355X only")
         N = int(np.asarray(chunk["actions"]).shape[0])
         ent = entries_of_chunk(chunk["actions"], self.act_type, self.geo, idxs)
         M = len(ent)
@@ -178,25 +186,46 @@ class StatePairBatcher:
             pd, cd = up("prev_depths", np.int16), up("cur_depths", np.int16)         # float16 bit patterns
             assert prgb.shape == (N, H * W * 3) and pd.shape == (N, H * W), "chunk arrays do not match vis_size"
             dsrc, dswap = torch.from_numpy(src).to(dev), torch.from_numpy(swap).to(dev)
-            frames = None
+            tdv_frames = None
             if self.tdv is not None:
                 d32 = torch.empty((2 * N, H, W), device=dev, dtype=torch.float32)
                 _lib.check(_lib.lib.pnvo_half_to_float(_ptr(pd), N * H * W, _ptr(d32), st))
                 _lib.check(_lib.lib.pnvo_half_to_float(_ptr(cd), N * H * W, C.c_void_p(d32.data_ptr() + 4 * N * H * W), st))
-                frames = self.tdv.gen_top_down_view_batch(d32)
+                tdv_frames = self.tdv.gen_top_down_view_batch(d32)
             new = lambda c: torch.empty((M, H, W, c), device=dev, dtype=torch.float32)
+            if frames:
+                rgb_f = torch.empty((M, 2, H, W, 3), device=dev, dtype=torch.uint8)
+                dep_f = torch.empty((M, 2, H, W), device=dev, dtype=torch.float32)
+                tdv = new(2)
+                self._flag.zero_()
+                _lib.check(_lib.lib.pnvo_dataset_frames(_ptr(prgb), _ptr(crgb), _ptr(pd), _ptr(cd), _ptr(dsrc), _ptr(dswap), N, M, H, W,
+                                                        _ptr(rgb_f), _ptr(dep_f), _ptr(self._flag), st))
+                # the top-down pairs: the pair kernel with only tdv_pairs asked for
+                _lib.check(_lib.lib.pnvo_dataset_pairs(_ptr(prgb), _ptr(crgb), _ptr(pd), _ptr(cd), _ptr(tdv_frames), _ptr(dsrc),
+                                                       _ptr(dswap), N, M, H, W, 0, None, None, None, None, _ptr(tdv), None, st))
+                # (as the pair form: the one-hot depth is only defined for depth in [0, 1]; without it nothing asserts)
+                if self.bins and int(self._flag.item()):
+                    raise AssertionError("depth outside [0, 1] (regression_iter_dataset.py:33-34)")
+                return self._batch_dict(ent, tgt, src, chunk_i, M, rgb_frames=rgb_f, depth_frames=dep_f, top_down_view_pairs=tdv,
+                                        edges=self.edges)
             rgb, depth = new(6), new(2)
             dd = new(2 * self.bins) if self.bins else torch.zeros((M, H, W, 2), device=dev)   # :238-239 zeros when "none"
             tdv = new(2)
             self._flag.zero_()
-            _lib.check(_lib.lib.pnvo_dataset_pairs(_ptr(prgb), _ptr(crgb), _ptr(pd), _ptr(cd), _ptr(frames), _ptr(dsrc),
+            _lib.check(_lib.lib.pnvo_dataset_pairs(_ptr(prgb), _ptr(crgb), _ptr(pd), _ptr(cd), _ptr(tdv_frames), _ptr(dsrc),
                                                    _ptr(dswap), N, M, H, W, self.bins, self.edges, _ptr(rgb), _ptr(depth),
                                                    _ptr(dd) if self.bins else None, _ptr(tdv), _ptr(self._flag), st))
             if int(self._flag.item()):
                 raise AssertionError("depth outside [0, 1] (regression_iter_dataset.py:33-34)")
+        return self._batch_dict(ent, tgt, src, chunk_i, M, rgb_pairs=rgb, depth_pairs=depth, discretized_depth_pairs=dd,
+                                top_down_view_pairs=tdv)
+
+    @staticmethod
+    def _batch_dict(ent, tgt, src, chunk_i, M, **observations):
+        """The batch dict in the reference's key order: data types, the observation tensors, the bookkeeping."""
         t = torch.from_numpy(tgt)
         return dict(data_types=torch.tensor([e[3] for e in ent], dtype=torch.float32).unsqueeze(1),
-                    rgb_pairs=rgb, depth_pairs=depth, discretized_depth_pairs=dd, top_down_view_pairs=tdv,
+                    **observations,
                     actions=torch.tensor([e[2] for e in ent], dtype=torch.int64).unsqueeze(1),
                     delta_xs=t[:, 0:1], delta_ys=t[:, 1:2], delta_zs=t[:, 2:3], delta_yaws=t[:, 3:4],
                     dz_regress_masks=torch.ones((M, 1)), chunk_idxs=torch.full((M, 1), float(chunk_i)),

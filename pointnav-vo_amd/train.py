@@ -139,7 +139,55 @@ class VOTrainStep:
         h = self.model._handle
         _lib.check(_lib.lib.pnvo_input_moments(h, *ptrs, int(B), _ptr(center), int(power), _ptr(out), stream), h)
 
-    def _update_running_stats(self, ptrs, B, stream):
+    def _frame_ptrs(self, rgb_frames, depth_frames, top_down_view, edges):
+        """The sensor-frame inputs of the *_raw methods -> ([rgb, depth, tdv, edges] arguments of the pnvo_*_raw calls, tensors to
+        keep alive, B).  rgb_frames uint8 [B,2,H,W,3] (None for models without rgb), depth_frames float32 [B,2,H,W], top_down_view
+        float32 [B,H,W,2] (None without that modality), on the model's device; edges: None (float32(i / bins), the navigation
+        boundary's) or bins + 1 floats (a ctypes float array as StatePairBatcher.edges, or any sequence)."""
+        c, dev = self.model.cfg, self.dev
+        if depth_frames is None or not torch.is_tensor(depth_frames) or depth_frames.dim() != 4:
+            raise ValueError("depth_frames: expected a float32 tensor [B,2,H,W]")
+        B = depth_frames.shape[0]
+        keep = []
+
+        def ptr(t, dtype, shape, what):
+            if t is None:
+                return None
+            if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or tuple(t.shape) != shape:
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"{what}: expected {dtype} {shape} on {dev}, got {got}")
+            t = t.contiguous()
+            keep.append(t)
+            return _ptr(t)
+
+        if c.n_rgb and rgb_frames is None:
+            raise ValueError("rgb_frames: this model has the rgb modality, the frames are required")
+        if c.n_tdv and top_down_view is None:
+            raise ValueError("top_down_view: this model has the top_down_view modality, the pair tensor is required")
+        p_rgb = ptr(rgb_frames if c.n_rgb else None, torch.uint8, (B, 2, c.height, c.width, 3), "rgb_frames")
+        p_dep = ptr(depth_frames, torch.float32, (B, 2, c.height, c.width), "depth_frames")
+        p_tdv = ptr(top_down_view if c.n_tdv else None, torch.float32, (B, c.height, c.width, 2), "top_down_view")
+        p_edges = None
+        if edges is not None:
+            bins = c.n_dd // 2
+            vals = [float(x) for x in edges]
+            if bins == 0 or len(vals) != bins + 1:
+                raise ValueError(f"edges: expected {bins + 1} bin edges for this model's one-hot depth, got {len(vals)}")
+            p_edges = (C.c_float * (bins + 1))(*vals)
+        return [p_rgb, p_dep, p_tdv, p_edges], keep, B
+
+    def _input_moments_raw(self, fptrs, B, center, power, out, err_flag, stream):
+        """_input_moments from the sensor frames (pnvo_input_moments_raw: one pass over the frames)."""
+        h = self.model._handle
+        _lib.check(_lib.lib.pnvo_input_moments_raw(h, *fptrs, int(B), _ptr(center), int(power), _ptr(out), _ptr(err_flag), stream), h)
+
+    def _update_running_stats_raw(self, fptrs, B, err_flag, stream):
+        """_update_running_stats for a frame batch: the moments come from pnvo_input_moments_raw, everything behind them (the
+        single-process fused merge, the distributed branch) is _update_running_stats' own."""
+        self._update_running_stats(None, B, stream, moments=lambda center: self._input_moments_raw(fptrs, B, center, 3, self._m12,
+                                                                                                   err_flag, stream))
+
+    def _update_running_stats(self, ptrs, B, stream, moments=None):
         """RunningMeanAndVar.forward, training branch (running_mean_and_var.py:23-60): batch statistics from ONE pass over
         the observation tensors (_input_moments power 3: first and second moment about the current running mean c), the
         three all-reduces of :27-38 when torch.distributed is initialised, Chan's merge :44-60.  The reference's second
@@ -149,7 +197,9 @@ class VOTrainStep:
         distributed = dist.is_available() and dist.is_initialized()
         C_ = self._m12.numel() // 2
         center = rmv._mean.reshape(-1).to(torch.float32).contiguous()
-        if B > 0:
+        if B > 0 and moments is not None:
+            moments(center)
+        elif B > 0:
             self._input_moments(ptrs, B, center, 3, self._m12, stream)
         else:                      # a rank without entries for this action model (participate_absent): contributes zeros
             self._m12.zero_()
@@ -245,6 +295,64 @@ class VOTrainStep:
             else:
                 grad_out = grad_out.to(device=self.dev, dtype=torch.float32).contiguous()
             _lib.check(_lib.lib.pnvo_train_backward(h, _ptr(grad_out), stream), h)
+        return out, loss
+
+    def _forward_raw(self, rgb_frames, depth_frames, top_down_view, actions, edges, err_flag):
+        """The train-mode forward from sensor frames: RunningMeanAndVar update from pnvo_input_moments_raw, pnvo_train_forward_raw.
+        -> (out, stream); the caller is inside no device / no_grad context yet."""
+        ref = next(self.model.parameters())
+        if ref.device.type != "cuda":
+            raise RuntimeError("VOTrainStep runs on an MI355X only: move the model with .to('cuda') first (there is no CPU fallback)")
+        h = self.model._handle
+        fptrs, keep, B = self._frame_ptrs(rgb_frames, depth_frames, top_down_view, edges)
+        if err_flag is not None and (not torch.is_tensor(err_flag) or err_flag.dtype != torch.int32 or err_flag.device != self.dev):
+            raise ValueError(f"err_flag: expected an int32 tensor on {self.dev}")
+        self._set_actions(actions, B)
+        self._frames_kept = keep                  # the backward reads the frames again: alive until the next forward
+        out = torch.empty((B, self.model.cfg.out_dim), device=self.dev, dtype=torch.float32)
+        with torch.cuda.device(self.dev), torch.no_grad():
+            stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            self._sync_params(stream)
+            mean = var = None
+            if self.rmv is not None:
+                self._update_running_stats_raw(fptrs, B, err_flag, stream)
+                mean = self.rmv._mean.reshape(-1).contiguous()
+                var = self.rmv._var.reshape(-1).contiguous()
+            _lib.check(_lib.lib.pnvo_train_forward_raw(h, *fptrs, int(B), _ptr(mean), _ptr(var), _ptr(out), _ptr(err_flag), stream), h)
+        return out, stream
+
+    def forward_train_raw(self, rgb_frames, depth_frames, top_down_view=None, actions=None, edges=None, err_flag=None):
+        """forward_train from the SENSOR frames (pnvo_train_forward_raw): rgb_frames uint8 [B,2,H,W,3] (prev, cur; None for models
+        without rgb), depth_frames float32 [B,2,H,W] in 0..1, top_down_view float32 [B,H,W,2] (None without that modality).  No
+        observation-pair tensors are built, and the call never waits for the device.  edges: the bin edges of the one-hot depth —
+        None for float32(i / bins), StatePairBatcher.edges for a batch of the dataset.  err_flag: optional int32 device tensor [1],
+        set when a depth is outside [0, 1].  The frames must stay unchanged until the backward has run."""
+        return self._forward_raw(rgb_frames, depth_frames, top_down_view, actions, edges, err_flag)[0]
+
+    def forward_backward_raw(self, rgb_frames, depth_frames, top_down_view=None, target=None, grad_out=None, actions=None, edges=None,
+                             err_flag=None):
+        """forward_backward from the sensor frames (arguments as forward_train_raw and forward_backward)."""
+        h = self.model._handle
+        out, stream = self._forward_raw(rgb_frames, depth_frames, top_down_view, actions, edges, err_flag)
+        B = out.shape[0]
+        with torch.cuda.device(self.dev), torch.no_grad():
+            loss = None
+            if grad_out is None:
+                tgt = target.to(device=self.dev, dtype=torch.float32).contiguous()
+                grad_out = torch.empty_like(out)
+                _lib.check(_lib.lib.pnvo_mse_loss(_ptr(out), _ptr(tgt), int(B), out.shape[1], _ptr(self._loss),
+                                                  _ptr(grad_out), stream))
+                loss = self._loss.clone()
+            else:
+                grad_out = grad_out.to(device=self.dev, dtype=torch.float32).contiguous()
+            _lib.check(_lib.lib.pnvo_train_backward(h, _ptr(grad_out), stream), h)
+        return out, loss
+
+    def step_raw(self, rgb_frames, depth_frames, top_down_view=None, target=None, actions=None, edges=None, err_flag=None):
+        """step from the sensor frames — returns (out [B,3], loss tensor)."""
+        out, loss = self.forward_backward_raw(rgb_frames, depth_frames, top_down_view, target=target, actions=actions, edges=edges,
+                                              err_flag=err_flag)
+        self.optimizer_step()
         return out, loss
 
     def backward(self, grad_out):
@@ -439,8 +547,11 @@ class GeoInvarianceTrainStep:
 
     steps: {act: VOTrainStep} with act in {-1 (all actions), MOVE_FORWARD, TURN_LEFT, TURN_RIGHT}."""
 
-    def __init__(self, steps, invariance_types=("inverse_joint_train",), loss_inv_weight=1.0, metrics=False):
+    def __init__(self, steps, invariance_types=("inverse_joint_train",), loss_inv_weight=1.0, metrics=False, edges=None):
         self.steps = dict(steps)
+        # bin edges of the one-hot depth for FRAME batches (step()): None = float32(i / bins); a batch of StatePairBatcher passes the
+        # batcher's edges (the dataset compares float16 depth with float16-rounded edges)
+        self.edges = edges
         self.invariance_types = tuple(invariance_types)
         self.loss_inv_weight = float(loss_inv_weight)
         self.dev = next(iter(self.steps.values())).dev
@@ -471,7 +582,9 @@ class GeoInvarianceTrainStep:
                               slots=[(a, t) for a in acts for t in (types if types is not None else [None])])
 
     def step(self, batch, actions, data_types, targets, loss_weights=None, dz_regress_masks=None):
-        """batch: dict of NHWC device tensors [M,...] (the model's observation_pairs); actions [M] int; data_types [M]
+        """batch: dict of NHWC device tensors [M,...] (the model's observation_pairs) — or a FRAME batch, a dict with "rgb_frames"
+        uint8 [M,2,H,W,3], "depth_frames" float32 [M,2,H,W] and, for models with that modality, "top_down_view" float32 [M,H,W,2]
+        (every model then runs forward_train_raw on the entries of its action, with the constructor's `edges`); actions [M] int; data_types [M]
         (CUR_REL_TO_PREV / PREV_REL_TO_CUR); targets [M,3] (dx, dz, dyaw).  Returns (total loss tensor [1], preds [M,3]
         in batch order)."""
         dev = self.dev
@@ -505,7 +618,12 @@ class GeoInvarianceTrainStep:
                     continue
                 di = idx.to(dev)
                 sub = {k: v.index_select(0, di).contiguous() for k, v in batch.items()}
-                out = st.forward_train(sub, actions[idx] if st.model.cfg.act_embed else None)
+                acts = actions[idx] if st.model.cfg.act_embed else None
+                if "depth_frames" in sub:
+                    out = st.forward_train_raw(sub.get("rgb_frames"), sub["depth_frames"], sub.get("top_down_view"), actions=acts,
+                                               edges=self.edges)
+                else:
+                    out = st.forward_train(sub, acts)
                 preds.index_copy_(0, di, out)
                 coef = regression_coef(
                     idx.numel(), data_types[idx] if use_types else None,
