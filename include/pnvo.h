@@ -115,6 +115,12 @@ int pnvo_forward(pnvo_handle h, const float *rgb, const float *depth, const floa
  *                                                            then leaves NaN poses and fails the handle's next call)
  *   "graph"           0 | 1                                  replay the forward from a captured hipGraph
  *   "wgrad_stem"      mx | fp32        "pool_bwd" fused | separate        "dgrad" phase | masked        (training step)
+ *   "wgrad3"          x3 | fp32                              weight gradient of the 3x3 stride-1 convs on the bf16 matrix cores |
+ *                                                            on the float32 kernels
+ *   "wgrad"           auto | lds9 | generic                  float32 weight-gradient kernels: lds9 takes the nine-wave LDS kernel
+ *                                                            where the twelve-wave one would run (only what wgrad3 = fp32 leaves
+ *                                                            off the matrix cores), generic skips every LDS-staged kernel, the
+ *                                                            float32 stem kernel included
  *   "bf16_fuse"       on | off         "stem_dbg" <int>                                           (experiments)
  * Unknown keys / values return PNVO_ERR_ARG with the accepted spellings in pnvo_last_error.
  */
@@ -857,6 +863,14 @@ int pnvo_layer_kernel(pnvo_handle h, const char *name, int B, char *family, size
  * plan options force, strip, fine, w8, m16, ksplit, persistent workgroups, rows (options conv=x3, x3_strip ... x3_rows) and the CU count.
  * problem == NULL: the instance key of row n of the table of instantiated kernels, PNVO_ERR_ARG past its last row. */
 int pnvo_conv_x3_describe(const int *problem, int n, char *buf, size_t cap);
+
+/* Host only (no device, no handle): what the weight-gradient planner of the training step decides for one problem, as one line —
+ *   "<family> <instance> | grid <n> block <threads> lds <bytes> partial <scratch floats> reduce <grid of the reduce launch> | <geometry>"
+ * family: generic, lds9, mw12, stem_lds, x3.  problem: n = 16 ints — B, H, W, CIN, Ho, Wo, COUT, DYC (channels per pixel of the output
+ * gradient), KH, KW, stride, pad, mode (0 plain input, 1 producer GroupNorm + ReLU recomputed, 2 observation tensors), operand pieces
+ * (2: the float16 form is permitted, 3), option wgrad3 (1 x3, 0 fp32), option wgrad (0 auto, 1 lds9, 2 generic).
+ * problem == NULL: the instance name of row n of the table of instantiated kernels, PNVO_ERR_ARG past its last row. */
+int pnvo_wgrad_describe(const int *problem, int n, char *buf, size_t cap);
 
 int pnvo_timing_mode(pnvo_handle h, int mode);
 int pnvo_timing_read(pnvo_handle h, pnvo_kernel_time *entries, int cap, int *n_out);

@@ -1111,6 +1111,7 @@ const OptDef kOptions[] = {
     {"stem_dbg_pad", nullptr, &PnvoOptions::stem_dbg_pad, true, {{nullptr, 0}}},
     {"wgrad_stem", "PNVO_WGRAD_STEM", &PnvoOptions::wgrad_stem, false, {{"mx", 0}, {"fp32", 1}, {nullptr, 0}}},
     {"wgrad3", "PNVO_WGRAD3", &PnvoOptions::wgrad3, false, {{"x3", 1}, {"fp32", 0}, {nullptr, 0}}},
+    {"wgrad", "PNVO_WGRAD", &PnvoOptions::wgrad, false, {{"auto", 0}, {"lds9", 1}, {"generic", 2}, {nullptr, 0}}},
     {"pool_bwd", "PNVO_POOL_BWD", &PnvoOptions::pool_bwd, false, {{"fused", 1}, {"separate", 0}, {nullptr, 0}}},
     {"dgrad", "PNVO_DGRAD", &PnvoOptions::dgrad, false, {{"phase", 1}, {"masked", 0}, {nullptr, 0}}},
     {"bf16_fuse", nullptr, &PnvoOptions::bf16_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
@@ -2512,6 +2513,20 @@ int pnvo_conv_x3_describe(const int *problem, int n, char *buf, size_t cap) {
   q.opt = {.force = v[14], .strip = v[15], .fine = v[16], .w8 = v[17], .m16 = v[18], .ksw = v[19], .persist_wgs = v[20], .rows = v[21], .num_cus = v[22]};
   conv_x3_describe(&q, 0, buf, cap);
   return PNVO_OK;
+}
+
+int pnvo_wgrad_describe(const int *problem, int n, char *buf, size_t cap) {
+  if (!buf || cap == 0) return fail(nullptr, PNVO_ERR_ARG, "bad argument");
+  if (problem == nullptr) return wgrad_describe(nullptr, n, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;   // (past the last row: no message)
+  if (n != 16) return fail(nullptr, PNVO_ERR_ARG, "a weight-gradient problem has 16 fields");
+  const int *v = problem;
+  const WgradProblem q{.B = v[0], .H = v[1], .W = v[2], .CIN = v[3], .Ho = v[4], .Wo = v[5], .COUT = v[6], .DYC = v[7], .KH = v[8], .KW = v[9],
+                       .stride = v[10], .pad = v[11], .mode = v[12], .np = v[13], .wgrad3 = v[14], .wgrad = v[15]};
+  for (int k = 0; k < 11; ++k)
+    if (v[k] <= 0) return fail(nullptr, PNVO_ERR_ARG, "a weight-gradient problem's sizes are positive");
+  if (q.pad < 0 || q.mode < 0 || q.mode > 2 || (q.np != 2 && q.np != 3) || (q.wgrad3 | 1) != 1 || q.wgrad < 0 || q.wgrad > 2)
+    return fail(nullptr, PNVO_ERR_ARG, "mode is 0-2, np 2 or 3, wgrad3 0 or 1, wgrad 0-2");
+  return wgrad_describe(&q, 0, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;
 }
 
 int pnvo_timing_mode(pnvo_handle h, int mode) {

@@ -444,6 +444,36 @@ struct SrcLane {            // stem weight gradient: the observation-tensor slot
   float sc, sh;
 };
 
+// Weight gradients on the host, as conv_x3: a PROBLEM (shape, input mode, operand pieces the caller permits, the handle's two options)
+// -> wgrad_plan -> a PLAN (kernel family, the instance's row in the table of instantiated kernels, both launches' sizes, the geometry
+// the kernels read) -> wgrad_args + launch_wgrad.  The families:
+//   GENERIC   wgrad_kernel<TG, MODE>: any conv, taps in groups of TG (9 / 7 / 6 / 3 / 1), four units per workgroup
+//   LDS9      wgrad3_lds_kernel<MODE, STRIDE>: nine waves, 3x3 pad-1 convs of 32-channel multiples, two persistent workgroups per CU
+//   MW12      wgrad3_mw_kernel<MODE, STRIDE>: twelve waves, four units of (ci-tile, co-tile, row group) per workgroup, one per CU
+//   STEM_LDS  wgrad_stem_lds_kernel: the 7x7 stride-2 stem from the observation tensors in float32, one workgroup per CU
+//   X3        wgrad3_x3_kernel<MODE, NP> (wgrad_x3.hip): 3x3 stride-1 convs on the bf16 matrix cores, operands in NP pieces
+struct WgradProblem {
+  int B, H, W, CIN, Ho, Wo, COUT, DYC, KH, KW, stride, pad;
+  int mode;                 // 0 plain, 1 producer GN+ReLU recomputed, 2 gathered+whitened observation tensors
+  int np;                   // 2: the caller permits two float16 pieces per operand (granted to X3 alone); 3: three bf16 pieces
+  int wgrad3;               // option wgrad3: 1 X3 allowed, 0 float32 kernels
+  int wgrad;                // option wgrad: 0 auto, 1 lds9 (no X3 / MW12 once wgrad3 has excluded X3), 2 generic (no LDS family at all)
+};
+struct WgradPlan {
+  enum Family { GENERIC, LDS9, MW12, STEM_LDS, X3 } family = GENERIC;
+  int inst = -1;            // row of the instance table
+  unsigned grid = 0, reduce_grid = 0;   // main launch, wgrad_reduce_kernel
+  int block = 0;
+  size_t lds_bytes = 0, partial_floats = 0;
+  int np = 0;               // X3: 2 float16 pieces (three terms, dY scaled from its absolute maximum) or 3 bf16 pieces (six terms)
+  int TG = 0, groups = 0, ci_tiles = 0, pairs = 0, chunks = 0;
+  long pix_per_chunk = 0;
+  int TH = 0, TW = 0, tiles_x = 0, tiles_y = 0, tiles_per_chunk = 0;
+  // MW12: units per workgroup = cs ci-tiles x os co-tiles x rs row groups (= 4), workgroups = pair groups x wg_chunks, LDS buffers
+  int cs = 0, os = 0, rs = 0, wg_chunks = 0, nbuf = 0;
+  int xr_rsegs = 0;         // X3: row segments per strip
+};
+
 struct WgradArgs {
   const float *x;           // input activation [B,H,W,CIN] (mode 0/1)
   const float *in_scale, *in_shift;   // [B,CIN] (mode 1: relu(x*scale+shift))
@@ -452,24 +482,23 @@ struct WgradArgs {
   const float *zero_page;
   SrcLane src[32];          // mode 2
   int B, H, W, CIN, Ho, Wo, COUT, DYC, KH, KW, stride, pad;
-  int mode;                 // 0 plain, 1 producer GN+ReLU recomputed, 2 gathered+whitened observation tensors
-  int TG, groups, ci_tiles, pairs, chunks;
+  int mode;
+  int TG, groups, ci_tiles, pairs, chunks;      // the plan's geometry (wgrad_args)
   long pix_per_chunk;
-  // LDS-staged path (wgrad3_lds_kernel: 3x3 stride-1 convs with 32-channel multiples), chosen by wgrad_plan
-  int lds3, TH, TW, tiles_x, tiles_y, tiles_per_chunk;
-  // twelve-wave path (wgrad3_mw_kernel, lds3 = 4 / 5): units per workgroup = cs ci-tiles x os co-tiles x rs row groups (= 4),
-  // workgroups = pair groups x wg_chunks, LDS buffers
+  int TH, TW, tiles_x, tiles_y, tiles_per_chunk;
   int cs, os, rs, wg_chunks, nbuf;
   long grad_pitch;          // row pitch of the OIHW gradient tensor (0: cin_out * KH * KW)
-  // bf16-matrix-core path (wgrad_x3.hip, lds3 = 6): row segments per strip; use_x3 = 0 keeps wgrad_plan off it
-  int xr_rsegs, use_x3;
-  // np = 2: two float16 pieces per operand, three terms (X bounded by the forward's range check; dY scaled by 2^(14 - e) from
-  // dy_absmax, un-scaled on the accumulators); np = 3 (or 0): three bf16 pieces, six terms
-  int np;
-  const unsigned *dy_absmax;
+  int xr_rsegs;
+  const unsigned *dy_absmax;   // X3 with two float16 pieces: dY is scaled by 2^(14 - e) from this record, un-scaled on the accumulators
 };
-bool wgrad_x3_plan(WgradArgs &a);
-hipError_t launch_wgrad_x3(const WgradArgs &a, hipStream_t s);
+WgradPlan wgrad_plan(const WgradProblem &q);                                     // pure host code
+bool wgrad_x3_plan(const WgradProblem &q, WgradPlan &p);                          // the X3 branch (wgrad_x3.hip); false: shape outside it
+WgradArgs wgrad_args(const WgradProblem &q, const WgradPlan &p);                  // shape and the plan's geometry, every operand zero
+int wgrad_describe(const WgradProblem *q, int row, char *buf, size_t cap);       // one line for q's plan, or (q == nullptr) for a table row
+hipError_t launch_wgrad(const WgradArgs &a, const WgradPlan &p, float *grad, const int *ci_perm, int cin_out, hipStream_t s);
+inline size_t wgrad_partial_floats(const WgradPlan &p) { return p.partial_floats; }
+// the X3 kernel's instances for the table: wgrad_x3_launch<MODE, NP>
+template <int MODE, int NP> hipError_t wgrad_x3_launch(const WgradArgs &a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s);
 // Weight gradient of the 7x7 stem on the bf16 matrix cores (wgrad_stem_mx.hip): exact three-piece bf16 on both operands.
 struct WgradStemMXArgs {
   const float *src[4];        // rgb, depth, discretised depth, top-down view observation tensors (nullptr if absent)
@@ -493,9 +522,6 @@ hipError_t launch_wgrad_stem_mx_frames(const WgradStemMXFrameArgs &a, float *scr
 size_t wgrad_stem_mx_scratch_floats(const WgradStemMXArgs &a);
 hipError_t launch_wgrad_stem_mx(const WgradStemMXArgs &a, float *scratch, const float *sc_new, const float *sh_new, const int *slot_ref,
                                 const int *slot_new, int cin, float *grad, hipStream_t s);
-void wgrad_plan(WgradArgs &a);
-size_t wgrad_partial_floats(const WgradArgs &a);
-hipError_t launch_wgrad(const WgradArgs &a, float *grad, const int *ci_perm, int cin_out, hipStream_t s);
 
 hipError_t launch_gn_bwd(const float *x, const float *dout, const float *scale, const float *shift, const float *mu,
                          const float *rstd, const float *gamma, int B, long P, int C, int Creal, int G, int mask,

@@ -78,6 +78,7 @@ struct PnvoOptions {
   int stem_dbg = 0, stem_dbg_pad = 0;   // developer instrumentation of the stem kernels
   int wgrad_stem = 0;  // 0 bf16 matrix cores, 1 fp32
   int wgrad3 = 1;      // weight gradient of the 3x3 stride-1 convs: 1 bf16 matrix cores (wgrad_x3.hip), 0 fp32 kernels
+  int wgrad = 0;       // weight-gradient kernel families (wgrad_plan): 0 auto, 1 lds9 (nine-wave kernel where wgrad3 = 0 would take the twelve-wave one), 2 generic (no LDS-staged family, the float32 stem kernel included)
   int pool_bwd = 1;    // max-pool backward fused into the stem's GroupNorm backward
   int dgrad = 1;       // stride-2 backward-data as four parity-phase convs (0: masked taps)
   int bf16_fuse = 1;   // bf16 path: block tails fused

@@ -436,28 +436,30 @@ struct ConvInput {
   bool obs = false;                // the stem's gathered, whitened observation tensors
 };
 
-// The weight-gradient launch of layer l (a conv of m->convs, m->fc or m->head) at B samples, planned: input geometry = the forward
-// conv's.  ensure_train_ws sizes the scratch through it (null tensors), the backward launches through it.
-WgradArgs wgrad_request(pnvo_handle m, const TrainState *t, const Layer &l, int B, const ConvInput &in, const float *dy) {
+// The weight-gradient launch of layer l (a conv of m->convs, m->fc or m->head) at B samples: problem (input geometry = the forward
+// conv's), plan, and the kernel arguments with their operands.  ensure_train_ws sizes the scratch through it (null tensors), the backward
+// launches through it.  dy_absmax: the absolute-maximum record of dy where the caller permits the float16 form, else nullptr.
+struct WgradRequest {
+  WgradPlan plan;
+  WgradArgs args;
+};
+WgradRequest wgrad_request(pnvo_handle m, const TrainState *t, const Layer &l, int B, const ConvInput &in, const float *dy,
+                           const unsigned *dy_absmax = nullptr) {
   const pnvo_config &c = m->cfg;
-  WgradArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.use_x3 = m->opt.wgrad3;
-  a.B = B;
-  a.H = l.hin;
-  a.W = l.win;
-  a.Ho = l.hout;
-  a.Wo = l.wout;
-  a.COUT = l.cout;
-  a.KH = l.k;
-  a.KW = l.kw;
-  a.stride = l.stride;
-  a.pad = l.pad;
-  a.dy = dy;
-  a.DYC = &l == &m->head ? 8 : &l == &m->fc ? c.hidden : l.coutp;       // dout8 / gh / a conv's raw-output gradient
+  WgradProblem q{.B = B, .H = l.hin, .W = l.win, .Ho = l.hout, .Wo = l.wout, .COUT = l.cout, .KH = l.k, .KW = l.kw, .stride = l.stride, .pad = l.pad};
+  q.DYC = &l == &m->head ? 8 : &l == &m->fc ? c.hidden : l.coutp;       // dout8 / gh / a conv's raw-output gradient
   // channels per pixel of what the kernel reads.  The hidden layer reads the channel-PADDED compression map (H/W/CIN = fh, fw,
   // comp_cp tell the kernel the real row pitch); comp_cp is comp_c rounded up to whole 32-channel tiles, so the plan is the same.
-  a.CIN = in.obs ? 32 : &l == &m->fc ? m->comp_cp : l.cin;
+  q.CIN = in.obs ? 32 : &l == &m->fc ? m->comp_cp : l.cin;
+  q.mode = in.obs ? 2 : in.gn != nullptr ? 1 : 0;
+  q.np = dy_absmax != nullptr ? 2 : 3;
+  q.wgrad3 = m->opt.wgrad3;
+  q.wgrad = m->opt.wgrad;
+  WgradRequest r;
+  r.plan = wgrad_plan(q);          // picks the kernel by mode, geometry and the two options
+  WgradArgs &a = r.args = wgrad_args(q, r.plan);
+  a.dy = dy;
+  if (r.plan.np == 2) a.dy_absmax = dy_absmax;
   if (in.obs) {                    // mode 2 reads its per-channel whitening from the device tables
     const int nsrc[4] = {c.n_rgb, c.n_depth, c.n_dd, c.n_tdv};
     for (int k = 0; k < 32; ++k) {
@@ -466,17 +468,14 @@ WgradArgs wgrad_request(pnvo_handle m, const TrainState *t, const Layer &l, int 
     }
     a.in_scale = m->stem_sc;
     a.in_shift = m->stem_sh;
-    a.mode = 2;
   } else if (in.gn != nullptr) {
     a.x = in.gn->raw;
     a.in_scale = in.gn->ss[0];
     a.in_shift = in.gn->ss[1];
-    a.mode = 1;
   } else {
     a.x = in.x;
   }
-  wgrad_plan(a);                   // picks the kernel by mode and geometry
-  return a;
+  return r;
 }
 
 // stem weight gradient on the bf16 matrix cores
@@ -520,9 +519,9 @@ bool train_frames_direct(pnvo_handle m) {
 size_t wgrad_scratch_floats(pnvo_handle m, const TrainState *t, int B) {
   size_t n = 0;
   for (size_t li = 0; li < m->convs.size(); ++li)
-    n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->convs[li], B, ConvInput{.obs = li == 0}, nullptr)));
-  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->fc, B, {}, nullptr)));
-  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->head, B, {}, nullptr)));
+    n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->convs[li], B, ConvInput{.obs = li == 0}, nullptr).plan));
+  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->fc, B, {}, nullptr).plan));
+  n = std::max(n, wgrad_partial_floats(wgrad_request(m, t, m->head, B, {}, nullptr).plan));
   if (m->train_mx) n = std::max(n, wgrad_stem_mx_scratch_floats(wgrad_stem_mx_request(m, t, B)));
   return n;
 }
@@ -716,12 +715,13 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
   return PNVO_OK;
 }
 
-int run_wgrad(pnvo_handle m, TrainState *t, WgradArgs &a, const Weight &w, const int *perm, int cin_out, hipStream_t s) {
-  if (wgrad_partial_floats(a) > t->ws.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+int run_wgrad(pnvo_handle m, TrainState *t, WgradRequest &r, const Weight &w, const int *perm, int cin_out, hipStream_t s) {
+  WgradArgs &a = r.args;
+  if (wgrad_partial_floats(r.plan) > t->ws.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
   a.partial = t->ws.wg_partial;
   a.zero_page = m->zero_page;
   PnvoTimed tm(m, s, w.t_wgrad, 2.0 * (double)a.B * a.Ho * a.Wo * a.COUT * a.CIN * a.KH * a.KW, 0.0);
-  HIPCHK(m, launch_wgrad(a, t->grads + w.off, perm, cin_out, s));
+  HIPCHK(m, launch_wgrad(a, r.plan, t->grads + w.off, perm, cin_out, s));
   return PNVO_OK;
 }
 
@@ -980,7 +980,7 @@ static int backward_head(pnvo_handle m, TrainState *t, int B, const float *grad_
   TrainWs &w = t->ws;
   HIPCHK(m, launch_padcopy(grad_out, B, c.out_dim, 8, w.dout8, s));
   HIPCHK(m, launch_colsum(grad_out, B, c.out_dim, c.out_dim, t->grads + t->head.b.off, s));
-  WgradArgs a = wgrad_request(m, t, m->head, B, {.x = t->drop_p > 0.f ? w.hdrop : w.hid}, w.dout8);
+  WgradRequest a = wgrad_request(m, t, m->head, B, {.x = t->drop_p > 0.f ? w.hdrop : w.hid}, w.dout8);
   if (int rc = run_wgrad(m, t, a, t->head.w, nullptr, c.hidden, s)) return rc;
   HIPCHK(m, launch_conv(linear_t_args(w.dout8, t->head_t, w.dh, B, 8, c.hidden), s));
   return PNVO_OK;
@@ -996,10 +996,10 @@ static int backward_hidden(pnvo_handle m, TrainState *t, int B, bool stop_after_
   HIPCHK(m, launch_relu_mask(w.dh, w.hid, nullptr, (long)B * c.hidden, w.gh, s));
   HIPCHK(m, launch_colsum(w.gh, B, c.hidden, c.hidden, t->grads + t->fc.b.off, s));
   // with dropout the Linear saw the dropped, already activated feature
-  WgradArgs a = wgrad_request(m, t, m->fc, B, drop ? ConvInput{.x = w.zdrop} : ConvInput{.gn = &w.cs[m->comp]}, w.gh);
+  WgradRequest a = wgrad_request(m, t, m->fc, B, drop ? ConvInput{.x = w.zdrop} : ConvInput{.gn = &w.cs[m->comp]}, w.gh);
   if (c.act_embed) {                // gradient rows are [flat | 32] wide; the embedding columns and rows come from embed_*
     const int flat = m->comp_c * m->fh * m->fw;
-    a.grad_pitch = t->w1_pitch;
+    a.args.grad_pitch = t->w1_pitch;
     HIPCHK(m, launch_embed_backward(w.gh, w.efeat, t->params + t->fc.w.off, t->w1_pitch, flat, B, c.hidden, t->grads + t->fc.w.off, w.dfeat,
                                     s));
     if (drop) HIPCHK(m, launch_dropout(w.dfeat, nullptr, nullptr, B, 1, 32, t->drop_p, t->drop_seed, t->drop_step, 2, w.dfeat, s));
@@ -1020,7 +1020,7 @@ static int backward_compression(pnvo_handle m, TrainState *t, int B, float *dY, 
   const Layer &l = m->convs[li];
   int rc = run_gn_bwd(m, t, li, B, w.dz, 1, w.dz, s);   // in place: dz -> dCompRaw
   if (rc != PNVO_OK) return rc;
-  WgradArgs a = wgrad_request(m, t, l, B, {.x = w.y[m->blocks.size()]}, w.dz);
+  WgradRequest a = wgrad_request(m, t, l, B, {.x = w.y[m->blocks.size()]}, w.dz);
   if ((rc = run_wgrad(m, t, a, t->conv[li].w, nullptr, l.cin, s)) != PNVO_OK) return rc;
   return run_dgrad(m, t, li, B, w.dz, dY, false, s);
 }
@@ -1041,11 +1041,10 @@ static int backward_block(pnvo_handle m, TrainState *t, size_t blk, int B, const
     const Layer &ck = m->convs[ik[k]];
     if ((rc = run_gn_bwd(m, t, ik[k], B, din, k == K - 1 ? 0 : 1, w.dRaw, s)) != PNVO_OK) return rc;
     // conv k > 0 saw relu(GN(raw of the previous conv))
-    WgradArgs a = wgrad_request(m, t, ck, B, k ? ConvInput{.gn = &w.cs[ik[k - 1]]} : ConvInput{.x = xin}, w.dRaw);
-    if (a.lds3 == 6 && m->opt.train_pieces == 2 && t->dmax != nullptr && ck.in_bound < 6.0e4f) {
-      a.np = 2;                     // float16 pieces: X inside float16's range (the forward's bound), dY scaled from its maximum
-      a.dy_absmax = t->dmax + ik[k] * PNVO_ABSMAX_UINTS;
-    }
+    // float16 pieces are permitted with X inside float16's range (the forward's bound) and dY scaled from its recorded maximum
+    const bool f16 = m->opt.train_pieces == 2 && t->dmax != nullptr && ck.in_bound < 6.0e4f;
+    WgradRequest a = wgrad_request(m, t, ck, B, k ? ConvInput{.gn = &w.cs[ik[k - 1]]} : ConvInput{.x = xin}, w.dRaw,
+                                   f16 ? t->dmax + ik[k] * PNVO_ABSMAX_UINTS : nullptr);
     if ((rc = run_wgrad(m, t, a, t->conv[ik[k]].w, nullptr, ck.cin, s)) != PNVO_OK) return rc;
     if ((rc = run_dgrad(m, t, ik[k], B, w.dRaw, k ? w.dA : dX, false, s)) != PNVO_OK) return rc;
     din = w.dA;
@@ -1056,7 +1055,7 @@ static int backward_block(pnvo_handle m, TrainState *t, size_t blk, int B, const
   }
   const Layer &cd = m->convs[b.ds];
   if ((rc = run_gn_bwd(m, t, b.ds, B, w.G, 0, w.dRaw, s)) != PNVO_OK) return rc;
-  WgradArgs a = wgrad_request(m, t, cd, B, {.x = xin}, w.dRaw);
+  WgradRequest a = wgrad_request(m, t, cd, B, {.x = xin}, w.dRaw);
   if ((rc = run_wgrad(m, t, a, t->conv[b.ds].w, nullptr, cd.cin, s)) != PNVO_OK) return rc;
   return run_dgrad(m, t, b.ds, B, w.dRaw, dX, true, s);
 }
@@ -1078,24 +1077,21 @@ static int backward_stem(pnvo_handle m, TrainState *t, int B, const float *dY, h
   }
   // option wgrad_stem=fp32: the float32-MFMA kernel; also once an input outside the exact-operand contract was met
   const bool stem_fp32 = m->opt.wgrad_stem == 1 || m->dense_sticky;
+  // the matrix-core stem kernel, from the pair tensors or the sensor frames: scratch check, timing entry, launch
+  const auto run_mx = [&](const auto &a, auto launch) -> int {
+    if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
+    PnvoTimed tm(m, s, tl.w.t_wgrad, 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
+    HIPCHK(m, launch(a, w.wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, t->grads + tl.w.off, s));
+    return PNVO_OK;
+  };
   if (t->from_frames) {              // the forward read sensor frames: wgrad_stem_mx_kernel<FRAMES> reads them again, nothing else can
     if (!train_frames_direct(m))
       return pnvo_fail(m, PNVO_ERR_STATE, "the last forward came from sensor frames and an option moved the handle off the frame-reading "
                                           "kernels before its backward: run pnvo_train_forward_raw again");
-    const WgradStemMXFrameArgs a = wgrad_stem_mx_frames_request(m, t, B);
-    if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
-    PnvoTimed tm(m, s, tl.w.t_wgrad, 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
-    HIPCHK(m, launch_wgrad_stem_mx_frames(a, w.wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, t->grads + tl.w.off, s));
-    return PNVO_OK;
+    return run_mx(wgrad_stem_mx_frames_request(m, t, B), launch_wgrad_stem_mx_frames);
   }
-  if (m->train_mx && l.coutp == 32 && !stem_fp32) {
-    const WgradStemMXArgs a = wgrad_stem_mx_request(m, t, B);
-    if (wgrad_stem_mx_scratch_floats(a) > w.wg_partial.size()) return pnvo_fail(m, PNVO_ERR_STATE, "wgrad scratch too small");
-    PnvoTimed tm(m, s, tl.w.t_wgrad, 2.0 * (double)B * m->Hs * m->Ws * l.cout * l.cin * 49, 0.0);
-    HIPCHK(m, launch_wgrad_stem_mx(a, w.wg_partial, m->stem_sc, m->stem_sh, t->d_mxmaps, t->d_mxmaps + 32, l.cin, t->grads + tl.w.off, s));
-    return PNVO_OK;
-  }
-  WgradArgs a = wgrad_request(m, t, l, B, {.obs = true}, w.dStem);
+  if (m->train_mx && l.coutp == 32 && !stem_fp32) return run_mx(wgrad_stem_mx_request(m, t, B), launch_wgrad_stem_mx);
+  WgradRequest a = wgrad_request(m, t, l, B, {.obs = true}, w.dStem);
   return run_wgrad(m, t, a, tl.w, t->d_ciperm, l.cin, s);
 }
 

@@ -7,7 +7,6 @@
 // Reductions have one writer per partial and a fixed summation order: gradients are bit-reproducible.
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "pnvo_internal.h"
@@ -636,218 +635,211 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradArgs p, in
   }
 }
 
-template <int TG>
-static hipError_t launch_wgrad_t(const WgradArgs &a, hipStream_t s) {
-  const long nunits = (long)a.chunks * a.pairs * a.groups;
-  dim3 grid((unsigned)((nunits + 3) / 4));
-  if (a.mode == 2)
-    hipLaunchKernelGGL((wgrad_kernel<TG, 2>), grid, dim3(256), 0, s, a);
-  else if (a.mode == 1)
-    hipLaunchKernelGGL((wgrad_kernel<TG, 1>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((wgrad_kernel<TG, 0>), grid, dim3(256), 0, s, a);
+// Every instantiated weight-gradient kernel, one row each: wgrad_plan looks the instance of its plan up here, launch_wgrad launches
+// the row the plan names.  Template arguments (a, b): GENERIC (TG, MODE), LDS9 / MW12 (MODE, STRIDE), X3 (MODE, NP).
+namespace {
+struct WgradInstance {
+  WgradPlan::Family family;
+  int a, b, block;
+  hipError_t (*launch)(const WgradArgs &a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s);
+};
+template <auto KERNEL>
+hipError_t wg_launch(const WgradArgs &a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, s, a);
   return hipGetLastError();
+}
+#define WG_GENERIC(TG) \
+  {WgradPlan::GENERIC, TG, 0, 256, wg_launch<wgrad_kernel<TG, 0>>}, {WgradPlan::GENERIC, TG, 1, 256, wg_launch<wgrad_kernel<TG, 1>>}, \
+  {WgradPlan::GENERIC, TG, 2, 256, wg_launch<wgrad_kernel<TG, 2>>},
+#define WG_MS(FAMILY, KERNEL, BLOCK) /* (mode, stride) of the two 3x3 LDS kernels */ \
+  {FAMILY, 0, 1, BLOCK, wg_launch<KERNEL<0, 1>>}, {FAMILY, 1, 1, BLOCK, wg_launch<KERNEL<1, 1>>}, \
+  {FAMILY, 0, 2, BLOCK, wg_launch<KERNEL<0, 2>>}, {FAMILY, 1, 2, BLOCK, wg_launch<KERNEL<1, 2>>},
+const WgradInstance wgrad_table[] = {
+  WG_GENERIC(9) WG_GENERIC(7) WG_GENERIC(6) WG_GENERIC(3) WG_GENERIC(1)
+  WG_MS(WgradPlan::LDS9, wgrad3_lds_kernel, 576) WG_MS(WgradPlan::MW12, wgrad3_mw_kernel, 768)
+  {WgradPlan::STEM_LDS, 0, 0, 448, wg_launch<wgrad_stem_lds_kernel>},
+  {WgradPlan::X3, 0, 2, 256, wgrad_x3_launch<0, 2>}, {WgradPlan::X3, 1, 2, 256, wgrad_x3_launch<1, 2>},
+  {WgradPlan::X3, 0, 3, 256, wgrad_x3_launch<0, 3>}, {WgradPlan::X3, 1, 3, 256, wgrad_x3_launch<1, 3>},
+};
+#undef WG_MS
+#undef WG_GENERIC
+constexpr int wgrad_table_rows = (int)(sizeof(wgrad_table) / sizeof(wgrad_table[0]));
+int wgrad_find(WgradPlan::Family f, int a, int b) {
+  for (int i = 0; i < wgrad_table_rows; ++i)
+    if (wgrad_table[i].family == f && wgrad_table[i].a == a && wgrad_table[i].b == b) return i;
+  return -1;
+}
+
+// B x tiles_x x tiles_y tiles over at most `want` chunks of whole tiles: tiles per chunk, then the chunks that leaves
+void tiles_to_chunks(const WgradProblem &q, WgradPlan &p, long want) {
+  const long ntiles = (long)q.B * p.tiles_x * p.tiles_y;
+  if (want < 1) want = 1;
+  if (want > ntiles) want = ntiles;
+  p.tiles_per_chunk = (int)((ntiles + want - 1) / want);
+  p.chunks = (int)((ntiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk);
+}
+
+// tiles of at most th_max x tw_max outputs, even in width, as equal as the map allows
+void even_tiles(const WgradProblem &q, WgradPlan &p, int th_max, int tw_max) {
+  p.tiles_x = (q.Wo + tw_max - 1) / tw_max;
+  p.TW = ((q.Wo + p.tiles_x - 1) / p.tiles_x + 1) / 2 * 2;
+  p.tiles_y = (q.Ho + th_max - 1) / th_max;
+  p.TH = (q.Ho + p.tiles_y - 1) / p.tiles_y;
+}
+
+// floats of one staged (patch, dY slab) set of the two 3x3 LDS kernels: 36-float pixel rows
+size_t patch_bytes(const WgradPlan &p, int S, int cs, int os) {
+  return (size_t)(cs * ((p.TH - 1) * S + 3) * ((p.TW - 1) * S + 3) + os * p.TH * p.TW) * 36 * 4;
 }
 
 // tile + unit plan of wgrad3_mw_kernel; false: shape outside it (the nine-wave kernel or the generic one takes over)
-static bool wgrad_plan_mw(WgradArgs &a) {
-  const int S = a.stride;
-  const int cit = a.CIN / 32, cot = (a.COUT + 31) / 32;    // (a padded last co-tile reads dY's zero pad channels)
+bool wgrad_plan_mw(const WgradProblem &q, WgradPlan &p) {
+  const int S = q.stride;
+  const int cit = q.CIN / 32, cot = (q.COUT + 31) / 32;    // (a padded last co-tile reads dY's zero pad channels)
   if (cit % 2 == 0 && cot % 2 == 0) {
-    a.cs = 2; a.os = 2; a.rs = 1;
+    p.cs = 2; p.os = 2; p.rs = 1;
   } else if (cit == 1 && cot % 2 == 0) {
-    a.cs = 1; a.os = 2; a.rs = 2;
+    p.cs = 1; p.os = 2; p.rs = 2;
   } else if (cit % 2 == 0 && cot == 1) {
-    a.cs = 2; a.os = 1; a.rs = 2;
+    p.cs = 2; p.os = 1; p.rs = 2;
   } else if (cit == 1 && cot == 1) {
-    a.cs = 1; a.os = 1; a.rs = 4;
+    p.cs = 1; p.os = 1; p.rs = 4;
   } else {
     return false;
   }
-  const int tw_max = S == 1 ? 24 : 12;
-  a.tiles_x = (a.Wo + tw_max - 1) / tw_max;
-  a.TW = ((a.Wo + a.tiles_x - 1) / a.tiles_x + 1) / 2 * 2;
   const size_t lds_max = 160 * 1024;
-  auto bytes = [&](int th) {
-    return (size_t)(a.cs * ((th - 1) * S + 3) * ((a.TW - 1) * S + 3) + a.os * th * a.TW) * 36 * 4;
+  auto fits = [&](int th, int nbuf) {                      // staging items per thread within the kernel's NX / ND, LDS within the CU's
+    even_tiles(q, p, th, S == 1 ? 24 : 12);
+    p.TH = th;
+    return (long)p.cs * ((th - 1) * S + 3) * ((p.TW - 1) * S + 3) * 8 <= 5 * 768 && (long)p.os * th * p.TW * 8 <= 2 * 768 &&
+           nbuf * patch_bytes(p, S, p.cs, p.os) <= lds_max;
   };
-  auto items_ok = [&](int th) {
-    return (long)a.cs * ((th - 1) * S + 3) * ((a.TW - 1) * S + 3) * 8 <= 5 * 768 && (long)a.os * th * a.TW * 8 <= 2 * 768;
-  };
-  int th = a.Ho < 8 ? a.Ho : 8;
-  while (th > 1 && (!items_ok(th) || 2 * bytes(th) > lds_max)) --th;
-  if (!items_ok(th) || bytes(th) > lds_max) return false;
-  a.tiles_y = (a.Ho + th - 1) / th;
-  a.TH = (a.Ho + a.tiles_y - 1) / a.tiles_y;
-  a.nbuf = 2 * bytes(a.TH) <= lds_max ? 2 : 1;
-  a.TG = 9;
-  a.groups = 1;
-  a.ci_tiles = cit;
-  a.pairs = cit * cot;
-  const int pgs = (cit / a.cs) * (cot / a.os);
-  const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-  long chunks = 256 / pgs;                              // one 12-wave workgroup per CU
-  if (chunks < 1) chunks = 1;
-  if (chunks > ntiles) chunks = ntiles;
-  a.tiles_per_chunk = (int)((ntiles + chunks - 1) / chunks);
-  a.wg_chunks = (int)((ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk);
-  a.chunks = a.wg_chunks;                               // row groups are summed inside the workgroup
-  a.pix_per_chunk = 0;
-  a.lds3 = S == 1 ? 4 : 5;
+  int th = q.Ho < 8 ? q.Ho : 8;
+  while (th > 1 && !fits(th, 2)) --th;
+  if (!fits(th, 1)) return false;
+  even_tiles(q, p, th, S == 1 ? 24 : 12);
+  p.nbuf = 2 * patch_bytes(p, S, p.cs, p.os) <= lds_max ? 2 : 1;
+  p.TG = 9;
+  p.groups = 1;
+  p.ci_tiles = cit;
+  p.pairs = cit * cot;
+  const int pgs = (cit / p.cs) * (cot / p.os);
+  tiles_to_chunks(q, p, 256 / pgs);                        // one 12-wave workgroup per CU
+  p.wg_chunks = p.chunks;                                  // row groups are summed inside the workgroup
+  p.lds_bytes = patch_bytes(p, S, p.cs, p.os) * p.nbuf;
+  if (p.rs > 1 && p.lds_bytes < 12 * 16 * 64 * 4) p.lds_bytes = 12 * 16 * 64 * 4;      // the row-group sum at the end goes through LDS
+  p.grid = (unsigned)(pgs * p.wg_chunks);
   return true;
 }
+}  // namespace
 
-void wgrad_plan(WgradArgs &a) {
-  a.lds3 = 0;
-  if (a.use_x3 && wgrad_x3_plan(a)) return;              // 3x3 stride-1 convs: three-piece operands on the bf16 matrix cores
-  static const bool no_lds = std::getenv("PNVO_WGRAD") && std::strcmp(std::getenv("PNVO_WGRAD"), "generic") == 0;
-  static const bool nine = std::getenv("PNVO_WGRAD") && std::strcmp(std::getenv("PNVO_WGRAD"), "lds9") == 0;
-  if (!no_lds && !nine && a.mode != 2 && a.KH == 3 && a.KW == 3 && a.pad == 1 && a.CIN % 32 == 0 && a.DYC >= (a.COUT + 31) / 32 * 32 &&
-      a.DYC % 4 == 0 && ((a.stride == 1 && a.H == a.Ho && a.W == a.Wo) || a.stride == 2) && wgrad_plan_mw(a))
-    return;
-  if (!no_lds && a.mode != 2 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.CIN % 32 == 0 &&
-      a.COUT % 32 == 0 && a.DYC % 4 == 0 && a.H == a.Ho && a.W == a.Wo) {
-    a.lds3 = 1;
-    a.TG = 9;
-    a.groups = 1;
-    a.ci_tiles = a.CIN / 32;
-    a.pairs = a.ci_tiles * (a.COUT / 32);
-    a.tiles_x = (a.W + 23) / 24;
-    a.TW = ((a.W + a.tiles_x - 1) / a.tiles_x + 1) / 2 * 2;
-    a.tiles_y = (a.H + 7) / 8;                        // rows of at most 8
-    a.TH = (a.H + a.tiles_y - 1) / a.tiles_y;
-    const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-    long chunks = 256L * 2 / a.pairs;                 // two persistent workgroups per CU
+WgradPlan wgrad_plan(const WgradProblem &q) {
+  WgradPlan p;
+  const bool lds_ok = q.wgrad != 2, conv3 = q.mode != 2 && q.KH == 3 && q.KW == 3 && q.pad == 1 && q.CIN % 32 == 0 && q.DYC % 4 == 0;
+  const bool same = q.stride == 1 && q.H == q.Ho && q.W == q.Wo;
+  if (q.wgrad3 && wgrad_x3_plan(q, p)) {                   // 3x3 stride-1 convs: three- or two-piece operands on the matrix cores
+    p.family = WgradPlan::X3;
+    p.np = q.np == 2 ? 2 : 3;
+    p.inst = wgrad_find(p.family, q.mode, p.np);
+  } else if (lds_ok && q.wgrad != 1 && conv3 && q.DYC >= (q.COUT + 31) / 32 * 32 && (same || q.stride == 2) && wgrad_plan_mw(q, p)) {
+    p.family = WgradPlan::MW12;
+    p.inst = wgrad_find(p.family, q.mode, q.stride);
+  } else if (lds_ok && conv3 && q.COUT % 32 == 0 && (same || q.stride == 2)) {
+    // tiles of <= 8 x 24 outputs; strided: <= 4 x 12, which keeps the (2T+1)-pixel patch at 9 x 25 (<= 4 sixteen-byte staging items per thread)
+    p = WgradPlan{};
+    p.family = WgradPlan::LDS9;
+    p.TG = 9;
+    p.groups = 1;
+    p.ci_tiles = q.CIN / 32;
+    p.pairs = p.ci_tiles * (q.COUT / 32);
+    even_tiles(q, p, q.stride == 1 ? 8 : 4, q.stride == 1 ? 24 : 12);
+    tiles_to_chunks(q, p, 256L * 2 / p.pairs);             // two persistent workgroups per CU
+    p.lds_bytes = patch_bytes(p, q.stride, 1, 1);
+    p.grid = (unsigned)(p.pairs * p.chunks);
+    p.inst = wgrad_find(p.family, q.mode, q.stride);
+  } else if (lds_ok && q.mode == 2 && q.KH == 7 && q.KW == 7 && q.stride == 2 && q.pad == 3 && q.CIN <= 32 && q.COUT == 32 && q.DYC % 4 == 0) {
+    p = WgradPlan{};
+    p.family = WgradPlan::STEM_LDS;                        // the stem: one workgroup per CU
+    p.TG = 7;
+    p.groups = 7;
+    p.ci_tiles = p.pairs = 1;
+    p.TH = 4;
+    p.TW = 16;
+    p.tiles_x = (q.Wo + 15) / 16;
+    p.tiles_y = (q.Ho + 3) / 4;
+    tiles_to_chunks(q, p, 256);
+    p.lds_bytes = (size_t)(13 * 37 + 64) * 36 * 4;
+    p.grid = (unsigned)p.chunks;
+    p.inst = wgrad_find(p.family, 0, 0);
+  } else {
+    p = WgradPlan{};
+    const int T = q.KH * q.KW;
+    p.TG = T == 1 ? 1 : T >= 9 ? (T % 9 == 0 ? 9 : (T % 7 == 0 ? 7 : (T % 6 == 0 ? 6 : 9))) : (T >= 3 ? 3 : 1);
+    p.groups = (T + p.TG - 1) / p.TG;
+    p.ci_tiles = (q.CIN + 31) / 32;
+    p.pairs = p.ci_tiles * ((q.COUT + 31) / 32);
+    const long M = (long)q.B * q.Ho * q.Wo;
+    long chunks = 2048 / ((long)p.pairs * p.groups);
     if (chunks < 1) chunks = 1;
-    if (chunks > ntiles) chunks = ntiles;
-    a.tiles_per_chunk = (int)((ntiles + chunks - 1) / chunks);
-    a.chunks = (int)((ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk);
-    a.pix_per_chunk = 0;
-    return;
+    long ppc = (M + chunks - 1) / chunks;
+    if (ppc < 64) ppc = 64;
+    p.pix_per_chunk = (ppc + 1) / 2 * 2;
+    p.chunks = (int)((M + p.pix_per_chunk - 1) / p.pix_per_chunk);
+    p.grid = (unsigned)(((long)p.chunks * p.pairs * p.groups + 3) / 4);   // four units per workgroup
+    p.inst = wgrad_find(p.family, p.TG, q.mode == 2 ? 2 : q.mode == 1 ? 1 : 0);
   }
-  if (!no_lds && a.mode != 2 && a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.CIN % 32 == 0 &&
-      a.COUT % 32 == 0 && a.DYC % 4 == 0) {
-    // strided 3x3: same kernel with a (2T+1)-pixel patch per axis; tiles of <= 4 x 12 outputs keep the patch at 9 x 25
-    // pixels (<= 4 sixteen-byte staging items per thread)
-    a.lds3 = 3;
-    a.TG = 9;
-    a.groups = 1;
-    a.ci_tiles = a.CIN / 32;
-    a.pairs = a.ci_tiles * (a.COUT / 32);
-    a.tiles_x = (a.Wo + 11) / 12;
-    a.TW = ((a.Wo + a.tiles_x - 1) / a.tiles_x + 1) / 2 * 2;
-    a.tiles_y = (a.Ho + 3) / 4;
-    a.TH = (a.Ho + a.tiles_y - 1) / a.tiles_y;
-    const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-    long chunks = 256L * 2 / a.pairs;
-    if (chunks < 1) chunks = 1;
-    if (chunks > ntiles) chunks = ntiles;
-    a.tiles_per_chunk = (int)((ntiles + chunks - 1) / chunks);
-    a.chunks = (int)((ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk);
-    a.pix_per_chunk = 0;
-    return;
-  }
-  if (!no_lds && a.mode == 2 && a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad == 3 && a.CIN <= 32 && a.COUT == 32 &&
-      a.DYC % 4 == 0) {                                  // the stem: wgrad_stem_lds_kernel, one workgroup per CU
-    a.lds3 = 2;
-    a.TG = 7;
-    a.groups = 7;
-    a.ci_tiles = 1;
-    a.pairs = 1;
-    a.TH = 4;
-    a.TW = 16;
-    a.tiles_x = (a.Wo + 15) / 16;
-    a.tiles_y = (a.Ho + 3) / 4;
-    const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-    long chunks = ntiles < 256 ? ntiles : 256;
-    a.tiles_per_chunk = (int)((ntiles + chunks - 1) / chunks);
-    a.chunks = (int)((ntiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk);
-    a.pix_per_chunk = 0;
-    return;
-  }
-  const int T = a.KH * a.KW;
-  a.TG = T >= 9 ? (T % 9 == 0 ? 9 : (T % 7 == 0 ? 7 : (T % 6 == 0 ? 6 : 9))) : (T >= 3 ? 3 : 1);
-  if (T == 1) a.TG = 1;
-  a.groups = (T + a.TG - 1) / a.TG;
-  a.ci_tiles = (a.CIN + 31) / 32;
-  a.pairs = a.ci_tiles * ((a.COUT + 31) / 32);
-  const long M = (long)a.B * a.Ho * a.Wo;
-  long chunks = 2048 / ((long)a.pairs * a.groups);
-  if (chunks < 1) chunks = 1;
-  long ppc = (M + chunks - 1) / chunks;
-  if (ppc < 64) ppc = 64;
-  ppc = (ppc + 1) / 2 * 2;
-  a.pix_per_chunk = ppc;
-  a.chunks = (int)((M + ppc - 1) / ppc);
+  p.block = p.inst >= 0 ? wgrad_table[p.inst].block : 0;
+  p.partial_floats = (size_t)p.chunks * p.pairs * p.groups * p.TG * 1024;
+  p.reduce_grid = (unsigned)(p.pairs * q.KH * q.KW * 32);   // one block per (pair, tap, ci row)
+  return p;
 }
 
-size_t wgrad_partial_floats(const WgradArgs &a) { return (size_t)a.chunks * a.pairs * a.groups * a.TG * 1024; }
+WgradArgs wgrad_args(const WgradProblem &q, const WgradPlan &p) {
+  WgradArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.B = q.B; a.H = q.H; a.W = q.W; a.CIN = q.CIN; a.Ho = q.Ho; a.Wo = q.Wo; a.COUT = q.COUT; a.DYC = q.DYC; a.KH = q.KH; a.KW = q.KW;
+  a.stride = q.stride; a.pad = q.pad; a.mode = q.mode;
+  a.TG = p.TG; a.groups = p.groups; a.ci_tiles = p.ci_tiles; a.pairs = p.pairs; a.chunks = p.chunks; a.pix_per_chunk = p.pix_per_chunk;
+  a.TH = p.TH; a.TW = p.TW; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.tiles_per_chunk = p.tiles_per_chunk;
+  a.cs = p.cs; a.os = p.os; a.rs = p.rs; a.wg_chunks = p.wg_chunks; a.nbuf = p.nbuf; a.xr_rsegs = p.xr_rsegs;
+  return a;
+}
 
-hipError_t launch_wgrad(const WgradArgs &a, float *grad, const int *ci_perm, int cin_out, hipStream_t s) {
-  hipError_t e;
-  if (a.lds3 == 6) {
-    e = launch_wgrad_x3(a, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(a.pairs * 9 * 32)), dim3(256), 0, s, a, a.TG, grad, ci_perm, cin_out);
-    return hipGetLastError();
-  }
-  if (a.lds3 == 2) {
-    const size_t lds = (size_t)(13 * 37 + 64) * 36 * 4;
-    hipLaunchKernelGGL(wgrad_stem_lds_kernel, dim3((unsigned)a.chunks), dim3(448), lds, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(49 * 32)), dim3(256), 0, s, a, a.TG, grad, ci_perm, cin_out);
-    return hipGetLastError();
-  }
-  if (a.lds3 == 4 || a.lds3 == 5) {
-    const int S = a.lds3 == 5 ? 2 : 1;
-    size_t lds = (size_t)(a.cs * ((a.TH - 1) * S + 3) * ((a.TW - 1) * S + 3) + a.os * a.TH * a.TW) * 36 * 4 * a.nbuf;
-    if (a.rs > 1 && lds < 12 * 16 * 64 * 4) lds = 12 * 16 * 64 * 4;      // the row-group sum at the end goes through LDS
-    dim3 grid((unsigned)((a.ci_tiles / a.cs) * ((a.COUT + 31) / 32 / a.os) * a.wg_chunks));
-    if (S == 2 && a.mode == 1)
-      hipLaunchKernelGGL((wgrad3_mw_kernel<1, 2>), grid, dim3(768), lds, s, a);
-    else if (S == 2)
-      hipLaunchKernelGGL((wgrad3_mw_kernel<0, 2>), grid, dim3(768), lds, s, a);
-    else if (a.mode == 1)
-      hipLaunchKernelGGL((wgrad3_mw_kernel<1, 1>), grid, dim3(768), lds, s, a);
-    else
-      hipLaunchKernelGGL((wgrad3_mw_kernel<0, 1>), grid, dim3(768), lds, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(a.pairs * 9 * 32)), dim3(256), 0, s, a, a.TG, grad, ci_perm,
-                       cin_out);
-    return hipGetLastError();
-  }
-  if (a.lds3) {
-    const int S = a.lds3 == 3 ? 2 : 1;
-    const size_t lds = (size_t)(((a.TH - 1) * S + 3) * ((a.TW - 1) * S + 3) + a.TH * a.TW) * 36 * 4;
-    dim3 grid((unsigned)(a.pairs * a.chunks));
-    if (S == 2 && a.mode == 1)
-      hipLaunchKernelGGL((wgrad3_lds_kernel<1, 2>), grid, dim3(576), lds, s, a);
-    else if (S == 2)
-      hipLaunchKernelGGL((wgrad3_lds_kernel<0, 2>), grid, dim3(576), lds, s, a);
-    else if (a.mode == 1)
-      hipLaunchKernelGGL((wgrad3_lds_kernel<1, 1>), grid, dim3(576), lds, s, a);
-    else
-      hipLaunchKernelGGL((wgrad3_lds_kernel<0, 1>), grid, dim3(576), lds, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(a.pairs * 9 * 32)), dim3(256), 0, s, a, a.TG, grad, ci_perm,
-                       cin_out);
-    return hipGetLastError();
-  }
-  switch (a.TG) {
-    case 9: e = launch_wgrad_t<9>(a, s); break;
-    case 7: e = launch_wgrad_t<7>(a, s); break;
-    case 6: e = launch_wgrad_t<6>(a, s); break;
-    case 3: e = launch_wgrad_t<3>(a, s); break;
-    case 1: e = launch_wgrad_t<1>(a, s); break;
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_wgrad(const WgradArgs &a, const WgradPlan &p, float *grad, const int *ci_perm, int cin_out, hipStream_t s) {
+  if (p.inst < 0 || p.inst >= wgrad_table_rows) return hipErrorInvalidValue;
+  const hipError_t e = wgrad_table[p.inst].launch(a, dim3(p.grid), dim3((unsigned)p.block), p.lds_bytes, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(a.pairs * a.KH * a.KW * 32)), dim3(256), 0, s, a, a.TG, grad,
-                     ci_perm, cin_out);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, s, a, p.TG, grad, ci_perm, cin_out);
   return hipGetLastError();
+}
+
+// "<family> <instance> | grid, block, LDS bytes, scratch floats, reduce grid | geometry" of q's plan; q == nullptr: the instance name of
+// table row `row`.  Touches no HIP runtime call.
+int wgrad_describe(const WgradProblem *q, int row, char *buf, size_t cap) {
+  const auto name = [&](const WgradInstance &r) {
+    switch (r.family) {
+      case WgradPlan::GENERIC: return std::snprintf(buf, cap, "generic tg%d mode%d", r.a, r.b);
+      case WgradPlan::LDS9: return std::snprintf(buf, cap, "lds9 mode%d s%d", r.a, r.b);
+      case WgradPlan::MW12: return std::snprintf(buf, cap, "mw12 mode%d s%d", r.a, r.b);
+      case WgradPlan::STEM_LDS: return std::snprintf(buf, cap, "stem_lds");
+      default: return std::snprintf(buf, cap, "x3 mode%d np%d", r.a, r.b);
+    }
+  };
+  if (q == nullptr) {
+    if (row < 0 || row >= wgrad_table_rows) return -1;
+    name(wgrad_table[row]);
+    return 0;
+  }
+  const WgradPlan p = wgrad_plan(*q);
+  if (p.inst < 0) return -1;
+  const int at = name(wgrad_table[p.inst]);
+  if (at > 0 && (size_t)at < cap)
+    std::snprintf(buf + at, cap - at,
+                  " | grid %u block %d lds %zu partial %zu reduce %u | TG %d groups %d ci_tiles %d pairs %d chunks %d ppc %ld TH %d TW %d tiles %dx%d "
+                  "tpc %d cs %d os %d rs %d wgc %d nbuf %d rsegs %d np %d",
+                  p.grid, p.block, p.lds_bytes, p.partial_floats, p.reduce_grid, p.TG, p.groups, p.ci_tiles, p.pairs, p.chunks, p.pix_per_chunk, p.TH,
+                  p.TW, p.tiles_x, p.tiles_y, p.tiles_per_chunk, p.cs, p.os, p.rs, p.wg_chunks, p.nbuf, p.xr_rsegs, p.np);
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -301,48 +301,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-// plan: false = shape outside this kernel
-bool wgrad_x3_plan(WgradArgs &a) {
-  if (a.mode == 2 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.H != a.Ho || a.W != a.Wo) return false;
-  if (a.CIN % 32 || a.COUT % 32 || a.DYC < a.COUT) return false;
-  if ((long)a.B * a.H * a.W * (long)(a.CIN > a.DYC ? a.CIN : a.DYC) * 4 >= 0x7FFFF000L) return false;   // 32-bit buffer offsets
-  a.TG = 9;
-  a.groups = 1;
-  a.ci_tiles = a.CIN / 32;
-  a.pairs = a.ci_tiles * (a.COUT / 32);
+// the X3 branch of wgrad_plan: geometry only; false = shape outside this kernel
+bool wgrad_x3_plan(const WgradProblem &q, WgradPlan &p) {
+  if (q.mode == 2 || q.KH != 3 || q.KW != 3 || q.stride != 1 || q.pad != 1 || q.H != q.Ho || q.W != q.Wo) return false;
+  if (q.CIN % 32 || q.COUT % 32 || q.DYC < q.COUT) return false;
+  if ((long)q.B * q.H * q.W * (long)(q.CIN > q.DYC ? q.CIN : q.DYC) * 4 >= 0x7FFFF000L) return false;   // 32-bit buffer offsets
+  p.TG = 9;
+  p.groups = 1;
+  p.ci_tiles = q.CIN / 32;
+  p.pairs = p.ci_tiles * (q.COUT / 32);
   // one wave per SIMD: ~1024 waves per launch, four per workgroup
-  int wgs = 256 / a.pairs;
+  int wgs = 256 / p.pairs;
   if (wgs < 1) wgs = 1;
-  a.chunks = wgs;
-  const int strips = (a.W + 15) / 16;
+  p.chunks = wgs;
+  const int strips = (q.W + 15) / 16;
   // units per wave >= ~4 keeps the split even; a unit's prologue costs two extra row loads, so row segments stay >= 4 rows
   long want = 4L * wgs * 4;
-  int rsegs = (int)((want + (long)a.B * strips - 1) / ((long)a.B * strips));
-  const int max_rsegs = (a.H + 3) / 4;
+  int rsegs = (int)((want + (long)q.B * strips - 1) / ((long)q.B * strips));
+  const int max_rsegs = (q.H + 3) / 4;
   if (rsegs > max_rsegs) rsegs = max_rsegs;
   if (rsegs < 1) rsegs = 1;
-  while (rsegs > 1 && ((a.H + rsegs - 1) / rsegs) % 3 != 0) --rsegs;     // whole groups of three rows per segment where the map allows
-  a.xr_rsegs = rsegs;
-  if ((long)a.B * strips * rsegs < (long)wgs * 4) {        // fewer units than waves (tiny batches): fewer workgroups
-    a.chunks = (int)(((long)a.B * strips * rsegs + 3) / 4);
-    if (a.chunks < 1) a.chunks = 1;
+  while (rsegs > 1 && ((q.H + rsegs - 1) / rsegs) % 3 != 0) --rsegs;     // whole groups of three rows per segment where the map allows
+  p.xr_rsegs = rsegs;
+  if ((long)q.B * strips * rsegs < (long)wgs * 4) {        // fewer units than waves (tiny batches): fewer workgroups
+    p.chunks = (int)(((long)q.B * strips * rsegs + 3) / 4);
+    if (p.chunks < 1) p.chunks = 1;
   }
-  a.pix_per_chunk = 0;
-  a.lds3 = 6;
+  p.grid = (unsigned)(p.pairs * p.chunks);
   return true;
 }
 
-hipError_t launch_wgrad_x3(const WgradArgs &a, hipStream_t s) {
-  dim3 grid((unsigned)(a.pairs * a.chunks));
-  if (a.np == 2 && a.mode == 1)
-    hipLaunchKernelGGL((wgrad3_x3_kernel<1, 2>), grid, dim3(256), 0, s, a);
-  else if (a.np == 2)
-    hipLaunchKernelGGL((wgrad3_x3_kernel<0, 2>), grid, dim3(256), 0, s, a);
-  else if (a.mode == 1)
-    hipLaunchKernelGGL((wgrad3_x3_kernel<1, 3>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((wgrad3_x3_kernel<0, 3>), grid, dim3(256), 0, s, a);
+template <int MODE, int NP>
+hipError_t wgrad_x3_launch(const WgradArgs &a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s) {
+  hipLaunchKernelGGL((wgrad3_x3_kernel<MODE, NP>), grid, block, lds_bytes, s, a);
   return hipGetLastError();
 }
+template hipError_t wgrad_x3_launch<0, 2>(const WgradArgs &, dim3, dim3, size_t, hipStream_t);
+template hipError_t wgrad_x3_launch<1, 2>(const WgradArgs &, dim3, dim3, size_t, hipStream_t);
+template hipError_t wgrad_x3_launch<0, 3>(const WgradArgs &, dim3, dim3, size_t, hipStream_t);
+template hipError_t wgrad_x3_launch<1, 3>(const WgradArgs &, dim3, dim3, size_t, hipStream_t);
 
 }  // namespace pnvo

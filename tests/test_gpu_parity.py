@@ -4,6 +4,7 @@
   (3) size-independent properties at BASELINE sizes (batch-composition invariance, determinism).
 Tolerance for the network outputs (fp32): per-pair ||out-ref||_2 / max(||ref||_2, 1e-2) < 1e-4 vs the fp64 reference
 (BASELINE.md §5).  Pre-processing (integer/bin work): bit-exact."""
+import os
 import ctypes as C
 
 import numpy as np
@@ -225,6 +226,9 @@ def test_unknown_option_is_refused():
         model.set_option("no_such_knob", "1")
     with pytest.raises(_lib.PnvoError, match="mx"):
         model.set_option("stem", "sparse")
+    assert model.get_option("wgrad") == os.environ.get("PNVO_WGRAD", "auto")     # a table option: the environment gives the default ...
+    model.set_option("wgrad", "generic")
+    assert model.get_option("wgrad") == "generic"                                # ... and the handle keeps what it is told
 
 
 def test_soft_depth_codes_on_the_dense_stem():
