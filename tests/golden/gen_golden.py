@@ -498,7 +498,12 @@ def main():
         train_fixture(registry, "train_act_embed_64x48_b5_f64.npz", "vo_cnn_act_embed", ["rgb", "depth"], (64, 48), 5, 0, 33,
                       torch.float64, actions=[1, 3, 2, 3, 1])
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "joint":         # regenerate just the joint-training fixtures
+    if len(sys.argv) > 1 and sys.argv[1] == "trainmodels":   # regenerate just the 64-base-plane and the rgb + one-hot + top-down fixtures
+        train_fixture(registry, "train_wider_45x37_b3_f64.npz", "vo_cnn_wider", ["rgb", "depth"], (45, 37), 3, 0, 51, torch.float64)
+        train_fixture(registry, "train_rgb_dd_tdv_45x37_b3_f64.npz", "vo_cnn_rgb_dd_top_down",
+                      ["rgb", "discretized_depth", "top_down_view"], (45, 37), 3, 10, 51, torch.float64)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "joint":        # regenerate just the joint-training fixtures
         joint_train_fixture(registry, "train_joint_64x48_p4.npz", (64, 48), 4, 41, True)
         joint_train_fixture(registry, "train_joint_45x37_p3_w.npz", (45, 37), 3, 42, False)
         return
@@ -525,6 +530,9 @@ def main():
                   torch.float64, actions=[1, 3, 2, 3, 1])
     train_fixture(registry, "train_deeper_64x48_b2_f64.npz", "vo_cnn_deeper", ["rgb", "depth"], (64, 48), 2, 0, 34,
                   torch.float64, extra={"backbone": "resnet101"})
+    train_fixture(registry, "train_wider_45x37_b3_f64.npz", "vo_cnn_wider", ["rgb", "depth"], (45, 37), 3, 0, 51, torch.float64)
+    train_fixture(registry, "train_rgb_dd_tdv_45x37_b3_f64.npz", "vo_cnn_rgb_dd_top_down",
+                  ["rgb", "discretized_depth", "top_down_view"], (45, 37), 3, 10, 51, torch.float64)
     geo_loss_fixture()
     joint_train_fixture(registry, "train_joint_64x48_p4.npz", (64, 48), 4, 41, True)
     joint_train_fixture(registry, "train_joint_45x37_p3_w.npz", (45, 37), 3, 42, False)

@@ -30,7 +30,8 @@ conv is its first and reads a plain tensor).  Tap groups of 7 come from the hidd
 itself reaches the generic kernel only with wgrad_stem=fp32 and wgrad=generic together, which no case sets.  The twelve-wave kernel runs
 double-buffered (nbuf 2) in every case: no problem of tests/test_wgrad_plan.py's whole grid plans a single buffer.  The float16 form counts as permitted for the
 second conv of a block when train_pieces is 2: the third condition, the forward's bound on the conv's input below 6.0e4, holds for these
-seeded models by orders of magnitude and is not visible from here.  The stem's request is described only where it runs (wgrad_stem=fp32).
+seeded models by orders of magnitude and is not visible from here.  The stem's request is described only where it runs (wgrad_stem=fp32;
+a 64-output stem, which no case here has: stem_is_a_request, used by tests/test_gpu_train_models.py, which runs `generic tg7 mode2`).
 """
 import ctypes as C
 import os
@@ -61,6 +62,20 @@ def case_name(kind, opts):
     return kind + "".join(f":{k}={v}" for k, v in opts.items())
 
 
+def stem_is_a_request(cfg, opts):
+    """Does the stem's weight gradient go through the planner?  Not where the matrix-core stem kernel serves it: 32 stem outputs
+    (backward_stem's l.coutp == 32; every modality layout of the registered models fits that kernel) and no wgrad_stem=fp32."""
+    return opts.get("wgrad_stem", "mx") == "fp32" or cfg.baseplanes != 32
+
+
+def request_names(cfg, opts):
+    """The parameter each row of requests() is the weight gradient of, in the same order."""
+    from pointnav_vo_amd import model_spec as ms
+
+    names = [cd.name + ".weight" for k, cd in enumerate(ms.conv_plan(cfg)) if k or stem_is_a_request(cfg, opts)]
+    return names + [("hidden_generator.1" if cfg.act_embed else "visual_fc.2") + ".weight", "output_head.1.weight"]
+
+
 def requests(cfg, B, opts, dropout):
     """The problems of one backward's weight-gradient requests, as FIELDS rows (csrc/pnvo_train_api.hip: wgrad_request and its callers)."""
     from pointnav_vo_amd import model_spec as ms
@@ -70,7 +85,7 @@ def requests(cfg, B, opts, dropout):
     f16 = opts.get("train_pieces", "2") == "2"
     rows = []
     for k, cd in enumerate(ms.conv_plan(cfg)):
-        if k == 0 and opts.get("wgrad_stem", "mx") != "fp32":
+        if k == 0 and not stem_is_a_request(cfg, opts):
             continue                                       # the matrix-core stem kernel is not a request of this planner
         block_conv = ".convs." in cd.name
         mode = 2 if k == 0 else 1 if block_conv and not cd.name.endswith(".convs.0") else 0

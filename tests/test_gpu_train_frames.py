@@ -157,9 +157,14 @@ def test_train_forward_raw_on_three_bf16_pieces():
 
 
 @pytest.mark.parametrize("name,space,bins", [("vo_cnn", ["rgb", "depth"], 0),
-                                             ("vo_cnn_d_dd_top_down", ["depth", "discretized_depth", "top_down_view"], 10)])
+                                             ("vo_cnn_d_dd_top_down", ["depth", "discretized_depth", "top_down_view"], 10),
+                                             ("vo_cnn_rgb_d_dd", ["rgb", "depth", "discretized_depth"], 10),
+                                             ("vo_cnn_rgb_d_top_down", ["rgb", "depth", "top_down_view"], 0),
+                                             ("vo_cnn_rgb_dd_top_down", ["rgb", "discretized_depth", "top_down_view"], 10)])
 def test_train_forward_raw_on_models_with_fewer_modalities(name, space, bins):
-    """No one-hot and no top-down view; no rgb frames."""
+    """No one-hot and no top-down view; no rgb frames; no top-down view; no one-hot; the one-hot without the depth tensor (the depth
+    frames are still what it is derived from).  The pair path compared against is held to fp64 on each of these layouts by
+    tests/test_gpu_train_models.py."""
     H, W, B = 66, 98, 3
     model = build_model(name, space, W, H, seed=6, bins=bins)
     rgb, dep = frames(B, H, W, seed=13)
