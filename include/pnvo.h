@@ -872,6 +872,18 @@ int pnvo_conv_x3_describe(const int *problem, int n, char *buf, size_t cap);
  * problem == NULL: the instance name of row n of the table of instantiated kernels, PNVO_ERR_ARG past its last row. */
 int pnvo_wgrad_describe(const int *problem, int n, char *buf, size_t cap);
 
+/* Host only (no device, no handle): what the planner of the float32-MFMA convs and Linear layers decides for one problem, as one line —
+ *   "<family> <instance> | grid <x>x<y>x<z> block <threads> lds <bytes> wsplit <0/1> ksplit <slices> scratch <floats> reduce <none|plain|head> <grid>
+ *    | tiles <x>x<y> groups <n> items <n> ldsf <floats> slots <n> wrows <n>"          or "none" (no instantiated kernel serves it)
+ * family: generic (mt, nt, mode, jc, feat), lds_tile (blk, wy, wx, nt, mode), lds_wave (blk, nt, mode, mt).  problem: n = 33 ints — B, H, W,
+ * CIN, Ho, Wo, COUT, COUTP, KH, KW, stride, pad, up (2: input upsampled by two), channel stride of the output, operand mode (0 plain,
+ * 1 producer GroupNorm + ReLU, 2 observation tensors), accumulate (0 / 1), the strided output map y_sh, y_sw, y_oh, y_ow, y_H, y_W (y_sh = 0:
+ * dense), then 0 / 1 each: linear epilogue (bias / ReLU), statistics wanted, split-K scratch available; the units of an output head offered
+ * to ride on a split-K reduction (0: none); LDS-staged forms allowed (0 / 1); then the plan options fp32_tile (0 auto, 10*MT+NT),
+ * fp32_wsplit (-1 auto, 0, 1), fp32_form (0 auto, 1 tile, 2 wave), wave_wgs, wave_nt and the CU count.
+ * problem == NULL: the instance key of row n of the table of instantiated kernels, PNVO_ERR_ARG past its last row. */
+int pnvo_conv_fp32_describe(const int *problem, int n, char *buf, size_t cap);
+
 int pnvo_timing_mode(pnvo_handle h, int mode);
 int pnvo_timing_read(pnvo_handle h, pnvo_kernel_time *entries, int cap, int *n_out);
 

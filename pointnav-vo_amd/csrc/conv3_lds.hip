@@ -16,10 +16,6 @@
 //   * input channels beyond 32 are walked in chunks with the next chunk's global loads in flight during the MFMAs of
 //     the current one (double-buffered LDS, one barrier per chunk).
 // Statistics slot = (tile, wave): one writer per (sample, slot, channel), fixed summation order in gn_finalize.
-#include <cstdlib>
-#include <cstring>
-#include <map>
-
 #include "pnvo_internal.h"
 
 namespace pnvo {
@@ -464,157 +460,39 @@ __global__ __launch_bounds__(256) void conv3_wave_kernel(const ConvArgs p, int b
   }
 }
 
-namespace {
-struct Cfg {
-  int blk, wy, wx;
-};
-constexpr Cfg CFGS[3] = {{0, 4, 1}, {1, 3, 1}, {0, 3, 1}};
-
-inline void cfg_tiles(const Cfg &c, int Ho, int Wo, int *tx, int *ty) {
-  const int th = (c.blk ? 8 : 4) * c.wy, tw = (c.blk ? 4 : 8) * c.wx;
-  *tx = (Wo + tw - 1) / tw;
-  *ty = (Ho + th - 1) / th;
+// ---- the instances conv_fp32_plan's table lists (conv_mfma.hip): launch size, tiles and item count come with the plan
+size_t conv3_tile_lds_bytes(int blk, int wy, int wx) {   // two buffers of the workgroup's (TH+2) x (TW+2) patch
+  const int ph = (blk ? 8 : 4) * wy + 2, pwr = (blk ? 4 : 8) * wx + 2;
+  return (size_t)ph * patch_pitch(blk, pwr) * PP * 4 * 2;
 }
-inline double cfg_waste(const Cfg &c, int Ho, int Wo) {
-  int tx, ty;
-  cfg_tiles(c, Ho, Wo, &tx, &ty);
-  const int th = (c.blk ? 8 : 4) * c.wy, tw = (c.blk ? 4 : 8) * c.wx;
-  return (double)tx * tw * ty * th / ((double)Ho * Wo);
-}
-inline int pick_cfg(int Ho, int Wo) {
-  int best = 0;
-  for (int k = 1; k < 3; ++k)
-    if (cfg_waste(CFGS[k], Ho, Wo) < cfg_waste(CFGS[best], Ho, Wo) - 1e-9) best = k;
-  return best;
+size_t conv3_wave_lds_bytes(int blk, int mt) {           // one patch of mt stacked pixel blocks per wave
+  const int ph = (blk ? 8 : 4) * mt + 2, pwr = (blk ? 4 : 8) + 2;
+  return (size_t)4 * ph * patch_pitch(blk, pwr) * PP * 4;
 }
 
-template <int BLK, int WY, int WX, int NT>
-hipError_t launch_cfg(const ConvArgs &a, int tiles_x, int tiles_y, hipStream_t s) {
-  constexpr int BH = BLK ? 8 : 4, BW = BLK ? 4 : 8;
-  constexpr int PH = BH * WY + 2, PWR = BW * WX + 2, PWP = patch_pitch(BLK, PWR);
-  const size_t lds = (size_t)PH * PWP * PP * 4 * 2;
-  const int ngroups = a.COUTP / 32 / NT;
-  const long nwork = (long)a.B * tiles_x * tiles_y * ngroups;
-  // persistent grid: as many workgroups as fit (LDS-limited), rounded so that every workgroup gets the same item count
-  const long resident = 256L * (long)((160 * 1024) / lds);
-  const long rounds = (nwork + resident - 1) / resident;
-  const long grid_x = (nwork + rounds - 1) / rounds;
-  dim3 grid((unsigned)grid_x);
-  if (a.in_scale != nullptr)
-    hipLaunchKernelGGL((conv3_lds_kernel<BLK, WY, WX, NT, 1>), grid, dim3(64 * WY * WX), lds, s, a, tiles_x, tiles_y,
-                       ngroups, (int)nwork);
-  else
-    hipLaunchKernelGGL((conv3_lds_kernel<BLK, WY, WX, NT, 0>), grid, dim3(64 * WY * WX), lds, s, a, tiles_x, tiles_y,
-                       ngroups, (int)nwork);
+template <int BLK, int WY, int WX, int NT, int XF>
+hipError_t conv3_tile_launch(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s) {
+  hipLaunchKernelGGL((conv3_lds_kernel<BLK, WY, WX, NT, XF>), dim3(p.grid_x), dim3(64 * WY * WX), p.lds_bytes, s, a, p.tiles_x, p.tiles_y,
+                     p.ngroups, (int)p.items);
   return hipGetLastError();
 }
-}  // namespace
-
-namespace {
-inline int wave_blk(int Ho, int Wo, double *waste) {   // block shape (0: 4x8, 1: 8x4) with the least padding
-  auto w = [&](int bh, int bw) { return (double)((Ho + bh - 1) / bh * bh) * ((Wo + bw - 1) / bw * bw) / ((double)Ho * Wo); };
-  const double w0 = w(4, 8), w1 = w(8, 4);
-  if (waste) *waste = w0 <= w1 ? w0 : w1;
-  return w0 <= w1 ? 0 : 1;
-}
-
-template <int BLK, int NT, int MT>
-hipError_t launch_wave(const ConvArgs &a, hipStream_t s) {
-  constexpr int BH = (BLK ? 8 : 4) * MT, BW = BLK ? 4 : 8;
-  constexpr int PH = BH + 2, PWR = BW + 2, PWP = patch_pitch(BLK, PWR);
-  const size_t lds = (size_t)4 * PH * PWP * PP * 4;
-  const int bx = (a.Wo + BW - 1) / BW, by = (a.Ho + BH - 1) / BH;
-  const int ngroups = a.COUTP / 32 / NT;
-  const long nwork = (long)a.B * bx * by * ngroups;
-  long wgs = 256L * (long)((160 * 1024) / lds);
-  // 3 workgroups per CU (12 waves): measured 112 vs 103 TFLOP/s against 4 on the 64-channel stage (8448 items: with 4096
-  // waves a quarter of the SIMDs end with one wave running a third item alone), equal on the 128-channel stage.
-  static const int cap = std::getenv("PNVO_WAVE_WGS") ? std::atoi(std::getenv("PNVO_WAVE_WGS")) : 3;
-  if (cap > 0 && wgs > 256L * cap) wgs = 256L * cap;
-  if (wgs * 4 > nwork) wgs = (nwork + 3) / 4;
-  if (a.in_scale != nullptr)
-    hipLaunchKernelGGL((conv3_wave_kernel<BLK, NT, 1, MT>), dim3((unsigned)wgs), dim3(256), lds, s, a, bx, by, ngroups,
-                       (int)nwork);
-  else
-    hipLaunchKernelGGL((conv3_wave_kernel<BLK, NT, 0, MT>), dim3((unsigned)wgs), dim3(256), lds, s, a, bx, by, ngroups,
-                       (int)nwork);
+template <int BLK, int NT, int XF, int MT>
+hipError_t conv3_wave_launch(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s) {
+  hipLaunchKernelGGL((conv3_wave_kernel<BLK, NT, XF, MT>), dim3(p.grid_x), dim3(256), p.lds_bytes, s, a, p.tiles_x, p.tiles_y, p.ngroups,
+                     (int)p.items);
   return hipGetLastError();
 }
-
-// 32-channel layers carry few MFMAs per block: stack two 4x8 blocks per wave item when the height allows it.
-int wave_mt(const ConvArgs &a, int blk) { return (blk == 0 && a.CIN == 32 && a.COUTP == 32 && a.Ho % 8 == 0) ? 2 : 1; }
-
-// Which LDS-staged kernel?  The wave-private one wins where an item carries enough MFMAs to amortise its private staging
-// (>= 64 input channels: 105-112 vs 87-93 TFLOP/s); the 32-channel stage keeps the workgroup-tile kernel (100 vs 85).
-// PNVO_CONV3 = tile | wave forces one of them.
-bool use_wave_kernel(const ConvArgs &a) {
-  static const int v = [] {
-    const char *e = std::getenv("PNVO_CONV3");
-    return !e ? -1 : (std::strcmp(e, "tile") == 0 ? 0 : (std::strcmp(e, "wave") == 0 ? 1 : -1));
-  }();
-  if (v >= 0) return v != 0;
-  return a.CIN >= 64;
-}
-}  // namespace
-
-// Can this layer run on an LDS-staged kernel?  (3x3, stride 1, pad 1, 32-channel multiples, per-sample image big
-// enough that the pixel blocks waste < 15 % of the MFMA rows, offsets within 32 bits.)
-bool conv3_lds_supported(const ConvArgs &a) {
-  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.up == 2 || a.accum || a.src_mode || a.bias != nullptr ||
-      a.relu_out)
-    return false;
-  if (a.CIN % 32 != 0 || a.COUTP % 32 != 0 || a.H != a.Ho || a.W != a.Wo) return false;
-  if ((long)a.H * a.W * a.CIN * 4 >= 0x7FFFF000L || (long)a.Ho * a.Wo * a.y_cstride * 4 >= 0x7FFFF000L) return false;
-  if (use_wave_kernel(a)) {
-    double waste;
-    (void)wave_blk(a.Ho, a.Wo, &waste);
-    return waste < 1.15;
-  }
-  return cfg_waste(CFGS[pick_cfg(a.Ho, a.Wo)], a.Ho, a.Wo) < 1.15;
-}
-
-int conv3_lds_slots(const ConvArgs &a) {
-  if (use_wave_kernel(a)) {
-    const int blk = wave_blk(a.Ho, a.Wo, nullptr);
-    const int bh = (blk ? 8 : 4) * wave_mt(a, blk), bw = blk ? 4 : 8;
-    return ((a.Ho + bh - 1) / bh) * ((a.Wo + bw - 1) / bw);
-  }
-  const Cfg &c = CFGS[pick_cfg(a.Ho, a.Wo)];
-  int tx, ty;
-  cfg_tiles(c, a.Ho, a.Wo, &tx, &ty);
-  return tx * ty * c.wy * c.wx;
-}
-
-// nt: output n-tiles (32 channels) per wave, 1 or 2 (a.COUTP / 32 must be divisible by it).
-hipError_t launch_conv3_lds(const ConvArgs &a, int nt, hipStream_t s) {
-  if (!conv3_lds_supported(a) || (nt != 1 && nt != 2) || (a.COUTP / 32) % nt != 0) return hipErrorInvalidValue;
-  if (use_wave_kernel(a)) {
-    // one output-channel tile per item: twice the items of half the size divide more evenly over the 3072 waves (stage 3:
-    // 9216 items = exactly 3 each) — 115-119 vs 109-112 TFLOP/s with two (PNVO_WAVE_NT=2)
-    static const int wnt = std::getenv("PNVO_WAVE_NT") ? std::atoi(std::getenv("PNVO_WAVE_NT")) : 1;
-    if (wnt == 1) nt = 1;
-    const int blk = wave_blk(a.Ho, a.Wo, nullptr);
-    const int mt = wave_mt(a, blk);
-    switch (blk * 100 + nt * 10 + mt) {
-      case 11: return launch_wave<0, 1, 1>(a, s);
-      case 12: return launch_wave<0, 1, 2>(a, s);
-      case 21: return launch_wave<0, 2, 1>(a, s);
-      case 111: return launch_wave<1, 1, 1>(a, s);
-      default: return launch_wave<1, 2, 1>(a, s);
-    }
-  }
-  const int k = pick_cfg(a.Ho, a.Wo);
-  int tx, ty;
-  cfg_tiles(CFGS[k], a.Ho, a.Wo, &tx, &ty);
-  switch (k * 10 + nt) {
-    case 1: return launch_cfg<0, 4, 1, 1>(a, tx, ty, s);
-    case 2: return launch_cfg<0, 4, 1, 2>(a, tx, ty, s);
-    case 11: return launch_cfg<1, 3, 1, 1>(a, tx, ty, s);
-    case 12: return launch_cfg<1, 3, 1, 2>(a, tx, ty, s);
-    case 21: return launch_cfg<0, 3, 1, 1>(a, tx, ty, s);
-    case 22: return launch_cfg<0, 3, 1, 2>(a, tx, ty, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+#define PNVO_TILE(BLK, WY, WX)                                                                              \
+  template hipError_t conv3_tile_launch<BLK, WY, WX, 1, 0>(const ConvArgs &, const ConvFp32Plan &, hipStream_t); \
+  template hipError_t conv3_tile_launch<BLK, WY, WX, 1, 1>(const ConvArgs &, const ConvFp32Plan &, hipStream_t); \
+  template hipError_t conv3_tile_launch<BLK, WY, WX, 2, 0>(const ConvArgs &, const ConvFp32Plan &, hipStream_t); \
+  template hipError_t conv3_tile_launch<BLK, WY, WX, 2, 1>(const ConvArgs &, const ConvFp32Plan &, hipStream_t);
+#define PNVO_WAVE(BLK, NT, MT)                                                                           \
+  template hipError_t conv3_wave_launch<BLK, NT, 0, MT>(const ConvArgs &, const ConvFp32Plan &, hipStream_t); \
+  template hipError_t conv3_wave_launch<BLK, NT, 1, MT>(const ConvArgs &, const ConvFp32Plan &, hipStream_t);
+PNVO_TILE(0, 4, 1) PNVO_TILE(1, 3, 1) PNVO_TILE(0, 3, 1)
+PNVO_WAVE(0, 1, 1) PNVO_WAVE(0, 1, 2) PNVO_WAVE(0, 2, 1) PNVO_WAVE(1, 1, 1) PNVO_WAVE(1, 2, 1)
+#undef PNVO_TILE
+#undef PNVO_WAVE
 
 }  // namespace pnvo

@@ -19,6 +19,8 @@
 //  * no barriers in the K loop: waves are independent, 2-3 waves/SIMD hide the load latency under the 64-cycle MFMAs.
 #include "pnvo_internal.h"
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 
 namespace pnvo {
 
@@ -47,7 +49,7 @@ __device__ __forceinline__ unsigned clamp_records(long bytes) {
 // loads of a lane hit ONE 128-B line back to back, so the line comes from L2 once per tap instead of once per 16-B
 // slice (measured 4x L2 over-fetch with JC = 1: profiles/r1_kernel_mfma_busy.md).
 // FEAT (compile-time so that the common kernels carry none of it): 0 plain; 1 the 4 waves of a workgroup share one tile and
-// split its reduction (ConvArgs::wsplit); 2 strided output map (ConvArgs::y_sh, parity phases of a stride-2 backward-data conv).
+// split its reduction (ConvFp32Plan::wsplit); 2 strided output map (ConvArgs::y_sh, parity phases of a stride-2 backward-data conv).
 template <int MT, int NT, int MODE, int JC, int FEAT>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
   constexpr bool XF = (MODE != 0);
@@ -376,140 +378,6 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
   }
 }
 
-int conv_slots(int P, int MT) {
-  const int WM = MT * 32;
-  return (P + WM - 1) / WM + 1;
-}
-
-void choose_tile(long M, int COUTP, int *MT, int *NT) {
-  // One 32-pixel tile per wave, 1 / 2 / 4 output-channel tiles.  Measured on every generic conv of the default model at 256
-  // pairs (PNVO_CONV_TILE sweep): what decides is how evenly the workgroups divide over the 256 CUs —
-  // 528 workgroups (2.06 per CU) lose to 1056 of half the size by 8 % despite the lower operand reuse — so: score =
-  // (workgroups per CU) / ceil(workgroups per CU) x a mild preference for more n-tiles per wave; larger pixel tiles
-  // (MT = 2, 4) lost everywhere.
-  const int ntg = COUTP / 32;
-  const long rows = (M + 127) / 128;                       // workgroups along M (4 waves x 32 pixels)
-  static const double reuse[5] = {0.0, 1.0, 1.08, 0.0, 1.12};
-  int best_nt = 1;
-  double best = -1.0;
-  for (int nt = 1; nt <= 4; nt *= 2) {
-    if (ntg % nt) continue;
-    const double per_cu = (double)(rows * (ntg / nt)) / 256.0;
-    const double balance = per_cu >= 1.0 ? per_cu / std::ceil(per_cu) : per_cu;
-    const double score = balance * reuse[nt];
-    if (score > best) {
-      best = score;
-      best_nt = nt;
-    }
-  }
-  int mt = 1, nt = best_nt;
-  static const int force = std::getenv("PNVO_CONV_TILE") ? std::atoi(std::getenv("PNVO_CONV_TILE")) : 0;   // experiment knob: 10*MT+NT
-  if (force > 0 && ntg % (force % 10) == 0 && M >= 8192) {
-    mt = force / 10;
-    nt = force % 10;
-  }
-  *MT = mt;
-  *NT = nt;
-}
-
-// Split the reduction of every tile over the 4 waves of its workgroup?  Pays when whole-tile items divide badly over the
-// SIMDs (stage 4 at 256 pairs: 4.125 wave items per SIMD run as 5; split, 16.5 quarter items run as 17) or do not fill the
-// chip at all (batch 1), and the reduction is long enough to quarter.
-int conv_wsplit(const ConvArgs &a) {
-  static const int force = std::getenv("PNVO_CONV_WSPLIT") ? std::atoi(std::getenv("PNVO_CONV_WSPLIT")) : -1;   // experiment knob
-  if (a.src_mode || a.ksplit > 1 || a.MT != 1 || a.NT > 2 || a.y_sh != 0) return 0;
-  const int jc = (a.MT != 4 && a.CIN % 32 == 0) ? ((a.in_scale != nullptr && a.MT * a.NT >= 4) ? 2 : 4) : 1;
-  const int S = a.KH * a.KW * (a.CIN / 8) / jc;
-  if (S < 16) return 0;
-  if (force >= 0) return force;
-  const long P = (long)a.Ho * a.Wo, M = (long)a.B * P;
-  const long WM = a.MT * 32, groups = a.COUTP / 32 / a.NT;
-  const double whole = (double)(((M + 4 * WM - 1) / (4 * WM)) * groups) / 256.0;      // 4-wave workgroups per CU = waves per SIMD
-  const double split = (double)(((M + WM - 1) / WM) * groups) / 256.0;                // quarter-size waves per SIMD
-  const double t_whole = std::ceil(whole), t_split = std::ceil(split) / 4.0;
-  return t_split < 0.88 * t_whole ? 1 : 0;      // the LDS hand-over and three idle epilogues cost ~8 % (measured: 33/4 vs 9 lost)
-}
-
-template <int MT, int NT>
-static hipError_t launch_t(const ConvArgs &a, hipStream_t s) {
-  const long P = (long)a.Ho * a.Wo, M = (long)a.B * P;
-  const int WM = MT * 32;
-  ConvArgs p = a;
-  p.wsplit = conv_wsplit(a);
-  const long wg_rows = p.wsplit ? WM : 4L * WM;
-  const size_t red_bytes = p.wsplit ? (size_t)3 * MT * NT * 16 * 64 * 4 : 0;
-  dim3 grid((unsigned)((M + wg_rows - 1) / wg_rows), (unsigned)(a.COUTP / 32 / NT), (unsigned)(a.ksplit > 1 ? a.ksplit : 1));
-  if (a.ksplit > 1) {            // raw partials: bias and ReLU belong to the reduce
-    p.bias = nullptr;
-    p.bias_row = nullptr;
-    p.relu_out = 0;
-  }
-  size_t lds_bytes = 0;
-  // 32-channel stages where the register file allows 2 waves/SIMD; the GN-prologue variant of the 4-accumulator
-  // tiles (2x2, 1x4) only fits 16-channel stages
-  constexpr int JCF = (MT == 4) ? 1 : 4;
-  constexpr int JCX = (MT == 4) ? 1 : ((MT * NT >= 4) ? 2 : 4);
-  const bool wide = (JCF > 1) && (a.CIN % 32 == 0);
-  const int feat = p.wsplit ? 1 : (a.y_sh != 0 ? 2 : 0);
-  if (feat != 0 && (MT != 1 || NT > 2 + 2 * (feat == 2) || a.src_mode || (feat == 2 && a.in_scale != nullptr))) return hipErrorInvalidValue;
-#define PNVO_LAUNCH(MODE_, JC_, LDS_)                                                                                   \
-  do {                                                                                                                  \
-    if (feat == 0)                                                                                                      \
-      hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, MODE_, JC_, 0>), grid, dim3(256), (LDS_), s, p);                     \
-    else if constexpr (MT == 1 && NT <= 2 && MODE_ != 2) {                                                              \
-      if (feat == 1)                                                                                                    \
-        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, MODE_, JC_, 1>), grid, dim3(256), (LDS_) + red_bytes, s, p);       \
-      else if constexpr (MODE_ == 0)                                                                                    \
-        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, MODE_, JC_, 2>), grid, dim3(256), (LDS_), s, p);                   \
-    } else if constexpr (MT == 1 && MODE_ == 0) {                                                                       \
-      if (feat == 2) hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, MODE_, JC_, 2>), grid, dim3(256), (LDS_), s, p);     \
-    }                                                                                                                   \
-  } while (0)
-  if (a.src_mode) {
-    p.lds_floats = 2 * a.CIN;
-    PNVO_LAUNCH(2, 1, (size_t)p.lds_floats * 4);
-  } else if (a.in_scale != nullptr) {
-    const long cnt_max = (wg_rows + P - 2) / P + 1;
-    const long need = cnt_max * a.CIN * 2;
-    if (need * 4 <= 48 * 1024) {
-      p.lds_floats = (int)need;
-      lds_bytes = (size_t)need * 4;
-    } else {
-      p.lds_floats = 0;
-    }
-    if (wide)
-      PNVO_LAUNCH(1, JCX, lds_bytes);
-    else
-      PNVO_LAUNCH(1, 1, lds_bytes);
-  } else {
-    p.lds_floats = 0;
-    if (wide)
-      PNVO_LAUNCH(0, JCF, (size_t)0);
-    else
-      PNVO_LAUNCH(0, 1, (size_t)0);
-  }
-#undef PNVO_LAUNCH
-  return hipGetLastError();
-}
-
-// Split-K pays when a linear layer has too few output tiles to fill the chip and a long reduction (the 6x11 "conv" of the
-// FC: 32 workgroups x 66 stages at 256 pairs).  Only for plain linear epilogues (no statistics, no accumulate).
-int conv_ksplit(const ConvArgs &a) {
-  if (a.kpart == nullptr || a.stats != nullptr || a.accum || a.src_mode) return 1;
-  const long P = (long)a.Ho * a.Wo, M = (long)a.B * P;
-  const long wgs = ((M + 4L * a.MT * 32 - 1) / (4L * a.MT * 32)) * (a.COUTP / 32 / a.NT);
-  int jc = 1;                          // channel groups per pipeline stage, as launch_t picks them
-  if (a.MT != 4 && a.CIN % 32 == 0) jc = (a.in_scale != nullptr && a.MT * a.NT >= 4) ? 2 : 4;
-  const int S = a.KH * a.KW * (a.CIN / 8) / jc;
-  if (wgs >= 128 || S < 16) return 1;
-  int k = (int)(512 / wgs);
-  if (k > S / 4) k = S / 4;
-  if (k > 32) k = 32;
-  if (k < 2) return 1;
-  const int per = (S + k - 1) / k;
-  return (S + per - 1) / per;        // every slice non-empty
-}
-
 __global__ __launch_bounds__(256) void ksplit_reduce_kernel(const float *part, int ks, long M, int C, const float *bias,
                                                           const int64_t *bias_row, int COUT, long P, int relu, float *y) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -560,31 +428,317 @@ __global__ __launch_bounds__(256) void ksplit_reduce_head_kernel(const float *pa
   }
 }
 
-hipError_t launch_ksplit_reduce_head(const ConvArgs &a, const float *w2, const float *b2, int out_dim, float *out, hipStream_t s) {
-  if (a.Ho * a.Wo != 1 || out_dim < 1 || out_dim > 4 || a.y_cstride != a.COUT) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ksplit_reduce_head_kernel, dim3((unsigned)a.B), dim3(256), 0, s, a.kpart, a.ksplit, (long)a.B, a.y_cstride, a.bias,
-                     a.bias_row, a.relu_out, a.y, w2, b2, out_dim, out);
+// ---- host side: the table of instantiated kernels (this file's and conv3_lds.hip's), the planner, the launch
+namespace {
+struct Fp32Key {
+  int family;      // ConvFp32Plan::Family
+  int t[5];        // GENERIC MT, NT, MODE, JC, FEAT | LDS_TILE BLK, WY, WX, NT, XF | LDS_WAVE BLK, NT, XF, MT, 0
+  bool operator==(const Fp32Key &o) const { return std::memcmp(this, &o, sizeof(Fp32Key)) == 0; }
+};
+struct Fp32Instance {
+  Fp32Key key;
+  int threads;
+  hipError_t (*launch)(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s);
+};
+template <int MT, int NT, int MODE, int JC, int FEAT>
+hipError_t generic_launch(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s) {
+  hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, MODE, JC, FEAT>), dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), p.lds_bytes, s, a);
   return hipGetLastError();
 }
-
-hipError_t launch_ksplit_reduce(const ConvArgs &a, hipStream_t s) {
-  const long P = (long)a.Ho * a.Wo, M = (long)a.B * P;
-  hipLaunchKernelGGL(ksplit_reduce_kernel, dim3((unsigned)((M * a.y_cstride + 255) / 256)), dim3(256), 0, s, a.kpart, a.ksplit,
-                     M, a.y_cstride, a.bias, a.bias_row, a.COUT, P, a.relu_out, a.y);
-  return hipGetLastError();
+#define FP32_G(MT, NT, MODE, JC, FEAT) {{ConvFp32Plan::GENERIC, {MT, NT, MODE, JC, FEAT}}, 256, generic_launch<MT, NT, MODE, JC, FEAT>},
+// a wave tile's plain instances: the observation-tensor fetch, then each operand mode on 32-channel stages (JC 4; the GroupNorm
+// prologue of the four-accumulator tiles 2x2 and 1x4 only fits 16-channel stages, JC 2) and on 8-channel stages (JC 1)
+#define FP32_G_TILE(MT, NT, JCX) FP32_G(MT, NT, 2, 1, 0) FP32_G(MT, NT, 1, JCX, 0) FP32_G(MT, NT, 1, 1, 0) FP32_G(MT, NT, 0, 4, 0) FP32_G(MT, NT, 0, 1, 0)
+#define FP32_G_WSPLIT(NT) FP32_G(1, NT, 1, 4, 1) FP32_G(1, NT, 1, 1, 1) FP32_G(1, NT, 0, 4, 1) FP32_G(1, NT, 0, 1, 1)
+#define FP32_G_PHASE(NT) FP32_G(1, NT, 0, 4, 2) FP32_G(1, NT, 0, 1, 2)
+#define FP32_T1(BLK, WY, WX, NT, XF) {{ConvFp32Plan::LDS_TILE, {BLK, WY, WX, NT, XF}}, 64 * WY * WX, conv3_tile_launch<BLK, WY, WX, NT, XF>},
+#define FP32_T(BLK, WY, WX) FP32_T1(BLK, WY, WX, 1, 0) FP32_T1(BLK, WY, WX, 1, 1) FP32_T1(BLK, WY, WX, 2, 0) FP32_T1(BLK, WY, WX, 2, 1)
+#define FP32_W1(BLK, NT, XF, MT) {{ConvFp32Plan::LDS_WAVE, {BLK, NT, XF, MT, 0}}, 256, conv3_wave_launch<BLK, NT, XF, MT>},
+#define FP32_W(BLK, NT, MT) FP32_W1(BLK, NT, 0, MT) FP32_W1(BLK, NT, 1, MT)
+const Fp32Instance fp32_table[] = {
+  FP32_G(4, 1, 2, 1, 0) FP32_G(4, 1, 1, 1, 0) FP32_G(4, 1, 0, 1, 0)          // 4x1: 8-channel stages only (the register file)
+  FP32_G_TILE(2, 1, 4) FP32_G_TILE(1, 1, 4) FP32_G_TILE(2, 2, 2) FP32_G_TILE(1, 2, 4) FP32_G_TILE(1, 4, 2)
+  FP32_G_WSPLIT(1) FP32_G_WSPLIT(2)                                          // FEAT 1: the four waves split one tile's reduction
+  FP32_G_PHASE(1) FP32_G_PHASE(2) FP32_G_PHASE(4)                            // FEAT 2: strided output map, plain operand only
+  FP32_T(0, 4, 1) FP32_T(1, 3, 1) FP32_T(0, 3, 1)                            // conv3_lds_kernel: the three workgroup tiles (CFGS)
+  FP32_W(0, 1, 1) FP32_W(0, 1, 2) FP32_W(0, 2, 1) FP32_W(1, 1, 1) FP32_W(1, 2, 1)   // conv3_wave_kernel
+};
+#undef FP32_G
+#undef FP32_G_TILE
+#undef FP32_G_WSPLIT
+#undef FP32_G_PHASE
+#undef FP32_T1
+#undef FP32_T
+#undef FP32_W1
+#undef FP32_W
+constexpr int fp32_table_rows = (int)(sizeof(fp32_table) / sizeof(fp32_table[0]));
+int fp32_find(const Fp32Key &k) {
+  for (int i = 0; i < fp32_table_rows; ++i)
+    if (fp32_table[i].key == k) return i;
+  return -1;
 }
 
-hipError_t launch_conv(const ConvArgs &a, hipStream_t s) {
-  if (a.CIN % 8 != 0 || a.COUTP % 32 != 0 || (a.COUTP / 32) % a.NT != 0) return hipErrorInvalidValue;
-  switch (a.MT * 10 + a.NT) {
-    case 41: return launch_t<4, 1>(a, s);
-    case 21: return launch_t<2, 1>(a, s);
-    case 11: return launch_t<1, 1>(a, s);
-    case 22: return launch_t<2, 2>(a, s);
-    case 12: return launch_t<1, 2>(a, s);
-    case 14: return launch_t<1, 4>(a, s);
-    default: return hipErrorInvalidValue;
+void choose_tile(const ConvFp32Problem &q, long M, int *MT, int *NT) {
+  // One 32-pixel tile per wave, 1 / 2 / 4 output-channel tiles.  Measured on every generic conv of the default model at 256
+  // pairs (option fp32_tile sweep): what decides is how evenly the workgroups divide over the CUs —
+  // 528 workgroups (2.06 per CU) lose to 1056 of half the size by 8 % despite the lower operand reuse — so: score =
+  // (workgroups per CU) / ceil(workgroups per CU) x a mild preference for more n-tiles per wave; larger pixel tiles
+  // (MT = 2, 4) lost everywhere.
+  const int ntg = q.COUTP / 32;
+  const long rows = (M + 127) / 128;                       // workgroups along M (4 waves x 32 pixels)
+  static const double reuse[5] = {0.0, 1.0, 1.08, 0.0, 1.12};
+  int best_nt = 1;
+  double best = -1.0;
+  for (int nt = 1; nt <= 4; nt *= 2) {
+    if (ntg % nt) continue;
+    const double per_cu = (double)(rows * (ntg / nt)) / (double)q.opt.num_cus;
+    const double balance = per_cu >= 1.0 ? per_cu / std::ceil(per_cu) : per_cu;
+    const double score = balance * reuse[nt];
+    if (score > best) {
+      best = score;
+      best_nt = nt;
+    }
   }
+  *MT = 1;
+  *NT = best_nt;
+  const int force = q.opt.tile;                            // experiment knob: 10*MT+NT
+  if (force > 0 && force % 10 > 0 && ntg % (force % 10) == 0 && M >= 8192) {
+    *MT = force / 10;
+    *NT = force % 10;
+  }
+}
+
+// 8-channel groups per pipeline stage: 32-channel stages where the register file allows 2 waves/SIMD; the GN-prologue variant of
+// the 4-accumulator tiles (2x2, 1x4) only fits 16-channel stages
+int stage_groups(const ConvFp32Problem &q, int MT, int NT) {
+  if (q.mode == 2 || MT == 4 || q.CIN % 32 != 0) return 1;
+  return (q.mode == 1 && MT * NT >= 4) ? 2 : 4;
+}
+
+// Split-K pays when a linear layer has too few output tiles to fill the chip and a long reduction (the 6x11 "conv" of the
+// FC: 32 workgroups x 66 stages at 256 pairs).  Only for plain linear epilogues (no statistics, no accumulate, dense output).
+int conv_ksplit(const ConvFp32Problem &q, long M, int MT, int NT, int S) {
+  if (!q.ksplit_ok || q.stats || q.accum || q.mode == 2 || q.y_sh != 0) return 1;
+  const long wgs = ((M + 4L * MT * 32 - 1) / (4L * MT * 32)) * (q.COUTP / 32 / NT);
+  if (wgs >= 128 || S < 16) return 1;
+  int k = (int)(512 / wgs);
+  if (k > S / 4) k = S / 4;
+  if (k > 32) k = 32;
+  if (k < 2) return 1;
+  const int per = (S + k - 1) / k;
+  return (S + per - 1) / per;        // every slice non-empty
+}
+
+// Split the reduction of every tile over the 4 waves of its workgroup?  Pays when whole-tile items divide badly over the
+// SIMDs (stage 4 at 256 pairs: 4.125 wave items per SIMD run as 5; split, 16.5 quarter items run as 17) or do not fill the
+// chip at all (batch 1), and the reduction is long enough to quarter.
+int conv_wsplit(const ConvFp32Problem &q, long M, int MT, int NT, int S, int ksplit) {
+  if (q.mode == 2 || ksplit > 1 || MT != 1 || NT > 2 || q.y_sh != 0) return 0;
+  if (S < 16) return 0;
+  if (q.opt.wsplit >= 0) return q.opt.wsplit;
+  const long WM = MT * 32, groups = q.COUTP / 32 / NT;
+  const double cus = (double)q.opt.num_cus;
+  const double whole = (double)(((M + 4 * WM - 1) / (4 * WM)) * groups) / cus;      // 4-wave workgroups per CU = waves per SIMD
+  const double split = (double)(((M + WM - 1) / WM) * groups) / cus;                // quarter-size waves per SIMD
+  const double t_whole = std::ceil(whole), t_split = std::ceil(split) / 4.0;
+  return t_split < 0.88 * t_whole ? 1 : 0;      // the LDS hand-over and three idle epilogues cost ~8 % (measured: 33/4 vs 9 lost)
+}
+
+// conv3_lds_kernel's workgroup tiles {BLK, WY, WX}: the one that pads the sample's map least
+struct Cfg {
+  int blk, wy, wx;
+};
+constexpr Cfg CFGS[3] = {{0, 4, 1}, {1, 3, 1}, {0, 3, 1}};
+void cfg_tiles(const Cfg &c, int Ho, int Wo, int *tx, int *ty) {
+  const int th = (c.blk ? 8 : 4) * c.wy, tw = (c.blk ? 4 : 8) * c.wx;
+  *tx = (Wo + tw - 1) / tw;
+  *ty = (Ho + th - 1) / th;
+}
+double cfg_waste(const Cfg &c, int Ho, int Wo) {
+  int tx, ty;
+  cfg_tiles(c, Ho, Wo, &tx, &ty);
+  const int th = (c.blk ? 8 : 4) * c.wy, tw = (c.blk ? 4 : 8) * c.wx;
+  return (double)tx * tw * ty * th / ((double)Ho * Wo);
+}
+int pick_cfg(int Ho, int Wo) {
+  int best = 0;
+  for (int k = 1; k < 3; ++k)
+    if (cfg_waste(CFGS[k], Ho, Wo) < cfg_waste(CFGS[best], Ho, Wo) - 1e-9) best = k;
+  return best;
+}
+int wave_blk(int Ho, int Wo, double *waste) {   // conv3_wave_kernel's block shape (0: 4x8, 1: 8x4) with the least padding
+  auto w = [&](int bh, int bw) { return (double)((Ho + bh - 1) / bh * bh) * ((Wo + bw - 1) / bw * bw) / ((double)Ho * Wo); };
+  const double w0 = w(4, 8), w1 = w(8, 4);
+  *waste = w0 <= w1 ? w0 : w1;
+  return w0 <= w1 ? 0 : 1;
+}
+// 32-channel layers carry few MFMAs per block: stack two 4x8 blocks per wave item when the height allows it.
+int wave_mt(const ConvFp32Problem &q, int blk) { return (blk == 0 && q.CIN == 32 && q.COUTP == 32 && q.Ho % 8 == 0) ? 2 : 1; }
+// Which LDS-staged kernel?  The wave-private one wins where an item carries enough MFMAs to amortise its private staging
+// (>= 64 input channels: 105-112 vs 87-93 TFLOP/s); the 32-channel stage keeps the workgroup-tile kernel (100 vs 85).
+// Option fp32_form = tile | wave forces one of them.
+bool use_wave_kernel(const ConvFp32Problem &q) { return q.opt.form != 0 ? q.opt.form == 2 : q.CIN >= 64; }
+
+// The LDS-staged forms take 3x3 stride-1 pad-1 convs of 32-channel multiples with a plain epilogue, offsets within 32 bits, whose
+// per-sample map is big enough that the pixel blocks waste < 15 % of the MFMA rows.  NONE: the generic kernel's launch.
+ConvFp32Plan lds_candidate(const ConvFp32Problem &q) {
+  ConvFp32Plan p;
+  if (!q.lds_ok || q.KH != 3 || q.KW != 3 || q.stride != 1 || q.pad != 1 || q.up == 2 || q.accum || q.linear || q.y_sh != 0) return p;
+  if (q.CIN % 32 != 0 || q.H != q.Ho || q.W != q.Wo) return p;
+  if ((long)q.H * q.W * q.CIN * 4 >= 0x7FFFF000L || (long)q.Ho * q.Wo * q.y_cstride * 4 >= 0x7FFFF000L) return p;
+  const int ntg = q.COUTP / 32, cus = q.opt.num_cus;
+  p.NT = ntg % 2 == 0 ? 2 : 1;                             // output n-tiles (32 channels) per wave
+  p.MODE = q.mode;
+  if (use_wave_kernel(q)) {
+    double waste;
+    p.BLK = wave_blk(q.Ho, q.Wo, &waste);
+    if (!(waste < 1.15)) return p;
+    // one output-channel tile per item: twice the items of half the size divide more evenly over the 3072 waves (stage 3:
+    // 9216 items = exactly 3 each) — 115-119 vs 109-112 TFLOP/s with two (option wave_nt = 2)
+    if (q.opt.wave_nt == 1) p.NT = 1;
+    p.MT = wave_mt(q, p.BLK);
+    const int bh = (p.BLK ? 8 : 4) * p.MT, bw = p.BLK ? 4 : 8;
+    p.tiles_x = (q.Wo + bw - 1) / bw;
+    p.tiles_y = (q.Ho + bh - 1) / bh;
+    p.ngroups = ntg / p.NT;
+    p.items = (long)q.B * p.tiles_x * p.tiles_y * p.ngroups;
+    p.lds_bytes = conv3_wave_lds_bytes(p.BLK, p.MT);
+    long wgs = (long)cus * (long)((160 * 1024) / p.lds_bytes);
+    // 3 workgroups per CU (12 waves): measured 112 vs 103 TFLOP/s against 4 on the 64-channel stage (8448 items: with 4096
+    // waves a quarter of the SIMDs end with one wave running a third item alone), equal on the 128-channel stage.
+    if (q.opt.wave_wgs > 0 && wgs > (long)cus * q.opt.wave_wgs) wgs = (long)cus * q.opt.wave_wgs;
+    if (wgs * 4 > p.items) wgs = (p.items + 3) / 4;
+    p.grid_x = (unsigned)wgs;
+    p.block = 256;
+    p.slots = p.tiles_x * p.tiles_y;
+    p.inst = fp32_find({ConvFp32Plan::LDS_WAVE, {p.BLK, p.NT, p.MODE, p.MT, 0}});
+    p.family = ConvFp32Plan::LDS_WAVE;
+  } else {
+    const Cfg &c = CFGS[pick_cfg(q.Ho, q.Wo)];
+    if (!(cfg_waste(c, q.Ho, q.Wo) < 1.15)) return p;
+    p.BLK = c.blk;
+    p.WY = c.wy;
+    p.WX = c.wx;
+    cfg_tiles(c, q.Ho, q.Wo, &p.tiles_x, &p.tiles_y);
+    p.ngroups = ntg / p.NT;
+    p.items = (long)q.B * p.tiles_x * p.tiles_y * p.ngroups;
+    p.lds_bytes = conv3_tile_lds_bytes(c.blk, c.wy, c.wx);
+    // persistent grid: as many workgroups as fit (LDS-limited), rounded so that every workgroup gets the same item count
+    const long resident = (long)cus * (long)((160 * 1024) / p.lds_bytes);
+    const long rounds = (p.items + resident - 1) / resident;
+    p.grid_x = (unsigned)((p.items + rounds - 1) / rounds);
+    p.block = 64 * c.wy * c.wx;
+    p.slots = p.tiles_x * p.tiles_y * c.wy * c.wx;         // statistics slot = (tile, wave)
+    p.inst = fp32_find({ConvFp32Plan::LDS_TILE, {p.BLK, p.WY, p.WX, p.NT, p.MODE}});
+    p.family = ConvFp32Plan::LDS_TILE;
+  }
+  return p;
+}
+}  // namespace
+
+// The plan of a launch.  Family, wave tile and statistics slots are decided from shape, epilogue and options alone — never from the
+// operand mode — so a schedule that asks per layer with a default ask (mode 0) sizes buffers and names the family of the launch that
+// later comes with its real mode; mode moves only the stage width, the wave split and the LDS table (and the instance with them).
+ConvFp32Plan conv_fp32_plan(const ConvFp32Problem &q) {
+  const ConvFp32Plan none;
+  if (q.mode < 0 || q.mode > 2 || q.B <= 0 || q.H <= 0 || q.W <= 0 || q.Ho <= 0 || q.Wo <= 0 || q.KH <= 0 || q.KW <= 0 || q.CIN <= 0 ||
+      q.CIN % 8 != 0 || q.COUTP <= 0 || q.COUTP % 32 != 0 || q.y_cstride <= 0 || q.opt.num_cus <= 0)
+    return none;
+  if (ConvFp32Plan p = lds_candidate(q)) {
+    if (p.inst < 0 || p.items > 0x7fffffffL) return none;   // (the observation-tensor fetch: the LDS stagers have none)
+    return p;
+  }
+  ConvFp32Plan p;
+  const long P = (long)q.Ho * q.Wo, M = (long)q.B * P;
+  choose_tile(q, M, &p.MT, &p.NT);
+  p.MODE = q.mode;
+  p.JC = stage_groups(q, p.MT, p.NT);
+  const int WM = p.MT * 32, S = q.KH * q.KW * (q.CIN / 8) / p.JC;   // pipeline stages of the whole reduction
+  p.ksplit = conv_ksplit(q, M, p.MT, p.NT, S);
+  p.wsplit = conv_wsplit(q, M, p.MT, p.NT, S, p.ksplit);
+  p.FEAT = p.wsplit ? 1 : (q.y_sh != 0 ? 2 : 0);
+  p.inst = fp32_find({ConvFp32Plan::GENERIC, {p.MT, p.NT, p.MODE, p.JC, p.FEAT}});
+  if (p.inst < 0) return none;
+  const long wg_rows = p.wsplit ? WM : 4L * WM;
+  p.grid_x = (unsigned)((M + wg_rows - 1) / wg_rows);
+  p.grid_y = (unsigned)(q.COUTP / 32 / p.NT);
+  p.grid_z = (unsigned)p.ksplit;
+  p.block = 256;
+  p.items = (long)p.grid_x * p.grid_y * p.grid_z;
+  if (q.mode == 2) {                                       // the whitening table of the one input "sample"
+    p.lds_floats = 2 * q.CIN;
+  } else if (q.mode == 1) {                                // the producer's scale / shift of every sample a workgroup can touch, if they fit
+    const long need = ((wg_rows + P - 2) / P + 1) * q.CIN * 2;
+    p.lds_floats = need * 4 <= 48 * 1024 ? (int)need : 0;
+  }
+  p.lds_bytes = (size_t)p.lds_floats * 4 + (p.wsplit ? (size_t)3 * p.MT * p.NT * 16 * 64 * 4 : 0);   // ... and the split tile's hand-over
+  if (p.ksplit > 1) {
+    p.scratch_floats = (size_t)p.ksplit * M * q.y_cstride;
+    const bool rides = q.head >= 1 && q.head <= 4 && P == 1 && q.y_cstride == q.COUT;   // ksplit_reduce_head_kernel: one row per sample
+    p.reduce = rides ? ConvFp32Plan::HEAD : ConvFp32Plan::PLAIN;
+    p.reduce_grid = rides ? (unsigned)q.B : (unsigned)((M * q.y_cstride + 255) / 256);
+  }
+  p.slots = (int)((P + WM - 1) / WM) + 1;
+  p.wave_rows = WM;
+  p.family = ConvFp32Plan::GENERIC;
+  return p;
+}
+
+ConvArgs conv_fp32_args(const ConvFp32Problem &q, const ConvFp32Plan &p) {
+  ConvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.B = q.B; a.H = q.H; a.W = q.W; a.CIN = q.CIN; a.Ho = q.Ho; a.Wo = q.Wo; a.COUT = q.COUT; a.COUTP = q.COUTP;
+  a.KH = q.KH; a.KW = q.KW; a.stride = q.stride; a.pad = q.pad; a.up = q.up; a.y_cstride = q.y_cstride; a.accum = q.accum ? 1 : 0;
+  a.y_sh = q.y_sh; a.y_sw = q.y_sw; a.y_oh = q.y_oh; a.y_ow = q.y_ow; a.y_H = q.y_H; a.y_W = q.y_W;
+  a.slots = p.slots; a.lds_floats = p.lds_floats; a.ksplit = p.ksplit > 1 ? p.ksplit : 0;
+  return a;
+}
+
+// "<family> <instance key> | grid, block, LDS bytes, wsplit, ksplit, scratch floats, reduce launch | geometry, slots, wave_rows" of
+// q's plan, "none" without one; q == nullptr: the key of table row `row`.  Touches no HIP runtime call.
+int conv_fp32_describe(const ConvFp32Problem *q, int row, char *buf, size_t cap) {
+  const auto key = [&](const Fp32Key &k) {
+    const int *t = k.t;
+    if (k.family == ConvFp32Plan::GENERIC) return std::snprintf(buf, cap, "generic mt%d nt%d mode%d jc%d feat%d", t[0], t[1], t[2], t[3], t[4]);
+    if (k.family == ConvFp32Plan::LDS_TILE) return std::snprintf(buf, cap, "lds_tile blk%d wy%d wx%d nt%d mode%d", t[0], t[1], t[2], t[3], t[4]);
+    return std::snprintf(buf, cap, "lds_wave blk%d nt%d mode%d mt%d", t[0], t[1], t[2], t[3]);
+  };
+  if (q == nullptr) {
+    if (row < 0 || row >= fp32_table_rows) return -1;
+    key(fp32_table[row].key);
+    return 0;
+  }
+  const ConvFp32Plan p = conv_fp32_plan(*q);
+  if (!p) {
+    std::snprintf(buf, cap, "none");
+    return 0;
+  }
+  const int at = key(fp32_table[p.inst].key);
+  const char *const reduce[] = {"none", "plain", "head"};
+  if (at > 0 && (size_t)at < cap)
+    std::snprintf(buf + at, cap - at, " | grid %ux%ux%u block %d lds %zu wsplit %d ksplit %d scratch %zu reduce %s %u | tiles %dx%d groups %d items %ld ldsf %d slots %d wrows %d",
+                  p.grid_x, p.grid_y, p.grid_z, fp32_table[p.inst].threads, p.lds_bytes, p.wsplit, p.ksplit, p.scratch_floats, reduce[p.reduce],
+                  p.reduce_grid, p.tiles_x, p.tiles_y, p.ngroups, p.items, p.lds_floats, p.slots, p.wave_rows);
+  return 0;
+}
+
+hipError_t launch_conv_fp32(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s, const ConvFp32Head *head) {
+  if (p.inst < 0 || p.inst >= fp32_table_rows) return hipErrorInvalidValue;
+  if (p.ksplit <= 1) return fp32_table[p.inst].launch(a, p, s);
+  if (a.kpart == nullptr || (p.reduce == ConvFp32Plan::HEAD && (head == nullptr || head->out_dim < 1 || head->out_dim > 4))) return hipErrorInvalidValue;
+  ConvArgs raw = a;              // raw partials: bias and ReLU belong to the reduce
+  raw.bias = nullptr;
+  raw.bias_row = nullptr;
+  raw.relu_out = 0;
+  if (hipError_t e = fp32_table[p.inst].launch(raw, p, s)) return e;
+  const long P = (long)a.Ho * a.Wo, M = (long)a.B * P;
+  if (p.reduce == ConvFp32Plan::HEAD)
+    hipLaunchKernelGGL(ksplit_reduce_head_kernel, dim3(p.reduce_grid), dim3(256), 0, s, a.kpart, a.ksplit, M, a.y_cstride, a.bias, a.bias_row,
+                       a.relu_out, a.y, head->w, head->b, head->out_dim, head->out);
+  else
+    hipLaunchKernelGGL(ksplit_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, s, a.kpart, a.ksplit, M, a.y_cstride, a.bias, a.bias_row, a.COUT, P,
+                       a.relu_out, a.y);
+  return hipGetLastError();
 }
 
 // Packed layout consumed by the kernel: float4 index ((ntg*T + tap)*J + j)*64 + lane, lane = h*32 + n,

@@ -279,23 +279,13 @@ bool x3_two_pieces(pnvo_handle m, const Layer &l) {
     return m->opt.train_pieces == 2 && pnvo_train_x2_scale(m, l) != nullptr;
   return m->opt.pieces == 2;
 }
-// The implicit-GEMM geometry of layer l at B samples, the rest of the launch zero.
-void conv_geometry(const Layer &l, int B, int y_cstride, ConvArgs &a) {
-  std::memset(&a, 0, sizeof(a));
-  a.B = B;
-  a.H = l.hin;
-  a.W = l.win;
-  a.CIN = l.cinp;
-  a.Ho = l.hout;
-  a.Wo = l.wout;
-  a.COUT = l.cout;
-  a.COUTP = l.coutp;
-  a.KH = l.k;
-  a.KW = l.kw;
-  a.stride = l.stride;
-  a.pad = l.pad;
-  a.y_cstride = y_cstride;
-  a.up = 1;
+// Layer l at B samples as a problem of the float32-MFMA kernels under options o: the shape and the plan options — a plain conv with
+// a dense output and nothing else asked; the caller states the rest.
+ConvFp32Problem fp32_problem(pnvo_handle m, const PnvoOptions &o, const Layer &l, int B, int y_cstride) {
+  ConvFp32Problem q{.B = B, .H = l.hin, .W = l.win, .CIN = l.cinp, .Ho = l.hout, .Wo = l.wout, .COUT = l.cout, .COUTP = l.coutp, .KH = l.k,
+                    .KW = l.kw, .stride = l.stride, .pad = l.pad, .up = 1, .y_cstride = y_cstride};
+  q.opt = pnvo_fp32_opts(o, m->num_cus);
+  return q;
 }
 
 // launch timing of a conv of l at B samples: algorithmic flops and bytes
@@ -356,13 +346,14 @@ ConvChoice conv_choice(pnvo_handle m, const PnvoOptions &o, const Layer &l, int 
       return c;
     }
   }
-  // The float32-MFMA kernels: the LDS-staged 3x3 conv (input patch staged in LDS; slots = tiles x waves), else the generic implicit GEMM
-  ConvArgs a;
-  conv_geometry(l, B, l.coutp, a);
-  choose_tile((long)B * P, l.coutp, &c.MT, &c.NT);
-  const bool lds = dense_gn && o.conv != 3 && conv3_lds_supported(a);
-  c.family = lds ? ConvChoice::FP32_LDS : ConvChoice::FP32_GENERIC;
-  c.slots = lds ? conv3_lds_slots(a) : conv_slots(P, c.MT);
+  // The float32-MFMA kernels: an LDS-staged 3x3 conv (slots = tiles x waves) where the ask allows one, else the generic implicit GEMM.
+  // The problem is the layer's with the plain operand; conv_fp32_plan keeps family, wave tile and slots for the launch's real mode.
+  c.fp32q = fp32_problem(m, o, l, B, l.coutp);
+  c.fp32q.stats = ask.gn;
+  c.fp32q.lds_ok = dense_gn && o.conv != 3;
+  c.fp32p = conv_fp32_plan(c.fp32q);
+  c.family = c.fp32p.family == ConvFp32Plan::LDS_TILE || c.fp32p.family == ConvFp32Plan::LDS_WAVE ? ConvChoice::FP32_LDS : ConvChoice::FP32_GENERIC;
+  c.slots = c.fp32p.slots;
   return c;
 }
 }  // namespace
@@ -387,7 +378,10 @@ size_t stats_floats(pnvo_handle m, const Layer &l, int B) {
   PnvoOptions o = m->opt;
   int slots = 0;
   o.x3_s2 = 1;
-  for (o.conv = 1; o.conv <= 3; ++o.conv) slots = std::max(slots, conv_choice(m, o, l, B, {}).slots);   // x3 | fp32 | generic
+  o.fp32_tile = 0;                                                     // (one 32-pixel tile per wave: the most slots of the generic kernel)
+  for (o.conv = 1; o.conv <= 3; ++o.conv)                              // x3 | fp32 | generic
+    for (o.fp32_form = 1; o.fp32_form <= 2; ++o.fp32_form)             // the LDS-staged convs: tile | wave
+      slots = std::max(slots, conv_choice(m, o, l, B, {}).slots);
   return (size_t)B * (size_t)slots * l.coutp * 2;
 }
 
@@ -684,18 +678,28 @@ int run_conv_x3(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, cons
 // output tiles alone cannot fill the chip, and the output head may ride on that reduction.
 int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, const ConvChoice &c) {
   hipStream_t s = r.s;
-  ConvArgs a;
-  conv_geometry(l, B, r.y_cstride, a);
-  if (r.src != nullptr) {        // fused stem: gather A from the observation tensors
+  // the choice's problem with what the request adds: output stride, operand mode, epilogue, and what this handle can provide
+  ConvFp32Problem q = c.fp32q;
+  q.y_cstride = r.y_cstride;
+  q.mode = r.src != nullptr ? 2 : r.in_scale != nullptr ? 1 : 0;
+  q.linear = r.bias != nullptr || r.relu_out != 0;
+  q.stats = r.ss != nullptr;
+  q.ksplit_ok = r.bias != nullptr && !r.ss;          // linear layer: the reduction may be split (scratch: m->kpart, grown below)
+  q.head = r.head_out != nullptr ? m->cfg.out_dim : 0;
+  const ConvFp32Plan p = conv_fp32_plan(q);
+  if (!p) return fail(m, PNVO_ERR_STATE, "conv " + l.name + ": no float32-MFMA kernel is instantiated for this launch (check options fp32_tile, fp32_form)");
+  if (p.family != c.fp32p.family || (r.ss && p.slots != c.slots))
+    return fail(m, PNVO_ERR_STATE, "conv " + l.name + ": the launch's plan left the schedule's choice");
+  ConvArgs a = conv_fp32_args(q, p);
+  if (q.mode == 2) {             // fused stem: gather A from the observation tensors
     const int nsrc[4] = {m->cfg.n_rgb, m->cfg.n_depth, m->cfg.n_dd, m->cfg.n_tdv};
-    a.src_mode = 1;
     a.zero_page = m->zero_page;
     for (int j = 0; j < m->CP / 8; ++j)
       for (int hh = 0; hh < 2; ++hh)
-        for (int q = 0; q < 2; ++q) {
-          const int nc = 8 * j + 4 * hh + 2 * q;
+        for (int k = 0; k < 2; ++k) {
+          const int nc = 8 * j + 4 * hh + 2 * k;
           const int tn = m->stem_tensor_of_new[nc];
-          SrcPiece &pc = a.pieces[j][hh][q];
+          SrcPiece &pc = a.pieces[j][hh][k];
           pc.base = tn >= 0 ? r.src[tn] : nullptr;
           pc.nch = tn >= 0 ? nsrc[tn] : 0;
           pc.choff = m->stem_ch_of_new[nc];
@@ -710,43 +714,20 @@ int run_conv_fp32(pnvo_handle m, const Layer &l, int B, const ConvRequest &r, co
   a.bias = r.bias;
   a.bias_row = r.bias_row;
   a.relu_out = r.relu_out;
-  const long P = (long)l.hout * l.wout, M = (long)B * P;
-  a.MT = c.MT;
-  a.NT = c.NT;
-  a.slots = c.slots;
-  if (c.family == ConvChoice::FP32_LDS) {             // 3x3 stride-1 residual-stage conv: input patch staged in LDS
-    const int nt = (l.coutp / 32) % 2 == 0 ? 2 : 1;
-    {
-      Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
-      HIPCHK(m, launch_conv3_lds(a, nt, s));
+  if (p.scratch_floats > 0) {
+    if (p.scratch_floats > m->kpart.size()) {
+      pnvo_drop_graphs(m);                           // captured launches point into the old scratch
+      HIPCHK(m, m->kpart.alloc(p.scratch_floats));
     }
-    return finalize_gn(m, l, B, a.slots, 0, r.ss, r.mu, r.rstd, s);
-  }
-  if (r.bias != nullptr && !r.ss) {  // linear layer: split the reduction when the output tiles alone cannot fill the chip
-    a.kpart = reinterpret_cast<float *>(8);          // non-null: "scratch available" for the query
-    const int ks = conv_ksplit(a);
-    a.kpart = nullptr;
-    if (ks > 1) {
-      const size_t need = (size_t)ks * M * r.y_cstride;
-      if (need > m->kpart.size()) {
-        pnvo_drop_graphs(m);                         // captured launches point into the old scratch
-        HIPCHK(m, m->kpart.alloc(need));
-      }
-      a.kpart = m->kpart;
-      a.ksplit = ks;
-    }
+    a.kpart = m->kpart;
   }
   {
     Timed t(m, s, "conv:" + l.name, conv_flops(l, B), conv_bytes(l, B));
-    HIPCHK(m, launch_conv(a, s));
-    if (a.ksplit > 1 && r.head_out != nullptr && P == 1 && r.y_cstride == l.cout) {   // the output head on the reduction launch
-      HIPCHK(m, launch_ksplit_reduce_head(a, r.head_w, m->head_bias, m->cfg.out_dim, r.head_out, s));
-      if (r.head_rode != nullptr) *r.head_rode = true;
-    } else if (a.ksplit > 1) {
-      HIPCHK(m, launch_ksplit_reduce(a, s));
-    }
+    const ConvFp32Head head{.w = r.head_w, .b = m->head_bias, .out_dim = m->cfg.out_dim, .out = r.head_out};
+    HIPCHK(m, launch_conv_fp32(a, p, s, &head));     // ... with the split-K reduction, the output head on it where the plan says so
+    if (p.reduce == ConvFp32Plan::HEAD && r.head_rode != nullptr) *r.head_rode = true;
   }
-  return r.ss ? finalize_gn(m, l, B, a.slots, a.MT * 32, r.ss, r.mu, r.rstd, s) : PNVO_OK;
+  return r.ss ? finalize_gn(m, l, B, p.slots, p.wave_rows, r.ss, r.mu, r.rstd, s) : PNVO_OK;
 }
 
 // The grouped 3x3 conv of a ResNeXt block (conv_group.hip) + the GroupNorm finalisation that follows it.
@@ -1099,6 +1080,12 @@ const OptDef kOptions[] = {
     {"x3_w8", "PNVO_X3_W8", &PnvoOptions::x3_w8, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_m16", "PNVO_X3_M16", &PnvoOptions::x3_m16, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"x3_ksplit", "PNVO_X3_KSPLIT", &PnvoOptions::x3_ksplit, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
+    // the float32-MFMA kernels' plan options (ConvFp32Opts); the environment spells the wave split 1 / 0
+    {"fp32_tile", "PNVO_CONV_TILE", &PnvoOptions::fp32_tile, true, {{nullptr, 0}}},
+    {"fp32_wsplit", "PNVO_CONV_WSPLIT", &PnvoOptions::fp32_wsplit, false, {{"auto", -1}, {"on", 1}, {"off", 0}, {"1", 1}, {"0", 0}, {nullptr, 0}}},
+    {"fp32_form", "PNVO_CONV3", &PnvoOptions::fp32_form, false, {{"auto", 0}, {"tile", 1}, {"wave", 2}, {nullptr, 0}}},
+    {"wave_wgs", "PNVO_WAVE_WGS", &PnvoOptions::wave_wgs, true, {{nullptr, 0}}},
+    {"wave_nt", "PNVO_WAVE_NT", &PnvoOptions::wave_nt, true, {{nullptr, 0}}},
     {"fc_rows", "PNVO_FC_ROWS", &PnvoOptions::fc_rows, true, {{nullptr, 0}}},
     {"head_fuse", "PNVO_HEAD_FUSE", &PnvoOptions::head_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
     {"ds_fuse", "PNVO_DS_FUSE", &PnvoOptions::ds_fuse, false, {{"on", 1}, {"off", 0}, {nullptr, 0}}},
@@ -2527,6 +2514,24 @@ int pnvo_wgrad_describe(const int *problem, int n, char *buf, size_t cap) {
   if (q.pad < 0 || q.mode < 0 || q.mode > 2 || (q.np != 2 && q.np != 3) || (q.wgrad3 | 1) != 1 || q.wgrad < 0 || q.wgrad > 2)
     return fail(nullptr, PNVO_ERR_ARG, "mode is 0-2, np 2 or 3, wgrad3 0 or 1, wgrad 0-2");
   return wgrad_describe(&q, 0, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;
+}
+
+int pnvo_conv_fp32_describe(const int *problem, int n, char *buf, size_t cap) {
+  if (!buf || cap == 0) return fail(nullptr, PNVO_ERR_ARG, "bad argument");
+  if (problem == nullptr) return conv_fp32_describe(nullptr, n, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;   // (past the last row: no message)
+  if (n != 33) return fail(nullptr, PNVO_ERR_ARG, "a float32-MFMA conv problem has 33 fields");
+  const int *v = problem;
+  ConvFp32Problem q{.B = v[0], .H = v[1], .W = v[2], .CIN = v[3], .Ho = v[4], .Wo = v[5], .COUT = v[6], .COUTP = v[7], .KH = v[8], .KW = v[9],
+                    .stride = v[10], .pad = v[11], .up = v[12], .y_cstride = v[13], .mode = v[14], .accum = v[15] != 0, .y_sh = v[16], .y_sw = v[17],
+                    .y_oh = v[18], .y_ow = v[19], .y_H = v[20], .y_W = v[21], .linear = v[22] != 0, .stats = v[23] != 0, .ksplit_ok = v[24] != 0,
+                    .head = v[25], .lds_ok = v[26] != 0};
+  q.opt = {.tile = v[27], .wsplit = v[28], .form = v[29], .wave_wgs = v[30], .wave_nt = v[31], .num_cus = v[32]};
+  for (int k : {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13, 32})
+    if (v[k] <= 0) return fail(nullptr, PNVO_ERR_ARG, "a float32-MFMA conv problem's sizes are positive");
+  if (q.pad < 0 || (q.up != 1 && q.up != 2) || q.mode < 0 || q.mode > 2 || q.opt.wsplit < -1 || q.opt.wsplit > 1 || q.opt.form < 0 || q.opt.form > 2 ||
+      q.opt.tile < 0 || q.opt.wave_wgs < 0 || q.head < 0 || q.y_sh < 0 || q.y_sw < 0)
+    return fail(nullptr, PNVO_ERR_ARG, "pad >= 0, up 1 or 2, mode 0-2, fp32_wsplit -1..1, fp32_form 0-2, the rest non-negative");
+  return conv_fp32_describe(&q, 0, buf, cap) == 0 ? PNVO_OK : PNVO_ERR_ARG;
 }
 
 int pnvo_timing_mode(pnvo_handle h, int mode) {

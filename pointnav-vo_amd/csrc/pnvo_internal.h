@@ -32,15 +32,11 @@ struct ConvArgs {
   int relu_out;          // epilogue ReLU (after bias)
   int slots;             // stats slots per sample
   int lds_floats;        // dynamic LDS available for staging the input transform tables
-  int MT, NT;            // wave tile: MT*32 pixels x NT*32 output channels
-  int src_mode;          // 1: A is gathered from the observation tensors through `pieces` (x unused)
   int up;                // 2: transposed (backward-data of a stride-2 conv): source = (pos - pad + k) / 2 when even; else 1
   int accum;             // epilogue adds into y instead of overwriting it
   const float *zero_page;            // >= 16 B of zeros (target of masked gathers)
   int y_sh, y_sw, y_oh, y_ow, y_H, y_W;   // y_sh != 0: output pixel (n,i,j) is stored at (n, i*y_sh + y_oh, j*y_sw + y_ow) of a
                                           // [B, y_H, y_W, y_cstride] tensor (one parity phase of a stride-2 backward-data conv)
-  int wsplit;            // 1: the 4 waves of a workgroup share ONE 32-pixel tile and split its reduction (summed through LDS in
-                         // a fixed order): 4x finer work items for layers whose grid divides badly over the 256 CUs
   int ksplit;            // > 1: blockIdx.z owns a slice of the (tap, channel-group) stages and writes a raw partial
   float *kpart;          // [ksplit][M][y_cstride] partials (bias / ReLU / y are left to ksplit_reduce)
   SrcPiece pieces[8][2][2];          // [j][lane half h][q]: channels 8j+4h+2q, +1 of the stem's K order
@@ -295,12 +291,68 @@ hipError_t launch_residual_bf16(const unsigned short *const *a, const float *con
                                 const unsigned short *const *b, const float *const *sb, const float *const *tb, int B, long P,
                                 int C, unsigned short *const *y, int nmodels, hipStream_t s);
 
-int conv_slots(int P, int MT);                       // stats slots per sample for a given wave tile
-void choose_tile(long M, int COUTP, int *MT, int *NT);
-hipError_t launch_conv(const ConvArgs &a, hipStream_t s);
-// y = [relu](sum_z kpart[z] + bias[row]) for a split-K linear layer (a.ksplit > 1)
-hipError_t launch_ksplit_reduce(const ConvArgs &a, hipStream_t s);
-// ... with the output head (Linear COUT -> out_dim <= 4, plain [out_dim][COUT] weight + bias) computed on the reduced row: out [B][out_dim]
+// The float32-MFMA convs on the host, as conv_x3: a PROBLEM (shape, operand mode, epilogue, what the caller can provide, the handle's
+// options) -> conv_fp32_plan -> a PLAN (kernel family, the instance's row in the table of instantiated kernels, launch size, splits,
+// scratch, statistics slots) -> conv_fp32_args + launch_conv_fp32.  The families:
+//   GENERIC   conv_mfma_kernel<MT, NT, MODE, JC, FEAT> (conv_mfma.hip): any conv or Linear layer, A straight from L2
+//   LDS_TILE  conv3_lds_kernel<BLK, WY, WX, NT, XF> (conv3_lds.hip): 3x3 stride-1 pad-1 convs, a workgroup stages one patch
+//   LDS_WAVE  conv3_wave_kernel<BLK, NT, XF, MT> (conv3_lds.hip): the same convs, every wave stages its own patch
+struct ConvFp32Opts {
+  int tile;                 // option fp32_tile: 0 auto, 10*MT+NT forces that wave tile from 8192 output pixels on (where NT divides the N-tiles)
+  int wsplit;               // option fp32_wsplit: -1 auto, 0 off, 1 on (wherever the split is possible)
+  int form;                 // option fp32_form: 0 auto, 1 tile, 2 wave — which LDS-staged kernel
+  int wave_wgs;             // option wave_wgs: workgroups per CU of the wave kernel's persistent grid (0: as many as LDS allows)
+  int wave_nt;              // option wave_nt: 1 = one N-tile per wave item whatever the layer's N-tile count
+  int num_cus;
+};
+struct ConvFp32Problem {
+  int B, H, W, CIN, Ho, Wo, COUT, COUTP, KH, KW, stride, pad, up;
+  int y_cstride;            // channel stride of the output (COUT or COUTP)
+  int mode;                 // A operand: 0 as stored, 1 relu(x*scale+shift) of the producer's GroupNorm, 2 gathered from the observation tensors
+  bool accum;               // the epilogue adds into y
+  int y_sh, y_sw, y_oh, y_ow, y_H, y_W;   // y_sh != 0: strided output map (ConvArgs: a parity phase of a stride-2 backward-data conv)
+  bool linear;              // a Linear layer's epilogue: bias and / or ReLU
+  bool stats;               // GroupNorm partial sums wanted
+  bool ksplit_ok;           // the caller can provide split-K scratch (ConvFp32Plan::scratch_floats)
+  int head;                 // > 0: the caller offers an output head of this many units to ride on a split-K reduction
+  bool lds_ok;              // the caller allows the LDS-staged forms
+  ConvFp32Opts opt;
+};
+struct ConvFp32Plan {
+  enum Family { NONE, GENERIC, LDS_TILE, LDS_WAVE } family = NONE;
+  int inst = -1;            // row of the instance table
+  int MT = 0, NT = 0, MODE = 0, JC = 0, FEAT = 0;   // the instance's template arguments: GENERIC all five; LDS_TILE BLK, WY, WX, NT, MODE;
+  int BLK = 0, WY = 0, WX = 0;                      // LDS_WAVE BLK, NT, MODE, MT
+  unsigned grid_x = 0, grid_y = 1, grid_z = 1;
+  int block = 0;
+  size_t lds_bytes = 0;
+  int lds_floats = 0;       // GENERIC: LDS floats for the input-transform tables (ConvArgs::lds_floats)
+  int wsplit = 0;           // GENERIC: the four waves of a workgroup share one 32-pixel tile and split its reduction (FEAT 1)
+  int ksplit = 1;           // GENERIC: > 1: K slices over blockIdx.z, raw partials to scratch, reduced by a second launch
+  size_t scratch_floats = 0;
+  enum Reduce { NO_REDUCE, PLAIN, HEAD } reduce = NO_REDUCE;   // that launch: ksplit_reduce_kernel, or ksplit_reduce_head_kernel with the head riding
+  unsigned reduce_grid = 0;
+  int tiles_x = 0, tiles_y = 0, ngroups = 0;   // LDS forms: tiles (wave: pixel blocks) per sample, N-tile groups
+  long items = 0;           // work items: workgroups (GENERIC), (tile, N-tile group) items the persistent grid walks (LDS forms)
+  int slots = 0;            // statistics slots per sample
+  int wave_rows = 0;        // what launch_gn_finalize is given as WM: MT * 32 (GENERIC: slots follow the flattened wave tiles), 0 (LDS: fixed slots)
+  explicit operator bool() const { return family != NONE; }
+};
+struct ConvFp32Head {       // the output head riding on the split-K reduction: plain [out_dim][COUT] weight, bias, out [B][out_dim]
+  const float *w, *b;
+  int out_dim;
+  float *out;
+};
+ConvFp32Plan conv_fp32_plan(const ConvFp32Problem &q);                            // pure host code; NONE: no instantiated kernel serves q
+ConvArgs conv_fp32_args(const ConvFp32Problem &q, const ConvFp32Plan &p);         // geometry and the plan's fields, every operand zero
+int conv_fp32_describe(const ConvFp32Problem *q, int row, char *buf, size_t cap); // one line for q's plan, or (q == nullptr) for a table row
+// the launch, and behind a split-K launch its reduction y = [relu](sum_z kpart[z] + bias[row]) — with the head on it where the plan says so
+hipError_t launch_conv_fp32(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s, const ConvFp32Head *head = nullptr);
+// conv3_lds.hip's instances for the table, and the dynamic LDS of a tile / wave kernel of that shape
+template <int BLK, int WY, int WX, int NT, int XF> hipError_t conv3_tile_launch(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s);
+template <int BLK, int NT, int XF, int MT> hipError_t conv3_wave_launch(const ConvArgs &a, const ConvFp32Plan &p, hipStream_t s);
+size_t conv3_tile_lds_bytes(int blk, int wy, int wx);
+size_t conv3_wave_lds_bytes(int blk, int mt);
 // fc_rows.hip: the hidden layer (+ GroupNorm / ReLU of its input) and the output head for <= 32 samples, every action model of a grouped
 // forward in one launch each
 constexpr int FC_ROWS_MAXV = 12;          // 16-byte vectors of a weight row per lane: Kp <= 3072
@@ -313,14 +365,6 @@ struct FcRowsArgs {
   const float *w[3], *bias[3], *head_w[3], *head_b[3];   // per model: [hidden][Kp] rows in the activation's (h, w, padded c) order, bias rows, head
 };
 hipError_t launch_fc_rows(const FcRowsArgs &a, bool with_head, hipStream_t s);
-hipError_t launch_ksplit_reduce_head(const ConvArgs &a, const float *w2, const float *b2, int out_dim, float *out, hipStream_t s);
-int conv_ksplit(const ConvArgs &a);   // how many K slices launch_conv would use for `a` when a.kpart is set (1: none)
-
-// LDS-staged 3x3 stride-1 kernel (conv3_lds.hip): same arguments / packing / epilogue contract as launch_conv.
-bool conv3_lds_supported(const ConvArgs &a);
-int conv3_lds_slots(const ConvArgs &a);                       // statistics slots per sample (tiles x waves)
-hipError_t launch_conv3_lds(const ConvArgs &a, int nt, hipStream_t s);
-
 size_t packed_conv_floats(int cout, int cin, int kh, int kw);
 void pack_conv_weight(const float *oihw, int cout, int cin, int kh, int kw, float *out);
 

@@ -67,6 +67,11 @@ struct PnvoOptions {
   int x3_m16 = 1;      // MFMA-count-bound stride-1 convs (one-tile-per-sample 256-channel launches from 200 tiles on, 128-channel strips) on 16x16x32 MFMAs: M padded to 16 rows
   int x3_w8 = 1;       // 256-channel convs on 6 x 11 maps with a tile per CU or more: eight waves of (3,1) tiles per workgroup (two per SIMD) instead of four of (3,2)
   int x3_ksplit = 1;   // fine-plan conv tiles of three / four M-tiles behind >= 128 input channels: the four waves split the K walk, partial sums meet in LDS
+  int fp32_tile = 0;   // float32-MFMA generic kernel: 0 auto, 10*MT+NT forces that wave tile from 8192 output pixels on (experiment knob)
+  int fp32_wsplit = -1;  // ... its four waves share one tile and split the reduction: -1 auto, 1 wherever possible, 0 never
+  int fp32_form = 0;   // LDS-staged float32 3x3 convs: 0 auto (wave-private patches from 64 input channels on), 1 tile, 2 wave
+  int wave_wgs = 3;    // ... workgroups per CU of the wave kernel's persistent grid (0: as many as LDS allows)
+  int wave_nt = 1;     // ... 1: one N-tile per wave item; else two where the layer's N-tile count is even
   int fc_rows = 48;    // up to this many samples the hidden layer and the head run as fc_rows.hip's two launches (every model of a grouped forward in one)
   int head_fuse = 1;   // the output head (Linear hidden -> out_dim) is computed by the hidden layer's split-K reduction launch (one launch less)
   int ds_fuse = 1;     // the 1x1 stride-2 downsample conv rides on its block's first 3x3 conv (bit-identical raw output, one launch less, block input read once)
@@ -89,6 +94,11 @@ struct PnvoOptions {
   int small_coop = 1;  // cooperative launch (hipLaunchCooperativeKernel): every workgroup resident by the runtime's guarantee, also next to other
                        // processes' kernels (+17 us); 0: plain launch of <= 144 workgroups (one per CU) for a process that owns the GPU
 };
+
+// The plan options of the float32-MFMA kernels as options o state them (every ConvFp32Problem of a handle takes them from here).
+inline pnvo::ConvFp32Opts pnvo_fp32_opts(const PnvoOptions &o, int num_cus) {
+  return {.tile = o.fp32_tile, .wsplit = o.fp32_wsplit, .form = o.fp32_form, .wave_wgs = o.wave_wgs, .wave_nt = o.wave_nt, .num_cus = num_cus};
+}
 
 struct TimingRec {
   hipEvent_t a, b;
@@ -119,7 +129,7 @@ struct pnvo_model_s {
   std::vector<int> stem_ref_of_new;  // new channel -> reference channel (vo_cnn.py:169-174 order), -1 = pad
   std::vector<int> stem_tensor_of_new, stem_ch_of_new;
   DevBuf<float> stem_sc, stem_sh, zero_page; // whitening table in the new order
-  DevBuf<float> kpart;               // split-K partials of the linear layers (conv_mfma.hip conv_ksplit); only grows
+  DevBuf<float> kpart;               // split-K partials of the linear layers (ConvFp32Plan::scratch_floats); only grows
   DevBuf<float> stem_wpk16;          // stem weights packed for the LDS-staged 16x16x4 kernel
   int CPL = 0;                       // stem channels per pixel in LDS (C rounded up to 16)
   // one-hot-aware stem (stem_dd.hip): dense channels + indicator on the matrix cores, depth bins as a table gather
@@ -299,8 +309,9 @@ struct ConvChoice {
   enum Family { GROUP, X3, FP32_LDS, FP32_GENERIC } family = FP32_GENERIC;
   pnvo::ConvX3Problem x3q{};   // X3: the launch's problem and its plan
   pnvo::ConvX3Plan x3p;
+  pnvo::ConvFp32Problem fp32q{};   // FP32_*: the layer's problem as the ask states it, and its plan (family, wave tile and slots hold for
+  pnvo::ConvFp32Plan fp32p;        //   the launch whatever its operand mode: conv_fp32_plan)
   int slots = 0;               // statistics slots per sample the launch writes ([B][slots][coutp][2] in m->stats)
-  int MT = 0, NT = 0;          // FP32_*: choose_tile's wave tile
   double flops = 0.0;          // executed matrix-core FLOPs (X3: of the tile plan)
 };
 

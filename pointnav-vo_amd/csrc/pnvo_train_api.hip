@@ -589,65 +589,51 @@ int ensure_train_ws(pnvo_handle m, TrainState *t, int B) {
 
 // ---- backward launches -----------------------------------------------------------------------------------------------------
 
-// The backward-data conv of layer l: dX[B, hin, win, cin] (+)= conv(dRaw[B, hout, wout, coutp], wpk = flipped / transposed weights).
-// phase < 0: the full form (every tap, the forward's stride as upsampling).  phase = ph*2 + pw: the 1- or 2-tap dense stride-1 conv
-// that produces output parity (ph, pw) of a stride-2 3x3 conv (a.Ho or a.Wo may come out 0: nothing to launch).
-ConvArgs dgrad_conv_args(const Layer &l, int B, const float *draw, const float *wpk, float *dx, bool accum, int phase) {
+// The backward-data conv of layer l as a float32-MFMA problem: dX[B, hin, win, cin] (+)= conv(dRaw[B, hout, wout, coutp], flipped /
+// transposed weights).  phase < 0: the full form (every tap, the forward's stride as upsampling).  phase = ph*2 + pw: the 1- or 2-tap
+// dense stride-1 conv that produces output parity (ph, pw) of a stride-2 3x3 conv (Ho or Wo may come out 0: nothing to launch).
+// What is off: the gradient is read as stored (mode 0), nothing is normalised behind it (no statistics), there is no bias or ReLU, and
+// no split-K scratch is handed over.  The full form may take an LDS-staged kernel whatever option conv says — backward-data of a 3x3
+// stride-1 conv is a 3x3 stride-1 conv; a phase writes a strided map, which only the generic kernel has.
+ConvFp32Problem dgrad_problem(pnvo_handle m, const Layer &l, int B, bool accum, int phase) {
   const bool full = phase < 0;
   const int ph = full ? 0 : phase >> 1, pw = full ? 0 : phase & 1;
-  ConvArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.x = draw;
-  a.wpk = wpk;
-  a.y = dx;
-  a.B = B;
-  a.H = l.hout;
-  a.W = l.wout;
-  a.CIN = l.coutp;
-  a.Ho = full ? l.hin : (l.hin - ph + 1) / 2;
-  a.Wo = full ? l.win : (l.win - pw + 1) / 2;
-  a.COUT = l.cin;
-  a.COUTP = rup(l.cin, 32);
-  a.KH = full ? l.k : ph ? 2 : 1;
-  a.KW = full ? l.kw : pw ? 2 : 1;
-  a.stride = 1;
-  a.pad = full ? l.k - 1 - l.pad : 0;
-  a.up = full ? l.stride : 1;
-  a.accum = accum ? 1 : 0;
-  a.y_cstride = l.cin;
+  ConvFp32Problem q{.B = B, .H = l.hout, .W = l.wout, .CIN = l.coutp, .Ho = full ? l.hin : (l.hin - ph + 1) / 2, .Wo = full ? l.win : (l.win - pw + 1) / 2,
+                    .COUT = l.cin, .COUTP = rup(l.cin, 32), .KH = full ? l.k : ph ? 2 : 1, .KW = full ? l.kw : pw ? 2 : 1, .stride = 1,
+                    .pad = full ? l.k - 1 - l.pad : 0, .up = full ? l.stride : 1, .y_cstride = l.cin, .mode = 0, .accum = accum};
   if (!full) {
-    a.y_sh = a.y_sw = 2;
-    a.y_oh = ph;
-    a.y_ow = pw;
-    a.y_H = l.hin;
-    a.y_W = l.win;
+    q.y_sh = q.y_sw = 2;
+    q.y_oh = ph;
+    q.y_ow = pw;
+    q.y_H = l.hin;
+    q.y_W = l.win;
   }
-  if (a.Ho > 0 && a.Wo > 0) {
-    choose_tile((long)B * a.Ho * a.Wo, a.COUTP, &a.MT, &a.NT);
-    a.slots = conv_slots(a.Ho * a.Wo, a.MT);
-  }
-  return a;
+  q.linear = q.stats = q.ksplit_ok = false;
+  q.head = 0;
+  q.lds_ok = full;
+  q.opt = pnvo_fp32_opts(m->opt, m->num_cus);
+  return q;
 }
 
-// A transposed Linear as a 1x1 conv over B one-pixel samples: y[B, cout] = x[B, cin] . wpk
-ConvArgs linear_t_args(const float *x, const float *wpk, float *y, int B, int cin, int cout) {
-  ConvArgs d;
-  std::memset(&d, 0, sizeof(d));
-  d.x = x;
-  d.wpk = wpk;
-  d.y = y;
-  d.B = B;
-  d.H = d.W = d.Ho = d.Wo = 1;
-  d.CIN = cin;
-  d.COUT = cout;
-  d.COUTP = rup(cout, 32);
-  d.KH = d.KW = 1;
-  d.stride = 1;
-  d.up = 1;
-  d.y_cstride = cout;
-  choose_tile(B, d.COUTP, &d.MT, &d.NT);
-  d.slots = conv_slots(1, d.MT);
-  return d;
+// A transposed Linear as a 1x1 conv over B one-pixel samples, y[B, cout] = x[B, cin] . wpk: plain operand, no epilogue, no statistics,
+// no split-K scratch, nothing for an LDS-staged kernel to stage.
+ConvFp32Problem linear_t_problem(pnvo_handle m, int B, int cin, int cout) {
+  ConvFp32Problem q{.B = B, .H = 1, .W = 1, .CIN = cin, .Ho = 1, .Wo = 1, .COUT = cout, .COUTP = rup(cout, 32), .KH = 1, .KW = 1, .stride = 1, .pad = 0,
+                    .up = 1, .y_cstride = cout};
+  q.opt = pnvo_fp32_opts(m->opt, m->num_cus);
+  return q;
+}
+
+// Plan q and launch it on (x, wpk) -> y; a problem no instantiated kernel serves is an error named after `what`.
+int run_fp32(pnvo_handle m, const ConvFp32Problem &q, const float *x, const float *wpk, float *y, const std::string &what, hipStream_t s) {
+  const ConvFp32Plan p = conv_fp32_plan(q);
+  if (!p) return pnvo_fail(m, PNVO_ERR_STATE, what + ": no float32-MFMA kernel is instantiated for this launch (check options fp32_tile, fp32_form)");
+  ConvArgs a = conv_fp32_args(q, p);
+  a.x = x;
+  a.wpk = wpk;
+  a.y = y;
+  HIPCHK(m, launch_conv_fp32(a, p, s));
+  return PNVO_OK;
 }
 
 // The conv_x3 operand of conv li's backward-data conv in np pieces (2: float16 on the forward's per-tensor scale wsc, 3: bf16),
@@ -674,8 +660,9 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
   if (tl.dgrad_wph[0] != nullptr && m->opt.dgrad) {   // stride-2 3x3: four dense parity-phase convs instead of 9 taps, 3/4 masked
     PnvoTimed tm(m, s, tl.t_dgrad, flops, 0.0);
     for (int phase = 0; phase < 4; ++phase) {
-      const ConvArgs a = dgrad_conv_args(l, B, draw, tl.dgrad_wph[phase], dx, accum, phase);
-      if (a.Ho > 0 && a.Wo > 0) HIPCHK(m, launch_conv(a, s));
+      const ConvFp32Problem q = dgrad_problem(m, l, B, accum, phase);
+      if (q.Ho > 0 && q.Wo > 0)
+        if (int rc = run_fp32(m, q, draw, tl.dgrad_wph[phase], dx, "backward-data phase of " + l.name, s)) return rc;
     }
     return PNVO_OK;
   }
@@ -706,13 +693,8 @@ int run_dgrad(pnvo_handle m, TrainState *t, size_t li, int B, const float *draw,
       return PNVO_OK;
     }
   }
-  const ConvArgs a = dgrad_conv_args(l, B, draw, tl.dgrad_w, dx, accum, -1);
   PnvoTimed tm(m, s, tl.t_dgrad, flops, 0.0);
-  if (conv3_lds_supported(a))         // backward-data of a 3x3 stride-1 conv is a 3x3 stride-1 conv: LDS-staged kernel
-    HIPCHK(m, launch_conv3_lds(a, (a.COUTP / 32) % 2 == 0 ? 2 : 1, s));
-  else
-    HIPCHK(m, launch_conv(a, s));
-  return PNVO_OK;
+  return run_fp32(m, dgrad_problem(m, l, B, accum, -1), draw, tl.dgrad_w, dx, "backward-data of " + l.name, s);
 }
 
 int run_wgrad(pnvo_handle m, TrainState *t, WgradRequest &r, const Weight &w, const int *perm, int cin_out, hipStream_t s) {
@@ -982,8 +964,7 @@ static int backward_head(pnvo_handle m, TrainState *t, int B, const float *grad_
   HIPCHK(m, launch_colsum(grad_out, B, c.out_dim, c.out_dim, t->grads + t->head.b.off, s));
   WgradRequest a = wgrad_request(m, t, m->head, B, {.x = t->drop_p > 0.f ? w.hdrop : w.hid}, w.dout8);
   if (int rc = run_wgrad(m, t, a, t->head.w, nullptr, c.hidden, s)) return rc;
-  HIPCHK(m, launch_conv(linear_t_args(w.dout8, t->head_t, w.dh, B, 8, c.hidden), s));
-  return PNVO_OK;
+  return run_fp32(m, linear_t_problem(m, B, 8, c.hidden), w.dout8, t->head_t, w.dh, "transposed output head", s);
 }
 
 // hidden layer: hid = relu(z . W1^T + b1); dh -> dz (stop_after_fc: only the layer's own gradients)
@@ -1007,7 +988,7 @@ static int backward_hidden(pnvo_handle m, TrainState *t, int B, bool stop_after_
   }
   if (int rc = run_wgrad(m, t, a, t->fc.w, nullptr, m->comp_c, s)) return rc;
   if (stop_after_fc) return PNVO_OK;
-  HIPCHK(m, launch_conv(linear_t_args(w.gh, t->fc_t, w.dz, B, c.hidden, m->fh * m->fw * m->comp_cp), s));
+  if (int rc = run_fp32(m, linear_t_problem(m, B, c.hidden, m->fh * m->fw * m->comp_cp), w.gh, t->fc_t, w.dz, "transposed hidden layer", s)) return rc;
   if (drop)
     HIPCHK(m, launch_dropout(w.dz, nullptr, nullptr, B, (long)m->fh * m->fw, m->comp_cp, t->drop_p, t->drop_seed, t->drop_step, 0, w.dz, s));
   return PNVO_OK;

@@ -1,4 +1,6 @@
 # Sweep one experiment knob of libpnvo over bench.py and print the step time plus the kernels whose name matches a filter.
+# (The variables seed the handle's options in pnvo_create — fp32_tile, wave_wgs, wave_nt, ... — so one value per process is what is swept;
+#  tools/ab_option.py compares two values of an option in one process.)
 # Usage: bash tools/knob_sweep.sh <ENV_VAR> "<value> <value> ..." [kernel-name-substring]
 #   e.g. bash tools/knob_sweep.sh PNVO_CONV_TILE "0 11 12 21 22 14" layer4      (generic conv wave tile: 10*MT+NT)
 #        bash tools/knob_sweep.sh PNVO_WAVE_WGS "2 3 4" layer2                   (wave-private conv: workgroups per CU)
