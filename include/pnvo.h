@@ -796,6 +796,32 @@ int pnvo_nav_update(const float *deltas, int64_t delta_row_stride, const int32_t
 int pnvo_nav_reset(const double *goal_world, const double *start_delta, const double *start_rot, const double *start_pos,
                    const int32_t *env, int n, double *goal, double *rot, double *pos, float *polar, void *stream);
 
+/* ---- Evaluation bookkeeping of the same loop (ppo_trainer.py:742-805, 845-873, 1104-1128; geometry.py's NavEvalStats owns the
+ * tensors, NavEvalBook is the host form and the definition).  Per environment: steps int64 [E] (VO steps of the running episode),
+ * abs_sum float64 [E,3] (sum of |delta - gt|), std_sum float64 [E,3]; optionally traj float64 [E, max_steps, 16], one record
+ * (delta[3], gt[3], std[3], rot[4], pos[3]) per step holding the pose AFTER the step.  Run totals: episodes and steps_total int64
+ * [1], l2_sum / std_sum_total / diff_sum float64 [3].  Every sum is sequential — step order within an episode, row order of the
+ * call across episodes — so everything but sqrt / atan2 of the yaw diff (and the sin / cos of the pose) is bit-equal to the host
+ * form.  One launch each, no atomics, no LDS, no host wait. ---- */
+
+/* pnvo_nav_update with the book's step in front of it: for row i and e = env[i], in this order, abs_sum[e] += |double(delta_i) -
+ * gt_i|, std_sum[e] += double(std_i) (zeros when std is NULL), then goal / polar / rot / pos exactly as pnvo_nav_update (the same
+ * device functions: the tracker's state is bit for bit what that call writes), steps[e] += 1, and with traj the record of this
+ * step at traj[e, steps[e] before the step] (not written once that index reaches max_steps; the caller refuses such a step).
+ * gt: DEVICE float64 [n,3]; std: DEVICE float32 [n,3] or NULL, both contiguous.  rot and pos are required. */
+int pnvo_nav_update_eval(const float *deltas, int64_t delta_row_stride, const int32_t *env, int n, double *goal, double *rot,
+                         double *pos, float *polar, const double *gt, const float *std, int64_t *steps, double *abs_sum,
+                         double *std_sum, double *traj, int max_steps, void *stream);
+
+/* Episode end of rows env[i], BEFORE their pnvo_nav_reset: diff[i] = (|sim_x - vo_x|, |sim_z - vo_z|, angle between sim_rot[i] and
+ * rot[e]: dq = conj(sim) * vo, 2 atan2(sqrt((dq_x^2 + dq_y^2) + dq_z^2), |dq_w|)) when steps[e] >= 1, zeros otherwise; then, walking
+ * the rows in call order with one thread per component, l2_sum += abs_sum[e], std_sum_total += std_sum[e], diff_sum += diff[i],
+ * steps_total += steps[e], episodes += 1, and steps / abs_sum / std_sum of e are cleared.  One workgroup: the diff rows are spread
+ * over its threads, a barrier separates them from the walk.  sim_pos [n,3], sim_rot [n,4], diff [n,3]: DEVICE float64. */
+int pnvo_nav_episode_end(const int32_t *env, int n, const double *sim_pos, const double *sim_rot, const double *rot,
+                         const double *pos, int64_t *steps, double *abs_sum, double *std_sum, int64_t *episodes,
+                         int64_t *steps_total, double *l2_sum, double *std_sum_total, double *diff_sum, double *diff, void *stream);
+
 /* F.avg_pool2d(x, 2) of 1-channel NHWC frames [N,H,W,1] -> [N,H/2,W/2,2] with channel 1 = 0 (resnet_policy.py:168). */
 int pnvo_avgpool2(const float *depth, int N, int H, int W, float *out, void *stream);
 

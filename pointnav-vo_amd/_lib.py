@@ -172,6 +172,8 @@ _SIGNATURES = {
     "pnvo_rollout_gather_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     "pnvo_nav_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "pnvo_nav_reset": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5),
+    "pnvo_nav_update_eval": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]),
+    "pnvo_nav_episode_end": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 14),
     "pnvo_avgpool2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pnvo_layer_kernel": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]),
     "pnvo_conv_x3_describe": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_size_t]),

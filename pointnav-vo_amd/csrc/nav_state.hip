@@ -8,9 +8,11 @@
 //
 //   pnvo_nav_update   rows env[i] of goal / rot / pos / polar advance by float32 delta row i      ppo_trainer.py:843-871
 //   pnvo_nav_reset    rows env[i] start an episode: goal from the world goal and the start delta   ppo_trainer.py:727-740
+//   pnvo_nav_update_eval   the update, with the evaluation book's step in front: VO error, std, log  ppo_trainer.py:845-873
+//   pnvo_nav_episode_end   drift against the simulator's pose, run totals, the book's rows cleared   ppo_trainer.py:742-805
 //
-// One thread per row, no atomics, no LDS.  float64 in the operation order of pointnav_vo_amd.geometry (compute_goal_pos_batch,
-// _quat_rotate, _quat_mul).  This file is built with -ffp-contract=off: numpy rounds after every multiply and add (no a*b+c
+// One thread per row (the episode end: one workgroup, rows spread over it, then one thread per component), no atomics, no LDS.
+// float64 in the operation order of pointnav_vo_amd.geometry (compute_goal_pos_batch, _quat_rotate, _quat_mul).  This file is built with -ffp-contract=off: numpy rounds after every multiply and add (no a*b+c
 // fusion), so everything except sin, cos, hypot and atan2 is bit-equal to the host functions.  The literal `* 0.0` and `+ 0.0`
 // terms of those functions are kept: they decide the sign of a zero.
 #include <hip/hip_runtime.h>
@@ -104,6 +106,110 @@ __global__ __launch_bounds__(kThreads) void nav_reset_kernel(ResetArgs a) {
   }
 }
 
+// The evaluation book (geometry.NavEvalBook is the host form): per-environment sums of the running episode, run totals.
+struct EvalUpdateArgs {
+  UpdateArgs u;              // rot and pos are not null here
+  const double *gt;          // [n,3]
+  const float *std;          // [n,3] or null: zeros
+  int64_t *steps;            // [E]
+  double *abs_sum, *std_sum; // [E,3]
+  double *traj;              // [E, max_steps, 16] or null
+  int max_steps;
+};
+
+// NavEvalBook.step, then the two device functions of nav_update_kernel on the same values.
+__global__ __launch_bounds__(kThreads) void nav_update_eval_kernel(EvalUpdateArgs a) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= a.u.n) return;
+  const int64_t e = a.u.env ? (int64_t)a.u.env[i] : (int64_t)i;
+  if (e < 0) return;
+  const float *d = a.u.deltas + (int64_t)i * a.u.delta_row_stride;
+  const double dl[3] = {(double)d[0], (double)d[1], (double)d[2]};
+  const double *gt = a.gt + (int64_t)i * 3;
+  const double g3[3] = {gt[0], gt[1], gt[2]};
+  double sd[3] = {0.0, 0.0, 0.0};
+  if (a.std)
+    for (int k = 0; k < 3; ++k) sd[k] = (double)a.std[(int64_t)i * 3 + k];
+  for (int k = 0; k < 3; ++k) a.abs_sum[e * 3 + k] = a.abs_sum[e * 3 + k] + fabs(dl[k] - g3[k]);
+  for (int k = 0; k < 3; ++k) a.std_sum[e * 3 + k] = a.std_sum[e * 3 + k] + sd[k];
+  double *g = a.u.goal + e * 3;
+  const double prev[3] = {g[0], g[1], g[2]};
+  goal_step(prev, dl[0], dl[1], dl[2], g, a.u.polar + e * 2);
+  double *rot = a.u.rot + e * 4, *pos = a.u.pos + e * 3;
+  pose_step(dl[0], dl[1], dl[2], rot, pos);
+  const int64_t s = a.steps[e];
+  a.steps[e] = s + 1;
+  if (a.traj && s >= 0 && s < (int64_t)a.max_steps) {
+    double *r = a.traj + (e * (int64_t)a.max_steps + s) * 16;
+    for (int k = 0; k < 3; ++k) r[k] = dl[k], r[3 + k] = g3[k], r[6 + k] = sd[k];
+    for (int k = 0; k < 4; ++k) r[9 + k] = rot[k];
+    for (int k = 0; k < 3; ++k) r[13 + k] = pos[k];
+  }
+}
+
+struct EpisodeEndArgs {
+  const int32_t *env;
+  int n;
+  const double *sim_pos, *sim_rot;   // [n,3], [n,4]
+  const double *rot, *pos;           // the tracker's [E,4], [E,3]
+  int64_t *steps;
+  double *abs_sum, *std_sum;
+  int64_t *episodes, *steps_total;
+  double *l2_sum, *std_sum_total, *diff_sum;   // [3] each
+  double *diff;                      // [n,3]
+};
+
+// ONE workgroup.  First the diff rows, spread over the threads (geometry.angle_between_quaternions: dq = conj(sim) * vo through
+// _quat_mul, 2 atan2(|dq_xyz|, |dq_w|)); behind a barrier, which also makes the rows visible to the workgroup, thread k < 3 walks
+// the rows in call order for component k of the three totals and thread 3 for the two counts, each clearing what it has read.
+// The totals therefore do not depend on how the threads were scheduled.  Nothing after the barrier reads `steps` except thread 3.
+__global__ __launch_bounds__(kThreads) void nav_episode_end_kernel(EpisodeEndArgs a) {
+  const int tid = (int)threadIdx.x;
+  for (int i = tid; i < a.n; i += kThreads) {
+    const int64_t e = a.env ? (int64_t)a.env[i] : (int64_t)i;
+    double out[3] = {0.0, 0.0, 0.0};
+    if (e >= 0 && a.steps[e] >= 1) {
+      const double *sp = a.sim_pos + (int64_t)i * 3, *sr = a.sim_rot + (int64_t)i * 4;
+      const double *vp = a.pos + e * 3, *vr = a.rot + e * 4;
+      out[0] = fabs(sp[0] - vp[0]);
+      out[1] = fabs(sp[2] - vp[2]);
+      const double ax = -sr[0], ay = -sr[1], az = -sr[2], aw = sr[3];
+      const double bx = vr[0], by = vr[1], bz = vr[2], bw = vr[3];
+      const double qx = ((aw * bx + ax * bw) + ay * bz) - az * by;
+      const double qy = ((aw * by - ax * bz) + ay * bw) + az * bx;
+      const double qz = ((aw * bz + ax * by) - ay * bx) + az * bw;
+      const double qw = ((aw * bw - ax * bx) - ay * by) - az * bz;
+      const double nrm = sqrt((qx * qx + qy * qy) + qz * qz);
+      out[2] = 2.0 * atan2(nrm, fabs(qw));
+    }
+    for (int k = 0; k < 3; ++k) a.diff[(int64_t)i * 3 + k] = out[k];
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double l2 = a.l2_sum[tid], sd = a.std_sum_total[tid], df = a.diff_sum[tid];
+    for (int i = 0; i < a.n; ++i) {
+      const int64_t e = a.env ? (int64_t)a.env[i] : (int64_t)i;
+      if (e < 0) continue;
+      l2 = l2 + a.abs_sum[e * 3 + tid];
+      sd = sd + a.std_sum[e * 3 + tid];
+      df = df + a.diff[(int64_t)i * 3 + tid];
+      a.abs_sum[e * 3 + tid] = 0.0;
+      a.std_sum[e * 3 + tid] = 0.0;
+    }
+    a.l2_sum[tid] = l2, a.std_sum_total[tid] = sd, a.diff_sum[tid] = df;
+  } else if (tid == 3) {
+    int64_t total = *a.steps_total, episodes = *a.episodes;
+    for (int i = 0; i < a.n; ++i) {
+      const int64_t e = a.env ? (int64_t)a.env[i] : (int64_t)i;
+      if (e < 0) continue;
+      total += a.steps[e];
+      episodes += 1;
+      a.steps[e] = 0;
+    }
+    *a.steps_total = total, *a.episodes = episodes;
+  }
+}
+
 inline int bad(const char *fn, const char *what) { return pnvo_fail(nullptr, PNVO_ERR_ARG, std::string(fn) + ": " + what); }
 
 }  // namespace
@@ -135,6 +241,40 @@ int pnvo_nav_reset(const double *goal_world, const double *start_delta, const do
   a.goal_world = goal_world, a.start_delta = start_delta, a.start_rot = start_rot, a.start_pos = start_pos, a.env = env, a.n = n;
   a.goal = goal, a.rot = rot, a.pos = pos, a.polar = polar;
   hipLaunchKernelGGL(nav_reset_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, a);
+  HIPCHK(nullptr, hipGetLastError());
+  return PNVO_OK;
+}
+
+int pnvo_nav_update_eval(const float *deltas, int64_t delta_row_stride, const int32_t *env, int n, double *goal, double *rot,
+                         double *pos, float *polar, const double *gt, const float *std, int64_t *steps, double *abs_sum,
+                         double *std_sum, double *traj, int max_steps, void *stream) {
+  if (!deltas || !goal || !polar || !gt || !steps || !abs_sum || !std_sum) return bad("pnvo_nav_update_eval", "null pointer");
+  if (!rot || !pos) return bad("pnvo_nav_update_eval", "the evaluation book needs a tracked pose (rot and pos)");
+  if (n < 0) return bad("pnvo_nav_update_eval", "negative row count");
+  if (traj && max_steps < 1) return bad("pnvo_nav_update_eval", "a trajectory buffer needs max_steps >= 1");
+  if (n == 0) return PNVO_OK;
+  EvalUpdateArgs a;
+  a.u.deltas = deltas, a.u.delta_row_stride = delta_row_stride, a.u.env = env, a.u.n = n;
+  a.u.goal = goal, a.u.rot = rot, a.u.pos = pos, a.u.polar = polar;
+  a.gt = gt, a.std = std, a.steps = steps, a.abs_sum = abs_sum, a.std_sum = std_sum, a.traj = traj, a.max_steps = max_steps;
+  hipLaunchKernelGGL(nav_update_eval_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, a);
+  HIPCHK(nullptr, hipGetLastError());
+  return PNVO_OK;
+}
+
+int pnvo_nav_episode_end(const int32_t *env, int n, const double *sim_pos, const double *sim_rot, const double *rot,
+                         const double *pos, int64_t *steps, double *abs_sum, double *std_sum, int64_t *episodes,
+                         int64_t *steps_total, double *l2_sum, double *std_sum_total, double *diff_sum, double *diff, void *stream) {
+  if (!sim_pos || !sim_rot || !rot || !pos || !steps || !abs_sum || !std_sum || !episodes || !steps_total || !l2_sum ||
+      !std_sum_total || !diff_sum || !diff)
+    return bad("pnvo_nav_episode_end", "null pointer");
+  if (n < 0) return bad("pnvo_nav_episode_end", "negative row count");
+  if (n == 0) return PNVO_OK;
+  EpisodeEndArgs a;
+  a.env = env, a.n = n, a.sim_pos = sim_pos, a.sim_rot = sim_rot, a.rot = rot, a.pos = pos;
+  a.steps = steps, a.abs_sum = abs_sum, a.std_sum = std_sum, a.episodes = episodes, a.steps_total = steps_total;
+  a.l2_sum = l2_sum, a.std_sum_total = std_sum_total, a.diff_sum = diff_sum, a.diff = diff;
+  hipLaunchKernelGGL(nav_episode_end_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
   HIPCHK(nullptr, hipGetLastError());
   return PNVO_OK;
 }

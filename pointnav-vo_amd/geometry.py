@@ -81,6 +81,130 @@ def compute_goal_pos_batch(prev_goal_pos, local_delta_states):
     return {"cartesian": cur, "polar": np.stack([rho, -phi], axis=1).astype(np.float32)}
 
 
+def angle_between_quaternions(q1, q2):
+    """Angle of the rotation that takes q1 to q2, in [0, pi]: habitat's `angle_between_quaternions` as the evaluation uses it for the
+    yaw drift (ppo_trainer.py:772), restated from its published definition — dq = conj(q1) * q2, 2 atan2(|dq_xyz|, |dq_w|).  PARITY
+    UNPINNED (habitat is absent, see the header).  The norm is written out in this order; the device form follows it."""
+    q1 = np.asarray(q1, dtype=np.float64)
+    q2 = np.asarray(q2, dtype=np.float64)
+    dq = _quat_mul(np.array([-q1[0], -q1[1], -q1[2], q1[3]]), q2)
+    n = np.sqrt((dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2])
+    return 2 * np.arctan2(n, np.abs(dq[3]))
+
+
+TRAJ_RECORD = 16      # one logged step: delta[3], gt[3], std[3], rot[4], pos[3] (the pose AFTER the step), float64
+
+
+class NavEvalBook:
+    """The evaluation loop's VO bookkeeping on the host, in array form, one row per environment: the per-step VO error against the
+    simulator's delta and the prediction std (ppo_trainer.py:845-848), the pose integrated from the VO (:856-873), at every episode
+    end the drift of that pose against the simulator's (:742-805), and the three numbers the run reports (:1104-1128).
+
+    The reference appends to per-environment lists and reduces them with np.sum / np.mean; here every sum is kept running and is
+    SEQUENTIAL — step order within an episode, completion order (the row order of `end_episodes`) across episodes.  This order is
+    the definition of the arithmetic: `NavEvalStats` below reproduces it on the device bit for bit, except through sqrt / atan2 of
+    the yaw drift and the sin / cos inside the pose.  (np.sum over a handful of rows adds in the same order; over many rows it adds
+    pairwise, so the list form agrees to rounding, not to the bit: tests/test_nav_eval_host.py.)"""
+
+    def __init__(self, num_envs, max_episode_steps=500, keep_trajectories=False):
+        if int(num_envs) != num_envs or int(num_envs) < 1:
+            raise ValueError(f"num_envs must be a positive integer, got {num_envs!r}")
+        if int(max_episode_steps) != max_episode_steps or int(max_episode_steps) < 1:
+            raise ValueError(f"max_episode_steps must be a positive integer, got {max_episode_steps!r}")
+        E = self.num_envs = int(num_envs)
+        self.max_episode_steps = int(max_episode_steps)
+        self.keep_trajectories = bool(keep_trajectories)
+        self.rot = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (E, 1))
+        self.pos = np.zeros((E, 3))
+        self.steps = np.zeros(E, dtype=np.int64)
+        self.abs_sum = np.zeros((E, 3))
+        self.std_sum = np.zeros((E, 3))
+        self.traj = np.zeros((E, self.max_episode_steps, TRAJ_RECORD)) if self.keep_trajectories else None
+        self.episodes = 0
+        self.steps_total = 0
+        self.l2_sum = np.zeros(3)
+        self.std_sum_total = np.zeros(3)
+        self.diff_sum = np.zeros(3)
+
+    @staticmethod
+    def _rows(a, n, cols, what):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (n, cols):
+            raise ValueError(f"{what} must have shape ({n}, {cols}), got {a.shape}")
+        return a
+
+    def reset(self, env_indices, start_positions, start_rotations):
+        """Episode start: the pose from the VO becomes the start pose (:737-740)."""
+        idx = list(env_indices)
+        spos = self._rows(start_positions, len(idx), 3, "start_positions")
+        srot = self._rows(start_rotations, len(idx), 4, "start_rotations")
+        for i, e in enumerate(idx):
+            if self.steps[e] != 0 or self.abs_sum[e].any() or self.std_sum[e].any():
+                raise ValueError(f"environment {e} is inside an episode: end it before it starts the next one")
+            self.rot[e], self.pos[e] = srot[i], spos[i]
+
+    def step(self, env_indices, deltas, gt_deltas, stds=None):
+        """One VO step of the named environments: float32 deltas [n,3], the simulator's float64 deltas [n,3], stds [n,3] or None."""
+        idx = list(env_indices)
+        n = len(idx)
+        deltas = np.asarray(deltas)
+        if deltas.dtype != np.float32 or deltas.shape != (n, 3):
+            raise ValueError(f"deltas must be float32 ({n}, 3), got {deltas.dtype} {deltas.shape}")
+        d = deltas.astype(np.float64)                      # widened first, as the device form does
+        gt = self._rows(gt_deltas, n, 3, "gt_deltas")
+        sd = np.zeros((n, 3)) if stds is None else self._rows(stds, n, 3, "stds")
+        over = [e for e in idx if self.steps[e] >= self.max_episode_steps]
+        if over:                                           # refused before any row is touched, as the device form does
+            raise ValueError(f"environments {over} are already at max_episode_steps = {self.max_episode_steps}")
+        for i, e in enumerate(idx):
+            self.abs_sum[e] += np.abs(d[i] - gt[i])                                          # :845-847
+            self.std_sum[e] += sd[i]                                                         # :848
+            self.rot[e], self.pos[e] = compute_global_state((self.rot[e], self.pos[e]), d[i])   # :864-871
+            s = int(self.steps[e])
+            self.steps[e] = s + 1
+            if self.traj is not None:
+                self.traj[e, s] = np.concatenate([d[i], gt[i], sd[i], self.rot[e], self.pos[e]])
+
+    def end_episodes(self, env_indices, sim_positions, sim_rotations):
+        """Episode end of the named environments, rows in the order given (:742-805) -> the diff rows [n,3] (|dx|, |dz|, yaw angle
+        between the simulator's pose and the one from the VO); with keep_trajectories (diff rows, [one [steps,16] array per row])."""
+        idx = list(env_indices)
+        n = len(idx)
+        spos = self._rows(sim_positions, n, 3, "sim_positions")
+        srot = self._rows(sim_rotations, n, 4, "sim_rotations")
+        diff = np.zeros((n, 3))
+        logs = []
+        for i, e in enumerate(idx):
+            s = int(self.steps[e])
+            if s >= 1:                                                                       # :744-783
+                diff[i] = [abs(spos[i, 0] - self.pos[e, 0]), abs(spos[i, 2] - self.pos[e, 2]),
+                           angle_between_quaternions(srot[i], self.rot[e])]
+            self.steps_total += s                          # (an episode of zero steps adds (0, zeros) and a zero row, :789-805)
+            self.l2_sum += self.abs_sum[e]
+            self.std_sum_total += self.std_sum[e]
+            self.diff_sum += diff[i]
+            self.episodes += 1
+            if self.traj is not None:
+                logs.append(self.traj[e, :s].copy())
+            self.steps[e] = 0
+            self.abs_sum[e] = 0.0
+            self.std_sum[e] = 0.0
+        return (diff, logs) if self.traj is not None else diff
+
+    def result(self):
+        """The run's numbers (:1104-1128; `vo_l2_gloabl_state` is the reference's spelling of its key), the counts and the raw sums."""
+        return _eval_result(self.episodes, self.steps_total, self.l2_sum, self.std_sum_total, self.diff_sum)
+
+
+def _eval_result(episodes, steps_total, l2_sum, std_sum, diff_sum):
+    episodes, steps_total = int(episodes), int(steps_total)
+    l2_sum, std_sum, diff_sum = (np.array(a, dtype=np.float64) for a in (l2_sum, std_sum, diff_sum))
+    with np.errstate(invalid="ignore", divide="ignore"):   # (a run without a step or an episode: nan, as the reference's 0 / 0)
+        return {"vo_l2_loss": l2_sum / np.float64(steps_total), "vo_pred_std": std_sum / np.float64(steps_total),
+                "vo_l2_gloabl_state": diff_sum / np.float64(episodes), "episodes": episodes, "steps": steps_total,
+                "l2_sum": l2_sum, "std_sum": std_sum, "diff_sum": diff_sum}
+
+
 class GoalTracker:
     """Goal, pose and polar goal of `num_envs` environments as device tensors, advanced by the VO deltas without a host round trip
     (the device form of the bookkeeping of rl/ppo/ppo_trainer.py:727-740, 856-878):
@@ -200,11 +324,8 @@ class GoalTracker:
                                                self._ptr(self.rot), self._ptr(self.pos), self._ptr(self.polar),
                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
-    def update(self, deltas, env_indices=None):
-        """One simulator step: row i of `deltas` — a CUDA float32 [n,3] tensor of (dx, dz, dyaw), any row stride, e.g. what
-        `compute_local_delta_states_batch(..., to_host=False)` returns — advances environment env_indices[i] (all `num_envs`
-        environments in order when env_indices is None).  Environments not named keep every byte of their state.  One launch on the
-        current stream, no host wait; the index tensor of a repeated env_indices tuple is cached."""
+    def _check_deltas(self, deltas, env_indices):
+        """Shape and dtype of an update's deltas and its indices -> (row count, index tuple or None for all environments)."""
         import torch
         if not isinstance(deltas, torch.Tensor):
             raise ValueError(f"deltas must be a CUDA float32 tensor [n,3], got {type(deltas).__name__}")
@@ -214,9 +335,16 @@ class GoalTracker:
         if env_indices is None:
             if n != self.num_envs:
                 raise ValueError(f"{n} delta rows for {self.num_envs} environments: pass env_indices to update a subset")
-            idx = None
-        else:
-            idx = self._check_indices(env_indices, n)
+            return n, None
+        return n, self._check_indices(env_indices, n)
+
+    def update(self, deltas, env_indices=None):
+        """One simulator step: row i of `deltas` — a CUDA float32 [n,3] tensor of (dx, dz, dyaw), any row stride, e.g. what
+        `compute_local_delta_states_batch(..., to_host=False)` returns — advances environment env_indices[i] (all `num_envs`
+        environments in order when env_indices is None).  Environments not named keep every byte of their state.  One launch on the
+        current stream, no host wait; the index tensor of a repeated env_indices tuple is cached."""
+        import torch
+        n, idx = self._check_deltas(deltas, env_indices)
         if not deltas.is_cuda:
             raise ValueError("deltas must be a CUDA tensor (the host form of this update is compute_goal_pos_batch)")
         self._need_gpu()
@@ -244,3 +372,162 @@ class GoalTracker:
         if not self.track_pose:
             raise RuntimeError("this GoalTracker was built with track_pose=False")
         return self.rot.cpu().numpy(), self.pos.cpu().numpy()
+
+
+class EpisodeLog:
+    """One ended episode of a `NavEvalStats(keep_trajectories=True)`: the environment, its step count (known on the host), and — copied
+    asynchronously into pinned memory — its records float64 [steps,16] (delta[3], gt[3], std[3], rot[4], pos[3] after each step) and
+    its diff row [3].  Reading `records` or `diff` waits for the copies' event; nothing else does."""
+
+    def __init__(self, env, steps, records, diff, event):
+        self.env, self.steps = env, steps
+        self._records, self._diff, self._event = records, diff, event
+
+    def _wait(self):
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+
+    @property
+    def records(self):
+        self._wait()
+        return self._records.numpy()
+
+    @property
+    def diff(self):
+        self._wait()
+        return self._diff.numpy()
+
+
+class NavEvalStats:
+    """`NavEvalBook` on the device, around a `GoalTracker(track_pose=True)` whose pose IS the book's pose (csrc/nav_state.hip:
+    pnvo_nav_update_eval / pnvo_nav_episode_end).  In the evaluation loop `update` takes the place of `tracker.update`, and
+    `end_episodes` runs BEFORE `tracker.reset` of the same environments (stream order then lets it read the pose the episode ended
+    with).  Both are one launch on the current stream and never wait for the device; `result()` waits once.
+
+      steps    int64   [E]     VO steps of the running episode        abs_sum, std_sum  float64 [E,3]  its sums
+      traj     float64 [E, max_episode_steps, 16]  (keep_trajectories) the running episode's records
+      counts   int64   [2]     episodes, steps of the run             totals  float64 [3,3]  l2_sum, std_sum, diff_sum
+
+    The host keeps a step counter of its own per environment (nothing is read back for it): it refuses a step beyond
+    `max_episode_steps` before anything is launched and sizes the trajectory copies."""
+
+    def __init__(self, tracker, max_episode_steps=500, keep_trajectories=False):
+        import torch
+        if not isinstance(tracker, GoalTracker) or not tracker.track_pose:
+            raise ValueError("NavEvalStats needs a GoalTracker built with track_pose=True: the drift is measured on its pose")
+        if int(max_episode_steps) != max_episode_steps or int(max_episode_steps) < 1:
+            raise ValueError(f"max_episode_steps must be a positive integer, got {max_episode_steps!r}")
+        self.tracker = tracker
+        self.max_episode_steps = int(max_episode_steps)
+        self.keep_trajectories = bool(keep_trajectories)
+        E, dev = tracker.num_envs, tracker.device
+        self.steps = torch.zeros(E, dtype=torch.int64, device=dev)
+        self.abs_sum = torch.zeros((E, 3), dtype=torch.float64, device=dev)
+        self.std_sum = torch.zeros((E, 3), dtype=torch.float64, device=dev)
+        self.traj = (torch.zeros((E, self.max_episode_steps, TRAJ_RECORD), dtype=torch.float64, device=dev)
+                     if self.keep_trajectories else None)
+        self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.totals = torch.zeros((3, 3), dtype=torch.float64, device=dev)
+        self._host_steps = np.zeros(E, dtype=np.int64)
+
+    @staticmethod
+    def _host_rows(a, n, cols, what):
+        try:
+            a = np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a numeric array of shape ({n}, {cols})") from None
+        if a.shape != (n, cols):
+            raise ValueError(f"{what} must have shape ({n}, {cols}), got {a.shape}")
+        return a
+
+    def update(self, deltas, gt_deltas, env_indices=None, stds=None):
+        """`tracker.update(deltas, env_indices)` plus the book's step: gt_deltas is the simulator's float64 [n,3] (a host array: one
+        pinned non-blocking upload), stds an optional CUDA float32 [n,3] tensor (zeros when None)."""
+        import torch
+        tr = self.tracker
+        n, idx = tr._check_deltas(deltas, env_indices)
+        gt = self._host_rows(gt_deltas, n, 3, "gt_deltas")
+        if stds is not None:
+            if not isinstance(stds, torch.Tensor) or stds.dtype != torch.float32 or tuple(stds.shape) != (n, 3):
+                raise ValueError(f"stds must be a CUDA float32 tensor [{n},3] or None")
+        rows = np.arange(n) if idx is None else np.asarray(idx, dtype=np.int64)
+        over = rows[self._host_steps[rows] >= self.max_episode_steps]
+        if over.size:
+            raise ValueError(f"environments {over.tolist()} are already at max_episode_steps = {self.max_episode_steps}: "
+                             "end their episodes first")
+        if not deltas.is_cuda or (stds is not None and not stds.is_cuda):
+            raise ValueError("deltas and stds must be CUDA tensors (the host form of this update is NavEvalBook.step)")
+        tr._need_gpu()
+        if deltas.device != tr.device or (stds is not None and stds.device != tr.device):
+            raise ValueError(f"deltas / stds are not on the tracker's device {tr.device}")
+        if n == 0:
+            return
+        if deltas.stride(1) != 1:
+            deltas = deltas.contiguous()
+        if stds is not None:
+            stds = stds.contiguous()
+        dev, p = tr.device, tr._ptr
+        from . import _lib
+        with torch.cuda.device(dev):
+            env = tr._device_indices(idx) if idx is not None else None
+            h = torch.empty((n, 3), dtype=torch.float64, pin_memory=True)
+            h.numpy()[:] = gt
+            g = h.to(dev, non_blocking=True)
+            _lib.check(_lib.lib.pnvo_nav_update_eval(p(deltas), int(deltas.stride(0)) if n > 1 else 3, p(env), n, p(tr.goal), p(tr.rot),
+                                                     p(tr.pos), p(tr.polar), p(g), p(stds), p(self.steps), p(self.abs_sum),
+                                                     p(self.std_sum), p(self.traj), self.max_episode_steps,
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._host_steps[rows] += 1                       # (only once the launch is enqueued: the counter mirrors the device's)
+
+    def end_episodes(self, env_indices, sim_positions, sim_rotations):
+        """Episode end of the named environments, in the order given, against the simulator's final pose (host arrays [n,3] and
+        [n,4] as [x,y,z,w]) -> the diff rows as a device tensor float64 [n,3] (reading it waits, returning it does not); with
+        keep_trajectories (that tensor, [one `EpisodeLog` per row])."""
+        import torch
+        tr = self.tracker
+        idx = tr._check_indices(env_indices)
+        n = len(idx)
+        spos = self._host_rows(sim_positions, n, 3, "sim_positions")
+        srot = self._host_rows(sim_rotations, n, 4, "sim_rotations")
+        tr._need_gpu()
+        if n == 0:
+            diff = torch.empty((0, 3), dtype=torch.float64, device=tr.device)
+            return (diff, []) if self.keep_trajectories else diff
+        dev, p = tr.device, tr._ptr
+        from . import _lib
+        with torch.cuda.device(dev):
+            env = tr._device_indices(idx)
+            h = torch.empty(n * 7, dtype=torch.float64, pin_memory=True)
+            h.numpy()[:3 * n].reshape(n, 3)[:] = spos
+            h.numpy()[3 * n:].reshape(n, 4)[:] = srot
+            d = h.to(dev, non_blocking=True)
+            diff = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib.pnvo_nav_episode_end(p(env), n, p(d), C.c_void_p(d.data_ptr() + 8 * 3 * n), p(tr.rot), p(tr.pos),
+                                                     p(self.steps), p(self.abs_sum), p(self.std_sum), p(self.counts),
+                                                     C.c_void_p(self.counts.data_ptr() + 8), p(self.totals),
+                                                     C.c_void_p(self.totals.data_ptr() + 24), C.c_void_p(self.totals.data_ptr() + 48),
+                                                     p(diff), C.c_void_p(stream.cuda_stream)))
+            ended = self._host_steps[list(idx)].copy()
+            self._host_steps[list(idx)] = 0
+            if not self.keep_trajectories:
+                return diff
+            hdiff = torch.empty((n, 3), dtype=torch.float64, pin_memory=True)
+            hdiff.copy_(diff, non_blocking=True)
+            recs = []
+            for e, s in zip(idx, ended):                  # (the next update of e overwrites these rows only behind the copies)
+                r = torch.empty((int(s), TRAJ_RECORD), dtype=torch.float64, pin_memory=True)
+                if s:
+                    r.copy_(self.traj[e, :int(s)], non_blocking=True)
+                recs.append(r)
+            event = torch.cuda.Event()
+            event.record(stream)
+            return diff, [EpisodeLog(e, int(s), r, hdiff[i], event) for i, (e, s, r) in enumerate(zip(idx, ended, recs))]
+
+    def result(self):
+        """The same dict as `NavEvalBook.result()`; one synchronising copy."""
+        import torch
+        self.tracker._need_gpu()
+        flat = torch.cat([self.counts.to(torch.float64), self.totals.reshape(-1)]).cpu().numpy()   # (counts < 2^53: exact)
+        return _eval_result(int(flat[0]), int(flat[1]), flat[2:5], flat[5:8], flat[8:11])

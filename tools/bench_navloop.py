@@ -10,16 +10,24 @@ simulator step and for E parallel environments of one process:
 Everything the reference does on the trainer process between two simulator steps, with host numpy observations as the
 simulator delivers them (uint8 rgb + float32 depth, PCIe copies included).  Reports env-steps/s and the eval wall-clock this
 implies for the GPU part of 994 episodes (the reference's full run took 4.5 h including simulation).
-    python tools/bench_navloop.py [--envs 8 32] [--steps 30] [--device-goal]
+    python tools/bench_navloop.py [--envs 8 32] [--steps 30] [--device-goal | --eval-stats]
 
 --device-goal keeps the goal on the device: the VO call returns its deltas as a device tensor (to_host=False), geometry.GoalTracker
 advances the goal from them in one launch, and the policy reads tracker.polar — the only device-to-host copy left in a loop step is
-the actions.  Without the flag the loop is the host form above."""
+the actions.  Without the flag the loop is the host form above.
+
+--eval-stats times what the evaluation's VO statistics (VO error, prediction std, pose drift: ppo_trainer.py:742-805, 845-873) cost on
+that loop, three forms in one process, alternated --rounds times per environment count:
+    device        the --device-goal loop as it is
+    device+stats  the same with geometry.NavEvalStats.update in place of tracker.update (synthetic ground-truth deltas), and every
+                  --end-every steps a quarter of the environments ending an episode (end_episodes, then tracker.reset)
+    host+book     what device+stats replaces: deltas to the host (to_host=True), host goal update, geometry.NavEvalBook"""
 import argparse
 import json
 import os
 import sys
 import time
+import types
 
 import numpy as np
 import torch
@@ -52,15 +60,18 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--episode-steps", type=float, default=150.0, help="mean steps per episode used for the extrapolation")
     ap.add_argument("--device-goal", action="store_true", help="goal update on the device (GoalTracker), deltas never reach the host")
+    ap.add_argument("--eval-stats", action="store_true", help="device / device+stats / host+book, alternated in one process")
+    ap.add_argument("--rounds", type=int, default=4, help="--eval-stats: timed runs of each form per environment count")
+    ap.add_argument("--end-every", type=int, default=25, help="--eval-stats: loop steps between two episode-end calls")
     a = ap.parse_args()
+    if a.eval_stats:
+        print(json.dumps(run_eval_stats(a.envs, a.steps, a.rounds, a.end_every, torch.device("cuda", 0))))
+        return
     print(json.dumps(run(a.envs, a.steps, a.episode_steps, torch.device("cuda", 0), device_goal=a.device_goal)))
 
 
-def run(envs, steps, episode_steps=150.0, dev=None, device_goal=False):
-    """-> the result record (also what bench.py reports under secondary["navloop_gpu_side"])."""
-    import types
-    a = types.SimpleNamespace(envs=envs, steps=steps, episode_steps=episode_steps)
-    dev = dev if dev is not None else torch.device("cuda", 0)
+def setup(dev):
+    """-> (trainer with its VO models, policy, the synthetic frames), built once per process."""
     cfg = AttrDict(
         VO=dict(VO_TYPE="REGRESS", OBS_TRANSFORM="none", VIS_SIZE_W=W, VIS_SIZE_H=H,
                 REGRESS_MODEL=dict(name="vo_cnn_rgb_d_dd_top_down", visual_backbone="resnet18", hidden_size=512,
@@ -81,77 +92,141 @@ def run(envs, steps, episode_steps=150.0, dev=None, device_goal=False):
     pol.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in psd.items()})
     pol = pol.to(dev).eval()
     frames = [synth.make_raw_obs(H, W, seed=5, index=i) for i in range(96)]
+    return t, pol, frames
+
+
+def time_loop(world, dev, E, steps, form, end_every=25):
+    """Seconds per loop step of E environments over `steps` timed steps (12 warm-up steps first).  form: "host" | "device" |
+    "device+stats" | "host+book" (the module docstring)."""
+    t, pol, frames = world
+    a = types.SimpleNamespace(steps=steps)
+    device_goal = form in ("device", "device+stats")
+    goals = [np.array([0.0, 0.0, -5.0]) for _ in range(E)]           # goal in the agent frame (x, y, z)
+    tracker = None
+    start_pos, start_rot = np.zeros((E, 3)), np.tile([0.0, 0.0, 0.0, 1.0], (E, 1))
+    if device_goal:                     # the same start: agents at the origin, looking down -z (the pose is logged by the stats only)
+        tracker = geometry.GoalTracker(E, dev, track_pose=form == "device+stats")
+        tracker.reset(range(E), np.stack(goals), start_pos, start_rot)
+    # the evaluation's VO statistics: on the device around the tracker, or on the host from the deltas the host form fetches anyway
+    stats = geometry.NavEvalStats(tracker) if form == "device+stats" else None
+    book = geometry.NavEvalBook(E) if form == "host+book" else None
+    if book is not None:
+        book.reset(range(E), start_pos, start_rot)
+    gt = np.random.default_rng(E).normal(0.0, 0.1, size=(E, 3))      # synthetic ground-truth deltas (the simulator's, in the reference)
+    quarter = max(1, E // 4)
+
+    def end_some(s):
+        """Every end_every steps a quarter of the environments (rotating) end their episodes and start the next ones."""
+        if (stats is None and book is None) or (s + 1) % end_every:
+            return
+        first = ((s + 1) // end_every * quarter) % E
+        rows = [(first + i) % E for i in range(quarter)]
+        if stats is not None:
+            stats.end_episodes(rows, start_pos[:quarter], start_rot[:quarter])
+            tracker.reset(rows, np.stack(goals)[:quarter], start_pos[:quarter], start_rot[:quarter])
+        else:
+            book.end_episodes(rows, start_pos[:quarter], start_rot[:quarter])
+            book.reset(rows, start_pos[:quarter], start_rot[:quarter])
+
+    hid = torch.zeros(pol.num_recurrent_layers, E, 512, device=dev)
+    prev_a = torch.zeros(E, 1, dtype=torch.long, device=dev)
+    masks = torch.ones(E, 1, device=dev)
+    prev_obs = [frames[e % 96] for e in range(E)]
+    env_ids = list(range(E)) if os.environ.get("PNVO_NAVLOOP_RING", "1") != "0" else None
+    ring_depth = os.environ.get("PNVO_NAVLOOP_RING_DEPTH", "1") != "0"
+
+    phases = os.environ.get("PNVO_NAVLOOP_PHASES") is not None      # developer: host-synchronised time of each part (slower loop)
+    ph = {"policy input (stack + H2D)": 0.0, "policy.act": 0.0, "actions to host": 0.0, "VO boundary call": 0.0, "goal update": 0.0}
+
+    def mark(name, t_prev):
+        if not phases:
+            return t_prev
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        ph[name] += now - t_prev
+        return now
+
+    def step(s):
+        nonlocal hid, prev_a, prev_obs
+        tp = time.perf_counter()
+        if env_ids is not None and ring_depth:       # the policy's depth = the frames the last VO call left in the device ring
+            depth = t.ring_depth(prev_obs, env_ids)
+        else:
+            depth = torch.from_numpy(np.stack([o["depth"] for o in prev_obs])).to(dev, non_blocking=True)
+        if tracker is not None:
+            obs = {"depth": depth, "pointgoal_with_gps_compass": tracker.polar}
+        else:
+            polar = geometry.compute_goal_pos_batch(np.stack(goals), np.zeros((E, 3)))["polar"]
+            obs = {"depth": depth, "pointgoal_with_gps_compass": torch.from_numpy(polar).to(dev)}
+        tp = mark("policy input (stack + H2D)", tp)
+        _, act, _, hid = pol.act(obs, hid, prev_a, masks, deterministic=False)
+        tp = mark("policy.act", tp)
+        acts = (act.view(-1).cpu().numpy() % 3 + 1).tolist()          # STOP never ends a synthetic episode here
+        tp = mark("actions to host", tp)
+        cur_obs = [frames[(e + s + 1) % 96] for e in range(E)]
+        deltas = t.compute_local_delta_states_batch(prev_obs, cur_obs, acts, env_ids=env_ids,   # prev_obs IS last step's cur_obs: frame ring
+                                                    to_host=tracker is None)
+        tp = mark("VO boundary call", tp)
+        if stats is not None:
+            stats.update(deltas, gt)
+        elif tracker is not None:
+            tracker.update(deltas)
+        else:
+            goals[:] = list(geometry.compute_goal_pos_batch(np.stack(goals), deltas)["cartesian"])
+            if book is not None:
+                book.step(range(E), np.asarray(deltas, dtype=np.float32), gt)
+        end_some(s)
+        prev_a = torch.as_tensor(acts, device=dev).view(E, 1)
+        prev_obs = cur_obs
+        mark("goal update", tp)
+
+    for s in range(12):                 # (every action model, the policy and their small-batch kernels have run before the clock starts)
+        step(s)
+    end_some(end_every - 1)             # (and one episode-end call of the forms that have one)
+    torch.cuda.synchronize()
+    for k in ph:
+        ph[k] = 0.0
+    t0 = time.perf_counter()
+    for s in range(a.steps):
+        step(s)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / a.steps
+    t.check_deferred()
+    if phases:
+        print(f"[navloop] {E} envs, ms per loop step by phase (host-synchronised):",
+              {k: round(1e3 * v / a.steps, 3) for k, v in ph.items()}, file=sys.stderr)
+    if stats is not None:
+        stats.result()
+    return dt
+
+
+def run_eval_stats(envs, steps, rounds, end_every, dev=None):
+    """-> the record of --eval-stats: ms per loop step of the three forms, every round's value in the order they ran."""
+    dev = dev if dev is not None else torch.device("cuda", 0)
+    world = setup(dev)
+    forms = ("device", "device+stats", "host+book")
+    res = {"metric": "nav-loop ms per loop step with the evaluation's VO statistics (simulator excluded)", "frame": f"{W}x{H}",
+           "dtype": "f32", "steps": steps, "rounds": rounds, "end_every": end_every, "results": []}
+    for E in envs:
+        ms = {f: [] for f in forms}
+        for _ in range(rounds):
+            for f in forms:                                          # alternated: a, b, c, a, b, c, ...
+                ms[f].append(time_loop(world, dev, E, steps, f, end_every) * 1e3)
+        res["results"].append({"envs": E, "ms_per_loop_step": ms, "mean": {f: float(np.mean(v)) for f, v in ms.items()}})
+    return res
+
+
+def run(envs, steps, episode_steps=150.0, dev=None, device_goal=False):
+    """-> the result record (also what bench.py reports under secondary["navloop_gpu_side"])."""
+    a = types.SimpleNamespace(envs=envs, steps=steps, episode_steps=episode_steps)
+    dev = dev if dev is not None else torch.device("cuda", 0)
+    world = setup(dev)
     res = {"metric": "nav-loop env-steps (policy act + VO + goal update; simulator excluded)", "unit": "env-steps/s",
            "frame": f"{W}x{H}", "dtype": "f32", "results": []}
     if device_goal:
         res["goal_update"] = "device (GoalTracker; deltas stay on the GPU)"
     for E in a.envs:
-        goals = [np.array([0.0, 0.0, -5.0]) for _ in range(E)]           # goal in the agent frame (x, y, z)
-        tracker = None
-        if device_goal:                     # the same start: agents at the origin, looking down -z (the pose is not logged here)
-            tracker = geometry.GoalTracker(E, dev, track_pose=False)
-            tracker.reset(range(E), np.stack(goals), np.zeros((E, 3)), np.tile([0.0, 0.0, 0.0, 1.0], (E, 1)))
-        hid = torch.zeros(pol.num_recurrent_layers, E, 512, device=dev)
-        prev_a = torch.zeros(E, 1, dtype=torch.long, device=dev)
-        masks = torch.ones(E, 1, device=dev)
-        prev_obs = [frames[e % 96] for e in range(E)]
-        env_ids = list(range(E)) if os.environ.get("PNVO_NAVLOOP_RING", "1") != "0" else None
-        ring_depth = os.environ.get("PNVO_NAVLOOP_RING_DEPTH", "1") != "0"
-
-        phases = os.environ.get("PNVO_NAVLOOP_PHASES") is not None      # developer: host-synchronised time of each part (slower loop)
-        ph = {"policy input (stack + H2D)": 0.0, "policy.act": 0.0, "actions to host": 0.0, "VO boundary call": 0.0, "goal update": 0.0}
-
-        def mark(name, t_prev):
-            if not phases:
-                return t_prev
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            ph[name] += now - t_prev
-            return now
-
-        def step(s):
-            nonlocal hid, prev_a, prev_obs
-            tp = time.perf_counter()
-            if env_ids is not None and ring_depth:       # the policy's depth = the frames the last VO call left in the device ring
-                depth = t.ring_depth(prev_obs, env_ids)
-            else:
-                depth = torch.from_numpy(np.stack([o["depth"] for o in prev_obs])).to(dev, non_blocking=True)
-            if tracker is not None:
-                obs = {"depth": depth, "pointgoal_with_gps_compass": tracker.polar}
-            else:
-                polar = geometry.compute_goal_pos_batch(np.stack(goals), np.zeros((E, 3)))["polar"]
-                obs = {"depth": depth, "pointgoal_with_gps_compass": torch.from_numpy(polar).to(dev)}
-            tp = mark("policy input (stack + H2D)", tp)
-            _, act, _, hid = pol.act(obs, hid, prev_a, masks, deterministic=False)
-            tp = mark("policy.act", tp)
-            acts = (act.view(-1).cpu().numpy() % 3 + 1).tolist()          # STOP never ends a synthetic episode here
-            tp = mark("actions to host", tp)
-            cur_obs = [frames[(e + s + 1) % 96] for e in range(E)]
-            deltas = t.compute_local_delta_states_batch(prev_obs, cur_obs, acts, env_ids=env_ids,   # prev_obs IS last step's cur_obs: frame ring
-                                                        to_host=tracker is None)
-            tp = mark("VO boundary call", tp)
-            if tracker is not None:
-                tracker.update(deltas)
-            else:
-                goals[:] = list(geometry.compute_goal_pos_batch(np.stack(goals), deltas)["cartesian"])
-            prev_a = torch.as_tensor(acts, device=dev).view(E, 1)
-            prev_obs = cur_obs
-            mark("goal update", tp)
-
-        for s in range(12):                 # (every action model, the policy and their small-batch kernels have run before the clock starts)
-            step(s)
-        torch.cuda.synchronize()
-        for k in ph:
-            ph[k] = 0.0
-        t0 = time.perf_counter()
-        for s in range(a.steps):
-            step(s)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / a.steps
-        t.check_deferred()
-        if phases:
-            print(f"[navloop] {E} envs, ms per loop step by phase (host-synchronised):",
-                  {k: round(1e3 * v / a.steps, 3) for k, v in ph.items()}, file=sys.stderr)
+        dt = time_loop(world, dev, E, a.steps, "device" if device_goal else "host")
         res["results"].append({"envs": E, "ms_per_loop_step": dt * 1e3, "env_steps_per_s": E / dt,
                                "gpu_side_minutes_for_994_episodes": 994 * a.episode_steps / (E / dt) / 60.0})
     res["note"] = (f"extrapolation assumes {a.episode_steps:.0f} steps per episode on one GPU; the reference's 4.5 h includes "
